@@ -5,7 +5,7 @@ bytes on the host" -- seeds, AES-CTR masks, interpreter, BLAKE3 commitments, Fia
 device-to-host copy of the proof (what the reference's bench_prover times around Proof::new,
 /root/reference/src/proof/mod.rs:346-353, plus the PCIe leg a GPU prover has to pay).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (config.workload): BASELINE configs[3] — the synthetic 10^7-gate layered random AND/XOR GF(2) circuit of
@@ -15,7 +15,12 @@ metric (and the north-star 10^9 AND/s target) is quoted on.  One step = one comp
 the 256 repetitions are split N ways (strong scaling of ONE proof), one RCCL all-gather of digests per proof, and the
 step ends with the assembled proof bytes on rank 0's host.
 
-Next to `value` the line carries, all outside the timed region and each with its own parity flag: `device_resident`
+A plain run sets up, warms up, times the K steps, checks that the last timed proof verifies (strict; `value` is 0 when it does
+not), writes that proof with --dump-outputs DIR and prints the headline line.
+
+With --full the timed steps carry HIP events around the interpreter's phase, and the line also carries `roofline` (phase times, the
+kernel alone, the committed profiles' counters), `first_proof`, `shard_ms` and, all outside the timed region and each with its own
+parity flag: `device_resident`
 (round 1's headline: the same proof left in HBM), `prove_batch_host` (rv_prove_batch, host to host), `all_and`
 (the 10^7-AND variant), `secondary` (AES-128 / SHA-256 Bristol circuits, single proof and 64 / 256 proofs per call;
 the 10^6-MUL Z64 circuit), `streaming` (the bounded-memory prover), `verifier`, and `cpu_baseline` (the CPU oracle,
@@ -42,6 +47,25 @@ PROFILE_TAG = "r06"    # profiles/<tag>_pmc_traffic.json feeds roofline.traffic
 def rule_seeds():
     rng = np.random.default_rng(0x5EED)
     return rng.integers(0, 256, (256, 16), dtype=np.uint8)
+
+
+DUMP_SAMPLE = 8 << 20  # proof bytes --dump-outputs writes one by one (32 MB as float32)
+
+
+def dump_outputs(d, proof: bytes):
+    """--dump-outputs: the proof bytes a step hands its caller, one float32 per byte (a changed byte differs by at least 1).
+    proof_bytes.npy: every byte of a proof up to DUMP_SAMPLE bytes, else the bytes at a fixed seeded sample of DUMP_SAMPLE positions;
+    proof_sha256_per_mib.npy: the SHA-256 of every MiB of the proof ([MiBs, 32]), which sees a change anywhere; proof_len.npy."""
+    import hashlib
+
+    os.makedirs(d, exist_ok=True)
+    a = np.frombuffer(proof, np.uint8)
+    pos = np.sort(np.random.default_rng(0xD0).integers(0, a.size, DUMP_SAMPLE)) if a.size > DUMP_SAMPLE else slice(None)
+    np.save(os.path.join(d, "proof_bytes.npy"), a[pos].astype(np.float32))
+    mib = 1 << 20
+    dig = [np.frombuffer(hashlib.sha256(proof[i:i + mib]).digest(), np.uint8) for i in range(0, len(proof), mib)]
+    np.save(os.path.join(d, "proof_sha256_per_mib.npy"), np.array(dig, np.float32).reshape(-1, 32))
+    np.save(os.path.join(d, "proof_len.npy"), np.array([len(proof)], np.float64))
 
 
 def host_info():
@@ -353,13 +377,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--layers", type=int, default=153, help="circuit depth (153 = the BASELINE workload)")
     ap.add_argument("--p-and", type=float, default=0.5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: roofline and phase figures, first proof, verifier, shard times, device-resident, "
+                         "batch, all-AND, secondary and streaming records, the CPU baseline and the byte comparisons with it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed proof to DIR/*.npy (float32 bytes: a fixed seeded sample and a SHA-256 per MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) no CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="only the timed configuration (rocprofv3 runs whose summary should contain nothing else)")
+                    help="(with --full) only the timed configuration (rocprofv3 runs whose summary should contain nothing else)")
     ap.add_argument("--profile-run", action="store_true",
-                    help="only the timed proofs and the parity check (tools/profile_round.sh: the kernel counts of a profiled run must "
+                    help="only the timed proofs, no verification (tools/profile_round.sh: the kernel counts of a profiled run must "
                          "be those of warmup + steps proofs)")
-    ap.add_argument("--quick", action="store_true", help="fewer repetitions in the secondary records, Z64 at 10^5 MUL")
+    ap.add_argument("--quick", action="store_true", help="(with --full) fewer repetitions in the secondary records, Z64 at 10^5 MUL")
     ap.add_argument("--device-resident", action="store_true",
                     help="time rv_prove_device (openings left in HBM: round 1's headline) instead of the host-to-host rv_prove")
     ap.add_argument("--no-two-in-flight", action="store_true", help="(accepted for old command lines; implied by --no-secondary)")
@@ -413,6 +442,7 @@ def main():
     hp = HostProver(circuit, wit, [], seeds)
     dev_buf = torch.empty(max(sum(backend.single_shard_sizes()), 1), dtype=torch.uint8, device="cuda")
     last_bytes = [None]
+    last_dev = [None]  # (--device-resident: (comm, omit, lens) of the last step, its openings in dev_buf)
 
     # N > 1: the library's own communicator (rv_comm_* / rv_prove_sharded: RCCL all-gather on the library's stream,
     # openings to rank 0 by ncclSend/ncclRecv, one D2H).  If it cannot be set up, or its first proof fails, on ANY rank,
@@ -449,7 +479,7 @@ def main():
                 comm, bufs, all_lens = out
                 last_bytes[0] = assemble_device_parts(comm, bufs, all_lens)
         elif args.device_resident:
-            backend.prove_device(wit, [], seeds, dev_buf)
+            last_dev[0] = backend.prove_device(wit, [], seeds, dev_buf)
         else:
             p, n = hp.prove()
             if last_bytes[0] is not None:
@@ -461,8 +491,10 @@ def main():
     # HIP events around the dominant phase (the interpreter's: generator || levels) of every timed step; the other phases are timed on
     # PHASE_PASS proofs right behind the timed region -- every event in the stream costs a proof ~5 us of idle GPU, and seven of them
     # per step were 0.5 % of the headline spent on its own measurement
+    # per-phase events only for --full's roofline: a plain run times the proofs alone
     interp_only = world == 1 and not args.device_resident and not args.profile_run  # (a profiled run makes exactly warmup + steps proofs: its summaries divide by that)
-    L.rv_ctx_profile(ctx.handle, 2 if interp_only else 1, 1, None)
+    if args.full:
+        L.rv_ctx_profile(ctx.handle, 2 if interp_only else 1, 1, None)
     sync_all()
     t0 = time.perf_counter()
     step_marks = []
@@ -474,11 +506,18 @@ def main():
     if os.environ.get("RV_BENCH_STEP_TIMES") and rank == 0:  # (diagnostic: the K steps one by one; the timed region is unchanged)
         prev = [t0] + step_marks[:-1]
         print("step ms: " + " ".join("%.3f" % ((b - a) * 1e3) for a, b in zip(prev, step_marks)), file=sys.stderr)
+    if args.dump_outputs and rank == 0:  # (before --full's extra proofs: the last TIMED step's proof)
+        if args.device_resident:
+            comm, _, lens = last_dev[0]
+            dump_outputs(args.dump_outputs, assemble_device_parts(comm, [dev_buf], [lens]))
+        else:
+            dump_outputs(args.dump_outputs, C.string_at(*last_bytes[0]) if isinstance(last_bytes[0], tuple) else last_bytes[0])
     prof = _lib.Profile()
-    L.rv_ctx_profile(ctx.handle, 0, 0, C.byref(prof))
+    if args.full:
+        L.rv_ctx_profile(ctx.handle, 0, 0, C.byref(prof))
     PHASE_PASS = 10
     prof_all = None
-    if interp_only and rank == 0:
+    if args.full and interp_only and rank == 0:
         L.rv_ctx_profile(ctx.handle, 1, 1, None)
         for _ in range(PHASE_PASS):
             step()
@@ -496,6 +535,24 @@ def main():
 
     result = None
     if rank == 0:
+        boundary = (("rv_prove_sharded (library communicator: RCCL all-gather of digests on the library's stream, ncclSend/ncclRecv of "
+                     "the openings); rank 0 ends with bincode(Proof) bytes in host memory" if lib_comm is not None else
+                     "sharded rv_shard_* + torch.distributed all-gather; rank 0 ends with bincode(Proof) bytes in host memory"
+                     + (f" [{comm_note}]" if comm_note else "")) if world > 1 else
+                    "rv_prove_device: openings left in HBM (NOT the SURVEY 8(d) boundary)" if args.device_resident else
+                    "rv_prove: witness bytes on the host -> bincode(Proof) bytes on the host (page-locked), D2H of the proof included")
+        result = {
+            "metric": "prover AND-gates/sec on GF(2) Bristol circuit; 1/2/4/8-GPU; proof bit-exact",
+            "value": n_and * args.steps / dt, "unit": "AND gates/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+            "config": {"workload": f"synthetic layered AND/XOR GF(2) circuit, {st['gates']} gates ({st['and']} AND), "
+                                   f"{st['inputs']} inputs, {args.layers} layers x 65536, p_and={args.p_and}, 256 reps x 8 players, 40 online",
+                       "boundary": boundary, "parallelism": f"reps/{world}", "levels": info["levels"], "compile_s": compile_s,
+                       "compile_hint": "RV_COMPILE_WHOLE_PROVER" if world == 1 else "none",
+                       "gate_stream_upload_ms": info["upload_us"] / 1e3, "gate_stream_bytes": info["device_bytes"]},
+        }
+    if rank == 0 and args.full:
         phases = {n: prof.ms[i] / max(args.steps, 1) for i, n in enumerate(_lib.PHASES)}
         launches = {n: int(prof.launches[i] // max(args.steps, 1)) for i, n in enumerate(_lib.PHASES)}
         if prof_all is not None:
@@ -668,24 +725,7 @@ def main():
                 # (kept at the top level for the tools that read them)
                 for k in ("kernel_alone", "concurrent", "early_corrections", "launches_per_proof", "avg_launch_us", "algorithmic_bytes_per_proof"):
                     roofline[k] = hbm_view.get(k)
-        boundary = (("rv_prove_sharded (library communicator: RCCL all-gather of digests on the library's stream, ncclSend/ncclRecv of "
-                     "the openings); rank 0 ends with bincode(Proof) bytes in host memory" if lib_comm is not None else
-                     "sharded rv_shard_* + torch.distributed all-gather; rank 0 ends with bincode(Proof) bytes in host memory"
-                     + (f" [{comm_note}]" if comm_note else "")) if world > 1 else
-                    "rv_prove_device: openings left in HBM (NOT the SURVEY 8(d) boundary)" if args.device_resident else
-                    "rv_prove: witness bytes on the host -> bincode(Proof) bytes on the host (page-locked), D2H of the proof included")
-        result = {
-            "metric": "prover AND-gates/sec on GF(2) Bristol circuit; 1/2/4/8-GPU; proof bit-exact",
-            "value": n_and * args.steps / dt, "unit": "AND gates/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-            "config": {"workload": f"synthetic layered AND/XOR GF(2) circuit, {st['gates']} gates ({st['and']} AND), "
-                                   f"{st['inputs']} inputs, {args.layers} layers x 65536, p_and={args.p_and}, 256 reps x 8 players, 40 online",
-                       "boundary": boundary, "parallelism": f"reps/{world}", "levels": info["levels"], "compile_s": compile_s,
-                       "compile_hint": "RV_COMPILE_WHOLE_PROVER" if world == 1 else "none",
-                       "gate_stream_upload_ms": info["upload_us"] / 1e3, "gate_stream_bytes": info["device_bytes"]},
-            "roofline": roofline,
-        }
+        result["roofline"] = roofline
 
     # ---- parity gate and the secondary records, outside the timed region (rank 0; the other ranks wait at the barrier)
     if rank == 0:
@@ -695,11 +735,11 @@ def main():
             last = reverie_amd.Proof(last_bytes[0])
         # (a profiled run verifies nothing: its kernel summaries are divided by the number of proofs it makes)
         parity = {"last_timed_proof_verifies_strict": None if args.profile_run else bool(last.verify(circuit)), "proof_bytes": len(last)}
-        if world > 1:
+        if world > 1 and args.full:
             single = reverie_amd.Proof.new(circuit, wit, [], seeds=seeds)
             parity["sharded_proof_equals_single_gpu_proof"] = bytes(single) == bytes(last)
         result["parity"] = parity
-        if world == 1 and not args.profile_run:
+        if args.full and world == 1 and not args.profile_run:
             # the first proof of a circuit the library has not seen: rv_prove_ops from the raw op list (the reference's
             # Proof::new walks the raw ops, proof/mod.rs:150-152) = compile on the host threads + upload + prove
             fp = []
@@ -737,7 +777,7 @@ def main():
                         "levelised by the parallel compiler (csrc/compile_par.cpp), uploaded and proved once, then released "
                         "(median of 3 on the warm context, RV_OPS_CACHE=0); rv_verify_ops likewise (one run); repeat_proof_ms = the same call on "
                         "the same op list once the context has seen it (content-addressed cache: hash + proof, the Python mirror's array checks included)"}
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             # verifier: rv_verify (strict) from host proof bytes, second call timed; the verifying party
             # compiles the circuit for itself (no prover hint)
             host_proof = reverie_amd.Proof.new(circuit, wit, [], seeds=seeds)
@@ -807,7 +847,7 @@ def main():
                                           "ms_per_proof_min_max": [min(d3s) / B * 1e3, max(d3s) / B * 1e3],
                                           "note": "rv_prove_batch: witness bytes on the host -> B proofs' bytes on the host, one call (median of 12 calls after two warm-ups; worker streams on hardware queues of their own, csrc/batch.inc)"}
             del proofs
-    if world > 1:
+    if world > 1 and args.full:
         # informational, outside the timed region: the same N GPUs proving N INDEPENDENT statements, one whole proof
         # (256 repetitions) per rank and no collective -- weak scaling, what a proving service with a queue of
         # statements would run.  `value` above stays the north-star's sharded single proof (strong scaling).
@@ -823,7 +863,7 @@ def main():
             result["independent_proofs"] = {"value": n_and * n_ind * world / float(ti.item()), "unit": "AND gates/s", "scaling": "weak",
                                             "ms_per_proof_per_gpu": float(ti.item()) / n_ind * 1e3, "proofs": n_ind * world,
                                             "note": "one whole rv_prove (host to host) per GPU at a time, no collective"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         what = f"the whole timed workload ({st['gates']} gates, {st['and']} AND), same seeds"
         base, cproof = cpu_baseline(prog, wit, [], wc, seeds, st["and"], "AND gates/s", what, runs=5)
         result["cpu_baseline"] = base
@@ -831,7 +871,7 @@ def main():
         # proof, byte for byte
         result["parity"]["timed_proof_bit_exact_vs_cpu"] = bytes(last) == cproof
         del cproof
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         # the all-AND variant (the north-star's "10^7-gate" phrasing read as 10^7 AND gates)
         circuit.close()
         aprog, awit, awc, ast = circuits.layered_gf2(layers=args.layers, p_and=1.0)

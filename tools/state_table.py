@@ -2,7 +2,7 @@
 """The "current state" table of README.md / DESIGN.md section 9 from a bench.py record -- so the documents quote a run, not a memory.
 
 usage: python tools/state_table.py BENCH_rNN.json            (a driver record: its "parsed" object is the bench line)
-       python tools/state_table.py gpurun_out/bench_x.json   (bench.py's own JSON line)
+       python tools/state_table.py bench_x.json              (the JSON line of `bench.py --full`)
 Prints a markdown table; --update rewrites the block between the STATE-TABLE markers of README.md and DESIGN.md in place."""
 import json
 import os
