@@ -226,7 +226,9 @@ int rv_prove_device(rv_ctx *ctx, const rv_circuit *c, const uint8_t *wit_gf2, si
  * proofs[b] / proof_lens[b] as rv_prove (rv_free each, exactly once).  The proofs of a call are slices of one
  * page-locked buffer that goes back to the library's pool when the last of them has been freed (RV_BATCH_COPY_OUT=1:
  * separately malloc'ed buffers, small-circuit path only).  Each proof is byte-identical to what rv_prove returns for
- * the same witness and seeds.  Mixed / Z64 circuits fall back to one rv_prove per proof. */
+ * the same witness and seeds.  Z64 and mixed circuits below 2^20 gates (GF(2) and Z64 gates counted together) take the
+ * one-pass path as well, their Z64 levels through k_interp64_b, in chunks of what fits in device memory; larger Z64 / mixed
+ * circuits prove one rv_prove per proof. */
 int rv_prove_batch(rv_ctx *ctx, const rv_circuit *c, size_t batch, const uint8_t *wit_gf2, size_t n_gf2,
                    const uint64_t *wit_z64, size_t n_z64, const uint8_t *seeds, uint8_t **proofs, size_t *proof_lens);
 
@@ -428,8 +430,8 @@ int rv_verify_shard_ex(rv_ctx *ctx, const rv_circuit *c, const uint8_t *proof, s
 int rv_verify_finish_ex(const uint8_t *proof, size_t proof_len, const uint8_t *slot_digests /* 256 x 32 */, uint32_t flags,
                         int zero_checks_ok, int *ok);
 
-/* Many proofs of one circuit in one pass (the verifier's counterpart of rv_prove_batch; pure GF(2) circuits below the
- * large-circuit threshold -- everything else verifies proof after proof): ok[b] as rv_verify_ex would set it for
+/* Many proofs of one circuit in one pass (the verifier's counterpart of rv_prove_batch; GF(2), Z64 and mixed circuits below
+ * the large-circuit threshold -- larger ones verify proof after proof): ok[b] as rv_verify_ex would set it for
  * proofs[b] with the same flags.  A proof whose bytes cannot be parsed (or whose records rv_verify_ex would answer with
  * RV_E_PROOF_MALFORMED) is a REJECTED proof, ok[b] = 0, and the others are verified all the same; a non-zero return
  * code means an argument or device error. */

@@ -516,51 +516,17 @@ void launch_bitslice_rk(hipStream_t st, const uint8_t* d_rkbytes, uint32_t NQ, u
 // 128 bit-planes of a lane are transposed back to two little-endian u64 per (rep, player)
 // slot.  masks64[(2j+h)*S + slot] with S = NQ*32 slots, slot = rep*8 + player.
 template <int QW>
+struct B_k_aes_z64_masks {
+    __device__ __forceinline__ void operator()(const uint32_t* __restrict__ rk, const uint32_t* __restrict__ keep, uint32_t NQ, uint64_t first_block,
+                                               uint64_t n_blocks, uint32_t blocks_per_wg, uint64_t* __restrict__ masks64) const {
+#include "aes_z64_masks.inc"
+}
+};
+template <int QW>
 __global__ __launch_bounds__(512, 2) void k_aes_z64_masks(const uint32_t* __restrict__ rk, const uint32_t* __restrict__ keep,
                                                        uint32_t NQ, uint64_t first_block, uint64_t n_blocks, uint32_t blocks_per_wg,
                                                        uint64_t* __restrict__ masks64) {
-    __shared__ uint32_t lds_rk[11 * 128 * QW];
-    constexpr uint32_t JW = 64 / QW;
-    const uint32_t n_qg = NQ / QW;
-    const uint32_t qg = blockIdx.x % n_qg;
-    const uint64_t chunk = blockIdx.x / n_qg;
-    stage_round_keys<QW>(rk, NQ, qg, lds_rk);
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t ql = lane % QW, jsub = lane / QW;
-    const uint32_t q = qg * QW + ql;
-    const uint32_t kp = keep ? keep[q] : 0xFFFFFFFFu;
-    const uint32_t* rkl = lds_rk + ql;
-    const uint64_t S = (uint64_t)NQ * 32;
-    const uint64_t j_lo = chunk * blocks_per_wg;
-    const uint64_t j_hi = (j_lo + blocks_per_wg < n_blocks) ? j_lo + blocks_per_wg : n_blocks;
-    for (uint64_t jb = j_lo + (uint64_t)wave * JW; jb < j_hi; jb += 8 * JW) {
-        const uint64_t j = jb + jsub;  // block inside this launch: its output slot; CTR index first_block + j
-        if (j >= j_hi) continue;
-        uint32_t s[128], t[128];
-        rounds_0_to_9<QW>(first_block + j, s, t, rkl);
-        sub_shift(s, t);
-        const uint32_t* rk10 = rkl + 10 * 128 * QW;
-#pragma unroll
-        for (int i = 0; i < 128; i++) t[i] ^= rk10[i * QW];
-        // plane 8*i + k = bit k of keystream byte i; u64 h, bit b  <->  plane 64*h + b
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            uint32_t lo[32], hi[32];
-#pragma unroll
-            for (int k = 0; k < 32; k++) {
-                lo[k] = t[64 * h + 31 - k];
-                hi[k] = t[64 * h + 32 + 31 - k];
-            }
-            transpose32(lo);
-            transpose32(hi);
-            uint64_t* out = masks64 + (2 * j + h) * S + (uint64_t)q * 32;
-#pragma unroll
-            for (int sl = 0; sl < 32; sl++) {
-                const uint32_t on = (uint32_t)0 - ((kp >> (31 - sl)) & 1u);  // omitted player's stream stays zero
-                out[sl] = ((uint64_t)(hi[sl] & on) << 32) | (lo[sl] & on);
-            }
-        }
-    }
+#include "aes_z64_masks.inc"
 }
 
 template <int QW>
@@ -605,11 +571,14 @@ static void launch_z64_qw(hipStream_t st, const uint32_t* d_rk, const uint32_t* 
                           uint64_t* d_masks64) {
     const uint32_t n_qg = NQ / QW;
     constexpr uint32_t JW = 64 / QW;
-    uint64_t per = (n_blocks * n_qg + 511) / 512;
+    // recorded for a batch of proofs: a proof's share of the 512 workgroups is its 1/batch, at least one per quad group (each
+    // workgroup stages 88 KiB of round keys before its first block; launch_masks_qw does the same for the GF(2) generator)
+    const uint64_t wgs = g_recorder ? std::max<uint64_t>(n_qg, 512 / std::max(g_recorder->batch, 1u)) : 512;
+    uint64_t per = (n_blocks * n_qg + wgs - 1) / wgs;
     per = ((per + 8 * JW - 1) / (8 * JW)) * (8 * JW);
     const uint64_t chunks = (n_blocks + per - 1) / per;
-    hipLaunchKernelGGL(k_aes_z64_masks<QW>, dim3((unsigned)(chunks * n_qg)), dim3(512), 0, st, d_rk, d_keep, NQ, first_block, n_blocks,
-                       (uint32_t)per, d_masks64);
+    launch<B_k_aes_z64_masks<QW>, 512>(k_aes_z64_masks<QW>, st, dim3((unsigned)(chunks * n_qg)), dim3(512), d_rk, d_keep, NQ, first_block, n_blocks,
+                                       (uint32_t)per, d_masks64);
 }
 
 void launch_aes_z64_masks(hipStream_t st, const uint32_t* d_rk, const uint32_t* d_keep, uint32_t NQ, uint64_t n_blocks,

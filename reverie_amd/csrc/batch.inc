@@ -20,7 +20,7 @@ static int replay_recorded(rv_ctx* ctx, std::vector<LaunchRecorder>& recs, std::
         const auto& c0 = recs[0].calls[i];
         for (size_t b = 1; b < batch; b++) {
             const auto& c = recs[b].calls[i];
-            if (c.replay != c0.replay || c.grid.x != c0.grid.x || c.block.x != c0.block.x || c.arg_bytes != c0.arg_bytes) return RV_E_DEVICE;
+            if (c.replay != c0.replay || c.fill != c0.fill || c.grid.x != c0.grid.x || c.block.x != c0.block.x || c.arg_bytes != c0.arg_bytes) return RV_E_DEVICE;
         }
         if (!c0.replay) continue;
         if (c0.grid.y != 1 || c0.grid.z != 1) return RV_E_DEVICE;
@@ -49,7 +49,8 @@ static int replay_recorded(rv_ctx* ctx, std::vector<LaunchRecorder>& recs, std::
         } else {
             for (size_t b = 0; b < batch; b++) {
                 const auto& c = recs[b].calls[i];
-                if (hipMemcpyAsync(c.dst, c.src, c.n, c.kind, ctx->stream) != hipSuccess) return RV_E_DEVICE;
+                if ((c.fill ? hipMemsetAsync(c.dst, c.value, c.n, ctx->stream) : hipMemcpyAsync(c.dst, c.src, c.n, c.kind, ctx->stream)) != hipSuccess)
+                    return RV_E_DEVICE;
             }
         }
     }
@@ -88,12 +89,39 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
         }
         return (int)RV_OK;
     };
-    if (batch == 1 || !cc.gates64.empty()) return one_by_one();
+    if (batch == 1) return one_by_one();
     HIPCHK(hipSetDevice(ctx->device));
     static const size_t big_gates = [] {
         const char* e = getenv("RV_BATCH_BIG_GATES");  // circuits from this many gates on take the two-proofs-in-flight path
         return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)1 << 20;
     }();
+    // Z64 / mixed circuits take the one-pass path below the same threshold (GF(2) and Z64 gates counted together); large ones
+    // prove one by one (the worker threads' path is GF(2)-only: its early corrections would need a 2 GB staging area per worker)
+    const bool has64 = !cc.gates64.empty();
+    if (has64 && cc.gates.size() + cc.gates64.size() >= big_gates) return one_by_one();
+    if (has64) {
+        // A pass keeps every proof's working set resident (wmask64 alone is 16 KB per Z64 wire): larger batches run as
+        // consecutive chunks of what fits in half of the free device memory (RV_BATCH_MAX caps a chunk), each with its own slab
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return RV_E_DEVICE;
+        uint8_t om[RV_TOTAL_REPS];
+        for (uint32_t r = 0; r < RV_TOTAL_REPS; r++) om[r] = r < RV_ONLINE_REPS ? 0 : RV_PLAYERS;
+        const size_t per_proof = cc.info.scratch_bytes + open_layout(cc, om, RV_TOTAL_REPS, true).total + cc.n_in + 8 * cc.n_in64 + 4096;
+        size_t chunk = std::min<size_t>(std::max<size_t>((free_b + ctx->cached_bytes) / 2 / per_proof, 2), 4096);
+        if (const char* e = getenv("RV_BATCH_MAX")) chunk = std::min<size_t>(chunk, (size_t)std::max(atoi(e), 1));
+        if (batch > chunk) {
+            for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+                const int rc = rv_prove_batch_impl(ctx, c, std::min(chunk, batch - b0), wit_gf2 ? wit_gf2 + b0 * n_gf2 : nullptr, n_gf2,
+                                                   wit_z64 ? wit_z64 + b0 * n_z64 : nullptr, n_z64, seeds + b0 * RV_TOTAL_REPS * 16, proofs + b0,
+                                                   proof_lens + b0);
+                if (rc) {
+                    for (size_t k = 0; k < b0; k++) rv_free(proofs[k]), proofs[k] = nullptr, proof_lens[k] = 0;
+                    return rc;
+                }
+            }
+            return RV_OK;
+        }
+    }
     if (cc.gates.size() >= big_gates) {
         // Large circuits fill the GPU on their own; what is left to gain is overlapping one proof's VALU-bound phases
         // (masks, digests) with another's memory-bound interpreter, and a third one's 50 MB trip over PCIe.  A few host
@@ -197,6 +225,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
     }
     std::vector<rv_shard*> sh(batch, nullptr);
     std::vector<InterpParams> pp(batch);
+    std::vector<Interp64Params> pp64(has64 ? batch : 0);
     InterpParams* d_pp = nullptr;
     int rc = RV_OK;
     uint8_t* staging = nullptr;
@@ -259,6 +288,15 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
         (cc.n_in && hipMemcpy2DAsync(d_wit_all + SLAB_HEAD, wit_stride, wit_gf2, n_gf2, cc.n_in, batch, hipMemcpyHostToDevice,
                                      ctx->stream) != hipSuccess))
         return cleanup(RV_E_DEVICE);
+    const size_t wit64_stride = (std::max<size_t>(cc.n_in64, 1) + 1) & ~(size_t)1;  // (u64 words)
+    uint64_t* d_wit64_all = nullptr;
+    if (has64) {
+        if ((rc = dalloc(ctx, SLAB_HEAD / 8 + batch * wit64_stride, &d_wit64_all))) return cleanup(rc);
+        device_tmp.push_back(d_wit64_all);
+        if (cc.n_in64 && hipMemcpy2DAsync(d_wit64_all + SLAB_HEAD / 8, wit64_stride * 8, wit_z64, n_z64 * 8, cc.n_in64 * 8, batch,
+                                          hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+            return cleanup(RV_E_DEVICE);
+    }
     for (size_t b = 0; b < batch && !rc; b++) {
         rv_shard* s = sh[b] = new rv_shard();
         s->ctx = ctx;
@@ -272,10 +310,17 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
         if ((rc = dalloc(ctx, (size_t)R * 128, &s->d_keys))) break;
         g_recorder = &recs[b];
         launch_expand_seeds(ctx->stream, s->d_seeds, R, s->d_keys);
+        // (a fresh shard's z64f is false, and rv_shard_commit never sets it under a recorder: k_z64_fused, whose mask generator
+        // and schedule are per proof, stays out of the batch; the Z64 masks come from the recorded k_aes_z64_masks, the levels
+        // from k_interp64_b)
         Interp64Params p64{};
         pp[b] = InterpParams{};
         pp[b].wit = s->d_wit;
         if (!(rc = shard_setup_prg(s, nullptr))) rc = shard_run_alloc(s, pp[b], p64);
+        if (has64) {
+            p64.wit = d_wit64_all + SLAB_HEAD / 8 + b * wit64_stride;
+            pp64[b] = p64;
+        }
         g_recorder = nullptr;
     }
     if (rc) return cleanup(rc);
@@ -287,25 +332,45 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
     ctx->phase(RV_PH_INTERP);
     if ((rc = dalloc(ctx, batch, &d_pp))) return cleanup(rc);
     if (hipMemcpyAsync(d_pp, pp.data(), batch * sizeof(InterpParams), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return cleanup(RV_E_DEVICE);
+    Interp64Params* d_pp64 = nullptr;
+    if (has64) {
+        if ((rc = dalloc(ctx, batch, &d_pp64))) return cleanup(rc);
+        device_tmp.push_back(d_pp64);
+        if (hipMemcpyAsync(d_pp64, pp64.data(), batch * sizeof(Interp64Params), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return cleanup(RV_E_DEVICE);
+    }
     {
+        // (the order of shard_run_levels: per level the GF(2) launch, then the Z64 one.  LDS and narrow runs cover levels
+        // without Z64 gates only -- rv_circuit's run plans -- so the levels they `continue` past have no Z64 launch to skip.
+        // Z64 / mixed circuits count one launch per batched launch, whatever the batch size)
         const size_t n_levels = cc.level_start.empty() ? 0 : cc.level_start.size() - 1;
         for (size_t l = 0; l < n_levels; l++) {
             if (lds_run_for_batch(c, l, batch)) {
                 const auto& pl = c->lds_runs[(size_t)c->lds_run_of_level[l]];
-                if (l == pl.run.l0)
+                if (l == pl.run.l0) {
                     launch_interp_lds(ctx->stream, MODE_PROVE, pl.qs, RV_TOTAL_REPS / 4, c->d_lds_recs + pl.run.rec0, pl.run.n_steps, pl.run.n_slots,
                                       pl.run.eo0, pl.run.ep0, InterpParams{}, d_pp, (uint32_t)batch);
+                    if (has64) ctx->count();
+                }
                 continue;
             }
             if (c->run_of_level[l] >= 0) {
                 const auto& run = c->narrow_runs[(size_t)c->run_of_level[l]];
-                if (l == run.first)
+                if (l == run.first) {
                     launch_interp_narrow_batched(ctx->stream, c->d_gates, c->d_level_range, run.first, run.second, run.tiny, d_pp, (uint32_t)batch);
+                    if (has64) ctx->count();
+                }
                 continue;
             }
             launch_interp_batched(ctx->stream, c->d_gates, cc.level_range[l], d_pp, (uint32_t)batch);
+            if (has64 && cc.level_start[l + 1] > cc.level_start[l]) ctx->count();
+            if (has64 && cc.level_start64[l + 1] > cc.level_start64[l]) {
+                launch_interp64_batched(ctx->stream, MODE_PROVE, c->d_gates64, cc.level_start64[l], cc.level_start64[l + 1], d_pp64, (uint32_t)batch);
+                ctx->count();
+            }
         }
     }
+    // (the digests' recording below counts its launches too: the interpreter's phase ends here)
+    if (has64) ctx->phase(-1);
     mark("interpreter launches");
     // ---- per proof: digests, commitment + challenge + openings on the device, proof bytes to the host
     size_t slot = 0;

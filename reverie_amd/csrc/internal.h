@@ -216,6 +216,8 @@ void launch_interp_lds(hipStream_t st, int mode, uint32_t QS, uint32_t NQ, const
 void launch_interp_narrow_batched(hipStream_t st, const Gate* d_gates, const LevelRange* d_level_range, uint32_t l0, uint32_t l1,
                                   int tiny, const InterpParams* d_pp, uint32_t batch, int mode = MODE_PROVE);
 void launch_interp64(hipStream_t st, int mode, const Gate64* d_gates, uint32_t lo, uint32_t hi, const Interp64Params& p);
+// rv_prove_batch / rv_verify_batch: one level for `batch` whole proofs, proof b's buffers in d_pp[b] (k_interp64_b, gridDim.y = proof)
+void launch_interp64_batched(hipStream_t st, int mode, const Gate64* d_gates, uint32_t lo, uint32_t hi, const Interp64Params* d_pp, uint32_t batch);
 // Z64 masks: masks64[m][slot] = LE64(keystream[slot][8m..8m+8)), blocks [first, first+n_blocks) -> masks 2*first..
 void launch_aes_z64_masks(hipStream_t st, const uint32_t* d_rk, const uint32_t* d_keep, uint32_t NQ, uint64_t n_blocks,
                           uint64_t* d_masks64, uint64_t first_block = 0);

@@ -62,11 +62,13 @@ struct LaunchRecorder {
         void (*replay)(hipStream_t, dim3, dim3, const void*, unsigned) = nullptr;
         dim3 grid, block;
         uint32_t arg_bytes = 0;
-        // replay == nullptr: an asynchronous copy, replayed as it is
+        // replay == nullptr: an asynchronous copy (or, with `fill` set, a memset of n bytes to `value`), replayed as it is
         void* dst = nullptr;
         const void* src = nullptr;
         size_t n = 0;
         hipMemcpyKind kind = hipMemcpyDefault;
+        bool fill = false;
+        int value = 0;
         std::vector<uint8_t> args;
     };
     std::vector<Call> calls;
@@ -110,6 +112,20 @@ inline hipError_t memcpy_async(void* dst, const void* src, size_t n, hipMemcpyKi
         return hipSuccess;
     }
     return hipMemcpyAsync(dst, src, n, kind, st);
+}
+
+// hipMemsetAsync, or its place in the recorded sequence (a clear queued at record time would run before every replayed step)
+inline hipError_t memset_async(void* dst, int value, size_t n, hipStream_t st) {
+    if (LaunchRecorder* r = g_recorder) {
+        LaunchRecorder::Call c;
+        c.dst = dst;
+        c.n = n;
+        c.fill = true;
+        c.value = value;
+        r->calls.push_back(std::move(c));
+        return hipSuccess;
+    }
+    return hipMemsetAsync(dst, value, n, st);
 }
 
 }  // namespace rv

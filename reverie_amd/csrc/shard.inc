@@ -333,14 +333,14 @@ static int shard_run_alloc(rv_shard* s, InterpParams& p, Interp64Params& p64) {
         if ((rc = dalloc(ctx, (size_t)cc.n_ssa64 * s->R * 8, &s->d_wmask64))) return rc;
         if (s->z64f && !s->d_keys64) {  // (the fused PROVER: cleartext values; the verifier keeps per-repetition corrections)
             if ((rc = dalloc(ctx, (size_t)cc.n_ssa64, &s->d_v64))) return rc;
-            HIPCHK(hipMemsetAsync(s->d_v64, 0, 8, ctx->stream));  // (SSA id 0 = the zero wire)
+            HIPCHK(hipMemsetAsync(s->d_v64, 0, 8, ctx->stream));  // (SSA id 0 = the zero wire; the fused path is never recorded)
         } else {
             if ((rc = dalloc(ctx, (size_t)cc.n_ssa64 * s->R, &s->d_wcorr64))) return rc;
-            HIPCHK(hipMemsetAsync(s->d_wcorr64, 0, (size_t)s->R * 8, ctx->stream));
+            HIPCHK(rv::memset_async(s->d_wcorr64, 0, (size_t)s->R * 8, ctx->stream));  // (recorded by rv_prove_batch / rv_verify_batch)
         }
         if ((rc = dalloc(ctx, (size_t)std::max<uint64_t>(cc.on_words64, 1) * s->R, &s->d_on64))) return rc;
         if ((rc = dalloc(ctx, (size_t)std::max<uint64_t>(cc.pre_words64, 1) * s->R, &s->d_pre64))) return rc;
-        HIPCHK(hipMemsetAsync(s->d_wmask64, 0, (size_t)s->R * 64, ctx->stream));
+        HIPCHK(rv::memset_async(s->d_wmask64, 0, (size_t)s->R * 64, ctx->stream));
     }
     hipStream_t sb = ctx->stream;
     // error flag and the zero row (first computed row: mask 0, corr 0), one launch

@@ -2,8 +2,8 @@
 
 // ------------------------------------------------------------------------------------
 // rv_verify_batch: many proofs of one circuit in one pass -- the verifier's counterpart of rv_prove_batch's fused path
-// (pure GF(2) circuits below the large-circuit threshold; everything else verifies proof after proof).  Per proof the
-// host only parses the bincode framing and fills its slot of ONE page-locked staging slab (seeds, omitted players,
+// (circuits below the large-circuit threshold, GF(2) and Z64 gates counted together; larger ones verify proof after
+// proof).  Per proof the host only parses the bincode framing and fills its slot of ONE page-locked staging slab (seeds, omitted players,
 // masks, opened keys, carried-over commitments, source offsets and the proof bytes themselves), which goes to the
 // device in one copy; the per-proof kernel strings are recorded and replayed once per batch (launch.h), the levels run
 // through the batched interpreter kernels in verify mode, and the slot digests plus the zero-check flags come back in
@@ -35,7 +35,8 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         const char* e = getenv("RV_BATCH_BIG_GATES");
         return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)1 << 20;
     }();
-    if (batch == 1 || !cc.gates64.empty() || cc.gates.size() >= big_gates) return one_by_one();
+    if (batch == 1 || cc.gates.size() + cc.gates64.size() >= big_gates) return one_by_one();
+    const bool has64 = !cc.gates64.empty();
     // ---- parse; proofs with the wrong repetition counts are `false` (proof/mod.rs:225-230) and take no further part
     std::vector<Parsed> P(batch);
     std::vector<size_t> live;  // indices of the proofs that go to the GPU
@@ -74,7 +75,8 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
     {  // a pass keeps one proof's working set resident per proof: larger batches run as consecutive chunks
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return RV_E_DEVICE;
-        const size_t per_proof = std::max<size_t>(cc.info.scratch_bytes + 3 * (size_t)std::max<uint64_t>({cc.n_in, cc.n_pre, cc.n_rec, 1}) * 256, 1);
+        size_t per_proof = std::max<size_t>(cc.info.scratch_bytes + 3 * (size_t)std::max<uint64_t>({cc.n_in, cc.n_pre, cc.n_rec, 1}) * 256, 1);
+        if (has64) per_proof += 3 * (size_t)std::max<uint64_t>({cc.n_in64, cc.n_corr64, cc.n_rec64, 1}) * 64 * 8 + (size_t)RV_TOTAL_REPS * 128;
         size_t chunk = std::min<size_t>(std::max<size_t>((free_b + ctx->cached_bytes) / 2 / per_proof, 2), 4096);
         if (const char* e = getenv("RV_BATCH_MAX")) chunk = std::min<size_t>(chunk, (size_t)std::max(atoi(e), 2));
         if (batch > chunk) {
@@ -89,7 +91,7 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
     const uint32_t R = RV_TOTAL_REPS, NQ = R / 4;
     // ---- the staging slab: one slot per proof
     struct Slot {
-        size_t seeds, omit, keep, onm, quads, hkeys, hco, hco64, src, proof, stride;
+        size_t seeds, omit, keep, onm, quads, hkeys, hco, hco64, src, seeds64, omit64, keep64, hkeys64, src64, proof, stride;
     } L{};
     {
         size_t o = 0;
@@ -107,6 +109,12 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         L.hco = take((size_t)R * 32);
         L.hco64 = take((size_t)R * 32);
         L.src = take((size_t)6 * R * 8);
+        // the Z64 side (empty for a pure GF(2) circuit): its own seeds, omitted players, kept streams, opened keys, source offsets
+        L.seeds64 = take(has64 ? (size_t)R * 16 : 0);
+        L.omit64 = take(has64 ? R : 0);
+        L.keep64 = take(has64 ? (size_t)NQ * 4 : 0);
+        L.hkeys64 = take(has64 ? (size_t)R * 128 : 0);
+        L.src64 = take(has64 ? (size_t)6 * R * 8 : 0);
         L.proof = take(max_len);
         L.stride = o;
     }
@@ -155,6 +163,13 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         uint32_t* onm = (uint32_t*)(h + L.onm);
         for (uint32_t q = 0; q < NQ; q++) keep[q] = 0xFFFFFFFFu;
         uint64_t* src = (uint64_t*)(h + L.src);
+        uint8_t* omit64 = h + L.omit64;
+        uint32_t* keep64 = (uint32_t*)(h + L.keep64);
+        uint64_t* src64 = (uint64_t*)(h + L.src64);
+        if (has64) {
+            memset(omit64, 8, R);
+            for (uint32_t q = 0; q < NQ; q++) keep64[q] = 0xFFFFFFFFu;
+        }
         // VerifierTranscriptOnline::new (online.rs:25-119) / VerifierTranscriptPreprocess::new (preprocess.rs:17-43),
         // as in rv_verify_shard: slots 0..39 are the online records in proof order, 40..255 the preprocessing ones
         for (uint32_t g0 = 0; g0 < R; g0 += 8) {
@@ -175,6 +190,17 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
                     keep[r / 4] &= ~(1u << (31 - 8 * (r % 4) - o[i].omit));
                     onm[r / 4] |= 0xFFu << (24 - 8 * (r % 4));
                     memcpy(h + L.hkeys + (size_t)r * 128, proofs[b] + o[i].keys, 128);
+                    if (has64) {  // (rv_verify_shard: the group's first record gives the lengths, missing words read as zero)
+                        omit64[r] = z[i].omit;
+                        keep64[r / 4] &= ~(1u << (31 - 8 * (r % 4) - z[i].omit));
+                        src64[0 * R + r] = L.proof + z[i].rec;
+                        src64[1 * R + r] = std::min(z[i].n_rec, z[0].n_rec / 8 * 8);
+                        src64[2 * R + r] = L.proof + z[i].corr;
+                        src64[3 * R + r] = std::min(z[i].n_corr, z[0].n_corr / 8 * 8);
+                        src64[4 * R + r] = L.proof + z[i].in;
+                        src64[5 * R + r] = std::min(z[i].n_in, z[0].n_in / 8 * 8);
+                        memcpy(h + L.hkeys64 + (size_t)r * 128, proofs[b] + z[i].keys, 128);
+                    }
                 }
             } else {
                 const PreRec* q = &Q.gf2.pre[g0 - RV_ONLINE_REPS];
@@ -183,6 +209,7 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
                     memcpy(h + L.seeds + (size_t)(g0 + i) * 16, proofs[b] + q[i].seed, 16);
                     memcpy(h + L.hco + (size_t)(g0 + i) * 32, proofs[b] + q[i].comm_online, 32);
                     memcpy(h + L.hco64 + (size_t)(g0 + i) * 32, proofs[b] + q64[i].comm_online, 32);
+                    if (has64) memcpy(h + L.seeds64 + (size_t)(g0 + i) * 16, proofs[b] + q64[i].seed, 16);
                 }
             }
         }
@@ -221,6 +248,9 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
     if (hipMemcpyAsync(d_slab + HEAD, h_slab, L.stride * B, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return cleanup(RV_E_DEVICE);
     // ---- per proof (recorded): keys, masks, supplied-value rows, buffers
     std::vector<InterpParams> pp(B);
+    std::vector<Interp64Params> pp64(has64 ? B : 0);
+    // the Z64 supplied values of the opened repetitions -- slots 0 .. 39 -- in rows of 64 (rv_verify_shard's sup_r for a whole proof)
+    constexpr uint32_t SUP_R64 = 64;
     for (size_t k = 0; k < B && !rc; k++) {
         uint8_t* d = d_slab + HEAD + k * L.stride;
         rv_shard* s = sh[k] = new rv_shard();
@@ -243,15 +273,43 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         s->extra.push_back(d_sup_corr);
         if ((rc = dalloc(ctx, (size_t)std::max<uint64_t>(cc.n_rec, 1) * NQ, &d_sup_rec))) break;
         s->extra.push_back(d_sup_rec);
+        uint64_t *d_sup_in64 = nullptr, *d_sup_corr64 = nullptr, *d_sup_rec64 = nullptr;
+        if (has64) {
+            s->d_omit64 = d + L.omit64;
+            if ((rc = dalloc(ctx, (size_t)R * 128, &s->d_keys64))) break;
+            if ((rc = dalloc(ctx, (size_t)std::max<uint64_t>(cc.n_in64, 1) * SUP_R64, &d_sup_in64))) break;
+            s->extra.push_back(d_sup_in64);
+            if ((rc = dalloc(ctx, (size_t)std::max<uint64_t>(cc.n_corr64, 1) * SUP_R64, &d_sup_corr64))) break;
+            s->extra.push_back(d_sup_corr64);
+            if ((rc = dalloc(ctx, (size_t)std::max<uint64_t>(cc.n_rec64, 1) * SUP_R64, &d_sup_rec64))) break;
+            s->extra.push_back(d_sup_rec64);
+        }
         g_recorder = &recs[k];
         launch_expand_seeds(ctx->stream, s->d_seeds, R, s->d_keys);
         launch_overlay_rows(ctx->stream, (uint32_t*)s->d_keys, (const uint32_t*)(d + L.hkeys), s->d_omit, R, 32, 1);
-        if (!(rc = shard_setup_prg(s, (const uint32_t*)(d + L.keep)))) {
+        if (has64) {
+            launch_expand_seeds(ctx->stream, d + L.seeds64, R, s->d_keys64);
+            launch_overlay_rows(ctx->stream, (uint32_t*)s->d_keys64, (const uint32_t*)(d + L.hkeys64), s->d_omit64, R, 32, 1);
+        }
+        // (k_z64_fused and the single verifier's side-stream schedule for the Z64 records -- ev_sup64, mid64 -- stay out: a fresh
+        // shard's z64f is false, and the records are unpacked here, from the slot, on the main stream)
+        if (!(rc = shard_setup_prg(s, (const uint32_t*)(d + L.keep), has64 ? (const uint32_t*)(d + L.keep64) : nullptr))) {
             const uint64_t* d_src = (const uint64_t*)(d + L.src);
             launch_unpack_bits(ctx->stream, d, d_src + 4 * R, d_src + 5 * R, s->d_omit, cc.n_in, NQ, 1, d_sup_in, NQ);
             launch_unpack_bits(ctx->stream, d, d_src + 2 * R, d_src + 3 * R, s->d_omit, cc.n_pre, NQ, 1, d_sup_corr, NQ);
             launch_unpack_bits(ctx->stream, d, d_src + 0 * R, d_src + 1 * R, s->d_omit, cc.n_rec, NQ, 0, d_sup_rec, NQ);
             Interp64Params p64{};
+            if (has64) {
+                const uint64_t* d_src64 = (const uint64_t*)(d + L.src64);
+                launch_unpack64(ctx->stream, d, d_src64 + 4 * R, d_src64 + 5 * R, s->d_omit64, cc.n_in64, R, d_sup_in64, SUP_R64);
+                launch_unpack64(ctx->stream, d, d_src64 + 2 * R, d_src64 + 3 * R, s->d_omit64, cc.n_corr64, R, d_sup_corr64, SUP_R64);
+                launch_unpack64(ctx->stream, d, d_src64 + 0 * R, d_src64 + 1 * R, s->d_omit64, cc.n_rec64, R, d_sup_rec64, SUP_R64);
+                p64.omit = s->d_omit64;
+                p64.sup_in = d_sup_in64;
+                p64.sup_corr = d_sup_corr64;
+                p64.sup_rec = d_sup_rec64;
+                p64.sup_r = SUP_R64;
+            }
             pp[k] = InterpParams{};
             pp[k].on_mask = (const uint32_t*)(d + L.onm);
             pp[k].sup_in = d_sup_in;
@@ -259,6 +317,7 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
             pp[k].sup_rec = d_sup_rec;
             pp[k].sup_nq = NQ;
             rc = shard_run_alloc(s, pp[k], p64);
+            if (has64) pp64[k] = p64;
         }
         g_recorder = nullptr;
     }
@@ -267,25 +326,43 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
     // ---- all proofs level by level, verify mode
     if ((rc = dalloc(ctx, B, &d_pp))) return cleanup(rc);
     if (hipMemcpyAsync(d_pp, pp.data(), B * sizeof(InterpParams), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return cleanup(RV_E_DEVICE);
+    Interp64Params* d_pp64 = nullptr;
+    if (has64) {
+        if ((rc = dalloc(ctx, B, &d_pp64))) return cleanup(rc);
+        device_tmp.push_back(d_pp64);
+        if (hipMemcpyAsync(d_pp64, pp64.data(), B * sizeof(Interp64Params), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return cleanup(RV_E_DEVICE);
+        ctx->phase(RV_PH_INTERP);  // (Z64 / mixed circuits: one count per batched launch, as in rv_prove_batch)
+    }
     {
+        // (the prover's order: per level the GF(2) launch, then the Z64 one; LDS and narrow runs hold no Z64 gates)
         const size_t n_levels = cc.level_start.empty() ? 0 : cc.level_start.size() - 1;
         for (size_t l = 0; l < n_levels; l++) {
             if (lds_run_for_batch(c, l, B)) {
                 const auto& pl = c->lds_runs[(size_t)c->lds_run_of_level[l]];
-                if (l == pl.run.l0)
+                if (l == pl.run.l0) {
                     launch_interp_lds(ctx->stream, MODE_VERIFY, pl.qs, RV_TOTAL_REPS / 4, c->d_lds_recs + pl.run.rec0, pl.run.n_steps, pl.run.n_slots,
                                       pl.run.eo0, pl.run.ep0, InterpParams{}, d_pp, (uint32_t)B);
+                    if (has64) ctx->count();
+                }
                 continue;
             }
             if (c->run_of_level[l] >= 0) {
                 const auto& run = c->narrow_runs[(size_t)c->run_of_level[l]];
-                if (l == run.first)
+                if (l == run.first) {
                     launch_interp_narrow_batched(ctx->stream, c->d_gates, c->d_level_range, run.first, run.second, run.tiny, d_pp, (uint32_t)B, MODE_VERIFY);
+                    if (has64) ctx->count();
+                }
                 continue;
             }
             launch_interp_batched(ctx->stream, c->d_gates, cc.level_range[l], d_pp, (uint32_t)B, MODE_VERIFY);
+            if (has64 && cc.level_start[l + 1] > cc.level_start[l]) ctx->count();
+            if (has64 && cc.level_start64[l + 1] > cc.level_start64[l]) {
+                launch_interp64_batched(ctx->stream, MODE_VERIFY, c->d_gates64, cc.level_start64[l], cc.level_start64[l + 1], d_pp64, (uint32_t)B);
+                ctx->count();
+            }
         }
     }
+    if (has64) ctx->phase(-1);
     // ---- per proof (recorded): digests, the commitments the preprocessing slots carry over, join
     for (size_t k = 0; k < B && !rc; k++) {
         uint8_t* d = d_slab + HEAD + k * L.stride;
@@ -307,6 +384,7 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
     if (hipMemcpyAsync(h_out, d_out + HEAD, out_stride * B, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess)
         return cleanup(hip_fail(hipGetLastError(), "verify batch sync", __FILE__, __LINE__));
+    if (has64) ctx->collect();
     // ---- the final check per proof (proof/mod.rs:283-306)
     for (size_t k = 0; k < B; k++) {
         const size_t b = live[k];
