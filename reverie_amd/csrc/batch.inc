@@ -59,6 +59,51 @@ static int replay_recorded(rv_ctx* ctx, std::vector<LaunchRecorder>& recs, std::
     return RV_OK;
 }
 
+// Circuits from this many gates on (GF(2) and Z64 gates counted together where the circuit has Z64 gates) leave the one-pass
+// path of rv_prove_batch and rv_verify_batch (RV_BATCH_BIG_GATES, default 2^20)
+static size_t batch_big_gates() {
+    static const size_t n = [] {
+        const char* e = getenv("RV_BATCH_BIG_GATES");
+        return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)1 << 20;
+    }();
+    return n;
+}
+
+// All proofs of a one-pass batch level by level (mode: MODE_PROVE / MODE_VERIFY; d_pp64 only for Z64 / mixed circuits), in the
+// order of shard_run_levels: per level the GF(2) launch, then the Z64 one.  LDS and narrow runs cover levels without Z64 gates
+// only -- rv_circuit's run plans -- so the levels they `continue` past have no Z64 launch to skip.  Z64 / mixed circuits count
+// one launch per batched launch, whatever the batch size.
+static void launch_levels_batched(rv_ctx* ctx, const rv_circuit* c, int mode, const InterpParams* d_pp, const Interp64Params* d_pp64, size_t batch) {
+    const Compiled& cc = c->cc;
+    const bool has64 = !cc.gates64.empty();
+    const size_t n_levels = cc.level_start.empty() ? 0 : cc.level_start.size() - 1;
+    for (size_t l = 0; l < n_levels; l++) {
+        if (lds_run_for_batch(c, l, batch)) {
+            const auto& pl = c->lds_runs[(size_t)c->lds_run_of_level[l]];
+            if (l == pl.run.l0) {
+                launch_interp_lds(ctx->stream, mode, pl.qs, RV_TOTAL_REPS / 4, c->d_lds_recs + pl.run.rec0, pl.run.n_steps, pl.run.n_slots,
+                                  pl.run.eo0, pl.run.ep0, InterpParams{}, d_pp, (uint32_t)batch);
+                if (has64) ctx->count();
+            }
+            continue;
+        }
+        if (c->run_of_level[l] >= 0) {
+            const auto& run = c->narrow_runs[(size_t)c->run_of_level[l]];
+            if (l == run.first) {
+                launch_interp_narrow_batched(ctx->stream, c->d_gates, c->d_level_range, run.first, run.second, run.tiny, d_pp, (uint32_t)batch, mode);
+                if (has64) ctx->count();
+            }
+            continue;
+        }
+        launch_interp_batched(ctx->stream, c->d_gates, cc.level_range[l], d_pp, (uint32_t)batch, mode);
+        if (has64 && cc.level_start[l + 1] > cc.level_start[l]) ctx->count();
+        if (has64 && cc.level_start64[l + 1] > cc.level_start64[l]) {
+            launch_interp64_batched(ctx->stream, mode, c->d_gates64, cc.level_start64[l], cc.level_start64[l + 1], d_pp64, (uint32_t)batch);
+            ctx->count();
+        }
+    }
+}
+
 static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, const uint8_t* wit_gf2, size_t n_gf2,
                                const uint64_t* wit_z64, size_t n_z64, const uint8_t* seeds, uint8_t** proofs, size_t* proof_lens) {
     LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
@@ -91,10 +136,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
     };
     if (batch == 1) return one_by_one();
     HIPCHK(hipSetDevice(ctx->device));
-    static const size_t big_gates = [] {
-        const char* e = getenv("RV_BATCH_BIG_GATES");  // circuits from this many gates on take the two-proofs-in-flight path
-        return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)1 << 20;
-    }();
+    const size_t big_gates = batch_big_gates();  // (GF(2) circuits from this many gates on take the proofs-in-flight path)
     // Z64 / mixed circuits take the one-pass path below the same threshold (GF(2) and Z64 gates counted together); large ones
     // prove one by one (the worker threads' path is GF(2)-only: its early corrections would need a 2 GB staging area per worker)
     const bool has64 = !cc.gates64.empty();
@@ -338,37 +380,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
         device_tmp.push_back(d_pp64);
         if (hipMemcpyAsync(d_pp64, pp64.data(), batch * sizeof(Interp64Params), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return cleanup(RV_E_DEVICE);
     }
-    {
-        // (the order of shard_run_levels: per level the GF(2) launch, then the Z64 one.  LDS and narrow runs cover levels
-        // without Z64 gates only -- rv_circuit's run plans -- so the levels they `continue` past have no Z64 launch to skip.
-        // Z64 / mixed circuits count one launch per batched launch, whatever the batch size)
-        const size_t n_levels = cc.level_start.empty() ? 0 : cc.level_start.size() - 1;
-        for (size_t l = 0; l < n_levels; l++) {
-            if (lds_run_for_batch(c, l, batch)) {
-                const auto& pl = c->lds_runs[(size_t)c->lds_run_of_level[l]];
-                if (l == pl.run.l0) {
-                    launch_interp_lds(ctx->stream, MODE_PROVE, pl.qs, RV_TOTAL_REPS / 4, c->d_lds_recs + pl.run.rec0, pl.run.n_steps, pl.run.n_slots,
-                                      pl.run.eo0, pl.run.ep0, InterpParams{}, d_pp, (uint32_t)batch);
-                    if (has64) ctx->count();
-                }
-                continue;
-            }
-            if (c->run_of_level[l] >= 0) {
-                const auto& run = c->narrow_runs[(size_t)c->run_of_level[l]];
-                if (l == run.first) {
-                    launch_interp_narrow_batched(ctx->stream, c->d_gates, c->d_level_range, run.first, run.second, run.tiny, d_pp, (uint32_t)batch);
-                    if (has64) ctx->count();
-                }
-                continue;
-            }
-            launch_interp_batched(ctx->stream, c->d_gates, cc.level_range[l], d_pp, (uint32_t)batch);
-            if (has64 && cc.level_start[l + 1] > cc.level_start[l]) ctx->count();
-            if (has64 && cc.level_start64[l + 1] > cc.level_start64[l]) {
-                launch_interp64_batched(ctx->stream, MODE_PROVE, c->d_gates64, cc.level_start64[l], cc.level_start64[l + 1], d_pp64, (uint32_t)batch);
-                ctx->count();
-            }
-        }
-    }
+    launch_levels_batched(ctx, c, MODE_PROVE, d_pp, d_pp64, batch);
     // (the digests' recording below counts its launches too: the interpreter's phase ends here)
     if (has64) ctx->phase(-1);
     mark("interpreter launches");

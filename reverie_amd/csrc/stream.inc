@@ -629,9 +629,7 @@ static int stream_chunk_run(rv_stream* S, rv_circuit* c, uint64_t digest, size_t
                     len -= skip;
                 }
             SCHK(hipMemcpyAsync(d_src64, src64c.data(), src64c.size() * 8, hipMemcpyHostToDevice, st));
-            launch_unpack64(st, S->d_vproof, d_src64 + 4 * R, d_src64 + 5 * R, S->d_omit64_v, cc.n_in64, R, d_sup_in64, SR);
-            launch_unpack64(st, S->d_vproof, d_src64 + 2 * R, d_src64 + 3 * R, S->d_omit64_v, cc.n_corr64, R, d_sup_corr64, SR);
-            launch_unpack64(st, S->d_vproof, d_src64 + 0 * R, d_src64 + 1 * R, S->d_omit64_v, cc.n_rec64, R, d_sup_rec64, SR);
+            launch_unpack_supplied64(st, cc, S->d_vproof, d_src64, S->d_omit64_v, R, d_sup_in64, d_sup_corr64, d_sup_rec64, SR);
         }
     }
     // ---- masks of this chunk: CTR blocks [first_block, first_block + n_blocks) (the first one may be shared with the
@@ -1464,52 +1462,16 @@ static int stream_verify_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wi
         return RV_OK;
     }
     // ---- the slots (verifier's order: the 40 opened repetitions first), as rv_verify_shard prepares them
-    std::vector<uint8_t> seeds((size_t)R * 16, 0), omit(R, 8), seeds64((size_t)R * 16, 0), omit64(R, 8);
-    std::vector<uint8_t> hkeys((size_t)R * 128, 0), hkeys64((size_t)R * 128, 0), hco((size_t)R * 32, 0), hco64((size_t)R * 32, 0);
-    std::vector<uint64_t> src((size_t)6 * R, 0), src64((size_t)6 * R, 0);
-    std::vector<uint32_t> keep(NQ, 0xFFFFFFFFu), onm(NQ, 0), keep64(NQ, 0xFFFFFFFFu);
-    for (uint32_t g0 = 0; g0 < R; g0 += 8) {
-        if (g0 < RV_ONLINE_REPS) {
-            const OnRec* o = &P.gf2.on[g0];
-            const OnRec* z = &P.z64.on[g0];
-            for (int i = 0; i < 8; i++) {
-                if (o[i].omit >= 8 || z[i].omit >= 8) return RV_E_PROOF_MALFORMED;  // UB upstream (gf2/share.rs:167-199)
-                if (o[i].n_corr < o[0].n_corr || o[i].n_in < o[0].n_in) return RV_E_PROOF_MALFORMED;  // gf2/recon.rs:241-259
-                if (o[i].n_rec != o[0].n_rec) return RV_E_PROOF_MALFORMED;                             // gf2/share.rs:157-164
-                const uint32_t r = g0 + i;
-                omit[r] = o[i].omit;
-                src[0 * R + r] = o[i].rec, src[1 * R + r] = o[0].n_rec;
-                src[2 * R + r] = o[i].corr, src[3 * R + r] = o[0].n_corr;
-                src[4 * R + r] = o[i].in, src[5 * R + r] = o[0].n_in;
-                keep[r / 4] &= ~(1u << (31 - 8 * (r % 4) - o[i].omit));  // BatchGen skips the omitted player
-                onm[r / 4] |= 0xFFu << (24 - 8 * (r % 4));
-                omit64[r] = z[i].omit;
-                keep64[r / 4] &= ~(1u << (31 - 8 * (r % 4) - z[i].omit));
-                // length of the group's first record, missing chunks read as zero (z64/recon.rs:68-108, z64/share.rs:51-91)
-                src64[0 * R + r] = z[i].rec, src64[1 * R + r] = std::min(z[i].n_rec, z[0].n_rec / 8 * 8);
-                src64[2 * R + r] = z[i].corr, src64[3 * R + r] = std::min(z[i].n_corr, z[0].n_corr / 8 * 8);
-                src64[4 * R + r] = z[i].in, src64[5 * R + r] = std::min(z[i].n_in, z[0].n_in / 8 * 8);
-                memcpy(&hkeys[(size_t)r * 128], proof + o[i].keys, 128);
-                memcpy(&hkeys64[(size_t)r * 128], proof + z[i].keys, 128);
-            }
-        } else {
-            const PreRec* q = &P.gf2.pre[g0 - RV_ONLINE_REPS];
-            const PreRec* q64 = &P.z64.pre[g0 - RV_ONLINE_REPS];
-            for (int i = 0; i < 8; i++) {
-                memcpy(&seeds[(size_t)(g0 + i) * 16], proof + q[i].seed, 16);
-                memcpy(&seeds64[(size_t)(g0 + i) * 16], proof + q64[i].seed, 16);
-                memcpy(&hco[(size_t)(g0 + i) * 32], proof + q[i].comm_online, 32);
-                memcpy(&hco64[(size_t)(g0 + i) * 32], proof + q64[i].comm_online, 32);
-            }
-        }
-    }
+    if ((rc = check_records(P, 0, R))) return rc;
+    HostSlots H(R, true);
+    fill_slots(P, proof, 0, R, 0, true, H.arrays());
     // the prover's begin gives the stream its buffers and the GF(2) keys of the preprocessing slots (opened slots: overlaid below)
     rv_stream* S = nullptr;
-    if ((rc = stream_begin_impl(ctx, z64_wires, gf2_wires, seeds.data(), max_chunk_ops, &S))) return rc;
+    if ((rc = stream_begin_impl(ctx, z64_wires, gf2_wires, H.seeds.data(), max_chunk_ops, &S))) return rc;
     S->pass = 3;
     S->h_proof = proof;
     S->proof_len = proof_len;
-    S->src64 = src64;
+    S->src64 = H.src64;
     hipStream_t st = ctx->stream;
     auto fail = [&](int code) {
         rv_stream_abort(S);
@@ -1529,29 +1491,25 @@ static int stream_verify_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wi
     bool ok = true;
     auto up = [&](void* dst, const void* from, size_t n) { ok = ok && hipMemcpyAsync(dst, from, n, hipMemcpyHostToDevice, st) == hipSuccess; };
     up(S->d_vproof, proof, proof_len);
-    up(S->d_omit_v, omit.data(), R);
-    up(S->d_omit64_v, omit64.data(), R);
-    up(S->d_hco, hco.data(), hco.size());
-    up(S->d_hco64, hco64.data(), hco64.size());
-    up(S->d_keep, keep.data(), (size_t)NQ * 4);
-    up(S->d_keep64, keep64.data(), (size_t)NQ * 4);
-    up(S->d_onm, onm.data(), (size_t)NQ * 4);
-    S->sup_nq = 16;
-    for (uint32_t q = 16; q < NQ; q++)
-        if (onm[q]) S->sup_nq = NQ;
-    S->sup_r = 64;
-    for (uint32_t r = 64; r < R; r++)
-        if (omit64[r] < 8) S->sup_r = R;
-    up(S->d_src, src.data(), src.size() * 8);
+    up(S->d_omit_v, H.omit.data(), R);
+    up(S->d_omit64_v, H.omit64.data(), R);
+    up(S->d_hco, H.hco.data(), H.hco.size());
+    up(S->d_hco64, H.hco64.data(), H.hco64.size());
+    up(S->d_keep, H.keep.data(), (size_t)NQ * 4);
+    up(S->d_keep64, H.keep64.data(), (size_t)NQ * 4);
+    up(S->d_onm, H.onm.data(), (size_t)NQ * 4);
+    S->sup_nq = supplied_nq(H.onm.data(), NQ);
+    S->sup_r = supplied_r64(H.omit64.data(), R);
+    up(S->d_src, H.src.data(), H.src.size() * 8);
     // GF(2) transcript: the opened slots' keys are the proof's (omitted one zeroed, online.rs:101-113)
-    up(d_hkeys, hkeys.data(), hkeys.size());
+    up(d_hkeys, H.hkeys.data(), H.hkeys.size());
     launch_overlay_rows(st, (uint32_t*)S->d_keys, (const uint32_t*)d_hkeys, S->d_omit_v, R, 32, 1);
     launch_key_schedule(st, S->d_keys, R * 8, S->d_rkbytes);
     launch_bitslice_rk(st, S->d_rkbytes, NQ, S->d_rk);
     // Z64 transcript: its own seeds / keys per repetition
-    up(d_seeds64, seeds64.data(), seeds64.size());
+    up(d_seeds64, H.seeds64.data(), H.seeds64.size());
     launch_expand_seeds(st, d_seeds64, R, d_keys64);
-    up(d_hkeys, hkeys64.data(), hkeys64.size());  // (stream order: behind the overlay above that read the GF(2) keys)
+    up(d_hkeys, H.hkeys64.data(), H.hkeys64.size());  // (stream order: behind the overlay above that read the GF(2) keys)
     launch_overlay_rows(st, (uint32_t*)d_keys64, (const uint32_t*)d_hkeys, S->d_omit64_v, R, 32, 1);
     launch_key_schedule(st, d_keys64, R * 8, S->d_rkbytes);
     launch_bitslice_rk(st, S->d_rkbytes, NQ, S->d_rk64);

@@ -78,6 +78,156 @@ bool format_ok(const Parsed& p) {  // ProofSingle::check_format, proof/mod.rs:11
     return p.gf2.on.size() == RV_ONLINE_REPS && p.gf2.pre.size() == RV_PREPROCESSING_REPS &&
            p.z64.on.size() == RV_ONLINE_REPS && p.z64.pre.size() == RV_PREPROCESSING_REPS;
 }
+
+// ------------------------------------------------------------------------------------
+// the verifier's slots (VerifierTranscriptOnline::new, online.rs:25-119; VerifierTranscriptPreprocess::new, preprocess.rs:17-43),
+// shared by rv_verify_shard, rv_verify_batch and the streaming verifier.  Slots 0 .. 39 are the online records in proof order,
+// 40 .. 255 the preprocessing ones; a slot range starts and ends on a group of eight.
+// ------------------------------------------------------------------------------------
+// what the online records of [slot_begin, slot_begin + slot_count) must satisfy (a proof that passed format_ok):
+// RV_OK / RV_E_PROOF_MALFORMED
+int check_records(const Parsed& P, uint32_t slot_begin, uint32_t slot_count) {
+    for (uint32_t g0 = slot_begin; g0 < std::min<uint32_t>(slot_begin + slot_count, RV_ONLINE_REPS); g0 += 8) {
+        const OnRec* o = &P.gf2.on[g0];
+        const OnRec* z = &P.z64.on[g0];
+        for (int i = 0; i < 8; i++) {
+            if (o[i].omit >= 8 || z[i].omit >= 8) return RV_E_PROOF_MALFORMED;  // UB upstream (gf2/share.rs:167-199)
+            // Recon::unpack indexes every vector up to the first one's length (gf2/recon.rs:241-259)
+            if (o[i].n_corr < o[0].n_corr || o[i].n_in < o[0].n_in) return RV_E_PROOF_MALFORMED;
+            // Share::unpack_selected asserts equal lengths (gf2/share.rs:157-164)
+            if (o[i].n_rec != o[0].n_rec) return RV_E_PROOF_MALFORMED;
+        }
+    }
+    return RV_OK;
+}
+// where fill_slots writes the arrays of R slots (NQ = R / 4 quad words)
+struct SlotArrays {
+    uint8_t *seeds, *omit, *hkeys, *hco, *hco64;  // [R][16], [R], [R][128], [R][32], [R][32]
+    uint32_t *keep, *onm;                          // [NQ] each
+    uint64_t* src;                                 // [6][R]: rec offset, length; corr offset, length; in offset, length
+    uint8_t *seeds64, *omit64, *hkeys64;           // the Z64 side, as the GF(2) one
+    uint32_t* keep64;
+    uint64_t* src64;
+};
+// ... and host vectors for them
+struct HostSlots {
+    std::vector<uint8_t> seeds, omit, hkeys, hco, hco64, seeds64, omit64, hkeys64;
+    std::vector<uint32_t> keep, onm, keep64;
+    std::vector<uint64_t> src, src64;
+    HostSlots(uint32_t R, bool has64)
+        : seeds((size_t)R * 16), omit(R), hkeys((size_t)R * 128), hco((size_t)R * 32), hco64((size_t)R * 32), keep(R / 4), onm(R / 4),
+          src((size_t)6 * R) {
+        if (has64) {
+            seeds64.resize((size_t)R * 16);
+            omit64.resize(R);
+            hkeys64.resize((size_t)R * 128);
+            keep64.resize(R / 4);
+            src64.resize((size_t)6 * R);
+        }
+    }
+    SlotArrays arrays() {
+        return {seeds.data(),   omit.data(),   hkeys.data(),   hco.data(),    hco64.data(), keep.data(), onm.data(), src.data(),
+                seeds64.data(), omit64.data(), hkeys64.data(), keep64.data(), src64.data()};
+    }
+};
+// The slot arrays of [slot_begin, slot_begin + R) from a proof that passed check_records: omit / omit64 start at 8 (not opened),
+// keep / keep64 at all ones, everything else at zero.  `base` is added to every src / src64 offset (the proof's place in the
+// device buffer the unpack kernels read).  The Z64 seeds, keys, omit64, keep64 and src64 are written only when has64 is set.
+void fill_slots(const Parsed& P, const uint8_t* proof, uint32_t slot_begin, uint32_t R, uint64_t base, bool has64, const SlotArrays& a) {
+    const uint32_t NQ = R / 4;
+    memset(a.seeds, 0, (size_t)R * 16);
+    memset(a.omit, 8, R);
+    memset(a.hkeys, 0, (size_t)R * 128);
+    memset(a.hco, 0, (size_t)R * 32);
+    memset(a.hco64, 0, (size_t)R * 32);
+    std::fill_n(a.keep, NQ, 0xFFFFFFFFu);
+    std::fill_n(a.onm, NQ, 0u);
+    std::fill_n(a.src, (size_t)6 * R, (uint64_t)0);
+    if (has64) {
+        memset(a.seeds64, 0, (size_t)R * 16);
+        memset(a.omit64, 8, R);
+        memset(a.hkeys64, 0, (size_t)R * 128);
+        std::fill_n(a.keep64, NQ, 0xFFFFFFFFu);
+        std::fill_n(a.src64, (size_t)6 * R, (uint64_t)0);
+    }
+    for (uint32_t g0 = 0; g0 < R; g0 += 8) {
+        const uint32_t slot0 = slot_begin + g0;
+        if (slot0 < RV_ONLINE_REPS) {
+            const OnRec* o = &P.gf2.on[slot0];
+            const OnRec* z = &P.z64.on[slot0];
+            for (int i = 0; i < 8; i++) {
+                const uint32_t r = g0 + i;
+                a.omit[r] = o[i].omit;
+                a.src[0 * R + r] = base + o[i].rec;
+                a.src[1 * R + r] = o[0].n_rec;
+                a.src[2 * R + r] = base + o[i].corr;
+                a.src[3 * R + r] = o[0].n_corr;
+                a.src[4 * R + r] = base + o[i].in;
+                a.src[5 * R + r] = o[0].n_in;
+                a.keep[r / 4] &= ~(1u << (31 - 8 * (r % 4) - o[i].omit));  // BatchGen skips the omitted player
+                a.onm[r / 4] |= 0xFFu << (24 - 8 * (r % 4));
+                memcpy(a.hkeys + (size_t)r * 128, proof + o[i].keys, 128);  // the opened players' keys (online.rs:101-113)
+                if (has64) {
+                    // Z64 vectors: length of the group's first record, missing chunks read as zero
+                    // (z64/recon.rs:68-108, z64/share.rs:51-91)
+                    a.omit64[r] = z[i].omit;
+                    a.keep64[r / 4] &= ~(1u << (31 - 8 * (r % 4) - z[i].omit));
+                    a.src64[0 * R + r] = base + z[i].rec;
+                    a.src64[1 * R + r] = std::min(z[i].n_rec, z[0].n_rec / 8 * 8);
+                    a.src64[2 * R + r] = base + z[i].corr;
+                    a.src64[3 * R + r] = std::min(z[i].n_corr, z[0].n_corr / 8 * 8);
+                    a.src64[4 * R + r] = base + z[i].in;
+                    a.src64[5 * R + r] = std::min(z[i].n_in, z[0].n_in / 8 * 8);
+                    memcpy(a.hkeys64 + (size_t)r * 128, proof + z[i].keys, 128);
+                }
+            }
+        } else {
+            // seeds, and the online commitments the preprocessing slots carry over from the proof (preprocess.rs:55-57)
+            const PreRec* q = &P.gf2.pre[slot0 - RV_ONLINE_REPS];
+            const PreRec* q64 = &P.z64.pre[slot0 - RV_ONLINE_REPS];
+            for (int i = 0; i < 8; i++) {
+                const uint32_t r = g0 + i;
+                memcpy(a.seeds + (size_t)r * 16, proof + q[i].seed, 16);
+                memcpy(a.hco + (size_t)r * 32, proof + q[i].comm_online, 32);
+                memcpy(a.hco64 + (size_t)r * 32, proof + q64[i].comm_online, 32);
+                if (has64) memcpy(a.seeds64 + (size_t)r * 16, proof + q64[i].seed, 16);
+            }
+        }
+    }
+}
+// the quad words that hold an opened repetition, in order, into quads[NQ]: their number
+uint32_t opened_quads(const uint32_t* onm, uint32_t NQ, uint32_t* quads) {
+    uint32_t n = 0;
+    for (uint32_t q = 0; q < NQ; q++)
+        if (onm[q]) quads[n++] = q;
+    return n;
+}
+// rows of the GF(2) supplied values: sixteen quad words (two sectors, written whole) when the opened repetitions sit in the first
+// sixteen -- the verifier's slot order puts them into the first ten -- instead of full share rows
+uint32_t supplied_nq(const uint32_t* onm, uint32_t NQ) {
+    for (uint32_t q = 16; q < NQ; q++)
+        if (onm[q]) return NQ;
+    return std::min(NQ, 16u);
+}
+// ... and the Z64 ones: the first 64 repetitions when no other is opened
+uint32_t supplied_r64(const uint8_t* omit64, uint32_t R) {
+    for (uint32_t r = 64; r < R; r++)
+        if (omit64[r] < 8) return R;
+    return std::min(R, 64u);
+}
+// the supplied-value rows of R slots, unpacked from the proof bytes at d_blob through the src / src64 table fill_slots wrote
+void launch_unpack_supplied(hipStream_t st, const Compiled& cc, const uint8_t* d_blob, const uint64_t* d_src, const uint8_t* d_omit, uint32_t R,
+                            uint32_t* d_in, uint32_t* d_corr, uint32_t* d_rec, uint32_t sup_nq) {
+    launch_unpack_bits(st, d_blob, d_src + 4 * R, d_src + 5 * R, d_omit, cc.n_in, R / 4, 1, d_in, sup_nq);
+    launch_unpack_bits(st, d_blob, d_src + 2 * R, d_src + 3 * R, d_omit, cc.n_pre, R / 4, 1, d_corr, sup_nq);
+    launch_unpack_bits(st, d_blob, d_src + 0 * R, d_src + 1 * R, d_omit, cc.n_rec, R / 4, 0, d_rec, sup_nq);
+}
+void launch_unpack_supplied64(hipStream_t st, const Compiled& cc, const uint8_t* d_blob, const uint64_t* d_src64, const uint8_t* d_omit64, uint32_t R,
+                              uint64_t* d_in, uint64_t* d_corr, uint64_t* d_rec, uint32_t sup_r) {
+    launch_unpack64(st, d_blob, d_src64 + 4 * R, d_src64 + 5 * R, d_omit64, cc.n_in64, R, d_in, sup_r);
+    launch_unpack64(st, d_blob, d_src64 + 2 * R, d_src64 + 3 * R, d_omit64, cc.n_corr64, R, d_corr, sup_r);
+    launch_unpack64(st, d_blob, d_src64 + 0 * R, d_src64 + 1 * R, d_omit64, cc.n_rec64, R, d_rec, sup_r);
+}
 }  // namespace
 
 static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* proof, size_t proof_len, uint32_t slot_begin,
@@ -112,54 +262,15 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
     if (int rs2 = ctx_stream2(ctx)) return rs2;
     const uint32_t R = slot_count, NQ = R / 4;
 
-    // ---- host-side preparation of the slots (VerifierTranscriptOnline::new, online.rs:25-119;
-    //      VerifierTranscriptPreprocess::new, preprocess.rs:17-43)
-    std::vector<uint8_t> seeds((size_t)R * 16, 0), omit(R, 8), seeds64((size_t)R * 16, 0), omit64(R, 8);
-    std::vector<uint64_t> src((size_t)6 * R, 0);  // rec off,len ; corr off,len ; in off,len
-    std::vector<uint64_t> src64((size_t)6 * R, 0);
-    std::vector<uint32_t> keep(NQ, 0xFFFFFFFFu), onm(NQ, 0), keep64(NQ, 0xFFFFFFFFu);
+    // ---- host-side preparation of the slots
+    if ((rc = check_records(P, slot_begin, R))) return rc;
     const bool has64 = !cc.gates64.empty();
-    for (uint32_t g0 = 0; g0 < R; g0 += 8) {
-        const uint32_t slot0 = slot_begin + g0;
-        if (slot0 < RV_ONLINE_REPS) {
-            const OnRec* o = &P.gf2.on[slot0];
-            const OnRec* z = &P.z64.on[slot0];
-            for (int i = 0; i < 8; i++) {
-                if (o[i].omit >= 8 || z[i].omit >= 8) return RV_E_PROOF_MALFORMED;  // UB upstream (gf2/share.rs:167-199)
-                // Recon::unpack indexes every vector up to the first one's length (gf2/recon.rs:241-259)
-                if (o[i].n_corr < o[0].n_corr || o[i].n_in < o[0].n_in) return RV_E_PROOF_MALFORMED;
-                // Share::unpack_selected asserts equal lengths (gf2/share.rs:157-164)
-                if (o[i].n_rec != o[0].n_rec) return RV_E_PROOF_MALFORMED;
-                const uint32_t r = g0 + i;
-                omit[r] = o[i].omit;
-                src[0 * R + r] = o[i].rec;
-                src[1 * R + r] = o[0].n_rec;
-                src[2 * R + r] = o[i].corr;
-                src[3 * R + r] = o[0].n_corr;
-                src[4 * R + r] = o[i].in;
-                src[5 * R + r] = o[0].n_in;
-                keep[r / 4] &= ~(1u << (31 - 8 * (r % 4) - o[i].omit));  // BatchGen skips the omitted player
-                onm[r / 4] |= 0xFFu << (24 - 8 * (r % 4));
-                // Z64 vectors: length of the group's first record, missing chunks read as zero
-                // (z64/recon.rs:68-108, z64/share.rs:51-91)
-                omit64[r] = z[i].omit;
-                keep64[r / 4] &= ~(1u << (31 - 8 * (r % 4) - z[i].omit));
-                src64[0 * R + r] = z[i].rec;
-                src64[1 * R + r] = std::min(z[i].n_rec, z[0].n_rec / 8 * 8);
-                src64[2 * R + r] = z[i].corr;
-                src64[3 * R + r] = std::min(z[i].n_corr, z[0].n_corr / 8 * 8);
-                src64[4 * R + r] = z[i].in;
-                src64[5 * R + r] = std::min(z[i].n_in, z[0].n_in / 8 * 8);
-            }
-        } else {
-            const PreRec* q = &P.gf2.pre[slot0 - RV_ONLINE_REPS];
-            const PreRec* q64 = &P.z64.pre[slot0 - RV_ONLINE_REPS];
-            for (int i = 0; i < 8; i++) {
-                memcpy(&seeds[(size_t)(g0 + i) * 16], proof + q[i].seed, 16);
-                memcpy(&seeds64[(size_t)(g0 + i) * 16], proof + q64[i].seed, 16);
-            }
-        }
-    }
+    HostSlots H(R, has64);
+    fill_slots(P, proof, slot_begin, R, 0, has64, H.arrays());
+    std::vector<uint32_t> on_quads(NQ);
+    on_quads.resize(opened_quads(H.onm.data(), NQ, on_quads.data()));
+    const uint32_t sup_nq = supplied_nq(H.onm.data(), NQ);
+    const uint32_t sup_r = has64 ? supplied_r64(H.omit64.data(), R) : R;
 
     rv_shard* s = new rv_shard();
     s->ctx = ctx;
@@ -176,32 +287,6 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
     hipEvent_t ev_arena = nullptr;
     uint32_t *d_keep = nullptr, *d_onm = nullptr, *d_sup_in = nullptr, *d_sup_corr = nullptr, *d_sup_rec = nullptr;
     auto track = [&](void* p) { s->extra.push_back(p); };
-    std::vector<uint32_t> on_quads;
-    for (uint32_t q = 0; q < NQ; q++)
-        if (onm[q]) on_quads.push_back(q);
-    // rows of the supplied values: sixteen quad words (two sectors, written whole) when the opened repetitions sit in the first
-    // sixteen -- the verifier's slot order puts them into the first ten -- instead of full share rows
-    const uint32_t sup_nq = (NQ > 16 && (on_quads.empty() || on_quads.back() < 16)) ? 16u : NQ;
-    uint32_t sup_r = R;  // ... and the Z64 ones: the first 64 repetitions when no other is opened there
-    if (R > 64) {
-        sup_r = 64;
-        for (uint32_t r = 64; r < R; r++)
-            if (omit64[r] < 8) sup_r = R;
-    }
-    // ---- staging (one copy each instead of one per repetition): opened player keys (online.rs:101-113) and the
-    //      online commitments the preprocessing slots carry over from the proof (preprocess.rs:55-57)
-    std::vector<uint8_t> hkeys((size_t)R * 128, 0), hco((size_t)R * 32, 0), hkeys64, hco64((size_t)R * 32, 0);
-    if (has64) hkeys64.assign((size_t)R * 128, 0);
-    for (uint32_t r = 0; r < R; r++) {
-        if (omit[r] < 8) {
-            memcpy(&hkeys[(size_t)r * 128], proof + P.gf2.on[slot_begin + r].keys, 128);
-            if (has64 && omit64[r] < 8) memcpy(&hkeys64[(size_t)r * 128], proof + P.z64.on[slot_begin + r].keys, 128);
-        } else {
-            const uint32_t k = slot_begin + r - RV_ONLINE_REPS;
-            memcpy(&hco[(size_t)r * 32], proof + P.gf2.pre[k].comm_online, 32);
-            memcpy(&hco64[(size_t)r * 32], proof + P.z64.pre[k].comm_online, 32);
-        }
-    }
     uint32_t* d_on_quads = nullptr;
     uint8_t *d_hkeys = nullptr, *d_hco = nullptr, *d_hkeys64 = nullptr, *d_hco64 = nullptr;
     // A small GF(2) proof goes over in ONE copy: every host array above and the proof itself are packed into the
@@ -213,9 +298,9 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
         blob_bytes += (len + 15) & ~(size_t)15;
         return o;
     };
-    const size_t o_seeds = seg(seeds.size()), o_omit = seg(omit.size()), o_keep = seg((size_t)NQ * 4), o_onm = seg((size_t)NQ * 4),
-                 o_onq = seg(std::max<size_t>(on_quads.size(), 1) * 4), o_hkeys = seg(hkeys.size()), o_hco = seg(hco.size()),
-                 o_hco64 = seg(hco64.size()), o_src = seg(src.size() * 8), o_proof = seg(proof_len);
+    const size_t o_seeds = seg(H.seeds.size()), o_omit = seg(H.omit.size()), o_keep = seg((size_t)NQ * 4), o_onm = seg((size_t)NQ * 4),
+                 o_onq = seg(std::max<size_t>(on_quads.size(), 1) * 4), o_hkeys = seg(H.hkeys.size()), o_hco = seg(H.hco.size()),
+                 o_hco64 = seg(H.hco64.size()), o_src = seg(H.src.size() * 8), o_proof = seg(proof_len);
     constexpr bool small_stage = true;
     bool blob = small_stage && !has64 && !g_recorder && blob_bytes <= rv_ctx::IN_STAGE_BYTES;
     if (blob && !ctx->h_in && hipHostMalloc((void**)&ctx->h_in, rv_ctx::IN_STAGE_BYTES, hipHostMallocDefault) != hipSuccess) {
@@ -236,15 +321,15 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
         d_src = (uint64_t*)(b + o_src);
         d_proof = b + o_proof;
         uint8_t* h = ctx->h_in;
-        memcpy(h + o_seeds, seeds.data(), seeds.size());
-        memcpy(h + o_omit, omit.data(), omit.size());
-        memcpy(h + o_keep, keep.data(), (size_t)NQ * 4);
-        memcpy(h + o_onm, onm.data(), (size_t)NQ * 4);
+        memcpy(h + o_seeds, H.seeds.data(), H.seeds.size());
+        memcpy(h + o_omit, H.omit.data(), H.omit.size());
+        memcpy(h + o_keep, H.keep.data(), (size_t)NQ * 4);
+        memcpy(h + o_onm, H.onm.data(), (size_t)NQ * 4);
         if (!on_quads.empty()) memcpy(h + o_onq, on_quads.data(), on_quads.size() * 4);
-        memcpy(h + o_hkeys, hkeys.data(), hkeys.size());
-        memcpy(h + o_hco, hco.data(), hco.size());
-        memcpy(h + o_hco64, hco64.data(), hco64.size());
-        memcpy(h + o_src, src.data(), src.size() * 8);
+        memcpy(h + o_hkeys, H.hkeys.data(), H.hkeys.size());
+        memcpy(h + o_hco, H.hco.data(), H.hco.size());
+        memcpy(h + o_hco64, H.hco64.data(), H.hco64.size());
+        memcpy(h + o_src, H.src.data(), H.src.size() * 8);
         memcpy(h + o_proof, proof, proof_len);
     } else {
         if ((rc = dalloc(ctx, (size_t)R * 16, &s->d_seeds)) || (rc = dalloc(ctx, (size_t)R * 128, &s->d_keys)) ||
@@ -252,7 +337,7 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
             return fail(rc);
         if ((rc = dalloc(ctx, proof_len, &d_proof))) return fail(rc);
         track(d_proof);
-        if ((rc = dalloc(ctx, src.size(), &d_src))) return fail(rc);
+        if ((rc = dalloc(ctx, H.src.size(), &d_src))) return fail(rc);
         track(d_src);
         // d_proof / d_src may be filled from the SECOND stream further down (beside the mask kernels).  The arena hands blocks out
         // in the main stream's order, so the side stream first waits for everything the main stream holds NOW -- whatever used
@@ -268,11 +353,11 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
         track(d_onm);
         if ((rc = dalloc(ctx, std::max<size_t>(on_quads.size(), 1), &d_on_quads))) return fail(rc);
         track(d_on_quads);
-        if ((rc = dalloc(ctx, hkeys.size(), &d_hkeys))) return fail(rc);
+        if ((rc = dalloc(ctx, H.hkeys.size(), &d_hkeys))) return fail(rc);
         track(d_hkeys);
-        if ((rc = dalloc(ctx, hco.size(), &d_hco))) return fail(rc);
+        if ((rc = dalloc(ctx, H.hco.size(), &d_hco))) return fail(rc);
         track(d_hco);
-        if ((rc = dalloc(ctx, hco64.size(), &d_hco64))) return fail(rc);
+        if ((rc = dalloc(ctx, H.hco64.size(), &d_hco64))) return fail(rc);
         track(d_hco64);
     }
     if ((rc = dalloc(ctx, (size_t)std::max<uint64_t>(cc.n_in, 1) * sup_nq, &d_sup_in))) return fail(rc);
@@ -288,7 +373,7 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
         if ((rc = dalloc(ctx, (size_t)R * 16, &d_seeds64))) return fail(rc);
         track(d_seeds64);
         if ((rc = dalloc(ctx, (size_t)R * 128, &s->d_keys64)) || (rc = dalloc(ctx, R, &s->d_omit64))) return fail(rc);
-        if ((rc = dalloc(ctx, src64.size(), &d_src64))) return fail(rc);
+        if ((rc = dalloc(ctx, H.src64.size(), &d_src64))) return fail(rc);
         track(d_src64);
         if ((rc = dalloc(ctx, NQ, &d_keep64))) return fail(rc);
         track(d_keep64);
@@ -308,21 +393,21 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
     } while (0)
     const size_t DW = (size_t)R * 8;
     if (has64) {
-        if ((rc = dalloc(ctx, hkeys64.size(), &d_hkeys64))) return fail(rc);
+        if ((rc = dalloc(ctx, H.hkeys64.size(), &d_hkeys64))) return fail(rc);
         track(d_hkeys64);
     }
     // ---- stream 1: everything the mask generator needs, then the masks themselves
     if (blob) {
         HC(hipMemcpyAsync(s->d_seeds, ctx->h_in, blob_bytes, hipMemcpyHostToDevice, ctx->stream));
     } else {
-        HC(hipMemcpyAsync(s->d_seeds, seeds.data(), seeds.size(), hipMemcpyHostToDevice, ctx->stream));
-        HC(hipMemcpyAsync(s->d_omit, omit.data(), omit.size(), hipMemcpyHostToDevice, ctx->stream));
-        HC(hipMemcpyAsync(d_keep, keep.data(), NQ * 4, hipMemcpyHostToDevice, ctx->stream));
-        HC(hipMemcpyAsync(d_onm, onm.data(), NQ * 4, hipMemcpyHostToDevice, ctx->stream));
+        HC(hipMemcpyAsync(s->d_seeds, H.seeds.data(), H.seeds.size(), hipMemcpyHostToDevice, ctx->stream));
+        HC(hipMemcpyAsync(s->d_omit, H.omit.data(), H.omit.size(), hipMemcpyHostToDevice, ctx->stream));
+        HC(hipMemcpyAsync(d_keep, H.keep.data(), NQ * 4, hipMemcpyHostToDevice, ctx->stream));
+        HC(hipMemcpyAsync(d_onm, H.onm.data(), NQ * 4, hipMemcpyHostToDevice, ctx->stream));
         if (!on_quads.empty()) HC(hipMemcpyAsync(d_on_quads, on_quads.data(), on_quads.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        HC(hipMemcpyAsync(d_hkeys, hkeys.data(), hkeys.size(), hipMemcpyHostToDevice, ctx->stream));
-        HC(hipMemcpyAsync(d_hco, hco.data(), hco.size(), hipMemcpyHostToDevice, ctx->stream));
-        HC(hipMemcpyAsync(d_hco64, hco64.data(), hco64.size(), hipMemcpyHostToDevice, ctx->stream));
+        HC(hipMemcpyAsync(d_hkeys, H.hkeys.data(), H.hkeys.size(), hipMemcpyHostToDevice, ctx->stream));
+        HC(hipMemcpyAsync(d_hco, H.hco.data(), H.hco.size(), hipMemcpyHostToDevice, ctx->stream));
+        HC(hipMemcpyAsync(d_hco64, H.hco64.data(), H.hco64.size(), hipMemcpyHostToDevice, ctx->stream));
     }
     s->d_on_quads = d_on_quads;
     s->n_on_quads = (uint32_t)on_quads.size();
@@ -338,10 +423,10 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
     launch_expand_seeds(ctx->stream, s->d_seeds, R, s->d_keys);
     launch_overlay_rows(ctx->stream, (uint32_t*)s->d_keys, (const uint32_t*)d_hkeys, s->d_omit, R, 32, 1);
     if (has64) {
-        HC(hipMemcpyAsync(d_seeds64, seeds64.data(), seeds64.size(), hipMemcpyHostToDevice, ctx->stream));
-        HC(hipMemcpyAsync(s->d_omit64, omit64.data(), omit64.size(), hipMemcpyHostToDevice, ctx->stream));
-        HC(hipMemcpyAsync(d_keep64, keep64.data(), NQ * 4, hipMemcpyHostToDevice, ctx->stream));
-        HC(hipMemcpyAsync(d_hkeys64, hkeys64.data(), hkeys64.size(), hipMemcpyHostToDevice, ctx->stream));
+        HC(hipMemcpyAsync(d_seeds64, H.seeds64.data(), H.seeds64.size(), hipMemcpyHostToDevice, ctx->stream));
+        HC(hipMemcpyAsync(s->d_omit64, H.omit64.data(), H.omit64.size(), hipMemcpyHostToDevice, ctx->stream));
+        HC(hipMemcpyAsync(d_keep64, H.keep64.data(), NQ * 4, hipMemcpyHostToDevice, ctx->stream));
+        HC(hipMemcpyAsync(d_hkeys64, H.hkeys64.data(), H.hkeys64.size(), hipMemcpyHostToDevice, ctx->stream));
         launch_expand_seeds(ctx->stream, d_seeds64, R, s->d_keys64);
         launch_overlay_rows(ctx->stream, (uint32_t*)s->d_keys64, (const uint32_t*)d_hkeys64, s->d_omit64, R, 32, 1);
         ctx->count(2);
@@ -389,7 +474,7 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
         hipStream_t sc = (side && ev_arena) ? ctx->stream2 : sb;
         if (sc != sb) HC(hipStreamWaitEvent(sc, ev_arena, 0));
         HC(hipMemcpyAsync(d_proof, proof, proof_len, hipMemcpyHostToDevice, sc));
-        HC(hipMemcpyAsync(d_src, src.data(), src.size() * 8, hipMemcpyHostToDevice, sc));
+        HC(hipMemcpyAsync(d_src, H.src.data(), H.src.size() * 8, hipMemcpyHostToDevice, sc));
         if (sc != sb) {
             if (side_unpack && ev_inputs) {
                 HC(hipStreamWaitEvent(sc, ev_inputs, 0));
@@ -403,9 +488,7 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
         }
     }
     if (!split64) {  // (split64: a circuit without GF(2) gates has none of these)
-        launch_unpack_bits(su, d_proof, d_src + 4 * R, d_src + 5 * R, s->d_omit, cc.n_in, NQ, 1, d_sup_in, sup_nq);
-        launch_unpack_bits(su, d_proof, d_src + 2 * R, d_src + 3 * R, s->d_omit, cc.n_pre, NQ, 1, d_sup_corr, sup_nq);
-        launch_unpack_bits(su, d_proof, d_src + 0 * R, d_src + 1 * R, s->d_omit, cc.n_rec, NQ, 0, d_sup_rec, sup_nq);
+        launch_unpack_supplied(su, cc, d_proof, d_src, s->d_omit, R, d_sup_in, d_sup_corr, d_sup_rec, sup_nq);
         if (su != sb) {
             hipEvent_t e = ctx->get_sync_event();
             s->misc_events.push_back(e);
@@ -422,19 +505,15 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
                 hipStream_t sc = ctx->stream2;
                 if (hipStreamWaitEvent(sc, ev_arena, 0) != hipSuccess || hipMemcpyAsync(d_proof, proof, proof_len, hipMemcpyHostToDevice, sc) != hipSuccess ||
                     hipStreamWaitEvent(sc, ev_inputs64, 0) != hipSuccess ||
-                    hipMemcpyAsync(d_src64, src64.data(), src64.size() * 8, hipMemcpyHostToDevice, sc) != hipSuccess)
+                    hipMemcpyAsync(d_src64, H.src64.data(), H.src64.size() * 8, hipMemcpyHostToDevice, sc) != hipSuccess)
                     return hip_fail(hipGetLastError(), "rv_verify: the proof's copy", __FILE__, __LINE__);
-                launch_unpack64(sc, d_proof, d_src64 + 4 * R, d_src64 + 5 * R, s->d_omit64, cc.n_in64, R, d_sup_in64, sup_r);
-                launch_unpack64(sc, d_proof, d_src64 + 2 * R, d_src64 + 3 * R, s->d_omit64, cc.n_corr64, R, d_sup_corr64, sup_r);
-                launch_unpack64(sc, d_proof, d_src64 + 0 * R, d_src64 + 1 * R, s->d_omit64, cc.n_rec64, R, d_sup_rec64, sup_r);
+                launch_unpack_supplied64(sc, cc, d_proof, d_src64, s->d_omit64, R, d_sup_in64, d_sup_corr64, d_sup_rec64, sup_r);
                 if (hipEventRecord(s->ev_sup64, sc) != hipSuccess) return hip_fail(hipGetLastError(), "hipEventRecord", __FILE__, __LINE__);
                 return RV_OK;
             };
         } else {
-            HC(hipMemcpyAsync(d_src64, src64.data(), src64.size() * 8, hipMemcpyHostToDevice, sb));
-            launch_unpack64(sb, d_proof, d_src64 + 4 * R, d_src64 + 5 * R, s->d_omit64, cc.n_in64, R, d_sup_in64, sup_r);
-            launch_unpack64(sb, d_proof, d_src64 + 2 * R, d_src64 + 3 * R, s->d_omit64, cc.n_corr64, R, d_sup_corr64, sup_r);
-            launch_unpack64(sb, d_proof, d_src64 + 0 * R, d_src64 + 1 * R, s->d_omit64, cc.n_rec64, R, d_sup_rec64, sup_r);
+            HC(hipMemcpyAsync(d_src64, H.src64.data(), H.src64.size() * 8, hipMemcpyHostToDevice, sb));
+            launch_unpack_supplied64(sb, cc, d_proof, d_src64, s->d_omit64, R, d_sup_in64, d_sup_corr64, d_sup_rec64, sup_r);
         }
         p64.omit = s->d_omit64;
         p64.sup_in = d_sup_in64;

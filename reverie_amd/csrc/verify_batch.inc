@@ -18,56 +18,26 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         if (!proofs[b]) return RV_E_ARG;
     }
     const Compiled& cc = c->cc;
-    // A proof that cannot be parsed is a rejected proof (ok[b] = 0), not a failed call: one bad proof from an untrusted
-    // peer must not keep the others from being verified.  Non-zero return codes are left to argument / device errors.
-    auto one_by_one = [&]() -> int {
-        for (size_t b = 0; b < batch; b++) {
-            const int rc = rv_verify_ex(ctx, c, proofs[b], proof_lens[b], flags, &ok[b]);
-            if (rc == RV_E_PROOF_MALFORMED) {
-                ok[b] = 0;
-                continue;
-            }
-            if (rc) return rc;
-        }
-        return RV_OK;
-    };
-    static const size_t big_gates = [] {
-        const char* e = getenv("RV_BATCH_BIG_GATES");
-        return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)1 << 20;
-    }();
-    if (batch == 1 || cc.gates.size() + cc.gates64.size() >= big_gates) return one_by_one();
     const bool has64 = !cc.gates64.empty();
-    // ---- parse; proofs with the wrong repetition counts are `false` (proof/mod.rs:225-230) and take no further part
+    // ---- parse.  A proof that cannot be parsed, has the wrong repetition counts (`false`, proof/mod.rs:225-230) or online records
+    // the verifier's slots cannot take (check_records) is a rejected proof (ok[b] = 0) and takes no further part, not a failed
+    // call: one bad proof from an untrusted peer must not keep the others from being verified.  Non-zero return codes are left
+    // to argument / device errors.
     std::vector<Parsed> P(batch);
     std::vector<size_t> live;  // indices of the proofs that go to the GPU
     size_t max_len = 0;
-    // what the verifier groups require of the online records (the checks of fill() below, made before anything is
-    // staged so that a malformed proof simply drops out of the batch)
-    auto records_ok = [](const Parsed& Q) {
-        for (uint32_t g0 = 0; g0 < RV_ONLINE_REPS; g0 += 8) {
-            const OnRec* o = &Q.gf2.on[g0];
-            const OnRec* z = &Q.z64.on[g0];
-            for (int i = 0; i < 8; i++) {
-                if (o[i].omit >= 8 || z[i].omit >= 8) return false;
-                if (o[i].n_corr < o[0].n_corr || o[i].n_in < o[0].n_in || o[i].n_rec != o[0].n_rec) return false;
-            }
-        }
-        return true;
-    };
     for (size_t b = 0; b < batch; b++) {
-        if (parse_proof(proofs[b], proof_lens[b], P[b]) != RV_OK) continue;  // ok[b] stays 0
-        if (!format_ok(P[b]) || !records_ok(P[b])) continue;
+        if (parse_proof(proofs[b], proof_lens[b], P[b]) != RV_OK || !format_ok(P[b]) || check_records(P[b], 0, RV_TOTAL_REPS) != RV_OK) continue;
         live.push_back(b);
         max_len = std::max(max_len, proof_lens[b]);
     }
-    if (live.size() < 2) {
+    if (batch == 1 || live.size() < 2 || cc.gates.size() + cc.gates64.size() >= batch_big_gates()) {  // proof after proof
         for (size_t b : live) {
             const int rc = rv_verify_ex(ctx, c, proofs[b], proof_lens[b], flags, &ok[b]);
-            if (rc == RV_E_PROOF_MALFORMED) {
+            if (rc == RV_E_PROOF_MALFORMED)
                 ok[b] = 0;
-                continue;
-            }
-            if (rc) return rc;
+            else if (rc)
+                return rc;
         }
         return RV_OK;
     }
@@ -152,98 +122,33 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
     if ((rc = dalloc(ctx, HEAD + out_stride * B, &d_out))) return cleanup(rc);
     device_tmp.push_back(d_out);
     std::vector<uint32_t> n_quads(B, 0);
-    auto fill = [&](size_t k) -> int {
+    auto fill = [&](size_t k) {
         const size_t b = live[k];
-        const Parsed& Q = P[b];
         uint8_t* h = h_slab + k * L.stride;
-        memset(h, 0, L.proof);  // everything in front of the proof bytes
-        uint8_t* omit = h + L.omit;
-        memset(omit, 8, R);
-        uint32_t* keep = (uint32_t*)(h + L.keep);
-        uint32_t* onm = (uint32_t*)(h + L.onm);
-        for (uint32_t q = 0; q < NQ; q++) keep[q] = 0xFFFFFFFFu;
-        uint64_t* src = (uint64_t*)(h + L.src);
-        uint8_t* omit64 = h + L.omit64;
-        uint32_t* keep64 = (uint32_t*)(h + L.keep64);
-        uint64_t* src64 = (uint64_t*)(h + L.src64);
-        if (has64) {
-            memset(omit64, 8, R);
-            for (uint32_t q = 0; q < NQ; q++) keep64[q] = 0xFFFFFFFFu;
-        }
-        // VerifierTranscriptOnline::new (online.rs:25-119) / VerifierTranscriptPreprocess::new (preprocess.rs:17-43),
-        // as in rv_verify_shard: slots 0..39 are the online records in proof order, 40..255 the preprocessing ones
-        for (uint32_t g0 = 0; g0 < R; g0 += 8) {
-            if (g0 < RV_ONLINE_REPS) {
-                const OnRec* o = &Q.gf2.on[g0];
-                const OnRec* z = &Q.z64.on[g0];
-                for (int i = 0; i < 8; i++) {
-                    if (o[i].omit >= 8 || z[i].omit >= 8) return RV_E_PROOF_MALFORMED;
-                    if (o[i].n_corr < o[0].n_corr || o[i].n_in < o[0].n_in || o[i].n_rec != o[0].n_rec) return RV_E_PROOF_MALFORMED;
-                    const uint32_t r = g0 + i;
-                    omit[r] = o[i].omit;
-                    src[0 * R + r] = L.proof + o[i].rec;  // offsets into this proof's slot
-                    src[1 * R + r] = o[0].n_rec;
-                    src[2 * R + r] = L.proof + o[i].corr;
-                    src[3 * R + r] = o[0].n_corr;
-                    src[4 * R + r] = L.proof + o[i].in;
-                    src[5 * R + r] = o[0].n_in;
-                    keep[r / 4] &= ~(1u << (31 - 8 * (r % 4) - o[i].omit));
-                    onm[r / 4] |= 0xFFu << (24 - 8 * (r % 4));
-                    memcpy(h + L.hkeys + (size_t)r * 128, proofs[b] + o[i].keys, 128);
-                    if (has64) {  // (rv_verify_shard: the group's first record gives the lengths, missing words read as zero)
-                        omit64[r] = z[i].omit;
-                        keep64[r / 4] &= ~(1u << (31 - 8 * (r % 4) - z[i].omit));
-                        src64[0 * R + r] = L.proof + z[i].rec;
-                        src64[1 * R + r] = std::min(z[i].n_rec, z[0].n_rec / 8 * 8);
-                        src64[2 * R + r] = L.proof + z[i].corr;
-                        src64[3 * R + r] = std::min(z[i].n_corr, z[0].n_corr / 8 * 8);
-                        src64[4 * R + r] = L.proof + z[i].in;
-                        src64[5 * R + r] = std::min(z[i].n_in, z[0].n_in / 8 * 8);
-                        memcpy(h + L.hkeys64 + (size_t)r * 128, proofs[b] + z[i].keys, 128);
-                    }
-                }
-            } else {
-                const PreRec* q = &Q.gf2.pre[g0 - RV_ONLINE_REPS];
-                const PreRec* q64 = &Q.z64.pre[g0 - RV_ONLINE_REPS];
-                for (int i = 0; i < 8; i++) {
-                    memcpy(h + L.seeds + (size_t)(g0 + i) * 16, proofs[b] + q[i].seed, 16);
-                    memcpy(h + L.hco + (size_t)(g0 + i) * 32, proofs[b] + q[i].comm_online, 32);
-                    memcpy(h + L.hco64 + (size_t)(g0 + i) * 32, proofs[b] + q64[i].comm_online, 32);
-                    if (has64) memcpy(h + L.seeds64 + (size_t)(g0 + i) * 16, proofs[b] + q64[i].seed, 16);
-                }
-            }
-        }
-        uint32_t* quads = (uint32_t*)(h + L.quads);
-        for (uint32_t q = 0; q < NQ; q++)
-            if (onm[q]) quads[n_quads[k]++] = q;
+        const SlotArrays a{h + L.seeds, h + L.omit, h + L.hkeys, h + L.hco, h + L.hco64, (uint32_t*)(h + L.keep), (uint32_t*)(h + L.onm),
+                           (uint64_t*)(h + L.src), h + L.seeds64, h + L.omit64, h + L.hkeys64, (uint32_t*)(h + L.keep64), (uint64_t*)(h + L.src64)};
+        fill_slots(P[b], proofs[b], 0, R, L.proof, has64, a);  // (src offsets into this proof's slot)
+        n_quads[k] = opened_quads(a.onm, NQ, (uint32_t*)(h + L.quads));
         memcpy(h + L.proof, proofs[b], proof_lens[b]);
-        return RV_OK;
     };
     {
         // host work per proof (a few hundred KB of copies each): shared by a few threads for large batches
         const size_t n_thr = B >= 32 ? std::min<size_t>({(size_t)8, B / 8, (size_t)std::max(1u, std::thread::hardware_concurrency())}) : 1;
-        std::vector<int> rcs(std::max<size_t>(n_thr, 1), RV_OK);
-        auto range = [&](size_t t, size_t k0, size_t k1) {
-            try {  // (runs on a worker thread: nothing may escape it)
-                for (size_t k = k0; k < k1 && rcs[t] == RV_OK; k++) rcs[t] = fill(k);
-            } catch (...) {
-                rcs[t] = RV_E_NOMEM;
-            }
+        auto range = [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; k++) fill(k);
         };
         if (n_thr <= 1) {
-            range(0, 0, B);
+            range(0, B);
         } else {
             std::vector<std::thread> th;
             th.reserve(n_thr);
             try {
-                for (size_t t = 0; t < n_thr; t++) th.emplace_back(range, t, B * t / n_thr, B * (t + 1) / n_thr);
+                for (size_t t = 0; t < n_thr; t++) th.emplace_back(range, B * t / n_thr, B * (t + 1) / n_thr);
             } catch (...) {  // a thread could not be started: the ranges without one are done here
-                for (size_t t = th.size(); t < n_thr; t++) range(t, B * t / n_thr, B * (t + 1) / n_thr);
+                for (size_t t = th.size(); t < n_thr; t++) range(B * t / n_thr, B * (t + 1) / n_thr);
             }
             for (auto& x : th) x.join();
         }
-        for (int r : rcs)
-            if (r) return cleanup(r);
     }
     if (hipMemcpyAsync(d_slab + HEAD, h_slab, L.stride * B, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return cleanup(RV_E_DEVICE);
     // ---- per proof (recorded): keys, masks, supplied-value rows, buffers
@@ -294,16 +199,11 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         // (k_z64_fused and the single verifier's side-stream schedule for the Z64 records -- ev_sup64, mid64 -- stay out: a fresh
         // shard's z64f is false, and the records are unpacked here, from the slot, on the main stream)
         if (!(rc = shard_setup_prg(s, (const uint32_t*)(d + L.keep), has64 ? (const uint32_t*)(d + L.keep64) : nullptr))) {
-            const uint64_t* d_src = (const uint64_t*)(d + L.src);
-            launch_unpack_bits(ctx->stream, d, d_src + 4 * R, d_src + 5 * R, s->d_omit, cc.n_in, NQ, 1, d_sup_in, NQ);
-            launch_unpack_bits(ctx->stream, d, d_src + 2 * R, d_src + 3 * R, s->d_omit, cc.n_pre, NQ, 1, d_sup_corr, NQ);
-            launch_unpack_bits(ctx->stream, d, d_src + 0 * R, d_src + 1 * R, s->d_omit, cc.n_rec, NQ, 0, d_sup_rec, NQ);
+            launch_unpack_supplied(ctx->stream, cc, d, (const uint64_t*)(d + L.src), s->d_omit, R, d_sup_in, d_sup_corr, d_sup_rec, NQ);
             Interp64Params p64{};
             if (has64) {
-                const uint64_t* d_src64 = (const uint64_t*)(d + L.src64);
-                launch_unpack64(ctx->stream, d, d_src64 + 4 * R, d_src64 + 5 * R, s->d_omit64, cc.n_in64, R, d_sup_in64, SUP_R64);
-                launch_unpack64(ctx->stream, d, d_src64 + 2 * R, d_src64 + 3 * R, s->d_omit64, cc.n_corr64, R, d_sup_corr64, SUP_R64);
-                launch_unpack64(ctx->stream, d, d_src64 + 0 * R, d_src64 + 1 * R, s->d_omit64, cc.n_rec64, R, d_sup_rec64, SUP_R64);
+                launch_unpack_supplied64(ctx->stream, cc, d, (const uint64_t*)(d + L.src64), s->d_omit64, R, d_sup_in64, d_sup_corr64, d_sup_rec64,
+                                         SUP_R64);
                 p64.omit = s->d_omit64;
                 p64.sup_in = d_sup_in64;
                 p64.sup_corr = d_sup_corr64;
@@ -333,35 +233,7 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         if (hipMemcpyAsync(d_pp64, pp64.data(), B * sizeof(Interp64Params), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return cleanup(RV_E_DEVICE);
         ctx->phase(RV_PH_INTERP);  // (Z64 / mixed circuits: one count per batched launch, as in rv_prove_batch)
     }
-    {
-        // (the prover's order: per level the GF(2) launch, then the Z64 one; LDS and narrow runs hold no Z64 gates)
-        const size_t n_levels = cc.level_start.empty() ? 0 : cc.level_start.size() - 1;
-        for (size_t l = 0; l < n_levels; l++) {
-            if (lds_run_for_batch(c, l, B)) {
-                const auto& pl = c->lds_runs[(size_t)c->lds_run_of_level[l]];
-                if (l == pl.run.l0) {
-                    launch_interp_lds(ctx->stream, MODE_VERIFY, pl.qs, RV_TOTAL_REPS / 4, c->d_lds_recs + pl.run.rec0, pl.run.n_steps, pl.run.n_slots,
-                                      pl.run.eo0, pl.run.ep0, InterpParams{}, d_pp, (uint32_t)B);
-                    if (has64) ctx->count();
-                }
-                continue;
-            }
-            if (c->run_of_level[l] >= 0) {
-                const auto& run = c->narrow_runs[(size_t)c->run_of_level[l]];
-                if (l == run.first) {
-                    launch_interp_narrow_batched(ctx->stream, c->d_gates, c->d_level_range, run.first, run.second, run.tiny, d_pp, (uint32_t)B, MODE_VERIFY);
-                    if (has64) ctx->count();
-                }
-                continue;
-            }
-            launch_interp_batched(ctx->stream, c->d_gates, cc.level_range[l], d_pp, (uint32_t)B, MODE_VERIFY);
-            if (has64 && cc.level_start[l + 1] > cc.level_start[l]) ctx->count();
-            if (has64 && cc.level_start64[l + 1] > cc.level_start64[l]) {
-                launch_interp64_batched(ctx->stream, MODE_VERIFY, c->d_gates64, cc.level_start64[l], cc.level_start64[l + 1], d_pp64, (uint32_t)B);
-                ctx->count();
-            }
-        }
-    }
+    launch_levels_batched(ctx, c, MODE_VERIFY, d_pp, d_pp64, B);
     if (has64) ctx->phase(-1);
     // ---- per proof (recorded): digests, the commitments the preprocessing slots carry over, join
     for (size_t k = 0; k < B && !rc; k++) {
