@@ -144,6 +144,10 @@ int rv_circuit_compile(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_w
  * benchmark circuit: rv_prove 6.4 -> 6.15 ms); the verifier and repetition shards (32-byte to 128-byte rows, corr-bit
  * rows per operand) run 3-15 % slower on such a stream, so rv_circuit_compile does not choose it. */
 #define RV_COMPILE_WHOLE_PROVER 1u
+/* RV_COMPILE_KEEP_WIRES: the circuit also keeps, in HBM, the value form every wire has at the end of the program (GF(2): at most
+ * three share rows plus a constant bit; Z64: the final SSA id; a wire that is never written reads as zero) -- what rv_evaluate needs
+ * to return wire values.  Proofs of such a circuit are byte-identical to those of a circuit compiled without it. */
+#define RV_COMPILE_KEEP_WIRES 2u
 int rv_circuit_compile_ex(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                           rv_circuit **out);
 void rv_circuit_destroy(rv_circuit *c);
@@ -231,6 +235,24 @@ int rv_prove_device(rv_ctx *ctx, const rv_circuit *c, const uint8_t *wit_gf2, si
  * circuits prove one rv_prove per proof. */
 int rv_prove_batch(rv_ctx *ctx, const rv_circuit *c, size_t batch, const uint8_t *wit_gf2, size_t n_gf2,
                    const uint64_t *wit_z64, size_t n_z64, const uint8_t *seeds, uint8_t **proofs, size_t *proof_lens);
+
+/* ---- cleartext evaluation (mcircuit::evaluate_composite_program, re-exported at src/lib.rs:6; the CLI's `oneshot`) ----
+ * Evaluates the circuit on the witness in the clear, on the GPU: no shares, no transcripts.  A failing AssertZero is not an error:
+ * the call returns RV_OK and the status says which assertions do not hold.  gf2_values / z64_values (NULL: not wanted) receive the
+ * first gf2_wires / z64_wires wires' values at the end of the program (the wire counts the circuit was compiled with; one byte 0/1
+ * per GF(2) wire), which needs a circuit compiled with RV_COMPILE_KEEP_WIRES (RV_E_ARG otherwise).  Op lists with Random ops have no
+ * single cleartext value: RV_E_UNSUPPORTED.  A witness shorter than the Input ops: RV_E_WITNESS_SHORT (as rv_prove).
+ * rv_evaluate_batch: `batch` witnesses at once (witness b at wit_gf2 + b*n_gf2 / wit_z64 + b*n_z64, values at gf2_values +
+ * b*gf2_wires / z64_values + b*z64_wires, status st[b]); each result equals rv_evaluate's for that witness.  Runs on the context's
+ * stream; a batch that does not fit in half of the free device memory is evaluated in parts. */
+typedef struct rv_eval_status {
+    uint64_t n_failed;        /* AssertZero ops that do not hold */
+    uint64_t first_failed_op; /* op-list index of the first failing AssertZero in program order; UINT64_MAX if none */
+} rv_eval_status;
+int rv_evaluate(rv_ctx *ctx, const rv_circuit *c, const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64, size_t n_z64,
+                uint8_t *gf2_values, uint64_t *z64_values, rv_eval_status *st);
+int rv_evaluate_batch(rv_ctx *ctx, const rv_circuit *c, size_t batch, const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64,
+                      size_t n_z64, uint8_t *gf2_values, uint64_t *z64_values, rv_eval_status *st);
 
 /* ---- Proof::verify ----------------------------------------------------------------
  * Verification is STRICT by default (flags 0, rv_verify): on top of the reference's check (*ok = 0 when a ProofSingle
@@ -528,6 +550,9 @@ uint64_t rv_hook_overlap_commits(void);
  * reference's: verifier/online.rs:122-183 computes the same values).  The answer is the same either way; the tests use the
  * counter to know which path they compared.  RV_VERIFY_VC=0 turns the path off. */
 uint64_t rv_hook_verify_vc_count(void);
+/* How often this process's evaluations (rv_evaluate, rv_evaluate_batch) ran each schedule: out[0] = one launch per dependency level,
+ * out[1] = one workgroup per slice of witness words walking every level (csrc/eval.hip).  The results are the same either way. */
+int rv_hook_eval_schedules(uint64_t out[2]);
 /* The early-corrections plan of a program (host only, no device): the ops are compiled as rv_circuit_compile_ex(flags) would and
  * the plan rv_prove would use is built and checked against the compiled gate records.  out[0] = a plan exists (0 / 1: the circuit
  * is pure GF(2) with >= 2^21 Mul gates -- RV_EARLY_MIN -- or pure Z64, its preprocessing rows complete in step with the levels

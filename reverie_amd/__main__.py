@@ -78,6 +78,26 @@ def evaluate_clear(prog, witness):
     return v
 
 
+def evaluate_gpu(prog, wc, witness):
+    """`oneshot` on the GPU (rv_evaluate): any program without Random ops, GF(2), Z64 and B2A alike (the CLI's witness is
+    GF(2) bits only, as the reference's).  Raises SystemExit naming the op index of the first failing AssertZero."""
+    from .proof import Circuit
+
+    r = Circuit(prog, wc).evaluate(witness, [])
+    if not r.ok:
+        raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (r.first_failed_op, r.n_failed))
+
+
+# --evaluator auto: programs from this many ops on (and every program with Z64 or B2A ops) are evaluated on the GPU
+GPU_EVAL_MIN_OPS = 100_000
+
+
+def use_gpu_evaluator(prog, evaluator: str) -> bool:
+    if evaluator != "auto":
+        return evaluator == "gpu"
+    return len(prog) >= GPU_EVAL_MIN_OPS or bool(np.isin(prog["domain"], (1, 2)).any())
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="speed-reverie", description="Gotta go fast (MI355X)")
     ap.add_argument("--operation", required=True, choices=["prove", "verify", "oneshot", "oneshot-zk", "version_info"])
@@ -87,6 +107,9 @@ def build_parser():
     ap.add_argument("--program-format", default="auto", choices=["auto", "bristol", "rvops", "mcircuit-bincode"])
     ap.add_argument("--expected-outputs-path")
     ap.add_argument("--strict", action="store_true", help="(default; kept for old command lines)")
+    ap.add_argument("--evaluator", default="auto", choices=["auto", "host", "gpu"],
+                    help="oneshot: evaluate on the host (GF(2) programs only) or on the GPU; auto = the GPU for programs with Z64 or "
+                         "B2A ops or at least %d ops" % GPU_EVAL_MIN_OPS)
     ap.add_argument("--reference-compat", action="store_true",
                     help="verify / oneshot-zk: RV_VERIFY_REFERENCE_COMPAT -- answer exactly like the reference's verifier, which "
                          "accepts proofs whose opened repetitions fail an AssertZero or name another omitted player than the "
@@ -110,7 +133,11 @@ def main(argv=None) -> int:
     prog, wc = load_program(a.program_path, a.program_format, a.expected_outputs_path)
     if a.operation == "oneshot":
         print("Evaluating program in cleartext")
-        evaluate_clear(prog, parse_witness(open(a.witness_path, "rb").read()))
+        wit = parse_witness(open(a.witness_path, "rb").read())
+        if use_gpu_evaluator(prog, a.evaluator):
+            evaluate_gpu(prog, wc, wit)
+        else:
+            evaluate_clear(prog, wit)
         print("()")
         return 0
     from .proof import Circuit, Proof

@@ -52,6 +52,10 @@ class StreamInfo(C.Structure):
                                           "peak_chunk_bytes", "hash_state_bytes", "proof_bytes")] + [("pass_", C.c_uint32), ("kept_mib", C.c_uint32)]
 
 
+class EvalStatus(C.Structure):  # rv_eval_status
+    _fields_ = [("n_failed", C.c_uint64), ("first_failed_op", C.c_uint64)]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8), ("calls", C.c_uint64)]
 
@@ -73,9 +77,11 @@ SYMBOLS = [
     "rv_stream_begin", "rv_stream_feed", "rv_stream_commit", "rv_stream_finish", "rv_stream_abort", "rv_stream_get_info", "rv_stream_same_cuts",
     "rv_prove_streaming", "rv_prove_ops", "rv_verify_ops", "rv_stream_verify_begin", "rv_stream_verify_finish", "rv_verify_streaming",
     "rv_comm_unique_id", "rv_comm_create", "rv_comm_create_all", "rv_comm_destroy", "rv_prove_sharded", "rv_prove_multi",
+    "rv_evaluate", "rv_evaluate_batch", "rv_hook_eval_schedules",
 ]
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1
+RV_COMPILE_KEEP_WIRES = 2  # the circuit keeps every wire's final value form: rv_evaluate can return wire values
 RV_VERIFY_REFERENCE_COMPAT = 2  # the reference verifier's two unchecked conditions stay unchecked
 
 _lib = None

@@ -651,7 +651,15 @@ struct rv_circuit {
     mutable std::once_flag ec_once;
     mutable EarlyPlan ec_plan;
     bool persist_gen = false;  // some level has enough multi-base Mul / Xor gates for the kernel variant with their loops (kernels.hip: level_is_general)
+    // rv_evaluate (eval.inc): the final wire forms (RV_COMPILE_KEEP_WIRES, uploaded with the circuit) and the Z64 level table (on the
+    // first evaluation; the provers do not read it)
+    bool keep_wires = false;
+    WireForm* d_wire_forms = nullptr;
+    uint32_t* d_wire_ssa64 = nullptr;
+    mutable std::mutex eval_mu;
+    mutable uint32_t* d_level_start64 = nullptr;
 };
+static int eval_upload_wires(rv_ctx* ctx, rv_circuit* c);
 
 // RV_Z64_FUSED: 1 (default) = the prover of eligible Z64 circuits runs its mask generator inside the interpreter's level launches
 // (internal.h: Z64FParams); 0 = masks to HBM first, k_interp64 behind.  Read at every call (tests switch it).
@@ -723,7 +731,7 @@ static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged = false)
 
 extern "C" int rv_circuit_compile_ex(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                                      rv_circuit** out) {
-    if (flags & ~RV_COMPILE_WHOLE_PROVER) return RV_E_ARG;
+    if (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES)) return RV_E_ARG;
     try {  // no C++ exception may cross the C boundary
         return rv_circuit_compile_impl(ctx, ops, n_ops, z64_wires, gf2_wires, flags, out);
     } catch (...) {
@@ -746,7 +754,9 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
     const auto t_begin = std::chrono::steady_clock::now();
     // RV_COMPILE_WHOLE_PROVER: lazy sums of up to RV_LIN_K rows for every circuit (the compiler chooses them on its own only
     // for deep, narrow ones); RV_LAZY_K still overrides
-    int rc = compile_ops(ops, n_ops, z64_wires, gf2_wires, c->cc, nullptr, ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0);
+    const bool keep = (flags & RV_COMPILE_KEEP_WIRES) != 0;
+    int rc = compile_ops(ops, n_ops, z64_wires, gf2_wires, c->cc, nullptr, ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0,
+                         keep);
     if (rc) {
         delete c;
         return rc;
@@ -757,6 +767,10 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
         fprintf(stderr, "[rv circuit] compile_ops: %.3f s for %zu ops\n", std::chrono::duration<double>(t_compiled - t_begin).count(),
                 n_ops);
     if ((rc = circuit_upload(ctx, c))) return rc;  // (destroys c on failure)
+    if (keep && (rc = eval_upload_wires(ctx, c))) {
+        rv_circuit_destroy(c);
+        return rc;
+    }
     if (getenv("RV_COMPILE_STATS"))
         fprintf(stderr, "[rv circuit] compiled + uploaded after %.3f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count());
     *out = c;
@@ -1024,6 +1038,9 @@ extern "C" void rv_circuit_destroy(rv_circuit* c) {
     c->ctx->release(c->d_level_start);
     c->ctx->release(c->d_level_range);
     c->ctx->release(c->d_lds_recs);
+    c->ctx->release(c->d_wire_forms);
+    c->ctx->release(c->d_wire_ssa64);
+    c->ctx->release(c->d_level_start64);
     // the early-corrections staging of a LARGE plan (2 GB of page-locked memory for the 10^6-MUL Z64 circuit) does not outlive the
     // circuit that needed it: a context that moves on to small circuits would otherwise hold it until rv_ctx_destroy.
     // Small stagings (the 160 MB of the 10^7-gate GF(2) circuit) stay: re-mapping them costs more than they weigh.
@@ -1090,12 +1107,13 @@ extern "C" int rv_hook_compile_info(const rv_op* ops, size_t n_ops, size_t z64_w
 }
 
 extern "C" int rv_hook_compile_compare(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, int threads, int* diff) {
-    if (!diff || (n_ops && !ops) || (flags & ~RV_COMPILE_WHOLE_PROVER) || threads < 2) return RV_E_ARG;
+    if (!diff || (n_ops && !ops) || (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES)) || threads < 2) return RV_E_ARG;
     try {
         const int k = ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0;
+        const bool keep = (flags & RV_COMPILE_KEEP_WIRES) != 0;
         Compiled a, b;
-        const int rc = compile_ops_seq(ops, n_ops, z64_wires, gf2_wires, a, nullptr, k);
-        const int rp = compile_ops_par(ops, n_ops, z64_wires, gf2_wires, b, k, threads);
+        const int rc = compile_ops_seq(ops, n_ops, z64_wires, gf2_wires, a, nullptr, k, keep);
+        const int rp = compile_ops_par(ops, n_ops, z64_wires, gf2_wires, b, k, threads, keep);
         if (rp == RV_COMPILE_FALLBACK)
             *diff = -1;
         else if (rp != rc)
@@ -1170,3 +1188,4 @@ extern "C" int rv_challenge(const uint8_t comm[RV_HASH_SIZE], uint8_t omit[RV_TO
 #include "hooks.inc"
 #include "stream.inc"
 #include "comm.inc"
+#include "eval.inc"

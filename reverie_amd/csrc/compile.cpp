@@ -50,6 +50,8 @@ struct Builder {
     std::vector<uint32_t> cur64;
     uint32_t max_level = 0;
     bool any = false;
+    bool keep_wires = false;  // RV_COMPILE_KEEP_WIRES: the wires' final values are live out of the program
+    uint64_t op_index = 0;    // the op being compiled (AssertZero table)
 
     Builder(Compiled& o, bool counting_, std::vector<uint32_t>& uses_, size_t size_hint = 0) : out(o), counting(counting_), uses(uses_) {
         if (!counting) {
@@ -151,6 +153,19 @@ struct Builder {
         emit(g, (uint32_t)lvl);
         out.info.gf2_linear++;
         return g.dst;
+    }
+
+    // The GF(2) wires live out of the op list (a streaming chunk writes them back, RV_COMPILE_KEEP_WIRES keeps their forms):
+    // f(w, ssa) for every wire w < n the program wrote (ssa = its last SSA id).  Pass 1 counts one more read of each: a final
+    // value is read after the program, so the XOR that produces it is not dead.
+    template <class F>
+    void live_out(size_t n, bool chunk, F f) {
+        for (size_t w = 0; w < n; w++) {
+            const uint32_t ssa = cur[w];
+            if (ssa == (chunk ? 1 + (uint32_t)w : 0u)) continue;  // never written (in this chunk)
+            use(ssa);
+            if (!counting) f((uint32_t)w, ssa);
+        }
     }
 
     // streaming chunk: the chunk's last level writes a wire's final value (a linear form) into its carried row
@@ -310,6 +325,10 @@ struct Builder {
         out.rec_rows.push_back(eo);
         const int32_t lvl = lin_level(lin[a]) + 1;
         uint32_t res = 0;
+        if (!recon) {
+            out.assert_rec2.push_back(x);
+            out.assert_op2.push_back(op_index);
+        }
         if (recon) {
             g.dst = COMP | n_comp++;  // {mask 0, corr = revealed value}
             out.n_random_or_recon++;
@@ -356,6 +375,7 @@ static int run_pass(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
     for (size_t i = 0; i < n_ops; i++) {
         const rv_op& op = ops[i];
         if (op.reserved != 0) return RV_E_BAD_OP;
+        b.op_index = i;
         switch (op.domain) {
         case RV_DOM_SIZEHINT:  // interpreter/combine.rs:122-129
             // (a streaming chunk's wire store was sized when the stream began: growing it mid-stream is not supported)
@@ -374,6 +394,7 @@ static int run_pass(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
             case RV_OP_RANDOM:
                 if (op.dst >= nw) return RV_E_WIRE_OOB;
                 b.cur[op.dst] = b.g_random();
+                out.n_user_random++;
                 break;
             case RV_OP_CONST:
                 if (op.dst >= nw) return RV_E_WIRE_OOB;
@@ -427,6 +448,7 @@ static int run_pass(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
             case RV_OP_RANDOM:
                 if (op.dst >= nw) return RV_E_WIRE_OOB;
                 g.op = G64_RANDOM;
+                out.n_user_random++;
                 g.m = (uint32_t)out.n_masks64++;
                 g.dst = b.new_ssa64(0);
                 b.cur64[op.dst] = g.dst;
@@ -490,6 +512,8 @@ static int run_pass(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
                 out.rec_offs64.push_back(g.eo);
                 out.on_words64 += 8;
                 g.x = (uint32_t)out.n_rec64++;
+                out.assert_rec64.push_back(g.x);
+                out.assert_op64.push_back(i);
                 const int32_t lvl = b.ssa_level64[g.a] + 1;
                 b.emit64(g, (uint32_t)lvl);
                 info.z64_asserts++;
@@ -555,17 +579,13 @@ static int run_pass(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
         // Write-back level.  A final form that still reads carried rows is materialised first: its write-back would
         // otherwise race with the write-back of the rows it reads (two wires swapped by the chunk).
         std::vector<std::pair<uint32_t, Lin>> wb;
-        for (size_t w = 0; w < gf2_wires; w++) {
-            const uint32_t ssa = b.cur[w];
-            if (ssa == 1 + (uint32_t)w) continue;  // never written in this chunk
-            b.use(ssa);                            // (pass 1: a wire that is live out is not dead)
-            if (b.counting) continue;
+        b.live_out(gf2_wires, true, [&](uint32_t w, uint32_t ssa) {
             Lin L = b.lin[ssa];
             bool reads_carry = false;
             for (int i = 0; i < L.n; i++) reads_carry |= (L.b[i] & CARRY) != 0;
             if (reads_carry) L = Builder::base(b.materialise(L.b, L.n, L.c));
-            wb.emplace_back((uint32_t)w, L);
-        }
+            wb.emplace_back(w, L);
+        });
         if (!b.counting) {
             const uint32_t last = b.any ? b.max_level + 1 : 0;
             for (const auto& e : wb) b.write_back(e.first, e.second, last);
@@ -579,6 +599,8 @@ static int run_pass(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
                 info.z64_linear++;
             }
         }
+    } else if (b.keep_wires) {
+        b.live_out(gf2_wires, false, [](uint32_t, uint32_t) {});  // (compile_ops_seq reads the forms)
     }
     return RV_OK;
 }
@@ -646,24 +668,27 @@ void relocate_chunk(Compiled& cc, uint64_t on0, uint64_t pre0, uint64_t on_words
     }
 }
 
-int compile_ops(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, Compiled& out, const ChunkStart* chunk, int force_lazy_k) {
+int compile_ops(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, Compiled& out, const ChunkStart* chunk, int force_lazy_k,
+                bool keep_wires) {
     const size_t par_min = getenv("RV_COMPILE_PAR_MIN") ? (size_t)atoll(getenv("RV_COMPILE_PAR_MIN")) : 200000;
     const bool seq = getenv("RV_COMPILE_SEQ") && atoi(getenv("RV_COMPILE_SEQ")) != 0;
     if (!chunk && !seq && n_ops >= par_min) {
         const int nt = compile_threads();
         if (nt > 1) {
             const auto t0 = std::chrono::steady_clock::now();
-            const int rc = compile_ops_par(ops, n_ops, z64_wires, gf2_wires, out, force_lazy_k, nt);
+            const int rc = compile_ops_par(ops, n_ops, z64_wires, gf2_wires, out, force_lazy_k, nt, keep_wires);
             if (getenv("RV_COMPILE_STATS"))
                 fprintf(stderr, "[rv compile] parallel compiler (%d threads) returned %d after %.3f s\n", nt, rc,
                         std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
             if (rc != RV_COMPILE_FALLBACK) return rc;
         }
     }
-    return compile_ops_seq(ops, n_ops, z64_wires, gf2_wires, out, chunk, force_lazy_k);
+    return compile_ops_seq(ops, n_ops, z64_wires, gf2_wires, out, chunk, force_lazy_k, keep_wires);
 }
 
-int compile_ops_seq(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, Compiled& out, const ChunkStart* chunk, int force_lazy_k) {
+int compile_ops_seq(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, Compiled& out, const ChunkStart* chunk, int force_lazy_k,
+                    bool keep_wires) {
+    if (chunk) keep_wires = false;  // (a chunk writes its wires back instead)
     const auto t0 = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (getenv("RV_COMPILE_STATS"))
@@ -678,6 +703,7 @@ int compile_ops_seq(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
         // pass 1: SSA numbering + read counts (the materialisation rule needs each wire's fan-out)
         Compiled scratch;
         Builder b1(scratch, true, uses);
+        b1.keep_wires = keep_wires;
         int rc = run_pass(ops, n_ops, z64_wires, gf2_wires, b1, chunk);
         if (rc) return rc;
     }
@@ -715,6 +741,7 @@ int compile_ops_seq(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
         bp->lazy_k = lazy_k;
         bp->lazy_slack = lazy_slack_for(lazy_k, forced);
         bp->balance = balance;
+        bp->keep_wires = keep_wires;
         int rc = run_pass(ops, n_ops, z64_wires, gf2_wires, *bp, chunk);
         if (rc) {
             delete bp;
@@ -852,6 +879,19 @@ int compile_ops_seq(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
             fix(g.a);
             g.m2 += base;
         }
+    if (keep_wires) {
+        out.wire_forms.resize(gf2_wires);
+        for (size_t w = 0; w < gf2_wires; w++) {
+            const Lin& L = b.lin[b.cur[w]];
+            WireForm& f = out.wire_forms[w];
+            for (int i = 0; i < K; i++) {
+                f.b[i] = i < L.n ? L.b[i] : ZERO_ROW;
+                fix(f.b[i]);
+            }
+            f.c = L.c;
+        }
+        out.wire_ssa64.assign(b.cur64.begin(), b.cur64.begin() + z64_wires);
+    }
     info.gf2_masks = out.n_masks;
     info.z64_masks = out.n_masks64;
     info.levels = n_levels;

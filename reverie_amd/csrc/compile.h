@@ -94,6 +94,14 @@ struct Compiled {
     // row numbering: [0, row_prg_base) carried wire rows (streaming chunks only), then the PRG mask rows, then the
     // computed rows; zero_row = the all-zero row (first computed row)
     uint64_t row_prg_base = 0, zero_row = 0;
+    // the AssertZero ops (always kept; host only): reconstruction ordinals (Gate::x / Gate64::x, in program order) and op-list indices
+    std::vector<uint32_t> assert_rec2, assert_rec64;
+    std::vector<uint64_t> assert_op2, assert_op64;
+    uint64_t n_user_random = 0;  // Random ops of the op list, both domains (B2A's own fresh masks not counted)
+    // RV_COMPILE_KEEP_WIRES (empty without it): the first gf2_wires / z64_wires wires' values at the end of the program (the
+    // wire counts passed to the compiler; a never-written wire reads as the zero row / Z64 SSA id 0)
+    std::vector<WireForm> wire_forms;
+    std::vector<uint32_t> wire_ssa64;
     rv_circuit_info info{};
 };
 
@@ -127,8 +135,10 @@ void relocate_chunk(Compiled& cc, uint64_t on0, uint64_t pre0, uint64_t on_words
 // Whole programs of RV_COMPILE_PAR_MIN ops and more (default 200 000) without B2A gates are compiled by several host threads
 // (compile_par.cpp; RV_COMPILE_THREADS, default min(16, hardware threads); RV_COMPILE_SEQ=1 turns it off); everything else,
 // and every program with an error in it, by the sequential compiler.  The result is the same bit for bit.
+// keep_wires: RV_COMPILE_KEEP_WIRES (whole programs only) -- every wire's final value is read once more after the program, so the
+// linear gates that produce one are not dropped as unread, and Compiled::wire_forms / wire_ssa64 are filled
 int compile_ops(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, Compiled& out, const ChunkStart* chunk = nullptr,
-                int force_lazy_k = 0);
+                int force_lazy_k = 0, bool keep_wires = false);
 // the sequential compiler (one thread; the reference implementation of the gate stream, the error path, streaming chunks)
 // Does keeping XORs of up to RV_LIN_K rows symbolic pay for this circuit?  Decided from its K = 1 compile: deep circuits whose
 // levels fit the narrow-run kernels (at most 256 gates on average) are bound by the number of dependency levels and of
@@ -144,10 +154,11 @@ inline uint32_t lazy_slack_for(int lazy_k, bool forced) {
 inline bool lazy_forms_pay(uint64_t n_levels, uint64_t n_gates) { return n_gates && n_levels > 64 && n_gates / n_levels < 256 && n_gates < 5000000; }
 
 int compile_ops_seq(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, Compiled& out, const ChunkStart* chunk = nullptr,
-                    int force_lazy_k = 0);
+                    int force_lazy_k = 0, bool keep_wires = false);
 // the parallel compiler: RV_OK, or RV_COMPILE_FALLBACK when the program is one it leaves to compile_ops_seq
 constexpr int RV_COMPILE_FALLBACK = -1;
-int compile_ops_par(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, Compiled& out, int force_lazy_k, int n_threads);
+int compile_ops_par(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, Compiled& out, int force_lazy_k, int n_threads,
+                    bool keep_wires = false);
 int compile_threads();
 unsigned cpu_budget();  // logical CPUs capped by the cgroup's CPU quota
 // 0 when the two compiled circuits are identical field by field, else a number naming the first difference (test hook)

@@ -87,6 +87,7 @@ struct Ctr {
     uint32_t ssa = 1, masks = 0, on = 0, pre = 0, rec = 0, in = 0;                               // GF(2)
     uint32_t ssa64 = 1, masks64 = 0, in64 = 0, rec64 = 0, corr64 = 0, gates64 = 0;              // Z64
     uint64_t onw64 = 0, prew64 = 0;
+    uint32_t random = 0;  // Random ops of both domains
     uint32_t gf2_linear_random = 0, gf2_inputs = 0, gf2_muls = 0, gf2_asserts = 0, z64_inputs = 0, z64_muls = 0, z64_asserts = 0, z64_linear = 0;
 };
 inline uint8_t make_kind(const rv_op& op) { return (uint8_t)(op.domain << 6 | op.opcode << 1 | (uint8_t)(op.imm & 1)); }
@@ -99,7 +100,7 @@ inline void advance(Ctr& c, uint8_t k) {
     if (k_dom(k) == RV_DOM_GF2) {
         switch (opc) {
         case RV_OP_INPUT: c.ssa++, c.masks++, c.on++, c.in++, c.gf2_inputs++; break;
-        case RV_OP_RANDOM: c.ssa++, c.masks++, c.gf2_linear_random++; break;
+        case RV_OP_RANDOM: c.ssa++, c.masks++, c.gf2_linear_random++, c.random++; break;
         case RV_OP_MUL: c.ssa++, c.masks += 2, c.on++, c.pre++, c.rec++, c.gf2_muls++; break;
         case RV_OP_ASSERTZERO: c.on++, c.rec++, c.gf2_asserts++; break;
         default: c.ssa++; break;  // Const, Add, Sub, AddConst, SubConst, MulConst
@@ -108,7 +109,7 @@ inline void advance(Ctr& c, uint8_t k) {
         c.gates64++;
         switch (opc) {
         case RV_OP_INPUT: c.ssa64++, c.masks64++, c.onw64 += 1, c.in64++, c.z64_inputs++; break;
-        case RV_OP_RANDOM: c.ssa64++, c.masks64++, c.z64_linear++; break;
+        case RV_OP_RANDOM: c.ssa64++, c.masks64++, c.z64_linear++, c.random++; break;
         case RV_OP_MUL: c.ssa64++, c.masks64 += 2, c.prew64 += 1, c.corr64++, c.onw64 += 8, c.rec64++, c.z64_muls++; break;
         case RV_OP_ASSERTZERO: c.onw64 += 8, c.rec64++, c.z64_asserts++; break;
         default: c.ssa64++, c.z64_linear++; break;
@@ -118,7 +119,7 @@ inline void advance(Ctr& c, uint8_t k) {
 inline void add_ctr(Ctr& a, const Ctr& d) {  // a += d where d was counted from a zero start (ssa / ssa64 start at 1: subtract it)
     a.ssa += d.ssa - 1, a.masks += d.masks, a.on += d.on, a.pre += d.pre, a.rec += d.rec, a.in += d.in;
     a.ssa64 += d.ssa64 - 1, a.masks64 += d.masks64, a.in64 += d.in64, a.rec64 += d.rec64, a.corr64 += d.corr64, a.gates64 += d.gates64;
-    a.onw64 += d.onw64, a.prew64 += d.prew64;
+    a.onw64 += d.onw64, a.prew64 += d.prew64, a.random += d.random;
     a.gf2_linear_random += d.gf2_linear_random, a.gf2_inputs += d.gf2_inputs, a.gf2_muls += d.gf2_muls, a.gf2_asserts += d.gf2_asserts;
     a.z64_inputs += d.z64_inputs, a.z64_muls += d.z64_muls, a.z64_asserts += d.z64_asserts, a.z64_linear += d.z64_linear;
 }
@@ -438,7 +439,8 @@ int compile_threads() {
     return (int)std::min(16u, cpu_budget());
 }
 
-int compile_ops_par(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, Compiled& out, int force_lazy_k, int n_threads) {
+int compile_ops_par(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, Compiled& out, int force_lazy_k, int n_threads,
+                    bool keep_wires) {
     const auto t_begin = std::chrono::steady_clock::now();
     const bool stats = getenv("RV_COMPILE_STATS") != nullptr;
     auto lap = [&](const char* what) {
@@ -692,6 +694,29 @@ int compile_ops_par(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
                 }
             });
         }
+    }
+    // RV_COMPILE_KEEP_WIRES: the wires' final SSA ids (the last range that writes a wire holds its last write), each read once
+    // more after the program (compile.cpp: Builder::live_out)
+    std::vector<uint32_t> fin2, fin64;
+    if (keep_wires) {
+        fin2.assign(gf2_wires, 0);
+        fin64.assign(z64_wires, 0);
+        pool.run([&](int t) {
+            size_t lo, hi;
+            Pool::slice(gf2_wires, t, T, lo, hi);
+            for (size_t w = lo; w < hi; w++) {
+                uint32_t v = 0;
+                for (int r = T1 - 1; r >= 0 && !v; r--) v = loc2[(size_t)r]->p[w];
+                fin2[w] = v;
+                use(v);
+            }
+            Pool::slice(z64_wires, t, T, lo, hi);
+            for (size_t w = lo; w < hi; w++) {
+                uint32_t v = 0;
+                for (int r = T1 - 1; r >= 0 && !v; r--) v = loc64[(size_t)r]->p[w];
+                fin64[w] = v;
+            }
+        });
     }
     loc2.clear();
     loc64.clear();
@@ -1060,6 +1085,11 @@ int compile_ops_par(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
     out.in_rows.resize(tot.in);
     out.rec_offs64.resize(tot.rec64);
     out.in_offs64.resize(tot.in64);
+    out.assert_rec2.resize(tot.gf2_asserts);
+    out.assert_op2.resize(tot.gf2_asserts);
+    out.assert_rec64.resize(tot.z64_asserts);
+    out.assert_op64.resize(tot.z64_asserts);
+    out.n_user_random = tot.random;
     Raw<uint32_t> row_level(std::max<uint32_t>(tot.on, 1));
     struct alignas(64) Info {
         uint64_t operand_rows = 0, rows_written = 0;
@@ -1123,6 +1153,8 @@ int compile_ops_par(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
                     g.op = G_ASSERT;
                     fill(lin[ra[i]], nullptr);
                     g.eo = c.on, g.x = c.rec;
+                    out.assert_rec2[c.gf2_asserts] = c.rec;
+                    out.assert_op2[c.gf2_asserts] = i;
                     out.rec_rows[c.rec] = c.on;
                     row_level[c.on] = lvl;
                     inf.operand_rows += g_na(g);
@@ -1174,6 +1206,8 @@ int compile_ops_par(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
                     break;
                 case RV_OP_ASSERTZERO:
                     g.op = G64_ASSERT, g.a = ra[i], g.eo = c.onw64, g.x = c.rec64;
+                    out.assert_rec64[c.z64_asserts] = c.rec64;
+                    out.assert_op64[c.z64_asserts] = i;
                     out.rec_offs64[c.rec64] = c.onw64;
                     break;
                 }
@@ -1186,6 +1220,20 @@ int compile_ops_par(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2
         infos[(size_t)r] = inf;
     });
     lap("pass 2b (gates at their sorted places)");
+    if (keep_wires) {
+        out.wire_forms.resize(gf2_wires);
+        pool.run([&](int t) {
+            size_t lo, hi;
+            Pool::slice(gf2_wires, t, T, lo, hi);
+            for (size_t w = lo; w < hi; w++) {
+                const LinP& L = lin[fin2[w]];
+                WireForm& f = out.wire_forms[w];
+                for (uint32_t q = 0; q < (uint32_t)K; q++) f.b[q] = fix(q < l_n(L) ? L.b[q] : ZERO_ROW);
+                f.c = l_c(L);
+            }
+        });
+        out.wire_ssa64 = std::move(fin64);
+    }
 
     // ---------------- pipelining tables (as compile_ops_seq) ----------------
     out.level_need_blocks.assign(n_levels, 0);
@@ -1247,6 +1295,10 @@ int compiled_diff(const Compiled& a, const Compiled& b) {
         a.n_in64 != b.n_in64 || a.n_rec64 != b.n_rec64 || a.n_corr64 != b.n_corr64 || a.row_prg_base != b.row_prg_base || a.zero_row != b.zero_row)
         return 13;
     if (memcmp(&a.info, &b.info, sizeof a.info) != 0) return 14;
+    if (!veq(a.assert_rec2, b.assert_rec2) || !veq(a.assert_op2, b.assert_op2) || !veq(a.assert_rec64, b.assert_rec64) ||
+        !veq(a.assert_op64, b.assert_op64) || a.n_user_random != b.n_user_random)
+        return 15;
+    if (!veq(a.wire_forms, b.wire_forms) || !veq(a.wire_ssa64, b.wire_ssa64)) return 16;
     return 0;
 }
 

@@ -1,0 +1,186 @@
+// rv_evaluate / rv_evaluate_batch: cleartext evaluation of a compiled circuit on a batch of witnesses (kernels: eval.hip).
+// Included by api.hip.
+
+// The schedule the evaluations ran: [0] one launch per level, [1] one walking workgroup per slice of witness words (rv_hook_eval_schedules)
+static std::atomic<uint64_t> g_eval_sched[2];
+
+// RV_COMPILE_KEEP_WIRES: the final wire forms to HBM (rv_circuit_compile_impl; c is destroyed by the caller on failure)
+static int eval_upload_wires(rv_ctx* ctx, rv_circuit* c) {
+    const Compiled& cc = c->cc;
+    c->keep_wires = true;
+    if (!cc.wire_forms.empty()) {
+        if (int rc = dalloc(ctx, cc.wire_forms.size(), &c->d_wire_forms)) return rc;
+        HIPCHK(hipMemcpyAsync(c->d_wire_forms, cc.wire_forms.data(), cc.wire_forms.size() * sizeof(WireForm), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (!cc.wire_ssa64.empty()) {
+        if (int rc = dalloc(ctx, cc.wire_ssa64.size(), &c->d_wire_ssa64)) return rc;
+        HIPCHK(hipMemcpyAsync(c->d_wire_ssa64, cc.wire_ssa64.data(), cc.wire_ssa64.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return RV_OK;
+}
+
+// Which schedule runs a circuit (DESIGN.md §13).  A level of a deep, narrow circuit (SHA-256, AES) is a few dozen gates: launched on
+// its own it costs the launch floor, so one workgroup per slice of witness words walks all levels instead, __syncthreads() between
+// them.  Wide levels (the 10^7-gate benchmark circuit: ~55 000 gates each) need the whole GPU: one launch per level.  The measure is
+// the work of an average level for one witness word: GF(2) gates plus 32 x Z64 gates (a Z64 gate takes a thread per witness).
+static bool eval_walks(const Compiled& cc) {
+    const uint64_t n_levels = cc.level_range.size();
+    if (n_levels < 2) return false;
+    return (cc.gates.size() + 32 * (uint64_t)cc.gates64.size()) / n_levels <= 2048;
+}
+
+// the op-list index of the AssertZero with reconstruction ordinal x (UINT64_MAX for none)
+static uint64_t eval_assert_op(const std::vector<uint32_t>& rec, const std::vector<uint64_t>& op, uint32_t x) {
+    if (x == UINT32_MAX) return UINT64_MAX;
+    const auto it = std::lower_bound(rec.begin(), rec.end(), x);
+    return (it != rec.end() && *it == x) ? op[(size_t)(it - rec.begin())] : UINT64_MAX;
+}
+
+// one part of a batch that fits in device memory
+static int eval_part(rv_ctx* ctx, const rv_circuit* c, size_t B, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64, size_t n_z64,
+                     uint8_t* gf2_values, uint64_t* z64_values, rv_eval_status* st) {
+    const Compiled& cc = c->cc;
+    const size_t W = (B + 31) / 32, n_in = cc.n_in, n_in64 = cc.n_in64;
+    const size_t nw2 = gf2_values ? cc.wire_forms.size() : 0, nw64 = z64_values ? cc.wire_ssa64.size() : 0;
+    // device: one block, 256-byte aligned parts
+    size_t off = 0;
+    auto part = [&](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t o_val = part(cc.n_rows * W * 4), o_win = part(n_in * W * 4), o_v64 = part(cc.n_ssa64 * B * 8);
+    auto r8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
+    const size_t in_wz = r8(B * n_in), in_bytes = in_wz + B * n_in64 * 8;  // [B][n_in] bytes, then [B][n_in64] words
+    const size_t o_in = part(in_bytes);
+    // n_failed, first2, first64 ([B] u32 each), then [B][nw2] bytes and [B][nw64] words
+    const size_t out2_at = r8(3 * B * 4), out64_at = r8(out2_at + B * nw2), out_bytes = out64_at + B * nw64 * 8;
+    const size_t o_out = part(out_bytes);
+    uint8_t* d = nullptr;
+    if (int rc = dalloc(ctx, off, &d)) return rc;
+    struct Release {
+        rv_ctx* ctx;
+        void* p;
+        ~Release() { ctx->release(p); }
+    } release{ctx, d};
+    // witnesses in through a page-locked slot (only the elements the Input gates consume)
+    int slot = -1;
+    uint8_t* h_in = ctx->open_slot(std::max<size_t>(in_bytes, 1), &slot);
+    if (!h_in) return RV_E_NOMEM;
+    for (size_t b = 0; b < B; b++) {
+        if (n_in) memcpy(h_in + b * n_in, wit_gf2 + b * n_gf2, n_in);
+        if (n_in64) memcpy(h_in + in_wz + b * n_in64 * 8, wit_z64 + b * n_z64, n_in64 * 8);
+    }
+    hipStream_t s = ctx->stream;
+    if (in_bytes) HIPCHK(hipMemcpyAsync(d + o_in, h_in, in_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(ctx->ev_open[slot], s));
+    EvalParams p{};
+    p.B = (uint32_t)B;
+    p.W = (uint32_t)W;
+    p.val = (uint32_t*)(d + o_val);
+    p.win = (const uint32_t*)(d + o_win);
+    p.v64 = (uint64_t*)(d + o_v64);
+    p.wz = (const uint64_t*)(d + o_in + in_wz);
+    p.wz_stride = n_in64;
+    p.n_failed = (uint32_t*)(d + o_out);
+    p.first2 = p.n_failed + B;
+    p.first64 = p.first2 + B;
+    HIPCHK(hipMemsetAsync(p.val + cc.zero_row * W, 0, W * 4, s));  // the zero row (never-written wires, unused operand slots)
+    HIPCHK(hipMemsetAsync(p.v64, 0, B * 8, s));                   // Z64 SSA id 0
+    HIPCHK(hipMemsetAsync(p.n_failed, 0, B * 4, s));
+    HIPCHK(hipMemsetAsync(p.first2, 0xFF, 2 * B * 4, s));
+    launch_eval_wit(s, d + o_in, (uint32_t)n_in, (uint32_t)B, (uint32_t)W, (uint32_t*)p.win);
+    const uint32_t n_levels = (uint32_t)cc.level_range.size();
+    if (eval_walks(cc)) {
+        const uint32_t* d_ls64 = nullptr;
+        if (!cc.gates64.empty()) {
+            std::lock_guard<std::mutex> lk(c->eval_mu);
+            if (!c->d_level_start64) {
+                uint32_t* t = nullptr;
+                if (int rc = dalloc(ctx, cc.level_start64.size(), &t)) return rc;
+                HIPCHK(hipMemcpyAsync(t, cc.level_start64.data(), cc.level_start64.size() * 4, hipMemcpyHostToDevice, s));
+                HIPCHK(hipStreamSynchronize(s));
+                c->d_level_start64 = t;
+            }
+            d_ls64 = c->d_level_start64;
+        }
+        // a slice of one witness word per workgroup (up to 256 workgroups; more words: wider slices)
+        const uint32_t S = (uint32_t)((W + 255) / 256);
+        const uint64_t per_level = (cc.gates.size() + 32 * (uint64_t)cc.gates64.size()) / n_levels * S;
+        launch_eval_walk(s, p, c->d_gates, c->d_level_range, c->d_gates64, d_ls64, n_levels, S, per_level <= 256 ? 256 : 1024);
+        g_eval_sched[1]++;
+    } else {
+        for (uint32_t l = 0; l < n_levels; l++) {
+            const LevelRange& r = cc.level_range[l];
+            const uint32_t lo64 = cc.gates64.empty() ? 0 : cc.level_start64[l], hi64 = cc.gates64.empty() ? 0 : cc.level_start64[l + 1];
+            launch_eval_level(s, p, c->d_gates, r.lo, r.hi - r.lo, c->d_gates64, lo64, hi64 - lo64);
+        }
+        g_eval_sched[0]++;
+    }
+    uint8_t* d_out2 = nw2 ? d + o_out + out2_at : nullptr;
+    uint64_t* d_out64 = nw64 ? (uint64_t*)(d + o_out + out64_at) : nullptr;
+    launch_eval_out(s, p, c->d_wire_forms, (uint32_t)nw2, c->d_wire_ssa64, (uint32_t)nw64, d_out2, d_out64);
+    HIPCHK(hipGetLastError());
+    int oslot = -1;
+    uint8_t* h_out = ctx->open_slot(out_bytes, &oslot);
+    if (!h_out) return RV_E_NOMEM;
+    HIPCHK(hipMemcpyAsync(h_out, d + o_out, out_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipEventRecord(ctx->ev_open[oslot], s));
+    HIPCHK(hipStreamSynchronize(s));
+    const uint32_t* nf = (const uint32_t*)h_out;
+    for (size_t b = 0; b < B; b++) {
+        st[b].n_failed = nf[b];
+        st[b].first_failed_op = std::min(eval_assert_op(cc.assert_rec2, cc.assert_op2, nf[B + b]), eval_assert_op(cc.assert_rec64, cc.assert_op64, nf[2 * B + b]));
+    }
+    if (nw2) memcpy(gf2_values, h_out + out2_at, B * nw2);
+    if (nw64) memcpy(z64_values, h_out + out64_at, B * nw64 * 8);
+    return RV_OK;
+}
+
+static int rv_evaluate_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
+                                  size_t n_z64, uint8_t* gf2_values, uint64_t* z64_values, rv_eval_status* st) {
+    LibBusy busy_guard;
+    if (!ctx || !c || !st || !batch) return RV_E_ARG;
+    const Compiled& cc = c->cc;
+    if ((gf2_values || z64_values) && !c->keep_wires) return RV_E_ARG;
+    if (cc.n_user_random) return RV_E_UNSUPPORTED;  // (a Random wire has no single cleartext value)
+    if (n_gf2 < cc.n_in || n_z64 < cc.n_in64) return RV_E_WITNESS_SHORT;
+    if ((cc.n_in && !wit_gf2) || (cc.n_in64 && !wit_z64)) return RV_E_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    // parts of what fits in half of the free device memory (as rv_prove_batch), whole witness words each
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return RV_E_DEVICE;
+    const size_t nw2 = gf2_values ? cc.wire_forms.size() : 0, nw64 = z64_values ? cc.wire_ssa64.size() : 0;
+    const size_t per32 = cc.n_rows * 4 + cc.n_in * 4 + 32 * (cc.n_ssa64 * 8 + cc.n_in + cc.n_in64 * 8 + 12 + nw2 + nw64 * 8);
+    const size_t part = std::max<size_t>((free_b + ctx->cached_bytes) / 2 / std::max<size_t>(per32, 1), 1) * 32;
+    for (size_t b0 = 0; b0 < batch; b0 += part) {
+        const size_t n = std::min(part, batch - b0);
+        const int rc = eval_part(ctx, c, n, wit_gf2 ? wit_gf2 + b0 * n_gf2 : nullptr, n_gf2, wit_z64 ? wit_z64 + b0 * n_z64 : nullptr, n_z64,
+                                 gf2_values ? gf2_values + b0 * nw2 : nullptr, z64_values ? z64_values + b0 * nw64 : nullptr, st + b0);
+        if (rc) return rc;
+    }
+    return RV_OK;
+}
+
+extern "C" int rv_evaluate_batch(rv_ctx* ctx, const rv_circuit* c, size_t batch, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
+                                 size_t n_z64, uint8_t* gf2_values, uint64_t* z64_values, rv_eval_status* st) {
+    try {
+        return rv_evaluate_batch_impl(ctx, c, batch, wit_gf2, n_gf2, wit_z64, n_z64, gf2_values, z64_values, st);
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}
+
+extern "C" int rv_evaluate(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64, size_t n_z64,
+                           uint8_t* gf2_values, uint64_t* z64_values, rv_eval_status* st) {
+    return rv_evaluate_batch(ctx, c, 1, wit_gf2, n_gf2, wit_z64, n_z64, gf2_values, z64_values, st);
+}
+
+extern "C" int rv_hook_eval_schedules(uint64_t out[2]) {
+    if (!out) return RV_E_ARG;
+    out[0] = g_eval_sched[0].load();
+    out[1] = g_eval_sched[1].load();
+    return RV_OK;
+}

@@ -138,6 +138,35 @@ struct InterpParams {
 void set_device_lds_limit(size_t bytes);
 size_t device_lds_limit();
 
+// Cleartext evaluation (eval.hip, eval.inc): `B` witnesses, GF(2) values bit-sliced across them
+struct EvalParams {
+    uint32_t B, W;           // witnesses, u32 words per GF(2) row (ceil(B / 32))
+    uint32_t* val;           // [n_rows][W]
+    const uint32_t* win;     // [n_in][W] the witnesses' input bits
+    uint64_t* v64;           // [n_ssa64][B]
+    const uint64_t* wz;      // [B][wz_stride] Z64 witness words
+    uint64_t wz_stride;
+    uint32_t* n_failed;      // [B] failing AssertZero gates
+    uint32_t* first2;        // [B] smallest reconstruction ordinal of a failing GF(2) AssertZero (UINT32_MAX: none)
+    uint32_t* first64;       // [B] ... of a failing Z64 AssertZero
+};
+// RV_COMPILE_KEEP_WIRES: the value form a GF(2) wire has at the end of the program -- XOR of the values of the share rows b[]
+// (unused slots: the zero row) plus the constant c
+struct WireForm {
+    uint32_t b[RV_LIN_K];
+    uint32_t c;
+};
+// schedule (a): one level, GF(2) gates [lo, lo + n2) and Z64 gates [lo64, lo64 + n64)
+void launch_eval_level(hipStream_t st, const EvalParams& p, const Gate* d_gates, uint32_t lo, uint32_t n2, const Gate64* d_gates64, uint32_t lo64,
+                       uint32_t n64);
+struct LevelRange;
+// schedule (b): one workgroup of `threads` per S witness words walks levels [0, n_levels); d_ls64 null: no Z64 gates
+void launch_eval_walk(hipStream_t st, const EvalParams& p, const Gate* d_gates, const LevelRange* d_lr, const Gate64* d_gates64, const uint32_t* d_ls64,
+                      uint32_t n_levels, uint32_t S, uint32_t threads);
+void launch_eval_wit(hipStream_t st, const uint8_t* d_wit /*[B][n]*/, uint32_t n, uint32_t B, uint32_t W, uint32_t* d_out /*[n][W]*/);
+void launch_eval_out(hipStream_t st, const EvalParams& p, const WireForm* d_forms, uint32_t n_gf2, const uint32_t* d_ssa64, uint32_t n_z64,
+                     uint8_t* d_out2 /*[B][n_gf2] or null*/, uint64_t* d_out64 /*[B][n_z64] or null*/);
+
 // ---- launchers (implemented in the .hip files) ----
 void launch_expand_seeds(hipStream_t st, const uint8_t* d_seeds, uint32_t n_reps, uint8_t* d_keys /*[n][8][16]*/);
 // Per AES key: the 11 round keys (176 bytes) followed by 32 bytes of first-round constants (k_key_schedule):

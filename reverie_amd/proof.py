@@ -60,16 +60,21 @@ class Context:
 class Circuit:
     """A gate stream compiled (levelised) and resident in HBM (rv_circuit)."""
 
-    def __init__(self, ops, wire_counts: Tuple[int, int], ctx: Optional[Context] = None, whole_prover: bool = False):
+    def __init__(self, ops, wire_counts: Tuple[int, int], ctx: Optional[Context] = None, whole_prover: bool = False,
+                 keep_wires: bool = False):
         """whole_prover: the circuit will mostly serve whole proofs on one GPU (Proof.new / new_batch) -- the
-        RV_COMPILE_WHOLE_PROVER hint of rv_circuit_compile_ex; any use of the circuit still gives identical bytes."""
+        RV_COMPILE_WHOLE_PROVER hint of rv_circuit_compile_ex; any use of the circuit still gives identical bytes.
+        keep_wires: RV_COMPILE_KEEP_WIRES -- the circuit keeps every wire's final value form, so that `evaluate` can return
+        wire values (proofs stay byte-identical)."""
         self.ctx = ctx or Context.default()
         self.ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
         self.wire_counts = (int(wire_counts[0]), int(wire_counts[1]))  # (z64, gf2), proof/mod.rs:125
+        self.keep_wires = bool(keep_wires)
         self.handle = C.c_void_p()
+        flags = (_lib.RV_COMPILE_WHOLE_PROVER if whole_prover else 0) | (_lib.RV_COMPILE_KEEP_WIRES if keep_wires else 0)
         _lib.check(_lib.lib().rv_circuit_compile_ex(self.ctx.handle, _ptr(self.ops), C.c_size_t(len(self.ops)),
                                                     C.c_size_t(self.wire_counts[0]), C.c_size_t(self.wire_counts[1]),
-                                                    C.c_uint32(_lib.RV_COMPILE_WHOLE_PROVER if whole_prover else 0), C.byref(self.handle)))
+                                                    C.c_uint32(flags), C.byref(self.handle)))
 
     @property
     def info(self) -> dict:
@@ -80,6 +85,42 @@ class Circuit:
         _lib.check(_lib.lib().rv_circuit_early_staging_bytes(self.handle, C.byref(esb)))
         d["early_staging_bytes"] = int(esb.value)
         return d
+
+    def evaluate(self, wit_gf2, wit_z64=()) -> "Evaluation":
+        """Cleartext evaluation on the GPU (rv_evaluate): `ok`, `n_failed`, `first_failed_op` (op-list index of the first
+        failing AssertZero, None if all hold) and, for a circuit compiled with keep_wires, the wires' final values `gf2`
+        (uint8, one per GF(2) wire) and `z64` (uint64).  A failing assertion is a result, not an error."""
+        g, z = _witness(wit_gf2, wit_z64)
+        st = _lib.EvalStatus()
+        gv = np.zeros(self.wire_counts[1], np.uint8) if self.keep_wires else None
+        zv = np.zeros(self.wire_counts[0], np.uint64) if self.keep_wires else None
+        _lib.check(_lib.lib().rv_evaluate(self.ctx.handle, self.handle, _ptr(g), C.c_size_t(len(g)), _ptr(z), C.c_size_t(len(z)),
+                                          _ptr(gv) if gv is not None else None, _ptr(zv) if zv is not None else None, C.byref(st)))
+        first = None if st.first_failed_op == 0xFFFFFFFFFFFFFFFF else int(st.first_failed_op)
+        return Evaluation(st.n_failed == 0, int(st.n_failed), first, gv, zv)
+
+    def evaluate_batch(self, wits_gf2, wits_z64=None, values: bool = False) -> "Evaluation":
+        """rv_evaluate_batch: `len(wits_gf2)` witnesses ([B][n] bits; wits_z64 [B][m] words or None) in one pass.  Returns
+        arrays: `ok` (bool [B]), `n_failed` ([B]), `first_failed_op` ([B] int64, -1 where every assertion holds) and, with
+        values=True (needs keep_wires), `gf2` ([B][gf2_wires] uint8) and `z64` ([B][z64_wires] uint64).  Witness b's results
+        equal evaluate(wits_gf2[b], wits_z64[b])."""
+        g = np.ascontiguousarray(np.asarray(wits_gf2, dtype=np.uint8))
+        if g.ndim != 2:
+            raise ValueError("wits_gf2 must be [batch][n_bits]")
+        batch = g.shape[0]
+        z = np.ascontiguousarray(np.asarray(wits_z64 if wits_z64 is not None else np.zeros((batch, 0)), dtype=np.uint64))
+        if z.ndim != 2 or z.shape[0] != batch:
+            raise ValueError("wits_z64 must be [batch][n_words]")
+        st = np.zeros((max(batch, 1), 2), np.uint64)
+        gv = np.zeros((batch, self.wire_counts[1]), np.uint8) if values else None
+        zv = np.zeros((batch, self.wire_counts[0]), np.uint64) if values else None
+        if batch:
+            _lib.check(_lib.lib().rv_evaluate_batch(self.ctx.handle, self.handle, C.c_size_t(batch), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z),
+                                                    C.c_size_t(z.shape[1]), _ptr(gv) if values else None, _ptr(zv) if values else None,
+                                                    st.ctypes.data_as(C.c_void_p)))
+        st = st[:batch]
+        n_failed = st[:, 0].astype(np.int64)
+        return Evaluation(n_failed == 0, n_failed, st[:, 1].view(np.int64).copy(), gv, zv)
 
     def record_sizes(self) -> Tuple[int, int]:
         """bytes of one OpenOnline record in the gf2 / z64 section of a proof of this circuit"""
@@ -98,6 +139,32 @@ class Circuit:
             self.close()
         except Exception:
             pass
+
+
+class Evaluation:
+    """What Circuit.evaluate / evaluate_batch return (scalars for one witness, arrays for a batch)."""
+
+    def __init__(self, ok, n_failed, first_failed_op, gf2=None, z64=None):
+        self.ok, self.n_failed, self.first_failed_op, self.gf2, self.z64 = ok, n_failed, first_failed_op, gf2, z64
+
+    def __repr__(self):
+        return f"Evaluation(ok={self.ok!r}, n_failed={self.n_failed!r}, first_failed_op={self.first_failed_op!r})"
+
+
+def evaluate_composite_program(ops, wit_gf2, wit_z64=(), wire_counts=None, ctx: Optional[Context] = None):
+    """mcircuit::evaluate_composite_program, which the reference re-exports (src/lib.rs:6) and its CLI's `oneshot` calls
+    (src/main.rs:115-132): the op list evaluated in the clear on the witness -> (gf2, z64) wire vectors (uint8 / uint64) at the
+    end of the program.  Raises ValueError naming the op index of the first AssertZero that does not hold.  The crate's exact
+    signature and return type cannot be checked here (it is not vendored); this is the evaluation it names, on the
+    GPU (rv_evaluate).  wire_counts (z64, gf2) defaults to largest_wires(ops)."""
+    from .ops import largest_wires
+
+    prog = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+    wc = tuple(wire_counts) if wire_counts is not None else largest_wires(prog)
+    r = Circuit(prog, wc, ctx, keep_wires=True).evaluate(wit_gf2, wit_z64)
+    if not r.ok:
+        raise ValueError(f"AssertZero at op {r.first_failed_op} does not hold ({r.n_failed} failing assertions)")
+    return r.gf2, r.z64
 
 
 def _as_circuit(circuit, wire_counts, ctx=None, whole_prover=False) -> Circuit:
