@@ -64,6 +64,8 @@ static int eval_part(rv_ctx* ctx, const rv_circuit* c, size_t B, const uint8_t* 
         void* p;
         ~Release() { ctx->release(p); }
     } release{ctx, d};
+    // RV_EVAL_POISON=1 (tests): the block starts non-zero, so that a row read before anything writes it shows (read at every call)
+    if (getenv("RV_EVAL_POISON") && atoi(getenv("RV_EVAL_POISON"))) HIPCHK(hipMemsetAsync(d, 0xA5, off, ctx->stream));
     // witnesses in through a page-locked slot (only the elements the Input gates consume)
     int slot = -1;
     uint8_t* h_in = ctx->open_slot(std::max<size_t>(in_bytes, 1), &slot);
@@ -153,7 +155,9 @@ static int rv_evaluate_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return RV_E_DEVICE;
     const size_t nw2 = gf2_values ? cc.wire_forms.size() : 0, nw64 = z64_values ? cc.wire_ssa64.size() : 0;
     const size_t per32 = cc.n_rows * 4 + cc.n_in * 4 + 32 * (cc.n_ssa64 * 8 + cc.n_in + cc.n_in64 * 8 + 12 + nw2 + nw64 * 8);
-    const size_t part = std::max<size_t>((free_b + ctx->cached_bytes) / 2 / std::max<size_t>(per32, 1), 1) * 32;
+    size_t part = std::max<size_t>((free_b + ctx->cached_bytes) / 2 / std::max<size_t>(per32, 1), 1) * 32;
+    // RV_EVAL_PART=n (tests): parts of at most n witnesses, rounded up to whole words (read at every call)
+    if (const char* e = getenv("RV_EVAL_PART")) part = std::min(part, ((size_t)std::max(atoll(e), 1LL) + 31) / 32 * 32);
     for (size_t b0 = 0; b0 < batch; b0 += part) {
         const size_t n = std::min(part, batch - b0);
         const int rc = eval_part(ctx, c, n, wit_gf2 ? wit_gf2 + b0 * n_gf2 : nullptr, n_gf2, wit_z64 ? wit_z64 + b0 * n_z64 : nullptr, n_z64,

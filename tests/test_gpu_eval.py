@@ -9,6 +9,7 @@ import pytest
 
 import bristol_gen
 import circuits
+import eval_ref
 from conftest import golden_matches
 from reverie_amd.ops import B2A, GF2, OP_DTYPE, Z64, SizeHint, program
 
@@ -205,6 +206,10 @@ def test_batches_equal_single_calls(rv, B):
             assert np.array_equal(r.gf2[k], one.gf2) and np.array_equal(r.z64[k], one.z64)
         plain = c.evaluate_batch(w2, w64)
         assert np.array_equal(plain.ok, r.ok) and plain.gf2 is None
+        # every output against the independent reference (the wide circuit layer by layer)
+        g, z, nf, ff = (eval_ref.evaluate_layers if prog is wide else eval_ref.evaluate)(prog, wc, w2, w64)
+        assert np.array_equal(r.n_failed, nf) and np.array_equal(r.first_failed_op, ff)
+        assert np.array_equal(r.gf2, g) and np.array_equal(r.z64, z)
     s1 = schedules()
     assert s1[0] > s0[0] and s1[1] > s0[1]  # both schedules ran
 
@@ -268,6 +273,8 @@ def test_config4_full_size(rv, oracle):
     for w in rng.choice(wc[1], 2, replace=False):
         og, _ = oracle.group_wire_values(prog, wit, [], wc, ZERO8, gf2_wire=int(w))
         assert og == (ONE if r.gf2[w] else 0)
+    g, _z, nf, _ff = eval_ref.evaluate_layers(prog, wc, wit)  # (every wire)
+    assert nf[0] == 0 and np.array_equal(r.gf2, g[0])
 
 
 # ---------------------------------------------------------------- 6. proofs of keep_wires circuits, errors
@@ -276,8 +283,9 @@ def test_keep_wires_proofs_are_golden(rv, oracle, rule_seeds):
 
     for name in tp.ALL_GOLDEN:
         m, prog, w2, w64, wc, _gold = tp.load_case(name)
-        c = rv.Circuit(prog, wc, keep_wires=True)
-        assert golden_matches(oracle, name, m, bytes(rv.Proof.new(c, w2, w64, seeds=rule_seeds))), name
+        for whole_prover in (False, True):  # (whole_prover: lazy forms of up to RV_LIN_K rows)
+            c = rv.Circuit(prog, wc, whole_prover=whole_prover, keep_wires=True)
+            assert golden_matches(oracle, name, m, bytes(rv.Proof.new(c, w2, w64, seeds=rule_seeds))), (name, whole_prover)
 
 
 def test_errors(rv):
