@@ -254,6 +254,41 @@ int rv_evaluate(rv_ctx *ctx, const rv_circuit *c, const uint8_t *wit_gf2, size_t
 int rv_evaluate_batch(rv_ctx *ctx, const rv_circuit *c, size_t batch, const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64,
                       size_t n_z64, uint8_t *gf2_values, uint64_t *z64_values, rv_eval_status *st);
 
+/* ---- cleartext evaluation of a gate stream with bounded device memory (the streaming evaluator) ----
+ * rv_evaluate_batch over an op list fed in pieces, as the streaming prover takes it: no compiled circuit, no keep-wires flag.
+ *     rv_eval_stream_begin(ctx, z64_wires, gf2_wires, batch, max_chunk_ops, &s)
+ *     rv_eval_stream_feed(s, ops_0, ...) ... rv_eval_stream_feed(s, ops_k, ...)
+ *     rv_eval_stream_finish(s, gf2_values, z64_values, st)
+ *     rv_eval_stream_abort(s)             releases the stream (also after a finish or an error)
+ * A feed carries, for each witness b of the batch, the witness elements its Input gates consume, in order, at wit_gf2 + b*n_gf2 and
+ * wit_z64 + b*n_z64 (more may be passed; RV_E_WITNESS_SHORT if fewer).  A feed longer than max_chunk_ops (0 = 2^18) is cut into
+ * device chunks as rv_stream_feed cuts it.  A Random op gives RV_E_UNSUPPORTED (as rv_evaluate), and so does a SizeHint that grows
+ * the wire counts given at begin (as rv_stream_feed); compile errors keep their codes (RV_E_WIRE_OOB, RV_E_BAD_OP).  After an error
+ * the stream only accepts rv_eval_stream_abort.  A feed returns without waiting for the GPU.
+ * finish: st[b] is what rv_evaluate_batch returns for witness b and the concatenated op list -- n_failed counts the failing
+ * AssertZero ops of all chunks, first_failed_op is the index in the whole op list of the first one in program order (both domains;
+ * a failing assertion is a result, not an error).  gf2_values ([batch][gf2_wires] bytes 0/1) and z64_values ([batch][z64_wires])
+ * are nullable and receive every wire's final value; a wire that is never written reads 0.  finish may be called once.
+ * Device memory: the wire store -- gf2_wires * ceil(batch/32) * 4 + (1 + z64_wires) * batch * 8 bytes plus 28 status bytes per
+ * witness -- and one chunk, independent of the number of ops.  A wire store larger than half of the free device memory gives
+ * RV_E_NOMEM at begin, before anything is allocated (the batch is not split: run several streams). */
+typedef struct rv_eval_stream rv_eval_stream;
+typedef struct rv_eval_stream_info {
+    uint64_t n_ops, chunks, levels;
+    uint64_t wire_store_bytes;  /* HBM held for the carried wires (and status words) of all witnesses */
+    uint64_t peak_chunk_bytes;  /* largest chunk's working set (rows, SSA slots, gate records, witness words) */
+} rv_eval_stream_info;
+int rv_eval_stream_begin(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, size_t batch, size_t max_chunk_ops, rv_eval_stream **out);
+int rv_eval_stream_feed(rv_eval_stream *s, const rv_op *ops, size_t n_ops, const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64,
+                        size_t n_z64);
+int rv_eval_stream_finish(rv_eval_stream *s, uint8_t *gf2_values, uint64_t *z64_values, rv_eval_status *st);
+int rv_eval_stream_get_info(const rv_eval_stream *s, rv_eval_stream_info *info);
+void rv_eval_stream_abort(rv_eval_stream *s);
+/* begin + one feed of an op array that already sits in host memory + finish; info (nullable): the stream's final figures */
+int rv_evaluate_streaming(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, size_t batch,
+                          const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64, size_t n_z64, size_t max_chunk_ops,
+                          uint8_t *gf2_values, uint64_t *z64_values, rv_eval_status *st, rv_eval_stream_info *info);
+
 /* ---- Proof::verify ----------------------------------------------------------------
  * Verification is STRICT by default (flags 0, rv_verify): on top of the reference's check (*ok = 0 when a ProofSingle
  * has the wrong number of repetitions or the recomputed commitment differs) it closes the two soundness gaps of the
@@ -550,8 +585,9 @@ uint64_t rv_hook_overlap_commits(void);
  * reference's: verifier/online.rs:122-183 computes the same values).  The answer is the same either way; the tests use the
  * counter to know which path they compared.  RV_VERIFY_VC=0 turns the path off. */
 uint64_t rv_hook_verify_vc_count(void);
-/* How often this process's evaluations (rv_evaluate, rv_evaluate_batch) ran each schedule: out[0] = one launch per dependency level,
- * out[1] = one workgroup per slice of witness words walking every level (csrc/eval.hip).  The results are the same either way. */
+/* How often this process's evaluations (rv_evaluate, rv_evaluate_batch; the streaming evaluator once per chunk) ran each schedule:
+ * out[0] = one launch per dependency level, out[1] = one workgroup per slice of witness words walking every level (csrc/eval.hip).
+ * The results are the same either way. */
 int rv_hook_eval_schedules(uint64_t out[2]);
 /* The early-corrections plan of a program (host only, no device): the ops are compiled as rv_circuit_compile_ex(flags) would and
  * the plan rv_prove would use is built and checked against the compiled gate records.  out[0] = a plan exists (0 / 1: the circuit

@@ -88,6 +88,49 @@ def evaluate_gpu(prog, wc, witness):
         raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (r.first_failed_op, r.n_failed))
 
 
+def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops):
+    """`oneshot --evaluator stream`: the program evaluated in pieces with bounded device memory (rv_eval_stream_*), on the GPU like
+    --evaluator gpu and with the same outcome.  An rvops file is read through a memory map, piece by piece; its wire counts come from
+    one pass over the mapping."""
+    from .stream import StreamingEvaluator
+
+    if fmt == "auto":
+        fmt = "rvops" if program_path.endswith(".rvops") else "bristol"
+    wit = np.ascontiguousarray(np.asarray(witness, dtype=np.uint8))
+    if fmt != "rvops":
+        prog, wc = load_program(program_path, fmt, expected_path)
+        pieces, n = [prog], len(prog)
+    else:
+        import os
+
+        size = os.path.getsize(program_path)
+        if size % OP_DTYPE.itemsize:
+            raise SystemExit("program file is not a whole number of 24-byte rv_op records")
+        n = size // OP_DTYPE.itemsize
+        prog = np.memmap(program_path, dtype=OP_DTYPE, mode="r", shape=(n,)) if n else np.zeros(0, OP_DTYPE)
+        step = STREAM_FEED_OPS
+        z64 = gf2 = 0
+        for at in range(0, n, step):
+            z, g = largest_wires(np.asarray(prog[at:at + step]))
+            z64, gf2 = max(z64, z), max(gf2, g)
+        wc = (z64, gf2)
+        pieces = (np.asarray(prog[at:at + step]) for at in range(0, n, step))
+    se = StreamingEvaluator(wc, 1, max_chunk_ops)
+    try:
+        used = 0
+        for piece in pieces:
+            se.feed(piece, wit[used:])  # (the CLI's witness is GF(2) bits: a piece consumes one per GF(2) Input op)
+            used += int(np.count_nonzero((piece["domain"] == 0) & (piece["opcode"] == 0)))
+        r = se.finish()
+    finally:
+        se.close()
+    if not r.ok[0]:
+        raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (r.first_failed_op[0], r.n_failed[0]))
+
+
+# --evaluator stream: an rvops file is fed in pieces of this many ops (the evaluator cuts them into chunks of --max-chunk-ops)
+STREAM_FEED_OPS = 1 << 22
+
 # --evaluator auto: programs from this many ops on (and every program with Z64 or B2A ops) are evaluated on the GPU
 GPU_EVAL_MIN_OPS = 100_000
 
@@ -107,9 +150,12 @@ def build_parser():
     ap.add_argument("--program-format", default="auto", choices=["auto", "bristol", "rvops", "mcircuit-bincode"])
     ap.add_argument("--expected-outputs-path")
     ap.add_argument("--strict", action="store_true", help="(default; kept for old command lines)")
-    ap.add_argument("--evaluator", default="auto", choices=["auto", "host", "gpu"],
+    ap.add_argument("--evaluator", default="auto", choices=["auto", "host", "gpu", "stream"],
                     help="oneshot: evaluate on the host (GF(2) programs only) or on the GPU; auto = the GPU for programs with Z64 or "
-                         "B2A ops or at least %d ops" % GPU_EVAL_MIN_OPS)
+                         "B2A ops or at least %d ops; stream = on the GPU in pieces, with device memory bounded by the wire counts "
+                         "and one chunk (an rvops file is read piece by piece)" % GPU_EVAL_MIN_OPS)
+    ap.add_argument("--max-chunk-ops", type=int, default=0,
+                    help="oneshot --evaluator stream: ops per device chunk (0 = the library's default, 2^18)")
     ap.add_argument("--reference-compat", action="store_true",
                     help="verify / oneshot-zk: RV_VERIFY_REFERENCE_COMPAT -- answer exactly like the reference's verifier, which "
                          "accepts proofs whose opened repetitions fail an AssertZero or name another omitted player than the "
@@ -129,6 +175,12 @@ def main(argv=None) -> int:
         from . import _lib
 
         print("reverie_version: speed-reverie (reverie_amd, C-ABI v%d, drop-in for reverie-zk 0.3.2)" % _lib.lib().rv_abi_version())
+        return 0
+    if a.operation == "oneshot" and a.evaluator == "stream":
+        print("Evaluating program in cleartext")
+        evaluate_stream(a.program_path, a.program_format, a.expected_outputs_path, parse_witness(open(a.witness_path, "rb").read()),
+                        a.max_chunk_ops)
+        print("()")
         return 0
     prog, wc = load_program(a.program_path, a.program_format, a.expected_outputs_path)
     if a.operation == "oneshot":

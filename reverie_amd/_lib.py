@@ -56,6 +56,10 @@ class EvalStatus(C.Structure):  # rv_eval_status
     _fields_ = [("n_failed", C.c_uint64), ("first_failed_op", C.c_uint64)]
 
 
+class EvalStreamInfo(C.Structure):  # rv_eval_stream_info
+    _fields_ = [(n, C.c_uint64) for n in ("n_ops", "chunks", "levels", "wire_store_bytes", "peak_chunk_bytes")]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8), ("calls", C.c_uint64)]
 
@@ -78,6 +82,8 @@ SYMBOLS = [
     "rv_prove_streaming", "rv_prove_ops", "rv_verify_ops", "rv_stream_verify_begin", "rv_stream_verify_finish", "rv_verify_streaming",
     "rv_comm_unique_id", "rv_comm_create", "rv_comm_create_all", "rv_comm_destroy", "rv_prove_sharded", "rv_prove_multi",
     "rv_evaluate", "rv_evaluate_batch", "rv_hook_eval_schedules",
+    "rv_eval_stream_begin", "rv_eval_stream_feed", "rv_eval_stream_finish", "rv_eval_stream_get_info", "rv_eval_stream_abort",
+    "rv_evaluate_streaming",
 ]
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1
@@ -125,7 +131,8 @@ def lib():
         L.rv_abi_version.restype = C.c_uint32
         for name in SYMBOLS:
             fn = getattr(L, name)
-            if name in ("rv_ctx_destroy", "rv_circuit_destroy", "rv_shard_destroy", "rv_free", "rv_stream_abort", "rv_comm_destroy"):
+            if name in ("rv_ctx_destroy", "rv_circuit_destroy", "rv_shard_destroy", "rv_free", "rv_stream_abort", "rv_comm_destroy",
+                        "rv_eval_stream_abort"):
                 fn.restype = None
             elif name in ("rv_hook_early_proofs", "rv_hook_open_direct_proofs", "rv_hook_verify_vc_count", "rv_hook_ops_cache_hits", "rv_hook_overlap_commits"):
                 fn.restype = C.c_uint64

@@ -1189,3 +1189,4 @@ extern "C" int rv_challenge(const uint8_t comm[RV_HASH_SIZE], uint8_t omit[RV_TO
 #include "stream.inc"
 #include "comm.inc"
 #include "eval.inc"
+#include "eval_stream.inc"

@@ -160,6 +160,48 @@ __global__ __launch_bounds__(256) void k_eval_out(EvalParams p, const WireForm* 
     }
 }
 
+// the op-list index of the AssertZero with reconstruction ordinal x: binary search in the chunk's ordinal table (UINT64_MAX: none)
+__device__ __forceinline__ uint64_t ev_assert_op(const uint32_t* rec, const uint64_t* op, uint32_t n, uint32_t x) {
+    if (x == UINT32_MAX) return UINT64_MAX;
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (rec[mid] < x)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return (lo < n && rec[lo] == x) ? op[lo] : UINT64_MAX;
+}
+
+// streaming evaluation, once per chunk, one thread per witness: the chunk's first failing assertion (the smaller op index of the two
+// domains) becomes the stream's if it has none yet -- earlier chunks come first in program order -- and the chunk's count is added
+__global__ __launch_bounds__(256) void k_eval_fold(EvalParams p, EvalFold f) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= p.B) return;
+    const uint64_t x = min(ev_assert_op(f.rec2, f.op2, f.n2, p.first2[b]), ev_assert_op(f.rec64, f.op64, f.n64, p.first64[b]));
+    if (x != UINT64_MAX && f.first_op[b] == UINT64_MAX) f.first_op[b] = f.op_base + x;
+    f.total[b] += p.n_failed[b];
+    p.n_failed[b] = 0;
+    p.first2[b] = UINT32_MAX;
+    p.first64[b] = UINT32_MAX;
+}
+
+// streaming evaluation: the carried wires' values of witnesses [b0, b0 + nb) -> [nb][n_gf2] bytes and [nb][n_z64] words
+__global__ __launch_bounds__(256) void k_eval_stream_out(EvalParams p, uint32_t n_gf2, uint32_t n_z64, uint32_t b0, uint32_t nb,
+                                                         uint8_t* __restrict__ out2, uint64_t* __restrict__ out64) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t t2 = out2 ? (uint64_t)n_gf2 * nb : 0;
+    if (t < t2) {
+        const uint32_t b = b0 + (uint32_t)(t / n_gf2), w = (uint32_t)(t % n_gf2);
+        out2[t] = (uint8_t)((p.val[(size_t)w * p.W + (b >> 5)] >> (b & 31)) & 1u);
+    } else if (out64 && t - t2 < (uint64_t)n_z64 * nb) {
+        const uint64_t u = t - t2;
+        const uint32_t b = b0 + (uint32_t)(u / n_z64), w = (uint32_t)(u % n_z64);
+        out64[u] = p.v64[(size_t)(1 + w) * p.B + b];
+    }
+}
+
 inline unsigned blocks_for(uint64_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
 }  // namespace
@@ -187,6 +229,17 @@ void launch_eval_out(hipStream_t st, const EvalParams& p, const WireForm* d_form
     const uint64_t t = (d_out2 ? (uint64_t)n_gf2 * p.B : 0) + (d_out64 ? (uint64_t)n_z64 * p.B : 0);
     if (!t) return;
     hipLaunchKernelGGL(k_eval_out, dim3(blocks_for(t, 256)), dim3(256), 0, st, p, d_forms, n_gf2, d_ssa64, n_z64, d_out2, d_out64);
+}
+
+void launch_eval_fold(hipStream_t st, const EvalParams& p, const EvalFold& f) {
+    hipLaunchKernelGGL(k_eval_fold, dim3(blocks_for(p.B, 256)), dim3(256), 0, st, p, f);
+}
+
+void launch_eval_stream_out(hipStream_t st, const EvalParams& p, uint32_t n_gf2, uint32_t n_z64, uint32_t b0, uint32_t nb, uint8_t* d_out2,
+                            uint64_t* d_out64) {
+    const uint64_t t = (d_out2 ? (uint64_t)n_gf2 * nb : 0) + (d_out64 ? (uint64_t)n_z64 * nb : 0);
+    if (!t) return;
+    hipLaunchKernelGGL(k_eval_stream_out, dim3(blocks_for(t, 256)), dim3(256), 0, st, p, n_gf2, n_z64, b0, nb, d_out2, d_out64);
 }
 
 }  // namespace rv

@@ -30,6 +30,28 @@ static bool eval_walks(const Compiled& cc) {
     return (cc.gates.size() + 32 * (uint64_t)cc.gates64.size()) / n_levels <= 2048;
 }
 
+// The gate levels of a compiled circuit (eval_part) or streaming chunk (eval_stream.inc) on the values of p, by the schedule
+// eval_walks chooses (counted in g_eval_sched).  d_ls64: the Z64 level table on the device -- needed when the circuit walks
+// and has Z64 gates, else unread.
+static void eval_run_levels(hipStream_t s, const EvalParams& p, const Compiled& cc, const Gate* d_gates, const LevelRange* d_lr,
+                            const Gate64* d_gates64, const uint32_t* d_ls64) {
+    const uint32_t n_levels = (uint32_t)cc.level_range.size();
+    if (eval_walks(cc)) {
+        // a slice of one witness word per workgroup (up to 256 workgroups; more words: wider slices)
+        const uint32_t S = (uint32_t)((p.W + 255) / 256);
+        const uint64_t per_level = (cc.gates.size() + 32 * (uint64_t)cc.gates64.size()) / n_levels * S;
+        launch_eval_walk(s, p, d_gates, d_lr, d_gates64, cc.gates64.empty() ? nullptr : d_ls64, n_levels, S, per_level <= 256 ? 256 : 1024);
+        g_eval_sched[1]++;
+    } else {
+        for (uint32_t l = 0; l < n_levels; l++) {
+            const LevelRange& r = cc.level_range[l];
+            const uint32_t lo64 = cc.gates64.empty() ? 0 : cc.level_start64[l], hi64 = cc.gates64.empty() ? 0 : cc.level_start64[l + 1];
+            launch_eval_level(s, p, d_gates, r.lo, r.hi - r.lo, d_gates64, lo64, hi64 - lo64);
+        }
+        g_eval_sched[0]++;
+    }
+}
+
 // the op-list index of the AssertZero with reconstruction ordinal x (UINT64_MAX for none)
 static uint64_t eval_assert_op(const std::vector<uint32_t>& rec, const std::vector<uint64_t>& op, uint32_t x) {
     if (x == UINT32_MAX) return UINT64_MAX;
@@ -93,33 +115,19 @@ static int eval_part(rv_ctx* ctx, const rv_circuit* c, size_t B, const uint8_t* 
     HIPCHK(hipMemsetAsync(p.n_failed, 0, B * 4, s));
     HIPCHK(hipMemsetAsync(p.first2, 0xFF, 2 * B * 4, s));
     launch_eval_wit(s, d + o_in, (uint32_t)n_in, (uint32_t)B, (uint32_t)W, (uint32_t*)p.win);
-    const uint32_t n_levels = (uint32_t)cc.level_range.size();
-    if (eval_walks(cc)) {
-        const uint32_t* d_ls64 = nullptr;
-        if (!cc.gates64.empty()) {
-            std::lock_guard<std::mutex> lk(c->eval_mu);
-            if (!c->d_level_start64) {
-                uint32_t* t = nullptr;
-                if (int rc = dalloc(ctx, cc.level_start64.size(), &t)) return rc;
-                HIPCHK(hipMemcpyAsync(t, cc.level_start64.data(), cc.level_start64.size() * 4, hipMemcpyHostToDevice, s));
-                HIPCHK(hipStreamSynchronize(s));
-                c->d_level_start64 = t;
-            }
-            d_ls64 = c->d_level_start64;
+    const uint32_t* d_ls64 = nullptr;
+    if (eval_walks(cc) && !cc.gates64.empty()) {
+        std::lock_guard<std::mutex> lk(c->eval_mu);
+        if (!c->d_level_start64) {
+            uint32_t* t = nullptr;
+            if (int rc = dalloc(ctx, cc.level_start64.size(), &t)) return rc;
+            HIPCHK(hipMemcpyAsync(t, cc.level_start64.data(), cc.level_start64.size() * 4, hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));
+            c->d_level_start64 = t;
         }
-        // a slice of one witness word per workgroup (up to 256 workgroups; more words: wider slices)
-        const uint32_t S = (uint32_t)((W + 255) / 256);
-        const uint64_t per_level = (cc.gates.size() + 32 * (uint64_t)cc.gates64.size()) / n_levels * S;
-        launch_eval_walk(s, p, c->d_gates, c->d_level_range, c->d_gates64, d_ls64, n_levels, S, per_level <= 256 ? 256 : 1024);
-        g_eval_sched[1]++;
-    } else {
-        for (uint32_t l = 0; l < n_levels; l++) {
-            const LevelRange& r = cc.level_range[l];
-            const uint32_t lo64 = cc.gates64.empty() ? 0 : cc.level_start64[l], hi64 = cc.gates64.empty() ? 0 : cc.level_start64[l + 1];
-            launch_eval_level(s, p, c->d_gates, r.lo, r.hi - r.lo, c->d_gates64, lo64, hi64 - lo64);
-        }
-        g_eval_sched[0]++;
+        d_ls64 = c->d_level_start64;
     }
+    eval_run_levels(s, p, cc, c->d_gates, c->d_level_range, c->d_gates64, d_ls64);
     uint8_t* d_out2 = nw2 ? d + o_out + out2_at : nullptr;
     uint64_t* d_out64 = nw64 ? (uint64_t*)(d + o_out + out64_at) : nullptr;
     launch_eval_out(s, p, c->d_wire_forms, (uint32_t)nw2, c->d_wire_ssa64, (uint32_t)nw64, d_out2, d_out64);

@@ -167,6 +167,24 @@ void launch_eval_wit(hipStream_t st, const uint8_t* d_wit /*[B][n]*/, uint32_t n
 void launch_eval_out(hipStream_t st, const EvalParams& p, const WireForm* d_forms, uint32_t n_gf2, const uint32_t* d_ssa64, uint32_t n_z64,
                      uint8_t* d_out2 /*[B][n_gf2] or null*/, uint64_t* d_out64 /*[B][n_z64] or null*/);
 
+// rv_eval_stream (eval_stream.inc): a chunk's failing-assertion ordinals (EvalParams::first2 / first64, chunk-local) folded into the
+// stream's per-witness status, then the chunk's counters reset.  rec2 / op2 and rec64 / op64: the chunk's Compiled::assert_rec* /
+// assert_op* tables on the device; op_base: the chunk's first op in the whole op list.
+struct EvalFold {
+    const uint32_t* rec2;
+    const uint64_t* op2;
+    const uint32_t* rec64;
+    const uint64_t* op64;
+    uint32_t n2, n64;
+    uint64_t op_base;
+    uint64_t* first_op;  // [B] op-list index of the first failing AssertZero so far (UINT64_MAX: none)
+    uint64_t* total;     // [B] failing AssertZero ops so far
+};
+void launch_eval_fold(hipStream_t st, const EvalParams& p, const EvalFold& f);
+// the carried wires' values (GF(2) row w, Z64 slot 1 + w) of witnesses [b0, b0 + nb) -> [nb][n_gf2] bytes and [nb][n_z64] words
+void launch_eval_stream_out(hipStream_t st, const EvalParams& p, uint32_t n_gf2, uint32_t n_z64, uint32_t b0, uint32_t nb, uint8_t* d_out2,
+                            uint64_t* d_out64);
+
 // ---- launchers (implemented in the .hip files) ----
 void launch_expand_seeds(hipStream_t st, const uint8_t* d_seeds, uint32_t n_reps, uint8_t* d_keys /*[n][8][16]*/);
 // Per AES key: the 11 round keys (176 bytes) followed by 32 bytes of first-round constants (k_key_schedule):

@@ -897,6 +897,20 @@ static unsigned stream_threads() {
     return std::min(std::max(hc / 2, 1u), 24u);
 }
 
+// Where a feed is cut: every `full` ops -- except that a long feed of large chunks starts with pieces of 1/8, 1/4 and 1/2 of
+// that (a piece is compiled by ONE worker thread at ~0.1 us per op; with all pieces the full size the GPU sat idle for the
+// 0.1 s the first one takes).  The rule depends on the feed's length and the chunk size only, so pass 2 cuts the same feed
+// the same way and finds pass 1's compiled pieces.  Piece i = ops [cut[i], cut[i + 1]).  (Also the streaming evaluator's.)
+static std::vector<size_t> stream_cuts(size_t n_ops, size_t full) {
+    std::vector<size_t> cut;
+    size_t at = 0;
+    cut.push_back(0);
+    if (full >= ((size_t)1 << 16) && n_ops >= 4 * full)
+        for (size_t part : {full / 8, full / 4, full / 2}) cut.push_back(at += part);
+    while (at < n_ops) cut.push_back(at = std::min(n_ops, at + full));
+    return cut;
+}
+
 static int stream_feed_impl(rv_stream* S, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64, size_t n_z64) {
     LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
     if (!S || (n_ops && !ops)) return RV_E_ARG;
@@ -904,19 +918,7 @@ static int stream_feed_impl(rv_stream* S, const rv_op* ops, size_t n_ops, const 
     if (S->format_bad) return RV_OK;  // (a verifier stream whose proof has the wrong shape: the answer is already `false`)
     HIPCHK(hipSetDevice(S->ctx->device));
     const auto t_feed0 = std::chrono::steady_clock::now();
-    // Where a feed is cut: every max_chunk_ops ops -- except that a long feed of large chunks starts with pieces of 1/8, 1/4
-    // and 1/2 of that (a piece is compiled by ONE worker thread at ~0.1 us per op; with all pieces the full size the GPU sat
-    // idle for the 0.1 s the first one takes).  The rule depends on the feed's length and the chunk size only, so pass 2
-    // cuts the same feed the same way and finds pass 1's compiled pieces.
-    std::vector<size_t> cut;  // piece i = ops [cut[i], cut[i + 1])
-    {
-        const size_t full = S->max_chunk_ops;
-        size_t at = 0;
-        cut.push_back(0);
-        if (full >= ((size_t)1 << 16) && n_ops >= 4 * full)
-            for (size_t part : {full / 8, full / 4, full / 2}) cut.push_back(at += part);
-        while (at < n_ops) cut.push_back(at = std::min(n_ops, at + full));
-    }
+    const std::vector<size_t> cut = stream_cuts(n_ops, S->max_chunk_ops);  // piece i = ops [cut[i], cut[i + 1])
     const size_t n_pieces = cut.size() - 1;
     const unsigned n_threads = (unsigned)std::min<size_t>(stream_threads(), n_pieces);
     auto advance = [&](size_t u2, size_t u64) {

@@ -10,6 +10,7 @@ The reference's README promises a streaming interface (/root/reference/README.md
     proof = sp.finish()                                    # == Proof.new(all ops, all witness, seeds=seeds)
 
 Device memory is bounded by the wire counts, one piece's working set and the proof; everything runs through the C-ABI.
+`StreamingVerifier` checks a proof against a gate list fed in pieces, and `StreamingEvaluator` evaluates one in the clear.
 """
 from __future__ import annotations
 
@@ -20,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from .ops import OP_DTYPE, TOTAL_REPS, program
-from .proof import Context, Proof, _ptr
+from .proof import Context, Evaluation, Proof, _ptr
 
 
 class StreamingProver:
@@ -140,3 +141,94 @@ def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = Tr
                                               buf, C.c_size_t(n), C.c_uint32(0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT), C.c_size_t(max_chunk_ops),
                                               C.byref(ok), C.byref(si)))
     return bool(ok.value), {k: int(getattr(si, k)) for k, _ in si._fields_}
+
+
+def _eval_status(st: np.ndarray, gv, zv) -> Evaluation:
+    n_failed = st[:, 0].astype(np.int64)
+    return Evaluation(n_failed == 0, n_failed, st[:, 1].view(np.int64).copy(), gv, zv)
+
+
+def _eval_wits(w, batch: int, dtype) -> np.ndarray:
+    a = np.ascontiguousarray(np.asarray(w, dtype=dtype))
+    if a.ndim == 1 and batch == 1:
+        a = a.reshape(1, -1)
+    if a.ndim == 1 and a.size == 0:
+        a = np.zeros((batch, 0), dtype)
+    if a.ndim != 2 or a.shape[0] != batch:
+        raise ValueError(f"witnesses must be [batch={batch}][n] (1-D for batch 1)")
+    return a
+
+
+class StreamingEvaluator:
+    """Cleartext evaluation of an op list fed in pieces, with bounded device memory (rv_eval_stream_*): what
+    Circuit(all ops, keep_wires=True).evaluate_batch(..., values=True) computes, without compiling the whole list.
+
+        se = StreamingEvaluator((z64_wires, gf2_wires), batch=B)
+        for ops, w2, w64 in pieces: se.feed(ops, w2, w64)   # w2: [B][n] (1-D for B = 1), the elements these ops' Inputs consume
+        r = se.finish(values=True)                            # the array-shaped Evaluation of Circuit.evaluate_batch
+
+    Device memory is the wire store (wire counts x batch) plus one chunk of at most max_chunk_ops ops (0 = 2^18)."""
+
+    def __init__(self, wire_counts: Tuple[int, int], batch: int = 1, max_chunk_ops: int = 0, ctx: Optional[Context] = None):
+        self.ctx = ctx or Context.default()
+        self.wire_counts = (int(wire_counts[0]), int(wire_counts[1]))
+        self.batch = int(batch)
+        self.handle = C.c_void_p()
+        _lib.check(_lib.lib().rv_eval_stream_begin(self.ctx.handle, C.c_size_t(self.wire_counts[0]), C.c_size_t(self.wire_counts[1]),
+                                                   C.c_size_t(self.batch), C.c_size_t(max_chunk_ops), C.byref(self.handle)))
+
+    def feed(self, ops, wits_gf2=(), wits_z64=()):
+        ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+        g = _eval_wits(wits_gf2, self.batch, np.uint8)
+        z = _eval_wits(wits_z64, self.batch, np.uint64)
+        _lib.check(_lib.lib().rv_eval_stream_feed(self.handle, _ptr(ops), C.c_size_t(len(ops)), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z),
+                                                  C.c_size_t(z.shape[1])))
+
+    def finish(self, values: bool = False) -> Evaluation:
+        st = np.zeros((self.batch, 2), np.uint64)
+        gv = np.zeros((self.batch, self.wire_counts[1]), np.uint8) if values else None
+        zv = np.zeros((self.batch, self.wire_counts[0]), np.uint64) if values else None
+        _lib.check(_lib.lib().rv_eval_stream_finish(self.handle, _ptr(gv), _ptr(zv), st.ctypes.data_as(C.c_void_p)))
+        return _eval_status(st, gv, zv)
+
+    @property
+    def info(self) -> dict:
+        si = _lib.EvalStreamInfo()
+        _lib.check(_lib.lib().rv_eval_stream_get_info(self.handle, C.byref(si)))
+        return {n: int(getattr(si, n)) for n, _ in si._fields_}
+
+    def close(self):
+        if self.handle:
+            if self.ctx.handle:
+                _lib.lib().rv_eval_stream_abort(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], max_chunk_ops: int = 0, values: bool = False,
+                       ctx: Optional[Context] = None, info: Optional[dict] = None) -> Evaluation:
+    """rv_evaluate_streaming: one op array in host memory, evaluated chunk by chunk with bounded device memory.  wits_gf2 /
+    wits_z64: [B][n] (1-D for one witness; the batch is len(wits_gf2)).  Returns the array-shaped Evaluation of
+    Circuit.evaluate_batch; `info` (a dict, optional) receives the stream's figures."""
+    ctx = ctx or Context.default()
+    ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+    g0 = np.asarray(wits_gf2, dtype=np.uint8)
+    batch = g0.shape[0] if g0.ndim == 2 else 1
+    g = _eval_wits(g0, batch, np.uint8)
+    z = _eval_wits(wits_z64, batch, np.uint64)
+    wc = (int(wire_counts[0]), int(wire_counts[1]))
+    st = np.zeros((batch, 2), np.uint64)
+    gv = np.zeros((batch, wc[1]), np.uint8) if values else None
+    zv = np.zeros((batch, wc[0]), np.uint64) if values else None
+    si = _lib.EvalStreamInfo()
+    _lib.check(_lib.lib().rv_evaluate_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(wc[0]), C.c_size_t(wc[1]),
+                                                C.c_size_t(batch), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z), C.c_size_t(z.shape[1]),
+                                                C.c_size_t(max_chunk_ops), _ptr(gv), _ptr(zv), st.ctypes.data_as(C.c_void_p), C.byref(si)))
+    if info is not None:
+        info.update({k: int(getattr(si, k)) for k, _ in si._fields_})
+    return _eval_status(st, gv, zv)
