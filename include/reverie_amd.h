@@ -381,6 +381,48 @@ int rv_stream_verify_finish(rv_stream *s, uint32_t flags, int *ok);
 int rv_verify_streaming(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const uint8_t *proof, size_t proof_len,
                         uint32_t flags, size_t max_chunk_ops, int *ok, rv_stream_info *info);
 
+/* ---- batches over one stream: B witnesses (or B proofs) of ONE statement, the op list fed once per pass ------------------------
+ * The host work of a chunk (compile, relocation, gate upload) -- what paces a streamed proof -- is done once for the batch; the
+ * device work of the chunk is issued for every proof of the batch.
+ *     rv_stream_begin_batch(ctx, z64_wires, gf2_wires, B, seeds, max_chunk_ops, &s)   seeds: B x 256 x 16 (rv_prove_batch's layout)
+ *                                                                                     or NULL (fresh seeds for every proof)
+ *     rv_stream_feed(s, ops, n, wit_gf2, n_gf2, wit_z64, n_z64)   ...   pass 1; witness b at wit_gf2 + b*n_gf2, wit_z64 + b*n_z64
+ *                                                                       (n_gf2 / n_z64 per witness: rv_eval_stream_feed's layout)
+ *     rv_stream_commit_batch(s, comms)          comms: B x 32 (nullable)
+ *     rv_stream_feed(s, ...)                    ...   pass 2: pass 1's op list and every witness again
+ *     rv_stream_finish_batch(s, proofs, lens)   proofs[b] (rv_free each) is byte-identical to rv_prove's for witness b and
+ *                                               seeds + b*4096, and to rv_stream_* / rv_prove_streaming's
+ * rv_stream_feed, rv_stream_same_cuts, rv_stream_get_info and rv_stream_abort take batch streams unchanged.  A batch of 1 is a
+ * single stream in every output (the _batch forms also take a stream of rv_stream_begin).  rv_stream_commit, rv_stream_finish and
+ * rv_stream_verify_finish on a stream of batch > 1, batch == 0, a null handle or array, and a _batch form on the other kind of
+ * stream (prover / verifier) give RV_E_ARG.
+ * A failing AssertZero of any witness gives RV_E_WITNESS_INVALID from the feed that holds it (rv_last_error names the first such
+ * witness); the stream then only accepts rv_stream_abort.  The witness digests are kept per proof: pass 2 with any witness changed
+ * gives RV_E_ARG at finish.  rv_stream_same_cuts keeps a chunk's transcripts for all B proofs or for none, and RV_STREAM_KEEP_MB is
+ * the budget of the whole batch.
+ * Device memory: B wire stores + one chunk's working set per proof + B proofs (+ the kept budget).  If B > 1 wire stores exceed half
+ * of the free device memory, begin gives RV_E_NOMEM before anything is allocated (the batch is not split; a batch of 1 is begun as
+ * rv_stream_begin begins a stream).  rv_stream_get_info on a
+ * batch: n_ops .. z64_muls are the stream's (every proof's are the same); wire_store_bytes, peak_chunk_bytes, hash_state_bytes,
+ * proof_bytes and kept_mib are totals over the batch. */
+int rv_stream_begin_batch(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, size_t batch, const uint8_t *seeds /* batch x 256 x 16, or NULL */,
+                          size_t max_chunk_ops, rv_stream **out);
+int rv_stream_commit_batch(rv_stream *s, uint8_t *comms /* batch x 32, nullable */);
+int rv_stream_finish_batch(rv_stream *s, uint8_t **proofs /* [batch] */, size_t *proof_lens /* [batch] */);
+/* both passes over an op array in host memory; wit_gf2 / wit_z64: [batch][n_gf2] / [batch][n_z64]; info (nullable) as above */
+int rv_prove_streaming_batch(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, size_t batch,
+                             const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64, size_t n_z64, const uint8_t *seeds,
+                             size_t max_chunk_ops, uint8_t **proofs, size_t *proof_lens, rv_stream_info *info);
+/* The batched streaming verifier: ok[b] is what rv_verify_streaming / rv_verify_ex answers for proof b with the same flags.  A proof
+ * that cannot be parsed or has the wrong repetition counts gets ok[b] = 0 and the others are verified all the same (rv_verify_batch's
+ * rule); a non-zero return is an argument or device error.  The proofs must outlive the stream. */
+int rv_stream_verify_begin_batch(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, size_t batch, const uint8_t *const *proofs,
+                                 const size_t *proof_lens, size_t max_chunk_ops, rv_stream **out);
+int rv_stream_verify_finish_batch(rv_stream *s, uint32_t flags, int *ok /* [batch] */);
+int rv_verify_streaming_batch(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, size_t batch,
+                              const uint8_t *const *proofs, const size_t *proof_lens, uint32_t flags, size_t max_chunk_ops,
+                              int *ok, rv_stream_info *info);
+
 /* ---- sharded form (one process per GPU; repetitions [rep_begin, rep_begin+rep_count),
  * both multiples of 8).  rv_prove == commit(0,256) -> combine -> challenge -> open ->
  * assemble.  Between commit and open the caller exchanges the 32-byte per-repetition

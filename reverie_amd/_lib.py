@@ -84,7 +84,21 @@ SYMBOLS = [
     "rv_evaluate", "rv_evaluate_batch", "rv_hook_eval_schedules",
     "rv_eval_stream_begin", "rv_eval_stream_feed", "rv_eval_stream_finish", "rv_eval_stream_get_info", "rv_eval_stream_abort",
     "rv_evaluate_streaming",
+    "rv_stream_begin_batch", "rv_stream_commit_batch", "rv_stream_finish_batch", "rv_prove_streaming_batch",
+    "rv_stream_verify_begin_batch", "rv_stream_verify_finish_batch", "rv_verify_streaming_batch",
 ]
+_P, _Z = C.c_void_p, C.c_size_t
+# argument types of the batched stream entry points (ctypes checks every call against them)
+ARGTYPES = {
+    "rv_stream_begin_batch": [_P, _Z, _Z, _Z, _P, _Z, C.POINTER(C.c_void_p)],
+    "rv_stream_commit_batch": [_P, _P],
+    "rv_stream_finish_batch": [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)],
+    "rv_prove_streaming_batch": [_P, _P, _Z, _Z, _Z, _Z, _P, _Z, _P, _Z, _P, _Z, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(StreamInfo)],
+    "rv_stream_verify_begin_batch": [_P, _Z, _Z, _Z, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), _Z, C.POINTER(C.c_void_p)],
+    "rv_stream_verify_finish_batch": [_P, C.c_uint32, C.POINTER(C.c_int)],
+    "rv_verify_streaming_batch": [_P, _P, _Z, _Z, _Z, _Z, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32, _Z, C.POINTER(C.c_int),
+                                  C.POINTER(StreamInfo)],
+}
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1
 RV_COMPILE_KEEP_WIRES = 2  # the circuit keeps every wire's final value form: rv_evaluate can return wire values
@@ -138,6 +152,8 @@ def lib():
                 fn.restype = C.c_uint64
             elif name not in ("rv_strerror", "rv_last_error", "rv_abi_version"):
                 fn.restype = C.c_int
+            if name in ARGTYPES:
+                fn.argtypes = ARGTYPES[name]
         _lib = L
     return _lib
 

@@ -333,6 +333,14 @@ void launch_b3_stream_bits_chunks(hipStream_t st, const uint8_t* d_stream, uint6
 void launch_b3_contig_chunks(hipStream_t st, const uint64_t* d_streams, uint64_t stride_words, uint64_t n_words, uint32_t R, uint32_t* d_cv,
                              uint64_t chunk_base, uint32_t root_ok);
 void launch_b3_pairs(hipStream_t st, const uint32_t* d_pending, const uint32_t* d_in, uint64_t n_pairs, uint32_t R, uint32_t* d_out);
+struct B3PairsBatch {  // per stream: pending root (or null), input chaining values, output -- the arguments of launch_b3_pairs
+    static constexpr uint32_t MAX = 32;
+    const uint32_t* pending[MAX];
+    const uint32_t* in[MAX];
+    uint32_t* out[MAX];
+    uint32_t n;
+};
+void launch_b3_pairs_batched(hipStream_t st, const B3PairsBatch& L, uint64_t n_pairs, uint32_t R);
 struct B3FoldList {
     uint32_t n;
     const uint32_t* p[48];  // pending subtree roots, smallest subtree first ([R][8] each)

@@ -1524,8 +1524,8 @@ uint32_t launch_b3_stream_bits(hipStream_t st, const uint8_t* d_stream, uint64_t
 // ---- incremental BLAKE3 tree (streaming prover): the chunk chaining values of a stream arrive in batches ----
 // one tree level over a batch: seq = [pending?] ++ in[0 .. n_in); out[i] = parent(seq[2i], seq[2i+1]) for i < n_pairs
 // (never ROOT: whether a merge is the root is only known when the stream ends, see k_b3_fold)
-__global__ __launch_bounds__(256) void k_b3_pairs(const uint32_t* __restrict__ pending /* [R][8] or null */, const uint32_t* __restrict__ in,
-                                                  uint64_t n_pairs, uint32_t R, uint32_t* __restrict__ out) {
+__device__ __forceinline__ void b3_pairs_body(const uint32_t* __restrict__ pending, const uint32_t* __restrict__ in, uint64_t n_pairs, uint32_t R,
+                                              uint32_t* __restrict__ out) {
     const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t i = tid / R;
     const uint32_t r = (uint32_t)(tid % R);
@@ -1543,6 +1543,20 @@ __global__ __launch_bounds__(256) void k_b3_pairs(const uint32_t* __restrict__ p
     uint32_t* d = out + ((size_t)i * R + r) * 8;
 #pragma unroll
     for (int k = 0; k < 8; k++) d[k] = o[k];
+}
+__global__ __launch_bounds__(256) void k_b3_pairs(const uint32_t* __restrict__ pending /* [R][8] or null */, const uint32_t* __restrict__ in,
+                                                  uint64_t n_pairs, uint32_t R, uint32_t* __restrict__ out) {
+    b3_pairs_body(pending, in, n_pairs, R, out);
+}
+// the same tree level for up to B3PairsBatch::MAX streams of equal shape at once: blockIdx.y = stream (a batch stream's proofs)
+__global__ __launch_bounds__(256) void k_b3_pairs_batched(B3PairsBatch L, uint64_t n_pairs, uint32_t R) {
+    const uint32_t y = blockIdx.y;
+    b3_pairs_body(L.pending[y], L.in[y], n_pairs, R, L.out[y]);
+}
+void launch_b3_pairs_batched(hipStream_t st, const B3PairsBatch& L, uint64_t n_pairs, uint32_t R) {
+    if (!n_pairs || !L.n) return;
+    const uint64_t threads = n_pairs * R;
+    hipLaunchKernelGGL(k_b3_pairs_batched, dim3((unsigned)((threads + 255) / 256), L.n), dim3(256), 0, st, L, n_pairs, R);
 }
 void launch_b3_pairs(hipStream_t st, const uint32_t* d_pending, const uint32_t* d_in, uint64_t n_pairs, uint32_t R, uint32_t* d_out) {
     if (!n_pairs) return;

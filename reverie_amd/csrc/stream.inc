@@ -64,6 +64,48 @@ static void launch_copy_segs(hipStream_t st, const CopySegs& cs) {
     if (cs.n) hipLaunchKernelGGL(k_copy_segs, dim3(cs.n), dim3(256), 0, st, cs);
 }
 
+// A batch stream's small copies of one step, for every proof at once: up to 64 strided segments (rows x row_bytes, own pitches) per
+// launch, blockIdx.y = segment.  The tails carried in front of a chunk and out of it, the trees' odd nodes, the pending opening rows:
+// per proof they were a hipMemcpy(2D)Async or a k_copy_segs launch each.  Sizes and pitches are multiples of 4 bytes; src and dst of
+// a launch do not overlap.
+struct CopyRows {
+    static constexpr uint32_t MAX = 64;
+    const uint8_t* src[MAX];
+    uint8_t* dst[MAX];
+    uint64_t spitch[MAX], dpitch[MAX];
+    uint32_t row_bytes[MAX], rows[MAX];
+    uint32_t n;
+};
+__global__ __launch_bounds__(256) void k_copy_rows_batched(CopyRows L) {
+    const uint32_t y = blockIdx.y;
+    const uint32_t wpr = L.row_bytes[y] / 4;
+    const uint64_t total = (uint64_t)wpr * L.rows[y];
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t row = i / wpr, w = i % wpr;
+        ((uint32_t*)(L.dst[y] + row * L.dpitch[y]))[w] = ((const uint32_t*)(L.src[y] + row * L.spitch[y]))[w];
+    }
+}
+struct CopyBatch {
+    hipStream_t st;
+    CopyRows L{};
+    explicit CopyBatch(hipStream_t s) : st(s) {}
+    void add(void* dst, uint64_t dpitch, const void* src, uint64_t spitch, uint64_t row_bytes, uint64_t rows) {
+        if (!row_bytes || !rows) return;
+        if (L.n == CopyRows::MAX) flush();
+        const uint32_t k = L.n++;
+        L.src[k] = (const uint8_t*)src, L.dst[k] = (uint8_t*)dst, L.spitch[k] = spitch, L.dpitch[k] = dpitch;
+        L.row_bytes[k] = (uint32_t)row_bytes, L.rows[k] = (uint32_t)rows;
+    }
+    void add(void* dst, const void* src, uint64_t bytes) { add(dst, bytes, src, bytes, bytes, 1); }
+    void add(const CopySegs& cs) {
+        for (uint32_t i = 0; i < cs.n; i++) add(cs.dst[i], cs.src[i], cs.bytes[i]);
+    }
+    void flush() {
+        if (L.n) hipLaunchKernelGGL(k_copy_rows_batched, dim3(16, L.n), dim3(256), 0, st, L);
+        L.n = 0;
+    }
+};
+
 struct rv_stream {
     rv_ctx* ctx = nullptr;
     size_t z64_wires = 0, gf2_wires = 0;
@@ -115,6 +157,7 @@ struct rv_stream {
     uint32_t sup_nq = 0, sup_r = 0;  // verifier: quad words / repetitions per row of the supplied-value arrays (InterpParams::sup_nq, Interp64Params::sup_r)
     uint64_t* d_src = nullptr;         // [6][R]: rec off, len; corr off, len; in off, len (bytes inside the proof)
     std::vector<uint64_t> src64;       // the same for the Z64 vectors (shifted per chunk on the host)
+    std::vector<uint64_t> src64c;      // ... as the current chunk's copy reads them (lives until the chunk's final synchronisation)
     // pass 1's compiled chunks, kept on the host for pass 2 while they fit RV_STREAM_CACHE_MB (default 1024): a chunk that
     // is fed again with the same cut only needs its transcript offsets moved (relocate_chunk), not a second compile
     struct CachedPiece {
@@ -151,6 +194,18 @@ struct rv_stream {
     std::map<uint64_t, FeedCounts> feed_counts;
     bool same_cuts = false;   // rv_stream_same_cuts
     bool p2_skipped = false;  // pass 2: a chunk was served from kept transcripts (the wire store is stale from there on)
+    // A BATCH stream (rv_stream_begin_batch / rv_stream_verify_begin_batch with batch > 1) is a handle over `bat`: one complete
+    // single-proof stream per witness / proof, none of which is the handle.  The handle holds no device memory; a feed compiles each
+    // chunk once (on the first member that runs: its cache, its counts) and issues the chunk for every member (stream_chunk_run).
+    std::vector<rv_stream*> bat;
+    // the proofs a feed runs for: the stream itself, or the batch's members (a verifier's members with a malformed proof run nothing)
+    std::vector<rv_stream*> running() {
+        if (bat.empty()) return format_bad ? std::vector<rv_stream*>() : std::vector<rv_stream*>{this};
+        std::vector<rv_stream*> v;
+        for (rv_stream* m : bat)
+            if (!m->format_bad) v.push_back(m);
+        return v;
+    }
     void release_kept(Kept& k) {
         ctx->release(k.on_base);
         ctx->release(k.pre_base);
@@ -215,6 +270,65 @@ static int inc_absorb(rv_ctx* ctx, IncHash& H, uint32_t* cvs, uint64_t n, uint32
     return RV_OK;
 }
 
+// inc_absorb for the proofs of a batch stream at once: their trees have the same shape (the same event counts), so every level is one
+// k_b3_pairs_batched launch over them and one copy of their odd nodes.  cvs[b]: proof b's n chaining values.
+static int inc_absorb_batch(rv_ctx* ctx, const std::vector<IncHash*>& Hs, const std::vector<uint32_t*>& cvs, uint64_t n, uint32_t R) {
+    hipStream_t st = ctx->stream;
+    const size_t B = Hs.size();
+    for (IncHash* H : Hs)
+        if (H->chunks != Hs[0]->chunks || H->full != Hs[0]->full || H->node.size() != Hs[0]->node.size()) {
+            for (size_t b = 0; b < B; b++) {  // (cannot happen: the members see the same chunks)
+                int rc = inc_absorb(ctx, *Hs[b], cvs[b], n, R);
+                if (rc) return rc;
+            }
+            return RV_OK;
+        }
+    std::vector<uint32_t*> cur(cvs);
+    bool cur_owned = false;
+    uint64_t n_cur = n;
+    size_t lvl = 0;
+    int rc;
+    CopyBatch cp(st);
+    while (n_cur) {
+        if (Hs[0]->node.size() <= lvl)
+            for (IncHash* H : Hs) {
+                uint32_t* p = nullptr;
+                if ((rc = dalloc(ctx, (size_t)R * 8, &p))) return rc;
+                H->node.push_back(p);
+                H->full.push_back(0);
+            }
+        const bool pend = Hs[0]->full[lvl] != 0;
+        const uint64_t total = n_cur + (pend ? 1 : 0), pairs = total / 2;
+        std::vector<uint32_t*> out(B, nullptr);
+        if (pairs) {
+            uint32_t* blk = nullptr;  // (one allocation for the level's outputs of every proof)
+            if ((rc = dalloc(ctx, (size_t)B * pairs * R * 8, &blk))) return rc;
+            for (size_t b = 0; b < B; b++) out[b] = blk + b * pairs * R * 8;
+            for (size_t b0 = 0; b0 < B; b0 += B3PairsBatch::MAX) {
+                B3PairsBatch L{};
+                for (size_t b = b0; b < std::min(B, b0 + B3PairsBatch::MAX); b++, L.n++) {
+                    L.pending[L.n] = pend ? Hs[b]->node[lvl] : nullptr;
+                    L.in[L.n] = cur[b];
+                    L.out[L.n] = out[b];
+                }
+                launch_b3_pairs_batched(st, L, pairs, R);
+            }
+        }
+        if (total & 1)
+            for (size_t b = 0; b < B; b++) cp.add(Hs[b]->node[lvl], cur[b] + (size_t)(n_cur - 1) * R * 8, (size_t)R * 32);
+        cp.flush();
+        for (IncHash* H : Hs) H->full[lvl] = (total & 1) ? 1 : 0;
+        if (cur_owned) ctx->release(cur[0]);  // (stream order keeps the arena's reuse behind the kernels that read it)
+        cur = out;
+        cur_owned = true;
+        n_cur = pairs;
+        lvl++;
+    }
+    if (cur_owned) ctx->release(cur[0]);
+    for (IncHash* H : Hs) H->chunks += n;
+    return RV_OK;
+}
+
 // the stream ends: its last chunk (chaining value in d_last, hashed with chunk counter H.chunks and the ROOT flag iff it
 // is the only chunk) folded into the pending subtree roots
 static void inc_finish(rv_ctx* ctx, const IncHash& H, const uint32_t* d_last, uint32_t R, uint32_t* d_digest) {
@@ -228,6 +342,8 @@ extern "C" void rv_stream_abort(rv_stream* S) {
     if (!S) return;
     (void)hipSetDevice(S->ctx->device);
     (void)hipStreamSynchronize(S->ctx->stream);
+    for (rv_stream* m : S->bat) rv_stream_abort(m);
+    S->bat.clear();
     S->free_all();
     delete S;
 }
@@ -395,11 +511,38 @@ static int stream_compile_piece(const rv_stream* S, const rv_op* ops, size_t n_o
     return RV_OK;
 }
 
+// the error flags of the proofs' chunks since the pass began, read with one wait.  The prover: the first witness whose AssertZero
+// failed is named in rv_last_error (RV_E_WITNESS_INVALID); the verifier: RV_DEV_ZERO_CHECK goes into each proof's dev_flags.
+static int stream_read_errs(const std::vector<rv_stream*>& proofs, const char* what) {
+    hipStream_t st = proofs[0]->ctx->stream;
+    std::vector<int> err(proofs.size(), 0);
+    for (size_t b = 0; b < proofs.size(); b++)
+        if (hipMemcpyAsync(&err[b], proofs[b]->d_err, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess)
+            return hip_fail(hipGetLastError(), what, __FILE__, __LINE__);
+    if (hipStreamSynchronize(st) != hipSuccess) return hip_fail(hipGetLastError(), what, __FILE__, __LINE__);
+    for (size_t b = 0; b < proofs.size(); b++) {
+        if (proofs[b]->pass == 3) {
+            proofs[b]->dev_flags |= err[b];  // RV_DEV_ZERO_CHECK: an AssertZero of an opened repetition (the strict verifier reads it at the end)
+        } else if (err[b]) {
+            char buf[96];
+            snprintf(buf, sizeof buf, "an AssertZero fails for witness %zu of the stream", b);
+            g_last_error = buf;
+            return RV_E_WITNESS_INVALID;
+        }
+    }
+    return RV_OK;
+}
+
 // c: the chunk compiled by stream_compile_piece with the phases the stream is at now (consumed here)
 // digest: ops_digest of the chunk's ops at their position in the stream; carried: the transcript offsets c's arrays already
 // hold (zero for a fresh compile, pass 1's for a chunk that comes out of the cache)
-static int stream_chunk_run(rv_stream* S, rv_circuit* c, uint64_t digest, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
-                            size_t n_z64, size_t* used_gf2, size_t* used_z64, const ChunkStart& carried = ChunkStart()) {
+// proofs: the proofs the chunk runs for (proofs[0] == S, which holds the host-side state: cache, counts, pass); proof b takes its
+// witness at wit_gf2 + b * stride2 and wit_z64 + b * stride64.  The compile, relocation and gate upload happen once; for a batch the
+// level loop, the tree levels and the small copies run once with the proof in gridDim.y, the masks, chunk hashes and openings
+// proof after proof, with no wait between them.
+static int stream_chunk_run(rv_stream* S, const std::vector<rv_stream*>& proofs, rv_circuit* c, uint64_t digest, size_t n_ops, const uint8_t* wit_gf2,
+                            size_t n_gf2, size_t stride2, const uint64_t* wit_z64, size_t n_z64, size_t stride64, size_t* used_gf2, size_t* used_z64,
+                            const ChunkStart& carried = ChunkStart()) {
     rv_ctx* ctx = S->ctx;
     hipStream_t st = ctx->stream;
     constexpr uint32_t R = rv_stream::R, NQ = rv_stream::NQ;
@@ -442,36 +585,58 @@ static int stream_chunk_run(rv_stream* S, rv_circuit* c, uint64_t digest, size_t
         delete c;
         return RV_E_UNSUPPORTED;  // the mask kernels' first-round shortcut covers CTR indices below 2^24 (internal.h)
     }
-    // pass 2 of a chunk whose transcripts pass 1 kept: only the openings are taken from them
-    rv_stream::Kept* kp = nullptr;
+    const uint64_t first_op = S->run.n_ops;
+    // pass 2 of a chunk whose transcripts pass 1 kept: only the openings are taken from them (for every proof of the stream or for none)
+    bool use_kept = false;
     if (S->pass == 2) {
-        auto it = S->kept.find(S->run.n_ops);
-        if (it != S->kept.end()) {
-            if (it->second.n_ops == n_ops && it->second.digest == digest) {
-                kp = &it->second;
-            } else {  // (cut differently, or other ops: finish reports those) -- of no use any more
-                S->release_kept(it->second);
-                S->kept.erase(it);
-            }
+        size_t n_match = 0, n_found = 0;
+        for (rv_stream* Q : proofs) {
+            auto it = Q->kept.find(first_op);
+            if (it == Q->kept.end()) continue;
+            n_found++;
+            n_match += it->second.n_ops == n_ops && it->second.digest == digest;
         }
+        use_kept = n_found && n_match == proofs.size();
+        if (n_found && !use_kept)  // (cut differently, or other ops: finish reports those) -- of no use any more
+            for (rv_stream* Q : proofs) {
+                auto it = Q->kept.find(first_op);
+                if (it == Q->kept.end()) continue;
+                Q->release_kept(it->second);
+                Q->kept.erase(it);
+            }
     }
-    if (kp) S->p2_skipped = true;
-    if (!kp && S->pass == 2 && S->p2_skipped) {
+    if (use_kept)
+        for (rv_stream* Q : proofs) Q->p2_skipped = true;
+    if (!use_kept && S->pass == 2 && S->p2_skipped) {
         g_last_error = "rv_stream_same_cuts was promised, but pass 2 is not fed in pass 1's pieces";
         rv_circuit_destroy(c);
         return RV_E_ARG;
     }
     // ---- buffers of this chunk
-    std::vector<void*> tmp;  // released at the end of the chunk
-    const uint64_t first_op = S->run.n_ops;
+    std::vector<void*> tmp;  // released when a proof's work is issued (the next proof's buffers reuse them behind it on the stream)
+    rv_stream* P = S;                 // the proof being issued
+    rv_stream::Kept* kp = nullptr;    // its kept transcripts of this chunk (use_kept)
+    auto release_tmp = [&] {
+        for (void* p : tmp) ctx->release(p);
+        tmp.clear();
+    };
+    auto drop_all_kept = [&] {
+        for (rv_stream* Q : proofs) {
+            for (auto& kv : Q->kept) Q->release_kept(kv.second);
+            Q->kept.clear();
+            Q->keep_cap = 0;
+        }
+    };
     auto done = [&](int code) {
         if (code != RV_OK) (void)hipStreamSynchronize(st);
-        for (void* p : tmp) ctx->release(p);
-        if (kp) {  // (back to the arena: whatever takes them next is ordered behind this chunk's kernels on the stream)
-            S->release_kept(*kp);
-            S->kept.erase(first_op);
-            kp = nullptr;
-        }
+        release_tmp();
+        if (use_kept)  // (back to the arena: whatever takes them next is ordered behind this chunk's kernels on the stream)
+            for (rv_stream* Q : proofs) {
+                auto it = Q->kept.find(first_op);
+                if (it == Q->kept.end()) continue;
+                Q->release_kept(it->second);
+                Q->kept.erase(it);
+            }
         if (code == RV_OK && p1) {  // keep the compiled chunk for pass 2 (host arrays only; the device copies go back to the arena)
             static const uint64_t cap = (uint64_t)(getenv("RV_STREAM_CACHE_MB") ? std::max(atoi(getenv("RV_STREAM_CACHE_MB")), 0) : 1024) << 20;
             const uint64_t b = rv_stream::compiled_bytes(c->cc);
@@ -489,11 +654,11 @@ static int stream_chunk_run(rv_stream* S, rv_circuit* c, uint64_t digest, size_t
     };
     auto take = [&](size_t bytes, void** p) {
         int r = ctx->alloc(bytes, p);
-        if (r == RV_E_NOMEM && !kp && !S->kept.empty()) {  // the kept transcripts are a convenience of pass 2: they go before a chunk fails for memory
+        bool any_kept = false;
+        for (rv_stream* Q : proofs) any_kept = any_kept || !Q->kept.empty();
+        if (r == RV_E_NOMEM && !kp && any_kept) {  // the kept transcripts are a convenience of pass 2: they go before a chunk fails for memory
             (void)hipStreamSynchronize(st);
-            for (auto& kv : S->kept) S->release_kept(kv.second);
-            S->kept.clear();
-            S->keep_cap = 0;
+            drop_all_kept();
             ctx->trim();
             r = ctx->alloc(bytes, p);
         }
@@ -508,20 +673,45 @@ static int stream_chunk_run(rv_stream* S, rv_circuit* c, uint64_t digest, size_t
         if (e_ != hipSuccess) return done(hip_fail(e_, #x, __FILE__, __LINE__)); \
     } while (0)
     // no wait per chunk (the feed ends with one: stream_feed_settle) unless the phase timers are on or the piece is not in a ring slot
-    if (!kp && (rc = circuit_upload(ctx, c, !ctx->profiling))) {
+    if (!use_kept && (rc = circuit_upload(ctx, c, !ctx->profiling))) {
         c = nullptr;  // (circuit_upload destroys the circuit on every failure)
         return done(rc);
     }
-    const bool no_wait = !kp && c->upload_pending && !(ver && !c->cc.gates64.empty());  // (the verifier's Z64 chunks feed a copy from a local array)
+    const bool no_wait = !use_kept && c->upload_pending && !(ver && !c->cc.gates64.empty());  // (the verifier's Z64 chunks feed a copy from a local array)
     const auto t_up = now();
-    if ((rc = stream_reserve(S, cc))) return done(rc);
+    const uint64_t on_rows = std::max<uint64_t>(cc.n_on, 1), pre_rows = std::max<uint64_t>(cc.n_pre, 1);
+    const bool has64 = !cc.gates64.empty();
+    const bool tr64 = has64 || cc.on_words64 || cc.pre_words64;
+    // own events of this chunk (the compiled counters include the carried ones in front)
+    const uint64_t new_on = cc.n_on - cs.on0, new_pre = cc.n_pre - cs.pre0;
+    const uint64_t new_on64 = cc.on_words64 - cs.on_words64_0, new_pre64 = cc.pre_words64 - cs.pre_words64_0;
+    auto t_alloc = now();
+    // A batch stream (proofs.size() > 1) takes each step of the chunk for all its proofs together where it can: the small copies go
+    // into one k_copy_rows_batched launch per step, the level loop is launch_levels_batched over per-proof parameter blocks (the
+    // proof in gridDim.y, as rv_prove_batch), the trees grow through k_b3_pairs_batched.  A single stream keeps its own launches.
+    const size_t NB = proofs.size();
+    const bool batched = NB > 1;
+    struct ProofBufs {
+        uint32_t* d_on;
+        uint8_t* d_pre;
+        uint64_t *d_on64, *d_pre64;
+        uint64_t onw, prew;
+        rv_stream::Kept* kp;
+    };
+    std::vector<ProofBufs> pbs(NB);
+    std::vector<InterpParams> pps(NB);
+    std::vector<Interp64Params> pp64s(NB);
+    CopyBatch cpb(st);
+    for (size_t bi = 0; bi < proofs.size(); bi++) {
+    P = proofs[bi];
+    kp = use_kept ? &P->kept[first_op] : nullptr;
+    const uint8_t* w2 = wit_gf2 ? wit_gf2 + bi * stride2 : nullptr;
+    const uint64_t* w64 = wit_z64 ? wit_z64 + bi * stride64 : nullptr;
+    if ((rc = stream_reserve(P, cc))) return done(rc);
     uint32_t* d_on = nullptr;
     uint8_t *d_pre = nullptr, *d_wit = nullptr;
     uint64_t *d_on64 = nullptr, *d_pre64 = nullptr, *d_wit64 = nullptr, *d_masks64 = nullptr;
-    const uint64_t on_rows = std::max<uint64_t>(cc.n_on, 1), pre_rows = std::max<uint64_t>(cc.n_pre, 1);
     uint64_t onw = std::max<uint64_t>(cc.on_words64, 1), prew = std::max<uint64_t>(cc.pre_words64, 1);
-    const bool has64 = !cc.gates64.empty();
-    const bool tr64 = has64 || cc.on_words64 || cc.pre_words64;
     if (kp) {
         // the chunk's own events sit behind kp->on0 carried ones in the kept buffers and belong behind cs.on0 now
         d_on = kp->d_on + ((int64_t)kp->on0 - (int64_t)cs.on0) * (int64_t)NQ;
@@ -538,11 +728,11 @@ static int stream_chunk_run(rv_stream* S, rv_circuit* c, uint64_t digest, size_t
         constexpr uint64_t HEAD_ON = 16, HEAD_PRE = 8;
         const uint64_t keep_need = (on_rows + HEAD_ON) * NQ * 4 + (pre_rows + HEAD_PRE) * (NQ / 2) + (tr64 ? (onw + prew) * R * 8 : 0);
         // (the kept chunks stay a suffix of the stream: the oldest ones make room; a chunk that cannot be kept empties the set)
-        const bool keep = p1 && S->same_cuts && keep_need <= S->keep_cap;
+        const bool keep = p1 && S->same_cuts && keep_need <= P->keep_cap;
         if (p1 && S->same_cuts)
-            while (!S->kept.empty() && (!keep || S->kept_bytes + keep_need > S->keep_cap)) {
-                S->release_kept(S->kept.begin()->second);
-                S->kept.erase(S->kept.begin());
+            while (!P->kept.empty() && (!keep || P->kept_bytes + keep_need > P->keep_cap)) {
+                P->release_kept(P->kept.begin()->second);
+                P->kept.erase(P->kept.begin());
             }
         if (keep) {
             rv_stream::Kept k;
@@ -554,16 +744,16 @@ static int stream_chunk_run(rv_stream* S, rv_circuit* c, uint64_t digest, size_t
             if (!r && tr64) r = ctx->alloc(prew * R * 8, (void**)&k.d_pre64);
             if (r) {  // (no room after all: nothing is kept from here back -- the kept chunks must be a suffix -- and the chunk runs as ever)
                 ctx->release(k.on_base), ctx->release(k.pre_base), ctx->release(k.d_on64), ctx->release(k.d_pre64);
-                for (auto& kv : S->kept) S->release_kept(kv.second);
-                S->kept.clear();
-                S->keep_cap = 0;
+                for (auto& kv : P->kept) P->release_kept(kv.second);
+                P->kept.clear();
+                P->keep_cap = 0;
             } else {
                 k.d_on = (uint32_t*)k.on_base + HEAD_ON * NQ;
                 k.d_pre = (uint8_t*)k.pre_base + HEAD_PRE * (NQ / 2);
                 d_on = k.d_on, d_pre = k.d_pre, d_on64 = k.d_on64, d_pre64 = k.d_pre64;
-                S->kept_bytes += keep_need;
-                S->kept_peak = std::max(S->kept_peak, S->kept_bytes);
-                S->kept[first_op] = k;
+                P->kept_bytes += keep_need;
+                P->kept_peak = std::max(P->kept_peak, P->kept_bytes);
+                P->kept[first_op] = k;
             }
         }
         if (!d_on) {
@@ -577,50 +767,58 @@ static int stream_chunk_run(rv_stream* S, rv_circuit* c, uint64_t digest, size_t
     {
         const uint64_t ws = cc.n_rows * (uint64_t)(NQ * 4 + NQ / 2) + on_rows * NQ * 4 + pre_rows * (NQ / 2) + cc.gates.size() * sizeof(Gate) +
                             (has64 ? (onw + prew) * R * 8 + n_blocks64 * 2 * R * 64 + cc.n_ssa64 * (uint64_t)R * 72 : 0);
-        S->peak_bytes = std::max(S->peak_bytes, ws);
+        P->peak_bytes = std::max(P->peak_bytes, ws);
     }
     // carried events in front of the chunk's own
-    if (hashing) {
-        if (S->on_tail) SCHK(hipMemcpyAsync(d_on, S->d_on_tail, S->on_tail * NQ * 4, hipMemcpyDeviceToDevice, st));
-        if (S->pre_tail) SCHK(hipMemcpyAsync(d_pre, S->d_pre_tail, S->pre_tail * (NQ / 2), hipMemcpyDeviceToDevice, st));
-        if (S->on64_tail && d_on64)
-            SCHK(hipMemcpy2DAsync(d_on64, onw * 8, S->d_on64_tail, 128 * 8, S->on64_tail * 8, R, hipMemcpyDeviceToDevice, st));
-        if (S->pre64_tail && d_pre64)
-            SCHK(hipMemcpy2DAsync(d_pre64, prew * 8, S->d_pre64_tail, 128 * 8, S->pre64_tail * 8, R, hipMemcpyDeviceToDevice, st));
+    if (hashing && batched) {
+        cpb.add(d_on, P->d_on_tail, P->on_tail * NQ * 4);
+        cpb.add(d_pre, P->d_pre_tail, P->pre_tail * (NQ / 2));
+        if (d_on64) cpb.add(d_on64, onw * 8, P->d_on64_tail, 128 * 8, P->on64_tail * 8, R);
+        if (d_pre64) cpb.add(d_pre64, prew * 8, P->d_pre64_tail, 128 * 8, P->pre64_tail * 8, R);
+    } else if (hashing) {
+        if (P->on_tail) SCHK(hipMemcpyAsync(d_on, P->d_on_tail, P->on_tail * NQ * 4, hipMemcpyDeviceToDevice, st));
+        if (P->pre_tail) SCHK(hipMemcpyAsync(d_pre, P->d_pre_tail, P->pre_tail * (NQ / 2), hipMemcpyDeviceToDevice, st));
+        if (P->on64_tail && d_on64)
+            SCHK(hipMemcpy2DAsync(d_on64, onw * 8, P->d_on64_tail, 128 * 8, P->on64_tail * 8, R, hipMemcpyDeviceToDevice, st));
+        if (P->pre64_tail && d_pre64)
+            SCHK(hipMemcpy2DAsync(d_pre64, prew * 8, P->d_pre64_tail, 128 * 8, P->pre64_tail * 8, R, hipMemcpyDeviceToDevice, st));
     } else {
         CopySegs cs_{};
-        if (S->pend_rec) cs_.add(S->d_pend_rec, d_on, S->pend_rec * NQ * 4);
-        if (S->pend_in) cs_.add(S->d_pend_in, d_on + (size_t)S->pend_rec * NQ, S->pend_in * NQ * 4);
-        if (S->pend_pre) cs_.add(S->d_pend_pre, d_pre, S->pend_pre * (NQ / 2));
-        launch_copy_segs(st, cs_);
+        if (P->pend_rec) cs_.add(P->d_pend_rec, d_on, P->pend_rec * NQ * 4);
+        if (P->pend_in) cs_.add(P->d_pend_in, d_on + (size_t)P->pend_rec * NQ, P->pend_in * NQ * 4);
+        if (P->pend_pre) cs_.add(P->d_pend_pre, d_pre, P->pend_pre * (NQ / 2));
+        if (batched)
+            cpb.add(cs_);
+        else
+            launch_copy_segs(st, cs_);
     }
-    if (cc.n_in && !ver && !kp) SCHK(hipMemcpyAsync(d_wit, wit_gf2, cc.n_in, hipMemcpyHostToDevice, st));
-    if (cc.n_in64 && !ver && !kp) SCHK(hipMemcpyAsync(d_wit64, wit_z64, cc.n_in64 * 8, hipMemcpyHostToDevice, st));
+    if (cc.n_in && !ver && !kp) SCHK(hipMemcpyAsync(d_wit, w2, cc.n_in, hipMemcpyHostToDevice, st));
+    if (cc.n_in64 && !ver && !kp) SCHK(hipMemcpyAsync(d_wit64, w64, cc.n_in64 * 8, hipMemcpyHostToDevice, st));
     // ---- verifier: the values the proof supplies for this chunk's items (verifier/online.rs:122-183), rebuilt from the
     // vectors' items [items so far, + this chunk's) -- at any bit offset
     uint32_t *d_sup_in = nullptr, *d_sup_corr = nullptr, *d_sup_rec = nullptr;
     uint64_t *d_sup_in64 = nullptr, *d_sup_corr64 = nullptr, *d_sup_rec64 = nullptr;
-    std::vector<uint64_t> src64c;  // (feeds an asynchronous copy: the chunk's final synchronisation comes before it leaves scope)
+    std::vector<uint64_t>& src64c = P->src64c;  // (feeds an asynchronous copy: the chunk's final synchronisation comes before it is written again)
     if (ver) {
-        const uint32_t SNQ = S->sup_nq;
+        const uint32_t SNQ = P->sup_nq;
         if ((rc = take(std::max<uint64_t>(cc.n_in, 1) * SNQ * 4, (void**)&d_sup_in)) || (rc = take(std::max<uint64_t>(cc.n_pre, 1) * SNQ * 4, (void**)&d_sup_corr)) ||
             (rc = take(std::max<uint64_t>(cc.n_rec, 1) * SNQ * 4, (void**)&d_sup_rec)))
             return done(rc);
         // (corrections are addressed by their transcript row: the chunk's own start behind the cs.pre0 carried rows)
-        launch_unpack_bits(st, S->d_vproof, S->d_src + 4 * R, S->d_src + 5 * R, S->d_omit_v, cc.n_in, NQ, 1, d_sup_in, SNQ, S->run.n_in);
-        launch_unpack_bits(st, S->d_vproof, S->d_src + 2 * R, S->d_src + 3 * R, S->d_omit_v, cc.n_pre - cs.pre0, NQ, 1, d_sup_corr + (size_t)cs.pre0 * SNQ,
-                           SNQ, S->run.n_pre);
-        launch_unpack_bits(st, S->d_vproof, S->d_src + 0 * R, S->d_src + 1 * R, S->d_omit_v, cc.n_rec, NQ, 0, d_sup_rec, SNQ, S->run.n_rec);
+        launch_unpack_bits(st, P->d_vproof, P->d_src + 4 * R, P->d_src + 5 * R, P->d_omit_v, cc.n_in, NQ, 1, d_sup_in, SNQ, P->run.n_in);
+        launch_unpack_bits(st, P->d_vproof, P->d_src + 2 * R, P->d_src + 3 * R, P->d_omit_v, cc.n_pre - cs.pre0, NQ, 1, d_sup_corr + (size_t)cs.pre0 * SNQ,
+                           SNQ, P->run.n_pre);
+        launch_unpack_bits(st, P->d_vproof, P->d_src + 0 * R, P->d_src + 1 * R, P->d_omit_v, cc.n_rec, NQ, 0, d_sup_rec, SNQ, P->run.n_rec);
         if (has64) {
             uint64_t* d_src64 = nullptr;
-            const uint32_t SR = S->sup_r;
+            const uint32_t SR = P->sup_r;
             if ((rc = take((size_t)6 * R * 8, (void**)&d_src64)) || (rc = take(std::max<uint64_t>(cc.n_in64, 1) * SR * 8, (void**)&d_sup_in64)) ||
                 (rc = take(std::max<uint64_t>(cc.n_corr64, 1) * SR * 8, (void**)&d_sup_corr64)) ||
                 (rc = take(std::max<uint64_t>(cc.n_rec64, 1) * SR * 8, (void**)&d_sup_rec64)))
                 return done(rc);
             // 8-byte items: the chunk's first item is a byte offset into every vector
-            src64c = S->src64;
-            const uint64_t first[3] = {S->run.n_rec64, S->run.n_corr64, S->run.n_in64};
+            src64c = P->src64;
+            const uint64_t first[3] = {P->run.n_rec64, P->run.n_corr64, P->run.n_in64};
             for (int v = 0; v < 3; v++)
                 for (uint32_t r = 0; r < R; r++) {
                     uint64_t &off = src64c[(size_t)(2 * v) * R + r], &len = src64c[(size_t)(2 * v + 1) * R + r];
@@ -629,18 +827,18 @@ static int stream_chunk_run(rv_stream* S, rv_circuit* c, uint64_t digest, size_t
                     len -= skip;
                 }
             SCHK(hipMemcpyAsync(d_src64, src64c.data(), src64c.size() * 8, hipMemcpyHostToDevice, st));
-            launch_unpack_supplied64(st, cc, S->d_vproof, d_src64, S->d_omit64_v, R, d_sup_in64, d_sup_corr64, d_sup_rec64, SR);
+            launch_unpack_supplied64(st, cc, P->d_vproof, d_src64, P->d_omit64_v, R, d_sup_in64, d_sup_corr64, d_sup_rec64, SR);
         }
     }
     // ---- masks of this chunk: CTR blocks [first_block, first_block + n_blocks) (the first one may be shared with the
     // previous chunk: its leading masks were consumed there and are simply regenerated)
-    const auto t_alloc = now();
+    if (bi == 0) t_alloc = now();
     ctx->phase(RV_PH_MASKS);
     // (verifier: the omitted player of every opened repetition is skipped, generator/batch.rs:32-34; the Z64 transcript of a
     // repetition has its own keys, online.rs:101-113)
     if (!kp) {
-        launch_aes_gf2_masks(st, S->d_rk, ver ? S->d_keep : nullptr, NQ, first_block, n_blocks, S->d_rows + (size_t)cc.row_prg_base * NQ);
-        if (n_blocks64 && d_masks64) launch_aes_z64_masks(st, ver ? S->d_rk64 : S->d_rk, ver ? S->d_keep64 : nullptr, NQ, n_blocks64, d_masks64, first_block64);
+        launch_aes_gf2_masks(st, P->d_rk, ver ? P->d_keep : nullptr, NQ, first_block, n_blocks, P->d_rows + (size_t)cc.row_prg_base * NQ);
+        if (n_blocks64 && d_masks64) launch_aes_z64_masks(st, ver ? P->d_rk64 : P->d_rk, ver ? P->d_keep64 : nullptr, NQ, n_blocks64, d_masks64, first_block64);
         ctx->count(2);
     }
     ctx->phase(-1);
@@ -648,39 +846,39 @@ static int stream_chunk_run(rv_stream* S, rv_circuit* c, uint64_t digest, size_t
     InterpParams p{};
     Interp64Params p64{};
     p.NQ = NQ;
-    p.rows = S->d_rows;
-    p.corr = S->d_corr;
+    p.rows = P->d_rows;
+    p.corr = P->d_corr;
     p.on = d_on;
     p.pre = d_pre;
     p.wit = d_wit;
-    p.err = S->d_err;
+    p.err = P->d_err;
     p64.R = R;
-    p64.wmask = S->d_wmask64;
-    p64.wcorr = S->d_wcorr64;
+    p64.wmask = P->d_wmask64;
+    p64.wcorr = P->d_wcorr64;
     p64.masks = d_masks64;
     p64.on = d_on64;
     p64.pre = d_pre64;
     p64.on_words = onw;
     p64.pre_words = prew;
     p64.wit = d_wit64;
-    p64.corr2 = S->d_corr;
-    p64.masks2 = S->d_rows;
+    p64.corr2 = P->d_corr;
+    p64.masks2 = P->d_rows;
     p64.NQ = NQ;
-    p64.err = S->d_err;
+    p64.err = P->d_err;
     if (ver) {
-        p.on_mask = S->d_onm;
+        p.on_mask = P->d_onm;
         p.sup_in = d_sup_in;
         p.sup_corr = d_sup_corr;
         p.sup_rec = d_sup_rec;
-        p.sup_nq = S->sup_nq;
-        p64.omit = S->d_omit64_v;
+        p.sup_nq = P->sup_nq;
+        p64.omit = P->d_omit64_v;
         p64.sup_in = d_sup_in64;
         p64.sup_corr = d_sup_corr64;
         p64.sup_rec = d_sup_rec64;
-        p64.sup_r = S->sup_r;
+        p64.sup_r = P->sup_r;
     }
-    if (!kp) launch_shard_init(st, S->d_err0, S->d_rows + (size_t)cc.zero_row * NQ, NQ, S->d_corr + (size_t)cc.zero_row * (NQ / 2), NQ / 2);
-    if (!kp) {
+    if (!kp) launch_shard_init(st, P->d_err0, P->d_rows + (size_t)cc.zero_row * NQ, NQ, P->d_corr + (size_t)cc.zero_row * (NQ / 2), NQ / 2);
+    if (!kp && !batched) {
         rv_shard sh;  // the level loop only needs the circuit and the context
         sh.ctx = ctx;
         sh.c = c;
@@ -690,78 +888,119 @@ static int stream_chunk_run(rv_stream* S, rv_circuit* c, uint64_t digest, size_t
         ctx->phase(-1);
         if (rc) return done(rc);
     }
-    // own events of this chunk (the compiled counters include the carried ones in front)
-    const uint64_t new_on = cc.n_on - cs.on0, new_pre = cc.n_pre - cs.pre0;
-    const uint64_t new_on64 = cc.on_words64 - cs.on_words64_0, new_pre64 = cc.pre_words64 - cs.pre_words64_0;
-    if (hashing) {
-        // ---- chunk chaining values of everything but the stream's last (possibly incomplete) chunk, into the trees
-        ctx->phase(RV_PH_HASH);
-        struct Piece {
-            IncHash* H;
-            uint64_t total, unit;  // events in the buffer, events per BLAKE3 chunk
-            uint64_t* tail;
-            int kind;
-        } pcs[4] = {{&S->h_pre, cc.n_pre, 1024, &S->pre_tail, 0},
-                    {&S->h_on, cc.n_on, 1024, &S->on_tail, 1},
-                    {&S->h_pre64, cc.pre_words64, 128, &S->pre64_tail, 2},
-                    {&S->h_on64, cc.on_words64, 128, &S->on64_tail, 3}};
-        for (Piece& pc : pcs) {
-            const uint64_t n_chunks = pc.total ? (pc.total - 1) / pc.unit : 0;  // at least one event stays behind
-            const uint64_t hashed = n_chunks * pc.unit, tail = pc.total - hashed;
-            if (n_chunks) {
-                uint32_t* cvs = nullptr;
-                if ((rc = take((size_t)n_chunks * R * 32, (void**)&cvs))) return done(rc);
-                switch (pc.kind) {
-                case 0: launch_b3_stream_bits_chunks(st, d_pre, hashed, NQ, cvs, pc.H->chunks, 0); break;
-                case 1: launch_b3_stream_chunks(st, d_on, hashed, NQ, cvs, nullptr, 0, pc.H->chunks, 0); break;
-                case 2: launch_b3_contig_chunks(st, d_pre64, prew, hashed, R, cvs, pc.H->chunks, 0); break;
-                default: launch_b3_contig_chunks(st, d_on64, onw, hashed, R, cvs, pc.H->chunks, 0); break;
-                }
-                if ((rc = inc_absorb(ctx, *pc.H, cvs, n_chunks, R))) return done(rc);
-            }
-            if (tail) {
-                switch (pc.kind) {
-                case 0: SCHK(hipMemcpyAsync(S->d_pre_tail, d_pre + hashed * (NQ / 2), tail * (NQ / 2), hipMemcpyDeviceToDevice, st)); break;
-                case 1: SCHK(hipMemcpyAsync(S->d_on_tail, d_on + hashed * NQ, tail * NQ * 4, hipMemcpyDeviceToDevice, st)); break;
-                case 2: SCHK(hipMemcpy2DAsync(S->d_pre64_tail, 128 * 8, d_pre64 + hashed, prew * 8, tail * 8, R, hipMemcpyDeviceToDevice, st)); break;
-                default: SCHK(hipMemcpy2DAsync(S->d_on64_tail, 128 * 8, d_on64 + hashed, onw * 8, tail * 8, R, hipMemcpyDeviceToDevice, st)); break;
-                }
-            }
-            *pc.tail = tail;
-        }
+    pbs[bi] = ProofBufs{d_on, d_pre, d_on64, d_pre64, onw, prew, kp};
+    pps[bi] = p;
+    pp64s[bi] = p64;
+    }
+    cpb.flush();  // (the carried events are in place before any level runs)
+    if (batched && !use_kept) {
+        // the proofs' parameter blocks go to the device in one copy out of a page-locked slot
+        const size_t o64 = (NB * sizeof(InterpParams) + 63) & ~(size_t)63, bytes = o64 + NB * sizeof(Interp64Params);
+        int slot = 0;
+        uint8_t* hp = ctx->open_slot(bytes, &slot);
+        if (!hp) return done(RV_E_NOMEM);
+        memcpy(hp, pps.data(), NB * sizeof(InterpParams));
+        memcpy(hp + o64, pp64s.data(), NB * sizeof(Interp64Params));
+        uint8_t* dp = nullptr;
+        if ((rc = take(bytes, (void**)&dp))) return done(rc);
+        SCHK(hipMemcpyAsync(dp, hp, bytes, hipMemcpyHostToDevice, st));
+        SCHK(hipEventRecord(ctx->ev_open[slot], st));
+        ctx->phase(RV_PH_INTERP);
+        launch_levels_batched(ctx, c, ver ? MODE_VERIFY : MODE_PROVE, (const InterpParams*)dp, has64 ? (const Interp64Params*)(dp + o64) : nullptr, NB);
         ctx->phase(-1);
-    } else {
+        if (hipGetLastError() != hipSuccess) return done(RV_E_DEVICE);
+    }
+    if (hashing) {
+        // ---- chunk chaining values of everything but the stream's last (possibly incomplete) chunk, into the trees: per kind of
+        // transcript the chunk hashes of every proof, then their trees (together when batched), then their tails
+        ctx->phase(RV_PH_HASH);
+        for (int kind = 0; kind < 4; kind++) {
+            const uint64_t total = kind == 0 ? cc.n_pre : kind == 1 ? cc.n_on : kind == 2 ? cc.pre_words64 : cc.on_words64;
+            const uint64_t unit = kind < 2 ? 1024 : 128;
+            const uint64_t n_chunks = total ? (total - 1) / unit : 0;  // at least one event stays behind
+            const uint64_t hashed = n_chunks * unit, tail = total - hashed;
+            std::vector<IncHash*> Hs;
+            std::vector<uint32_t*> cvsv;
+            for (size_t bi = 0; bi < NB; bi++) {
+                P = proofs[bi];
+                const ProofBufs& q = pbs[bi];
+                IncHash* H = kind == 0 ? &P->h_pre : kind == 1 ? &P->h_on : kind == 2 ? &P->h_pre64 : &P->h_on64;
+                uint64_t* tailp = kind == 0 ? &P->pre_tail : kind == 1 ? &P->on_tail : kind == 2 ? &P->pre64_tail : &P->on64_tail;
+                if (n_chunks) {
+                    uint32_t* cvs = nullptr;
+                    if ((rc = take((size_t)n_chunks * R * 32, (void**)&cvs))) return done(rc);
+                    switch (kind) {
+                    case 0: launch_b3_stream_bits_chunks(st, q.d_pre, hashed, NQ, cvs, H->chunks, 0); break;
+                    case 1: launch_b3_stream_chunks(st, q.d_on, hashed, NQ, cvs, nullptr, 0, H->chunks, 0); break;
+                    case 2: launch_b3_contig_chunks(st, q.d_pre64, q.prew, hashed, R, cvs, H->chunks, 0); break;
+                    default: launch_b3_contig_chunks(st, q.d_on64, q.onw, hashed, R, cvs, H->chunks, 0); break;
+                    }
+                    Hs.push_back(H);
+                    cvsv.push_back(cvs);
+                }
+                if (tail) {
+                    if (batched) {
+                        switch (kind) {
+                        case 0: cpb.add(P->d_pre_tail, q.d_pre + hashed * (NQ / 2), tail * (NQ / 2)); break;
+                        case 1: cpb.add(P->d_on_tail, q.d_on + hashed * NQ, tail * NQ * 4); break;
+                        case 2: cpb.add(P->d_pre64_tail, 128 * 8, q.d_pre64 + hashed, q.prew * 8, tail * 8, R); break;
+                        default: cpb.add(P->d_on64_tail, 128 * 8, q.d_on64 + hashed, q.onw * 8, tail * 8, R); break;
+                        }
+                    } else {
+                        switch (kind) {
+                        case 0: SCHK(hipMemcpyAsync(P->d_pre_tail, q.d_pre + hashed * (NQ / 2), tail * (NQ / 2), hipMemcpyDeviceToDevice, st)); break;
+                        case 1: SCHK(hipMemcpyAsync(P->d_on_tail, q.d_on + hashed * NQ, tail * NQ * 4, hipMemcpyDeviceToDevice, st)); break;
+                        case 2: SCHK(hipMemcpy2DAsync(P->d_pre64_tail, 128 * 8, q.d_pre64 + hashed, q.prew * 8, tail * 8, R, hipMemcpyDeviceToDevice, st)); break;
+                        default: SCHK(hipMemcpy2DAsync(P->d_on64_tail, 128 * 8, q.d_on64 + hashed, q.onw * 8, tail * 8, R, hipMemcpyDeviceToDevice, st)); break;
+                        }
+                    }
+                }
+                *tailp = tail;
+            }
+            if (n_chunks && (rc = batched ? inc_absorb_batch(ctx, Hs, cvsv, n_chunks, R) : inc_absorb(ctx, *Hs[0], cvsv[0], n_chunks, R))) return done(rc);
+        }
+        cpb.flush();
+        ctx->phase(-1);
+    }
+    for (size_t bi = 0; bi < NB && !hashing; bi++) {
+    P = proofs[bi];
+    kp = pbs[bi].kp;
+    uint32_t* d_on = pbs[bi].d_on;
+    uint8_t* d_pre = pbs[bi].d_pre;
+    uint64_t *d_on64 = pbs[bi].d_on64, *d_pre64 = pbs[bi].d_pre64;
+    const uint64_t onw = pbs[bi].onw, prew = pbs[bi].prew;
+    {
         // ---- openings of the challenged repetitions for this chunk's items.  Eight items make a byte, so a vector's
         // last (< 8) items wait in d_pend_* for the next chunk; what is extracted is always whole bytes.
         ctx->phase(RV_PH_OPEN);
         // the chunk's host-built tables in one page-locked blob: [dst 6R u64 | OnlineList | rec_offs64 | in_offs64 | rec_list | in_list]
-        const size_t n_recl = (size_t)S->pend_rec + cc.rec_rows.size(), n_inl = (size_t)S->pend_in + cc.in_rows.size();
+        const size_t n_recl = (size_t)P->pend_rec + cc.rec_rows.size(), n_inl = (size_t)P->pend_in + cc.in_rows.size();
         const size_t o_dst = 0, o_ol = o_dst + (size_t)6 * R * 8, o_ro = (o_ol + sizeof(OnlineList) + 7) & ~(size_t)7, o_io = o_ro + cc.rec_offs64.size() * 8,
                      o_rl = o_io + cc.in_offs64.size() * 8, o_il = o_rl + n_recl * 4, blob_bytes = o_il + n_inl * 4 + 8;
         int slot = 0;
         uint8_t* hb = ctx->open_slot(blob_bytes, &slot);
         if (!hb) return done(RV_E_NOMEM);
         uint64_t* dst = (uint64_t*)(hb + o_dst);  // per repetition: where this chunk's bytes of each vector go
-        const uint64_t by_rec = (S->run.n_rec - S->pend_rec) / 8, by_in = (S->run.n_in - S->pend_in) / 8, by_pre = (S->run.n_pre - S->pend_pre) / 8;
+        const uint64_t by_rec = (P->run.n_rec - P->pend_rec) / 8, by_in = (P->run.n_in - P->pend_in) / 8, by_pre = (P->run.n_pre - P->pend_pre) / 8;
         for (uint32_t r = 0; r < R; r++) {
-            dst[0 * R + r] = S->offs[2 * R + r] + by_rec;
-            dst[1 * R + r] = S->offs[4 * R + r] + by_in;
-            dst[2 * R + r] = S->offs[5 * R + r] + 8 * S->run.n_rec64;
-            dst[3 * R + r] = S->offs[6 * R + r] + 8 * S->run.n_corr64;
-            dst[4 * R + r] = S->offs[7 * R + r] + 8 * S->run.n_in64;
+            dst[0 * R + r] = P->offs[2 * R + r] + by_rec;
+            dst[1 * R + r] = P->offs[4 * R + r] + by_in;
+            dst[2 * R + r] = P->offs[5 * R + r] + 8 * P->run.n_rec64;
+            dst[3 * R + r] = P->offs[6 * R + r] + 8 * P->run.n_corr64;
+            dst[4 * R + r] = P->offs[7 * R + r] + 8 * P->run.n_in64;
             dst[5 * R + r] = 0;
         }
         OnlineList& ol = *(OnlineList*)(hb + o_ol);
-        ol = S->ol;
+        ol = P->ol;
         for (uint32_t k = 0; k < ol.n; k++) ol.dst[k] += by_pre;
         if (!cc.rec_offs64.empty()) memcpy(hb + o_ro, cc.rec_offs64.data(), cc.rec_offs64.size() * 8);
         if (!cc.in_offs64.empty()) memcpy(hb + o_io, cc.in_offs64.data(), cc.in_offs64.size() * 8);
         // item -> online row lists, the pending rows (now rows 0.. of this chunk's buffer) first
         uint32_t *rec_list = (uint32_t*)(hb + o_rl), *in_list = (uint32_t*)(hb + o_il);
-        for (uint32_t i = 0; i < S->pend_rec; i++) rec_list[i] = i;
-        if (!cc.rec_rows.empty()) memcpy(rec_list + S->pend_rec, cc.rec_rows.data(), cc.rec_rows.size() * 4);
-        for (uint32_t i = 0; i < S->pend_in; i++) in_list[i] = S->pend_rec + i;
-        if (!cc.in_rows.empty()) memcpy(in_list + S->pend_in, cc.in_rows.data(), cc.in_rows.size() * 4);
+        for (uint32_t i = 0; i < P->pend_rec; i++) rec_list[i] = i;
+        if (!cc.rec_rows.empty()) memcpy(rec_list + P->pend_rec, cc.rec_rows.data(), cc.rec_rows.size() * 4);
+        for (uint32_t i = 0; i < P->pend_in; i++) in_list[i] = P->pend_rec + i;
+        if (!cc.in_rows.empty()) memcpy(in_list + P->pend_in, cc.in_rows.data(), cc.in_rows.size() * 4);
         const uint64_t rec_full = n_recl & ~(size_t)7, in_full = n_inl & ~(size_t)7, pre_full = cc.n_pre & ~(uint64_t)7;
         uint8_t* db = nullptr;
         if ((rc = take(blob_bytes, (void**)&db))) return done(rc);
@@ -769,53 +1008,56 @@ static int stream_chunk_run(rv_stream* S, rv_circuit* c, uint64_t digest, size_t
         SCHK(hipEventRecord(ctx->ev_open[slot], st));
         uint64_t* d_dst = (uint64_t*)(db + o_dst);
         const uint32_t *d_rec_list = (const uint32_t*)(db + o_rl), *d_in_list = (const uint32_t*)(db + o_il);
-        if (rec_full) launch_extract_bits(st, d_on, d_rec_list, rec_full, NQ, 0, S->d_omit, d_dst + 0 * R, S->d_proof);
-        if (in_full) launch_extract_bits(st, d_on, d_in_list, in_full, NQ, 1, S->d_omit, d_dst + 1 * R, S->d_proof);
-        if (pre_full) launch_extract_from_bits(st, d_pre, pre_full, NQ, (const OnlineList*)(db + o_ol), S->d_proof);
+        if (rec_full) launch_extract_bits(st, d_on, d_rec_list, rec_full, NQ, 0, P->d_omit, d_dst + 0 * R, P->d_proof);
+        if (in_full) launch_extract_bits(st, d_on, d_in_list, in_full, NQ, 1, P->d_omit, d_dst + 1 * R, P->d_proof);
+        if (pre_full) launch_extract_from_bits(st, d_pre, pre_full, NQ, (const OnlineList*)(db + o_ol), P->d_proof);
         if (has64) {
-            launch_extract64(st, d_on64, onw, (const uint64_t*)(db + o_ro), cc.n_rec64, 1, R, S->d_omit, d_dst + 2 * R, S->d_proof);
-            launch_extract64(st, d_pre64, prew, nullptr, cc.n_corr64, 0, R, S->d_omit, d_dst + 3 * R, S->d_proof);
-            launch_extract64(st, d_on64, onw, (const uint64_t*)(db + o_io), cc.n_in64, 0, R, S->d_omit, d_dst + 4 * R, S->d_proof);
+            launch_extract64(st, d_on64, onw, (const uint64_t*)(db + o_ro), cc.n_rec64, 1, R, P->d_omit, d_dst + 2 * R, P->d_proof);
+            launch_extract64(st, d_pre64, prew, nullptr, cc.n_corr64, 0, R, P->d_omit, d_dst + 3 * R, P->d_proof);
+            launch_extract64(st, d_on64, onw, (const uint64_t*)(db + o_io), cc.n_in64, 0, R, P->d_omit, d_dst + 4 * R, P->d_proof);
         }
         // the items that do not fill a byte yet: their rows move to the pending buffers (one launch; the chunk's buffer and the
         // pending buffers are different allocations)
         const uint32_t nr = (uint32_t)(n_recl - rec_full), ni = (uint32_t)(n_inl - in_full), np = (uint32_t)(cc.n_pre - pre_full);
         {
             CopySegs cs_{};
-            for (uint32_t i = 0; i < nr; i++) cs_.add(d_on + (size_t)rec_list[rec_full + i] * NQ, S->d_pend_rec + (size_t)i * NQ, NQ * 4);
-            for (uint32_t i = 0; i < ni; i++) cs_.add(d_on + (size_t)in_list[in_full + i] * NQ, S->d_pend_in + (size_t)i * NQ, NQ * 4);
-            if (np) cs_.add(d_pre + pre_full * (NQ / 2), S->d_pend_pre, np * (NQ / 2));
-            launch_copy_segs(st, cs_);
+            for (uint32_t i = 0; i < nr; i++) cs_.add(d_on + (size_t)rec_list[rec_full + i] * NQ, P->d_pend_rec + (size_t)i * NQ, NQ * 4);
+            for (uint32_t i = 0; i < ni; i++) cs_.add(d_on + (size_t)in_list[in_full + i] * NQ, P->d_pend_in + (size_t)i * NQ, NQ * 4);
+            if (np) cs_.add(d_pre + pre_full * (NQ / 2), P->d_pend_pre, np * (NQ / 2));
+            if (batched)
+                cpb.add(cs_);
+            else
+                launch_copy_segs(st, cs_);
         }
-        S->pend_rec = nr;
-        S->pend_in = ni;
-        S->pend_pre = np;
+        P->pend_rec = nr;
+        P->pend_in = ni;
+        P->pend_pre = np;
         ctx->phase(-1);
-        if (no_wait) {
-            S->unsettled = true;
-        } else if (!kp) {  // (a chunk that ran: its error flag.  A kept chunk ran nothing -- and nothing on the host waits for its openings)
-            int err = 0;
-            if (hipMemcpyAsync(&err, S->d_err, sizeof err, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-                return done(hip_fail(hipGetLastError(), "stream chunk", __FILE__, __LINE__));
-            if (err) return done(RV_E_WITNESS_INVALID);
-        }
+    }
+    }
+    cpb.flush();
+    kp = nullptr;
+    // the kept transcripts stay a chunk for every proof or for none
+    if (p1 && S->same_cuts) {
+        size_t n_kept = 0;
+        for (rv_stream* Q : proofs) n_kept += Q->kept.count(first_op);
+        if (n_kept && n_kept != proofs.size()) drop_all_kept();
     }
     const auto t_issue = now();
-    if (hashing && no_wait) {
+    if (no_wait) {
         S->unsettled = true;
-    } else if (hashing) {
-        int err = 0;
-        if (hipMemcpyAsync(&err, S->d_err, sizeof err, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return done(hip_fail(hipGetLastError(), "stream chunk", __FILE__, __LINE__));
-        if (ver)
-            S->dev_flags |= err;  // RV_DEV_ZERO_CHECK: an AssertZero of an opened repetition (the strict verifier reads it at the end)
-        else if (err)
-            return done(RV_E_WITNESS_INVALID);
+    } else if (hashing || !use_kept) {  // (a chunk that ran: its error flags.  A kept chunk ran nothing -- and nothing on the host waits for its openings)
+        if ((rc = stream_read_errs(proofs, "stream chunk"))) return done(rc);
     }
     ctx->collect();
     const auto t_gpu = now();
-    // ---- counters
-    if (!ver) S->run.wit_hash += wit_digest(wit_gf2, cc.n_in, S->run.n_in, wit_z64, cc.n_in64, S->run.n_in64);  // (before the ordinals advance)
+    // ---- counters (the same for every proof but the witness digest)
+    if (!ver)
+        for (size_t bi = 0; bi < proofs.size(); bi++) {  // (before the ordinals advance)
+            rv_stream* Q = proofs[bi];
+            Q->run.wit_hash += wit_digest(wit_gf2 ? wit_gf2 + bi * stride2 : nullptr, cc.n_in, Q->run.n_in, wit_z64 ? wit_z64 + bi * stride64 : nullptr, cc.n_in64,
+                                          Q->run.n_in64);
+        }
     S->run.n_ops += n_ops;
     S->run.ops_hash += digest;
     if (stats) {
@@ -844,6 +1086,12 @@ static int stream_chunk_run(rv_stream* S, rv_circuit* c, uint64_t digest, size_t
     S->run.n_in64 += cc.n_in64;
     S->run.levels += cc.info.levels;
     S->run.chunks++;
+    for (size_t bi = 1; bi < proofs.size(); bi++) {
+        rv_stream* Q = proofs[bi];
+        const uint64_t wh = Q->run.wit_hash;
+        Q->run = S->run;
+        Q->run.wit_hash = wh;
+    }
     if (used_gf2) *used_gf2 = ver ? 0 : cc.n_in;  // (the verifier has no witness to advance in)
     if (used_z64) *used_z64 = ver ? 0 : cc.n_in64;
     return done(RV_OK);
@@ -865,8 +1113,8 @@ static rv_circuit* stream_take_cached(rv_stream* S, uint64_t first_op, size_t n_
     return c;
 }
 
-static int stream_chunk(rv_stream* S, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64, size_t n_z64,
-                        size_t* used_gf2, size_t* used_z64) {
+static int stream_chunk(rv_stream* S, const std::vector<rv_stream*>& proofs, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2,
+                        size_t stride2, const uint64_t* wit_z64, size_t n_z64, size_t stride64, size_t* used_gf2, size_t* used_z64) {
     ChunkStart carried;
     uint64_t digest = 0;
     rv_circuit* c = stream_take_cached(S, S->run.n_ops, n_ops, &carried, &digest);
@@ -881,7 +1129,7 @@ static int stream_chunk(rv_stream* S, const rv_op* ops, size_t n_ops, const uint
         if (rc) return rc;
         digest = ops_digest(ops, n_ops, S->run.n_ops);
     }
-    return stream_chunk_run(S, c, digest, n_ops, wit_gf2, n_gf2, wit_z64, n_z64, used_gf2, used_z64, carried);
+    return stream_chunk_run(S, proofs, c, digest, n_ops, wit_gf2, n_gf2, stride2, wit_z64, n_z64, stride64, used_gf2, used_z64, carried);
 }
 
 // worker threads of a feed (RV_STREAM_THREADS; default: the host's cores, at most 6 -- measured on the 10^7-gate circuit:
@@ -911,11 +1159,20 @@ static std::vector<size_t> stream_cuts(size_t n_ops, size_t full) {
     return cut;
 }
 
-static int stream_feed_impl(rv_stream* S, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64, size_t n_z64) {
+// H: the caller's handle -- a single stream, or a batch whose members are fed witness b at wit_gf2 + b * n_gf2, wit_z64 + b * n_z64
+static int stream_feed_impl(rv_stream* H, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64, size_t n_z64) {
     LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
-    if (!S || (n_ops && !ops)) return RV_E_ARG;
-    if (S->sticky) return S->sticky;
-    if (S->format_bad) return RV_OK;  // (a verifier stream whose proof has the wrong shape: the answer is already `false`)
+    if (!H || (n_ops && !ops)) return RV_E_ARG;
+    if (H->sticky) return H->sticky;
+    const std::vector<rv_stream*> proofs = H->running();
+    if (proofs.empty()) return RV_OK;  // (a verifier stream whose proof has the wrong shape: the answer is already `false`)
+    rv_stream* S = proofs[0];          // (the host-side state of the feed: compiled-chunk cache, counts, pass)
+    if (S->sticky) return H->sticky = S->sticky;
+    const size_t stride2 = n_gf2, stride64 = n_z64;
+    auto fail = [&](int rc) {
+        S->sticky = rc;
+        return H->sticky = rc;
+    };
     HIPCHK(hipSetDevice(S->ctx->device));
     const auto t_feed0 = std::chrono::steady_clock::now();
     const std::vector<size_t> cut = stream_cuts(n_ops, S->max_chunk_ops);  // piece i = ops [cut[i], cut[i + 1])
@@ -930,8 +1187,8 @@ static int stream_feed_impl(rv_stream* S, const rv_op* ops, size_t n_ops, const 
     if (n_threads <= 1) {
         for (size_t i = 0; i < n_pieces; i++) {
             size_t u2 = 0, u64 = 0;
-            const int rc = stream_chunk(S, ops + cut[i], cut[i + 1] - cut[i], wit_gf2, n_gf2, wit_z64, n_z64, &u2, &u64);
-            if (rc) return S->sticky = rc;
+            const int rc = stream_chunk(S, proofs, ops + cut[i], cut[i + 1] - cut[i], wit_gf2, n_gf2, stride2, wit_z64, n_z64, stride64, &u2, &u64);
+            if (rc) return fail(rc);
             advance(u2, u64);
         }
         return RV_OK;
@@ -1189,7 +1446,7 @@ static int stream_feed_impl(rv_stream* S, const rv_op* ops, size_t n_ops, const 
         const auto t1 = std::chrono::steady_clock::now();
         if (!rc) {
             size_t u2 = 0, u64 = 0;
-            rc = stream_chunk_run(S, c, pieces[i].digest, pieces[i].n, wit_gf2, n_gf2, wit_z64, n_z64, &u2, &u64, pieces[i].carried);
+            rc = stream_chunk_run(S, proofs, c, pieces[i].digest, pieces[i].n, wit_gf2, n_gf2, stride2, wit_z64, n_z64, stride64, &u2, &u64, pieces[i].carried);
             advance(u2, u64);
         }
         t_wait += std::chrono::duration<double>(t1 - t0).count();
@@ -1212,22 +1469,20 @@ static int stream_feed_impl(rv_stream* S, const rv_op* ops, size_t n_ops, const 
     if (stats)
         fprintf(stderr, "[rv stream] feed of %zu pieces on %u threads: %.3f s waiting for compiled pieces, %.3f s running them\n", n_pieces, n_threads,
                 t_wait, t_run);
-    if (rc) return S->sticky = rc;
+    if (rc) return fail(rc);
     return RV_OK;
 }
 
 // the one wait of a feed whose chunks were issued without one each (stream_chunk_run: no_wait): the error flags they left
-static int stream_feed_settle(rv_stream* S) {
-    if (!S || !S->unsettled) return RV_OK;
+static int stream_feed_settle(rv_stream* H) {
+    if (!H) return RV_OK;
+    const std::vector<rv_stream*> proofs = H->running();
+    if (proofs.empty() || !proofs[0]->unsettled) return RV_OK;
+    rv_stream* S = proofs[0];
     S->unsettled = false;
-    int err = 0;
-    if (hipMemcpyAsync(&err, S->d_err, sizeof err, hipMemcpyDeviceToHost, S->ctx->stream) != hipSuccess || hipStreamSynchronize(S->ctx->stream) != hipSuccess)
-        return S->sticky = hip_fail(hipGetLastError(), "stream feed", __FILE__, __LINE__);
-    if (S->pass == 3)
-        S->dev_flags |= err;  // RV_DEV_ZERO_CHECK (the strict verifier reads it at the end)
-    else if (err)
-        return S->sticky = RV_E_WITNESS_INVALID;
-    return RV_OK;
+    const int rc = stream_read_errs(proofs, "stream feed");  // (the verifier: RV_DEV_ZERO_CHECK, read by the strict verifier at the end)
+    if (rc) S->sticky = H->sticky = rc;
+    return rc;
 }
 
 extern "C" int rv_stream_feed(rv_stream* S, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
@@ -1270,7 +1525,7 @@ static int stream_final_digests(rv_stream* S) {
 
 // end of pass 1: the four stream digests, the per-repetition commitments, comm and the challenge -- all on the device
 static int stream_commit_impl(rv_stream* S, uint8_t comm_out[RV_HASH_SIZE]) {
-    if (!S) return RV_E_ARG;
+    if (!S || !S->bat.empty()) return RV_E_ARG;  // (a batch of several proofs commits with rv_stream_commit_batch)
     if (S->sticky) return S->sticky;
     if (S->pass != 1) return RV_E_ARG;
     rv_ctx* ctx = S->ctx;
@@ -1340,6 +1595,7 @@ extern "C" int rv_stream_same_cuts(rv_stream* S) {
     if (S->sticky) return S->sticky;
     if (S->pass != 1) return RV_E_ARG;  // (a promise about pass 2, made during pass 1; a verifier stream has one pass)
     S->same_cuts = true;
+    for (rv_stream* m : S->bat) m->same_cuts = true;
     return RV_OK;
 }
 
@@ -1356,6 +1612,7 @@ static int stream_finish_impl(rv_stream* S, uint8_t** proof, size_t* proof_len) 
     if (!S || !proof || !proof_len) return RV_E_ARG;
     *proof = nullptr;
     *proof_len = 0;
+    if (!S->bat.empty()) return RV_E_ARG;  // (rv_stream_finish_batch)
     if (S->sticky) return S->sticky;
     if (S->pass != 2) return RV_E_ARG;
     if (!(S->run == S->tot)) return S->sticky = RV_E_ARG;  // pass 2 was not fed what pass 1 was
@@ -1419,6 +1676,25 @@ extern "C" int rv_stream_finish(rv_stream* S, uint8_t** proof, size_t* proof_len
 extern "C" int rv_stream_get_info(const rv_stream* S, rv_stream_info* info) {
     if (!S || !info) return RV_E_ARG;
     memset(info, 0, sizeof *info);
+    if (!S->bat.empty()) {  // a batch: the stream's counts (every proof's are the same) and the device bytes of all proofs together
+        bool counted = false;
+        for (const rv_stream* m : S->bat) {
+            rv_stream_info mi;
+            rv_stream_get_info(m, &mi);
+            if (!counted && !m->format_bad) {
+                counted = true;
+                info->n_ops = mi.n_ops, info->chunks = mi.chunks, info->levels = mi.levels, info->gf2_masks = mi.gf2_masks, info->z64_masks = mi.z64_masks;
+                info->gf2_muls = mi.gf2_muls, info->z64_muls = mi.z64_muls;
+            }
+            info->wire_store_bytes += mi.wire_store_bytes;
+            info->peak_chunk_bytes += mi.peak_chunk_bytes;
+            info->hash_state_bytes += mi.hash_state_bytes;
+            info->proof_bytes += mi.proof_bytes;
+            info->kept_mib += mi.kept_mib;
+        }
+        info->pass = (uint32_t)S->pass;
+        return RV_OK;
+    }
     const StreamTotals& t = S->pass == 1 ? S->run : S->tot;
     info->n_ops = t.n_ops;
     info->chunks = t.chunks;
@@ -1535,7 +1811,7 @@ extern "C" int rv_stream_verify_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_
 }
 
 static int stream_verify_finish_impl(rv_stream* S, uint32_t flags, int* ok) {
-    if (!S || !ok || S->pass != 3) return RV_E_ARG;
+    if (!S || !ok || S->pass != 3 || !S->bat.empty()) return RV_E_ARG;
     if (!verify_flags_ok(flags)) return RV_E_ARG;
     *ok = 0;
     if (S->format_bad) return RV_OK;
@@ -1611,5 +1887,228 @@ extern "C" int rv_prove_streaming(rv_ctx* ctx, const rv_op* ops, size_t n_ops, s
     if (info) rv_stream_get_info(S, info);
     rv_stream_abort(S);
     lap("released");
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------
+// BATCHES: B witnesses (prover) or B proofs (verifier) of one statement over ONE fed op list.  The handle's members are complete
+// single-proof streams; a feed compiles, relocates and uploads every chunk once and runs it for all members (stream_chunk_run),
+// so B proofs cost one stream's host work -- the part that paces a streamed GF(2) proof -- plus B times the chunks' device work.
+// ------------------------------------------------------------------------------------
+// B wire stores must fit in half of what the device has free (plus what the context's arena holds idle): the batch is not split
+static int stream_batch_fits(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch) {
+    constexpr uint64_t R = rv_stream::R, NQ = rv_stream::NQ;
+    const long double one = (long double)gf2_wires * (NQ * 4 + NQ / 2) + (long double)(1 + z64_wires) * R * 72;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return hip_fail(hipGetLastError(), "hipMemGetInfo", __FILE__, __LINE__);
+    if (one * (long double)batch > ((long double)free_b + (long double)ctx->cached_bytes) / 2) {
+        g_last_error = "the batch's wire stores exceed half of the free device memory";
+        return RV_E_NOMEM;
+    }
+    return RV_OK;
+}
+
+static int stream_begin_batch_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch, const uint8_t* seeds, size_t max_chunk_ops,
+                                   rv_stream** out) {
+    if (!ctx || !out) return RV_E_ARG;
+    *out = nullptr;
+    if (!batch) return RV_E_ARG;
+    if (gf2_wires > 0x3FFFFFFFull || z64_wires > 0x3FFFFFFFull) return RV_E_UNSUPPORTED;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (batch == 1) return stream_begin_impl(ctx, z64_wires, gf2_wires, seeds, max_chunk_ops, out);  // (a single stream, as rv_stream_begin)
+    int rc;
+    if ((rc = stream_batch_fits(ctx, z64_wires, gf2_wires, batch))) return rc;
+    rv_stream* H = new rv_stream();
+    H->ctx = ctx;
+    H->z64_wires = z64_wires;
+    H->gf2_wires = gf2_wires;
+    for (size_t b = 0; b < batch; b++) {
+        rv_stream* m = nullptr;
+        if ((rc = stream_begin_impl(ctx, z64_wires, gf2_wires, seeds ? seeds + b * RV_TOTAL_REPS * RV_KEY_SIZE : nullptr, max_chunk_ops, &m))) {
+            rv_stream_abort(H);
+            return rc;
+        }
+        H->bat.push_back(m);
+    }
+    for (rv_stream* m : H->bat) m->keep_cap /= batch;  // (RV_STREAM_KEEP_MB is the budget of the whole batch)
+    *out = H;
+    return RV_OK;
+}
+
+extern "C" int rv_stream_begin_batch(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch, const uint8_t* seeds, size_t max_chunk_ops,
+                                     rv_stream** out) {
+    try {
+        return stream_begin_batch_impl(ctx, z64_wires, gf2_wires, batch, seeds, max_chunk_ops, out);
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}
+
+static int stream_commit_batch_impl(rv_stream* S, uint8_t* comms) {
+    if (!S) return RV_E_ARG;
+    if (S->bat.empty()) return stream_commit_impl(S, comms);
+    if (S->sticky) return S->sticky;
+    if (S->pass != 1) return RV_E_ARG;
+    HIPCHK(hipSetDevice(S->ctx->device));
+    for (size_t b = 0; b < S->bat.size(); b++) {
+        const int rc = stream_commit_impl(S->bat[b], comms ? comms + b * RV_HASH_SIZE : nullptr);
+        if (rc) return S->sticky = rc;
+    }
+    S->pass = 2;
+    return RV_OK;
+}
+
+extern "C" int rv_stream_commit_batch(rv_stream* S, uint8_t* comms) {
+    try {
+        return stream_commit_batch_impl(S, comms);
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}
+
+static int stream_finish_batch_impl(rv_stream* S, uint8_t** proofs, size_t* proof_lens) {
+    if (!S || !proofs || !proof_lens) return RV_E_ARG;
+    if (S->bat.empty()) return stream_finish_impl(S, proofs, proof_lens);
+    const size_t B = S->bat.size();
+    for (size_t b = 0; b < B; b++) proofs[b] = nullptr, proof_lens[b] = 0;
+    if (S->sticky) return S->sticky;
+    if (S->pass != 2) return RV_E_ARG;
+    HIPCHK(hipSetDevice(S->ctx->device));
+    for (size_t b = 0; b < B; b++) {
+        const int rc = stream_finish_impl(S->bat[b], &proofs[b], &proof_lens[b]);
+        if (rc) {  // (pass 2 was not fed what pass 1 was, for this witness or the stream: no proof comes out)
+            for (size_t k = 0; k < b; k++) rv_free(proofs[k]), proofs[k] = nullptr, proof_lens[k] = 0;
+            return S->sticky = rc;
+        }
+    }
+    S->sticky = RV_E_ARG;  // a finished stream takes no further calls (rv_stream_abort releases it)
+    return RV_OK;
+}
+
+extern "C" int rv_stream_finish_batch(rv_stream* S, uint8_t** proofs, size_t* proof_lens) {
+    try {
+        return stream_finish_batch_impl(S, proofs, proof_lens);
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}
+
+// one member of a verifier batch: a proof that cannot be parsed, or that the verifier's slots cannot take, is a member that runs
+// nothing and answers `false` (rv_verify_batch's rule), like one with the wrong repetition counts
+static int stream_verify_member(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, const uint8_t* proof, size_t proof_len, size_t max_chunk_ops,
+                                rv_stream** out) {
+    int rc = stream_verify_begin_impl(ctx, z64_wires, gf2_wires, proof, proof_len, max_chunk_ops, out);
+    if (rc == RV_E_PROOF_MALFORMED) {
+        rv_stream* S = new rv_stream();
+        S->ctx = ctx;
+        S->pass = 3;
+        S->format_bad = true;
+        S->h_proof = proof;
+        S->proof_len = proof_len;
+        *out = S;
+        rc = RV_OK;
+    }
+    return rc;
+}
+
+static int stream_verify_begin_batch_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch, const uint8_t* const* proofs,
+                                          const size_t* proof_lens, size_t max_chunk_ops, rv_stream** out) {
+    if (!ctx || !out || !proofs || !proof_lens) return RV_E_ARG;
+    *out = nullptr;
+    if (!batch) return RV_E_ARG;
+    for (size_t b = 0; b < batch; b++)
+        if (!proofs[b]) return RV_E_ARG;
+    if (gf2_wires > 0x3FFFFFFFull || z64_wires > 0x3FFFFFFFull) return RV_E_UNSUPPORTED;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (batch == 1) return stream_verify_member(ctx, z64_wires, gf2_wires, proofs[0], proof_lens[0], max_chunk_ops, out);
+    int rc;
+    if ((rc = stream_batch_fits(ctx, z64_wires, gf2_wires, batch))) return rc;
+    rv_stream* H = new rv_stream();
+    H->ctx = ctx;
+    H->z64_wires = z64_wires;
+    H->gf2_wires = gf2_wires;
+    H->pass = 3;
+    for (size_t b = 0; b < batch; b++) {
+        rv_stream* m = nullptr;
+        if ((rc = stream_verify_member(ctx, z64_wires, gf2_wires, proofs[b], proof_lens[b], max_chunk_ops, &m))) {
+            rv_stream_abort(H);
+            return rc;
+        }
+        H->bat.push_back(m);
+    }
+    *out = H;
+    return RV_OK;
+}
+
+extern "C" int rv_stream_verify_begin_batch(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch, const uint8_t* const* proofs,
+                                            const size_t* proof_lens, size_t max_chunk_ops, rv_stream** out) {
+    try {
+        return stream_verify_begin_batch_impl(ctx, z64_wires, gf2_wires, batch, proofs, proof_lens, max_chunk_ops, out);
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}
+
+static int stream_verify_finish_batch_impl(rv_stream* S, uint32_t flags, int* ok) {
+    if (!S || !ok) return RV_E_ARG;
+    if (S->bat.empty()) return stream_verify_finish_impl(S, flags, ok);
+    if (S->pass != 3 || !verify_flags_ok(flags)) return RV_E_ARG;
+    for (size_t b = 0; b < S->bat.size(); b++) ok[b] = 0;
+    if (S->sticky) return S->sticky;
+    for (size_t b = 0; b < S->bat.size(); b++) {
+        const int rc = stream_verify_finish_impl(S->bat[b], flags, &ok[b]);
+        if (rc == RV_E_PROOF_MALFORMED) {
+            ok[b] = 0;  // (rejected alone)
+        } else if (rc) {
+            for (size_t k = 0; k < S->bat.size(); k++) ok[k] = 0;
+            return S->sticky = rc;
+        }
+    }
+    return RV_OK;
+}
+
+extern "C" int rv_stream_verify_finish_batch(rv_stream* S, uint32_t flags, int* ok) {
+    try {
+        return stream_verify_finish_batch_impl(S, flags, ok);
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}
+
+// both passes of a batch over an op array that is already in host memory
+extern "C" int rv_prove_streaming_batch(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, size_t batch,
+                                        const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64, size_t n_z64, const uint8_t* seeds,
+                                        size_t max_chunk_ops, uint8_t** proofs, size_t* proof_lens, rv_stream_info* info) {
+    if (!ctx || !proofs || !proof_lens || !batch) return RV_E_ARG;
+    rv_stream* S = nullptr;
+    int rc = rv_stream_begin_batch(ctx, z64_wires, gf2_wires, batch, seeds, max_chunk_ops, &S);
+    if (rc) return rc;
+    (void)rv_stream_same_cuts(S);  // (the same array, cut by the same rule in both passes)
+    for (int pass = 0; pass < 2 && !rc; pass++) {
+        rc = rv_stream_feed(S, ops, n_ops, wit_gf2, n_gf2, wit_z64, n_z64);
+        if (!rc && pass == 0) rc = rv_stream_commit_batch(S, nullptr);
+    }
+    if (!rc) rc = rv_stream_finish_batch(S, proofs, proof_lens);
+    if (info) rv_stream_get_info(S, info);
+    rv_stream_abort(S);
+    return rc;
+}
+
+extern "C" int rv_verify_streaming_batch(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, size_t batch,
+                                         const uint8_t* const* proofs, const size_t* proof_lens, uint32_t flags, size_t max_chunk_ops, int* ok,
+                                         rv_stream_info* info) {
+    if (!ctx || !proofs || !proof_lens || !ok || !batch) return RV_E_ARG;
+    rv_stream* S = nullptr;
+    int rc = rv_stream_verify_begin_batch(ctx, z64_wires, gf2_wires, batch, proofs, proof_lens, max_chunk_ops, &S);
+    if (rc) return rc;
+    rc = rv_stream_feed(S, ops, n_ops, nullptr, 0, nullptr, 0);
+    if (!rc) rc = rv_stream_verify_finish_batch(S, flags, ok);
+    if (info) rv_stream_get_info(S, info);
+    rv_stream_abort(S);
     return rc;
 }

@@ -11,6 +11,7 @@ The reference's README promises a streaming interface (/root/reference/README.md
 
 Device memory is bounded by the wire counts, one piece's working set and the proof; everything runs through the C-ABI.
 `StreamingVerifier` checks a proof against a gate list fed in pieces, and `StreamingEvaluator` evaluates one in the clear.
+`StreamingBatchProver` / `StreamingBatchVerifier` prove or verify several witnesses / proofs of one statement over one fed list.
 """
 from __future__ import annotations
 
@@ -141,6 +142,162 @@ def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = Tr
                                               buf, C.c_size_t(n), C.c_uint32(0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT), C.c_size_t(max_chunk_ops),
                                               C.byref(ok), C.byref(si)))
     return bool(ok.value), {k: int(getattr(si, k)) for k, _ in si._fields_}
+
+
+def _batch_seeds(seeds, batch: int):
+    if seeds is None:
+        return None
+    a = np.frombuffer(bytes(seeds), np.uint8) if isinstance(seeds, (bytes, bytearray)) else np.asarray(seeds, dtype=np.uint8)
+    return np.ascontiguousarray(a).reshape(batch, TOTAL_REPS, 16)
+
+
+def _proof_array(proofs):
+    """(kept objects, pointer array, length array) of Proof objects or bytes, read in place"""
+    n = len(proofs)
+    keep, ptrs, lens = [], (C.c_void_p * n)(), (C.c_size_t * n)()
+    for i, p in enumerate(proofs):
+        pr = p if isinstance(p, Proof) else Proof(bytes(p))
+        buf, ln = pr._buffer()
+        keep += [pr, buf]
+        ptrs[i] = C.cast(buf, C.c_void_p).value
+        lens[i] = ln
+    return keep, ptrs, lens
+
+
+def _info(si) -> dict:
+    return {k: int(getattr(si, k)) for k, _ in si._fields_}
+
+
+class StreamingBatchProver:
+    """`batch` proofs of one statement over ONE streamed op list (rv_stream_begin_batch): each piece is compiled once per pass
+    and proved for every witness.
+
+        sp = StreamingBatchProver((z64_wires, gf2_wires), batch=B, seeds=seeds)   # seeds: [B][256][16] or None
+        for ops, w2, w64 in pieces: sp.feed(ops, w2, w64)    # w2: [B][n], w64: [B][m] -- the elements these ops' Inputs consume
+        comms = sp.commit()
+        for ops, w2, w64 in pieces: sp.feed(ops, w2, w64)    # pass 2: the same ops and witnesses again
+        proofs = sp.finish()                                  # proofs[b] == Proof.new(all ops, witness b, seeds=seeds[b])
+    """
+
+    def __init__(self, wire_counts: Tuple[int, int], batch: int, seeds=None, max_chunk_ops: int = 0, ctx: Optional[Context] = None):
+        self.ctx = ctx or Context.default()
+        self.batch = int(batch)
+        self.handle = C.c_void_p()
+        if self.batch < 1:
+            raise ValueError("batch must be at least 1")
+        s = _batch_seeds(seeds, self.batch)
+        _lib.check(_lib.lib().rv_stream_begin_batch(self.ctx.handle, int(wire_counts[0]), int(wire_counts[1]), self.batch, _ptr(s),
+                                                    int(max_chunk_ops), C.byref(self.handle)))
+
+    def feed(self, ops, wits_gf2=(), wits_z64=()):
+        ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+        g = _eval_wits(wits_gf2, self.batch, np.uint8)
+        z = _eval_wits(wits_z64, self.batch, np.uint64)
+        _lib.check(_lib.lib().rv_stream_feed(self.handle, _ptr(ops), C.c_size_t(len(ops)), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z),
+                                             C.c_size_t(z.shape[1])))
+
+    same_cuts = StreamingProver.same_cuts
+
+    def commit(self) -> "list[bytes]":
+        comms = np.zeros((self.batch, 32), np.uint8)
+        _lib.check(_lib.lib().rv_stream_commit_batch(self.handle, _ptr(comms)))
+        return [comms[b].tobytes() for b in range(self.batch)]
+
+    def finish(self) -> "list[Proof]":
+        outs = (C.c_void_p * self.batch)()
+        lens = (C.c_size_t * self.batch)()
+        _lib.check(_lib.lib().rv_stream_finish_batch(self.handle, outs, lens))
+        return [Proof(_owned=(C.c_void_p(outs[b]), int(lens[b]))) for b in range(self.batch)]
+
+    info = StreamingProver.info
+    close = StreamingProver.close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
+                          ctx: Optional[Context] = None, info: Optional[dict] = None) -> "list[Proof]":
+    """rv_prove_streaming_batch: both passes over an op array in host memory for the witnesses wits_gf2 [B][n] / wits_z64
+    [B][m] (B from whichever of the two is 2-D; the other may be []); seeds [B][256][16] or None.  `info` (a dict, optional) receives the stream's figures."""
+    ctx = ctx or Context.default()
+    ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+    g0 = np.asarray(wits_gf2, dtype=np.uint8)
+    z0 = np.asarray(wits_z64, dtype=np.uint64)
+    if g0.ndim == 2:  # (the batch is the first dimension of whichever witness array is 2-D: [] for the other domain)
+        batch = g0.shape[0]
+    elif z0.ndim == 2:
+        batch = z0.shape[0]
+    else:
+        raise ValueError("wits_gf2 or wits_z64 must be [batch][n]")
+    g = _eval_wits(g0, batch, np.uint8)
+    z = _eval_wits(z0, batch, np.uint64)
+    s = _batch_seeds(seeds, batch)
+    outs = (C.c_void_p * batch)()
+    lens = (C.c_size_t * batch)()
+    si = _lib.StreamInfo()
+    _lib.check(_lib.lib().rv_prove_streaming_batch(ctx.handle, _ptr(ops), len(ops), int(wire_counts[0]), int(wire_counts[1]), batch, _ptr(g),
+                                                   g.shape[1], _ptr(z), z.shape[1], _ptr(s), int(max_chunk_ops), outs, lens, C.byref(si)))
+    if info is not None:
+        info.update(_info(si))
+    return [Proof(_owned=(C.c_void_p(outs[b]), int(lens[b]))) for b in range(batch)]
+
+
+class StreamingBatchVerifier:
+    """Proof::verify for several proofs of one statement over ONE streamed op list (rv_stream_verify_begin_batch).
+
+        sv = StreamingBatchVerifier((z64_wires, gf2_wires), proofs)
+        for ops in pieces: sv.feed(ops)
+        oks = sv.finish()       # oks[b] == verify_streaming(all ops, ..., proofs[b]); a proof that cannot be parsed is False
+    """
+
+    def __init__(self, wire_counts: Tuple[int, int], proofs, max_chunk_ops: int = 0, ctx: Optional[Context] = None):
+        self.ctx = ctx or Context.default()
+        self.handle = C.c_void_p()
+        self.batch = len(proofs)
+        if self.batch < 1:
+            raise ValueError("no proofs")
+        self._keep, ptrs, lens = _proof_array(proofs)  # (kept alive: the stream reads them until finish)
+        _lib.check(_lib.lib().rv_stream_verify_begin_batch(self.ctx.handle, int(wire_counts[0]), int(wire_counts[1]), self.batch, ptrs, lens,
+                                                           int(max_chunk_ops), C.byref(self.handle)))
+
+    feed = StreamingVerifier.feed
+
+    def finish(self, strict: bool = True) -> "list[bool]":
+        ok = (C.c_int * self.batch)()
+        _lib.check(_lib.lib().rv_stream_verify_finish_batch(self.handle, 0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT, ok))
+        return [bool(x) for x in ok]
+
+    info = StreamingProver.info
+    close = StreamingProver.close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bool = True, max_chunk_ops: int = 0,
+                           ctx: Optional[Context] = None, info: Optional[dict] = None) -> "list[bool]":
+    """rv_verify_streaming_batch: one pass over an op array in host memory for every proof -> one bool per proof"""
+    ctx = ctx or Context.default()
+    ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+    n = len(proofs)
+    if n == 0:
+        return []
+    keep, ptrs, lens = _proof_array(proofs)
+    ok = (C.c_int * n)()
+    si = _lib.StreamInfo()
+    _lib.check(_lib.lib().rv_verify_streaming_batch(ctx.handle, _ptr(ops), len(ops), int(wire_counts[0]), int(wire_counts[1]), n, ptrs, lens,
+                                                    0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT, int(max_chunk_ops), ok, C.byref(si)))
+    del keep
+    if info is not None:
+        info.update(_info(si))
+    return [bool(x) for x in ok]
 
 
 def _eval_status(st: np.ndarray, gv, zv) -> Evaluation:
