@@ -529,6 +529,36 @@ int rv_verify_shard_ex(rv_ctx *ctx, const rv_circuit *c, const uint8_t *proof, s
 int rv_verify_finish_ex(const uint8_t *proof, size_t proof_len, const uint8_t *slot_digests /* 256 x 32 */, uint32_t flags,
                         int zero_checks_ok, int *ok);
 
+/* ---- multi-GPU verification inside the library -------------------------------------------
+ * The verifier's 256 slots fall into 32 GROUPS of eight (group g = slots 8g .. 8g+7): groups 0..4 are the 40 online records
+ * in proof order, groups 5..31 the preprocessing records.  A rank verifies a set of groups; the ranks meet once, in ONE
+ * ncclAllGather of their groups' 32-byte slot digests (plus a small trailer with the zero-check flag) on the library's own
+ * stream, and every rank then decides on the host (rv_verify_finish_ex over the 256 digests: one BLAKE3 over 8 KiB).
+ * Only the proof bytes a rank reads cross PCIe: the records of its online groups (a preprocessing slot needs its seed and
+ * online commitment, 48 bytes that travel in the host-side slot arrays).  Nearly all of a proof's bytes are the 40 online
+ * records, so the partition deals the 5 online groups round-robin instead of handing them all to rank 0.
+ *
+ * rv_verify_shard_groups: the digests of groups[0 .. n_groups) (distinct values in 0..31), n_groups * 8 * 32 bytes in the
+ * order the groups are given (group g, slot i -> slot 8g+i); zero_checks_ok as rv_verify_shard_ex (which is this call on the
+ * groups of its range).  Only the byte ranges of the given online groups' records are copied to the device.  RV_E_ARG for
+ * n_groups == 0, a group >= 32, a group given twice or a NULL pointer.  Online groups listed first keep the supplied-value rows
+ * narrow (the slot order rv_verify uses). */
+int rv_verify_shard_groups(rv_ctx *ctx, const rv_circuit *c, const uint8_t *proof, size_t proof_len, const uint8_t *groups,
+                           uint32_t n_groups, uint8_t *digests /* n_groups x 8 x 32 */, int *zero_checks_ok);
+/* The groups rank `rank` of `world` verifies (host only, no GPU).  world in {1, 2, 4, 8, 16, 32}: 32/world groups per rank,
+ * every group exactly once; the online groups are dealt round-robin (rank r gets online groups r, r+world, ...) and listed
+ * first, then the preprocessing groups in ascending order fill every rank, rank after rank, to 32/world.  RV_E_ARG otherwise. */
+int rv_verify_partition(int world, int rank, uint8_t groups[32], uint32_t *n_groups);
+/* COLLECTIVE: every rank passes the same proof bytes and flags, and *ok is rv_verify_ex's answer on EVERY rank.  The format and
+ * record checks run before the all-gather, so a malformed proof gets the same return code and *ok on every rank and no rank
+ * waits for another; so does a communicator whose world does not divide 32 (RV_E_ARG).  world == 1: a device copy instead of
+ * RCCL.  c must have been compiled on the rank's own context. */
+int rv_verify_sharded(rv_comm *comm, const rv_circuit *c, const uint8_t *proof, size_t proof_len, uint32_t flags, int *ok);
+/* One process, n GPUs: a host thread per rank runs rv_verify_sharded; returns the ranks' common (rc, *ok) -- ranks that
+ * disagree (which the design rules out) give RV_E_DEVICE with rv_last_error naming them */
+int rv_verify_multi(rv_comm *const *comms, const rv_circuit *const *circuits, int n, const uint8_t *proof, size_t proof_len,
+                    uint32_t flags, int *ok);
+
 /* Many proofs of one circuit in one pass (the verifier's counterpart of rv_prove_batch; GF(2), Z64 and mixed circuits below
  * the large-circuit threshold -- larger ones verify proof after proof): ok[b] as rv_verify_ex would set it for
  * proofs[b] with the same flags.  A proof whose bytes cannot be parsed (or whose records rv_verify_ex would answer with
@@ -627,6 +657,9 @@ uint64_t rv_hook_overlap_commits(void);
  * reference's: verifier/online.rs:122-183 computes the same values).  The answer is the same either way; the tests use the
  * counter to know which path they compared.  RV_VERIFY_VC=0 turns the path off. */
 uint64_t rv_hook_verify_vc_count(void);
+/* Running total of the proof bytes this process's shard verifiers (rv_verify_shard*, rv_verify_shard_groups, hence rv_verify,
+ * rv_verify_sharded) copied host-to-device: the records of the online groups they verified, both domains. */
+uint64_t rv_hook_verify_proof_bytes(void);
 /* How often this process's evaluations (rv_evaluate, rv_evaluate_batch; the streaming evaluator once per chunk) ran each schedule:
  * out[0] = one launch per dependency level, out[1] = one workgroup per slice of witness words walking every level (csrc/eval.hip).
  * The results are the same either way. */

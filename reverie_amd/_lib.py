@@ -86,6 +86,7 @@ SYMBOLS = [
     "rv_evaluate_streaming",
     "rv_stream_begin_batch", "rv_stream_commit_batch", "rv_stream_finish_batch", "rv_prove_streaming_batch",
     "rv_stream_verify_begin_batch", "rv_stream_verify_finish_batch", "rv_verify_streaming_batch",
+    "rv_verify_shard_groups", "rv_verify_partition", "rv_verify_sharded", "rv_verify_multi", "rv_hook_verify_proof_bytes",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -98,6 +99,12 @@ ARGTYPES = {
     "rv_stream_verify_finish_batch": [_P, C.c_uint32, C.POINTER(C.c_int)],
     "rv_verify_streaming_batch": [_P, _P, _Z, _Z, _Z, _Z, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32, _Z, C.POINTER(C.c_int),
                                   C.POINTER(StreamInfo)],
+    # multi-GPU verification
+    "rv_verify_shard_groups": [_P, _P, _P, _Z, _P, C.c_uint32, _P, C.POINTER(C.c_int)],
+    "rv_verify_partition": [C.c_int, C.c_int, _P, C.POINTER(C.c_uint32)],
+    "rv_verify_sharded": [_P, _P, _P, _Z, C.c_uint32, C.POINTER(C.c_int)],
+    "rv_verify_multi": [_P, _P, C.c_int, _P, _Z, C.c_uint32, C.POINTER(C.c_int)],
+    "rv_hook_verify_proof_bytes": [],
 }
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1
@@ -148,7 +155,8 @@ def lib():
             if name in ("rv_ctx_destroy", "rv_circuit_destroy", "rv_shard_destroy", "rv_free", "rv_stream_abort", "rv_comm_destroy",
                         "rv_eval_stream_abort"):
                 fn.restype = None
-            elif name in ("rv_hook_early_proofs", "rv_hook_open_direct_proofs", "rv_hook_verify_vc_count", "rv_hook_ops_cache_hits", "rv_hook_overlap_commits"):
+            elif name in ("rv_hook_early_proofs", "rv_hook_open_direct_proofs", "rv_hook_verify_vc_count", "rv_hook_ops_cache_hits", "rv_hook_overlap_commits",
+                          "rv_hook_verify_proof_bytes"):
                 fn.restype = C.c_uint64
             elif name not in ("rv_strerror", "rv_last_error", "rv_abi_version"):
                 fn.restype = C.c_int

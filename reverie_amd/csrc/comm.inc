@@ -96,7 +96,11 @@ struct rv_comm {
     nccl_comm_t comm = nullptr;
     int world = 1, rank = 0;
     uint8_t* d_allh = nullptr;  // [256][32] gathered digests
+    // rv_verify_sharded: this rank's part (its groups' slot digests, then a VERIFY_TRAILER-byte trailer that carries its
+    // zero-check flag) and every rank's, gathered in rank order
+    uint8_t *d_vmine = nullptr, *d_vall = nullptr;
 };
+constexpr size_t VERIFY_TRAILER = 32;
 
 extern "C" int rv_comm_unique_id(uint8_t id[RV_COMM_ID_BYTES]) {
     if (!id) return RV_E_ARG;
@@ -117,7 +121,13 @@ static int comm_wrap(rv_ctx* ctx, nccl_comm_t c, int world, int rank, rv_comm** 
     m->comm = c;
     m->world = world;
     m->rank = rank;
+    const size_t part = (size_t)RV_TOTAL_REPS / (size_t)world * 32 + VERIFY_TRAILER;
     int rc = dalloc(ctx, (size_t)RV_TOTAL_REPS * 32, &m->d_allh);
+    if (!rc && (rc = dalloc(ctx, part, &m->d_vmine))) ctx->release(m->d_allh);
+    if (!rc && (rc = dalloc(ctx, part * (size_t)world, &m->d_vall))) {
+        ctx->release(m->d_allh);
+        ctx->release(m->d_vmine);
+    }
     if (rc) {
         delete m;
         return rc;
@@ -171,6 +181,8 @@ extern "C" void rv_comm_destroy(rv_comm* m) {
     (void)hipStreamSynchronize(m->ctx->stream);
     if (m->comm) (void)rccl()->CommDestroy(m->comm);
     m->ctx->release(m->d_allh);
+    m->ctx->release(m->d_vmine);
+    m->ctx->release(m->d_vall);
     delete m;
 }
 
@@ -408,4 +420,103 @@ extern "C" int rv_prove_multi(rv_comm* const* comms, const rv_circuit* const* ci
     *proof = outs[0];
     *proof_len = lens[0];
     return RV_OK;
+}
+
+
+// ---- multi-GPU verification: the verifier's 32 groups of eight slots dealt over the ranks, one all-gather of their digests
+
+extern "C" int rv_verify_partition(int world, int rank, uint8_t groups[32], uint32_t* n_groups) {
+    if (!groups || !n_groups || world < 1 || world > 32 || (32 % world) || rank < 0 || rank >= world) return RV_E_ARG;
+    const int per = 32 / world, n_online = RV_ONLINE_REPS / 8;
+    uint32_t n = 0;
+    for (int g = rank; g < n_online; g += world) groups[n++] = (uint8_t)g;  // online groups round-robin, first
+    // then the preprocessing groups in ascending order, each rank in turn filled up to `per`
+    int next = n_online;
+    for (int r = 0; r < rank; r++) next += per - (r < n_online ? (n_online - 1 - r) / world + 1 : 0);
+    while ((int)n < per) groups[n++] = (uint8_t)next++;
+    *n_groups = n;
+    return RV_OK;
+}
+
+static int verify_sharded_impl(rv_comm* m, const rv_circuit* c, const uint8_t* proof, size_t proof_len, uint32_t flags, int* ok) {
+    if (!m || !c || !proof || !ok || !verify_flags_ok(flags)) return RV_E_ARG;
+    *ok = 0;
+    rv_ctx* ctx = m->ctx;
+    if (c->ctx != ctx) return RV_E_ARG;
+    // ---- everything that can reject the proof without the GPU, before the collective: every rank sees the same bytes, so every
+    //      rank returns here with the same answer and none is left waiting in the all-gather
+    if (32 % m->world) return RV_E_ARG;  // (rv_comm_create takes any world; the verifier deals whole groups)
+    Parsed P;
+    int rc = parse_proof(proof, proof_len, P);
+    if (rc) return rc;
+    if (!format_ok(P)) return RV_OK;  // as rv_verify_ex: `false`, not an error
+    if ((rc = check_records_range(P, 0, RV_TOTAL_REPS))) return rc;
+    // ---- this rank's groups
+    uint8_t groups[32];
+    uint32_t n_groups = 0;
+    if ((rc = rv_verify_partition(m->world, m->rank, groups, &n_groups))) return rc;
+    const size_t part = (size_t)n_groups * 8 * 32 + VERIFY_TRAILER;
+    std::vector<uint8_t> mine(part, 0);
+    int zc = 1;
+    if ((rc = verify_groups_impl(ctx, c, proof, proof_len, groups, n_groups, mine.data(), &zc))) return rc;
+    mine[(size_t)n_groups * 8 * 32] = zc ? 1 : 0;
+    // ---- the one collective, on the library's stream
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    std::vector<uint8_t> all(part * (size_t)m->world);
+    HIPCHK(hipMemcpyAsync(m->d_vmine, mine.data(), part, hipMemcpyHostToDevice, st));
+    if (m->world > 1) {
+        if (rccl()->AllGather(m->d_vmine, m->d_vall, part, NCCL_UINT8, m->comm, st) != 0) return nccl_fail(1, "ncclAllGather");
+    } else {
+        HIPCHK(hipMemcpyAsync(m->d_vall, m->d_vmine, part, hipMemcpyDeviceToDevice, st));
+    }
+    HIPCHK(hipMemcpyAsync(all.data(), m->d_vall, all.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // ---- the digests back in slot order, the flags ANDed, and the decision on the host (one BLAKE3 over 8 KiB)
+    std::vector<uint8_t> dig((size_t)RV_TOTAL_REPS * 32);
+    int zc_all = 1;
+    for (int r = 0; r < m->world; r++) {
+        uint8_t g[32];
+        uint32_t n = 0;
+        if ((rc = rv_verify_partition(m->world, r, g, &n))) return rc;
+        const uint8_t* at = all.data() + (size_t)r * part;
+        for (uint32_t k = 0; k < n; k++) memcpy(dig.data() + (size_t)g[k] * 8 * 32, at + (size_t)k * 8 * 32, 8 * 32);
+        if (!at[(size_t)n * 8 * 32]) zc_all = 0;
+    }
+    return rv_verify_finish_impl(proof, proof_len, dig.data(), flags, zc_all, ok);
+}
+
+extern "C" int rv_verify_sharded(rv_comm* m, const rv_circuit* c, const uint8_t* proof, size_t proof_len, uint32_t flags, int* ok) {
+    try {
+        return verify_sharded_impl(m, c, proof, proof_len, flags, ok);
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}
+
+// one process, n GPUs: a host thread per rank runs rv_verify_sharded; every rank must come to the same (rc, ok)
+extern "C" int rv_verify_multi(rv_comm* const* comms, const rv_circuit* const* circuits, int n, const uint8_t* proof, size_t proof_len,
+                               uint32_t flags, int* ok) {
+    if (!comms || !circuits || n < 1 || !proof || !ok) return RV_E_ARG;
+    *ok = 0;
+    std::vector<int> rcs((size_t)n, RV_OK), oks((size_t)n, 0);
+    std::vector<std::string> errs((size_t)n);
+    auto run = [&](int i) {
+        rcs[(size_t)i] = rv_verify_sharded(comms[i], circuits[i], proof, proof_len, flags, &oks[(size_t)i]);
+        if (rcs[(size_t)i]) errs[(size_t)i] = g_last_error;
+    };
+    std::vector<std::thread> th;
+    for (int i = 1; i < n; i++) th.emplace_back(run, i);
+    run(0);
+    for (auto& t : th) t.join();
+    for (int i = 1; i < n; i++)
+        if (rcs[(size_t)i] != rcs[0] || oks[(size_t)i] != oks[0]) {
+            g_last_error = "rv_verify_multi: rank " + std::to_string(i) + " answered (" + std::to_string(rcs[(size_t)i]) + ", " +
+                           std::to_string(oks[(size_t)i]) + "), rank 0 (" + std::to_string(rcs[0]) + ", " + std::to_string(oks[0]) + ")";
+            return RV_E_DEVICE;
+        }
+    if (rcs[0]) g_last_error = errs[0];
+    *ok = oks[0];
+    return rcs[0];
 }

@@ -1740,9 +1740,9 @@ static int stream_verify_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wi
         return RV_OK;
     }
     // ---- the slots (verifier's order: the 40 opened repetitions first), as rv_verify_shard prepares them
-    if ((rc = check_records(P, 0, R))) return rc;
+    if ((rc = check_records_range(P, 0, R))) return rc;
     HostSlots H(R, true);
-    fill_slots(P, proof, 0, R, 0, true, H.arrays());
+    fill_slots_range(P, proof, 0, R, 0, true, H.arrays());
     // the prover's begin gives the stream its buffers and the GF(2) keys of the preprocessing slots (opened slots: overlaid below)
     rv_stream* S = nullptr;
     if ((rc = stream_begin_impl(ctx, z64_wires, gf2_wires, H.seeds.data(), max_chunk_ops, &S))) return rc;

@@ -82,12 +82,22 @@ bool format_ok(const Parsed& p) {  // ProofSingle::check_format, proof/mod.rs:11
 // ------------------------------------------------------------------------------------
 // the verifier's slots (VerifierTranscriptOnline::new, online.rs:25-119; VerifierTranscriptPreprocess::new, preprocess.rs:17-43),
 // shared by rv_verify_shard, rv_verify_batch and the streaming verifier.  Slots 0 .. 39 are the online records in proof order,
-// 40 .. 255 the preprocessing ones; a slot range starts and ends on a group of eight.
+// 40 .. 255 the preprocessing ones.  They go by GROUPS of eight (group g = slots 8g .. 8g+7: 0 .. 4 online, 5 .. 31 preprocessing);
+// a slot range starts and ends on a group.
 // ------------------------------------------------------------------------------------
-// what the online records of [slot_begin, slot_begin + slot_count) must satisfy (a proof that passed format_ok):
+// The groups of a slot range [slot_begin, slot_begin + slot_count) (multiples of 8): the range forms below are calls of the
+// group forms
+std::vector<uint8_t> range_groups(uint32_t slot_begin, uint32_t slot_count) {
+    std::vector<uint8_t> g(slot_count / 8);
+    for (uint32_t k = 0; k < slot_count / 8; k++) g[k] = (uint8_t)(slot_begin / 8 + k);
+    return g;
+}
+// what the online records of the groups groups[0 .. n_groups) must satisfy (a proof that passed format_ok):
 // RV_OK / RV_E_PROOF_MALFORMED
-int check_records(const Parsed& P, uint32_t slot_begin, uint32_t slot_count) {
-    for (uint32_t g0 = slot_begin; g0 < std::min<uint32_t>(slot_begin + slot_count, RV_ONLINE_REPS); g0 += 8) {
+int check_records(const Parsed& P, const uint8_t* groups, uint32_t n_groups) {
+    for (uint32_t k = 0; k < n_groups; k++) {
+        const uint32_t g0 = 8u * groups[k];
+        if (g0 >= RV_ONLINE_REPS) continue;
         const OnRec* o = &P.gf2.on[g0];
         const OnRec* z = &P.z64.on[g0];
         for (int i = 0; i < 8; i++) {
@@ -99,6 +109,19 @@ int check_records(const Parsed& P, uint32_t slot_begin, uint32_t slot_count) {
         }
     }
     return RV_OK;
+}
+int check_records_range(const Parsed& P, uint32_t slot_begin, uint32_t slot_count) {
+    const std::vector<uint8_t> g = range_groups(slot_begin, slot_count);
+    return check_records(P, g.data(), (uint32_t)g.size());
+}
+// The proof bytes of an online group's eight records in one domain (they are adjacent in the proof): [begin, end)
+struct Span {
+    size_t begin, end;
+};
+Span group_span(const Single& s, uint32_t group) {
+    const OnRec& a = s.on[8 * (size_t)group];
+    const OnRec& b = s.on[8 * (size_t)group + 7];
+    return {a.keys - 1, b.in + (size_t)b.n_in};  // (from the first record's omit byte to the last one's `in` vector)
 }
 // where fill_slots writes the arrays of R slots (NQ = R / 4 quad words)
 struct SlotArrays {
@@ -130,10 +153,14 @@ struct HostSlots {
                 seeds64.data(), omit64.data(), hkeys64.data(), keep64.data(), src64.data()};
     }
 };
-// The slot arrays of [slot_begin, slot_begin + R) from a proof that passed check_records: omit / omit64 start at 8 (not opened),
-// keep / keep64 at all ones, everything else at zero.  `base` is added to every src / src64 offset (the proof's place in the
-// device buffer the unpack kernels read).  The Z64 seeds, keys, omit64, keep64 and src64 are written only when has64 is set.
-void fill_slots(const Parsed& P, const uint8_t* proof, uint32_t slot_begin, uint32_t R, uint64_t base, bool has64, const SlotArrays& a) {
+// The slot arrays of the groups groups[0 .. n_groups) (R = 8 * n_groups slots; group k's slot i is slot 8 * groups[k] + i of the
+// proof) from a proof that passed check_records for them: omit / omit64 start at 8 (not opened), keep / keep64 at all ones,
+// everything else at zero.  base[2k] / base[2k + 1] is added to group k's GF(2) / Z64 src / src64 offsets (the place of its
+// records' bytes in the device buffer the unpack kernels read, minus their place in the proof; modulo 2^64).  The Z64 seeds,
+// keys, omit64, keep64 and src64 are written only when has64 is set.
+void fill_slots(const Parsed& P, const uint8_t* proof, const uint8_t* groups, uint32_t n_groups, const uint64_t* base, bool has64,
+                const SlotArrays& a) {
+    const uint32_t R = 8 * n_groups;
     const uint32_t NQ = R / 4;
     memset(a.seeds, 0, (size_t)R * 16);
     memset(a.omit, 8, R);
@@ -150,19 +177,20 @@ void fill_slots(const Parsed& P, const uint8_t* proof, uint32_t slot_begin, uint
         std::fill_n(a.keep64, NQ, 0xFFFFFFFFu);
         std::fill_n(a.src64, (size_t)6 * R, (uint64_t)0);
     }
-    for (uint32_t g0 = 0; g0 < R; g0 += 8) {
-        const uint32_t slot0 = slot_begin + g0;
+    for (uint32_t k = 0; k < n_groups; k++) {
+        const uint32_t g0 = 8 * k, slot0 = 8u * groups[k];
+        const uint64_t b2 = base[2 * k], b64 = base[2 * k + 1];
         if (slot0 < RV_ONLINE_REPS) {
             const OnRec* o = &P.gf2.on[slot0];
             const OnRec* z = &P.z64.on[slot0];
             for (int i = 0; i < 8; i++) {
                 const uint32_t r = g0 + i;
                 a.omit[r] = o[i].omit;
-                a.src[0 * R + r] = base + o[i].rec;
+                a.src[0 * R + r] = b2 + o[i].rec;
                 a.src[1 * R + r] = o[0].n_rec;
-                a.src[2 * R + r] = base + o[i].corr;
+                a.src[2 * R + r] = b2 + o[i].corr;
                 a.src[3 * R + r] = o[0].n_corr;
-                a.src[4 * R + r] = base + o[i].in;
+                a.src[4 * R + r] = b2 + o[i].in;
                 a.src[5 * R + r] = o[0].n_in;
                 a.keep[r / 4] &= ~(1u << (31 - 8 * (r % 4) - o[i].omit));  // BatchGen skips the omitted player
                 a.onm[r / 4] |= 0xFFu << (24 - 8 * (r % 4));
@@ -172,11 +200,11 @@ void fill_slots(const Parsed& P, const uint8_t* proof, uint32_t slot_begin, uint
                     // (z64/recon.rs:68-108, z64/share.rs:51-91)
                     a.omit64[r] = z[i].omit;
                     a.keep64[r / 4] &= ~(1u << (31 - 8 * (r % 4) - z[i].omit));
-                    a.src64[0 * R + r] = base + z[i].rec;
+                    a.src64[0 * R + r] = b64 + z[i].rec;
                     a.src64[1 * R + r] = std::min(z[i].n_rec, z[0].n_rec / 8 * 8);
-                    a.src64[2 * R + r] = base + z[i].corr;
+                    a.src64[2 * R + r] = b64 + z[i].corr;
                     a.src64[3 * R + r] = std::min(z[i].n_corr, z[0].n_corr / 8 * 8);
-                    a.src64[4 * R + r] = base + z[i].in;
+                    a.src64[4 * R + r] = b64 + z[i].in;
                     a.src64[5 * R + r] = std::min(z[i].n_in, z[0].n_in / 8 * 8);
                     memcpy(a.hkeys64 + (size_t)r * 128, proof + z[i].keys, 128);
                 }
@@ -194,6 +222,12 @@ void fill_slots(const Parsed& P, const uint8_t* proof, uint32_t slot_begin, uint
             }
         }
     }
+}
+// ... of the slot range [slot_begin, slot_begin + R), every offset moved by `base` (the proof's place in the device buffer)
+void fill_slots_range(const Parsed& P, const uint8_t* proof, uint32_t slot_begin, uint32_t R, uint64_t base, bool has64, const SlotArrays& a) {
+    const std::vector<uint8_t> g = range_groups(slot_begin, R);
+    const std::vector<uint64_t> b(2 * g.size(), base);
+    fill_slots(P, proof, g.data(), (uint32_t)g.size(), b.data(), has64, a);
 }
 // the quad words that hold an opened repetition, in order, into quads[NQ]: their number
 uint32_t opened_quads(const uint32_t* onm, uint32_t NQ, uint32_t* quads) {
@@ -230,13 +264,40 @@ void launch_unpack_supplied64(hipStream_t st, const Compiled& cc, const uint8_t*
 }
 }  // namespace
 
-static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* proof, size_t proof_len, uint32_t slot_begin,
-                               uint32_t slot_count, uint8_t* digests, int* zero_checks_ok);
+// proof bytes the shard verifiers copied to the device (rv_hook_verify_proof_bytes)
+static std::atomic<uint64_t> g_verify_proof_bytes{0};
+extern "C" uint64_t rv_hook_verify_proof_bytes(void) { return g_verify_proof_bytes.load(std::memory_order_relaxed); }
+
+static int verify_groups_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* proof, size_t proof_len, const uint8_t* groups,
+                              uint32_t n_groups, uint8_t* digests, int* zero_checks_ok);
+
+// RV_OK, or RV_E_ARG for an empty list, a group >= 32 or one given twice
+static int groups_ok(const uint8_t* groups, uint32_t n_groups) {
+    if (!groups || n_groups == 0 || n_groups > RV_TOTAL_REPS / 8) return RV_E_ARG;
+    uint32_t seen = 0;
+    for (uint32_t k = 0; k < n_groups; k++) {
+        if (groups[k] >= RV_TOTAL_REPS / 8 || (seen >> groups[k]) & 1u) return RV_E_ARG;
+        seen |= 1u << groups[k];
+    }
+    return RV_OK;
+}
+
+extern "C" int rv_verify_shard_groups(rv_ctx* ctx, const rv_circuit* c, const uint8_t* proof, size_t proof_len, const uint8_t* groups,
+                                      uint32_t n_groups, uint8_t* digests, int* zero_checks_ok) {
+    try {  // no C++ exception may cross the C boundary
+        return verify_groups_impl(ctx, c, proof, proof_len, groups, n_groups, digests, zero_checks_ok);
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}
 
 extern "C" int rv_verify_shard_ex(rv_ctx* ctx, const rv_circuit* c, const uint8_t* proof, size_t proof_len, uint32_t slot_begin,
                                   uint32_t slot_count, uint8_t* digests, int* zero_checks_ok) {
-    try {  // no C++ exception may cross the C boundary
-        return rv_verify_shard_impl(ctx, c, proof, proof_len, slot_begin, slot_count, digests, zero_checks_ok);
+    if (slot_count == 0 || slot_count % 8 || slot_begin % 8 || slot_begin + slot_count > RV_TOTAL_REPS) return RV_E_ARG;
+    try {
+        const std::vector<uint8_t> g = range_groups(slot_begin, slot_count);
+        return verify_groups_impl(ctx, c, proof, proof_len, g.data(), (uint32_t)g.size(), digests, zero_checks_ok);
     } catch (...) {
         g_last_error = "out of host memory";
         return RV_E_NOMEM;
@@ -248,11 +309,10 @@ extern "C" int rv_verify_shard(rv_ctx* ctx, const rv_circuit* c, const uint8_t* 
     return rv_verify_shard_ex(ctx, c, proof, proof_len, slot_begin, slot_count, digests, nullptr);
 }
 
-static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* proof, size_t proof_len, uint32_t slot_begin,
-                               uint32_t slot_count, uint8_t* digests, int* zero_checks_ok) {
+static int verify_groups_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* proof, size_t proof_len, const uint8_t* groups,
+                              uint32_t n_groups, uint8_t* digests, int* zero_checks_ok) {
     LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
-    if (!ctx || !c || !proof || !digests) return RV_E_ARG;
-    if (slot_count == 0 || slot_count % 8 || slot_begin % 8 || slot_begin + slot_count > RV_TOTAL_REPS) return RV_E_ARG;
+    if (!ctx || !c || !proof || !digests || groups_ok(groups, n_groups)) return RV_E_ARG;
     Parsed P;
     int rc = parse_proof(proof, proof_len, P);
     if (rc) return rc;
@@ -260,13 +320,40 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
     const Compiled& cc = c->cc;
     HIPCHK(hipSetDevice(ctx->device));
     if (int rs2 = ctx_stream2(ctx)) return rs2;
-    const uint32_t R = slot_count, NQ = R / 4;
+    const uint32_t R = 8 * n_groups, NQ = R / 4;
 
     // ---- host-side preparation of the slots
-    if ((rc = check_records(P, slot_begin, R))) return rc;
+    if ((rc = check_records(P, groups, n_groups))) return rc;
+    // The proof bytes the unpack kernels read: the records of the listed online groups, nothing else (a preprocessing slot's seed
+    // and online commitment go over in the host arrays).  A group's eight records are one span per domain; spans that follow each
+    // other in the proof are one run and one copy, and every run keeps its offset modulo 16 (the kernels' aligned loads see what
+    // they saw in the whole proof).  base: what fill_slots adds to a group's offsets to land in the packed runs.
+    struct Run {
+        size_t begin, end, dst;
+    };
+    std::vector<Run> runs;
+    std::vector<uint64_t> base((size_t)2 * n_groups, 0);
+    std::vector<uint32_t> run_of((size_t)2 * n_groups, 0);
+    for (int dom = 0; dom < 2; dom++)
+        for (uint32_t k = 0; k < n_groups; k++) {
+            if (8u * groups[k] >= RV_ONLINE_REPS) continue;
+            const Span sp = group_span(dom ? P.z64 : P.gf2, groups[k]);
+            if (runs.empty() || runs.back().end != sp.begin) runs.push_back({sp.begin, sp.begin, 0});
+            runs.back().end = sp.end;
+            run_of[2 * k + dom] = (uint32_t)runs.size() - 1;
+        }
+    size_t up_bytes = 0, up_total = 0;
+    for (Run& u : runs) {
+        u.dst = ((up_total + 15) & ~(size_t)15) + u.begin % 16;
+        up_total = u.dst + (u.end - u.begin);
+        up_bytes += u.end - u.begin;
+    }
+    for (uint32_t k = 0; k < n_groups; k++)
+        if (8u * groups[k] < RV_ONLINE_REPS)
+            for (int dom = 0; dom < 2; dom++) base[2 * k + dom] = (uint64_t)runs[run_of[2 * k + dom]].dst - (uint64_t)runs[run_of[2 * k + dom]].begin;
     const bool has64 = !cc.gates64.empty();
     HostSlots H(R, has64);
-    fill_slots(P, proof, slot_begin, R, 0, has64, H.arrays());
+    fill_slots(P, proof, groups, n_groups, base.data(), has64, H.arrays());
     std::vector<uint32_t> on_quads(NQ);
     on_quads.resize(opened_quads(H.onm.data(), NQ, on_quads.data()));
     const uint32_t sup_nq = supplied_nq(H.onm.data(), NQ);
@@ -275,7 +362,7 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
     rv_shard* s = new rv_shard();
     s->ctx = ctx;
     s->c = c;
-    s->rep_begin = slot_begin;
+    s->rep_begin = 8u * groups[0];  // (read by the prover's openings only)
     s->R = R;
     s->NQ = NQ;
     auto fail = [&](int code) {
@@ -289,7 +376,7 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
     auto track = [&](void* p) { s->extra.push_back(p); };
     uint32_t* d_on_quads = nullptr;
     uint8_t *d_hkeys = nullptr, *d_hco = nullptr, *d_hkeys64 = nullptr, *d_hco64 = nullptr;
-    // A small GF(2) proof goes over in ONE copy: every host array above and the proof itself are packed into the
+    // A small GF(2) proof goes over in ONE copy: every host array above and the proof's runs are packed into the
     // page-locked input staging buffer and land in one device block (ten pageable copies of ~10 us each otherwise).
     // The function waits for the stream before it returns, so the buffer is free again by the next call.
     size_t blob_bytes = 0;
@@ -300,7 +387,7 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
     };
     const size_t o_seeds = seg(H.seeds.size()), o_omit = seg(H.omit.size()), o_keep = seg((size_t)NQ * 4), o_onm = seg((size_t)NQ * 4),
                  o_onq = seg(std::max<size_t>(on_quads.size(), 1) * 4), o_hkeys = seg(H.hkeys.size()), o_hco = seg(H.hco.size()),
-                 o_hco64 = seg(H.hco64.size()), o_src = seg(H.src.size() * 8), o_proof = seg(proof_len);
+                 o_hco64 = seg(H.hco64.size()), o_src = seg(H.src.size() * 8), o_proof = seg(up_total);
     constexpr bool small_stage = true;
     bool blob = small_stage && !has64 && !g_recorder && blob_bytes <= rv_ctx::IN_STAGE_BYTES;
     if (blob && !ctx->h_in && hipHostMalloc((void**)&ctx->h_in, rv_ctx::IN_STAGE_BYTES, hipHostMallocDefault) != hipSuccess) {
@@ -330,19 +417,19 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
         memcpy(h + o_hco, H.hco.data(), H.hco.size());
         memcpy(h + o_hco64, H.hco64.data(), H.hco64.size());
         memcpy(h + o_src, H.src.data(), H.src.size() * 8);
-        memcpy(h + o_proof, proof, proof_len);
+        for (const Run& u : runs) memcpy(h + o_proof + u.dst, proof + u.begin, u.end - u.begin);
     } else {
         if ((rc = dalloc(ctx, (size_t)R * 16, &s->d_seeds)) || (rc = dalloc(ctx, (size_t)R * 128, &s->d_keys)) ||
             (rc = dalloc(ctx, R, &s->d_omit)))
             return fail(rc);
-        if ((rc = dalloc(ctx, proof_len, &d_proof))) return fail(rc);
+        if ((rc = dalloc(ctx, std::max<size_t>(up_total, 1), &d_proof))) return fail(rc);
         track(d_proof);
         if ((rc = dalloc(ctx, H.src.size(), &d_src))) return fail(rc);
         track(d_src);
         // d_proof / d_src may be filled from the SECOND stream further down (beside the mask kernels).  The arena hands blocks out
         // in the main stream's order, so the side stream first waits for everything the main stream holds NOW -- whatever used
         // these blocks last -- and nothing of this call's own kernels (they are queued after this point)
-        if (!g_recorder && proof_len >= ((size_t)4 << 20)) {
+        if (!g_recorder && up_total >= ((size_t)4 << 20)) {
             ev_arena = ctx->get_sync_event();
             s->misc_events.push_back(ev_arena);
             if (hipEventRecord(ev_arena, ctx->stream) != hipSuccess) return fail(hip_fail(hipGetLastError(), "hipEventRecord", __FILE__, __LINE__));
@@ -473,7 +560,7 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
     if (!blob && !split64) {
         hipStream_t sc = (side && ev_arena) ? ctx->stream2 : sb;
         if (sc != sb) HC(hipStreamWaitEvent(sc, ev_arena, 0));
-        HC(hipMemcpyAsync(d_proof, proof, proof_len, hipMemcpyHostToDevice, sc));
+        for (const Run& u : runs) HC(hipMemcpyAsync(d_proof + u.dst, proof + u.begin, u.end - u.begin, hipMemcpyHostToDevice, sc));
         HC(hipMemcpyAsync(d_src, H.src.data(), H.src.size() * 8, hipMemcpyHostToDevice, sc));
         if (sc != sb) {
             if (side_unpack && ev_inputs) {
@@ -503,8 +590,10 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
             s->misc_events.push_back(s->ev_sup64);
             s->mid64 = [&, s, ctx]() -> int {
                 hipStream_t sc = ctx->stream2;
-                if (hipStreamWaitEvent(sc, ev_arena, 0) != hipSuccess || hipMemcpyAsync(d_proof, proof, proof_len, hipMemcpyHostToDevice, sc) != hipSuccess ||
-                    hipStreamWaitEvent(sc, ev_inputs64, 0) != hipSuccess ||
+                bool copied = hipStreamWaitEvent(sc, ev_arena, 0) == hipSuccess;
+                for (const Run& u : runs)
+                    copied = copied && hipMemcpyAsync(d_proof + u.dst, proof + u.begin, u.end - u.begin, hipMemcpyHostToDevice, sc) == hipSuccess;
+                if (!copied || hipStreamWaitEvent(sc, ev_inputs64, 0) != hipSuccess ||
                     hipMemcpyAsync(d_src64, H.src64.data(), H.src64.size() * 8, hipMemcpyHostToDevice, sc) != hipSuccess)
                     return hip_fail(hipGetLastError(), "rv_verify: the proof's copy", __FILE__, __LINE__);
                 launch_unpack_supplied64(sc, cc, d_proof, d_src64, s->d_omit64, R, d_sup_in64, d_sup_corr64, d_sup_rec64, sup_r);
@@ -573,6 +662,7 @@ static int rv_verify_shard_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
         HC(hipStreamSynchronize(ctx->stream));
     }
     if (zero_checks_ok) *zero_checks_ok = !(dev_flags & RV_DEV_ZERO_CHECK);
+    g_verify_proof_bytes.fetch_add(up_bytes, std::memory_order_relaxed);
     ctx->collect();
     ctx->prof.calls++;
 #undef HC

@@ -27,7 +27,7 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
     std::vector<size_t> live;  // indices of the proofs that go to the GPU
     size_t max_len = 0;
     for (size_t b = 0; b < batch; b++) {
-        if (parse_proof(proofs[b], proof_lens[b], P[b]) != RV_OK || !format_ok(P[b]) || check_records(P[b], 0, RV_TOTAL_REPS) != RV_OK) continue;
+        if (parse_proof(proofs[b], proof_lens[b], P[b]) != RV_OK || !format_ok(P[b]) || check_records_range(P[b], 0, RV_TOTAL_REPS) != RV_OK) continue;
         live.push_back(b);
         max_len = std::max(max_len, proof_lens[b]);
     }
@@ -127,7 +127,7 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         uint8_t* h = h_slab + k * L.stride;
         const SlotArrays a{h + L.seeds, h + L.omit, h + L.hkeys, h + L.hco, h + L.hco64, (uint32_t*)(h + L.keep), (uint32_t*)(h + L.onm),
                            (uint64_t*)(h + L.src), h + L.seeds64, h + L.omit64, h + L.hkeys64, (uint32_t*)(h + L.keep64), (uint64_t*)(h + L.src64)};
-        fill_slots(P[b], proofs[b], 0, R, L.proof, has64, a);  // (src offsets into this proof's slot)
+        fill_slots_range(P[b], proofs[b], 0, R, L.proof, has64, a);  // (src offsets into this proof's slot)
         n_quads[k] = opened_quads(a.onm, NQ, (uint32_t*)(h + L.quads));
         memcpy(h + L.proof, proofs[b], proof_lens[b]);
     };

@@ -10,6 +10,9 @@ collective is an all-gather of 32-byte digests (8 KiB total — RCCL over xGMI w
 own repetitions, and rank 0 concatenates the openings in ascending repetition order
 (proof/mod.rs:200-221) — a point-to-point collection of output, not a reduction.
 
+The verifier shards the same way inside the library (LibComm.verify, rv_verify_sharded): its 32 groups of eight
+slots are dealt over the ranks by verify_partition and the ranks meet in one all-gather of slot digests.
+
 `backend` supplies the per-shard compute.  The product backend is HipShardBackend (C-ABI,
 GPU).  Tests inject an oracle-backed stand-in to exercise this orchestration on CPU.
 """
@@ -23,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from .ops import TOTAL_REPS
-from .proof import Circuit, _ptr, challenge, combine_digests
+from .proof import Circuit, Proof, _ptr, challenge, combine_digests
 
 
 def shard_range(rank: int, world: int) -> Tuple[int, int]:
@@ -31,6 +34,22 @@ def shard_range(rank: int, world: int) -> Tuple[int, int]:
         raise ValueError("world size must divide 32 packed groups")
     n = TOTAL_REPS // world
     return rank * n, n
+
+
+def verify_partition(world: int, rank: int) -> List[int]:
+    """The verifier's groups of eight slots rank `rank` of `world` checks (rv_verify_partition): the online groups 0..4
+    round-robin and first, then preprocessing groups up to 32 / world"""
+    groups = np.zeros(32, np.uint8)
+    n = C.c_uint32()
+    _lib.check(_lib.lib().rv_verify_partition(C.c_int(world), C.c_int(rank), _ptr(groups), C.byref(n)))
+    return [int(g) for g in groups[:n.value]]
+
+
+def _proof_buffer(proof):
+    """(Proof, pointer, length) of a Proof or of proof bytes, without copying a Proof's buffer (the Proof keeps it alive)"""
+    pf = proof if isinstance(proof, Proof) else Proof(bytes(proof))
+    buf, n = pf._buffer()
+    return pf, buf, n
 
 
 class HipShardBackend:
@@ -144,6 +163,19 @@ class HipShardBackend:
 
     def destroy(self, shard):
         _lib.lib().rv_shard_destroy(shard[0])
+
+    def verify_groups(self, proof, groups) -> Tuple[np.ndarray, bool]:
+        """rv_verify_shard_groups: the slot digests of the given verifier groups, for callers that bring their own collective
+        -> (digests [len(groups) * 8, 32] in the order of `groups`, zero_checks_ok); hand them, placed by slot, to
+        rv_verify_finish_ex"""
+        pf, buf, n = _proof_buffer(proof)
+        g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint8))
+        out = np.zeros((len(g) * 8, 32), np.uint8)
+        zc = C.c_int()
+        _lib.check(_lib.lib().rv_verify_shard_groups(self.circuit.ctx.handle, self.circuit.handle, buf, C.c_size_t(n), _ptr(g),
+                                                     C.c_uint32(len(g)), _ptr(out), C.byref(zc)))
+        del pf
+        return out, bool(zc.value)
 
 
 def assemble_device_parts(comm: bytes, bufs, all_lens) -> bytes:
@@ -289,9 +321,9 @@ def prove_sharded(backend, wit_gf2, wit_z64, seeds, group=None, device_resident:
 
 
 class LibComm:
-    """This rank's place in a group of GPUs proving together INSIDE the library (rv_comm_*, rv_prove_sharded): the
-    library owns the RCCL communicator, the digests' all-gather runs on its own stream and the openings go to rank 0
-    with ncclSend/ncclRecv.  torch.distributed (any backend) is only used once, to hand rank 0's communicator id to
+    """This rank's place in a group of GPUs proving and verifying together INSIDE the library (rv_comm_*, rv_prove_sharded,
+    rv_verify_sharded): the library owns the RCCL communicator, the digests' all-gather runs on its own stream and the
+    openings go to rank 0 with ncclSend/ncclRecv.  torch.distributed (any backend) is only used once, to hand rank 0's communicator id to
     the other ranks; with world == 1 nothing is exchanged."""
 
     def __init__(self, circuit: Circuit, group=None):
@@ -323,6 +355,16 @@ class LibComm:
         _lib.check(_lib.lib().rv_prove_sharded(self.handle, self.circuit.handle, _ptr(g), C.c_size_t(len(g)), _ptr(z), C.c_size_t(len(z)),
                                                _ptr(s), C.byref(out), C.byref(n)))
         return (C.c_void_p(out.value), n.value) if out.value else None
+
+    def verify(self, proof, strict: bool = True) -> bool:
+        """rv_verify_sharded (collective): every rank passes the same proof and gets rv_verify_ex's answer; each verifies its
+        groups (verify_partition) and the ranks meet in one all-gather of their digests"""
+        pf, buf, n = _proof_buffer(proof)
+        ok = C.c_int()
+        flags = 0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT
+        _lib.check(_lib.lib().rv_verify_sharded(self.handle, self.circuit.handle, buf, C.c_size_t(n), C.c_uint32(flags), C.byref(ok)))
+        del pf
+        return bool(ok.value)
 
     def close(self):
         if self.handle:
