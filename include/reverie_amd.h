@@ -150,6 +150,21 @@ int rv_circuit_compile(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_w
 #define RV_COMPILE_KEEP_WIRES 2u
 int rv_circuit_compile_ex(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                           rv_circuit **out);
+/* RV_COMPILE_DEVICE: the op list is uploaded and compiled on the context's GPU (csrc/compile_dev.hip) into a circuit identical field
+ * by field to the host compiler's, so every proof, verification and evaluation is byte-identical.  The device path takes whole
+ * programs of GF(2) ops (no Z64, B2A or SizeHint op) whose plain compile keeps every Xor of two rows materialised: not with
+ * RV_COMPILE_KEEP_WIRES, RV_COMPILE_WHOLE_PROVER or RV_LAZY_K, and not for the deep, narrow circuits the host compiler recompiles with
+ * lazy sums (AES-128, SHA-256).  Everything else, op-list errors included, is compiled by the host compiler, with its error codes. */
+#define RV_COMPILE_DEVICE 4u
+/* The same for an op array already in device memory (n_ops packed 24-byte records on the context's device, e.g. a torch tensor);
+ * the caller keeps ownership of d_ops and must have finished writing it.  A program the device path does not take is copied to the
+ * host and compiled there. */
+int rv_circuit_compile_device(rv_ctx *ctx, const rv_op *d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
+                              rv_circuit **out);
+/* Compile flags of the context's own compiles (rv_prove_ops, rv_verify_ops); 0 (the default) or RV_COMPILE_DEVICE.  Under
+ * RV_COMPILE_DEVICE rv_prove_ops compiles the plain form on the device instead of the RV_COMPILE_WHOLE_PROVER one: the same proof
+ * bytes, a faster first proof of a wide circuit, 2-4 % slower proofs of it afterwards.  RV_E_ARG for any other bit. */
+int rv_ctx_set_compile_flags(rv_ctx *ctx, uint32_t flags);
 void rv_circuit_destroy(rv_circuit *c);
 
 typedef struct rv_circuit_info {
@@ -624,6 +639,14 @@ int rv_hook_compile_info(const rv_op *ops, size_t n_ops, size_t z64_wires, size_
  * compiler declined the program (B2A gates, an error in the op list) -- the sequential result is what rv_circuit_compile uses.
  * Returns the sequential compiler's status (RV_OK or the error the reference raises while stepping, single.rs:106-156). */
 int rv_hook_compile_compare(const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, int threads, int *diff);
+/* The device compiler against the host compiler (compile_ops) on the same program: *path = 1 when the device path compiled it, 0
+ * when it handed it to the host compiler; *diff = 0 when the two results are identical field by field (as rv_hook_compile_compare).
+ * Returns the host compiler's status. */
+int rv_hook_compile_compare_device(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, int *path,
+                                   int *diff);
+/* Per-phase times of this process's last device compile, ms from HIP events: out[0] classify and count, [1] last writers and consumer
+ * lists, [2] values and levels (topological rounds), [3] rows, sort and tables, [4] the host's copy; out[5] = rounds launched. */
+int rv_hook_compile_device_laps(double out[6]);
 /* DomainGF2::reconstruct (gf2/domain.rs:47-63) on n packed u64 shares (bit 63 - (8*rep + player)) -> n ReconGF2 words
  * (one 0x00/0xFF byte per repetition), through the interpreter's own device function */
 int rv_hook_gf2_reconstruct(rv_ctx *ctx, const uint64_t *shares, size_t n, uint64_t *out);

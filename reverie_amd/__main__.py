@@ -156,6 +156,9 @@ def build_parser():
                          "and one chunk (an rvops file is read piece by piece)" % GPU_EVAL_MIN_OPS)
     ap.add_argument("--max-chunk-ops", type=int, default=0,
                     help="oneshot --evaluator stream: ops per device chunk (0 = the library's default, 2^18)")
+    ap.add_argument("--compiler", default="host", choices=["host", "device"],
+                    help="prove / verify / oneshot-zk: compile the program on the host (default) or on the GPU (RV_COMPILE_DEVICE: GF(2) "
+                         "programs; anything else still compiles on the host); the proof bytes are the same")
     ap.add_argument("--reference-compat", action="store_true",
                     help="verify / oneshot-zk: RV_VERIFY_REFERENCE_COMPAT -- answer exactly like the reference's verifier, which "
                          "accepts proofs whose opened repetitions fail an AssertZero or name another omitted player than the "
@@ -194,7 +197,7 @@ def main(argv=None) -> int:
         return 0
     from .proof import Circuit, Proof
 
-    circuit = Circuit(prog, wc)
+    circuit = Circuit(prog, wc, device_compile=a.compiler == "device")
     if a.operation in ("prove", "oneshot-zk"):
         wit = parse_witness(open(a.witness_path, "rb").read())
         print("Evaluating program in ~zero knowledge~")

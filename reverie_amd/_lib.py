@@ -87,6 +87,7 @@ SYMBOLS = [
     "rv_stream_begin_batch", "rv_stream_commit_batch", "rv_stream_finish_batch", "rv_prove_streaming_batch",
     "rv_stream_verify_begin_batch", "rv_stream_verify_finish_batch", "rv_verify_streaming_batch",
     "rv_verify_shard_groups", "rv_verify_partition", "rv_verify_sharded", "rv_verify_multi", "rv_hook_verify_proof_bytes",
+    "rv_circuit_compile_device", "rv_ctx_set_compile_flags", "rv_hook_compile_compare_device", "rv_hook_compile_device_laps",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -105,10 +106,16 @@ ARGTYPES = {
     "rv_verify_sharded": [_P, _P, _P, _Z, C.c_uint32, C.POINTER(C.c_int)],
     "rv_verify_multi": [_P, _P, C.c_int, _P, _Z, C.c_uint32, C.POINTER(C.c_int)],
     "rv_hook_verify_proof_bytes": [],
+    # the device compiler
+    "rv_circuit_compile_device": [_P, _P, _Z, _Z, _Z, C.c_uint32, C.POINTER(C.c_void_p)],
+    "rv_ctx_set_compile_flags": [_P, C.c_uint32],
+    "rv_hook_compile_compare_device": [_P, _P, _Z, _Z, _Z, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "rv_hook_compile_device_laps": [C.POINTER(C.c_double)],
 }
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1
 RV_COMPILE_KEEP_WIRES = 2  # the circuit keeps every wire's final value form: rv_evaluate can return wire values
+RV_COMPILE_DEVICE = 4  # compiled on the GPU (GF(2) programs at K = 1; anything else by the host compiler): the same circuit
 RV_VERIFY_REFERENCE_COMPAT = 2  # the reference verifier's two unchecked conditions stay unchecked
 
 _lib = None

@@ -22,6 +22,7 @@
 
 #include "b3.h"
 #include "compile.h"
+#include "compile_dev.h"
 #include "internal.h"
 #include "launch.h"
 #include "ldsrun.h"
@@ -225,6 +226,7 @@ struct rv_ctx {
         uint64_t stamp;
     };
     std::vector<OpsEntry> ops_cache;
+    uint32_t compile_flags = 0;  // rv_ctx_set_compile_flags: RV_COMPILE_DEVICE = the cold compiles of rv_prove_ops / rv_verify_ops on the GPU
     uint64_t ops_clock = 0;
     std::vector<hipEvent_t> sync_pool;
     hipEvent_t get_sync_event() {
@@ -615,6 +617,7 @@ struct rv_circuit {
     int staged_slot = -1;             // ... in this slot of rv_ctx::h_ring
     bool upload_pending = false;      // circuit_upload(async_staged) left the copies in flight on the context's stream
     Compiled cc;  // gates kept on the host too (level table, counts)
+    bool dev_compiled = false;  // compiled on the device (compile_dev.hip): d_gates, d_rec_rows, d_in_rows are already in HBM
     Gate* d_gates = nullptr;
     uint32_t* d_rec_rows = nullptr;
     uint32_t* d_in_rows = nullptr;
@@ -726,12 +729,15 @@ static size_t scratch_bytes_for(const Compiled& cc, uint32_t R) {
 }
 
 static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
-                                  rv_circuit** out);
+                                  rv_circuit** out, const rv_op* d_ops = nullptr);
 static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged = false);
 
 extern "C" int rv_circuit_compile_ex(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                                      rv_circuit** out) {
-    if (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES)) return RV_E_ARG;
+    if (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE)) {
+        g_last_error = "rv_circuit_compile_ex: unknown flag bits";
+        return RV_E_ARG;
+    }
     try {  // no C++ exception may cross the C boundary
         return rv_circuit_compile_impl(ctx, ops, n_ops, z64_wires, gf2_wires, flags, out);
     } catch (...) {
@@ -745,9 +751,59 @@ extern "C" int rv_circuit_compile(rv_ctx* ctx, const rv_op* ops, size_t n_ops, s
     return rv_circuit_compile_ex(ctx, ops, n_ops, z64_wires, gf2_wires, 0, out);
 }
 
+// The device compiler's memory comes from the context arena (compile_dev.h)
+static int ctx_dev_alloc(void* self, size_t bytes, void** out) { return ((rv_ctx*)self)->alloc(bytes, out); }
+static void ctx_dev_release(void* self, void* p) { ((rv_ctx*)self)->release(p); }
+static DevAlloc ctx_dev_allocator(rv_ctx* ctx) {
+    DevAlloc a;
+    a.self = ctx;
+    a.alloc = ctx_dev_alloc;
+    a.release = ctx_dev_release;
+    return a;
+}
+// the requests the device compiler hands to the host compiler whatever the op list holds (compile_dev.h): no upload for them
+static bool device_compile_possible(uint32_t flags) {
+    return !(flags & (RV_COMPILE_KEEP_WIRES | RV_COMPILE_WHOLE_PROVER)) && !getenv("RV_LAZY_K");
+}
+static std::mutex g_dev_laps_mu;
+static DevCompileLaps g_dev_laps;
+// the device compile of d_ops (device memory) into `cc` (and, with keep, the circuit's gate / ordinal arrays in HBM); RV_OK,
+// RV_COMPILE_FALLBACK or an error code
+static int compile_on_device(rv_ctx* ctx, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, Compiled& cc,
+                             DevCompileKeep* keep) {
+    const int k = ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0;
+    DevCompileLaps laps;
+    const int rc = compile_ops_device(ctx->stream, ctx_dev_allocator(ctx), d_ops, n_ops, z64_wires, gf2_wires, (flags & RV_COMPILE_KEEP_WIRES) != 0, k,
+                                      cc, keep, &laps);
+    if (rc == RV_E_DEVICE) g_last_error = "device compile: HIP error";
+    if (rc == RV_E_NOMEM) g_last_error = "device compile: out of device memory";
+    if (rc == RV_OK) {
+        std::lock_guard<std::mutex> lk(g_dev_laps_mu);
+        g_dev_laps = laps;
+    }
+    return rc;
+}
+// host ops to the device (the context arena), for the device compiler; *d = nullptr when there is nothing to copy
+static int upload_ops(rv_ctx* ctx, const rv_op* ops, size_t n_ops, rv_op** d) {
+    *d = nullptr;
+    if (!n_ops) return RV_OK;
+    int rc = ctx->alloc(n_ops * sizeof(rv_op), (void**)d);
+    if (rc) return rc;
+    const hipError_t e = hipMemcpyAsync(*d, ops, n_ops * sizeof(rv_op), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) {
+        ctx->release(*d);
+        *d = nullptr;
+        return hip_fail(e, "hipMemcpyAsync(ops)", __FILE__, __LINE__);
+    }
+    return RV_OK;
+}
+
 static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
-                                  rv_circuit** out) {
-    if (!ctx || !out || (n_ops && !ops)) return RV_E_ARG;
+                                  rv_circuit** out, const rv_op* d_ops) {
+    if (!ctx || !out || (n_ops && !ops && !d_ops)) {
+        g_last_error = "circuit compile: NULL context, output or op array";
+        return RV_E_ARG;
+    }
     *out = nullptr;
     rv_circuit* c = new rv_circuit();
     c->ctx = ctx;
@@ -755,7 +811,48 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
     // RV_COMPILE_WHOLE_PROVER: lazy sums of up to RV_LIN_K rows for every circuit (the compiler chooses them on its own only
     // for deep, narrow ones); RV_LAZY_K still overrides
     const bool keep = (flags & RV_COMPILE_KEEP_WIRES) != 0;
-    int rc = compile_ops(ops, n_ops, z64_wires, gf2_wires, c->cc, nullptr, ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0,
+    int rc = RV_COMPILE_FALLBACK;
+    std::vector<rv_op> h_ops;  // (ops in device memory that the device path hands back: the host compiler's copy)
+    if (d_ops || (flags & RV_COMPILE_DEVICE)) {
+        // RV_COMPILE_DEVICE / rv_circuit_compile_device: the GF(2) K = 1 compile on the context's GPU (compile_dev.hip)
+        if (hipSetDevice(ctx->device) != hipSuccess) {
+            delete c;
+            return hip_fail(hipGetLastError(), "hipSetDevice", __FILE__, __LINE__);
+        }
+        if (device_compile_possible(flags) && n_ops) {
+            rv_op* up = nullptr;
+            rc = d_ops ? RV_OK : upload_ops(ctx, ops, n_ops, &up);
+            if (rc == RV_OK) {
+                DevCompileKeep kept;
+                rc = compile_on_device(ctx, d_ops ? d_ops : up, n_ops, z64_wires, gf2_wires, flags, c->cc, &kept);
+                if (rc == RV_OK) {
+                    c->d_gates = kept.d_gates;
+                    c->d_rec_rows = kept.d_rec_rows;
+                    c->d_in_rows = kept.d_in_rows;
+                    c->dev_compiled = true;
+                }
+            }
+            ctx->release(up);  // (the device compile synchronised the stream)
+            if (rc != RV_OK && rc != RV_COMPILE_FALLBACK) {
+                delete c;
+                return rc;
+            }
+        }
+        if (rc == RV_COMPILE_FALLBACK && !ops) {  // the host compiler reads the ops from host memory
+            h_ops.resize(n_ops);
+            if (n_ops) {
+                hipError_t e = hipMemcpyAsync(h_ops.data(), d_ops, n_ops * sizeof(rv_op), hipMemcpyDeviceToHost, ctx->stream);
+                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+                if (e != hipSuccess) {
+                    delete c;
+                    return hip_fail(e, "hipMemcpyAsync(ops to host)", __FILE__, __LINE__);
+                }
+            }
+            ops = h_ops.data();
+        }
+    }
+    if (rc == RV_COMPILE_FALLBACK)
+        rc = compile_ops(ops, n_ops, z64_wires, gf2_wires, c->cc, nullptr, ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0,
                          keep);
     if (rc) {
         delete c;
@@ -828,7 +925,8 @@ static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged) {
     // everything below goes through one page-locked buffer when it fits (the function waits for the stream before it
     // returns, so the buffer is free again for the next circuit)
     size_t stage_need = (size_t)1 << 20;  // (+ the LDS-run records, built further down: they fall back to a pageable copy when they do not fit)
-    for (size_t b : {cc.gates.size() * sizeof(Gate), cc.rec_rows.size() * 4, cc.in_rows.size() * 4, cc.gates64.size() * sizeof(Gate64),
+    const size_t dev_sent = c->dev_compiled ? 0 : 1;  // (a device-compiled circuit's gates and ordinal tables are not sent: below)
+    for (size_t b : {dev_sent * cc.gates.size() * sizeof(Gate), dev_sent * cc.rec_rows.size() * 4, dev_sent * cc.in_rows.size() * 4, cc.gates64.size() * sizeof(Gate64),
                      cc.rec_offs64.size() * 8, cc.in_offs64.size() * 8, cc.level_start.size() * 4, cc.level_range.size() * sizeof(LevelRange)})
         stage_need += (b + 255) & ~(size_t)255;
     constexpr bool stage_on = true;
@@ -864,9 +962,11 @@ static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged) {
         HIPCHK(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
         return RV_OK;
     };
-    if ((rc = up(cc.gates.data(), cc.gates.size() * sizeof(Gate), (void**)&c->d_gates)) ||
-        (rc = up(cc.rec_rows.data(), cc.rec_rows.size() * 4, (void**)&c->d_rec_rows)) ||
-        (rc = up(cc.in_rows.data(), cc.in_rows.size() * 4, (void**)&c->d_in_rows)) ||
+    // (a device-compiled circuit's gate records and ordinal tables were written in HBM by the compiler: not sent again)
+    const bool dev = c->dev_compiled;
+    if ((!dev && (rc = up(cc.gates.data(), cc.gates.size() * sizeof(Gate), (void**)&c->d_gates))) ||
+        (!dev && (rc = up(cc.rec_rows.data(), cc.rec_rows.size() * 4, (void**)&c->d_rec_rows))) ||
+        (!dev && (rc = up(cc.in_rows.data(), cc.in_rows.size() * 4, (void**)&c->d_in_rows))) ||
         (rc = up(cc.gates64.data(), cc.gates64.size() * sizeof(Gate64), (void**)&c->d_gates64)) ||
         (rc = up(cc.rec_offs64.data(), cc.rec_offs64.size() * 8, (void**)&c->d_rec_offs64)) ||
         (rc = up(cc.in_offs64.data(), cc.in_offs64.size() * 8, (void**)&c->d_in_offs64)) ||
@@ -1125,6 +1225,66 @@ extern "C" int rv_hook_compile_compare(const rv_op* ops, size_t n_ops, size_t z6
         g_last_error = "out of host memory";
         return RV_E_NOMEM;
     }
+}
+
+extern "C" int rv_circuit_compile_device(rv_ctx* ctx, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
+                                         rv_circuit** out) {
+    if (!ctx || !out || (n_ops && !d_ops) || (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE))) return RV_E_ARG;
+    try {
+        return rv_circuit_compile_impl(ctx, nullptr, n_ops, z64_wires, gf2_wires, flags | RV_COMPILE_DEVICE, out, d_ops);
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}
+
+extern "C" int rv_ctx_set_compile_flags(rv_ctx* ctx, uint32_t flags) {
+    if (!ctx || (flags & ~RV_COMPILE_DEVICE)) return RV_E_ARG;
+    ctx->compile_flags = flags;
+    return RV_OK;
+}
+
+extern "C" int rv_hook_compile_compare_device(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, int* path,
+                                              int* diff) {
+    if (!ctx || !path || !diff || (n_ops && !ops) || (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE))) return RV_E_ARG;
+    try {
+        const int k = ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0;
+        Compiled a, b;
+        const int rc = compile_ops(ops, n_ops, z64_wires, gf2_wires, a, nullptr, k, (flags & RV_COMPILE_KEEP_WIRES) != 0);
+        int rd = RV_COMPILE_FALLBACK;
+        if (device_compile_possible(flags) && n_ops) {
+            HIPCHK(hipSetDevice(ctx->device));
+            rv_op* up = nullptr;
+            rd = upload_ops(ctx, ops, n_ops, &up);
+            if (rd == RV_OK) rd = compile_on_device(ctx, up, n_ops, z64_wires, gf2_wires, flags, b, nullptr);
+            ctx->release(up);
+        }
+        if (rd == RV_OK) {
+            *path = 1;
+            *diff = rc == RV_OK ? compiled_diff(a, b) : 100;  // (the device path compiled an op list the host compiler rejects)
+        } else if (rd == RV_COMPILE_FALLBACK) {
+            *path = 0;
+            *diff = 0;
+        } else {
+            return rd;
+        }
+        return rc;
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}
+
+extern "C" int rv_hook_compile_device_laps(double out[6]) {
+    if (!out) return RV_E_ARG;
+    std::lock_guard<std::mutex> lk(g_dev_laps_mu);
+    out[0] = g_dev_laps.classify;
+    out[1] = g_dev_laps.writers;
+    out[2] = g_dev_laps.levels;
+    out[3] = g_dev_laps.tables;
+    out[4] = g_dev_laps.download;
+    out[5] = g_dev_laps.rounds;
+    return RV_OK;
 }
 
 static uint64_t early_staging_bytes_of(const rv_circuit* c);  // (with the early-corrections plan below)

@@ -1,0 +1,39 @@
+// Gate-stream compiler on the GPU (compile_dev.hip): the K = 1 compile of a whole GF(2) program, from an op list in device
+// memory, to a Compiled identical field by field to what compile_ops makes of it.  Scope: GF(2) ops only (no Z64, B2A or
+// SizeHint), no RV_COMPILE_KEEP_WIRES, no forced or environment-chosen lazy_k, and a K = 1 compile that compile_ops_seq would keep
+// (lazy_forms_pay false).  Everything else, every op-list error included, is RV_COMPILE_FALLBACK: the caller runs compile_ops,
+// which returns the canonical result or error code.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "compile.h"
+
+namespace rv {
+
+// device memory of the compile: taken and given back through the caller's allocator (the context arena)
+struct DevAlloc {
+    void* self = nullptr;
+    int (*alloc)(void* self, size_t bytes, void** out) = nullptr;  // RV_OK or RV_E_NOMEM
+    void (*release)(void* self, void* p) = nullptr;
+};
+
+// per-phase times of the last device compile (HIP events on the compile's stream, ms)
+struct DevCompileLaps {
+    float classify = 0, writers = 0, levels = 0, tables = 0, download = 0;
+    uint32_t rounds = 0;  // topological rounds launched
+};
+
+// The device arrays a device compile leaves for the circuit (null: freed before the call returns, nothing is kept)
+struct DevCompileKeep {
+    Gate* d_gates = nullptr;
+    uint32_t* d_rec_rows = nullptr;
+    uint32_t* d_in_rows = nullptr;
+};
+
+// RV_OK (out filled; compile_us / upload_us / device_bytes / scratch_bytes left zero), RV_COMPILE_FALLBACK, or RV_E_NOMEM /
+// RV_E_DEVICE.  d_ops: n_ops packed rv_op records in device memory (read only).  Runs on `st`; synchronises it before returning.
+int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires,
+                       bool keep_wires, int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps = nullptr);
+
+}  // namespace rv

@@ -1,0 +1,827 @@
+// see compile_dev.h
+//
+// The device compile of a whole GF(2) program at K = 1 (every XOR of two distinct rows materialised), in the steps of the host
+// compiler (compile.cpp: run_pass, Builder, the (level, class) sort and the pipelining tables):
+//   1. classify   one thread per op: validation (any error -> the flag word -> the host compiler), the counters Builder::g_* keep
+//                 (masks, Mul, AssertZero, Input: one exclusive scan gives every gate's m / eo / ep / x), the ordinal tables
+//   2. writers    the writes keyed by wire (stable LSD radix sort, op index as value); a read of wire w at op i resolves to the last
+//                 write of w before i by binary search in w's segment -- none: the never-written wire, SSA 0 (single.rs:14-16);
+//                 the same pass counts every value's reads (pass 1's `uses`) and each op's pending operands
+//   3. levels     Kahn rounds over the op DAG (consumer CSR from the read counts): one bounded launch per round, the frontier of
+//                 round r + 1 gathered per workgroup in LDS and appended while round r runs.  A value is (row = the op that wrote its row, or none;
+//                 constant bit; the row's level), the rules of Builder::g_xor / g_xorc / g_andc / g_const / g_mul at lazy_k = 1
+//   4. rows       computed rows numbered in program order after the zero row (a scan of the materialised XORs)
+//   5. tables     (level, class) keys, a stable radix sort of the gates, the records written straight into the circuit's gate array,
+//                 the LevelRange bounds, the per-level mask-block maxima and the online rows' levels (-> level_done_on)
+// No kernel waits for another workgroup; every loop is bounded by the op count, the level count or a round cap.
+#include "compile_dev.h"
+
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <vector>
+
+namespace rv {
+
+namespace {
+
+constexpr int TB = 256;           // threads per workgroup of every kernel here
+constexpr int SI = 8;             // items per thread of the scans and the radix sort
+constexpr int TILE = TB * SI;     // items per workgroup
+constexpr uint32_t MAX_ROUNDS = 1u << 16;  // topological rounds before the host compiler takes over
+
+// the counters of one op (compile.cpp Builder): ShareGen::next() calls, Mul gates, AssertZero gates, Input gates
+struct C4 {
+    uint32_t m, mul, as, in;
+};
+struct SumC4 {
+    __device__ C4 operator()(const C4& a, const C4& b) const { return C4{a.m + b.m, a.mul + b.mul, a.as + b.as, a.in + b.in}; }
+    static __device__ C4 id() { return C4{0, 0, 0, 0}; }
+};
+struct SumU32 {
+    __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; }
+    static __device__ uint32_t id() { return 0; }
+};
+struct MaxU32 {
+    __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; }
+    static __device__ uint32_t id() { return 0; }
+};
+
+// ---- exclusive scan (reduce, scan of the workgroup sums, down-sweep) ----
+template <class T, class Op>
+__global__ __launch_bounds__(TB) void k_scan_up(const T* in, size_t n, T* sums) {
+    Op op;
+    __shared__ T sh[TB];
+    const size_t base = (size_t)blockIdx.x * TILE + (size_t)threadIdx.x * SI;
+    T acc = Op::id();
+    for (int k = 0; k < SI; k++)
+        if (base + k < n) acc = op(acc, in[base + k]);
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = TB / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] = op(sh[threadIdx.x], sh[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) sums[blockIdx.x] = sh[0];
+}
+template <class T, class Op>
+__device__ T block_excl(T v, T* sh, T* total) {  // exclusive scan of one value per thread across the workgroup
+    Op op;
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 1; s < TB; s <<= 1) {
+        const T t = (int)threadIdx.x >= s ? sh[threadIdx.x - s] : Op::id();
+        __syncthreads();
+        sh[threadIdx.x] = op(sh[threadIdx.x], t);
+        __syncthreads();
+    }
+    const T ex = threadIdx.x ? sh[threadIdx.x - 1] : Op::id();
+    *total = sh[TB - 1];
+    __syncthreads();
+    return ex;
+}
+template <class T, class Op>
+__global__ __launch_bounds__(TB) void k_scan_mid(T* sums, size_t nb, T* total) {
+    Op op;
+    __shared__ T sh[TB];
+    T carry = Op::id();
+    for (size_t c0 = 0; c0 < nb; c0 += TB) {
+        const size_t i = c0 + threadIdx.x;
+        T tot;
+        const T ex = block_excl<T, Op>(i < nb ? sums[i] : Op::id(), sh, &tot);
+        if (i < nb) sums[i] = op(carry, ex);
+        carry = op(carry, tot);
+    }
+    if (threadIdx.x == 0 && total) *total = carry;
+}
+template <class T, class Op>
+__global__ __launch_bounds__(TB) void k_scan_down(const T* in, T* out, size_t n, const T* sums) {
+    Op op;
+    __shared__ T sh[TB];
+    const size_t base = (size_t)blockIdx.x * TILE + (size_t)threadIdx.x * SI;
+    T v[SI];
+    T acc = Op::id();
+    for (int k = 0; k < SI; k++) {
+        v[k] = base + k < n ? in[base + k] : Op::id();
+        acc = op(acc, v[k]);
+    }
+    T tot;
+    T run = op(sums[blockIdx.x], block_excl<T, Op>(acc, sh, &tot));
+    for (int k = 0; k < SI; k++)
+        if (base + k < n) {
+            out[base + k] = run;
+            run = op(run, v[k]);
+        }
+}
+
+// ---- stable LSD radix sort of (key, value) pairs, 8 bits per pass ----
+__global__ __launch_bounds__(TB) void k_rs_hist(const uint32_t* keys, size_t n, int shift, uint32_t* hist, uint32_t n_tiles) {
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * TILE;
+    for (int s = 0; s < SI; s++) {
+        const size_t i = base + (size_t)s * TB + threadIdx.x;
+        if (i < n) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    hist[(size_t)threadIdx.x * n_tiles + blockIdx.x] = h[threadIdx.x];
+}
+// items of a tile in order: sub-round s, then thread; the rank of an item among the equal digits before it comes from
+// wavefront ballots (the lanes that share its digit) and the per-wavefront digit counts of the sub-round in LDS
+__global__ __launch_bounds__(TB) void k_rs_scatter(const uint32_t* kin, const uint32_t* vin, uint32_t* kout, uint32_t* vout, size_t n, int shift,
+                                                   const uint32_t* off, uint32_t n_tiles) {
+    __shared__ uint32_t run[256];
+    __shared__ uint32_t wc[TB / 64][256];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    run[threadIdx.x] = off[(size_t)threadIdx.x * n_tiles + blockIdx.x];
+    const size_t base = (size_t)blockIdx.x * TILE;
+    for (int s = 0; s < SI; s++) {
+        for (int w = 0; w < TB / 64; w++) wc[w][threadIdx.x] = 0;
+        __syncthreads();
+        const size_t i = base + (size_t)s * TB + threadIdx.x;
+        const bool valid = i < n;
+        const uint32_t k = valid ? kin[i] : 0u;
+        const uint32_t d = (k >> shift) & 255u;
+        unsigned long long peers = __ballot(valid);
+        for (int b = 0; b < 8; b++) {
+            const unsigned long long bb = __ballot(valid && ((d >> b) & 1u));
+            peers &= ((d >> b) & 1u) ? bb : ~bb;
+        }
+        const uint32_t rank = (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
+        const uint32_t cnt = (uint32_t)__popcll(peers);
+        if (valid && rank + 1 == cnt) wc[wave][d] = cnt;
+        __syncthreads();
+        if (valid) {
+            uint32_t at = run[d] + rank;
+            for (uint32_t w = 0; w < wave; w++) at += wc[w][d];
+            kout[at] = k;
+            vout[at] = vin[i];
+        }
+        __syncthreads();
+        uint32_t add = 0;
+        for (int w = 0; w < TB / 64; w++) add += wc[w][threadIdx.x];
+        run[threadIdx.x] += add;
+        __syncthreads();
+    }
+}
+
+// ---- the op list ----
+__device__ inline bool op_writes(uint32_t opc) { return opc != RV_OP_ASSERTZERO; }
+__device__ inline int op_reads(uint32_t opc) {
+    switch (opc) {
+    case RV_OP_ADD: case RV_OP_SUB: case RV_OP_MUL: return 2;
+    case RV_OP_ADDCONST: case RV_OP_SUBCONST: case RV_OP_MULCONST: case RV_OP_ASSERTZERO: return 1;
+    default: return 0;
+    }
+}
+
+// step 1: validation, counters, the wire sort's keys (a wire; W for ops that write none: they sort behind every wire)
+__global__ __launch_bounds__(TB) void k_cd_classify(const rv_op* ops, size_t n, uint32_t W, C4* cnt, uint32_t* keys, uint32_t* vals, uint32_t* flag) {
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const rv_op op = ops[i];
+    bool bad = op.domain != RV_DOM_GF2 || op.reserved != 0 || op.opcode > RV_OP_CONST;
+    const int nr = bad ? 0 : op_reads(op.opcode);
+    const bool wr = !bad && op_writes(op.opcode);
+    if (wr && op.dst >= W) bad = true;
+    if (nr >= 1 && op.a >= W) bad = true;
+    if (nr >= 2 && op.b >= W) bad = true;
+    if (bad) atomicOr(flag, 1u);
+    C4 c{0, 0, 0, 0};
+    if (!bad) {
+        if (op.opcode == RV_OP_INPUT) c.m = 1, c.in = 1;
+        else if (op.opcode == RV_OP_RANDOM) c.m = 1;
+        else if (op.opcode == RV_OP_MUL) c.m = 2, c.mul = 1;
+        else if (op.opcode == RV_OP_ASSERTZERO) c.as = 1;
+    }
+    cnt[i] = c;
+    keys[i] = wr ? op.dst : W;
+    vals[i] = (uint32_t)i;
+}
+
+// the ordinal tables: reconstruction ordinal -> online row, input ordinal -> online row, the AssertZero ops
+__global__ __launch_bounds__(TB) void k_cd_ordinals(const rv_op* ops, size_t n, const C4* cx, uint32_t* rec_rows, uint32_t* in_rows, uint32_t* as_rec,
+                                                    uint64_t* as_op) {
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t opc = ops[i].opcode;
+    const C4 c = cx[i];
+    const uint32_t eo = c.in + c.mul + c.as, x = c.mul + c.as;
+    if (opc == RV_OP_INPUT) in_rows[c.in] = eo;
+    if (opc == RV_OP_MUL || opc == RV_OP_ASSERTZERO) rec_rows[x] = eo;
+    if (opc == RV_OP_ASSERTZERO) {
+        as_rec[c.as] = x;
+        as_op[c.as] = i;
+    }
+}
+
+// step 2: each wire's segment of the sorted writes
+__global__ __launch_bounds__(TB) void k_cd_segs(const uint32_t* sk, size_t n, uint32_t W, uint32_t* seg_lo, uint32_t* seg_hi) {
+    const size_t p = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t k = sk[p];
+    if (k >= W) return;
+    if (p == 0 || sk[p - 1] != k) seg_lo[k] = (uint32_t)p;
+    if (p + 1 == n || sk[p + 1] != k) seg_hi[k] = (uint32_t)p + 1;
+}
+__device__ inline int last_writer(const uint32_t* sv, const uint32_t* seg_lo, const uint32_t* seg_hi, uint32_t w, uint32_t i) {
+    uint32_t lo = seg_lo[w], a = lo, b = seg_hi[w];
+    while (a < b) {  // (at most 32 steps)
+        const uint32_t mid = a + (b - a) / 2;
+        if (sv[mid] < i) a = mid + 1;
+        else b = mid;
+    }
+    return a > lo ? (int)sv[a - 1] : -1;
+}
+// the producer of every operand (-1: the never-written wire), read counts, pending operands
+__global__ __launch_bounds__(TB) void k_cd_resolve(const rv_op* ops, size_t n, const uint32_t* sv, const uint32_t* seg_lo, const uint32_t* seg_hi,
+                                                   int2* prod, uint32_t* uses, uint32_t* rem) {
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const rv_op op = ops[i];
+    const int nr = op_reads(op.opcode);
+    int2 p = make_int2(-1, -1);
+    if (nr >= 1) p.x = last_writer(sv, seg_lo, seg_hi, op.a, (uint32_t)i);
+    if (nr >= 2) p.y = last_writer(sv, seg_lo, seg_hi, op.b, (uint32_t)i);
+    uint32_t r = 0;
+    if (p.x >= 0) atomicAdd(&uses[p.x], 1u), r++;
+    if (p.y >= 0) atomicAdd(&uses[p.y], 1u), r++;
+    prod[i] = p;
+    rem[i] = r;
+}
+__global__ __launch_bounds__(TB) void k_cd_consumers(const int2* prod, size_t n, const uint32_t* cons_off, uint32_t* cursor, uint32_t* cons) {
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const int2 p = prod[i];
+    if (p.x >= 0) cons[cons_off[p.x] + atomicAdd(&cursor[p.x], 1u)] = (uint32_t)i;
+    if (p.y >= 0) cons[cons_off[p.y] + atomicAdd(&cursor[p.y], 1u)] = (uint32_t)i;
+}
+// round 0's frontier: the ops with no pending operand
+__global__ __launch_bounds__(TB) void k_cd_front0(const uint32_t* rem, size_t n, uint32_t* frontier, uint2* rounds) {
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    if (rem[i] == 0) frontier[atomicAdd(&rounds[0].y, 1u)] = (uint32_t)i;
+}
+
+// a value: x = the op that wrote its row (-1: a constant), y = (level of that row + 1) << 1 | constant bit
+__device__ inline int2 val_of(const int2* V, int p) { return p < 0 ? make_int2(-1, 0) : V[p]; }
+__device__ inline int lvl_of(int2 v) { return (v.y >> 1) - 1; }
+
+// step 3: one round.  rounds[r] = {first frontier slot, count}; the ops whose last pending operand this round resolves form
+// round r + 1's frontier
+__global__ __launch_bounds__(TB) void k_cd_round(uint32_t r, const rv_op* ops, const int2* prod, const uint32_t* uses, const uint32_t* cons_off,
+                                                 const uint32_t* cons, uint32_t* rem, int2* V, int* glvl, uint32_t* mat, uint32_t* frontier,
+                                                 uint2* rounds) {
+    // the next frontier is gathered in LDS and appended with one global atomic per workgroup (65 536 appends to one counter per
+    // round of the benchmark circuit otherwise); what does not fit the LDS queue is appended one by one
+    constexpr uint32_t FQ = 2048;
+    __shared__ uint32_t q[FQ];
+    __shared__ uint32_t qn, qbase;
+    if (threadIdx.x == 0) qn = 0;
+    __syncthreads();
+    const uint2 R = rounds[r];
+    const uint32_t nb = R.x + R.y;
+    if (blockIdx.x == 0 && threadIdx.x == 0) rounds[r + 1].x = nb;
+    for (uint32_t t = blockIdx.x * TB + threadIdx.x; t < R.y; t += gridDim.x * TB) {
+        const uint32_t i = frontier[R.x + t];
+        const rv_op op = ops[i];
+        const int2 p = prod[i];
+        const int2 A = val_of(V, p.x), B = val_of(V, p.y);
+        const int cb = (int)(op.imm & 1);
+        int2 out = make_int2(-1, 0);
+        int gl = -1;
+        uint32_t mt = 0;
+        switch (op.opcode) {
+        case RV_OP_INPUT:
+        case RV_OP_RANDOM:
+            gl = 0;
+            out = make_int2((int)i, 1 << 1);
+            break;
+        case RV_OP_CONST:
+            out = make_int2(-1, cb);
+            break;
+        case RV_OP_ADD:
+        case RV_OP_SUB:
+            if (A.x == B.x) out = make_int2(-1, (A.y ^ B.y) & 1);       // x ^ x = 0 (or two constants)
+            else if (A.x < 0) out = make_int2(B.x, B.y ^ (A.y & 1));    // a constant plus a row: the row
+            else if (B.x < 0) out = make_int2(A.x, A.y ^ (B.y & 1));
+            else if (uses[i] == 0) out = make_int2(-1, 0);              // an unread sum is dropped
+            else {                                                      // two rows: a G_XORK
+                gl = max(lvl_of(A), lvl_of(B)) + 1;
+                out = make_int2((int)i, (gl + 1) << 1);
+                mt = 1;
+            }
+            break;
+        case RV_OP_ADDCONST:
+        case RV_OP_SUBCONST:
+            out = make_int2(A.x, A.y ^ cb);
+            break;
+        case RV_OP_MULCONST:
+            out = cb ? A : make_int2(-1, 0);
+            break;
+        case RV_OP_MUL:
+            gl = max(lvl_of(A), lvl_of(B)) + 1;
+            out = make_int2((int)i, (gl + 1) << 1);
+            break;
+        default:  // AssertZero
+            gl = lvl_of(A) + 1;
+            break;
+        }
+        V[i] = out;
+        glvl[i] = gl;
+        mat[i] = mt;
+        const uint32_t c0 = cons_off[i], c1 = c0 + uses[i];
+        for (uint32_t k = c0; k < c1; k++) {
+            const uint32_t c = cons[k];
+            if (atomicSub(&rem[c], 1u) == 1u) {
+                const uint32_t s = atomicAdd(&qn, 1u);
+                if (s < FQ) q[s] = c;
+                else frontier[nb + atomicAdd(&rounds[r + 1].y, 1u)] = c;
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t m = min(qn, FQ);
+    if (threadIdx.x == 0 && m) qbase = atomicAdd(&rounds[r + 1].y, m);
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < m; j += TB) frontier[nb + qbase + j] = q[j];
+}
+
+struct DevStats {
+    int max_level;
+    uint32_t n_gates, n_mat, pad;
+    unsigned long long operand_rows;
+};
+// the gate count, materialised XORs, levels and operand rows (one atomic per workgroup and counter)
+__global__ __launch_bounds__(TB) void k_cd_stats(const rv_op* ops, size_t n, const int2* prod, const int2* V, const int* glvl, const uint32_t* mat,
+                                                 DevStats* st) {
+    __shared__ int sl[TB];
+    __shared__ uint32_t sg[TB], sm[TB], so[TB];
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    int l = -1;
+    uint32_t g = 0, m = 0, o = 0;
+    if (i < n) {
+        l = glvl[i];
+        g = l >= 0;
+        m = mat[i];
+        const uint32_t opc = ops[i].opcode;
+        const int2 p = prod[i];
+        if (opc == RV_OP_MUL) o = (val_of(V, p.x).x >= 0) + (val_of(V, p.y).x >= 0);
+        else if (opc == RV_OP_ASSERTZERO) o = val_of(V, p.x).x >= 0;
+        else if (m) o = 2;
+    }
+    sl[threadIdx.x] = l, sg[threadIdx.x] = g, sm[threadIdx.x] = m, so[threadIdx.x] = o;
+    __syncthreads();
+    for (int s = TB / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            sl[threadIdx.x] = max(sl[threadIdx.x], sl[threadIdx.x + s]);
+            sg[threadIdx.x] += sg[threadIdx.x + s];
+            sm[threadIdx.x] += sm[threadIdx.x + s];
+            so[threadIdx.x] += so[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        atomicMax(&st->max_level, sl[0]);
+        atomicAdd(&st->n_gates, sg[0]);
+        atomicAdd(&st->n_mat, sm[0]);
+        atomicAdd(&st->operand_rows, (unsigned long long)so[0]);
+    }
+}
+
+// step 5: the (level, class) key of every gate (LevelRange classes: Mul of one-base operands 0, other Mul 1, two-row Xor 2,
+// the rest 4; ops without a gate get `sentinel`, behind every gate)
+__global__ __launch_bounds__(TB) void k_cd_keys(const rv_op* ops, size_t n, const int2* prod, const int2* V, const int* glvl, const uint32_t* mat,
+                                                uint32_t sentinel, uint32_t* keys, uint32_t* vals) {
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const int l = glvl[i];
+    uint32_t key = sentinel;
+    if (l >= 0) {
+        const uint32_t opc = ops[i].opcode;
+        uint32_t cls = 4;
+        if (opc == RV_OP_MUL) {
+            const int2 p = prod[i];
+            cls = (val_of(V, p.x).x >= 0 && val_of(V, p.y).x >= 0) ? 0u : 1u;
+        } else if (mat[i]) {
+            cls = 2;
+        }
+        key = (uint32_t)l * 5u + cls;
+    }
+    keys[i] = key;
+    vals[i] = (uint32_t)i;
+}
+// pos[k] = first sorted gate with key >= k, k in [0, n_buckets]
+__global__ __launch_bounds__(TB) void k_cd_bounds(const uint32_t* sk, size_t n_gates, uint32_t n_buckets, uint32_t* pos) {
+    const size_t p = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (p > n_gates) return;
+    const uint32_t lo = p == 0 ? 0u : sk[p - 1] + 1u;
+    const uint32_t hi = p == n_gates ? n_buckets : sk[p];
+    for (uint32_t k = lo; k <= hi; k++) pos[k] = (uint32_t)p;
+}
+
+// a value's row as a share row index: PRG rows first (Input / Random: m, Mul: m + 1), then the computed rows (zero row first)
+__device__ inline uint32_t row_index(const rv_op* ops, const C4* cx, const uint32_t* comp, uint32_t pad, int q) {
+    if (q < 0) return pad;
+    const uint32_t opc = ops[q].opcode;
+    if (opc == RV_OP_MUL) return cx[q].m + 1;
+    if (opc == RV_OP_INPUT || opc == RV_OP_RANDOM) return cx[q].m;
+    return pad + 1 + comp[q];
+}
+__device__ inline uint32_t wave_max_u32(uint32_t v) {
+    for (int s = 32; s > 0; s >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, s));
+    return v;
+}
+// the gate records in (level, class, program) order, the per-level mask blocks and the online rows' levels
+__global__ __launch_bounds__(TB) void k_cd_gates(const uint32_t* sk, const uint32_t* sv, size_t n_gates, const rv_op* ops, const int2* prod, const int2* V,
+                                                 const C4* cx, const uint32_t* comp, uint32_t pad, Gate* gates, uint32_t* need_raw, uint32_t* on_lvl) {
+    const size_t p = (size_t)blockIdx.x * TB + threadIdx.x;
+    const bool valid = p < n_gates;
+    uint32_t l = 0, need = 0;
+    if (valid) {
+        l = sk[p] / 5u;
+        const uint32_t i = sv[p];
+        const rv_op op = ops[i];
+        const C4 c = cx[i];
+        const int2 pr = prod[i];
+        const int2 A = val_of(V, pr.x), B = val_of(V, pr.y);
+        const uint32_t eo = c.in + c.mul + c.as, x = c.mul + c.as;
+        Gate g;
+        g.dst = 0, g.m = 0, g.eo = 0, g.ep = 0, g.x = 0;
+        for (int k = 0; k < RV_LIN_K; k++) g.a[k] = pad, g.b[k] = pad;
+        switch (op.opcode) {
+        case RV_OP_INPUT:
+            g.op = G_INPUT;
+            g.m = g.dst = c.m;
+            g.eo = eo;
+            g.x = c.in;
+            need = c.m / 128 + 1;
+            on_lvl[eo] = l;
+            break;
+        case RV_OP_RANDOM:
+            g.op = G_RANDOM;
+            g.m = g.dst = c.m;
+            need = c.m / 128 + 1;
+            break;
+        case RV_OP_MUL: {
+            const uint32_t na = A.x >= 0, nb = B.x >= 0;
+            g.op = G_MUL | na << 8 | nb << 12 | (uint32_t)(A.y & 1) << 16 | (uint32_t)(B.y & 1) << 17;
+            if (na) g.a[0] = row_index(ops, cx, comp, pad, A.x);
+            if (nb) g.b[0] = row_index(ops, cx, comp, pad, B.x);
+            g.m = c.m;
+            g.dst = c.m + 1;
+            g.eo = eo;
+            g.ep = c.mul;
+            g.x = x;
+            need = (c.m + 1) / 128 + 1;
+            on_lvl[eo] = l;
+            break;
+        }
+        case RV_OP_ASSERTZERO: {
+            const uint32_t na = A.x >= 0;
+            g.op = G_ASSERT | na << 8 | (uint32_t)(A.y & 1) << 16;
+            if (na) g.a[0] = row_index(ops, cx, comp, pad, A.x);
+            g.eo = eo;
+            g.x = x;
+            on_lvl[eo] = l;
+            break;
+        }
+        default: {  // a materialised Add / Sub: its two rows in ascending order
+            const uint32_t ra = row_index(ops, cx, comp, pad, A.x), rb = row_index(ops, cx, comp, pad, B.x);
+            g.op = G_XORK | 2u << 8 | (uint32_t)((A.y ^ B.y) & 1) << 16;
+            g.a[0] = min(ra, rb);
+            g.a[1] = max(ra, rb);
+            g.dst = pad + 1 + comp[i];
+            break;
+        }
+        }
+        gates[p] = g;
+    }
+    // a wavefront's gates mostly share a level: one atomic for them
+    const uint32_t l0 = (uint32_t)__shfl((int)l, 0);
+    if (__all(!valid || l == l0)) {
+        const uint32_t m = wave_max_u32(need);
+        if ((threadIdx.x & 63u) == 0 && m) atomicMax(&need_raw[l0], m);
+    } else if (valid && need) {
+        atomicMax(&need_raw[l], need);
+    }
+}
+// level_done_on[l] = online rows e whose prefix maximum of levels is <= l; pm = exclusive prefix maximum of on_lvl (n_on + 1 entries)
+__global__ __launch_bounds__(TB) void k_cd_done_on(const uint32_t* pm, const uint32_t* on_lvl, size_t n_on, uint32_t n_levels, uint32_t* done_on) {
+    const size_t e = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (e > n_on) return;
+    const uint32_t lo = pm[e];
+    const uint32_t hi = e == n_on ? n_levels : max(pm[e], on_lvl[e]);
+    for (uint32_t l = lo; l < hi && l < n_levels; l++) done_on[l] = (uint32_t)e;
+}
+
+inline uint32_t blocks(size_t n, size_t per) { return (uint32_t)std::max<size_t>(1, (n + per - 1) / per); }
+inline int bit_len(uint64_t v) {
+    int b = 0;
+    while (v) b++, v >>= 1;
+    return b;
+}
+
+// device allocations of one compile, given back (after a stream sync) when it ends
+struct Scratch {
+    const DevAlloc& A;
+    hipStream_t st;
+    std::vector<void*> ps;
+    bool failed = false;
+    Scratch(const DevAlloc& a, hipStream_t s) : A(a), st(s) {}
+    template <class T>
+    T* get(size_t count) {
+        void* p = nullptr;
+        if (failed || A.alloc(A.self, std::max<size_t>(count, 1) * sizeof(T), &p) != RV_OK) {
+            failed = true;
+            return nullptr;
+        }
+        ps.push_back(p);
+        return (T*)p;
+    }
+    void keep(void* p) { ps.erase(std::remove(ps.begin(), ps.end(), p), ps.end()); }
+    ~Scratch() {
+        (void)hipStreamSynchronize(st);
+        for (void* p : ps) A.release(A.self, p);
+    }
+};
+
+template <class T, class Op>
+hipError_t scan_excl(Scratch& S, hipStream_t st, const T* in, T* out, size_t n, T* d_total) {
+    const uint32_t nb = blocks(n, TILE);
+    T* sums = S.get<T>(nb);
+    if (!sums) return hipErrorOutOfMemory;
+    k_scan_up<T, Op><<<nb, TB, 0, st>>>(in, n, sums);
+    k_scan_mid<T, Op><<<1, TB, 0, st>>>(sums, nb, d_total);
+    k_scan_down<T, Op><<<nb, TB, 0, st>>>(in, out, n, sums);
+    return hipGetLastError();
+}
+// sorts (k[0], v[0]) by the low `bits` bits of the keys (stable); the result is left in (k[*which], v[*which])
+hipError_t radix_sort(Scratch& S, hipStream_t st, uint32_t* k[2], uint32_t* v[2], size_t n, int bits, int* which) {
+    const uint32_t nt = blocks(n, TILE);
+    uint32_t* hist = S.get<uint32_t>((size_t)256 * nt);
+    if (!hist) return hipErrorOutOfMemory;
+    int cur = 0;
+    for (int shift = 0; shift < std::max(bits, 1); shift += 8) {
+        k_rs_hist<<<nt, TB, 0, st>>>(k[cur], n, shift, hist, nt);
+        hipError_t e = scan_excl<uint32_t, SumU32>(S, st, hist, hist, (size_t)256 * nt, nullptr);
+        if (e != hipSuccess) return e;
+        k_rs_scatter<<<nt, TB, 0, st>>>(k[cur], v[cur], k[cur ^ 1], v[cur ^ 1], n, shift, hist, nt);
+        cur ^= 1;
+    }
+    *which = cur;
+    return hipGetLastError();
+}
+
+}  // namespace
+
+int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, bool keep_wires,
+                       int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps) {
+    (void)z64_wires;  // (a Z64 op in the list is what sends a program to the host; the Z64 wire count alone does not)
+    if (keep_wires || force_lazy_k || getenv("RV_LAZY_K") || n_ops == 0 || n_ops >= (1u << 28) || gf2_wires >= (1u << 31))
+        return RV_COMPILE_FALLBACK;
+    const size_t n = n_ops;
+    const uint32_t W = (uint32_t)gf2_wires;
+    Scratch S(A, st);
+    hipEvent_t ev[6] = {};
+    const bool timed = laps != nullptr;
+    if (timed)
+        for (auto& e : ev)
+            if (hipEventCreate(&e) != hipSuccess) return RV_E_DEVICE;
+    struct EvGuard {
+        hipEvent_t* e;
+        ~EvGuard() {
+            for (int k = 0; k < 6; k++)
+                if (e[k]) (void)hipEventDestroy(e[k]);
+        }
+    } ev_guard{ev};
+    auto mark = [&](int k) {
+        if (timed) (void)hipEventRecord(ev[k], st);
+    };
+#define CDCHK(x)                                               \
+    do {                                                       \
+        if ((x) != hipSuccess) {                               \
+            (void)hipGetLastError();                           \
+            return S.failed ? RV_E_NOMEM : RV_E_DEVICE;        \
+        }                                                      \
+    } while (0)
+#define CDNEED(p) \
+    if (!(p)) return RV_E_NOMEM
+    const uint32_t gb = blocks(n, TB);
+    mark(0);
+    // ---- 1. classify ----
+    C4* cx = S.get<C4>(n + 1);
+    uint32_t* kbuf[2] = {S.get<uint32_t>(n), S.get<uint32_t>(n)};
+    uint32_t* vbuf[2] = {S.get<uint32_t>(n), S.get<uint32_t>(n)};
+    uint32_t* d_small = S.get<uint32_t>(64);  // [0] error flag, [8..12) C4 totals, [16..24) DevStats
+    CDNEED(cx && kbuf[0] && kbuf[1] && vbuf[0] && vbuf[1] && d_small);
+    C4* d_tot = (C4*)(d_small + 8);
+    DevStats* d_stats = (DevStats*)(d_small + 16);
+    CDCHK(hipMemsetAsync(d_small, 0, 64 * 4, st));
+    k_cd_classify<<<gb, TB, 0, st>>>(d_ops, n, W, cx, kbuf[0], vbuf[0], d_small);
+    CDCHK(hipGetLastError());
+    CDCHK((scan_excl<C4, SumC4>(S, st, cx, cx, n, d_tot)));
+    uint32_t h_small[24];
+    CDCHK(hipMemcpyAsync(h_small, d_small, sizeof h_small, hipMemcpyDeviceToHost, st));
+    CDCHK(hipStreamSynchronize(st));
+    if (h_small[0]) return RV_COMPILE_FALLBACK;  // an op the device path does not take, or an op-list error: the host compiler reports it
+    const C4 tot{h_small[8], h_small[9], h_small[10], h_small[11]};
+    const uint64_t n_on = (uint64_t)tot.in + tot.mul + tot.as, n_rec = (uint64_t)tot.mul + tot.as;
+    uint32_t* rec_rows = nullptr;
+    uint32_t* in_rows = nullptr;
+    {
+        void* p = nullptr;
+        if (A.alloc(A.self, std::max<size_t>(n_rec, 1) * 4, &p) != RV_OK) return RV_E_NOMEM;
+        rec_rows = (uint32_t*)p;
+        S.ps.push_back(p);
+        if (A.alloc(A.self, std::max<size_t>(tot.in, 1) * 4, &p) != RV_OK) return RV_E_NOMEM;
+        in_rows = (uint32_t*)p;
+        S.ps.push_back(p);
+    }
+    uint32_t* as_rec = S.get<uint32_t>(tot.as);
+    uint64_t* as_op = S.get<uint64_t>(tot.as);
+    CDNEED(as_rec && as_op);
+    k_cd_ordinals<<<gb, TB, 0, st>>>(d_ops, n, cx, rec_rows, in_rows, as_rec, as_op);
+    CDCHK(hipGetLastError());
+    mark(1);
+    // ---- 2. the last writer of every read ----
+    int which = 0;
+    CDCHK(radix_sort(S, st, kbuf, vbuf, n, bit_len(W), &which));
+    uint32_t* seg_lo = S.get<uint32_t>(W);
+    uint32_t* seg_hi = S.get<uint32_t>(W);
+    int2* prod = S.get<int2>(n);
+    uint32_t* uses = S.get<uint32_t>(n + 1);
+    uint32_t* rem = S.get<uint32_t>(n);
+    CDNEED(seg_lo && seg_hi && prod && uses && rem);
+    CDCHK(hipMemsetAsync(seg_lo, 0, std::max<size_t>(W, 1) * 4, st));
+    CDCHK(hipMemsetAsync(seg_hi, 0, std::max<size_t>(W, 1) * 4, st));
+    CDCHK(hipMemsetAsync(uses, 0, (n + 1) * 4, st));
+    k_cd_segs<<<gb, TB, 0, st>>>(kbuf[which], n, W, seg_lo, seg_hi);
+    k_cd_resolve<<<gb, TB, 0, st>>>(d_ops, n, vbuf[which], seg_lo, seg_hi, prod, uses, rem);
+    CDCHK(hipGetLastError());
+    uint32_t* cons_off = S.get<uint32_t>(n + 1);
+    uint32_t* cursor = S.get<uint32_t>(n);
+    uint32_t* cons = S.get<uint32_t>(2 * n);
+    CDNEED(cons_off && cursor && cons);
+    CDCHK((scan_excl<uint32_t, SumU32>(S, st, uses, cons_off, n + 1, nullptr)));
+    CDCHK(hipMemsetAsync(cursor, 0, n * 4, st));
+    k_cd_consumers<<<gb, TB, 0, st>>>(prod, n, cons_off, cursor, cons);
+    CDCHK(hipGetLastError());
+    mark(2);
+    // ---- 3. values and levels, round by round ----
+    int2* V = S.get<int2>(n);
+    int* glvl = S.get<int>(n);
+    uint32_t* mat = S.get<uint32_t>(n + 1);
+    uint32_t* frontier = S.get<uint32_t>(n);
+    const uint32_t max_rounds = (uint32_t)std::min<size_t>(n + 1, MAX_ROUNDS);
+    uint2* rounds = S.get<uint2>((size_t)max_rounds + 2);
+    CDNEED(V && glvl && mat && frontier && rounds);
+    CDCHK(hipMemsetAsync(rounds, 0, ((size_t)max_rounds + 2) * sizeof(uint2), st));
+    CDCHK(hipMemsetAsync(mat + n, 0, 4, st));
+    k_cd_front0<<<gb, TB, 0, st>>>(rem, n, frontier, rounds);
+    CDCHK(hipGetLastError());
+    const uint32_t round_blocks = std::min<uint32_t>(gb, 1024);
+    uint32_t r = 0, batch = 8;
+    bool done = false;
+    while (!done) {
+        if (r >= max_rounds) return RV_COMPILE_FALLBACK;  // (the cap: a chain of ops this deep compiles on the host)
+        const uint32_t e = std::min(r + batch, max_rounds);
+        for (; r < e; r++) k_cd_round<<<round_blocks, TB, 0, st>>>(r, d_ops, prod, uses, cons_off, cons, rem, V, glvl, mat, frontier, rounds);
+        CDCHK(hipGetLastError());
+        uint2 nxt;
+        CDCHK(hipMemcpyAsync(&nxt, rounds + r, sizeof nxt, hipMemcpyDeviceToHost, st));
+        CDCHK(hipStreamSynchronize(st));
+        if (nxt.y == 0) {
+            if (nxt.x != n) return RV_COMPILE_FALLBACK;  // (every op resolves exactly once; cannot happen)
+            done = true;
+        }
+        batch = std::min<uint32_t>(batch * 2, 256);
+    }
+    if (laps) laps->rounds = r;
+    k_cd_stats<<<gb, TB, 0, st>>>(d_ops, n, prod, V, glvl, mat, d_stats);
+    CDCHK(hipGetLastError());
+    // d_stats->max_level starts at 0 (memset): max_level + 1 levels when there are gates
+    DevStats hs;
+    CDCHK(hipMemcpyAsync(&hs, d_stats, sizeof hs, hipMemcpyDeviceToHost, st));
+    CDCHK(hipStreamSynchronize(st));
+    mark(3);
+    const uint64_t n_gates = hs.n_gates;
+    const uint32_t n_levels = n_gates ? (uint32_t)hs.max_level + 1 : 0;
+    // the K = 1 compile is final unless the circuit is deep and narrow (compile_ops_seq): those go to the host compiler
+    if (n_levels && lazy_forms_pay(n_levels, n_gates)) return RV_COMPILE_FALLBACK;
+    const uint64_t n_masks_pad = ((uint64_t)tot.m + 127) / 128 * 128;
+    const uint64_t LIM = 0xFFFFFFFFull - 512;
+    if (n_masks_pad + 1 + hs.n_mat > LIM || n_masks_pad / 128 > RV_MAX_CTR_BLOCKS || (uint64_t)n_levels * 5 + 1 >= (1ull << 32))
+        return RV_COMPILE_FALLBACK;
+    // ---- 4. computed rows ----
+    uint32_t* comp = S.get<uint32_t>(n + 1);
+    CDNEED(comp);
+    CDCHK((scan_excl<uint32_t, SumU32>(S, st, mat, comp, n + 1, nullptr)));
+    // ---- 5. tables ----
+    const uint32_t n_buckets = n_levels * 5;
+    k_cd_keys<<<gb, TB, 0, st>>>(d_ops, n, prod, V, glvl, mat, n_buckets, kbuf[0], vbuf[0]);
+    CDCHK(hipGetLastError());
+    CDCHK(radix_sort(S, st, kbuf, vbuf, n, bit_len(n_buckets), &which));
+    void* pg = nullptr;
+    if (A.alloc(A.self, std::max<size_t>(n_gates, 1) * sizeof(Gate), &pg) != RV_OK) return RV_E_NOMEM;
+    S.ps.push_back(pg);
+    Gate* gates = (Gate*)pg;
+    uint32_t* pos = S.get<uint32_t>((size_t)n_buckets + 1);
+    uint32_t* need_raw = S.get<uint32_t>(n_levels);
+    uint32_t* on_lvl = S.get<uint32_t>(n_on + 1);
+    uint32_t* pm = S.get<uint32_t>(n_on + 1);
+    uint32_t* done_on = S.get<uint32_t>(n_levels);
+    CDNEED(pos && need_raw && on_lvl && pm && done_on);
+    CDCHK(hipMemsetAsync(need_raw, 0, std::max<size_t>(n_levels, 1) * 4, st));
+    CDCHK(hipMemsetAsync(on_lvl + n_on, 0, 4, st));
+    k_cd_bounds<<<blocks(n_gates + 1, TB), TB, 0, st>>>(kbuf[which], n_gates, n_buckets, pos);
+    if (n_gates)
+        k_cd_gates<<<blocks(n_gates, TB), TB, 0, st>>>(kbuf[which], vbuf[which], n_gates, d_ops, prod, V, cx, comp, (uint32_t)n_masks_pad, gates,
+                                                       need_raw, on_lvl);
+    CDCHK(hipGetLastError());
+    CDCHK((scan_excl<uint32_t, MaxU32>(S, st, on_lvl, pm, n_on + 1, nullptr)));
+    k_cd_done_on<<<blocks(n_on + 1, TB), TB, 0, st>>>(pm, on_lvl, n_on, n_levels, done_on);
+    CDCHK(hipGetLastError());
+    mark(4);
+    // ---- the host's copy (the planners of circuit_upload read it) ----
+    Compiled& cc = out;
+    cc = Compiled();
+    cc.gates.resize(n_gates);
+    cc.rec_rows.resize(n_rec);
+    cc.in_rows.resize(tot.in);
+    cc.assert_rec2.resize(tot.as);
+    cc.assert_op2.resize(tot.as);
+    std::vector<uint32_t> h_pos((size_t)n_buckets + 1), h_need(n_levels);
+    cc.level_done_on.resize(n_levels);
+    auto d2h = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess; };
+    CDCHK(d2h(cc.gates.data(), gates, n_gates * sizeof(Gate)));
+    CDCHK(d2h(cc.rec_rows.data(), rec_rows, n_rec * 4));
+    CDCHK(d2h(cc.in_rows.data(), in_rows, (size_t)tot.in * 4));
+    CDCHK(d2h(cc.assert_rec2.data(), as_rec, (size_t)tot.as * 4));
+    CDCHK(d2h(cc.assert_op2.data(), as_op, (size_t)tot.as * 8));
+    CDCHK(d2h(h_pos.data(), pos, h_pos.size() * 4));
+    CDCHK(d2h(h_need.data(), need_raw, (size_t)n_levels * 4));
+    CDCHK(d2h(cc.level_done_on.data(), done_on, (size_t)n_levels * 4));
+    mark(5);
+    CDCHK(hipStreamSynchronize(st));
+    cc.level_start.assign(n_levels + 1, 0);
+    cc.level_range.assign(n_levels, LevelRange{});
+    cc.level_need_blocks.assign(n_levels, 0);
+    uint32_t need = 0;
+    for (uint32_t l = 0; l < n_levels; l++) {
+        const uint32_t* e = &h_pos[(size_t)l * 5];
+        cc.level_start[l] = e[0];
+        cc.level_range[l] = LevelRange{e[0], e[1], e[2], e[3], e[4], e[5]};
+        need = std::max(need, h_need[l]);
+        cc.level_need_blocks[l] = need;
+    }
+    cc.level_start[n_levels] = (uint32_t)n_gates;
+    cc.level_start64.assign(n_levels + 1, 0);
+    const uint64_t randoms = (uint64_t)tot.m - tot.in - 2ull * tot.mul;
+    cc.n_ssa = 1 + n - tot.as;
+    cc.n_masks = tot.m;
+    cc.n_masks_pad = n_masks_pad;
+    cc.n_rows = n_masks_pad + 1 + hs.n_mat;
+    cc.n_on = n_on;
+    cc.n_pre = tot.mul;
+    cc.n_in = tot.in;
+    cc.n_rec = n_rec;
+    cc.n_random_or_recon = randoms;
+    cc.n_user_random = randoms;
+    cc.row_prg_base = 0;
+    cc.zero_row = n_masks_pad;
+    rv_circuit_info& info = cc.info;
+    info.n_ops = n;
+    info.gf2_inputs = tot.in;
+    info.gf2_muls = tot.mul;
+    info.gf2_asserts = tot.as;
+    info.gf2_linear = randoms + hs.n_mat;
+    info.gf2_masks = tot.m;
+    info.levels = n_levels;
+    info.gf2_operand_rows = hs.operand_rows;
+    info.gf2_rows_written = hs.n_mat;
+    if (laps) {
+        float ms[5] = {0, 0, 0, 0, 0};
+        for (int k = 0; k < 5; k++) (void)hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+        laps->classify = ms[0];
+        laps->writers = ms[1];
+        laps->levels = ms[2];
+        laps->tables = ms[3];
+        laps->download = ms[4];
+    }
+    if (keep) {
+        keep->d_gates = gates;
+        keep->d_rec_rows = rec_rows;
+        keep->d_in_rows = in_rows;
+        S.keep(gates);
+        S.keep(rec_rows);
+        S.keep(in_rows);
+    }
+    return RV_OK;
+#undef CDCHK
+#undef CDNEED
+}
+
+}  // namespace rv

@@ -138,7 +138,10 @@ extern "C" int rv_prove_ops(rv_ctx* ctx, const rv_op* ops, size_t n_ops, const u
     bool hit = false, owned = true;
     int rc;
     try {
-        rc = ops_cache_get(ctx, ops, n_ops, z64_wires, gf2_wires, RV_COMPILE_WHOLE_PROVER, &c, &hit, &owned);
+        // (under RV_COMPILE_DEVICE the prover's circuit is the device compiler's K = 1 form instead of the RV_COMPILE_WHOLE_PROVER
+        // one, which it does not build: the proof bytes are the same, header)
+        const uint32_t fl = (ctx && (ctx->compile_flags & RV_COMPILE_DEVICE)) ? RV_COMPILE_DEVICE : RV_COMPILE_WHOLE_PROVER;
+        rc = ops_cache_get(ctx, ops, n_ops, z64_wires, gf2_wires, fl, &c, &hit, &owned);
     } catch (...) {
         g_last_error = "out of host memory";
         return RV_E_NOMEM;
@@ -161,7 +164,7 @@ extern "C" int rv_verify_ops(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t
     bool hit = false, owned = true;
     int rc;
     try {
-        rc = ops_cache_get(ctx, ops, n_ops, z64_wires, gf2_wires, 0, &c, &hit, &owned);
+        rc = ops_cache_get(ctx, ops, n_ops, z64_wires, gf2_wires, ctx ? (ctx->compile_flags & RV_COMPILE_DEVICE) : 0u, &c, &hit, &owned);
     } catch (...) {
         g_last_error = "out of host memory";
         return RV_E_NOMEM;

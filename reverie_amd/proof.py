@@ -45,6 +45,11 @@ class Context:
     def sync(self):
         _lib.check(_lib.lib().rv_ctx_sync(self.handle))
 
+    def set_compile_flags(self, flags: int):
+        """rv_ctx_set_compile_flags: 0 (default) or RV_COMPILE_DEVICE -- the cold compiles of Proof.new_ops / verify_ops-style calls
+        (rv_prove_ops, rv_verify_ops) then run on the GPU.  Proof bytes and answers are unchanged."""
+        _lib.check(_lib.lib().rv_ctx_set_compile_flags(self.handle, C.c_uint32(flags)))
+
     def close(self):
         if self.handle:
             _lib.lib().rv_ctx_destroy(self.handle)
@@ -61,20 +66,58 @@ class Circuit:
     """A gate stream compiled (levelised) and resident in HBM (rv_circuit)."""
 
     def __init__(self, ops, wire_counts: Tuple[int, int], ctx: Optional[Context] = None, whole_prover: bool = False,
-                 keep_wires: bool = False):
+                 keep_wires: bool = False, device_compile: bool = False):
         """whole_prover: the circuit will mostly serve whole proofs on one GPU (Proof.new / new_batch) -- the
         RV_COMPILE_WHOLE_PROVER hint of rv_circuit_compile_ex; any use of the circuit still gives identical bytes.
         keep_wires: RV_COMPILE_KEEP_WIRES -- the circuit keeps every wire's final value form, so that `evaluate` can return
-        wire values (proofs stay byte-identical)."""
+        wire values (proofs stay byte-identical).
+        device_compile: RV_COMPILE_DEVICE -- the ops are uploaded and compiled on the GPU (GF(2) programs; anything the device
+        path does not take is compiled on the host); the circuit is the same either way."""
         self.ctx = ctx or Context.default()
         self.ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
         self.wire_counts = (int(wire_counts[0]), int(wire_counts[1]))  # (z64, gf2), proof/mod.rs:125
         self.keep_wires = bool(keep_wires)
         self.handle = C.c_void_p()
-        flags = (_lib.RV_COMPILE_WHOLE_PROVER if whole_prover else 0) | (_lib.RV_COMPILE_KEEP_WIRES if keep_wires else 0)
+        flags = (_lib.RV_COMPILE_WHOLE_PROVER if whole_prover else 0) | (_lib.RV_COMPILE_KEEP_WIRES if keep_wires else 0) | \
+            (_lib.RV_COMPILE_DEVICE if device_compile else 0)
         _lib.check(_lib.lib().rv_circuit_compile_ex(self.ctx.handle, _ptr(self.ops), C.c_size_t(len(self.ops)),
                                                     C.c_size_t(self.wire_counts[0]), C.c_size_t(self.wire_counts[1]),
                                                     C.c_uint32(flags), C.byref(self.handle)))
+
+    @classmethod
+    def from_device_ops(cls, ops, wire_counts: Tuple[int, int], ctx: Optional[Context] = None, whole_prover: bool = False,
+                        keep_wires: bool = False) -> "Circuit":
+        """rv_circuit_compile_device: compile an op list that already sits in GPU memory -- a torch tensor on the context's
+        device holding packed 24-byte rv_op records, as uint8 of shape [n, 24] (or [n * 24]) or int64 / uint64 of shape [n, 3];
+        contiguous.  The tensor is not copied to the host unless the device path hands the program to the host compiler; the
+        caller keeps it.  The circuit is the one Circuit(host ops, device_compile=True) compiles."""
+        import torch
+
+        if not isinstance(ops, torch.Tensor) or ops.device.type != "cuda":
+            raise TypeError("from_device_ops takes a torch tensor in GPU memory")
+        if not ops.is_contiguous():
+            raise ValueError("the op tensor must be contiguous")
+        if ops.dtype == torch.uint8 and (ops.dim() == 1 and ops.numel() % OP_DTYPE.itemsize == 0 or ops.dim() == 2 and ops.shape[1] == OP_DTYPE.itemsize):
+            n_ops = ops.numel() // OP_DTYPE.itemsize
+        elif ops.dtype in (torch.int64, getattr(torch, "uint64", torch.int64)) and ops.dim() == 2 and ops.shape[1] == OP_DTYPE.itemsize // 8:
+            n_ops = ops.shape[0]
+        else:
+            raise ValueError(f"op tensor must be uint8 [n, {OP_DTYPE.itemsize}] / [n * {OP_DTYPE.itemsize}] or int64 [n, 3], got "
+                             f"{ops.dtype} {tuple(ops.shape)}")
+        self = cls.__new__(cls)
+        self.ctx = ctx or Context.default()
+        if ops.device.index is not None and ops.device.index != self.ctx.device:
+            raise ValueError(f"op tensor is on {ops.device}, the context on device {self.ctx.device}")
+        self.ops = None  # (on the device only)
+        self.wire_counts = (int(wire_counts[0]), int(wire_counts[1]))
+        self.keep_wires = bool(keep_wires)
+        self.handle = C.c_void_p()
+        flags = (_lib.RV_COMPILE_WHOLE_PROVER if whole_prover else 0) | (_lib.RV_COMPILE_KEEP_WIRES if keep_wires else 0)
+        torch.cuda.synchronize(ops.device)  # (the op list is complete before the library's stream reads it)
+        _lib.check(_lib.lib().rv_circuit_compile_device(self.ctx.handle, C.c_void_p(ops.data_ptr()), C.c_size_t(n_ops),
+                                                        C.c_size_t(self.wire_counts[0]), C.c_size_t(self.wire_counts[1]),
+                                                        C.c_uint32(flags), C.byref(self.handle)))
+        return self
 
     @property
     def info(self) -> dict:
