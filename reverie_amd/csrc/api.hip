@@ -26,6 +26,7 @@
 #include "internal.h"
 #include "launch.h"
 #include "ldsrun.h"
+#include "piece_pipe.h"
 
 using namespace rv;
 
@@ -43,6 +44,17 @@ static int hip_fail(hipError_t e, const char* what, const char* file, int line) 
         hipError_t e_ = (x);                                          \
         if (e_ != hipSuccess) return hip_fail(e_, #x, __FILE__, __LINE__); \
     } while (0)
+
+// the body of an extern "C" entry point: no exception crosses the C ABI (the only ones the library meets are failed host allocations)
+template <class F>
+static int guarded(F&& body) {
+    try {
+        return body();
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}
 
 extern "C" const char* rv_last_error(void) { return g_last_error.c_str(); }
 extern "C" uint32_t rv_abi_version(void) { return 8; }  // 3: verification strict by default (RV_VERIFY_REFERENCE_COMPAT), rv_bristol_parse takes n_expected,

@@ -88,12 +88,7 @@ static int eval_stream_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wire
 }
 
 extern "C" int rv_eval_stream_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch, size_t max_chunk_ops, rv_eval_stream** out) {
-    try {
-        return eval_stream_begin_impl(ctx, z64_wires, gf2_wires, batch, max_chunk_ops, out);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return eval_stream_begin_impl(ctx, z64_wires, gf2_wires, batch, max_chunk_ops, out); });
 }
 
 // value rows / SSA slots for a chunk: a larger block, the carried prefix copied over on the stream (the old block goes back to the arena;
@@ -233,93 +228,20 @@ static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, size_t n_o
     const size_t n_pieces = cut.size() - 1;
     const uint64_t first_op = E->n_ops;
     size_t u2 = 0, u64 = 0;
-    auto compile = [&](size_t i, std::unique_ptr<Compiled>& out) -> int {
-        ChunkStart cs;  // (values do not depend on mask phases or transcript offsets)
-        out.reset(new Compiled());
-        return compile_ops(ops + cut[i], cut[i + 1] - cut[i], E->z64_wires, E->gf2_wires, *out, &cs);
-    };
+    // the pieces are compiled ahead on worker threads and run in order (piece_pipe.h)
     const unsigned n_threads = (unsigned)std::min<size_t>(eval_stream_threads(), n_pieces);
-    if (n_threads <= 1) {
-        for (size_t i = 0; i < n_pieces; i++) {
-            std::unique_ptr<Compiled> cc;
-            int rc = compile(i, cc);
-            if (!rc) rc = eval_stream_chunk(E, *cc, first_op + cut[i], wit_gf2, n_gf2, wit_z64, n_z64, &u2, &u64);
-            if (rc) return E->sticky = rc;
-        }
-        E->n_ops += n_ops;
-        return RV_OK;
-    }
-    // ---- the pieces are compiled ahead on worker threads (a window of 2 x threads compiled pieces at most) and run in order
-    struct Piece {
-        std::unique_ptr<Compiled> cc;
-        int rc = 0;
-        bool ready = false;
-    };
-    std::vector<Piece> pieces(n_pieces);
-    std::mutex mu;
-    std::condition_variable cv;
-    size_t next = 0, consumed = 0;
-    bool stop = false;
-    const size_t window = 2 * (size_t)n_threads;
-    auto worker = [&] {
-        for (;;) {
-            size_t i;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || next >= n_pieces || next < consumed + window; });
-                if (stop || next >= n_pieces) return;
-                i = next++;
-            }
-            std::unique_ptr<Compiled> cc;
-            int rc;
-            try {
-                rc = compile(i, cc);
-            } catch (...) {
-                rc = RV_E_NOMEM;
-            }
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                pieces[i].cc = std::move(cc);
-                pieces[i].rc = rc;
-                pieces[i].ready = true;
-            }
-            cv.notify_all();
-        }
-    };
-    std::vector<std::thread> pool;
-    struct PoolGuard {  // stops and joins the workers on every way out
-        std::vector<std::thread>& pool;
-        std::mutex& mu;
-        std::condition_variable& cv;
-        bool& stop;
-        ~PoolGuard() {
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                stop = true;
-            }
-            cv.notify_all();
-            for (std::thread& t : pool)
-                if (t.joinable()) t.join();
-        }
-    } guard{pool, mu, cv, stop};
-    for (unsigned t = 0; t < n_threads; t++) pool.emplace_back(worker);
+    std::vector<std::unique_ptr<Compiled>> pieces(n_pieces);
+    PiecePipe pipe(n_pieces, n_threads, RV_E_NOMEM, [&](size_t i) {
+        ChunkStart cs;  // (values do not depend on mask phases or transcript offsets)
+        pieces[i].reset(new Compiled());
+        return compile_ops(ops + cut[i], cut[i + 1] - cut[i], E->z64_wires, E->gf2_wires, *pieces[i], &cs);
+    });
     int rc = RV_OK;
     for (size_t i = 0; i < n_pieces && !rc; i++) {
-        std::unique_ptr<Compiled> cc;
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return pieces[i].ready; });
-            rc = pieces[i].rc;
-            cc = std::move(pieces[i].cc);
-        }
-        if (!rc) rc = eval_stream_chunk(E, *cc, first_op + cut[i], wit_gf2, n_gf2, wit_z64, n_z64, &u2, &u64);
-        cc.reset();  // (host memory of the compiled piece: freed here, on the main thread, while the GPU runs it)
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            consumed = i + 1;
-            if (rc) stop = true;
-        }
-        cv.notify_all();
+        rc = pipe.wait(i);
+        if (!rc) rc = eval_stream_chunk(E, *pieces[i], first_op + cut[i], wit_gf2, n_gf2, wit_z64, n_z64, &u2, &u64);
+        pieces[i].reset();  // (host memory of the compiled piece: freed here, on the main thread, while the GPU runs it)
+        pipe.consumed(i, rc);
     }
     if (rc) return E->sticky = rc;
     E->n_ops += n_ops;
@@ -328,12 +250,9 @@ static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, size_t n_o
 
 extern "C" int rv_eval_stream_feed(rv_eval_stream* E, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
                                    size_t n_z64) {
-    try {
-        return eval_stream_feed_impl(E, ops, n_ops, wit_gf2, n_gf2, wit_z64, n_z64);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return E ? (E->sticky = RV_E_NOMEM) : RV_E_NOMEM;
-    }
+    const int rc = guarded([&] { return eval_stream_feed_impl(E, ops, n_ops, wit_gf2, n_gf2, wit_z64, n_z64); });
+    if (rc == RV_E_NOMEM && E) E->sticky = rc;  // (a thrown one too: the stream is dead after any failed allocation)
+    return rc;
 }
 
 static int eval_stream_finish_impl(rv_eval_stream* E, uint8_t* gf2_values, uint64_t* z64_values, rv_eval_status* st) {
@@ -382,12 +301,9 @@ static int eval_stream_finish_impl(rv_eval_stream* E, uint8_t* gf2_values, uint6
 }
 
 extern "C" int rv_eval_stream_finish(rv_eval_stream* E, uint8_t* gf2_values, uint64_t* z64_values, rv_eval_status* st) {
-    try {
-        return eval_stream_finish_impl(E, gf2_values, z64_values, st);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return E ? (E->sticky = RV_E_NOMEM) : RV_E_NOMEM;
-    }
+    const int rc = guarded([&] { return eval_stream_finish_impl(E, gf2_values, z64_values, st); });
+    if (rc == RV_E_NOMEM && E) E->sticky = rc;  // (a thrown one too: the stream is dead after any failed allocation)
+    return rc;
 }
 
 extern "C" int rv_eval_stream_get_info(const rv_eval_stream* E, rv_eval_stream_info* info) {

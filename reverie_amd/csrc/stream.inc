@@ -85,12 +85,23 @@ __global__ __launch_bounds__(256) void k_copy_rows_batched(CopyRows L) {
         ((uint32_t*)(L.dst[y] + row * L.dpitch[y]))[w] = ((const uint32_t*)(L.src[y] + row * L.spitch[y]))[w];
     }
 }
+// The small device-to-device copies of one step.  A batch stream collects them and flush() launches them together; a single stream
+// (direct) issues every add at once as the call it always was: hipMemcpyAsync for a contiguous run, hipMemcpy2DAsync for a strided
+// one, k_copy_segs for a CopySegs.  The first failure of a direct copy stays in `err`.
 struct CopyBatch {
     hipStream_t st;
+    bool direct;
+    hipError_t err = hipSuccess;
     CopyRows L{};
-    explicit CopyBatch(hipStream_t s) : st(s) {}
+    CopyBatch(hipStream_t s, bool direct_) : st(s), direct(direct_) {}
     void add(void* dst, uint64_t dpitch, const void* src, uint64_t spitch, uint64_t row_bytes, uint64_t rows) {
         if (!row_bytes || !rows) return;
+        if (direct) {
+            const hipError_t e = rows == 1 ? hipMemcpyAsync(dst, src, row_bytes, hipMemcpyDeviceToDevice, st)
+                                           : hipMemcpy2DAsync(dst, dpitch, src, spitch, row_bytes, rows, hipMemcpyDeviceToDevice, st);
+            if (err == hipSuccess) err = e;
+            return;
+        }
         if (L.n == CopyRows::MAX) flush();
         const uint32_t k = L.n++;
         L.src[k] = (const uint8_t*)src, L.dst[k] = (uint8_t*)dst, L.spitch[k] = spitch, L.dpitch[k] = dpitch;
@@ -98,13 +109,69 @@ struct CopyBatch {
     }
     void add(void* dst, const void* src, uint64_t bytes) { add(dst, bytes, src, bytes, bytes, 1); }
     void add(const CopySegs& cs) {
+        if (direct) return launch_copy_segs(st, cs);
         for (uint32_t i = 0; i < cs.n; i++) add(cs.dst[i], cs.src[i], cs.bytes[i]);
     }
     void flush() {
         if (L.n) hipLaunchKernelGGL(k_copy_rows_batched, dim3(16, L.n), dim3(256), 0, st, L);
         L.n = 0;
     }
+    // flush, and the code of the step's copies
+    int finish(const char* what) {
+        flush();
+        return err == hipSuccess ? RV_OK : hip_fail(err, what, __FILE__, __LINE__);
+    }
 };
+
+// The four transcript streams of a repetition -- GF(2) preprocessing / online, Z64 preprocessing / online -- in the order of
+// rv_stream::d_dig's slots.  What tells them apart is in TR_KIND; everything else treats them alike.
+enum { TR_PRE = 0, TR_ON = 1, TR_PRE64 = 2, TR_ON64 = 3, TR_KINDS = 4 };
+struct TranscriptKind {
+    uint32_t unit;      // events per 1 KiB BLAKE3 chunk
+    uint32_t ev_bytes;  // bytes of one event: a row over all repetitions (GF(2)) or one repetition's word (Z64)
+    bool per_rep;       // a buffer is [R][pitch] words, one row per repetition (Z64; the tail: [R][128]); else one row per event ([1024][ev_bytes])
+    // chaining values of the first n events of a buffer (pitch: a per-repetition buffer's words per row)
+    void (*hash)(hipStream_t st, const void* buf, uint64_t pitch, uint64_t n, uint32_t* cvs, uint64_t chunk_base, uint32_t root_ok);
+    uint64_t tail_bytes() const { return (uint64_t)(per_rep ? RV_TOTAL_REPS : 1) * unit * ev_bytes; }
+    // of `total` events, those that stay unhashed: the last, possibly incomplete chunk -- at least one event stays behind
+    uint64_t tail_of(uint64_t total) const { return total ? total - (total - 1) / unit * unit : 0; }
+    // n events from the front of src to the front of dst (pitches in words, per-repetition kinds only)
+    void copy(CopyBatch& cp, void* dst, uint64_t dpitch, const void* src, uint64_t spitch, uint64_t n) const {
+        if (per_rep)
+            cp.add(dst, dpitch * 8, src, spitch * 8, n * 8, RV_TOTAL_REPS);
+        else
+            cp.add(dst, src, n * ev_bytes);
+    }
+};
+static const TranscriptKind TR_KIND[TR_KINDS] = {
+    {1024, RV_TOTAL_REPS / 8, false,
+     [](hipStream_t st, const void* b, uint64_t, uint64_t n, uint32_t* cvs, uint64_t base, uint32_t root) {
+         launch_b3_stream_bits_chunks(st, (const uint8_t*)b, n, RV_TOTAL_REPS / 4, cvs, base, root);
+     }},
+    {1024, RV_TOTAL_REPS, false,
+     [](hipStream_t st, const void* b, uint64_t, uint64_t n, uint32_t* cvs, uint64_t base, uint32_t root) {
+         launch_b3_stream_chunks(st, (const uint32_t*)b, n, RV_TOTAL_REPS / 4, cvs, nullptr, 0, base, root);
+     }},
+    {128, 8, true,
+     [](hipStream_t st, const void* b, uint64_t pitch, uint64_t n, uint32_t* cvs, uint64_t base, uint32_t root) {
+         launch_b3_contig_chunks(st, (const uint64_t*)b, pitch, n, RV_TOTAL_REPS, cvs, base, root);
+     }},
+    {128, 8, true,
+     [](hipStream_t st, const void* b, uint64_t pitch, uint64_t n, uint32_t* cvs, uint64_t base, uint32_t root) {
+         launch_b3_contig_chunks(st, (const uint64_t*)b, pitch, n, RV_TOTAL_REPS, cvs, base, root);
+     }},
+};
+// the carried events of the four streams as a chunk's compile takes them
+static void set_carried(ChunkStart& cs, uint64_t pre, uint64_t on, uint64_t pre64, uint64_t on64) {
+    cs.pre0 = pre, cs.on0 = on, cs.pre_words64_0 = pre64, cs.on_words64_0 = on64;
+}
+static bool same_carried(const ChunkStart& a, const ChunkStart& b) {
+    return a.on0 == b.on0 && a.pre0 == b.pre0 && a.on_words64_0 == b.on_words64_0 && a.pre_words64_0 == b.pre_words64_0;
+}
+// (unsigned differences: the 32-bit fields of the arrays wrap the same way)
+static void relocate_to(Compiled& cc, const ChunkStart& from, const ChunkStart& to) {
+    relocate_chunk(cc, to.on0 - from.on0, to.pre0 - from.pre0, to.on_words64_0 - from.on_words64_0, to.pre_words64_0 - from.pre_words64_0);
+}
 
 struct rv_stream {
     rv_ctx* ctx = nullptr;
@@ -125,13 +192,14 @@ struct rv_stream {
     int* d_err0 = nullptr;
     bool unsettled = false;  // chunks were issued without a wait: stream_feed_settle reads d_err behind them
     StreamTotals run, tot;  // running counters of the current pass / totals of pass 1
-    // pass 1: unhashed tails (events of the last, incomplete BLAKE3 chunk) and the incremental trees
-    uint32_t* d_on_tail = nullptr;    // [1024][NQ]
-    uint8_t* d_pre_tail = nullptr;    // [1024][NQ/2]
-    uint64_t* d_on64_tail = nullptr;  // [R][128]
-    uint64_t* d_pre64_tail = nullptr; // [R][128]
-    uint64_t on_tail = 0, pre_tail = 0, on64_tail = 0, pre64_tail = 0;
-    IncHash h_pre, h_on, h_pre64, h_on64;
+    // pass 1: per transcript stream (TR_PRE .. TR_ON64) the incremental tree and the unhashed tail: the events of the last, incomplete
+    // BLAKE3 chunk -- [1024][NQ/2] bytes, [1024][NQ] u32, [R][128] u64 twice (TR_KIND)
+    struct Transcript {
+        IncHash tree;
+        uint8_t* d_tail = nullptr;
+        uint64_t tail = 0;  // events in d_tail
+    };
+    Transcript tr[TR_KINDS];
     uint32_t* d_dig = nullptr;  // [4][R][8]
     uint8_t* d_h = nullptr;     // [R][32]
     // pass 2
@@ -196,7 +264,7 @@ struct rv_stream {
     bool p2_skipped = false;  // pass 2: a chunk was served from kept transcripts (the wire store is stale from there on)
     // A BATCH stream (rv_stream_begin_batch / rv_stream_verify_begin_batch with batch > 1) is a handle over `bat`: one complete
     // single-proof stream per witness / proof, none of which is the handle.  The handle holds no device memory; a feed compiles each
-    // chunk once (on the first member that runs: its cache, its counts) and issues the chunk for every member (stream_chunk_run).
+    // chunk once (on the first member that runs: its cache, its counts) and issues the chunk for every member (ChunkRun).
     std::vector<rv_stream*> bat;
     // the proofs a feed runs for: the stream itself, or the batch's members (a verifier's members with a malformed proof run nothing)
     std::vector<rv_stream*> running() {
@@ -220,65 +288,29 @@ struct rv_stream {
     }
 
     void free_all() {
-        void* ps[] = {d_seeds, d_keys, d_rkbytes, d_rk, d_rows, d_corr, d_wmask64, d_wcorr64, d_err, d_err0, d_on_tail, d_pre_tail, d_on64_tail, d_pre64_tail,
-                      d_dig, d_h, d_omit, d_offs, d_proof, d_pend_rec, d_pend_in, d_pend_pre,
+        void* ps[] = {d_seeds, d_keys, d_rkbytes, d_rk, d_rows, d_corr, d_wmask64, d_wcorr64, d_err, d_err0, d_dig, d_h, d_omit, d_offs, d_proof, d_pend_rec, d_pend_in, d_pend_pre,
                       d_vproof, d_omit_v, d_omit64_v, d_hco, d_hco64, d_keep, d_keep64, d_onm, d_rk64, d_src};
         for (void* p : ps) ctx->release(p);
         for (auto& kv : kept) release_kept(kv.second);
         kept.clear();
-        for (IncHash* h : {&h_pre, &h_on, &h_pre64, &h_on64})
-            for (uint32_t* p : h->node) ctx->release(p);
+        for (Transcript& t : tr) {
+            ctx->release(t.d_tail);
+            for (uint32_t* p : t.tree.node) ctx->release(p);
+        }
     }
 };
 
-// one level of the binary counter per loop trip: [pending?] ++ cur is paired up, an odd last node becomes the new pending
-static int inc_absorb(rv_ctx* ctx, IncHash& H, uint32_t* cvs, uint64_t n, uint32_t R) {
-    hipStream_t st = ctx->stream;
-    uint32_t* cur = cvs;
-    bool cur_owned = false;
-    uint64_t n_cur = n;
-    size_t lvl = 0;
-    int rc;
-    while (n_cur) {
-        if (H.node.size() <= lvl) {
-            uint32_t* p = nullptr;
-            if ((rc = dalloc(ctx, (size_t)R * 8, &p))) return rc;
-            H.node.push_back(p);
-            H.full.push_back(0);
-        }
-        const bool pend = H.full[lvl] != 0;
-        const uint64_t total = n_cur + (pend ? 1 : 0), pairs = total / 2;
-        uint32_t* out = nullptr;
-        if (pairs) {
-            if ((rc = dalloc(ctx, (size_t)pairs * R * 8, &out))) return rc;
-            launch_b3_pairs(st, pend ? H.node[lvl] : nullptr, cur, pairs, R, out);
-        }
-        if (total & 1) {
-            HIPCHK(hipMemcpyAsync(H.node[lvl], cur + (size_t)(n_cur - 1) * R * 8, (size_t)R * 32, hipMemcpyDeviceToDevice, st));
-            H.full[lvl] = 1;
-        } else {
-            H.full[lvl] = 0;
-        }
-        if (cur_owned) ctx->release(cur);  // (stream order keeps the arena's reuse behind the kernels that read it)
-        cur = out;
-        cur_owned = true;
-        n_cur = pairs;
-        lvl++;
-    }
-    if (cur_owned) ctx->release(cur);
-    H.chunks += n;
-    return RV_OK;
-}
-
-// inc_absorb for the proofs of a batch stream at once: their trees have the same shape (the same event counts), so every level is one
-// k_b3_pairs_batched launch over them and one copy of their odd nodes.  cvs[b]: proof b's n chaining values.
-static int inc_absorb_batch(rv_ctx* ctx, const std::vector<IncHash*>& Hs, const std::vector<uint32_t*>& cvs, uint64_t n, uint32_t R) {
+// n chaining values per proof into the proofs' trees (one proof for a single stream; cvs[b]: proof b's).  One level of the binary
+// counter per loop trip: [pending?] ++ cur is paired up, an odd last node becomes the new pending.  The trees of a batch have the same
+// shape (the same event counts), so every level is one k_b3_pairs_batched launch over them and one copy of their odd nodes; a single
+// stream keeps launch_b3_pairs and a hipMemcpyAsync.
+static int inc_absorb(rv_ctx* ctx, const std::vector<IncHash*>& Hs, const std::vector<uint32_t*>& cvs, uint64_t n, uint32_t R) {
     hipStream_t st = ctx->stream;
     const size_t B = Hs.size();
     for (IncHash* H : Hs)
         if (H->chunks != Hs[0]->chunks || H->full != Hs[0]->full || H->node.size() != Hs[0]->node.size()) {
             for (size_t b = 0; b < B; b++) {  // (cannot happen: the members see the same chunks)
-                int rc = inc_absorb(ctx, *Hs[b], cvs[b], n, R);
+                int rc = inc_absorb(ctx, {Hs[b]}, {cvs[b]}, n, R);
                 if (rc) return rc;
             }
             return RV_OK;
@@ -288,7 +320,7 @@ static int inc_absorb_batch(rv_ctx* ctx, const std::vector<IncHash*>& Hs, const 
     uint64_t n_cur = n;
     size_t lvl = 0;
     int rc;
-    CopyBatch cp(st);
+    CopyBatch cp(st, B == 1);
     while (n_cur) {
         if (Hs[0]->node.size() <= lvl)
             for (IncHash* H : Hs) {
@@ -304,7 +336,8 @@ static int inc_absorb_batch(rv_ctx* ctx, const std::vector<IncHash*>& Hs, const 
             uint32_t* blk = nullptr;  // (one allocation for the level's outputs of every proof)
             if ((rc = dalloc(ctx, (size_t)B * pairs * R * 8, &blk))) return rc;
             for (size_t b = 0; b < B; b++) out[b] = blk + b * pairs * R * 8;
-            for (size_t b0 = 0; b0 < B; b0 += B3PairsBatch::MAX) {
+            if (B == 1) launch_b3_pairs(st, pend ? Hs[0]->node[lvl] : nullptr, cur[0], pairs, R, out[0]);
+            for (size_t b0 = 0; B > 1 && b0 < B; b0 += B3PairsBatch::MAX) {
                 B3PairsBatch L{};
                 for (size_t b = b0; b < std::min(B, b0 + B3PairsBatch::MAX); b++, L.n++) {
                     L.pending[L.n] = pend ? Hs[b]->node[lvl] : nullptr;
@@ -316,7 +349,7 @@ static int inc_absorb_batch(rv_ctx* ctx, const std::vector<IncHash*>& Hs, const 
         }
         if (total & 1)
             for (size_t b = 0; b < B; b++) cp.add(Hs[b]->node[lvl], cur[b] + (size_t)(n_cur - 1) * R * 8, (size_t)R * 32);
-        cp.flush();
+        if ((rc = cp.finish("tree node copy"))) return rc;
         for (IncHash* H : Hs) H->full[lvl] = (total & 1) ? 1 : 0;
         if (cur_owned) ctx->release(cur[0]);  // (stream order keeps the arena's reuse behind the kernels that read it)
         cur = out;
@@ -388,12 +421,12 @@ static int stream_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, co
     };
     if ((rc = dalloc(ctx, (size_t)R * 16, &S->d_seeds)) || (rc = dalloc(ctx, (size_t)R * 128, &S->d_keys)) ||
         (rc = dalloc(ctx, (size_t)R * 8 * RK_BYTES, &S->d_rkbytes)) || (rc = dalloc(ctx, (size_t)RK_AREAS * 128 * NQ, &S->d_rk)) ||
-        (rc = dalloc(ctx, 1, &S->d_err)) || (rc = dalloc(ctx, 1, &S->d_err0)) || (rc = dalloc(ctx, (size_t)1024 * NQ, &S->d_on_tail)) ||
-        (rc = dalloc(ctx, (size_t)1024 * (NQ / 2), &S->d_pre_tail)) || (rc = dalloc(ctx, (size_t)R * 128, &S->d_on64_tail)) ||
-        (rc = dalloc(ctx, (size_t)R * 128, &S->d_pre64_tail)) || (rc = dalloc(ctx, (size_t)4 * R * 8, &S->d_dig)) ||
+        (rc = dalloc(ctx, 1, &S->d_err)) || (rc = dalloc(ctx, 1, &S->d_err0)) || (rc = dalloc(ctx, (size_t)TR_KINDS * R * 8, &S->d_dig)) ||
         (rc = dalloc(ctx, (size_t)R * 32, &S->d_h)) || (rc = dalloc(ctx, (size_t)8 * NQ, &S->d_pend_rec)) ||
         (rc = dalloc(ctx, (size_t)8 * NQ, &S->d_pend_in)) || (rc = dalloc(ctx, (size_t)8 * (NQ / 2), &S->d_pend_pre)))
         return fail(rc);
+    for (int kind = 0; kind < TR_KINDS; kind++)
+        if ((rc = dalloc(ctx, TR_KIND[kind].tail_bytes(), &S->tr[kind].d_tail))) return fail(rc);
     if (hipMemcpyAsync(S->d_seeds, seeds, (size_t)R * 16, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
     if (hipMemsetAsync(S->d_err, 0, sizeof(int), ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
     launch_expand_seeds(ctx->stream, S->d_seeds, R, S->d_keys);
@@ -405,12 +438,7 @@ static int stream_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, co
 }
 
 extern "C" int rv_stream_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, const uint8_t* seeds, size_t max_chunk_ops, rv_stream** out) {
-    try {
-        return stream_begin_impl(ctx, z64_wires, gf2_wires, seeds, max_chunk_ops, out);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return stream_begin_impl(ctx, z64_wires, gf2_wires, seeds, max_chunk_ops, out); });
 }
 
 // wire store large enough for the chunk; the carried region survives a reallocation
@@ -489,11 +517,7 @@ static uint64_t wit_digest(const uint8_t* w2, size_t n2, uint64_t first2, const 
     return sum;
 }
 
-// one chunk of the gate stream through masks -> interpreter -> (pass 1) chunk hashes / (pass 2) openings
-// The host side of a chunk: levelising 10^6 ops takes ~0.1 s on one core, ~200 times the chunk's GPU work, and needs
-// nothing of the stream's state but the two ShareGen phases (transcript offsets are added afterwards, relocate_chunk).
-// A feed of several chunks therefore compiles them on worker threads ahead of the GPU (stream_feed_impl).
-// at: the transcript offsets to compile the piece at (null: zero -- relocate_chunk moves it later)
+// one piece compiled as a streaming chunk.  at: the transcript offsets to compile it at (null: zero -- relocate_chunk moves it later)
 static int stream_compile_piece(const rv_stream* S, const rv_op* ops, size_t n_ops, uint32_t mask_phase, uint32_t mask64_phase, rv_circuit** out,
                                 const ChunkStart* at = nullptr) {
     ChunkStart cs;
@@ -533,197 +557,245 @@ static int stream_read_errs(const std::vector<rv_stream*>& proofs, const char* w
     return RV_OK;
 }
 
-// c: the chunk compiled by stream_compile_piece with the phases the stream is at now (consumed here)
-// digest: ops_digest of the chunk's ops at their position in the stream; carried: the transcript offsets c's arrays already
-// hold (zero for a fresh compile, pass 1's for a chunk that comes out of the cache)
-// proofs: the proofs the chunk runs for (proofs[0] == S, which holds the host-side state: cache, counts, pass); proof b takes its
-// witness at wit_gf2 + b * stride2 and wit_z64 + b * stride64.  The compile, relocation and gate upload happen once; for a batch the
-// level loop, the tree levels and the small copies run once with the proof in gridDim.y, the masks, chunk hashes and openings
-// proof after proof, with no wait between them.
-static int stream_chunk_run(rv_stream* S, const std::vector<rv_stream*>& proofs, rv_circuit* c, uint64_t digest, size_t n_ops, const uint8_t* wit_gf2,
-                            size_t n_gf2, size_t stride2, const uint64_t* wit_z64, size_t n_z64, size_t stride64, size_t* used_gf2, size_t* used_z64,
-                            const ChunkStart& carried = ChunkStart()) {
-    rv_ctx* ctx = S->ctx;
-    hipStream_t st = ctx->stream;
-    constexpr uint32_t R = rv_stream::R, NQ = rv_stream::NQ;
-    const bool p1 = S->pass == 1;
-    const bool ver = S->pass == 3;        // the streaming verifier: verify-mode chunks, transcripts hashed as in pass 1
-    const bool hashing = p1 || ver;
-    ChunkStart cs;
-    cs.mask_phase = (uint32_t)(S->run.masks % 128);
-    cs.mask64_phase = (uint32_t)(S->run.masks64 % 2);
-    cs.on0 = hashing ? S->on_tail : S->pend_rec + S->pend_in;
-    cs.pre0 = hashing ? S->pre_tail : S->pend_pre;
-    cs.on_words64_0 = hashing ? S->on64_tail : 0;
-    cs.pre_words64_0 = hashing ? S->pre64_tail : 0;
-    static const bool stats = getenv("RV_STREAM_STATS") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-    const auto t_begin = now();
-    // (unsigned differences: the 32-bit fields of the arrays wrap the same way)
-    if (stats && (cs.on0 != carried.on0 || cs.pre0 != carried.pre0 || cs.on_words64_0 != carried.on_words64_0 || cs.pre_words64_0 != carried.pre_words64_0)) {
-        static int moved = 0;
-        if (++moved <= 3) fprintf(stderr, "[rv stream] a chunk's transcript offsets are moved on the main thread (not predicted, or a single-piece feed)\n");
+// the witnesses of a feed: proof b's elements at gf2 + b * stride2 and z64 + b * stride64, n_gf2 / n_z64 of them still unconsumed
+struct WitnessRows {
+    const uint8_t* gf2;
+    size_t n_gf2, stride2;
+    const uint64_t* z64;
+    size_t n_z64, stride64;
+    const uint8_t* gf2_of(size_t b) const { return gf2 ? gf2 + b * stride2 : nullptr; }
+    const uint64_t* z64_of(size_t b) const { return z64 ? z64 + b * stride64 : nullptr; }
+    void advance(size_t u2, size_t u64) {
+        gf2 = gf2 ? gf2 + u2 : gf2;
+        n_gf2 -= u2;
+        z64 = z64 ? z64 + u64 : z64;
+        n_z64 -= u64;
     }
-    if (cs.on0 != carried.on0 || cs.pre0 != carried.pre0 || cs.on_words64_0 != carried.on_words64_0 || cs.pre_words64_0 != carried.pre_words64_0)
-        c->staged = nullptr;  // (a worker's page-locked copy of the arrays predates this move)
-    relocate_chunk(c->cc, cs.on0 - carried.on0, cs.pre0 - carried.pre0, cs.on_words64_0 - carried.on_words64_0, cs.pre_words64_0 - carried.pre_words64_0);
-    const auto t_reloc = now();
-    int rc;
-    const Compiled& cc = c->cc;
-    if (!ver && (cc.n_in > n_gf2 || cc.n_in64 > n_z64)) {
-        rv_circuit_destroy(c);
-        return RV_E_WITNESS_SHORT;
+};
+
+// One chunk of the gate stream through masks -> interpreter -> (pass 1, verifier) chunk hashes / (pass 2) openings, as a sequence of
+// steps that run() calls in order:
+//   plan (offsets, relocate, witness / CTR-range checks, kept-chunk match) -> upload -> per proof: buffers (kept / keep / scratch),
+//   carried events in, witness copy, verifier's supplied values, masks, parameter block, k_shard_init, (single) level loop ->
+//   (batch) parameter upload + batched level loop -> hashing: chunk hashes, trees, tails -> pass 2: openings per proof ->
+//   kept-set consistency -> error flags / no-wait -> counters.
+// The compile, relocation and gate upload happen once; a batch (proofs.size() > 1) takes each step for all its proofs together where
+// it can: the small copies go into one k_copy_rows_batched launch per step (CopyBatch), the level loop is launch_levels_batched over
+// per-proof parameter blocks (the proof in gridDim.y, as rv_prove_batch), the trees grow through k_b3_pairs_batched; the masks, chunk
+// hashes and openings go proof after proof, with no wait between them.  A single stream keeps its own launches.
+// The host side of a chunk: levelising 10^6 ops takes ~0.1 s on one core, ~200 times the chunk's GPU work, and needs nothing of the
+// stream's state but the two ShareGen phases (transcript offsets are added afterwards, relocate_chunk).  A feed of several chunks
+// therefore compiles them on worker threads ahead of the GPU (stream_feed_impl).
+struct ChunkRun {
+    static constexpr uint32_t R = rv_stream::R, NQ = rv_stream::NQ;
+    using Clock = std::chrono::steady_clock;
+    struct ProofBufs {  // one proof's buffers of the chunk
+        uint8_t* tr[TR_KINDS] = {nullptr, nullptr, nullptr, nullptr};  // its transcripts, carried events in front
+        uint64_t pitch[TR_KINDS] = {0, 0, 1, 1};                      // words per repetition of the Z64 ones
+        rv_stream::Kept* kp = nullptr;                                // pass 1's kept transcripts of this chunk (use_kept)
+        uint8_t* d_wit = nullptr;
+        uint64_t *d_wit64 = nullptr, *d_masks64 = nullptr;
+        uint32_t *d_sup_in = nullptr, *d_sup_corr = nullptr, *d_sup_rec = nullptr;  // verifier: the values the proof supplies
+        uint64_t *d_sup_in64 = nullptr, *d_sup_corr64 = nullptr, *d_sup_rec64 = nullptr;
+        uint32_t* on() const { return (uint32_t*)tr[TR_ON]; }
+        uint8_t* pre() const { return tr[TR_PRE]; }
+        uint64_t* on64() const { return (uint64_t*)tr[TR_ON64]; }
+        uint64_t* pre64() const { return (uint64_t*)tr[TR_PRE64]; }
+    };
+
+    rv_stream* const S;                      // proofs[0]: holds the host-side state (cache, counts, pass)
+    const std::vector<rv_stream*>& proofs;   // the proofs the chunk runs for
+    rv_circuit* c;                           // the chunk, compiled with the phases the stream is at now (consumed here)
+    const uint64_t digest;                   // ops_digest of the chunk's ops at their position in the stream
+    const size_t n_ops;
+    const WitnessRows wit;
+    rv_ctx* const ctx;
+    const hipStream_t st;
+    const bool p1, ver, hashing, batched;    // ver: the streaming verifier ("pass 3"): verify-mode chunks, transcripts hashed as in pass 1
+    const Compiled& cc;
+    const uint64_t first_op;
+    const bool has64;
+    const uint64_t first_block, n_blocks, first_block64, n_blocks64;  // the chunk's CTR blocks of the two mask generators
+    ChunkStart cs;                           // where the chunk starts: mask phases, carried events
+    bool use_kept = false;                   // pass 2 of a chunk whose transcripts pass 1 kept: only the openings are taken from them
+    bool no_wait = false;
+    bool tr64 = false;                       // the chunk has Z64 transcripts
+    uint64_t on_rows = 1, pre_rows = 1;      // rows of its GF(2) transcript buffers
+    size_t used_gf2 = 0, used_z64 = 0;       // witness elements a chunk that ran has consumed, per proof
+    std::vector<void*> tmp;                  // scratch, released when the chunk is issued (the next chunk's buffers reuse it behind it on the stream)
+    std::vector<ProofBufs> pbs;
+    std::vector<InterpParams> pps;
+    std::vector<Interp64Params> pp64s;
+    CopyBatch cp;
+    Clock::time_point t_begin = Clock::now(), t_reloc, t_up, t_alloc, t_issue, t_gpu;
+
+    ChunkRun(const std::vector<rv_stream*>& proofs_, rv_circuit* c_, uint64_t digest_, size_t n_ops_, const WitnessRows& wit_)
+        : S(proofs_[0]), proofs(proofs_), c(c_), digest(digest_), n_ops(n_ops_), wit(wit_), ctx(S->ctx), st(ctx->stream), p1(S->pass == 1), ver(S->pass == 3),
+          hashing(p1 || ver), batched(proofs_.size() > 1), cc(c_->cc), first_op(S->run.n_ops), has64(!cc.gates64.empty()),
+          first_block(S->run.masks / 128), n_blocks(cc.n_masks_pad / 128), first_block64(S->run.masks64 / 2), n_blocks64((cc.n_masks64 + 1) / 2),
+          pbs(proofs_.size()), pps(proofs_.size()), pp64s(proofs_.size()), cp(st, !batched) {
+        cs.mask_phase = (uint32_t)(S->run.masks % 128);
+        cs.mask64_phase = (uint32_t)(S->run.masks64 % 2);
+        if (hashing)
+            set_carried(cs, S->tr[TR_PRE].tail, S->tr[TR_ON].tail, S->tr[TR_PRE64].tail, S->tr[TR_ON64].tail);
+        else
+            set_carried(cs, S->pend_pre, S->pend_rec + S->pend_in, 0, 0);
     }
-    if (!ver && ((cc.n_in && !wit_gf2) || (cc.n_in64 && !wit_z64))) {
-        rv_circuit_destroy(c);
-        return RV_E_ARG;
-    }
-    const uint64_t first_block = S->run.masks / 128, n_blocks = cc.n_masks_pad / 128;
-    const uint64_t first_block64 = S->run.masks64 / 2, n_blocks64 = (cc.n_masks64 + 1) / 2;
-    if (first_block + n_blocks > RV_MAX_CTR_BLOCKS || first_block64 + n_blocks64 > RV_MAX_CTR_BLOCKS) {
-        delete c;
-        return RV_E_UNSUPPORTED;  // the mask kernels' first-round shortcut covers CTR indices below 2^24 (internal.h)
-    }
-    const uint64_t first_op = S->run.n_ops;
-    // pass 2 of a chunk whose transcripts pass 1 kept: only the openings are taken from them (for every proof of the stream or for none)
-    bool use_kept = false;
-    if (S->pass == 2) {
-        size_t n_match = 0, n_found = 0;
-        for (rv_stream* Q : proofs) {
-            auto it = Q->kept.find(first_op);
-            if (it == Q->kept.end()) continue;
-            n_found++;
-            n_match += it->second.n_ops == n_ops && it->second.digest == digest;
+
+    // carried: the transcript offsets c's arrays already hold (zero for a fresh compile, pass 1's for a chunk out of the cache)
+    int run(const ChunkStart& carried) {
+        if (int rc = plan(carried)) {  // (nothing of the chunk is on the stream yet)
+            rv_circuit_destroy(c);
+            return rc;
         }
-        use_kept = n_found && n_match == proofs.size();
-        if (n_found && !use_kept)  // (cut differently, or other ops: finish reports those) -- of no use any more
+        return finish(issue());
+    }
+
+    int plan(const ChunkStart& carried) {
+        static const bool stats = getenv("RV_STREAM_STATS") != nullptr;
+        if (!same_carried(cs, carried)) {
+            static int moved = 0;
+            if (stats && ++moved <= 3) fprintf(stderr, "[rv stream] a chunk's transcript offsets are moved on the main thread (not predicted, or a single-piece feed)\n");
+            c->staged = nullptr;  // (a worker's page-locked copy of the arrays predates this move)
+        }
+        relocate_to(c->cc, carried, cs);
+        t_reloc = Clock::now();
+        on_rows = std::max<uint64_t>(cc.n_on, 1), pre_rows = std::max<uint64_t>(cc.n_pre, 1);  // (the compiled counters include the carried events)
+        tr64 = has64 || cc.on_words64 || cc.pre_words64;
+        if (!ver && (cc.n_in > wit.n_gf2 || cc.n_in64 > wit.n_z64)) return RV_E_WITNESS_SHORT;
+        if (!ver && ((cc.n_in && !wit.gf2) || (cc.n_in64 && !wit.z64))) return RV_E_ARG;
+        // the mask kernels' first-round shortcut covers CTR indices below 2^24 (internal.h)
+        if (first_block + n_blocks > RV_MAX_CTR_BLOCKS || first_block64 + n_blocks64 > RV_MAX_CTR_BLOCKS) return RV_E_UNSUPPORTED;
+        // pass 2 of a chunk whose transcripts pass 1 kept: for every proof of the stream or for none
+        if (S->pass == 2) {
+            size_t n_match = 0, n_found = 0;
             for (rv_stream* Q : proofs) {
                 auto it = Q->kept.find(first_op);
                 if (it == Q->kept.end()) continue;
-                Q->release_kept(it->second);
-                Q->kept.erase(it);
+                n_found++;
+                n_match += it->second.n_ops == n_ops && it->second.digest == digest;
             }
+            use_kept = n_found && n_match == proofs.size();
+            if (n_found && !use_kept) drop_kept_chunk();  // (cut differently, or other ops: finish reports those) -- of no use any more
+        }
+        if (use_kept)
+            for (rv_stream* Q : proofs) Q->p2_skipped = true;
+        if (!use_kept && S->pass == 2 && S->p2_skipped) {
+            g_last_error = "rv_stream_same_cuts was promised, but pass 2 is not fed in pass 1's pieces";
+            return RV_E_ARG;
+        }
+        return RV_OK;
     }
-    if (use_kept)
-        for (rv_stream* Q : proofs) Q->p2_skipped = true;
-    if (!use_kept && S->pass == 2 && S->p2_skipped) {
-        g_last_error = "rv_stream_same_cuts was promised, but pass 2 is not fed in pass 1's pieces";
-        rv_circuit_destroy(c);
-        return RV_E_ARG;
+
+    // every step from the upload on; whatever it returns goes through finish()
+    int issue() {
+        int rc;
+        if ((rc = upload())) return rc;
+        for (size_t bi = 0; bi < proofs.size(); bi++)
+            if ((rc = issue_proof(bi))) return rc;
+        if ((rc = cp.finish("carried events"))) return rc;  // (the carried events are in place before any level runs)
+        if (batched && !use_kept && (rc = run_levels_batched())) return rc;
+        if (hashing && (rc = hash_transcripts())) return rc;
+        for (size_t bi = 0; bi < proofs.size() && !hashing; bi++)
+            if ((rc = open_proof(bi))) return rc;
+        if ((rc = cp.finish("pending rows"))) return rc;
+        keep_for_all_or_none();
+        t_issue = Clock::now();
+        if ((rc = settle())) return rc;
+        count();
+        return RV_OK;
     }
-    // ---- buffers of this chunk
-    std::vector<void*> tmp;  // released when a proof's work is issued (the next proof's buffers reuse them behind it on the stream)
-    rv_stream* P = S;                 // the proof being issued
-    rv_stream::Kept* kp = nullptr;    // its kept transcripts of this chunk (use_kept)
-    auto release_tmp = [&] {
+
+    // With no wait per chunk, work of this chunk may still be in flight: an error waits for the stream before the chunk, its scratch
+    // and a matched Kept entry go back.  A successful pass-1 chunk goes into the compiled-chunk cache.
+    int finish(int code) {
+        if (code != RV_OK) (void)hipStreamSynchronize(st);
         for (void* p : tmp) ctx->release(p);
         tmp.clear();
-    };
-    auto drop_all_kept = [&] {
+        if (use_kept) drop_kept_chunk();  // (back to the arena: whatever takes them next is ordered behind this chunk's kernels on the stream)
+        if (code == RV_OK && p1) {        // keep the compiled chunk for pass 2 (host arrays only; the device copies go back to the arena)
+            static const uint64_t cap = (uint64_t)(getenv("RV_STREAM_CACHE_MB") ? std::max(atoi(getenv("RV_STREAM_CACHE_MB")), 0) : 1024) << 20;
+            const uint64_t b = rv_stream::compiled_bytes(c->cc);
+            if (S->cache_bytes + b <= cap) {
+                rv_stream::CachedPiece& k = S->cache[first_op];
+                k.n_ops = n_ops;
+                k.digest = digest;
+                k.at = cs;
+                k.cc = std::move(c->cc);
+                S->cache_bytes += b;
+            }
+        }
+        rv_circuit_destroy(c);
+        c = nullptr;
+        return code;
+    }
+
+    void drop_kept_chunk() {
+        for (rv_stream* Q : proofs) {
+            auto it = Q->kept.find(first_op);
+            if (it == Q->kept.end()) continue;
+            Q->release_kept(it->second);
+            Q->kept.erase(it);
+        }
+    }
+    void drop_all_kept() {
         for (rv_stream* Q : proofs) {
             for (auto& kv : Q->kept) Q->release_kept(kv.second);
             Q->kept.clear();
             Q->keep_cap = 0;
         }
-    };
-    auto done = [&](int code) {
-        if (code != RV_OK) (void)hipStreamSynchronize(st);
-        release_tmp();
-        if (use_kept)  // (back to the arena: whatever takes them next is ordered behind this chunk's kernels on the stream)
-            for (rv_stream* Q : proofs) {
-                auto it = Q->kept.find(first_op);
-                if (it == Q->kept.end()) continue;
-                Q->release_kept(it->second);
-                Q->kept.erase(it);
-            }
-        if (code == RV_OK && p1) {  // keep the compiled chunk for pass 2 (host arrays only; the device copies go back to the arena)
-            static const uint64_t cap = (uint64_t)(getenv("RV_STREAM_CACHE_MB") ? std::max(atoi(getenv("RV_STREAM_CACHE_MB")), 0) : 1024) << 20;
-            const uint64_t b = rv_stream::compiled_bytes(c->cc);
-            if (S->cache_bytes + b <= cap) {
-                rv_stream::CachedPiece& cp = S->cache[first_op];
-                cp.n_ops = n_ops;
-                cp.digest = digest;
-                cp.at = cs;
-                cp.cc = std::move(c->cc);
-                S->cache_bytes += b;
-            }
-        }
-        rv_circuit_destroy(c);
-        return code;
-    };
-    auto take = [&](size_t bytes, void** p) {
-        int r = ctx->alloc(bytes, p);
+    }
+    // device scratch of the chunk
+    template <class T>
+    int take(size_t bytes, T** out) {
+        void* p = nullptr;
+        int r = ctx->alloc(bytes, &p);
         bool any_kept = false;
         for (rv_stream* Q : proofs) any_kept = any_kept || !Q->kept.empty();
-        if (r == RV_E_NOMEM && !kp && any_kept) {  // the kept transcripts are a convenience of pass 2: they go before a chunk fails for memory
+        if (r == RV_E_NOMEM && !use_kept && any_kept) {  // the kept transcripts are a convenience of pass 2: they go before a chunk fails for memory
             (void)hipStreamSynchronize(st);
             drop_all_kept();
             ctx->trim();
-            r = ctx->alloc(bytes, p);
+            r = ctx->alloc(bytes, &p);
         }
-        if (!r) tmp.push_back(*p);
+        if (!r) tmp.push_back(p);
+        *out = (T*)p;
         return r;
-    };
-    // (every exit from here on goes through done(): with no wait per chunk, work of this chunk may still be in flight, and done() waits for it on
-    // an error before the chunk, its scratch and a matched Kept entry go back)
-#define SCHK(x)                                                          \
-    do {                                                                 \
-        hipError_t e_ = (x);                                             \
-        if (e_ != hipSuccess) return done(hip_fail(e_, #x, __FILE__, __LINE__)); \
-    } while (0)
-    // no wait per chunk (the feed ends with one: stream_feed_settle) unless the phase timers are on or the piece is not in a ring slot
-    if (!use_kept && (rc = circuit_upload(ctx, c, !ctx->profiling))) {
-        c = nullptr;  // (circuit_upload destroys the circuit on every failure)
-        return done(rc);
     }
-    const bool no_wait = !use_kept && c->upload_pending && !(ver && !c->cc.gates64.empty());  // (the verifier's Z64 chunks feed a copy from a local array)
-    const auto t_up = now();
-    const uint64_t on_rows = std::max<uint64_t>(cc.n_on, 1), pre_rows = std::max<uint64_t>(cc.n_pre, 1);
-    const bool has64 = !cc.gates64.empty();
-    const bool tr64 = has64 || cc.on_words64 || cc.pre_words64;
-    // own events of this chunk (the compiled counters include the carried ones in front)
-    const uint64_t new_on = cc.n_on - cs.on0, new_pre = cc.n_pre - cs.pre0;
-    const uint64_t new_on64 = cc.on_words64 - cs.on_words64_0, new_pre64 = cc.pre_words64 - cs.pre_words64_0;
-    auto t_alloc = now();
-    // A batch stream (proofs.size() > 1) takes each step of the chunk for all its proofs together where it can: the small copies go
-    // into one k_copy_rows_batched launch per step, the level loop is launch_levels_batched over per-proof parameter blocks (the
-    // proof in gridDim.y, as rv_prove_batch), the trees grow through k_b3_pairs_batched.  A single stream keeps its own launches.
-    const size_t NB = proofs.size();
-    const bool batched = NB > 1;
-    struct ProofBufs {
-        uint32_t* d_on;
-        uint8_t* d_pre;
-        uint64_t *d_on64, *d_pre64;
-        uint64_t onw, prew;
-        rv_stream::Kept* kp;
-    };
-    std::vector<ProofBufs> pbs(NB);
-    std::vector<InterpParams> pps(NB);
-    std::vector<Interp64Params> pp64s(NB);
-    CopyBatch cpb(st);
-    for (size_t bi = 0; bi < proofs.size(); bi++) {
-    P = proofs[bi];
-    kp = use_kept ? &P->kept[first_op] : nullptr;
-    const uint8_t* w2 = wit_gf2 ? wit_gf2 + bi * stride2 : nullptr;
-    const uint64_t* w64 = wit_z64 ? wit_z64 + bi * stride64 : nullptr;
-    if ((rc = stream_reserve(P, cc))) return done(rc);
-    uint32_t* d_on = nullptr;
-    uint8_t *d_pre = nullptr, *d_wit = nullptr;
-    uint64_t *d_on64 = nullptr, *d_pre64 = nullptr, *d_wit64 = nullptr, *d_masks64 = nullptr;
-    uint64_t onw = std::max<uint64_t>(cc.on_words64, 1), prew = std::max<uint64_t>(cc.pre_words64, 1);
-    if (kp) {
-        // the chunk's own events sit behind kp->on0 carried ones in the kept buffers and belong behind cs.on0 now
-        d_on = kp->d_on + ((int64_t)kp->on0 - (int64_t)cs.on0) * (int64_t)NQ;
-        d_pre = kp->d_pre + ((int64_t)kp->pre0 - (int64_t)cs.pre0) * (int64_t)(NQ / 2);
-        if (tr64) {
-            if (!kp->d_on64 || !kp->d_pre64) return done(RV_E_DEVICE);
-            d_on64 = kp->d_on64 + kp->on64_0;  // (pass 2 carries no Z64 words: cs.on_words64_0 = 0)
-            d_pre64 = kp->d_pre64 + kp->pre64_0;
-            onw = kp->onw;
-            prew = kp->prew;
+    int hip_code(hipError_t e, const char* what) { return e == hipSuccess ? RV_OK : hip_fail(e, what, __FILE__, __LINE__); }
+
+    // no wait per chunk (the feed ends with one: stream_feed_settle) unless the phase timers are on or the piece is not in a ring slot
+    int upload() {
+        if (!use_kept) {
+            if (int rc = circuit_upload(ctx, c, !ctx->profiling)) {
+                c = nullptr;  // (circuit_upload destroys the circuit on every failure)
+                return rc;
+            }
         }
-    } else {
+        no_wait = !use_kept && c->upload_pending && !(ver && has64);  // (the verifier's Z64 chunks feed a copy from a local array)
+        t_up = t_alloc = Clock::now();
+        return RV_OK;
+    }
+
+    // the proof's transcript buffers: pass 1's kept ones, new ones to keep for pass 2, or scratch; then the rest of its scratch
+    int proof_buffers(rv_stream* P, ProofBufs& q) {
+        int rc;
+        uint64_t &onw = q.pitch[TR_ON64], &prew = q.pitch[TR_PRE64];
+        onw = std::max<uint64_t>(cc.on_words64, 1), prew = std::max<uint64_t>(cc.pre_words64, 1);
+        if (use_kept) {
+            rv_stream::Kept* kp = q.kp = &P->kept[first_op];
+            // the chunk's own events sit behind kp->on0 carried ones in the kept buffers and belong behind cs.on0 now
+            q.tr[TR_ON] = (uint8_t*)(kp->d_on + ((int64_t)kp->on0 - (int64_t)cs.on0) * (int64_t)NQ);
+            q.tr[TR_PRE] = kp->d_pre + ((int64_t)kp->pre0 - (int64_t)cs.pre0) * (int64_t)(NQ / 2);
+            if (tr64) {
+                if (!kp->d_on64 || !kp->d_pre64) return RV_E_DEVICE;
+                q.tr[TR_ON64] = (uint8_t*)(kp->d_on64 + kp->on64_0);  // (pass 2 carries no Z64 words: cs.on_words64_0 = 0)
+                q.tr[TR_PRE64] = (uint8_t*)(kp->d_pre64 + kp->pre64_0);
+                onw = kp->onw;
+                prew = kp->prew;
+            }
+            return RV_OK;
+        }
         // pass 1 keeps the transcripts for pass 2 while they fit the budget
         constexpr uint64_t HEAD_ON = 16, HEAD_PRE = 8;
         const uint64_t keep_need = (on_rows + HEAD_ON) * NQ * 4 + (pre_rows + HEAD_PRE) * (NQ / 2) + (tr64 ? (onw + prew) * R * 8 : 0);
@@ -750,228 +822,203 @@ static int stream_chunk_run(rv_stream* S, const std::vector<rv_stream*>& proofs,
             } else {
                 k.d_on = (uint32_t*)k.on_base + HEAD_ON * NQ;
                 k.d_pre = (uint8_t*)k.pre_base + HEAD_PRE * (NQ / 2);
-                d_on = k.d_on, d_pre = k.d_pre, d_on64 = k.d_on64, d_pre64 = k.d_pre64;
+                q.tr[TR_ON] = (uint8_t*)k.d_on, q.tr[TR_PRE] = k.d_pre, q.tr[TR_ON64] = (uint8_t*)k.d_on64, q.tr[TR_PRE64] = (uint8_t*)k.d_pre64;
                 P->kept_bytes += keep_need;
                 P->kept_peak = std::max(P->kept_peak, P->kept_bytes);
                 P->kept[first_op] = k;
             }
         }
-        if (!d_on) {
-            if ((rc = take(on_rows * NQ * 4, (void**)&d_on)) || (rc = take(pre_rows * (NQ / 2), (void**)&d_pre))) return done(rc);
-            if (tr64 && ((rc = take(onw * R * 8, (void**)&d_on64)) || (rc = take(prew * R * 8, (void**)&d_pre64)))) return done(rc);
+        if (!q.tr[TR_ON]) {
+            if ((rc = take(on_rows * NQ * 4, &q.tr[TR_ON])) || (rc = take(pre_rows * (NQ / 2), &q.tr[TR_PRE]))) return rc;
+            if (tr64 && ((rc = take(onw * R * 8, &q.tr[TR_ON64])) || (rc = take(prew * R * 8, &q.tr[TR_PRE64])))) return rc;
         }
-        if ((rc = take(std::max<size_t>(cc.n_in, 1), (void**)&d_wit))) return done(rc);
-        if (tr64 && ((rc = take(std::max<size_t>(cc.n_in64, 1) * 8, (void**)&d_wit64)) || (rc = take(std::max<uint64_t>(n_blocks64, 1) * 2 * R * 64, (void**)&d_masks64))))
-            return done(rc);
+        if ((rc = take(std::max<size_t>(cc.n_in, 1), &q.d_wit))) return rc;
+        if (tr64 && ((rc = take(std::max<size_t>(cc.n_in64, 1) * 8, &q.d_wit64)) || (rc = take(std::max<uint64_t>(n_blocks64, 1) * 2 * R * 64, &q.d_masks64)))) return rc;
+        return RV_OK;
     }
-    {
-        const uint64_t ws = cc.n_rows * (uint64_t)(NQ * 4 + NQ / 2) + on_rows * NQ * 4 + pre_rows * (NQ / 2) + cc.gates.size() * sizeof(Gate) +
-                            (has64 ? (onw + prew) * R * 8 + n_blocks64 * 2 * R * 64 + cc.n_ssa64 * (uint64_t)R * 72 : 0);
-        P->peak_bytes = std::max(P->peak_bytes, ws);
+
+    // carried events in front of the chunk's own: the unhashed tails (pass 1, verifier) or the pending rows (pass 2)
+    void carry_in(rv_stream* P, const ProofBufs& q) {
+        if (hashing) {
+            for (int kind : {TR_ON, TR_PRE, TR_ON64, TR_PRE64})
+                if (q.tr[kind]) TR_KIND[kind].copy(cp, q.tr[kind], q.pitch[kind], P->tr[kind].d_tail, TR_KIND[kind].unit, P->tr[kind].tail);
+        } else {
+            CopySegs segs{};
+            if (P->pend_rec) segs.add(P->d_pend_rec, q.on(), P->pend_rec * NQ * 4);
+            if (P->pend_in) segs.add(P->d_pend_in, q.on() + (size_t)P->pend_rec * NQ, P->pend_in * NQ * 4);
+            if (P->pend_pre) segs.add(P->d_pend_pre, q.pre(), P->pend_pre * (NQ / 2));
+            cp.add(segs);
+        }
     }
-    // carried events in front of the chunk's own
-    if (hashing && batched) {
-        cpb.add(d_on, P->d_on_tail, P->on_tail * NQ * 4);
-        cpb.add(d_pre, P->d_pre_tail, P->pre_tail * (NQ / 2));
-        if (d_on64) cpb.add(d_on64, onw * 8, P->d_on64_tail, 128 * 8, P->on64_tail * 8, R);
-        if (d_pre64) cpb.add(d_pre64, prew * 8, P->d_pre64_tail, 128 * 8, P->pre64_tail * 8, R);
-    } else if (hashing) {
-        if (P->on_tail) SCHK(hipMemcpyAsync(d_on, P->d_on_tail, P->on_tail * NQ * 4, hipMemcpyDeviceToDevice, st));
-        if (P->pre_tail) SCHK(hipMemcpyAsync(d_pre, P->d_pre_tail, P->pre_tail * (NQ / 2), hipMemcpyDeviceToDevice, st));
-        if (P->on64_tail && d_on64)
-            SCHK(hipMemcpy2DAsync(d_on64, onw * 8, P->d_on64_tail, 128 * 8, P->on64_tail * 8, R, hipMemcpyDeviceToDevice, st));
-        if (P->pre64_tail && d_pre64)
-            SCHK(hipMemcpy2DAsync(d_pre64, prew * 8, P->d_pre64_tail, 128 * 8, P->pre64_tail * 8, R, hipMemcpyDeviceToDevice, st));
-    } else {
-        CopySegs cs_{};
-        if (P->pend_rec) cs_.add(P->d_pend_rec, d_on, P->pend_rec * NQ * 4);
-        if (P->pend_in) cs_.add(P->d_pend_in, d_on + (size_t)P->pend_rec * NQ, P->pend_in * NQ * 4);
-        if (P->pend_pre) cs_.add(P->d_pend_pre, d_pre, P->pend_pre * (NQ / 2));
-        if (batched)
-            cpb.add(cs_);
-        else
-            launch_copy_segs(st, cs_);
-    }
-    if (cc.n_in && !ver && !kp) SCHK(hipMemcpyAsync(d_wit, w2, cc.n_in, hipMemcpyHostToDevice, st));
-    if (cc.n_in64 && !ver && !kp) SCHK(hipMemcpyAsync(d_wit64, w64, cc.n_in64 * 8, hipMemcpyHostToDevice, st));
-    // ---- verifier: the values the proof supplies for this chunk's items (verifier/online.rs:122-183), rebuilt from the
-    // vectors' items [items so far, + this chunk's) -- at any bit offset
-    uint32_t *d_sup_in = nullptr, *d_sup_corr = nullptr, *d_sup_rec = nullptr;
-    uint64_t *d_sup_in64 = nullptr, *d_sup_corr64 = nullptr, *d_sup_rec64 = nullptr;
-    std::vector<uint64_t>& src64c = P->src64c;  // (feeds an asynchronous copy: the chunk's final synchronisation comes before it is written again)
-    if (ver) {
+
+    // verifier: the values the proof supplies for this chunk's items (verifier/online.rs:122-183), rebuilt from the vectors' items
+    // [items so far, + this chunk's) -- at any bit offset
+    int supplied_values(rv_stream* P, ProofBufs& q) {
+        int rc;
         const uint32_t SNQ = P->sup_nq;
-        if ((rc = take(std::max<uint64_t>(cc.n_in, 1) * SNQ * 4, (void**)&d_sup_in)) || (rc = take(std::max<uint64_t>(cc.n_pre, 1) * SNQ * 4, (void**)&d_sup_corr)) ||
-            (rc = take(std::max<uint64_t>(cc.n_rec, 1) * SNQ * 4, (void**)&d_sup_rec)))
-            return done(rc);
+        if ((rc = take(std::max<uint64_t>(cc.n_in, 1) * SNQ * 4, &q.d_sup_in)) || (rc = take(std::max<uint64_t>(cc.n_pre, 1) * SNQ * 4, &q.d_sup_corr)) ||
+            (rc = take(std::max<uint64_t>(cc.n_rec, 1) * SNQ * 4, &q.d_sup_rec)))
+            return rc;
         // (corrections are addressed by their transcript row: the chunk's own start behind the cs.pre0 carried rows)
-        launch_unpack_bits(st, P->d_vproof, P->d_src + 4 * R, P->d_src + 5 * R, P->d_omit_v, cc.n_in, NQ, 1, d_sup_in, SNQ, P->run.n_in);
-        launch_unpack_bits(st, P->d_vproof, P->d_src + 2 * R, P->d_src + 3 * R, P->d_omit_v, cc.n_pre - cs.pre0, NQ, 1, d_sup_corr + (size_t)cs.pre0 * SNQ,
-                           SNQ, P->run.n_pre);
-        launch_unpack_bits(st, P->d_vproof, P->d_src + 0 * R, P->d_src + 1 * R, P->d_omit_v, cc.n_rec, NQ, 0, d_sup_rec, SNQ, P->run.n_rec);
-        if (has64) {
-            uint64_t* d_src64 = nullptr;
-            const uint32_t SR = P->sup_r;
-            if ((rc = take((size_t)6 * R * 8, (void**)&d_src64)) || (rc = take(std::max<uint64_t>(cc.n_in64, 1) * SR * 8, (void**)&d_sup_in64)) ||
-                (rc = take(std::max<uint64_t>(cc.n_corr64, 1) * SR * 8, (void**)&d_sup_corr64)) ||
-                (rc = take(std::max<uint64_t>(cc.n_rec64, 1) * SR * 8, (void**)&d_sup_rec64)))
-                return done(rc);
-            // 8-byte items: the chunk's first item is a byte offset into every vector
-            src64c = P->src64;
-            const uint64_t first[3] = {P->run.n_rec64, P->run.n_corr64, P->run.n_in64};
-            for (int v = 0; v < 3; v++)
-                for (uint32_t r = 0; r < R; r++) {
-                    uint64_t &off = src64c[(size_t)(2 * v) * R + r], &len = src64c[(size_t)(2 * v + 1) * R + r];
-                    const uint64_t skip = std::min(len, 8 * first[v]);
-                    off += skip;
-                    len -= skip;
-                }
-            SCHK(hipMemcpyAsync(d_src64, src64c.data(), src64c.size() * 8, hipMemcpyHostToDevice, st));
-            launch_unpack_supplied64(st, cc, P->d_vproof, d_src64, P->d_omit64_v, R, d_sup_in64, d_sup_corr64, d_sup_rec64, SR);
+        launch_unpack_bits(st, P->d_vproof, P->d_src + 4 * R, P->d_src + 5 * R, P->d_omit_v, cc.n_in, NQ, 1, q.d_sup_in, SNQ, P->run.n_in);
+        launch_unpack_bits(st, P->d_vproof, P->d_src + 2 * R, P->d_src + 3 * R, P->d_omit_v, cc.n_pre - cs.pre0, NQ, 1, q.d_sup_corr + (size_t)cs.pre0 * SNQ, SNQ,
+                           P->run.n_pre);
+        launch_unpack_bits(st, P->d_vproof, P->d_src + 0 * R, P->d_src + 1 * R, P->d_omit_v, cc.n_rec, NQ, 0, q.d_sup_rec, SNQ, P->run.n_rec);
+        if (!has64) return RV_OK;
+        uint64_t* d_src64 = nullptr;
+        const uint32_t SR = P->sup_r;
+        if ((rc = take((size_t)6 * R * 8, &d_src64)) || (rc = take(std::max<uint64_t>(cc.n_in64, 1) * SR * 8, &q.d_sup_in64)) ||
+            (rc = take(std::max<uint64_t>(cc.n_corr64, 1) * SR * 8, &q.d_sup_corr64)) || (rc = take(std::max<uint64_t>(cc.n_rec64, 1) * SR * 8, &q.d_sup_rec64)))
+            return rc;
+        // 8-byte items: the chunk's first item is a byte offset into every vector
+        std::vector<uint64_t>& src64c = P->src64c;  // (feeds an asynchronous copy: the chunk's final synchronisation comes before it is written again)
+        src64c = P->src64;
+        const uint64_t first[3] = {P->run.n_rec64, P->run.n_corr64, P->run.n_in64};
+        for (int v = 0; v < 3; v++)
+            for (uint32_t r = 0; r < R; r++) {
+                uint64_t &off = src64c[(size_t)(2 * v) * R + r], &len = src64c[(size_t)(2 * v + 1) * R + r];
+                const uint64_t skip = std::min(len, 8 * first[v]);
+                off += skip;
+                len -= skip;
+            }
+        if ((rc = hip_code(hipMemcpyAsync(d_src64, src64c.data(), src64c.size() * 8, hipMemcpyHostToDevice, st), "supplied Z64 offsets"))) return rc;
+        launch_unpack_supplied64(st, cc, P->d_vproof, d_src64, P->d_omit64_v, R, q.d_sup_in64, q.d_sup_corr64, q.d_sup_rec64, SR);
+        return RV_OK;
+    }
+
+    void fill_params(rv_stream* P, const ProofBufs& q, InterpParams& p, Interp64Params& p64) {
+        p.NQ = NQ;
+        p.rows = P->d_rows;
+        p.corr = P->d_corr;
+        p.on = q.on();
+        p.pre = q.pre();
+        p.wit = q.d_wit;
+        p.err = P->d_err;
+        p64.R = R;
+        p64.wmask = P->d_wmask64;
+        p64.wcorr = P->d_wcorr64;
+        p64.masks = q.d_masks64;
+        p64.on = q.on64();
+        p64.pre = q.pre64();
+        p64.on_words = q.pitch[TR_ON64];
+        p64.pre_words = q.pitch[TR_PRE64];
+        p64.wit = q.d_wit64;
+        p64.corr2 = P->d_corr;
+        p64.masks2 = P->d_rows;
+        p64.NQ = NQ;
+        p64.err = P->d_err;
+        if (ver) {
+            p.on_mask = P->d_onm;
+            p.sup_in = q.d_sup_in;
+            p.sup_corr = q.d_sup_corr;
+            p.sup_rec = q.d_sup_rec;
+            p.sup_nq = P->sup_nq;
+            p64.omit = P->d_omit64_v;
+            p64.sup_in = q.d_sup_in64;
+            p64.sup_corr = q.d_sup_corr64;
+            p64.sup_rec = q.d_sup_rec64;
+            p64.sup_r = P->sup_r;
         }
     }
-    // ---- masks of this chunk: CTR blocks [first_block, first_block + n_blocks) (the first one may be shared with the
-    // previous chunk: its leading masks were consumed there and are simply regenerated)
-    if (bi == 0) t_alloc = now();
-    ctx->phase(RV_PH_MASKS);
-    // (verifier: the omitted player of every opened repetition is skipped, generator/batch.rs:32-34; the Z64 transcript of a
-    // repetition has its own keys, online.rs:101-113)
-    if (!kp) {
-        launch_aes_gf2_masks(st, P->d_rk, ver ? P->d_keep : nullptr, NQ, first_block, n_blocks, P->d_rows + (size_t)cc.row_prg_base * NQ);
-        if (n_blocks64 && d_masks64) launch_aes_z64_masks(st, ver ? P->d_rk64 : P->d_rk, ver ? P->d_keep64 : nullptr, NQ, n_blocks64, d_masks64, first_block64);
-        ctx->count(2);
-    }
-    ctx->phase(-1);
-    // ---- interpreter
-    InterpParams p{};
-    Interp64Params p64{};
-    p.NQ = NQ;
-    p.rows = P->d_rows;
-    p.corr = P->d_corr;
-    p.on = d_on;
-    p.pre = d_pre;
-    p.wit = d_wit;
-    p.err = P->d_err;
-    p64.R = R;
-    p64.wmask = P->d_wmask64;
-    p64.wcorr = P->d_wcorr64;
-    p64.masks = d_masks64;
-    p64.on = d_on64;
-    p64.pre = d_pre64;
-    p64.on_words = onw;
-    p64.pre_words = prew;
-    p64.wit = d_wit64;
-    p64.corr2 = P->d_corr;
-    p64.masks2 = P->d_rows;
-    p64.NQ = NQ;
-    p64.err = P->d_err;
-    if (ver) {
-        p.on_mask = P->d_onm;
-        p.sup_in = d_sup_in;
-        p.sup_corr = d_sup_corr;
-        p.sup_rec = d_sup_rec;
-        p.sup_nq = P->sup_nq;
-        p64.omit = P->d_omit64_v;
-        p64.sup_in = d_sup_in64;
-        p64.sup_corr = d_sup_corr64;
-        p64.sup_rec = d_sup_rec64;
-        p64.sup_r = P->sup_r;
-    }
-    if (!kp) launch_shard_init(st, P->d_err0, P->d_rows + (size_t)cc.zero_row * NQ, NQ, P->d_corr + (size_t)cc.zero_row * (NQ / 2), NQ / 2);
-    if (!kp && !batched) {
+
+    // one proof's share of the chunk up to its levels (a batch runs the levels of all proofs afterwards)
+    int issue_proof(size_t bi) {
+        rv_stream* P = proofs[bi];
+        ProofBufs& q = pbs[bi];
+        int rc;
+        if ((rc = stream_reserve(P, cc)) || (rc = proof_buffers(P, q))) return rc;
+        const uint64_t ws = cc.n_rows * (uint64_t)(NQ * 4 + NQ / 2) + on_rows * NQ * 4 + pre_rows * (NQ / 2) + cc.gates.size() * sizeof(Gate) +
+                            (has64 ? (q.pitch[TR_ON64] + q.pitch[TR_PRE64]) * R * 8 + n_blocks64 * 2 * R * 64 + cc.n_ssa64 * (uint64_t)R * 72 : 0);
+        P->peak_bytes = std::max(P->peak_bytes, ws);
+        carry_in(P, q);
+        if (!ver && !q.kp) {
+            if (cc.n_in && (rc = hip_code(hipMemcpyAsync(q.d_wit, wit.gf2_of(bi), cc.n_in, hipMemcpyHostToDevice, st), "GF(2) witness"))) return rc;
+            if (cc.n_in64 && (rc = hip_code(hipMemcpyAsync(q.d_wit64, wit.z64_of(bi), cc.n_in64 * 8, hipMemcpyHostToDevice, st), "Z64 witness"))) return rc;
+        }
+        if (ver && (rc = supplied_values(P, q))) return rc;
+        if (bi == 0) t_alloc = Clock::now();
+        // masks of this chunk: CTR blocks [first_block, first_block + n_blocks) (the first one may be shared with the previous chunk: its
+        // leading masks were consumed there and are simply regenerated).  (verifier: the omitted player of every opened repetition is
+        // skipped, generator/batch.rs:32-34; the Z64 transcript of a repetition has its own keys, online.rs:101-113)
+        ctx->phase(RV_PH_MASKS);
+        if (!q.kp) {
+            launch_aes_gf2_masks(st, P->d_rk, ver ? P->d_keep : nullptr, NQ, first_block, n_blocks, P->d_rows + (size_t)cc.row_prg_base * NQ);
+            if (n_blocks64 && q.d_masks64)
+                launch_aes_z64_masks(st, ver ? P->d_rk64 : P->d_rk, ver ? P->d_keep64 : nullptr, NQ, n_blocks64, q.d_masks64, first_block64);
+            ctx->count(2);
+        }
+        ctx->phase(-1);
+        fill_params(P, q, pps[bi], pp64s[bi]);
+        if (q.kp) return RV_OK;
+        launch_shard_init(st, P->d_err0, P->d_rows + (size_t)cc.zero_row * NQ, NQ, P->d_corr + (size_t)cc.zero_row * (NQ / 2), NQ / 2);
+        if (batched) return RV_OK;
         rv_shard sh;  // the level loop only needs the circuit and the context
         sh.ctx = ctx;
         sh.c = c;
         sh.R = R;
         sh.NQ = NQ;
-        rc = shard_run_levels(&sh, ver ? MODE_VERIFY : MODE_PROVE, p, p64);
+        rc = shard_run_levels(&sh, ver ? MODE_VERIFY : MODE_PROVE, pps[bi], pp64s[bi]);
         ctx->phase(-1);
-        if (rc) return done(rc);
+        return rc;
     }
-    pbs[bi] = ProofBufs{d_on, d_pre, d_on64, d_pre64, onw, prew, kp};
-    pps[bi] = p;
-    pp64s[bi] = p64;
-    }
-    cpb.flush();  // (the carried events are in place before any level runs)
-    if (batched && !use_kept) {
-        // the proofs' parameter blocks go to the device in one copy out of a page-locked slot
+
+    // a batch: the proofs' parameter blocks go to the device in one copy out of a page-locked slot, then one level loop over them
+    int run_levels_batched() {
+        const size_t NB = proofs.size();
         const size_t o64 = (NB * sizeof(InterpParams) + 63) & ~(size_t)63, bytes = o64 + NB * sizeof(Interp64Params);
-        int slot = 0;
+        int slot = 0, rc;
         uint8_t* hp = ctx->open_slot(bytes, &slot);
-        if (!hp) return done(RV_E_NOMEM);
+        if (!hp) return RV_E_NOMEM;
         memcpy(hp, pps.data(), NB * sizeof(InterpParams));
         memcpy(hp + o64, pp64s.data(), NB * sizeof(Interp64Params));
         uint8_t* dp = nullptr;
-        if ((rc = take(bytes, (void**)&dp))) return done(rc);
-        SCHK(hipMemcpyAsync(dp, hp, bytes, hipMemcpyHostToDevice, st));
-        SCHK(hipEventRecord(ctx->ev_open[slot], st));
+        if ((rc = take(bytes, &dp))) return rc;
+        if ((rc = hip_code(hipMemcpyAsync(dp, hp, bytes, hipMemcpyHostToDevice, st), "parameter blocks")) ||
+            (rc = hip_code(hipEventRecord(ctx->ev_open[slot], st), "parameter blocks")))
+            return rc;
         ctx->phase(RV_PH_INTERP);
         launch_levels_batched(ctx, c, ver ? MODE_VERIFY : MODE_PROVE, (const InterpParams*)dp, has64 ? (const Interp64Params*)(dp + o64) : nullptr, NB);
         ctx->phase(-1);
-        if (hipGetLastError() != hipSuccess) return done(RV_E_DEVICE);
+        return hipGetLastError() != hipSuccess ? RV_E_DEVICE : RV_OK;
     }
-    if (hashing) {
-        // ---- chunk chaining values of everything but the stream's last (possibly incomplete) chunk, into the trees: per kind of
-        // transcript the chunk hashes of every proof, then their trees (together when batched), then their tails
+
+    // chunk chaining values of everything but the stream's last (possibly incomplete) chunk, into the trees: per kind of transcript
+    // the chunk hashes of every proof, then their trees (together when batched), then their tails
+    int hash_transcripts() {
+        int rc;
         ctx->phase(RV_PH_HASH);
-        for (int kind = 0; kind < 4; kind++) {
-            const uint64_t total = kind == 0 ? cc.n_pre : kind == 1 ? cc.n_on : kind == 2 ? cc.pre_words64 : cc.on_words64;
-            const uint64_t unit = kind < 2 ? 1024 : 128;
-            const uint64_t n_chunks = total ? (total - 1) / unit : 0;  // at least one event stays behind
-            const uint64_t hashed = n_chunks * unit, tail = total - hashed;
+        const uint64_t totals[TR_KINDS] = {cc.n_pre, cc.n_on, cc.pre_words64, cc.on_words64};
+        for (int kind = 0; kind < TR_KINDS; kind++) {
+            const TranscriptKind& K = TR_KIND[kind];
+            const uint64_t tail = K.tail_of(totals[kind]), hashed = totals[kind] - tail, n_chunks = hashed / K.unit;
             std::vector<IncHash*> Hs;
             std::vector<uint32_t*> cvsv;
-            for (size_t bi = 0; bi < NB; bi++) {
-                P = proofs[bi];
+            for (size_t bi = 0; bi < proofs.size(); bi++) {
+                rv_stream::Transcript& T = proofs[bi]->tr[kind];
                 const ProofBufs& q = pbs[bi];
-                IncHash* H = kind == 0 ? &P->h_pre : kind == 1 ? &P->h_on : kind == 2 ? &P->h_pre64 : &P->h_on64;
-                uint64_t* tailp = kind == 0 ? &P->pre_tail : kind == 1 ? &P->on_tail : kind == 2 ? &P->pre64_tail : &P->on64_tail;
                 if (n_chunks) {
                     uint32_t* cvs = nullptr;
-                    if ((rc = take((size_t)n_chunks * R * 32, (void**)&cvs))) return done(rc);
-                    switch (kind) {
-                    case 0: launch_b3_stream_bits_chunks(st, q.d_pre, hashed, NQ, cvs, H->chunks, 0); break;
-                    case 1: launch_b3_stream_chunks(st, q.d_on, hashed, NQ, cvs, nullptr, 0, H->chunks, 0); break;
-                    case 2: launch_b3_contig_chunks(st, q.d_pre64, q.prew, hashed, R, cvs, H->chunks, 0); break;
-                    default: launch_b3_contig_chunks(st, q.d_on64, q.onw, hashed, R, cvs, H->chunks, 0); break;
-                    }
-                    Hs.push_back(H);
+                    if ((rc = take((size_t)n_chunks * R * 32, &cvs))) return rc;
+                    K.hash(st, q.tr[kind], q.pitch[kind], hashed, cvs, T.tree.chunks, 0);
+                    Hs.push_back(&T.tree);
                     cvsv.push_back(cvs);
                 }
-                if (tail) {
-                    if (batched) {
-                        switch (kind) {
-                        case 0: cpb.add(P->d_pre_tail, q.d_pre + hashed * (NQ / 2), tail * (NQ / 2)); break;
-                        case 1: cpb.add(P->d_on_tail, q.d_on + hashed * NQ, tail * NQ * 4); break;
-                        case 2: cpb.add(P->d_pre64_tail, 128 * 8, q.d_pre64 + hashed, q.prew * 8, tail * 8, R); break;
-                        default: cpb.add(P->d_on64_tail, 128 * 8, q.d_on64 + hashed, q.onw * 8, tail * 8, R); break;
-                        }
-                    } else {
-                        switch (kind) {
-                        case 0: SCHK(hipMemcpyAsync(P->d_pre_tail, q.d_pre + hashed * (NQ / 2), tail * (NQ / 2), hipMemcpyDeviceToDevice, st)); break;
-                        case 1: SCHK(hipMemcpyAsync(P->d_on_tail, q.d_on + hashed * NQ, tail * NQ * 4, hipMemcpyDeviceToDevice, st)); break;
-                        case 2: SCHK(hipMemcpy2DAsync(P->d_pre64_tail, 128 * 8, q.d_pre64 + hashed, q.prew * 8, tail * 8, R, hipMemcpyDeviceToDevice, st)); break;
-                        default: SCHK(hipMemcpy2DAsync(P->d_on64_tail, 128 * 8, q.d_on64 + hashed, q.onw * 8, tail * 8, R, hipMemcpyDeviceToDevice, st)); break;
-                        }
-                    }
-                }
-                *tailp = tail;
+                K.copy(cp, T.d_tail, K.unit, q.tr[kind] + hashed * K.ev_bytes, q.pitch[kind], tail);
+                T.tail = tail;
             }
-            if (n_chunks && (rc = batched ? inc_absorb_batch(ctx, Hs, cvsv, n_chunks, R) : inc_absorb(ctx, *Hs[0], cvsv[0], n_chunks, R))) return done(rc);
+            if (n_chunks && (rc = inc_absorb(ctx, Hs, cvsv, n_chunks, R))) return rc;
         }
-        cpb.flush();
+        rc = cp.finish("transcript tails");
         ctx->phase(-1);
+        return rc;
     }
-    for (size_t bi = 0; bi < NB && !hashing; bi++) {
-    P = proofs[bi];
-    kp = pbs[bi].kp;
-    uint32_t* d_on = pbs[bi].d_on;
-    uint8_t* d_pre = pbs[bi].d_pre;
-    uint64_t *d_on64 = pbs[bi].d_on64, *d_pre64 = pbs[bi].d_pre64;
-    const uint64_t onw = pbs[bi].onw, prew = pbs[bi].prew;
-    {
-        // ---- openings of the challenged repetitions for this chunk's items.  Eight items make a byte, so a vector's
-        // last (< 8) items wait in d_pend_* for the next chunk; what is extracted is always whole bytes.
+
+    // pass 2: openings of the challenged repetitions for this chunk's items.  Eight items make a byte, so a vector's last (< 8) items
+    // wait in d_pend_* for the next chunk; what is extracted is always whole bytes.
+    int open_proof(size_t bi) {
+        rv_stream* P = proofs[bi];
+        const ProofBufs& q = pbs[bi];
+        int rc;
         ctx->phase(RV_PH_OPEN);
         // the chunk's host-built tables in one page-locked blob: [dst 6R u64 | OnlineList | rec_offs64 | in_offs64 | rec_list | in_list]
         const size_t n_recl = (size_t)P->pend_rec + cc.rec_rows.size(), n_inl = (size_t)P->pend_in + cc.in_rows.size();
@@ -979,7 +1026,7 @@ static int stream_chunk_run(rv_stream* S, const std::vector<rv_stream*>& proofs,
                      o_rl = o_io + cc.in_offs64.size() * 8, o_il = o_rl + n_recl * 4, blob_bytes = o_il + n_inl * 4 + 8;
         int slot = 0;
         uint8_t* hb = ctx->open_slot(blob_bytes, &slot);
-        if (!hb) return done(RV_E_NOMEM);
+        if (!hb) return RV_E_NOMEM;
         uint64_t* dst = (uint64_t*)(hb + o_dst);  // per repetition: where this chunk's bytes of each vector go
         const uint64_t by_rec = (P->run.n_rec - P->pend_rec) / 8, by_in = (P->run.n_in - P->pend_in) / 8, by_pre = (P->run.n_pre - P->pend_pre) / 8;
         for (uint32_t r = 0; r < R; r++) {
@@ -1003,100 +1050,103 @@ static int stream_chunk_run(rv_stream* S, const std::vector<rv_stream*>& proofs,
         if (!cc.in_rows.empty()) memcpy(in_list + P->pend_in, cc.in_rows.data(), cc.in_rows.size() * 4);
         const uint64_t rec_full = n_recl & ~(size_t)7, in_full = n_inl & ~(size_t)7, pre_full = cc.n_pre & ~(uint64_t)7;
         uint8_t* db = nullptr;
-        if ((rc = take(blob_bytes, (void**)&db))) return done(rc);
-        SCHK(hipMemcpyAsync(db, hb, blob_bytes, hipMemcpyHostToDevice, st));
-        SCHK(hipEventRecord(ctx->ev_open[slot], st));
+        if ((rc = take(blob_bytes, &db))) return rc;
+        if ((rc = hip_code(hipMemcpyAsync(db, hb, blob_bytes, hipMemcpyHostToDevice, st), "opening tables")) ||
+            (rc = hip_code(hipEventRecord(ctx->ev_open[slot], st), "opening tables")))
+            return rc;
         uint64_t* d_dst = (uint64_t*)(db + o_dst);
         const uint32_t *d_rec_list = (const uint32_t*)(db + o_rl), *d_in_list = (const uint32_t*)(db + o_il);
-        if (rec_full) launch_extract_bits(st, d_on, d_rec_list, rec_full, NQ, 0, P->d_omit, d_dst + 0 * R, P->d_proof);
-        if (in_full) launch_extract_bits(st, d_on, d_in_list, in_full, NQ, 1, P->d_omit, d_dst + 1 * R, P->d_proof);
-        if (pre_full) launch_extract_from_bits(st, d_pre, pre_full, NQ, (const OnlineList*)(db + o_ol), P->d_proof);
+        if (rec_full) launch_extract_bits(st, q.on(), d_rec_list, rec_full, NQ, 0, P->d_omit, d_dst + 0 * R, P->d_proof);
+        if (in_full) launch_extract_bits(st, q.on(), d_in_list, in_full, NQ, 1, P->d_omit, d_dst + 1 * R, P->d_proof);
+        if (pre_full) launch_extract_from_bits(st, q.pre(), pre_full, NQ, (const OnlineList*)(db + o_ol), P->d_proof);
         if (has64) {
-            launch_extract64(st, d_on64, onw, (const uint64_t*)(db + o_ro), cc.n_rec64, 1, R, P->d_omit, d_dst + 2 * R, P->d_proof);
-            launch_extract64(st, d_pre64, prew, nullptr, cc.n_corr64, 0, R, P->d_omit, d_dst + 3 * R, P->d_proof);
-            launch_extract64(st, d_on64, onw, (const uint64_t*)(db + o_io), cc.n_in64, 0, R, P->d_omit, d_dst + 4 * R, P->d_proof);
+            launch_extract64(st, q.on64(), q.pitch[TR_ON64], (const uint64_t*)(db + o_ro), cc.n_rec64, 1, R, P->d_omit, d_dst + 2 * R, P->d_proof);
+            launch_extract64(st, q.pre64(), q.pitch[TR_PRE64], nullptr, cc.n_corr64, 0, R, P->d_omit, d_dst + 3 * R, P->d_proof);
+            launch_extract64(st, q.on64(), q.pitch[TR_ON64], (const uint64_t*)(db + o_io), cc.n_in64, 0, R, P->d_omit, d_dst + 4 * R, P->d_proof);
         }
         // the items that do not fill a byte yet: their rows move to the pending buffers (one launch; the chunk's buffer and the
         // pending buffers are different allocations)
         const uint32_t nr = (uint32_t)(n_recl - rec_full), ni = (uint32_t)(n_inl - in_full), np = (uint32_t)(cc.n_pre - pre_full);
-        {
-            CopySegs cs_{};
-            for (uint32_t i = 0; i < nr; i++) cs_.add(d_on + (size_t)rec_list[rec_full + i] * NQ, P->d_pend_rec + (size_t)i * NQ, NQ * 4);
-            for (uint32_t i = 0; i < ni; i++) cs_.add(d_on + (size_t)in_list[in_full + i] * NQ, P->d_pend_in + (size_t)i * NQ, NQ * 4);
-            if (np) cs_.add(d_pre + pre_full * (NQ / 2), P->d_pend_pre, np * (NQ / 2));
-            if (batched)
-                cpb.add(cs_);
-            else
-                launch_copy_segs(st, cs_);
-        }
+        CopySegs segs{};
+        for (uint32_t i = 0; i < nr; i++) segs.add(q.on() + (size_t)rec_list[rec_full + i] * NQ, P->d_pend_rec + (size_t)i * NQ, NQ * 4);
+        for (uint32_t i = 0; i < ni; i++) segs.add(q.on() + (size_t)in_list[in_full + i] * NQ, P->d_pend_in + (size_t)i * NQ, NQ * 4);
+        if (np) segs.add(q.pre() + pre_full * (NQ / 2), P->d_pend_pre, np * (NQ / 2));
+        cp.add(segs);
         P->pend_rec = nr;
         P->pend_in = ni;
         P->pend_pre = np;
         ctx->phase(-1);
+        return RV_OK;
     }
-    }
-    cpb.flush();
-    kp = nullptr;
+
     // the kept transcripts stay a chunk for every proof or for none
-    if (p1 && S->same_cuts) {
+    void keep_for_all_or_none() {
+        if (!p1 || !S->same_cuts) return;
         size_t n_kept = 0;
         for (rv_stream* Q : proofs) n_kept += Q->kept.count(first_op);
         if (n_kept && n_kept != proofs.size()) drop_all_kept();
     }
-    const auto t_issue = now();
-    if (no_wait) {
-        S->unsettled = true;
-    } else if (hashing || !use_kept) {  // (a chunk that ran: its error flags.  A kept chunk ran nothing -- and nothing on the host waits for its openings)
-        if ((rc = stream_read_errs(proofs, "stream chunk"))) return done(rc);
+
+    // a chunk that ran leaves its error flags: read behind it now, or by the feed's one wait.  (A kept chunk ran nothing -- and
+    // nothing on the host waits for its openings)
+    int settle() {
+        int rc = RV_OK;
+        if (no_wait)
+            S->unsettled = true;
+        else if (hashing || !use_kept)
+            rc = stream_read_errs(proofs, "stream chunk");
+        if (!rc) ctx->collect();
+        t_gpu = Clock::now();
+        return rc;
     }
-    ctx->collect();
-    const auto t_gpu = now();
-    // ---- counters (the same for every proof but the witness digest)
-    if (!ver)
-        for (size_t bi = 0; bi < proofs.size(); bi++) {  // (before the ordinals advance)
+
+    // the counters: the same for every proof but the witness digest
+    void count() {
+        if (!ver)
+            for (size_t bi = 0; bi < proofs.size(); bi++) {  // (before the ordinals advance)
+                rv_stream* Q = proofs[bi];
+                Q->run.wit_hash += wit_digest(wit.gf2_of(bi), cc.n_in, Q->run.n_in, wit.z64_of(bi), cc.n_in64, Q->run.n_in64);
+            }
+        StreamTotals& t = S->run;
+        t.n_ops += n_ops;
+        t.ops_hash += digest;
+        t.masks += cc.n_masks - cs.mask_phase;
+        t.masks64 += cc.n_masks64 - cs.mask64_phase;
+        // own events of this chunk (the compiled counters include the carried ones in front)
+        t.n_on += cc.n_on - cs.on0;
+        t.n_pre += cc.n_pre - cs.pre0;
+        t.n_rec += cc.n_rec;
+        t.n_in += cc.n_in;
+        t.on_words64 += cc.on_words64 - cs.on_words64_0;
+        t.pre_words64 += cc.pre_words64 - cs.pre_words64_0;
+        t.n_rec64 += cc.n_rec64;
+        t.n_corr64 += cc.n_corr64;
+        t.n_in64 += cc.n_in64;
+        t.levels += cc.info.levels;
+        t.chunks++;
+        for (size_t bi = 1; bi < proofs.size(); bi++) {
             rv_stream* Q = proofs[bi];
-            Q->run.wit_hash += wit_digest(wit_gf2 ? wit_gf2 + bi * stride2 : nullptr, cc.n_in, Q->run.n_in, wit_z64 ? wit_z64 + bi * stride64 : nullptr, cc.n_in64,
-                                          Q->run.n_in64);
+            const uint64_t wh = Q->run.wit_hash;
+            Q->run = S->run;
+            Q->run.wit_hash = wh;
         }
-    S->run.n_ops += n_ops;
-    S->run.ops_hash += digest;
-    if (stats) {
+        used_gf2 = ver ? 0 : cc.n_in;  // (the verifier has no witness to advance in)
+        used_z64 = ver ? 0 : cc.n_in64;
+        lap_stats();
+    }
+
+    void lap_stats() {  // RV_STREAM_STATS: where the main thread's time goes, every 10 chunks
+        static const bool stats = getenv("RV_STREAM_STATS") != nullptr;
+        if (!stats) return;
         static double acc[6] = {0, 0, 0, 0, 0, 0};
         static int n_acc = 0;
-        acc[0] += secs(t_begin, t_reloc);
-        acc[1] += secs(t_reloc, t_up);
-        acc[2] += secs(t_up, t_alloc);
-        acc[3] += secs(t_alloc, t_issue);
-        acc[4] += secs(t_issue, t_gpu);
-        acc[5] += secs(t_gpu, now());
+        const Clock::time_point t[7] = {t_begin, t_reloc, t_up, t_alloc, t_issue, t_gpu, Clock::now()};
+        for (int k = 0; k < 6; k++) acc[k] += std::chrono::duration<double>(t[k + 1] - t[k]).count();
         if (++n_acc % 10 == 0)
             fprintf(stderr, "[rv stream] %d chunks: relocate %.3f s, upload / plan %.3f s, buffers %.3f s, issue %.3f s, final sync %.3f s, counters %.3f s\n",
                     n_acc, acc[0], acc[1], acc[2], acc[3], acc[4], acc[5]);
     }
-    S->run.masks += cc.n_masks - cs.mask_phase;
-    S->run.masks64 += cc.n_masks64 - cs.mask64_phase;
-    S->run.n_on += new_on;
-    S->run.n_pre += new_pre;
-    S->run.n_rec += cc.n_rec;
-    S->run.n_in += cc.n_in;
-    S->run.on_words64 += new_on64;
-    S->run.pre_words64 += new_pre64;
-    S->run.n_rec64 += cc.n_rec64;
-    S->run.n_corr64 += cc.n_corr64;
-    S->run.n_in64 += cc.n_in64;
-    S->run.levels += cc.info.levels;
-    S->run.chunks++;
-    for (size_t bi = 1; bi < proofs.size(); bi++) {
-        rv_stream* Q = proofs[bi];
-        const uint64_t wh = Q->run.wit_hash;
-        Q->run = S->run;
-        Q->run.wit_hash = wh;
-    }
-    if (used_gf2) *used_gf2 = ver ? 0 : cc.n_in;  // (the verifier has no witness to advance in)
-    if (used_z64) *used_z64 = ver ? 0 : cc.n_in64;
-    return done(RV_OK);
-}
-#undef SCHK
+};
 
 // pass 2: the chunk pass 1 compiled for the same ops (same first op, same length), if it was kept
 static rv_circuit* stream_take_cached(rv_stream* S, uint64_t first_op, size_t n_ops, ChunkStart* carried, uint64_t* digest) {
@@ -1111,25 +1161,6 @@ static rv_circuit* stream_take_cached(rv_stream* S, uint64_t first_op, size_t n_
     S->cache_bytes -= std::min(S->cache_bytes, rv_stream::compiled_bytes(c->cc));
     S->cache.erase(it);
     return c;
-}
-
-static int stream_chunk(rv_stream* S, const std::vector<rv_stream*>& proofs, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2,
-                        size_t stride2, const uint64_t* wit_z64, size_t n_z64, size_t stride64, size_t* used_gf2, size_t* used_z64) {
-    ChunkStart carried;
-    uint64_t digest = 0;
-    rv_circuit* c = stream_take_cached(S, S->run.n_ops, n_ops, &carried, &digest);
-    if (c && ops_digest(ops, n_ops, S->run.n_ops) != digest) {
-        // same position and length, other ops: pass 1's compile is not this chunk's (the totals will differ at finish: RV_E_ARG)
-        rv_circuit_destroy(c);
-        c = nullptr;
-        carried = ChunkStart();
-    }
-    if (!c) {
-        const int rc = stream_compile_piece(S, ops, n_ops, (uint32_t)(S->run.masks % 128), (uint32_t)(S->run.masks64 % 2), &c);
-        if (rc) return rc;
-        digest = ops_digest(ops, n_ops, S->run.n_ops);
-    }
-    return stream_chunk_run(S, proofs, c, digest, n_ops, wit_gf2, n_gf2, stride2, wit_z64, n_z64, stride64, used_gf2, used_z64, carried);
 }
 
 // worker threads of a feed (RV_STREAM_THREADS; default: the host's cores, at most 6 -- measured on the 10^7-gate circuit:
@@ -1159,7 +1190,157 @@ static std::vector<size_t> stream_cuts(size_t n_ops, size_t full) {
     return cut;
 }
 
-// H: the caller's handle -- a single stream, or a batch whose members are fed witness b at wit_gf2 + b * n_gf2, wit_z64 + b * n_z64
+// one piece of a feed on its way from the op array to the GPU
+struct FeedPiece {
+    size_t at = 0, n = 0;       // ops [at, at + n) of the feed
+    bool predicted = false;     // ph2 / ph64 / want follow from counts over the pieces before it (else: from the stream when it is prepared)
+    uint32_t ph2 = 0, ph64 = 0;
+    ChunkStart want;            // the offsets the piece is expected to run at
+    rv_circuit* c = nullptr;    // pass 1's compile out of the cache (checked against the ops fed now), then the piece as it will run
+    uint64_t digest = 0;
+    ChunkStart carried;         // the offsets c's arrays hold
+    bool kept = false;          // pass 2: pass 1 kept this piece's transcripts (rv_stream::Kept) -- nothing of it is uploaded
+};
+
+// A piece ready to run: pass 1's cached compile if its digest matches the ops fed now, else a fresh compile -- at the offsets the piece
+// is expected to run at where they were predicted (no relocation pass afterwards; ChunkRun moves it by the difference, which is zero
+// unless the prediction is off).  Runs on a worker thread, or inline right before the piece runs.
+static int prepare_piece(const rv_stream* S, const rv_op* ops, uint64_t first_op, FeedPiece& p) {
+    if (!p.predicted) p.ph2 = (uint32_t)(S->run.masks % 128), p.ph64 = (uint32_t)(S->run.masks64 % 2);
+    const uint64_t dg = ops_digest(ops + p.at, p.n, first_op + p.at);
+    if (p.c && dg != p.digest) {  // same position and length, other ops: pass 1's compile is not this piece's (finish reports RV_E_ARG)
+        rv_circuit_destroy(p.c);
+        p.c = nullptr;
+    }
+    p.digest = dg;
+    if (!p.c) {
+        p.carried = p.predicted ? p.want : ChunkStart();
+        if (int rc = stream_compile_piece(S, ops + p.at, p.n, p.ph2, p.ph64, &p.c, p.predicted ? &p.want : nullptr)) return rc;
+    }
+    if (p.predicted) {
+        relocate_to(p.c->cc, p.carried, p.want);
+        set_carried(p.carried, p.want.pre0, p.want.on0, p.want.pre_words64_0, p.want.on_words64_0);
+    }
+    return RV_OK;
+}
+
+// The ring of page-locked slots (rv_ctx::h_ring): piece s goes into slot s % NS once piece s - NS has run -- a copy of ~13 MB per
+// piece that used to sit on the main thread between two pieces' GPU work (1.2 of its ~2.2 ms per piece).  Returns NS (0: no ring).
+static size_t feed_ring(rv_stream* S) {
+    constexpr size_t NS_WANT = 6;
+    rv_ctx* ctx = S->ctx;
+    // a piece's arrays: its ops' gates and ordinal tables, PLUS the extra level that writes every wire it wrote back to the wire
+    // store (up to one more gate per wire index: for the 10^7-gate circuit with recycled indices 2 x 10^5 gates = 9.6 MB beside the
+    // 12 MB of a 2^18-op piece; sized without them, the slots were too small for every full-size piece and the main thread went
+    // on copying: 0.16 -> 0.11 s per proof once a larger feed had grown the ring)
+    const size_t wb2 = std::min<size_t>(S->gf2_wires, S->max_chunk_ops), wb64 = std::min<size_t>(S->z64_wires, S->max_chunk_ops);
+    const size_t want_cap = ((S->max_chunk_ops * (sizeof(Gate) + 8) + wb2 * sizeof(Gate) + wb64 * sizeof(Gate64) + ((size_t)2 << 20)) + 0xFFFFF) & ~(size_t)0xFFFFF;
+    if (want_cap > ((size_t)80 << 20)) return 0;
+    if (ctx->h_ring_cap < want_cap || ctx->h_ring.size() < NS_WANT) {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (uint8_t* p : ctx->h_ring) (void)hipHostFree(p);
+        ctx->h_ring.clear();
+        ctx->h_ring_cap = 0;
+        for (hipEvent_t e : ctx->ring_ev)
+            if (e) (void)hipEventDestroy(e);
+        ctx->ring_ev.clear();
+        for (size_t k = 0; k < NS_WANT; k++) {
+            uint8_t* p = nullptr;
+            if (hipHostMalloc((void**)&p, want_cap, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError();
+                break;
+            }
+            ctx->h_ring.push_back(p);
+        }
+        ctx->h_ring_cap = want_cap;
+    }
+    while (ctx->ring_ev.size() < ctx->h_ring.size()) {
+        hipEvent_t e = nullptr;
+        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) (void)hipGetLastError(), e = nullptr;
+        ctx->ring_ev.push_back(e);
+    }
+    return ctx->h_ring.size();
+}
+
+// the mask and event counts of every piece of a feed (on a few threads: two passes over 10^7 ops on the main thread were 40 ms of a feed)
+static rv_stream::FeedCounts feed_counts(rv_stream* S, const rv_op* ops, const std::vector<size_t>& cut, uint64_t first_op) {
+    // (rv_stream_same_cuts: pass 2 takes pass 1's counts of the same feed -- two passes over 240 MB of ops, 7 ms on 8 threads.
+    // Other ops in pass 2 only make the predictions wrong: the pieces are then compiled again in place, and finish reports it)
+    if (S->same_cuts && S->pass == 2) {
+        auto it = S->feed_counts.find(first_op);
+        if (it != S->feed_counts.end() && it->second.cut == cut) return it->second;
+    }
+    const size_t n_pieces = cut.size() - 1;
+    rv_stream::FeedCounts k;
+    k.cut = cut;
+    k.cm2.resize(n_pieces), k.cm64.resize(n_pieces), k.cev.resize(n_pieces);
+    const unsigned nt = (unsigned)std::min<size_t>({(size_t)16, n_pieces, (size_t)std::max(1u, std::thread::hardware_concurrency() / 2)});
+    auto count = [&](unsigned t) {
+        for (size_t i = t; i < n_pieces; i += nt) {
+            count_masks(ops + cut[i], cut[i + 1] - cut[i], &k.cm2[i], &k.cm64[i]);
+            count_events(ops + cut[i], cut[i + 1] - cut[i], &k.cev[i]);
+        }
+    };
+    std::vector<std::thread> th;
+    th.reserve(nt);
+    try {
+        for (unsigned t = 1; t < nt; t++) th.emplace_back(count, t);
+    } catch (...) {
+        for (auto& x : th) x.join();
+        th.clear();
+        for (unsigned t = 1; t < nt; t++) count(t);
+    }
+    count(0);
+    for (auto& x : th) x.join();
+    if (S->same_cuts && S->pass == 1) S->feed_counts[first_op] = k;
+    return k;
+}
+
+// The pieces of a feed.  predict: every piece's ShareGen phases AND the carried transcript events it will find in front of its own
+// follow from counts over the pieces before it, so the worker that compiles a piece also moves its transcript offsets (relocate_chunk:
+// a pass over all its gates, 3 ms per 10^6 ops that the main thread used to spend between two chunks' GPU work).
+static std::vector<FeedPiece> feed_pieces(rv_stream* S, const rv_op* ops, const std::vector<size_t>& cut, bool predict) {
+    const size_t n_pieces = cut.size() - 1;
+    const uint64_t first_op = S->run.n_ops;
+    std::vector<FeedPiece> pieces(n_pieces);
+    rv_stream::FeedCounts fc;
+    if (predict) fc = feed_counts(S, ops, cut, first_op);
+    uint64_t m2 = S->run.masks, m64 = S->run.masks64;
+    const bool tails = S->pass != 2;  // (the verifier's single pass carries unhashed tails like pass 1)
+    uint64_t t[TR_KINDS];             // pass 1: unhashed tails
+    for (int kind = 0; kind < TR_KINDS; kind++) t[kind] = S->tr[kind].tail;
+    uint64_t pr = S->pend_rec, pi = S->pend_in, pp = S->pend_pre;  // pass 2: items short of a byte
+    for (size_t i = 0; i < n_pieces; i++) {
+        FeedPiece& p = pieces[i];
+        p.at = cut[i];
+        p.n = cut[i + 1] - cut[i];
+        p.c = stream_take_cached(S, first_op + p.at, p.n, &p.carried, &p.digest);
+        if (S->pass == 2) {
+            auto it = S->kept.find(first_op + p.at);
+            p.kept = it != S->kept.end() && it->second.n_ops == p.n;
+        }
+        if (!predict) continue;
+        p.predicted = true;
+        p.want.mask_phase = p.ph2 = (uint32_t)(m2 % 128);
+        p.want.mask64_phase = p.ph64 = (uint32_t)(m64 % 2);
+        m2 += fc.cm2[i];
+        m64 += fc.cm64[i];
+        const StreamEvents& ev = fc.cev[i];
+        if (tails) {
+            set_carried(p.want, t[TR_PRE], t[TR_ON], t[TR_PRE64], t[TR_ON64]);
+            const uint64_t own[TR_KINDS] = {ev.pre2, ev.in2 + ev.rec2, ev.pre64, ev.on64};
+            for (int kind = 0; kind < TR_KINDS; kind++) t[kind] = TR_KIND[kind].tail_of(t[kind] + own[kind]);
+        } else {
+            set_carried(p.want, pp, pr + pi, 0, 0);
+            pr = (pr + ev.rec2) % 8, pi = (pi + ev.in2) % 8, pp = (pp + ev.pre2) % 8;
+        }
+    }
+    return pieces;
+}
+
+// H: the caller's handle -- a single stream, or a batch whose members are fed witness b at wit_gf2 + b * n_gf2, wit_z64 + b * n_z64.
+// The pieces are compiled ahead on worker threads (piece_pipe.h) and run in order; with one thread each is prepared right before it
+// runs, unpredicted and unstaged.
 static int stream_feed_impl(rv_stream* H, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64, size_t n_z64) {
     LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
     if (!H || (n_ops && !ops)) return RV_E_ARG;
@@ -1168,312 +1349,73 @@ static int stream_feed_impl(rv_stream* H, const rv_op* ops, size_t n_ops, const 
     if (proofs.empty()) return RV_OK;  // (a verifier stream whose proof has the wrong shape: the answer is already `false`)
     rv_stream* S = proofs[0];          // (the host-side state of the feed: compiled-chunk cache, counts, pass)
     if (S->sticky) return H->sticky = S->sticky;
-    const size_t stride2 = n_gf2, stride64 = n_z64;
-    auto fail = [&](int rc) {
-        S->sticky = rc;
-        return H->sticky = rc;
-    };
     HIPCHK(hipSetDevice(S->ctx->device));
-    const auto t_feed0 = std::chrono::steady_clock::now();
+    const bool stats = getenv("RV_STREAM_STATS") != nullptr;
+    using Clock = std::chrono::steady_clock;
+    auto secs = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    const auto t_feed0 = Clock::now();
+    WitnessRows wit{wit_gf2, n_gf2, n_gf2, wit_z64, n_z64, n_z64};
     const std::vector<size_t> cut = stream_cuts(n_ops, S->max_chunk_ops);  // piece i = ops [cut[i], cut[i + 1])
     const size_t n_pieces = cut.size() - 1;
     const unsigned n_threads = (unsigned)std::min<size_t>(stream_threads(), n_pieces);
-    auto advance = [&](size_t u2, size_t u64) {
-        wit_gf2 = wit_gf2 ? wit_gf2 + u2 : wit_gf2;
-        n_gf2 -= u2;
-        wit_z64 = wit_z64 ? wit_z64 + u64 : wit_z64;
-        n_z64 -= u64;
-    };
-    if (n_threads <= 1) {
-        for (size_t i = 0; i < n_pieces; i++) {
-            size_t u2 = 0, u64 = 0;
-            const int rc = stream_chunk(S, proofs, ops + cut[i], cut[i + 1] - cut[i], wit_gf2, n_gf2, stride2, wit_z64, n_z64, stride64, &u2, &u64);
-            if (rc) return fail(rc);
-            advance(u2, u64);
-        }
-        return RV_OK;
-    }
-    // ---- the pieces are compiled ahead on worker threads (a window of 2 x threads compiled pieces at most: each holds
-    // ~70 bytes per op) and run in order; a piece's ShareGen phases follow from the mask counts of the pieces before it
-    struct Piece {
-        size_t at = 0, n = 0;
-        uint32_t ph2 = 0, ph64 = 0;
-        rv_circuit* c = nullptr;
-        uint64_t digest = 0;
-        ChunkStart carried;
-        ChunkStart want;  // the offsets the piece is expected to run at
-        int rc = 0;
-        bool ready = false;
-        bool taken = false;    // the main thread has it (or is past it): not to be staged any more
-        bool staging = false;  // a worker is copying its arrays into a page-locked slot right now
-        bool kept = false;     // pass 2: pass 1 kept this piece's transcripts (rv_stream::Kept) -- nothing of it is uploaded
-    };
-    std::vector<Piece> pieces(n_pieces);
-    // The ring of page-locked slots (rv_ctx::h_ring): piece s goes into slot s % NS once piece s - NS has run -- a copy of
-    // ~13 MB per piece that used to sit on the main thread between two pieces' GPU work (1.2 of its ~2.2 ms per piece)
-    constexpr size_t NS_WANT = 6;
-    size_t NS = 0, slot_cap = 0;
-    {
-        rv_ctx* ctx = S->ctx;
-        // a piece's arrays: its ops' gates and ordinal tables, PLUS the extra level that writes every wire it wrote back to the wire
-        // store (up to one more gate per wire index: for the 10^7-gate circuit with recycled indices 2 x 10^5 gates = 9.6 MB beside the
-        // 12 MB of a 2^18-op piece; sized without them, the slots were too small for every full-size piece and the main thread went
-        // on copying: 0.16 -> 0.11 s per proof once a larger feed had grown the ring)
-        const size_t wb2 = std::min<size_t>(S->gf2_wires, S->max_chunk_ops), wb64 = std::min<size_t>(S->z64_wires, S->max_chunk_ops);
-        const size_t want_cap = ((S->max_chunk_ops * (sizeof(Gate) + 8) + wb2 * sizeof(Gate) + wb64 * sizeof(Gate64) + ((size_t)2 << 20)) + 0xFFFFF) & ~(size_t)0xFFFFF;
-        if (NS_WANT && want_cap <= ((size_t)80 << 20)) {
-            if (ctx->h_ring_cap < want_cap || ctx->h_ring.size() < NS_WANT) {
-                (void)hipStreamSynchronize(ctx->stream);
-                for (uint8_t* p : ctx->h_ring) (void)hipHostFree(p);
-                ctx->h_ring.clear();
-                ctx->h_ring_cap = 0;
-                for (hipEvent_t e : ctx->ring_ev)
-                    if (e) (void)hipEventDestroy(e);
-                ctx->ring_ev.clear();
-                for (size_t k = 0; k < NS_WANT; k++) {
-                    uint8_t* p = nullptr;
-                    if (hipHostMalloc((void**)&p, want_cap, hipHostMallocDefault) != hipSuccess) {
-                        (void)hipGetLastError();
-                        break;
-                    }
-                    ctx->h_ring.push_back(p);
-                }
-                ctx->h_ring_cap = want_cap;
-            }
-            while (ctx->ring_ev.size() < ctx->h_ring.size()) {
-                hipEvent_t e = nullptr;
-                if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) (void)hipGetLastError(), e = nullptr;
-                ctx->ring_ev.push_back(e);
-            }
-            NS = ctx->h_ring.size();
-            slot_cap = ctx->h_ring_cap;
-        }
-    }
+    const bool ahead = n_threads > 1;
+    const size_t NS = ahead ? feed_ring(S) : 0, slot_cap = S->ctx->h_ring_cap;
     const uint64_t first_op = S->run.n_ops;
-    {
-        // Every piece's ShareGen phases AND the carried transcript events it will find in front of its own follow from counts over
-        // the pieces before it, so the worker that compiles a piece also moves its transcript offsets (relocate_chunk: a pass over
-        // all its gates, 3 ms per 10^6 ops that the main thread used to spend between two chunks' GPU work); stream_chunk_run moves
-        // it again by the difference, which is zero unless this prediction is off
-        uint64_t m2 = S->run.masks, m64 = S->run.masks64;
-        const bool p1 = S->pass != 2;  // (the verifier's single pass carries unhashed tails like pass 1)
-        uint64_t on_t = S->on_tail, pre_t = S->pre_tail, on64_t = S->on64_tail, pre64_t = S->pre64_tail;  // pass 1: unhashed tails
-        uint64_t pr = S->pend_rec, pi = S->pend_in, pp = S->pend_pre;                                      // pass 2: items short of a byte
-        auto tail_of = [](uint64_t total, uint64_t unit) { return total ? total - (total - 1) / unit * unit : 0; };
-        // (the counts of all pieces at once, on a few threads: two passes over 10^7 ops on the main thread were 40 ms of a feed)
-        std::vector<uint64_t> cm2(n_pieces), cm64(n_pieces);
-        std::vector<StreamEvents> cev(n_pieces);
-        // (rv_stream_same_cuts: pass 2 takes pass 1's counts of the same feed -- two passes over 240 MB of ops, 7 ms on 8 threads.
-        // Other ops in pass 2 only make the predictions wrong: the pieces are then compiled again in place, and finish reports it)
-        rv_stream::FeedCounts* fc = nullptr;
-        if (S->same_cuts && S->pass == 2) {
-            auto it = S->feed_counts.find(first_op);
-            if (it != S->feed_counts.end() && it->second.cut == cut) fc = &it->second;
-        }
-        if (fc) {
-            cm2 = fc->cm2, cm64 = fc->cm64, cev = fc->cev;
-        } else {
-            const unsigned nt = (unsigned)std::min<size_t>({(size_t)16, n_pieces, (size_t)std::max(1u, std::thread::hardware_concurrency() / 2)});
-            auto count = [&](unsigned t) {
-                for (size_t i = t; i < n_pieces; i += nt) {
-                    count_masks(ops + cut[i], cut[i + 1] - cut[i], &cm2[i], &cm64[i]);
-                    count_events(ops + cut[i], cut[i + 1] - cut[i], &cev[i]);
-                }
-            };
-            std::vector<std::thread> th;
-            th.reserve(nt);
-            try {
-                for (unsigned t = 1; t < nt; t++) th.emplace_back(count, t);
-            } catch (...) {
-                for (auto& x : th) x.join();
-                th.clear();
-                for (unsigned t = 1; t < nt; t++) count(t);
-            }
-            count(0);
-            for (auto& x : th) x.join();
-            if (S->same_cuts && S->pass == 1) {
-                rv_stream::FeedCounts& k = S->feed_counts[first_op];
-                k.cut = cut, k.cm2 = cm2, k.cm64 = cm64, k.cev = cev;
-            }
-        }
-        for (size_t i = 0; i < n_pieces; i++) {
-            Piece& p = pieces[i];
-            p.at = cut[i];
-            p.n = cut[i + 1] - cut[i];
-            p.ph2 = (uint32_t)(m2 % 128);
-            p.ph64 = (uint32_t)(m64 % 2);
-            m2 += cm2[i];
-            m64 += cm64[i];
-            const StreamEvents& ev = cev[i];
-            p.want.mask_phase = p.ph2;
-            p.want.mask64_phase = p.ph64;
-            if (p1) {
-                p.want.on0 = on_t, p.want.pre0 = pre_t, p.want.on_words64_0 = on64_t, p.want.pre_words64_0 = pre64_t;
-                on_t = tail_of(on_t + ev.in2 + ev.rec2, 1024);
-                pre_t = tail_of(pre_t + ev.pre2, 1024);
-                on64_t = tail_of(on64_t + ev.on64, 128);
-                pre64_t = tail_of(pre64_t + ev.pre64, 128);
-            } else {
-                p.want.on0 = pr + pi, p.want.pre0 = pp;
-                pr = (pr + ev.rec2) % 8, pi = (pi + ev.in2) % 8, pp = (pp + ev.pre2) % 8;
-            }
-            p.c = stream_take_cached(S, first_op + p.at, p.n, &p.carried, &p.digest);  // (a worker checks it against the ops fed now)
-            if (S->pass == 2) {
-                auto it = S->kept.find(first_op + p.at);
-                p.kept = it != S->kept.end() && it->second.n_ops == p.n;
-            }
-        }
-    }
-    std::mutex mu;
-    std::condition_variable cv;
-    size_t next = 0, consumed = 0, next_stage = 0;
-    bool stop = false;
-    const size_t window = 2 * (size_t)n_threads;
-    // (call with mu held) the next piece a worker may copy into its slot: compiled, not yet with the main thread, slot free
-    auto stage_job = [&]() -> bool {
-        if (!NS) return false;
-        while (next_stage < n_pieces &&
-               (pieces[next_stage].taken || pieces[next_stage].kept || (pieces[next_stage].ready && (pieces[next_stage].rc || !pieces[next_stage].c))))
+    std::vector<FeedPiece> pieces = feed_pieces(S, ops, cut, ahead);
+    // the second job of a worker: the next piece that is compiled, not yet with the main thread and whose slot is free goes into it
+    size_t next_stage = 0;
+    auto stage_pick = [&](const PiecePipe& pp) {
+        while (next_stage < n_pieces && (pp.taken(next_stage) || pieces[next_stage].kept || (pp.ready(next_stage) && (pp.rc(next_stage) || !pieces[next_stage].c))))
             next_stage++;
-        return next_stage < n_pieces && pieces[next_stage].ready && next_stage < consumed + NS;
+        return next_stage < n_pieces && pp.ready(next_stage) && next_stage < pp.n_consumed() + NS ? next_stage++ : PiecePipe::NONE;
     };
-    auto worker = [&] {
-        for (;;) {
-            size_t i;
-            bool stage = false;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || stage_job() || (next < n_pieces && next < consumed + window); });
-                if (stop) return;
-                if (stage_job()) {
-                    i = next_stage++;
-                    pieces[i].staging = true;
-                    stage = true;
-                } else if (next < n_pieces && next < consumed + window) {
-                    i = next++;
-                } else {
-                    return;
-                }
-            }
-            if (stage) {
-                rv_circuit* c = pieces[i].c;
-                if (circuit_stage_bytes(c->cc) <= slot_cap) {
-                    // (the copies out of the slot's previous piece may still be in flight: stream_chunk_run no longer waits per chunk)
-                    if (S->ctx->ring_ev[i % NS]) (void)hipEventSynchronize(S->ctx->ring_ev[i % NS]);
-                    circuit_stage(c, S->ctx->h_ring[i % NS], (int)(i % NS));
-                }
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    pieces[i].staging = false;
-                }
-                cv.notify_all();
-                continue;
-            }
-            rv_circuit* c = pieces[i].c;  // pass 1's compile out of the cache, or null
-            ChunkStart carried = pieces[i].carried;
-            int rc = RV_OK;
-            uint64_t dg = 0;
-            try {
-                dg = ops_digest(ops + pieces[i].at, pieces[i].n, first_op + pieces[i].at);
-                if (c && dg != pieces[i].digest) {  // same position and length, other ops (finish reports RV_E_ARG)
-                    rv_circuit_destroy(c);
-                    c = nullptr;
-                    carried = ChunkStart();
-                }
-                if (!c) {  // (at the offsets it is expected to run at: no relocation pass afterwards)
-                    rc = stream_compile_piece(S, ops + pieces[i].at, pieces[i].n, pieces[i].ph2, pieces[i].ph64, &c, &pieces[i].want);
-                    if (!rc) carried = pieces[i].want;
-                }
-                if (!rc && c) {
-                    const ChunkStart& w = pieces[i].want;
-                    relocate_chunk(c->cc, w.on0 - carried.on0, w.pre0 - carried.pre0, w.on_words64_0 - carried.on_words64_0,
-                                   w.pre_words64_0 - carried.pre_words64_0);
-                    carried.on0 = w.on0, carried.pre0 = w.pre0, carried.on_words64_0 = w.on_words64_0, carried.pre_words64_0 = w.pre_words64_0;
-                }
-            } catch (...) {
-                rc = RV_E_NOMEM;
-            }
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                pieces[i].digest = dg;
-                pieces[i].c = c;
-                pieces[i].carried = carried;
-                pieces[i].rc = rc;
-                pieces[i].ready = true;
-            }
-            cv.notify_all();
-        }
+    auto stage = [&](size_t i) {
+        rv_circuit* c = pieces[i].c;
+        if (circuit_stage_bytes(c->cc) > slot_cap) return;
+        // (the copies out of the slot's previous piece may still be in flight: a chunk is not waited for)
+        if (S->ctx->ring_ev[i % NS]) (void)hipEventSynchronize(S->ctx->ring_ev[i % NS]);
+        circuit_stage(c, S->ctx->h_ring[i % NS], (int)(i % NS));
     };
-    std::vector<std::thread> pool;
-    struct PoolGuard {  // stops and joins the workers on every way out (an exception from the main loop must not reach joinable threads)
-        std::vector<std::thread>& pool;
-        std::mutex& mu;
-        std::condition_variable& cv;
-        bool& stop;
-        ~PoolGuard() {
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                stop = true;
-            }
-            cv.notify_all();
-            for (std::thread& t : pool)
-                if (t.joinable()) t.join();
-        }
-    } guard{pool, mu, cv, stop};
-    for (unsigned t = 0; t < n_threads; t++) pool.emplace_back(worker);
+    PiecePipe pipe(n_pieces, n_threads, RV_E_NOMEM, [&](size_t i) { return prepare_piece(S, ops, first_op, pieces[i]); },
+                   NS ? PiecePipe::Pick(stage_pick) : PiecePipe::Pick(), stage);
+    if (stats) fprintf(stderr, "[rv stream] feed set up (cuts, counts, cached pieces, %u workers) in %.3f s\n", n_threads, secs(t_feed0, Clock::now()));
     int rc = RV_OK;
-    const bool stats = getenv("RV_STREAM_STATS") != nullptr;
-    if (stats) fprintf(stderr, "[rv stream] feed set up (cuts, counts, cached pieces, %u workers) in %.3f s\n", n_threads, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_feed0).count());
     double t_wait = 0, t_run = 0;
     for (size_t i = 0; i < n_pieces && !rc; i++) {
-        rv_circuit* c = nullptr;
-        const auto t0 = std::chrono::steady_clock::now();
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return pieces[i].ready && !pieces[i].staging; });
-            pieces[i].taken = true;
-            rc = pieces[i].rc;
-            c = pieces[i].c;
-            pieces[i].c = nullptr;
-        }
-        if (!rc && (pieces[i].ph2 != (uint32_t)(S->run.masks % 128) || pieces[i].ph64 != (uint32_t)(S->run.masks64 % 2))) {
+        FeedPiece& p = pieces[i];
+        const auto t0 = Clock::now();
+        rc = pipe.wait(i);
+        rv_circuit* c = p.c;
+        p.c = nullptr;
+        if (rc) rv_circuit_destroy(c);
+        if (!rc && (p.ph2 != (uint32_t)(S->run.masks % 128) || p.ph64 != (uint32_t)(S->run.masks64 % 2))) {
             // (cannot happen while count_masks agrees with the compiler; compile again in place rather than trust it)
             rv_circuit_destroy(c);
             c = nullptr;
-            pieces[i].carried = ChunkStart();
-            rc = stream_compile_piece(S, ops + pieces[i].at, pieces[i].n, (uint32_t)(S->run.masks % 128), (uint32_t)(S->run.masks64 % 2), &c);
+            p.carried = ChunkStart();
+            rc = stream_compile_piece(S, ops + p.at, p.n, (uint32_t)(S->run.masks % 128), (uint32_t)(S->run.masks64 % 2), &c);
         }
-        const auto t1 = std::chrono::steady_clock::now();
+        const auto t1 = Clock::now();
         if (!rc) {
-            size_t u2 = 0, u64 = 0;
-            rc = stream_chunk_run(S, proofs, c, pieces[i].digest, pieces[i].n, wit_gf2, n_gf2, stride2, wit_z64, n_z64, stride64, &u2, &u64, pieces[i].carried);
-            advance(u2, u64);
+            ChunkRun run(proofs, c, p.digest, p.n, wit);
+            rc = run.run(p.carried);
+            wit.advance(run.used_gf2, run.used_z64);
         }
-        t_wait += std::chrono::duration<double>(t1 - t0).count();
-        t_run += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            consumed = i + 1;
-            if (rc) stop = true;
-        }
-        cv.notify_all();
+        t_wait += secs(t0, t1);
+        t_run += secs(t1, Clock::now());
+        pipe.consumed(i, rc);
     }
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        stop = true;
-    }
-    cv.notify_all();
-    for (std::thread& t : pool) t.join();  // (the guard finds nothing left to join)
-    for (Piece& p : pieces)
+    pipe.stop();
+    for (FeedPiece& p : pieces)
         if (p.c) rv_circuit_destroy(p.c);  // compiled but never run (an earlier piece failed)
     if (stats)
         fprintf(stderr, "[rv stream] feed of %zu pieces on %u threads: %.3f s waiting for compiled pieces, %.3f s running them\n", n_pieces, n_threads,
                 t_wait, t_run);
-    if (rc) return fail(rc);
-    return RV_OK;
+    if (rc) S->sticky = H->sticky = rc;
+    return rc;
 }
 
-// the one wait of a feed whose chunks were issued without one each (stream_chunk_run: no_wait): the error flags they left
+// the one wait of a feed whose chunks were issued without one each (ChunkRun: no_wait): the error flags they left
 static int stream_feed_settle(rv_stream* H) {
     if (!H) return RV_OK;
     const std::vector<rv_stream*> proofs = H->running();
@@ -1487,13 +1429,7 @@ static int stream_feed_settle(rv_stream* H) {
 
 extern "C" int rv_stream_feed(rv_stream* S, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
                               size_t n_z64) {
-    int rc;
-    try {
-        rc = stream_feed_impl(S, ops, n_ops, wit_gf2, n_gf2, wit_z64, n_z64);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        rc = RV_E_NOMEM;
-    }
+    const int rc = guarded([&] { return stream_feed_impl(S, ops, n_ops, wit_gf2, n_gf2, wit_z64, n_z64); });
     // (also after a failed feed: the caller's witness arrays and the ring slots may still feed copies)
     const int rs = stream_feed_settle(S);
     return rc ? rc : rs;
@@ -1502,22 +1438,17 @@ extern "C" int rv_stream_feed(rv_stream* S, const rv_op* ops, size_t n_ops, cons
 // the four stream digests of every repetition from the trees and the tails (S->d_dig: H_pre, H_on of GF(2), then of Z64)
 static int stream_final_digests(rv_stream* S) {
     rv_ctx* ctx = S->ctx;
-    hipStream_t st = ctx->stream;
-    constexpr uint32_t R = rv_stream::R, NQ = rv_stream::NQ;
+    constexpr uint32_t R = rv_stream::R;
     int rc;
     uint32_t* last = nullptr;
     if ((rc = dalloc(ctx, (size_t)R * 8, &last))) return rc;
-    const size_t DW = (size_t)R * 8;
     ctx->phase(RV_PH_HASH);
     // the streams' last chunks: what sits in the tails (an empty stream hashes as BLAKE3(""), root flag set)
-    launch_b3_stream_bits_chunks(st, S->d_pre_tail, S->pre_tail, NQ, last, S->h_pre.chunks, S->h_pre.chunks == 0);
-    inc_finish(ctx, S->h_pre, last, R, S->d_dig + 0 * DW);
-    launch_b3_stream_chunks(st, S->d_on_tail, S->on_tail, NQ, last, nullptr, 0, S->h_on.chunks, S->h_on.chunks == 0);
-    inc_finish(ctx, S->h_on, last, R, S->d_dig + 1 * DW);
-    launch_b3_contig_chunks(st, S->d_pre64_tail, 128, S->pre64_tail, R, last, S->h_pre64.chunks, S->h_pre64.chunks == 0);
-    inc_finish(ctx, S->h_pre64, last, R, S->d_dig + 2 * DW);
-    launch_b3_contig_chunks(st, S->d_on64_tail, 128, S->on64_tail, R, last, S->h_on64.chunks, S->h_on64.chunks == 0);
-    inc_finish(ctx, S->h_on64, last, R, S->d_dig + 3 * DW);
+    for (int kind = 0; kind < TR_KINDS; kind++) {
+        const rv_stream::Transcript& T = S->tr[kind];
+        TR_KIND[kind].hash(ctx->stream, T.d_tail, TR_KIND[kind].unit, T.tail, last, T.tree.chunks, T.tree.chunks == 0);
+        inc_finish(ctx, T.tree, last, R, S->d_dig + (size_t)kind * R * 8);
+    }
     ctx->phase(-1);
     ctx->release(last);  // (stream order keeps the arena's reuse behind the kernels that read it)
     return RV_OK;
@@ -1600,12 +1531,7 @@ extern "C" int rv_stream_same_cuts(rv_stream* S) {
 }
 
 extern "C" int rv_stream_commit(rv_stream* S, uint8_t comm[RV_HASH_SIZE]) {
-    try {
-        return stream_commit_impl(S, comm);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return stream_commit_impl(S, comm); });
 }
 
 static int stream_finish_impl(rv_stream* S, uint8_t** proof, size_t* proof_len) {
@@ -1665,12 +1591,7 @@ static int stream_finish_impl(rv_stream* S, uint8_t** proof, size_t* proof_len) 
 }
 
 extern "C" int rv_stream_finish(rv_stream* S, uint8_t** proof, size_t* proof_len) {
-    try {
-        return stream_finish_impl(S, proof, proof_len);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return stream_finish_impl(S, proof, proof_len); });
 }
 
 extern "C" int rv_stream_get_info(const rv_stream* S, rv_stream_info* info) {
@@ -1707,9 +1628,7 @@ extern "C" int rv_stream_get_info(const rv_stream* S, rv_stream_info* info) {
     info->kept_mib = (uint32_t)std::min<uint64_t>((S->kept_peak + ((1u << 20) - 1)) >> 20, 0xFFFFFFFFu);
     info->wire_store_bytes = (uint64_t)S->rows_cap * (rv_stream::NQ * 4 + rv_stream::NQ / 2) + (uint64_t)S->ssa64_cap * rv_stream::R * 72;
     info->peak_chunk_bytes = S->peak_bytes;
-    uint64_t nodes = 0;
-    for (const IncHash* h : {&S->h_pre, &S->h_on, &S->h_pre64, &S->h_on64}) nodes += h->node.size();
-    info->hash_state_bytes = nodes * rv_stream::R * 32 + (uint64_t)1024 * rv_stream::NQ * 4 + 1024 * (rv_stream::NQ / 2) + 2 * (uint64_t)rv_stream::R * 128 * 8;
+    for (int kind = 0; kind < TR_KINDS; kind++) info->hash_state_bytes += S->tr[kind].tree.node.size() * rv_stream::R * 32 + TR_KIND[kind].tail_bytes();
     info->proof_bytes = S->pass == 2 ? S->L.total : 0;
     return RV_OK;
 }
@@ -1802,12 +1721,7 @@ static int stream_verify_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wi
 
 extern "C" int rv_stream_verify_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, const uint8_t* proof, size_t proof_len, size_t max_chunk_ops,
                                       rv_stream** out) {
-    try {
-        return stream_verify_begin_impl(ctx, z64_wires, gf2_wires, proof, proof_len, max_chunk_ops, out);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return stream_verify_begin_impl(ctx, z64_wires, gf2_wires, proof, proof_len, max_chunk_ops, out); });
 }
 
 static int stream_verify_finish_impl(rv_stream* S, uint32_t flags, int* ok) {
@@ -1839,12 +1753,7 @@ static int stream_verify_finish_impl(rv_stream* S, uint32_t flags, int* ok) {
 }
 
 extern "C" int rv_stream_verify_finish(rv_stream* S, uint32_t flags, int* ok) {
-    try {
-        return stream_verify_finish_impl(S, flags, ok);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return stream_verify_finish_impl(S, flags, ok); });
 }
 
 // Proof::verify with bounded device memory over an op array that already sits in host memory
@@ -1892,7 +1801,7 @@ extern "C" int rv_prove_streaming(rv_ctx* ctx, const rv_op* ops, size_t n_ops, s
 
 // ------------------------------------------------------------------------------------
 // BATCHES: B witnesses (prover) or B proofs (verifier) of one statement over ONE fed op list.  The handle's members are complete
-// single-proof streams; a feed compiles, relocates and uploads every chunk once and runs it for all members (stream_chunk_run),
+// single-proof streams; a feed compiles, relocates and uploads every chunk once and runs it for all members (ChunkRun),
 // so B proofs cost one stream's host work -- the part that paces a streamed GF(2) proof -- plus B times the chunks' device work.
 // ------------------------------------------------------------------------------------
 // B wire stores must fit in half of what the device has free (plus what the context's arena holds idle): the batch is not split
@@ -1937,12 +1846,7 @@ static int stream_begin_batch_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wir
 
 extern "C" int rv_stream_begin_batch(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch, const uint8_t* seeds, size_t max_chunk_ops,
                                      rv_stream** out) {
-    try {
-        return stream_begin_batch_impl(ctx, z64_wires, gf2_wires, batch, seeds, max_chunk_ops, out);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return stream_begin_batch_impl(ctx, z64_wires, gf2_wires, batch, seeds, max_chunk_ops, out); });
 }
 
 static int stream_commit_batch_impl(rv_stream* S, uint8_t* comms) {
@@ -1960,12 +1864,7 @@ static int stream_commit_batch_impl(rv_stream* S, uint8_t* comms) {
 }
 
 extern "C" int rv_stream_commit_batch(rv_stream* S, uint8_t* comms) {
-    try {
-        return stream_commit_batch_impl(S, comms);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return stream_commit_batch_impl(S, comms); });
 }
 
 static int stream_finish_batch_impl(rv_stream* S, uint8_t** proofs, size_t* proof_lens) {
@@ -1988,12 +1887,7 @@ static int stream_finish_batch_impl(rv_stream* S, uint8_t** proofs, size_t* proo
 }
 
 extern "C" int rv_stream_finish_batch(rv_stream* S, uint8_t** proofs, size_t* proof_lens) {
-    try {
-        return stream_finish_batch_impl(S, proofs, proof_lens);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return stream_finish_batch_impl(S, proofs, proof_lens); });
 }
 
 // one member of a verifier batch: a proof that cannot be parsed, or that the verifier's slots cannot take, is a member that runs
@@ -2045,12 +1939,7 @@ static int stream_verify_begin_batch_impl(rv_ctx* ctx, size_t z64_wires, size_t 
 
 extern "C" int rv_stream_verify_begin_batch(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch, const uint8_t* const* proofs,
                                             const size_t* proof_lens, size_t max_chunk_ops, rv_stream** out) {
-    try {
-        return stream_verify_begin_batch_impl(ctx, z64_wires, gf2_wires, batch, proofs, proof_lens, max_chunk_ops, out);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return stream_verify_begin_batch_impl(ctx, z64_wires, gf2_wires, batch, proofs, proof_lens, max_chunk_ops, out); });
 }
 
 static int stream_verify_finish_batch_impl(rv_stream* S, uint32_t flags, int* ok) {
@@ -2072,12 +1961,7 @@ static int stream_verify_finish_batch_impl(rv_stream* S, uint32_t flags, int* ok
 }
 
 extern "C" int rv_stream_verify_finish_batch(rv_stream* S, uint32_t flags, int* ok) {
-    try {
-        return stream_verify_finish_batch_impl(S, flags, ok);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return stream_verify_finish_batch_impl(S, flags, ok); });
 }
 
 // both passes of a batch over an op array that is already in host memory
