@@ -294,6 +294,8 @@ typedef struct rv_eval_stream_info {
     uint64_t peak_chunk_bytes;  /* largest chunk's working set (rows, SSA slots, gate records, witness words) */
 } rv_eval_stream_info;
 int rv_eval_stream_begin(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, size_t batch, size_t max_chunk_ops, rv_eval_stream **out);
+/* As rv_stream_set_compile_flags (below): 0 or RV_COMPILE_DEVICE, before the first feed; the context's flags are the default. */
+int rv_eval_stream_set_compile_flags(rv_eval_stream *s, uint32_t flags);
 int rv_eval_stream_feed(rv_eval_stream *s, const rv_op *ops, size_t n_ops, const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64,
                         size_t n_z64);
 int rv_eval_stream_finish(rv_eval_stream *s, uint8_t *gf2_values, uint64_t *z64_values, rv_eval_status *st);
@@ -350,6 +352,14 @@ void rv_free(void *p);
  * (RV_E_UNSUPPORTED).  After an error the stream only accepts rv_stream_abort. */
 int rv_stream_begin(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, const uint8_t *seeds /* 256 x 16 or NULL */,
                     size_t max_chunk_ops, rv_stream **out);
+/* Where the stream's pieces are compiled.  A stream takes the context's flags (rv_ctx_set_compile_flags) when it begins; this call
+ * overrides them before the first feed: 0 = on host worker threads (the default), RV_COMPILE_DEVICE = every all-GF(2) piece is
+ * uploaded and compiled on the GPU (the chunk mode of the device compiler: the same chunk, field by field), its gate records and
+ * ordinal tables staying in device memory; a piece the device path hands back (Z64 / B2A / SizeHint ops, an op-list error) is compiled
+ * on the host, with the host compiler's result or error code.  The proofs, answers and values are the same bytes either way.  On a
+ * batch handle (rv_stream_begin_batch, rv_stream_verify_begin_batch) it holds for the whole batch.  RV_E_ARG: NULL handle, any other
+ * bit, or a call after the first feed. */
+int rv_stream_set_compile_flags(rv_stream *s, uint32_t flags);
 int rv_stream_feed(rv_stream *s, const rv_op *ops, size_t n_ops, const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64,
                    size_t n_z64);
 int rv_stream_commit(rv_stream *s, uint8_t comm[RV_HASH_SIZE] /* nullable */);
@@ -644,6 +654,13 @@ int rv_hook_compile_compare(const rv_op *ops, size_t n_ops, size_t z64_wires, si
  * Returns the host compiler's status. */
 int rv_hook_compile_compare_device(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, int *path,
                                    int *diff);
+/* The same for one piece of a stream: both sides compile the ops as the streaming chunk that starts at `start` = { mask_phase (< 128),
+ * mask64_phase (< 2), on0, pre0, on_words64_0, pre_words64_0 } (the ShareGen phases and the carried transcript events in front of the
+ * piece's own).  *path, *diff and the return value as rv_hook_compile_compare_device. */
+int rv_hook_compile_compare_device_chunk(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const uint64_t start[6], int *path, int *diff);
+/* Pieces of this process's streams (rv_stream_*, rv_eval_stream_* and the one-shot calls over them) that the device path compiled so
+ * far: a test tells a device compile from a fallback to the host compiler by it. */
+uint64_t rv_hook_stream_device_chunks(void);
 /* Per-phase times of this process's last device compile, ms from HIP events: out[0] classify and count, [1] last writers and consumer
  * lists, [2] values and levels (topological rounds), [3] rows, sort and tables, [4] the host's copy; out[5] = rounds launched. */
 int rv_hook_compile_device_laps(double out[6]);

@@ -88,6 +88,7 @@ SYMBOLS = [
     "rv_stream_verify_begin_batch", "rv_stream_verify_finish_batch", "rv_verify_streaming_batch",
     "rv_verify_shard_groups", "rv_verify_partition", "rv_verify_sharded", "rv_verify_multi", "rv_hook_verify_proof_bytes",
     "rv_circuit_compile_device", "rv_ctx_set_compile_flags", "rv_hook_compile_compare_device", "rv_hook_compile_device_laps",
+    "rv_stream_set_compile_flags", "rv_eval_stream_set_compile_flags", "rv_hook_compile_compare_device_chunk", "rv_hook_stream_device_chunks",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -111,6 +112,11 @@ ARGTYPES = {
     "rv_ctx_set_compile_flags": [_P, C.c_uint32],
     "rv_hook_compile_compare_device": [_P, _P, _Z, _Z, _Z, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "rv_hook_compile_device_laps": [C.POINTER(C.c_double)],
+    # the device compiler in the streams
+    "rv_stream_set_compile_flags": [_P, C.c_uint32],
+    "rv_eval_stream_set_compile_flags": [_P, C.c_uint32],
+    "rv_hook_compile_compare_device_chunk": [_P, _P, _Z, _Z, _Z, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "rv_hook_stream_device_chunks": [],
 }
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1
@@ -163,7 +169,7 @@ def lib():
                         "rv_eval_stream_abort"):
                 fn.restype = None
             elif name in ("rv_hook_early_proofs", "rv_hook_open_direct_proofs", "rv_hook_verify_vc_count", "rv_hook_ops_cache_hits", "rv_hook_overlap_commits",
-                          "rv_hook_verify_proof_bytes"):
+                          "rv_hook_verify_proof_bytes", "rv_hook_stream_device_chunks"):
                 fn.restype = C.c_uint64
             elif name not in ("rv_strerror", "rv_last_error", "rv_abi_version"):
                 fn.restype = C.c_int

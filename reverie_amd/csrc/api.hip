@@ -810,6 +810,39 @@ static int upload_ops(rv_ctx* ctx, const rv_op* ops, size_t n_ops, rv_op** d) {
     return RV_OK;
 }
 
+// One piece of a stream (rv_stream_*, rv_eval_stream_*) through the chunk-mode device compiler: the ops go up, the compile runs on the
+// context's stream in order, and the host gets the piece as compile_ops(..., &cs) would have made it (keep: its gate records and
+// ordinal tables stay in HBM).  Called on the thread that drives the context: the arena keeps no lock.  RV_OK, RV_COMPILE_FALLBACK
+// (the caller compiles the piece on the host) or an error code.  laps (RV_STREAM_STATS): seconds of op upload, compile, host copy.
+static std::atomic<uint64_t> g_stream_device_chunks{0};  // pieces of this process's streams that the device path compiled
+static bool piece_all_gf2(const rv_op* ops, size_t n_ops) {
+    for (size_t i = 0; i < n_ops; i++)
+        if (ops[i].domain != RV_DOM_GF2) return false;
+    return true;
+}
+static int compile_chunk_on_device(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const ChunkStart& cs, Compiled& cc,
+                                   DevCompileKeep* keep, double laps[3] = nullptr) {
+    if (getenv("RV_LAZY_K")) return RV_COMPILE_FALLBACK;
+    const auto t0 = std::chrono::steady_clock::now();
+    rv_op* up = nullptr;
+    int rc = upload_ops(ctx, ops, n_ops, &up);
+    if (rc) return rc;
+    const auto t1 = std::chrono::steady_clock::now();
+    DevCompileLaps dl;
+    rc = compile_ops_device(ctx->stream, ctx_dev_allocator(ctx), up, n_ops, z64_wires, gf2_wires, false, 0, cc, keep, laps ? &dl : nullptr, &cs);
+    ctx->release(up);  // (the device compile synchronised the stream)
+    if (rc == RV_E_DEVICE) g_last_error = "device compile of a stream's piece: HIP error";
+    if (rc == RV_E_NOMEM) g_last_error = "device compile of a stream's piece: out of device memory";
+    if (laps) {
+        const double total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+        laps[0] += std::chrono::duration<double>(t1 - t0).count();
+        laps[1] += total - dl.download * 1e-3;
+        laps[2] += dl.download * 1e-3;
+    }
+    return rc;
+}
+extern "C" uint64_t rv_hook_stream_device_chunks(void) { return g_stream_device_chunks.load(std::memory_order_relaxed); }
+
 static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                                   rv_circuit** out, const rv_op* d_ops) {
     if (!ctx || !out || (n_ops && !ops && !d_ops)) {
@@ -1274,6 +1307,34 @@ extern "C" int rv_hook_compile_compare_device(rv_ctx* ctx, const rv_op* ops, siz
         if (rd == RV_OK) {
             *path = 1;
             *diff = rc == RV_OK ? compiled_diff(a, b) : 100;  // (the device path compiled an op list the host compiler rejects)
+        } else if (rd == RV_COMPILE_FALLBACK) {
+            *path = 0;
+            *diff = 0;
+        } else {
+            return rd;
+        }
+        return rc;
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}
+
+extern "C" int rv_hook_compile_compare_device_chunk(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const uint64_t start[6],
+                                                    int* path, int* diff) {
+    if (!ctx || !path || !diff || !start || (n_ops && !ops)) return RV_E_ARG;
+    try {
+        ChunkStart cs;
+        cs.mask_phase = (uint32_t)start[0], cs.mask64_phase = (uint32_t)start[1];
+        cs.on0 = start[2], cs.pre0 = start[3], cs.on_words64_0 = start[4], cs.pre_words64_0 = start[5];
+        if (start[0] >= 128 || start[1] >= 2) return RV_E_ARG;
+        Compiled a, b;
+        const int rc = compile_ops_seq(ops, n_ops, z64_wires, gf2_wires, a, &cs);
+        HIPCHK(hipSetDevice(ctx->device));
+        const int rd = compile_chunk_on_device(ctx, ops, n_ops, z64_wires, gf2_wires, cs, b, nullptr);
+        if (rd == RV_OK) {
+            *path = 1;
+            *diff = rc == RV_OK ? compiled_diff(a, b) : 100;  // (the device path compiled a piece the host compiler rejects)
         } else if (rd == RV_COMPILE_FALLBACK) {
             *path = 0;
             *diff = 0;

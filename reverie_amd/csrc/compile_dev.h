@@ -3,6 +3,10 @@
 // SizeHint), no RV_COMPILE_KEEP_WIRES, no forced or environment-chosen lazy_k, and a K = 1 compile that compile_ops_seq would keep
 // (lazy_forms_pay false).  Everything else, every op-list error included, is RV_COMPILE_FALLBACK: the caller runs compile_ops,
 // which returns the canonical result or error code.
+//
+// Chunk mode (`chunk` not null): one piece of a stream, identical to compile_ops_seq(..., chunk) -- the wires start in their carried
+// rows, the counters at the ChunkStart's, no sum is dropped as unread, and one more level writes every wire the piece wrote back to
+// its carried row.  A chunk is final at K = 1 whatever its shape (lazy_forms_pay does not apply); an empty piece is compiled too.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,6 +38,7 @@ struct DevCompileKeep {
 // RV_OK (out filled; compile_us / upload_us / device_bytes / scratch_bytes left zero), RV_COMPILE_FALLBACK, or RV_E_NOMEM /
 // RV_E_DEVICE.  d_ops: n_ops packed rv_op records in device memory (read only).  Runs on `st`; synchronises it before returning.
 int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires,
-                       bool keep_wires, int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps = nullptr);
+                       bool keep_wires, int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps = nullptr,
+                       const ChunkStart* chunk = nullptr);
 
 }  // namespace rv

@@ -14,10 +14,17 @@
 //   5. tables     (level, class) keys, a stable radix sort of the gates, the records written straight into the circuit's gate array,
 //                 the LevelRange bounds, the per-level mask-block maxima and the online rows' levels (-> level_done_on)
 // No kernel waits for another workgroup; every loop is bounded by the op count, the level count or a round cap.
+//
+// Chunk mode (a ChunkStart: one piece of a stream, compile_ops_seq's `chunk`): a read with no write before it in the piece resolves to
+// the wire's carried row (producer -2 - wire instead of -1), the counters start at the ChunkStart's, nothing is dropped as unread, and
+//   6. write-back  a flag scan over the wires (written; final form still reads a carried row) numbers the extra computed rows and the
+//                  gates of the write-back level, which go straight to their places: the materialised carried forms are level 0's
+//                  class 3, the write-backs the last level's, both in wire order -- no op gate has class 3 at K = 1
 #include "compile_dev.h"
 
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <vector>
@@ -38,6 +45,14 @@ struct C4 {
 struct SumC4 {
     __device__ C4 operator()(const C4& a, const C4& b) const { return C4{a.m + b.m, a.mul + b.mul, a.as + b.as, a.in + b.in}; }
     static __device__ C4 id() { return C4{0, 0, 0, 0}; }
+};
+// what a streaming chunk adds to the kernels' numbering (all zero: a whole program)
+struct Seeds {
+    uint32_t chunk;    // 1: chunk mode
+    uint32_t base;     // carried rows in front of the PRG rows (row_prg_base)
+    uint32_t m0;       // ShareGen calls before the piece, modulo 128
+    uint32_t on0, pre0;  // transcript rows in front of the piece's own
+    uint32_t n_wbmat;  // carried forms materialised for the write-back level (level 0, class 3)
 };
 struct SumU32 {
     __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; }
@@ -202,13 +217,13 @@ __global__ __launch_bounds__(TB) void k_cd_classify(const rv_op* ops, size_t n, 
 }
 
 // the ordinal tables: reconstruction ordinal -> online row, input ordinal -> online row, the AssertZero ops
-__global__ __launch_bounds__(TB) void k_cd_ordinals(const rv_op* ops, size_t n, const C4* cx, uint32_t* rec_rows, uint32_t* in_rows, uint32_t* as_rec,
-                                                    uint64_t* as_op) {
+__global__ __launch_bounds__(TB) void k_cd_ordinals(const rv_op* ops, size_t n, const C4* cx, uint32_t on0, uint32_t* rec_rows, uint32_t* in_rows,
+                                                    uint32_t* as_rec, uint64_t* as_op) {
     const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
     if (i >= n) return;
     const uint32_t opc = ops[i].opcode;
     const C4 c = cx[i];
-    const uint32_t eo = c.in + c.mul + c.as, x = c.mul + c.as;
+    const uint32_t eo = on0 + c.in + c.mul + c.as, x = c.mul + c.as;
     if (opc == RV_OP_INPUT) in_rows[c.in] = eo;
     if (opc == RV_OP_MUL || opc == RV_OP_ASSERTZERO) rec_rows[x] = eo;
     if (opc == RV_OP_ASSERTZERO) {
@@ -235,9 +250,9 @@ __device__ inline int last_writer(const uint32_t* sv, const uint32_t* seg_lo, co
     }
     return a > lo ? (int)sv[a - 1] : -1;
 }
-// the producer of every operand (-1: the never-written wire), read counts, pending operands
+// the producer of every operand (-1: the never-written wire; chunk mode: -2 - w, wire w's carried row), read counts, pending operands
 __global__ __launch_bounds__(TB) void k_cd_resolve(const rv_op* ops, size_t n, const uint32_t* sv, const uint32_t* seg_lo, const uint32_t* seg_hi,
-                                                   int2* prod, uint32_t* uses, uint32_t* rem) {
+                                                   uint32_t chunk, int2* prod, uint32_t* uses, uint32_t* rem) {
     const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
     if (i >= n) return;
     const rv_op op = ops[i];
@@ -245,6 +260,10 @@ __global__ __launch_bounds__(TB) void k_cd_resolve(const rv_op* ops, size_t n, c
     int2 p = make_int2(-1, -1);
     if (nr >= 1) p.x = last_writer(sv, seg_lo, seg_hi, op.a, (uint32_t)i);
     if (nr >= 2) p.y = last_writer(sv, seg_lo, seg_hi, op.b, (uint32_t)i);
+    if (chunk) {
+        if (nr >= 1 && p.x < 0) p.x = -2 - (int)op.a;
+        if (nr >= 2 && p.y < 0) p.y = -2 - (int)op.b;
+    }
     uint32_t r = 0;
     if (p.x >= 0) atomicAdd(&uses[p.x], 1u), r++;
     if (p.y >= 0) atomicAdd(&uses[p.y], 1u), r++;
@@ -265,13 +284,15 @@ __global__ __launch_bounds__(TB) void k_cd_front0(const uint32_t* rem, size_t n,
     if (rem[i] == 0) frontier[atomicAdd(&rounds[0].y, 1u)] = (uint32_t)i;
 }
 
-// a value: x = the op that wrote its row (-1: a constant), y = (level of that row + 1) << 1 | constant bit
-__device__ inline int2 val_of(const int2* V, int p) { return p < 0 ? make_int2(-1, 0) : V[p]; }
+// a value: x = the op that wrote its row (-1: a constant; -2 - w: wire w's carried row, there before level 0),
+// y = (level of that row + 1) << 1 | constant bit
+__device__ inline int2 val_of(const int2* V, int p) { return p < 0 ? make_int2(p, 0) : V[p]; }
 __device__ inline int lvl_of(int2 v) { return (v.y >> 1) - 1; }
+__device__ inline bool is_row(int2 v) { return v.x != -1; }
 
 // step 3: one round.  rounds[r] = {first frontier slot, count}; the ops whose last pending operand this round resolves form
 // round r + 1's frontier
-__global__ __launch_bounds__(TB) void k_cd_round(uint32_t r, const rv_op* ops, const int2* prod, const uint32_t* uses, const uint32_t* cons_off,
+__global__ __launch_bounds__(TB) void k_cd_round(uint32_t r, uint32_t chunk, const rv_op* ops, const int2* prod, const uint32_t* uses, const uint32_t* cons_off,
                                                  const uint32_t* cons, uint32_t* rem, int2* V, int* glvl, uint32_t* mat, uint32_t* frontier,
                                                  uint2* rounds) {
     // the next frontier is gathered in LDS and appended with one global atomic per workgroup (65 536 appends to one counter per
@@ -305,9 +326,9 @@ __global__ __launch_bounds__(TB) void k_cd_round(uint32_t r, const rv_op* ops, c
         case RV_OP_ADD:
         case RV_OP_SUB:
             if (A.x == B.x) out = make_int2(-1, (A.y ^ B.y) & 1);       // x ^ x = 0 (or two constants)
-            else if (A.x < 0) out = make_int2(B.x, B.y ^ (A.y & 1));    // a constant plus a row: the row
-            else if (B.x < 0) out = make_int2(A.x, A.y ^ (B.y & 1));
-            else if (uses[i] == 0) out = make_int2(-1, 0);              // an unread sum is dropped
+            else if (!is_row(A)) out = make_int2(B.x, B.y ^ (A.y & 1));  // a constant plus a row: the row
+            else if (!is_row(B)) out = make_int2(A.x, A.y ^ (B.y & 1));
+            else if (!chunk && uses[i] == 0) out = make_int2(-1, 0);    // an unread sum is dropped (a chunk counts no reads)
             else {                                                      // two rows: a G_XORK
                 gl = max(lvl_of(A), lvl_of(B)) + 1;
                 out = make_int2((int)i, (gl + 1) << 1);
@@ -368,8 +389,8 @@ __global__ __launch_bounds__(TB) void k_cd_stats(const rv_op* ops, size_t n, con
         m = mat[i];
         const uint32_t opc = ops[i].opcode;
         const int2 p = prod[i];
-        if (opc == RV_OP_MUL) o = (val_of(V, p.x).x >= 0) + (val_of(V, p.y).x >= 0);
-        else if (opc == RV_OP_ASSERTZERO) o = val_of(V, p.x).x >= 0;
+        if (opc == RV_OP_MUL) o = is_row(val_of(V, p.x)) + is_row(val_of(V, p.y));
+        else if (opc == RV_OP_ASSERTZERO) o = is_row(val_of(V, p.x));
         else if (m) o = 2;
     }
     sl[threadIdx.x] = l, sg[threadIdx.x] = g, sm[threadIdx.x] = m, so[threadIdx.x] = o;
@@ -404,7 +425,7 @@ __global__ __launch_bounds__(TB) void k_cd_keys(const rv_op* ops, size_t n, cons
         uint32_t cls = 4;
         if (opc == RV_OP_MUL) {
             const int2 p = prod[i];
-            cls = (val_of(V, p.x).x >= 0 && val_of(V, p.y).x >= 0) ? 0u : 1u;
+            cls = (is_row(val_of(V, p.x)) && is_row(val_of(V, p.y))) ? 0u : 1u;
         } else if (mat[i]) {
             cls = 2;
         }
@@ -422,21 +443,27 @@ __global__ __launch_bounds__(TB) void k_cd_bounds(const uint32_t* sk, size_t n_g
     for (uint32_t k = lo; k <= hi; k++) pos[k] = (uint32_t)p;
 }
 
-// a value's row as a share row index: PRG rows first (Input / Random: m, Mul: m + 1), then the computed rows (zero row first)
-__device__ inline uint32_t row_index(const rv_op* ops, const C4* cx, const uint32_t* comp, uint32_t pad, int q) {
-    if (q < 0) return pad;
+// a value's row as a share row index: a chunk's carried rows, the PRG rows (Input / Random: m, Mul: m + 1), then the computed rows
+// (zero row first)
+__device__ inline uint32_t row_index(const rv_op* ops, const C4* cx, const uint32_t* comp, const Seeds& s, uint32_t pad, int q) {
+    if (q == -1) return s.base + pad;
+    if (q < -1) return (uint32_t)(-2 - q);
     const uint32_t opc = ops[q].opcode;
-    if (opc == RV_OP_MUL) return cx[q].m + 1;
-    if (opc == RV_OP_INPUT || opc == RV_OP_RANDOM) return cx[q].m;
-    return pad + 1 + comp[q];
+    if (opc == RV_OP_MUL) return s.base + s.m0 + cx[q].m + 1;
+    if (opc == RV_OP_INPUT || opc == RV_OP_RANDOM) return s.base + s.m0 + cx[q].m;
+    return s.base + pad + 1 + comp[q];
 }
+// the host compiler sorts a sum's rows as it names them before the final numbering: PRG rows, carried rows, computed rows
+__device__ inline uint32_t row_rank(const Seeds& s, uint32_t pad, uint32_t row) { return row < s.base ? 1u : row >= s.base + pad ? 2u : 0u; }
 __device__ inline uint32_t wave_max_u32(uint32_t v) {
     for (int s = 32; s > 0; s >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, s));
     return v;
 }
 // the gate records in (level, class, program) order, the per-level mask blocks and the online rows' levels
+// (pad: the PRG rows, whole cipher blocks; a gate with key >= 4 sits behind the chunk's materialised carried forms)
 __global__ __launch_bounds__(TB) void k_cd_gates(const uint32_t* sk, const uint32_t* sv, size_t n_gates, const rv_op* ops, const int2* prod, const int2* V,
-                                                 const C4* cx, const uint32_t* comp, uint32_t pad, Gate* gates, uint32_t* need_raw, uint32_t* on_lvl) {
+                                                 const C4* cx, const uint32_t* comp, Seeds s, uint32_t pad, Gate* gates, uint32_t* need_raw,
+                                                 uint32_t* on_lvl) {
     const size_t p = (size_t)blockIdx.x * TB + threadIdx.x;
     const bool valid = p < n_gates;
     uint32_t l = 0, need = 0;
@@ -447,57 +474,60 @@ __global__ __launch_bounds__(TB) void k_cd_gates(const uint32_t* sk, const uint3
         const C4 c = cx[i];
         const int2 pr = prod[i];
         const int2 A = val_of(V, pr.x), B = val_of(V, pr.y);
-        const uint32_t eo = c.in + c.mul + c.as, x = c.mul + c.as;
+        const uint32_t e = c.in + c.mul + c.as, x = c.mul + c.as;  // e: the online row among the piece's own
+        const uint32_t eo = s.on0 + e, m = s.m0 + c.m, zero = s.base + pad;
         Gate g;
-        g.dst = 0, g.m = 0, g.eo = 0, g.ep = 0, g.x = 0;
-        for (int k = 0; k < RV_LIN_K; k++) g.a[k] = pad, g.b[k] = pad;
+        g.dst = s.base, g.m = s.base, g.eo = 0, g.ep = 0, g.x = 0;  // (the host compiler's unused fields: PRG row 0 after the carried rows)
+        for (int k = 0; k < RV_LIN_K; k++) g.a[k] = zero, g.b[k] = zero;
         switch (op.opcode) {
         case RV_OP_INPUT:
             g.op = G_INPUT;
-            g.m = g.dst = c.m;
+            g.m = g.dst = s.base + m;
             g.eo = eo;
             g.x = c.in;
-            need = c.m / 128 + 1;
-            on_lvl[eo] = l;
+            need = m / 128 + 1;
+            on_lvl[e] = l;
             break;
         case RV_OP_RANDOM:
             g.op = G_RANDOM;
-            g.m = g.dst = c.m;
-            need = c.m / 128 + 1;
+            g.m = g.dst = s.base + m;
+            need = m / 128 + 1;
             break;
         case RV_OP_MUL: {
-            const uint32_t na = A.x >= 0, nb = B.x >= 0;
+            const uint32_t na = is_row(A), nb = is_row(B);
             g.op = G_MUL | na << 8 | nb << 12 | (uint32_t)(A.y & 1) << 16 | (uint32_t)(B.y & 1) << 17;
-            if (na) g.a[0] = row_index(ops, cx, comp, pad, A.x);
-            if (nb) g.b[0] = row_index(ops, cx, comp, pad, B.x);
-            g.m = c.m;
-            g.dst = c.m + 1;
+            if (na) g.a[0] = row_index(ops, cx, comp, s, pad, A.x);
+            if (nb) g.b[0] = row_index(ops, cx, comp, s, pad, B.x);
+            g.m = s.base + m;
+            g.dst = s.base + m + 1;
             g.eo = eo;
-            g.ep = c.mul;
+            g.ep = s.pre0 + c.mul;
             g.x = x;
-            need = (c.m + 1) / 128 + 1;
-            on_lvl[eo] = l;
+            need = (m + 1) / 128 + 1;
+            on_lvl[e] = l;
             break;
         }
         case RV_OP_ASSERTZERO: {
-            const uint32_t na = A.x >= 0;
+            const uint32_t na = is_row(A);
             g.op = G_ASSERT | na << 8 | (uint32_t)(A.y & 1) << 16;
-            if (na) g.a[0] = row_index(ops, cx, comp, pad, A.x);
+            if (na) g.a[0] = row_index(ops, cx, comp, s, pad, A.x);
             g.eo = eo;
             g.x = x;
-            on_lvl[eo] = l;
+            on_lvl[e] = l;
             break;
         }
-        default: {  // a materialised Add / Sub: its two rows in ascending order
-            const uint32_t ra = row_index(ops, cx, comp, pad, A.x), rb = row_index(ops, cx, comp, pad, B.x);
+        default: {  // a materialised Add / Sub: its two rows in the host compiler's order
+            const uint32_t ra = row_index(ops, cx, comp, s, pad, A.x), rb = row_index(ops, cx, comp, s, pad, B.x);
+            const uint32_t ka = row_rank(s, pad, ra), kb = row_rank(s, pad, rb);
+            const bool a_first = ka < kb || (ka == kb && ra < rb);
             g.op = G_XORK | 2u << 8 | (uint32_t)((A.y ^ B.y) & 1) << 16;
-            g.a[0] = min(ra, rb);
-            g.a[1] = max(ra, rb);
-            g.dst = pad + 1 + comp[i];
+            g.a[0] = a_first ? ra : rb;
+            g.a[1] = a_first ? rb : ra;
+            g.dst = zero + 1 + comp[i];
             break;
         }
         }
-        gates[p] = g;
+        gates[p + (sk[p] >= 4u ? s.n_wbmat : 0u)] = g;
     }
     // a wavefront's gates mostly share a level: one atomic for them
     const uint32_t l0 = (uint32_t)__shfl((int)l, 0);
@@ -507,6 +537,55 @@ __global__ __launch_bounds__(TB) void k_cd_gates(const uint32_t* sk, const uint3
     } else if (valid && need) {
         atomicMax(&need_raw[l], need);
     }
+}
+// step 6 (chunk mode).  Per wire: m = the piece wrote it, mul = its final form still reads a carried row (materialised first: two wires
+// swapped by a piece must not race), as = the final form has a row (else it is a constant); lastw = the op that wrote it last.
+constexpr uint32_t NO_WRITER = 0xFFFFFFFFu;
+__global__ __launch_bounds__(TB) void k_cd_wb_flags(const uint32_t* sv, const uint32_t* seg_lo, const uint32_t* seg_hi, uint32_t W, const int2* V, C4* fl,
+                                                    uint32_t* lastw) {
+    const size_t w = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (w >= W) return;
+    C4 f{0, 0, 0, 0};
+    uint32_t q = NO_WRITER;
+    if (seg_hi[w] > seg_lo[w]) {
+        q = sv[seg_hi[w] - 1];
+        const int2 v = V[q];
+        f.m = 1;
+        f.mul = v.x < -1;
+        f.as = is_row(v);
+    }
+    fl[w] = f;
+    lastw[w] = q;
+}
+// fx: the exclusive scan of the flags.  The materialised carried forms take the computed rows after the ops' own (n_mat of them) and
+// level 0's class 3 (from *pos3; null: the piece has no op gate); the write-backs follow every other gate (from wb_at).
+__global__ __launch_bounds__(TB) void k_cd_wb_gates(const uint32_t* lastw, const C4* fx, uint32_t W, const rv_op* ops, const int2* V, const C4* cx,
+                                                    const uint32_t* comp, Seeds s, uint32_t pad, uint32_t n_mat, const uint32_t* pos3, uint32_t wb_at,
+                                                    Gate* gates) {
+    const size_t w = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (w >= W) return;
+    const uint32_t q = lastw[w];
+    if (q == NO_WRITER) return;
+    const C4 r = fx[w];
+    const int2 v = V[q];
+    const uint32_t zero = s.base + pad;
+    Gate g;
+    g.op = G_XORK, g.dst = 0, g.m = s.base, g.eo = 0, g.ep = 0, g.x = 0;
+    for (int k = 0; k < RV_LIN_K; k++) g.a[k] = zero, g.b[k] = zero;
+    uint32_t row = zero, n = 0, c = (uint32_t)(v.y & 1);
+    if (v.x < -1) {
+        g.op = G_XORK | 1u << 8 | c << 16;
+        g.a[0] = (uint32_t)(-2 - v.x);
+        g.dst = zero + 1 + n_mat + r.mul;
+        gates[(pos3 ? *pos3 : 0u) + r.mul] = g;
+        row = g.dst, n = 1, c = 0;
+    } else if (v.x >= 0) {
+        row = row_index(ops, cx, comp, s, pad, v.x), n = 1;
+    }
+    g.op = G_XORK | n << 8 | c << 16;
+    g.a[0] = row;
+    g.dst = (uint32_t)w;
+    gates[wb_at + r.m] = g;
 }
 // level_done_on[l] = online rows e whose prefix maximum of levels is <= l; pm = exclusive prefix maximum of on_lvl (n_on + 1 entries)
 __global__ __launch_bounds__(TB) void k_cd_done_on(const uint32_t* pm, const uint32_t* on_lvl, size_t n_on, uint32_t n_levels, uint32_t* done_on) {
@@ -578,12 +657,23 @@ hipError_t radix_sort(Scratch& S, hipStream_t st, uint32_t* k[2], uint32_t* v[2]
 }  // namespace
 
 int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, bool keep_wires,
-                       int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps) {
-    (void)z64_wires;  // (a Z64 op in the list is what sends a program to the host; the Z64 wire count alone does not)
-    if (keep_wires || force_lazy_k || getenv("RV_LAZY_K") || n_ops == 0 || n_ops >= (1u << 28) || gf2_wires >= (1u << 31))
+                       int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps, const ChunkStart* chunk) {
+    // (a Z64 op in the list is what sends a program to the host; the Z64 wire count alone does not)
+    if (keep_wires || force_lazy_k || getenv("RV_LAZY_K") || (n_ops == 0 && !chunk) || n_ops >= (1u << 28) || gf2_wires >= (1u << 31) ||
+        (chunk && gf2_wires >= (1u << 30)))  // (a chunk names wire w's carried row -2 - w, below the host compiler's CARRY flag bit)
         return RV_COMPILE_FALLBACK;
     const size_t n = n_ops;
     const uint32_t W = (uint32_t)gf2_wires;
+    const uint64_t LIM = 0xFFFFFFFFull - 512;
+    Seeds seeds{0, 0, 0, 0, 0, 0};
+    if (chunk) {
+        if (chunk->mask_phase >= 128 || chunk->on0 > LIM || chunk->pre0 > LIM || z64_wires > LIM) return RV_COMPILE_FALLBACK;
+        seeds.chunk = 1;
+        seeds.base = W;
+        seeds.m0 = chunk->mask_phase;
+        seeds.on0 = (uint32_t)chunk->on0;
+        seeds.pre0 = (uint32_t)chunk->pre0;
+    }
     Scratch S(A, st);
     hipEvent_t ev[6] = {};
     const bool timed = laps != nullptr;
@@ -615,7 +705,7 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     C4* cx = S.get<C4>(n + 1);
     uint32_t* kbuf[2] = {S.get<uint32_t>(n), S.get<uint32_t>(n)};
     uint32_t* vbuf[2] = {S.get<uint32_t>(n), S.get<uint32_t>(n)};
-    uint32_t* d_small = S.get<uint32_t>(64);  // [0] error flag, [8..12) C4 totals, [16..24) DevStats
+    uint32_t* d_small = S.get<uint32_t>(64);  // [0] error flag, [8..12) C4 totals, [16..24) DevStats, [24..28) the write-back totals
     CDNEED(cx && kbuf[0] && kbuf[1] && vbuf[0] && vbuf[1] && d_small);
     C4* d_tot = (C4*)(d_small + 8);
     DevStats* d_stats = (DevStats*)(d_small + 16);
@@ -623,7 +713,7 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     k_cd_classify<<<gb, TB, 0, st>>>(d_ops, n, W, cx, kbuf[0], vbuf[0], d_small);
     CDCHK(hipGetLastError());
     CDCHK((scan_excl<C4, SumC4>(S, st, cx, cx, n, d_tot)));
-    uint32_t h_small[24];
+    uint32_t h_small[28];
     CDCHK(hipMemcpyAsync(h_small, d_small, sizeof h_small, hipMemcpyDeviceToHost, st));
     CDCHK(hipStreamSynchronize(st));
     if (h_small[0]) return RV_COMPILE_FALLBACK;  // an op the device path does not take, or an op-list error: the host compiler reports it
@@ -643,7 +733,7 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     uint32_t* as_rec = S.get<uint32_t>(tot.as);
     uint64_t* as_op = S.get<uint64_t>(tot.as);
     CDNEED(as_rec && as_op);
-    k_cd_ordinals<<<gb, TB, 0, st>>>(d_ops, n, cx, rec_rows, in_rows, as_rec, as_op);
+    k_cd_ordinals<<<gb, TB, 0, st>>>(d_ops, n, cx, seeds.on0, rec_rows, in_rows, as_rec, as_op);
     CDCHK(hipGetLastError());
     mark(1);
     // ---- 2. the last writer of every read ----
@@ -659,7 +749,7 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     CDCHK(hipMemsetAsync(seg_hi, 0, std::max<size_t>(W, 1) * 4, st));
     CDCHK(hipMemsetAsync(uses, 0, (n + 1) * 4, st));
     k_cd_segs<<<gb, TB, 0, st>>>(kbuf[which], n, W, seg_lo, seg_hi);
-    k_cd_resolve<<<gb, TB, 0, st>>>(d_ops, n, vbuf[which], seg_lo, seg_hi, prod, uses, rem);
+    k_cd_resolve<<<gb, TB, 0, st>>>(d_ops, n, vbuf[which], seg_lo, seg_hi, seeds.chunk, prod, uses, rem);
     CDCHK(hipGetLastError());
     uint32_t* cons_off = S.get<uint32_t>(n + 1);
     uint32_t* cursor = S.get<uint32_t>(n);
@@ -688,7 +778,7 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     while (!done) {
         if (r >= max_rounds) return RV_COMPILE_FALLBACK;  // (the cap: a chain of ops this deep compiles on the host)
         const uint32_t e = std::min(r + batch, max_rounds);
-        for (; r < e; r++) k_cd_round<<<round_blocks, TB, 0, st>>>(r, d_ops, prod, uses, cons_off, cons, rem, V, glvl, mat, frontier, rounds);
+        for (; r < e; r++) k_cd_round<<<round_blocks, TB, 0, st>>>(r, seeds.chunk, d_ops, prod, uses, cons_off, cons, rem, V, glvl, mat, frontier, rounds);
         CDCHK(hipGetLastError());
         uint2 nxt;
         CDCHK(hipMemcpyAsync(&nxt, rounds + r, sizeof nxt, hipMemcpyDeviceToHost, st));
@@ -702,25 +792,46 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     if (laps) laps->rounds = r;
     k_cd_stats<<<gb, TB, 0, st>>>(d_ops, n, prod, V, glvl, mat, d_stats);
     CDCHK(hipGetLastError());
+    // ---- 6a. (chunk mode) the wires the piece wrote, while the writers sort is still in place ----
+    C4* wfl = nullptr;
+    uint32_t* lastw = nullptr;
+    if (chunk) {
+        wfl = S.get<C4>(W);
+        lastw = S.get<uint32_t>(W);
+        CDNEED(wfl && lastw);
+        k_cd_wb_flags<<<blocks(W, TB), TB, 0, st>>>(vbuf[which], seg_lo, seg_hi, W, V, wfl, lastw);
+        CDCHK(hipGetLastError());
+        CDCHK((scan_excl<C4, SumC4>(S, st, wfl, wfl, W, (C4*)(d_small + 24))));
+    }
     // d_stats->max_level starts at 0 (memset): max_level + 1 levels when there are gates
-    DevStats hs;
-    CDCHK(hipMemcpyAsync(&hs, d_stats, sizeof hs, hipMemcpyDeviceToHost, st));
+    CDCHK(hipMemcpyAsync(h_small, d_small, sizeof h_small, hipMemcpyDeviceToHost, st));
     CDCHK(hipStreamSynchronize(st));
+    DevStats hs;
+    memcpy(&hs, h_small + 16, sizeof hs);
     mark(3);
-    const uint64_t n_gates = hs.n_gates;
-    const uint32_t n_levels = n_gates ? (uint32_t)hs.max_level + 1 : 0;
+    const uint64_t n_gates_ops = hs.n_gates;
+    const uint32_t n_levels_ops = n_gates_ops ? (uint32_t)hs.max_level + 1 : 0;
+    // the write-back level: one G_XORK per written wire behind every other level; the carried forms it reads are level 0's
+    const uint32_t n_wb = chunk ? h_small[24] : 0, n_wbmat = chunk ? h_small[25] : 0, n_wbrow = chunk ? h_small[26] : 0;
+    seeds.n_wbmat = n_wbmat;
+    const uint32_t wb_level = std::max<uint32_t>(n_levels_ops, n_wbmat ? 1u : 0u);
+    const uint32_t n_levels = n_wb ? wb_level + 1 : n_levels_ops;
+    const uint64_t n_gates = n_gates_ops + n_wbmat + n_wb;
     // the K = 1 compile is final unless the circuit is deep and narrow (compile_ops_seq): those go to the host compiler
-    if (n_levels && lazy_forms_pay(n_levels, n_gates)) return RV_COMPILE_FALLBACK;
-    const uint64_t n_masks_pad = ((uint64_t)tot.m + 127) / 128 * 128;
-    const uint64_t LIM = 0xFFFFFFFFull - 512;
-    if (n_masks_pad + 1 + hs.n_mat > LIM || n_masks_pad / 128 > RV_MAX_CTR_BLOCKS || (uint64_t)n_levels * 5 + 1 >= (1ull << 32))
+    // (a chunk is compiled once, at K = 1, whatever its shape)
+    if (!chunk && n_levels && lazy_forms_pay(n_levels, n_gates)) return RV_COMPILE_FALLBACK;
+    const uint64_t n_masks = (uint64_t)seeds.m0 + tot.m;
+    const uint64_t n_masks_pad = (n_masks + 127) / 128 * 128;
+    const uint64_t n_comp = 1 + (uint64_t)hs.n_mat + n_wbmat;
+    if ((uint64_t)W + n_masks_pad + n_comp > LIM || n_masks_pad / 128 > RV_MAX_CTR_BLOCKS || (uint64_t)n_levels * 5 + 1 >= (1ull << 32) ||
+        n_comp > LIM / 2 || 1 + (uint64_t)W + n > LIM || (uint64_t)seeds.on0 + n_on > LIM || (uint64_t)seeds.pre0 + tot.mul > LIM)
         return RV_COMPILE_FALLBACK;
     // ---- 4. computed rows ----
     uint32_t* comp = S.get<uint32_t>(n + 1);
     CDNEED(comp);
     CDCHK((scan_excl<uint32_t, SumU32>(S, st, mat, comp, n + 1, nullptr)));
     // ---- 5. tables ----
-    const uint32_t n_buckets = n_levels * 5;
+    const uint32_t n_buckets = n_levels_ops * 5;  // (of the ops' gates: the write-back gates do not go through the sort)
     k_cd_keys<<<gb, TB, 0, st>>>(d_ops, n, prod, V, glvl, mat, n_buckets, kbuf[0], vbuf[0]);
     CDCHK(hipGetLastError());
     CDCHK(radix_sort(S, st, kbuf, vbuf, n, bit_len(n_buckets), &which));
@@ -736,10 +847,13 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     CDNEED(pos && need_raw && on_lvl && pm && done_on);
     CDCHK(hipMemsetAsync(need_raw, 0, std::max<size_t>(n_levels, 1) * 4, st));
     CDCHK(hipMemsetAsync(on_lvl + n_on, 0, 4, st));
-    k_cd_bounds<<<blocks(n_gates + 1, TB), TB, 0, st>>>(kbuf[which], n_gates, n_buckets, pos);
-    if (n_gates)
-        k_cd_gates<<<blocks(n_gates, TB), TB, 0, st>>>(kbuf[which], vbuf[which], n_gates, d_ops, prod, V, cx, comp, (uint32_t)n_masks_pad, gates,
-                                                       need_raw, on_lvl);
+    k_cd_bounds<<<blocks(n_gates_ops + 1, TB), TB, 0, st>>>(kbuf[which], n_gates_ops, n_buckets, pos);
+    if (n_gates_ops)
+        k_cd_gates<<<blocks(n_gates_ops, TB), TB, 0, st>>>(kbuf[which], vbuf[which], n_gates_ops, d_ops, prod, V, cx, comp, seeds, (uint32_t)n_masks_pad,
+                                                           gates, need_raw, on_lvl);
+    if (n_wb)
+        k_cd_wb_gates<<<blocks(W, TB), TB, 0, st>>>(lastw, wfl, W, d_ops, V, cx, comp, seeds, (uint32_t)n_masks_pad, hs.n_mat, n_buckets >= 3 ? pos + 3 : nullptr,
+                                                    (uint32_t)(n_gates_ops + n_wbmat), gates);
     CDCHK(hipGetLastError());
     CDCHK((scan_excl<uint32_t, MaxU32>(S, st, on_lvl, pm, n_on + 1, nullptr)));
     k_cd_done_on<<<blocks(n_on + 1, TB), TB, 0, st>>>(pm, on_lvl, n_on, n_levels, done_on);
@@ -770,38 +884,54 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     cc.level_range.assign(n_levels, LevelRange{});
     cc.level_need_blocks.assign(n_levels, 0);
     uint32_t need = 0;
+    // first gate with key >= k: the ops' gates (h_pos), the materialised carried forms (key 3) and the write-backs (the last level's key 3)
+    auto first_at = [&](size_t k) {
+        uint64_t v = k <= n_buckets ? h_pos[k] : n_gates_ops;
+        if (k >= 4) v += n_wbmat;
+        if (n_wb && k >= (size_t)wb_level * 5 + 4) v += n_wb;
+        return (uint32_t)v;
+    };
     for (uint32_t l = 0; l < n_levels; l++) {
-        const uint32_t* e = &h_pos[(size_t)l * 5];
+        uint32_t e[6];
+        for (int j = 0; j < 6; j++) e[j] = first_at((size_t)l * 5 + j);
         cc.level_start[l] = e[0];
         cc.level_range[l] = LevelRange{e[0], e[1], e[2], e[3], e[4], e[5]};
         need = std::max(need, h_need[l]);
         cc.level_need_blocks[l] = need;
+        cc.level_done_on[l] += seeds.on0;  // (the carried rows in front are complete before level 0)
     }
     cc.level_start[n_levels] = (uint32_t)n_gates;
     cc.level_start64.assign(n_levels + 1, 0);
     const uint64_t randoms = (uint64_t)tot.m - tot.in - 2ull * tot.mul;
-    cc.n_ssa = 1 + n - tot.as;
-    cc.n_masks = tot.m;
+    cc.n_ssa = 1 + (chunk ? (uint64_t)W : 0) + n - tot.as;
+    cc.n_masks = n_masks;
     cc.n_masks_pad = n_masks_pad;
-    cc.n_rows = n_masks_pad + 1 + hs.n_mat;
-    cc.n_on = n_on;
-    cc.n_pre = tot.mul;
+    cc.n_rows = (chunk ? (uint64_t)W : 0) + n_masks_pad + n_comp;
+    cc.n_on = (chunk ? chunk->on0 : 0) + n_on;
+    cc.n_pre = (chunk ? chunk->pre0 : 0) + tot.mul;
     cc.n_in = tot.in;
     cc.n_rec = n_rec;
     cc.n_random_or_recon = randoms;
     cc.n_user_random = randoms;
-    cc.row_prg_base = 0;
-    cc.zero_row = n_masks_pad;
+    cc.row_prg_base = chunk ? W : 0;
+    cc.zero_row = cc.row_prg_base + n_masks_pad;
+    if (chunk) {  // (the Z64 side of a GF(2) piece: its carried slots and counters, untouched)
+        cc.n_ssa64 = 1 + z64_wires;
+        cc.n_masks64 = chunk->mask64_phase;
+        cc.on_words64 = chunk->on_words64_0;
+        cc.pre_words64 = chunk->pre_words64_0;
+    }
     rv_circuit_info& info = cc.info;
     info.n_ops = n;
     info.gf2_inputs = tot.in;
     info.gf2_muls = tot.mul;
     info.gf2_asserts = tot.as;
-    info.gf2_linear = randoms + hs.n_mat;
-    info.gf2_masks = tot.m;
+    info.gf2_linear = randoms + hs.n_mat + n_wbmat + n_wb;
+    info.gf2_masks = n_masks;
+    info.z64_masks = cc.n_masks64;
     info.levels = n_levels;
-    info.gf2_operand_rows = hs.operand_rows;
-    info.gf2_rows_written = hs.n_mat;
+    info.gf2_operand_rows = hs.operand_rows + n_wbmat + n_wbrow;
+    info.gf2_rows_written = (uint64_t)hs.n_mat + n_wbmat + n_wb;
     if (laps) {
         float ms[5] = {0, 0, 0, 0, 0};
         for (int k = 0; k < 5; k++) (void)hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);

@@ -17,6 +17,8 @@ struct rv_eval_stream {
     size_t max_chunk_ops = (size_t)1 << 18;
     int sticky = RV_OK;  // first error: only abort from here on
     bool finished = false;
+    uint32_t compile_flags = 0;  // rv_eval_stream_set_compile_flags (the context's at the begin): RV_COMPILE_DEVICE, as rv_stream's
+    bool fed = false;
     uint32_t* d_val = nullptr;  // [rows_cap][W]
     size_t rows_cap = 0;
     uint64_t* d_v64 = nullptr;  // [ssa64_cap][B]
@@ -65,6 +67,7 @@ static int eval_stream_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wire
     E->gf2_wires = gf2_wires;
     E->B = batch;
     E->W = W;
+    E->compile_flags = ctx->compile_flags & RV_COMPILE_DEVICE;
     if (max_chunk_ops) E->max_chunk_ops = max_chunk_ops;
     int rc;
     E->rows_cap = std::max<size_t>(gf2_wires, 1);
@@ -89,6 +92,12 @@ static int eval_stream_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wire
 
 extern "C" int rv_eval_stream_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch, size_t max_chunk_ops, rv_eval_stream** out) {
     return guarded([&] { return eval_stream_begin_impl(ctx, z64_wires, gf2_wires, batch, max_chunk_ops, out); });
+}
+
+extern "C" int rv_eval_stream_set_compile_flags(rv_eval_stream* E, uint32_t flags) {
+    if (!E || (flags & ~RV_COMPILE_DEVICE) || E->fed) return RV_E_ARG;
+    E->compile_flags = flags;
+    return RV_OK;
 }
 
 // value rows / SSA slots for a chunk: a larger block, the carried prefix copied over on the stream (the old block goes back to the arena;
@@ -223,6 +232,7 @@ static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, size_t n_o
     if (!E) return RV_E_ARG;
     if (E->sticky) return E->sticky;
     if (E->finished || (n_ops && !ops) || (n_gf2 && !wit_gf2) || (n_z64 && !wit_z64)) return E->sticky = RV_E_ARG;
+    E->fed = true;
     HIPCHK(hipSetDevice(E->ctx->device));
     const std::vector<size_t> cut = stream_cuts(n_ops, E->max_chunk_ops);  // (the streaming prover's rule)
     const size_t n_pieces = cut.size() - 1;
@@ -231,14 +241,24 @@ static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, size_t n_o
     // the pieces are compiled ahead on worker threads and run in order (piece_pipe.h)
     const unsigned n_threads = (unsigned)std::min<size_t>(eval_stream_threads(), n_pieces);
     std::vector<std::unique_ptr<Compiled>> pieces(n_pieces);
+    const bool device = (E->compile_flags & RV_COMPILE_DEVICE) != 0;
+    const ChunkStart cs;  // (values do not depend on mask phases or transcript offsets)
     PiecePipe pipe(n_pieces, n_threads, RV_E_NOMEM, [&](size_t i) {
-        ChunkStart cs;  // (values do not depend on mask phases or transcript offsets)
+        // (RV_COMPILE_DEVICE: an all-GF(2) piece stays empty here -- the main thread compiles it on the GPU right before it runs)
+        if (device && piece_all_gf2(ops + cut[i], cut[i + 1] - cut[i])) return (int)RV_OK;
         pieces[i].reset(new Compiled());
         return compile_ops(ops + cut[i], cut[i + 1] - cut[i], E->z64_wires, E->gf2_wires, *pieces[i], &cs);
     });
     int rc = RV_OK;
     for (size_t i = 0; i < n_pieces && !rc; i++) {
         rc = pipe.wait(i);
+        if (!rc && !pieces[i]) {
+            // (the piece comes back to the host whole: the chunk's arrays go up in one block with its witness, eval_stream_chunk)
+            pieces[i].reset(new Compiled());
+            const int rd = compile_chunk_on_device(E->ctx, ops + cut[i], cut[i + 1] - cut[i], E->z64_wires, E->gf2_wires, cs, *pieces[i], nullptr);
+            if (rd == RV_OK) g_stream_device_chunks.fetch_add(1, std::memory_order_relaxed);
+            rc = rd == RV_COMPILE_FALLBACK ? compile_ops(ops + cut[i], cut[i + 1] - cut[i], E->z64_wires, E->gf2_wires, *pieces[i], &cs) : rd;
+        }
         if (!rc) rc = eval_stream_chunk(E, *pieces[i], first_op + cut[i], wit_gf2, n_gf2, wit_z64, n_z64, &u2, &u64);
         pieces[i].reset();  // (host memory of the compiled piece: freed here, on the main thread, while the GPU runs it)
         pipe.consumed(i, rc);

@@ -179,6 +179,10 @@ struct rv_stream {
     static constexpr uint32_t R = RV_TOTAL_REPS, NQ = RV_TOTAL_REPS / 4;
     int pass = 1;
     int sticky = RV_OK;  // first error: the stream is dead afterwards
+    // rv_stream_set_compile_flags (the context's when the stream began): RV_COMPILE_DEVICE = every all-GF(2) piece is compiled by the
+    // chunk-mode device compiler, on the context's stream right before it runs; what that hands back is compiled on the host
+    uint32_t compile_flags = 0;
+    bool fed = false;  // a feed has begun: the flags are fixed
     size_t max_chunk_ops = (size_t)1 << 18;  // (10^7-gate circuit: 179 ms with 2^18, 233 ms with 2^20: a piece is compiled by one thread)
     // per-stream device state
     uint8_t *d_seeds = nullptr, *d_keys = nullptr, *d_rkbytes = nullptr;
@@ -390,6 +394,7 @@ static int stream_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, co
     S->ctx = ctx;
     S->z64_wires = z64_wires;
     S->gf2_wires = gf2_wires;
+    S->compile_flags = ctx->compile_flags & RV_COMPILE_DEVICE;
     if (max_chunk_ops) S->max_chunk_ops = std::max<size_t>(max_chunk_ops, 1024);
     if (const char* e = getenv("RV_STREAM_KEEP_MB")) {
         S->keep_cap = (uint64_t)std::max(atoll(e), 0ll) << 20;
@@ -439,6 +444,13 @@ static int stream_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, co
 
 extern "C" int rv_stream_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, const uint8_t* seeds, size_t max_chunk_ops, rv_stream** out) {
     return guarded([&] { return stream_begin_impl(ctx, z64_wires, gf2_wires, seeds, max_chunk_ops, out); });
+}
+
+extern "C" int rv_stream_set_compile_flags(rv_stream* S, uint32_t flags) {
+    if (!S || (flags & ~RV_COMPILE_DEVICE) || S->fed) return RV_E_ARG;
+    S->compile_flags = flags;
+    for (rv_stream* m : S->bat) m->compile_flags = flags;  // (a batch: the feed's host-side state is its first running member's)
+    return RV_OK;
 }
 
 // wire store large enough for the chunk; the carried region survives a reallocation
@@ -586,6 +598,19 @@ struct WitnessRows {
 // The host side of a chunk: levelising 10^6 ops takes ~0.1 s on one core, ~200 times the chunk's GPU work, and needs nothing of the
 // stream's state but the two ShareGen phases (transcript offsets are added afterwards, relocate_chunk).  A feed of several chunks
 // therefore compiles them on worker threads ahead of the GPU (stream_feed_impl).
+// where the next chunk of the stream starts: the ShareGen phases and the carried events in front of its own (pass 1 and the verifier:
+// the unhashed tails; pass 2: the items short of a byte)
+static ChunkStart stream_chunk_start(const rv_stream* S) {
+    ChunkStart cs;
+    cs.mask_phase = (uint32_t)(S->run.masks % 128);
+    cs.mask64_phase = (uint32_t)(S->run.masks64 % 2);
+    if (S->pass != 2)
+        set_carried(cs, S->tr[TR_PRE].tail, S->tr[TR_ON].tail, S->tr[TR_PRE64].tail, S->tr[TR_ON64].tail);
+    else
+        set_carried(cs, S->pend_pre, S->pend_rec + S->pend_in, 0, 0);
+    return cs;
+}
+
 struct ChunkRun {
     static constexpr uint32_t R = rv_stream::R, NQ = rv_stream::NQ;
     using Clock = std::chrono::steady_clock;
@@ -633,14 +658,7 @@ struct ChunkRun {
         : S(proofs_[0]), proofs(proofs_), c(c_), digest(digest_), n_ops(n_ops_), wit(wit_), ctx(S->ctx), st(ctx->stream), p1(S->pass == 1), ver(S->pass == 3),
           hashing(p1 || ver), batched(proofs_.size() > 1), cc(c_->cc), first_op(S->run.n_ops), has64(!cc.gates64.empty()),
           first_block(S->run.masks / 128), n_blocks(cc.n_masks_pad / 128), first_block64(S->run.masks64 / 2), n_blocks64((cc.n_masks64 + 1) / 2),
-          pbs(proofs_.size()), pps(proofs_.size()), pp64s(proofs_.size()), cp(st, !batched) {
-        cs.mask_phase = (uint32_t)(S->run.masks % 128);
-        cs.mask64_phase = (uint32_t)(S->run.masks64 % 2);
-        if (hashing)
-            set_carried(cs, S->tr[TR_PRE].tail, S->tr[TR_ON].tail, S->tr[TR_PRE64].tail, S->tr[TR_ON64].tail);
-        else
-            set_carried(cs, S->pend_pre, S->pend_rec + S->pend_in, 0, 0);
-    }
+          cs(stream_chunk_start(S)), pbs(proofs_.size()), pps(proofs_.size()), pp64s(proofs_.size()), cp(st, !batched) {}
 
     // carried: the transcript offsets c's arrays already hold (zero for a fresh compile, pass 1's for a chunk out of the cache)
     int run(const ChunkStart& carried) {
@@ -1200,6 +1218,7 @@ struct FeedPiece {
     uint64_t digest = 0;
     ChunkStart carried;         // the offsets c's arrays hold
     bool kept = false;          // pass 2: pass 1 kept this piece's transcripts (rv_stream::Kept) -- nothing of it is uploaded
+    bool device = false;        // RV_COMPILE_DEVICE, all GF(2), not in pass 1's cache: c stays null until the main thread compiles it on the GPU
 };
 
 // A piece ready to run: pass 1's cached compile if its digest matches the ops fed now, else a fresh compile -- at the offsets the piece
@@ -1213,6 +1232,9 @@ static int prepare_piece(const rv_stream* S, const rv_op* ops, uint64_t first_op
         p.c = nullptr;
     }
     p.digest = dg;
+    // (a piece whose transcripts pass 1 kept is compiled on the host as ever: ChunkRun::plan decides whether it runs at all)
+    p.device = !p.c && !p.kept && (S->compile_flags & RV_COMPILE_DEVICE) && piece_all_gf2(ops + p.at, p.n);
+    if (p.device) return RV_OK;
     if (!p.c) {
         p.carried = p.predicted ? p.want : ChunkStart();
         if (int rc = stream_compile_piece(S, ops + p.at, p.n, p.ph2, p.ph64, &p.c, p.predicted ? &p.want : nullptr)) return rc;
@@ -1349,6 +1371,7 @@ static int stream_feed_impl(rv_stream* H, const rv_op* ops, size_t n_ops, const 
     if (proofs.empty()) return RV_OK;  // (a verifier stream whose proof has the wrong shape: the answer is already `false`)
     rv_stream* S = proofs[0];          // (the host-side state of the feed: compiled-chunk cache, counts, pass)
     if (S->sticky) return H->sticky = S->sticky;
+    H->fed = S->fed = true;
     HIPCHK(hipSetDevice(S->ctx->device));
     const bool stats = getenv("RV_STREAM_STATS") != nullptr;
     using Clock = std::chrono::steady_clock;
@@ -1380,7 +1403,8 @@ static int stream_feed_impl(rv_stream* H, const rv_op* ops, size_t n_ops, const 
                    NS ? PiecePipe::Pick(stage_pick) : PiecePipe::Pick(), stage);
     if (stats) fprintf(stderr, "[rv stream] feed set up (cuts, counts, cached pieces, %u workers) in %.3f s\n", n_threads, secs(t_feed0, Clock::now()));
     int rc = RV_OK;
-    double t_wait = 0, t_run = 0;
+    double t_wait = 0, t_run = 0, dev_laps[3] = {0, 0, 0};
+    size_t n_dev = 0;
     for (size_t i = 0; i < n_pieces && !rc; i++) {
         FeedPiece& p = pieces[i];
         const auto t0 = Clock::now();
@@ -1388,6 +1412,30 @@ static int stream_feed_impl(rv_stream* H, const rv_op* ops, size_t n_ops, const 
         rv_circuit* c = p.c;
         p.c = nullptr;
         if (rc) rv_circuit_destroy(c);
+        if (!rc && !c && p.device) {
+            // the device compile, here and in order on the context's stream: at the offsets the piece runs at (no relocation), its gate
+            // records and ordinal tables left in HBM for circuit_upload
+            const ChunkStart at = stream_chunk_start(S);
+            c = new rv_circuit();
+            c->ctx = S->ctx;
+            DevCompileKeep kept;
+            const int rd = compile_chunk_on_device(S->ctx, ops + p.at, p.n, S->z64_wires, S->gf2_wires, at, c->cc, &kept, stats ? dev_laps : nullptr);
+            if (rd == RV_OK) {
+                c->d_gates = kept.d_gates, c->d_rec_rows = kept.d_rec_rows, c->d_in_rows = kept.d_in_rows;
+                c->dev_compiled = true;
+                p.carried = at;
+                p.ph2 = at.mask_phase, p.ph64 = at.mask64_phase;
+                g_stream_device_chunks.fetch_add(1, std::memory_order_relaxed);
+                n_dev++;
+            } else {
+                delete c;
+                c = nullptr;
+                p.carried = ChunkStart();
+                p.ph2 = at.mask_phase, p.ph64 = at.mask64_phase;
+                // (handed back -- an op-list error, a chain deeper than the round cap: the host compiler's result or error code)
+                rc = rd == RV_COMPILE_FALLBACK ? stream_compile_piece(S, ops + p.at, p.n, p.ph2, p.ph64, &c) : rd;
+            }
+        }
         if (!rc && (p.ph2 != (uint32_t)(S->run.masks % 128) || p.ph64 != (uint32_t)(S->run.masks64 % 2))) {
             // (cannot happen while count_masks agrees with the compiler; compile again in place rather than trust it)
             rv_circuit_destroy(c);
@@ -1411,6 +1459,9 @@ static int stream_feed_impl(rv_stream* H, const rv_op* ops, size_t n_ops, const 
     if (stats)
         fprintf(stderr, "[rv stream] feed of %zu pieces on %u threads: %.3f s waiting for compiled pieces, %.3f s running them\n", n_pieces, n_threads,
                 t_wait, t_run);
+    if (stats && n_dev)
+        fprintf(stderr, "[rv stream] device compile of %zu pieces (inside the waiting time): op upload %.3f s, compile %.3f s, host copy %.3f s\n", n_dev,
+                dev_laps[0], dev_laps[1], dev_laps[2]);
     if (rc) S->sticky = H->sticky = rc;
     return rc;
 }

@@ -33,6 +33,7 @@ class Context:
         self.handle = C.c_void_p()
         _lib.check(_lib.lib().rv_ctx_create(C.c_int(device), C.byref(self.handle)))
         self.device = device
+        self.compile_flags = 0
 
     @classmethod
     def default(cls) -> "Context":
@@ -47,8 +48,10 @@ class Context:
 
     def set_compile_flags(self, flags: int):
         """rv_ctx_set_compile_flags: 0 (default) or RV_COMPILE_DEVICE -- the cold compiles of Proof.new_ops / verify_ops-style calls
-        (rv_prove_ops, rv_verify_ops) then run on the GPU.  Proof bytes and answers are unchanged."""
+        (rv_prove_ops, rv_verify_ops) then run on the GPU, and so do the piece compiles of the streams that begin afterwards
+        (reverie_amd.stream).  Proof bytes and answers are unchanged."""
         _lib.check(_lib.lib().rv_ctx_set_compile_flags(self.handle, C.c_uint32(flags)))
+        self.compile_flags = int(flags)
 
     def close(self):
         if self.handle:

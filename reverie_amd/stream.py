@@ -12,9 +12,14 @@ The reference's README promises a streaming interface (/root/reference/README.md
 Device memory is bounded by the wire counts, one piece's working set and the proof; everything runs through the C-ABI.
 `StreamingVerifier` checks a proof against a gate list fed in pieces, and `StreamingEvaluator` evaluates one in the clear.
 `StreamingBatchProver` / `StreamingBatchVerifier` prove or verify several witnesses / proofs of one statement over one fed list.
+
+Every class and one-shot function here takes `device_compile` (default False): the stream's all-GF(2) pieces are then compiled on the
+GPU (RV_COMPILE_DEVICE: rv_stream_set_compile_flags / rv_eval_stream_set_compile_flags) instead of on host worker threads; pieces with
+Z64, B2A or SizeHint ops, and pieces with an error in them, are still compiled on the host.  Proofs, answers and values are the same.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional, Sequence, Tuple
 
@@ -25,8 +30,33 @@ from .ops import OP_DTYPE, TOTAL_REPS, program
 from .proof import Context, Evaluation, Proof, _ptr
 
 
+def _set_device_compile(handle, device_compile: bool, setter: str = "rv_stream_set_compile_flags"):
+    """a new stream follows its context's flags; device_compile=True asks for the device compiler whatever they are"""
+    if device_compile:
+        _lib.check(getattr(_lib.lib(), setter)(handle, C.c_uint32(_lib.RV_COMPILE_DEVICE)))
+
+
+@contextlib.contextmanager
+def _ctx_device_compile(ctx: Context, device_compile: bool):
+    """The one-shot calls of the library follow their context's compile flags, so device_compile=True sets RV_COMPILE_DEVICE on `ctx`
+    for the duration of the call and puts back what Context.set_compile_flags last set.  The context is shared state: another
+    thread's cold rv_prove_ops / rv_verify_ops compiles on the same context meanwhile use the device compiler too (same results),
+    and flags set through the C API behind Context's back are not seen here.  A caller who minds either sets the flag on the
+    context once, or uses the Streaming* classes, whose flag lives on the stream handle."""
+    before = getattr(ctx, "compile_flags", 0)
+    if device_compile and not before & _lib.RV_COMPILE_DEVICE:
+        ctx.set_compile_flags(before | _lib.RV_COMPILE_DEVICE)
+        try:
+            yield
+        finally:
+            ctx.set_compile_flags(before)
+    else:
+        yield
+
+
 class StreamingProver:
-    def __init__(self, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0, ctx: Optional[Context] = None):
+    def __init__(self, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
+                 device_compile: bool = False):
         self.ctx = ctx or Context.default()
         self.handle = C.c_void_p()
         s = None
@@ -35,6 +65,7 @@ class StreamingProver:
                                      else np.asarray(seeds, dtype=np.uint8)).reshape(TOTAL_REPS, 16)
         _lib.check(_lib.lib().rv_stream_begin(self.ctx.handle, C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])), _ptr(s),
                                               C.c_size_t(max_chunk_ops), C.byref(self.handle)))
+        _set_device_compile(self.handle, device_compile)
 
     def feed(self, ops, wit_gf2: Sequence[int] = (), wit_z64: Sequence[int] = ()):
         ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
@@ -77,7 +108,7 @@ class StreamingProver:
 
 
 def prove_streaming(ops, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
-                    ctx: Optional[Context] = None) -> Tuple[Proof, dict]:
+                    ctx: Optional[Context] = None, device_compile: bool = False) -> Tuple[Proof, dict]:
     """rv_prove_streaming: both passes over an op array in host memory -> (Proof, stream info)"""
     ctx = ctx or Context.default()
     ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
@@ -88,9 +119,10 @@ def prove_streaming(ops, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=N
         s = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint8)).reshape(TOTAL_REPS, 16)
     out, n = C.c_void_p(), C.c_size_t()
     si = _lib.StreamInfo()
-    _lib.check(_lib.lib().rv_prove_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(int(wire_counts[0])),
-                                             C.c_size_t(int(wire_counts[1])), _ptr(g), C.c_size_t(len(g)), _ptr(z), C.c_size_t(len(z)), _ptr(s),
-                                             C.c_size_t(max_chunk_ops), C.byref(out), C.byref(n), C.byref(si)))
+    with _ctx_device_compile(ctx, device_compile):
+        _lib.check(_lib.lib().rv_prove_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(int(wire_counts[0])),
+                                                 C.c_size_t(int(wire_counts[1])), _ptr(g), C.c_size_t(len(g)), _ptr(z), C.c_size_t(len(z)), _ptr(s),
+                                                 C.c_size_t(max_chunk_ops), C.byref(out), C.byref(n), C.byref(si)))
     return Proof(_owned=(C.c_void_p(out.value), n.value)), {k: int(getattr(si, k)) for k, _ in si._fields_}
 
 
@@ -102,13 +134,15 @@ class StreamingVerifier:
         ok = sv.finish()            # == proof.verify(all ops, (z64_wires, gf2_wires))
     """
 
-    def __init__(self, wire_counts: Tuple[int, int], proof, max_chunk_ops: int = 0, ctx: Optional[Context] = None):
+    def __init__(self, wire_counts: Tuple[int, int], proof, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
+                 device_compile: bool = False):
         self.ctx = ctx or Context.default()
         self.handle = C.c_void_p()
         self._proof = proof if isinstance(proof, Proof) else Proof(bytes(proof))  # (kept alive: the stream reads it until finish)
         buf, n = self._proof._buffer()
         _lib.check(_lib.lib().rv_stream_verify_begin(self.ctx.handle, C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])), buf,
                                                      C.c_size_t(n), C.c_size_t(max_chunk_ops), C.byref(self.handle)))
+        _set_device_compile(self.handle, device_compile)
 
     def feed(self, ops):
         ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
@@ -130,7 +164,7 @@ class StreamingVerifier:
 
 
 def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = True, max_chunk_ops: int = 0,
-                     ctx: Optional[Context] = None) -> Tuple[bool, dict]:
+                     ctx: Optional[Context] = None, device_compile: bool = False) -> Tuple[bool, dict]:
     """rv_verify_streaming: one pass over an op array in host memory -> (ok, stream info)"""
     ctx = ctx or Context.default()
     ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
@@ -138,9 +172,10 @@ def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = Tr
     buf, n = pr._buffer()
     ok = C.c_int()
     si = _lib.StreamInfo()
-    _lib.check(_lib.lib().rv_verify_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])),
-                                              buf, C.c_size_t(n), C.c_uint32(0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT), C.c_size_t(max_chunk_ops),
-                                              C.byref(ok), C.byref(si)))
+    with _ctx_device_compile(ctx, device_compile):
+        _lib.check(_lib.lib().rv_verify_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])),
+                                                  buf, C.c_size_t(n), C.c_uint32(0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT), C.c_size_t(max_chunk_ops),
+                                                  C.byref(ok), C.byref(si)))
     return bool(ok.value), {k: int(getattr(si, k)) for k, _ in si._fields_}
 
 
@@ -179,7 +214,8 @@ class StreamingBatchProver:
         proofs = sp.finish()                                  # proofs[b] == Proof.new(all ops, witness b, seeds=seeds[b])
     """
 
-    def __init__(self, wire_counts: Tuple[int, int], batch: int, seeds=None, max_chunk_ops: int = 0, ctx: Optional[Context] = None):
+    def __init__(self, wire_counts: Tuple[int, int], batch: int, seeds=None, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
+                 device_compile: bool = False):
         self.ctx = ctx or Context.default()
         self.batch = int(batch)
         self.handle = C.c_void_p()
@@ -188,6 +224,7 @@ class StreamingBatchProver:
         s = _batch_seeds(seeds, self.batch)
         _lib.check(_lib.lib().rv_stream_begin_batch(self.ctx.handle, int(wire_counts[0]), int(wire_counts[1]), self.batch, _ptr(s),
                                                     int(max_chunk_ops), C.byref(self.handle)))
+        _set_device_compile(self.handle, device_compile)
 
     def feed(self, ops, wits_gf2=(), wits_z64=()):
         ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
@@ -220,7 +257,7 @@ class StreamingBatchProver:
 
 
 def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
-                          ctx: Optional[Context] = None, info: Optional[dict] = None) -> "list[Proof]":
+                          ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False) -> "list[Proof]":
     """rv_prove_streaming_batch: both passes over an op array in host memory for the witnesses wits_gf2 [B][n] / wits_z64
     [B][m] (B from whichever of the two is 2-D; the other may be []); seeds [B][256][16] or None.  `info` (a dict, optional) receives the stream's figures."""
     ctx = ctx or Context.default()
@@ -239,8 +276,9 @@ def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int],
     outs = (C.c_void_p * batch)()
     lens = (C.c_size_t * batch)()
     si = _lib.StreamInfo()
-    _lib.check(_lib.lib().rv_prove_streaming_batch(ctx.handle, _ptr(ops), len(ops), int(wire_counts[0]), int(wire_counts[1]), batch, _ptr(g),
-                                                   g.shape[1], _ptr(z), z.shape[1], _ptr(s), int(max_chunk_ops), outs, lens, C.byref(si)))
+    with _ctx_device_compile(ctx, device_compile):
+        _lib.check(_lib.lib().rv_prove_streaming_batch(ctx.handle, _ptr(ops), len(ops), int(wire_counts[0]), int(wire_counts[1]), batch, _ptr(g),
+                                                       g.shape[1], _ptr(z), z.shape[1], _ptr(s), int(max_chunk_ops), outs, lens, C.byref(si)))
     if info is not None:
         info.update(_info(si))
     return [Proof(_owned=(C.c_void_p(outs[b]), int(lens[b]))) for b in range(batch)]
@@ -254,7 +292,8 @@ class StreamingBatchVerifier:
         oks = sv.finish()       # oks[b] == verify_streaming(all ops, ..., proofs[b]); a proof that cannot be parsed is False
     """
 
-    def __init__(self, wire_counts: Tuple[int, int], proofs, max_chunk_ops: int = 0, ctx: Optional[Context] = None):
+    def __init__(self, wire_counts: Tuple[int, int], proofs, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
+                 device_compile: bool = False):
         self.ctx = ctx or Context.default()
         self.handle = C.c_void_p()
         self.batch = len(proofs)
@@ -263,6 +302,7 @@ class StreamingBatchVerifier:
         self._keep, ptrs, lens = _proof_array(proofs)  # (kept alive: the stream reads them until finish)
         _lib.check(_lib.lib().rv_stream_verify_begin_batch(self.ctx.handle, int(wire_counts[0]), int(wire_counts[1]), self.batch, ptrs, lens,
                                                            int(max_chunk_ops), C.byref(self.handle)))
+        _set_device_compile(self.handle, device_compile)
 
     feed = StreamingVerifier.feed
 
@@ -282,7 +322,7 @@ class StreamingBatchVerifier:
 
 
 def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bool = True, max_chunk_ops: int = 0,
-                           ctx: Optional[Context] = None, info: Optional[dict] = None) -> "list[bool]":
+                           ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False) -> "list[bool]":
     """rv_verify_streaming_batch: one pass over an op array in host memory for every proof -> one bool per proof"""
     ctx = ctx or Context.default()
     ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
@@ -292,8 +332,9 @@ def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bo
     keep, ptrs, lens = _proof_array(proofs)
     ok = (C.c_int * n)()
     si = _lib.StreamInfo()
-    _lib.check(_lib.lib().rv_verify_streaming_batch(ctx.handle, _ptr(ops), len(ops), int(wire_counts[0]), int(wire_counts[1]), n, ptrs, lens,
-                                                    0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT, int(max_chunk_ops), ok, C.byref(si)))
+    with _ctx_device_compile(ctx, device_compile):
+        _lib.check(_lib.lib().rv_verify_streaming_batch(ctx.handle, _ptr(ops), len(ops), int(wire_counts[0]), int(wire_counts[1]), n, ptrs, lens,
+                                                        0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT, int(max_chunk_ops), ok, C.byref(si)))
     del keep
     if info is not None:
         info.update(_info(si))
@@ -326,13 +367,15 @@ class StreamingEvaluator:
 
     Device memory is the wire store (wire counts x batch) plus one chunk of at most max_chunk_ops ops (0 = 2^18)."""
 
-    def __init__(self, wire_counts: Tuple[int, int], batch: int = 1, max_chunk_ops: int = 0, ctx: Optional[Context] = None):
+    def __init__(self, wire_counts: Tuple[int, int], batch: int = 1, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
+                 device_compile: bool = False):
         self.ctx = ctx or Context.default()
         self.wire_counts = (int(wire_counts[0]), int(wire_counts[1]))
         self.batch = int(batch)
         self.handle = C.c_void_p()
         _lib.check(_lib.lib().rv_eval_stream_begin(self.ctx.handle, C.c_size_t(self.wire_counts[0]), C.c_size_t(self.wire_counts[1]),
                                                    C.c_size_t(self.batch), C.c_size_t(max_chunk_ops), C.byref(self.handle)))
+        _set_device_compile(self.handle, device_compile, "rv_eval_stream_set_compile_flags")
 
     def feed(self, ops, wits_gf2=(), wits_z64=()):
         ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
@@ -368,7 +411,7 @@ class StreamingEvaluator:
 
 
 def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], max_chunk_ops: int = 0, values: bool = False,
-                       ctx: Optional[Context] = None, info: Optional[dict] = None) -> Evaluation:
+                       ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False) -> Evaluation:
     """rv_evaluate_streaming: one op array in host memory, evaluated chunk by chunk with bounded device memory.  wits_gf2 /
     wits_z64: [B][n] (1-D for one witness; the batch is len(wits_gf2)).  Returns the array-shaped Evaluation of
     Circuit.evaluate_batch; `info` (a dict, optional) receives the stream's figures."""
@@ -383,9 +426,10 @@ def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], ma
     gv = np.zeros((batch, wc[1]), np.uint8) if values else None
     zv = np.zeros((batch, wc[0]), np.uint64) if values else None
     si = _lib.EvalStreamInfo()
-    _lib.check(_lib.lib().rv_evaluate_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(wc[0]), C.c_size_t(wc[1]),
-                                                C.c_size_t(batch), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z), C.c_size_t(z.shape[1]),
-                                                C.c_size_t(max_chunk_ops), _ptr(gv), _ptr(zv), st.ctypes.data_as(C.c_void_p), C.byref(si)))
+    with _ctx_device_compile(ctx, device_compile):
+        _lib.check(_lib.lib().rv_evaluate_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(wc[0]), C.c_size_t(wc[1]),
+                                                    C.c_size_t(batch), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z), C.c_size_t(z.shape[1]),
+                                                    C.c_size_t(max_chunk_ops), _ptr(gv), _ptr(zv), st.ctypes.data_as(C.c_void_p), C.byref(si)))
     if info is not None:
         info.update({k: int(getattr(si, k)) for k, _ in si._fields_})
     return _eval_status(st, gv, zv)

@@ -1,7 +1,10 @@
 """Streaming prover on the benchmark workloads: time, device footprint, byte equality with rv_prove.
 
     python tools/stream_bench.py            # config 4 (recycled wire indices) and config 5
-bench.py imports streaming_record() for its `streaming` record."""
+    python tools/stream_bench.py --compiler device            # the same with the pieces compiled on the GPU (RV_COMPILE_DEVICE)
+    python tools/stream_bench.py --compare [--runs 5]         # config 4, host and device compiler side by side, one JSON line per row
+bench.py imports streaming_record() for its `streaming` record.  RV_STREAM_STATS=1 prints the feeds' laps; with the device compiler they
+name the op upload, the device compile and the host copy of the pieces."""
 import os
 import sys
 import time
@@ -68,6 +71,65 @@ def streaming_record(ctx, prog, wit, wc, st, seeds, want: bytes, chunk_ops: int 
     return rec
 
 
+def _timed(f, runs):
+    """median and min - max (ms) of `runs` calls after a warm-up, and the last result"""
+    out = f()
+    dts = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        out = f()
+        dts.append((time.perf_counter() - t0) * 1e3)
+    dts.sort()
+    return {"ms": dts[len(dts) // 2], "ms_min_max": [dts[0], dts[-1]]}, out
+
+
+def compare_compilers(ctx, seeds, want: bytes, runs: int = 5, chunk_ops: int = 1 << 18, layers: int = 153):
+    """config 4 (recycled wire indices) through every streaming entry point, pieces compiled on the host (the default) and on the GPU:
+    yields one record per row.  The proofs are compared with rv_prove's, the evaluator's values between the two compilers."""
+    import circuits
+    from reverie_amd import _lib
+    from reverie_amd.stream import evaluate_streaming, prove_streaming, prove_streaming_batch, verify_streaming
+
+    prog, wit, wc, st = circuits.layered_gf2(layers=layers, recycle=True)
+    wit = np.asarray(wit, np.uint8)
+    chunks = _lib.lib().rv_hook_stream_device_chunks
+    proof0, _ = prove_streaming(prog, wit, [], wc, seeds=seeds, max_chunk_ops=chunk_ops, ctx=ctx)
+    bseeds = np.stack([np.roll(seeds, b, axis=0) for b in range(8)])
+    bwits = np.tile(wit, (8, 1))
+    values = {}
+
+    def row(name, f, check, env=None):
+        for k, v in (env or {}).items():
+            os.environ[k] = v
+        try:
+            rec = {"row": name}
+            for compiler in ("host", "device"):
+                before = chunks()
+                t, out = _timed(lambda: f(compiler == "device"), runs)
+                rec[compiler] = dict(t, ok=bool(check(out, compiler)), device_chunks_per_call=(chunks() - before) // (runs + 1))
+            rec["device_over_host"] = rec["device"]["ms"] / rec["host"]["ms"]
+            return rec
+        finally:
+            for k in env or {}:
+                os.environ.pop(k, None)
+
+    def same_values(out, compiler):
+        key = out.gf2.tobytes()
+        values.setdefault("host", key)
+        return bool(out.ok.all()) and values["host"] == key
+
+    prove = lambda dev: prove_streaming(prog, wit, [], wc, seeds=seeds, max_chunk_ops=chunk_ops, ctx=ctx, device_compile=dev)
+    yield row("prove_streaming", prove, lambda o, c: bytes(o[0]) == want)
+    yield row("verify_streaming", lambda dev: verify_streaming(prog, wc, proof0, max_chunk_ops=chunk_ops, ctx=ctx, device_compile=dev), lambda o, c: o[0])
+    yield row("prove_streaming RV_STREAM_KEEP_MB=0", prove, lambda o, c: bytes(o[0]) == want, {"RV_STREAM_KEEP_MB": "0"})
+    yield row("evaluate_streaming", lambda dev: evaluate_streaming(prog, wit, [], wc, max_chunk_ops=chunk_ops, values=True, ctx=ctx, device_compile=dev),
+              same_values)
+    yield row("prove_streaming_batch of 8",
+              lambda dev: prove_streaming_batch(prog, bwits, [], wc, seeds=bseeds, max_chunk_ops=chunk_ops, ctx=ctx, device_compile=dev),
+              lambda o, c: bytes(o[0]) == want and len(o) == 8)
+    yield row("prove_streaming RV_STREAM_THREADS=1", prove, lambda o, c: bytes(o[0]) == want, {"RV_STREAM_THREADS": "1"})
+
+
 def z64_record(ctx, seeds, n_mul=1_000_000, chunk_ops=1 << 16):
     import circuits
     import reverie_amd
@@ -97,19 +159,34 @@ def z64_record(ctx, seeds, n_mul=1_000_000, chunk_ops=1 << 16):
 
 
 if __name__ == "__main__":
+    import argparse
     import json
 
     import circuits
     import reverie_amd
 
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--compiler", default="host", choices=["host", "device"], help="where the streams' pieces are compiled (RV_COMPILE_DEVICE)")
+    ap.add_argument("--compare", action="store_true", help="config 4 with both compilers, every streaming entry point")
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--bench-record", action="store_true")
+    args = ap.parse_args()
     ctx = reverie_amd.Context(0)
+    if args.compiler == "device":  # (the one-shot calls follow the context's flags)
+        from reverie_amd import _lib
+
+        ctx.set_compile_flags(_lib.RV_COMPILE_DEVICE)
     seeds = np.random.default_rng(0x5EED).integers(0, 256, (256, 16), dtype=np.uint8)
     layers = int(os.environ.get("LAYERS", "153"))
     prog, wit, wc, st = circuits.layered_gf2(layers=layers)
     circ = reverie_amd.Circuit(prog, wc, ctx)
     want = bytes(reverie_amd.Proof.new(circ, wit, [], seeds=seeds))
     circ.close()
-    if "--bench-record" in sys.argv:  # bench.py's `streaming` record: the default chunk size only, one JSON line
+    if args.compare:
+        for rec in compare_compilers(ctx, seeds, want, runs=args.runs, layers=layers):
+            print(json.dumps(rec), flush=True)
+        sys.exit(0)
+    if args.bench_record:  # bench.py's `streaming` record: the default chunk size only, one JSON line
         rec = streaming_record(ctx, prog, wit, wc, st, seeds, want, chunk_ops=1 << 18, layers=layers)
         rec["note"] += "; measured in a process of its own (tools/stream_bench.py --bench-record): inside bench.py's process -- 20+ GB of host arrays, the oracle's and torch's thread pools -- the host-side compile of the chunks runs ~1.5x slower (0.18 s)"
         print(json.dumps(rec))
