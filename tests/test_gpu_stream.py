@@ -293,8 +293,8 @@ def test_stream_verify_golden(rv, name):
 @pytest.mark.parametrize("seed", range(5))
 def test_stream_verify_matches_resident_verifier(rv, oracle, seed):
     """random GF(2) + Z64 + B2A programs cut at random places: the streaming verifier answers what rv_verify_ex answers -- for
-    honest proofs, for proofs with a flipped byte anywhere (strict and reference-compatible), and for proofs whose supplied
-    vectors are short (exhausted iterators read as zero, online.rs:124,162,170)"""
+    honest proofs and for proofs with a flipped byte anywhere (strict and reference-compatible).  Proofs whose supplied vectors
+    are short or long (exhausted iterators read as zero, online.rs:124,162,170): tests/test_gpu_verify_lengths.py"""
     rng = np.random.default_rng(7700 + seed)
     prog, w2, w64, wc = circuits.random_mixed(rng, n_gates=int(rng.integers(150, 600)))
     hint = prog[prog["domain"] == 3]
