@@ -692,7 +692,7 @@ int rv_hook_ops_same(const void *a, const void *b, size_t bytes);
  * lane-distributed cipher of csrc/aes_col4.hip on a stream of its own, chunk by chunk; RV_OVERLAP=0 runs it before the first level;
  * circuits below RV_OVERLAP_MIN = 8192 cipher blocks and rows narrower than 64 repetitions keep that order anyway).  Same bytes. */
 uint64_t rv_hook_overlap_commits(void);
-/* Verifications this process has run with one u64 of public corrections per share row instead of corr rows (csrc/kernels.hip:
+/* Verifications this process has run with one u64 of public corrections per share row instead of corr rows (csrc/interp.hip:
  * MODE_VERIFY_C -- the verify-mode interpreter of whole proofs of pure GF(2) one-base gate streams; replaces nothing of the
  * reference's: verifier/online.rs:122-183 computes the same values).  The answer is the same either way; the tests use the
  * counter to know which path they compared.  RV_VERIFY_VC=0 turns the path off. */

@@ -603,7 +603,7 @@ extern "C" int rv_ctx_profile(rv_ctx* ctx, int enable, int reset, rv_profile* ou
 // ------------------------------------------------------------------------------------
 // circuit
 // ------------------------------------------------------------------------------------
-// Early corrections (rv_prove_impl; kernels.hip "Early corrections"): which byte ranges of the repetitions' corrections
+// Early corrections (rv_prove_impl; open.hip "Early corrections"): which byte ranges of the repetitions' corrections
 // vectors leave for the host after which level.  A pure function of the compiled circuit, computed on first use.
 struct EarlyPlan {
     bool ok = false;
@@ -665,7 +665,7 @@ struct rv_circuit {
     LdsRec* d_lds_recs = nullptr;
     mutable std::once_flag ec_once;
     mutable EarlyPlan ec_plan;
-    bool persist_gen = false;  // some level has enough multi-base Mul / Xor gates for the kernel variant with their loops (kernels.hip: level_is_general)
+    bool general_levels = false;  // any_level_general() of the gate stream: some level runs the kernel variant with the multi-base loops (verify.inc: no MODE_VERIFY_C then)
     // rv_evaluate (eval.inc): the final wire forms (RV_COMPILE_KEEP_WIRES, uploaded with the circuit) and the Z64 level table (on the
     // first evaluation; the provers do not read it)
     bool keep_wires = false;
@@ -1166,7 +1166,7 @@ static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged) {
             c->cc.info.device_bytes += sorted.size() * sizeof(Gate64);
         }
     }
-    c->persist_gen = persist_general(cc.level_range.data(), cc.level_range.size());
+    c->general_levels = any_level_general(cc.level_range.data(), cc.level_range.size());
     return RV_OK;
 #undef UPCHK
 }

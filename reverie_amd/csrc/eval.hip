@@ -5,7 +5,7 @@
 //   GF(2): val[row][W] u32, W = ceil(B / 32): bit b % 32 of word b / 32 of a row is witness b's value of that share row (rows are the
 //          compiled gates' row ids, the index space of InterpParams::vclr); the zero row holds zeros.
 //   Z64:   v64[ssa][B] u64; SSA id 0 (the never-written wire) holds zeros.
-// Per gate the MODE_PROVE_V branches of k_interp_full (kernels.hip): Input copies the witness bit, Xor sums its base rows, Mul ANDs
+// Per gate the MODE_PROVE_V branches of k_interp_full (interp.hip): Input copies the witness bit, Xor sums its base rows, Mul ANDs
 // its two operand forms, AssertZero records the witnesses whose operand is not zero.  B2A (combine.rs:132-219) is compiled into 64
 // fresh GF(2) masks, a ripple-carry adder and 64 revealed sum bits: with every fresh mask taken as zero (G_RANDOM writes zeros --
 // the op list has no Random op of its own, the caller checked) the sum bits ARE the source bits, and the Z64 value is their binary

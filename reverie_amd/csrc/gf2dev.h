@@ -1,4 +1,4 @@
-// Device helpers shared by the GF(2) interpreter kernels (kernels.hip, ldsrun.hip): the quad-word arithmetic of
+// Device helpers shared by the GF(2) interpreter kernels (interp.hip, open.hip, ldsrun.hip): the quad-word arithmetic of
 // algebra/gf2/domain.rs:10-63 (reconstruct = per-byte parity) and the one-bit-per-repetition packing of corr /
 // preprocessing bits.
 #pragma once

@@ -112,7 +112,7 @@ struct Interp64Params {
 // in the one-launch-per-level kernels (a level reads what the previous LAUNCH wrote).
 // MODE_VERIFY_C: the verifier of a whole proof with one u64 of public corrections per share row (the opened repetitions' quad
 // words, InterpParams::vc) instead of corr rows; full-width rows, every level launched on its own, no Random / B2A gates.
-enum Mode : int { MODE_PROVE = 0, MODE_VERIFY = 1, MODE_PROVE_V = 2, /* 3: the flat schedule of rounds 4 - 5, gone */ MODE_VERIFY_C = 4 };
+enum Mode : int { MODE_PROVE = 0, MODE_VERIFY = 1, MODE_PROVE_V = 2, MODE_VERIFY_C = 4 };
 // bit set in the device error word when an AssertZero of an online-verified repetition does not reconstruct to zero
 // (VerifierTranscriptOnline.okay, online.rs:175-177; only the strict verifier looks at it)
 constexpr int RV_DEV_ZERO_CHECK = 0x100;
@@ -217,8 +217,9 @@ void launch_aes_blocks(hipStream_t st, const uint8_t* d_rkbytes, uint32_t n_keys
 struct LevelRange {
     uint32_t lo, mul11, mul, xor2, xork, hi;
 };
-// some level has enough multi-base Mul / Xor gates for the kernel variant with their loops (kernels.hip: level_is_general)
-bool persist_general(const LevelRange* lr, size_t n_levels);
+// some level has enough multi-base Mul / Xor gates for the kernel variant with their loops (interp.hip: level_is_general);
+// launch_interp chooses per level, the verifier asks for the whole stream before it takes MODE_VERIFY_C
+bool any_level_general(const LevelRange* lr, size_t n_levels);
 // next: the level launched after this one by launch_interp too (nullable) -- the tail of this launch prefetches
 // its first gate records
 void launch_interp(hipStream_t st, int mode, const Gate* d_gates, const LevelRange& r, const InterpParams& p,
@@ -231,7 +232,7 @@ void launch_interp_narrow(hipStream_t st, int mode, const Gate* d_gates, const L
 // array of one InterpParams per proof
 void launch_interp_batched(hipStream_t st, const Gate* d_gates, const LevelRange& r, const InterpParams* d_pp, uint32_t batch,
                            int mode = MODE_PROVE);
-// large proofs: the two transcripts' trees in shared launches (kernels.hip); four ping-pong buffers of b3_stream_scratch_words each
+// large proofs: the two transcripts' trees in shared launches (b3_tree.hip); four ping-pong buffers of b3_stream_scratch_words each
 // (d_quads / n_quads as in launch_b3_stream: the verifier's online stream of the quad words with an opened repetition)
 bool b3_pair_big_ok(uint64_t n_pre, uint64_t n_on, uint32_t NQ, const uint32_t* d_quads = nullptr, uint32_t n_quads = 0);
 uint32_t launch_b3_pair_big(hipStream_t st, const uint8_t* d_pre, uint64_t n_pre, const uint32_t* d_on, uint64_t n_on, uint32_t NQ, uint32_t* cv_a0,
@@ -240,7 +241,7 @@ uint32_t launch_b3_pair_big(hipStream_t st, const uint8_t* d_pre, uint64_t n_pre
 bool launch_b3_pair_small(hipStream_t st, const uint8_t* d_pre, uint64_t n_pre, const uint32_t* d_on, uint64_t n_on, uint32_t NQ, uint32_t* d_cv_a,
                           uint32_t* d_cv_b, uint32_t* d_dig_pre, uint32_t* d_dig_on, const uint32_t* d_quads = nullptr, uint32_t n_quads = 0);
 void launch_store_word(hipStream_t st, const int* d_src, int* dst_mapped);
-// early corrections (kernels.hip, api.hip: rv_prove on large GF(2) circuits)
+// early corrections (open.hip, api.hip: rv_prove on large GF(2) circuits)
 void launch_pack_corr_all(hipStream_t st, const uint8_t* d_bits, uint64_t n_items, uint64_t byte0, uint64_t n_bytes, uint64_t pitch, uint8_t* d_out);
 // OpenDirect: the first n_direct tiles of the opened repetitions' broadcast vectors (tile = `tile` bytes, a power of two, of every
 // opened repetition; vector at record + rvec_at, rvec_len bytes) are written to the page-locked proof buffer by the extraction kernel
@@ -374,7 +375,7 @@ void launch_fs_challenge(hipStream_t st, const uint8_t* d_h, const FsLayout& L, 
                          uint8_t* d_omit, uint8_t* d_omit_all, uint64_t* d_offs, OnlineList* d_ol, uint32_t* d_res,
                          uint32_t* mbox = nullptr /* host-mapped: comm, the opening map, the counts for the host; then *mbox_flag = mbox_seq */,
                          uint32_t* mbox_flag = nullptr, uint32_t mbox_seq = 0);
-// one small GF(2) proof's openings (heads + the three kinds of vectors [+ the error word]) in ONE launch (kernels.hip: k_open_small);
+// one small GF(2) proof's openings (heads + the three kinds of vectors [+ the error word]) in ONE launch (open.hip: k_open_small);
 // false: not taken (a recorded batch, long vectors) -- the caller launches the pieces
 bool launch_open_small(hipStream_t st, uint32_t R, const uint8_t* d_omit, const uint8_t* d_seeds, const uint8_t* d_keys, const uint32_t* d_on2,
                        const uint32_t* d_on64, const uint64_t* d_offs, uint64_t l2r, uint64_t l2c, uint64_t l2i, uint64_t l64r, uint64_t l64c, uint64_t l64i,

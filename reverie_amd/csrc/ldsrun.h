@@ -2,7 +2,7 @@
 //
 // A stretch of consecutive narrow dependency levels (ripple-carry adders, AES / SHA rounds from Bristol files: thousands
 // of levels of a few dozen gates) is latency-bound in the row interpreter: every level is one L2 round trip for the
-// operand rows plus a workgroup barrier, ~1.2 us, on ONE compute unit (k_interp_narrow, kernels.hip).  Here the
+// operand rows plus a workgroup barrier, ~1.2 us, on ONE compute unit (k_interp_narrow, interp.hip).  Here the
 // repetitions of the shard are cut into NQ / QS independent slices of QS quad words (4 QS repetitions); a slice is one
 // workgroup whose CONSUMER wavefront walks the run step by step -- a step = up to 64 / QS gates of one level, one lane
 // per (gate, quad word) -- with every wire that is live inside the run in an LDS slot (QS share words + QS words of corr bits).
@@ -15,7 +15,7 @@
 // The program (one record per gate slot of a step, slots allocated by liveness) is built on the host at circuit-compile
 // time; it does not depend on NQ, only on QS.
 //
-// Reference semantics: interpreter/single.rs:25-157 (Instance::step) exactly as interp_one_impl (kernels.hip) restates
+// Reference semantics: interpreter/single.rs:25-157 (Instance::step) exactly as interp_one (interp.hip) restates
 // them; this is a second schedule of the same gates, not a second implementation of the protocol.
 #pragma once
 #include <stdint.h>

@@ -1,6 +1,6 @@
 // LDS runs: narrow / deep stretches of a GF(2) circuit with the live wires in LDS (ldsrun.h has the design).
 //
-// Replaces, for those stretches, the same reference code as the row interpreter (kernels.hip):
+// Replaces, for those stretches, the same reference code as the row interpreter (interp.hip):
 //   interpreter/single.rs:25-157      Instance::step / op_mul over the GF(2) ring
 //   algebra/gf2/domain.rs:10-63       reconstruct (per-byte parity)
 //   transcript/prover.rs:181-232, verifier/online.rs:122-183, verifier/preprocess.rs:46-79

@@ -38,7 +38,7 @@ static int rv_prove_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf
     }
     rv_shard* s = nullptr;
     uint8_t* out = nullptr;
-    // Early corrections (kernels.hip): half of a large GF(2) proof -- the corrections vectors -- does not depend on the
+    // Early corrections (open.hip): half of a large GF(2) proof -- the corrections vectors -- does not depend on the
     // challenge beyond the choice of repetitions.  Every repetition's vector goes to a page-locked staging buffer through
     // the copy engine while the interpreter and the hash kernels run; once the challenge is known (published into a mapped
     // mailbox the host polls, no stream synchronisation) helper threads copy the 40 opened ones into the proof while the GPU

@@ -97,7 +97,7 @@ struct rv_shard {
     // vectors' tiles that the extraction kernel writes there itself
     uint8_t* od_out = nullptr;
     uint32_t od_n_direct = 0;
-    // small proofs (kernels.hip: k_open_small): where the openings' one launch also leaves the error word for the host, and whether it did
+    // small proofs (open.hip: k_open_small): where the openings' one launch also leaves the error word for the host, and whether it did
     int* err_dst_mapped = nullptr;
     bool err_word_sent = false;
     bool keys_deferred = false;  // rv_shard_commit: expand_seeds is part of shard_setup_prg's k_setup_keys

@@ -623,7 +623,7 @@ static int verify_groups_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* p
     int vmode = MODE_VERIFY;
     // (not for gate streams with multi-base levels -- the prover's lazy linear forms: their kernel variant runs at 4 - 5 wavefronts
     // per SIMD either way and measured 0.07 ms SLOWER with the compact corrections; one-base streams: -0.03 ... -0.08 ms)
-    if (vc_on && c->vclr_ok && !c->persist_gen && NQ == 64 && sup_nq == 16 && !on_quads.empty() && !g_recorder) {
+    if (vc_on && c->vclr_ok && !c->general_levels && NQ == 64 && sup_nq == 16 && !on_quads.empty() && !g_recorder) {
         uint64_t* d_vc = nullptr;
         if ((rc = dalloc(ctx, (size_t)cc.n_rows, &d_vc))) return fail(rc);
         track(d_vc);

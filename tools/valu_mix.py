@@ -93,7 +93,8 @@ def main():
         if "k_aes_gf2_masks_col4" in name:
             # outer block loop (1 trip per CTR block: the unit) and the middle rounds' loop inside it (8 trips per block)
             out["kernels"]["rv::k_aes_gf2_masks_col4"] = mix(items, [1, 8])
-    kk = functions(asm_of(os.path.join(ROOT, "reverie_amd", "csrc", "kernels.hip")))
+    kk = {**functions(asm_of(os.path.join(ROOT, "reverie_amd", "csrc", "interp.hip"))),
+          **functions(asm_of(os.path.join(ROOT, "reverie_amd", "csrc", "b3_tree.hip")))}
     for name, items in kk.items():
         if "k_interp_fullILi2ELi64ELb1E" in name:
             out["kernels"]["rv::k_interp_full<2, 64, true>"] = mix(items, [1])
