@@ -152,9 +152,12 @@ int rv_circuit_compile_ex(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z6
                           rv_circuit **out);
 /* RV_COMPILE_DEVICE: the op list is uploaded and compiled on the context's GPU (csrc/compile_dev.hip) into a circuit identical field
  * by field to the host compiler's, so every proof, verification and evaluation is byte-identical.  The device path takes whole
- * programs of GF(2) ops (no Z64, B2A or SizeHint op) whose plain compile keeps every Xor of two rows materialised: not with
- * RV_COMPILE_KEEP_WIRES, RV_COMPILE_WHOLE_PROVER or RV_LAZY_K, and not for the deep, narrow circuits the host compiler recompiles with
- * lazy sums (AES-128, SHA-256).  Everything else, op-list errors included, is compiled by the host compiler, with its error codes. */
+ * programs of GF(2) ops (no Z64, B2A or SizeHint op) in either gate-stream form: the plain one (every Xor of two rows materialised)
+ * when that is the host compiler's final answer -- not for the deep, narrow circuits it recompiles with lazy sums (AES-128, SHA-256)
+ * --, and, combined with RV_COMPILE_WHOLE_PROVER, the lazy-sum form of any such program (a forced form is final, so AES-128 and
+ * SHA-256 compile on the device under both flags).  Not with RV_COMPILE_KEEP_WIRES or RV_LAZY_K, and not past 2^16 dependency
+ * rounds.  Everything else, op-list errors included, is compiled by the host compiler, with its error codes;
+ * rv_circuit_compiled_on_device tells which compiler made a circuit. */
 #define RV_COMPILE_DEVICE 4u
 /* The same for an op array already in device memory (n_ops packed 24-byte records on the context's device, e.g. a torch tensor);
  * the caller keeps ownership of d_ops and must have finished writing it.  A program the device path does not take is copied to the
@@ -163,7 +166,9 @@ int rv_circuit_compile_device(rv_ctx *ctx, const rv_op *d_ops, size_t n_ops, siz
                               rv_circuit **out);
 /* Compile flags of the context's own compiles (rv_prove_ops, rv_verify_ops); 0 (the default) or RV_COMPILE_DEVICE.  Under
  * RV_COMPILE_DEVICE rv_prove_ops compiles the plain form on the device instead of the RV_COMPILE_WHOLE_PROVER one: the same proof
- * bytes, a faster first proof of a wide circuit, 2-4 % slower proofs of it afterwards.  RV_E_ARG for any other bit. */
+ * bytes, a faster first proof of a wide circuit, 2-4 % slower proofs of it afterwards.  (The device compiler builds the
+ * RV_COMPILE_WHOLE_PROVER form too -- rv_circuit_compile_ex with both flags --; rv_prove_ops does not ask it for that form,
+ * DESIGN.md 14.)  rv_verify_ops keeps the plain form either way.  RV_E_ARG for any other bit, RV_COMPILE_WHOLE_PROVER included. */
 int rv_ctx_set_compile_flags(rv_ctx *ctx, uint32_t flags);
 void rv_circuit_destroy(rv_circuit *c);
 
@@ -183,6 +188,9 @@ typedef struct rv_circuit_info {
     uint64_t gf2_operand_rows, gf2_rows_written;
 } rv_circuit_info; /* (no size field: this struct does not grow -- later additions get getters of their own, like the one below) */
 int rv_circuit_get_info(const rv_circuit *c, rv_circuit_info *info);
+/* *on_device = 1 when the device compiler (RV_COMPILE_DEVICE, rv_circuit_compile_device) made this circuit, 0 when the host compiler
+ * did -- because the flag was not set, or because the device path handed the program back.  The circuit is the same either way. */
+int rv_circuit_compiled_on_device(const rv_circuit *c, int *on_device);
 /* ABI 7 (ABI 6 had it as a field of rv_circuit_info): page-locked host memory rv_prove's early-corrections path stages this
  * circuit's corrections vectors in (0: the path does not apply to the circuit), as the RV_EARLY_* environment stands at the call.
  * Allocated once per context, on the first proof that takes the path (its first mapping costs 0.15 - 1.5 s), and kept;
@@ -651,7 +659,9 @@ int rv_hook_compile_info(const rv_op *ops, size_t n_ops, size_t z64_wires, size_
 int rv_hook_compile_compare(const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, int threads, int *diff);
 /* The device compiler against the host compiler (compile_ops) on the same program: *path = 1 when the device path compiled it, 0
  * when it handed it to the host compiler; *diff = 0 when the two results are identical field by field (as rv_hook_compile_compare).
- * Returns the host compiler's status. */
+ * The hook tries the device whether or not RV_COMPILE_DEVICE is set, except that RV_COMPILE_WHOLE_PROVER without the device bit stays
+ * a host compile (*path = 0): with RV_COMPILE_WHOLE_PROVER | RV_COMPILE_DEVICE it tries the device compiler on the lazy-sum form and
+ * compares with the host compiler's forced lazy-sum compile.  Returns the host compiler's status. */
 int rv_hook_compile_compare_device(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, int *path,
                                    int *diff);
 /* The same for one piece of a stream: both sides compile the ops as the streaming chunk that starts at `start` = { mask_phase (< 128),

@@ -89,6 +89,7 @@ SYMBOLS = [
     "rv_verify_shard_groups", "rv_verify_partition", "rv_verify_sharded", "rv_verify_multi", "rv_hook_verify_proof_bytes",
     "rv_circuit_compile_device", "rv_ctx_set_compile_flags", "rv_hook_compile_compare_device", "rv_hook_compile_device_laps",
     "rv_stream_set_compile_flags", "rv_eval_stream_set_compile_flags", "rv_hook_compile_compare_device_chunk", "rv_hook_stream_device_chunks",
+    "rv_circuit_compiled_on_device",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -117,11 +118,12 @@ ARGTYPES = {
     "rv_eval_stream_set_compile_flags": [_P, C.c_uint32],
     "rv_hook_compile_compare_device_chunk": [_P, _P, _Z, _Z, _Z, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "rv_hook_stream_device_chunks": [],
+    "rv_circuit_compiled_on_device": [_P, C.POINTER(C.c_int)],
 }
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1
 RV_COMPILE_KEEP_WIRES = 2  # the circuit keeps every wire's final value form: rv_evaluate can return wire values
-RV_COMPILE_DEVICE = 4  # compiled on the GPU (GF(2) programs at K = 1; anything else by the host compiler): the same circuit
+RV_COMPILE_DEVICE = 4  # compiled on the GPU (GF(2) programs, plain or -- with WHOLE_PROVER -- lazy sums; anything else by the host compiler): the same circuit
 RV_VERIFY_REFERENCE_COMPAT = 2  # the reference verifier's two unchecked conditions stay unchecked
 
 _lib = None

@@ -774,9 +774,7 @@ static DevAlloc ctx_dev_allocator(rv_ctx* ctx) {
     return a;
 }
 // the requests the device compiler hands to the host compiler whatever the op list holds (compile_dev.h): no upload for them
-static bool device_compile_possible(uint32_t flags) {
-    return !(flags & (RV_COMPILE_KEEP_WIRES | RV_COMPILE_WHOLE_PROVER)) && !getenv("RV_LAZY_K");
-}
+static bool device_compile_possible(uint32_t flags) { return !(flags & RV_COMPILE_KEEP_WIRES) && !getenv("RV_LAZY_K"); }
 static std::mutex g_dev_laps_mu;
 static DevCompileLaps g_dev_laps;
 // the device compile of d_ops (device memory) into `cc` (and, with keep, the circuit's gate / ordinal arrays in HBM); RV_OK,
@@ -859,7 +857,8 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
     int rc = RV_COMPILE_FALLBACK;
     std::vector<rv_op> h_ops;  // (ops in device memory that the device path hands back: the host compiler's copy)
     if (d_ops || (flags & RV_COMPILE_DEVICE)) {
-        // RV_COMPILE_DEVICE / rv_circuit_compile_device: the GF(2) K = 1 compile on the context's GPU (compile_dev.hip)
+        // RV_COMPILE_DEVICE / rv_circuit_compile_device: the GF(2) compile on the context's GPU (compile_dev.hip), at K = 1 or, with
+        // RV_COMPILE_WHOLE_PROVER, in the lazy-sum form
         if (hipSetDevice(ctx->device) != hipSuccess) {
             delete c;
             return hip_fail(hipGetLastError(), "hipSetDevice", __FILE__, __LINE__);
@@ -1297,7 +1296,8 @@ extern "C" int rv_hook_compile_compare_device(rv_ctx* ctx, const rv_op* ops, siz
         Compiled a, b;
         const int rc = compile_ops(ops, n_ops, z64_wires, gf2_wires, a, nullptr, k, (flags & RV_COMPILE_KEEP_WIRES) != 0);
         int rd = RV_COMPILE_FALLBACK;
-        if (device_compile_possible(flags) && n_ops) {
+        // (without the device bit the hook tries the device on the plain form only: RV_COMPILE_WHOLE_PROVER alone is a host compile)
+        if (device_compile_possible(flags) && (!(flags & RV_COMPILE_WHOLE_PROVER) || (flags & RV_COMPILE_DEVICE)) && n_ops) {
             HIPCHK(hipSetDevice(ctx->device));
             rv_op* up = nullptr;
             rd = upload_ops(ctx, ops, n_ops, &up);
@@ -1364,6 +1364,11 @@ static uint64_t early_staging_bytes_of(const rv_circuit* c);  // (with the early
 extern "C" int rv_circuit_get_info(const rv_circuit* c, rv_circuit_info* info) {
     if (!c || !info) return RV_E_ARG;
     *info = c->cc.info;
+    return RV_OK;
+}
+extern "C" int rv_circuit_compiled_on_device(const rv_circuit* c, int* on_device) {
+    if (!c || !on_device) return RV_E_ARG;
+    *on_device = c->dev_compiled ? 1 : 0;
     return RV_OK;
 }
 extern "C" int rv_circuit_early_staging_bytes(const rv_circuit* c, uint64_t* bytes) {

@@ -1,12 +1,15 @@
-// Gate-stream compiler on the GPU (compile_dev.hip): the K = 1 compile of a whole GF(2) program, from an op list in device
-// memory, to a Compiled identical field by field to what compile_ops makes of it.  Scope: GF(2) ops only (no Z64, B2A or
-// SizeHint), no RV_COMPILE_KEEP_WIRES, no forced or environment-chosen lazy_k, and a K = 1 compile that compile_ops_seq would keep
-// (lazy_forms_pay false).  Everything else, every op-list error included, is RV_COMPILE_FALLBACK: the caller runs compile_ops,
-// which returns the canonical result or error code.
+// Gate-stream compiler on the GPU (compile_dev.hip): the compile of a whole GF(2) program, from an op list in device memory, to a
+// Compiled identical field by field to what compile_ops makes of it.  Two forms: K = 1 (force_lazy_k = 0; every Xor of two rows
+// materialised), when that is a compile compile_ops_seq would keep (lazy_forms_pay false), and the lazy-sum form (force_lazy_k =
+// RV_LIN_K, what RV_COMPILE_WHOLE_PROVER asks for: sums of up to RV_LIN_K rows stay symbolic by Builder::g_xor's rule at lazy_slack 1,
+// balance 0), which is final for every circuit.  Scope: GF(2) ops only (no Z64, B2A or SizeHint), no RV_COMPILE_KEEP_WIRES, no other
+// forced lazy_k, no RV_LAZY_K in the environment, at most 2^16 topological rounds.  Everything else, every op-list error included, is
+// RV_COMPILE_FALLBACK: the caller runs compile_ops, which returns the canonical result or error code.
 //
 // Chunk mode (`chunk` not null): one piece of a stream, identical to compile_ops_seq(..., chunk) -- the wires start in their carried
 // rows, the counters at the ChunkStart's, no sum is dropped as unread, and one more level writes every wire the piece wrote back to
-// its carried row.  A chunk is final at K = 1 whatever its shape (lazy_forms_pay does not apply); an empty piece is compiled too.
+// its carried row.  A chunk is final at K = 1 whatever its shape (lazy_forms_pay does not apply; a forced lazy_k is a fallback); an
+// empty piece is compiled too.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,6 +1,7 @@
 // see compile_dev.h
 //
-// The device compile of a whole GF(2) program at K = 1 (every XOR of two distinct rows materialised), in the steps of the host
+// The device compile of a whole GF(2) program at K = 1 (every XOR of two distinct rows materialised; the lazy-sum form's differences are
+// with its kernels: value_lazy, and the LAZY instantiations of steps 3 and 5), in the steps of the host
 // compiler (compile.cpp: run_pass, Builder, the (level, class) sort and the pipelining tables):
 //   1. classify   one thread per op: validation (any error -> the flag word -> the host compiler), the counters Builder::g_* keep
 //                 (masks, Mul, AssertZero, Input: one exclusive scan gives every gate's m / eo / ep / x), the ordinal tables
@@ -290,10 +291,153 @@ __device__ inline int2 val_of(const int2* V, int p) { return p < 0 ? make_int2(p
 __device__ inline int lvl_of(int2 v) { return (v.y >> 1) - 1; }
 __device__ inline bool is_row(int2 v) { return v.x != -1; }
 
+// ---- the lazy-sum form (force_lazy_k = RV_LIN_K; whole programs only) ----
+// A value is a Lin of compile.cpp: x, y, z = up to RV_LIN_K rows in the host compiler's order, w = count | constant bit << 2 (the
+// value of a materialised sum also keeps that gate's row count, << 8, for the statistics and the class keys).  A row is named by the
+// op that wrote it, with ROW_COMP set when that op is a materialised sum: the host compiler sorts PRG rows (mask index) before
+// computed rows (COMP | index), and both indices grow in op order, so comparing these names compares its row numbers.
+// A row's level is glvl of its op; a never-written wire is the empty form.
+static_assert(RV_LIN_K == 3, "a lazy value holds three rows");
+constexpr uint32_t ROW_COMP = 1u << 30;  // (n_ops < 2^28)
+__device__ inline uint4 form_of(const uint4* V3, int p) { return p < 0 ? make_uint4(0, 0, 0, 0) : V3[p]; }
+__device__ inline uint32_t form_n(const uint4& F) { return F.w & 3u; }
+__device__ inline uint32_t form_c(const uint4& F) { return (F.w >> 2) & 1u; }
+__device__ inline uint32_t form_row(const uint4& F, int k) { return k == 0 ? F.x : k == 1 ? F.y : F.z; }
+__device__ inline int form_lvl(const uint4& F, const int* glvl) {
+    const uint32_t n = form_n(F);
+    int l = -1;
+    if (n > 0) l = max(l, glvl[F.x & ~ROW_COMP]);
+    if (n > 1) l = max(l, glvl[F.y & ~ROW_COMP]);
+    if (n > 2) l = max(l, glvl[F.z & ~ROW_COMP]);
+    return l;
+}
+// Builder::g_xor's symmetric difference of two sorted row lists (x ^ x = 0): at most 6 rows, one or two consumed per step
+__device__ inline int form_xor(const uint4& A, const uint4& B, uint32_t (&rows)[2 * RV_LIN_K]) {
+    const int na = (int)form_n(A), nb = (int)form_n(B);
+    int i = 0, j = 0, n = 0;
+#pragma unroll
+    for (int k = 0; k < 2 * RV_LIN_K; k++) rows[k] = 0;
+#pragma unroll
+    for (int t = 0; t < 2 * RV_LIN_K; t++) {
+        if (i < na || j < nb) {
+            const uint32_t x = i < na ? form_row(A, i) : 0xFFFFFFFFu, y = j < nb ? form_row(B, j) : 0xFFFFFFFFu;
+            if (x == y) {
+                i++, j++;
+            } else {
+                const uint32_t v = min(x, y);
+                i += x < y, j += y < x;
+#pragma unroll
+                for (int k = 0; k < 2 * RV_LIN_K; k++)
+                    if (n == k) rows[k] = v;
+                n++;
+            }
+        }
+    }
+    return n;
+}
+
+// the value of op i, the level of its gate (-1: none) and whether it is a materialised sum: the rules of Builder::g_xor / g_xorc /
+// g_andc / g_const / g_mul at lazy_k = 1 ...
+__device__ inline int2 value_k1(const rv_op& op, uint32_t i, int2 p, uint32_t chunk, const uint32_t* uses, const int2* V, int* gl, uint32_t* mt) {
+    const int2 A = val_of(V, p.x), B = val_of(V, p.y);
+    const int cb = (int)(op.imm & 1);
+    int2 out = make_int2(-1, 0);
+    switch (op.opcode) {
+    case RV_OP_INPUT:
+    case RV_OP_RANDOM:
+        *gl = 0;
+        out = make_int2((int)i, 1 << 1);
+        break;
+    case RV_OP_CONST:
+        out = make_int2(-1, cb);
+        break;
+    case RV_OP_ADD:
+    case RV_OP_SUB:
+        if (A.x == B.x) out = make_int2(-1, (A.y ^ B.y) & 1);       // x ^ x = 0 (or two constants)
+        else if (!is_row(A)) out = make_int2(B.x, B.y ^ (A.y & 1));  // a constant plus a row: the row
+        else if (!is_row(B)) out = make_int2(A.x, A.y ^ (B.y & 1));
+        else if (!chunk && uses[i] == 0) out = make_int2(-1, 0);    // an unread sum is dropped (a chunk counts no reads)
+        else {                                                      // two rows: a G_XORK
+            *gl = max(lvl_of(A), lvl_of(B)) + 1;
+            out = make_int2((int)i, (*gl + 1) << 1);
+            *mt = 1;
+        }
+        break;
+    case RV_OP_ADDCONST:
+    case RV_OP_SUBCONST:
+        out = make_int2(A.x, A.y ^ cb);
+        break;
+    case RV_OP_MULCONST:
+        out = cb ? A : make_int2(-1, 0);
+        break;
+    case RV_OP_MUL:
+        *gl = max(lvl_of(A), lvl_of(B)) + 1;
+        out = make_int2((int)i, (*gl + 1) << 1);
+        break;
+    default:  // AssertZero
+        *gl = lvl_of(A) + 1;
+        break;
+    }
+    return out;
+}
+// ... and at lazy_k = RV_LIN_K, lazy_slack = 1, balance = 0 (a forced compile): a sum of n rows read f times stays symbolic while
+// f x (n - 1) extra operand rows cost no more than the n reads and one write of materialising it
+__device__ inline uint4 value_lazy(const rv_op& op, uint32_t i, int2 p, const uint32_t* uses, const uint4* V3, const int* glvl, int* gl, uint32_t* mt) {
+    const uint4 A = form_of(V3, p.x), B = form_of(V3, p.y);
+    const uint32_t cb = (uint32_t)(op.imm & 1);
+    const uint4 none = make_uint4(0, 0, 0, 0);
+    uint4 out = none;
+    switch (op.opcode) {
+    case RV_OP_INPUT:
+    case RV_OP_RANDOM:
+        *gl = 0;
+        out = make_uint4(i, 0, 0, 1);
+        break;
+    case RV_OP_CONST:
+        out = make_uint4(0, 0, 0, cb << 2);
+        break;
+    case RV_OP_ADD:
+    case RV_OP_SUB: {
+        uint32_t rows[2 * RV_LIN_K];
+        const uint32_t n = (uint32_t)form_xor(A, B, rows), c = form_c(A) ^ form_c(B);
+        const uint32_t f = uses[i];
+        if (f == 0) break;  // an unread sum is dropped
+        if (n <= 1 || (n <= (uint32_t)RV_LIN_K && (uint64_t)f * (n - 1) <= (uint64_t)n + 1)) {
+            out = make_uint4(rows[0], rows[1], rows[2], n | c << 2);
+        } else {  // one G_XORK of n rows; the constant goes into the gate
+            int l = -1;
+#pragma unroll
+            for (int k = 0; k < 2 * RV_LIN_K; k++)
+                if ((uint32_t)k < n) l = max(l, glvl[rows[k] & ~ROW_COMP]);
+            *gl = l + 1;
+            *mt = 1;
+            out = make_uint4(i | ROW_COMP, 0, 0, 1u | n << 8);
+        }
+        break;
+    }
+    case RV_OP_ADDCONST:
+    case RV_OP_SUBCONST:
+        out = make_uint4(A.x, A.y, A.z, (A.w & 7u) ^ cb << 2);
+        break;
+    case RV_OP_MULCONST:
+        out = cb ? make_uint4(A.x, A.y, A.z, A.w & 7u) : none;
+        break;
+    case RV_OP_MUL:
+        *gl = max(form_lvl(A, glvl), form_lvl(B, glvl)) + 1;
+        out = make_uint4(i, 0, 0, 1);
+        break;
+    default:  // AssertZero
+        *gl = form_lvl(A, glvl) + 1;
+        break;
+    }
+    return out;
+}
+
 // step 3: one round.  rounds[r] = {first frontier slot, count}; the ops whose last pending operand this round resolves form
-// round r + 1's frontier
+// round r + 1's frontier.  LAZY: the values are lazy sums in V3 (V unused), else one row or a constant in V (V3 unused).
+template <bool LAZY>
 __global__ __launch_bounds__(TB) void k_cd_round(uint32_t r, uint32_t chunk, const rv_op* ops, const int2* prod, const uint32_t* uses, const uint32_t* cons_off,
-                                                 const uint32_t* cons, uint32_t* rem, int2* V, int* glvl, uint32_t* mat, uint32_t* frontier,
+                                                 const uint32_t* cons, uint32_t* rem, int2* V, uint4* V3, int* glvl, uint32_t* mat, uint32_t* frontier,
                                                  uint2* rounds) {
     // the next frontier is gathered in LDS and appended with one global atomic per workgroup (65 536 appends to one counter per
     // round of the benchmark circuit otherwise); what does not fit the LDS queue is appended one by one
@@ -309,48 +453,10 @@ __global__ __launch_bounds__(TB) void k_cd_round(uint32_t r, uint32_t chunk, con
         const uint32_t i = frontier[R.x + t];
         const rv_op op = ops[i];
         const int2 p = prod[i];
-        const int2 A = val_of(V, p.x), B = val_of(V, p.y);
-        const int cb = (int)(op.imm & 1);
-        int2 out = make_int2(-1, 0);
         int gl = -1;
         uint32_t mt = 0;
-        switch (op.opcode) {
-        case RV_OP_INPUT:
-        case RV_OP_RANDOM:
-            gl = 0;
-            out = make_int2((int)i, 1 << 1);
-            break;
-        case RV_OP_CONST:
-            out = make_int2(-1, cb);
-            break;
-        case RV_OP_ADD:
-        case RV_OP_SUB:
-            if (A.x == B.x) out = make_int2(-1, (A.y ^ B.y) & 1);       // x ^ x = 0 (or two constants)
-            else if (!is_row(A)) out = make_int2(B.x, B.y ^ (A.y & 1));  // a constant plus a row: the row
-            else if (!is_row(B)) out = make_int2(A.x, A.y ^ (B.y & 1));
-            else if (!chunk && uses[i] == 0) out = make_int2(-1, 0);    // an unread sum is dropped (a chunk counts no reads)
-            else {                                                      // two rows: a G_XORK
-                gl = max(lvl_of(A), lvl_of(B)) + 1;
-                out = make_int2((int)i, (gl + 1) << 1);
-                mt = 1;
-            }
-            break;
-        case RV_OP_ADDCONST:
-        case RV_OP_SUBCONST:
-            out = make_int2(A.x, A.y ^ cb);
-            break;
-        case RV_OP_MULCONST:
-            out = cb ? A : make_int2(-1, 0);
-            break;
-        case RV_OP_MUL:
-            gl = max(lvl_of(A), lvl_of(B)) + 1;
-            out = make_int2((int)i, (gl + 1) << 1);
-            break;
-        default:  // AssertZero
-            gl = lvl_of(A) + 1;
-            break;
-        }
-        V[i] = out;
+        if constexpr (LAZY) V3[i] = value_lazy(op, i, p, uses, V3, glvl, &gl, &mt);
+        else V[i] = value_k1(op, i, p, chunk, uses, V, &gl, &mt);
         glvl[i] = gl;
         mat[i] = mt;
         const uint32_t c0 = cons_off[i], c1 = c0 + uses[i];
@@ -376,8 +482,9 @@ struct DevStats {
     unsigned long long operand_rows;
 };
 // the gate count, materialised XORs, levels and operand rows (one atomic per workgroup and counter)
-__global__ __launch_bounds__(TB) void k_cd_stats(const rv_op* ops, size_t n, const int2* prod, const int2* V, const int* glvl, const uint32_t* mat,
-                                                 DevStats* st) {
+template <bool LAZY>
+__global__ __launch_bounds__(TB) void k_cd_stats(const rv_op* ops, size_t n, const int2* prod, const int2* V, const uint4* V3, const int* glvl,
+                                                 const uint32_t* mat, DevStats* st) {
     __shared__ int sl[TB];
     __shared__ uint32_t sg[TB], sm[TB], so[TB];
     const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
@@ -389,9 +496,15 @@ __global__ __launch_bounds__(TB) void k_cd_stats(const rv_op* ops, size_t n, con
         m = mat[i];
         const uint32_t opc = ops[i].opcode;
         const int2 p = prod[i];
-        if (opc == RV_OP_MUL) o = is_row(val_of(V, p.x)) + is_row(val_of(V, p.y));
-        else if (opc == RV_OP_ASSERTZERO) o = is_row(val_of(V, p.x));
-        else if (m) o = 2;
+        if constexpr (LAZY) {  // the rows of the operand forms; a materialised sum's own
+            if (opc == RV_OP_MUL) o = form_n(form_of(V3, p.x)) + form_n(form_of(V3, p.y));
+            else if (opc == RV_OP_ASSERTZERO) o = form_n(form_of(V3, p.x));
+            else if (m) o = V3[i].w >> 8;
+        } else {
+            if (opc == RV_OP_MUL) o = is_row(val_of(V, p.x)) + is_row(val_of(V, p.y));
+            else if (opc == RV_OP_ASSERTZERO) o = is_row(val_of(V, p.x));
+            else if (m) o = 2;
+        }
     }
     sl[threadIdx.x] = l, sg[threadIdx.x] = g, sm[threadIdx.x] = m, so[threadIdx.x] = o;
     __syncthreads();
@@ -413,9 +526,10 @@ __global__ __launch_bounds__(TB) void k_cd_stats(const rv_op* ops, size_t n, con
 }
 
 // step 5: the (level, class) key of every gate (LevelRange classes: Mul of one-base operands 0, other Mul 1, two-row Xor 2,
-// the rest 4; ops without a gate get `sentinel`, behind every gate)
-__global__ __launch_bounds__(TB) void k_cd_keys(const rv_op* ops, size_t n, const int2* prod, const int2* V, const int* glvl, const uint32_t* mat,
-                                                uint32_t sentinel, uint32_t* keys, uint32_t* vals) {
+// any other Xor 3 -- lazy sums only --, the rest 4; ops without a gate get `sentinel`, behind every gate)
+template <bool LAZY>
+__global__ __launch_bounds__(TB) void k_cd_keys(const rv_op* ops, size_t n, const int2* prod, const int2* V, const uint4* V3, const int* glvl,
+                                                const uint32_t* mat, uint32_t sentinel, uint32_t* keys, uint32_t* vals) {
     const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
     if (i >= n) return;
     const int l = glvl[i];
@@ -425,9 +539,11 @@ __global__ __launch_bounds__(TB) void k_cd_keys(const rv_op* ops, size_t n, cons
         uint32_t cls = 4;
         if (opc == RV_OP_MUL) {
             const int2 p = prod[i];
-            cls = (is_row(val_of(V, p.x)) && is_row(val_of(V, p.y))) ? 0u : 1u;
+            if constexpr (LAZY) cls = (form_n(form_of(V3, p.x)) == 1 && form_n(form_of(V3, p.y)) == 1) ? 0u : 1u;
+            else cls = (is_row(val_of(V, p.x)) && is_row(val_of(V, p.y))) ? 0u : 1u;
         } else if (mat[i]) {
             cls = 2;
+            if constexpr (LAZY) cls = (V3[i].w >> 8) == 2 ? 2u : 3u;
         }
         key = (uint32_t)l * 5u + cls;
     }
@@ -461,9 +577,11 @@ __device__ inline uint32_t wave_max_u32(uint32_t v) {
 }
 // the gate records in (level, class, program) order, the per-level mask blocks and the online rows' levels
 // (pad: the PRG rows, whole cipher blocks; a gate with key >= 4 sits behind the chunk's materialised carried forms)
+// LAZY: Builder::fill of whole forms (up to RV_LIN_K rows per operand), a materialised sum of up to 2 RV_LIN_K rows
+template <bool LAZY>
 __global__ __launch_bounds__(TB) void k_cd_gates(const uint32_t* sk, const uint32_t* sv, size_t n_gates, const rv_op* ops, const int2* prod, const int2* V,
-                                                 const C4* cx, const uint32_t* comp, Seeds s, uint32_t pad, Gate* gates, uint32_t* need_raw,
-                                                 uint32_t* on_lvl) {
+                                                 const uint4* V3, const C4* cx, const uint32_t* comp, Seeds s, uint32_t pad, Gate* gates,
+                                                 uint32_t* need_raw, uint32_t* on_lvl) {
     const size_t p = (size_t)blockIdx.x * TB + threadIdx.x;
     const bool valid = p < n_gates;
     uint32_t l = 0, need = 0;
@@ -473,7 +591,10 @@ __global__ __launch_bounds__(TB) void k_cd_gates(const uint32_t* sk, const uint3
         const rv_op op = ops[i];
         const C4 c = cx[i];
         const int2 pr = prod[i];
-        const int2 A = val_of(V, pr.x), B = val_of(V, pr.y);
+        int2 A = make_int2(-1, 0), B = A;
+        uint4 FA = make_uint4(0, 0, 0, 0), FB = FA;
+        if constexpr (LAZY) FA = form_of(V3, pr.x), FB = form_of(V3, pr.y);
+        else A = val_of(V, pr.x), B = val_of(V, pr.y);
         const uint32_t e = c.in + c.mul + c.as, x = c.mul + c.as;  // e: the online row among the piece's own
         const uint32_t eo = s.on0 + e, m = s.m0 + c.m, zero = s.base + pad;
         Gate g;
@@ -494,10 +615,19 @@ __global__ __launch_bounds__(TB) void k_cd_gates(const uint32_t* sk, const uint3
             need = m / 128 + 1;
             break;
         case RV_OP_MUL: {
-            const uint32_t na = is_row(A), nb = is_row(B);
-            g.op = G_MUL | na << 8 | nb << 12 | (uint32_t)(A.y & 1) << 16 | (uint32_t)(B.y & 1) << 17;
-            if (na) g.a[0] = row_index(ops, cx, comp, s, pad, A.x);
-            if (nb) g.b[0] = row_index(ops, cx, comp, s, pad, B.x);
+            if constexpr (LAZY) {
+                const uint32_t na = form_n(FA), nb = form_n(FB);
+                g.op = G_MUL | na << 8 | nb << 12 | form_c(FA) << 16 | form_c(FB) << 17;
+                for (int k = 0; k < RV_LIN_K; k++) {
+                    if ((uint32_t)k < na) g.a[k] = row_index(ops, cx, comp, s, pad, (int)(form_row(FA, k) & ~ROW_COMP));
+                    if ((uint32_t)k < nb) g.b[k] = row_index(ops, cx, comp, s, pad, (int)(form_row(FB, k) & ~ROW_COMP));
+                }
+            } else {
+                const uint32_t na = is_row(A), nb = is_row(B);
+                g.op = G_MUL | na << 8 | nb << 12 | (uint32_t)(A.y & 1) << 16 | (uint32_t)(B.y & 1) << 17;
+                if (na) g.a[0] = row_index(ops, cx, comp, s, pad, A.x);
+                if (nb) g.b[0] = row_index(ops, cx, comp, s, pad, B.x);
+            }
             g.m = s.base + m;
             g.dst = s.base + m + 1;
             g.eo = eo;
@@ -508,15 +638,34 @@ __global__ __launch_bounds__(TB) void k_cd_gates(const uint32_t* sk, const uint3
             break;
         }
         case RV_OP_ASSERTZERO: {
-            const uint32_t na = is_row(A);
-            g.op = G_ASSERT | na << 8 | (uint32_t)(A.y & 1) << 16;
-            if (na) g.a[0] = row_index(ops, cx, comp, s, pad, A.x);
+            if constexpr (LAZY) {
+                const uint32_t na = form_n(FA);
+                g.op = G_ASSERT | na << 8 | form_c(FA) << 16;
+                for (int k = 0; k < RV_LIN_K; k++)
+                    if ((uint32_t)k < na) g.a[k] = row_index(ops, cx, comp, s, pad, (int)(form_row(FA, k) & ~ROW_COMP));
+            } else {
+                const uint32_t na = is_row(A);
+                g.op = G_ASSERT | na << 8 | (uint32_t)(A.y & 1) << 16;
+                if (na) g.a[0] = row_index(ops, cx, comp, s, pad, A.x);
+            }
             g.eo = eo;
             g.x = x;
             on_lvl[e] = l;
             break;
         }
         default: {  // a materialised Add / Sub: its two rows in the host compiler's order
+            if constexpr (LAZY) {  // (Builder::materialise: the first RV_LIN_K rows in a[], the rest in b[], the constant in the gate)
+                uint32_t rows[2 * RV_LIN_K];
+                const uint32_t nr = (uint32_t)form_xor(FA, FB, rows), na = min(nr, (uint32_t)RV_LIN_K);
+                g.op = G_XORK | na << 8 | (nr - na) << 12 | (form_c(FA) ^ form_c(FB)) << 16;
+#pragma unroll
+                for (int k = 0; k < RV_LIN_K; k++) {
+                    if ((uint32_t)k < nr) g.a[k] = row_index(ops, cx, comp, s, pad, (int)(rows[k] & ~ROW_COMP));
+                    if ((uint32_t)(RV_LIN_K + k) < nr) g.b[k] = row_index(ops, cx, comp, s, pad, (int)(rows[RV_LIN_K + k] & ~ROW_COMP));
+                }
+                g.dst = zero + 1 + comp[i];
+                break;
+            }
             const uint32_t ra = row_index(ops, cx, comp, s, pad, A.x), rb = row_index(ops, cx, comp, s, pad, B.x);
             const uint32_t ka = row_rank(s, pad, ra), kb = row_rank(s, pad, rb);
             const bool a_first = ka < kb || (ka == kb && ra < rb);
@@ -603,7 +752,11 @@ inline int bit_len(uint64_t v) {
     return b;
 }
 
-// device allocations of one compile, given back (after a stream sync) when it ends
+// device allocations of one compile, given back (after a stream sync) when it ends.  Per op, beside the caller's 24-byte op and the
+// 48-byte gate records that stay with the circuit: counters 16, two key / value pairs of the sorts 16, producers 8, read counts,
+// pending operands, consumer offsets and cursors 16, consumers 8, value 8 (the lazy-sum form: 16), level, materialised flag, frontier
+// and computed-row index 16, the sorts' histograms 0.5: 89 bytes (lazy sums: 97); 8 bytes per wire for the writer segments, and a chunk
+// 20 more for its write-back flags and last writers
 struct Scratch {
     const DevAlloc& A;
     hipStream_t st;
@@ -659,7 +812,8 @@ hipError_t radix_sort(Scratch& S, hipStream_t st, uint32_t* k[2], uint32_t* v[2]
 int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, bool keep_wires,
                        int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps, const ChunkStart* chunk) {
     // (a Z64 op in the list is what sends a program to the host; the Z64 wire count alone does not)
-    if (keep_wires || force_lazy_k || getenv("RV_LAZY_K") || (n_ops == 0 && !chunk) || n_ops >= (1u << 28) || gf2_wires >= (1u << 31) ||
+    const bool lazy = force_lazy_k == RV_LIN_K;  // the lazy-sum form: whole programs only (a chunk is final at K = 1)
+    if (keep_wires || (force_lazy_k && (!lazy || chunk)) || getenv("RV_LAZY_K") || (n_ops == 0 && !chunk) || n_ops >= (1u << 28) || gf2_wires >= (1u << 31) ||
         (chunk && gf2_wires >= (1u << 30)))  // (a chunk names wire w's carried row -2 - w, below the host compiler's CARRY flag bit)
         return RV_COMPILE_FALLBACK;
     const size_t n = n_ops;
@@ -761,13 +915,14 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     CDCHK(hipGetLastError());
     mark(2);
     // ---- 3. values and levels, round by round ----
-    int2* V = S.get<int2>(n);
+    int2* V = lazy ? nullptr : S.get<int2>(n);
+    uint4* V3 = lazy ? S.get<uint4>(n) : nullptr;
     int* glvl = S.get<int>(n);
     uint32_t* mat = S.get<uint32_t>(n + 1);
     uint32_t* frontier = S.get<uint32_t>(n);
     const uint32_t max_rounds = (uint32_t)std::min<size_t>(n + 1, MAX_ROUNDS);
     uint2* rounds = S.get<uint2>((size_t)max_rounds + 2);
-    CDNEED(V && glvl && mat && frontier && rounds);
+    CDNEED((V || V3) && glvl && mat && frontier && rounds);
     CDCHK(hipMemsetAsync(rounds, 0, ((size_t)max_rounds + 2) * sizeof(uint2), st));
     CDCHK(hipMemsetAsync(mat + n, 0, 4, st));
     k_cd_front0<<<gb, TB, 0, st>>>(rem, n, frontier, rounds);
@@ -778,7 +933,10 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     while (!done) {
         if (r >= max_rounds) return RV_COMPILE_FALLBACK;  // (the cap: a chain of ops this deep compiles on the host)
         const uint32_t e = std::min(r + batch, max_rounds);
-        for (; r < e; r++) k_cd_round<<<round_blocks, TB, 0, st>>>(r, seeds.chunk, d_ops, prod, uses, cons_off, cons, rem, V, glvl, mat, frontier, rounds);
+        for (; r < e; r++) {
+            if (lazy) k_cd_round<true><<<round_blocks, TB, 0, st>>>(r, 0u, d_ops, prod, uses, cons_off, cons, rem, V, V3, glvl, mat, frontier, rounds);
+            else k_cd_round<false><<<round_blocks, TB, 0, st>>>(r, seeds.chunk, d_ops, prod, uses, cons_off, cons, rem, V, V3, glvl, mat, frontier, rounds);
+        }
         CDCHK(hipGetLastError());
         uint2 nxt;
         CDCHK(hipMemcpyAsync(&nxt, rounds + r, sizeof nxt, hipMemcpyDeviceToHost, st));
@@ -790,7 +948,8 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
         batch = std::min<uint32_t>(batch * 2, 256);
     }
     if (laps) laps->rounds = r;
-    k_cd_stats<<<gb, TB, 0, st>>>(d_ops, n, prod, V, glvl, mat, d_stats);
+    if (lazy) k_cd_stats<true><<<gb, TB, 0, st>>>(d_ops, n, prod, V, V3, glvl, mat, d_stats);
+    else k_cd_stats<false><<<gb, TB, 0, st>>>(d_ops, n, prod, V, V3, glvl, mat, d_stats);
     CDCHK(hipGetLastError());
     // ---- 6a. (chunk mode) the wires the piece wrote, while the writers sort is still in place ----
     C4* wfl = nullptr;
@@ -818,8 +977,8 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     const uint32_t n_levels = n_wb ? wb_level + 1 : n_levels_ops;
     const uint64_t n_gates = n_gates_ops + n_wbmat + n_wb;
     // the K = 1 compile is final unless the circuit is deep and narrow (compile_ops_seq): those go to the host compiler
-    // (a chunk is compiled once, at K = 1, whatever its shape)
-    if (!chunk && n_levels && lazy_forms_pay(n_levels, n_gates)) return RV_COMPILE_FALLBACK;
+    // (a chunk is compiled once, at K = 1, whatever its shape; a forced lazy-sum compile is final too)
+    if (!chunk && !lazy && n_levels && lazy_forms_pay(n_levels, n_gates)) return RV_COMPILE_FALLBACK;
     const uint64_t n_masks = (uint64_t)seeds.m0 + tot.m;
     const uint64_t n_masks_pad = (n_masks + 127) / 128 * 128;
     const uint64_t n_comp = 1 + (uint64_t)hs.n_mat + n_wbmat;
@@ -832,7 +991,8 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     CDCHK((scan_excl<uint32_t, SumU32>(S, st, mat, comp, n + 1, nullptr)));
     // ---- 5. tables ----
     const uint32_t n_buckets = n_levels_ops * 5;  // (of the ops' gates: the write-back gates do not go through the sort)
-    k_cd_keys<<<gb, TB, 0, st>>>(d_ops, n, prod, V, glvl, mat, n_buckets, kbuf[0], vbuf[0]);
+    if (lazy) k_cd_keys<true><<<gb, TB, 0, st>>>(d_ops, n, prod, V, V3, glvl, mat, n_buckets, kbuf[0], vbuf[0]);
+    else k_cd_keys<false><<<gb, TB, 0, st>>>(d_ops, n, prod, V, V3, glvl, mat, n_buckets, kbuf[0], vbuf[0]);
     CDCHK(hipGetLastError());
     CDCHK(radix_sort(S, st, kbuf, vbuf, n, bit_len(n_buckets), &which));
     void* pg = nullptr;
@@ -848,9 +1008,12 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     CDCHK(hipMemsetAsync(need_raw, 0, std::max<size_t>(n_levels, 1) * 4, st));
     CDCHK(hipMemsetAsync(on_lvl + n_on, 0, 4, st));
     k_cd_bounds<<<blocks(n_gates_ops + 1, TB), TB, 0, st>>>(kbuf[which], n_gates_ops, n_buckets, pos);
-    if (n_gates_ops)
-        k_cd_gates<<<blocks(n_gates_ops, TB), TB, 0, st>>>(kbuf[which], vbuf[which], n_gates_ops, d_ops, prod, V, cx, comp, seeds, (uint32_t)n_masks_pad,
-                                                           gates, need_raw, on_lvl);
+    if (n_gates_ops && lazy)
+        k_cd_gates<true><<<blocks(n_gates_ops, TB), TB, 0, st>>>(kbuf[which], vbuf[which], n_gates_ops, d_ops, prod, V, V3, cx, comp, seeds,
+                                                                 (uint32_t)n_masks_pad, gates, need_raw, on_lvl);
+    else if (n_gates_ops)
+        k_cd_gates<false><<<blocks(n_gates_ops, TB), TB, 0, st>>>(kbuf[which], vbuf[which], n_gates_ops, d_ops, prod, V, V3, cx, comp, seeds,
+                                                                  (uint32_t)n_masks_pad, gates, need_raw, on_lvl);
     if (n_wb)
         k_cd_wb_gates<<<blocks(W, TB), TB, 0, st>>>(lastw, wfl, W, d_ops, V, cx, comp, seeds, (uint32_t)n_masks_pad, hs.n_mat, n_buckets >= 3 ? pos + 3 : nullptr,
                                                     (uint32_t)(n_gates_ops + n_wbmat), gates);

@@ -139,7 +139,8 @@ extern "C" int rv_prove_ops(rv_ctx* ctx, const rv_op* ops, size_t n_ops, const u
     int rc;
     try {
         // (under RV_COMPILE_DEVICE the prover's circuit is the device compiler's K = 1 form instead of the RV_COMPILE_WHOLE_PROVER
-        // one, which it does not build: the proof bytes are the same, header)
+        // one: the proof bytes are the same, header.  The device compiler builds the lazy-sum form too; asking it for that here made
+        // the cold call faster but not, measurably, the calls after it -- DESIGN.md 14.2)
         const uint32_t fl = (ctx && (ctx->compile_flags & RV_COMPILE_DEVICE)) ? RV_COMPILE_DEVICE : RV_COMPILE_WHOLE_PROVER;
         rc = ops_cache_get(ctx, ops, n_ops, z64_wires, gf2_wires, fl, &c, &hit, &owned);
     } catch (...) {

@@ -74,8 +74,9 @@ class Circuit:
         RV_COMPILE_WHOLE_PROVER hint of rv_circuit_compile_ex; any use of the circuit still gives identical bytes.
         keep_wires: RV_COMPILE_KEEP_WIRES -- the circuit keeps every wire's final value form, so that `evaluate` can return
         wire values (proofs stay byte-identical).
-        device_compile: RV_COMPILE_DEVICE -- the ops are uploaded and compiled on the GPU (GF(2) programs; anything the device
-        path does not take is compiled on the host); the circuit is the same either way."""
+        device_compile: RV_COMPILE_DEVICE -- the ops are uploaded and compiled on the GPU (GF(2) programs, in the plain form or, with
+        whole_prover, the lazy-sum form; anything the device path does not take is compiled on the host); the circuit is the same
+        either way, and `compiled_on_device` tells which compiler made it."""
         self.ctx = ctx or Context.default()
         self.ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
         self.wire_counts = (int(wire_counts[0]), int(wire_counts[1]))  # (z64, gf2), proof/mod.rs:125
@@ -93,7 +94,8 @@ class Circuit:
         """rv_circuit_compile_device: compile an op list that already sits in GPU memory -- a torch tensor on the context's
         device holding packed 24-byte rv_op records, as uint8 of shape [n, 24] (or [n * 24]) or int64 / uint64 of shape [n, 3];
         contiguous.  The tensor is not copied to the host unless the device path hands the program to the host compiler; the
-        caller keeps it.  The circuit is the one Circuit(host ops, device_compile=True) compiles."""
+        caller keeps it.  The circuit is the one Circuit(host ops, device_compile=True) compiles, with whole_prover the lazy-sum
+        form (also built on the device)."""
         import torch
 
         if not isinstance(ops, torch.Tensor) or ops.device.type != "cuda":
@@ -131,6 +133,14 @@ class Circuit:
         _lib.check(_lib.lib().rv_circuit_early_staging_bytes(self.handle, C.byref(esb)))
         d["early_staging_bytes"] = int(esb.value)
         return d
+
+    @property
+    def compiled_on_device(self) -> bool:
+        """rv_circuit_compiled_on_device: True when the device compiler made this circuit, False when the host compiler did (no
+        device_compile, or a program the device path handed back)."""
+        on = C.c_int()
+        _lib.check(_lib.lib().rv_circuit_compiled_on_device(self.handle, C.byref(on)))
+        return bool(on.value)
 
     def evaluate(self, wit_gf2, wit_z64=()) -> "Evaluation":
         """Cleartext evaluation on the GPU (rv_evaluate): `ok`, `n_failed`, `first_failed_op` (op-list index of the first

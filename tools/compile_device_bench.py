@@ -1,8 +1,10 @@
 """Cold compiles of the 10^7-gate benchmark circuit (config 4) and its all-AND variant, host compiler against the device compiler
 (RV_COMPILE_DEVICE), in one process on one GPU: rv_circuit_compile_ex wall time (compile + upload, the compiled circuit resident in
-HBM), the library's own compile_us / upload_us, the device compiler's per-phase laps (HIP events), and a cold rv_prove_ops with and
-without the context flag (the ops cache cleared before every call).
-usage: python tools/compile_device_bench.py [reps]"""
+HBM), the library's own compile_us / upload_us, the device compiler's per-phase laps (HIP events), and rv_prove_ops with and
+without the context flag: cold (the ops cache cleared before the call) and once more on the same ops (from the ops cache).
+Medians of `reps` runs after a warm-up, with [min, max] beside them.  --whole-prover: the same table with RV_COMPILE_WHOLE_PROVER
+on both compilers (the lazy-sum form).
+usage: python tools/compile_device_bench.py [--whole-prover] [reps]"""
 import ctypes as C
 import json
 import os
@@ -19,7 +21,10 @@ import reverie_amd  # noqa: E402
 from reverie_amd import _lib  # noqa: E402
 
 L = _lib.lib()
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 3
+args = [a for a in sys.argv[1:] if a != "--whole-prover"]
+WP = _lib.RV_COMPILE_WHOLE_PROVER if "--whole-prover" in sys.argv[1:] else 0
+DEV = _lib.RV_COMPILE_DEVICE
+reps = int(args[0]) if args else 3
 ctx = reverie_amd.Context(0)
 seeds = np.arange(4096, dtype=np.uint32).astype(np.uint8).reshape(256, 16)
 out = {}
@@ -39,13 +44,22 @@ def compile_ms(prog, wc, flags):
 
 
 def prove_ops_ms(prog, wit, wc, flags):
+    """-> (cold ms, second-call ms, proof bytes)"""
     L.rv_ctx_set_compile_flags(ctx.handle, C.c_uint32(flags))
     L.rv_ctx_ops_cache_clear(ctx.handle)
-    t = time.perf_counter()
-    p = reverie_amd.Proof.new(prog, wit, [], wc, seeds=seeds, ctx=ctx)
-    ms = (time.perf_counter() - t) * 1e3
+    ms = []
+    for _ in range(2):
+        t = time.perf_counter()
+        p = reverie_amd.Proof.new(prog, wit, [], wc, seeds=seeds, ctx=ctx)
+        ms.append((time.perf_counter() - t) * 1e3)
     L.rv_ctx_set_compile_flags(ctx.handle, C.c_uint32(0))
-    return ms, bytes(p)
+    return ms[0], ms[1], bytes(p)
+
+
+def med(v):
+    """median [min, max]"""
+    v = np.asarray(v, float)
+    return [round(float(np.median(v)), 2), round(float(v.min()), 2), round(float(v.max()), 2)]
 
 
 for name, p_and in (("config4", 0.5), ("all_and", 1.0)):
@@ -53,23 +67,32 @@ for name, p_and in (("config4", 0.5), ("all_and", 1.0)):
     wit = list(wit)
     path, diff = C.c_int(), C.c_int()
     assert L.rv_hook_compile_compare_device(ctx.handle, prog.ctypes.data_as(C.c_void_p), C.c_size_t(len(prog)), C.c_size_t(wc[0]),
-                                            C.c_size_t(wc[1]), C.c_uint32(0), C.byref(path), C.byref(diff)) == 0
-    rec = {"ops": len(prog), "device_path": path.value, "diff": diff.value, "host": [], "device": [], "laps_ms": []}
-    compile_ms(prog, wc, 0)  # (warm-up: the arena's blocks, the page-locked staging buffer)
-    compile_ms(prog, wc, 4)
+                                            C.c_size_t(wc[1]), C.c_uint32(WP | DEV if WP else 0), C.byref(path), C.byref(diff)) == 0
+    rec = {"ops": len(prog), "whole_prover": bool(WP), "device_path": path.value, "diff": diff.value, "host": [], "device": [], "laps_ms": []}
+    compile_ms(prog, wc, WP)  # (warm-up: the arena's blocks, the page-locked staging buffer)
+    compile_ms(prog, wc, WP | DEV)
     for _ in range(reps):
-        rec["host"].append(compile_ms(prog, wc, 0))
-        rec["device"].append(compile_ms(prog, wc, 4))
+        rec["host"].append(compile_ms(prog, wc, WP))
+        rec["device"].append(compile_ms(prog, wc, WP | DEV))
         laps = (C.c_double * 6)()
         L.rv_hook_compile_device_laps(laps)
         rec["laps_ms"].append(dict(zip(("classify", "writers", "levels", "tables", "download", "rounds"), [round(x, 3) for x in laps])))
-    hp, hb = prove_ops_ms(prog, wit, wc, 0)
-    dp, db = prove_ops_ms(prog, wit, wc, 4)
-    rec["prove_ops_cold_ms"] = {"host": round(hp, 2), "device": round(dp, 2), "same_bytes": hb == db}
+    # rv_prove_ops chooses its own form (the context flag decides where it is compiled): the same rows with and without --whole-prover
+    prove_ops_ms(prog, wit, wc, 0)
+    runs = {"host": [], "device": []}
+    same = True
+    for _ in range(reps):
+        h = prove_ops_ms(prog, wit, wc, 0)
+        d = prove_ops_ms(prog, wit, wc, DEV)
+        runs["host"].append(h[:2])
+        runs["device"].append(d[:2])
+        same = same and h[2] == d[2]
+    rec["prove_ops_cold_ms"] = {k: med([r[0] for r in v]) for k, v in runs.items()}
+    rec["prove_ops_second_ms"] = {k: med([r[1] for r in v]) for k, v in runs.items()}
+    rec["prove_ops_same_bytes"] = same
     for k in ("host", "device"):
         v = np.array(rec[k])
-        rec[k + "_ms"] = {"wall": round(float(np.median(v[:, 0])), 2), "compile": round(float(np.median(v[:, 1])), 2),
-                          "upload": round(float(np.median(v[:, 2])), 2)}
+        rec[k + "_ms"] = {"wall": med(v[:, 0]), "compile": med(v[:, 1]), "upload": med(v[:, 2])}
         del rec[k]
     out[name] = rec
     print(name, json.dumps(rec), flush=True)
