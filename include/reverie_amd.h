@@ -643,6 +643,16 @@ int rv_hook_expand_seed(rv_ctx *ctx, const uint8_t *seeds, size_t n, uint8_t *ke
 int rv_hook_sharegen_gf2(rv_ctx *ctx, const uint8_t *keys, const uint32_t omit[8], size_t n, uint64_t *out);
 /* ShareGen<Z64>::next() x n -> n x 8 x 8 u64 */
 int rv_hook_sharegen_z64(rv_ctx *ctx, const uint8_t *keys, const uint32_t omit[8], size_t n, uint64_t *out);
+/* One mask generator as a shard of R repetitions launches it (R a multiple of 8, at most 256; rows of R/4 quad words), on CTR blocks
+ * [first_block, first_block + n_blocks) of the 8 R player keys of seeds [R][16].
+ *   omit       [R], 0..7 = the player whose stream stays zero, 8 = none; NULL = the prover's launch (no keep words at all)
+ *   generator  0 = the 128-plane GF(2) generator, 1 = the lane-distributed GF(2) generator, 2 = the Z64 generator
+ *   key_path   0 = expand_seeds + key_schedule + bitslice_rk (+ the lane-distributed key image), 1 = the one-launch key setup
+ *   out        the device rows as they are: GF(2) uint32 [n_blocks * 128][R/4], Z64 uint64 [2 * n_blocks][8 R]
+ * Checked before anything is launched: RV_E_UNSUPPORTED for generator 1 at a width it does not take (R/4 not a multiple of 16) and for
+ * first_block + n_blocks > 2^24; RV_E_ARG for any other R, an omit value above 8, n_blocks == 0, an unknown generator or key path. */
+int rv_hook_maskgen(rv_ctx *ctx, const uint8_t *seeds, uint32_t R, const uint8_t *omit, uint32_t generator, uint32_t key_path,
+                    uint64_t first_block, uint64_t n_blocks, void *out);
 /* The gate-stream compiler alone (host only, no device: ctx-free): what rv_circuit_compile_ex would report through
  * rv_circuit_get_info -- the counters that are pure functions of the op list (ShareGen::next() calls per repetition,
  * generator/share.rs:54-65; transcript events, prover.rs:194,210,216), dependency levels, operand rows -- and the errors the

@@ -89,6 +89,16 @@ void rvo_expand_seed(const uint8_t seed[16], uint8_t keys[8][16]) { /* transcrip
     for (int p = 0; p < 8; p++) rvo_prg_gen(&prg, keys[p], 16);
 }
 
+/* ------------------------------------------------------------------ bulk keystream */
+void rvo_prg_blocks(const uint8_t *keys, size_t n_keys, uint64_t first_block, size_t n_blocks, uint8_t *out) {
+    for (size_t k = 0; k < n_keys; k++) { /* prg.rs:16-37 with the counter started at first_block */
+        rvo_prg prg;
+        rvo_prg_init(&prg, keys + 16 * k);
+        prg.ctr_lo = first_block;
+        rvo_prg_gen(&prg, out + 16 * k * n_blocks, 16 * n_blocks);
+    }
+}
+
 /* ------------------------------------------------------------------ GF2 algebra */
 uint64_t rvo_gf2_reconstruct(uint64_t t) { /* gf2/domain.rs:47-63 */
     t ^= t >> 4;

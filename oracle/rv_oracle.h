@@ -106,6 +106,10 @@ void rvo_free(void *p);
 /* expand_seed (transcript/mod.rs:99-106): rep seed -> 8 player keys */
 void rvo_expand_seed(const uint8_t seed[16], uint8_t keys[8][16]);
 
+/* PRG keystream (crypto/prg.rs:16-37) in bulk: blocks [first_block, first_block + n_blocks) of each of n_keys keys
+ * [n_keys][16] -> out [n_keys][n_blocks][16].  Block by block this is rvo_prg_block. */
+void rvo_prg_blocks(const uint8_t *keys, size_t n_keys, uint64_t first_block, size_t n_blocks, uint8_t *out);
+
 /* ShareGen<GF2>::next() x n (generator/share.rs:54-65).  keys [8 reps][8 players][16],
  * omit[8] (8 = none).  out: n packed u64 shares. */
 void rvo_sharegen_gf2(const uint8_t *keys, const uint32_t omit[8], size_t n, uint64_t *out);

@@ -90,6 +90,7 @@ SYMBOLS = [
     "rv_circuit_compile_device", "rv_ctx_set_compile_flags", "rv_hook_compile_compare_device", "rv_hook_compile_device_laps",
     "rv_stream_set_compile_flags", "rv_eval_stream_set_compile_flags", "rv_hook_compile_compare_device_chunk", "rv_hook_stream_device_chunks",
     "rv_circuit_compiled_on_device",
+    "rv_hook_maskgen",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -119,6 +120,8 @@ ARGTYPES = {
     "rv_hook_compile_compare_device_chunk": [_P, _P, _Z, _Z, _Z, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "rv_hook_stream_device_chunks": [],
     "rv_circuit_compiled_on_device": [_P, C.POINTER(C.c_int)],
+    # the mask generators (parity hook)
+    "rv_hook_maskgen": [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _P],
 }
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1

@@ -364,18 +364,10 @@ __device__ __forceinline__ void round_cols(const uint32_t* s, uint32_t* n, const
 // counter, so round 1 is 3 S-boxes plus the linear spread of those three bytes over K1 instead of 16 S-boxes and a
 // full MixColumns, and round 2 reads 4 of its 16 S-box outputs from LDS.  Rounds 3..9 run two per loop trip so no
 // register shuffling is needed at the back edge.
-// REP (rep-major mask generator): the lane's 32 slots are 4 CONSECUTIVE counter blocks x 8 players of one repetition
-// (counter 4j + c in byte c from the MSB), so the two lowest counter bits are constants of the slot position and the
-// rest is j shifted up by two; otherwise all 32 slots share the counter j.
-template <bool REP>
-__device__ __forceinline__ uint32_t ctr_bit_word(uint64_t j, int bit) {
-    if (!REP) return (uint32_t)0 - (uint32_t)((j >> bit) & 1);
-    if (bit == 0) return 0x00FF00FFu;  // c & 1: bytes 1 and 3 (from the MSB)
-    if (bit == 1) return 0x0000FFFFu;  // c & 2: bytes 2 and 3
-    return (uint32_t)0 - (uint32_t)((j >> (bit - 2)) & 1);
-}
+// All 32 slots of a lane share the counter j: its bit `bit`, in every slot.
+__device__ __forceinline__ uint32_t ctr_bit_word(uint64_t j, int bit) { return (uint32_t)0 - (uint32_t)((j >> bit) & 1); }
 
-template <int QW, bool REP = false>
+template <int QW>
 __device__ __forceinline__ void rounds_0_to_9(uint64_t j, uint32_t* s, uint32_t* t, const uint32_t* rkl) {
     const uint32_t* a0 = rkl;             // area 0: SK (bytes 0..3), rk0[13..15] (bytes 13..15)
     const uint32_t* k1 = rkl + 128 * QW;  // area 1: K1
@@ -386,7 +378,7 @@ __device__ __forceinline__ void rounds_0_to_9(uint64_t j, uint32_t* s, uint32_t*
         uint32_t v[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-            const uint32_t cb = ctr_bit_word<REP>(j, 8 * (15 - b) + k);
+            const uint32_t cb = ctr_bit_word(j, 8 * (15 - b) + k);
             v[k] = a0[(8 * b + k) * QW] ^ cb;
         }
         sbox8(v[7], v[6], v[5], v[4], v[3], v[2], v[1], v[0]);

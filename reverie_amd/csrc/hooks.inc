@@ -104,6 +104,59 @@ extern "C" int rv_hook_sharegen_z64(rv_ctx* ctx, const uint8_t* keys, const uint
     return RV_OK;
 }
 
+// Every mask generator as a shard launches it (shard.inc: shard_setup_prg), at any shard width, counter window and key setup
+extern "C" int rv_hook_maskgen(rv_ctx* ctx, const uint8_t* seeds, uint32_t R, const uint8_t* omit, uint32_t generator, uint32_t key_path,
+                               uint64_t first_block, uint64_t n_blocks, void* out) {
+    if (!ctx || !seeds || !out || !n_blocks || generator > 2 || key_path > 1) return RV_E_ARG;
+    if (!R || R % 8 || R > RV_TOTAL_REPS) return RV_E_ARG;
+    if (first_block > RV_MAX_CTR_BLOCKS || n_blocks > RV_MAX_CTR_BLOCKS - first_block) return RV_E_UNSUPPORTED;
+    const uint32_t NQ = R / 4;
+    const bool col4 = generator == 1;
+    if (col4 && !aes_col4_supports(NQ)) return RV_E_UNSUPPORTED;
+    std::vector<uint32_t> keep(NQ, 0xFFFFFFFFu);
+    if (omit)
+        for (uint32_t r = 0; r < R; r++) {
+            if (omit[r] > 8) return RV_E_ARG;
+            if (omit[r] < 8) keep[r / 4] &= ~(1u << (31 - 8 * (r % 4) - omit[r]));
+        }
+    HIPCHK(hipSetDevice(ctx->device));
+    // what the launch writes: GF(2) rows [n_blocks * 128][NQ] u32, Z64 rows [2 * n_blocks][NQ * 32] u64
+    const size_t out_words = generator == 2 ? (size_t)n_blocks * 2 * NQ * 32 * 2 : (size_t)n_blocks * 128 * NQ;
+    uint8_t *ds = nullptr, *dk = nullptr, *drkb = nullptr;
+    uint32_t *d_rk = nullptr, *d_img = nullptr, *d_keep = nullptr, *d_out = nullptr;
+    int rc;
+    if ((rc = dalloc(ctx, (size_t)R * 16, &ds)) || (rc = dalloc(ctx, (size_t)R * 128, &dk)) || (rc = dalloc(ctx, (size_t)R * 8 * RK_BYTES, &drkb)) ||
+        (rc = dalloc(ctx, (size_t)RK_AREAS * 128 * NQ, &d_rk)) || (omit && (rc = dalloc(ctx, NQ, &d_keep))) ||
+        (col4 && (rc = dalloc(ctx, aes_col4_image_bytes(NQ) / 4, &d_img))) || (rc = dalloc(ctx, out_words, &d_out)))
+        return rc;
+    HIPCHK(hipMemcpyAsync(ds, seeds, (size_t)R * 16, hipMemcpyHostToDevice, ctx->stream));
+    if (omit) HIPCHK(hipMemcpyAsync(d_keep, keep.data(), (size_t)NQ * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (key_path == 0) {
+        launch_expand_seeds(ctx->stream, ds, R, dk);
+        launch_key_schedule(ctx->stream, dk, R * 8, drkb);
+        launch_bitslice_rk(ctx->stream, drkb, NQ, d_rk);
+        if (col4) launch_rk_col4(ctx->stream, d_rk, NQ, d_img);
+    } else {
+        launch_setup_keys(ctx->stream, ds, NQ, dk, drkb, d_rk, d_img);
+    }
+    if (generator == 0)
+        launch_aes_gf2_masks(ctx->stream, d_rk, d_keep, NQ, first_block, n_blocks, d_out);
+    else if (generator == 1)
+        launch_aes_gf2_masks_col4(ctx->stream, d_img, d_keep, NQ, first_block, n_blocks, d_out);
+    else
+        launch_aes_z64_masks(ctx->stream, d_rk, d_keep, NQ, n_blocks, (uint64_t*)d_out, first_block);
+    HIPCHK(hipMemcpyAsync(out, d_out, out_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->release(ds);
+    ctx->release(dk);
+    ctx->release(drkb);
+    ctx->release(d_rk);
+    if (d_keep) ctx->release(d_keep);
+    if (d_img) ctx->release(d_img);
+    ctx->release(d_out);
+    return RV_OK;
+}
+
 extern "C" int rv_hook_blake3(rv_ctx* ctx, const uint8_t* data, size_t n_streams, size_t len, uint8_t* out) {
     if (!ctx || !out || !n_streams || (len && !data)) return RV_E_ARG;
     HIPCHK(hipSetDevice(ctx->device));

@@ -107,6 +107,14 @@ def expand_seed(seed) -> np.ndarray:
     return keys
 
 
+def prg_blocks(keys, first_block, n_blocks) -> np.ndarray:
+    """keystream blocks [first_block, first_block + n_blocks) of every key: [n_keys, n_blocks, 16] bytes"""
+    keys = np.ascontiguousarray(np.asarray(keys, dtype=np.uint8)).reshape(-1, 16)
+    out = np.zeros((len(keys), n_blocks, 16), np.uint8)
+    lib().rvo_prg_blocks(_p(keys), C.c_size_t(len(keys)), C.c_uint64(first_block), C.c_size_t(n_blocks), _p(out))
+    return out
+
+
 def sharegen_gf2(keys, omit, n) -> np.ndarray:
     keys = np.ascontiguousarray(np.asarray(keys, dtype=np.uint8)).reshape(8, 8, 16)
     omit = np.ascontiguousarray(np.asarray(omit, dtype=np.uint32))

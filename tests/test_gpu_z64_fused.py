@@ -1,7 +1,17 @@
 """The Z64 prover with the mask generator inside the interpreter's level launches (reverie_amd/csrc/aes.hip: k_z64_fused,
 internal.h: Z64FParams) against the CPU oracle and against the two-kernel path (RV_Z64_FUSED=0), byte for byte.
 Reference: Instance::op_mul / step at Z64 (src/interpreter/single.rs:25-157), ShareGen::next (src/generator/share.rs:54-65),
-DomainZ64::batches_to_shares (src/algebra/z64/domain.rs:64-83), ProverTranscript (src/transcript/prover.rs:181-232)."""
+DomainZ64::batches_to_shares (src/algebra/z64/domain.rs:64-83), ProverTranscript (src/transcript/prover.rs:181-232).
+
+Counter coverage.  k_z64_fused runs the cipher's first rounds (rounds_0_to_9) at CTR block first_block + (m >> 1) of a Mul's mask
+pair m, and it has no launch without a gate list, so tests/test_gpu_maskgen.py (which pins the stand-alone generators at every counter
+byte and at the last legal counter 2^24 - 1) does not reach it: these whole proofs are its only check.  A program's Z64 cipher
+blocks number (Inputs + 2 Muls + 1) // 2.  The largest circuit here (layered_z64, 64 Inputs, 20 000 Muls) ends at block 20 031, the
+others at 12 031, 9 000, 3 511, 2 531, 1 531, 731, 531 and below; the random programs have 19 to 469 Muls (29 to 479 blocks).  So
+the carry of counter byte 15 into byte 14 (block 255 -> 256) is crossed by most of them, but counter byte 13 stays 0 everywhere in
+this file: blocks from 65 536 up (32 768 Muls) are reached through this kernel only by the 10^5-Mul proof of
+tests/test_gpu_parity.py::test_z64_mid_size_vs_oracle_and_full_size_round_trip (against the oracle) and its 10^6-Mul round trip
+(prover against verifier only), and the last legal counter by nothing."""
 import numpy as np
 import pytest
 
