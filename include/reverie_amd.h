@@ -306,6 +306,10 @@ int rv_eval_stream_begin(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, size_t
 int rv_eval_stream_set_compile_flags(rv_eval_stream *s, uint32_t flags);
 int rv_eval_stream_feed(rv_eval_stream *s, const rv_op *ops, size_t n_ops, const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64,
                         size_t n_z64);
+/* rv_eval_stream_feed for an op array in the memory of the stream's device (rv_stream_feed_device's conventions; the witnesses
+ * stay in host memory): the same statuses and values. */
+int rv_eval_stream_feed_device(rv_eval_stream *s, const rv_op *d_ops, size_t n_ops, const uint8_t *wit_gf2, size_t n_gf2,
+                               const uint64_t *wit_z64, size_t n_z64);
 int rv_eval_stream_finish(rv_eval_stream *s, uint8_t *gf2_values, uint64_t *z64_values, rv_eval_status *st);
 int rv_eval_stream_get_info(const rv_eval_stream *s, rv_eval_stream_info *info);
 void rv_eval_stream_abort(rv_eval_stream *s);
@@ -370,6 +374,19 @@ int rv_stream_begin(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, const uint8
 int rv_stream_set_compile_flags(rv_stream *s, uint32_t flags);
 int rv_stream_feed(rv_stream *s, const rv_op *ops, size_t n_ops, const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64,
                    size_t n_z64);
+/* rv_stream_feed for an op array that already sits in device memory: d_ops is n_ops packed 24-byte records in the memory of the
+ * stream's device (rv_circuit_compile_device's convention: the caller keeps ownership and must have finished writing it; 8-byte
+ * aligned, RV_E_ARG otherwise).  The witnesses stay in host memory, in rv_stream_feed's layouts.  Serves every stream rv_stream_feed
+ * serves -- single and batch provers in both passes, the streaming verifiers -- and may be mixed freely with it inside one stream
+ * and between its passes: the pieces are cut by the same rule, the digests and counters are the same numbers, and every proof,
+ * answer, error code and rv_stream_info figure is what rv_stream_feed gives for the same ops.  The op list is not copied to the
+ * host: one kernel makes each piece's digest and mask / event counts where the ops are; under RV_COMPILE_DEVICE an all-GF(2) piece
+ * is compiled from d_ops in place, and only a piece the host compiler has to read (no RV_COMPILE_DEVICE, Z64 / B2A / SizeHint ops,
+ * an op-list error, more than 2^16 rounds) is copied down, into one of a fixed number of page-locked slots: one per compiling
+ * thread plus one, each as long as the feed's longest piece, at most 32 and within 512 MiB (two at least).  The slots belong to the
+ * context and stay allocated for its next device feed until rv_ctx_destroy.  Returns when the library no longer reads d_ops. */
+int rv_stream_feed_device(rv_stream *s, const rv_op *d_ops, size_t n_ops, const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64,
+                          size_t n_z64);
 int rv_stream_commit(rv_stream *s, uint8_t comm[RV_HASH_SIZE] /* nullable */);
 int rv_stream_finish(rv_stream *s, uint8_t **proof, size_t *proof_len);
 void rv_stream_abort(rv_stream *s);
@@ -681,6 +698,15 @@ int rv_hook_compile_compare_device_chunk(rv_ctx *ctx, const rv_op *ops, size_t n
 /* Pieces of this process's streams (rv_stream_*, rv_eval_stream_* and the one-shot calls over them) that the device path compiled so
  * far: a test tells a device compile from a fallback to the host compiler by it. */
 uint64_t rv_hook_stream_device_chunks(void);
+/* out[0] / out[1]: op bytes this process's stream feeds copied host -> device (the pieces a host feed uploads under RV_COMPILE_DEVICE)
+ * and device -> host (the pieces of a device feed that the host compiler had to read) since the library was loaded */
+int rv_hook_stream_op_traffic(uint64_t out[2]);
+/* The eight sums a feed takes from the content of a piece -- digest, GF(2) masks, Z64 masks, in2, rec2, pre2, on64, pre64 -- for
+ * every piece of ops [0, n_ops) at stream position first_index, cut every piece_ops ops (0: one piece, also an empty one):
+ * host_out from the host feed's loops, dev_out from one launch of the device feed's kernel over all pieces (the ops are uploaded
+ * for it); both [pieces][8], pieces = max(1, ceil(n_ops / piece_ops)).  They must agree on every op array, malformed ops included. */
+int rv_hook_stream_piece_sums(rv_ctx *ctx, const rv_op *ops, size_t n_ops, uint64_t first_index, size_t piece_ops, uint64_t *host_out,
+                              uint64_t *dev_out);
 /* Per-phase times of this process's last device compile, ms from HIP events: out[0] classify and count, [1] last writers and consumer
  * lists, [2] values and levels (topological rounds), [3] rows, sort and tables, [4] the host's copy; out[5] = rounds launched. */
 int rv_hook_compile_device_laps(double out[6]);

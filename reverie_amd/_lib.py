@@ -91,6 +91,7 @@ SYMBOLS = [
     "rv_stream_set_compile_flags", "rv_eval_stream_set_compile_flags", "rv_hook_compile_compare_device_chunk", "rv_hook_stream_device_chunks",
     "rv_circuit_compiled_on_device",
     "rv_hook_maskgen",
+    "rv_stream_feed_device", "rv_eval_stream_feed_device", "rv_hook_stream_op_traffic", "rv_hook_stream_piece_sums",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -120,6 +121,11 @@ ARGTYPES = {
     "rv_hook_compile_compare_device_chunk": [_P, _P, _Z, _Z, _Z, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "rv_hook_stream_device_chunks": [],
     "rv_circuit_compiled_on_device": [_P, C.POINTER(C.c_int)],
+    # streams fed from device memory
+    "rv_stream_feed_device": [_P, _P, _Z, _P, _Z, _P, _Z],
+    "rv_eval_stream_feed_device": [_P, _P, _Z, _P, _Z, _P, _Z],
+    "rv_hook_stream_op_traffic": [C.POINTER(C.c_uint64)],
+    "rv_hook_stream_piece_sums": [_P, _P, _Z, C.c_uint64, _Z, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     # the mask generators (parity hook)
     "rv_hook_maskgen": [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _P],
 }

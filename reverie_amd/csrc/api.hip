@@ -27,6 +27,7 @@
 #include "launch.h"
 #include "ldsrun.h"
 #include "piece_pipe.h"
+#include "piece_sums.h"
 
 using namespace rv;
 
@@ -186,6 +187,24 @@ struct rv_ctx {
     std::vector<uint8_t*> h_ring;
     size_t h_ring_cap = 0;
     std::vector<hipEvent_t> ring_ev;  // per slot: recorded behind the copies out of it (a worker waits for it before it fills the slot again)
+    // ... and the device feeds' slots (feed_ops.inc): a piece of an op list in device memory that the HOST compiler has to read is
+    // copied into one, on stream_ops, by the thread that compiles it; a slot is held for the length of that compile.  At most
+    // max_slots of them are in use (set by the feed), so the host copy of a fed op list is bounded by that many pieces.  The table
+    // never moves (a fixed array); busy, and p / cap of a slot that is not busy, are read and written under mu only -- the holder of
+    // a busy slot owns its p and cap.  The buffers stay with the context until rv_ctx_destroy.
+    struct OpsSlots {
+        static constexpr size_t MAX = 32;
+        struct Slot {
+            uint8_t* p = nullptr;
+            size_t cap = 0;
+            bool busy = false;
+        };
+        std::mutex mu;
+        std::condition_variable cv;
+        Slot slot[MAX];
+        size_t max_slots = 2;
+    } ops_slots;
+    hipStream_t stream_ops = nullptr;
     // ... and pass 2's small ring: a chunk's host-built tables (proof offsets, item -> row lists) go to the device as ONE copy out
     // of a page-locked slot; a slot is written again only after the copy out of it has finished (its event).  Kept by the context:
     // unmapping four slots at the end of every stream was 20 ms of a 110 ms streamed proof.
@@ -462,6 +481,9 @@ extern "C" void rv_ctx_destroy(rv_ctx* ctx) {
     for (uint8_t* p : ctx->h_ring) (void)hipHostFree(p);
     for (hipEvent_t e : ctx->ring_ev)
         if (e) (void)hipEventDestroy(e);
+    for (auto& sl : ctx->ops_slots.slot)
+        if (sl.p) (void)hipHostFree(sl.p);
+    if (ctx->stream_ops) (void)hipStreamDestroy(ctx->stream_ops);
     for (int k = 0; k < rv_ctx::OPEN_SLOTS; k++) {
         if (ctx->ev_open[k]) (void)hipEventDestroy(ctx->ev_open[k]);
         if (ctx->h_open[k]) (void)hipHostFree(ctx->h_open[k]);
@@ -818,16 +840,22 @@ static bool piece_all_gf2(const rv_op* ops, size_t n_ops) {
         if (ops[i].domain != RV_DOM_GF2) return false;
     return true;
 }
-static int compile_chunk_on_device(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const ChunkStart& cs, Compiled& cc,
-                                   DevCompileKeep* keep, double laps[3] = nullptr) {
+static std::atomic<uint64_t> g_op_bytes_h2d{0}, g_op_bytes_d2h{0};  // op bytes this process's stream feeds copied to / from the device
+// d_ops not null (rv_stream_feed_device): the piece already sits in device memory -- nothing goes up, `ops` is not read.
+// up_bytes (the feeds: &g_op_bytes_h2d): receives the bytes of an upload.
+static int compile_chunk_on_device(rv_ctx* ctx, const rv_op* ops, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires,
+                                   const ChunkStart& cs, Compiled& cc, DevCompileKeep* keep, double laps[3] = nullptr,
+                                   std::atomic<uint64_t>* up_bytes = nullptr) {
     if (getenv("RV_LAZY_K")) return RV_COMPILE_FALLBACK;
     const auto t0 = std::chrono::steady_clock::now();
     rv_op* up = nullptr;
-    int rc = upload_ops(ctx, ops, n_ops, &up);
+    int rc = d_ops ? RV_OK : upload_ops(ctx, ops, n_ops, &up);
     if (rc) return rc;
+    if (up && up_bytes) up_bytes->fetch_add(n_ops * sizeof(rv_op), std::memory_order_relaxed);
     const auto t1 = std::chrono::steady_clock::now();
     DevCompileLaps dl;
-    rc = compile_ops_device(ctx->stream, ctx_dev_allocator(ctx), up, n_ops, z64_wires, gf2_wires, false, 0, cc, keep, laps ? &dl : nullptr, &cs);
+    rc = compile_ops_device(ctx->stream, ctx_dev_allocator(ctx), d_ops ? d_ops : up, n_ops, z64_wires, gf2_wires, false, 0, cc, keep, laps ? &dl : nullptr,
+                            &cs);
     ctx->release(up);  // (the device compile synchronised the stream)
     if (rc == RV_E_DEVICE) g_last_error = "device compile of a stream's piece: HIP error";
     if (rc == RV_E_NOMEM) g_last_error = "device compile of a stream's piece: out of device memory";
@@ -840,6 +868,12 @@ static int compile_chunk_on_device(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
     return rc;
 }
 extern "C" uint64_t rv_hook_stream_device_chunks(void) { return g_stream_device_chunks.load(std::memory_order_relaxed); }
+extern "C" int rv_hook_stream_op_traffic(uint64_t out[2]) {
+    if (!out) return RV_E_ARG;
+    out[0] = g_op_bytes_h2d.load(std::memory_order_relaxed);
+    out[1] = g_op_bytes_d2h.load(std::memory_order_relaxed);
+    return RV_OK;
+}
 
 static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                                   rv_circuit** out, const rv_op* d_ops) {
@@ -1331,7 +1365,7 @@ extern "C" int rv_hook_compile_compare_device_chunk(rv_ctx* ctx, const rv_op* op
         Compiled a, b;
         const int rc = compile_ops_seq(ops, n_ops, z64_wires, gf2_wires, a, &cs);
         HIPCHK(hipSetDevice(ctx->device));
-        const int rd = compile_chunk_on_device(ctx, ops, n_ops, z64_wires, gf2_wires, cs, b, nullptr);
+        const int rd = compile_chunk_on_device(ctx, ops, nullptr, n_ops, z64_wires, gf2_wires, cs, b, nullptr);
         if (rd == RV_OK) {
             *path = 1;
             *diff = rc == RV_OK ? compiled_diff(a, b) : 100;  // (the device path compiled a piece the host compiler rejects)
@@ -1424,6 +1458,7 @@ extern "C" int rv_challenge(const uint8_t comm[RV_HASH_SIZE], uint8_t omit[RV_TO
 #include "opscache.inc"
 #include "verify_batch.inc"
 #include "hooks.inc"
+#include "feed_ops.inc"
 #include "stream.inc"
 #include "comm.inc"
 #include "eval.inc"

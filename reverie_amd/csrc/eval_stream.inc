@@ -226,12 +226,13 @@ static int eval_stream_chunk(rv_eval_stream* E, const Compiled& cc, uint64_t op_
 // worker threads of a feed: the CPUs this process may use, at most 16 (oversubscribed compile threads throttle the GPU's feeder)
 static unsigned eval_stream_threads() { return std::min(cpu_budget(), 16u); }
 
-static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
-                                 size_t n_z64) {
+// ops_on_device: `ops` is in the memory of the stream's device (rv_eval_stream_feed_device; feed_ops.inc)
+static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, bool ops_on_device, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2,
+                                 const uint64_t* wit_z64, size_t n_z64) {
     LibBusy busy_guard;
     if (!E) return RV_E_ARG;
     if (E->sticky) return E->sticky;
-    if (E->finished || (n_ops && !ops) || (n_gf2 && !wit_gf2) || (n_z64 && !wit_z64)) return E->sticky = RV_E_ARG;
+    if (E->finished || (n_ops && !ops) || (n_gf2 && !wit_gf2) || (n_z64 && !wit_z64) || (ops_on_device && ((uintptr_t)ops & 7))) return E->sticky = RV_E_ARG;
     E->fed = true;
     HIPCHK(hipSetDevice(E->ctx->device));
     const std::vector<size_t> cut = stream_cuts(n_ops, E->max_chunk_ops);  // (the streaming prover's rule)
@@ -243,11 +244,17 @@ static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, size_t n_o
     std::vector<std::unique_ptr<Compiled>> pieces(n_pieces);
     const bool device = (E->compile_flags & RV_COMPILE_DEVICE) != 0;
     const ChunkStart cs;  // (values do not depend on mask phases or transcript offsets)
+    FeedOps fo(E->ctx, ops, ops_on_device && n_ops, cut);
+    if (int rs = fo.load_sums(first_op, n_threads)) return E->sticky = rs;
+    auto compile_on_host = [&](size_t i) {
+        const PieceOnHost h(fo, i);
+        return h.rc() ? h.rc() : compile_ops(h.ops(), fo.len(i), E->z64_wires, E->gf2_wires, *pieces[i], &cs);
+    };
     PiecePipe pipe(n_pieces, n_threads, RV_E_NOMEM, [&](size_t i) {
         // (RV_COMPILE_DEVICE: an all-GF(2) piece stays empty here -- the main thread compiles it on the GPU right before it runs)
-        if (device && piece_all_gf2(ops + cut[i], cut[i + 1] - cut[i])) return (int)RV_OK;
+        if (device && fo.all_gf2(i)) return (int)RV_OK;
         pieces[i].reset(new Compiled());
-        return compile_ops(ops + cut[i], cut[i + 1] - cut[i], E->z64_wires, E->gf2_wires, *pieces[i], &cs);
+        return compile_on_host(i);
     });
     int rc = RV_OK;
     for (size_t i = 0; i < n_pieces && !rc; i++) {
@@ -255,9 +262,9 @@ static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, size_t n_o
         if (!rc && !pieces[i]) {
             // (the piece comes back to the host whole: the chunk's arrays go up in one block with its witness, eval_stream_chunk)
             pieces[i].reset(new Compiled());
-            const int rd = compile_chunk_on_device(E->ctx, ops + cut[i], cut[i + 1] - cut[i], E->z64_wires, E->gf2_wires, cs, *pieces[i], nullptr);
+            const int rd = fo.compile_on_device(i, E->z64_wires, E->gf2_wires, cs, *pieces[i], nullptr);
             if (rd == RV_OK) g_stream_device_chunks.fetch_add(1, std::memory_order_relaxed);
-            rc = rd == RV_COMPILE_FALLBACK ? compile_ops(ops + cut[i], cut[i + 1] - cut[i], E->z64_wires, E->gf2_wires, *pieces[i], &cs) : rd;
+            rc = rd == RV_COMPILE_FALLBACK ? compile_on_host(i) : rd;
         }
         if (!rc) rc = eval_stream_chunk(E, *pieces[i], first_op + cut[i], wit_gf2, n_gf2, wit_z64, n_z64, &u2, &u64);
         pieces[i].reset();  // (host memory of the compiled piece: freed here, on the main thread, while the GPU runs it)
@@ -270,8 +277,16 @@ static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, size_t n_o
 
 extern "C" int rv_eval_stream_feed(rv_eval_stream* E, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
                                    size_t n_z64) {
-    const int rc = guarded([&] { return eval_stream_feed_impl(E, ops, n_ops, wit_gf2, n_gf2, wit_z64, n_z64); });
+    const int rc = guarded([&] { return eval_stream_feed_impl(E, ops, false, n_ops, wit_gf2, n_gf2, wit_z64, n_z64); });
     if (rc == RV_E_NOMEM && E) E->sticky = rc;  // (a thrown one too: the stream is dead after any failed allocation)
+    return rc;
+}
+
+extern "C" int rv_eval_stream_feed_device(rv_eval_stream* E, const rv_op* d_ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2,
+                                          const uint64_t* wit_z64, size_t n_z64) {
+    // (every read of d_ops has finished when this returns: the device compiles and the copies down are waited for)
+    const int rc = guarded([&] { return eval_stream_feed_impl(E, d_ops, true, n_ops, wit_gf2, n_gf2, wit_z64, n_z64); });
+    if (rc == RV_E_NOMEM && E) E->sticky = rc;
     return rc;
 }
 

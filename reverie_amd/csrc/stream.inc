@@ -1224,20 +1224,22 @@ struct FeedPiece {
 // A piece ready to run: pass 1's cached compile if its digest matches the ops fed now, else a fresh compile -- at the offsets the piece
 // is expected to run at where they were predicted (no relocation pass afterwards; ChunkRun moves it by the difference, which is zero
 // unless the prediction is off).  Runs on a worker thread, or inline right before the piece runs.
-static int prepare_piece(const rv_stream* S, const rv_op* ops, uint64_t first_op, FeedPiece& p) {
+static int prepare_piece(const rv_stream* S, const FeedOps& fo, size_t i, uint64_t first_op, FeedPiece& p) {
     if (!p.predicted) p.ph2 = (uint32_t)(S->run.masks % 128), p.ph64 = (uint32_t)(S->run.masks64 % 2);
-    const uint64_t dg = ops_digest(ops + p.at, p.n, first_op + p.at);
+    const uint64_t dg = fo.digest(i, first_op);
     if (p.c && dg != p.digest) {  // same position and length, other ops: pass 1's compile is not this piece's (finish reports RV_E_ARG)
         rv_circuit_destroy(p.c);
         p.c = nullptr;
     }
     p.digest = dg;
     // (a piece whose transcripts pass 1 kept is compiled on the host as ever: ChunkRun::plan decides whether it runs at all)
-    p.device = !p.c && !p.kept && (S->compile_flags & RV_COMPILE_DEVICE) && piece_all_gf2(ops + p.at, p.n);
+    p.device = !p.c && !p.kept && (S->compile_flags & RV_COMPILE_DEVICE) && fo.all_gf2(i);
     if (p.device) return RV_OK;
     if (!p.c) {
         p.carried = p.predicted ? p.want : ChunkStart();
-        if (int rc = stream_compile_piece(S, ops + p.at, p.n, p.ph2, p.ph64, &p.c, p.predicted ? &p.want : nullptr)) return rc;
+        const PieceOnHost h(fo, i);
+        if (h.rc()) return h.rc();
+        if (int rc = stream_compile_piece(S, h.ops(), p.n, p.ph2, p.ph64, &p.c, p.predicted ? &p.want : nullptr)) return rc;
     }
     if (p.predicted) {
         relocate_to(p.c->cc, p.carried, p.want);
@@ -1285,7 +1287,7 @@ static size_t feed_ring(rv_stream* S) {
 }
 
 // the mask and event counts of every piece of a feed (on a few threads: two passes over 10^7 ops on the main thread were 40 ms of a feed)
-static rv_stream::FeedCounts feed_counts(rv_stream* S, const rv_op* ops, const std::vector<size_t>& cut, uint64_t first_op) {
+static rv_stream::FeedCounts feed_counts(rv_stream* S, const FeedOps& fo, const std::vector<size_t>& cut, uint64_t first_op) {
     // (rv_stream_same_cuts: pass 2 takes pass 1's counts of the same feed -- two passes over 240 MB of ops, 7 ms on 8 threads.
     // Other ops in pass 2 only make the predictions wrong: the pieces are then compiled again in place, and finish reports it)
     if (S->same_cuts && S->pass == 2) {
@@ -1296,12 +1298,10 @@ static rv_stream::FeedCounts feed_counts(rv_stream* S, const rv_op* ops, const s
     rv_stream::FeedCounts k;
     k.cut = cut;
     k.cm2.resize(n_pieces), k.cm64.resize(n_pieces), k.cev.resize(n_pieces);
-    const unsigned nt = (unsigned)std::min<size_t>({(size_t)16, n_pieces, (size_t)std::max(1u, std::thread::hardware_concurrency() / 2)});
+    // (a device feed has them from its kernel: nothing to spread over threads)
+    const unsigned nt = fo.device ? 1u : (unsigned)std::min<size_t>({(size_t)16, n_pieces, (size_t)std::max(1u, std::thread::hardware_concurrency() / 2)});
     auto count = [&](unsigned t) {
-        for (size_t i = t; i < n_pieces; i += nt) {
-            count_masks(ops + cut[i], cut[i + 1] - cut[i], &k.cm2[i], &k.cm64[i]);
-            count_events(ops + cut[i], cut[i + 1] - cut[i], &k.cev[i]);
-        }
+        for (size_t i = t; i < n_pieces; i += nt) fo.counts(i, &k.cm2[i], &k.cm64[i], &k.cev[i]);
     };
     std::vector<std::thread> th;
     th.reserve(nt);
@@ -1321,12 +1321,12 @@ static rv_stream::FeedCounts feed_counts(rv_stream* S, const rv_op* ops, const s
 // The pieces of a feed.  predict: every piece's ShareGen phases AND the carried transcript events it will find in front of its own
 // follow from counts over the pieces before it, so the worker that compiles a piece also moves its transcript offsets (relocate_chunk:
 // a pass over all its gates, 3 ms per 10^6 ops that the main thread used to spend between two chunks' GPU work).
-static std::vector<FeedPiece> feed_pieces(rv_stream* S, const rv_op* ops, const std::vector<size_t>& cut, bool predict) {
+static std::vector<FeedPiece> feed_pieces(rv_stream* S, const FeedOps& fo, const std::vector<size_t>& cut, bool predict) {
     const size_t n_pieces = cut.size() - 1;
     const uint64_t first_op = S->run.n_ops;
     std::vector<FeedPiece> pieces(n_pieces);
     rv_stream::FeedCounts fc;
-    if (predict) fc = feed_counts(S, ops, cut, first_op);
+    if (predict) fc = feed_counts(S, fo, cut, first_op);
     uint64_t m2 = S->run.masks, m64 = S->run.masks64;
     const bool tails = S->pass != 2;  // (the verifier's single pass carries unhashed tails like pass 1)
     uint64_t t[TR_KINDS];             // pass 1: unhashed tails
@@ -1362,10 +1362,12 @@ static std::vector<FeedPiece> feed_pieces(rv_stream* S, const rv_op* ops, const 
 
 // H: the caller's handle -- a single stream, or a batch whose members are fed witness b at wit_gf2 + b * n_gf2, wit_z64 + b * n_z64.
 // The pieces are compiled ahead on worker threads (piece_pipe.h) and run in order; with one thread each is prepared right before it
-// runs, unpredicted and unstaged.
-static int stream_feed_impl(rv_stream* H, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64, size_t n_z64) {
+// runs, unpredicted and unstaged.  ops_on_device: `ops` is in the memory of the stream's device (rv_stream_feed_device); what differs is
+// behind FeedOps / PieceOnHost (feed_ops.inc).
+static int stream_feed_impl(rv_stream* H, const rv_op* ops, bool ops_on_device, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
+                            size_t n_z64) {
     LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
-    if (!H || (n_ops && !ops)) return RV_E_ARG;
+    if (!H || (n_ops && !ops) || (ops_on_device && ((uintptr_t)ops & 7))) return RV_E_ARG;
     if (H->sticky) return H->sticky;
     const std::vector<rv_stream*> proofs = H->running();
     if (proofs.empty()) return RV_OK;  // (a verifier stream whose proof has the wrong shape: the answer is already `false`)
@@ -1384,7 +1386,13 @@ static int stream_feed_impl(rv_stream* H, const rv_op* ops, size_t n_ops, const 
     const bool ahead = n_threads > 1;
     const size_t NS = ahead ? feed_ring(S) : 0, slot_cap = S->ctx->h_ring_cap;
     const uint64_t first_op = S->run.n_ops;
-    std::vector<FeedPiece> pieces = feed_pieces(S, ops, cut, ahead);
+    FeedOps fo(S->ctx, ops, ops_on_device && n_ops, cut);
+    const auto t_sums0 = Clock::now();
+    if (int rs = fo.load_sums(first_op, n_threads)) return S->sticky = H->sticky = rs;
+    if (stats && fo.device)
+        fprintf(stderr, "[rv stream] device feed: digest and counts of %zu pieces (%zu ops) in %.6f s (kernel, copy back, one wait)\n", n_pieces, n_ops,
+                secs(t_sums0, Clock::now()));
+    std::vector<FeedPiece> pieces = feed_pieces(S, fo, cut, ahead);
     // the second job of a worker: the next piece that is compiled, not yet with the main thread and whose slot is free goes into it
     size_t next_stage = 0;
     auto stage_pick = [&](const PiecePipe& pp) {
@@ -1399,12 +1407,17 @@ static int stream_feed_impl(rv_stream* H, const rv_op* ops, size_t n_ops, const 
         if (S->ctx->ring_ev[i % NS]) (void)hipEventSynchronize(S->ctx->ring_ev[i % NS]);
         circuit_stage(c, S->ctx->h_ring[i % NS], (int)(i % NS));
     };
-    PiecePipe pipe(n_pieces, n_threads, RV_E_NOMEM, [&](size_t i) { return prepare_piece(S, ops, first_op, pieces[i]); },
+    PiecePipe pipe(n_pieces, n_threads, RV_E_NOMEM, [&](size_t i) { return prepare_piece(S, fo, i, first_op, pieces[i]); },
                    NS ? PiecePipe::Pick(stage_pick) : PiecePipe::Pick(), stage);
     if (stats) fprintf(stderr, "[rv stream] feed set up (cuts, counts, cached pieces, %u workers) in %.3f s\n", n_threads, secs(t_feed0, Clock::now()));
     int rc = RV_OK;
     double t_wait = 0, t_run = 0, dev_laps[3] = {0, 0, 0};
     size_t n_dev = 0;
+    // the host compile of a piece on this thread (what the device compiler handed back; a prediction that was off)
+    auto compile_here = [&](size_t i, uint32_t ph2, uint32_t ph64, rv_circuit** out) {
+        const PieceOnHost h(fo, i);
+        return h.rc() ? h.rc() : stream_compile_piece(S, h.ops(), pieces[i].n, ph2, ph64, out);
+    };
     for (size_t i = 0; i < n_pieces && !rc; i++) {
         FeedPiece& p = pieces[i];
         const auto t0 = Clock::now();
@@ -1419,7 +1432,7 @@ static int stream_feed_impl(rv_stream* H, const rv_op* ops, size_t n_ops, const 
             c = new rv_circuit();
             c->ctx = S->ctx;
             DevCompileKeep kept;
-            const int rd = compile_chunk_on_device(S->ctx, ops + p.at, p.n, S->z64_wires, S->gf2_wires, at, c->cc, &kept, stats ? dev_laps : nullptr);
+            const int rd = fo.compile_on_device(i, S->z64_wires, S->gf2_wires, at, c->cc, &kept, stats ? dev_laps : nullptr);
             if (rd == RV_OK) {
                 c->d_gates = kept.d_gates, c->d_rec_rows = kept.d_rec_rows, c->d_in_rows = kept.d_in_rows;
                 c->dev_compiled = true;
@@ -1433,7 +1446,7 @@ static int stream_feed_impl(rv_stream* H, const rv_op* ops, size_t n_ops, const 
                 p.carried = ChunkStart();
                 p.ph2 = at.mask_phase, p.ph64 = at.mask64_phase;
                 // (handed back -- an op-list error, a chain deeper than the round cap: the host compiler's result or error code)
-                rc = rd == RV_COMPILE_FALLBACK ? stream_compile_piece(S, ops + p.at, p.n, p.ph2, p.ph64, &c) : rd;
+                rc = rd == RV_COMPILE_FALLBACK ? compile_here(i, p.ph2, p.ph64, &c) : rd;
             }
         }
         if (!rc && (p.ph2 != (uint32_t)(S->run.masks % 128) || p.ph64 != (uint32_t)(S->run.masks64 % 2))) {
@@ -1441,7 +1454,7 @@ static int stream_feed_impl(rv_stream* H, const rv_op* ops, size_t n_ops, const 
             rv_circuit_destroy(c);
             c = nullptr;
             p.carried = ChunkStart();
-            rc = stream_compile_piece(S, ops + p.at, p.n, (uint32_t)(S->run.masks % 128), (uint32_t)(S->run.masks64 % 2), &c);
+            rc = compile_here(i, (uint32_t)(S->run.masks % 128), (uint32_t)(S->run.masks64 % 2), &c);
         }
         const auto t1 = Clock::now();
         if (!rc) {
@@ -1480,9 +1493,16 @@ static int stream_feed_settle(rv_stream* H) {
 
 extern "C" int rv_stream_feed(rv_stream* S, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
                               size_t n_z64) {
-    const int rc = guarded([&] { return stream_feed_impl(S, ops, n_ops, wit_gf2, n_gf2, wit_z64, n_z64); });
+    const int rc = guarded([&] { return stream_feed_impl(S, ops, false, n_ops, wit_gf2, n_gf2, wit_z64, n_z64); });
     // (also after a failed feed: the caller's witness arrays and the ring slots may still feed copies)
     const int rs = stream_feed_settle(S);
+    return rc ? rc : rs;
+}
+
+extern "C" int rv_stream_feed_device(rv_stream* S, const rv_op* d_ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
+                                     size_t n_z64) {
+    const int rc = guarded([&] { return stream_feed_impl(S, d_ops, true, n_ops, wit_gf2, n_gf2, wit_z64, n_z64); });
+    const int rs = stream_feed_settle(S);  // (every read of d_ops has finished: the device compiles and the copies down are waited for)
     return rc ? rc : rs;
 }
 

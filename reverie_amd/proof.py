@@ -65,6 +65,39 @@ class Context:
             pass
 
 
+def _is_device_ops(ops) -> bool:
+    """a torch tensor (torch stays an optional import: a caller who holds one has imported it)"""
+    import sys
+
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(ops, torch.Tensor)
+
+
+def _device_ops(ops, ctx: "Optional[Context]", what: str) -> "Tuple[int, int, Context]":
+    """(device pointer, n_ops, context) of an op list in GPU memory: a torch tensor on the context's device holding packed 24-byte
+    rv_op records, as uint8 of shape [n, 24] (or [n * 24]) or int64 / uint64 of shape [n, 3]; contiguous.  Host memory is refused
+    before any context is made (ctx None: the default one).  Waits for the tensor's device, so that the op list is complete before
+    the library's stream reads it."""
+    import torch
+
+    if not isinstance(ops, torch.Tensor) or ops.device.type != "cuda":
+        raise TypeError(f"{what} takes a torch tensor in GPU memory")
+    if not ops.is_contiguous():
+        raise ValueError("the op tensor must be contiguous")
+    if ops.dtype == torch.uint8 and (ops.dim() == 1 and ops.numel() % OP_DTYPE.itemsize == 0 or ops.dim() == 2 and ops.shape[1] == OP_DTYPE.itemsize):
+        n_ops = ops.numel() // OP_DTYPE.itemsize
+    elif ops.dtype in (torch.int64, getattr(torch, "uint64", torch.int64)) and ops.dim() == 2 and ops.shape[1] == OP_DTYPE.itemsize // 8:
+        n_ops = ops.shape[0]
+    else:
+        raise ValueError(f"op tensor must be uint8 [n, {OP_DTYPE.itemsize}] / [n * {OP_DTYPE.itemsize}] or int64 [n, 3], got "
+                         f"{ops.dtype} {tuple(ops.shape)}")
+    ctx = ctx or Context.default()
+    if ops.device.index is not None and ops.device.index != ctx.device:
+        raise ValueError(f"op tensor is on {ops.device}, the context on device {ctx.device}")
+    torch.cuda.synchronize(ops.device)
+    return ops.data_ptr(), n_ops, ctx
+
+
 class Circuit:
     """A gate stream compiled (levelised) and resident in HBM (rv_circuit)."""
 
@@ -96,30 +129,15 @@ class Circuit:
         contiguous.  The tensor is not copied to the host unless the device path hands the program to the host compiler; the
         caller keeps it.  The circuit is the one Circuit(host ops, device_compile=True) compiles, with whole_prover the lazy-sum
         form (also built on the device)."""
-        import torch
-
-        if not isinstance(ops, torch.Tensor) or ops.device.type != "cuda":
-            raise TypeError("from_device_ops takes a torch tensor in GPU memory")
-        if not ops.is_contiguous():
-            raise ValueError("the op tensor must be contiguous")
-        if ops.dtype == torch.uint8 and (ops.dim() == 1 and ops.numel() % OP_DTYPE.itemsize == 0 or ops.dim() == 2 and ops.shape[1] == OP_DTYPE.itemsize):
-            n_ops = ops.numel() // OP_DTYPE.itemsize
-        elif ops.dtype in (torch.int64, getattr(torch, "uint64", torch.int64)) and ops.dim() == 2 and ops.shape[1] == OP_DTYPE.itemsize // 8:
-            n_ops = ops.shape[0]
-        else:
-            raise ValueError(f"op tensor must be uint8 [n, {OP_DTYPE.itemsize}] / [n * {OP_DTYPE.itemsize}] or int64 [n, 3], got "
-                             f"{ops.dtype} {tuple(ops.shape)}")
+        d_ops, n_ops, ctx = _device_ops(ops, ctx, "from_device_ops")
         self = cls.__new__(cls)
-        self.ctx = ctx or Context.default()
-        if ops.device.index is not None and ops.device.index != self.ctx.device:
-            raise ValueError(f"op tensor is on {ops.device}, the context on device {self.ctx.device}")
+        self.ctx = ctx
         self.ops = None  # (on the device only)
         self.wire_counts = (int(wire_counts[0]), int(wire_counts[1]))
         self.keep_wires = bool(keep_wires)
         self.handle = C.c_void_p()
         flags = (_lib.RV_COMPILE_WHOLE_PROVER if whole_prover else 0) | (_lib.RV_COMPILE_KEEP_WIRES if keep_wires else 0)
-        torch.cuda.synchronize(ops.device)  # (the op list is complete before the library's stream reads it)
-        _lib.check(_lib.lib().rv_circuit_compile_device(self.ctx.handle, C.c_void_p(ops.data_ptr()), C.c_size_t(n_ops),
+        _lib.check(_lib.lib().rv_circuit_compile_device(self.ctx.handle, C.c_void_p(d_ops), C.c_size_t(n_ops),
                                                         C.c_size_t(self.wire_counts[0]), C.c_size_t(self.wire_counts[1]),
                                                         C.c_uint32(flags), C.byref(self.handle)))
         return self

@@ -16,6 +16,11 @@ Device memory is bounded by the wire counts, one piece's working set and the pro
 Every class and one-shot function here takes `device_compile` (default False): the stream's all-GF(2) pieces are then compiled on the
 GPU (RV_COMPILE_DEVICE: rv_stream_set_compile_flags / rv_eval_stream_set_compile_flags) instead of on host worker threads; pieces with
 Z64, B2A or SizeHint ops, and pieces with an error in them, are still compiled on the host.  Proofs, answers and values are the same.
+
+Wherever an op list is taken -- every `feed`, every one-shot function -- it may also be a torch tensor in GPU memory holding packed
+rv_op records (what `Circuit.from_device_ops` accepts; on the context's device, or it is an error).  The ops are then fed from where
+they are (rv_stream_feed_device / rv_eval_stream_feed_device): with `device_compile` an all-GF(2) piece never reaches the host, and a
+piece the host compiler has to read is copied down alone.  Witnesses stay host arrays.  Results are the same bytes.
 """
 from __future__ import annotations
 
@@ -27,7 +32,22 @@ import numpy as np
 
 from . import _lib
 from .ops import OP_DTYPE, TOTAL_REPS, program
-from .proof import Context, Evaluation, Proof, _ptr
+from .proof import Context, Evaluation, Proof, _device_ops, _is_device_ops, _ptr
+
+
+def _ops_ctx(ops, ctx: Optional[Context]) -> Context:
+    """the context of a one-shot call; an op tensor that is not in GPU memory is refused before a context is made"""
+    return _device_ops(ops, ctx, "a stream of device ops")[2] if _is_device_ops(ops) else ctx or Context.default()
+
+
+def _feed(handle, ctx: Context, ops, g, n_g: int, z, n_z: int, entry: str = "rv_stream_feed"):
+    """one feed of host ops (anything `program` takes) or of a torch GPU tensor of packed rv_op records (the _device entry point)"""
+    if _is_device_ops(ops):
+        d_ops, n_ops, _ = _device_ops(ops, ctx, "a feed of device ops")
+        _lib.check(getattr(_lib.lib(), entry + "_device")(handle, C.c_void_p(d_ops), C.c_size_t(n_ops), _ptr(g), C.c_size_t(n_g), _ptr(z), C.c_size_t(n_z)))
+        return
+    ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+    _lib.check(getattr(_lib.lib(), entry)(handle, _ptr(ops), C.c_size_t(len(ops)), _ptr(g), C.c_size_t(n_g), _ptr(z), C.c_size_t(n_z)))
 
 
 def _set_device_compile(handle, device_compile: bool, setter: str = "rv_stream_set_compile_flags"):
@@ -68,10 +88,9 @@ class StreamingProver:
         _set_device_compile(self.handle, device_compile)
 
     def feed(self, ops, wit_gf2: Sequence[int] = (), wit_z64: Sequence[int] = ()):
-        ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
         g = np.ascontiguousarray(np.asarray(wit_gf2, dtype=np.uint8))
         z = np.ascontiguousarray(np.asarray(wit_z64, dtype=np.uint64))
-        _lib.check(_lib.lib().rv_stream_feed(self.handle, _ptr(ops), C.c_size_t(len(ops)), _ptr(g), C.c_size_t(len(g)), _ptr(z), C.c_size_t(len(z))))
+        _feed(self.handle, self.ctx, ops, g, len(g), z, len(z))
 
     def same_cuts(self):
         """rv_stream_same_cuts: pass 2 will be fed in pass 1's pieces -- pass 1 keeps the last chunks' transcripts within
@@ -109,8 +128,19 @@ class StreamingProver:
 
 def prove_streaming(ops, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
                     ctx: Optional[Context] = None, device_compile: bool = False) -> Tuple[Proof, dict]:
-    """rv_prove_streaming: both passes over an op array in host memory -> (Proof, stream info)"""
-    ctx = ctx or Context.default()
+    """rv_prove_streaming: both passes over an op array in host memory -> (Proof, stream info).  A torch GPU tensor of ops: the same
+    through rv_stream_begin / rv_stream_feed_device / rv_stream_finish."""
+    ctx = _ops_ctx(ops, ctx)
+    if _is_device_ops(ops):
+        sp = StreamingProver(wire_counts, seeds, max_chunk_ops, ctx, device_compile)
+        try:
+            sp.same_cuts()  # (the same tensor, cut by the same rule in both passes)
+            sp.feed(ops, wit_gf2, wit_z64)
+            sp.commit()
+            sp.feed(ops, wit_gf2, wit_z64)
+            return sp.finish(), sp.info
+        finally:
+            sp.close()
     ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
     g = np.ascontiguousarray(np.asarray(wit_gf2, dtype=np.uint8))
     z = np.ascontiguousarray(np.asarray(wit_z64, dtype=np.uint64))
@@ -145,8 +175,7 @@ class StreamingVerifier:
         _set_device_compile(self.handle, device_compile)
 
     def feed(self, ops):
-        ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
-        _lib.check(_lib.lib().rv_stream_feed(self.handle, _ptr(ops), C.c_size_t(len(ops)), None, C.c_size_t(0), None, C.c_size_t(0)))
+        _feed(self.handle, self.ctx, ops, None, 0, None, 0)
 
     def finish(self, strict: bool = True) -> bool:
         ok = C.c_int()
@@ -165,8 +194,16 @@ class StreamingVerifier:
 
 def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = True, max_chunk_ops: int = 0,
                      ctx: Optional[Context] = None, device_compile: bool = False) -> Tuple[bool, dict]:
-    """rv_verify_streaming: one pass over an op array in host memory -> (ok, stream info)"""
-    ctx = ctx or Context.default()
+    """rv_verify_streaming: one pass over an op array in host memory -> (ok, stream info).  A torch GPU tensor of ops: the same through
+    rv_stream_verify_begin / rv_stream_feed_device / rv_stream_verify_finish."""
+    ctx = _ops_ctx(ops, ctx)
+    if _is_device_ops(ops):
+        sv = StreamingVerifier(wire_counts, proof, max_chunk_ops, ctx, device_compile)
+        try:
+            sv.feed(ops)
+            return sv.finish(strict), sv.info
+        finally:
+            sv.close()
     ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
     pr = proof if isinstance(proof, Proof) else Proof(bytes(proof))
     buf, n = pr._buffer()
@@ -227,11 +264,9 @@ class StreamingBatchProver:
         _set_device_compile(self.handle, device_compile)
 
     def feed(self, ops, wits_gf2=(), wits_z64=()):
-        ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
         g = _eval_wits(wits_gf2, self.batch, np.uint8)
         z = _eval_wits(wits_z64, self.batch, np.uint64)
-        _lib.check(_lib.lib().rv_stream_feed(self.handle, _ptr(ops), C.c_size_t(len(ops)), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z),
-                                             C.c_size_t(z.shape[1])))
+        _feed(self.handle, self.ctx, ops, g, g.shape[1], z, z.shape[1])
 
     same_cuts = StreamingProver.same_cuts
 
@@ -260,8 +295,7 @@ def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int],
                           ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False) -> "list[Proof]":
     """rv_prove_streaming_batch: both passes over an op array in host memory for the witnesses wits_gf2 [B][n] / wits_z64
     [B][m] (B from whichever of the two is 2-D; the other may be []); seeds [B][256][16] or None.  `info` (a dict, optional) receives the stream's figures."""
-    ctx = ctx or Context.default()
-    ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+    ctx = _ops_ctx(ops, ctx)
     g0 = np.asarray(wits_gf2, dtype=np.uint8)
     z0 = np.asarray(wits_z64, dtype=np.uint64)
     if g0.ndim == 2:  # (the batch is the first dimension of whichever witness array is 2-D: [] for the other domain)
@@ -270,6 +304,20 @@ def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int],
         batch = z0.shape[0]
     else:
         raise ValueError("wits_gf2 or wits_z64 must be [batch][n]")
+    if _is_device_ops(ops):  # (a torch GPU tensor: begin / rv_stream_feed_device twice / finish)
+        sp = StreamingBatchProver(wire_counts, batch, seeds, max_chunk_ops, ctx, device_compile)
+        try:
+            sp.same_cuts()
+            sp.feed(ops, g0, z0)
+            sp.commit()
+            sp.feed(ops, g0, z0)
+            proofs = sp.finish()
+            if info is not None:
+                info.update(sp.info)
+            return proofs
+        finally:
+            sp.close()
+    ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
     g = _eval_wits(g0, batch, np.uint8)
     z = _eval_wits(z0, batch, np.uint64)
     s = _batch_seeds(seeds, batch)
@@ -324,11 +372,21 @@ class StreamingBatchVerifier:
 def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bool = True, max_chunk_ops: int = 0,
                            ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False) -> "list[bool]":
     """rv_verify_streaming_batch: one pass over an op array in host memory for every proof -> one bool per proof"""
-    ctx = ctx or Context.default()
-    ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+    ctx = _ops_ctx(ops, ctx)
     n = len(proofs)
     if n == 0:
         return []
+    if _is_device_ops(ops):  # (a torch GPU tensor: begin / rv_stream_feed_device / finish)
+        sv = StreamingBatchVerifier(wire_counts, proofs, max_chunk_ops, ctx, device_compile)
+        try:
+            sv.feed(ops)
+            oks = sv.finish(strict)
+            if info is not None:
+                info.update(sv.info)
+            return oks
+        finally:
+            sv.close()
+    ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
     keep, ptrs, lens = _proof_array(proofs)
     ok = (C.c_int * n)()
     si = _lib.StreamInfo()
@@ -378,11 +436,9 @@ class StreamingEvaluator:
         _set_device_compile(self.handle, device_compile, "rv_eval_stream_set_compile_flags")
 
     def feed(self, ops, wits_gf2=(), wits_z64=()):
-        ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
         g = _eval_wits(wits_gf2, self.batch, np.uint8)
         z = _eval_wits(wits_z64, self.batch, np.uint64)
-        _lib.check(_lib.lib().rv_eval_stream_feed(self.handle, _ptr(ops), C.c_size_t(len(ops)), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z),
-                                                  C.c_size_t(z.shape[1])))
+        _feed(self.handle, self.ctx, ops, g, g.shape[1], z, z.shape[1], "rv_eval_stream_feed")
 
     def finish(self, values: bool = False) -> Evaluation:
         st = np.zeros((self.batch, 2), np.uint64)
@@ -415,10 +471,20 @@ def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], ma
     """rv_evaluate_streaming: one op array in host memory, evaluated chunk by chunk with bounded device memory.  wits_gf2 /
     wits_z64: [B][n] (1-D for one witness; the batch is len(wits_gf2)).  Returns the array-shaped Evaluation of
     Circuit.evaluate_batch; `info` (a dict, optional) receives the stream's figures."""
-    ctx = ctx or Context.default()
-    ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+    ctx = _ops_ctx(ops, ctx)
     g0 = np.asarray(wits_gf2, dtype=np.uint8)
     batch = g0.shape[0] if g0.ndim == 2 else 1
+    if _is_device_ops(ops):  # (a torch GPU tensor: begin / rv_eval_stream_feed_device / finish)
+        se = StreamingEvaluator(wire_counts, batch, max_chunk_ops, ctx, device_compile)
+        try:
+            se.feed(ops, g0, wits_z64)
+            r = se.finish(values)
+            if info is not None:
+                info.update(se.info)
+            return r
+        finally:
+            se.close()
+    ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
     g = _eval_wits(g0, batch, np.uint8)
     z = _eval_wits(wits_z64, batch, np.uint64)
     wc = (int(wire_counts[0]), int(wire_counts[1]))

@@ -3,6 +3,8 @@
     python tools/stream_bench.py            # config 4 (recycled wire indices) and config 5
     python tools/stream_bench.py --compiler device            # the same with the pieces compiled on the GPU (RV_COMPILE_DEVICE)
     python tools/stream_bench.py --compare [--runs 5]         # config 4, host and device compiler side by side, one JSON line per row
+    python tools/stream_bench.py --compiler device --ops device [--runs 5]   # config 4 fed from a GPU tensor (rv_stream_feed_device) beside
+                                                              # the same calls fed from host memory, one JSON line per entry point
 bench.py imports streaming_record() for its `streaming` record.  RV_STREAM_STATS=1 prints the feeds' laps; with the device compiler they
 name the op upload, the device compile and the host copy of the pieces."""
 import os
@@ -130,6 +132,48 @@ def compare_compilers(ctx, seeds, want: bytes, runs: int = 5, chunk_ops: int = 1
     yield row("prove_streaming RV_STREAM_THREADS=1", prove, lambda o, c: bytes(o[0]) == want, {"RV_STREAM_THREADS": "1"})
 
 
+def device_ops_rows(ctx, seeds, want: bytes, runs: int = 5, chunk_ops: int = 1 << 18, layers: int = 153):
+    """config 4 (recycled wire indices) through the prover, verifier and evaluator with the op list in host memory and in a GPU tensor
+    (uploaded once, outside the timed region), at the context's compile flags: one record per entry point, with the op bytes each
+    call moved (rv_hook_stream_op_traffic: host -> device, device -> host)."""
+    import ctypes as C
+
+    import torch
+
+    import circuits
+    from reverie_amd import _lib
+    from reverie_amd.stream import evaluate_streaming, prove_streaming, verify_streaming
+
+    prog, wit, wc, st = circuits.layered_gf2(layers=layers, recycle=True)
+    wit = np.asarray(wit, np.uint8)
+    d_prog = torch.from_numpy(prog.view(np.uint8).reshape(-1, prog.dtype.itemsize)).to(f"cuda:{ctx.device}")
+    torch.cuda.synchronize()
+    proof0, _ = prove_streaming(prog, wit, [], wc, seeds=seeds, max_chunk_ops=chunk_ops, ctx=ctx)
+    values = {}
+
+    def traffic():
+        out = (C.c_uint64 * 2)()
+        _lib.check(_lib.lib().rv_hook_stream_op_traffic(out))
+        return np.array([int(out[0]), int(out[1])])
+
+    def same_values(out):
+        key = out.gf2.tobytes()
+        values.setdefault("first", key)
+        return bool(out.ok.all()) and values["first"] == key
+
+    calls = [("prove_streaming", lambda ops: prove_streaming(ops, wit, [], wc, seeds=seeds, max_chunk_ops=chunk_ops, ctx=ctx), lambda o: bytes(o[0]) == want),
+             ("verify_streaming", lambda ops: verify_streaming(ops, wc, proof0, max_chunk_ops=chunk_ops, ctx=ctx), lambda o: bool(o[0])),
+             ("evaluate_streaming", lambda ops: evaluate_streaming(ops, wit, [], wc, max_chunk_ops=chunk_ops, values=True, ctx=ctx), same_values)]
+    for name, f, check in calls:
+        rec = {"row": name, "n_ops": int(len(prog)), "chunk_ops": chunk_ops, "compile_flags": int(getattr(ctx, "compile_flags", 0))}
+        for where, ops in (("host_ops", prog), ("device_ops", d_prog)):
+            before = traffic()
+            t, out = _timed(lambda: f(ops), runs)
+            rec[where] = dict(t, ok=bool(check(out)), op_bytes_h2d_d2h_per_call=[int(x) for x in (traffic() - before) // (runs + 1)])
+        rec["device_over_host"] = rec["device_ops"]["ms"] / rec["host_ops"]["ms"]
+        yield rec
+
+
 def z64_record(ctx, seeds, n_mul=1_000_000, chunk_ops=1 << 16):
     import circuits
     import reverie_amd
@@ -168,6 +212,8 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--compiler", default="host", choices=["host", "device"], help="where the streams' pieces are compiled (RV_COMPILE_DEVICE)")
     ap.add_argument("--compare", action="store_true", help="config 4 with both compilers, every streaming entry point")
+    ap.add_argument("--ops", default="host", choices=["host", "device"],
+                    help="device: config 4 fed from a GPU tensor beside the host-fed calls (prover, verifier, evaluator), one JSON line each")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--bench-record", action="store_true")
     args = ap.parse_args()
@@ -182,6 +228,10 @@ if __name__ == "__main__":
     circ = reverie_amd.Circuit(prog, wc, ctx)
     want = bytes(reverie_amd.Proof.new(circ, wit, [], seeds=seeds))
     circ.close()
+    if args.ops == "device":
+        for rec in device_ops_rows(ctx, seeds, want, runs=args.runs, layers=layers):
+            print(json.dumps(rec), flush=True)
+        sys.exit(0)
     if args.compare:
         for rec in compare_compilers(ctx, seeds, want, runs=args.runs, layers=layers):
             print(json.dumps(rec), flush=True)
