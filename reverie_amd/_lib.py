@@ -92,6 +92,7 @@ SYMBOLS = [
     "rv_circuit_compiled_on_device",
     "rv_hook_maskgen",
     "rv_stream_feed_device", "rv_eval_stream_feed_device", "rv_hook_stream_op_traffic", "rv_hook_stream_piece_sums",
+    "rv_hook_compile_compare_device_chunk_ex", "rv_hook_compile_device_laps_z64",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -119,6 +120,8 @@ ARGTYPES = {
     "rv_stream_set_compile_flags": [_P, C.c_uint32],
     "rv_eval_stream_set_compile_flags": [_P, C.c_uint32],
     "rv_hook_compile_compare_device_chunk": [_P, _P, _Z, _Z, _Z, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "rv_hook_compile_compare_device_chunk_ex": [_P, _P, _Z, _Z, _Z, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "rv_hook_compile_device_laps_z64": [C.POINTER(C.c_double)],
     "rv_hook_stream_device_chunks": [],
     "rv_circuit_compiled_on_device": [_P, C.POINTER(C.c_int)],
     # streams fed from device memory
@@ -133,6 +136,7 @@ RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1
 RV_COMPILE_KEEP_WIRES = 2  # the circuit keeps every wire's final value form: rv_evaluate can return wire values
 RV_COMPILE_DEVICE = 4  # compiled on the GPU (GF(2) programs, plain or -- with WHOLE_PROVER -- lazy sums; anything else by the host compiler): the same circuit
+RV_COMPILE_DEVICE_Z64 = 8  # with RV_COMPILE_DEVICE: Z64 ops and SizeHint ops that grow nothing compile on the GPU too (B2A still on the host)
 RV_VERIFY_REFERENCE_COMPAT = 2  # the reference verifier's two unchecked conditions stay unchecked
 
 _lib = None

@@ -257,7 +257,7 @@ struct rv_ctx {
         uint64_t stamp;
     };
     std::vector<OpsEntry> ops_cache;
-    uint32_t compile_flags = 0;  // rv_ctx_set_compile_flags: RV_COMPILE_DEVICE = the cold compiles of rv_prove_ops / rv_verify_ops on the GPU
+    uint32_t compile_flags = 0;  // rv_ctx_set_compile_flags: RV_COMPILE_DEVICE [| RV_COMPILE_DEVICE_Z64] = the cold compiles of rv_prove_ops / rv_verify_ops on the GPU
     uint64_t ops_clock = 0;
     std::vector<hipEvent_t> sync_pool;
     hipEvent_t get_sync_event() {
@@ -766,10 +766,18 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
                                   rv_circuit** out, const rv_op* d_ops = nullptr);
 static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged = false);
 
+// the two bits that choose the compiler: RV_COMPILE_DEVICE_Z64 widens RV_COMPILE_DEVICE's scope and means nothing without it
+constexpr uint32_t RV_COMPILE_DEVICE_BITS = RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64;
+static bool device_bits_ok(uint32_t flags) { return !(flags & RV_COMPILE_DEVICE_Z64) || (flags & RV_COMPILE_DEVICE); }
+
 extern "C" int rv_circuit_compile_ex(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                                      rv_circuit** out) {
-    if (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE)) {
+    if (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE_BITS)) {
         g_last_error = "rv_circuit_compile_ex: unknown flag bits";
+        return RV_E_ARG;
+    }
+    if (!device_bits_ok(flags)) {
+        g_last_error = "rv_circuit_compile_ex: the flag RV_COMPILE_DEVICE_Z64 needs RV_COMPILE_DEVICE";
         return RV_E_ARG;
     }
     try {  // no C++ exception may cross the C boundary
@@ -806,7 +814,7 @@ static int compile_on_device(rv_ctx* ctx, const rv_op* d_ops, size_t n_ops, size
     const int k = ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0;
     DevCompileLaps laps;
     const int rc = compile_ops_device(ctx->stream, ctx_dev_allocator(ctx), d_ops, n_ops, z64_wires, gf2_wires, (flags & RV_COMPILE_KEEP_WIRES) != 0, k,
-                                      cc, keep, &laps);
+                                      cc, keep, &laps, nullptr, (flags & RV_COMPILE_DEVICE_Z64) != 0);
     if (rc == RV_E_DEVICE) g_last_error = "device compile: HIP error";
     if (rc == RV_E_NOMEM) g_last_error = "device compile: out of device memory";
     if (rc == RV_OK) {
@@ -840,12 +848,14 @@ static bool piece_all_gf2(const rv_op* ops, size_t n_ops) {
         if (ops[i].domain != RV_DOM_GF2) return false;
     return true;
 }
+// RV_COMPILE_DEVICE_Z64: a piece without B2A ops (compile.h)
+static bool piece_no_b2a(const rv_op* ops, size_t n_ops) { return ops_without_b2a(ops, n_ops); }
 static std::atomic<uint64_t> g_op_bytes_h2d{0}, g_op_bytes_d2h{0};  // op bytes this process's stream feeds copied to / from the device
 // d_ops not null (rv_stream_feed_device): the piece already sits in device memory -- nothing goes up, `ops` is not read.
 // up_bytes (the feeds: &g_op_bytes_h2d): receives the bytes of an upload.
 static int compile_chunk_on_device(rv_ctx* ctx, const rv_op* ops, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires,
                                    const ChunkStart& cs, Compiled& cc, DevCompileKeep* keep, double laps[3] = nullptr,
-                                   std::atomic<uint64_t>* up_bytes = nullptr) {
+                                   std::atomic<uint64_t>* up_bytes = nullptr, bool admit_z64 = false) {
     if (getenv("RV_LAZY_K")) return RV_COMPILE_FALLBACK;
     const auto t0 = std::chrono::steady_clock::now();
     rv_op* up = nullptr;
@@ -855,7 +865,7 @@ static int compile_chunk_on_device(rv_ctx* ctx, const rv_op* ops, const rv_op* d
     const auto t1 = std::chrono::steady_clock::now();
     DevCompileLaps dl;
     rc = compile_ops_device(ctx->stream, ctx_dev_allocator(ctx), d_ops ? d_ops : up, n_ops, z64_wires, gf2_wires, false, 0, cc, keep, laps ? &dl : nullptr,
-                            &cs);
+                            &cs, admit_z64);
     ctx->release(up);  // (the device compile synchronised the stream)
     if (rc == RV_E_DEVICE) g_last_error = "device compile of a stream's piece: HIP error";
     if (rc == RV_E_NOMEM) g_last_error = "device compile of a stream's piece: out of device memory";
@@ -878,7 +888,7 @@ extern "C" int rv_hook_stream_op_traffic(uint64_t out[2]) {
 static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                                   rv_circuit** out, const rv_op* d_ops) {
     if (!ctx || !out || (n_ops && !ops && !d_ops)) {
-        g_last_error = "circuit compile: NULL context, output or op array";
+        g_last_error = "circuit compile: NULL context, output or op array (flags " + std::to_string(flags) + ")";
         return RV_E_ARG;
     }
     *out = nullptr;
@@ -891,8 +901,8 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
     int rc = RV_COMPILE_FALLBACK;
     std::vector<rv_op> h_ops;  // (ops in device memory that the device path hands back: the host compiler's copy)
     if (d_ops || (flags & RV_COMPILE_DEVICE)) {
-        // RV_COMPILE_DEVICE / rv_circuit_compile_device: the GF(2) compile on the context's GPU (compile_dev.hip), at K = 1 or, with
-        // RV_COMPILE_WHOLE_PROVER, in the lazy-sum form
+        // RV_COMPILE_DEVICE / rv_circuit_compile_device: the compile on the context's GPU (compile_dev.hip) -- GF(2) programs, with
+        // RV_COMPILE_DEVICE_Z64 also Z64 and mixed ones --, at K = 1 or, with RV_COMPILE_WHOLE_PROVER, in the lazy-sum form
         if (hipSetDevice(ctx->device) != hipSuccess) {
             delete c;
             return hip_fail(hipGetLastError(), "hipSetDevice", __FILE__, __LINE__);
@@ -907,6 +917,7 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
                     c->d_gates = kept.d_gates;
                     c->d_rec_rows = kept.d_rec_rows;
                     c->d_in_rows = kept.d_in_rows;
+                    c->d_gates64 = kept.d_gates64, c->d_rec_offs64 = kept.d_rec_offs64, c->d_in_offs64 = kept.d_in_offs64;
                     c->dev_compiled = true;
                 }
             }
@@ -1004,8 +1015,9 @@ static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged) {
     // returns, so the buffer is free again for the next circuit)
     size_t stage_need = (size_t)1 << 20;  // (+ the LDS-run records, built further down: they fall back to a pageable copy when they do not fit)
     const size_t dev_sent = c->dev_compiled ? 0 : 1;  // (a device-compiled circuit's gates and ordinal tables are not sent: below)
-    for (size_t b : {dev_sent * cc.gates.size() * sizeof(Gate), dev_sent * cc.rec_rows.size() * 4, dev_sent * cc.in_rows.size() * 4, cc.gates64.size() * sizeof(Gate64),
-                     cc.rec_offs64.size() * 8, cc.in_offs64.size() * 8, cc.level_start.size() * 4, cc.level_range.size() * sizeof(LevelRange)})
+    const size_t z_sent = c->d_gates64 ? 0 : 1;  // (... nor the Z64 records and offset tables when it left them)
+    for (size_t b : {dev_sent * cc.gates.size() * sizeof(Gate), dev_sent * cc.rec_rows.size() * 4, dev_sent * cc.in_rows.size() * 4, z_sent * cc.gates64.size() * sizeof(Gate64),
+                     z_sent * cc.rec_offs64.size() * 8, z_sent * cc.in_offs64.size() * 8, cc.level_start.size() * 4, cc.level_range.size() * sizeof(LevelRange)})
         stage_need += (b + 255) & ~(size_t)255;
     constexpr bool stage_on = true;
     if (stage_on && stage_need <= rv_ctx::UP_STAGE_MAX && stage_need > ctx->h_up_cap) {
@@ -1041,13 +1053,13 @@ static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged) {
         return RV_OK;
     };
     // (a device-compiled circuit's gate records and ordinal tables were written in HBM by the compiler: not sent again)
-    const bool dev = c->dev_compiled;
+    const bool dev = c->dev_compiled, dev64 = c->d_gates64 != nullptr;  // (the three Z64 arrays are kept together)
     if ((!dev && (rc = up(cc.gates.data(), cc.gates.size() * sizeof(Gate), (void**)&c->d_gates))) ||
         (!dev && (rc = up(cc.rec_rows.data(), cc.rec_rows.size() * 4, (void**)&c->d_rec_rows))) ||
         (!dev && (rc = up(cc.in_rows.data(), cc.in_rows.size() * 4, (void**)&c->d_in_rows))) ||
-        (rc = up(cc.gates64.data(), cc.gates64.size() * sizeof(Gate64), (void**)&c->d_gates64)) ||
-        (rc = up(cc.rec_offs64.data(), cc.rec_offs64.size() * 8, (void**)&c->d_rec_offs64)) ||
-        (rc = up(cc.in_offs64.data(), cc.in_offs64.size() * 8, (void**)&c->d_in_offs64)) ||
+        (!dev64 && (rc = up(cc.gates64.data(), cc.gates64.size() * sizeof(Gate64), (void**)&c->d_gates64))) ||
+        (!dev64 && (rc = up(cc.rec_offs64.data(), cc.rec_offs64.size() * 8, (void**)&c->d_rec_offs64))) ||
+        (!dev64 && (rc = up(cc.in_offs64.data(), cc.in_offs64.size() * 8, (void**)&c->d_in_offs64))) ||
         (rc = up(cc.level_start.data(), cc.level_start.size() * 4, (void**)&c->d_level_start)) ||
         (rc = up(cc.level_range.data(), cc.level_range.size() * sizeof(LevelRange), (void**)&c->d_level_range))) {
         rv_circuit_destroy(c);
@@ -1307,7 +1319,8 @@ extern "C" int rv_hook_compile_compare(const rv_op* ops, size_t n_ops, size_t z6
 
 extern "C" int rv_circuit_compile_device(rv_ctx* ctx, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                                          rv_circuit** out) {
-    if (!ctx || !out || (n_ops && !d_ops) || (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE))) return RV_E_ARG;
+    // (the call implies RV_COMPILE_DEVICE: RV_COMPILE_DEVICE_Z64 needs no other bit here)
+    if (!ctx || !out || (n_ops && !d_ops) || (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE_BITS))) return RV_E_ARG;
     try {
         return rv_circuit_compile_impl(ctx, nullptr, n_ops, z64_wires, gf2_wires, flags | RV_COMPILE_DEVICE, out, d_ops);
     } catch (...) {
@@ -1317,14 +1330,16 @@ extern "C" int rv_circuit_compile_device(rv_ctx* ctx, const rv_op* d_ops, size_t
 }
 
 extern "C" int rv_ctx_set_compile_flags(rv_ctx* ctx, uint32_t flags) {
-    if (!ctx || (flags & ~RV_COMPILE_DEVICE)) return RV_E_ARG;
+    if (!ctx || (flags & ~RV_COMPILE_DEVICE_BITS) || !device_bits_ok(flags)) return RV_E_ARG;
     ctx->compile_flags = flags;
     return RV_OK;
 }
 
 extern "C" int rv_hook_compile_compare_device(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, int* path,
                                               int* diff) {
-    if (!ctx || !path || !diff || (n_ops && !ops) || (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE))) return RV_E_ARG;
+    if (!ctx || !path || !diff || (n_ops && !ops) || (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE_BITS)) ||
+        !device_bits_ok(flags))
+        return RV_E_ARG;
     try {
         const int k = ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0;
         Compiled a, b;
@@ -1354,9 +1369,9 @@ extern "C" int rv_hook_compile_compare_device(rv_ctx* ctx, const rv_op* ops, siz
     }
 }
 
-extern "C" int rv_hook_compile_compare_device_chunk(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const uint64_t start[6],
-                                                    int* path, int* diff) {
-    if (!ctx || !path || !diff || !start || (n_ops && !ops)) return RV_E_ARG;
+extern "C" int rv_hook_compile_compare_device_chunk_ex(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires,
+                                                       const uint64_t start[6], uint32_t flags, int* path, int* diff) {
+    if (!ctx || !path || !diff || !start || (n_ops && !ops) || (flags & ~RV_COMPILE_DEVICE_BITS) || !device_bits_ok(flags)) return RV_E_ARG;
     try {
         ChunkStart cs;
         cs.mask_phase = (uint32_t)start[0], cs.mask64_phase = (uint32_t)start[1];
@@ -1365,7 +1380,8 @@ extern "C" int rv_hook_compile_compare_device_chunk(rv_ctx* ctx, const rv_op* op
         Compiled a, b;
         const int rc = compile_ops_seq(ops, n_ops, z64_wires, gf2_wires, a, &cs);
         HIPCHK(hipSetDevice(ctx->device));
-        const int rd = compile_chunk_on_device(ctx, ops, nullptr, n_ops, z64_wires, gf2_wires, cs, b, nullptr);
+        const int rd = compile_chunk_on_device(ctx, ops, nullptr, n_ops, z64_wires, gf2_wires, cs, b, nullptr, nullptr, nullptr,
+                                               (flags & RV_COMPILE_DEVICE_Z64) != 0);
         if (rd == RV_OK) {
             *path = 1;
             *diff = rc == RV_OK ? compiled_diff(a, b) : 100;  // (the device path compiled a piece the host compiler rejects)
@@ -1380,6 +1396,18 @@ extern "C" int rv_hook_compile_compare_device_chunk(rv_ctx* ctx, const rv_op* op
         g_last_error = "out of host memory";
         return RV_E_NOMEM;
     }
+}
+
+extern "C" int rv_hook_compile_compare_device_chunk(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const uint64_t start[6],
+                                                    int* path, int* diff) {
+    return rv_hook_compile_compare_device_chunk_ex(ctx, ops, n_ops, z64_wires, gf2_wires, start, 0, path, diff);
+}
+
+extern "C" int rv_hook_compile_device_laps_z64(double* out) {
+    if (!out) return RV_E_ARG;
+    std::lock_guard<std::mutex> lk(g_dev_laps_mu);
+    *out = g_dev_laps.z64;
+    return RV_OK;
 }
 
 extern "C" int rv_hook_compile_device_laps(double out[6]) {

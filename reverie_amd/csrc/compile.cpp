@@ -644,6 +644,12 @@ void count_events(const rv_op* ops, size_t n_ops, StreamEvents* ev) {
     *ev = e;
 }
 
+bool ops_without_b2a(const rv_op* ops, size_t n_ops) {
+    for (size_t i = 0; i < n_ops; i++)
+        if (ops[i].domain != RV_DOM_GF2 && ops[i].domain != RV_DOM_Z64 && ops[i].domain != RV_DOM_SIZEHINT) return false;
+    return true;
+}
+
 void relocate_chunk(Compiled& cc, uint64_t on0, uint64_t pre0, uint64_t on_words64_0, uint64_t pre_words64_0) {
     if (on0 || pre0) {
         for (Gate& g : cc.gates) {  // (eo / ep of gates without a transcript row are never read)

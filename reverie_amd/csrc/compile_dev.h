@@ -6,6 +6,12 @@
 // forced lazy_k, no RV_LAZY_K in the environment, at most 2^16 topological rounds.  Everything else, every op-list error included, is
 // RV_COMPILE_FALLBACK: the caller runs compile_ops, which returns the canonical result or error code.
 //
+// admit_z64 (RV_COMPILE_DEVICE_Z64): the list may also hold Z64 ops (all ten opcodes) and SizeHint ops that grow neither wire count.
+// The GF(2) ops of such a list go through the same pipeline, in either form; every Z64 op becomes one Gate64 at one level above its
+// deepest operand, and the two domains share the level numbering (the deeper one's count; the other's tables have empty trailing
+// levels).  Still RV_COMPILE_FALLBACK: a B2A op, a SizeHint that grows a wire count, RV_COMPILE_KEEP_WIRES, RV_LAZY_K, an op-list
+// error in either domain, more than 2^16 rounds in either domain, and a plain whole-program compile for which lazy_forms_pay holds.
+//
 // Chunk mode (`chunk` not null): one piece of a stream, identical to compile_ops_seq(..., chunk) -- the wires start in their carried
 // rows, the counters at the ChunkStart's, no sum is dropped as unread, and one more level writes every wire the piece wrote back to
 // its carried row.  A chunk is final at K = 1 whatever its shape (lazy_forms_pay does not apply; a forced lazy_k is a fallback); an
@@ -29,6 +35,7 @@ struct DevAlloc {
 struct DevCompileLaps {
     float classify = 0, writers = 0, levels = 0, tables = 0, download = 0;
     uint32_t rounds = 0;  // topological rounds launched
+    float z64 = 0;        // admit_z64, a list with Z64 ops: the split and the Z64 ops' steps (the five above are then the GF(2) ops')
 };
 
 // The device arrays a device compile leaves for the circuit (null: freed before the call returns, nothing is kept)
@@ -36,12 +43,16 @@ struct DevCompileKeep {
     Gate* d_gates = nullptr;
     uint32_t* d_rec_rows = nullptr;
     uint32_t* d_in_rows = nullptr;
+    // a list with Z64 ops (admit_z64; null otherwise)
+    Gate64* d_gates64 = nullptr;
+    uint64_t* d_rec_offs64 = nullptr;
+    uint64_t* d_in_offs64 = nullptr;
 };
 
 // RV_OK (out filled; compile_us / upload_us / device_bytes / scratch_bytes left zero), RV_COMPILE_FALLBACK, or RV_E_NOMEM /
 // RV_E_DEVICE.  d_ops: n_ops packed rv_op records in device memory (read only).  Runs on `st`; synchronises it before returning.
 int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires,
                        bool keep_wires, int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps = nullptr,
-                       const ChunkStart* chunk = nullptr);
+                       const ChunkStart* chunk = nullptr, bool admit_z64 = false);
 
 }  // namespace rv

@@ -1,5 +1,6 @@
 // see compile_dev.h
 //
+// (Z64 ops and mixed lists, RV_COMPILE_DEVICE_Z64: compile_mixed_device, at the end of this file.)
 // The device compile of a whole GF(2) program at K = 1 (every XOR of two distinct rows materialised; the lazy-sum form's differences are
 // with its kernels: value_lazy, and the LAZY instantiations of steps 3 and 5), in the steps of the host
 // compiler (compile.cpp: run_pass, Builder, the (level, class) sort and the pipelining tables):
@@ -219,7 +220,7 @@ __global__ __launch_bounds__(TB) void k_cd_classify(const rv_op* ops, size_t n, 
 
 // the ordinal tables: reconstruction ordinal -> online row, input ordinal -> online row, the AssertZero ops
 __global__ __launch_bounds__(TB) void k_cd_ordinals(const rv_op* ops, size_t n, const C4* cx, uint32_t on0, uint32_t* rec_rows, uint32_t* in_rows,
-                                                    uint32_t* as_rec, uint64_t* as_op) {
+                                                    uint32_t* as_rec, uint64_t* as_op, const uint32_t* orig) {
     const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
     if (i >= n) return;
     const uint32_t opc = ops[i].opcode;
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(TB) void k_cd_ordinals(const rv_op* ops, size_t n, 
     if (opc == RV_OP_MUL || opc == RV_OP_ASSERTZERO) rec_rows[x] = eo;
     if (opc == RV_OP_ASSERTZERO) {
         as_rec[c.as] = x;
-        as_op[c.as] = i;
+        as_op[c.as] = orig ? orig[i] : i;  // (orig: the ops are the GF(2) ops of a mixed list, orig[i] = op i's place in it)
     }
 }
 
@@ -433,9 +434,18 @@ __device__ inline uint4 value_lazy(const rv_op& op, uint32_t i, int2 p, const ui
     return out;
 }
 
+// a Z64 op's level (run_pass, case RV_DOM_Z64): Input, Random and Const 0, every other gate one above its deepest operand; SSA 0 and
+// a chunk's carried slots (p < 0) count as -1
+__device__ inline int level_z64(const rv_op& op, int2 p, const int* glvl) {
+    if (op_reads(op.opcode) == 0) return 0;
+    return max(p.x >= 0 ? glvl[p.x] : -1, p.y >= 0 ? glvl[p.y] : -1) + 1;
+}
+
 // step 3: one round.  rounds[r] = {first frontier slot, count}; the ops whose last pending operand this round resolves form
-// round r + 1's frontier.  LAZY: the values are lazy sums in V3 (V unused), else one row or a constant in V (V3 unused).
-template <bool LAZY>
+// round r + 1's frontier.  FORM_LAZY: the values are lazy sums in V3 (V unused); FORM_K1: one row or a constant in V (V3 unused);
+// FORM_Z64: Z64 ops, which have a level and no value (V, V3, mat unused).
+enum { FORM_K1 = 0, FORM_LAZY = 1, FORM_Z64 = 2 };
+template <int FORM>
 __global__ __launch_bounds__(TB) void k_cd_round(uint32_t r, uint32_t chunk, const rv_op* ops, const int2* prod, const uint32_t* uses, const uint32_t* cons_off,
                                                  const uint32_t* cons, uint32_t* rem, int2* V, uint4* V3, int* glvl, uint32_t* mat, uint32_t* frontier,
                                                  uint2* rounds) {
@@ -455,10 +465,11 @@ __global__ __launch_bounds__(TB) void k_cd_round(uint32_t r, uint32_t chunk, con
         const int2 p = prod[i];
         int gl = -1;
         uint32_t mt = 0;
-        if constexpr (LAZY) V3[i] = value_lazy(op, i, p, uses, V3, glvl, &gl, &mt);
+        if constexpr (FORM == FORM_Z64) gl = level_z64(op, p, glvl);
+        else if constexpr (FORM == FORM_LAZY) V3[i] = value_lazy(op, i, p, uses, V3, glvl, &gl, &mt);
         else V[i] = value_k1(op, i, p, chunk, uses, V, &gl, &mt);
         glvl[i] = gl;
-        mat[i] = mt;
+        if constexpr (FORM != FORM_Z64) mat[i] = mt;
         const uint32_t c0 = cons_off[i], c1 = c0 + uses[i];
         for (uint32_t k = c0; k < c1; k++) {
             const uint32_t c = cons[k];
@@ -807,13 +818,59 @@ hipError_t radix_sort(Scratch& S, hipStream_t st, uint32_t* k[2], uint32_t* v[2]
     return hipGetLastError();
 }
 
-}  // namespace
+// step 3's launches: rounds until the frontier is empty, in batches between two looks at the round table.  *n_rounds: rounds launched.
+// RV_OK, RV_COMPILE_FALLBACK (the cap: a chain of ops this deep compiles on the host) or RV_E_DEVICE.
+struct RoundArgs {
+    const rv_op* ops;
+    const int2* prod;
+    const uint32_t *uses, *cons_off, *cons;
+    uint32_t* rem;
+    int2* V;
+    uint4* V3;
+    int* glvl;
+    uint32_t *mat, *frontier;
+    uint2* rounds;
+};
+int run_rounds(hipStream_t st, int form, uint32_t chunk, size_t n, uint32_t max_rounds, const RoundArgs& a, uint32_t* n_rounds) {
+    const uint32_t round_blocks = std::min<uint32_t>(blocks(n, TB), 1024);
+    uint32_t r = 0, batch = 8;
+    for (;;) {
+        if (r >= max_rounds) return RV_COMPILE_FALLBACK;
+        const uint32_t e = std::min(r + batch, max_rounds);
+        for (; r < e; r++) {
+#define CD_ROUND(F) k_cd_round<F><<<round_blocks, TB, 0, st>>>(r, chunk, a.ops, a.prod, a.uses, a.cons_off, a.cons, a.rem, a.V, a.V3, a.glvl, a.mat, a.frontier, a.rounds)
+            if (form == FORM_LAZY) CD_ROUND(FORM_LAZY);
+            else if (form == FORM_Z64) CD_ROUND(FORM_Z64);
+            else CD_ROUND(FORM_K1);
+#undef CD_ROUND
+        }
+        uint2 nxt;
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&nxt, a.rounds + r, sizeof nxt, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) {
+            (void)hipGetLastError();
+            return RV_E_DEVICE;
+        }
+        if (nxt.y == 0) {
+            *n_rounds = r;
+            return nxt.x == n ? RV_OK : RV_COMPILE_FALLBACK;  // (every op resolves exactly once; the second cannot happen)
+        }
+        batch = std::min<uint32_t>(batch * 2, 256);
+    }
+}
 
-int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, bool keep_wires,
-                       int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps, const ChunkStart* chunk) {
+// What the Z64 side of a mixed list tells the GF(2) compile (compile_mixed_device): the ops are the list's GF(2) ops in order
+struct Mixed {
+    const uint32_t* orig;  // op i's place in the whole list (the AssertZero table)
+    size_t n_total;        // ops of the whole list
+    uint32_t levels64;     // levels the Z64 ops take (the level count is the deeper domain's, Builder::max_level)
+    bool wb64;             // a chunk whose Z64 side has write-back gates: they share the GF(2) write-backs' level
+};
+
+int compile_gf2_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, bool keep_wires,
+                       int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps, const ChunkStart* chunk, const Mixed* mx) {
     // (a Z64 op in the list is what sends a program to the host; the Z64 wire count alone does not)
     const bool lazy = force_lazy_k == RV_LIN_K;  // the lazy-sum form: whole programs only (a chunk is final at K = 1)
-    if (keep_wires || (force_lazy_k && (!lazy || chunk)) || getenv("RV_LAZY_K") || (n_ops == 0 && !chunk) || n_ops >= (1u << 28) || gf2_wires >= (1u << 31) ||
+    if (keep_wires || (force_lazy_k && (!lazy || chunk)) || getenv("RV_LAZY_K") || (n_ops == 0 && !chunk && !mx) || n_ops >= (1u << 28) || gf2_wires >= (1u << 31) ||
         (chunk && gf2_wires >= (1u << 30)))  // (a chunk names wire w's carried row -2 - w, below the host compiler's CARRY flag bit)
         return RV_COMPILE_FALLBACK;
     const size_t n = n_ops;
@@ -887,7 +944,7 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     uint32_t* as_rec = S.get<uint32_t>(tot.as);
     uint64_t* as_op = S.get<uint64_t>(tot.as);
     CDNEED(as_rec && as_op);
-    k_cd_ordinals<<<gb, TB, 0, st>>>(d_ops, n, cx, seeds.on0, rec_rows, in_rows, as_rec, as_op);
+    k_cd_ordinals<<<gb, TB, 0, st>>>(d_ops, n, cx, seeds.on0, rec_rows, in_rows, as_rec, as_op, mx ? mx->orig : nullptr);
     CDCHK(hipGetLastError());
     mark(1);
     // ---- 2. the last writer of every read ----
@@ -927,25 +984,11 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     CDCHK(hipMemsetAsync(mat + n, 0, 4, st));
     k_cd_front0<<<gb, TB, 0, st>>>(rem, n, frontier, rounds);
     CDCHK(hipGetLastError());
-    const uint32_t round_blocks = std::min<uint32_t>(gb, 1024);
-    uint32_t r = 0, batch = 8;
-    bool done = false;
-    while (!done) {
-        if (r >= max_rounds) return RV_COMPILE_FALLBACK;  // (the cap: a chain of ops this deep compiles on the host)
-        const uint32_t e = std::min(r + batch, max_rounds);
-        for (; r < e; r++) {
-            if (lazy) k_cd_round<true><<<round_blocks, TB, 0, st>>>(r, 0u, d_ops, prod, uses, cons_off, cons, rem, V, V3, glvl, mat, frontier, rounds);
-            else k_cd_round<false><<<round_blocks, TB, 0, st>>>(r, seeds.chunk, d_ops, prod, uses, cons_off, cons, rem, V, V3, glvl, mat, frontier, rounds);
-        }
-        CDCHK(hipGetLastError());
-        uint2 nxt;
-        CDCHK(hipMemcpyAsync(&nxt, rounds + r, sizeof nxt, hipMemcpyDeviceToHost, st));
-        CDCHK(hipStreamSynchronize(st));
-        if (nxt.y == 0) {
-            if (nxt.x != n) return RV_COMPILE_FALLBACK;  // (every op resolves exactly once; cannot happen)
-            done = true;
-        }
-        batch = std::min<uint32_t>(batch * 2, 256);
+    uint32_t r = 0;
+    {
+        const RoundArgs ra{d_ops, prod, uses, cons_off, cons, rem, V, V3, glvl, mat, frontier, rounds};
+        const int rr = run_rounds(st, lazy ? FORM_LAZY : FORM_K1, lazy ? 0u : seeds.chunk, n, max_rounds, ra, &r);
+        if (rr != RV_OK) return rr;
     }
     if (laps) laps->rounds = r;
     if (lazy) k_cd_stats<true><<<gb, TB, 0, st>>>(d_ops, n, prod, V, V3, glvl, mat, d_stats);
@@ -973,8 +1016,10 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     // the write-back level: one G_XORK per written wire behind every other level; the carried forms it reads are level 0's
     const uint32_t n_wb = chunk ? h_small[24] : 0, n_wbmat = chunk ? h_small[25] : 0, n_wbrow = chunk ? h_small[26] : 0;
     seeds.n_wbmat = n_wbmat;
-    const uint32_t wb_level = std::max<uint32_t>(n_levels_ops, n_wbmat ? 1u : 0u);
-    const uint32_t n_levels = n_wb ? wb_level + 1 : n_levels_ops;
+    // (a mixed list: the deeper domain's levels count, and either domain's write-backs make the last level)
+    const uint32_t levels64 = mx ? mx->levels64 : 0;
+    const uint32_t wb_level = std::max<uint32_t>({n_levels_ops, n_wbmat ? 1u : 0u, levels64});
+    const uint32_t n_levels = (n_wb || (mx && mx->wb64)) ? wb_level + 1 : std::max(n_levels_ops, levels64);
     const uint64_t n_gates = n_gates_ops + n_wbmat + n_wb;
     // the K = 1 compile is final unless the circuit is deep and narrow (compile_ops_seq): those go to the host compiler
     // (a chunk is compiled once, at K = 1, whatever its shape; a forced lazy-sum compile is final too)
@@ -1085,7 +1130,7 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
         cc.pre_words64 = chunk->pre_words64_0;
     }
     rv_circuit_info& info = cc.info;
-    info.n_ops = n;
+    info.n_ops = mx ? mx->n_total : n;
     info.gf2_inputs = tot.in;
     info.gf2_muls = tot.mul;
     info.gf2_asserts = tot.as;
@@ -1113,8 +1158,405 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
         S.keep(in_rows);
     }
     return RV_OK;
+}
+
+// ---- Z64 ops and mixed lists (RV_COMPILE_DEVICE_Z64) ----
+// The two domains share no wire and, without B2A, no gate: run_pass keeps them apart except for the level count.  So a mixed list is
+// split: its GF(2) ops, compacted in order, go through the pipeline above unchanged, and its Z64 ops through the same steps in a
+// simpler form -- no folding, every op one Gate64, every counter a prefix sum, a gate's level one above its deepest operand.
+//   1. classify    one thread per op of the whole list: the Z64 and SizeHint checks of run_pass (the GF(2) ops are checked by
+//                  k_cd_classify once compacted), the Z64 counters and each op's place in its domain's list: two 16-byte tuple scans
+//   2. writers     the sort, segments and resolve kernels above, over the Z64 ops and wires
+//   3. levels      the round kernel in its FORM_Z64
+//   4. tables      a stable sort by level; the records, offsets and AssertZero tables written by one thread per gate; a chunk's
+//                  write-back copies (one G64_ADDC per written wire, in wire order) behind them
+static_assert(sizeof(Gate64) == 64, "Gate64 is compared bytewise: no padding");
+struct Seeds64 {
+    uint32_t ssa_base;  // the first op's SSA id: 1, or 1 + z64_wires behind a chunk's carried slots
+    uint32_t m0;        // ShareGen<Z64> calls before the piece (mask64_phase)
+    uint64_t on0, pre0;  // transcript words in front of the piece's own
+};
+
+// pc: {GF(2) op, Z64 op, 0, 0} -- their exclusive scan is every op's place in its domain's list; zc: the Z64 counters of compile.cpp
+// (m: Input 1, Random 1, Mul 2; mul; as; in).  A B2A op, an unknown domain, a SizeHint that grows a wire count and any Z64 op
+// run_pass rejects raise the flag: the host compiler takes the list.
+__global__ __launch_bounds__(TB) void k_z_classify(const rv_op* ops, size_t n, uint32_t W2, uint32_t W64, C4* zc, C4* pc, uint32_t* flag) {
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const rv_op op = ops[i];
+    bool bad = op.reserved != 0;
+    C4 z{0, 0, 0, 0}, p{0, 0, 0, 0};
+    if (op.domain == RV_DOM_GF2) {
+        p.m = 1;
+    } else if (op.domain == RV_DOM_Z64) {
+        if (op.opcode > RV_OP_CONST) bad = true;
+        const int nr = bad ? 0 : op_reads(op.opcode);
+        if (!bad && op_writes(op.opcode) && op.dst >= W64) bad = true;
+        if (nr >= 1 && op.a >= W64) bad = true;
+        if (nr >= 2 && op.b >= W64) bad = true;
+        p.mul = 1;
+        if (op.opcode == RV_OP_INPUT) z.m = 1, z.in = 1;
+        else if (op.opcode == RV_OP_RANDOM) z.m = 1;
+        else if (op.opcode == RV_OP_MUL) z.m = 2, z.mul = 1;
+        else if (op.opcode == RV_OP_ASSERTZERO) z.as = 1;
+    } else if (op.domain == RV_DOM_SIZEHINT) {
+        if (op.a > W64 || op.b > W2) bad = true;
+    } else {
+        bad = true;
+    }
+    if (bad) atomicOr(flag, 1u);
+    zc[i] = z;
+    pc[i] = p;
+}
+// px, zx: the exclusive scans.  Each domain's ops in order, with their places in the whole list; the Z64 ops' counters go with them
+__global__ __launch_bounds__(TB) void k_z_compact(const rv_op* ops, size_t n, const C4* px, const C4* zx, rv_op* ops2, uint32_t* orig2, rv_op* ops64,
+                                                  uint32_t* orig64, C4* zc64) {
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const rv_op op = ops[i];
+    const C4 p = px[i];
+    if (op.domain == RV_DOM_GF2) {
+        ops2[p.m] = op;
+        orig2[p.m] = (uint32_t)i;
+    } else if (op.domain == RV_DOM_Z64) {
+        ops64[p.mul] = op;
+        orig64[p.mul] = (uint32_t)i;
+        zc64[p.mul] = zx[i];
+    }
+}
+// the writer sort's keys (as k_cd_classify's: the wire, W64 for AssertZero)
+__global__ __launch_bounds__(TB) void k_z_wkeys(const rv_op* ops, size_t n, uint32_t W64, uint32_t* keys, uint32_t* vals) {
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const rv_op op = ops[i];
+    keys[i] = op_writes(op.opcode) ? op.dst : W64;
+    vals[i] = (uint32_t)i;
+}
+// the level sort's keys, and the deepest level (one atomic per wavefront)
+__global__ __launch_bounds__(TB) void k_z_lkeys(const int* glvl, size_t n, uint32_t* keys, uint32_t* vals, uint32_t* max_level) {
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    const uint32_t l = i < n ? (uint32_t)glvl[i] : 0u;
+    if (i < n) {
+        keys[i] = l;
+        vals[i] = (uint32_t)i;
+    }
+    const uint32_t m = wave_max_u32(l);
+    if ((threadIdx.x & 63u) == 0 && m) atomicMax(max_level, m);
+}
+// a chunk's written wires (each gets a write-back: an op's SSA id is never the carried slot's)
+__global__ __launch_bounds__(TB) void k_z_wb_flags(const uint32_t* seg_lo, const uint32_t* seg_hi, uint32_t W64, uint32_t* fl) {
+    const size_t w = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (w >= W64) return;
+    fl[w] = seg_hi[w] > seg_lo[w];
+}
+// an operand: its SSA id (never written: 0; a chunk's carried slot 1 + w) and where its mask row lives (Builder::emit64's ssa_row64)
+__device__ inline uint32_t z_ssa(int p, const C4* zc, const Seeds64& s) {
+    return p >= 0 ? s.ssa_base + (uint32_t)p - zc[p].as : p == -1 ? 0u : 1u + (uint32_t)(-2 - p);
+}
+__device__ inline uint32_t z_mask_row(int p, const rv_op* ops, const C4* zc, const Seeds64& s) {
+    if (p >= 0) {
+        const uint32_t opc = ops[p].opcode;
+        if (opc == RV_OP_INPUT || opc == RV_OP_RANDOM) return G64_MASK_ROW | (s.m0 + zc[p].m);
+        if (opc == RV_OP_MUL) return G64_MASK_ROW | (s.m0 + zc[p].m + 1);
+    }
+    return z_ssa(p, zc, s);
+}
+// the Gate64 records in (level, program) order; the input / reconstruction offsets and the AssertZero tables by ordinal
+__global__ __launch_bounds__(TB) void k_z_gates(const uint32_t* sv, size_t n, const rv_op* ops, const int2* prod, const C4* zc, const uint32_t* orig, Seeds64 s,
+                                                Gate64* gates, uint64_t* rec_offs, uint64_t* in_offs, uint32_t* as_rec, uint64_t* as_op) {
+    const size_t p = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t i = sv[p];
+    const rv_op op = ops[i];
+    const C4 c = zc[i];
+    const int2 pr = prod[i];
+    const int nr = op_reads(op.opcode);
+    Gate64 g;
+    g.op = 0, g.dst = 0, g.a = 0, g.b = 0, g.m = 0, g.m2 = 0, g.eo = 0, g.ep = 0, g.x = 0, g.xc = 0;
+    g.imm = op.imm;
+    g.a = nr >= 1 ? z_ssa(pr.x, zc, s) : 0u;
+    g.b = nr >= 2 ? z_ssa(pr.y, zc, s) : 0u;
+    g.am = nr >= 1 ? z_mask_row(pr.x, ops, zc, s) : 0u;
+    g.bm = nr >= 2 ? z_mask_row(pr.y, ops, zc, s) : 0u;
+    if (op_writes(op.opcode)) g.dst = s.ssa_base + i - c.as;
+    const uint64_t eo = s.on0 + c.in + 8ull * ((uint64_t)c.mul + c.as);
+    const uint32_t x = c.mul + c.as;
+    switch (op.opcode) {
+    case RV_OP_INPUT:
+        g.op = G64_INPUT;
+        g.m = s.m0 + c.m;
+        g.eo = eo;
+        g.x = c.in;
+        in_offs[c.in] = eo;
+        break;
+    case RV_OP_RANDOM:
+        g.op = G64_RANDOM;
+        g.m = s.m0 + c.m;
+        break;
+    case RV_OP_CONST: g.op = G64_CONST; break;
+    case RV_OP_ADD: g.op = G64_ADD; break;
+    case RV_OP_SUB: g.op = G64_SUB; break;
+    case RV_OP_ADDCONST: g.op = G64_ADDC; break;
+    case RV_OP_SUBCONST: g.op = G64_SUBC; break;
+    case RV_OP_MULCONST: g.op = G64_MULC; break;
+    case RV_OP_MUL:
+        g.op = G64_MUL;
+        g.m = s.m0 + c.m;
+        g.ep = s.pre0 + c.mul;
+        g.xc = c.mul;
+        g.eo = eo;
+        g.x = x;
+        rec_offs[x] = eo;
+        break;
+    default:  // AssertZero
+        g.op = G64_ASSERT;
+        g.eo = eo;
+        g.x = x;
+        rec_offs[x] = eo;
+        as_rec[c.as] = x;
+        as_op[c.as] = orig ? orig[i] : i;
+        break;
+    }
+    gates[p] = g;
+}
+// a chunk's write-back level: wire w's final value copied to its carried slot.  sv: the writer sort's op indices; fx: the exclusive
+// scan of k_z_wb_flags
+__global__ __launch_bounds__(TB) void k_z_wb_gates(const uint32_t* sv, const uint32_t* seg_lo, const uint32_t* seg_hi, const uint32_t* fx, uint32_t W64,
+                                                   const rv_op* ops, const C4* zc, Seeds64 s, Gate64* gates) {
+    const size_t w = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (w >= W64 || seg_hi[w] <= seg_lo[w]) return;
+    const int q = (int)sv[seg_hi[w] - 1];
+    Gate64 g;
+    g.op = G64_ADDC, g.dst = 1u + (uint32_t)w, g.b = 0, g.m = 0, g.m2 = 0, g.eo = 0, g.ep = 0, g.x = 0, g.xc = 0, g.imm = 0, g.bm = 0;
+    g.a = z_ssa(q, zc, s);
+    g.am = z_mask_row(q, ops, zc, s);
+    gates[fx[w]] = g;
+}
+
+int compile_mixed_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n, size_t z64_wires, size_t gf2_wires, bool keep_wires, int force_lazy_k,
+                         Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps, const ChunkStart* chunk) {
+    const bool lazy = force_lazy_k == RV_LIN_K;
+    if (keep_wires || (force_lazy_k && (!lazy || chunk)) || getenv("RV_LAZY_K") || n >= (1u << 28) || gf2_wires >= (1u << 31) || z64_wires >= (1u << 30))
+        return RV_COMPILE_FALLBACK;
+    if (n == 0)  // (an empty piece; an empty program is the host compiler's)
+        return compile_gf2_device(st, A, d_ops, n, z64_wires, gf2_wires, keep_wires, force_lazy_k, out, keep, laps, chunk, nullptr);
+    const uint32_t W2 = (uint32_t)gf2_wires, W64 = (uint32_t)z64_wires;
+    const uint64_t LIM = 0xFFFFFFFFull - 512;
+    if (chunk && (chunk->mask64_phase >= 2 || chunk->on_words64_0 > (1ull << 62) || chunk->pre_words64_0 > (1ull << 62))) return RV_COMPILE_FALLBACK;
+    Scratch S(A, st);
+    hipEvent_t ev[4] = {};
+    if (laps)
+        for (auto& e : ev)
+            if (hipEventCreate(&e) != hipSuccess) return RV_E_DEVICE;
+    struct EvGuard {
+        hipEvent_t* e;
+        ~EvGuard() {
+            for (int k = 0; k < 4; k++)
+                if (e[k]) (void)hipEventDestroy(e[k]);
+        }
+    } ev_guard{ev};
+    auto mark = [&](int k) {
+        if (laps) (void)hipEventRecord(ev[k], st);
+    };
+    const uint32_t gb = blocks(n, TB);
+    mark(0);
+    // ---- 1. classify, split ----
+    C4* zx = S.get<C4>(n);
+    C4* px = S.get<C4>(n);
+    uint32_t* d_small = S.get<uint32_t>(32);  // [0] error flag, [4..8) Z64 counter totals, [8..12) op counts, [12] deepest Z64 level, [13] write-backs
+    CDNEED(zx && px && d_small);
+    CDCHK(hipMemsetAsync(d_small, 0, 32 * 4, st));
+    k_z_classify<<<gb, TB, 0, st>>>(d_ops, n, W2, W64, zx, px, d_small);
+    CDCHK(hipGetLastError());
+    CDCHK((scan_excl<C4, SumC4>(S, st, zx, zx, n, (C4*)(d_small + 4))));
+    CDCHK((scan_excl<C4, SumC4>(S, st, px, px, n, (C4*)(d_small + 8))));
+    uint32_t h_small[16];
+    CDCHK(hipMemcpyAsync(h_small, d_small, sizeof h_small, hipMemcpyDeviceToHost, st));
+    CDCHK(hipStreamSynchronize(st));
+    if (h_small[0]) return RV_COMPILE_FALLBACK;
+    const C4 tot{h_small[4], h_small[5], h_small[6], h_small[7]};
+    const size_t n2 = h_small[8], n64 = h_small[9];
+    if (n2 == n)  // no Z64 op and no SizeHint: the list as it is
+        return compile_gf2_device(st, A, d_ops, n, z64_wires, gf2_wires, keep_wires, force_lazy_k, out, keep, laps, chunk, nullptr);
+    Seeds64 s64{1u + (chunk ? W64 : 0u), chunk ? chunk->mask64_phase : 0u, chunk ? chunk->on_words64_0 : 0, chunk ? chunk->pre_words64_0 : 0};
+    const uint64_t n_masks64 = (uint64_t)s64.m0 + tot.m;
+    if ((uint64_t)s64.ssa_base + n64 > LIM || n_masks64 > LIM || (n_masks64 + 1) / 2 > RV_MAX_CTR_BLOCKS) return RV_COMPILE_FALLBACK;
+    rv_op* ops2 = S.get<rv_op>(n2);
+    uint32_t* orig2 = S.get<uint32_t>(n2);
+    rv_op* ops64 = S.get<rv_op>(n64);
+    uint32_t* orig64 = S.get<uint32_t>(n64);
+    C4* zc = S.get<C4>(n64);
+    CDNEED(ops2 && orig2 && ops64 && orig64 && zc);
+    k_z_compact<<<gb, TB, 0, st>>>(d_ops, n, px, zx, ops2, orig2, ops64, orig64, zc);
+    CDCHK(hipGetLastError());
+    // ---- 2. / 3. the Z64 ops' writers and levels ----
+    const uint32_t gb64 = blocks(n64, TB);
+    uint32_t *kbuf[2] = {nullptr, nullptr}, *vbuf[2] = {nullptr, nullptr}, *seg_lo = nullptr, *seg_hi = nullptr, *wbx = nullptr;
+    int2* prod = nullptr;
+    int* glvl = nullptr;
+    int wsort = 0;
+    uint32_t levels64 = 0, n_wb64 = 0;
+    if (n64) {
+        for (int k = 0; k < 2; k++) kbuf[k] = S.get<uint32_t>(n64), vbuf[k] = S.get<uint32_t>(n64);
+        seg_lo = S.get<uint32_t>(W64);
+        seg_hi = S.get<uint32_t>(W64);
+        prod = S.get<int2>(n64);
+        uint32_t* uses = S.get<uint32_t>(n64 + 1);
+        uint32_t* rem = S.get<uint32_t>(n64);
+        uint32_t* cons_off = S.get<uint32_t>(n64 + 1);
+        uint32_t* cursor = S.get<uint32_t>(n64);
+        uint32_t* cons = S.get<uint32_t>(2 * n64);
+        glvl = S.get<int>(n64);
+        uint32_t* frontier = S.get<uint32_t>(n64);
+        const uint32_t max_rounds = (uint32_t)std::min<size_t>(n64 + 1, MAX_ROUNDS);
+        uint2* rounds = S.get<uint2>((size_t)max_rounds + 2);
+        CDNEED(kbuf[0] && kbuf[1] && vbuf[0] && vbuf[1] && seg_lo && seg_hi && prod && uses && rem && cons_off && cursor && cons && glvl && frontier && rounds);
+        k_z_wkeys<<<gb64, TB, 0, st>>>(ops64, n64, W64, kbuf[0], vbuf[0]);
+        CDCHK(hipGetLastError());
+        CDCHK(radix_sort(S, st, kbuf, vbuf, n64, bit_len(W64), &wsort));
+        CDCHK(hipMemsetAsync(seg_lo, 0, std::max<size_t>(W64, 1) * 4, st));
+        CDCHK(hipMemsetAsync(seg_hi, 0, std::max<size_t>(W64, 1) * 4, st));
+        CDCHK(hipMemsetAsync(uses, 0, (n64 + 1) * 4, st));
+        k_cd_segs<<<gb64, TB, 0, st>>>(kbuf[wsort], n64, W64, seg_lo, seg_hi);
+        k_cd_resolve<<<gb64, TB, 0, st>>>(ops64, n64, vbuf[wsort], seg_lo, seg_hi, chunk ? 1u : 0u, prod, uses, rem);
+        CDCHK(hipGetLastError());
+        CDCHK((scan_excl<uint32_t, SumU32>(S, st, uses, cons_off, n64 + 1, nullptr)));
+        CDCHK(hipMemsetAsync(cursor, 0, n64 * 4, st));
+        CDCHK(hipMemsetAsync(rounds, 0, ((size_t)max_rounds + 2) * sizeof(uint2), st));
+        k_cd_consumers<<<gb64, TB, 0, st>>>(prod, n64, cons_off, cursor, cons);
+        k_cd_front0<<<gb64, TB, 0, st>>>(rem, n64, frontier, rounds);
+        CDCHK(hipGetLastError());
+        uint32_t r = 0;
+        const RoundArgs ra{ops64, prod, uses, cons_off, cons, rem, nullptr, nullptr, glvl, nullptr, frontier, rounds};
+        const int rr = run_rounds(st, FORM_Z64, 0u, n64, max_rounds, ra, &r);
+        if (rr != RV_OK) return rr;
+        if (chunk) {
+            wbx = S.get<uint32_t>(W64);
+            CDNEED(wbx);
+            k_z_wb_flags<<<blocks(W64, TB), TB, 0, st>>>(seg_lo, seg_hi, W64, wbx);
+            CDCHK(hipGetLastError());
+            CDCHK((scan_excl<uint32_t, SumU32>(S, st, wbx, wbx, W64, d_small + 13)));
+        }
+    }
+    // the level sort's keys (the writer sort's values stay in vbuf[wsort] for the write-back gates; its other three buffers are free)
+    uint32_t *lk[2] = {nullptr, nullptr}, *lv[2] = {nullptr, nullptr};
+    if (n64) {
+        lk[0] = kbuf[wsort], lk[1] = kbuf[wsort ^ 1];
+        lv[0] = vbuf[wsort ^ 1], lv[1] = S.get<uint32_t>(n64);
+        CDNEED(lv[1]);
+        k_z_lkeys<<<gb64, TB, 0, st>>>(glvl, n64, lk[0], lv[0], d_small + 12);
+        CDCHK(hipGetLastError());
+        CDCHK(hipMemcpyAsync(h_small, d_small, sizeof h_small, hipMemcpyDeviceToHost, st));
+        CDCHK(hipStreamSynchronize(st));
+        levels64 = h_small[12] + 1;
+        n_wb64 = chunk ? h_small[13] : 0;
+    }
+    mark(1);
+    // ---- the GF(2) ops ----
+    const Mixed mx{orig2, n, levels64, n_wb64 != 0};
+    {
+        const int rc = compile_gf2_device(st, A, ops2, n2, z64_wires, gf2_wires, keep_wires, force_lazy_k, out, keep, laps, chunk, &mx);
+        if (rc != RV_OK) return rc;
+    }
+    Compiled& cc = out;
+    // (from here on a failure gives back what the GF(2) compile kept for the circuit)
+    struct KeepGuard {
+        const DevAlloc& A;
+        hipStream_t st;
+        DevCompileKeep* k;
+        bool ok = false;
+        ~KeepGuard() {
+            if (ok || !k) return;
+            (void)hipStreamSynchronize(st);
+            for (void* p : {(void*)k->d_gates, (void*)k->d_rec_rows, (void*)k->d_in_rows, (void*)k->d_gates64, (void*)k->d_rec_offs64, (void*)k->d_in_offs64})
+                if (p) A.release(A.self, p);
+            *k = DevCompileKeep();
+        }
+    } keep_guard{A, st, keep};
+    const uint32_t n_levels = (uint32_t)cc.level_start.size() - 1;
+    cc.level_start64.assign((size_t)n_levels + 1, 0);
+    if (n64) {
+        if (n_levels < levels64 + (n_wb64 ? 1u : 0u)) return RV_E_DEVICE;  // (cannot happen)
+        mark(2);
+        // ---- 4. the Z64 tables ----
+        const uint64_t n_rec64 = (uint64_t)tot.mul + tot.as, n_g64 = (uint64_t)n64 + n_wb64;
+        Gate64* gates64 = nullptr;
+        uint64_t *rec_offs = nullptr, *in_offs = nullptr;
+        {
+            void* p = nullptr;
+            if (A.alloc(A.self, n_g64 * sizeof(Gate64), &p) != RV_OK) return RV_E_NOMEM;
+            S.ps.push_back(p), gates64 = (Gate64*)p;
+            if (A.alloc(A.self, std::max<uint64_t>(n_rec64, 1) * 8, &p) != RV_OK) return RV_E_NOMEM;
+            S.ps.push_back(p), rec_offs = (uint64_t*)p;
+            if (A.alloc(A.self, std::max<size_t>(tot.in, 1) * 8, &p) != RV_OK) return RV_E_NOMEM;
+            S.ps.push_back(p), in_offs = (uint64_t*)p;
+        }
+        uint32_t* as_rec = S.get<uint32_t>(tot.as);
+        uint64_t* as_op = S.get<uint64_t>(tot.as);
+        uint32_t* pos = S.get<uint32_t>((size_t)n_levels + 1);
+        CDNEED(as_rec && as_op && pos);
+        if (n_wb64) k_z_wb_gates<<<blocks(W64, TB), TB, 0, st>>>(vbuf[wsort], seg_lo, seg_hi, wbx, W64, ops64, zc, s64, gates64 + n64);
+        int lsort = 0;
+        CDCHK(radix_sort(S, st, lk, lv, n64, bit_len(levels64), &lsort));
+        k_cd_bounds<<<blocks(n64 + 1, TB), TB, 0, st>>>(lk[lsort], n64, n_levels, pos);
+        k_z_gates<<<gb64, TB, 0, st>>>(lv[lsort], n64, ops64, prod, zc, orig64, s64, gates64, rec_offs, in_offs, as_rec, as_op);
+        CDCHK(hipGetLastError());
+        cc.gates64.resize(n_g64);
+        cc.rec_offs64.resize(n_rec64);
+        cc.in_offs64.resize(tot.in);
+        cc.assert_rec64.resize(tot.as);
+        cc.assert_op64.resize(tot.as);
+        auto d2h = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess; };
+        CDCHK(d2h(cc.gates64.data(), gates64, n_g64 * sizeof(Gate64)));
+        CDCHK(d2h(cc.rec_offs64.data(), rec_offs, n_rec64 * 8));
+        CDCHK(d2h(cc.in_offs64.data(), in_offs, (size_t)tot.in * 8));
+        CDCHK(d2h(cc.assert_rec64.data(), as_rec, (size_t)tot.as * 4));
+        CDCHK(d2h(cc.assert_op64.data(), as_op, (size_t)tot.as * 8));
+        CDCHK(d2h(cc.level_start64.data(), pos, ((size_t)n_levels + 1) * 4));
+        mark(3);
+        CDCHK(hipStreamSynchronize(st));
+        cc.level_start64[n_levels] = (uint32_t)n_g64;  // (the write-backs: the last level's, behind every op's gate)
+        const uint64_t randoms = (uint64_t)tot.m - tot.in - 2ull * tot.mul;
+        cc.n_ssa64 = (uint64_t)s64.ssa_base + n64 - tot.as;
+        cc.n_masks64 = n_masks64;
+        cc.on_words64 = s64.on0 + tot.in + 8 * n_rec64;
+        cc.pre_words64 = s64.pre0 + tot.mul;
+        cc.n_in64 = tot.in;
+        cc.n_rec64 = n_rec64;
+        cc.n_corr64 = tot.mul;
+        cc.n_user_random += randoms;
+        cc.info.z64_inputs = tot.in;
+        cc.info.z64_muls = tot.mul;
+        cc.info.z64_asserts = tot.as;
+        cc.info.z64_linear = (uint64_t)n64 - tot.in - tot.mul - tot.as + n_wb64;
+        cc.info.z64_masks = n_masks64;
+        if (laps) {
+            float a = 0, b = 0;
+            (void)hipEventElapsedTime(&a, ev[0], ev[1]);
+            (void)hipEventElapsedTime(&b, ev[2], ev[3]);
+            laps->z64 = a + b;
+        }
+        if (keep) {
+            keep->d_gates64 = gates64;
+            keep->d_rec_offs64 = rec_offs;
+            keep->d_in_offs64 = in_offs;
+            S.keep(gates64);
+            S.keep(rec_offs);
+            S.keep(in_offs);
+        }
+    }
+    keep_guard.ok = true;
+    return RV_OK;
+}
+}  // namespace
+
+int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, bool keep_wires,
+                       int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps, const ChunkStart* chunk, bool admit_z64) {
+    if (keep) *keep = DevCompileKeep();
+    if (admit_z64) return compile_mixed_device(st, A, d_ops, n_ops, z64_wires, gf2_wires, keep_wires, force_lazy_k, out, keep, laps, chunk);
+    return compile_gf2_device(st, A, d_ops, n_ops, z64_wires, gf2_wires, keep_wires, force_lazy_k, out, keep, laps, chunk, nullptr);
+}
 #undef CDCHK
 #undef CDNEED
-}
 
 }  // namespace rv

@@ -67,7 +67,7 @@ static int eval_stream_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wire
     E->gf2_wires = gf2_wires;
     E->B = batch;
     E->W = W;
-    E->compile_flags = ctx->compile_flags & RV_COMPILE_DEVICE;
+    E->compile_flags = ctx->compile_flags & RV_COMPILE_DEVICE_BITS;
     if (max_chunk_ops) E->max_chunk_ops = max_chunk_ops;
     int rc;
     E->rows_cap = std::max<size_t>(gf2_wires, 1);
@@ -95,7 +95,7 @@ extern "C" int rv_eval_stream_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wi
 }
 
 extern "C" int rv_eval_stream_set_compile_flags(rv_eval_stream* E, uint32_t flags) {
-    if (!E || (flags & ~RV_COMPILE_DEVICE) || E->fed) return RV_E_ARG;
+    if (!E || (flags & ~RV_COMPILE_DEVICE_BITS) || !device_bits_ok(flags) || E->fed) return RV_E_ARG;
     E->compile_flags = flags;
     return RV_OK;
 }
@@ -242,7 +242,6 @@ static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, bool ops_o
     // the pieces are compiled ahead on worker threads and run in order (piece_pipe.h)
     const unsigned n_threads = (unsigned)std::min<size_t>(eval_stream_threads(), n_pieces);
     std::vector<std::unique_ptr<Compiled>> pieces(n_pieces);
-    const bool device = (E->compile_flags & RV_COMPILE_DEVICE) != 0;
     const ChunkStart cs;  // (values do not depend on mask phases or transcript offsets)
     FeedOps fo(E->ctx, ops, ops_on_device && n_ops, cut);
     if (int rs = fo.load_sums(first_op, n_threads)) return E->sticky = rs;
@@ -251,8 +250,9 @@ static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, bool ops_o
         return h.rc() ? h.rc() : compile_ops(h.ops(), fo.len(i), E->z64_wires, E->gf2_wires, *pieces[i], &cs);
     };
     PiecePipe pipe(n_pieces, n_threads, RV_E_NOMEM, [&](size_t i) {
-        // (RV_COMPILE_DEVICE: an all-GF(2) piece stays empty here -- the main thread compiles it on the GPU right before it runs)
-        if (device && fo.all_gf2(i)) return (int)RV_OK;
+        // (RV_COMPILE_DEVICE: an all-GF(2) piece -- under RV_COMPILE_DEVICE_Z64 any piece without B2A -- stays empty here: the main
+        // thread compiles it on the GPU right before it runs)
+        if (fo.for_device(i, E->compile_flags)) return (int)RV_OK;
         pieces[i].reset(new Compiled());
         return compile_on_host(i);
     });
@@ -262,7 +262,7 @@ static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, bool ops_o
         if (!rc && !pieces[i]) {
             // (the piece comes back to the host whole: the chunk's arrays go up in one block with its witness, eval_stream_chunk)
             pieces[i].reset(new Compiled());
-            const int rd = fo.compile_on_device(i, E->z64_wires, E->gf2_wires, cs, *pieces[i], nullptr);
+            const int rd = fo.compile_on_device(i, E->z64_wires, E->gf2_wires, cs, *pieces[i], nullptr, nullptr, E->compile_flags);
             if (rd == RV_OK) g_stream_device_chunks.fetch_add(1, std::memory_order_relaxed);
             rc = rd == RV_COMPILE_FALLBACK ? compile_on_host(i) : rd;
         }

@@ -141,7 +141,7 @@ extern "C" int rv_prove_ops(rv_ctx* ctx, const rv_op* ops, size_t n_ops, const u
         // (under RV_COMPILE_DEVICE the prover's circuit is the device compiler's K = 1 form instead of the RV_COMPILE_WHOLE_PROVER
         // one: the proof bytes are the same, header.  The device compiler builds the lazy-sum form too; asking it for that here made
         // the cold call faster but not, measurably, the calls after it -- DESIGN.md 14.2)
-        const uint32_t fl = (ctx && (ctx->compile_flags & RV_COMPILE_DEVICE)) ? RV_COMPILE_DEVICE : RV_COMPILE_WHOLE_PROVER;
+        const uint32_t fl = (ctx && (ctx->compile_flags & RV_COMPILE_DEVICE)) ? (ctx->compile_flags & RV_COMPILE_DEVICE_BITS) : RV_COMPILE_WHOLE_PROVER;
         rc = ops_cache_get(ctx, ops, n_ops, z64_wires, gf2_wires, fl, &c, &hit, &owned);
     } catch (...) {
         g_last_error = "out of host memory";
@@ -165,7 +165,7 @@ extern "C" int rv_verify_ops(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t
     bool hit = false, owned = true;
     int rc;
     try {
-        rc = ops_cache_get(ctx, ops, n_ops, z64_wires, gf2_wires, ctx ? (ctx->compile_flags & RV_COMPILE_DEVICE) : 0u, &c, &hit, &owned);
+        rc = ops_cache_get(ctx, ops, n_ops, z64_wires, gf2_wires, ctx ? (ctx->compile_flags & RV_COMPILE_DEVICE_BITS) : 0u, &c, &hit, &owned);
     } catch (...) {
         g_last_error = "out of host memory";
         return RV_E_NOMEM;

@@ -1,6 +1,7 @@
 // What a streaming feed derives from the CONTENT of a piece, as sums over its ops (piece_sums.hip): the position-keyed digest
 // (stream.inc: ops_digest), the ShareGen::next() calls (compile.h: count_masks) and the transcript events (count_events) -- and how
-// many of its ops are not GF(2) (piece_all_gf2).  For a feed whose ops sit in device memory one kernel makes them for every piece in
+// many of its ops are not GF(2) (piece_all_gf2) or of no domain the device compiler takes under RV_COMPILE_DEVICE_Z64
+// (compile.h: ops_without_b2a).  For a feed whose ops sit in device memory one kernel makes them for every piece in
 // a single read of the ops; the host feeds keep their three loops.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,9 +16,10 @@ struct PieceSums {
     uint64_t masks2, masks64;   // count_masks
     uint64_t in2, rec2, pre2, on64, pre64;  // count_events
     uint64_t not_gf2;           // ops of another domain (0: piece_all_gf2)
+    uint64_t not_z64;           // ops that are neither GF(2), Z64 nor SizeHint: B2A, unknown domains (0: piece_no_b2a)
 };
-constexpr int PIECE_SUM_WORDS = 9;
-static_assert(sizeof(PieceSums) == PIECE_SUM_WORDS * 8, "PieceSums is nine packed words");
+constexpr int PIECE_SUM_WORDS = 10;
+static_assert(sizeof(PieceSums) == PIECE_SUM_WORDS * 8, "PieceSums is ten packed words");
 
 // Piece i of n_pieces = ops [d_cut[i], d_cut[i + 1]) of d_ops (d_cut: n_pieces + 1 non-decreasing offsets in device memory); the op
 // at offset j has stream position first_index + j.  Clears d_sums ([n_pieces] PieceSums) and adds every piece's sums into it, on `st`.

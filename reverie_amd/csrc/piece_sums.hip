@@ -2,7 +2,7 @@
 //
 // One thread per op with a stride loop over the piece (blockIdx.y = piece, blockIdx.x = the workgroups that share it).  An op is
 // three aligned 64-bit words; every rule below is the host loop's, bad opcodes and domains included (they count as whatever the host
-// comparisons make of them: the compiler reports the error, not this kernel).  The nine sums go through the wavefront (shuffles),
+// comparisons make of them: the compiler reports the error, not this kernel).  The ten sums go through the wavefront (shuffles),
 // the workgroup (LDS) and one 64-bit atomic add each per workgroup: integer sums, so the order of arrival does not matter.
 #include "piece_sums.h"
 
@@ -49,7 +49,10 @@ __global__ __launch_bounds__(TB) void k_piece_sums(const rv_op* __restrict__ ops
                 acc[2] += one ? 1 : (mul ? 2 : 0);
                 acc[6] += opcode == RV_OP_INPUT ? 1 : ((mul || az) ? 8 : 0);
                 acc[7] += mul;
-            } else if (domain == RV_DOM_B2A) {  // 64 fresh masks + 63 Mul, one Z64 mask
+            } else if (domain != RV_DOM_SIZEHINT) {
+                acc[9] += 1;
+            }
+            if (domain == RV_DOM_B2A) {  // 64 fresh masks + 63 Mul, one Z64 mask
                 acc[1] += 64 + 63 * 2;
                 acc[2] += 1;
                 acc[4] += 63 + 64;

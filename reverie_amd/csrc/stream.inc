@@ -179,7 +179,8 @@ struct rv_stream {
     static constexpr uint32_t R = RV_TOTAL_REPS, NQ = RV_TOTAL_REPS / 4;
     int pass = 1;
     int sticky = RV_OK;  // first error: the stream is dead afterwards
-    // rv_stream_set_compile_flags (the context's when the stream began): RV_COMPILE_DEVICE = every all-GF(2) piece is compiled by the
+    // rv_stream_set_compile_flags (the context's when the stream began): RV_COMPILE_DEVICE = every all-GF(2) piece (with
+    // RV_COMPILE_DEVICE_Z64: every piece without a B2A op) is compiled by the
     // chunk-mode device compiler, on the context's stream right before it runs; what that hands back is compiled on the host
     uint32_t compile_flags = 0;
     bool fed = false;  // a feed has begun: the flags are fixed
@@ -394,7 +395,7 @@ static int stream_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, co
     S->ctx = ctx;
     S->z64_wires = z64_wires;
     S->gf2_wires = gf2_wires;
-    S->compile_flags = ctx->compile_flags & RV_COMPILE_DEVICE;
+    S->compile_flags = ctx->compile_flags & RV_COMPILE_DEVICE_BITS;
     if (max_chunk_ops) S->max_chunk_ops = std::max<size_t>(max_chunk_ops, 1024);
     if (const char* e = getenv("RV_STREAM_KEEP_MB")) {
         S->keep_cap = (uint64_t)std::max(atoll(e), 0ll) << 20;
@@ -447,7 +448,7 @@ extern "C" int rv_stream_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, 
 }
 
 extern "C" int rv_stream_set_compile_flags(rv_stream* S, uint32_t flags) {
-    if (!S || (flags & ~RV_COMPILE_DEVICE) || S->fed) return RV_E_ARG;
+    if (!S || (flags & ~RV_COMPILE_DEVICE_BITS) || !device_bits_ok(flags) || S->fed) return RV_E_ARG;
     S->compile_flags = flags;
     for (rv_stream* m : S->bat) m->compile_flags = flags;  // (a batch: the feed's host-side state is its first running member's)
     return RV_OK;
@@ -1218,7 +1219,7 @@ struct FeedPiece {
     uint64_t digest = 0;
     ChunkStart carried;         // the offsets c's arrays hold
     bool kept = false;          // pass 2: pass 1 kept this piece's transcripts (rv_stream::Kept) -- nothing of it is uploaded
-    bool device = false;        // RV_COMPILE_DEVICE, all GF(2), not in pass 1's cache: c stays null until the main thread compiles it on the GPU
+    bool device = false;        // RV_COMPILE_DEVICE, all GF(2) (RV_COMPILE_DEVICE_Z64: no B2A), not in pass 1's cache: c stays null until the main thread compiles it on the GPU
 };
 
 // A piece ready to run: pass 1's cached compile if its digest matches the ops fed now, else a fresh compile -- at the offsets the piece
@@ -1233,7 +1234,7 @@ static int prepare_piece(const rv_stream* S, const FeedOps& fo, size_t i, uint64
     }
     p.digest = dg;
     // (a piece whose transcripts pass 1 kept is compiled on the host as ever: ChunkRun::plan decides whether it runs at all)
-    p.device = !p.c && !p.kept && (S->compile_flags & RV_COMPILE_DEVICE) && fo.all_gf2(i);
+    p.device = !p.c && !p.kept && fo.for_device(i, S->compile_flags);
     if (p.device) return RV_OK;
     if (!p.c) {
         p.carried = p.predicted ? p.want : ChunkStart();
@@ -1432,9 +1433,10 @@ static int stream_feed_impl(rv_stream* H, const rv_op* ops, bool ops_on_device, 
             c = new rv_circuit();
             c->ctx = S->ctx;
             DevCompileKeep kept;
-            const int rd = fo.compile_on_device(i, S->z64_wires, S->gf2_wires, at, c->cc, &kept, stats ? dev_laps : nullptr);
+            const int rd = fo.compile_on_device(i, S->z64_wires, S->gf2_wires, at, c->cc, &kept, stats ? dev_laps : nullptr, S->compile_flags);
             if (rd == RV_OK) {
                 c->d_gates = kept.d_gates, c->d_rec_rows = kept.d_rec_rows, c->d_in_rows = kept.d_in_rows;
+                c->d_gates64 = kept.d_gates64, c->d_rec_offs64 = kept.d_rec_offs64, c->d_in_offs64 = kept.d_in_offs64;
                 c->dev_compiled = true;
                 p.carried = at;
                 p.ph2 = at.mask_phase, p.ph64 = at.mask64_phase;

@@ -16,6 +16,8 @@ Device memory is bounded by the wire counts, one piece's working set and the pro
 Every class and one-shot function here takes `device_compile` (default False): the stream's all-GF(2) pieces are then compiled on the
 GPU (RV_COMPILE_DEVICE: rv_stream_set_compile_flags / rv_eval_stream_set_compile_flags) instead of on host worker threads; pieces with
 Z64, B2A or SizeHint ops, and pieces with an error in them, are still compiled on the host.  Proofs, answers and values are the same.
+With `device_z64=True` as well (RV_COMPILE_DEVICE_Z64; a ValueError without `device_compile`) Z64 and mixed pieces are compiled on the
+GPU too: only pieces with a B2A op or an error in them are left to the host.
 
 Wherever an op list is taken -- every `feed`, every one-shot function -- it may also be a torch tensor in GPU memory holding packed
 rv_op records (what `Circuit.from_device_ops` accepts; on the context's device, or it is an error).  The ops are then fed from where
@@ -50,22 +52,35 @@ def _feed(handle, ctx: Context, ops, g, n_g: int, z, n_z: int, entry: str = "rv_
     _lib.check(getattr(_lib.lib(), entry)(handle, _ptr(ops), C.c_size_t(len(ops)), _ptr(g), C.c_size_t(n_g), _ptr(z), C.c_size_t(n_z)))
 
 
-def _set_device_compile(handle, device_compile: bool, setter: str = "rv_stream_set_compile_flags"):
-    """a new stream follows its context's flags; device_compile=True asks for the device compiler whatever they are"""
+def _check_device_z64(device_compile: bool, device_z64: bool):
+    if device_z64 and not device_compile:
+        raise ValueError("device_z64=True needs device_compile=True")
+
+
+def _device_flags(device_compile: bool, device_z64: bool) -> int:
+    _check_device_z64(device_compile, device_z64)
+    return (_lib.RV_COMPILE_DEVICE if device_compile else 0) | (_lib.RV_COMPILE_DEVICE_Z64 if device_z64 else 0)
+
+
+def _set_device_compile(handle, device_compile: bool, device_z64: bool = False, setter: str = "rv_stream_set_compile_flags"):
+    """a new stream follows its context's flags; device_compile=True asks for the device compiler whatever they are (device_z64: for
+    Z64 and mixed pieces too)"""
     if device_compile:
-        _lib.check(getattr(_lib.lib(), setter)(handle, C.c_uint32(_lib.RV_COMPILE_DEVICE)))
+        _lib.check(getattr(_lib.lib(), setter)(handle, C.c_uint32(_device_flags(device_compile, device_z64))))
 
 
 @contextlib.contextmanager
-def _ctx_device_compile(ctx: Context, device_compile: bool):
-    """The one-shot calls of the library follow their context's compile flags, so device_compile=True sets RV_COMPILE_DEVICE on `ctx`
+def _ctx_device_compile(ctx: Context, device_compile: bool, device_z64: bool = False):
+    """The one-shot calls of the library follow their context's compile flags, so device_compile=True sets RV_COMPILE_DEVICE (and
+    device_z64=True RV_COMPILE_DEVICE_Z64) on `ctx`
     for the duration of the call and puts back what Context.set_compile_flags last set.  The context is shared state: another
     thread's cold rv_prove_ops / rv_verify_ops compiles on the same context meanwhile use the device compiler too (same results),
     and flags set through the C API behind Context's back are not seen here.  A caller who minds either sets the flag on the
     context once, or uses the Streaming* classes, whose flag lives on the stream handle."""
     before = getattr(ctx, "compile_flags", 0)
-    if device_compile and not before & _lib.RV_COMPILE_DEVICE:
-        ctx.set_compile_flags(before | _lib.RV_COMPILE_DEVICE)
+    want = before | _device_flags(device_compile, device_z64)
+    if want != before:
+        ctx.set_compile_flags(want)
         try:
             yield
         finally:
@@ -76,7 +91,8 @@ def _ctx_device_compile(ctx: Context, device_compile: bool):
 
 class StreamingProver:
     def __init__(self, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
-                 device_compile: bool = False):
+                 device_compile: bool = False, device_z64: bool = False):
+        _check_device_z64(device_compile, device_z64)
         self.ctx = ctx or Context.default()
         self.handle = C.c_void_p()
         s = None
@@ -85,7 +101,7 @@ class StreamingProver:
                                      else np.asarray(seeds, dtype=np.uint8)).reshape(TOTAL_REPS, 16)
         _lib.check(_lib.lib().rv_stream_begin(self.ctx.handle, C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])), _ptr(s),
                                               C.c_size_t(max_chunk_ops), C.byref(self.handle)))
-        _set_device_compile(self.handle, device_compile)
+        _set_device_compile(self.handle, device_compile, device_z64)
 
     def feed(self, ops, wit_gf2: Sequence[int] = (), wit_z64: Sequence[int] = ()):
         g = np.ascontiguousarray(np.asarray(wit_gf2, dtype=np.uint8))
@@ -127,12 +143,13 @@ class StreamingProver:
 
 
 def prove_streaming(ops, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
-                    ctx: Optional[Context] = None, device_compile: bool = False) -> Tuple[Proof, dict]:
+                    ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False) -> Tuple[Proof, dict]:
     """rv_prove_streaming: both passes over an op array in host memory -> (Proof, stream info).  A torch GPU tensor of ops: the same
     through rv_stream_begin / rv_stream_feed_device / rv_stream_finish."""
+    _check_device_z64(device_compile, device_z64)
     ctx = _ops_ctx(ops, ctx)
     if _is_device_ops(ops):
-        sp = StreamingProver(wire_counts, seeds, max_chunk_ops, ctx, device_compile)
+        sp = StreamingProver(wire_counts, seeds, max_chunk_ops, ctx, device_compile, device_z64)
         try:
             sp.same_cuts()  # (the same tensor, cut by the same rule in both passes)
             sp.feed(ops, wit_gf2, wit_z64)
@@ -149,7 +166,7 @@ def prove_streaming(ops, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=N
         s = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint8)).reshape(TOTAL_REPS, 16)
     out, n = C.c_void_p(), C.c_size_t()
     si = _lib.StreamInfo()
-    with _ctx_device_compile(ctx, device_compile):
+    with _ctx_device_compile(ctx, device_compile, device_z64):
         _lib.check(_lib.lib().rv_prove_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(int(wire_counts[0])),
                                                  C.c_size_t(int(wire_counts[1])), _ptr(g), C.c_size_t(len(g)), _ptr(z), C.c_size_t(len(z)), _ptr(s),
                                                  C.c_size_t(max_chunk_ops), C.byref(out), C.byref(n), C.byref(si)))
@@ -165,14 +182,15 @@ class StreamingVerifier:
     """
 
     def __init__(self, wire_counts: Tuple[int, int], proof, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
-                 device_compile: bool = False):
+                 device_compile: bool = False, device_z64: bool = False):
+        _check_device_z64(device_compile, device_z64)
         self.ctx = ctx or Context.default()
         self.handle = C.c_void_p()
         self._proof = proof if isinstance(proof, Proof) else Proof(bytes(proof))  # (kept alive: the stream reads it until finish)
         buf, n = self._proof._buffer()
         _lib.check(_lib.lib().rv_stream_verify_begin(self.ctx.handle, C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])), buf,
                                                      C.c_size_t(n), C.c_size_t(max_chunk_ops), C.byref(self.handle)))
-        _set_device_compile(self.handle, device_compile)
+        _set_device_compile(self.handle, device_compile, device_z64)
 
     def feed(self, ops):
         _feed(self.handle, self.ctx, ops, None, 0, None, 0)
@@ -193,12 +211,13 @@ class StreamingVerifier:
 
 
 def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = True, max_chunk_ops: int = 0,
-                     ctx: Optional[Context] = None, device_compile: bool = False) -> Tuple[bool, dict]:
+                     ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False) -> Tuple[bool, dict]:
     """rv_verify_streaming: one pass over an op array in host memory -> (ok, stream info).  A torch GPU tensor of ops: the same through
     rv_stream_verify_begin / rv_stream_feed_device / rv_stream_verify_finish."""
+    _check_device_z64(device_compile, device_z64)
     ctx = _ops_ctx(ops, ctx)
     if _is_device_ops(ops):
-        sv = StreamingVerifier(wire_counts, proof, max_chunk_ops, ctx, device_compile)
+        sv = StreamingVerifier(wire_counts, proof, max_chunk_ops, ctx, device_compile, device_z64)
         try:
             sv.feed(ops)
             return sv.finish(strict), sv.info
@@ -209,7 +228,7 @@ def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = Tr
     buf, n = pr._buffer()
     ok = C.c_int()
     si = _lib.StreamInfo()
-    with _ctx_device_compile(ctx, device_compile):
+    with _ctx_device_compile(ctx, device_compile, device_z64):
         _lib.check(_lib.lib().rv_verify_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])),
                                                   buf, C.c_size_t(n), C.c_uint32(0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT), C.c_size_t(max_chunk_ops),
                                                   C.byref(ok), C.byref(si)))
@@ -252,7 +271,8 @@ class StreamingBatchProver:
     """
 
     def __init__(self, wire_counts: Tuple[int, int], batch: int, seeds=None, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
-                 device_compile: bool = False):
+                 device_compile: bool = False, device_z64: bool = False):
+        _check_device_z64(device_compile, device_z64)
         self.ctx = ctx or Context.default()
         self.batch = int(batch)
         self.handle = C.c_void_p()
@@ -261,7 +281,7 @@ class StreamingBatchProver:
         s = _batch_seeds(seeds, self.batch)
         _lib.check(_lib.lib().rv_stream_begin_batch(self.ctx.handle, int(wire_counts[0]), int(wire_counts[1]), self.batch, _ptr(s),
                                                     int(max_chunk_ops), C.byref(self.handle)))
-        _set_device_compile(self.handle, device_compile)
+        _set_device_compile(self.handle, device_compile, device_z64)
 
     def feed(self, ops, wits_gf2=(), wits_z64=()):
         g = _eval_wits(wits_gf2, self.batch, np.uint8)
@@ -292,9 +312,10 @@ class StreamingBatchProver:
 
 
 def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
-                          ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False) -> "list[Proof]":
+                          ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False) -> "list[Proof]":
     """rv_prove_streaming_batch: both passes over an op array in host memory for the witnesses wits_gf2 [B][n] / wits_z64
     [B][m] (B from whichever of the two is 2-D; the other may be []); seeds [B][256][16] or None.  `info` (a dict, optional) receives the stream's figures."""
+    _check_device_z64(device_compile, device_z64)
     ctx = _ops_ctx(ops, ctx)
     g0 = np.asarray(wits_gf2, dtype=np.uint8)
     z0 = np.asarray(wits_z64, dtype=np.uint64)
@@ -305,7 +326,7 @@ def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int],
     else:
         raise ValueError("wits_gf2 or wits_z64 must be [batch][n]")
     if _is_device_ops(ops):  # (a torch GPU tensor: begin / rv_stream_feed_device twice / finish)
-        sp = StreamingBatchProver(wire_counts, batch, seeds, max_chunk_ops, ctx, device_compile)
+        sp = StreamingBatchProver(wire_counts, batch, seeds, max_chunk_ops, ctx, device_compile, device_z64)
         try:
             sp.same_cuts()
             sp.feed(ops, g0, z0)
@@ -324,7 +345,7 @@ def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int],
     outs = (C.c_void_p * batch)()
     lens = (C.c_size_t * batch)()
     si = _lib.StreamInfo()
-    with _ctx_device_compile(ctx, device_compile):
+    with _ctx_device_compile(ctx, device_compile, device_z64):
         _lib.check(_lib.lib().rv_prove_streaming_batch(ctx.handle, _ptr(ops), len(ops), int(wire_counts[0]), int(wire_counts[1]), batch, _ptr(g),
                                                        g.shape[1], _ptr(z), z.shape[1], _ptr(s), int(max_chunk_ops), outs, lens, C.byref(si)))
     if info is not None:
@@ -341,7 +362,8 @@ class StreamingBatchVerifier:
     """
 
     def __init__(self, wire_counts: Tuple[int, int], proofs, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
-                 device_compile: bool = False):
+                 device_compile: bool = False, device_z64: bool = False):
+        _check_device_z64(device_compile, device_z64)
         self.ctx = ctx or Context.default()
         self.handle = C.c_void_p()
         self.batch = len(proofs)
@@ -350,7 +372,7 @@ class StreamingBatchVerifier:
         self._keep, ptrs, lens = _proof_array(proofs)  # (kept alive: the stream reads them until finish)
         _lib.check(_lib.lib().rv_stream_verify_begin_batch(self.ctx.handle, int(wire_counts[0]), int(wire_counts[1]), self.batch, ptrs, lens,
                                                            int(max_chunk_ops), C.byref(self.handle)))
-        _set_device_compile(self.handle, device_compile)
+        _set_device_compile(self.handle, device_compile, device_z64)
 
     feed = StreamingVerifier.feed
 
@@ -370,14 +392,15 @@ class StreamingBatchVerifier:
 
 
 def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bool = True, max_chunk_ops: int = 0,
-                           ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False) -> "list[bool]":
+                           ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False) -> "list[bool]":
     """rv_verify_streaming_batch: one pass over an op array in host memory for every proof -> one bool per proof"""
+    _check_device_z64(device_compile, device_z64)
     ctx = _ops_ctx(ops, ctx)
     n = len(proofs)
     if n == 0:
         return []
     if _is_device_ops(ops):  # (a torch GPU tensor: begin / rv_stream_feed_device / finish)
-        sv = StreamingBatchVerifier(wire_counts, proofs, max_chunk_ops, ctx, device_compile)
+        sv = StreamingBatchVerifier(wire_counts, proofs, max_chunk_ops, ctx, device_compile, device_z64)
         try:
             sv.feed(ops)
             oks = sv.finish(strict)
@@ -390,7 +413,7 @@ def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bo
     keep, ptrs, lens = _proof_array(proofs)
     ok = (C.c_int * n)()
     si = _lib.StreamInfo()
-    with _ctx_device_compile(ctx, device_compile):
+    with _ctx_device_compile(ctx, device_compile, device_z64):
         _lib.check(_lib.lib().rv_verify_streaming_batch(ctx.handle, _ptr(ops), len(ops), int(wire_counts[0]), int(wire_counts[1]), n, ptrs, lens,
                                                         0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT, int(max_chunk_ops), ok, C.byref(si)))
     del keep
@@ -426,14 +449,15 @@ class StreamingEvaluator:
     Device memory is the wire store (wire counts x batch) plus one chunk of at most max_chunk_ops ops (0 = 2^18)."""
 
     def __init__(self, wire_counts: Tuple[int, int], batch: int = 1, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
-                 device_compile: bool = False):
+                 device_compile: bool = False, device_z64: bool = False):
+        _check_device_z64(device_compile, device_z64)
         self.ctx = ctx or Context.default()
         self.wire_counts = (int(wire_counts[0]), int(wire_counts[1]))
         self.batch = int(batch)
         self.handle = C.c_void_p()
         _lib.check(_lib.lib().rv_eval_stream_begin(self.ctx.handle, C.c_size_t(self.wire_counts[0]), C.c_size_t(self.wire_counts[1]),
                                                    C.c_size_t(self.batch), C.c_size_t(max_chunk_ops), C.byref(self.handle)))
-        _set_device_compile(self.handle, device_compile, "rv_eval_stream_set_compile_flags")
+        _set_device_compile(self.handle, device_compile, device_z64, "rv_eval_stream_set_compile_flags")
 
     def feed(self, ops, wits_gf2=(), wits_z64=()):
         g = _eval_wits(wits_gf2, self.batch, np.uint8)
@@ -467,15 +491,16 @@ class StreamingEvaluator:
 
 
 def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], max_chunk_ops: int = 0, values: bool = False,
-                       ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False) -> Evaluation:
+                       ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False) -> Evaluation:
     """rv_evaluate_streaming: one op array in host memory, evaluated chunk by chunk with bounded device memory.  wits_gf2 /
     wits_z64: [B][n] (1-D for one witness; the batch is len(wits_gf2)).  Returns the array-shaped Evaluation of
     Circuit.evaluate_batch; `info` (a dict, optional) receives the stream's figures."""
+    _check_device_z64(device_compile, device_z64)
     ctx = _ops_ctx(ops, ctx)
     g0 = np.asarray(wits_gf2, dtype=np.uint8)
     batch = g0.shape[0] if g0.ndim == 2 else 1
     if _is_device_ops(ops):  # (a torch GPU tensor: begin / rv_eval_stream_feed_device / finish)
-        se = StreamingEvaluator(wire_counts, batch, max_chunk_ops, ctx, device_compile)
+        se = StreamingEvaluator(wire_counts, batch, max_chunk_ops, ctx, device_compile, device_z64)
         try:
             se.feed(ops, g0, wits_z64)
             r = se.finish(values)
@@ -492,7 +517,7 @@ def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], ma
     gv = np.zeros((batch, wc[1]), np.uint8) if values else None
     zv = np.zeros((batch, wc[0]), np.uint64) if values else None
     si = _lib.EvalStreamInfo()
-    with _ctx_device_compile(ctx, device_compile):
+    with _ctx_device_compile(ctx, device_compile, device_z64):
         _lib.check(_lib.lib().rv_evaluate_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(wc[0]), C.c_size_t(wc[1]),
                                                     C.c_size_t(batch), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z), C.c_size_t(z.shape[1]),
                                                     C.c_size_t(max_chunk_ops), _ptr(gv), _ptr(zv), st.ctypes.data_as(C.c_void_p), C.byref(si)))

@@ -3,8 +3,10 @@
 HBM), the library's own compile_us / upload_us, the device compiler's per-phase laps (HIP events), and rv_prove_ops with and
 without the context flag: cold (the ops cache cleared before the call) and once more on the same ops (from the ops cache).
 Medians of `reps` runs after a warm-up, with [min, max] beside them.  --whole-prover: the same table with RV_COMPILE_WHOLE_PROVER
-on both compilers (the lazy-sum form).
-usage: python tools/compile_device_bench.py [--whole-prover] [reps]"""
+on both compilers (the lazy-sum form).  --compiler device-z64: instead config 5 (circuits.layered_z64) and a half-and-half mixture of
+configs 4 and 5 at about 10^6 ops each, host compile + upload against the device compile under RV_COMPILE_DEVICE |
+RV_COMPILE_DEVICE_Z64, with the laps (z64: the split of the list and the Z64 ops' steps; the others: the GF(2) ops').
+usage: python tools/compile_device_bench.py [--whole-prover] [--compiler device|device-z64] [reps]"""
 import ctypes as C
 import json
 import os
@@ -22,8 +24,13 @@ from reverie_amd import _lib  # noqa: E402
 
 L = _lib.lib()
 args = [a for a in sys.argv[1:] if a != "--whole-prover"]
+COMPILER = "device"
+if "--compiler" in args:
+    COMPILER = args[args.index("--compiler") + 1]
+    assert COMPILER in ("device", "device-z64"), COMPILER
+    del args[args.index("--compiler"):args.index("--compiler") + 2]
 WP = _lib.RV_COMPILE_WHOLE_PROVER if "--whole-prover" in sys.argv[1:] else 0
-DEV = _lib.RV_COMPILE_DEVICE
+DEV = _lib.RV_COMPILE_DEVICE | (_lib.RV_COMPILE_DEVICE_Z64 if COMPILER == "device-z64" else 0)
 reps = int(args[0]) if args else 3
 ctx = reverie_amd.Context(0)
 seeds = np.arange(4096, dtype=np.uint32).astype(np.uint8).reshape(256, 16)
@@ -61,6 +68,48 @@ def med(v):
     v = np.asarray(v, float)
     return [round(float(np.median(v)), 2), round(float(v.min()), 2), round(float(v.max()), 2)]
 
+
+def z64_rows():
+    """config 5 and the mixture: medians of `reps` cold compiles after one warm-up"""
+    p5, w5, wc5, _ = circuits.layered_z64(n_mul=500_000)
+    yield "config5", p5, wc5
+    p4, _, wc4, _ = circuits.layered_gf2(layers=max(1, len(p5) // 65536))
+    n = min(len(p4), len(p5))
+    mix = np.empty(2 * n, p5.dtype)  # alternating runs of 4096 ops of each (the domains share no wire)
+    run = 4096
+    a4 = a5 = at = 0
+    while at < 2 * n:
+        k = min(run, n - a4)
+        mix[at:at + k] = p4[a4:a4 + k]
+        at, a4 = at + k, a4 + k
+        k = min(run, n - a5)
+        mix[at:at + k] = p5[a5:a5 + k]
+        at, a5 = at + k, a5 + k
+    yield "mix_config4_config5", mix, (wc5[0], wc4[1])
+
+
+if COMPILER == "device-z64":
+    for name, prog, wc in z64_rows():
+        path, diff = C.c_int(), C.c_int()
+        assert L.rv_hook_compile_compare_device(ctx.handle, prog.ctypes.data_as(C.c_void_p), C.c_size_t(len(prog)), C.c_size_t(wc[0]),
+                                                C.c_size_t(wc[1]), C.c_uint32(WP | DEV), C.byref(path), C.byref(diff)) == 0
+        rec = {"ops": len(prog), "whole_prover": bool(WP), "device_path": path.value, "diff": diff.value, "host": [], "device": [], "laps_ms": []}
+        compile_ms(prog, wc, WP)
+        compile_ms(prog, wc, WP | DEV)
+        for _ in range(reps):
+            rec["host"].append(compile_ms(prog, wc, WP))
+            rec["device"].append(compile_ms(prog, wc, WP | DEV))
+            laps, z = (C.c_double * 6)(), C.c_double()
+            L.rv_hook_compile_device_laps(laps)
+            L.rv_hook_compile_device_laps_z64(C.byref(z))
+            rec["laps_ms"].append(dict(zip(("classify", "writers", "levels", "tables", "download", "rounds"), [round(x, 3) for x in laps]), z64=round(z.value, 3)))
+        for k in ("host", "device"):
+            v = np.array(rec[k])
+            rec[k + "_ms"] = {"wall": med(v[:, 0]), "compile": med(v[:, 1]), "upload": med(v[:, 2])}
+            del rec[k]
+        print(name, json.dumps(rec), flush=True)
+    ctx.close()
+    sys.exit(0)
 
 for name, p_and in (("config4", 0.5), ("all_and", 1.0)):
     prog, wit, wc, st = circuits.layered_gf2(p_and=p_and)

@@ -2,6 +2,7 @@
 
     python tools/stream_bench.py            # config 4 (recycled wire indices) and config 5
     python tools/stream_bench.py --compiler device            # the same with the pieces compiled on the GPU (RV_COMPILE_DEVICE)
+    python tools/stream_bench.py --compiler device-z64 --z64 [--runs 5]   # config 5 (Z64) at the chosen compiler, beside RV_STREAM_THREADS=1
     python tools/stream_bench.py --compare [--runs 5]         # config 4, host and device compiler side by side, one JSON line per row
     python tools/stream_bench.py --compiler device --ops device [--runs 5]   # config 4 fed from a GPU tensor (rv_stream_feed_device) beside
                                                               # the same calls fed from host memory, one JSON line per entry point
@@ -174,6 +175,31 @@ def device_ops_rows(ctx, seeds, want: bytes, runs: int = 5, chunk_ops: int = 1 <
         yield rec
 
 
+def z64_compiler_rows(ctx, seeds, runs=5, n_mul=1_000_000, chunk_ops=1 << 16):
+    """config 5 through prove_streaming at the context's compile flags, with the default worker threads and with RV_STREAM_THREADS=1:
+    medians of `runs` calls after a warm-up, the pieces the device compiler took per call, the proof against rv_prove's"""
+    import circuits
+    import reverie_amd
+    from reverie_amd import _lib
+    from reverie_amd.stream import prove_streaming
+
+    prog, w64, wc, st = circuits.layered_z64(n_mul=n_mul, recycle=True)
+    circ = reverie_amd.Circuit(prog, wc, ctx)
+    want = bytes(reverie_amd.Proof.new(circ, [], w64, seeds=seeds))
+    circ.close()
+    for env in ({}, {"RV_STREAM_THREADS": "1"}):
+        os.environ.update(env)
+        try:
+            before = int(_lib.lib().rv_hook_stream_device_chunks())
+            t, out = _timed(lambda: prove_streaming(prog, [], w64, wc, seeds=seeds, max_chunk_ops=chunk_ops, ctx=ctx), runs)
+            yield dict(t, row="prove_streaming config 5" + "".join(" %s=%s" % kv for kv in env.items()), n_ops=int(len(prog)), chunk_ops=chunk_ops,
+                       compile_flags=int(getattr(ctx, "compile_flags", 0)), ok=bytes(out[0]) == want,
+                       device_chunks_per_call=(int(_lib.lib().rv_hook_stream_device_chunks()) - before) // (runs + 1))
+        finally:
+            for k in env:
+                os.environ.pop(k, None)
+
+
 def z64_record(ctx, seeds, n_mul=1_000_000, chunk_ops=1 << 16):
     import circuits
     import reverie_amd
@@ -210,7 +236,9 @@ if __name__ == "__main__":
     import reverie_amd
 
     ap = argparse.ArgumentParser()
-    ap.add_argument("--compiler", default="host", choices=["host", "device"], help="where the streams' pieces are compiled (RV_COMPILE_DEVICE)")
+    ap.add_argument("--compiler", default="host", choices=["host", "device", "device-z64"],
+                    help="where the streams' pieces are compiled (device: RV_COMPILE_DEVICE; device-z64: with RV_COMPILE_DEVICE_Z64, Z64 and mixed pieces too)")
+    ap.add_argument("--z64", action="store_true", help="config 5 only: prove_streaming at the chosen compiler, default threads and RV_STREAM_THREADS=1")
     ap.add_argument("--compare", action="store_true", help="config 4 with both compilers, every streaming entry point")
     ap.add_argument("--ops", default="host", choices=["host", "device"],
                     help="device: config 4 fed from a GPU tensor beside the host-fed calls (prover, verifier, evaluator), one JSON line each")
@@ -218,11 +246,15 @@ if __name__ == "__main__":
     ap.add_argument("--bench-record", action="store_true")
     args = ap.parse_args()
     ctx = reverie_amd.Context(0)
-    if args.compiler == "device":  # (the one-shot calls follow the context's flags)
+    if args.compiler != "host":  # (the one-shot calls follow the context's flags)
         from reverie_amd import _lib
 
-        ctx.set_compile_flags(_lib.RV_COMPILE_DEVICE)
+        ctx.set_compile_flags(_lib.RV_COMPILE_DEVICE | (_lib.RV_COMPILE_DEVICE_Z64 if args.compiler == "device-z64" else 0))
     seeds = np.random.default_rng(0x5EED).integers(0, 256, (256, 16), dtype=np.uint8)
+    if args.z64:
+        for rec in z64_compiler_rows(ctx, seeds, runs=args.runs, n_mul=int(os.environ.get("Z64_MULS", "1000000"))):
+            print(json.dumps(rec), flush=True)
+        sys.exit(0)
     layers = int(os.environ.get("LAYERS", "153"))
     prog, wit, wc, st = circuits.layered_gf2(layers=layers)
     circ = reverie_amd.Circuit(prog, wc, ctx)
