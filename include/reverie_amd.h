@@ -168,13 +168,28 @@ int rv_circuit_compile_ex(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z6
  * a plain (not RV_COMPILE_WHOLE_PROVER) whole-program compile of a deep, narrow circuit that the host compiler recompiles with lazy
  * sums.  Without this bit every call decides as it did before the bit existed. */
 #define RV_COMPILE_DEVICE_Z64 8u /* with RV_COMPILE_DEVICE: the device compiler also takes Z64 ops and SizeHint ops that grow nothing */
+/* RV_COMPILE_DEVICE_B2A, only together with RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64 (RV_E_ARG otherwise, with a message that names
+ * the missing bit; rv_circuit_compile_device implies RV_COMPILE_DEVICE and still needs RV_COMPILE_DEVICE_Z64): the device compiler
+ * also takes B2A ops, the one op kind that joins the two domains, so programs that really use both compile on the GPU -- whole, in
+ * both gate-stream forms, or as a stream's pieces (every piece then goes to the device compiler, and a device feed copies none to the
+ * host).  A B2A op is expanded where the list is split by domain: its 442 GF(2) steps (64 fresh masks, the 63 Mul and 250 Xor of the
+ * ripple-carry adder, 64 recorded reconstructions) join the GF(2) ops in the host compiler's order, and its Gate64 sits one level
+ * above its deepest reconstruction.  The circuit is again the host compiler's field by field.  Still compiled on the host, with its
+ * error codes: RV_COMPILE_KEEP_WIRES, a SizeHint that grows a wire count, RV_LAZY_K, any op-list error (a B2A whose result wire or
+ * whose 64 source wires are out of range included), more than 2^16 dependency rounds in either domain, an expanded GF(2) list of
+ * 2^28 entries or more, and a plain (not RV_COMPILE_WHOLE_PROVER) whole-program compile of a deep, narrow circuit -- one adder is
+ * about 190 levels deep, so of the B2A programs only wide ones are final in the plain form; the lazy-sum form takes them all.
+ * The value is 32, not 16: 16 stays an unknown bit (RV_E_ARG, "unknown flag bits"), as callers and tests written against the
+ * previous flag set expect of the first bit above it.  Without this bit every call decides as it did before the bit existed. */
+#define RV_COMPILE_DEVICE_B2A 32u /* with RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64: the device compiler also takes B2A ops */
 /* The same for an op array already in device memory (n_ops packed 24-byte records on the context's device, e.g. a torch tensor);
  * the caller keeps ownership of d_ops and must have finished writing it.  A program the device path does not take is copied to the
  * host and compiled there. */
 int rv_circuit_compile_device(rv_ctx *ctx, const rv_op *d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                               rv_circuit **out);
-/* Compile flags of the context's own compiles (rv_prove_ops, rv_verify_ops); 0 (the default), RV_COMPILE_DEVICE or
- * RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64 (the cold compiles of Z64 and mixed programs on the device too).  Under
+/* Compile flags of the context's own compiles (rv_prove_ops, rv_verify_ops); 0 (the default), RV_COMPILE_DEVICE,
+ * RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64 (the cold compiles of Z64 and mixed programs on the device too) or
+ * RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64 | RV_COMPILE_DEVICE_B2A (those of programs with B2A ops too).  Under
  * RV_COMPILE_DEVICE rv_prove_ops compiles the plain form on the device instead of the RV_COMPILE_WHOLE_PROVER one: the same proof
  * bytes, a faster first proof of a wide circuit, 2-4 % slower proofs of it afterwards.  (The device compiler builds the
  * RV_COMPILE_WHOLE_PROVER form too -- rv_circuit_compile_ex with both flags --; rv_prove_ops does not ask it for that form,
@@ -312,8 +327,8 @@ typedef struct rv_eval_stream_info {
     uint64_t peak_chunk_bytes;  /* largest chunk's working set (rows, SSA slots, gate records, witness words) */
 } rv_eval_stream_info;
 int rv_eval_stream_begin(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, size_t batch, size_t max_chunk_ops, rv_eval_stream **out);
-/* As rv_stream_set_compile_flags (below): 0, RV_COMPILE_DEVICE or RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64, before the first feed;
- * the context's flags are the default. */
+/* As rv_stream_set_compile_flags (below): 0, RV_COMPILE_DEVICE, RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64 or the latter with
+ * RV_COMPILE_DEVICE_B2A, before the first feed; the context's flags are the default. */
 int rv_eval_stream_set_compile_flags(rv_eval_stream *s, uint32_t flags);
 int rv_eval_stream_feed(rv_eval_stream *s, const rv_op *ops, size_t n_ops, const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64,
                         size_t n_z64);
@@ -382,7 +397,9 @@ int rv_stream_begin(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, const uint8
  * on the host, with the host compiler's result or error code.  RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64 = the same for every piece
  * without a B2A op: Z64 and mixed pieces are compiled on the GPU too and their Z64 records stay in device memory like the GF(2) ones;
  * handed back are B2A pieces, op-list errors (a SizeHint that grows a wire count is one in a stream) and chains deeper than 2^16
- * rounds.  The proofs, answers and values are the same bytes either way.  On a
+ * rounds.  RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64 | RV_COMPILE_DEVICE_B2A = every piece goes to the device compiler, B2A
+ * pieces too; handed back are op-list errors and chains deeper than 2^16 rounds.  The proofs, answers and values are the same bytes
+ * either way.  On a
  * batch handle (rv_stream_begin_batch, rv_stream_verify_begin_batch) it holds for the whole batch.  RV_E_ARG: NULL handle, any other
  * bit, or a call after the first feed. */
 int rv_stream_set_compile_flags(rv_stream *s, uint32_t flags);
@@ -397,7 +414,7 @@ int rv_stream_feed(rv_stream *s, const rv_op *ops, size_t n_ops, const uint8_t *
  * host: one kernel makes each piece's digest and mask / event counts where the ops are; under RV_COMPILE_DEVICE an all-GF(2) piece
  * is compiled from d_ops in place, and only a piece the host compiler has to read (no RV_COMPILE_DEVICE, Z64 / B2A / SizeHint ops,
  * an op-list error, more than 2^16 rounds; with RV_COMPILE_DEVICE_Z64 a Z64 or mixed piece is compiled in place too, and of these
- * only B2A pieces, errors and over-deep chains remain) is copied down, into one of a fixed number of page-locked slots: one per compiling
+ * only B2A pieces, errors and over-deep chains remain; with RV_COMPILE_DEVICE_B2A on top only errors and over-deep chains) is copied down, into one of a fixed number of page-locked slots: one per compiling
  * thread plus one, each as long as the feed's longest piece, at most 32 and within 512 MiB (two at least).  The slots belong to the
  * context and stay allocated for its next device feed until rv_ctx_destroy.  Returns when the library no longer reads d_ops. */
 int rv_stream_feed_device(rv_stream *s, const rv_op *d_ops, size_t n_ops, const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64,
@@ -704,7 +721,8 @@ int rv_hook_compile_compare(const rv_op *ops, size_t n_ops, size_t z64_wires, si
  * The hook tries the device whether or not RV_COMPILE_DEVICE is set, except that RV_COMPILE_WHOLE_PROVER without the device bit stays
  * a host compile (*path = 0): with RV_COMPILE_WHOLE_PROVER | RV_COMPILE_DEVICE it tries the device compiler on the lazy-sum form and
  * compares with the host compiler's forced lazy-sum compile.  RV_COMPILE_DEVICE_Z64 (with RV_COMPILE_DEVICE, else RV_E_ARG) lets the
- * device side take Z64 and mixed programs; every other flag value behaves as before.  Returns the host compiler's status. */
+ * device side take Z64 and mixed programs, RV_COMPILE_DEVICE_B2A (with both, else RV_E_ARG) programs with B2A ops; every other flag
+ * value behaves as before.  Returns the host compiler's status. */
 int rv_hook_compile_compare_device(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, int *path,
                                    int *diff);
 /* The same for one piece of a stream: both sides compile the ops as the streaming chunk that starts at `start` = { mask_phase (< 128),
@@ -712,7 +730,8 @@ int rv_hook_compile_compare_device(rv_ctx *ctx, const rv_op *ops, size_t n_ops, 
  * piece's own).  *path, *diff and the return value as rv_hook_compile_compare_device. */
 int rv_hook_compile_compare_device_chunk(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const uint64_t start[6], int *path, int *diff);
 /* The same with the stream's compile flags: 0 and RV_COMPILE_DEVICE are the hook above (GF(2) pieces only); RV_COMPILE_DEVICE |
- * RV_COMPILE_DEVICE_Z64 lets the device side take Z64 and mixed pieces.  RV_E_ARG for any other value. */
+ * RV_COMPILE_DEVICE_Z64 lets the device side take Z64 and mixed pieces, RV_COMPILE_DEVICE_B2A beside both pieces with B2A ops.
+ * RV_E_ARG for any other value. */
 int rv_hook_compile_compare_device_chunk_ex(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const uint64_t start[6],
                                             uint32_t flags, int *path, int *diff);
 /* Pieces of this process's streams (rv_stream_*, rv_eval_stream_* and the one-shot calls over them) that the device path compiled so
@@ -731,7 +750,8 @@ int rv_hook_stream_piece_sums(rv_ctx *ctx, const rv_op *ops, size_t n_ops, uint6
  * lists, [2] values and levels (topological rounds), [3] rows, sort and tables, [4] the host's copy; out[5] = rounds launched. */
 int rv_hook_compile_device_laps(double out[6]);
 /* RV_COMPILE_DEVICE_Z64, a list with Z64 ops: ms of the split of the list and of the Z64 ops' steps in that compile (0 otherwise);
- * the six figures above are then the GF(2) ops'. */
+ * the six figures above are then the GF(2) ops' (RV_COMPILE_DEVICE_B2A: the expansion of the B2A ops is part of the split, their
+ * 442 steps each are among the GF(2) ops). */
 int rv_hook_compile_device_laps_z64(double *out);
 /* DomainGF2::reconstruct (gf2/domain.rs:47-63) on n packed u64 shares (bit 63 - (8*rep + player)) -> n ReconGF2 words
  * (one 0x00/0xFF byte per repetition), through the interpreter's own device function */

@@ -88,7 +88,7 @@ def evaluate_gpu(prog, wc, witness):
         raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (r.first_failed_op, r.n_failed))
 
 
-def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, device_compile=False, device_z64=False):
+def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, device_compile=False, device_z64=False, device_b2a=False):
     """`oneshot --evaluator stream`: the program evaluated in pieces with bounded device memory (rv_eval_stream_*), on the GPU like
     --evaluator gpu and with the same outcome.  An rvops file is read through a memory map, piece by piece; its wire counts come from
     one pass over the mapping."""
@@ -115,7 +115,8 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
             z64, gf2 = max(z64, z), max(gf2, g)
         wc = (z64, gf2)
         pieces = (np.asarray(prog[at:at + step]) for at in range(0, n, step))
-    se = StreamingEvaluator(wc, 1, max_chunk_ops, device_compile=device_compile, **({"device_z64": True} if device_z64 else {}))
+    se = StreamingEvaluator(wc, 1, max_chunk_ops, device_compile=device_compile, **({"device_z64": True} if device_z64 else {}),
+                            **({"device_b2a": True} if device_b2a else {}))
     try:
         used = 0
         for piece in pieces:
@@ -156,10 +157,11 @@ def build_parser():
                          "and one chunk (an rvops file is read piece by piece)" % GPU_EVAL_MIN_OPS)
     ap.add_argument("--max-chunk-ops", type=int, default=0,
                     help="oneshot --evaluator stream: ops per device chunk (0 = the library's default, 2^18)")
-    ap.add_argument("--compiler", default="host", choices=["host", "device", "device-z64"],
+    ap.add_argument("--compiler", default="host", choices=["host", "device", "device-z64", "device-b2a"],
                     help="prove / verify / oneshot-zk and oneshot --evaluator stream: compile the program (the stream's pieces) on the host "
                          "(default) or on the GPU (device = RV_COMPILE_DEVICE: GF(2) programs; device-z64 = with RV_COMPILE_DEVICE_Z64: Z64 and "
-                         "mixed programs too; B2A ops, a SizeHint that grows a wire count, op-list errors, chains deeper than 2^16 rounds and "
+                         "mixed programs too; device-b2a = with RV_COMPILE_DEVICE_B2A as well: programs with B2A ops too; without it B2A ops, and "
+                         "always a SizeHint that grows a wire count, op-list errors, chains deeper than 2^16 rounds and "
                          "the deep, narrow circuits the host compiler recompiles with lazy sums still compile on the host); the proof bytes "
                          "and the outcome are the same")
     ap.add_argument("--reference-compat", action="store_true",
@@ -185,7 +187,8 @@ def main(argv=None) -> int:
     if a.operation == "oneshot" and a.evaluator == "stream":
         print("Evaluating program in cleartext")
         evaluate_stream(a.program_path, a.program_format, a.expected_outputs_path, parse_witness(open(a.witness_path, "rb").read()),
-                        a.max_chunk_ops, device_compile=a.compiler != "host", **({"device_z64": True} if a.compiler == "device-z64" else {}))
+                        a.max_chunk_ops, device_compile=a.compiler != "host", **({"device_z64": True} if a.compiler in ("device-z64", "device-b2a") else {}),
+                        **({"device_b2a": True} if a.compiler == "device-b2a" else {}))
         print("()")
         return 0
     prog, wc = load_program(a.program_path, a.program_format, a.expected_outputs_path)
@@ -200,7 +203,7 @@ def main(argv=None) -> int:
         return 0
     from .proof import Circuit, Proof
 
-    circuit = Circuit(prog, wc, device_compile=a.compiler != "host", device_z64=a.compiler == "device-z64")
+    circuit = Circuit(prog, wc, device_compile=a.compiler != "host", device_z64=a.compiler in ("device-z64", "device-b2a"), device_b2a=a.compiler == "device-b2a")
     if a.operation in ("prove", "oneshot-zk"):
         wit = parse_witness(open(a.witness_path, "rb").read())
         print("Evaluating program in ~zero knowledge~")

@@ -137,6 +137,7 @@ RV_COMPILE_WHOLE_PROVER = 1
 RV_COMPILE_KEEP_WIRES = 2  # the circuit keeps every wire's final value form: rv_evaluate can return wire values
 RV_COMPILE_DEVICE = 4  # compiled on the GPU (GF(2) programs, plain or -- with WHOLE_PROVER -- lazy sums; anything else by the host compiler): the same circuit
 RV_COMPILE_DEVICE_Z64 = 8  # with RV_COMPILE_DEVICE: Z64 ops and SizeHint ops that grow nothing compile on the GPU too (B2A still on the host)
+RV_COMPILE_DEVICE_B2A = 32  # with both bits above: B2A ops compile on the GPU too (16 stays an unknown bit)
 RV_VERIFY_REFERENCE_COMPAT = 2  # the reference verifier's two unchecked conditions stay unchecked
 
 _lib = None

@@ -766,9 +766,32 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
                                   rv_circuit** out, const rv_op* d_ops = nullptr);
 static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged = false);
 
-// the two bits that choose the compiler: RV_COMPILE_DEVICE_Z64 widens RV_COMPILE_DEVICE's scope and means nothing without it
-constexpr uint32_t RV_COMPILE_DEVICE_BITS = RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64;
-static bool device_bits_ok(uint32_t flags) { return !(flags & RV_COMPILE_DEVICE_Z64) || (flags & RV_COMPILE_DEVICE); }
+// the three bits that choose the compiler: RV_COMPILE_DEVICE_Z64 widens RV_COMPILE_DEVICE's scope and means nothing without it,
+// RV_COMPILE_DEVICE_B2A widens RV_COMPILE_DEVICE_Z64's in the same way
+constexpr uint32_t RV_COMPILE_DEVICE_BITS = RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64 | RV_COMPILE_DEVICE_B2A;
+// nullptr when the bits go together, else what is missing
+static const char* device_bits_missing(uint32_t flags) {
+    if ((flags & RV_COMPILE_DEVICE_B2A) && (flags & (RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64)) != (RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64)) {
+        if (flags & RV_COMPILE_DEVICE) return "the flag RV_COMPILE_DEVICE_B2A needs RV_COMPILE_DEVICE_Z64";
+        if (flags & RV_COMPILE_DEVICE_Z64) return "the flag RV_COMPILE_DEVICE_B2A needs RV_COMPILE_DEVICE";
+        return "the flag RV_COMPILE_DEVICE_B2A needs RV_COMPILE_DEVICE and RV_COMPILE_DEVICE_Z64";
+    }
+    if ((flags & RV_COMPILE_DEVICE_Z64) && !(flags & RV_COMPILE_DEVICE)) return "the flag RV_COMPILE_DEVICE_Z64 needs RV_COMPILE_DEVICE";
+    return nullptr;
+}
+static bool device_bits_ok(uint32_t flags) { return device_bits_missing(flags) == nullptr; }
+// the device bits of a set_compile_flags call: RV_OK, or RV_E_ARG with the call's own message
+static int check_device_flags(const char* who, uint32_t flags) {
+    if (flags & ~RV_COMPILE_DEVICE_BITS) {
+        g_last_error = std::string(who) + ": unknown flag bits";
+        return RV_E_ARG;
+    }
+    if (const char* m = device_bits_missing(flags)) {
+        g_last_error = std::string(who) + ": " + m;
+        return RV_E_ARG;
+    }
+    return RV_OK;
+}
 
 extern "C" int rv_circuit_compile_ex(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                                      rv_circuit** out) {
@@ -776,8 +799,8 @@ extern "C" int rv_circuit_compile_ex(rv_ctx* ctx, const rv_op* ops, size_t n_ops
         g_last_error = "rv_circuit_compile_ex: unknown flag bits";
         return RV_E_ARG;
     }
-    if (!device_bits_ok(flags)) {
-        g_last_error = "rv_circuit_compile_ex: the flag RV_COMPILE_DEVICE_Z64 needs RV_COMPILE_DEVICE";
+    if (const char* m = device_bits_missing(flags)) {
+        g_last_error = std::string("rv_circuit_compile_ex: ") + m;
         return RV_E_ARG;
     }
     try {  // no C++ exception may cross the C boundary
@@ -814,7 +837,7 @@ static int compile_on_device(rv_ctx* ctx, const rv_op* d_ops, size_t n_ops, size
     const int k = ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0;
     DevCompileLaps laps;
     const int rc = compile_ops_device(ctx->stream, ctx_dev_allocator(ctx), d_ops, n_ops, z64_wires, gf2_wires, (flags & RV_COMPILE_KEEP_WIRES) != 0, k,
-                                      cc, keep, &laps, nullptr, (flags & RV_COMPILE_DEVICE_Z64) != 0);
+                                      cc, keep, &laps, nullptr, (flags & RV_COMPILE_DEVICE_Z64) != 0, (flags & RV_COMPILE_DEVICE_B2A) != 0);
     if (rc == RV_E_DEVICE) g_last_error = "device compile: HIP error";
     if (rc == RV_E_NOMEM) g_last_error = "device compile: out of device memory";
     if (rc == RV_OK) {
@@ -855,7 +878,7 @@ static std::atomic<uint64_t> g_op_bytes_h2d{0}, g_op_bytes_d2h{0};  // op bytes 
 // up_bytes (the feeds: &g_op_bytes_h2d): receives the bytes of an upload.
 static int compile_chunk_on_device(rv_ctx* ctx, const rv_op* ops, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires,
                                    const ChunkStart& cs, Compiled& cc, DevCompileKeep* keep, double laps[3] = nullptr,
-                                   std::atomic<uint64_t>* up_bytes = nullptr, bool admit_z64 = false) {
+                                   std::atomic<uint64_t>* up_bytes = nullptr, uint32_t compile_flags = 0) {
     if (getenv("RV_LAZY_K")) return RV_COMPILE_FALLBACK;
     const auto t0 = std::chrono::steady_clock::now();
     rv_op* up = nullptr;
@@ -865,7 +888,7 @@ static int compile_chunk_on_device(rv_ctx* ctx, const rv_op* ops, const rv_op* d
     const auto t1 = std::chrono::steady_clock::now();
     DevCompileLaps dl;
     rc = compile_ops_device(ctx->stream, ctx_dev_allocator(ctx), d_ops ? d_ops : up, n_ops, z64_wires, gf2_wires, false, 0, cc, keep, laps ? &dl : nullptr,
-                            &cs, admit_z64);
+                            &cs, (compile_flags & RV_COMPILE_DEVICE_Z64) != 0, (compile_flags & RV_COMPILE_DEVICE_B2A) != 0);
     ctx->release(up);  // (the device compile synchronised the stream)
     if (rc == RV_E_DEVICE) g_last_error = "device compile of a stream's piece: HIP error";
     if (rc == RV_E_NOMEM) g_last_error = "device compile of a stream's piece: out of device memory";
@@ -1319,8 +1342,12 @@ extern "C" int rv_hook_compile_compare(const rv_op* ops, size_t n_ops, size_t z6
 
 extern "C" int rv_circuit_compile_device(rv_ctx* ctx, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                                          rv_circuit** out) {
-    // (the call implies RV_COMPILE_DEVICE: RV_COMPILE_DEVICE_Z64 needs no other bit here)
+    // (the call implies RV_COMPILE_DEVICE: RV_COMPILE_DEVICE_Z64 needs no other bit here, RV_COMPILE_DEVICE_B2A needs that one)
     if (!ctx || !out || (n_ops && !d_ops) || (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE_BITS))) return RV_E_ARG;
+    if (const char* m = device_bits_missing(flags | RV_COMPILE_DEVICE)) {
+        g_last_error = std::string("rv_circuit_compile_device: ") + m;
+        return RV_E_ARG;
+    }
     try {
         return rv_circuit_compile_impl(ctx, nullptr, n_ops, z64_wires, gf2_wires, flags | RV_COMPILE_DEVICE, out, d_ops);
     } catch (...) {
@@ -1330,7 +1357,8 @@ extern "C" int rv_circuit_compile_device(rv_ctx* ctx, const rv_op* d_ops, size_t
 }
 
 extern "C" int rv_ctx_set_compile_flags(rv_ctx* ctx, uint32_t flags) {
-    if (!ctx || (flags & ~RV_COMPILE_DEVICE_BITS) || !device_bits_ok(flags)) return RV_E_ARG;
+    if (int rc = check_device_flags("rv_ctx_set_compile_flags", flags)) return rc;
+    if (!ctx) return RV_E_ARG;
     ctx->compile_flags = flags;
     return RV_OK;
 }
@@ -1381,7 +1409,7 @@ extern "C" int rv_hook_compile_compare_device_chunk_ex(rv_ctx* ctx, const rv_op*
         const int rc = compile_ops_seq(ops, n_ops, z64_wires, gf2_wires, a, &cs);
         HIPCHK(hipSetDevice(ctx->device));
         const int rd = compile_chunk_on_device(ctx, ops, nullptr, n_ops, z64_wires, gf2_wires, cs, b, nullptr, nullptr, nullptr,
-                                               (flags & RV_COMPILE_DEVICE_Z64) != 0);
+                                               flags);
         if (rd == RV_OK) {
             *path = 1;
             *diff = rc == RV_OK ? compiled_diff(a, b) : 100;  // (the device path compiled a piece the host compiler rejects)

@@ -128,7 +128,7 @@ struct StreamEvents {
 void count_events(const rv_op* ops, size_t n_ops, StreamEvents* ev);
 // RV_COMPILE_DEVICE_Z64: true when every op is a GF(2), Z64 or SizeHint op -- the pieces of a stream that go to the device compiler
 // (a SizeHint that grows a wire count is an error in a chunk: the device compiler hands such a piece back and the host compiler
-// reports it)
+// reports it).  With RV_COMPILE_DEVICE_B2A every piece goes there and this is not asked.
 bool ops_without_b2a(const rv_op* ops, size_t n_ops);
 // A chunk compiled with zero transcript offsets, moved behind `on0` / `pre0` carried transcript rows and `on_words64_0` /
 // `pre_words64_0` carried Z64 words (they enter the compiled stream only as additive offsets)

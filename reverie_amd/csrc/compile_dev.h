@@ -12,6 +12,22 @@
 // levels).  Still RV_COMPILE_FALLBACK: a B2A op, a SizeHint that grows a wire count, RV_COMPILE_KEEP_WIRES, RV_LAZY_K, an op-list
 // error in either domain, more than 2^16 rounds in either domain, and a plain whole-program compile for which lazy_forms_pay holds.
 //
+// admit_b2a (RV_COMPILE_DEVICE_B2A; with admit_z64 only): the list may also hold B2A ops, whole or as a chunk, in either form.  Where
+// the list is split by domain a B2A contributes its 442 SSA-producing steps to the GF(2) list as private ops, in Builder::g_* call
+// order (run_pass, case RV_DOM_B2A: 64 Random, Mul and Xor, 62 x {Xor, Xor, Mul, Xor, Xor}, two Xor, 64 reconstructions), and one op
+// to the Z64 list.  The private ops write no wire; their operands inside the expansion are fixed places, and only the 64 reads of
+// the source wires go through the last-writer search.  A reconstruction is an AssertZero with a value: a computed row of its own,
+// counted in n_random_or_recon and absent from the AssertZero tables.  The Gate64 sits one level above its deepest reconstruction:
+// the Z64 ops' levels are made once the GF(2) ops have theirs.  RV_COMPILE_FALLBACK, each the host compiler's to compile or report:
+//   - RV_COMPILE_KEEP_WIRES (the wire forms are not built here);
+//   - a SizeHint that grows a wire count (the wire tables are sized once);
+//   - RV_LAZY_K in the environment, or any forced lazy_k other than RV_LIN_K (forms the device does not build);
+//   - any op-list error, a B2A's among them: dst >= z64_wires, src + 64 > gf2_wires (also when src + 64 wraps), reserved != 0;
+//   - more than 2^16 rounds in either domain (one adder takes about 190);
+//   - a plain whole-program compile for which lazy_forms_pay holds -- B2A programs are deep, so of them only wide ones (some 100
+//     adders side by side) are final at K = 1; the lazy-sum form takes them all;
+//   - an expanded GF(2) list of 2^28 entries or more.
+//
 // Chunk mode (`chunk` not null): one piece of a stream, identical to compile_ops_seq(..., chunk) -- the wires start in their carried
 // rows, the counters at the ChunkStart's, no sum is dropped as unread, and one more level writes every wire the piece wrote back to
 // its carried row.  A chunk is final at K = 1 whatever its shape (lazy_forms_pay does not apply; a forced lazy_k is a fallback); an
@@ -53,6 +69,6 @@ struct DevCompileKeep {
 // RV_E_DEVICE.  d_ops: n_ops packed rv_op records in device memory (read only).  Runs on `st`; synchronises it before returning.
 int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires,
                        bool keep_wires, int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps = nullptr,
-                       const ChunkStart* chunk = nullptr, bool admit_z64 = false);
+                       const ChunkStart* chunk = nullptr, bool admit_z64 = false, bool admit_b2a = false);
 
 }  // namespace rv

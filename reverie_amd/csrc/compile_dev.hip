@@ -1,6 +1,6 @@
 // see compile_dev.h
 //
-// (Z64 ops and mixed lists, RV_COMPILE_DEVICE_Z64: compile_mixed_device, at the end of this file.)
+// (Z64 ops and mixed lists, RV_COMPILE_DEVICE_Z64, and B2A ops, RV_COMPILE_DEVICE_B2A: compile_mixed_device, at the end of this file.)
 // The device compile of a whole GF(2) program at K = 1 (every XOR of two distinct rows materialised; the lazy-sum form's differences are
 // with its kernels: value_lazy, and the LAZY instantiations of steps 3 and 5), in the steps of the host
 // compiler (compile.cpp: run_pass, Builder, the (level, class) sort and the pipelining tables):
@@ -29,6 +29,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <vector>
 
 namespace rv {
@@ -185,6 +186,14 @@ __global__ __launch_bounds__(TB) void k_rs_scatter(const uint32_t* kin, const ui
 }
 
 // ---- the op list ----
+// The private ops of a B2A expansion (RV_COMPILE_DEVICE_B2A; k_z_expand writes them into the GF(2) list of a mixed compile, nobody
+// else may): GF(2) records whose `reserved` word says PS_OP = writes no wire (sort key W), PS_A / PS_B = operand a / b names its
+// producer by its place in the list instead of a wire.  A PS_OP AssertZero is Builder::g_reveal(recon = true): the gate is a G_RECON
+// and has a value, a fresh computed row.
+constexpr uint16_t PS_OP = 1, PS_A = 2, PS_B = 4;
+constexpr uint32_t B2A_STEPS = 442, B2A_RECON0 = 378;  // SSA-producing steps of one B2A (run_pass); its first reconstruction
+constexpr uint8_t ZOP_B2A = RV_OP_CONST + 1;           // the B2A's record in the Z64 list (a = its expansion's place in the GF(2) list)
+__device__ inline bool is_recon(const rv_op& op) { return op.opcode == RV_OP_ASSERTZERO && (op.reserved & PS_OP); }
 __device__ inline bool op_writes(uint32_t opc) { return opc != RV_OP_ASSERTZERO; }
 __device__ inline int op_reads(uint32_t opc) {
     switch (opc) {
@@ -195,16 +204,18 @@ __device__ inline int op_reads(uint32_t opc) {
 }
 
 // step 1: validation, counters, the wire sort's keys (a wire; W for ops that write none: they sort behind every wire)
-__global__ __launch_bounds__(TB) void k_cd_classify(const rv_op* ops, size_t n, uint32_t W, C4* cnt, uint32_t* keys, uint32_t* vals, uint32_t* flag) {
+// (pseudo: the list is a mixed compile's own and may hold the private ops of B2A expansions)
+__global__ __launch_bounds__(TB) void k_cd_classify(const rv_op* ops, size_t n, uint32_t W, uint32_t pseudo, C4* cnt, uint32_t* keys, uint32_t* vals,
+                                                    uint32_t* flag) {
     const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
     if (i >= n) return;
     const rv_op op = ops[i];
-    bool bad = op.domain != RV_DOM_GF2 || op.reserved != 0 || op.opcode > RV_OP_CONST;
+    bool bad = op.domain != RV_DOM_GF2 || (pseudo ? (op.reserved & ~(PS_OP | PS_A | PS_B)) != 0 : op.reserved != 0) || op.opcode > RV_OP_CONST;
     const int nr = bad ? 0 : op_reads(op.opcode);
-    const bool wr = !bad && op_writes(op.opcode);
+    const bool wr = !bad && op_writes(op.opcode) && !(op.reserved & PS_OP);
     if (wr && op.dst >= W) bad = true;
-    if (nr >= 1 && op.a >= W) bad = true;
-    if (nr >= 2 && op.b >= W) bad = true;
+    if (nr >= 1 && !(op.reserved & PS_A) && op.a >= W) bad = true;
+    if (nr >= 2 && !(op.reserved & PS_B) && op.b >= W) bad = true;
     if (bad) atomicOr(flag, 1u);
     C4 c{0, 0, 0, 0};
     if (!bad) {
@@ -219,18 +230,28 @@ __global__ __launch_bounds__(TB) void k_cd_classify(const rv_op* ops, size_t n, 
 }
 
 // the ordinal tables: reconstruction ordinal -> online row, input ordinal -> online row, the AssertZero ops
+// (b2a_base: where the n_b2a expansions start in the list, ascending.  Their reconstructions count in c.as like AssertZero ops but are
+// not in the AssertZero tables: 64 per expansion in front of op i come off its ordinal there)
 __global__ __launch_bounds__(TB) void k_cd_ordinals(const rv_op* ops, size_t n, const C4* cx, uint32_t on0, uint32_t* rec_rows, uint32_t* in_rows,
-                                                    uint32_t* as_rec, uint64_t* as_op, const uint32_t* orig) {
+                                                    uint32_t* as_rec, uint64_t* as_op, const uint32_t* orig, const uint32_t* b2a_base, uint32_t n_b2a) {
     const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
     if (i >= n) return;
-    const uint32_t opc = ops[i].opcode;
+    const rv_op op = ops[i];
+    const uint32_t opc = op.opcode;
     const C4 c = cx[i];
     const uint32_t eo = on0 + c.in + c.mul + c.as, x = c.mul + c.as;
     if (opc == RV_OP_INPUT) in_rows[c.in] = eo;
     if (opc == RV_OP_MUL || opc == RV_OP_ASSERTZERO) rec_rows[x] = eo;
-    if (opc == RV_OP_ASSERTZERO) {
-        as_rec[c.as] = x;
-        as_op[c.as] = orig ? orig[i] : i;  // (orig: the ops are the GF(2) ops of a mixed list, orig[i] = op i's place in it)
+    if (opc == RV_OP_ASSERTZERO && !is_recon(op)) {
+        uint32_t a = 0, b = n_b2a;
+        while (a < b) {  // (expansions that start before op i; at most 32 steps)
+            const uint32_t mid = a + (b - a) / 2;
+            if (b2a_base[mid] < i) a = mid + 1;
+            else b = mid;
+        }
+        const uint32_t k = c.as - 64u * a;
+        as_rec[k] = x;
+        as_op[k] = orig ? orig[i] : i;  // (orig: the ops are the GF(2) ops of a mixed list, orig[i] = op i's place in it)
     }
 }
 
@@ -260,8 +281,10 @@ __global__ __launch_bounds__(TB) void k_cd_resolve(const rv_op* ops, size_t n, c
     const rv_op op = ops[i];
     const int nr = op_reads(op.opcode);
     int2 p = make_int2(-1, -1);
-    if (nr >= 1) p.x = last_writer(sv, seg_lo, seg_hi, op.a, (uint32_t)i);
-    if (nr >= 2) p.y = last_writer(sv, seg_lo, seg_hi, op.b, (uint32_t)i);
+    // (a private op of a B2A expansion names the steps of its own expansion by their places; its reads of the source wires are
+    // searched like any other: no step of an expansion writes a wire, so every place in it sees the B2A's own last writers)
+    if (nr >= 1) p.x = (op.reserved & PS_A) ? (int)op.a : last_writer(sv, seg_lo, seg_hi, op.a, (uint32_t)i);
+    if (nr >= 2) p.y = (op.reserved & PS_B) ? (int)op.b : last_writer(sv, seg_lo, seg_hi, op.b, (uint32_t)i);
     if (chunk) {
         if (nr >= 1 && p.x < 0) p.x = -2 - (int)op.a;
         if (nr >= 2 && p.y < 0) p.y = -2 - (int)op.b;
@@ -375,8 +398,12 @@ __device__ inline int2 value_k1(const rv_op& op, uint32_t i, int2 p, uint32_t ch
         *gl = max(lvl_of(A), lvl_of(B)) + 1;
         out = make_int2((int)i, (*gl + 1) << 1);
         break;
-    default:  // AssertZero
+    default:  // AssertZero; a B2A's reconstruction also has a value, its own computed row
         *gl = lvl_of(A) + 1;
+        if (op.reserved & PS_OP) {
+            out = make_int2((int)i, (*gl + 1) << 1);
+            *mt = 1;
+        }
         break;
     }
     return out;
@@ -427,8 +454,12 @@ __device__ inline uint4 value_lazy(const rv_op& op, uint32_t i, int2 p, const ui
         *gl = max(form_lvl(A, glvl), form_lvl(B, glvl)) + 1;
         out = make_uint4(i, 0, 0, 1);
         break;
-    default:  // AssertZero
+    default:  // AssertZero; a B2A's reconstruction also has a value, its own computed row
         *gl = form_lvl(A, glvl) + 1;
+        if (op.reserved & PS_OP) {
+            out = make_uint4(i | ROW_COMP, 0, 0, 1);
+            *mt = 1;
+        }
         break;
     }
     return out;
@@ -436,7 +467,9 @@ __device__ inline uint4 value_lazy(const rv_op& op, uint32_t i, int2 p, const ui
 
 // a Z64 op's level (run_pass, case RV_DOM_Z64): Input, Random and Const 0, every other gate one above its deepest operand; SSA 0 and
 // a chunk's carried slots (p < 0) count as -1
-__device__ inline int level_z64(const rv_op& op, int2 p, const int* glvl) {
+// (a B2A: one above its deepest reconstruction, which k_z_b2a_levels wrote before the rounds)
+__device__ inline int level_z64(const rv_op& op, uint32_t i, int2 p, const int* glvl) {
+    if (op.opcode == ZOP_B2A) return glvl[i];
     if (op_reads(op.opcode) == 0) return 0;
     return max(p.x >= 0 ? glvl[p.x] : -1, p.y >= 0 ? glvl[p.y] : -1) + 1;
 }
@@ -465,7 +498,7 @@ __global__ __launch_bounds__(TB) void k_cd_round(uint32_t r, uint32_t chunk, con
         const int2 p = prod[i];
         int gl = -1;
         uint32_t mt = 0;
-        if constexpr (FORM == FORM_Z64) gl = level_z64(op, p, glvl);
+        if constexpr (FORM == FORM_Z64) gl = level_z64(op, i, p, glvl);
         else if constexpr (FORM == FORM_LAZY) V3[i] = value_lazy(op, i, p, uses, V3, glvl, &gl, &mt);
         else V[i] = value_k1(op, i, p, chunk, uses, V, &gl, &mt);
         glvl[i] = gl;
@@ -552,7 +585,7 @@ __global__ __launch_bounds__(TB) void k_cd_keys(const rv_op* ops, size_t n, cons
             const int2 p = prod[i];
             if constexpr (LAZY) cls = (form_n(form_of(V3, p.x)) == 1 && form_n(form_of(V3, p.y)) == 1) ? 0u : 1u;
             else cls = (is_row(val_of(V, p.x)) && is_row(val_of(V, p.y))) ? 0u : 1u;
-        } else if (mat[i]) {
+        } else if (opc != RV_OP_ASSERTZERO && mat[i]) {  // (a reconstruction has a computed row too: class 4)
             cls = 2;
             if constexpr (LAZY) cls = (V3[i].w >> 8) == 2 ? 2u : 3u;
         }
@@ -649,14 +682,16 @@ __global__ __launch_bounds__(TB) void k_cd_gates(const uint32_t* sk, const uint3
             break;
         }
         case RV_OP_ASSERTZERO: {
+            const uint32_t gop = is_recon(op) ? G_RECON : G_ASSERT;
+            if (gop == G_RECON) g.dst = zero + 1 + comp[i];
             if constexpr (LAZY) {
                 const uint32_t na = form_n(FA);
-                g.op = G_ASSERT | na << 8 | form_c(FA) << 16;
+                g.op = gop | na << 8 | form_c(FA) << 16;
                 for (int k = 0; k < RV_LIN_K; k++)
                     if ((uint32_t)k < na) g.a[k] = row_index(ops, cx, comp, s, pad, (int)(form_row(FA, k) & ~ROW_COMP));
             } else {
                 const uint32_t na = is_row(A);
-                g.op = G_ASSERT | na << 8 | (uint32_t)(A.y & 1) << 16;
+                g.op = gop | na << 8 | (uint32_t)(A.y & 1) << 16;
                 if (na) g.a[0] = row_index(ops, cx, comp, s, pad, A.x);
             }
             g.eo = eo;
@@ -862,12 +897,29 @@ int run_rounds(hipStream_t st, int form, uint32_t chunk, size_t n, uint32_t max_
 struct Mixed {
     const uint32_t* orig;  // op i's place in the whole list (the AssertZero table)
     size_t n_total;        // ops of the whole list
-    uint32_t levels64;     // levels the Z64 ops take (the level count is the deeper domain's, Builder::max_level)
-    bool wb64;             // a chunk whose Z64 side has write-back gates: they share the GF(2) write-backs' level
+    // The Z64 ops' writers and levels, run once the GF(2) ops have theirs (glvl2: the level of every GF(2) op's gate) -- a B2A gate
+    // sits one level above its deepest reconstruction.  Fills levels64 and wb64; RV_OK or what the compile returns.
+    std::function<int(const int* glvl2)> z64_levels;
+    uint32_t levels64 = 0;  // levels the Z64 ops take (the level count is the deeper domain's, Builder::max_level)
+    bool wb64 = false;      // a chunk whose Z64 side has write-back gates: they share the GF(2) write-backs' level
+    // B2A expansions in the list (RV_COMPILE_DEVICE_B2A): where each starts, ascending, and what its Gate64 needs from this compile
+    // (b2a_rows[2 j] = its first reconstruction's computed row, [2 j + 1] = its first fresh mask's row)
+    uint32_t n_b2a = 0;
+    const uint32_t* b2a_base = nullptr;
+    uint32_t* b2a_rows = nullptr;
 };
+// Gate64::a and Gate64::m2 of every B2A (run_pass: first_out and m2_first, as share rows)
+__global__ __launch_bounds__(TB) void k_cd_b2a_rows(const uint32_t* b2a_base, uint32_t n_b2a, const C4* cx, const uint32_t* comp, Seeds s, uint32_t pad,
+                                                    uint32_t* rows) {
+    const uint32_t j = blockIdx.x * TB + threadIdx.x;
+    if (j >= n_b2a) return;
+    const uint32_t b = b2a_base[j];
+    rows[2 * j] = s.base + pad + 1 + comp[b + B2A_RECON0];
+    rows[2 * j + 1] = s.base + s.m0 + cx[b].m;
+}
 
 int compile_gf2_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, bool keep_wires,
-                       int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps, const ChunkStart* chunk, const Mixed* mx) {
+                       int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps, const ChunkStart* chunk, Mixed* mx) {
     // (a Z64 op in the list is what sends a program to the host; the Z64 wire count alone does not)
     const bool lazy = force_lazy_k == RV_LIN_K;  // the lazy-sum form: whole programs only (a chunk is final at K = 1)
     if (keep_wires || (force_lazy_k && (!lazy || chunk)) || getenv("RV_LAZY_K") || (n_ops == 0 && !chunk && !mx) || n_ops >= (1u << 28) || gf2_wires >= (1u << 31) ||
@@ -921,7 +973,8 @@ int compile_gf2_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     C4* d_tot = (C4*)(d_small + 8);
     DevStats* d_stats = (DevStats*)(d_small + 16);
     CDCHK(hipMemsetAsync(d_small, 0, 64 * 4, st));
-    k_cd_classify<<<gb, TB, 0, st>>>(d_ops, n, W, cx, kbuf[0], vbuf[0], d_small);
+    const uint32_t n_b2a = mx ? mx->n_b2a : 0, n_recon = 64u * n_b2a;  // (n_b2a x 442 < 2^28)
+    k_cd_classify<<<gb, TB, 0, st>>>(d_ops, n, W, n_b2a ? 1u : 0u, cx, kbuf[0], vbuf[0], d_small);
     CDCHK(hipGetLastError());
     CDCHK((scan_excl<C4, SumC4>(S, st, cx, cx, n, d_tot)));
     uint32_t h_small[28];
@@ -941,10 +994,12 @@ int compile_gf2_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
         in_rows = (uint32_t*)p;
         S.ps.push_back(p);
     }
-    uint32_t* as_rec = S.get<uint32_t>(tot.as);
-    uint64_t* as_op = S.get<uint64_t>(tot.as);
+    if (tot.as < n_recon) return RV_E_DEVICE;  // (cannot happen: every expansion has its 64 reconstructions)
+    const uint32_t n_as = tot.as - n_recon;    // the AssertZero ops (a B2A's reconstructions count in tot.as, as in info.gf2_asserts)
+    uint32_t* as_rec = S.get<uint32_t>(n_as);
+    uint64_t* as_op = S.get<uint64_t>(n_as);
     CDNEED(as_rec && as_op);
-    k_cd_ordinals<<<gb, TB, 0, st>>>(d_ops, n, cx, seeds.on0, rec_rows, in_rows, as_rec, as_op, mx ? mx->orig : nullptr);
+    k_cd_ordinals<<<gb, TB, 0, st>>>(d_ops, n, cx, seeds.on0, rec_rows, in_rows, as_rec, as_op, mx ? mx->orig : nullptr, mx ? mx->b2a_base : nullptr, n_b2a);
     CDCHK(hipGetLastError());
     mark(1);
     // ---- 2. the last writer of every read ----
@@ -991,6 +1046,10 @@ int compile_gf2_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
         if (rr != RV_OK) return rr;
     }
     if (laps) laps->rounds = r;
+    if (mx && mx->z64_levels) {
+        const int rz = mx->z64_levels(glvl);
+        if (rz != RV_OK) return rz;
+    }
     if (lazy) k_cd_stats<true><<<gb, TB, 0, st>>>(d_ops, n, prod, V, V3, glvl, mat, d_stats);
     else k_cd_stats<false><<<gb, TB, 0, st>>>(d_ops, n, prod, V, V3, glvl, mat, d_stats);
     CDCHK(hipGetLastError());
@@ -1034,6 +1093,10 @@ int compile_gf2_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     uint32_t* comp = S.get<uint32_t>(n + 1);
     CDNEED(comp);
     CDCHK((scan_excl<uint32_t, SumU32>(S, st, mat, comp, n + 1, nullptr)));
+    if (n_b2a) {
+        k_cd_b2a_rows<<<blocks(n_b2a, TB), TB, 0, st>>>(mx->b2a_base, n_b2a, cx, comp, seeds, (uint32_t)n_masks_pad, mx->b2a_rows);
+        CDCHK(hipGetLastError());
+    }
     // ---- 5. tables ----
     const uint32_t n_buckets = n_levels_ops * 5;  // (of the ops' gates: the write-back gates do not go through the sort)
     if (lazy) k_cd_keys<true><<<gb, TB, 0, st>>>(d_ops, n, prod, V, V3, glvl, mat, n_buckets, kbuf[0], vbuf[0]);
@@ -1073,16 +1136,16 @@ int compile_gf2_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     cc.gates.resize(n_gates);
     cc.rec_rows.resize(n_rec);
     cc.in_rows.resize(tot.in);
-    cc.assert_rec2.resize(tot.as);
-    cc.assert_op2.resize(tot.as);
+    cc.assert_rec2.resize(n_as);
+    cc.assert_op2.resize(n_as);
     std::vector<uint32_t> h_pos((size_t)n_buckets + 1), h_need(n_levels);
     cc.level_done_on.resize(n_levels);
     auto d2h = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess; };
     CDCHK(d2h(cc.gates.data(), gates, n_gates * sizeof(Gate)));
     CDCHK(d2h(cc.rec_rows.data(), rec_rows, n_rec * 4));
     CDCHK(d2h(cc.in_rows.data(), in_rows, (size_t)tot.in * 4));
-    CDCHK(d2h(cc.assert_rec2.data(), as_rec, (size_t)tot.as * 4));
-    CDCHK(d2h(cc.assert_op2.data(), as_op, (size_t)tot.as * 8));
+    CDCHK(d2h(cc.assert_rec2.data(), as_rec, (size_t)n_as * 4));
+    CDCHK(d2h(cc.assert_op2.data(), as_op, (size_t)n_as * 8));
     CDCHK(d2h(h_pos.data(), pos, h_pos.size() * 4));
     CDCHK(d2h(h_need.data(), need_raw, (size_t)n_levels * 4));
     CDCHK(d2h(cc.level_done_on.data(), done_on, (size_t)n_levels * 4));
@@ -1111,7 +1174,7 @@ int compile_gf2_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     cc.level_start[n_levels] = (uint32_t)n_gates;
     cc.level_start64.assign(n_levels + 1, 0);
     const uint64_t randoms = (uint64_t)tot.m - tot.in - 2ull * tot.mul;
-    cc.n_ssa = 1 + (chunk ? (uint64_t)W : 0) + n - tot.as;
+    cc.n_ssa = 1 + (chunk ? (uint64_t)W : 0) + n - n_as;
     cc.n_masks = n_masks;
     cc.n_masks_pad = n_masks_pad;
     cc.n_rows = (chunk ? (uint64_t)W : 0) + n_masks_pad + n_comp;
@@ -1119,8 +1182,8 @@ int compile_gf2_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     cc.n_pre = (chunk ? chunk->pre0 : 0) + tot.mul;
     cc.n_in = tot.in;
     cc.n_rec = n_rec;
-    cc.n_random_or_recon = randoms;
-    cc.n_user_random = randoms;
+    cc.n_random_or_recon = randoms + n_recon;
+    cc.n_user_random = randoms - n_recon;  // (a B2A's 64 fresh masks are not the user's)
     cc.row_prg_base = chunk ? W : 0;
     cc.zero_row = cc.row_prg_base + n_masks_pad;
     if (chunk) {  // (the Z64 side of a GF(2) piece: its carried slots and counters, untouched)
@@ -1134,7 +1197,7 @@ int compile_gf2_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
     info.gf2_inputs = tot.in;
     info.gf2_muls = tot.mul;
     info.gf2_asserts = tot.as;
-    info.gf2_linear = randoms + hs.n_mat + n_wbmat + n_wb;
+    info.gf2_linear = randoms + (hs.n_mat - n_recon) + n_wbmat + n_wb;  // (n_mat: every gate with a computed row, reconstructions too)
     info.gf2_masks = n_masks;
     info.z64_masks = cc.n_masks64;
     info.levels = n_levels;
@@ -1164,6 +1227,9 @@ int compile_gf2_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, si
 // The two domains share no wire and, without B2A, no gate: run_pass keeps them apart except for the level count.  So a mixed list is
 // split: its GF(2) ops, compacted in order, go through the pipeline above unchanged, and its Z64 ops through the same steps in a
 // simpler form -- no folding, every op one Gate64, every counter a prefix sum, a gate's level one above its deepest operand.
+// B2A (RV_COMPILE_DEVICE_B2A) is the one dependency between them, and it runs one way: a B2A is expanded at the split into its 442
+// GF(2) steps (k_z_expand) and one Z64-list record; the GF(2) pipeline runs its levels first, the B2A records take theirs from their
+// reconstructions' (k_z_b2a_levels), and the Z64 rounds start from there.
 //   1. classify    one thread per op of the whole list: the Z64 and SizeHint checks of run_pass (the GF(2) ops are checked by
 //                  k_cd_classify once compacted), the Z64 counters and each op's place in its domain's list: two 16-byte tuple scans
 //   2. writers     the sort, segments and resolve kernels above, over the Z64 ops and wires
@@ -1180,7 +1246,9 @@ struct Seeds64 {
 // pc: {GF(2) op, Z64 op, 0, 0} -- their exclusive scan is every op's place in its domain's list; zc: the Z64 counters of compile.cpp
 // (m: Input 1, Random 1, Mul 2; mul; as; in).  A B2A op, an unknown domain, a SizeHint that grows a wire count and any Z64 op
 // run_pass rejects raise the flag: the host compiler takes the list.
-__global__ __launch_bounds__(TB) void k_z_classify(const rv_op* ops, size_t n, uint32_t W2, uint32_t W64, C4* zc, C4* pc, uint32_t* flag) {
+// admit_b2a: a B2A op is {442 entries of the GF(2) list, one of the Z64 list, one B2A} in pc and one Z64 mask in zc, checked as
+// run_pass checks it (dst in the Z64 wires, the 64 source wires in the GF(2) wires).
+__global__ __launch_bounds__(TB) void k_z_classify(const rv_op* ops, size_t n, uint32_t W2, uint32_t W64, uint32_t admit_b2a, C4* zc, C4* pc, uint32_t* flag) {
     const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
     if (i >= n) return;
     const rv_op op = ops[i];
@@ -1201,6 +1269,10 @@ __global__ __launch_bounds__(TB) void k_z_classify(const rv_op* ops, size_t n, u
         else if (op.opcode == RV_OP_ASSERTZERO) z.as = 1;
     } else if (op.domain == RV_DOM_SIZEHINT) {
         if (op.a > W64 || op.b > W2) bad = true;
+    } else if (op.domain == RV_DOM_B2A && admit_b2a) {
+        if (op.dst >= W64 || (uint64_t)op.a + 64 > W2) bad = true;
+        p.m = B2A_STEPS, p.mul = 1, p.as = 1;
+        z.m = 1;
     } else {
         bad = true;
     }
@@ -1209,8 +1281,11 @@ __global__ __launch_bounds__(TB) void k_z_classify(const rv_op* ops, size_t n, u
     pc[i] = p;
 }
 // px, zx: the exclusive scans.  Each domain's ops in order, with their places in the whole list; the Z64 ops' counters go with them
+// A B2A goes into the Z64 list as a ZOP_B2A record whose `a` is the place of its expansion in the GF(2) list (k_z_expand fills that);
+// bx64 (null: a list without B2A): the B2A ops in front of every Z64-list entry -- they share the correction ordinal with Mul;
+// b2a: per B2A {its expansion's place, its first source wire, its place in the whole list}
 __global__ __launch_bounds__(TB) void k_z_compact(const rv_op* ops, size_t n, const C4* px, const C4* zx, rv_op* ops2, uint32_t* orig2, rv_op* ops64,
-                                                  uint32_t* orig64, C4* zc64) {
+                                                  uint32_t* orig64, C4* zc64, uint32_t* bx64, uint32_t* b2a_base, uint2* b2a_src) {
     const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
     if (i >= n) return;
     const rv_op op = ops[i];
@@ -1218,11 +1293,67 @@ __global__ __launch_bounds__(TB) void k_z_compact(const rv_op* ops, size_t n, co
     if (op.domain == RV_DOM_GF2) {
         ops2[p.m] = op;
         orig2[p.m] = (uint32_t)i;
-    } else if (op.domain == RV_DOM_Z64) {
-        ops64[p.mul] = op;
+    } else if (op.domain == RV_DOM_Z64 || op.domain == RV_DOM_B2A) {
+        rv_op o = op;
+        if (op.domain == RV_DOM_B2A) {
+            o.domain = RV_DOM_Z64, o.opcode = ZOP_B2A, o.reserved = 0, o.a = p.m, o.b = 0, o.imm = 0;
+            b2a_base[p.as] = p.m;
+            b2a_src[p.as] = make_uint2(op.a, (uint32_t)i);
+        }
+        ops64[p.mul] = o;
         orig64[p.mul] = (uint32_t)i;
         zc64[p.mul] = zx[i];
+        if (bx64) bx64[p.mul] = p.as;
     }
+}
+// Step j of a B2A's expansion (run_pass, case RV_DOM_B2A, in Builder::g_* call order) at place B of the GF(2) list, S = its first source
+// wire: 64 Random a_k; Mul(a_0, b_0), Xor(a_0, b_0); for k = 1..62 ac = Xor(a_k, carry), bc = Xor(b_k, carry), t = Mul(ac, bc),
+// res_k = Xor(ac, b_k), carry = Xor(t, carry); Xor(a_63, b_63), res_63 = Xor(carry, that); 64 reconstructions of res_k
+__device__ inline rv_op b2a_step(uint32_t B, uint32_t S, uint32_t j) {
+    rv_op o;
+    o.domain = RV_DOM_GF2, o.opcode = RV_OP_ADD, o.reserved = PS_OP | PS_A | PS_B, o.dst = 0, o.a = 0, o.b = 0, o.imm = 0;
+    if (j < 64) {
+        o.opcode = RV_OP_RANDOM, o.reserved = PS_OP;
+    } else if (j == 64 || j == 65) {
+        o.opcode = j == 64 ? RV_OP_MUL : RV_OP_ADD;
+        o.reserved = PS_OP | PS_A, o.a = B, o.b = S;
+    } else if (j < 376) {
+        const uint32_t k = 1 + (j - 66) / 5, t = (j - 66) % 5, at = 66 + 5 * (k - 1), carry = k == 1 ? 64u : at - 1;
+        if (t == 0) o.a = B + k, o.b = B + carry;
+        else if (t == 1) o.reserved = PS_OP | PS_B, o.a = S + k, o.b = B + carry;
+        else if (t == 2) o.opcode = RV_OP_MUL, o.a = B + at, o.b = B + at + 1;
+        else if (t == 3) o.reserved = PS_OP | PS_A, o.a = B + at, o.b = S + k;
+        else o.a = B + at + 2, o.b = B + carry;
+    } else if (j == 376) {
+        o.reserved = PS_OP | PS_A, o.a = B + 63, o.b = S + 63;
+    } else if (j == 377) {
+        o.a = B + 375, o.b = B + 376;
+    } else {
+        const uint32_t k = j - B2A_RECON0;
+        o.opcode = RV_OP_ASSERTZERO, o.reserved = PS_OP | PS_A;
+        o.a = B + (k == 0 ? 65u : k == 63 ? 377u : 66 + 5 * (k - 1) + 3);
+    }
+    return o;
+}
+static_assert(66 + 5 * 62 == 376 && B2A_RECON0 + 64 == B2A_STEPS, "the steps of one B2A");
+// one workgroup per B2A
+__global__ __launch_bounds__(TB) void k_z_expand(const uint32_t* b2a_base, const uint2* b2a_src, rv_op* ops2, uint32_t* orig2) {
+    const uint32_t B = b2a_base[blockIdx.x];
+    const uint2 s = b2a_src[blockIdx.x];
+    for (uint32_t j = threadIdx.x; j < B2A_STEPS; j += TB) {
+        ops2[B + j] = b2a_step(B, s.x, j);
+        orig2[B + j] = s.y;
+    }
+}
+// a B2A gate's level, before the Z64 rounds: one above its deepest reconstruction (glvl2: the GF(2) list's gate levels)
+__global__ __launch_bounds__(TB) void k_z_b2a_levels(const rv_op* ops64, size_t n, const int* glvl2, int* glvl) {
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const rv_op op = ops64[i];
+    if (op.opcode != ZOP_B2A) return;
+    int l = 0;
+    for (uint32_t k = 0; k < 64; k++) l = max(l, glvl2[op.a + B2A_RECON0 + k]);
+    glvl[i] = l + 1;
 }
 // the writer sort's keys (as k_cd_classify's: the wire, W64 for AssertZero)
 __global__ __launch_bounds__(TB) void k_z_wkeys(const rv_op* ops, size_t n, uint32_t W64, uint32_t* keys, uint32_t* vals) {
@@ -1262,8 +1393,10 @@ __device__ inline uint32_t z_mask_row(int p, const rv_op* ops, const C4* zc, con
     return z_ssa(p, zc, s);
 }
 // the Gate64 records in (level, program) order; the input / reconstruction offsets and the AssertZero tables by ordinal
+// (bx: the B2A ops in front of each op, null without any; b2a_rows: Mixed::b2a_rows)
 __global__ __launch_bounds__(TB) void k_z_gates(const uint32_t* sv, size_t n, const rv_op* ops, const int2* prod, const C4* zc, const uint32_t* orig, Seeds64 s,
-                                                Gate64* gates, uint64_t* rec_offs, uint64_t* in_offs, uint32_t* as_rec, uint64_t* as_op) {
+                                                const uint32_t* bx, const uint32_t* b2a_rows, Gate64* gates, uint64_t* rec_offs, uint64_t* in_offs,
+                                                uint32_t* as_rec, uint64_t* as_op) {
     const size_t p = (size_t)blockIdx.x * TB + threadIdx.x;
     if (p >= n) return;
     const uint32_t i = sv[p];
@@ -1281,7 +1414,16 @@ __global__ __launch_bounds__(TB) void k_z_gates(const uint32_t* sv, size_t n, co
     if (op_writes(op.opcode)) g.dst = s.ssa_base + i - c.as;
     const uint64_t eo = s.on0 + c.in + 8ull * ((uint64_t)c.mul + c.as);
     const uint32_t x = c.mul + c.as;
+    const uint32_t nb = bx ? bx[i] : 0u, corr = c.mul + nb;  // corrections so far: Mul and B2A
     switch (op.opcode) {
+    case ZOP_B2A:
+        g.op = G64_B2A;
+        g.a = b2a_rows[2 * nb];
+        g.m = s.m0 + c.m;
+        g.m2 = b2a_rows[2 * nb + 1];
+        g.ep = s.pre0 + corr;
+        g.xc = corr;
+        break;
     case RV_OP_INPUT:
         g.op = G64_INPUT;
         g.m = s.m0 + c.m;
@@ -1302,8 +1444,8 @@ __global__ __launch_bounds__(TB) void k_z_gates(const uint32_t* sv, size_t n, co
     case RV_OP_MUL:
         g.op = G64_MUL;
         g.m = s.m0 + c.m;
-        g.ep = s.pre0 + c.mul;
-        g.xc = c.mul;
+        g.ep = s.pre0 + corr;
+        g.xc = corr;
         g.eo = eo;
         g.x = x;
         rec_offs[x] = eo;
@@ -1334,7 +1476,7 @@ __global__ __launch_bounds__(TB) void k_z_wb_gates(const uint32_t* sv, const uin
 }
 
 int compile_mixed_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n, size_t z64_wires, size_t gf2_wires, bool keep_wires, int force_lazy_k,
-                         Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps, const ChunkStart* chunk) {
+                         Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps, const ChunkStart* chunk, bool admit_b2a) {
     const bool lazy = force_lazy_k == RV_LIN_K;
     if (keep_wires || (force_lazy_k && (!lazy || chunk)) || getenv("RV_LAZY_K") || n >= (1u << 28) || gf2_wires >= (1u << 31) || z64_wires >= (1u << 30))
         return RV_COMPILE_FALLBACK;
@@ -1344,14 +1486,14 @@ int compile_mixed_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, 
     const uint64_t LIM = 0xFFFFFFFFull - 512;
     if (chunk && (chunk->mask64_phase >= 2 || chunk->on_words64_0 > (1ull << 62) || chunk->pre_words64_0 > (1ull << 62))) return RV_COMPILE_FALLBACK;
     Scratch S(A, st);
-    hipEvent_t ev[4] = {};
+    hipEvent_t ev[6] = {};  // the split [0, 1), the Z64 tables [2, 3), the Z64 levels inside the GF(2) compile [4, 5)
     if (laps)
         for (auto& e : ev)
             if (hipEventCreate(&e) != hipSuccess) return RV_E_DEVICE;
     struct EvGuard {
         hipEvent_t* e;
         ~EvGuard() {
-            for (int k = 0; k < 4; k++)
+            for (int k = 0; k < 6; k++)
                 if (e[k]) (void)hipEventDestroy(e[k]);
         }
     } ev_guard{ev};
@@ -1366,7 +1508,7 @@ int compile_mixed_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, 
     uint32_t* d_small = S.get<uint32_t>(32);  // [0] error flag, [4..8) Z64 counter totals, [8..12) op counts, [12] deepest Z64 level, [13] write-backs
     CDNEED(zx && px && d_small);
     CDCHK(hipMemsetAsync(d_small, 0, 32 * 4, st));
-    k_z_classify<<<gb, TB, 0, st>>>(d_ops, n, W2, W64, zx, px, d_small);
+    k_z_classify<<<gb, TB, 0, st>>>(d_ops, n, W2, W64, admit_b2a ? 1u : 0u, zx, px, d_small);
     CDCHK(hipGetLastError());
     CDCHK((scan_excl<C4, SumC4>(S, st, zx, zx, n, (C4*)(d_small + 4))));
     CDCHK((scan_excl<C4, SumC4>(S, st, px, px, n, (C4*)(d_small + 8))));
@@ -1375,8 +1517,10 @@ int compile_mixed_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, 
     CDCHK(hipStreamSynchronize(st));
     if (h_small[0]) return RV_COMPILE_FALLBACK;
     const C4 tot{h_small[4], h_small[5], h_small[6], h_small[7]};
+    const uint32_t n_b2a = h_small[10];
+    if ((uint64_t)n_b2a * B2A_STEPS >= (1u << 28)) return RV_COMPILE_FALLBACK;  // (the expanded GF(2) list: below 2^28 entries, and no sum above wrapped)
     const size_t n2 = h_small[8], n64 = h_small[9];
-    if (n2 == n)  // no Z64 op and no SizeHint: the list as it is
+    if (n2 == n && n64 == 0)  // no Z64 op, no B2A and no SizeHint: the list as it is
         return compile_gf2_device(st, A, d_ops, n, z64_wires, gf2_wires, keep_wires, force_lazy_k, out, keep, laps, chunk, nullptr);
     Seeds64 s64{1u + (chunk ? W64 : 0u), chunk ? chunk->mask64_phase : 0u, chunk ? chunk->on_words64_0 : 0, chunk ? chunk->pre_words64_0 : 0};
     const uint64_t n_masks64 = (uint64_t)s64.m0 + tot.m;
@@ -1387,16 +1531,33 @@ int compile_mixed_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, 
     uint32_t* orig64 = S.get<uint32_t>(n64);
     C4* zc = S.get<C4>(n64);
     CDNEED(ops2 && orig2 && ops64 && orig64 && zc);
-    k_z_compact<<<gb, TB, 0, st>>>(d_ops, n, px, zx, ops2, orig2, ops64, orig64, zc);
+    uint32_t *bx64 = nullptr, *b2a_base = nullptr, *b2a_rows = nullptr;
+    uint2* b2a_src = nullptr;
+    if (n_b2a) {
+        bx64 = S.get<uint32_t>(n64);
+        b2a_base = S.get<uint32_t>(n_b2a);
+        b2a_src = S.get<uint2>(n_b2a);
+        b2a_rows = S.get<uint32_t>(2 * (size_t)n_b2a);
+        CDNEED(bx64 && b2a_base && b2a_src && b2a_rows);
+    }
+    k_z_compact<<<gb, TB, 0, st>>>(d_ops, n, px, zx, ops2, orig2, ops64, orig64, zc, bx64, b2a_base, b2a_src);
+    if (n_b2a) k_z_expand<<<n_b2a, TB, 0, st>>>(b2a_base, b2a_src, ops2, orig2);
     CDCHK(hipGetLastError());
-    // ---- 2. / 3. the Z64 ops' writers and levels ----
+    mark(1);
+    // ---- 2. / 3. the Z64 ops' writers and levels: once the GF(2) ops have theirs (Mixed::z64_levels) ----
     const uint32_t gb64 = blocks(n64, TB);
     uint32_t *kbuf[2] = {nullptr, nullptr}, *vbuf[2] = {nullptr, nullptr}, *seg_lo = nullptr, *seg_hi = nullptr, *wbx = nullptr;
     int2* prod = nullptr;
     int* glvl = nullptr;
     int wsort = 0;
     uint32_t levels64 = 0, n_wb64 = 0;
-    if (n64) {
+    uint32_t *lk[2] = {nullptr, nullptr}, *lv[2] = {nullptr, nullptr};
+    Mixed mx;
+    mx.orig = orig2, mx.n_total = n;
+    mx.n_b2a = n_b2a, mx.b2a_base = b2a_base, mx.b2a_rows = b2a_rows;
+    mx.z64_levels = [&](const int* glvl2) -> int {
+        if (!n64) return RV_OK;
+        mark(4);
         for (int k = 0; k < 2; k++) kbuf[k] = S.get<uint32_t>(n64), vbuf[k] = S.get<uint32_t>(n64);
         seg_lo = S.get<uint32_t>(W64);
         seg_hi = S.get<uint32_t>(W64);
@@ -1425,6 +1586,7 @@ int compile_mixed_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, 
         CDCHK(hipMemsetAsync(rounds, 0, ((size_t)max_rounds + 2) * sizeof(uint2), st));
         k_cd_consumers<<<gb64, TB, 0, st>>>(prod, n64, cons_off, cursor, cons);
         k_cd_front0<<<gb64, TB, 0, st>>>(rem, n64, frontier, rounds);
+        if (n_b2a) k_z_b2a_levels<<<gb64, TB, 0, st>>>(ops64, n64, glvl2, glvl);
         CDCHK(hipGetLastError());
         uint32_t r = 0;
         const RoundArgs ra{ops64, prod, uses, cons_off, cons, rem, nullptr, nullptr, glvl, nullptr, frontier, rounds};
@@ -1437,10 +1599,7 @@ int compile_mixed_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, 
             CDCHK(hipGetLastError());
             CDCHK((scan_excl<uint32_t, SumU32>(S, st, wbx, wbx, W64, d_small + 13)));
         }
-    }
-    // the level sort's keys (the writer sort's values stay in vbuf[wsort] for the write-back gates; its other three buffers are free)
-    uint32_t *lk[2] = {nullptr, nullptr}, *lv[2] = {nullptr, nullptr};
-    if (n64) {
+        // the level sort's keys (the writer sort's values stay in vbuf[wsort] for the write-back gates; its other three buffers are free)
         lk[0] = kbuf[wsort], lk[1] = kbuf[wsort ^ 1];
         lv[0] = vbuf[wsort ^ 1], lv[1] = S.get<uint32_t>(n64);
         CDNEED(lv[1]);
@@ -1450,10 +1609,11 @@ int compile_mixed_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, 
         CDCHK(hipStreamSynchronize(st));
         levels64 = h_small[12] + 1;
         n_wb64 = chunk ? h_small[13] : 0;
-    }
-    mark(1);
-    // ---- the GF(2) ops ----
-    const Mixed mx{orig2, n, levels64, n_wb64 != 0};
+        mx.levels64 = levels64, mx.wb64 = n_wb64 != 0;
+        mark(5);
+        return RV_OK;
+    };
+    // ---- the GF(2) ops (a B2A's 442 steps among them) ----
     {
         const int rc = compile_gf2_device(st, A, ops2, n2, z64_wires, gf2_wires, keep_wires, force_lazy_k, out, keep, laps, chunk, &mx);
         if (rc != RV_OK) return rc;
@@ -1499,7 +1659,7 @@ int compile_mixed_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, 
         int lsort = 0;
         CDCHK(radix_sort(S, st, lk, lv, n64, bit_len(levels64), &lsort));
         k_cd_bounds<<<blocks(n64 + 1, TB), TB, 0, st>>>(lk[lsort], n64, n_levels, pos);
-        k_z_gates<<<gb64, TB, 0, st>>>(lv[lsort], n64, ops64, prod, zc, orig64, s64, gates64, rec_offs, in_offs, as_rec, as_op);
+        k_z_gates<<<gb64, TB, 0, st>>>(lv[lsort], n64, ops64, prod, zc, orig64, s64, bx64, b2a_rows, gates64, rec_offs, in_offs, as_rec, as_op);
         CDCHK(hipGetLastError());
         cc.gates64.resize(n_g64);
         cc.rec_offs64.resize(n_rec64);
@@ -1516,25 +1676,28 @@ int compile_mixed_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, 
         mark(3);
         CDCHK(hipStreamSynchronize(st));
         cc.level_start64[n_levels] = (uint32_t)n_g64;  // (the write-backs: the last level's, behind every op's gate)
-        const uint64_t randoms = (uint64_t)tot.m - tot.in - 2ull * tot.mul;
+        const uint64_t randoms = (uint64_t)tot.m - tot.in - 2ull * tot.mul - n_b2a;  // (a B2A's Z64 mask is not a Random op)
         cc.n_ssa64 = (uint64_t)s64.ssa_base + n64 - tot.as;
         cc.n_masks64 = n_masks64;
         cc.on_words64 = s64.on0 + tot.in + 8 * n_rec64;
-        cc.pre_words64 = s64.pre0 + tot.mul;
+        cc.pre_words64 = s64.pre0 + tot.mul + n_b2a;
         cc.n_in64 = tot.in;
         cc.n_rec64 = n_rec64;
-        cc.n_corr64 = tot.mul;
+        cc.n_corr64 = (uint64_t)tot.mul + n_b2a;
         cc.n_user_random += randoms;
         cc.info.z64_inputs = tot.in;
         cc.info.z64_muls = tot.mul;
         cc.info.z64_asserts = tot.as;
-        cc.info.z64_linear = (uint64_t)n64 - tot.in - tot.mul - tot.as + n_wb64;
+        cc.info.z64_linear = (uint64_t)n64 - tot.in - tot.mul - tot.as - n_b2a + n_wb64;
         cc.info.z64_masks = n_masks64;
+        cc.info.b2a = n_b2a;
         if (laps) {
-            float a = 0, b = 0;
+            float a = 0, b = 0, c = 0;
             (void)hipEventElapsedTime(&a, ev[0], ev[1]);
             (void)hipEventElapsedTime(&b, ev[2], ev[3]);
-            laps->z64 = a + b;
+            (void)hipEventElapsedTime(&c, ev[4], ev[5]);
+            laps->z64 = a + b + c;
+            laps->levels = std::max(0.0f, laps->levels - c);  // (the Z64 levels ran inside the GF(2) compile's third step)
         }
         if (keep) {
             keep->d_gates64 = gates64;
@@ -1551,9 +1714,10 @@ int compile_mixed_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, 
 }  // namespace
 
 int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, bool keep_wires,
-                       int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps, const ChunkStart* chunk, bool admit_z64) {
+                       int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps, const ChunkStart* chunk, bool admit_z64,
+                       bool admit_b2a) {
     if (keep) *keep = DevCompileKeep();
-    if (admit_z64) return compile_mixed_device(st, A, d_ops, n_ops, z64_wires, gf2_wires, keep_wires, force_lazy_k, out, keep, laps, chunk);
+    if (admit_z64) return compile_mixed_device(st, A, d_ops, n_ops, z64_wires, gf2_wires, keep_wires, force_lazy_k, out, keep, laps, chunk, admit_b2a);
     return compile_gf2_device(st, A, d_ops, n_ops, z64_wires, gf2_wires, keep_wires, force_lazy_k, out, keep, laps, chunk, nullptr);
 }
 #undef CDCHK

@@ -95,7 +95,8 @@ extern "C" int rv_eval_stream_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wi
 }
 
 extern "C" int rv_eval_stream_set_compile_flags(rv_eval_stream* E, uint32_t flags) {
-    if (!E || (flags & ~RV_COMPILE_DEVICE_BITS) || !device_bits_ok(flags) || E->fed) return RV_E_ARG;
+    if (int rc = check_device_flags("rv_eval_stream_set_compile_flags", flags)) return rc;
+    if (!E || E->fed) return RV_E_ARG;
     E->compile_flags = flags;
     return RV_OK;
 }
@@ -250,7 +251,7 @@ static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, bool ops_o
         return h.rc() ? h.rc() : compile_ops(h.ops(), fo.len(i), E->z64_wires, E->gf2_wires, *pieces[i], &cs);
     };
     PiecePipe pipe(n_pieces, n_threads, RV_E_NOMEM, [&](size_t i) {
-        // (RV_COMPILE_DEVICE: an all-GF(2) piece -- under RV_COMPILE_DEVICE_Z64 any piece without B2A -- stays empty here: the main
+        // (RV_COMPILE_DEVICE: an all-GF(2) piece -- under RV_COMPILE_DEVICE_Z64 any piece without B2A, with RV_COMPILE_DEVICE_B2A any piece -- stays empty here: the main
         // thread compiles it on the GPU right before it runs)
         if (fo.for_device(i, E->compile_flags)) return (int)RV_OK;
         pieces[i].reset(new Compiled());

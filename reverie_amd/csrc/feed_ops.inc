@@ -42,9 +42,10 @@ struct FeedOps {
     bool all_gf2(size_t i) const { return device ? sums[i].not_gf2 == 0 : piece_all_gf2(host + at(i), len(i)); }
     bool no_b2a(size_t i) const { return device ? sums[i].not_z64 == 0 : piece_no_b2a(host + at(i), len(i)); }
     // the pieces a stream with these compile flags sends to the device compiler: all-GF(2) ones; under RV_COMPILE_DEVICE_Z64 every
-    // piece without a B2A op
+    // piece without a B2A op; with RV_COMPILE_DEVICE_B2A every piece (an error in one comes back through the fallback)
     bool for_device(size_t i, uint32_t compile_flags) const {
         if (!(compile_flags & RV_COMPILE_DEVICE)) return false;
+        if ((compile_flags & RV_COMPILE_DEVICE_Z64) && (compile_flags & RV_COMPILE_DEVICE_B2A)) return true;
         return (compile_flags & RV_COMPILE_DEVICE_Z64) ? no_b2a(i) : all_gf2(i);
     }
     // piece i through the chunk mode of the device compiler: a host feed's ops go up (counted as op traffic), a device feed's are
@@ -52,7 +53,7 @@ struct FeedOps {
     int compile_on_device(size_t i, size_t z64_wires, size_t gf2_wires, const ChunkStart& cs, Compiled& cc, DevCompileKeep* keep, double laps[3] = nullptr,
                           uint32_t compile_flags = 0) const {
         return compile_chunk_on_device(ctx, device ? nullptr : host + at(i), device ? dev + at(i) : nullptr, len(i), z64_wires, gf2_wires, cs, cc, keep, laps,
-                                       &g_op_bytes_h2d, (compile_flags & RV_COMPILE_DEVICE_Z64) != 0);
+                                       &g_op_bytes_h2d, compile_flags);
     }
 
     // Device feed: the sums of every piece (on the context's stream, one wait), the copy stream, and how many slots PieceOnHost may

@@ -16,7 +16,7 @@ struct PieceSums {
     uint64_t masks2, masks64;   // count_masks
     uint64_t in2, rec2, pre2, on64, pre64;  // count_events
     uint64_t not_gf2;           // ops of another domain (0: piece_all_gf2)
-    uint64_t not_z64;           // ops that are neither GF(2), Z64 nor SizeHint: B2A, unknown domains (0: piece_no_b2a)
+    uint64_t not_z64;           // ops that are neither GF(2), Z64 nor SizeHint: B2A, unknown domains (0: piece_no_b2a; not asked under RV_COMPILE_DEVICE_B2A)
 };
 constexpr int PIECE_SUM_WORDS = 10;
 static_assert(sizeof(PieceSums) == PIECE_SUM_WORDS * 8, "PieceSums is ten packed words");

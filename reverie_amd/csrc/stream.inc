@@ -180,7 +180,7 @@ struct rv_stream {
     int pass = 1;
     int sticky = RV_OK;  // first error: the stream is dead afterwards
     // rv_stream_set_compile_flags (the context's when the stream began): RV_COMPILE_DEVICE = every all-GF(2) piece (with
-    // RV_COMPILE_DEVICE_Z64: every piece without a B2A op) is compiled by the
+    // RV_COMPILE_DEVICE_Z64: every piece without a B2A op; with RV_COMPILE_DEVICE_B2A as well: every piece) is compiled by the
     // chunk-mode device compiler, on the context's stream right before it runs; what that hands back is compiled on the host
     uint32_t compile_flags = 0;
     bool fed = false;  // a feed has begun: the flags are fixed
@@ -448,7 +448,8 @@ extern "C" int rv_stream_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, 
 }
 
 extern "C" int rv_stream_set_compile_flags(rv_stream* S, uint32_t flags) {
-    if (!S || (flags & ~RV_COMPILE_DEVICE_BITS) || !device_bits_ok(flags) || S->fed) return RV_E_ARG;
+    if (int rc = check_device_flags("rv_stream_set_compile_flags", flags)) return rc;
+    if (!S || S->fed) return RV_E_ARG;
     S->compile_flags = flags;
     for (rv_stream* m : S->bat) m->compile_flags = flags;  // (a batch: the feed's host-side state is its first running member's)
     return RV_OK;
@@ -1219,7 +1220,7 @@ struct FeedPiece {
     uint64_t digest = 0;
     ChunkStart carried;         // the offsets c's arrays hold
     bool kept = false;          // pass 2: pass 1 kept this piece's transcripts (rv_stream::Kept) -- nothing of it is uploaded
-    bool device = false;        // RV_COMPILE_DEVICE, all GF(2) (RV_COMPILE_DEVICE_Z64: no B2A), not in pass 1's cache: c stays null until the main thread compiles it on the GPU
+    bool device = false;        // RV_COMPILE_DEVICE, all GF(2) (RV_COMPILE_DEVICE_Z64: no B2A; RV_COMPILE_DEVICE_B2A: any piece), not in pass 1's cache: c stays null until the main thread compiles it on the GPU
 };
 
 // A piece ready to run: pass 1's cached compile if its digest matches the ops fed now, else a fresh compile -- at the offsets the piece

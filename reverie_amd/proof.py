@@ -48,7 +48,8 @@ class Context:
 
     def set_compile_flags(self, flags: int):
         """rv_ctx_set_compile_flags: 0 (default), RV_COMPILE_DEVICE or RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64 (Z64 and mixed programs
-        and pieces on the GPU too; the bit alone is an error) -- the cold compiles of Proof.new_ops / verify_ops-style calls
+        and pieces on the GPU too; the bit alone is an error), the latter also with RV_COMPILE_DEVICE_B2A (programs and pieces with
+        B2A ops too; an error without both other bits) -- the cold compiles of Proof.new_ops / verify_ops-style calls
         (rv_prove_ops, rv_verify_ops) then run on the GPU, and so do the piece compiles of the streams that begin afterwards
         (reverie_amd.stream).  Proof bytes and answers are unchanged."""
         _lib.check(_lib.lib().rv_ctx_set_compile_flags(self.handle, C.c_uint32(flags)))
@@ -103,7 +104,7 @@ class Circuit:
     """A gate stream compiled (levelised) and resident in HBM (rv_circuit)."""
 
     def __init__(self, ops, wire_counts: Tuple[int, int], ctx: Optional[Context] = None, whole_prover: bool = False,
-                 keep_wires: bool = False, device_compile: bool = False, device_z64: bool = False):
+                 keep_wires: bool = False, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False):
         """whole_prover: the circuit will mostly serve whole proofs on one GPU (Proof.new / new_batch) -- the
         RV_COMPILE_WHOLE_PROVER hint of rv_circuit_compile_ex; any use of the circuit still gives identical bytes.
         keep_wires: RV_COMPILE_KEEP_WIRES -- the circuit keeps every wire's final value form, so that `evaluate` can return
@@ -112,29 +113,38 @@ class Circuit:
         whole_prover, the lazy-sum form; anything the device path does not take is compiled on the host); the circuit is the same
         either way, and `compiled_on_device` tells which compiler made it.
         device_z64: RV_COMPILE_DEVICE_Z64, only with device_compile (ValueError otherwise) -- Z64 programs and programs that mix the
-        two domains compile on the GPU too; B2A, a SizeHint that grows a wire count and keep_wires still go to the host compiler."""
+        two domains compile on the GPU too; B2A, a SizeHint that grows a wire count and keep_wires still go to the host compiler.
+        device_b2a: RV_COMPILE_DEVICE_B2A, only with device_compile and device_z64 (ValueError otherwise) -- programs with B2A ops
+        compile on the GPU too (plain form: when that is final, which of these deep programs only wide ones are; with whole_prover
+        all of them)."""
         if device_z64 and not device_compile:
             raise ValueError("device_z64=True needs device_compile=True")
+        if device_b2a and not (device_compile and device_z64):
+            raise ValueError("device_b2a=True needs device_compile=True and device_z64=True")
         self.ctx = ctx or Context.default()
         self.ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
         self.wire_counts = (int(wire_counts[0]), int(wire_counts[1]))  # (z64, gf2), proof/mod.rs:125
         self.keep_wires = bool(keep_wires)
         self.handle = C.c_void_p()
         flags = (_lib.RV_COMPILE_WHOLE_PROVER if whole_prover else 0) | (_lib.RV_COMPILE_KEEP_WIRES if keep_wires else 0) | \
-            (_lib.RV_COMPILE_DEVICE if device_compile else 0) | (_lib.RV_COMPILE_DEVICE_Z64 if device_z64 else 0)
+            (_lib.RV_COMPILE_DEVICE if device_compile else 0) | (_lib.RV_COMPILE_DEVICE_Z64 if device_z64 else 0) | \
+            (_lib.RV_COMPILE_DEVICE_B2A if device_b2a else 0)
         _lib.check(_lib.lib().rv_circuit_compile_ex(self.ctx.handle, _ptr(self.ops), C.c_size_t(len(self.ops)),
                                                     C.c_size_t(self.wire_counts[0]), C.c_size_t(self.wire_counts[1]),
                                                     C.c_uint32(flags), C.byref(self.handle)))
 
     @classmethod
     def from_device_ops(cls, ops, wire_counts: Tuple[int, int], ctx: Optional[Context] = None, whole_prover: bool = False,
-                        keep_wires: bool = False, device_z64: bool = False) -> "Circuit":
+                        keep_wires: bool = False, device_z64: bool = False, device_b2a: bool = False) -> "Circuit":
         """rv_circuit_compile_device: compile an op list that already sits in GPU memory -- a torch tensor on the context's
         device holding packed 24-byte rv_op records, as uint8 of shape [n, 24] (or [n * 24]) or int64 / uint64 of shape [n, 3];
         contiguous.  The tensor is not copied to the host unless the device path hands the program to the host compiler; the
         caller keeps it.  The circuit is the one Circuit(host ops, device_compile=True) compiles, with whole_prover the lazy-sum
         form (also built on the device).  device_z64: RV_COMPILE_DEVICE_Z64 -- Z64 and mixed programs are compiled where they are too
-        (the call itself is the device compile the bit needs)."""
+        (the call itself is the device compile the bit needs).  device_b2a: RV_COMPILE_DEVICE_B2A, only with device_z64 (ValueError
+        otherwise) -- programs with B2A ops too."""
+        if device_b2a and not device_z64:
+            raise ValueError("device_b2a=True needs device_z64=True")
         d_ops, n_ops, ctx = _device_ops(ops, ctx, "from_device_ops")
         self = cls.__new__(cls)
         self.ctx = ctx
@@ -143,7 +153,7 @@ class Circuit:
         self.keep_wires = bool(keep_wires)
         self.handle = C.c_void_p()
         flags = (_lib.RV_COMPILE_WHOLE_PROVER if whole_prover else 0) | (_lib.RV_COMPILE_KEEP_WIRES if keep_wires else 0) | \
-            (_lib.RV_COMPILE_DEVICE_Z64 if device_z64 else 0)
+            (_lib.RV_COMPILE_DEVICE_Z64 if device_z64 else 0) | (_lib.RV_COMPILE_DEVICE_B2A if device_b2a else 0)
         _lib.check(_lib.lib().rv_circuit_compile_device(self.ctx.handle, C.c_void_p(d_ops), C.c_size_t(n_ops),
                                                         C.c_size_t(self.wire_counts[0]), C.c_size_t(self.wire_counts[1]),
                                                         C.c_uint32(flags), C.byref(self.handle)))

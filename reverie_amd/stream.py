@@ -17,7 +17,9 @@ Every class and one-shot function here takes `device_compile` (default False): t
 GPU (RV_COMPILE_DEVICE: rv_stream_set_compile_flags / rv_eval_stream_set_compile_flags) instead of on host worker threads; pieces with
 Z64, B2A or SizeHint ops, and pieces with an error in them, are still compiled on the host.  Proofs, answers and values are the same.
 With `device_z64=True` as well (RV_COMPILE_DEVICE_Z64; a ValueError without `device_compile`) Z64 and mixed pieces are compiled on the
-GPU too: only pieces with a B2A op or an error in them are left to the host.
+GPU too: only pieces with a B2A op or an error in them are left to the host.  With `device_b2a=True` on top of both
+(RV_COMPILE_DEVICE_B2A; a ValueError without the other two) pieces with B2A ops are compiled on the GPU as well: every piece goes to
+the device compiler, and only one with an error in it comes back to the host compiler, which reports it.
 
 Wherever an op list is taken -- every `feed`, every one-shot function -- it may also be a torch tensor in GPU memory holding packed
 rv_op records (what `Circuit.from_device_ops` accepts; on the context's device, or it is an error).  The ops are then fed from where
@@ -52,33 +54,36 @@ def _feed(handle, ctx: Context, ops, g, n_g: int, z, n_z: int, entry: str = "rv_
     _lib.check(getattr(_lib.lib(), entry)(handle, _ptr(ops), C.c_size_t(len(ops)), _ptr(g), C.c_size_t(n_g), _ptr(z), C.c_size_t(n_z)))
 
 
-def _check_device_z64(device_compile: bool, device_z64: bool):
+def _check_device_z64(device_compile: bool, device_z64: bool, device_b2a: bool = False):
     if device_z64 and not device_compile:
         raise ValueError("device_z64=True needs device_compile=True")
+    if device_b2a and not (device_compile and device_z64):
+        raise ValueError("device_b2a=True needs device_compile=True and device_z64=True")
 
 
-def _device_flags(device_compile: bool, device_z64: bool) -> int:
-    _check_device_z64(device_compile, device_z64)
-    return (_lib.RV_COMPILE_DEVICE if device_compile else 0) | (_lib.RV_COMPILE_DEVICE_Z64 if device_z64 else 0)
+def _device_flags(device_compile: bool, device_z64: bool, device_b2a: bool = False) -> int:
+    _check_device_z64(device_compile, device_z64, device_b2a)
+    return (_lib.RV_COMPILE_DEVICE if device_compile else 0) | (_lib.RV_COMPILE_DEVICE_Z64 if device_z64 else 0) | \
+        (_lib.RV_COMPILE_DEVICE_B2A if device_b2a else 0)
 
 
-def _set_device_compile(handle, device_compile: bool, device_z64: bool = False, setter: str = "rv_stream_set_compile_flags"):
+def _set_device_compile(handle, device_compile: bool, device_z64: bool = False, device_b2a: bool = False, setter: str = "rv_stream_set_compile_flags"):
     """a new stream follows its context's flags; device_compile=True asks for the device compiler whatever they are (device_z64: for
-    Z64 and mixed pieces too)"""
+    Z64 and mixed pieces too; device_b2a: for pieces with B2A ops too, that is for every piece)"""
     if device_compile:
-        _lib.check(getattr(_lib.lib(), setter)(handle, C.c_uint32(_device_flags(device_compile, device_z64))))
+        _lib.check(getattr(_lib.lib(), setter)(handle, C.c_uint32(_device_flags(device_compile, device_z64, device_b2a))))
 
 
 @contextlib.contextmanager
-def _ctx_device_compile(ctx: Context, device_compile: bool, device_z64: bool = False):
+def _ctx_device_compile(ctx: Context, device_compile: bool, device_z64: bool = False, device_b2a: bool = False):
     """The one-shot calls of the library follow their context's compile flags, so device_compile=True sets RV_COMPILE_DEVICE (and
-    device_z64=True RV_COMPILE_DEVICE_Z64) on `ctx`
+    device_z64=True RV_COMPILE_DEVICE_Z64, device_b2a=True RV_COMPILE_DEVICE_B2A) on `ctx`
     for the duration of the call and puts back what Context.set_compile_flags last set.  The context is shared state: another
     thread's cold rv_prove_ops / rv_verify_ops compiles on the same context meanwhile use the device compiler too (same results),
     and flags set through the C API behind Context's back are not seen here.  A caller who minds either sets the flag on the
     context once, or uses the Streaming* classes, whose flag lives on the stream handle."""
     before = getattr(ctx, "compile_flags", 0)
-    want = before | _device_flags(device_compile, device_z64)
+    want = before | _device_flags(device_compile, device_z64, device_b2a)
     if want != before:
         ctx.set_compile_flags(want)
         try:
@@ -91,8 +96,8 @@ def _ctx_device_compile(ctx: Context, device_compile: bool, device_z64: bool = F
 
 class StreamingProver:
     def __init__(self, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
-                 device_compile: bool = False, device_z64: bool = False):
-        _check_device_z64(device_compile, device_z64)
+                 device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False):
+        _check_device_z64(device_compile, device_z64, device_b2a)
         self.ctx = ctx or Context.default()
         self.handle = C.c_void_p()
         s = None
@@ -101,7 +106,7 @@ class StreamingProver:
                                      else np.asarray(seeds, dtype=np.uint8)).reshape(TOTAL_REPS, 16)
         _lib.check(_lib.lib().rv_stream_begin(self.ctx.handle, C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])), _ptr(s),
                                               C.c_size_t(max_chunk_ops), C.byref(self.handle)))
-        _set_device_compile(self.handle, device_compile, device_z64)
+        _set_device_compile(self.handle, device_compile, device_z64, device_b2a)
 
     def feed(self, ops, wit_gf2: Sequence[int] = (), wit_z64: Sequence[int] = ()):
         g = np.ascontiguousarray(np.asarray(wit_gf2, dtype=np.uint8))
@@ -143,13 +148,13 @@ class StreamingProver:
 
 
 def prove_streaming(ops, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
-                    ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False) -> Tuple[Proof, dict]:
+                    ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False) -> Tuple[Proof, dict]:
     """rv_prove_streaming: both passes over an op array in host memory -> (Proof, stream info).  A torch GPU tensor of ops: the same
     through rv_stream_begin / rv_stream_feed_device / rv_stream_finish."""
-    _check_device_z64(device_compile, device_z64)
+    _check_device_z64(device_compile, device_z64, device_b2a)
     ctx = _ops_ctx(ops, ctx)
     if _is_device_ops(ops):
-        sp = StreamingProver(wire_counts, seeds, max_chunk_ops, ctx, device_compile, device_z64)
+        sp = StreamingProver(wire_counts, seeds, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
             sp.same_cuts()  # (the same tensor, cut by the same rule in both passes)
             sp.feed(ops, wit_gf2, wit_z64)
@@ -166,7 +171,7 @@ def prove_streaming(ops, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=N
         s = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint8)).reshape(TOTAL_REPS, 16)
     out, n = C.c_void_p(), C.c_size_t()
     si = _lib.StreamInfo()
-    with _ctx_device_compile(ctx, device_compile, device_z64):
+    with _ctx_device_compile(ctx, device_compile, device_z64, device_b2a):
         _lib.check(_lib.lib().rv_prove_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(int(wire_counts[0])),
                                                  C.c_size_t(int(wire_counts[1])), _ptr(g), C.c_size_t(len(g)), _ptr(z), C.c_size_t(len(z)), _ptr(s),
                                                  C.c_size_t(max_chunk_ops), C.byref(out), C.byref(n), C.byref(si)))
@@ -182,15 +187,15 @@ class StreamingVerifier:
     """
 
     def __init__(self, wire_counts: Tuple[int, int], proof, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
-                 device_compile: bool = False, device_z64: bool = False):
-        _check_device_z64(device_compile, device_z64)
+                 device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False):
+        _check_device_z64(device_compile, device_z64, device_b2a)
         self.ctx = ctx or Context.default()
         self.handle = C.c_void_p()
         self._proof = proof if isinstance(proof, Proof) else Proof(bytes(proof))  # (kept alive: the stream reads it until finish)
         buf, n = self._proof._buffer()
         _lib.check(_lib.lib().rv_stream_verify_begin(self.ctx.handle, C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])), buf,
                                                      C.c_size_t(n), C.c_size_t(max_chunk_ops), C.byref(self.handle)))
-        _set_device_compile(self.handle, device_compile, device_z64)
+        _set_device_compile(self.handle, device_compile, device_z64, device_b2a)
 
     def feed(self, ops):
         _feed(self.handle, self.ctx, ops, None, 0, None, 0)
@@ -211,13 +216,13 @@ class StreamingVerifier:
 
 
 def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = True, max_chunk_ops: int = 0,
-                     ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False) -> Tuple[bool, dict]:
+                     ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False) -> Tuple[bool, dict]:
     """rv_verify_streaming: one pass over an op array in host memory -> (ok, stream info).  A torch GPU tensor of ops: the same through
     rv_stream_verify_begin / rv_stream_feed_device / rv_stream_verify_finish."""
-    _check_device_z64(device_compile, device_z64)
+    _check_device_z64(device_compile, device_z64, device_b2a)
     ctx = _ops_ctx(ops, ctx)
     if _is_device_ops(ops):
-        sv = StreamingVerifier(wire_counts, proof, max_chunk_ops, ctx, device_compile, device_z64)
+        sv = StreamingVerifier(wire_counts, proof, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
             sv.feed(ops)
             return sv.finish(strict), sv.info
@@ -228,7 +233,7 @@ def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = Tr
     buf, n = pr._buffer()
     ok = C.c_int()
     si = _lib.StreamInfo()
-    with _ctx_device_compile(ctx, device_compile, device_z64):
+    with _ctx_device_compile(ctx, device_compile, device_z64, device_b2a):
         _lib.check(_lib.lib().rv_verify_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])),
                                                   buf, C.c_size_t(n), C.c_uint32(0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT), C.c_size_t(max_chunk_ops),
                                                   C.byref(ok), C.byref(si)))
@@ -271,8 +276,8 @@ class StreamingBatchProver:
     """
 
     def __init__(self, wire_counts: Tuple[int, int], batch: int, seeds=None, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
-                 device_compile: bool = False, device_z64: bool = False):
-        _check_device_z64(device_compile, device_z64)
+                 device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False):
+        _check_device_z64(device_compile, device_z64, device_b2a)
         self.ctx = ctx or Context.default()
         self.batch = int(batch)
         self.handle = C.c_void_p()
@@ -281,7 +286,7 @@ class StreamingBatchProver:
         s = _batch_seeds(seeds, self.batch)
         _lib.check(_lib.lib().rv_stream_begin_batch(self.ctx.handle, int(wire_counts[0]), int(wire_counts[1]), self.batch, _ptr(s),
                                                     int(max_chunk_ops), C.byref(self.handle)))
-        _set_device_compile(self.handle, device_compile, device_z64)
+        _set_device_compile(self.handle, device_compile, device_z64, device_b2a)
 
     def feed(self, ops, wits_gf2=(), wits_z64=()):
         g = _eval_wits(wits_gf2, self.batch, np.uint8)
@@ -312,10 +317,10 @@ class StreamingBatchProver:
 
 
 def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
-                          ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False) -> "list[Proof]":
+                          ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False) -> "list[Proof]":
     """rv_prove_streaming_batch: both passes over an op array in host memory for the witnesses wits_gf2 [B][n] / wits_z64
     [B][m] (B from whichever of the two is 2-D; the other may be []); seeds [B][256][16] or None.  `info` (a dict, optional) receives the stream's figures."""
-    _check_device_z64(device_compile, device_z64)
+    _check_device_z64(device_compile, device_z64, device_b2a)
     ctx = _ops_ctx(ops, ctx)
     g0 = np.asarray(wits_gf2, dtype=np.uint8)
     z0 = np.asarray(wits_z64, dtype=np.uint64)
@@ -326,7 +331,7 @@ def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int],
     else:
         raise ValueError("wits_gf2 or wits_z64 must be [batch][n]")
     if _is_device_ops(ops):  # (a torch GPU tensor: begin / rv_stream_feed_device twice / finish)
-        sp = StreamingBatchProver(wire_counts, batch, seeds, max_chunk_ops, ctx, device_compile, device_z64)
+        sp = StreamingBatchProver(wire_counts, batch, seeds, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
             sp.same_cuts()
             sp.feed(ops, g0, z0)
@@ -345,7 +350,7 @@ def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int],
     outs = (C.c_void_p * batch)()
     lens = (C.c_size_t * batch)()
     si = _lib.StreamInfo()
-    with _ctx_device_compile(ctx, device_compile, device_z64):
+    with _ctx_device_compile(ctx, device_compile, device_z64, device_b2a):
         _lib.check(_lib.lib().rv_prove_streaming_batch(ctx.handle, _ptr(ops), len(ops), int(wire_counts[0]), int(wire_counts[1]), batch, _ptr(g),
                                                        g.shape[1], _ptr(z), z.shape[1], _ptr(s), int(max_chunk_ops), outs, lens, C.byref(si)))
     if info is not None:
@@ -362,8 +367,8 @@ class StreamingBatchVerifier:
     """
 
     def __init__(self, wire_counts: Tuple[int, int], proofs, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
-                 device_compile: bool = False, device_z64: bool = False):
-        _check_device_z64(device_compile, device_z64)
+                 device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False):
+        _check_device_z64(device_compile, device_z64, device_b2a)
         self.ctx = ctx or Context.default()
         self.handle = C.c_void_p()
         self.batch = len(proofs)
@@ -372,7 +377,7 @@ class StreamingBatchVerifier:
         self._keep, ptrs, lens = _proof_array(proofs)  # (kept alive: the stream reads them until finish)
         _lib.check(_lib.lib().rv_stream_verify_begin_batch(self.ctx.handle, int(wire_counts[0]), int(wire_counts[1]), self.batch, ptrs, lens,
                                                            int(max_chunk_ops), C.byref(self.handle)))
-        _set_device_compile(self.handle, device_compile, device_z64)
+        _set_device_compile(self.handle, device_compile, device_z64, device_b2a)
 
     feed = StreamingVerifier.feed
 
@@ -392,15 +397,15 @@ class StreamingBatchVerifier:
 
 
 def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bool = True, max_chunk_ops: int = 0,
-                           ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False) -> "list[bool]":
+                           ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False) -> "list[bool]":
     """rv_verify_streaming_batch: one pass over an op array in host memory for every proof -> one bool per proof"""
-    _check_device_z64(device_compile, device_z64)
+    _check_device_z64(device_compile, device_z64, device_b2a)
     ctx = _ops_ctx(ops, ctx)
     n = len(proofs)
     if n == 0:
         return []
     if _is_device_ops(ops):  # (a torch GPU tensor: begin / rv_stream_feed_device / finish)
-        sv = StreamingBatchVerifier(wire_counts, proofs, max_chunk_ops, ctx, device_compile, device_z64)
+        sv = StreamingBatchVerifier(wire_counts, proofs, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
             sv.feed(ops)
             oks = sv.finish(strict)
@@ -413,7 +418,7 @@ def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bo
     keep, ptrs, lens = _proof_array(proofs)
     ok = (C.c_int * n)()
     si = _lib.StreamInfo()
-    with _ctx_device_compile(ctx, device_compile, device_z64):
+    with _ctx_device_compile(ctx, device_compile, device_z64, device_b2a):
         _lib.check(_lib.lib().rv_verify_streaming_batch(ctx.handle, _ptr(ops), len(ops), int(wire_counts[0]), int(wire_counts[1]), n, ptrs, lens,
                                                         0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT, int(max_chunk_ops), ok, C.byref(si)))
     del keep
@@ -449,15 +454,15 @@ class StreamingEvaluator:
     Device memory is the wire store (wire counts x batch) plus one chunk of at most max_chunk_ops ops (0 = 2^18)."""
 
     def __init__(self, wire_counts: Tuple[int, int], batch: int = 1, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
-                 device_compile: bool = False, device_z64: bool = False):
-        _check_device_z64(device_compile, device_z64)
+                 device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False):
+        _check_device_z64(device_compile, device_z64, device_b2a)
         self.ctx = ctx or Context.default()
         self.wire_counts = (int(wire_counts[0]), int(wire_counts[1]))
         self.batch = int(batch)
         self.handle = C.c_void_p()
         _lib.check(_lib.lib().rv_eval_stream_begin(self.ctx.handle, C.c_size_t(self.wire_counts[0]), C.c_size_t(self.wire_counts[1]),
                                                    C.c_size_t(self.batch), C.c_size_t(max_chunk_ops), C.byref(self.handle)))
-        _set_device_compile(self.handle, device_compile, device_z64, "rv_eval_stream_set_compile_flags")
+        _set_device_compile(self.handle, device_compile, device_z64, device_b2a, "rv_eval_stream_set_compile_flags")
 
     def feed(self, ops, wits_gf2=(), wits_z64=()):
         g = _eval_wits(wits_gf2, self.batch, np.uint8)
@@ -491,16 +496,16 @@ class StreamingEvaluator:
 
 
 def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], max_chunk_ops: int = 0, values: bool = False,
-                       ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False) -> Evaluation:
+                       ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False) -> Evaluation:
     """rv_evaluate_streaming: one op array in host memory, evaluated chunk by chunk with bounded device memory.  wits_gf2 /
     wits_z64: [B][n] (1-D for one witness; the batch is len(wits_gf2)).  Returns the array-shaped Evaluation of
     Circuit.evaluate_batch; `info` (a dict, optional) receives the stream's figures."""
-    _check_device_z64(device_compile, device_z64)
+    _check_device_z64(device_compile, device_z64, device_b2a)
     ctx = _ops_ctx(ops, ctx)
     g0 = np.asarray(wits_gf2, dtype=np.uint8)
     batch = g0.shape[0] if g0.ndim == 2 else 1
     if _is_device_ops(ops):  # (a torch GPU tensor: begin / rv_eval_stream_feed_device / finish)
-        se = StreamingEvaluator(wire_counts, batch, max_chunk_ops, ctx, device_compile, device_z64)
+        se = StreamingEvaluator(wire_counts, batch, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
             se.feed(ops, g0, wits_z64)
             r = se.finish(values)
@@ -517,7 +522,7 @@ def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], ma
     gv = np.zeros((batch, wc[1]), np.uint8) if values else None
     zv = np.zeros((batch, wc[0]), np.uint64) if values else None
     si = _lib.EvalStreamInfo()
-    with _ctx_device_compile(ctx, device_compile, device_z64):
+    with _ctx_device_compile(ctx, device_compile, device_z64, device_b2a):
         _lib.check(_lib.lib().rv_evaluate_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(wc[0]), C.c_size_t(wc[1]),
                                                     C.c_size_t(batch), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z), C.c_size_t(z.shape[1]),
                                                     C.c_size_t(max_chunk_ops), _ptr(gv), _ptr(zv), st.ctypes.data_as(C.c_void_p), C.byref(si)))

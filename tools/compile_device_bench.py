@@ -6,7 +6,10 @@ Medians of `reps` runs after a warm-up, with [min, max] beside them.  --whole-pr
 on both compilers (the lazy-sum form).  --compiler device-z64: instead config 5 (circuits.layered_z64) and a half-and-half mixture of
 configs 4 and 5 at about 10^6 ops each, host compile + upload against the device compile under RV_COMPILE_DEVICE |
 RV_COMPILE_DEVICE_Z64, with the laps (z64: the split of the list and the Z64 ops' steps; the others: the GF(2) ops').
-usage: python tools/compile_device_bench.py [--whole-prover] [--compiler device|device-z64] [reps]"""
+--compiler device-b2a: that mixture with a band of B2A_OPS (default 4096) B2A ops behind it (tools/b2a_workload.py), host compile
+against the device compile under RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64 | RV_COMPILE_DEVICE_B2A; MIX_MULS (default 500000) sizes
+the mixture.  The host compiler of such a program is the sequential one.
+usage: python tools/compile_device_bench.py [--whole-prover] [--compiler device|device-z64|device-b2a] [reps]"""
 import ctypes as C
 import json
 import os
@@ -27,10 +30,10 @@ args = [a for a in sys.argv[1:] if a != "--whole-prover"]
 COMPILER = "device"
 if "--compiler" in args:
     COMPILER = args[args.index("--compiler") + 1]
-    assert COMPILER in ("device", "device-z64"), COMPILER
+    assert COMPILER in ("device", "device-z64", "device-b2a"), COMPILER
     del args[args.index("--compiler"):args.index("--compiler") + 2]
 WP = _lib.RV_COMPILE_WHOLE_PROVER if "--whole-prover" in sys.argv[1:] else 0
-DEV = _lib.RV_COMPILE_DEVICE | (_lib.RV_COMPILE_DEVICE_Z64 if COMPILER == "device-z64" else 0)
+DEV = _lib.RV_COMPILE_DEVICE | (_lib.RV_COMPILE_DEVICE_Z64 if COMPILER != "device" else 0) | (_lib.RV_COMPILE_DEVICE_B2A if COMPILER == "device-b2a" else 0)
 reps = int(args[0]) if args else 3
 ctx = reverie_amd.Context(0)
 seeds = np.arange(4096, dtype=np.uint32).astype(np.uint8).reshape(256, 16)
@@ -88,8 +91,16 @@ def z64_rows():
     yield "mix_config4_config5", mix, (wc5[0], wc4[1])
 
 
-if COMPILER == "device-z64":
-    for name, prog, wc in z64_rows():
+def b2a_rows():
+    import b2a_workload
+
+    n_b2a = int(os.environ.get("B2A_OPS", "4096"))
+    prog, _, _, wc = b2a_workload.mixed_b2a(n_b2a, int(os.environ.get("MIX_MULS", "500000")))
+    yield "mix_config4_config5_b2a%d" % n_b2a, prog, wc
+
+
+if COMPILER != "device":
+    for name, prog, wc in (z64_rows() if COMPILER == "device-z64" else b2a_rows()):
         path, diff = C.c_int(), C.c_int()
         assert L.rv_hook_compile_compare_device(ctx.handle, prog.ctypes.data_as(C.c_void_p), C.c_size_t(len(prog)), C.c_size_t(wc[0]),
                                                 C.c_size_t(wc[1]), C.c_uint32(WP | DEV), C.byref(path), C.byref(diff)) == 0

@@ -200,6 +200,31 @@ def z64_compiler_rows(ctx, seeds, runs=5, n_mul=1_000_000, chunk_ops=1 << 16):
                 os.environ.pop(k, None)
 
 
+def b2a_compiler_rows(ctx, seeds, runs=5, n_b2a=4096, n_mul=500_000, chunk_ops=1 << 16):
+    """the mixed workload with a band of B2A ops (tools/b2a_workload.py) through prove_streaming at the context's compile flags, as
+    z64_compiler_rows"""
+    import b2a_workload
+    import reverie_amd
+    from reverie_amd import _lib
+    from reverie_amd.stream import prove_streaming
+
+    prog, w2, w64, wc = b2a_workload.mixed_b2a(n_b2a, n_mul, recycle=True)
+    circ = reverie_amd.Circuit(prog, wc, ctx)
+    want = bytes(reverie_amd.Proof.new(circ, w2, w64, seeds=seeds))
+    circ.close()
+    for env in ({}, {"RV_STREAM_THREADS": "1"}):
+        os.environ.update(env)
+        try:
+            before = int(_lib.lib().rv_hook_stream_device_chunks())
+            t, out = _timed(lambda: prove_streaming(prog, w2, w64, wc, seeds=seeds, max_chunk_ops=chunk_ops, ctx=ctx), runs)
+            yield dict(t, row="prove_streaming mixture + %d B2A" % n_b2a + "".join(" %s=%s" % kv for kv in env.items()), n_ops=int(len(prog)),
+                       chunk_ops=chunk_ops, compile_flags=int(getattr(ctx, "compile_flags", 0)), ok=bytes(out[0]) == want,
+                       device_chunks_per_call=(int(_lib.lib().rv_hook_stream_device_chunks()) - before) // (runs + 1))
+        finally:
+            for k in env:
+                os.environ.pop(k, None)
+
+
 def z64_record(ctx, seeds, n_mul=1_000_000, chunk_ops=1 << 16):
     import circuits
     import reverie_amd
@@ -236,8 +261,12 @@ if __name__ == "__main__":
     import reverie_amd
 
     ap = argparse.ArgumentParser()
-    ap.add_argument("--compiler", default="host", choices=["host", "device", "device-z64"],
-                    help="where the streams' pieces are compiled (device: RV_COMPILE_DEVICE; device-z64: with RV_COMPILE_DEVICE_Z64, Z64 and mixed pieces too)")
+    ap.add_argument("--compiler", default="host", choices=["host", "device", "device-z64", "device-b2a"],
+                    help="where the streams' pieces are compiled (device: RV_COMPILE_DEVICE; device-z64: with RV_COMPILE_DEVICE_Z64, Z64 and mixed pieces too; "
+                         "device-b2a: with RV_COMPILE_DEVICE_B2A as well, every piece)")
+    ap.add_argument("--b2a", action="store_true",
+                    help="the config 4 / config 5 mixture with a band of B2A_OPS (default 4096) B2A ops only: prove_streaming at the chosen compiler, "
+                         "default threads and RV_STREAM_THREADS=1")
     ap.add_argument("--z64", action="store_true", help="config 5 only: prove_streaming at the chosen compiler, default threads and RV_STREAM_THREADS=1")
     ap.add_argument("--compare", action="store_true", help="config 4 with both compilers, every streaming entry point")
     ap.add_argument("--ops", default="host", choices=["host", "device"],
@@ -249,8 +278,13 @@ if __name__ == "__main__":
     if args.compiler != "host":  # (the one-shot calls follow the context's flags)
         from reverie_amd import _lib
 
-        ctx.set_compile_flags(_lib.RV_COMPILE_DEVICE | (_lib.RV_COMPILE_DEVICE_Z64 if args.compiler == "device-z64" else 0))
+        ctx.set_compile_flags(_lib.RV_COMPILE_DEVICE | (_lib.RV_COMPILE_DEVICE_Z64 if args.compiler != "device" else 0) |
+                              (_lib.RV_COMPILE_DEVICE_B2A if args.compiler == "device-b2a" else 0))
     seeds = np.random.default_rng(0x5EED).integers(0, 256, (256, 16), dtype=np.uint8)
+    if args.b2a:
+        for rec in b2a_compiler_rows(ctx, seeds, runs=args.runs, n_b2a=int(os.environ.get("B2A_OPS", "4096")), n_mul=int(os.environ.get("MIX_MULS", "500000"))):
+            print(json.dumps(rec), flush=True)
+        sys.exit(0)
     if args.z64:
         for rec in z64_compiler_rows(ctx, seeds, runs=args.runs, n_mul=int(os.environ.get("Z64_MULS", "1000000"))):
             print(json.dumps(rec), flush=True)
