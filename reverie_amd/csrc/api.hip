@@ -766,9 +766,6 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
                                   rv_circuit** out, const rv_op* d_ops = nullptr);
 static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged = false);
 
-// the three bits that choose the compiler: RV_COMPILE_DEVICE_Z64 widens RV_COMPILE_DEVICE's scope and means nothing without it,
-// RV_COMPILE_DEVICE_B2A widens RV_COMPILE_DEVICE_Z64's in the same way
-constexpr uint32_t RV_COMPILE_DEVICE_BITS = RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64 | RV_COMPILE_DEVICE_B2A;
 // nullptr when the bits go together, else what is missing
 static const char* device_bits_missing(uint32_t flags) {
     if ((flags & RV_COMPILE_DEVICE_B2A) && (flags & (RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64)) != (RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64)) {
@@ -836,8 +833,10 @@ static int compile_on_device(rv_ctx* ctx, const rv_op* d_ops, size_t n_ops, size
                              DevCompileKeep* keep) {
     const int k = ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0;
     DevCompileLaps laps;
-    const int rc = compile_ops_device(ctx->stream, ctx_dev_allocator(ctx), d_ops, n_ops, z64_wires, gf2_wires, (flags & RV_COMPILE_KEEP_WIRES) != 0, k,
-                                      cc, keep, &laps, nullptr, (flags & RV_COMPILE_DEVICE_Z64) != 0, (flags & RV_COMPILE_DEVICE_B2A) != 0);
+    DevCompileRequest req;
+    req.d_ops = d_ops, req.n_ops = n_ops, req.z64_wires = z64_wires, req.gf2_wires = gf2_wires;
+    req.keep_wires = (flags & RV_COMPILE_KEEP_WIRES) != 0, req.force_lazy_k = k, req.device_bits = flags & RV_COMPILE_DEVICE_BITS;
+    const int rc = compile_ops_device(ctx->stream, ctx_dev_allocator(ctx), req, cc, keep, &laps);
     if (rc == RV_E_DEVICE) g_last_error = "device compile: HIP error";
     if (rc == RV_E_NOMEM) g_last_error = "device compile: out of device memory";
     if (rc == RV_OK) {
@@ -887,8 +886,10 @@ static int compile_chunk_on_device(rv_ctx* ctx, const rv_op* ops, const rv_op* d
     if (up && up_bytes) up_bytes->fetch_add(n_ops * sizeof(rv_op), std::memory_order_relaxed);
     const auto t1 = std::chrono::steady_clock::now();
     DevCompileLaps dl;
-    rc = compile_ops_device(ctx->stream, ctx_dev_allocator(ctx), d_ops ? d_ops : up, n_ops, z64_wires, gf2_wires, false, 0, cc, keep, laps ? &dl : nullptr,
-                            &cs, (compile_flags & RV_COMPILE_DEVICE_Z64) != 0, (compile_flags & RV_COMPILE_DEVICE_B2A) != 0);
+    DevCompileRequest req;
+    req.d_ops = d_ops ? d_ops : up, req.n_ops = n_ops, req.z64_wires = z64_wires, req.gf2_wires = gf2_wires;
+    req.chunk = &cs, req.device_bits = compile_flags & RV_COMPILE_DEVICE_BITS;
+    rc = compile_ops_device(ctx->stream, ctx_dev_allocator(ctx), req, cc, keep, laps ? &dl : nullptr);
     ctx->release(up);  // (the device compile synchronised the stream)
     if (rc == RV_E_DEVICE) g_last_error = "device compile of a stream's piece: HIP error";
     if (rc == RV_E_NOMEM) g_last_error = "device compile of a stream's piece: out of device memory";

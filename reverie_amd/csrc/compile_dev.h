@@ -6,13 +6,13 @@
 // forced lazy_k, no RV_LAZY_K in the environment, at most 2^16 topological rounds.  Everything else, every op-list error included, is
 // RV_COMPILE_FALLBACK: the caller runs compile_ops, which returns the canonical result or error code.
 //
-// admit_z64 (RV_COMPILE_DEVICE_Z64): the list may also hold Z64 ops (all ten opcodes) and SizeHint ops that grow neither wire count.
+// RV_COMPILE_DEVICE_Z64 in device_bits: the list may also hold Z64 ops (all ten opcodes) and SizeHint ops that grow neither wire count.
 // The GF(2) ops of such a list go through the same pipeline, in either form; every Z64 op becomes one Gate64 at one level above its
 // deepest operand, and the two domains share the level numbering (the deeper one's count; the other's tables have empty trailing
 // levels).  Still RV_COMPILE_FALLBACK: a B2A op, a SizeHint that grows a wire count, RV_COMPILE_KEEP_WIRES, RV_LAZY_K, an op-list
 // error in either domain, more than 2^16 rounds in either domain, and a plain whole-program compile for which lazy_forms_pay holds.
 //
-// admit_b2a (RV_COMPILE_DEVICE_B2A; with admit_z64 only): the list may also hold B2A ops, whole or as a chunk, in either form.  Where
+// RV_COMPILE_DEVICE_B2A in device_bits (with RV_COMPILE_DEVICE_Z64 only): the list may also hold B2A ops, whole or as a chunk, in either form.  Where
 // the list is split by domain a B2A contributes its 442 SSA-producing steps to the GF(2) list as private ops, in Builder::g_* call
 // order (run_pass, case RV_DOM_B2A: 64 Random, Mul and Xor, 62 x {Xor, Xor, Mul, Xor, Xor}, two Xor, 64 reconstructions), and one op
 // to the Z64 list.  The private ops write no wire; their operands inside the expansion are fixed places, and only the 64 reads of
@@ -51,7 +51,7 @@ struct DevAlloc {
 struct DevCompileLaps {
     float classify = 0, writers = 0, levels = 0, tables = 0, download = 0;
     uint32_t rounds = 0;  // topological rounds launched
-    float z64 = 0;        // admit_z64, a list with Z64 ops: the split and the Z64 ops' steps (the five above are then the GF(2) ops')
+    float z64 = 0;        // RV_COMPILE_DEVICE_Z64, a list with Z64 ops: the split and the Z64 ops' steps (the five above are then the GF(2) ops')
 };
 
 // The device arrays a device compile leaves for the circuit (null: freed before the call returns, nothing is kept)
@@ -59,16 +59,29 @@ struct DevCompileKeep {
     Gate* d_gates = nullptr;
     uint32_t* d_rec_rows = nullptr;
     uint32_t* d_in_rows = nullptr;
-    // a list with Z64 ops (admit_z64; null otherwise)
+    // a list with Z64 ops (RV_COMPILE_DEVICE_Z64; null otherwise)
     Gate64* d_gates64 = nullptr;
     uint64_t* d_rec_offs64 = nullptr;
     uint64_t* d_in_offs64 = nullptr;
 };
 
+// the three bits that choose the compiler: RV_COMPILE_DEVICE_Z64 widens RV_COMPILE_DEVICE's scope and means nothing without it,
+// RV_COMPILE_DEVICE_B2A widens RV_COMPILE_DEVICE_Z64's in the same way
+constexpr uint32_t RV_COMPILE_DEVICE_BITS = RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64 | RV_COMPILE_DEVICE_B2A;
+
+struct DevCompileRequest {
+    const rv_op* d_ops = nullptr;  // n_ops packed rv_op records in device memory (read only)
+    size_t n_ops = 0;
+    size_t z64_wires = 0, gf2_wires = 0;
+    bool keep_wires = false;
+    int force_lazy_k = 0;
+    const ChunkStart* chunk = nullptr;
+    uint32_t device_bits = 0;  // the caller's compile flags & RV_COMPILE_DEVICE_BITS
+};
+
 // RV_OK (out filled; compile_us / upload_us / device_bytes / scratch_bytes left zero), RV_COMPILE_FALLBACK, or RV_E_NOMEM /
-// RV_E_DEVICE.  d_ops: n_ops packed rv_op records in device memory (read only).  Runs on `st`; synchronises it before returning.
-int compile_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires,
-                       bool keep_wires, int force_lazy_k, Compiled& out, DevCompileKeep* keep, DevCompileLaps* laps = nullptr,
-                       const ChunkStart* chunk = nullptr, bool admit_z64 = false, bool admit_b2a = false);
+// RV_E_DEVICE.  Runs on `st`; synchronises it before returning.
+int compile_ops_device(hipStream_t st, const DevAlloc& A, const DevCompileRequest& req, Compiled& out, DevCompileKeep* keep,
+                       DevCompileLaps* laps = nullptr);
 
 }  // namespace rv
