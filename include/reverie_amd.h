@@ -363,6 +363,31 @@ int rv_evaluate_streaming(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z6
 int rv_verify(rv_ctx *ctx, const rv_circuit *c, const uint8_t *proof, size_t proof_len, int *ok);
 int rv_verify_ex(rv_ctx *ctx, const rv_circuit *c, const uint8_t *proof, size_t proof_len, uint32_t flags, int *ok);
 
+/* ---- Proof::verify on proof bytes in device memory ------------------------------------------
+ * rv_verify_device: d_proof is proof_len bytes of bincode(Proof) in the memory of the context's device (e.g. a torch tensor); the
+ * caller keeps ownership and must have finished writing it (rv_circuit_compile_device's conventions).  flags: as rv_verify_ex.
+ * DEFINITION: the return code and *ok are exactly those of rv_verify_ex(ctx, c, a host copy of the same bytes, proof_len, flags, ok),
+ * for every byte string -- truncated, wrong repetition counts, altered vector lengths, trailing bytes.
+ * rv_verify_sections_device: d_sections is what rv_prove_device, rv_shard_open_self or rv_shard_open_into wrote for a shard of all
+ * 256 repetitions -- [gf2 online | gf2 preprocessing | z64 online | z64 preprocessing], contiguous, lens[4] -- and comm (host
+ * memory) the proof's commitment.  DEFINITION: the return code and *ok are those of rv_verify_ex on the byte string
+ *     comm | LE64(40) | section 0 | LE64(216) | section 1 | LE64(40) | section 2 | LE64(216) | section 3
+ * (what rv_assemble_proof frames from the same sections).
+ * Both: RV_E_ARG for a pointer that is not 16-byte aligned, that is host memory, or memory of another device.  NO PADDING is asked
+ * of the caller: a well-framed proof is read inside [d_proof, d_proof + proof_len) only.  (The GF(2) unpack kernel's aligned
+ * 32-bit loads reach up to 3 bytes in front of a vector and 3 behind it; at least 137 bytes of the record lie in front of every
+ * vector, and 8 or more bytes of the proof behind it -- the next length field, or the count and the preprocessing records that
+ * follow every online section.  The Z64 unpack kernel loads bytes of the vector only.)
+ * How: one small kernel walks the framing (at most 80 records; a repetition count other than 40 / 216 stops it at once), the host
+ * reads back its status with comm and the 80 omit bytes, a second kernel builds the verifier's slot arrays in device memory and the
+ * verifier runs on them with the vectors read in place: no proof byte crosses to the host and rv_hook_verify_proof_bytes does not
+ * move.  Bytes the walk refuses (they run out; a count is not 40 / 216; a section does not end where its records do; a group's
+ * records break the rules rv_verify_ex answers RV_E_PROOF_MALFORMED for) are copied to the host and handed to rv_verify_ex -- and
+ * only those: a well-framed proof whose records pass those rules takes the device path whatever its vector lengths. */
+int rv_verify_device(rv_ctx *ctx, const rv_circuit *c, const uint8_t *d_proof, size_t proof_len, uint32_t flags, int *ok);
+int rv_verify_sections_device(rv_ctx *ctx, const rv_circuit *c, const uint8_t comm[RV_HASH_SIZE], const uint8_t *d_sections,
+                              const size_t lens[4], uint32_t flags, int *ok);
+
 void rv_free(void *p);
 
 /* ---- streaming prover --------------------------------------------------------
@@ -789,6 +814,16 @@ uint64_t rv_hook_verify_vc_count(void);
 /* Running total of the proof bytes this process's shard verifiers (rv_verify_shard*, rv_verify_shard_groups, hence rv_verify,
  * rv_verify_sharded) copied host-to-device: the records of the online groups they verified, both domains. */
 uint64_t rv_hook_verify_proof_bytes(void);
+/* rv_verify_device / rv_verify_sections_device calls of this process that took out[0] = the device path, out[1] = the host fallback
+ * (calls refused with RV_E_ARG count as neither). */
+int rv_hook_verify_device_paths(uint64_t out[2]);
+/* The framing walk of those two entry points, run on the host (no device): bytes[0, len) in framing 0 = bincode(Proof) or 1 = the
+ * four sections, whose lengths the caller leaves in table[0 .. 3] (RV_E_ARG unless their sum is len).  table: 657 words (csrc/verify_dev.h)
+ * -- record k = 40 * domain + i at words 8k .. 8k + 7: the offsets of keys, rec (then its length), corr (length), in (length), the
+ * omit byte; words 640 / 641: where the domains' preprocessing records start; 642: the status; 643 .. 652: the 80 omit bytes;
+ * 653 .. 656: comm.  *status: 0 = walked, 1 = the bytes run out, 2 = a count is not 40 / 216, 3 = a section does not end where its
+ * records do (or a preprocessing section is not 216 x 48 bytes), 4 = a group's records are refused; words behind a stop are zero. */
+int rv_hook_verify_walk(const uint8_t *bytes, size_t len, int framing, uint64_t *table, int *status);
 /* How often this process's evaluations (rv_evaluate, rv_evaluate_batch; the streaming evaluator once per chunk) ran each schedule:
  * out[0] = one launch per dependency level, out[1] = one workgroup per slice of witness words walking every level (csrc/eval.hip).
  * The results are the same either way. */

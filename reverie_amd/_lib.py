@@ -93,6 +93,7 @@ SYMBOLS = [
     "rv_hook_maskgen",
     "rv_stream_feed_device", "rv_eval_stream_feed_device", "rv_hook_stream_op_traffic", "rv_hook_stream_piece_sums",
     "rv_hook_compile_compare_device_chunk_ex", "rv_hook_compile_device_laps_z64",
+    "rv_verify_device", "rv_verify_sections_device", "rv_hook_verify_device_paths", "rv_hook_verify_walk",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -129,6 +130,11 @@ ARGTYPES = {
     "rv_eval_stream_feed_device": [_P, _P, _Z, _P, _Z, _P, _Z],
     "rv_hook_stream_op_traffic": [C.POINTER(C.c_uint64)],
     "rv_hook_stream_piece_sums": [_P, _P, _Z, C.c_uint64, _Z, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    # verification from device memory
+    "rv_verify_device": [_P, _P, _P, _Z, C.c_uint32, C.POINTER(C.c_int)],
+    "rv_verify_sections_device": [_P, _P, _P, _P, C.POINTER(C.c_size_t), C.c_uint32, C.POINTER(C.c_int)],
+    "rv_hook_verify_device_paths": [C.POINTER(C.c_uint64)],
+    "rv_hook_verify_walk": [_P, _Z, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)],
     # the mask generators (parity hook)
     "rv_hook_maskgen": [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _P],
 }

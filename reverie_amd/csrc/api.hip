@@ -28,6 +28,7 @@
 #include "ldsrun.h"
 #include "piece_pipe.h"
 #include "piece_sums.h"
+#include "verify_dev.h"
 
 using namespace rv;
 
@@ -1512,6 +1513,7 @@ extern "C" int rv_challenge(const uint8_t comm[RV_HASH_SIZE], uint8_t omit[RV_TO
 #include "prove.inc"
 #include "batch.inc"
 #include "verify.inc"
+#include "verify_dev.inc"
 #include "opscache.inc"
 #include "verify_batch.inc"
 #include "hooks.inc"

@@ -678,17 +678,35 @@ static bool verify_flags_ok(uint32_t flags) {
 }
 static bool verify_is_strict(uint32_t flags) { return !(flags & RV_VERIFY_REFERENCE_COMPAT); }
 
+// The two halves of the final decision, shared by the host-bytes form below and the device form (verify_dev.inc), which has comm
+// and the records' omit bytes without a host copy of the proof.
+// The reference's check: the challenge comm opens (omit[256]), and whether the slot digests, put back into repetition order, hash to comm
+static bool digests_give_comm(const uint8_t comm[32], const uint8_t* slot_digests, uint8_t omit[RV_TOTAL_REPS]) {
+    rv_challenge(comm, omit);  // proof/mod.rs:290
+    b3::Hasher hs;
+    size_t on = 0, pre = RV_ONLINE_REPS;
+    for (int i = 0; i < RV_TOTAL_REPS; i++) hs.update(slot_digests + 32 * (omit[i] < 8 ? on++ : pre++), 32);
+    uint8_t again[32];
+    hs.finalize(again);
+    return memcmp(again, comm, 32) == 0;
+}
+// ... and the strict one: the 40 online records of both domains name the player the challenge omits
+static bool records_omit_challenge(const uint8_t omit[RV_TOTAL_REPS], const uint8_t* rec_omit2, const uint8_t* rec_omit64) {
+    bool same = true;
+    size_t k = 0;
+    for (int i = 0; i < RV_TOTAL_REPS; i++)
+        if (omit[i] < 8) {
+            if (rec_omit2[k] != omit[i] || rec_omit64[k] != omit[i]) same = false;
+            k++;
+        }
+    return same;
+}
+
 static int rv_verify_finish_impl(const uint8_t* proof, size_t proof_len, const uint8_t* slot_digests, uint32_t flags,
                                  int zero_checks_ok, int* ok) {
     if (!proof || !slot_digests || !ok || proof_len < 32 || !verify_flags_ok(flags)) return RV_E_ARG;
     uint8_t omit[RV_TOTAL_REPS];
-    rv_challenge(proof, omit);  // proof/mod.rs:290
-    b3::Hasher hs;
-    size_t on = 0, pre = RV_ONLINE_REPS;
-    for (int i = 0; i < RV_TOTAL_REPS; i++) hs.update(slot_digests + 32 * (omit[i] < 8 ? on++ : pre++), 32);
-    uint8_t comm[32];
-    hs.finalize(comm);
-    *ok = memcmp(comm, proof, 32) == 0;
+    *ok = digests_give_comm(proof, slot_digests, omit);
     if (verify_is_strict(flags)) {
         // SURVEY F9: the reference computes `okay` without reading it (online.rs:21,175-177) and only checks WHICH
         // repetitions are opened, never the records' omitted player (proof/mod.rs:292-302)
@@ -700,12 +718,9 @@ static int rv_verify_finish_impl(const uint8_t* proof, size_t proof_len, const u
             *ok = 0;
             return RV_OK;
         }
-        size_t k = 0;
-        for (int i = 0; i < RV_TOTAL_REPS; i++)
-            if (omit[i] < 8) {
-                if (P.gf2.on[k].omit != omit[i] || P.z64.on[k].omit != omit[i]) *ok = 0;
-                k++;
-            }
+        uint8_t rec2[RV_ONLINE_REPS], rec64[RV_ONLINE_REPS];
+        for (int k = 0; k < RV_ONLINE_REPS; k++) rec2[k] = P.gf2.on[k].omit, rec64[k] = P.z64.on[k].omit;
+        if (!records_omit_challenge(omit, rec2, rec64)) *ok = 0;
     }
     return RV_OK;
 }

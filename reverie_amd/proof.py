@@ -374,6 +374,117 @@ class Proof:
         return bool(ok.value)
 
 
+def _device_bytes(t, ctx: "Optional[Context]", what: str) -> "Tuple[int, int, Context]":
+    """(device pointer, length, context) of proof bytes in GPU memory: a contiguous one-dimensional torch uint8 tensor on the
+    context's device.  Host tensors and tensors of another device are refused before any library call (ctx None: the default
+    context).  Waits for the tensor's device, so that the bytes are complete before the library's stream reads them."""
+    import torch
+
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise TypeError(f"{what} takes a torch tensor in GPU memory")
+    if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f"{what} takes a contiguous one-dimensional uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+    ctx = ctx or Context.default()
+    if t.device.index is not None and t.device.index != ctx.device:
+        raise ValueError(f"the tensor is on {t.device}, the context on device {ctx.device}")
+    torch.cuda.synchronize(t.device)
+    return t.data_ptr(), t.numel(), ctx
+
+
+class DeviceProof:
+    """A proof that lies in GPU memory, verified where it is (rv_verify_device / rv_verify_sections_device): either
+
+        DeviceProof(tensor)                            bincode(Proof) bytes in a torch uint8 GPU tensor
+        DeviceProof(sections=t, lens=[..], comm=b)     what rv_prove_device left: [gf2 online | gf2 preprocessing | z64 online |
+                                                       z64 preprocessing] in `t`, the four lengths, the commitment (host bytes)
+
+    The tensor stays the caller's; it must start on a 16-byte boundary (a fresh torch allocation does).  `verify` answers what
+    `Proof.verify` answers on the same bytes; no proof byte is copied to the host unless the bytes are not a well-framed proof."""
+
+    def __init__(self, tensor=None, *, sections=None, lens=None, comm=None, ctx: Optional[Context] = None):
+        if (tensor is None) == (sections is None):
+            raise ValueError("DeviceProof takes a tensor of proof bytes, or sections with lens and comm")
+        if sections is not None:
+            if lens is None or comm is None or len(lens) != 4 or len(bytes(comm)) != 32:
+                raise ValueError("sections come with their four lengths and the 32-byte commitment")
+            self.lens = [int(x) for x in lens]
+            self._comm = bytes(comm)
+            self._ptr, n, self.ctx = _device_bytes(sections, ctx, "DeviceProof")
+            if sum(self.lens) > n:
+                raise ValueError(f"the sections' lengths add up to {sum(self.lens)} bytes, the tensor has {n}")
+        else:
+            self.lens = None
+            self._comm = None
+            self._ptr, self._len, self.ctx = _device_bytes(tensor, ctx, "DeviceProof")
+        self.tensor = tensor if tensor is not None else sections  # (keeps the memory alive)
+
+    @staticmethod
+    def new(circuit: "Circuit", wit_gf2: Sequence[int], wit_z64: Sequence[int], seeds: Union[None, bytes, np.ndarray] = None,
+            ctx: Optional[Context] = None) -> "DeviceProof":
+        """rv_prove_device: Proof::new with the openings left in GPU memory (the sections form).  `seeds` (256 x 16 bytes) as
+        Proof.new; None draws them from the OS (the entry point takes no NULL)."""
+        import os
+
+        import torch
+
+        if not isinstance(circuit, Circuit):
+            raise TypeError("DeviceProof.new takes a compiled Circuit")
+        if ctx is not None and ctx is not circuit.ctx:
+            raise ValueError("the circuit was compiled in another context")
+        g, z = _witness(wit_gf2, wit_z64)
+        raw = os.urandom(TOTAL_REPS * 16) if seeds is None else (bytes(seeds) if isinstance(seeds, (bytes, bytearray)) else None)
+        s = np.ascontiguousarray(np.frombuffer(raw, np.uint8) if raw is not None else np.asarray(seeds, dtype=np.uint8)).reshape(TOTAL_REPS, 16)
+        sz2, sz64 = circuit.record_sizes()
+        out = torch.empty(40 * (sz2 + sz64) + 2 * (TOTAL_REPS - 40) * 48, dtype=torch.uint8, device=f"cuda:{circuit.ctx.device}")
+        lens = (C.c_size_t * 4)()
+        comm = np.zeros(32, np.uint8)
+        omit = np.zeros(TOTAL_REPS, np.uint8)
+        _lib.check(_lib.lib().rv_prove_device(circuit.ctx.handle, circuit.handle, _ptr(g), C.c_size_t(len(g)), _ptr(z), C.c_size_t(len(z)),
+                                              _ptr(s), C.c_void_p(out.data_ptr()), _ptr(comm), _ptr(omit), lens))
+        return DeviceProof(sections=out, lens=[int(x) for x in lens], comm=comm.tobytes(), ctx=circuit.ctx)
+
+    @property
+    def comm(self) -> bytes:
+        if self._comm is None:
+            self._comm = bytes(self.tensor[:32].cpu().numpy().tobytes())
+        return self._comm
+
+    def verify(self, circuit: "Circuit", strict: bool = True) -> bool:
+        """Proof.verify(circuit, strict=strict) on these bytes, read in GPU memory"""
+        if not isinstance(circuit, Circuit):
+            raise TypeError("DeviceProof.verify takes a compiled Circuit")
+        if circuit.ctx.device != self.ctx.device:
+            raise ValueError(f"the proof is on device {self.ctx.device}, the circuit's context on device {circuit.ctx.device}")
+        ok = C.c_int()
+        flags = 0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT
+        if self.lens is None:
+            _lib.check(_lib.lib().rv_verify_device(circuit.ctx.handle, circuit.handle, C.c_void_p(self._ptr), C.c_size_t(self._len),
+                                                   C.c_uint32(flags), C.byref(ok)))
+        else:
+            comm = np.frombuffer(self._comm, np.uint8)
+            _lib.check(_lib.lib().rv_verify_sections_device(circuit.ctx.handle, circuit.handle, _ptr(comm), C.c_void_p(self._ptr),
+                                                            (C.c_size_t * 4)(*self.lens), C.c_uint32(flags), C.byref(ok)))
+        return bool(ok.value)
+
+    def to_proof(self) -> "Proof":
+        """the bytes as a host `Proof` (one copy down; sections are framed by rv_assemble_proof)"""
+        host = self.tensor.cpu().numpy()
+        if self.lens is None:
+            return Proof(host.tobytes())
+        parts = _lib.ShardParts()
+        at = 0
+        for name, n in zip(("gf2_online", "gf2_pre", "z64_online", "z64_pre"), self.lens):
+            setattr(parts, name, host.ctypes.data + at)
+            setattr(parts, name + "_len", n)
+            at += n
+        parts.n_online, parts.n_pre = 40, TOTAL_REPS - 40
+        comm = np.frombuffer(self._comm, np.uint8)
+        out = C.c_void_p()
+        n = C.c_size_t()
+        _lib.check(_lib.lib().rv_assemble_proof(_ptr(comm), C.byref(parts), C.c_size_t(1), C.byref(out), C.byref(n)))
+        return Proof(_owned=(C.c_void_p(out.value), n.value))
+
+
 def verify_batch(circuit, proofs, wire_counts: Optional[Tuple[int, int]] = None, ctx: Optional[Context] = None,
                  strict: bool = True) -> "list[bool]":
     """rv_verify_batch: Proof.verify for many proofs of one circuit in one pass (`proofs`: Proof objects or bytes);

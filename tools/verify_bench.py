@@ -1,8 +1,18 @@
 #!/usr/bin/env python3
 """Prover / verifier wall times through the host-bytes entry points (rv_prove / rv_verify, PCIe included)
-for the headline circuit and its all-AND variant.  Prints one JSON line per variant."""
+for the headline circuit and its all-AND variant.  Prints one JSON line per variant.
+
+--proof {host,device,sections} (repeatable; all in one process, on the same circuit and proof) adds "verify_modes" to the line:
+the verifier's wall time per call with the proof where that mode has it --
+    host      rv_verify_ex on the library's page-locked proof buffer (the README's rv_verify row)
+    device    rv_verify_device on the same bytes in a torch GPU tensor
+    sections  rv_verify_sections_device on what rv_prove_device left in GPU memory
+as median, min and max over --calls calls after --warmup calls, with the calls that took the device path and the proof bytes
+the verifier uploaded (rv_hook_verify_device_paths, rv_hook_verify_proof_bytes).  --only-headline leaves the all-AND variant out."""
+import argparse
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -15,8 +25,53 @@ import numpy as np  # noqa: E402
 import circuits  # noqa: E402
 import reverie_amd  # noqa: E402
 
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("--proof", action="append", choices=("host", "device", "sections"), default=[],
+                help="also time the verifier with the proof in host memory / in a GPU tensor / as rv_prove_device's sections")
+ap.add_argument("--calls", type=int, default=9, help="timed calls per --proof mode (median, min, max)")
+ap.add_argument("--warmup", type=int, default=2, help="untimed calls per --proof mode")
+ap.add_argument("--only-headline", action="store_true", help="the headline circuit only (p_and = 0.5)")
+args = ap.parse_args()
+
+
+def verify_modes(c, wit, proof):
+    """wall times of args.proof's verifier calls on `proof` (a Proof in the library's buffer)"""
+    import ctypes as C
+
+    import torch
+
+    from reverie_amd import _lib
+
+    L = _lib.lib()
+
+    def counters():
+        out = (C.c_uint64 * 2)()
+        L.rv_hook_verify_device_paths(out)
+        return int(out[0]), int(L.rv_hook_verify_proof_bytes())
+
+    out = {}
+    for mode in args.proof:
+        if mode == "host":
+            target = proof
+        elif mode == "device":
+            target = reverie_amd.DeviceProof(torch.frombuffer(bytearray(bytes(proof)), dtype=torch.uint8).cuda())
+        else:
+            target = reverie_amd.DeviceProof.new(c, wit, [], seeds=seeds)
+        ok = all(target.verify(c) for _ in range(args.warmup))
+        d0, b0 = counters()
+        ts = []
+        for _ in range(args.calls):
+            t0 = time.perf_counter()
+            ok = target.verify(c) and ok
+            ts.append((time.perf_counter() - t0) * 1e3)
+        d1, b1 = counters()
+        out[mode] = {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4), "calls": args.calls,
+                     "ok": bool(ok), "device_path_calls": d1 - d0, "proof_bytes_uploaded": b1 - b0}
+    return out
+
+
 seeds = np.random.default_rng(1).integers(0, 256, (256, 16), dtype=np.uint8)
-for p_and in (0.5, 1.0):
+for p_and in (0.5,) if args.only_headline else (0.5, 1.0):
     prog, wit, wc, st = circuits.layered_gf2(p_and=p_and)
     c = reverie_amd.Circuit(prog, wc)
     proof = reverie_amd.Proof.new(c, wit, [], seeds=seeds)
@@ -43,7 +98,10 @@ for p_and in (0.5, 1.0):
     copy = reverie_amd.Proof(bytes(proof))  # ordinary pageable memory, as a proof read from disk would be
     vp, okp, _ = phases(lambda: copy.verify(c))
     ok = ok and okp
-    print(json.dumps({"p_and": p_and, "and": st["and"], "gates": st["gates"], "proof_bytes": len(proof), "prove_ms_host": min(t) * 1e3,
-                      "verify_ms_host": min(v) * 1e3, "verify_ms_host_pageable_input": min(vp) * 1e3, "prove_and_per_s_host": st["and"] / min(t), "verify_and_per_s_host": st["and"] / min(v),
-                      "verify_ok": ok, "prove_device_phases_ms": prove_phases, "verify_device_phases_ms": verify_phases}))
+    line = {"p_and": p_and, "and": st["and"], "gates": st["gates"], "proof_bytes": len(proof), "prove_ms_host": min(t) * 1e3,
+            "verify_ms_host": min(v) * 1e3, "verify_ms_host_pageable_input": min(vp) * 1e3, "prove_and_per_s_host": st["and"] / min(t), "verify_and_per_s_host": st["and"] / min(v),
+            "verify_ok": ok, "prove_device_phases_ms": prove_phases, "verify_device_phases_ms": verify_phases}
+    if args.proof:
+        line["verify_modes"] = verify_modes(c, wit, proof)
+    print(json.dumps(line))
     c.close()
