@@ -155,7 +155,8 @@ int rv_circuit_compile_ex(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z6
  * programs of GF(2) ops (no Z64, B2A or SizeHint op) in either gate-stream form: the plain one (every Xor of two rows materialised)
  * when that is the host compiler's final answer -- not for the deep, narrow circuits it recompiles with lazy sums (AES-128, SHA-256)
  * --, and, combined with RV_COMPILE_WHOLE_PROVER, the lazy-sum form of any such program (a forced form is final, so AES-128 and
- * SHA-256 compile on the device under both flags).  Not with RV_COMPILE_KEEP_WIRES or RV_LAZY_K, and not past 2^16 dependency
+ * SHA-256 compile on the device under both flags).  Not with RV_COMPILE_KEEP_WIRES (unless RV_COMPILE_DEVICE_KEEP_WIRES is set as
+ * well, below) or RV_LAZY_K, and not past 2^16 dependency
  * rounds.  Everything else, op-list errors included, is compiled by the host compiler, with its error codes;
  * rv_circuit_compiled_on_device tells which compiler made a circuit. */
 #define RV_COMPILE_DEVICE 4u
@@ -182,6 +183,17 @@ int rv_circuit_compile_ex(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z6
  * The value is 32, not 16: 16 stays an unknown bit (RV_E_ARG, "unknown flag bits"), as callers and tests written against the
  * previous flag set expect of the first bit above it.  Without this bit every call decides as it did before the bit existed. */
 #define RV_COMPILE_DEVICE_B2A 32u /* with RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64: the device compiler also takes B2A ops */
+/* RV_COMPILE_DEVICE_KEEP_WIRES, only together with RV_COMPILE_KEEP_WIRES and RV_COMPILE_DEVICE (RV_E_ARG otherwise, with a message
+ * that names what is missing; rv_circuit_compile_device implies RV_COMPILE_DEVICE): RV_COMPILE_KEEP_WIRES no longer sends the program
+ * to the host compiler.  The device compiler counts one more read of every written wire's final value, so the sum that makes it is
+ * not dropped as unread, and builds both wire tables where the circuit lives -- every GF(2) wire's final form (rows numbered as gate
+ * operands are; a never-written wire is the zero form) and every Z64 wire's final SSA id -- so rv_evaluate / rv_evaluate_batch of an
+ * op list that sits in device memory need no host compile.  It combines freely with RV_COMPILE_WHOLE_PROVER, RV_COMPILE_DEVICE_Z64
+ * and RV_COMPILE_DEVICE_B2A, and every other fallback rule of those bits stands.  The circuit is the host compiler's
+ * RV_COMPILE_KEEP_WIRES circuit field by field.  For whole programs only: rv_ctx_set_compile_flags, rv_stream_set_compile_flags and
+ * rv_eval_stream_set_compile_flags answer "unknown flag bits" for it (a stream's pieces write their wires back instead).  The value
+ * is 128: 16 and 64 stay unknown bits.  Without this bit every call decides as it did before the bit existed. */
+#define RV_COMPILE_DEVICE_KEEP_WIRES 128u /* with RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE: the device compiler keeps the wires' final values too */
 /* The same for an op array already in device memory (n_ops packed 24-byte records on the context's device, e.g. a torch tensor);
  * the caller keeps ownership of d_ops and must have finished writing it.  A program the device path does not take is copied to the
  * host and compiled there. */
@@ -746,8 +758,9 @@ int rv_hook_compile_compare(const rv_op *ops, size_t n_ops, size_t z64_wires, si
  * The hook tries the device whether or not RV_COMPILE_DEVICE is set, except that RV_COMPILE_WHOLE_PROVER without the device bit stays
  * a host compile (*path = 0): with RV_COMPILE_WHOLE_PROVER | RV_COMPILE_DEVICE it tries the device compiler on the lazy-sum form and
  * compares with the host compiler's forced lazy-sum compile.  RV_COMPILE_DEVICE_Z64 (with RV_COMPILE_DEVICE, else RV_E_ARG) lets the
- * device side take Z64 and mixed programs, RV_COMPILE_DEVICE_B2A (with both, else RV_E_ARG) programs with B2A ops; every other flag
- * value behaves as before.  Returns the host compiler's status. */
+ * device side take Z64 and mixed programs, RV_COMPILE_DEVICE_B2A (with both, else RV_E_ARG) programs with B2A ops,
+ * RV_COMPILE_DEVICE_KEEP_WIRES (with RV_COMPILE_KEEP_WIRES and RV_COMPILE_DEVICE, else RV_E_ARG) RV_COMPILE_KEEP_WIRES compiles, whose
+ * wire tables are compared too; every other flag value behaves as before.  Returns the host compiler's status. */
 int rv_hook_compile_compare_device(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, int *path,
                                    int *diff);
 /* The same for one piece of a stream: both sides compile the ops as the streaming chunk that starts at `start` = { mask_phase (< 128),

@@ -78,12 +78,19 @@ def evaluate_clear(prog, witness):
     return v
 
 
-def evaluate_gpu(prog, wc, witness):
+def evaluate_gpu(prog, wc, witness, compiler="host"):
     """`oneshot` on the GPU (rv_evaluate): any program without Random ops, GF(2), Z64 and B2A alike (the CLI's witness is
-    GF(2) bits only, as the reference's).  Raises SystemExit naming the op index of the first failing AssertZero."""
+    GF(2) bits only, as the reference's).  Raises SystemExit naming the op index of the first failing AssertZero.
+    compiler: "device" / "device-z64" / "device-b2a" = the program is compiled on the GPU too, with those bits plus
+    RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE_KEEP_WIRES (the whole-circuit evaluator's compile); the outcome is the same."""
     from .proof import Circuit
 
-    r = Circuit(prog, wc).evaluate(witness, [])
+    if compiler == "host":
+        circuit = Circuit(prog, wc)
+    else:
+        circuit = Circuit(prog, wc, keep_wires=True, device_compile=True, device_z64=compiler in ("device-z64", "device-b2a"),
+                          device_b2a=compiler == "device-b2a", device_keep_wires=True)
+    r = circuit.evaluate(witness, [])
     if not r.ok:
         raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (r.first_failed_op, r.n_failed))
 
@@ -158,7 +165,7 @@ def build_parser():
     ap.add_argument("--max-chunk-ops", type=int, default=0,
                     help="oneshot --evaluator stream: ops per device chunk (0 = the library's default, 2^18)")
     ap.add_argument("--compiler", default="host", choices=["host", "device", "device-z64", "device-b2a"],
-                    help="prove / verify / oneshot-zk and oneshot --evaluator stream: compile the program (the stream's pieces) on the host "
+                    help="prove / verify / oneshot-zk and oneshot --evaluator gpu / stream: compile the program (the stream's pieces) on the host "
                          "(default) or on the GPU (device = RV_COMPILE_DEVICE: GF(2) programs; device-z64 = with RV_COMPILE_DEVICE_Z64: Z64 and "
                          "mixed programs too; device-b2a = with RV_COMPILE_DEVICE_B2A as well: programs with B2A ops too; without it B2A ops, and "
                          "always a SizeHint that grows a wire count, op-list errors, chains deeper than 2^16 rounds and "
@@ -196,7 +203,7 @@ def main(argv=None) -> int:
         print("Evaluating program in cleartext")
         wit = parse_witness(open(a.witness_path, "rb").read())
         if use_gpu_evaluator(prog, a.evaluator):
-            evaluate_gpu(prog, wc, wit)
+            evaluate_gpu(prog, wc, wit, a.compiler)
         else:
             evaluate_clear(prog, wit)
         print("()")

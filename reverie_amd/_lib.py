@@ -144,6 +144,7 @@ RV_COMPILE_KEEP_WIRES = 2  # the circuit keeps every wire's final value form: rv
 RV_COMPILE_DEVICE = 4  # compiled on the GPU (GF(2) programs, plain or -- with WHOLE_PROVER -- lazy sums; anything else by the host compiler): the same circuit
 RV_COMPILE_DEVICE_Z64 = 8  # with RV_COMPILE_DEVICE: Z64 ops and SizeHint ops that grow nothing compile on the GPU too (B2A still on the host)
 RV_COMPILE_DEVICE_B2A = 32  # with both bits above: B2A ops compile on the GPU too (16 stays an unknown bit)
+RV_COMPILE_DEVICE_KEEP_WIRES = 128  # with RV_COMPILE_KEEP_WIRES and RV_COMPILE_DEVICE: KEEP_WIRES programs compile on the GPU too (64 stays an unknown bit)
 RV_VERIFY_REFERENCE_COMPAT = 2  # the reference verifier's two unchecked conditions stay unchecked
 
 _lib = None

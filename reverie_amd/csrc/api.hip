@@ -767,8 +767,15 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
                                   rv_circuit** out, const rv_op* d_ops = nullptr);
 static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged = false);
 
+// what a whole-program compile takes (RV_COMPILE_DEVICE_KEEP_WIRES: whole programs only, so not one of RV_COMPILE_DEVICE_BITS)
+constexpr uint32_t RV_COMPILE_EX_BITS = RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE_BITS | RV_COMPILE_DEVICE_KEEP_WIRES;
 // nullptr when the bits go together, else what is missing
 static const char* device_bits_missing(uint32_t flags) {
+    if ((flags & RV_COMPILE_DEVICE_KEEP_WIRES) && (flags & (RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE)) != (RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE)) {
+        if (flags & RV_COMPILE_DEVICE) return "the flag RV_COMPILE_DEVICE_KEEP_WIRES needs RV_COMPILE_KEEP_WIRES";
+        if (flags & RV_COMPILE_KEEP_WIRES) return "the flag RV_COMPILE_DEVICE_KEEP_WIRES needs RV_COMPILE_DEVICE";
+        return "the flag RV_COMPILE_DEVICE_KEEP_WIRES needs RV_COMPILE_KEEP_WIRES and RV_COMPILE_DEVICE";
+    }
     if ((flags & RV_COMPILE_DEVICE_B2A) && (flags & (RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64)) != (RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64)) {
         if (flags & RV_COMPILE_DEVICE) return "the flag RV_COMPILE_DEVICE_B2A needs RV_COMPILE_DEVICE_Z64";
         if (flags & RV_COMPILE_DEVICE_Z64) return "the flag RV_COMPILE_DEVICE_B2A needs RV_COMPILE_DEVICE";
@@ -793,7 +800,7 @@ static int check_device_flags(const char* who, uint32_t flags) {
 
 extern "C" int rv_circuit_compile_ex(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                                      rv_circuit** out) {
-    if (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE_BITS)) {
+    if (flags & ~RV_COMPILE_EX_BITS) {
         g_last_error = "rv_circuit_compile_ex: unknown flag bits";
         return RV_E_ARG;
     }
@@ -825,7 +832,10 @@ static DevAlloc ctx_dev_allocator(rv_ctx* ctx) {
     return a;
 }
 // the requests the device compiler hands to the host compiler whatever the op list holds (compile_dev.h): no upload for them
-static bool device_compile_possible(uint32_t flags) { return !(flags & RV_COMPILE_KEEP_WIRES) && !getenv("RV_LAZY_K"); }
+// (RV_COMPILE_KEEP_WIRES: the wire tables are built on the device under RV_COMPILE_DEVICE_KEEP_WIRES only)
+static bool device_compile_possible(uint32_t flags) {
+    return (!(flags & RV_COMPILE_KEEP_WIRES) || (flags & RV_COMPILE_DEVICE_KEEP_WIRES)) && !getenv("RV_LAZY_K");
+}
 static std::mutex g_dev_laps_mu;
 static DevCompileLaps g_dev_laps;
 // the device compile of d_ops (device memory) into `cc` (and, with keep, the circuit's gate / ordinal arrays in HBM); RV_OK,
@@ -836,7 +846,7 @@ static int compile_on_device(rv_ctx* ctx, const rv_op* d_ops, size_t n_ops, size
     DevCompileLaps laps;
     DevCompileRequest req;
     req.d_ops = d_ops, req.n_ops = n_ops, req.z64_wires = z64_wires, req.gf2_wires = gf2_wires;
-    req.keep_wires = (flags & RV_COMPILE_KEEP_WIRES) != 0, req.force_lazy_k = k, req.device_bits = flags & RV_COMPILE_DEVICE_BITS;
+    req.keep_wires = (flags & RV_COMPILE_KEEP_WIRES) != 0, req.force_lazy_k = k, req.device_bits = flags & (RV_COMPILE_DEVICE_BITS | RV_COMPILE_DEVICE_KEEP_WIRES);
     const int rc = compile_ops_device(ctx->stream, ctx_dev_allocator(ctx), req, cc, keep, &laps);
     if (rc == RV_E_DEVICE) g_last_error = "device compile: HIP error";
     if (rc == RV_E_NOMEM) g_last_error = "device compile: out of device memory";
@@ -927,7 +937,8 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
     std::vector<rv_op> h_ops;  // (ops in device memory that the device path hands back: the host compiler's copy)
     if (d_ops || (flags & RV_COMPILE_DEVICE)) {
         // RV_COMPILE_DEVICE / rv_circuit_compile_device: the compile on the context's GPU (compile_dev.hip) -- GF(2) programs, with
-        // RV_COMPILE_DEVICE_Z64 also Z64 and mixed ones --, at K = 1 or, with RV_COMPILE_WHOLE_PROVER, in the lazy-sum form
+        // RV_COMPILE_DEVICE_Z64 also Z64 and mixed ones --, at K = 1 or, with RV_COMPILE_WHOLE_PROVER, in the lazy-sum form;
+        // RV_COMPILE_KEEP_WIRES under RV_COMPILE_DEVICE_KEEP_WIRES
         if (hipSetDevice(ctx->device) != hipSuccess) {
             delete c;
             return hip_fail(hipGetLastError(), "hipSetDevice", __FILE__, __LINE__);
@@ -943,6 +954,7 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
                     c->d_rec_rows = kept.d_rec_rows;
                     c->d_in_rows = kept.d_in_rows;
                     c->d_gates64 = kept.d_gates64, c->d_rec_offs64 = kept.d_rec_offs64, c->d_in_offs64 = kept.d_in_offs64;
+                    c->d_wire_forms = kept.d_wire_forms, c->d_wire_ssa64 = kept.d_wire_ssa64;
                     c->dev_compiled = true;
                 }
             }
@@ -978,7 +990,9 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
         fprintf(stderr, "[rv circuit] compile_ops: %.3f s for %zu ops\n", std::chrono::duration<double>(t_compiled - t_begin).count(),
                 n_ops);
     if ((rc = circuit_upload(ctx, c))) return rc;  // (destroys c on failure)
-    if (keep && (rc = eval_upload_wires(ctx, c))) {
+    if (keep && c->dev_compiled) {  // (RV_COMPILE_DEVICE_KEEP_WIRES: the device compiler left both wire tables in HBM)
+        c->keep_wires = true;
+    } else if (keep && (rc = eval_upload_wires(ctx, c))) {
         rv_circuit_destroy(c);
         return rc;
     }
@@ -1344,8 +1358,9 @@ extern "C" int rv_hook_compile_compare(const rv_op* ops, size_t n_ops, size_t z6
 
 extern "C" int rv_circuit_compile_device(rv_ctx* ctx, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags,
                                          rv_circuit** out) {
-    // (the call implies RV_COMPILE_DEVICE: RV_COMPILE_DEVICE_Z64 needs no other bit here, RV_COMPILE_DEVICE_B2A needs that one)
-    if (!ctx || !out || (n_ops && !d_ops) || (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE_BITS))) return RV_E_ARG;
+    // (the call implies RV_COMPILE_DEVICE: RV_COMPILE_DEVICE_Z64 needs no other bit here, RV_COMPILE_DEVICE_B2A needs that one,
+    // RV_COMPILE_DEVICE_KEEP_WIRES needs RV_COMPILE_KEEP_WIRES)
+    if (!ctx || !out || (n_ops && !d_ops) || (flags & ~RV_COMPILE_EX_BITS)) return RV_E_ARG;
     if (const char* m = device_bits_missing(flags | RV_COMPILE_DEVICE)) {
         g_last_error = std::string("rv_circuit_compile_device: ") + m;
         return RV_E_ARG;
@@ -1367,7 +1382,7 @@ extern "C" int rv_ctx_set_compile_flags(rv_ctx* ctx, uint32_t flags) {
 
 extern "C" int rv_hook_compile_compare_device(rv_ctx* ctx, const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, int* path,
                                               int* diff) {
-    if (!ctx || !path || !diff || (n_ops && !ops) || (flags & ~(RV_COMPILE_WHOLE_PROVER | RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE_BITS)) ||
+    if (!ctx || !path || !diff || (n_ops && !ops) || (flags & ~RV_COMPILE_EX_BITS) ||
         !device_bits_ok(flags))
         return RV_E_ARG;
     try {

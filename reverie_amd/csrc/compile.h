@@ -140,7 +140,8 @@ void relocate_chunk(Compiled& cc, uint64_t on0, uint64_t pre0, uint64_t on_words
 // (compile_par.cpp; RV_COMPILE_THREADS, default min(16, hardware threads); RV_COMPILE_SEQ=1 turns it off); everything else,
 // and every program with an error in it, by the sequential compiler.  The result is the same bit for bit.
 // keep_wires: RV_COMPILE_KEEP_WIRES (whole programs only) -- every wire's final value is read once more after the program, so the
-// linear gates that produce one are not dropped as unread, and Compiled::wire_forms / wire_ssa64 are filled
+// linear gates that produce one are not dropped as unread, and Compiled::wire_forms / wire_ssa64 are filled (the device compiler does
+// the same under RV_COMPILE_DEVICE_KEEP_WIRES: compile_dev.h)
 int compile_ops(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, Compiled& out, const ChunkStart* chunk = nullptr,
                 int force_lazy_k = 0, bool keep_wires = false);
 // the sequential compiler (one thread; the reference implementation of the gate stream, the error path, streaming chunks)

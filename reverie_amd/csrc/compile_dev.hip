@@ -24,6 +24,10 @@
 //                  gates of the write-back level, which go straight to their places: the materialised carried forms are level 0's
 //                  class 3, the write-backs the last level's, both in wire order -- no op gate has class 3 at K = 1
 //
+// RV_COMPILE_KEEP_WIRES (RV_COMPILE_DEVICE_KEEP_WIRES; whole programs): between steps 2 and 3 every written wire's last writer gets one
+// more read (k_cd_live: the final values are live out of the program), after step 5 the wires' final forms are written from the last
+// writers' values (k_cd_wire_forms), and the Z64 wires' final SSA ids come from the Z64 list's writers sort (k_z_wire_ssa).
+//
 // Z64 ops and mixed lists (RV_COMPILE_DEVICE_Z64).  The two domains share no wire and, without B2A, no gate: run_pass keeps them apart
 // except for the level count.  So a mixed list is split (z64_split): its GF(2) ops, compacted in order, go through the pipeline above
 // unchanged, and its Z64 ops through the same steps in a simpler form (z64_levels, z64_tables) -- no folding, every op one Gate64, every
@@ -110,7 +114,9 @@ int compile_gf2(hipStream_t st, const DevAlloc& A, const DevCompileRequest& q, S
     Scratch S(A, st);
     if (const int rc = gf2_levels(S, R ? *R : S, T, st, g)) return rc;
     if (const int rc = gf2_tables(S, R ? *R : S, T, st, g, 0, false, out, &res.d_gates)) return rc;
-    res.d_rec_rows = g.rec_rows, res.d_in_rows = g.in_rows;
+    res.d_rec_rows = g.rec_rows, res.d_in_rows = g.in_rows, res.d_wire_forms = g.wire_forms;
+    if (g.keep)  // (a GF(2) list: every Z64 wire reads as SSA 0)
+        if (const int rc = z64_wire_table(S, R ? *R : S, st, nullptr, g.z64_wires, out, &res.d_wire_ssa64)) return rc;
     if (laps) fill_laps(T, g.rounds, false, *laps);
     return RV_OK;
 }
@@ -121,7 +127,8 @@ int compile_mixed(hipStream_t st, const DevAlloc& A, const DevCompileRequest& q,
     const size_t n = q.n_ops;
     const ChunkStart* chunk = q.chunk;
     const bool lazy = q.force_lazy_k == RV_LIN_K;
-    if (q.keep_wires || (q.force_lazy_k && (!lazy || chunk)) || getenv("RV_LAZY_K") || n >= (1u << 28) || q.gf2_wires >= (1u << 31) ||
+    const bool keep_here = (q.device_bits & RV_COMPILE_DEVICE_KEEP_WIRES) && !chunk;  // (the wires' final values: whole programs, under their bit)
+    if ((q.keep_wires && !keep_here) || (q.force_lazy_k && (!lazy || chunk)) || getenv("RV_LAZY_K") || n >= (1u << 28) || q.gf2_wires >= (1u << 31) ||
         q.z64_wires >= (1u << 30))
         return RV_COMPILE_FALLBACK;
     if (n == 0) return compile_gf2(st, A, q, R, T, out, res, laps);  // (an empty piece; an empty program is the host compiler's)
@@ -140,9 +147,9 @@ int compile_mixed(hipStream_t st, const DevAlloc& A, const DevCompileRequest& q,
         if (const int rc = gf2_levels(S2, R ? *R : S2, T, st, g)) return rc;
         if (const int rc = z64_levels(S, T, st, z, g.glvl)) return rc;
         if (const int rc = gf2_tables(S2, R ? *R : S2, T, st, g, z.levels64, z.n_wb64 != 0, out, &res.d_gates)) return rc;
-        res.d_rec_rows = g.rec_rows, res.d_in_rows = g.in_rows;
+        res.d_rec_rows = g.rec_rows, res.d_in_rows = g.in_rows, res.d_wire_forms = g.wire_forms;
     }
-    if (const int rc = z64_tables(S, R ? *R : S, T, st, z, out, res)) return rc;
+    if (const int rc = z64_tables(S, R ? *R : S, T, st, z, g.keep, out, res)) return rc;
     if (laps) fill_laps(T, g.rounds, z.n64 != 0, *laps);
     return RV_OK;
 }
@@ -152,12 +159,12 @@ int compile_ops_device(hipStream_t st, const DevAlloc& A, const DevCompileReques
     if (keep) *keep = DevCompileKeep();
     const bool mixed = (q.device_bits & RV_COMPILE_DEVICE_Z64) != 0;
     LapTimer T(st, laps != nullptr);
-    // The result Scratch: the six arrays a circuit may keep, handed over in one place, after a successful compile (a failure frees all through
+    // The result Scratch: the arrays a circuit may keep (DevCompileKeep), handed over in one place, after a successful compile (a failure frees all through
     // the destructors).  Declared first, so it is released after every work Scratch, whose destructor synchronised the stream.
     Scratch R(A, st, false);
     DevCompileKeep res;
     const int rc = mixed ? compile_mixed(st, A, q, keep ? &R : nullptr, T, out, res, laps) : compile_gf2(st, A, q, keep ? &R : nullptr, T, out, res, laps);
-    if (rc == RV_OK && keep) *keep = res, R.keep_all();  // (R holds these six arrays and nothing else)
+    if (rc == RV_OK && keep) *keep = res, R.keep_all();  // (R holds these arrays and nothing else)
     return rc;
 }
 #undef CDCHK

@@ -336,7 +336,7 @@ __global__ __launch_bounds__(TB) void k_cd_round(uint32_t r, uint32_t chunk, con
         else V[i] = value_k1(op, i, p, chunk, uses, V, &gl, &mt);
         glvl[i] = gl;
         if constexpr (FORM != FORM_Z64) mat[i] = mt;
-        const uint32_t c0 = cons_off[i], c1 = c0 + uses[i];
+        const uint32_t c0 = cons_off[i], c1 = cons_off[i + 1];  // (not c0 + uses[i]: k_cd_live adds the reads after the program to uses)
         for (uint32_t k = c0; k < c1; k++) {
             const uint32_t c = cons[k];
             if (atomicSub(&rem[c], 1u) == 1u) {
@@ -615,6 +615,48 @@ __global__ __launch_bounds__(TB) void k_cd_wb_gates(const uint32_t* lastw, const
     g.dst = (uint32_t)w;
     gates[wb_at + r.m] = g;
 }
+// RV_COMPILE_KEEP_WIRES under RV_COMPILE_DEVICE_KEEP_WIRES (whole programs).  Liveness, Builder::live_out: every written wire's final
+// value is read once more after the program -- one read of its last writer per wire (not per distinct value), before the value step,
+// so a sum that is a wire's final value is not dropped as unread and the lazy rule has the read in f.  Unlike a chunk the reads are
+// still counted: an unread sum that is no wire's final value is dropped.  lastw[w] = wire w's last writer (NO_WRITER: never written),
+// taken while the writers sort is in place.
+__global__ __launch_bounds__(TB) void k_cd_live(const uint32_t* sv, const uint32_t* seg_lo, const uint32_t* seg_hi, uint32_t W, uint32_t* uses,
+                                                uint32_t* lastw) {
+    const size_t w = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (w >= W) return;
+    uint32_t q = NO_WRITER;
+    if (seg_hi[w] > seg_lo[w]) {
+        q = sv[seg_hi[w] - 1];
+        atomicAdd(&uses[q], 1u);
+    }
+    lastw[w] = q;
+}
+// The wires' final forms (compile_ops_seq: Compiled::wire_forms), once the rows have their numbers: the last writer's value, its rows
+// numbered as a gate's operands are, unused slots the zero row; a never-written wire is the all-zero form
+template <bool LAZY>
+__global__ __launch_bounds__(TB) void k_cd_wire_forms(const uint32_t* lastw, uint32_t W, const rv_op* ops, const int2* V, const uint4* V3, const C4* cx,
+                                                      const uint32_t* comp, Seeds s, uint32_t pad, WireForm* forms) {
+    const size_t w = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (w >= W) return;
+    const uint32_t q = lastw[w];
+    WireForm f;
+    for (int k = 0; k < RV_LIN_K; k++) f.b[k] = s.base + pad;
+    f.c = 0;
+    if (q != NO_WRITER) {
+        if constexpr (LAZY) {
+            const uint4 F = V3[q];
+            const uint32_t n = form_n(F);
+            for (int k = 0; k < RV_LIN_K; k++)
+                if ((uint32_t)k < n) f.b[k] = row_index(ops, cx, comp, s, pad, (int)(form_row(F, k) & ~ROW_COMP));
+            f.c = form_c(F);
+        } else {
+            const int2 v = V[q];
+            if (is_row(v)) f.b[0] = row_index(ops, cx, comp, s, pad, v.x);
+            f.c = (uint32_t)(v.y & 1);
+        }
+    }
+    forms[w] = f;
+}
 // level_done_on[l] = online rows e whose prefix maximum of levels is <= l; pm = exclusive prefix maximum of on_lvl (n_on + 1 entries)
 __global__ __launch_bounds__(TB) void k_cd_done_on(const uint32_t* pm, const uint32_t* on_lvl, size_t n_on, uint32_t n_levels, uint32_t* done_on) {
     const size_t e = (size_t)blockIdx.x * TB + threadIdx.x;
@@ -693,6 +735,7 @@ struct Gf2State {
     const ChunkStart* chunk;
     uint32_t W;
     bool lazy;  // the lazy-sum form: whole programs only (a chunk is final at K = 1)
+    bool keep;  // RV_COMPILE_KEEP_WIRES: the final values are read after the program, and the wires' forms are a result
     Seeds seeds;
     // device arrays (gf2_levels)
     Gf2Words* d_words;
@@ -704,6 +747,8 @@ struct Gf2State {
     uint4* V3;   // ... or as lazy sums (null: K = 1)
     int* glvl;   // the level of every op's gate (-1: none)
     uint32_t* mat;
+    uint32_t* lastw;        // keep: every wire's last writer (gf2_levels)
+    WireForm* wire_forms;   // keep: the wires' final forms (gf2_tables; the result Scratch's when the caller keeps them)
     // host numbers of gf2_levels
     C4 tot;
     uint64_t n_on, n_rec;
@@ -721,8 +766,9 @@ constexpr uint64_t LIM = 0xFFFFFFFFull - 512;  // what a 32-bit row, gate or tra
 // list holds (a Z64 op in the list is what sends a program to the host; the Z64 wire count alone does not)
 int gf2_begin(const DevCompileRequest& q, Gf2State& g) {
     const size_t gf2_wires = q.gf2_wires;
-    g.z64_wires = q.z64_wires, g.chunk = q.chunk, g.lazy = q.force_lazy_k == RV_LIN_K;
-    if (q.keep_wires || (q.force_lazy_k && (!g.lazy || g.chunk)) || getenv("RV_LAZY_K") || (g.n == 0 && !g.chunk && !g.mx) || g.n >= (1u << 28) ||
+    g.z64_wires = q.z64_wires, g.chunk = q.chunk, g.lazy = q.force_lazy_k == RV_LIN_K, g.keep = q.keep_wires;
+    // (the wires' final values are kept for whole programs, when the caller set RV_COMPILE_DEVICE_KEEP_WIRES)
+    if ((q.keep_wires && (!(q.device_bits & RV_COMPILE_DEVICE_KEEP_WIRES) || g.chunk || q.z64_wires >= (1u << 30))) || (q.force_lazy_k && (!g.lazy || g.chunk)) || getenv("RV_LAZY_K") || (g.n == 0 && !g.chunk && !g.mx) || g.n >= (1u << 28) ||
         gf2_wires >= (1u << 31) || (g.chunk && gf2_wires >= (1u << 30)))  // (a chunk names wire w's carried row -2 - w, below the host compiler's CARRY flag bit)
         return RV_COMPILE_FALLBACK;
     g.W = (uint32_t)gf2_wires;
@@ -770,6 +816,12 @@ int gf2_levels(Scratch& S, Scratch& R, LapTimer& T, hipStream_t st, Gf2State& g)
     T.mark(LAP_CLASSIFIED);
     // ---- 2. the last writer of every read ----
     if (const int rc = build_dag(S, st, g.ops, n, W, g.seeds.chunk, g.kbuf, g.vbuf, g.dag)) return rc;
+    if (g.keep) {  // the reads after the program, before any value is made
+        g.lastw = S.get<uint32_t>(W);
+        CDNEED(g.lastw);
+        k_cd_live<<<blocks(W, TB), TB, 0, st>>>(g.dag.sv, g.dag.seg_lo, g.dag.seg_hi, W, g.dag.uses, g.lastw);
+        CDCHK(hipGetLastError());
+    }
     T.mark(LAP_DAG);
     // ---- 3. values and levels, round by round ----
     g.V = g.lazy ? nullptr : S.get<int2>(n);
@@ -910,6 +962,11 @@ int gf2_tables(Scratch& S, Scratch& R, LapTimer& T, hipStream_t st, Gf2State& g,
     if (g.n_wb)
         k_cd_wb_gates<<<blocks(W, TB), TB, 0, st>>>(lastw, wfl, W, g.ops, g.V, g.cx, comp, seeds, pad, g.hs.n_mat, n_buckets >= 3 ? pos + 3 : nullptr,
                                                     (uint32_t)(n_gates_ops + g.n_wbmat), gates);
+    if (g.keep && W) {
+        g.wire_forms = R.get<WireForm>(W);
+        CDNEED(g.wire_forms);
+        CD_FORM(k_cd_wire_forms, blocks(W, TB), g.lastw, W, g.ops, g.V, g.V3, g.cx, comp, seeds, pad, g.wire_forms);
+    }
     CDCHK(hipGetLastError());
     CDCHK((scan_excl<uint32_t, MaxU32>(S, st, on_lvl, pm, n_on + 1, nullptr)));
     k_cd_done_on<<<blocks(n_on + 1, TB), TB, 0, st>>>(pm, on_lvl, n_on, n_levels, done_on);
@@ -932,6 +989,8 @@ int gf2_tables(Scratch& S, Scratch& R, LapTimer& T, hipStream_t st, Gf2State& g,
     CDCHK(fetch(st, h_pos, pos));
     CDCHK(fetch(st, h_need, need_raw));
     CDCHK(fetch(st, cc.level_done_on, done_on));
+    if (g.keep) cc.wire_forms.resize(W);
+    CDCHK(fetch(st, cc.wire_forms, g.wire_forms));
     T.mark(LAP_DOWNLOADED);
     CDCHK(hipStreamSynchronize(st));
     gf2_fill(cc, g, h_pos, h_need);

@@ -141,7 +141,8 @@ inline int bit_len(uint64_t v) {
 // 48-byte gate records that stay with the circuit: counters 16, two key / value pairs of the sorts 16, producers 8, read counts,
 // pending operands, consumer offsets and cursors 16, consumers 8, value 8 (the lazy-sum form: 16), level, materialised flag, frontier
 // and computed-row index 16, the sorts' histograms 0.5: 89 bytes (lazy sums: 97); 8 bytes per wire for the writer segments, and a chunk
-// 20 more for its write-back flags and last writers
+// 20 more for its write-back flags and last writers; RV_COMPILE_KEEP_WIRES: 4 bytes per GF(2) wire for the last writers, and the two wire
+// tables that stay with the circuit (16 bytes per GF(2) wire, 4 per Z64 wire)
 // (sync = false: a Scratch that outlives another one of the same stream and is destroyed right after it -- the stream is idle then)
 struct Scratch {
     const DevAlloc& A;

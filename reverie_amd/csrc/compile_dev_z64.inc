@@ -237,6 +237,14 @@ __global__ __launch_bounds__(TB) void k_z_wb_gates(const uint32_t* sv, const uin
     g.am = z_mask_row(q, ops, zc, s);
     gates[fx[w]] = g;
 }
+// RV_COMPILE_KEEP_WIRES: wire w's final SSA id, Builder::cur64 at the end of the program (a never-written wire: 0; a wire a B2A
+// wrote last: that Gate64's dst, numbered like any other op's)
+__global__ __launch_bounds__(TB) void k_z_wire_ssa(const uint32_t* sv, const uint32_t* seg_lo, const uint32_t* seg_hi, uint32_t W64, const C4* zc, Seeds64 s,
+                                                   uint32_t* ssa) {
+    const size_t w = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (w >= W64) return;
+    ssa[w] = seg_hi[w] > seg_lo[w] ? z_ssa((int)sv[seg_hi[w] - 1], zc, s) : 0u;
+}
 
 // ---- the host phases ----
 // the words the host reads back (zeroed once; the kernels get pointers to the members)
@@ -371,14 +379,30 @@ void z64_fill(Compiled& cc, const Z64State& z, uint64_t n_g64) {
     cc.info.z64_masks = z.n_masks64, cc.info.b2a = z.n_b2a;
 }
 
+// RV_COMPILE_KEEP_WIRES: Compiled::wire_ssa64 and its device copy (the result Scratch's), from the writers sort of the Z64 list
+// (z null or without Z64 entries: every wire reads as SSA 0).  Synchronises the stream.
+int z64_wire_table(Scratch& S, Scratch& R, hipStream_t st, const Z64State* z, size_t z64_wires, Compiled& cc, uint32_t** d_out) {
+    const uint32_t W64 = (uint32_t)z64_wires;
+    if (!W64) return RV_OK;
+    uint32_t* ssa = *d_out = R.get<uint32_t>(W64);
+    CDNEED(ssa);
+    if (z && z->n64) k_z_wire_ssa<<<blocks(W64, TB), TB, 0, st>>>(z->dag.sv, z->dag.seg_lo, z->dag.seg_hi, W64, z->zc, z->s64, ssa);
+    else CDCHK(hipMemsetAsync(ssa, 0, (size_t)W64 * 4, st));
+    CDCHK(hipGetLastError());
+    cc.wire_ssa64.resize(W64);
+    CDCHK(fetch(st, cc.wire_ssa64, ssa));
+    CDCHK(hipStreamSynchronize(st));
+    return RV_OK;
+}
+
 // step 4: the Z64 tables, into the Compiled gf2_tables filled (its level count is both domains') -- a stable sort by level; the records,
 // offsets and AssertZero tables written by one thread per gate; a chunk's write-back copies (one G64_ADDC per written wire, in wire
 // order) behind them.  res: gates64 and the two offset tables, the result Scratch's.
-int z64_tables(Scratch& S, Scratch& R, LapTimer& T, hipStream_t st, Z64State& z, Compiled& cc, DevCompileKeep& res) {
+int z64_tables(Scratch& S, Scratch& R, LapTimer& T, hipStream_t st, Z64State& z, bool keep_wires, Compiled& cc, DevCompileKeep& res) {
     const uint32_t n_levels = (uint32_t)cc.level_start.size() - 1, W64 = z.W64;
     cc.level_start64.assign((size_t)n_levels + 1, 0);
     const size_t n64 = z.n64;
-    if (!n64) return RV_OK;
+    if (!n64) return keep_wires ? z64_wire_table(S, R, st, &z, W64, cc, &res.d_wire_ssa64) : RV_OK;
     if (n_levels < z.levels64 + (z.n_wb64 ? 1u : 0u)) return RV_E_DEVICE;  // (cannot happen)
     T.mark(LAP_Z64_TABLES);
     const C4 tot = z.tot;
@@ -408,6 +432,8 @@ int z64_tables(Scratch& S, Scratch& R, LapTimer& T, hipStream_t st, Z64State& z,
     CDCHK(fetch(st, cc.assert_rec64, as_rec));
     CDCHK(fetch(st, cc.assert_op64, as_op));
     CDCHK(fetch(st, cc.level_start64, pos));
+    if (keep_wires)
+        if (const int rc = z64_wire_table(S, R, st, &z, W64, cc, &res.d_wire_ssa64)) return rc;
     T.mark(LAP_Z64_TABLES_END);
     CDCHK(hipStreamSynchronize(st));
     z64_fill(cc, z, n_g64);

@@ -104,7 +104,8 @@ class Circuit:
     """A gate stream compiled (levelised) and resident in HBM (rv_circuit)."""
 
     def __init__(self, ops, wire_counts: Tuple[int, int], ctx: Optional[Context] = None, whole_prover: bool = False,
-                 keep_wires: bool = False, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False):
+                 keep_wires: bool = False, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
+                 device_keep_wires: bool = False):
         """whole_prover: the circuit will mostly serve whole proofs on one GPU (Proof.new / new_batch) -- the
         RV_COMPILE_WHOLE_PROVER hint of rv_circuit_compile_ex; any use of the circuit still gives identical bytes.
         keep_wires: RV_COMPILE_KEEP_WIRES -- the circuit keeps every wire's final value form, so that `evaluate` can return
@@ -113,10 +114,17 @@ class Circuit:
         whole_prover, the lazy-sum form; anything the device path does not take is compiled on the host); the circuit is the same
         either way, and `compiled_on_device` tells which compiler made it.
         device_z64: RV_COMPILE_DEVICE_Z64, only with device_compile (ValueError otherwise) -- Z64 programs and programs that mix the
-        two domains compile on the GPU too; B2A, a SizeHint that grows a wire count and keep_wires still go to the host compiler.
+        two domains compile on the GPU too; B2A, a SizeHint that grows a wire count and keep_wires (without device_keep_wires) still go
+        to the host compiler.
         device_b2a: RV_COMPILE_DEVICE_B2A, only with device_compile and device_z64 (ValueError otherwise) -- programs with B2A ops
         compile on the GPU too (plain form: when that is final, which of these deep programs only wide ones are; with whole_prover
-        all of them)."""
+        all of them).
+        device_keep_wires: RV_COMPILE_DEVICE_KEEP_WIRES, only with keep_wires and device_compile (ValueError otherwise) -- keep_wires
+        no longer sends the program to the host compiler: the device compiler builds the wires' final forms too, in every scope the
+        other device keywords open, and `evaluate` returns the same values."""
+        if device_keep_wires and not (keep_wires and device_compile):
+            raise ValueError("device_keep_wires=True needs " + " and ".join(
+                k + "=True" for k, v in (("keep_wires", keep_wires), ("device_compile", device_compile)) if not v))
         if device_z64 and not device_compile:
             raise ValueError("device_z64=True needs device_compile=True")
         if device_b2a and not (device_compile and device_z64):
@@ -128,21 +136,26 @@ class Circuit:
         self.handle = C.c_void_p()
         flags = (_lib.RV_COMPILE_WHOLE_PROVER if whole_prover else 0) | (_lib.RV_COMPILE_KEEP_WIRES if keep_wires else 0) | \
             (_lib.RV_COMPILE_DEVICE if device_compile else 0) | (_lib.RV_COMPILE_DEVICE_Z64 if device_z64 else 0) | \
-            (_lib.RV_COMPILE_DEVICE_B2A if device_b2a else 0)
+            (_lib.RV_COMPILE_DEVICE_B2A if device_b2a else 0) | (_lib.RV_COMPILE_DEVICE_KEEP_WIRES if device_keep_wires else 0)
         _lib.check(_lib.lib().rv_circuit_compile_ex(self.ctx.handle, _ptr(self.ops), C.c_size_t(len(self.ops)),
                                                     C.c_size_t(self.wire_counts[0]), C.c_size_t(self.wire_counts[1]),
                                                     C.c_uint32(flags), C.byref(self.handle)))
 
     @classmethod
     def from_device_ops(cls, ops, wire_counts: Tuple[int, int], ctx: Optional[Context] = None, whole_prover: bool = False,
-                        keep_wires: bool = False, device_z64: bool = False, device_b2a: bool = False) -> "Circuit":
+                        keep_wires: bool = False, device_z64: bool = False, device_b2a: bool = False,
+                        device_keep_wires: bool = False) -> "Circuit":
         """rv_circuit_compile_device: compile an op list that already sits in GPU memory -- a torch tensor on the context's
         device holding packed 24-byte rv_op records, as uint8 of shape [n, 24] (or [n * 24]) or int64 / uint64 of shape [n, 3];
         contiguous.  The tensor is not copied to the host unless the device path hands the program to the host compiler; the
         caller keeps it.  The circuit is the one Circuit(host ops, device_compile=True) compiles, with whole_prover the lazy-sum
         form (also built on the device).  device_z64: RV_COMPILE_DEVICE_Z64 -- Z64 and mixed programs are compiled where they are too
         (the call itself is the device compile the bit needs).  device_b2a: RV_COMPILE_DEVICE_B2A, only with device_z64 (ValueError
-        otherwise) -- programs with B2A ops too."""
+        otherwise) -- programs with B2A ops too.  device_keep_wires: RV_COMPILE_DEVICE_KEEP_WIRES, only with keep_wires (ValueError
+        otherwise; the call itself is the device compile the bit needs) -- a keep_wires program is compiled where it is as well,
+        instead of being copied to the host."""
+        if device_keep_wires and not keep_wires:
+            raise ValueError("device_keep_wires=True needs keep_wires=True")
         if device_b2a and not device_z64:
             raise ValueError("device_b2a=True needs device_z64=True")
         d_ops, n_ops, ctx = _device_ops(ops, ctx, "from_device_ops")
@@ -153,7 +166,8 @@ class Circuit:
         self.keep_wires = bool(keep_wires)
         self.handle = C.c_void_p()
         flags = (_lib.RV_COMPILE_WHOLE_PROVER if whole_prover else 0) | (_lib.RV_COMPILE_KEEP_WIRES if keep_wires else 0) | \
-            (_lib.RV_COMPILE_DEVICE_Z64 if device_z64 else 0) | (_lib.RV_COMPILE_DEVICE_B2A if device_b2a else 0)
+            (_lib.RV_COMPILE_DEVICE_Z64 if device_z64 else 0) | (_lib.RV_COMPILE_DEVICE_B2A if device_b2a else 0) | \
+            (_lib.RV_COMPILE_DEVICE_KEEP_WIRES if device_keep_wires else 0)
         _lib.check(_lib.lib().rv_circuit_compile_device(self.ctx.handle, C.c_void_p(d_ops), C.c_size_t(n_ops),
                                                         C.c_size_t(self.wire_counts[0]), C.c_size_t(self.wire_counts[1]),
                                                         C.c_uint32(flags), C.byref(self.handle)))

@@ -9,7 +9,11 @@ RV_COMPILE_DEVICE_Z64, with the laps (z64: the split of the list and the Z64 ops
 --compiler device-b2a: that mixture with a band of B2A_OPS (default 4096) B2A ops behind it (tools/b2a_workload.py), host compile
 against the device compile under RV_COMPILE_DEVICE | RV_COMPILE_DEVICE_Z64 | RV_COMPILE_DEVICE_B2A; MIX_MULS (default 500000) sizes
 the mixture.  The host compiler of such a program is the sequential one.
-usage: python tools/compile_device_bench.py [--whole-prover] [--compiler device|device-z64|device-b2a] [reps]"""
+--keep-wires: every compile with RV_COMPILE_KEEP_WIRES, the device's with RV_COMPILE_DEVICE_KEEP_WIRES beside it (without that bit the
+flag sends the program to the host compiler); laps_nokeep_ms are the laps of the same device compile without the two flags, so the
+difference of the two lap records is the device time of the liveness and wire-table steps.  The rv_prove_ops rows are left out
+(rv_prove_ops does not keep wires).
+usage: python tools/compile_device_bench.py [--whole-prover] [--keep-wires] [--compiler device|device-z64|device-b2a] [reps]"""
 import ctypes as C
 import json
 import os
@@ -26,7 +30,7 @@ import reverie_amd  # noqa: E402
 from reverie_amd import _lib  # noqa: E402
 
 L = _lib.lib()
-args = [a for a in sys.argv[1:] if a != "--whole-prover"]
+args = [a for a in sys.argv[1:] if a not in ("--whole-prover", "--keep-wires")]
 COMPILER = "device"
 if "--compiler" in args:
     COMPILER = args[args.index("--compiler") + 1]
@@ -34,6 +38,8 @@ if "--compiler" in args:
     del args[args.index("--compiler"):args.index("--compiler") + 2]
 WP = _lib.RV_COMPILE_WHOLE_PROVER if "--whole-prover" in sys.argv[1:] else 0
 DEV = _lib.RV_COMPILE_DEVICE | (_lib.RV_COMPILE_DEVICE_Z64 if COMPILER != "device" else 0) | (_lib.RV_COMPILE_DEVICE_B2A if COMPILER == "device-b2a" else 0)
+KEEP = _lib.RV_COMPILE_KEEP_WIRES if "--keep-wires" in sys.argv[1:] else 0  # (both compilers)
+DKEEP = KEEP | (_lib.RV_COMPILE_DEVICE_KEEP_WIRES if KEEP else 0)            # (the device compiler)
 reps = int(args[0]) if args else 3
 ctx = reverie_amd.Context(0)
 seeds = np.arange(4096, dtype=np.uint32).astype(np.uint8).reshape(256, 16)
@@ -64,6 +70,19 @@ def prove_ops_ms(prog, wit, wc, flags):
         ms.append((time.perf_counter() - t) * 1e3)
     L.rv_ctx_set_compile_flags(ctx.handle, C.c_uint32(0))
     return ms[0], ms[1], bytes(p)
+
+
+LAP_NAMES = ("classify", "writers", "levels", "tables", "download", "rounds")
+
+
+def device_laps(z64):
+    laps, z = (C.c_double * 6)(), C.c_double()
+    L.rv_hook_compile_device_laps(laps)
+    d = dict(zip(LAP_NAMES, [round(x, 3) for x in laps]))
+    if z64:
+        L.rv_hook_compile_device_laps_z64(C.byref(z))
+        d["z64"] = round(z.value, 3)
+    return d
 
 
 def med(v):
@@ -103,17 +122,18 @@ if COMPILER != "device":
     for name, prog, wc in (z64_rows() if COMPILER == "device-z64" else b2a_rows()):
         path, diff = C.c_int(), C.c_int()
         assert L.rv_hook_compile_compare_device(ctx.handle, prog.ctypes.data_as(C.c_void_p), C.c_size_t(len(prog)), C.c_size_t(wc[0]),
-                                                C.c_size_t(wc[1]), C.c_uint32(WP | DEV), C.byref(path), C.byref(diff)) == 0
-        rec = {"ops": len(prog), "whole_prover": bool(WP), "device_path": path.value, "diff": diff.value, "host": [], "device": [], "laps_ms": []}
-        compile_ms(prog, wc, WP)
-        compile_ms(prog, wc, WP | DEV)
+                                                C.c_size_t(wc[1]), C.c_uint32(WP | DEV | DKEEP), C.byref(path), C.byref(diff)) == 0
+        rec = {"ops": len(prog), "whole_prover": bool(WP), "keep_wires": bool(KEEP), "device_path": path.value, "diff": diff.value, "host": [],
+               "device": [], "laps_ms": []}
+        compile_ms(prog, wc, WP | KEEP)
+        compile_ms(prog, wc, WP | DEV | DKEEP)
         for _ in range(reps):
-            rec["host"].append(compile_ms(prog, wc, WP))
-            rec["device"].append(compile_ms(prog, wc, WP | DEV))
-            laps, z = (C.c_double * 6)(), C.c_double()
-            L.rv_hook_compile_device_laps(laps)
-            L.rv_hook_compile_device_laps_z64(C.byref(z))
-            rec["laps_ms"].append(dict(zip(("classify", "writers", "levels", "tables", "download", "rounds"), [round(x, 3) for x in laps]), z64=round(z.value, 3)))
+            rec["host"].append(compile_ms(prog, wc, WP | KEEP))
+            rec["device"].append(compile_ms(prog, wc, WP | DEV | DKEEP))
+            rec["laps_ms"].append(device_laps(True))
+            if KEEP:
+                compile_ms(prog, wc, WP | DEV)
+                rec.setdefault("laps_nokeep_ms", []).append(device_laps(True))
         for k in ("host", "device"):
             v = np.array(rec[k])
             rec[k + "_ms"] = {"wall": med(v[:, 0]), "compile": med(v[:, 1]), "upload": med(v[:, 2])}
@@ -127,29 +147,32 @@ for name, p_and in (("config4", 0.5), ("all_and", 1.0)):
     wit = list(wit)
     path, diff = C.c_int(), C.c_int()
     assert L.rv_hook_compile_compare_device(ctx.handle, prog.ctypes.data_as(C.c_void_p), C.c_size_t(len(prog)), C.c_size_t(wc[0]),
-                                            C.c_size_t(wc[1]), C.c_uint32(WP | DEV if WP else 0), C.byref(path), C.byref(diff)) == 0
-    rec = {"ops": len(prog), "whole_prover": bool(WP), "device_path": path.value, "diff": diff.value, "host": [], "device": [], "laps_ms": []}
-    compile_ms(prog, wc, WP)  # (warm-up: the arena's blocks, the page-locked staging buffer)
-    compile_ms(prog, wc, WP | DEV)
+                                            C.c_size_t(wc[1]), C.c_uint32(WP | DEV | DKEEP if WP or KEEP else 0), C.byref(path), C.byref(diff)) == 0
+    rec = {"ops": len(prog), "whole_prover": bool(WP), "keep_wires": bool(KEEP), "device_path": path.value, "diff": diff.value, "host": [],
+           "device": [], "laps_ms": []}
+    compile_ms(prog, wc, WP | KEEP)  # (warm-up: the arena's blocks, the page-locked staging buffer)
+    compile_ms(prog, wc, WP | DEV | DKEEP)
     for _ in range(reps):
-        rec["host"].append(compile_ms(prog, wc, WP))
-        rec["device"].append(compile_ms(prog, wc, WP | DEV))
-        laps = (C.c_double * 6)()
-        L.rv_hook_compile_device_laps(laps)
-        rec["laps_ms"].append(dict(zip(("classify", "writers", "levels", "tables", "download", "rounds"), [round(x, 3) for x in laps])))
+        rec["host"].append(compile_ms(prog, wc, WP | KEEP))
+        rec["device"].append(compile_ms(prog, wc, WP | DEV | DKEEP))
+        rec["laps_ms"].append(device_laps(False))
+        if KEEP:
+            compile_ms(prog, wc, WP | DEV)
+            rec.setdefault("laps_nokeep_ms", []).append(device_laps(False))
     # rv_prove_ops chooses its own form (the context flag decides where it is compiled): the same rows with and without --whole-prover
-    prove_ops_ms(prog, wit, wc, 0)
-    runs = {"host": [], "device": []}
-    same = True
-    for _ in range(reps):
-        h = prove_ops_ms(prog, wit, wc, 0)
-        d = prove_ops_ms(prog, wit, wc, DEV)
-        runs["host"].append(h[:2])
-        runs["device"].append(d[:2])
-        same = same and h[2] == d[2]
-    rec["prove_ops_cold_ms"] = {k: med([r[0] for r in v]) for k, v in runs.items()}
-    rec["prove_ops_second_ms"] = {k: med([r[1] for r in v]) for k, v in runs.items()}
-    rec["prove_ops_same_bytes"] = same
+    if not KEEP:
+        prove_ops_ms(prog, wit, wc, 0)
+        runs = {"host": [], "device": []}
+        same = True
+        for _ in range(reps):
+            h = prove_ops_ms(prog, wit, wc, 0)
+            d = prove_ops_ms(prog, wit, wc, DEV)
+            runs["host"].append(h[:2])
+            runs["device"].append(d[:2])
+            same = same and h[2] == d[2]
+        rec["prove_ops_cold_ms"] = {k: med([r[0] for r in v]) for k, v in runs.items()}
+        rec["prove_ops_second_ms"] = {k: med([r[1] for r in v]) for k, v in runs.items()}
+        rec["prove_ops_same_bytes"] = same
     for k in ("host", "device"):
         v = np.array(rec[k])
         rec[k + "_ms"] = {"wall": med(v[:, 0]), "compile": med(v[:, 1]), "upload": med(v[:, 2])}
