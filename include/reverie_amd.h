@@ -296,6 +296,23 @@ int rv_prove_device(rv_ctx *ctx, const rv_circuit *c, const uint8_t *wit_gf2, si
 int rv_prove_batch(rv_ctx *ctx, const rv_circuit *c, size_t batch, const uint8_t *wit_gf2, size_t n_gf2,
                    const uint64_t *wit_z64, size_t n_z64, const uint8_t *seeds, uint8_t **proofs, size_t *proof_lens);
 
+/* rv_prove_batch with the proofs left in device memory.  Witnesses and seeds as rv_prove_batch (seeds must not be NULL, as with
+ * rv_prove_device).  dst_device + b*stride receives bincode(Proof) for witness b, repetition counts in place: the bytes
+ * rv_verify_device and rv_verify_batch_device take, byte-identical to rv_prove_batch's proof b for the same witnesses and seeds.
+ * The proof length is the same for every proof of a circuit,
+ *     32 + 4*8 + 40 * (gf2 + z64 online record sizes, rv_circuit_record_sizes) + 2 * 216 * 48,
+ * and is returned in *proof_len (also when the buffer is refused); bytes between it and `stride` are unspecified.
+ * dst_device: memory of the context's device, 256-byte aligned; stride: a multiple of 256, at least the proof length;
+ * batch * stride inside the allocation -- RV_E_ARG otherwise, before anything runs.
+ * The path is rv_prove_batch's (the one-pass path, Z64 chunks by free memory and RV_BATCH_MAX), and so are the error codes;
+ * per pass only the proofs' error words cross to the host, in one copy with one synchronisation.  A batch of one and circuits
+ * from RV_BATCH_BIG_GATES on are proved one proof after another on the context's stream, each opened straight into its place:
+ * sequential on purpose -- the worker threads of rv_prove_batch's large-circuit path exist to hide a proof's copy over PCIe
+ * behind the next proof's kernels, and this call makes no such copy. */
+int rv_prove_batch_device(rv_ctx *ctx, const rv_circuit *c, size_t batch, const uint8_t *wit_gf2, size_t n_gf2,
+                          const uint64_t *wit_z64, size_t n_z64, const uint8_t *seeds /* batch x 256 x 16, not NULL */,
+                          void *dst_device, size_t stride, size_t *proof_len);
+
 /* ---- cleartext evaluation (mcircuit::evaluate_composite_program, re-exported at src/lib.rs:6; the CLI's `oneshot`) ----
  * Evaluates the circuit on the witness in the clear, on the GPU: no shares, no transcripts.  A failing AssertZero is not an error:
  * the call returns RV_OK and the status says which assertions do not hold.  gf2_values / z64_values (NULL: not wanted) receive the
@@ -686,6 +703,18 @@ int rv_verify_multi(rv_comm *const *comms, const rv_circuit *const *circuits, in
 int rv_verify_batch(rv_ctx *ctx, const rv_circuit *c, size_t batch, const uint8_t *const *proofs, const size_t *proof_lens,
                     uint32_t flags, int *ok /* [batch] */);
 
+/* rv_verify_batch on proofs that lie in device memory: d_proofs is a HOST array of device pointers, d_proofs[b] to
+ * proof_lens[b] bytes of bincode(Proof) (what rv_prove_batch_device wrote, or any bytes).  DEFINITION: the return code and
+ * every ok[b] are exactly those of rv_verify_batch on host copies of the same byte strings, for every byte string.
+ * Every d_proofs[b] must be memory of the context's device, 16-byte aligned, with proof_lens[b] inside its allocation:
+ * RV_E_ARG otherwise, before any kernel runs.  One kernel walks every proof's framing; a proof whose walk stops (bytes that run
+ * out, wrong repetition counts, records the verifier's slots cannot take) is copied to the host, where the host verifier's
+ * own parse answers it; the others are verified where they lie and no byte of them crosses to the host -- in one pass
+ * (chunked by free memory and RV_BATCH_MAX as rv_verify_batch), or through rv_verify_device's path one after another for
+ * fewer than two such proofs, a batch of one, or a circuit from RV_BATCH_BIG_GATES on. */
+int rv_verify_batch_device(rv_ctx *ctx, const rv_circuit *c, size_t batch, const uint8_t *const *d_proofs /* host array of device pointers */,
+                           const size_t *proof_lens, uint32_t flags, int *ok /* [batch] */);
+
 /* ---- Bristol front end (host only, no GPU) ---------------------------------------------
  * The reference's README promises Bristol-format circuits; the parser itself lives in the
  * un-vendored `mcircuit` crate.  This turns Bristol text into the rv_op stream:
@@ -830,6 +859,9 @@ uint64_t rv_hook_verify_proof_bytes(void);
 /* rv_verify_device / rv_verify_sections_device calls of this process that took out[0] = the device path, out[1] = the host fallback
  * (calls refused with RV_E_ARG count as neither). */
 int rv_hook_verify_device_paths(uint64_t out[2]);
+/* Proofs rv_verify_batch_device verified in this process through out[0] = the one-pass device path, out[1] = the single-proof
+ * device verifier, out[2] = a host copy (walks that stopped); calls refused with RV_E_ARG count nowhere. */
+int rv_hook_verify_batch_device_paths(uint64_t out[3]);
 /* The framing walk of those two entry points, run on the host (no device): bytes[0, len) in framing 0 = bincode(Proof) or 1 = the
  * four sections, whose lengths the caller leaves in table[0 .. 3] (RV_E_ARG unless their sum is len).  table: 657 words (csrc/verify_dev.h)
  * -- record k = 40 * domain + i at words 8k .. 8k + 7: the offsets of keys, rec (then its length), corr (length), in (length), the

@@ -94,6 +94,7 @@ SYMBOLS = [
     "rv_stream_feed_device", "rv_eval_stream_feed_device", "rv_hook_stream_op_traffic", "rv_hook_stream_piece_sums",
     "rv_hook_compile_compare_device_chunk_ex", "rv_hook_compile_device_laps_z64",
     "rv_verify_device", "rv_verify_sections_device", "rv_hook_verify_device_paths", "rv_hook_verify_walk",
+    "rv_prove_batch_device", "rv_verify_batch_device", "rv_hook_verify_batch_device_paths",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -135,6 +136,10 @@ ARGTYPES = {
     "rv_verify_sections_device": [_P, _P, _P, _P, C.POINTER(C.c_size_t), C.c_uint32, C.POINTER(C.c_int)],
     "rv_hook_verify_device_paths": [C.POINTER(C.c_uint64)],
     "rv_hook_verify_walk": [_P, _Z, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)],
+    # batches that stay in device memory
+    "rv_prove_batch_device": [_P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _Z, C.POINTER(C.c_size_t)],
+    "rv_verify_batch_device": [_P, _P, _Z, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32, C.POINTER(C.c_int)],
+    "rv_hook_verify_batch_device_paths": [C.POINTER(C.c_uint64)],
     # the mask generators (parity hook)
     "rv_hook_maskgen": [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _P],
 }

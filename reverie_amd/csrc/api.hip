@@ -1531,6 +1531,7 @@ extern "C" int rv_challenge(const uint8_t comm[RV_HASH_SIZE], uint8_t omit[RV_TO
 #include "verify_dev.inc"
 #include "opscache.inc"
 #include "verify_batch.inc"
+#include "batch_dev.inc"
 #include "hooks.inc"
 #include "feed_ops.inc"
 #include "stream.inc"

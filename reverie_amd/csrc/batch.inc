@@ -104,12 +104,54 @@ static void launch_levels_batched(rv_ctx* ctx, const rv_circuit* c, int mode, co
     }
 }
 
+// Where a batch's proofs go.  rv_prove_batch: page-locked host buffers, proofs[b] / proof_lens[b].  rv_prove_batch_device
+// (d_dst set, proofs and proof_lens null): the caller's device buffer, proof b framed at d_dst + b * stride -- its entry point
+// has checked the buffer against the proof length -- and no proof byte goes to the host.
+struct BatchDst {
+    uint8_t** proofs;
+    size_t* proof_lens;
+    uint8_t* d_dst;
+    size_t stride;
+};
+
+// One proof, framed, straight into device memory at d_dst (rv_prove_batch_device's proof-after-proof branch): rv_prove_device_impl
+// with the framing of a whole Proof around the sections and the repetition counts from k_frame_counts; the error word is all
+// the host waits for.
+static int prove_framed_device(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64, size_t n_z64,
+                               const uint8_t* seeds, uint8_t* d_dst) {
+    rv_shard* s = nullptr;
+    int rc = rv_shard_commit_impl(ctx, c, wit_gf2, n_gf2, wit_z64, n_z64, seeds, 0, RV_TOTAL_REPS, &s, /*defer_sync=*/true);
+    if (rc) return rc;
+    do {
+        void* d = nullptr;
+        size_t lens[4];
+        if ((rc = shard_open_impl(s, nullptr, d_dst, &d, lens, true, nullptr, nullptr, /*no_sync=*/true))) break;
+        int err = 0;
+        if (!launch_frame_counts(ctx->stream, d_dst, 0, 1, lens) || hipGetLastError() != hipSuccess) {
+            rc = RV_E_DEVICE;
+            break;
+        }
+        if (hipMemcpyAsync(&err, s->d_err, sizeof err, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess) {
+            rc = hip_fail(hipGetLastError(), "rv_prove_batch_device", __FILE__, __LINE__);
+            break;
+        }
+        ctx->collect();
+        if (err) rc = RV_E_WITNESS_INVALID;
+    } while (0);
+    rv_shard_destroy(s);
+    return rc;
+}
+
 static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, const uint8_t* wit_gf2, size_t n_gf2,
-                               const uint64_t* wit_z64, size_t n_z64, const uint8_t* seeds, uint8_t** proofs, size_t* proof_lens) {
+                               const uint64_t* wit_z64, size_t n_z64, const uint8_t* seeds, const BatchDst& out) {
     LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
-    if (!ctx || !c || !proofs || !proof_lens || !batch) return RV_E_ARG;
+    uint8_t** const proofs = out.proofs;
+    size_t* const proof_lens = out.proof_lens;
+    const bool dev = out.d_dst != nullptr;
+    if (!ctx || !c || !batch || (dev ? !seeds : (!proofs || !proof_lens))) return RV_E_ARG;
     const Compiled& cc = c->cc;
-    for (size_t b = 0; b < batch; b++) proofs[b] = nullptr, proof_lens[b] = 0;
+    for (size_t b = 0; b < batch && !dev; b++) proofs[b] = nullptr, proof_lens[b] = 0;
     if (n_gf2 < cc.n_in || n_z64 < cc.n_in64) return RV_E_WITNESS_SHORT;
     if ((cc.n_in && !wit_gf2) || (cc.n_in64 && !wit_z64)) return RV_E_ARG;
     std::vector<uint8_t> os_seeds;
@@ -124,6 +166,12 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
         seeds = os_seeds.data();
     }
     auto one_by_one = [&]() {  // Z64 / mixed circuits and batches of one: the plain entry point, proof after proof
+        for (size_t b = 0; b < batch && dev; b++) {
+            int rc = prove_framed_device(ctx, c, wit_gf2 ? wit_gf2 + b * n_gf2 : nullptr, n_gf2, wit_z64 ? wit_z64 + b * n_z64 : nullptr, n_z64,
+                                         seeds + b * RV_TOTAL_REPS * 16, out.d_dst + b * out.stride);
+            if (rc) return rc;
+        }
+        if (dev) return (int)RV_OK;
         for (size_t b = 0; b < batch; b++) {
             int rc = rv_prove(ctx, c, wit_gf2 ? wit_gf2 + b * n_gf2 : nullptr, n_gf2, wit_z64 ? wit_z64 + b * n_z64 : nullptr, n_z64,
                               seeds + b * RV_TOTAL_REPS * 16, &proofs[b], &proof_lens[b]);
@@ -154,16 +202,20 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
         if (batch > chunk) {
             for (size_t b0 = 0; b0 < batch; b0 += chunk) {
                 const int rc = rv_prove_batch_impl(ctx, c, std::min(chunk, batch - b0), wit_gf2 ? wit_gf2 + b0 * n_gf2 : nullptr, n_gf2,
-                                                   wit_z64 ? wit_z64 + b0 * n_z64 : nullptr, n_z64, seeds + b0 * RV_TOTAL_REPS * 16, proofs + b0,
-                                                   proof_lens + b0);
+                                                   wit_z64 ? wit_z64 + b0 * n_z64 : nullptr, n_z64, seeds + b0 * RV_TOTAL_REPS * 16,
+                                                   dev ? BatchDst{nullptr, nullptr, out.d_dst + b0 * out.stride, out.stride}
+                                                       : BatchDst{proofs + b0, proof_lens + b0, nullptr, 0});
                 if (rc) {
-                    for (size_t k = 0; k < b0; k++) rv_free(proofs[k]), proofs[k] = nullptr, proof_lens[k] = 0;
+                    for (size_t k = 0; k < b0 && !dev; k++) rv_free(proofs[k]), proofs[k] = nullptr, proof_lens[k] = 0;
                     return rc;
                 }
             }
             return RV_OK;
         }
     }
+    // (the device form proves a large circuit's statements one after another: the workers below exist to hide a proof's trip
+    // over PCIe behind another proof's kernels, and the device form makes no such trip)
+    if (dev && cc.gates.size() >= big_gates) return one_by_one();
     if (cc.gates.size() >= big_gates) {
         // Large circuits fill the GPU on their own; what is left to gain is overlapping one proof's VALU-bound phases
         // (masks, digests) with another's memory-bound interpreter, and a third one's 50 MB trip over PCIe.  A few host
@@ -285,7 +337,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
         for (void* q : device_tmp) ctx->release(q);
         for (void* q : pinned_tmp) g_pinned.put(q);
         if (staging) g_pinned.put(staging);
-        if (code)
+        if (code && !dev)
             for (size_t b = 0; b < batch; b++) rv_free(proofs[b]), proofs[b] = nullptr, proof_lens[b] = 0;
         return code;
     };
@@ -322,8 +374,10 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
     device_tmp.push_back(d_seeds_all);
     if ((rc = dalloc(ctx, SLAB_HEAD + batch * wit_stride, &d_wit_all))) return cleanup(rc);
     device_tmp.push_back(d_wit_all);
-    if ((rc = dalloc(ctx, SLAB_HEAD + batch * out_stride, &d_out_all))) return cleanup(rc);
-    device_tmp.push_back(d_out_all);
+    if (!dev) {  // (the device form's proofs are written where the caller wants them)
+        if ((rc = dalloc(ctx, SLAB_HEAD + batch * out_stride, &d_out_all))) return cleanup(rc);
+        device_tmp.push_back(d_out_all);
+    }
     if ((rc = dalloc(ctx, SLAB_HEAD / sizeof(int) + batch, &d_err_all))) return cleanup(rc);
     device_tmp.push_back(d_err_all);
     if (hipMemcpyAsync(d_seeds_all + SLAB_HEAD, seeds, batch * (size_t)R * 16, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
@@ -392,7 +446,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
         void* d = nullptr;
         g_recorder = &recs[b];
         if (!(rc = shard_run_hash(s)) && !(rc = shard_join(s)))
-            rc = shard_open_impl(s, nullptr, d_out_all + SLAB_HEAD + b * out_stride, &d, lens, true, nullptr, nullptr, /*no_sync=*/true);
+            rc = shard_open_impl(s, nullptr, dev ? out.d_dst + b * out.stride : d_out_all + SLAB_HEAD + b * out_stride, &d, lens, true, nullptr, nullptr, /*no_sync=*/true);
         g_recorder = nullptr;
     }
     if (rc) return cleanup(rc);
@@ -402,7 +456,16 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
     ctx->phase(-1);
     mark("replay digests/openings");
     const size_t total = 32 + 4 * 8 + lens[0] + lens[1] + lens[2] + lens[3];
-    {
+    if (dev) {
+        // the counts on the device, and only the error flags to the host: one copy, one synchronisation
+        if (total > out.stride || batch > 0x3FFFFFFFu || !launch_frame_counts(ctx->stream, out.d_dst, out.stride, (uint32_t)batch, lens) ||
+            hipGetLastError() != hipSuccess)
+            return cleanup(RV_E_DEVICE);
+        staging = (uint8_t*)g_pinned.get(std::max<size_t>(batch * sizeof(int), PinnedPool::MIN_BYTES));
+        if (!staging) return cleanup(RV_E_NOMEM);
+        if (hipMemcpyAsync(staging, d_err_all + SLAB_HEAD / sizeof(int), batch * sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+            return cleanup(RV_E_DEVICE);
+    } else {
         // one page-locked staging area for the whole batch (a device-to-host copy into pageable memory would block the
         // host until the kernels have run): the proofs at their device stride, then the error flags
         if (total > out_stride) return cleanup(RV_E_DEVICE);
@@ -424,7 +487,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
         memcpy(&err, staging + slot * batch + b * sizeof(int), sizeof err);
         if (err) return cleanup(RV_E_WITNESS_INVALID);
     }
-    {
+    if (!dev) {
         // The proofs are handed out where they landed: slices of the page-locked staging buffer, which returns to the
         // pool when the last of them has been rv_free'd (no second copy into 256 freshly mapped buffers, no 256
         // munmaps in the caller: together they cost more than the GPU work of an AES-128 batch).  RV_BATCH_COPY_OUT=1
@@ -460,7 +523,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
 extern "C" int rv_prove_batch(rv_ctx* ctx, const rv_circuit* c, size_t batch, const uint8_t* wit_gf2, size_t n_gf2,
                               const uint64_t* wit_z64, size_t n_z64, const uint8_t* seeds, uint8_t** proofs, size_t* proof_lens) {
     try {  // no C++ exception may cross the C boundary
-        return rv_prove_batch_impl(ctx, c, batch, wit_gf2, n_gf2, wit_z64, n_z64, seeds, proofs, proof_lens);
+        return rv_prove_batch_impl(ctx, c, batch, wit_gf2, n_gf2, wit_z64, n_z64, seeds, BatchDst{proofs, proof_lens, nullptr, 0});
     } catch (...) {
         g_last_error = "out of host memory";
         return RV_E_NOMEM;

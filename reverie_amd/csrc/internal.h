@@ -257,6 +257,9 @@ void launch_copy_gaps(hipStream_t st, const uint8_t* d_img, uint8_t* dst_mapped,
 uint32_t extract_tile_bytes(uint64_t n_items);  // the tile of launch_extract_bits for vectors of n_items bits
 void launch_publish(hipStream_t st, const uint32_t* d_src, uint32_t n_words, uint32_t* dst_mapped, uint32_t* flag_mapped, uint32_t seq);
 void launch_store_words(hipStream_t st, const uint32_t* d_src, uint32_t n_words, uint32_t* dst_mapped, const int* d_err, int* dst_err_mapped);
+// k_frame_counts: the four repetition counts of `batch` framed proofs `stride` bytes apart at d_out, in front of sections of
+// lens[] bytes; false (nothing launched) for an empty batch or when a count would not lie on an 8-byte boundary
+bool launch_frame_counts(hipStream_t st, uint8_t* d_out, uint64_t stride, uint32_t batch, const size_t lens[4]);
 // a narrow stretch with its live wires in LDS (ldsrun.h); d_pp != null: `batch` proofs, parameters from the device array
 struct LdsRec;
 void launch_interp_lds(hipStream_t st, int mode, uint32_t QS, uint32_t NQ, const LdsRec* d_recs, uint32_t n_steps, uint32_t n_slots,

@@ -810,6 +810,30 @@ __global__ void k_store_words(const uint32_t* __restrict__ src, uint32_t n_words
 void launch_store_words(hipStream_t st, const uint32_t* d_src, uint32_t n_words, uint32_t* dst_mapped, const int* d_err, int* dst_err_mapped) {
     hipLaunchKernelGGL(k_store_words, dim3((n_words + 255) / 256), dim3(256), 0, st, d_src, n_words, dst_mapped, d_err, dst_err_mapped);
 }
+// The four repetition counts of bincode(Proof) -- 40, 216, 40, 216, u64 little-endian in front of their sections -- for `batch`
+// framed proofs that lie `stride` bytes apart (rv_prove_batch_device: the host form patches them into its copy).  One thread per
+// count; the offsets are multiples of 8 (a section is 40 records or 216 x 48 bytes) and the proofs 256-byte aligned.
+struct FrameCounts {
+    uint64_t off[4], value[4];
+};
+__global__ __launch_bounds__(256) void k_frame_counts(uint8_t* __restrict__ out, uint64_t stride, uint32_t batch, FrameCounts f) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch * 4u) return;
+    const uint32_t b = i >> 2, k = i & 3u;
+    *(uint64_t*)(out + (size_t)b * stride + f.off[k]) = f.value[k];
+}
+bool launch_frame_counts(hipStream_t st, uint8_t* d_out, uint64_t stride, uint32_t batch, const size_t lens[4]) {
+    FrameCounts f{};
+    uint64_t off = 32;
+    for (int k = 0; k < 4; k++) {
+        f.off[k] = off;
+        f.value[k] = k % 2 ? RV_PREPROCESSING_REPS : RV_ONLINE_REPS;
+        off += 8 + lens[k];
+    }
+    if (!batch || batch > 0x3FFFFFFFu || (((uintptr_t)d_out | stride | f.off[0] | f.off[1] | f.off[2] | f.off[3]) & 7)) return false;
+    hipLaunchKernelGGL(k_frame_counts, dim3((batch * 4 + 255) / 256), dim3(256), 0, st, d_out, stride, batch, f);
+    return true;
+}
 
 // ------------------------------------------------------------------------------------
 // Early corrections (api.hip, rv_prove on large GF(2) circuits).  The corrections vector of an opened repetition

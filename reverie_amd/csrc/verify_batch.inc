@@ -9,6 +9,34 @@
 // through the batched interpreter kernels in verify mode, and the slot digests plus the zero-check flags come back in
 // one copy each.  The final check (rv_verify_finish_ex) is host work per proof.
 // ------------------------------------------------------------------------------------
+// What the one-pass body (verify_batch_pass) verifies, `live` naming the proofs of the batch that take part.
+// The host form: the proofs' bytes and what parse_proof made of them.  The device form (d_proofs set; batch_dev.inc):
+// proofs that lie in device memory and whose walk ended VW_OK -- live_refs[k] has live proof k's bytes and its table in device
+// memory, heads[b] is proof b's table tail (status, the 80 omit bytes, comm) on the host.
+struct VerifyBatchSrc {
+    const uint8_t* const* proofs;
+    const size_t* proof_lens;
+    const std::vector<Parsed>* P;
+    size_t max_len;
+    const uint8_t* const* d_proofs;
+    const BatchProofRef* live_refs;
+    const uint64_t* heads;
+};
+static int verify_batch_pass(rv_ctx* ctx, const rv_circuit* c, const std::vector<size_t>& live, const VerifyBatchSrc& src, uint32_t flags, int* ok);
+
+// a one-pass chunk: what fits in half of the free device memory, at least two proofs, RV_BATCH_MAX at most (read at every call)
+static int verify_batch_chunk(rv_ctx* ctx, const Compiled& cc, size_t* chunk_out) {
+    const bool has64 = !cc.gates64.empty();
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return RV_E_DEVICE;
+    size_t per_proof = std::max<size_t>(cc.info.scratch_bytes + 3 * (size_t)std::max<uint64_t>({cc.n_in, cc.n_pre, cc.n_rec, 1}) * 256, 1);
+    if (has64) per_proof += 3 * (size_t)std::max<uint64_t>({cc.n_in64, cc.n_corr64, cc.n_rec64, 1}) * 64 * 8 + (size_t)RV_TOTAL_REPS * 128;
+    size_t chunk = std::min<size_t>(std::max<size_t>((free_b + ctx->cached_bytes) / 2 / per_proof, 2), 4096);
+    if (const char* e = getenv("RV_BATCH_MAX")) chunk = std::min<size_t>(chunk, (size_t)std::max(atoi(e), 2));
+    *chunk_out = chunk;
+    return RV_OK;
+}
+
 static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, const uint8_t* const* proofs, const size_t* proof_lens,
                                 uint32_t flags, int* ok) {
     LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
@@ -18,7 +46,6 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         if (!proofs[b]) return RV_E_ARG;
     }
     const Compiled& cc = c->cc;
-    const bool has64 = !cc.gates64.empty();
     // ---- parse.  A proof that cannot be parsed, has the wrong repetition counts (`false`, proof/mod.rs:225-230) or online records
     // the verifier's slots cannot take (check_records) is a rejected proof (ok[b] = 0) and takes no further part, not a failed
     // call: one bad proof from an untrusted peer must not keep the others from being verified.  Non-zero return codes are left
@@ -43,12 +70,8 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
     }
     HIPCHK(hipSetDevice(ctx->device));
     {  // a pass keeps one proof's working set resident per proof: larger batches run as consecutive chunks
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return RV_E_DEVICE;
-        size_t per_proof = std::max<size_t>(cc.info.scratch_bytes + 3 * (size_t)std::max<uint64_t>({cc.n_in, cc.n_pre, cc.n_rec, 1}) * 256, 1);
-        if (has64) per_proof += 3 * (size_t)std::max<uint64_t>({cc.n_in64, cc.n_corr64, cc.n_rec64, 1}) * 64 * 8 + (size_t)RV_TOTAL_REPS * 128;
-        size_t chunk = std::min<size_t>(std::max<size_t>((free_b + ctx->cached_bytes) / 2 / per_proof, 2), 4096);
-        if (const char* e = getenv("RV_BATCH_MAX")) chunk = std::min<size_t>(chunk, (size_t)std::max(atoi(e), 2));
+        size_t chunk = 0;
+        if (int rcc = verify_batch_chunk(ctx, cc, &chunk)) return rcc;
         if (batch > chunk) {
             for (size_t b0 = 0; b0 < batch; b0 += chunk) {
                 const int rc = rv_verify_batch_impl(ctx, c, std::min(chunk, batch - b0), proofs + b0, proof_lens + b0, flags, ok + b0);
@@ -57,6 +80,15 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
             return RV_OK;
         }
     }
+    return verify_batch_pass(ctx, c, live, VerifyBatchSrc{proofs, proof_lens, &P, max_len, nullptr, nullptr, nullptr}, flags, ok);
+}
+
+static int verify_batch_pass(rv_ctx* ctx, const rv_circuit* c, const std::vector<size_t>& live, const VerifyBatchSrc& src, uint32_t flags, int* ok) {
+    const Compiled& cc = c->cc;
+    const bool has64 = !cc.gates64.empty();
+    const bool dev = src.d_proofs != nullptr;  // (the slab made on the device, the proofs read where they lie)
+    const uint8_t* const* proofs = src.proofs;
+    const size_t* proof_lens = src.proof_lens;
     const size_t B = live.size();
     const uint32_t R = RV_TOTAL_REPS, NQ = R / 4;
     // ---- the staging slab: one slot per proof
@@ -85,7 +117,7 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         L.keep64 = take(has64 ? (size_t)NQ * 4 : 0);
         L.hkeys64 = take(has64 ? (size_t)R * 128 : 0);
         L.src64 = take(has64 ? (size_t)6 * R * 8 : 0);
-        L.proof = take(max_len);
+        L.proof = take(dev ? 0 : src.max_len);
         L.stride = o;
     }
     std::vector<rv_shard*> sh(B, nullptr);
@@ -110,9 +142,12 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         return code;
     };
     constexpr size_t HEAD = 256;  // (no slot pointer equals an arena block: the slabs are released exactly once)
-    uint8_t* h_slab = (uint8_t*)g_pinned.get(std::max<size_t>(L.stride * B, PinnedPool::MIN_BYTES));
-    if (!h_slab) return cleanup(RV_E_NOMEM);
-    pinned_tmp.push_back(h_slab);
+    uint8_t* h_slab = nullptr;
+    if (!dev) {
+        h_slab = (uint8_t*)g_pinned.get(std::max<size_t>(L.stride * B, PinnedPool::MIN_BYTES));
+        if (!h_slab) return cleanup(RV_E_NOMEM);
+        pinned_tmp.push_back(h_slab);
+    }
     uint8_t* d_slab = nullptr;
     int rc;
     if ((rc = dalloc(ctx, HEAD + L.stride * B, &d_slab))) return cleanup(rc);
@@ -121,8 +156,9 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
     const size_t out_stride = (size_t)R * 32 + 256;
     if ((rc = dalloc(ctx, HEAD + out_stride * B, &d_out))) return cleanup(rc);
     device_tmp.push_back(d_out);
-    std::vector<uint32_t> n_quads(B, 0);
+    std::vector<uint32_t> n_quads(B, RV_ONLINE_REPS / 4);  // (the device form: slots 0 .. 39 are the opened ones, quad words 0 .. 9)
     auto fill = [&](size_t k) {
+        const std::vector<Parsed>& P = *src.P;
         const size_t b = live[k];
         uint8_t* h = h_slab + k * L.stride;
         const SlotArrays a{h + L.seeds, h + L.omit, h + L.hkeys, h + L.hco, h + L.hco64, (uint32_t*)(h + L.keep), (uint32_t*)(h + L.onm),
@@ -131,7 +167,22 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         n_quads[k] = opened_quads(a.onm, NQ, (uint32_t*)(h + L.quads));
         memcpy(h + L.proof, proofs[b], proof_lens[b]);
     };
-    {
+    if (dev) {
+        // the slot arrays from the walks' tables, proof k's into slot k (src offsets from the proof's own first byte)
+        BatchProofRef* d_refs = nullptr;
+        if ((rc = dalloc(ctx, B, &d_refs))) return cleanup(rc);
+        device_tmp.push_back(d_refs);
+        BatchProofRef* h_refs = (BatchProofRef*)g_pinned.get(std::max<size_t>(B * sizeof(BatchProofRef), PinnedPool::MIN_BYTES));
+        if (!h_refs) return cleanup(RV_E_NOMEM);
+        pinned_tmp.push_back(h_refs);
+        memcpy(h_refs, src.live_refs, B * sizeof(BatchProofRef));
+        if (hipMemcpyAsync(d_refs, h_refs, B * sizeof(BatchProofRef), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return cleanup(RV_E_DEVICE);
+        BatchSlotLayout BL{};
+        BL.seeds = L.seeds, BL.omit = L.omit, BL.keep = L.keep, BL.onm = L.onm, BL.quads = L.quads, BL.hkeys = L.hkeys, BL.hco = L.hco, BL.hco64 = L.hco64;
+        BL.src = L.src, BL.seeds64 = L.seeds64, BL.omit64 = L.omit64, BL.keep64 = L.keep64, BL.hkeys64 = L.hkeys64, BL.src64 = L.src64, BL.stride = L.stride;
+        launch_fill_slots_batch(ctx->stream, d_refs, (uint32_t)B, d_slab + HEAD, BL, has64);
+        if (hipGetLastError() != hipSuccess) return cleanup(RV_E_DEVICE);
+    } else {
         // host work per proof (a few hundred KB of copies each): shared by a few threads for large batches
         const size_t n_thr = B >= 32 ? std::min<size_t>({(size_t)8, B / 8, (size_t)std::max(1u, std::thread::hardware_concurrency())}) : 1;
         auto range = [&](size_t k0, size_t k1) {
@@ -150,7 +201,7 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
             for (auto& x : th) x.join();
         }
     }
-    if (hipMemcpyAsync(d_slab + HEAD, h_slab, L.stride * B, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return cleanup(RV_E_DEVICE);
+    if (!dev && hipMemcpyAsync(d_slab + HEAD, h_slab, L.stride * B, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return cleanup(RV_E_DEVICE);
     // ---- per proof (recorded): keys, masks, supplied-value rows, buffers
     std::vector<InterpParams> pp(B);
     std::vector<Interp64Params> pp64(has64 ? B : 0);
@@ -158,6 +209,7 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
     constexpr uint32_t SUP_R64 = 64;
     for (size_t k = 0; k < B && !rc; k++) {
         uint8_t* d = d_slab + HEAD + k * L.stride;
+        const uint8_t* d_bytes = dev ? src.d_proofs[live[k]] : d;  // (what the src / src64 offsets count from)
         rv_shard* s = sh[k] = new rv_shard();
         s->ctx = ctx;
         s->c = c;
@@ -199,10 +251,10 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         // (k_z64_fused and the single verifier's side-stream schedule for the Z64 records -- ev_sup64, mid64 -- stay out: a fresh
         // shard's z64f is false, and the records are unpacked here, from the slot, on the main stream)
         if (!(rc = shard_setup_prg(s, (const uint32_t*)(d + L.keep), has64 ? (const uint32_t*)(d + L.keep64) : nullptr))) {
-            launch_unpack_supplied(ctx->stream, cc, d, (const uint64_t*)(d + L.src), s->d_omit, R, d_sup_in, d_sup_corr, d_sup_rec, NQ);
+            launch_unpack_supplied(ctx->stream, cc, d_bytes, (const uint64_t*)(d + L.src), s->d_omit, R, d_sup_in, d_sup_corr, d_sup_rec, NQ);
             Interp64Params p64{};
             if (has64) {
-                launch_unpack_supplied64(ctx->stream, cc, d, (const uint64_t*)(d + L.src64), s->d_omit64, R, d_sup_in64, d_sup_corr64, d_sup_rec64,
+                launch_unpack_supplied64(ctx->stream, cc, d_bytes, (const uint64_t*)(d + L.src64), s->d_omit64, R, d_sup_in64, d_sup_corr64, d_sup_rec64,
                                          SUP_R64);
                 p64.omit = s->d_omit64;
                 p64.sup_in = d_sup_in64;
@@ -262,6 +314,14 @@ static int rv_verify_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, 
         const size_t b = live[k];
         int dev_flags = 0;
         memcpy(&dev_flags, h_out + k * out_stride + (size_t)R * 32, sizeof dev_flags);
+        if (dev) {  // (verify_device_impl's decision: comm and the records' omit bytes are what the walk brought)
+            const uint64_t* head = src.heads + b * (size_t)VW_HEAD_WORDS;
+            const uint8_t* rec_omit = (const uint8_t*)(head + (VW_OMIT - VW_HEAD));
+            uint8_t omit[RV_TOTAL_REPS];
+            ok[b] = digests_give_comm((const uint8_t*)(head + (VW_COMM - VW_HEAD)), h_out + k * out_stride, omit);
+            if (verify_is_strict(flags) && ((dev_flags & RV_DEV_ZERO_CHECK) || !records_omit_challenge(omit, rec_omit, rec_omit + RV_ONLINE_REPS))) ok[b] = 0;
+            continue;
+        }
         if ((rc = rv_verify_finish_ex(proofs[b], proof_lens[b], h_out + k * out_stride, flags, !(dev_flags & RV_DEV_ZERO_CHECK), &ok[b])))
             return cleanup(rc);
     }

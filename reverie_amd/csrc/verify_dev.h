@@ -138,6 +138,25 @@ void launch_parse_proof(hipStream_t st, const uint8_t* d_bytes, uint64_t len, in
                         uint64_t* head_mapped);
 // k_fill_slots_dev on `st`: what fill_slots makes of a proof that walked to VW_OK, for groups 0 .. 31 at base offset 0
 void launch_fill_slots_dev(hipStream_t st, const uint8_t* d_bytes, const uint64_t* d_table, bool has64, const DevSlotArrays& a);
+
+// ---- the same for the proofs of a batch (rv_verify_batch_device, batch_dev.inc)
+// one proof of a batch: its bytes in device memory and, for the fill kernel, its table
+struct BatchProofRef {
+    const uint8_t* bytes;
+    uint64_t len;
+    const uint64_t* table;
+};
+// byte offsets of the slot arrays inside a proof's slot of the batch verifier's slab (verify_batch.inc: Slot), slots `stride` apart
+struct BatchSlotLayout {
+    uint64_t seeds, omit, keep, onm, quads, hkeys, hco, hco64, src, seeds64, omit64, keep64, hkeys64, src64, stride;
+};
+// k_parse_proofs on `st`: one wavefront per proof (blockIdx.x), lane 0 runs walk_proof over d_refs[b].bytes[0, len) into
+// d_tables[b][VW_WORDS]; heads[b][VW_HEAD_WORDS] (device memory, or the device address of mapped host memory) receives the
+// table's tail, zeros behind the status of a walk that stopped
+void launch_parse_proofs(hipStream_t st, const BatchProofRef* d_refs, uint32_t batch, uint64_t* d_tables, uint64_t* heads);
+// k_fill_slots_batch on `st`: k_fill_slots_dev's values for live proof k (gridDim.y) into d_slab + k * L.stride at L's offsets
+// (src offsets from the proof's own first byte), and the opened quad words 0 .. 9 into L.quads
+void launch_fill_slots_batch(hipStream_t st, const BatchProofRef* d_refs, uint32_t n_live, uint8_t* d_slab, const BatchSlotLayout& L, bool has64);
 #endif
 
 }  // namespace rv

@@ -31,8 +31,23 @@ __global__ __launch_bounds__(64) void k_parse_proof(const uint8_t* __restrict__ 
     }
 }
 
-__global__ __launch_bounds__(FILL_TB) void k_fill_slots_dev(const uint8_t* __restrict__ p, const uint64_t* __restrict__ t, int has64, DevSlotArrays a) {
-    const uint32_t tid = blockIdx.x * FILL_TB + threadIdx.x, nth = gridDim.x * FILL_TB;
+// k_parse_proof for the proofs of a batch: block b's first lane walks proof b into tables[b] and leaves the tail -- status, omit
+// bytes, comm -- in heads[b], a dense block of its own (device memory or mapped host memory: the host reads nothing else)
+__global__ __launch_bounds__(64) void k_parse_proofs(const BatchProofRef* __restrict__ refs, uint64_t* __restrict__ tables,
+                                                     uint64_t* __restrict__ heads) {
+    if (threadIdx.x != 0) return;
+    const BatchProofRef ref = refs[blockIdx.x];
+    uint64_t* table = tables + (size_t)blockIdx.x * VW_WORDS;
+    uint64_t* head = heads + (size_t)blockIdx.x * VW_HEAD_WORDS;
+    const uint64_t l[4] = {0, 0, 0, 0};
+    const int status = walk_proof(ref.bytes, ref.len, VW_FRAMING_PROOF, l, table);
+    head[0] = (uint64_t)status;
+    for (int i = 1; i < VW_HEAD_WORDS; i++) head[i] = status == VW_OK ? table[VW_HEAD + i] : 0;
+}
+
+// the slot arrays of one proof from its table (tid of nth threads)
+__device__ __forceinline__ void fill_slots_body(const uint8_t* __restrict__ p, const uint64_t* __restrict__ t, int has64, const DevSlotArrays& a,
+                                                uint32_t tid, uint32_t nth) {
     const uint8_t* om = (const uint8_t*)(t + VW_OMIT);
     const uint64_t pre2 = t[VW_PRE], pre64 = t[VW_PRE + 1];
     // per slot: omit (8: not opened) and the three vectors' places -- a GF(2) vector has the length of its group's first record,
@@ -93,6 +108,27 @@ __global__ __launch_bounds__(FILL_TB) void k_fill_slots_dev(const uint8_t* __res
     }
 }
 
+__global__ __launch_bounds__(FILL_TB) void k_fill_slots_dev(const uint8_t* __restrict__ p, const uint64_t* __restrict__ t, int has64, DevSlotArrays a) {
+    fill_slots_body(p, t, has64, a, blockIdx.x * FILL_TB + threadIdx.x, gridDim.x * FILL_TB);
+}
+
+// k_fill_slots_dev for the live proofs of a batch (gridDim.y): proof k's arrays go into its slot of the verifier's slab, at the
+// offsets of L, and the opened quad words -- 0 .. 9, from the slot order alone -- into the slot's quads
+__global__ __launch_bounds__(FILL_TB) void k_fill_slots_batch(const BatchProofRef* __restrict__ refs, uint8_t* __restrict__ slab, BatchSlotLayout L,
+                                                              int has64) {
+    const BatchProofRef ref = refs[blockIdx.y];
+    uint8_t* d = slab + (size_t)blockIdx.y * L.stride;
+    DevSlotArrays a{};
+    a.seeds = d + L.seeds, a.omit = d + L.omit, a.hkeys = d + L.hkeys, a.hco = d + L.hco, a.hco64 = d + L.hco64;
+    a.keep = (uint32_t*)(d + L.keep), a.onm = (uint32_t*)(d + L.onm), a.src = (uint64_t*)(d + L.src);
+    a.seeds64 = d + L.seeds64, a.omit64 = d + L.omit64, a.hkeys64 = d + L.hkeys64;
+    a.keep64 = (uint32_t*)(d + L.keep64), a.src64 = (uint64_t*)(d + L.src64);
+    const uint32_t tid = blockIdx.x * FILL_TB + threadIdx.x, nth = gridDim.x * FILL_TB;
+    fill_slots_body(ref.bytes, ref.table, has64, a, tid, nth);
+    uint32_t* quads = (uint32_t*)(d + L.quads);
+    for (uint32_t q = tid; q < R / 4; q += nth) quads[q] = q < ON / 4 ? q : 0u;
+}
+
 }  // namespace
 
 void launch_parse_proof(hipStream_t st, const uint8_t* d_bytes, uint64_t len, int framing, const uint64_t* d_lens, uint64_t* d_table,
@@ -102,6 +138,15 @@ void launch_parse_proof(hipStream_t st, const uint8_t* d_bytes, uint64_t len, in
 
 void launch_fill_slots_dev(hipStream_t st, const uint8_t* d_bytes, const uint64_t* d_table, bool has64, const DevSlotArrays& a) {
     hipLaunchKernelGGL(k_fill_slots_dev, dim3(FILL_GROUPS), dim3(FILL_TB), 0, st, d_bytes, d_table, has64 ? 1 : 0, a);
+}
+
+void launch_parse_proofs(hipStream_t st, const BatchProofRef* d_refs, uint32_t batch, uint64_t* d_tables, uint64_t* heads) {
+    hipLaunchKernelGGL(k_parse_proofs, dim3(batch), dim3(64), 0, st, d_refs, d_tables, heads);
+}
+
+void launch_fill_slots_batch(hipStream_t st, const BatchProofRef* d_refs, uint32_t n_live, uint8_t* d_slab, const BatchSlotLayout& L, bool has64) {
+    constexpr int GROUPS = 8;  // (a proof's share of the grid: 256 proofs fill the chip many times over)
+    hipLaunchKernelGGL(k_fill_slots_batch, dim3(GROUPS, n_live), dim3(FILL_TB), 0, st, d_refs, d_slab, L, has64 ? 1 : 0);
 }
 
 }  // namespace rv

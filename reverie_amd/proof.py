@@ -530,6 +530,88 @@ def verify_batch(circuit, proofs, wire_counts: Optional[Tuple[int, int]] = None,
     return [bool(x) for x in ok]
 
 
+def prove_batch_device(circuit: "Circuit", wits_gf2, wits_z64=None, seeds=None, ctx: Optional[Context] = None) -> "list[DeviceProof]":
+    """rv_prove_batch_device: Proof.new_batch with the proofs left in GPU memory.  -> one DeviceProof (bincode form) per witness,
+    all of them views of ONE torch uint8 GPU tensor of batch * stride bytes (stride: the proof length -- 64 + 40 * the circuit's
+    record sizes + 2 * 216 * 48 -- rounded up to 256), which every view keeps alive.  Proof b's bytes are those of
+    Proof.new_batch(...)[b] for the same witnesses and seeds.  wits_gf2: [B][n] bits; wits_z64: [B][m] words or None; seeds:
+    [B][256][16] bytes, None draws them from the OS (the entry point takes no NULL)."""
+    import os
+
+    import torch
+
+    if not isinstance(circuit, Circuit):
+        raise TypeError("prove_batch_device takes a compiled Circuit")
+    if ctx is not None and ctx is not circuit.ctx:
+        raise ValueError("the circuit was compiled in another context")
+    g = np.ascontiguousarray(np.asarray(wits_gf2, dtype=np.uint8))
+    if g.ndim != 2:
+        raise ValueError("wits_gf2 must be [batch][n_bits]")
+    batch = g.shape[0]
+    if batch == 0:
+        return []
+    z = np.ascontiguousarray(np.asarray(wits_z64 if wits_z64 is not None else np.zeros((batch, 0)), dtype=np.uint64))
+    if z.ndim != 2 or z.shape[0] != batch:
+        raise ValueError("wits_z64 must be [batch][n_words]")
+    if seeds is None:
+        seeds = np.frombuffer(os.urandom(batch * TOTAL_REPS * 16), np.uint8)
+    s = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint8)).reshape(batch, TOTAL_REPS, 16)
+    sz2, sz64 = circuit.record_sizes()
+    want = 32 + 4 * 8 + 40 * (sz2 + sz64) + 2 * (TOTAL_REPS - 40) * 48
+    stride = (want + 255) & ~255
+    out = torch.empty(batch * stride, dtype=torch.uint8, device=f"cuda:{circuit.ctx.device}")
+    n = C.c_size_t()
+    _lib.check(_lib.lib().rv_prove_batch_device(circuit.ctx.handle, circuit.handle, C.c_size_t(batch), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z),
+                                                C.c_size_t(z.shape[1]), _ptr(s), C.c_void_p(out.data_ptr()), C.c_size_t(stride), C.byref(n)))
+    if n.value != want:
+        raise _lib.ReverieError(7, f"proof length {n.value}, expected {want}")
+    proofs = []
+    for b in range(batch):  # (views made directly: the call has waited for its stream, a device-wide wait per view is not needed)
+        dp = DeviceProof.__new__(DeviceProof)
+        dp.lens, dp._comm, dp.ctx = None, None, circuit.ctx
+        dp.tensor = out[b * stride:b * stride + want]
+        dp._ptr, dp._len = out.data_ptr() + b * stride, want
+        proofs.append(dp)
+    return proofs
+
+
+def verify_batch_device(circuit: "Circuit", proofs, strict: bool = True) -> "list[bool]":
+    """rv_verify_batch_device: verify_batch on proofs that lie in GPU memory -- DeviceProof objects in bincode form (what
+    prove_batch_device returns) or contiguous one-dimensional uint8 GPU tensors on the circuit's device, each starting on a 16-byte
+    boundary.  -> one bool per proof, each what verify_batch gives host copies of the same bytes.  A sections-form DeviceProof, a
+    CPU tensor or any other object raises TypeError before the library is called (batched sections are not supported)."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    items = []
+    for p in proofs:
+        if isinstance(p, DeviceProof):
+            if p.lens is not None:
+                raise TypeError("verify_batch_device takes bincode-form proofs; a sections-form DeviceProof verifies on its own")
+            items.append((p._ptr, p._len, p.ctx.device, p))
+        elif torch is not None and isinstance(p, torch.Tensor) and p.device.type == "cuda":
+            if p.dtype != torch.uint8 or p.dim() != 1 or not p.is_contiguous():
+                raise ValueError(f"verify_batch_device takes contiguous one-dimensional uint8 tensors, got {p.dtype} {tuple(p.shape)}")
+            items.append((p.data_ptr(), p.numel(), p.device.index, p))
+        else:
+            raise TypeError("verify_batch_device takes DeviceProof objects or uint8 torch tensors in GPU memory")
+    if not isinstance(circuit, Circuit):
+        raise TypeError("verify_batch_device takes a compiled Circuit")
+    n = len(items)
+    if n == 0:
+        return []
+    for _, _, dev, _ in items:
+        if dev is not None and dev != circuit.ctx.device:
+            raise ValueError(f"a proof is on device {dev}, the circuit's context on device {circuit.ctx.device}")
+    torch.cuda.synchronize(circuit.ctx.device)  # (the bytes are complete before the library's stream reads them)
+    ptrs = (C.c_void_p * n)(*[it[0] for it in items])
+    lens = (C.c_size_t * n)(*[it[1] for it in items])
+    ok = (C.c_int * n)()
+    flags = 0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT
+    _lib.check(_lib.lib().rv_verify_batch_device(circuit.ctx.handle, circuit.handle, C.c_size_t(n), ptrs, lens, C.c_uint32(flags), ok))
+    return [bool(x) for x in ok]
+
+
 # ---- Fiat-Shamir helpers (host) ----
 def combine_digests(h) -> bytes:
     h = np.ascontiguousarray(np.asarray(h, dtype=np.uint8)).reshape(TOTAL_REPS, 32)

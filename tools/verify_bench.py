@@ -8,7 +8,14 @@ the verifier's wall time per call with the proof where that mode has it --
     device    rv_verify_device on the same bytes in a torch GPU tensor
     sections  rv_verify_sections_device on what rv_prove_device left in GPU memory
 as median, min and max over --calls calls after --warmup calls, with the calls that took the device path and the proof bytes
-the verifier uploaded (rv_hook_verify_device_paths, rv_hook_verify_proof_bytes).  --only-headline leaves the all-AND variant out."""
+the verifier uploaded (rv_hook_verify_device_paths, rv_hook_verify_proof_bytes).  --only-headline leaves the all-AND variant out.
+
+--batch N (with --proof host and / or device; --circuit aes128, sha256 or mixed, repeatable) times the batch entry points instead,
+N proofs per call, all modes in one process on the same statements, one JSON line per circuit:
+    host      rv_prove_batch, and rv_verify_batch on its proofs
+    device    rv_prove_batch_device, and rv_verify_batch_device on what it left in GPU memory
+each as median, min and max ms per call (and the median per proof) over --calls calls after --warmup, with the ways the device
+verifier's proofs went (rv_hook_verify_batch_device_paths).  The device prover's bytes are compared with the host prover's first."""
 import argparse
 import json
 import os
@@ -30,6 +37,9 @@ ap.add_argument("--proof", action="append", choices=("host", "device", "sections
                 help="also time the verifier with the proof in host memory / in a GPU tensor / as rv_prove_device's sections")
 ap.add_argument("--calls", type=int, default=9, help="timed calls per --proof mode (median, min, max)")
 ap.add_argument("--warmup", type=int, default=2, help="untimed calls per --proof mode")
+ap.add_argument("--batch", type=int, default=0, help="time the batch entry points at this many proofs per call instead")
+ap.add_argument("--circuit", action="append", choices=("aes128", "sha256", "mixed"), default=[],
+                help="--batch: the circuit (default aes128); mixed: the 2 000-gate mixed circuit of tools/batch_z64.py")
 ap.add_argument("--only-headline", action="store_true", help="the headline circuit only (p_and = 0.5)")
 args = ap.parse_args()
 
@@ -69,6 +79,71 @@ def verify_modes(c, wit, proof):
                      "ok": bool(ok), "device_path_calls": d1 - d0, "proof_bytes_uploaded": b1 - b0}
     return out
 
+
+def batch_modes(name, B):
+    """the batch entry points on B statements of one circuit: {"prove": {mode: ...}, "verify": {mode: ...}}"""
+    import ctypes as C
+
+    from reverie_amd import _lib
+
+    L = _lib.lib()
+    if name == "mixed":
+        import z64_batch_circuits as zc
+
+        prog, w2, w64, wc = zc.mixed(5, n_gates=2000)
+    else:
+        import bench
+
+        prog, w2, wc, _ = bench.bristol_case(name)
+        w64 = []
+    c = reverie_amd.Circuit(prog, wc, whole_prover=True)
+    bs = np.random.default_rng(B).integers(0, 256, (B, 256, 16), dtype=np.uint8)
+    g = np.tile(np.asarray(w2, np.uint8).reshape(1, -1), (B, 1))
+    z = np.tile(np.asarray(w64, np.uint64).reshape(1, -1), (B, 1))
+    zz = z if z.shape[1] else None
+
+    def paths():
+        out = (C.c_uint64 * 3)()
+        L.rv_hook_verify_batch_device_paths(out)
+        return [int(x) for x in out]
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        ts = []
+        for _ in range(args.calls):
+            t0 = time.perf_counter()
+            r = fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        med = statistics.median(ts)
+        return r, {"median_ms": round(med, 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4), "ms_per_proof": round(med / B, 5),
+                   "calls": args.calls}
+
+    host = reverie_amd.Proof.new_batch(c, g, zz, seeds=bs)
+    dev = reverie_amd.prove_batch_device(c, g, zz, seeds=bs)
+    if [bytes(p) for p in host] != [d.tensor.cpu().numpy().tobytes() for d in dev]:
+        raise SystemExit(f"{name}: rv_prove_batch_device's bytes differ from rv_prove_batch's")
+    out = {"circuit": name, "batch": B, "proof_bytes": len(host[0]), "prove": {}, "verify": {}}
+    for mode in args.proof:
+        if mode == "host":
+            _, out["prove"][mode] = timed(lambda: reverie_amd.Proof.new_batch(c, g, zz, seeds=bs))
+            ok, out["verify"][mode] = timed(lambda: reverie_amd.verify_batch(c, host))
+        elif mode == "device":
+            _, out["prove"][mode] = timed(lambda: reverie_amd.prove_batch_device(c, g, zz, seeds=bs))
+            p0 = paths()
+            ok, out["verify"][mode] = timed(lambda: reverie_amd.verify_batch_device(c, dev))
+            out["verify"][mode]["paths"] = [a - b for a, b in zip(paths(), p0)]
+        else:
+            raise SystemExit("--batch takes --proof host and --proof device")
+        out["verify"][mode]["ok"] = all(ok)
+    c.close()
+    return out
+
+
+if args.batch:
+    for name in args.circuit or ["aes128"]:
+        print(json.dumps(batch_modes(name, args.batch)), flush=True)
+    sys.exit(0)
 
 seeds = np.random.default_rng(1).integers(0, 256, (256, 16), dtype=np.uint8)
 for p_and in (0.5,) if args.only_headline else (0.5, 1.0):
