@@ -768,6 +768,47 @@ int rv_hook_sharegen_z64(rv_ctx *ctx, const uint8_t *keys, const uint32_t omit[8
  * first_block + n_blocks > 2^24; RV_E_ARG for any other R, an omit value above 8, n_blocks == 0, an unknown generator or key path. */
 int rv_hook_maskgen(rv_ctx *ctx, const uint8_t *seeds, uint32_t R, const uint8_t *omit, uint32_t generator, uint32_t key_path,
                     uint64_t first_block, uint64_t n_blocks, void *out);
+/* ---- the opening and unpacking kernels, one production launch each on caller-supplied data (csrc/open.hip, csrc/z64.hip; the Pack /
+ * PackSelected implementations of algebra/gf2/{share,recon}.rs and algebra/z64/{share,recon}.rs).  A shard of R repetitions (a multiple
+ * of 8, at most 256) has rows of NQ = R/4 quad words; omit[R] holds 0..7 = the opened repetition's omitted player, 8 = not opened.
+ * Every output buffer is read first and returned whole, so a byte the launch does not write keeps the caller's fill.  All of them
+ * return RV_E_ARG before anything is launched for an R that is not as above, an omit value above 8, more than RV_ONLINE_REPS opened
+ * repetitions (the kernels clamp there and no caller exceeds it), or a vector that does not lie inside its buffer. ---- */
+/* launch_extract_bits: the opened repetitions' packed vectors (n_items / 8 + 1 bytes, item i at bit 7 - i % 8 of byte i / 8) of items
+ * rows[0 .. n_items) (NULL: 0, 1, ...) of stream [stream_rows][NQ] u32, repetition r's at out + dst_off[r].  kind 0: the omitted player's
+ * bit of a share row; 1: a reconstruction row's 0x00 / 0xFF byte.  out2 (kind 0; NULL or out_bytes like out) and n_direct: the first
+ * n_direct tiles also go, in whole aligned 16-byte words, to out2.  gaps (NULL or 8 words; needs out2): k_copy_gaps then copies the
+ * image `out` into out2 around the corrections vectors of the first opened records -- gaps = {first, rec, corr_at, corr_len, n_rec,
+ * rep_limit, rvec_at, od}: n_rec <= 40 records of rec bytes from byte `first`, the corrections at [corr_at, corr_at + corr_len) of each,
+ * left out for the opened repetitions below rep_limit <= 256; od != 0: it also leaves out the words the extraction has sent, the
+ * vectors lying at rvec_at of their records (dst_off[r] = first + j * rec + rvec_at for the j-th opened repetition is the caller's
+ * part).  *tile = the tile of the launch in bytes. */
+int rv_hook_extract_bits(rv_ctx *ctx, const uint32_t *stream, uint64_t stream_rows, const uint32_t *rows, uint64_t n_items, uint32_t R, int kind,
+                         const uint8_t *omit, const uint64_t *dst_off, uint8_t *out, uint64_t out_bytes, uint8_t *out2, uint32_t n_direct,
+                         const uint64_t *gaps, uint32_t *tile);
+/* launch_extract_from_bits: the same vectors from a bit-per-repetition stream [n_items][R/8] bytes (bit k of nibble q of a row =
+ * repetition 4q + 3 - k), through the list of opened repetitions as the challenge kernel builds it from omit and dst_off; the
+ * repetitions below rep_min are left out.  *tile as above. */
+int rv_hook_extract_from_bits(rv_ctx *ctx, const uint8_t *bits, uint64_t n_items, uint32_t R, const uint8_t *omit, const uint64_t *dst_off,
+                              uint32_t rep_min, uint8_t *out, uint64_t out_bytes, uint32_t *tile);
+/* launch_pack_corr_all: bytes [byte0, byte0 + n_bytes) of ALL 256 repetitions' vectors of a stream [n_items][32], repetition r's at
+ * out + r * pitch; out is 256 * pitch bytes.  The kernel writes whole 16-byte words: up to 15 bytes behind n_bytes are padding.
+ * RV_E_ARG for a pitch that is not a multiple of 128 (or above 2^24) and for n_bytes > pitch. */
+int rv_hook_pack_corr_all(rv_ctx *ctx, const uint8_t *bits, uint64_t n_items, uint64_t byte0, uint64_t n_bytes, uint64_t pitch, uint8_t *out);
+/* launch_unpack_bits: rows_out [n_items][out_nq] u32 from the opened repetitions' vectors at blob + src_off[r], src_len[r] bytes each
+ * (items past a vector's end are zero); row 0 is item first_item of the vectors.  out_nq = R/4, or 16 when R > 64 and no repetition
+ * from 64 on is opened (RV_E_ARG otherwise: the kernel relies on it). */
+int rv_hook_unpack_bits(rv_ctx *ctx, const uint8_t *blob, uint64_t blob_bytes, const uint64_t *src_off, const uint64_t *src_len, const uint8_t *omit,
+                        uint64_t n_items, uint32_t R, int kind, uint32_t out_nq, uint64_t first_item, uint32_t *rows_out);
+/* launch_extract64: 8 bytes little-endian per item, word offs[i] (NULL: i) + (add_omit ? omit[r] : 0) of repetition r's stream
+ * [R][stride_words] u64, to out + dst_off[r].  use_list = 0: the kernel with a thread per (repetition, item); 1: the one over the list
+ * of opened repetitions, which leaves out those below rep_min. */
+int rv_hook_extract64(rv_ctx *ctx, const uint64_t *stream, uint64_t stride_words, const uint64_t *offs, uint64_t n_items, int add_omit, uint32_t R,
+                      const uint8_t *omit, const uint64_t *dst_off, int use_list, uint32_t rep_min, uint8_t *out, uint64_t out_bytes);
+/* launch_unpack64: out [n_items][out_r] u64 from vectors of 8-byte items as above (an item that is not whole reads as zero).
+ * out_r = R, or 64 when R > 64 and no repetition from 64 on is opened (RV_E_ARG otherwise). */
+int rv_hook_unpack64(rv_ctx *ctx, const uint8_t *blob, uint64_t blob_bytes, const uint64_t *src_off, const uint64_t *src_len, const uint8_t *omit,
+                     uint64_t n_items, uint32_t R, uint32_t out_r, uint64_t *out);
 /* The gate-stream compiler alone (host only, no device: ctx-free): what rv_circuit_compile_ex would report through
  * rv_circuit_get_info -- the counters that are pure functions of the op list (ShareGen::next() calls per repetition,
  * generator/share.rs:54-65; transcript events, prover.rs:194,210,216), dependency levels, operand rows -- and the errors the

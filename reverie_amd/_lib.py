@@ -95,6 +95,7 @@ SYMBOLS = [
     "rv_hook_compile_compare_device_chunk_ex", "rv_hook_compile_device_laps_z64",
     "rv_verify_device", "rv_verify_sections_device", "rv_hook_verify_device_paths", "rv_hook_verify_walk",
     "rv_prove_batch_device", "rv_verify_batch_device", "rv_hook_verify_batch_device_paths",
+    "rv_hook_extract_bits", "rv_hook_extract_from_bits", "rv_hook_pack_corr_all", "rv_hook_unpack_bits", "rv_hook_extract64", "rv_hook_unpack64",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -142,6 +143,13 @@ ARGTYPES = {
     "rv_hook_verify_batch_device_paths": [C.POINTER(C.c_uint64)],
     # the mask generators (parity hook)
     "rv_hook_maskgen": [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _P],
+    # the opening and unpacking kernels (parity hooks)
+    "rv_hook_extract_bits": [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, C.c_int, _P, _P, _P, C.c_uint64, _P, C.c_uint32, _P, C.POINTER(C.c_uint32)],
+    "rv_hook_extract_from_bits": [_P, _P, C.c_uint64, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint32)],
+    "rv_hook_pack_corr_all": [_P, _P, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _P],
+    "rv_hook_unpack_bits": [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint64, _P],
+    "rv_hook_extract64": [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_int, C.c_uint32, _P, _P, C.c_int, C.c_uint32, _P, C.c_uint64],
+    "rv_hook_unpack64": [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P],
 }
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1

@@ -217,3 +217,239 @@ extern "C" int rv_hook_z64_reconstruct(rv_ctx* ctx, const uint64_t* shares, size
     ctx->release(d_out);
     return RV_OK;
 }
+
+// ------------------------------------------------------------------------------------
+// The opening and unpacking kernels (open.hip, z64.hip), one production launch at a time on caller-supplied data: the launch_*
+// function is called unchanged, so the tile and the grid are production's.  Every output buffer arrives pre-filled, is uploaded
+// before the launch and comes back whole: a byte the launch did not write keeps the caller's fill.  Whatever a kernel relies on
+// its callers for (offsets inside the buffers, at most RV_ONLINE_REPS opened repetitions, an out_nq / out_r that holds every
+// opened repetition) is checked here on the host, RV_E_ARG before anything is allocated or launched.
+// ------------------------------------------------------------------------------------
+namespace {
+constexpr uint64_t HOOK_MAX = 1ull << 36;  // items / bytes: far above any test, far below where the checks' sums could wrap
+
+// device buffers of one hook call, back in the arena on every return path
+struct HookBufs {
+    rv_ctx* ctx;
+    std::vector<void*> owned;
+    explicit HookBufs(rv_ctx* c) : ctx(c) {}
+    ~HookBufs() {
+        for (void* p : owned) ctx->release(p);
+    }
+    template <class T>
+    int up(const T* src, size_t count, T** d) {  // count elements from the host (src may be NULL when count is 0)
+        int rc = dalloc(ctx, std::max<size_t>(count, 1), d);
+        if (rc) return rc;
+        owned.push_back(*d);
+        if (count) HIPCHK(hipMemcpyAsync(*d, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        return RV_OK;
+    }
+    template <class T>
+    int down(T* dst, const T* d, size_t count) {
+        if (count) HIPCHK(hipMemcpyAsync(dst, d, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        return RV_OK;
+    }
+};
+
+// a shard's opening map: R a multiple of 8 up to 256, values 0..8, at most RV_ONLINE_REPS below 8 (ex_slots clamps there)
+bool hook_map_ok(uint32_t R, const uint8_t* omit) {
+    if (!omit || !R || R % 8 || R > RV_TOTAL_REPS) return false;
+    uint32_t n_on = 0;
+    for (uint32_t r = 0; r < R; r++) {
+        if (omit[r] > 8) return false;
+        n_on += omit[r] < 8;
+    }
+    return n_on <= RV_ONLINE_REPS;
+}
+// [at[r], at[r] + len[r]) (or + fixed) inside a buffer of `bytes`, for every opened repetition
+bool hook_ranges_ok(uint32_t R, const uint8_t* omit, const uint64_t* at, const uint64_t* len, uint64_t fixed, uint64_t bytes) {
+    if (!at) return false;
+    for (uint32_t r = 0; r < R; r++) {
+        const uint64_t l = len ? len[r] : fixed;
+        if (omit[r] < 8 && (at[r] > bytes || l > bytes - at[r])) return false;
+    }
+    return true;
+}
+// the OnlineList of a map as k_fs_challenge leaves it: the opened repetitions in order, each with its vector's offset
+OnlineList hook_online_list(uint32_t R, const uint8_t* omit, const uint64_t* dst_off) {
+    OnlineList ol{};
+    for (uint32_t r = 0; r < R; r++)
+        if (omit[r] < 8) {
+            ol.rep[ol.n] = r;
+            ol.dst[ol.n] = dst_off[r];
+            ol.n++;
+        }
+    return ol;
+}
+}  // namespace
+
+extern "C" int rv_hook_extract_bits(rv_ctx* ctx, const uint32_t* stream, uint64_t stream_rows, const uint32_t* rows, uint64_t n_items, uint32_t R, int kind,
+                                    const uint8_t* omit, const uint64_t* dst_off, uint8_t* out, uint64_t out_bytes, uint8_t* out2, uint32_t n_direct,
+                                    const uint64_t* gaps, uint32_t* tile) {
+    if (!ctx || !out || !tile || (kind != 0 && kind != 1) || !hook_map_ok(R, omit)) return RV_E_ARG;
+    if (n_items > HOOK_MAX || stream_rows > HOOK_MAX || out_bytes > HOOK_MAX || (stream_rows && !stream)) return RV_E_ARG;
+    const uint64_t n_bytes = n_items / 8 + 1;
+    if (!hook_ranges_ok(R, omit, dst_off, nullptr, n_bytes, out_bytes)) return RV_E_ARG;
+    if (rows) {
+        for (uint64_t i = 0; i < n_items; i++)
+            if (rows[i] >= stream_rows) return RV_E_ARG;
+    } else if (n_items > stream_rows) {
+        return RV_E_ARG;
+    }
+    if ((n_direct || gaps) && (!out2 || kind != 0)) return RV_E_ARG;
+    OpenDirect od;
+    if (gaps) {
+        // {first, rec, corr_at, corr_len, n_rec, rep_limit, rvec_at, with OpenDirect}: n_rec records of rec bytes from `first` inside the image,
+        // each with its corrections inside it and -- for k_copy_gaps to leave words out -- its broadcast vector in front of them
+        const uint64_t first = gaps[0], rec = gaps[1], corr_at = gaps[2], corr_len = gaps[3], n_rec = gaps[4], rep_limit = gaps[5], rvec_at = gaps[6];
+        if (n_rec > RV_ONLINE_REPS || rep_limit > RV_TOTAL_REPS || first > out_bytes || rec > out_bytes || n_rec * rec > out_bytes - first) return RV_E_ARG;
+        if (corr_at > rec || corr_len > rec - corr_at) return RV_E_ARG;
+        if (gaps[7]) {
+            if (rvec_at > corr_at || n_bytes > corr_at - rvec_at) return RV_E_ARG;
+            od.n_direct = n_direct, od.tile = extract_tile_bytes(n_items), od.rvec_at = rvec_at, od.rvec_len = n_bytes;
+        }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    const uint32_t NQ = R / 4;
+    uint8_t omit_all[RV_TOTAL_REPS];  // (k_copy_gaps counts over the whole proof's map)
+    for (uint32_t r = 0; r < RV_TOTAL_REPS; r++) omit_all[r] = r < R ? omit[r] : (uint8_t)8;
+    HookBufs B(ctx);
+    uint32_t *d_stream = nullptr, *d_rows = nullptr;
+    uint8_t *d_omit = nullptr, *d_out = nullptr, *d_out2 = nullptr;
+    uint64_t* d_dst = nullptr;
+    int rc;
+    if ((rc = B.up(stream, (size_t)stream_rows * NQ, &d_stream)) || (rows && (rc = B.up(rows, (size_t)n_items, &d_rows))) ||
+        (rc = B.up(omit_all, (size_t)RV_TOTAL_REPS, &d_omit)) || (rc = B.up(dst_off, (size_t)R, &d_dst)) || (rc = B.up(out, (size_t)out_bytes, &d_out)) ||
+        (out2 && (rc = B.up(out2, (size_t)out_bytes, &d_out2))))
+        return rc;
+    launch_extract_bits(ctx->stream, d_stream, d_rows, n_items, NQ, kind, d_omit, d_dst, d_out, d_out2, n_direct);
+    if (gaps)
+        launch_copy_gaps(ctx->stream, d_out, d_out2, out_bytes, gaps[0], gaps[1], gaps[2], gaps[3], (uint32_t)gaps[4], d_omit, (uint32_t)gaps[5], od);
+    HIPCHK(hipGetLastError());
+    *tile = extract_tile_bytes(n_items);
+    if ((rc = B.down(out, d_out, (size_t)out_bytes)) || (out2 && (rc = B.down(out2, d_out2, (size_t)out_bytes)))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return RV_OK;
+}
+
+extern "C" int rv_hook_extract_from_bits(rv_ctx* ctx, const uint8_t* bits, uint64_t n_items, uint32_t R, const uint8_t* omit, const uint64_t* dst_off,
+                                         uint32_t rep_min, uint8_t* out, uint64_t out_bytes, uint32_t* tile) {
+    if (!ctx || !out || !tile || !hook_map_ok(R, omit) || n_items > HOOK_MAX || out_bytes > HOOK_MAX || (n_items && !bits)) return RV_E_ARG;
+    if (!hook_ranges_ok(R, omit, dst_off, nullptr, n_items / 8 + 1, out_bytes)) return RV_E_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    const OnlineList ol = hook_online_list(R, omit, dst_off);
+    HookBufs B(ctx);
+    uint8_t *d_bits = nullptr, *d_out = nullptr;
+    OnlineList* d_ol = nullptr;
+    int rc;
+    if ((rc = B.up(bits, (size_t)n_items * (R / 8), &d_bits)) || (rc = B.up(&ol, 1, &d_ol)) || (rc = B.up(out, (size_t)out_bytes, &d_out))) return rc;
+    launch_extract_from_bits(ctx->stream, d_bits, n_items, R / 4, d_ol, d_out, rep_min);
+    HIPCHK(hipGetLastError());
+    *tile = extract_from_bits_tile_bytes(n_items);
+    if ((rc = B.down(out, d_out, (size_t)out_bytes))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return RV_OK;
+}
+
+extern "C" int rv_hook_pack_corr_all(rv_ctx* ctx, const uint8_t* bits, uint64_t n_items, uint64_t byte0, uint64_t n_bytes, uint64_t pitch, uint8_t* out) {
+    if (!ctx || !out || n_items > HOOK_MAX || byte0 > HOOK_MAX || (n_items && !bits)) return RV_E_ARG;
+    if (!pitch || pitch % 128 || pitch > (1ull << 24) || n_bytes > pitch) return RV_E_ARG;  // (the kernel writes whole 16-byte words: up to the pitch's padding)
+    HIPCHK(hipSetDevice(ctx->device));
+    HookBufs B(ctx);
+    uint8_t *d_bits = nullptr, *d_out = nullptr;
+    int rc;
+    if ((rc = B.up(bits, (size_t)n_items * 32, &d_bits)) || (rc = B.up(out, (size_t)RV_TOTAL_REPS * pitch, &d_out))) return rc;
+    launch_pack_corr_all(ctx->stream, d_bits, n_items, byte0, n_bytes, pitch, d_out);
+    HIPCHK(hipGetLastError());
+    if ((rc = B.down(out, d_out, (size_t)RV_TOTAL_REPS * pitch))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return RV_OK;
+}
+
+extern "C" int rv_hook_unpack_bits(rv_ctx* ctx, const uint8_t* blob, uint64_t blob_bytes, const uint64_t* src_off, const uint64_t* src_len, const uint8_t* omit,
+                                   uint64_t n_items, uint32_t R, int kind, uint32_t out_nq, uint64_t first_item, uint32_t* rows_out) {
+    if (!ctx || !rows_out || (kind != 0 && kind != 1) || !hook_map_ok(R, omit) || !src_len) return RV_E_ARG;
+    if (n_items > HOOK_MAX || first_item > HOOK_MAX || blob_bytes > HOOK_MAX || (blob_bytes && !blob)) return RV_E_ARG;
+    if (!hook_ranges_ok(R, omit, src_off, src_len, 0, blob_bytes)) return RV_E_ARG;
+    // supplied_nq (verify.inc): full rows, or sixteen quad words when no repetition beyond them is opened
+    const uint32_t NQ = R / 4;
+    if (out_nq != NQ) {
+        if (out_nq != 16 || NQ < 16) return RV_E_ARG;
+        for (uint32_t r = 64; r < R; r++)
+            if (omit[r] < 8) return RV_E_ARG;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    HookBufs B(ctx);
+    uint8_t *d_blob = nullptr, *d_omit = nullptr;
+    uint64_t *d_off = nullptr, *d_len = nullptr;
+    uint32_t* d_rows = nullptr;
+    const size_t n_words = (size_t)n_items * out_nq;
+    int rc;
+    if ((rc = B.up(blob, (size_t)blob_bytes, &d_blob)) || (rc = B.up(src_off, (size_t)R, &d_off)) || (rc = B.up(src_len, (size_t)R, &d_len)) ||
+        (rc = B.up(omit, (size_t)R, &d_omit)) || (rc = B.up(rows_out, n_words, &d_rows)))
+        return rc;
+    launch_unpack_bits(ctx->stream, d_blob, d_off, d_len, d_omit, n_items, NQ, kind, d_rows, out_nq, first_item);
+    HIPCHK(hipGetLastError());
+    if ((rc = B.down(rows_out, d_rows, n_words))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return RV_OK;
+}
+
+extern "C" int rv_hook_extract64(rv_ctx* ctx, const uint64_t* stream, uint64_t stride_words, const uint64_t* offs, uint64_t n_items, int add_omit, uint32_t R,
+                                 const uint8_t* omit, const uint64_t* dst_off, int use_list, uint32_t rep_min, uint8_t* out, uint64_t out_bytes) {
+    if (!ctx || !out || !hook_map_ok(R, omit) || n_items > HOOK_MAX || stride_words > HOOK_MAX || out_bytes > HOOK_MAX || (stride_words && !stream)) return RV_E_ARG;
+    if (!hook_ranges_ok(R, omit, dst_off, nullptr, 8 * n_items, out_bytes)) return RV_E_ARG;
+    if (n_items) {
+        uint64_t top = n_items - 1;  // the last word of a repetition's stream that is read
+        if (offs) {
+            top = 0;
+            for (uint64_t i = 0; i < n_items; i++) top = std::max(top, offs[i]);
+        }
+        if (top > HOOK_MAX) return RV_E_ARG;
+        uint64_t om_max = 0;
+        for (uint32_t r = 0; r < R; r++)
+            if (omit[r] < 8) om_max = std::max<uint64_t>(om_max, omit[r]);
+        if (top + (add_omit ? om_max : 0) >= stride_words) return RV_E_ARG;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    const OnlineList ol = hook_online_list(R, omit, dst_off);
+    HookBufs B(ctx);
+    uint64_t *d_stream = nullptr, *d_offs = nullptr, *d_dst = nullptr;
+    uint8_t *d_omit = nullptr, *d_out = nullptr;
+    OnlineList* d_ol = nullptr;
+    int rc;
+    if ((rc = B.up(stream, (size_t)R * stride_words, &d_stream)) || (offs && (rc = B.up(offs, (size_t)n_items, &d_offs))) || (rc = B.up(omit, (size_t)R, &d_omit)) ||
+        (rc = B.up(dst_off, (size_t)R, &d_dst)) || (use_list && (rc = B.up(&ol, 1, &d_ol))) || (rc = B.up(out, (size_t)out_bytes, &d_out)))
+        return rc;
+    launch_extract64(ctx->stream, d_stream, stride_words, d_offs, n_items, add_omit ? 1 : 0, R, d_omit, d_dst, d_out, d_ol, rep_min);
+    HIPCHK(hipGetLastError());
+    if ((rc = B.down(out, d_out, (size_t)out_bytes))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return RV_OK;
+}
+
+extern "C" int rv_hook_unpack64(rv_ctx* ctx, const uint8_t* blob, uint64_t blob_bytes, const uint64_t* src_off, const uint64_t* src_len, const uint8_t* omit,
+                                uint64_t n_items, uint32_t R, uint32_t out_r, uint64_t* out) {
+    if (!ctx || !out || !hook_map_ok(R, omit) || !src_len || n_items > HOOK_MAX || blob_bytes > HOOK_MAX || (blob_bytes && !blob)) return RV_E_ARG;
+    if (!hook_ranges_ok(R, omit, src_off, src_len, 0, blob_bytes)) return RV_E_ARG;
+    // supplied_r64 (verify.inc): every repetition, or the first 64 when no other is opened
+    if (out_r != R) {
+        if (out_r != 64 || R < 64) return RV_E_ARG;
+        for (uint32_t r = 64; r < R; r++)
+            if (omit[r] < 8) return RV_E_ARG;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    HookBufs B(ctx);
+    uint8_t *d_blob = nullptr, *d_omit = nullptr;
+    uint64_t *d_off = nullptr, *d_len = nullptr, *d_out = nullptr;
+    const size_t n_words = (size_t)n_items * out_r;
+    int rc;
+    if ((rc = B.up(blob, (size_t)blob_bytes, &d_blob)) || (rc = B.up(src_off, (size_t)R, &d_off)) || (rc = B.up(src_len, (size_t)R, &d_len)) ||
+        (rc = B.up(omit, (size_t)R, &d_omit)) || (rc = B.up(out, n_words, &d_out)))
+        return rc;
+    launch_unpack64(ctx->stream, d_blob, d_off, d_len, d_omit, n_items, R, d_out, out_r);
+    HIPCHK(hipGetLastError());
+    if ((rc = B.down(out, d_out, n_words))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return RV_OK;
+}

@@ -255,6 +255,7 @@ void launch_copy_gaps(hipStream_t st, const uint8_t* d_img, uint8_t* dst_mapped,
                       uint64_t corr_len, uint32_t n_rec, const uint8_t* d_omit /*[256]*/, uint32_t rep_limit, OpenDirect od = OpenDirect(),
                       const int* d_err = nullptr, int* err_dst_mapped = nullptr /* also: the error word into a host-mapped word */);
 uint32_t extract_tile_bytes(uint64_t n_items);  // the tile of launch_extract_bits for vectors of n_items bits
+uint32_t extract_from_bits_tile_bytes(uint64_t n_items);  // ... and of launch_extract_from_bits
 void launch_publish(hipStream_t st, const uint32_t* d_src, uint32_t n_words, uint32_t* dst_mapped, uint32_t* flag_mapped, uint32_t seq);
 void launch_store_words(hipStream_t st, const uint32_t* d_src, uint32_t n_words, uint32_t* dst_mapped, const int* d_err, int* dst_err_mapped);
 // k_frame_counts: the four repetition counts of `batch` framed proofs `stride` bytes apart at d_out, in front of sections of

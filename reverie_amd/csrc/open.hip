@@ -529,6 +529,7 @@ void launch_fs_challenge(hipStream_t st, const uint8_t* d_h, const FsLayout& L, 
 }
 
 uint32_t extract_tile_bytes(uint64_t n_items) { return ex_tb_for(n_items / 8 + 1, EXR_TB); }
+uint32_t extract_from_bits_tile_bytes(uint64_t n_items) { return ex_tb_for(n_items / 8 + 1); }
 void launch_extract_bits(hipStream_t st, const void* d_stream, const uint32_t* d_rows, uint64_t n_items, uint32_t NQ,
                          int kind, const uint8_t* d_omit, const uint64_t* d_dst_off, uint8_t* d_out, uint8_t* d_out2, uint32_t n_direct) {
     const uint64_t n_bytes = n_items / 8 + 1;

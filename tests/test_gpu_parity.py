@@ -40,6 +40,7 @@ def load_case(name):
 
 
 # ---------------------------------------------------------------- primitives (rows a1, a2, a4, a16)
+# (the opening and unpacking kernels, one launch at a time against tests/pack_ref.py: tests/test_gpu_pack.py, tests/test_pack_ref_host.py)
 def test_prg_blocks(rv, oracle):
     from reverie_amd import _lib
 
