@@ -331,6 +331,48 @@ int rv_evaluate(rv_ctx *ctx, const rv_circuit *c, const uint8_t *wit_gf2, size_t
 int rv_evaluate_batch(rv_ctx *ctx, const rv_circuit *c, size_t batch, const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64,
                       size_t n_z64, uint8_t *gf2_values, uint64_t *z64_values, rv_eval_status *st);
 
+/* ---- witnesses taken from device memory; evaluation results left there ----------------------
+ * For a caller who computes witnesses on the GPU and filters them by evaluation before proving: no witness byte crosses PCIe in
+ * either direction.  A descriptor names the witnesses; every pointer in it is memory of the context's device.  Witness b of a batch
+ * starts at gf2 + b*stride_gf2 (bytes, one byte per bit) and z64 + b*stride_z64 (words); the calls that take one witness ignore the
+ * strides, and so does a batch of one.  The caller has finished writing the witnesses before the call; the library does not write
+ * them and no longer reads them when the call returns.
+ *
+ * Each _wdev prover is its host-witness sibling -- the same paths (one-pass batch, Z64 chunks, worker threads, one by one, early
+ * corrections), the same error codes, and proofs byte-identical to the sibling's for the same witness bytes and seeds: only the
+ * copy that brings the witness to where the kernels read it starts in device memory.
+ *
+ * Refused with RV_E_ARG before anything is launched: a NULL descriptor; a pointer that is not memory of the context's device, whose
+ * range leaves its allocation (where the runtime can tell) or that is misaligned (gf2: 1, z64: 8, d_z64_values: 8, d_status: 16
+ * bytes); a stride smaller than its n when batch > 1; a witness range that overlaps dst_device or an output buffer; NULL seeds on
+ * the calls whose siblings refuse them.  RV_E_WITNESS_SHORT as the siblings. */
+typedef struct rv_dev_witness {
+    const uint8_t *gf2; /* n_gf2 bytes per witness */
+    size_t n_gf2;
+    size_t stride_gf2;   /* bytes between two witnesses' first bits */
+    const uint64_t *z64; /* n_z64 words per witness, 8-byte aligned */
+    size_t n_z64;
+    size_t stride_z64;   /* words between two witnesses' first words */
+} rv_dev_witness;
+int rv_prove_wdev(rv_ctx *ctx, const rv_circuit *c, const rv_dev_witness *w, const uint8_t *seeds, uint8_t **proof, size_t *proof_len);
+int rv_prove_device_wdev(rv_ctx *ctx, const rv_circuit *c, const rv_dev_witness *w, const uint8_t *seeds, void *dst_device,
+                         uint8_t comm[RV_HASH_SIZE], uint8_t omit[RV_TOTAL_REPS], size_t lens[4]);
+int rv_prove_batch_wdev(rv_ctx *ctx, const rv_circuit *c, size_t batch, const rv_dev_witness *w, const uint8_t *seeds,
+                        uint8_t **proofs, size_t *proof_lens);
+int rv_prove_batch_device_wdev(rv_ctx *ctx, const rv_circuit *c, size_t batch, const rv_dev_witness *w, const uint8_t *seeds,
+                               void *dst_device, size_t stride, size_t *proof_len);
+/* rv_evaluate_batch with the witnesses read in device memory, the statuses written to device memory (d_status[b], the 16-byte
+ * rv_eval_status; first_failed_op UINT64_MAX when every assertion holds) and values written for chosen wires only:
+ * d_gf2_values[b*n_sel_gf2 + i] = the final bit of wire sel_gf2[i], d_z64_values[b*n_sel_z64 + i] = the word of wire sel_z64[i].
+ * sel_gf2 / sel_z64 are host arrays; they may be unsorted and may repeat.  A NULL values pointer: that domain is not wanted.  A values
+ * pointer with sel NULL and n_sel 0: every wire, in order (rv_evaluate_batch's meaning).  Values need RV_COMPILE_KEEP_WIRES (RV_E_ARG
+ * otherwise); an index at or beyond the circuit's wire count: RV_E_WIRE_OOB, before anything is launched.  Parts as
+ * rv_evaluate_batch (half of the free memory, RV_EVAL_PART), each writing its slice of the caller's buffers; no result is copied to
+ * the host, and the call waits for the device once, at the end. */
+int rv_evaluate_batch_device(rv_ctx *ctx, const rv_circuit *c, size_t batch, const rv_dev_witness *w, const uint32_t *sel_gf2,
+                             size_t n_sel_gf2, const uint32_t *sel_z64, size_t n_sel_z64, uint8_t *d_gf2_values, uint64_t *d_z64_values,
+                             rv_eval_status *d_status);
+
 /* ---- cleartext evaluation of a gate stream with bounded device memory (the streaming evaluator) ----
  * rv_evaluate_batch over an op list fed in pieces, as the streaming prover takes it: no compiled circuit, no keep-wires flag.
  *     rv_eval_stream_begin(ctx, z64_wires, gf2_wires, batch, max_chunk_ops, &s)
@@ -461,7 +503,9 @@ int rv_stream_feed(rv_stream *s, const rv_op *ops, size_t n_ops, const uint8_t *
                    size_t n_z64);
 /* rv_stream_feed for an op array that already sits in device memory: d_ops is n_ops packed 24-byte records in the memory of the
  * stream's device (rv_circuit_compile_device's convention: the caller keeps ownership and must have finished writing it; 8-byte
- * aligned, RV_E_ARG otherwise).  The witnesses stay in host memory, in rv_stream_feed's layouts.  Serves every stream rv_stream_feed
+ * aligned, RV_E_ARG otherwise).  The streams still take their witnesses from host memory, in rv_stream_feed's layouts (a stream digests
+ * the witness on the host as it is fed; the calls that read witnesses in device memory are the _wdev provers and
+ * rv_evaluate_batch_device).  Serves every stream rv_stream_feed
  * serves -- single and batch provers in both passes, the streaming verifiers -- and may be mixed freely with it inside one stream
  * and between its passes: the pieces are cut by the same rule, the digests and counters are the same numbers, and every proof,
  * answer, error code and rv_stream_info figure is what rv_stream_feed gives for the same ops.  The op list is not copied to the
@@ -914,6 +958,11 @@ int rv_hook_verify_walk(const uint8_t *bytes, size_t len, int framing, uint64_t 
  * out[0] = one launch per dependency level, out[1] = one workgroup per slice of witness words walking every level (csrc/eval.hip).
  * The results are the same either way. */
 int rv_hook_eval_schedules(uint64_t out[2]);
+/* Running totals since process start, counted where the provers and the evaluator queue the copies (the streams do not
+ * count): out[0] = witness bytes copied host-to-device, out[1] = witness bytes taken from device memory (copied
+ * device-to-device, or read in place by the evaluator), out[2] = evaluation result bytes copied device-to-host.  Only the elements
+ * the Input ops consume are counted.  Calls refused before anything is launched count nothing. */
+int rv_hook_witness_traffic(uint64_t out[3]);
 /* The early-corrections plan of a program (host only, no device): the ops are compiled as rv_circuit_compile_ex(flags) would and
  * the plan rv_prove would use is built and checked against the compiled gate records.  out[0] = a plan exists (0 / 1: the circuit
  * is pure GF(2) with >= 2^21 Mul gates -- RV_EARLY_MIN -- or pure Z64, its preprocessing rows complete in step with the levels

@@ -56,6 +56,11 @@ class EvalStatus(C.Structure):  # rv_eval_status
     _fields_ = [("n_failed", C.c_uint64), ("first_failed_op", C.c_uint64)]
 
 
+class DevWitness(C.Structure):  # rv_dev_witness: witnesses in the memory of the context's device
+    _fields_ = [("gf2", C.c_void_p), ("n_gf2", C.c_size_t), ("stride_gf2", C.c_size_t),
+                ("z64", C.c_void_p), ("n_z64", C.c_size_t), ("stride_z64", C.c_size_t)]
+
+
 class EvalStreamInfo(C.Structure):  # rv_eval_stream_info
     _fields_ = [(n, C.c_uint64) for n in ("n_ops", "chunks", "levels", "wire_store_bytes", "peak_chunk_bytes")]
 
@@ -95,6 +100,8 @@ SYMBOLS = [
     "rv_hook_compile_compare_device_chunk_ex", "rv_hook_compile_device_laps_z64",
     "rv_verify_device", "rv_verify_sections_device", "rv_hook_verify_device_paths", "rv_hook_verify_walk",
     "rv_prove_batch_device", "rv_verify_batch_device", "rv_hook_verify_batch_device_paths",
+    "rv_prove_wdev", "rv_prove_device_wdev", "rv_prove_batch_wdev", "rv_prove_batch_device_wdev", "rv_evaluate_batch_device",
+    "rv_hook_witness_traffic",
     "rv_hook_extract_bits", "rv_hook_extract_from_bits", "rv_hook_pack_corr_all", "rv_hook_unpack_bits", "rv_hook_extract64", "rv_hook_unpack64",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
@@ -141,6 +148,13 @@ ARGTYPES = {
     "rv_prove_batch_device": [_P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _Z, C.POINTER(C.c_size_t)],
     "rv_verify_batch_device": [_P, _P, _Z, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32, C.POINTER(C.c_int)],
     "rv_hook_verify_batch_device_paths": [C.POINTER(C.c_uint64)],
+    # witnesses taken from device memory, evaluation results left there
+    "rv_prove_wdev": [_P, _P, C.POINTER(DevWitness), _P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)],
+    "rv_prove_device_wdev": [_P, _P, C.POINTER(DevWitness), _P, _P, _P, _P, C.POINTER(C.c_size_t)],
+    "rv_prove_batch_wdev": [_P, _P, _Z, C.POINTER(DevWitness), _P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)],
+    "rv_prove_batch_device_wdev": [_P, _P, _Z, C.POINTER(DevWitness), _P, _P, _Z, C.POINTER(C.c_size_t)],
+    "rv_evaluate_batch_device": [_P, _P, _Z, C.POINTER(DevWitness), _P, _Z, _P, _Z, _P, _P, _P],
+    "rv_hook_witness_traffic": [C.POINTER(C.c_uint64)],
     # the mask generators (parity hook)
     "rv_hook_maskgen": [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _P],
     # the opening and unpacking kernels (parity hooks)

@@ -696,6 +696,11 @@ struct rv_circuit {
     uint32_t* d_wire_ssa64 = nullptr;
     mutable std::mutex eval_mu;
     mutable uint32_t* d_level_start64 = nullptr;
+    // rv_evaluate_batch_device: the ordinal -> op index tables of the AssertZero ops (Compiled::assert_rec* / assert_op*), on the
+    // first device evaluation
+    mutable bool assert_tables_up = false;
+    mutable uint32_t *d_assert_rec2 = nullptr, *d_assert_rec64 = nullptr;
+    mutable uint64_t *d_assert_op2 = nullptr, *d_assert_op64 = nullptr;
 };
 static int eval_upload_wires(rv_ctx* ctx, rv_circuit* c);
 
@@ -1270,6 +1275,10 @@ extern "C" void rv_circuit_destroy(rv_circuit* c) {
     c->ctx->release(c->d_wire_forms);
     c->ctx->release(c->d_wire_ssa64);
     c->ctx->release(c->d_level_start64);
+    c->ctx->release(c->d_assert_rec2);
+    c->ctx->release(c->d_assert_op2);
+    c->ctx->release(c->d_assert_rec64);
+    c->ctx->release(c->d_assert_op64);
     // the early-corrections staging of a LARGE plan (2 GB of page-locked memory for the 10^6-MUL Z64 circuit) does not outlive the
     // circuit that needed it: a context that moves on to small circuits would otherwise hold it until rv_ctx_destroy.
     // Small stagings (the 160 MB of the 10^7-gate GF(2) circuit) stay: re-mapping them costs more than they weigh.
@@ -1523,6 +1532,35 @@ extern "C" int rv_challenge(const uint8_t comm[RV_HASH_SIZE], uint8_t omit[RV_TO
     return RV_OK;
 }
 
+// Where a call's witnesses lie: host memory (every entry point that takes wit_gf2 / wit_z64) or the memory of the context's
+// device (the _wdev entry points and rv_evaluate_batch_device, witness_dev.inc, which have validated the ranges).  Witness b of a
+// batch starts at gf2 + b * stride_gf2 bytes / z64 + b * stride_z64 words; a host batch is packed (stride = n).  The shared _impl
+// functions take one of these and copy from it with kind() into the place their kernels read -- the same bytes either way.
+struct WitSrc {
+    const uint8_t* gf2;
+    size_t n_gf2, stride_gf2;
+    const uint64_t* z64;
+    size_t n_z64, stride_z64;
+    bool dev;
+    hipMemcpyKind kind() const { return dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; }
+    WitSrc from(size_t b) const {  // witnesses b, b + 1, ...
+        WitSrc w = *this;
+        if (gf2) w.gf2 = gf2 + b * stride_gf2;
+        if (z64) w.z64 = z64 + b * stride_z64;
+        return w;
+    }
+};
+static WitSrc wit_host(const uint8_t* gf2, size_t n_gf2, const uint64_t* z64, size_t n_z64) { return WitSrc{gf2, n_gf2, n_gf2, z64, n_z64, n_z64, false}; }
+// rv_hook_witness_traffic, counted where the copies are queued: witness bytes sent host-to-device, witness bytes taken from device
+// memory (copied or read in place), evaluation result bytes copied device-to-host
+static std::atomic<uint64_t> g_wit_traffic[3];
+static void wit_count(const WitSrc& w, uint64_t bytes) { g_wit_traffic[w.dev ? 1 : 0].fetch_add(bytes, std::memory_order_relaxed); }
+extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
+    if (!out) return RV_E_ARG;
+    for (int i = 0; i < 3; i++) out[i] = g_wit_traffic[i].load(std::memory_order_relaxed);
+    return RV_OK;
+}
+
 #include "shard.inc"
 #include "open.inc"
 #include "prove.inc"
@@ -1538,3 +1576,4 @@ extern "C" int rv_challenge(const uint8_t comm[RV_HASH_SIZE], uint8_t omit[RV_TO
 #include "comm.inc"
 #include "eval.inc"
 #include "eval_stream.inc"
+#include "witness_dev.inc"

@@ -117,10 +117,9 @@ struct BatchDst {
 // One proof, framed, straight into device memory at d_dst (rv_prove_batch_device's proof-after-proof branch): rv_prove_device_impl
 // with the framing of a whole Proof around the sections and the repetition counts from k_frame_counts; the error word is all
 // the host waits for.
-static int prove_framed_device(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64, size_t n_z64,
-                               const uint8_t* seeds, uint8_t* d_dst) {
+static int prove_framed_device(rv_ctx* ctx, const rv_circuit* c, const WitSrc& w, const uint8_t* seeds, uint8_t* d_dst) {
     rv_shard* s = nullptr;
-    int rc = rv_shard_commit_impl(ctx, c, wit_gf2, n_gf2, wit_z64, n_z64, seeds, 0, RV_TOTAL_REPS, &s, /*defer_sync=*/true);
+    int rc = rv_shard_commit_impl(ctx, c, w, seeds, 0, RV_TOTAL_REPS, &s, /*defer_sync=*/true);
     if (rc) return rc;
     do {
         void* d = nullptr;
@@ -143,9 +142,11 @@ static int prove_framed_device(rv_ctx* ctx, const rv_circuit* c, const uint8_t* 
     return rc;
 }
 
-static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, const uint8_t* wit_gf2, size_t n_gf2,
-                               const uint64_t* wit_z64, size_t n_z64, const uint8_t* seeds, const BatchDst& out) {
+static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, const WitSrc& w, const uint8_t* seeds, const BatchDst& out) {
     LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
+    const uint8_t* const wit_gf2 = w.gf2;
+    const uint64_t* const wit_z64 = w.z64;
+    const size_t n_gf2 = w.n_gf2, n_z64 = w.n_z64;
     uint8_t** const proofs = out.proofs;
     size_t* const proof_lens = out.proof_lens;
     const bool dev = out.d_dst != nullptr;
@@ -167,14 +168,12 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
     }
     auto one_by_one = [&]() {  // Z64 / mixed circuits and batches of one: the plain entry point, proof after proof
         for (size_t b = 0; b < batch && dev; b++) {
-            int rc = prove_framed_device(ctx, c, wit_gf2 ? wit_gf2 + b * n_gf2 : nullptr, n_gf2, wit_z64 ? wit_z64 + b * n_z64 : nullptr, n_z64,
-                                         seeds + b * RV_TOTAL_REPS * 16, out.d_dst + b * out.stride);
+            int rc = prove_framed_device(ctx, c, w.from(b), seeds + b * RV_TOTAL_REPS * 16, out.d_dst + b * out.stride);
             if (rc) return rc;
         }
         if (dev) return (int)RV_OK;
         for (size_t b = 0; b < batch; b++) {
-            int rc = rv_prove(ctx, c, wit_gf2 ? wit_gf2 + b * n_gf2 : nullptr, n_gf2, wit_z64 ? wit_z64 + b * n_z64 : nullptr, n_z64,
-                              seeds + b * RV_TOTAL_REPS * 16, &proofs[b], &proof_lens[b]);
+            int rc = guarded([&]() -> int { return rv_prove_impl(ctx, c, w.from(b), seeds + b * RV_TOTAL_REPS * 16, &proofs[b], &proof_lens[b]); });
             if (rc) {
                 for (size_t k = 0; k <= b; k++) rv_free(proofs[k]), proofs[k] = nullptr, proof_lens[k] = 0;
                 return rc;
@@ -201,8 +200,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
         if (const char* e = getenv("RV_BATCH_MAX")) chunk = std::min<size_t>(chunk, (size_t)std::max(atoi(e), 1));
         if (batch > chunk) {
             for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-                const int rc = rv_prove_batch_impl(ctx, c, std::min(chunk, batch - b0), wit_gf2 ? wit_gf2 + b0 * n_gf2 : nullptr, n_gf2,
-                                                   wit_z64 ? wit_z64 + b0 * n_z64 : nullptr, n_z64, seeds + b0 * RV_TOTAL_REPS * 16,
+                const int rc = rv_prove_batch_impl(ctx, c, std::min(chunk, batch - b0), w.from(b0), seeds + b0 * RV_TOTAL_REPS * 16,
                                                    dev ? BatchDst{nullptr, nullptr, out.d_dst + b0 * out.stride, out.stride}
                                                        : BatchDst{proofs + b0, proof_lens + b0, nullptr, 0});
                 if (rc) {
@@ -285,7 +283,8 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
                     // first -- proves more of the batch instead of idling at the end of its fixed share)
                     for (size_t b; rcs[t] == RV_OK && (b = next_proof.fetch_add(1, std::memory_order_relaxed)) < batch;) {
                         span[b][0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-                        rcs[t] = rv_prove_impl(ctx->workers[t], c, wit_gf2 ? wit_gf2 + b * n_gf2 : nullptr, n_gf2, nullptr, 0,
+                        // (GF(2) circuits only: the worker is given no Z64 witness)
+                        rcs[t] = rv_prove_impl(ctx->workers[t], c, WitSrc{w.from(b).gf2, n_gf2, w.stride_gf2, nullptr, 0, 0, w.dev},
                                                seeds + b * RV_TOTAL_REPS * 16, &proofs[b], &proof_lens[b], slab + b * stride, stride);
                         span[b][1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
                         for (int k = 0; k < 3; k++) span[b][2 + k] = g_prove_marks[k];
@@ -381,7 +380,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
     if ((rc = dalloc(ctx, SLAB_HEAD / sizeof(int) + batch, &d_err_all))) return cleanup(rc);
     device_tmp.push_back(d_err_all);
     if (hipMemcpyAsync(d_seeds_all + SLAB_HEAD, seeds, batch * (size_t)R * 16, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        (cc.n_in && hipMemcpy2DAsync(d_wit_all + SLAB_HEAD, wit_stride, wit_gf2, n_gf2, cc.n_in, batch, hipMemcpyHostToDevice,
+        (cc.n_in && hipMemcpy2DAsync(d_wit_all + SLAB_HEAD, wit_stride, wit_gf2, w.stride_gf2, cc.n_in, batch, w.kind(),
                                      ctx->stream) != hipSuccess))
         return cleanup(RV_E_DEVICE);
     const size_t wit64_stride = (std::max<size_t>(cc.n_in64, 1) + 1) & ~(size_t)1;  // (u64 words)
@@ -389,10 +388,11 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
     if (has64) {
         if ((rc = dalloc(ctx, SLAB_HEAD / 8 + batch * wit64_stride, &d_wit64_all))) return cleanup(rc);
         device_tmp.push_back(d_wit64_all);
-        if (cc.n_in64 && hipMemcpy2DAsync(d_wit64_all + SLAB_HEAD / 8, wit64_stride * 8, wit_z64, n_z64 * 8, cc.n_in64 * 8, batch,
-                                          hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        if (cc.n_in64 && hipMemcpy2DAsync(d_wit64_all + SLAB_HEAD / 8, wit64_stride * 8, wit_z64, w.stride_z64 * 8, cc.n_in64 * 8, batch,
+                                          w.kind(), ctx->stream) != hipSuccess)
             return cleanup(RV_E_DEVICE);
     }
+    wit_count(w, batch * (cc.n_in + cc.n_in64 * 8));
     for (size_t b = 0; b < batch && !rc; b++) {
         rv_shard* s = sh[b] = new rv_shard();
         s->ctx = ctx;
@@ -523,7 +523,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
 extern "C" int rv_prove_batch(rv_ctx* ctx, const rv_circuit* c, size_t batch, const uint8_t* wit_gf2, size_t n_gf2,
                               const uint64_t* wit_z64, size_t n_z64, const uint8_t* seeds, uint8_t** proofs, size_t* proof_lens) {
     try {  // no C++ exception may cross the C boundary
-        return rv_prove_batch_impl(ctx, c, batch, wit_gf2, n_gf2, wit_z64, n_z64, seeds, BatchDst{proofs, proof_lens, nullptr, 0});
+        return rv_prove_batch_impl(ctx, c, batch, wit_host(wit_gf2, n_gf2, wit_z64, n_z64), seeds, BatchDst{proofs, proof_lens, nullptr, 0});
     } catch (...) {
         g_last_error = "out of host memory";
         return RV_E_NOMEM;

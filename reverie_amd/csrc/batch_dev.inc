@@ -29,8 +29,8 @@ extern "C" int rv_prove_batch_device(rv_ctx* ctx, const rv_circuit* c, size_t ba
         *proof_len = total;
         if (((uintptr_t)dst_device & 255) || (stride & 255) || stride < total || batch > SIZE_MAX / stride) return RV_E_ARG;
         HIPCHK(hipSetDevice(ctx->device));
-        if (int rb = device_bytes_ok(ctx, dst_device, batch * stride)) return rb;
-        return rv_prove_batch_impl(ctx, c, batch, wit_gf2, n_gf2, wit_z64, n_z64, seeds, BatchDst{nullptr, nullptr, (uint8_t*)dst_device, stride});
+        if (int rb = device_bytes_ok(ctx, dst_device, batch * stride, 16)) return rb;
+        return rv_prove_batch_impl(ctx, c, batch, wit_host(wit_gf2, n_gf2, wit_z64, n_z64), seeds, BatchDst{nullptr, nullptr, (uint8_t*)dst_device, stride});
     });
 }
 
@@ -155,7 +155,7 @@ extern "C" int rv_verify_batch_device(rv_ctx* ctx, const rv_circuit* c, size_t b
         HIPCHK(hipSetDevice(ctx->device));
         for (size_t b = 0; b < batch; b++) {
             if (!d_proofs[b]) return RV_E_ARG;
-            if (int rb = device_bytes_ok(ctx, d_proofs[b], proof_lens[b])) return rb;
+            if (int rb = device_bytes_ok(ctx, d_proofs[b], proof_lens[b], 16)) return rb;
         }
         return rv_verify_batch_device_impl(ctx, c, batch, d_proofs, proof_lens, flags, ok);
     });

@@ -204,7 +204,7 @@ static int prove_sharded_impl(rv_comm* m, const rv_circuit* c, const uint8_t* wi
     hipStream_t st = ctx->stream;
     const uint32_t count = RV_TOTAL_REPS / (uint32_t)m->world, begin = (uint32_t)m->rank * count;
     rv_shard* s = nullptr;
-    int rc = rv_shard_commit_impl(ctx, c, wit_gf2, n_gf2, wit_z64, n_z64, seeds + (size_t)begin * 16, begin, count, &s, /*defer_sync=*/true);
+    int rc = rv_shard_commit_impl(ctx, c, wit_host(wit_gf2, n_gf2, wit_z64, n_z64), seeds + (size_t)begin * 16, begin, count, &s, /*defer_sync=*/true);
     if (rc) return rc;  // (the other ranks are left waiting in the collective: the communicator is dead after a failed rank)
     uint8_t* d_mine = nullptr;   // this rank's openings (worst case: every one of min(40, count) repetitions opens)
     uint8_t* d_final = nullptr;  // rank 0: the framed proof

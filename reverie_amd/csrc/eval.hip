@@ -1,4 +1,4 @@
-// Cleartext evaluation (rv_evaluate / rv_evaluate_batch, host side in eval.inc): the compiled gate stream run on witness values
+// Cleartext evaluation (rv_evaluate / rv_evaluate_batch / rv_evaluate_batch_device, host side in eval.inc): the compiled gate stream run on witness values
 // alone -- no shares, no masks, no transcripts -- for many witnesses at once.
 //
 // Values, one set per witness b of the batch:
@@ -131,14 +131,17 @@ __global__ __launch_bounds__(1024) void k_eval_walk(EvalParams p, const Gate* __
     }
 }
 
-// witness bytes [B][n] (0 / non-zero) -> bit-sliced input words [n][W]
-__global__ __launch_bounds__(256) void k_eval_wit(const uint8_t* __restrict__ wit, uint32_t n, uint32_t B, uint32_t W, uint32_t* __restrict__ out) {
+// witness bytes (0 / non-zero), witness b's n inputs at wit + b * stride -> bit-sliced input words [n][W].  One thread per output
+// word, threads along the input index: the 32 byte reads of a word go down 32 witness rows, and neighbouring threads read neighbouring
+// bytes of each row (a wavefront's load is 64 consecutive bytes, whatever the stride)
+__global__ __launch_bounds__(256) void k_eval_wit(const uint8_t* __restrict__ wit, size_t stride, uint32_t n, uint32_t B, uint32_t W,
+                                                  uint32_t* __restrict__ out) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (uint64_t)n * W) return;
-    const uint32_t i = (uint32_t)(t / W), j = (uint32_t)(t % W);
+    const uint32_t i = (uint32_t)(t % n), j = (uint32_t)(t / n);
     uint32_t w = 0;
-    for (uint32_t k = 0; k < 32 && 32 * j + k < B; k++) w |= (wit[(size_t)(32 * j + k) * n + i] ? 1u : 0u) << k;
-    out[t] = w;
+    for (uint32_t k = 0; k < 32 && 32 * j + k < B; k++) w |= (wit[(size_t)(32 * j + k) * stride + i] ? 1u : 0u) << k;
+    out[(size_t)i * W + j] = w;
 }
 
 // the wires' final values -> [B][gf2_wires] bytes and [B][z64_wires] words
@@ -172,6 +175,39 @@ __device__ __forceinline__ uint64_t ev_assert_op(const uint32_t* rec, const uint
             hi = mid;
     }
     return (lo < n && rec[lo] == x) ? op[lo] : UINT64_MAX;
+}
+
+// rv_evaluate_batch_device: the selected wires' final values of the part's witnesses -> [B][n_sel2] bytes and [B][n_sel64] words in
+// the caller's buffers (out2 / out64: where the part's first witness goes; null: not wanted).  sel2 / sel64 null: wire i itself
+// (every wire, in order).  Threads run along the selection index within a witness.
+__global__ __launch_bounds__(256) void k_eval_out_sel(EvalParams p, const WireForm* __restrict__ forms, const uint32_t* __restrict__ sel2,
+                                                      uint32_t n_sel2, const uint32_t* __restrict__ ssa64, const uint32_t* __restrict__ sel64,
+                                                      uint32_t n_sel64, uint8_t* __restrict__ out2, uint64_t* __restrict__ out64) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t t2 = out2 ? (uint64_t)n_sel2 * p.B : 0;
+    if (t < t2) {
+        const uint32_t b = (uint32_t)(t / n_sel2), i = (uint32_t)(t % n_sel2);
+        const WireForm f = forms[sel2 ? sel2[i] : i];
+        const uint32_t j = b >> 5;
+        uint32_t v = f.c;
+        for (int k = 0; k < RV_LIN_K; k++) v ^= p.val[(size_t)f.b[k] * p.W + j] >> (b & 31);
+        out2[t] = (uint8_t)(v & 1u);
+    } else if (out64 && t - t2 < (uint64_t)n_sel64 * p.B) {
+        const uint64_t u = t - t2;
+        const uint32_t b = (uint32_t)(u / n_sel64), i = (uint32_t)(u % n_sel64);
+        out64[u] = p.v64[(size_t)ssa64[sel64 ? sel64[i] : i] * p.B + b];
+    }
+}
+
+// rv_evaluate_batch_device, one thread per witness: the count of failing assertions and the first one's op-list index (the smaller
+// of the two domains'; UINT64_MAX: none) as one 16-byte rv_eval_status.  f: the circuit's ordinal tables (its stream fields unread).
+__global__ __launch_bounds__(256) void k_eval_status(EvalParams p, EvalFold f, rv_eval_status* __restrict__ out) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= p.B) return;
+    rv_eval_status st;
+    st.n_failed = p.n_failed[b];
+    st.first_failed_op = min(ev_assert_op(f.rec2, f.op2, f.n2, p.first2[b]), ev_assert_op(f.rec64, f.op64, f.n64, p.first64[b]));
+    out[b] = st;
 }
 
 // streaming evaluation, once per chunk, one thread per witness: the chunk's first failing assertion (the smaller op index of the two
@@ -218,10 +254,10 @@ void launch_eval_walk(hipStream_t st, const EvalParams& p, const Gate* d_gates, 
     hipLaunchKernelGGL(k_eval_walk, dim3((p.W + S - 1) / S), dim3(threads), 0, st, p, d_gates, d_lr, d_gates64, d_ls64, n_levels, S);
 }
 
-void launch_eval_wit(hipStream_t st, const uint8_t* d_wit, uint32_t n, uint32_t B, uint32_t W, uint32_t* d_out) {
+void launch_eval_wit(hipStream_t st, const uint8_t* d_wit, size_t stride, uint32_t n, uint32_t B, uint32_t W, uint32_t* d_out) {
     const uint64_t t = (uint64_t)n * W;
     if (!t) return;
-    hipLaunchKernelGGL(k_eval_wit, dim3(blocks_for(t, 256)), dim3(256), 0, st, d_wit, n, B, W, d_out);
+    hipLaunchKernelGGL(k_eval_wit, dim3(blocks_for(t, 256)), dim3(256), 0, st, d_wit, stride, n, B, W, d_out);
 }
 
 void launch_eval_out(hipStream_t st, const EvalParams& p, const WireForm* d_forms, uint32_t n_gf2, const uint32_t* d_ssa64, uint32_t n_z64,
@@ -229,6 +265,17 @@ void launch_eval_out(hipStream_t st, const EvalParams& p, const WireForm* d_form
     const uint64_t t = (d_out2 ? (uint64_t)n_gf2 * p.B : 0) + (d_out64 ? (uint64_t)n_z64 * p.B : 0);
     if (!t) return;
     hipLaunchKernelGGL(k_eval_out, dim3(blocks_for(t, 256)), dim3(256), 0, st, p, d_forms, n_gf2, d_ssa64, n_z64, d_out2, d_out64);
+}
+
+void launch_eval_out_sel(hipStream_t st, const EvalParams& p, const WireForm* d_forms, const uint32_t* d_sel2, uint32_t n_sel2, const uint32_t* d_ssa64,
+                         const uint32_t* d_sel64, uint32_t n_sel64, uint8_t* d_out2, uint64_t* d_out64) {
+    const uint64_t t = (d_out2 ? (uint64_t)n_sel2 * p.B : 0) + (d_out64 ? (uint64_t)n_sel64 * p.B : 0);
+    if (!t) return;
+    hipLaunchKernelGGL(k_eval_out_sel, dim3(blocks_for(t, 256)), dim3(256), 0, st, p, d_forms, d_sel2, n_sel2, d_ssa64, d_sel64, n_sel64, d_out2, d_out64);
+}
+
+void launch_eval_status(hipStream_t st, const EvalParams& p, const EvalFold& f, rv_eval_status* d_out) {
+    hipLaunchKernelGGL(k_eval_status, dim3(blocks_for(p.B, 256)), dim3(256), 0, st, p, f, d_out);
 }
 
 void launch_eval_fold(hipStream_t st, const EvalParams& p, const EvalFold& f) {

@@ -203,7 +203,7 @@ static int eval_stream_chunk(rv_eval_stream* E, const Compiled& cc, uint64_t op_
     p.first2 = p.n_failed + B;
     p.first64 = p.first2 + B;
     HIPCHK(hipMemsetAsync(p.val + cc.zero_row * W, 0, W * 4, s));  // the chunk's zero row (unused operand slots)
-    launch_eval_wit(s, d + o_w2, (uint32_t)n_in, (uint32_t)B, (uint32_t)W, (uint32_t*)p.win);
+    launch_eval_wit(s, d + o_w2, n_in, (uint32_t)n_in, (uint32_t)B, (uint32_t)W, (uint32_t*)p.win);
     eval_run_levels(s, p, cc, (const Gate*)(d + o_g), (const LevelRange*)(d + o_lr), (const Gate64*)(d + o_g64), (const uint32_t*)(d + o_ls64));
     EvalFold f{};
     f.rec2 = (const uint32_t*)(d + o_r2);

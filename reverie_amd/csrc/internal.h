@@ -163,7 +163,8 @@ struct LevelRange;
 // schedule (b): one workgroup of `threads` per S witness words walks levels [0, n_levels); d_ls64 null: no Z64 gates
 void launch_eval_walk(hipStream_t st, const EvalParams& p, const Gate* d_gates, const LevelRange* d_lr, const Gate64* d_gates64, const uint32_t* d_ls64,
                       uint32_t n_levels, uint32_t S, uint32_t threads);
-void launch_eval_wit(hipStream_t st, const uint8_t* d_wit /*[B][n]*/, uint32_t n, uint32_t B, uint32_t W, uint32_t* d_out /*[n][W]*/);
+void launch_eval_wit(hipStream_t st, const uint8_t* d_wit /*[B][stride], n used*/, size_t stride, uint32_t n, uint32_t B, uint32_t W,
+                     uint32_t* d_out /*[n][W]*/);
 void launch_eval_out(hipStream_t st, const EvalParams& p, const WireForm* d_forms, uint32_t n_gf2, const uint32_t* d_ssa64, uint32_t n_z64,
                      uint8_t* d_out2 /*[B][n_gf2] or null*/, uint64_t* d_out64 /*[B][n_z64] or null*/);
 
@@ -181,6 +182,11 @@ struct EvalFold {
     uint64_t* total;     // [B] failing AssertZero ops so far
 };
 void launch_eval_fold(hipStream_t st, const EvalParams& p, const EvalFold& f);
+// rv_evaluate_batch_device: the values of the selected wires (d_sel2 / d_sel64 null: every wire, in order) and the statuses, written
+// where the caller wants them; f: the circuit's ordinal tables (op_base, first_op and total are not read)
+void launch_eval_out_sel(hipStream_t st, const EvalParams& p, const WireForm* d_forms, const uint32_t* d_sel2, uint32_t n_sel2, const uint32_t* d_ssa64,
+                         const uint32_t* d_sel64, uint32_t n_sel64, uint8_t* d_out2 /*[B][n_sel2] or null*/, uint64_t* d_out64 /*[B][n_sel64] or null*/);
+void launch_eval_status(hipStream_t st, const EvalParams& p, const EvalFold& f, rv_eval_status* d_out /*[B]*/);
 // the carried wires' values (GF(2) row w, Z64 slot 1 + w) of witnesses [b0, b0 + nb) -> [nb][n_gf2] bytes and [nb][n_z64] words
 void launch_eval_stream_out(hipStream_t st, const EvalParams& p, uint32_t n_gf2, uint32_t n_z64, uint32_t b0, uint32_t nb, uint8_t* d_out2,
                             uint64_t* d_out64);

@@ -149,7 +149,7 @@ extern "C" int rv_prove_ops(rv_ctx* ctx, const rv_op* ops, size_t n_ops, const u
     }
     if (rc) return rc;
     try {  // (the first proof of a circuit, or of one nobody keeps: without the early-corrections staging; a circuit seen before takes it)
-        rc = rv_prove_impl(ctx, c, wit_gf2, n_gf2, wit_z64, n_z64, seeds, proof, proof_len, nullptr, 0, /*allow_early=*/hit);
+        rc = rv_prove_impl(ctx, c, wit_host(wit_gf2, n_gf2, wit_z64, n_z64), seeds, proof, proof_len, nullptr, 0, /*allow_early=*/hit);
     } catch (...) {
         g_last_error = "out of host memory";
         rc = RV_E_NOMEM;

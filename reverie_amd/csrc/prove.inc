@@ -4,14 +4,13 @@
 // proof a slice of one buffer); otherwise the proof gets a buffer of its own
 // allow_early: the early-corrections path may be taken (a one-shot rv_prove_ops does without: its staging buffer is 3x the proof
 // of page-locked memory, tens of milliseconds to map for a gain of half a millisecond)
-static int rv_prove_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
-                        size_t n_z64, const uint8_t* seeds, uint8_t** proof, size_t* proof_len, uint8_t* dst = nullptr,
-                        size_t dst_cap = 0, bool allow_early = true);
+static int rv_prove_impl(rv_ctx* ctx, const rv_circuit* c, const WitSrc& w, const uint8_t* seeds, uint8_t** proof, size_t* proof_len,
+                        uint8_t* dst = nullptr, size_t dst_cap = 0, bool allow_early = true);
 
 extern "C" int rv_prove(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
                         size_t n_z64, const uint8_t* seeds, uint8_t** proof, size_t* proof_len) {
     try {  // no C++ exception may cross the C boundary
-        return rv_prove_impl(ctx, c, wit_gf2, n_gf2, wit_z64, n_z64, seeds, proof, proof_len);
+        return rv_prove_impl(ctx, c, wit_host(wit_gf2, n_gf2, wit_z64, n_z64), seeds, proof, proof_len);
     } catch (...) {
         g_last_error = "out of host memory";
         return RV_E_NOMEM;
@@ -20,8 +19,8 @@ extern "C" int rv_prove(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf2
 
 // (RV_BATCH_STATS: when the calling thread's last plain-path proof had its commitment queued, its openings queued, its stream done -- ms since entry)
 static thread_local double g_prove_marks[3];
-static int rv_prove_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
-                        size_t n_z64, const uint8_t* seeds, uint8_t** proof, size_t* proof_len, uint8_t* dst, size_t dst_cap, bool allow_early) {
+static int rv_prove_impl(rv_ctx* ctx, const rv_circuit* c, const WitSrc& w, const uint8_t* seeds, uint8_t** proof, size_t* proof_len, uint8_t* dst,
+                        size_t dst_cap, bool allow_early) {
     LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
     if (!ctx || !c || !proof || !proof_len) return RV_E_ARG;
     *proof = nullptr;
@@ -110,7 +109,7 @@ static int rv_prove_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf
     }
     g_prove_t0 = since();
     g_ht.begin();
-    int rc = rv_shard_commit_impl(ctx, c, wit_gf2, n_gf2, wit_z64, n_z64, seeds, 0, RV_TOTAL_REPS, &s, /*defer_sync=*/true, early ? &er : nullptr);
+    int rc = rv_shard_commit_impl(ctx, c, w, seeds, 0, RV_TOTAL_REPS, &s, /*defer_sync=*/true, early ? &er : nullptr);
     g_ht.mark("commit");
     if (rc) return rc;
     g_prove_marks[0] = since();
@@ -325,13 +324,12 @@ static int rv_prove_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf
     return rc;
 }
 
-static int rv_prove_device_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
-                                size_t n_z64, const uint8_t* seeds, void* dst_device, uint8_t comm[RV_HASH_SIZE],
+static int rv_prove_device_impl(rv_ctx* ctx, const rv_circuit* c, const WitSrc& w, const uint8_t* seeds, void* dst_device, uint8_t comm[RV_HASH_SIZE],
                                 uint8_t omit[RV_TOTAL_REPS], size_t lens[4]) {
     LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
     if (!ctx || !c || !seeds || !dst_device || !comm || !omit || !lens) return RV_E_ARG;
     rv_shard* s = nullptr;
-    int rc = rv_shard_commit_impl(ctx, c, wit_gf2, n_gf2, wit_z64, n_z64, seeds, 0, RV_TOTAL_REPS, &s, /*defer_sync=*/true);
+    int rc = rv_shard_commit_impl(ctx, c, w, seeds, 0, RV_TOTAL_REPS, &s, /*defer_sync=*/true);
     if (rc) return rc;
     do {
         void* d = nullptr;
@@ -360,7 +358,7 @@ extern "C" int rv_prove_device(rv_ctx* ctx, const rv_circuit* c, const uint8_t* 
                                size_t n_z64, const uint8_t* seeds, void* dst_device, uint8_t comm[RV_HASH_SIZE],
                                uint8_t omit[RV_TOTAL_REPS], size_t lens[4]) {
     try {  // no C++ exception may cross the C boundary
-        return rv_prove_device_impl(ctx, c, wit_gf2, n_gf2, wit_z64, n_z64, seeds, dst_device, comm, omit, lens);
+        return rv_prove_device_impl(ctx, c, wit_host(wit_gf2, n_gf2, wit_z64, n_z64), seeds, dst_device, comm, omit, lens);
     } catch (...) {
         g_last_error = "out of host memory";
         return RV_E_NOMEM;

@@ -923,25 +923,26 @@ static int shard_join(rv_shard* s) {
 
 // defer_sync: do not wait for the device (nor look at the invalid-witness flag): the caller queues more work behind
 // the commitment and checks s->d_err itself after its own synchronisation
-static int rv_shard_commit_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
-                               size_t n_z64, const uint8_t* seeds, uint32_t rep_begin, uint32_t rep_count, rv_shard** out,
-                               bool defer_sync = false, EarlyRun* ec = nullptr);
+static int rv_shard_commit_impl(rv_ctx* ctx, const rv_circuit* c, const WitSrc& w, const uint8_t* seeds, uint32_t rep_begin, uint32_t rep_count,
+                               rv_shard** out, bool defer_sync = false, EarlyRun* ec = nullptr);
 
 extern "C" int rv_shard_commit(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
                                size_t n_z64, const uint8_t* seeds, uint32_t rep_begin, uint32_t rep_count, rv_shard** out) {
     try {  // no C++ exception may cross the C boundary
-        return rv_shard_commit_impl(ctx, c, wit_gf2, n_gf2, wit_z64, n_z64, seeds, rep_begin, rep_count, out);
+        return rv_shard_commit_impl(ctx, c, wit_host(wit_gf2, n_gf2, wit_z64, n_z64), seeds, rep_begin, rep_count, out);
     } catch (...) {
         g_last_error = "out of host memory";
         return RV_E_NOMEM;
     }
 }
 
-static int rv_shard_commit_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
-                               size_t n_z64, const uint8_t* seeds, uint32_t rep_begin, uint32_t rep_count, rv_shard** out,
-                               bool defer_sync, EarlyRun* ec) {
+static int rv_shard_commit_impl(rv_ctx* ctx, const rv_circuit* c, const WitSrc& w, const uint8_t* seeds, uint32_t rep_begin, uint32_t rep_count,
+                               rv_shard** out, bool defer_sync, EarlyRun* ec) {
     LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
     if (!ctx || !c || !out || !seeds) return RV_E_ARG;
+    const uint8_t* const wit_gf2 = w.gf2;
+    const uint64_t* const wit_z64 = w.z64;
+    const size_t n_gf2 = w.n_gf2, n_z64 = w.n_z64;
     if (rep_count == 0 || rep_count % 8 || rep_begin % 8 || rep_begin + rep_count > RV_TOTAL_REPS) return RV_E_ARG;
     *out = nullptr;
     const Compiled& cc = c->cc;
@@ -969,20 +970,24 @@ static int rv_shard_commit_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t*
         if ((rc = dalloc(ctx, seed_bytes + std::max<size_t>(cc.n_in, 1), &s->d_seeds)) || (rc = dalloc(ctx, (size_t)s->R * 128, &s->d_keys))) return fail(rc);
         s->d_wit = s->d_seeds + seed_bytes;  // (inside d_seeds' block: the arena ignores it on release)
         memcpy(ctx->h_in, seeds, seed_bytes);
-        if (cc.n_in) memcpy(ctx->h_in + seed_bytes, wit_gf2, cc.n_in);
-        if (hipMemcpyAsync(s->d_seeds, ctx->h_in, seed_bytes + cc.n_in, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
+        // (a witness in device memory: only the seeds are staged, the witness is copied behind them from where it lies)
+        const size_t staged_wit = w.dev ? 0 : cc.n_in;
+        if (staged_wit) memcpy(ctx->h_in + seed_bytes, wit_gf2, staged_wit);
+        if (hipMemcpyAsync(s->d_seeds, ctx->h_in, seed_bytes + staged_wit, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
+        if (w.dev && cc.n_in && hipMemcpyAsync(s->d_wit, wit_gf2, cc.n_in, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
     } else {
         if ((rc = dalloc(ctx, seed_bytes, &s->d_seeds)) || (rc = dalloc(ctx, (size_t)s->R * 128, &s->d_keys)) ||
             (rc = dalloc(ctx, std::max<size_t>(cc.n_in, 1), &s->d_wit)))
             return fail(rc);
         if (hipMemcpyAsync(s->d_seeds, seeds, seed_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
-        if (cc.n_in && hipMemcpyAsync(s->d_wit, wit_gf2, cc.n_in, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
+        if (cc.n_in && hipMemcpyAsync(s->d_wit, wit_gf2, cc.n_in, w.kind(), ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
     }
     if (cc.n_in64) {
         if ((rc = dalloc(ctx, cc.n_in64, &s->d_wit64))) return fail(rc);
-        if (hipMemcpyAsync(s->d_wit64, wit_z64, cc.n_in64 * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        if (hipMemcpyAsync(s->d_wit64, wit_z64, cc.n_in64 * 8, w.kind(), ctx->stream) != hipSuccess)
             return fail(RV_E_DEVICE);
     }
+    wit_count(w, cc.n_in + cc.n_in64 * 8);
     static const bool vclr_on = [] {
         const char* e = getenv("RV_VCLR");
         return !e || atoi(e) != 0;

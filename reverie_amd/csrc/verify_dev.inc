@@ -19,10 +19,10 @@ extern "C" int rv_hook_verify_device_paths(uint64_t out[2]) {
     return RV_OK;
 }
 
-// RV_OK when p is a 16-byte aligned address in the memory of the context's device and, where the runtime can tell, p[0, len) lies
-// inside its allocation; RV_E_ARG otherwise (host memory, another device's)
-static int device_bytes_ok(rv_ctx* ctx, const void* p, size_t len) {
-    if ((uintptr_t)p & 15) return RV_E_ARG;
+// RV_OK when p is an address aligned to `align` bytes (a power of two) in the memory of the context's device and, where the runtime
+// can tell, p[0, len) lies inside its allocation; RV_E_ARG otherwise (host memory, another device's)
+static int device_bytes_ok(rv_ctx* ctx, const void* p, size_t len, size_t align) {
+    if ((uintptr_t)p & (align - 1)) return RV_E_ARG;
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, p) != hipSuccess) {  // (plain host memory: an error with some runtimes, "unregistered" with others)
         (void)hipGetLastError();
@@ -204,7 +204,7 @@ static int verify_device_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* c
     const int framing = lens ? VW_FRAMING_SECTIONS : VW_FRAMING_PROOF;
     *ok = 0;
     HIPCHK(hipSetDevice(ctx->device));
-    if (int rb = device_bytes_ok(ctx, d_bytes, len)) return rb;
+    if (int rb = device_bytes_ok(ctx, d_bytes, len, 16)) return rb;
     if (int rs2 = ctx_stream2(ctx)) return rs2;
     // ---- the walk and its 120 bytes back
     uint64_t* d_table = nullptr;

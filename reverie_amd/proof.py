@@ -227,6 +227,43 @@ class Circuit:
         n_failed = st[:, 0].astype(np.int64)
         return Evaluation(n_failed == 0, n_failed, st[:, 1].view(np.int64).copy(), gv, zv)
 
+    def evaluate_batch_device(self, wits_gf2, wits_z64=None, gf2_wires=None, z64_wires=None) -> "DeviceEvaluation":
+        """rv_evaluate_batch_device: evaluate_batch on witnesses that lie in GPU memory, with the results left there.  wits_gf2 /
+        wits_z64: torch GPU tensors on the circuit's device in the forms `_device_witness` takes ([B][n] uint8 or bool, [B][m] int64 or
+        uint64; a row stride is allowed); anything else raises TypeError.  gf2_wires / z64_wires: None = no values of that domain,
+        ... (Ellipsis) = every wire in order, or a sequence of wire indices (unsorted, repeats allowed; values need keep_wires).
+        -> DeviceEvaluation; column i of its `gf2` / `z64` equals column wires[i] of evaluate_batch(values=True).  No witness and no
+        result crosses to the host."""
+        import torch
+
+        dw = _device_witness(wits_gf2, wits_z64, self.ctx, "evaluate_batch_device", batched=True)
+        if dw is None:
+            raise TypeError("evaluate_batch_device takes torch tensors in GPU memory")
+        w, batch, _keep, _ = dw
+        dev = f"cuda:{self.ctx.device}"
+
+        def selection(wires, n_wires, dtype):
+            # -> (host index array or None, its ctypes pointer, n_sel, values tensor or None)
+            if wires is None:
+                return None, None, 0, None
+            if wires is Ellipsis:
+                return None, None, 0, torch.empty((batch, n_wires), dtype=dtype, device=dev)
+            idx = np.ascontiguousarray(np.asarray(wires, dtype=np.int64).reshape(-1))
+            if idx.size and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
+                raise ValueError("wire indices are unsigned 32-bit numbers")
+            sel = np.zeros(max(idx.size, 1), np.uint32)  # (never NULL: an empty list asks for no wire, not for every wire)
+            sel[:idx.size] = idx
+            return sel, sel.ctypes.data_as(C.c_void_p), idx.size, torch.empty((batch, idx.size), dtype=dtype, device=dev)
+
+        s2, p2, n2, gv = selection(gf2_wires, self.wire_counts[1], torch.uint8)
+        s64, p64, n64, zv = selection(z64_wires, self.wire_counts[0], torch.int64)
+        status = torch.empty((batch, 2), dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().rv_evaluate_batch_device(
+            self.ctx.handle, self.handle, C.c_size_t(batch), C.byref(w), p2, C.c_size_t(n2), p64, C.c_size_t(n64),
+            C.c_void_p(gv.data_ptr()) if gv is not None else None, C.c_void_p(zv.data_ptr()) if zv is not None else None,
+            C.c_void_p(status.data_ptr())))
+        return DeviceEvaluation(status, gv, zv)
+
     def record_sizes(self) -> Tuple[int, int]:
         """bytes of one OpenOnline record in the gf2 / z64 section of a proof of this circuit"""
         a, b = C.c_size_t(), C.c_size_t()
@@ -254,6 +291,30 @@ class Evaluation:
 
     def __repr__(self):
         return f"Evaluation(ok={self.ok!r}, n_failed={self.n_failed!r}, first_failed_op={self.first_failed_op!r})"
+
+
+class DeviceEvaluation:
+    """What Circuit.evaluate_batch_device returns: torch tensors on the circuit's device.  `status` is int64 [B][2] (the
+    rv_eval_status records); `n_failed`, `first_failed_op` (-1 where every assertion holds) and `ok` are views of it resp. computed
+    from it on the device; `gf2` is uint8 [B][n_sel] and `z64` int64 [B][n_sel] (the words' bits), None where no values were asked."""
+
+    def __init__(self, status, gf2=None, z64=None):
+        self.status, self.gf2, self.z64 = status, gf2, z64
+
+    @property
+    def n_failed(self):
+        return self.status[:, 0]
+
+    @property
+    def first_failed_op(self):
+        return self.status[:, 1]
+
+    @property
+    def ok(self):
+        return self.status[:, 0] == 0
+
+    def __repr__(self):
+        return f"DeviceEvaluation(batch={self.status.shape[0]}, device={self.status.device})"
 
 
 def evaluate_composite_program(ops, wit_gf2, wit_z64=(), wire_counts=None, ctx: Optional[Context] = None):
@@ -284,6 +345,56 @@ def _witness(wit_gf2, wit_z64):
     g = np.ascontiguousarray(np.asarray(wit_gf2, dtype=np.uint8))
     z = np.ascontiguousarray(np.asarray(wit_z64, dtype=np.uint64))
     return g, z
+
+
+def _device_witness(wit_gf2, wit_z64, ctx: "Optional[Context]", what: str, batched: bool):
+    """The witnesses of a call as an rv_dev_witness when they lie in GPU memory: -> (descriptor, batch, the tensors (kept alive by
+    the caller for the call), context), or None when neither is a torch GPU tensor (the call then goes the host way, as ever).
+    Taken: uint8 or bool tensors [n] (batched: [B][n]) for GF(2), int64 or uint64 tensors [m] ([B][m]) for Z64, on the context's
+    device, the last dimension contiguous; a row stride is allowed.  The other witness may be absent (None or empty); one witness in
+    GPU memory and the other on the host is a TypeError.  Refuses before any context is made (ctx None: the default one), and waits
+    for the tensors' device, so that the witnesses are complete before the library's stream reads them."""
+    import sys
+
+    torch = sys.modules.get("torch")
+
+    def on_gpu(t):
+        return torch is not None and isinstance(t, torch.Tensor) and t.device.type == "cuda"
+
+    g_dev, z_dev = on_gpu(wit_gf2), on_gpu(wit_z64)
+    if not g_dev and not z_dev:
+        return None
+    for t, here in ((wit_gf2, g_dev), (wit_z64, z_dev)):
+        if not here and t is not None and np.size(t):
+            raise TypeError(f"{what}: one witness is in GPU memory and the other on the host")
+    dims = 2 if batched else 1
+    w = _lib.DevWitness()
+    batch = None
+    device = None
+    for name, t, dtypes in (("gf2", wit_gf2 if g_dev else None, (torch.uint8, torch.bool)),
+                            ("z64", wit_z64 if z_dev else None, (torch.int64, getattr(torch, "uint64", torch.int64)))):
+        if t is None:
+            continue
+        if t.dtype not in dtypes or t.dim() != dims or (t.shape[-1] > 1 and t.stride(-1) != 1) or \
+                (batched and t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise ValueError(f"{what}: the {name} witness must be {' or '.join(str(d) for d in dtypes)} "
+                             f"{'[batch][n]' if batched else '[n]'} with a contiguous last dimension, got {t.dtype} {tuple(t.shape)} "
+                             f"strides {tuple(t.stride())}")
+        if batched:
+            if batch is not None and t.shape[0] != batch:
+                raise ValueError(f"{what}: the witnesses' batch sizes differ")
+            batch = t.shape[0]
+        if device is not None and t.device != device:
+            raise ValueError(f"{what}: the witnesses are on different devices")
+        device = t.device
+        setattr(w, name, t.data_ptr() if t.numel() else None)
+        setattr(w, "n_" + name, t.shape[-1])
+        setattr(w, "stride_" + name, t.stride(0) if batched and t.shape[0] > 1 else t.shape[-1])
+    ctx = ctx or Context.default()
+    if device.index is not None and device.index != ctx.device:
+        raise ValueError(f"the witness is on {device}, the context on device {ctx.device}")
+    torch.cuda.synchronize(device)
+    return w, (batch if batched else 1), (wit_gf2, wit_z64), ctx
 
 
 class Proof:
@@ -324,15 +435,20 @@ class Proof:
     def new(circuit, wit_gf2: Sequence[int], wit_z64: Sequence[int], wire_counts: Optional[Tuple[int, int]] = None,
             seeds: Union[None, bytes, np.ndarray] = None, ctx: Optional[Context] = None) -> "Proof":
         """Proof::new.  `seeds` (256x16 bytes) injects the per-repetition seeds the reference
-        draws from OsRng; None draws them from the OS."""
-        g, z = _witness(wit_gf2, wit_z64)
+        draws from OsRng; None draws them from the OS.  Witnesses that are torch GPU tensors (`_device_witness`) are read where
+        they lie (rv_prove_wdev; a raw op list is compiled first): the proof is the one their host copies give."""
+        dw = _device_witness(wit_gf2, wit_z64, circuit.ctx if isinstance(circuit, Circuit) else ctx, "Proof.new", batched=False)
+        g, z = _witness(wit_gf2, wit_z64) if dw is None else (None, None)
         s = None
         if seeds is not None:
             s = np.ascontiguousarray(np.frombuffer(bytes(seeds), np.uint8) if isinstance(seeds, (bytes, bytearray))
                                      else np.asarray(seeds, dtype=np.uint8)).reshape(TOTAL_REPS, 16)
         out = C.c_void_p()
         n = C.c_size_t()
-        if isinstance(circuit, Circuit):
+        if dw is not None:
+            c = _as_circuit(circuit, wire_counts, dw[3])
+            _lib.check(_lib.lib().rv_prove_wdev(c.ctx.handle, c.handle, C.byref(dw[0]), _ptr(s), C.byref(out), C.byref(n)))
+        elif isinstance(circuit, Circuit):
             c = _as_circuit(circuit, wire_counts, ctx)
             _lib.check(_lib.lib().rv_prove(c.ctx.handle, c.handle, _ptr(g), C.c_size_t(len(g)), _ptr(z), C.c_size_t(len(z)),
                                            _ptr(s), C.byref(out), C.byref(n)))
@@ -350,22 +466,30 @@ class Proof:
                   ctx: Optional[Context] = None) -> "list[Proof]":
         """`len(wits_gf2)` proofs of one circuit in one pass (rv_prove_batch): every dependency level is launched
         once for the whole batch.  wits_gf2: [B][n] bits; wits_z64: [B][m] words or None; seeds: [B][256][16] bytes or
-        None (OS randomness).  Each proof equals Proof.new(circuit, wits_gf2[b], wits_z64[b], seeds=seeds[b])."""
-        c = _as_circuit(circuit, wire_counts, ctx, whole_prover=True)
-        g = np.ascontiguousarray(np.asarray(wits_gf2, dtype=np.uint8))
-        if g.ndim != 2:
-            raise ValueError("wits_gf2 must be [batch][n_bits]")
-        batch = g.shape[0]
-        z = np.ascontiguousarray(np.asarray(wits_z64 if wits_z64 is not None else np.zeros((batch, 0)), dtype=np.uint64))
-        if z.ndim != 2 or z.shape[0] != batch:
-            raise ValueError("wits_z64 must be [batch][n_words]")
+        None (OS randomness).  Each proof equals Proof.new(circuit, wits_gf2[b], wits_z64[b], seeds=seeds[b]).  Witnesses that are
+        torch GPU tensors (`_device_witness`; rows may be strided) are read where they lie (rv_prove_batch_wdev)."""
+        dw = _device_witness(wits_gf2, wits_z64, circuit.ctx if isinstance(circuit, Circuit) else ctx, "Proof.new_batch", batched=True)
+        c = _as_circuit(circuit, wire_counts, ctx if dw is None else dw[3], whole_prover=True)
+        if dw is None:
+            g = np.ascontiguousarray(np.asarray(wits_gf2, dtype=np.uint8))
+            if g.ndim != 2:
+                raise ValueError("wits_gf2 must be [batch][n_bits]")
+            batch = g.shape[0]
+            z = np.ascontiguousarray(np.asarray(wits_z64 if wits_z64 is not None else np.zeros((batch, 0)), dtype=np.uint64))
+            if z.ndim != 2 or z.shape[0] != batch:
+                raise ValueError("wits_z64 must be [batch][n_words]")
+        else:
+            batch = dw[1]
         s = None
         if seeds is not None:
             s = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint8)).reshape(batch, TOTAL_REPS, 16)
         outs = (C.c_void_p * batch)()
         lens = (C.c_size_t * batch)()
-        _lib.check(_lib.lib().rv_prove_batch(c.ctx.handle, c.handle, C.c_size_t(batch), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z),
-                                             C.c_size_t(z.shape[1]), _ptr(s), outs, lens))
+        if dw is not None:
+            _lib.check(_lib.lib().rv_prove_batch_wdev(c.ctx.handle, c.handle, C.c_size_t(batch), C.byref(dw[0]), _ptr(s), outs, lens))
+        else:
+            _lib.check(_lib.lib().rv_prove_batch(c.ctx.handle, c.handle, C.c_size_t(batch), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z),
+                                                 C.c_size_t(z.shape[1]), _ptr(s), outs, lens))
         return [Proof(_owned=(C.c_void_p(outs[b]), int(lens[b]))) for b in range(batch)]
 
     def verify(self, circuit, wire_counts: Optional[Tuple[int, int]] = None, ctx: Optional[Context] = None,
@@ -436,7 +560,8 @@ class DeviceProof:
     def new(circuit: "Circuit", wit_gf2: Sequence[int], wit_z64: Sequence[int], seeds: Union[None, bytes, np.ndarray] = None,
             ctx: Optional[Context] = None) -> "DeviceProof":
         """rv_prove_device: Proof::new with the openings left in GPU memory (the sections form).  `seeds` (256 x 16 bytes) as
-        Proof.new; None draws them from the OS (the entry point takes no NULL)."""
+        Proof.new; None draws them from the OS (the entry point takes no NULL).  Witnesses that are torch GPU tensors
+        (`_device_witness`) are read where they lie (rv_prove_device_wdev)."""
         import os
 
         import torch
@@ -445,7 +570,8 @@ class DeviceProof:
             raise TypeError("DeviceProof.new takes a compiled Circuit")
         if ctx is not None and ctx is not circuit.ctx:
             raise ValueError("the circuit was compiled in another context")
-        g, z = _witness(wit_gf2, wit_z64)
+        dw = _device_witness(wit_gf2, wit_z64, circuit.ctx, "DeviceProof.new", batched=False)
+        g, z = _witness(wit_gf2, wit_z64) if dw is None else (None, None)
         raw = os.urandom(TOTAL_REPS * 16) if seeds is None else (bytes(seeds) if isinstance(seeds, (bytes, bytearray)) else None)
         s = np.ascontiguousarray(np.frombuffer(raw, np.uint8) if raw is not None else np.asarray(seeds, dtype=np.uint8)).reshape(TOTAL_REPS, 16)
         sz2, sz64 = circuit.record_sizes()
@@ -453,8 +579,12 @@ class DeviceProof:
         lens = (C.c_size_t * 4)()
         comm = np.zeros(32, np.uint8)
         omit = np.zeros(TOTAL_REPS, np.uint8)
-        _lib.check(_lib.lib().rv_prove_device(circuit.ctx.handle, circuit.handle, _ptr(g), C.c_size_t(len(g)), _ptr(z), C.c_size_t(len(z)),
-                                              _ptr(s), C.c_void_p(out.data_ptr()), _ptr(comm), _ptr(omit), lens))
+        if dw is not None:
+            _lib.check(_lib.lib().rv_prove_device_wdev(circuit.ctx.handle, circuit.handle, C.byref(dw[0]), _ptr(s), C.c_void_p(out.data_ptr()),
+                                                       _ptr(comm), _ptr(omit), lens))
+        else:
+            _lib.check(_lib.lib().rv_prove_device(circuit.ctx.handle, circuit.handle, _ptr(g), C.c_size_t(len(g)), _ptr(z), C.c_size_t(len(z)),
+                                                  _ptr(s), C.c_void_p(out.data_ptr()), _ptr(comm), _ptr(omit), lens))
         return DeviceProof(sections=out, lens=[int(x) for x in lens], comm=comm.tobytes(), ctx=circuit.ctx)
 
     @property
@@ -535,7 +665,8 @@ def prove_batch_device(circuit: "Circuit", wits_gf2, wits_z64=None, seeds=None, 
     all of them views of ONE torch uint8 GPU tensor of batch * stride bytes (stride: the proof length -- 64 + 40 * the circuit's
     record sizes + 2 * 216 * 48 -- rounded up to 256), which every view keeps alive.  Proof b's bytes are those of
     Proof.new_batch(...)[b] for the same witnesses and seeds.  wits_gf2: [B][n] bits; wits_z64: [B][m] words or None; seeds:
-    [B][256][16] bytes, None draws them from the OS (the entry point takes no NULL)."""
+    [B][256][16] bytes, None draws them from the OS (the entry point takes no NULL).  Witnesses that are torch GPU tensors
+    (`_device_witness`; rows may be strided) are read where they lie (rv_prove_batch_device_wdev)."""
     import os
 
     import torch
@@ -544,15 +675,20 @@ def prove_batch_device(circuit: "Circuit", wits_gf2, wits_z64=None, seeds=None, 
         raise TypeError("prove_batch_device takes a compiled Circuit")
     if ctx is not None and ctx is not circuit.ctx:
         raise ValueError("the circuit was compiled in another context")
-    g = np.ascontiguousarray(np.asarray(wits_gf2, dtype=np.uint8))
-    if g.ndim != 2:
-        raise ValueError("wits_gf2 must be [batch][n_bits]")
-    batch = g.shape[0]
+    dw = _device_witness(wits_gf2, wits_z64, circuit.ctx, "prove_batch_device", batched=True)
+    if dw is None:
+        g = np.ascontiguousarray(np.asarray(wits_gf2, dtype=np.uint8))
+        if g.ndim != 2:
+            raise ValueError("wits_gf2 must be [batch][n_bits]")
+        batch = g.shape[0]
+    else:
+        batch = dw[1]
     if batch == 0:
         return []
-    z = np.ascontiguousarray(np.asarray(wits_z64 if wits_z64 is not None else np.zeros((batch, 0)), dtype=np.uint64))
-    if z.ndim != 2 or z.shape[0] != batch:
-        raise ValueError("wits_z64 must be [batch][n_words]")
+    if dw is None:
+        z = np.ascontiguousarray(np.asarray(wits_z64 if wits_z64 is not None else np.zeros((batch, 0)), dtype=np.uint64))
+        if z.ndim != 2 or z.shape[0] != batch:
+            raise ValueError("wits_z64 must be [batch][n_words]")
     if seeds is None:
         seeds = np.frombuffer(os.urandom(batch * TOTAL_REPS * 16), np.uint8)
     s = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint8)).reshape(batch, TOTAL_REPS, 16)
@@ -561,8 +697,12 @@ def prove_batch_device(circuit: "Circuit", wits_gf2, wits_z64=None, seeds=None, 
     stride = (want + 255) & ~255
     out = torch.empty(batch * stride, dtype=torch.uint8, device=f"cuda:{circuit.ctx.device}")
     n = C.c_size_t()
-    _lib.check(_lib.lib().rv_prove_batch_device(circuit.ctx.handle, circuit.handle, C.c_size_t(batch), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z),
-                                                C.c_size_t(z.shape[1]), _ptr(s), C.c_void_p(out.data_ptr()), C.c_size_t(stride), C.byref(n)))
+    if dw is not None:
+        _lib.check(_lib.lib().rv_prove_batch_device_wdev(circuit.ctx.handle, circuit.handle, C.c_size_t(batch), C.byref(dw[0]), _ptr(s),
+                                                         C.c_void_p(out.data_ptr()), C.c_size_t(stride), C.byref(n)))
+    else:
+        _lib.check(_lib.lib().rv_prove_batch_device(circuit.ctx.handle, circuit.handle, C.c_size_t(batch), _ptr(g), C.c_size_t(g.shape[1]), _ptr(z),
+                                                    C.c_size_t(z.shape[1]), _ptr(s), C.c_void_p(out.data_ptr()), C.c_size_t(stride), C.byref(n)))
     if n.value != want:
         raise _lib.ReverieError(7, f"proof length {n.value}, expected {want}")
     proofs = []

@@ -15,7 +15,10 @@ N proofs per call, all modes in one process on the same statements, one JSON lin
     host      rv_prove_batch, and rv_verify_batch on its proofs
     device    rv_prove_batch_device, and rv_verify_batch_device on what it left in GPU memory
 each as median, min and max ms per call (and the median per proof) over --calls calls after --warmup, with the ways the device
-verifier's proofs went (rv_hook_verify_batch_device_paths).  The device prover's bytes are compared with the host prover's first."""
+verifier's proofs went (rv_hook_verify_batch_device_paths).  The device prover's bytes are compared with the host prover's first.
+--witness {host,device} (repeatable, default host; all in one process on the same statements): where the provers take their
+witnesses from -- device: torch GPU tensors, read where they lie (rv_prove_batch_wdev / rv_prove_batch_device_wdev), reported as
+"prove": {"host_wdev": ..., "device_wdev": ...} beside the host-witness figures."""
 import argparse
 import json
 import os
@@ -40,6 +43,8 @@ ap.add_argument("--warmup", type=int, default=2, help="untimed calls per --proof
 ap.add_argument("--batch", type=int, default=0, help="time the batch entry points at this many proofs per call instead")
 ap.add_argument("--circuit", action="append", choices=("aes128", "sha256", "mixed"), default=[],
                 help="--batch: the circuit (default aes128); mixed: the 2 000-gate mixed circuit of tools/batch_z64.py")
+ap.add_argument("--witness", action="append", choices=("host", "device"), default=[],
+                help="--batch: the provers' witnesses in host memory (default) / in GPU tensors")
 ap.add_argument("--only-headline", action="store_true", help="the headline circuit only (p_and = 0.5)")
 args = ap.parse_args()
 
@@ -124,17 +129,26 @@ def batch_modes(name, B):
     if [bytes(p) for p in host] != [d.tensor.cpu().numpy().tobytes() for d in dev]:
         raise SystemExit(f"{name}: rv_prove_batch_device's bytes differ from rv_prove_batch's")
     out = {"circuit": name, "batch": B, "proof_bytes": len(host[0]), "prove": {}, "verify": {}}
+    wits = {"host": (g, zz)}
+    if "device" in args.witness:
+        import torch
+
+        wits["device"] = (torch.from_numpy(g).cuda(), torch.from_numpy(z.view(np.int64)).cuda() if z.shape[1] else None)
+        if [bytes(p) for p in reverie_amd.Proof.new_batch(c, *wits["device"], seeds=bs)] != [bytes(p) for p in host]:
+            raise SystemExit(f"{name}: rv_prove_batch_wdev's bytes differ from rv_prove_batch's")
     for mode in args.proof:
+        if mode == "sections":
+            raise SystemExit("--batch takes --proof host and --proof device")
+        prover = reverie_amd.Proof.new_batch if mode == "host" else reverie_amd.prove_batch_device
+        for where in args.witness or ["host"]:
+            wg, wz = wits[where]
+            _, out["prove"][mode if where == "host" else mode + "_wdev"] = timed(lambda: prover(c, wg, wz, seeds=bs))
         if mode == "host":
-            _, out["prove"][mode] = timed(lambda: reverie_amd.Proof.new_batch(c, g, zz, seeds=bs))
             ok, out["verify"][mode] = timed(lambda: reverie_amd.verify_batch(c, host))
-        elif mode == "device":
-            _, out["prove"][mode] = timed(lambda: reverie_amd.prove_batch_device(c, g, zz, seeds=bs))
+        else:
             p0 = paths()
             ok, out["verify"][mode] = timed(lambda: reverie_amd.verify_batch_device(c, dev))
             out["verify"][mode]["paths"] = [a - b for a, b in zip(paths(), p0)]
-        else:
-            raise SystemExit("--batch takes --proof host and --proof device")
         out["verify"][mode]["ok"] = all(ok)
     c.close()
     return out
