@@ -404,7 +404,7 @@ int rv_eval_stream_set_compile_flags(rv_eval_stream *s, uint32_t flags);
 int rv_eval_stream_feed(rv_eval_stream *s, const rv_op *ops, size_t n_ops, const uint8_t *wit_gf2, size_t n_gf2, const uint64_t *wit_z64,
                         size_t n_z64);
 /* rv_eval_stream_feed for an op array in the memory of the stream's device (rv_stream_feed_device's conventions; the witnesses
- * stay in host memory): the same statuses and values. */
+ * stay in host memory -- rv_eval_stream_feed_wdev, below, reads them in device memory): the same statuses and values. */
 int rv_eval_stream_feed_device(rv_eval_stream *s, const rv_op *d_ops, size_t n_ops, const uint8_t *wit_gf2, size_t n_gf2,
                                const uint64_t *wit_z64, size_t n_z64);
 int rv_eval_stream_finish(rv_eval_stream *s, uint8_t *gf2_values, uint64_t *z64_values, rv_eval_status *st);
@@ -503,9 +503,9 @@ int rv_stream_feed(rv_stream *s, const rv_op *ops, size_t n_ops, const uint8_t *
                    size_t n_z64);
 /* rv_stream_feed for an op array that already sits in device memory: d_ops is n_ops packed 24-byte records in the memory of the
  * stream's device (rv_circuit_compile_device's convention: the caller keeps ownership and must have finished writing it; 8-byte
- * aligned, RV_E_ARG otherwise).  The streams still take their witnesses from host memory, in rv_stream_feed's layouts (a stream digests
- * the witness on the host as it is fed; the calls that read witnesses in device memory are the _wdev provers and
- * rv_evaluate_batch_device).  Serves every stream rv_stream_feed
+ * aligned, RV_E_ARG otherwise).  Through this call and rv_stream_feed the streams still take their witnesses from host memory, in
+ * rv_stream_feed's layouts; rv_stream_feed_wdev (below: "streams in device memory") reads them in device memory, with ops from either
+ * side.  Serves every stream rv_stream_feed
  * serves -- single and batch provers in both passes, the streaming verifiers -- and may be mixed freely with it inside one stream
  * and between its passes: the pieces are cut by the same rule, the digests and counters are the same numbers, and every proof,
  * answer, error code and rv_stream_info figure is what rv_stream_feed gives for the same ops.  The op list is not copied to the
@@ -602,6 +602,46 @@ int rv_stream_verify_finish_batch(rv_stream *s, uint32_t flags, int *ok /* [batc
 int rv_verify_streaming_batch(rv_ctx *ctx, const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, size_t batch,
                               const uint8_t *const *proofs, const size_t *proof_lens, uint32_t flags, size_t max_chunk_ops,
                               int *ok, rv_stream_info *info);
+
+/* ---- streams in device memory: witnesses in, proofs out, verification in place --------------------------------------------------
+ * For a caller whose circuit, witness and proof live on the GPU: with rv_stream_feed_device's ops these calls keep the witness, the
+ * proof and the verifier's input off PCIe.  They are pure additions: every other entry point, proof byte and error code is unchanged.
+ *
+ * rv_stream_feed_wdev / rv_eval_stream_feed_wdev: a feed whose witnesses are read in the memory of the stream's device.  `ops` is a
+ * host array (ops_on_device == 0, rv_stream_feed's rules) or device memory (!= 0, rv_stream_feed_device's rules).  `w`: n_gf2 / n_z64
+ * are the elements still available to this feed, per witness (more may be passed; fewer: RV_E_WITNESS_SHORT, as the siblings); witness
+ * b of a batch stream starts at gf2 + b*stride_gf2 and z64 + b*stride_z64, a single stream and a batch of one ignore the strides.  A
+ * verifier stream takes w == NULL or a descriptor with both counts 0; a prover or evaluator stream needs a descriptor.  Checked before
+ * anything is launched (RV_E_ARG): the pointers are memory of the stream's device, the ranges lie inside their allocations (where the
+ * runtime can tell), alignment 1 (gf2) / 8 (z64), stride >= n when batch > 1.  Every error, these included, is sticky: the stream
+ * then only accepts its abort.  Host and device witness feeds may be mixed inside a stream and between its passes, like host and
+ * device op feeds: the proof, comm, every rv_stream_info figure and every error code are rv_stream_feed's for the same witness bytes
+ * (the position-keyed witness digest that lets finish refuse a pass 2 fed another witness is summed by a kernel for these feeds, and
+ * read at commit and at finish).  When the call returns the library no longer reads the witness (rv_eval_stream_feed_wdev therefore
+ * waits for the device once, which rv_eval_stream_feed does not). */
+int rv_stream_feed_wdev(rv_stream *s, const rv_op *ops, size_t n_ops, int ops_on_device, const rv_dev_witness *w);
+int rv_eval_stream_feed_wdev(rv_eval_stream *s, const rv_op *ops, size_t n_ops, int ops_on_device, const rv_dev_witness *w);
+/* rv_stream_finish / rv_stream_finish_batch with the proof left in device memory: the same bytes (comm, the four counts, the four
+ * sections -- rv_prove's for the same seeds) at dst_device, for a batch at dst_device + b*stride; no proof byte is copied to the host.
+ * The single form needs a 16-byte aligned destination (what rv_verify_device accepts) and cap >= rv_stream_info.proof_bytes; the
+ * batch form follows rv_prove_batch_device: 256-byte alignment, stride a multiple of 256 and >= the proof length.  A destination
+ * that is too small, misaligned, not memory of the stream's device or outside its allocation gives RV_E_ARG with *proof_len = the
+ * required length, and the stream is not finished: the caller may call again.  rv_stream_finish_batch_device on a single stream is
+ * rv_stream_finish_device with cap = stride; the single form on a batch > 1 gives RV_E_ARG. */
+int rv_stream_finish_device(rv_stream *s, void *dst_device, size_t cap, size_t *proof_len);
+int rv_stream_finish_batch_device(rv_stream *s, void *dst_device, size_t stride, size_t *proof_len);
+/* rv_stream_verify_begin / _begin_batch for proof bytes in the memory of the context's device (16-byte aligned; RV_E_ARG otherwise):
+ * the framing is walked where the bytes lie, the verifier's slot arrays are made on the device and the chunks read the vectors from
+ * the caller's buffer, which must outlive the stream and must not be written meanwhile.  Only the walk's table crosses to the host
+ * (offsets, lengths, the 80 omit bytes, comm).  Feeds, rv_stream_verify_finish(_batch), info and abort are unchanged, and the answer
+ * and return code are rv_verify_streaming's on a host copy of the same bytes, for every byte string: bytes that are not a well-framed
+ * proof of acceptable records are copied to a host buffer the stream owns and begin as the host form does (RV_E_PROOF_MALFORMED, or
+ * ok = 0 for wrong counts; in a batch such a member answers 0 alone).  d_proofs is a host array of device pointers. */
+int rv_stream_verify_begin_device(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, const uint8_t *d_proof, size_t proof_len,
+                                  size_t max_chunk_ops, rv_stream **out);
+int rv_stream_verify_begin_batch_device(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, size_t batch,
+                                        const uint8_t *const *d_proofs /* host array of device pointers */,
+                                        const size_t *proof_lens, size_t max_chunk_ops, rv_stream **out);
 
 /* ---- sharded form (one process per GPU; repetitions [rep_begin, rep_begin+rep_count),
  * both multiples of 8).  rv_prove == commit(0,256) -> combine -> challenge -> open ->
@@ -963,6 +1003,18 @@ int rv_hook_eval_schedules(uint64_t out[2]);
  * device-to-device, or read in place by the evaluator), out[2] = evaluation result bytes copied device-to-host.  Only the elements
  * the Input ops consume are counted.  Calls refused before anything is launched count nothing. */
 int rv_hook_witness_traffic(uint64_t out[3]);
+/* The streams' own running totals since process start, counted where they queue their copies: out[0] = witness bytes sent
+ * host-to-device, out[1] = witness bytes taken from device memory, out[2] = proof bytes copied device-to-host at finish, out[3] =
+ * proof bytes copied host-to-device at a streaming verifier's begin.  A chunk served from kept transcripts copies no witness. */
+int rv_hook_stream_traffic(uint64_t out[4]);
+/* rv_stream_verify_begin_device / _begin_batch_device proofs of this process that took out[0] = the in-place path, out[1] = the host
+ * fallback (calls refused with RV_E_ARG count as neither). */
+int rv_hook_stream_verify_device_paths(uint64_t out[2]);
+/* The streams' position-keyed witness digest of n_gf2 GF(2) bytes at input ordinal first_gf2 and n_z64 words at first_z64: *host_out
+ * from the host loop, *dev_out from the kernel the device-witness feeds use, run on a device copy of the same arrays (the GF(2) copy
+ * starts 3 bytes into its allocation).  They must agree on every input. */
+int rv_hook_stream_wit_sums(rv_ctx *ctx, const uint8_t *gf2, size_t n_gf2, uint64_t first_gf2, const uint64_t *z64, size_t n_z64,
+                            uint64_t first_z64, uint64_t *host_out, uint64_t *dev_out);
 /* The early-corrections plan of a program (host only, no device): the ops are compiled as rv_circuit_compile_ex(flags) would and
  * the plan rv_prove would use is built and checked against the compiled gate records.  out[0] = a plan exists (0 / 1: the circuit
  * is pure GF(2) with >= 2^21 Mul gates -- RV_EARLY_MIN -- or pure Z64, its preprocessing rows complete in step with the levels

@@ -102,6 +102,9 @@ SYMBOLS = [
     "rv_prove_batch_device", "rv_verify_batch_device", "rv_hook_verify_batch_device_paths",
     "rv_prove_wdev", "rv_prove_device_wdev", "rv_prove_batch_wdev", "rv_prove_batch_device_wdev", "rv_evaluate_batch_device",
     "rv_hook_witness_traffic",
+    "rv_stream_feed_wdev", "rv_eval_stream_feed_wdev", "rv_stream_finish_device", "rv_stream_finish_batch_device",
+    "rv_stream_verify_begin_device", "rv_stream_verify_begin_batch_device",
+    "rv_hook_stream_traffic", "rv_hook_stream_verify_device_paths", "rv_hook_stream_wit_sums",
     "rv_hook_extract_bits", "rv_hook_extract_from_bits", "rv_hook_pack_corr_all", "rv_hook_unpack_bits", "rv_hook_extract64", "rv_hook_unpack64",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
@@ -155,6 +158,16 @@ ARGTYPES = {
     "rv_prove_batch_device_wdev": [_P, _P, _Z, C.POINTER(DevWitness), _P, _P, _Z, C.POINTER(C.c_size_t)],
     "rv_evaluate_batch_device": [_P, _P, _Z, C.POINTER(DevWitness), _P, _Z, _P, _Z, _P, _P, _P],
     "rv_hook_witness_traffic": [C.POINTER(C.c_uint64)],
+    # streams in device memory: witnesses in, proofs out, verification in place
+    "rv_stream_feed_wdev": [_P, _P, _Z, C.c_int, C.POINTER(DevWitness)],
+    "rv_eval_stream_feed_wdev": [_P, _P, _Z, C.c_int, C.POINTER(DevWitness)],
+    "rv_stream_finish_device": [_P, _P, _Z, C.POINTER(C.c_size_t)],
+    "rv_stream_finish_batch_device": [_P, _P, _Z, C.POINTER(C.c_size_t)],
+    "rv_stream_verify_begin_device": [_P, _Z, _Z, _P, _Z, _Z, C.POINTER(C.c_void_p)],
+    "rv_stream_verify_begin_batch_device": [_P, _Z, _Z, _Z, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), _Z, C.POINTER(C.c_void_p)],
+    "rv_hook_stream_traffic": [C.POINTER(C.c_uint64)],
+    "rv_hook_stream_verify_device_paths": [C.POINTER(C.c_uint64)],
+    "rv_hook_stream_wit_sums": [_P, _P, _Z, C.c_uint64, _P, _Z, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     # the mask generators (parity hook)
     "rv_hook_maskgen": [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _P],
     # the opening and unpacking kernels (parity hooks)

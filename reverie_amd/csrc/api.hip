@@ -1576,4 +1576,5 @@ extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
 #include "comm.inc"
 #include "eval.inc"
 #include "eval_stream.inc"
+#include "stream_wdev.inc"
 #include "witness_dev.inc"

@@ -128,13 +128,23 @@ static int eval_stream_reserve(rv_eval_stream* E, const Compiled& cc) {
     return RV_OK;
 }
 
+// the witness rows of a feed: witness b's n_gf2 / n_z64 elements at gf2 + b * stride2, z64 + b * stride64 (elements); dev: in the
+// memory of the stream's device (rv_eval_stream_feed_wdev)
+struct EvalWitRows {
+    const uint8_t* gf2;
+    size_t n_gf2, stride2;
+    const uint64_t* z64;
+    size_t n_z64, stride64;
+    bool dev;
+};
+
 // One compiled chunk on the device.  op_base: the index of its first op in the whole op list.  The chunk consumes witness elements
-// [*u2, *u2 + n_in) and [*u64, *u64 + n_in64) of every witness row of the feed (strides n_gf2 / n_z64) and advances *u2 / *u64.
-static int eval_stream_chunk(rv_eval_stream* E, const Compiled& cc, uint64_t op_base, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
-                             size_t n_z64, size_t* u2, size_t* u64) {
+// [*u2, *u2 + n_in) and [*u64, *u64 + n_in64) of every witness row of the feed and advances *u2 / *u64.  Host rows are staged
+// with the chunk's tables; device rows go into the same input area by one strided device-to-device copy per domain.
+static int eval_stream_chunk(rv_eval_stream* E, const Compiled& cc, uint64_t op_base, const EvalWitRows& wit, size_t* u2, size_t* u64) {
     if (cc.n_user_random) return RV_E_UNSUPPORTED;  // (a Random wire has no single cleartext value)
     const size_t n_in = cc.n_in, n_in64 = cc.n_in64, B = E->B, W = E->W;
-    if (n_gf2 - *u2 < n_in || n_z64 - *u64 < n_in64) return RV_E_WITNESS_SHORT;
+    if (wit.n_gf2 - *u2 < n_in || wit.n_z64 - *u64 < n_in64) return RV_E_WITNESS_SHORT;
     rv_ctx* ctx = E->ctx;
     hipStream_t s = ctx->stream;
     if (int rc = eval_stream_reserve(E, cc)) return rc;
@@ -150,9 +160,10 @@ static int eval_stream_chunk(rv_eval_stream* E, const Compiled& cc, uint64_t op_
     const size_t n2 = cc.assert_rec2.size(), n64 = cc.assert_rec64.size();
     const size_t o_g = part(cc.gates.size() * sizeof(Gate)), o_lr = part(cc.level_range.size() * sizeof(LevelRange)),
                  o_g64 = part(cc.gates64.size() * sizeof(Gate64)), o_ls64 = part(has64 ? cc.level_start64.size() * 4 : 0),
-                 o_r2 = part(n2 * 4), o_op2 = part(n2 * 8), o_r64 = part(n64 * 4), o_op64 = part(n64 * 8), o_wz = part(B * n_in64 * 8),
-                 o_w2 = part(B * n_in);
-    const size_t staged = off;
+                 o_r2 = part(n2 * 4), o_op2 = part(n2 * 8), o_r64 = part(n64 * 4), o_op64 = part(n64 * 8);
+    const size_t tables = off;
+    const size_t o_wz = part(B * n_in64 * 8), o_w2 = part(B * n_in);
+    const size_t staged = wit.dev ? tables : off;
     const size_t o_win = part(n_in * W * 4);
     const size_t block = off;
     // the chunk's working set beside the wire store (rv_eval_stream_info::peak_chunk_bytes)
@@ -179,12 +190,18 @@ static int eval_stream_chunk(rv_eval_stream* E, const Compiled& cc, uint64_t op_
     put(o_op2, cc.assert_op2.data(), n2 * 8);
     put(o_r64, cc.assert_rec64.data(), n64 * 4);
     put(o_op64, cc.assert_op64.data(), n64 * 8);
-    for (size_t b = 0; b < B; b++) {
-        if (n_in64) memcpy(h + o_wz + b * n_in64 * 8, wit_z64 + b * n_z64 + *u64, n_in64 * 8);
-        if (n_in) memcpy(h + o_w2 + b * n_in, wit_gf2 + b * n_gf2 + *u2, n_in);
+    for (size_t b = 0; b < B && !wit.dev; b++) {
+        if (n_in64) memcpy(h + o_wz + b * n_in64 * 8, wit.z64 + b * wit.stride64 + *u64, n_in64 * 8);
+        if (n_in) memcpy(h + o_w2 + b * n_in, wit.gf2 + b * wit.stride2 + *u2, n_in);
     }
-    HIPCHK(hipMemcpyAsync(d, h, staged, hipMemcpyHostToDevice, s));
+    if (staged) HIPCHK(hipMemcpyAsync(d, h, staged, hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(ctx->ev_open[slot], s));
+    if (wit.dev) {
+        if (n_in64)
+            HIPCHK(hipMemcpy2DAsync(d + o_wz, n_in64 * 8, wit.z64 + *u64, (B > 1 ? wit.stride64 : n_in64) * 8, n_in64 * 8, B, hipMemcpyDeviceToDevice, s));
+        if (n_in) HIPCHK(hipMemcpy2DAsync(d + o_w2, n_in, wit.gf2 + *u2, B > 1 ? wit.stride2 : n_in, n_in, B, hipMemcpyDeviceToDevice, s));
+    }
+    stream_traffic(wit.dev ? 1 : 0, B * (n_in + n_in64 * 8));
     // RV_EVAL_POISON=1 (tests): the chunk's scratch rows and slots start non-zero, never the carried store (read at every call)
     if (getenv("RV_EVAL_POISON") && atoi(getenv("RV_EVAL_POISON"))) {
         HIPCHK(hipMemsetAsync(E->d_val + E->gf2_wires * W, 0xA5, (cc.n_rows - E->gf2_wires) * W * 4, s));
@@ -228,12 +245,11 @@ static int eval_stream_chunk(rv_eval_stream* E, const Compiled& cc, uint64_t op_
 static unsigned eval_stream_threads() { return std::min(cpu_budget(), 16u); }
 
 // ops_on_device: `ops` is in the memory of the stream's device (rv_eval_stream_feed_device; feed_ops.inc)
-static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, bool ops_on_device, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2,
-                                 const uint64_t* wit_z64, size_t n_z64) {
+static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, bool ops_on_device, size_t n_ops, const EvalWitRows& wit) {
     LibBusy busy_guard;
     if (!E) return RV_E_ARG;
     if (E->sticky) return E->sticky;
-    if (E->finished || (n_ops && !ops) || (n_gf2 && !wit_gf2) || (n_z64 && !wit_z64) || (ops_on_device && ((uintptr_t)ops & 7))) return E->sticky = RV_E_ARG;
+    if (E->finished || (n_ops && !ops) || (wit.n_gf2 && !wit.gf2) || (wit.n_z64 && !wit.z64) || (ops_on_device && ((uintptr_t)ops & 7))) return E->sticky = RV_E_ARG;
     E->fed = true;
     HIPCHK(hipSetDevice(E->ctx->device));
     const std::vector<size_t> cut = stream_cuts(n_ops, E->max_chunk_ops);  // (the streaming prover's rule)
@@ -267,7 +283,7 @@ static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, bool ops_o
             if (rd == RV_OK) g_stream_device_chunks.fetch_add(1, std::memory_order_relaxed);
             rc = rd == RV_COMPILE_FALLBACK ? compile_on_host(i) : rd;
         }
-        if (!rc) rc = eval_stream_chunk(E, *pieces[i], first_op + cut[i], wit_gf2, n_gf2, wit_z64, n_z64, &u2, &u64);
+        if (!rc) rc = eval_stream_chunk(E, *pieces[i], first_op + cut[i], wit, &u2, &u64);
         pieces[i].reset();  // (host memory of the compiled piece: freed here, on the main thread, while the GPU runs it)
         pipe.consumed(i, rc);
     }
@@ -278,7 +294,7 @@ static int eval_stream_feed_impl(rv_eval_stream* E, const rv_op* ops, bool ops_o
 
 extern "C" int rv_eval_stream_feed(rv_eval_stream* E, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
                                    size_t n_z64) {
-    const int rc = guarded([&] { return eval_stream_feed_impl(E, ops, false, n_ops, wit_gf2, n_gf2, wit_z64, n_z64); });
+    const int rc = guarded([&] { return eval_stream_feed_impl(E, ops, false, n_ops, EvalWitRows{wit_gf2, n_gf2, n_gf2, wit_z64, n_z64, n_z64, false}); });
     if (rc == RV_E_NOMEM && E) E->sticky = rc;  // (a thrown one too: the stream is dead after any failed allocation)
     return rc;
 }
@@ -286,7 +302,7 @@ extern "C" int rv_eval_stream_feed(rv_eval_stream* E, const rv_op* ops, size_t n
 extern "C" int rv_eval_stream_feed_device(rv_eval_stream* E, const rv_op* d_ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2,
                                           const uint64_t* wit_z64, size_t n_z64) {
     // (every read of d_ops has finished when this returns: the device compiles and the copies down are waited for)
-    const int rc = guarded([&] { return eval_stream_feed_impl(E, d_ops, true, n_ops, wit_gf2, n_gf2, wit_z64, n_z64); });
+    const int rc = guarded([&] { return eval_stream_feed_impl(E, d_ops, true, n_ops, EvalWitRows{wit_gf2, n_gf2, n_gf2, wit_z64, n_z64, n_z64, false}); });
     if (rc == RV_E_NOMEM && E) E->sticky = rc;
     return rc;
 }

@@ -27,4 +27,15 @@ static_assert(sizeof(PieceSums) == PIECE_SUM_WORDS * 8, "PieceSums is ten packed
 void launch_piece_sums(hipStream_t st, const rv_op* d_ops, const uint64_t* d_cut, size_t n_pieces, size_t max_piece, uint64_t first_index,
                        PieceSums* d_sums);
 
+// The witness twin of the digest above (stream.inc: wit_digest), for the witnesses of a feed that sit in device memory: proof b of
+// n_proofs (blockIdx.y) adds  sum_i mix(2 * (first2 + i), w2[b * stride2 + i] & 1) + sum_j mix(2 * (first64 + j) + 1, w64[b * stride64 + j])
+// over i < n2 GF(2) bytes and j < n64 Z64 words into *acc[b] (one 64-bit atomic add per workgroup; the accumulators are not cleared).
+// w2 is read byte by byte (alignment 1), w64 is 8-byte aligned; strides in elements.
+struct WitSumsAcc {
+    static constexpr uint32_t MAX = 64;
+    uint64_t* acc[MAX];
+};
+void launch_wit_sums(hipStream_t st, const uint8_t* d_w2, uint64_t stride2, uint64_t n2, uint64_t first2, const uint64_t* d_w64, uint64_t stride64,
+                     uint64_t n64, uint64_t first64, uint64_t* const* acc, size_t n_proofs);
+
 }  // namespace rv

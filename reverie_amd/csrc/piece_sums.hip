@@ -76,7 +76,47 @@ __global__ __launch_bounds__(TB) void k_piece_sums(const rv_op* __restrict__ ops
     }
 }
 
+// wit_digest's sum for proof blockIdx.y: item i < n2 is a GF(2) byte (only bit 0 counts), item n2 + j a Z64 word; each keyed by its
+// input ordinal (64-bit: a long stream's ordinals pass 2^32).  The reduction is k_piece_sums': wavefront, LDS, one atomic add.
+__global__ __launch_bounds__(TB) void k_wit_sums(const uint8_t* __restrict__ w2, uint64_t stride2, uint64_t n2, uint64_t first2,
+                                                 const uint64_t* __restrict__ w64, uint64_t stride64, uint64_t n64, uint64_t first64, WitSumsAcc A) {
+    const uint8_t* p2 = w2 + (uint64_t)blockIdx.y * stride2;      // (not dereferenced when n2 == 0)
+    const uint64_t* p64 = w64 + (uint64_t)blockIdx.y * stride64;  // (... n64 == 0)
+    auto mix = [](uint64_t pos, uint64_t x) {
+        uint64_t h = pos * 0x9E3779B97F4A7C15ull;
+        h ^= x + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
+        h *= 0xFF51AFD7ED558CCDull;
+        return h ^ (h >> 29);
+    };
+    unsigned long long v = 0;
+    const uint64_t total = n2 + n64;
+    for (uint64_t i = (uint64_t)blockIdx.x * TB + threadIdx.x; i < total; i += (uint64_t)gridDim.x * TB)
+        v += i < n2 ? mix(2 * (first2 + i), p2[i] & 1u) : mix(2 * (first64 + (i - n2)) + 1, p64[i - n2]);
+    __shared__ uint64_t sh[TB / WAVE];
+    for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_down(v, d, WAVE);
+    if (threadIdx.x % WAVE == 0) sh[threadIdx.x / WAVE] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long s = 0;
+        for (int wv = 0; wv < TB / WAVE; wv++) s += sh[wv];
+        if (s) atomicAdd((unsigned long long*)A.acc[blockIdx.y], s);
+    }
+}
+
 }  // namespace
+
+void launch_wit_sums(hipStream_t st, const uint8_t* d_w2, uint64_t stride2, uint64_t n2, uint64_t first2, const uint64_t* d_w64, uint64_t stride64,
+                     uint64_t n64, uint64_t first64, uint64_t* const* acc, size_t n_proofs) {
+    if (!n_proofs || !(n2 + n64)) return;
+    const size_t per_group = (size_t)TB * 4;
+    const uint32_t gx = (uint32_t)std::min<size_t>(std::max<size_t>((n2 + n64 + per_group - 1) / per_group, 1), MAX_GROUPS);
+    for (size_t b0 = 0; b0 < n_proofs; b0 += WitSumsAcc::MAX) {
+        WitSumsAcc A{};
+        const uint32_t nb = (uint32_t)std::min<size_t>(n_proofs - b0, WitSumsAcc::MAX);
+        for (uint32_t b = 0; b < nb; b++) A.acc[b] = acc[b0 + b];
+        hipLaunchKernelGGL(k_wit_sums, dim3(gx, nb), dim3(TB), 0, st, d_w2 + b0 * stride2, stride2, n2, first2, d_w64 + b0 * stride64, stride64, n64, first64, A);
+    }
+}
 
 void launch_piece_sums(hipStream_t st, const rv_op* d_ops, const uint64_t* d_cut, size_t n_pieces, size_t max_piece, uint64_t first_index,
                        PieceSums* d_sums) {

@@ -40,6 +40,11 @@ struct StreamTotals {
 
 }  // namespace
 
+// rv_hook_stream_traffic, counted where the streams queue their copies: witness bytes sent host-to-device, witness bytes taken from
+// device memory, proof bytes copied device-to-host at finish, proof bytes copied host-to-device at a verifier's begin
+static std::atomic<uint64_t> g_stream_traffic[4];
+static void stream_traffic(int k, uint64_t bytes) { g_stream_traffic[k].fetch_add(bytes, std::memory_order_relaxed); }
+
 // up to 24 small device-to-device copies as ONE launch (the pending rows of pass 2: up to 7 + 7 single rows and three short runs per chunk
 // were as many hipMemcpyAsync calls, ~5 us of GPU time and a launch each).  Sizes in bytes, multiples of 4; src and dst do not overlap.
 struct CopySegs {
@@ -197,6 +202,12 @@ struct rv_stream {
     int* d_err0 = nullptr;
     bool unsettled = false;  // chunks were issued without a wait: stream_feed_settle reads d_err behind them
     StreamTotals run, tot;  // running counters of the current pass / totals of pass 1
+    // The witness digest of the chunks whose witnesses were fed from device memory (rv_stream_feed_wdev): k_wit_sums adds into
+    // *d_wit_sum, and run.wit_hash is the host sum plus this word -- read at commit in the copy commit waits for anyway, and once at
+    // finish.  Allocated and cleared by the stream's first such chunk (a host-fed stream never has it), cleared again where commit
+    // resets the pass.
+    uint64_t* d_wit_sum = nullptr;
+    bool wit_dev_pass = false;  // a chunk of the current pass added to *d_wit_sum
     // pass 1: per transcript stream (TR_PRE .. TR_ON64) the incremental tree and the unhashed tail: the events of the last, incomplete
     // BLAKE3 chunk -- [1024][NQ/2] bytes, [1024][NQ] u32, [R][128] u64 twice (TR_KIND)
     struct Transcript {
@@ -222,6 +233,11 @@ struct rv_stream {
     uint64_t peak_bytes = 0;  // largest chunk working set seen (diagnostics)
     // pass 3 = the streaming VERIFIER (rv_stream_verify_begin): one pass, the chunks run in verify mode against the proof
     const uint8_t* h_proof = nullptr;  // the caller's proof bytes (must outlive the stream)
+    // rv_stream_verify_begin_device, the in-place path: d_vproof is the CALLER's buffer (not released here), no host copy of the proof
+    // exists, and finish decides from what the walk brought: comm and the 80 omit bytes of the online records
+    bool proof_in_place = false;
+    uint8_t dev_comm[32] = {0}, dev_rec_omit[2 * RV_ONLINE_REPS] = {0};
+    std::vector<uint8_t> own_proof;    // ... its fallback: the host copy h_proof points to
     size_t proof_len = 0;
     bool format_bad = false;           // wrong repetition counts: the answer is `false` (proof/mod.rs:225-230), nothing runs
     int dev_flags = 0;                 // RV_DEV_ZERO_CHECK of the chunks so far
@@ -294,7 +310,7 @@ struct rv_stream {
 
     void free_all() {
         void* ps[] = {d_seeds, d_keys, d_rkbytes, d_rk, d_rows, d_corr, d_wmask64, d_wcorr64, d_err, d_err0, d_dig, d_h, d_omit, d_offs, d_proof, d_pend_rec, d_pend_in, d_pend_pre,
-                      d_vproof, d_omit_v, d_omit64_v, d_hco, d_hco64, d_keep, d_keep64, d_onm, d_rk64, d_src};
+                      d_wit_sum, proof_in_place ? nullptr : d_vproof, d_omit_v, d_omit64_v, d_hco, d_hco64, d_keep, d_keep64, d_onm, d_rk64, d_src};
         for (void* p : ps) ctx->release(p);
         for (auto& kv : kept) release_kept(kv.second);
         kept.clear();
@@ -386,7 +402,9 @@ extern "C" void rv_stream_abort(rv_stream* S) {
     delete S;
 }
 
-static int stream_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, const uint8_t* seeds, size_t max_chunk_ops, rv_stream** out) {
+// seeds_on_device: `seeds` (not null) is 256 x 16 bytes in the memory of the context's device, written by work already queued on its stream
+static int stream_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, const uint8_t* seeds, size_t max_chunk_ops, rv_stream** out,
+                             bool seeds_on_device = false) {
     if (!ctx || !out) return RV_E_ARG;
     *out = nullptr;
     if (gf2_wires > 0x3FFFFFFFull || z64_wires > 0x3FFFFFFFull) return RV_E_UNSUPPORTED;
@@ -433,7 +451,8 @@ static int stream_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, co
         return fail(rc);
     for (int kind = 0; kind < TR_KINDS; kind++)
         if ((rc = dalloc(ctx, TR_KIND[kind].tail_bytes(), &S->tr[kind].d_tail))) return fail(rc);
-    if (hipMemcpyAsync(S->d_seeds, seeds, (size_t)R * 16, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
+    if (hipMemcpyAsync(S->d_seeds, seeds, (size_t)R * 16, seeds_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        return fail(RV_E_DEVICE);
     if (hipMemsetAsync(S->d_err, 0, sizeof(int), ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
     launch_expand_seeds(ctx->stream, S->d_seeds, R, S->d_keys);
     launch_key_schedule(ctx->stream, S->d_keys, R * 8, S->d_rkbytes);
@@ -577,6 +596,7 @@ struct WitnessRows {
     size_t n_gf2, stride2;
     const uint64_t* z64;
     size_t n_z64, stride64;
+    bool dev = false;  // the rows are in the memory of the stream's device (rv_stream_feed_wdev)
     const uint8_t* gf2_of(size_t b) const { return gf2 ? gf2 + b * stride2 : nullptr; }
     const uint64_t* z64_of(size_t b) const { return z64 ? z64 + b * stride64 : nullptr; }
     void advance(size_t u2, size_t u64) {
@@ -720,6 +740,7 @@ struct ChunkRun {
             if ((rc = open_proof(bi))) return rc;
         if ((rc = cp.finish("pending rows"))) return rc;
         keep_for_all_or_none();
+        if (!ver && wit.dev && (rc = digest_witness_on_device())) return rc;  // (in front of the chunk's or the feed's wait: the last read of the caller's rows)
         t_issue = Clock::now();
         if ((rc = settle())) return rc;
         count();
@@ -952,8 +973,15 @@ struct ChunkRun {
         P->peak_bytes = std::max(P->peak_bytes, ws);
         carry_in(P, q);
         if (!ver && !q.kp) {
-            if (cc.n_in && (rc = hip_code(hipMemcpyAsync(q.d_wit, wit.gf2_of(bi), cc.n_in, hipMemcpyHostToDevice, st), "GF(2) witness"))) return rc;
-            if (cc.n_in64 && (rc = hip_code(hipMemcpyAsync(q.d_wit64, wit.z64_of(bi), cc.n_in64 * 8, hipMemcpyHostToDevice, st), "Z64 witness"))) return rc;
+            // (device rows: device-to-device; a batch's Z64 words -- 8-byte aligned -- ride in the step's small-copy launch, the GF(2)
+            // bytes have alignment 1 and keep the copy call)
+            const hipMemcpyKind kind = wit.dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+            if (cc.n_in && (rc = hip_code(hipMemcpyAsync(q.d_wit, wit.gf2_of(bi), cc.n_in, kind, st), "GF(2) witness"))) return rc;
+            if (cc.n_in64 && wit.dev && batched)
+                cp.add(q.d_wit64, wit.z64_of(bi), cc.n_in64 * 8);
+            else if (cc.n_in64 && (rc = hip_code(hipMemcpyAsync(q.d_wit64, wit.z64_of(bi), cc.n_in64 * 8, kind, st), "Z64 witness")))
+                return rc;
+            stream_traffic(wit.dev ? 1 : 0, cc.n_in + cc.n_in64 * 8);
         }
         if (ver && (rc = supplied_values(P, q))) return rc;
         if (bi == 0) t_alloc = Clock::now();
@@ -1111,7 +1139,7 @@ struct ChunkRun {
     // nothing on the host waits for its openings)
     int settle() {
         int rc = RV_OK;
-        if (no_wait)
+        if (no_wait || (use_kept && !hashing && !ver && wit.dev))  // (a kept chunk runs nothing, but its device witness is still being digested)
             S->unsettled = true;
         else if (hashing || !use_kept)
             rc = stream_read_errs(proofs, "stream chunk");
@@ -1120,9 +1148,26 @@ struct ChunkRun {
         return rc;
     }
 
+    // The witness digest of a chunk fed from device memory: k_wit_sums over every proof's rows into the proofs' accumulators, keyed by
+    // the ordinals the stream is at (count() advances them afterwards).  Also for a chunk served from kept transcripts, as the host loop.
+    int digest_witness_on_device() {
+        std::vector<uint64_t*> acc(proofs.size());
+        for (size_t bi = 0; bi < proofs.size(); bi++) {
+            rv_stream* Q = proofs[bi];
+            if (!Q->d_wit_sum) {
+                if (int rc = dalloc(ctx, 1, &Q->d_wit_sum)) return rc;
+                if (int rc = hip_code(hipMemsetAsync(Q->d_wit_sum, 0, 8, st), "witness digest")) return rc;
+            }
+            acc[bi] = Q->d_wit_sum;
+            Q->wit_dev_pass = true;
+        }
+        launch_wit_sums(st, wit.gf2, wit.stride2, cc.n_in, S->run.n_in, wit.z64, wit.stride64, cc.n_in64, S->run.n_in64, acc.data(), acc.size());
+        return RV_OK;
+    }
+
     // the counters: the same for every proof but the witness digest
     void count() {
-        if (!ver)
+        if (!ver && !wit.dev)
             for (size_t bi = 0; bi < proofs.size(); bi++) {  // (before the ordinals advance)
                 rv_stream* Q = proofs[bi];
                 Q->run.wit_hash += wit_digest(wit.gf2_of(bi), cc.n_in, Q->run.n_in, wit.z64_of(bi), cc.n_in64, Q->run.n_in64);
@@ -1366,8 +1411,8 @@ static std::vector<FeedPiece> feed_pieces(rv_stream* S, const FeedOps& fo, const
 // The pieces are compiled ahead on worker threads (piece_pipe.h) and run in order; with one thread each is prepared right before it
 // runs, unpredicted and unstaged.  ops_on_device: `ops` is in the memory of the stream's device (rv_stream_feed_device); what differs is
 // behind FeedOps / PieceOnHost (feed_ops.inc).
-static int stream_feed_impl(rv_stream* H, const rv_op* ops, bool ops_on_device, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
-                            size_t n_z64) {
+// wit0: the feed's witness rows (host: rows n_gf2 / n_z64 apart; rv_stream_feed_wdev: the descriptor's, checked by its caller).
+static int stream_feed_impl(rv_stream* H, const rv_op* ops, bool ops_on_device, size_t n_ops, const WitnessRows& wit0) {
     LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
     if (!H || (n_ops && !ops) || (ops_on_device && ((uintptr_t)ops & 7))) return RV_E_ARG;
     if (H->sticky) return H->sticky;
@@ -1381,7 +1426,7 @@ static int stream_feed_impl(rv_stream* H, const rv_op* ops, bool ops_on_device, 
     using Clock = std::chrono::steady_clock;
     auto secs = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
     const auto t_feed0 = Clock::now();
-    WitnessRows wit{wit_gf2, n_gf2, n_gf2, wit_z64, n_z64, n_z64};
+    WitnessRows wit = wit0;
     const std::vector<size_t> cut = stream_cuts(n_ops, S->max_chunk_ops);  // piece i = ops [cut[i], cut[i + 1])
     const size_t n_pieces = cut.size() - 1;
     const unsigned n_threads = (unsigned)std::min<size_t>(stream_threads(), n_pieces);
@@ -1496,7 +1541,7 @@ static int stream_feed_settle(rv_stream* H) {
 
 extern "C" int rv_stream_feed(rv_stream* S, const rv_op* ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
                               size_t n_z64) {
-    const int rc = guarded([&] { return stream_feed_impl(S, ops, false, n_ops, wit_gf2, n_gf2, wit_z64, n_z64); });
+    const int rc = guarded([&] { return stream_feed_impl(S, ops, false, n_ops, WitnessRows{wit_gf2, n_gf2, n_gf2, wit_z64, n_z64, n_z64}); });
     // (also after a failed feed: the caller's witness arrays and the ring slots may still feed copies)
     const int rs = stream_feed_settle(S);
     return rc ? rc : rs;
@@ -1504,7 +1549,7 @@ extern "C" int rv_stream_feed(rv_stream* S, const rv_op* ops, size_t n_ops, cons
 
 extern "C" int rv_stream_feed_device(rv_stream* S, const rv_op* d_ops, size_t n_ops, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
                                      size_t n_z64) {
-    const int rc = guarded([&] { return stream_feed_impl(S, d_ops, true, n_ops, wit_gf2, n_gf2, wit_z64, n_z64); });
+    const int rc = guarded([&] { return stream_feed_impl(S, d_ops, true, n_ops, WitnessRows{wit_gf2, n_gf2, n_gf2, wit_z64, n_z64, n_z64}); });
     const int rs = stream_feed_settle(S);  // (every read of d_ops has finished: the device compiles and the copies down are waited for)
     return rc ? rc : rs;
 }
@@ -1572,9 +1617,12 @@ static int stream_commit_impl(rv_stream* S, uint8_t comm_out[RV_HASH_SIZE]) {
     ctx->phase(-1);
     S->offs.assign((size_t)8 * R + OL_WORDS, 0);
     uint8_t back[RV_TOTAL_REPS + 32];
+    uint64_t wit_sum = 0;  // pass 1's device half of the witness digest (the layout above does not depend on it)
     HIPCHK(hipMemcpyAsync(S->offs.data(), S->d_offs, S->offs.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(back, S->d_omit, sizeof back, hipMemcpyDeviceToHost, st));
+    if (S->wit_dev_pass) HIPCHK(hipMemcpyAsync(&wit_sum, S->d_wit_sum, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    S->tot.wit_hash += wit_sum;
     ctx->collect();
     memcpy(S->omit, back, RV_TOTAL_REPS);
     memcpy(S->comm, back + RV_TOTAL_REPS, 32);
@@ -1590,6 +1638,8 @@ static int stream_commit_impl(rv_stream* S, uint8_t comm_out[RV_HASH_SIZE]) {
         HIPCHK(hipMemsetAsync(S->d_wcorr64, 0, (1 + S->z64_wires) * (size_t)R * 8, st));
     }
     HIPCHK(hipMemsetAsync(S->d_err, 0, sizeof(int), st));
+    if (S->wit_dev_pass) HIPCHK(hipMemsetAsync(S->d_wit_sum, 0, 8, st));
+    S->wit_dev_pass = false;
     S->run = StreamTotals{};
     S->pass = 2;
     return RV_OK;
@@ -1608,19 +1658,33 @@ extern "C" int rv_stream_commit(rv_stream* S, uint8_t comm[RV_HASH_SIZE]) {
     return guarded([&] { return stream_commit_impl(S, comm); });
 }
 
-static int stream_finish_impl(rv_stream* S, uint8_t** proof, size_t* proof_len) {
-    if (!S || !proof || !proof_len) return RV_E_ARG;
-    *proof = nullptr;
-    *proof_len = 0;
+// pass 2's device half of the witness digest into run.wit_hash (once: the accumulator starts again at zero)
+static int stream_settle_wit_sum(rv_stream* S) {
+    if (!S->wit_dev_pass) return RV_OK;
+    uint64_t wit_sum = 0;
+    HIPCHK(hipMemcpyAsync(&wit_sum, S->d_wit_sum, 8, hipMemcpyDeviceToHost, S->ctx->stream));
+    HIPCHK(hipMemsetAsync(S->d_wit_sum, 0, 8, S->ctx->stream));
+    HIPCHK(hipStreamSynchronize(S->ctx->stream));
+    S->run.wit_hash += wit_sum;
+    S->wit_dev_pass = false;
+    return RV_OK;
+}
+
+// d_dst (null: the host form): the finished proof goes, counts and all, to the caller's device memory -- checked by the caller
+static int stream_finish_impl(rv_stream* S, uint8_t** proof, size_t* proof_len, uint8_t* d_dst = nullptr) {
+    if (!S || (!proof && !d_dst) || !proof_len) return RV_E_ARG;
+    if (proof) *proof = nullptr;
+    if (!d_dst) *proof_len = 0;
     if (!S->bat.empty()) return RV_E_ARG;  // (rv_stream_finish_batch)
     if (S->sticky) return S->sticky;
     if (S->pass != 2) return RV_E_ARG;
-    if (!(S->run == S->tot)) return S->sticky = RV_E_ARG;  // pass 2 was not fed what pass 1 was
     rv_ctx* ctx = S->ctx;
     hipStream_t st = ctx->stream;
     constexpr uint32_t R = rv_stream::R, NQ = rv_stream::NQ;
     HIPCHK(hipSetDevice(ctx->device));
     int rc;
+    if ((rc = stream_settle_wit_sum(S))) return S->sticky = rc;
+    if (!(S->run == S->tot)) return S->sticky = RV_E_ARG;  // pass 2 was not fed what pass 1 was
     // ---- the vectors' last bytes: the pending (< 8) items, or the all-zero extra byte the reference always appends
     // (gf2/share.rs:126-138, gf2/recon.rs:217-229)
     std::vector<uint64_t> dst((size_t)2 * R, 0);
@@ -1630,27 +1694,39 @@ static int stream_finish_impl(rv_stream* S, uint8_t** proof, size_t* proof_len) 
     }
     OnlineList ol = S->ol;
     for (uint32_t k = 0; k < ol.n; k++) ol.dst[k] += (S->run.n_pre - S->pend_pre) / 8;
-    uint64_t* d_dst = nullptr;
+    uint64_t* d_dst_rows = nullptr;
     OnlineList* d_ol = nullptr;
-    if ((rc = dalloc(ctx, dst.size(), &d_dst)) || (rc = dalloc(ctx, 1, &d_ol))) return S->sticky = rc;
-    HIPCHK(hipMemcpyAsync(d_dst, dst.data(), dst.size() * 8, hipMemcpyHostToDevice, st));
+    if ((rc = dalloc(ctx, dst.size(), &d_dst_rows)) || (rc = dalloc(ctx, 1, &d_ol))) return S->sticky = rc;
+    HIPCHK(hipMemcpyAsync(d_dst_rows, dst.data(), dst.size() * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_ol, &ol, sizeof ol, hipMemcpyHostToDevice, st));
     ctx->phase(RV_PH_OPEN);
-    launch_extract_bits(st, S->d_pend_rec, nullptr, S->pend_rec, NQ, 0, S->d_omit, d_dst + 0 * R, S->d_proof);
-    launch_extract_bits(st, S->d_pend_in, nullptr, S->pend_in, NQ, 1, S->d_omit, d_dst + 1 * R, S->d_proof);
+    launch_extract_bits(st, S->d_pend_rec, nullptr, S->pend_rec, NQ, 0, S->d_omit, d_dst_rows + 0 * R, S->d_proof);
+    launch_extract_bits(st, S->d_pend_in, nullptr, S->pend_in, NQ, 1, S->d_omit, d_dst_rows + 1 * R, S->d_proof);
     launch_extract_from_bits(st, S->d_pend_pre, S->pend_pre, NQ, d_ol, S->d_proof);
     const size_t DW = (size_t)R * 8;
     launch_open_headers(st, R, S->d_omit, S->d_seeds, S->d_keys, S->d_dig + 1 * DW, S->d_dig + 3 * DW, S->d_offs, S->d_offs + R, S->L.l2r, S->L.l2c,
                         S->L.l2i, S->L.l64r, S->L.l64c, S->L.l64i, S->d_proof);
     ctx->phase(-1);
+    if (d_dst) {  // the counts on the device, then the framed proof to where the caller wants it: no proof byte crosses to the host
+        if (!launch_frame_counts(st, S->d_proof, 0, 1, S->L.len) || hipGetLastError() != hipSuccess) return S->sticky = RV_E_DEVICE;
+        if (hipMemcpyAsync(d_dst, S->d_proof, S->L.total, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return S->sticky = hip_fail(hipGetLastError(), "stream proof D2D", __FILE__, __LINE__);
+        ctx->collect();
+        ctx->release(d_dst_rows);
+        ctx->release(d_ol);
+        *proof_len = S->L.total;
+        S->sticky = RV_E_ARG;  // a finished stream takes no further calls (rv_stream_abort releases it)
+        return RV_OK;
+    }
     uint8_t* out = (uint8_t*)out_alloc(S->L.total);
     if (!out) return S->sticky = RV_E_NOMEM;
+    stream_traffic(2, S->L.total);
     if (hipMemcpyAsync(out, S->d_proof, S->L.total, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
         rv_free(out);
         return S->sticky = hip_fail(hipGetLastError(), "stream proof D2H", __FILE__, __LINE__);
     }
     ctx->collect();
-    ctx->release(d_dst);
+    ctx->release(d_dst_rows);
     ctx->release(d_ol);
     size_t off = 32;
     const uint64_t counts[4] = {RV_ONLINE_REPS, RV_PREPROCESSING_REPS, RV_ONLINE_REPS, RV_PREPROCESSING_REPS};
@@ -1762,6 +1838,7 @@ static int stream_verify_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wi
     bool ok = true;
     auto up = [&](void* dst, const void* from, size_t n) { ok = ok && hipMemcpyAsync(dst, from, n, hipMemcpyHostToDevice, st) == hipSuccess; };
     up(S->d_vproof, proof, proof_len);
+    stream_traffic(3, proof_len);
     up(S->d_omit_v, H.omit.data(), R);
     up(S->d_omit64_v, H.omit64.data(), R);
     up(S->d_hco, H.hco.data(), H.hco.size());
@@ -1823,6 +1900,15 @@ static int stream_verify_finish_impl(rv_stream* S, uint32_t flags, int* ok) {
     ctx->collect();
     ctx->prof.calls++;
     S->tot = S->run;
+    if (S->proof_in_place) {  // verify_device_impl's end: rv_verify_finish_impl's decision from comm and the omit bytes the walk brought
+        uint8_t omit[RV_TOTAL_REPS];
+        *ok = digests_give_comm(S->dev_comm, digests, omit);
+        if (verify_is_strict(flags)) {
+            if (S->dev_flags & RV_DEV_ZERO_CHECK) *ok = 0;
+            if (!records_omit_challenge(omit, S->dev_rec_omit, S->dev_rec_omit + RV_ONLINE_REPS)) *ok = 0;
+        }
+        return RV_OK;
+    }
     return rv_verify_finish_impl(S->h_proof, S->proof_len, digests, flags, !(S->dev_flags & RV_DEV_ZERO_CHECK), ok);
 }
 

@@ -24,7 +24,13 @@ the device compiler, and only one with an error in it comes back to the host com
 Wherever an op list is taken -- every `feed`, every one-shot function -- it may also be a torch tensor in GPU memory holding packed
 rv_op records (what `Circuit.from_device_ops` accepts; on the context's device, or it is an error).  The ops are then fed from where
 they are (rv_stream_feed_device / rv_eval_stream_feed_device): with `device_compile` an all-GF(2) piece never reaches the host, and a
-piece the host compiler has to read is copied down alone.  Witnesses stay host arrays.  Results are the same bytes.
+piece the host compiler has to read is copied down alone.  Results are the same bytes.
+
+Wherever a witness is taken it may be a pair of torch tensors in GPU memory (`proof._device_witness`: uint8 / bool [n] or [B][n],
+int64 / uint64 [m] or [B][m], rows may be strided): the stream reads them where they lie (rv_stream_feed_wdev /
+rv_eval_stream_feed_wdev), with host or device ops alike.  `finish(device=True)` (one-shot: `device_proof=True`) leaves the proof in a
+torch uint8 GPU tensor and returns a `DeviceProof`; the verifiers take a `DeviceProof` or a uint8 GPU tensor wherever they take proof
+bytes and read it in place (rv_stream_verify_begin_device).  Proofs, answers and values are the same bytes either way.
 """
 from __future__ import annotations
 
@@ -36,7 +42,7 @@ import numpy as np
 
 from . import _lib
 from .ops import OP_DTYPE, TOTAL_REPS, program
-from .proof import Context, Evaluation, Proof, _device_ops, _is_device_ops, _ptr
+from .proof import Context, DeviceProof, Evaluation, Proof, _device_bytes, _device_ops, _device_witness, _is_device_ops, _ptr
 
 
 def _ops_ctx(ops, ctx: Optional[Context]) -> Context:
@@ -52,6 +58,54 @@ def _feed(handle, ctx: Context, ops, g, n_g: int, z, n_z: int, entry: str = "rv_
         return
     ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
     _lib.check(getattr(_lib.lib(), entry)(handle, _ptr(ops), C.c_size_t(len(ops)), _ptr(g), C.c_size_t(n_g), _ptr(z), C.c_size_t(n_z)))
+
+
+def _wdev(wit_gf2, wit_z64, ctx: Optional[Context], what: str, batched: bool):
+    """The witnesses of a feed when they are torch GPU tensors: `_device_witness`'s (descriptor, batch, tensors, context), or None for
+    host witnesses.  A torch tensor in host memory, and a pair that is half host and half device, is a TypeError -- raised before any
+    context is made (ctx None: the default one)."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    if torch is not None:
+        for t in (wit_gf2, wit_z64):
+            if isinstance(t, torch.Tensor) and t.device.type != "cuda":
+                raise TypeError(f"{what}: a witness tensor must be in GPU memory (pass host witnesses as arrays or sequences)")
+    return _device_witness(wit_gf2, wit_z64, ctx, what, batched)
+
+
+def _rows_batched(wit_gf2, wit_z64, batch: int) -> bool:
+    """a batch of one may pass its witness as [n]"""
+    return not (batch == 1 and all(getattr(t, "ndim", 2) == 1 for t in (wit_gf2, wit_z64) if hasattr(t, "data_ptr")))
+
+
+def _feed_wdev(handle, ctx: Context, ops, dw, entry: str = "rv_stream_feed"):
+    """one feed with witnesses in GPU memory (`dw` from `_wdev`); the ops from the host or from a torch GPU tensor"""
+    if _is_device_ops(ops):
+        d_ops, n_ops, _ = _device_ops(ops, ctx, "a feed of device ops")
+        ptr, on_device = C.c_void_p(d_ops), 1
+    else:
+        ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+        ptr, n_ops, on_device = _ptr(ops), len(ops), 0
+    _lib.check(getattr(_lib.lib(), entry + "_wdev")(handle, ptr, C.c_size_t(n_ops), C.c_int(on_device), C.byref(dw[0])))
+
+
+def _device_proof_bytes(proof, ctx: Optional[Context], what: str):
+    """(pointer, length, the object to keep alive) of a proof in GPU memory -- a bincode-form DeviceProof or a uint8 GPU tensor -- or
+    None for host bytes"""
+    import sys
+
+    torch = sys.modules.get("torch")
+    if isinstance(proof, DeviceProof):
+        if proof.lens is not None:
+            raise TypeError(f"{what} takes bincode-form proofs; a sections-form DeviceProof verifies on its own")
+        if ctx is not None and ctx.device != proof.ctx.device:
+            raise ValueError(f"the proof is on device {proof.ctx.device}, the context on device {ctx.device}")
+        return proof._ptr, proof._len, proof
+    if torch is not None and isinstance(proof, torch.Tensor):
+        ptr, n, _ = _device_bytes(proof, ctx, what)
+        return ptr, n, proof
+    return None
 
 
 def _check_device_z64(device_compile: bool, device_z64: bool, device_b2a: bool = False):
@@ -109,6 +163,9 @@ class StreamingProver:
         _set_device_compile(self.handle, device_compile, device_z64, device_b2a)
 
     def feed(self, ops, wit_gf2: Sequence[int] = (), wit_z64: Sequence[int] = ()):
+        dw = _wdev(wit_gf2, wit_z64, getattr(self, "ctx", None), "StreamingProver.feed", batched=False)
+        if dw is not None:
+            return _feed_wdev(self.handle, self.ctx, ops, dw)
         g = np.ascontiguousarray(np.asarray(wit_gf2, dtype=np.uint8))
         z = np.ascontiguousarray(np.asarray(wit_z64, dtype=np.uint64))
         _feed(self.handle, self.ctx, ops, g, len(g), z, len(z))
@@ -123,7 +180,16 @@ class StreamingProver:
         _lib.check(_lib.lib().rv_stream_commit(self.handle, _ptr(comm)))
         return comm.tobytes()
 
-    def finish(self) -> Proof:
+    def finish(self, device: bool = False) -> "Proof | DeviceProof":
+        """the proof; device=True: left in a torch uint8 GPU tensor (rv_stream_finish_device), as a DeviceProof -- the same bytes"""
+        if device:
+            import torch
+
+            want = self.info["proof_bytes"]
+            out = torch.empty(want, dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
+            n = C.c_size_t()
+            _lib.check(_lib.lib().rv_stream_finish_device(self.handle, C.c_void_p(out.data_ptr()), C.c_size_t(want), C.byref(n)))
+            return DeviceProof(out[:n.value], ctx=self.ctx)
         out, n = C.c_void_p(), C.c_size_t()
         _lib.check(_lib.lib().rv_stream_finish(self.handle, C.byref(out), C.byref(n)))
         return Proof(_owned=(C.c_void_p(out.value), n.value))
@@ -148,19 +214,21 @@ class StreamingProver:
 
 
 def prove_streaming(ops, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
-                    ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False) -> Tuple[Proof, dict]:
-    """rv_prove_streaming: both passes over an op array in host memory -> (Proof, stream info).  A torch GPU tensor of ops: the same
-    through rv_stream_begin / rv_stream_feed_device / rv_stream_finish."""
+                    ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
+                    device_proof: bool = False) -> Tuple[Proof, dict]:
+    """rv_prove_streaming: both passes over an op array in host memory -> (Proof, stream info).  A torch GPU tensor of ops, witnesses
+    that are torch GPU tensors or device_proof=True (-> a DeviceProof): the same through rv_stream_begin / the feeds / the finish."""
     _check_device_z64(device_compile, device_z64, device_b2a)
+    on_device = _wdev(wit_gf2, wit_z64, ctx, "prove_streaming", batched=False) is not None  # (refuses before a context is made)
     ctx = _ops_ctx(ops, ctx)
-    if _is_device_ops(ops):
+    if _is_device_ops(ops) or on_device or device_proof:
         sp = StreamingProver(wire_counts, seeds, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
-            sp.same_cuts()  # (the same tensor, cut by the same rule in both passes)
+            sp.same_cuts()  # (the same ops, cut by the same rule in both passes)
             sp.feed(ops, wit_gf2, wit_z64)
             sp.commit()
             sp.feed(ops, wit_gf2, wit_z64)
-            return sp.finish(), sp.info
+            return sp.finish(device=device_proof), sp.info
         finally:
             sp.close()
     ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
@@ -189,8 +257,15 @@ class StreamingVerifier:
     def __init__(self, wire_counts: Tuple[int, int], proof, max_chunk_ops: int = 0, ctx: Optional[Context] = None,
                  device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False):
         _check_device_z64(device_compile, device_z64, device_b2a)
-        self.ctx = ctx or Context.default()
         self.handle = C.c_void_p()
+        dev = _device_proof_bytes(proof, ctx, "StreamingVerifier")
+        self.ctx = ctx or (proof.ctx if isinstance(proof, DeviceProof) else Context.default())
+        if dev is not None:  # read in place: the tensor is kept alive for the stream's life
+            self._proof = dev[2]
+            _lib.check(_lib.lib().rv_stream_verify_begin_device(self.ctx.handle, C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])),
+                                                                C.c_void_p(dev[0]), C.c_size_t(dev[1]), C.c_size_t(max_chunk_ops), C.byref(self.handle)))
+            _set_device_compile(self.handle, device_compile, device_z64, device_b2a)
+            return
         self._proof = proof if isinstance(proof, Proof) else Proof(bytes(proof))  # (kept alive: the stream reads it until finish)
         buf, n = self._proof._buffer()
         _lib.check(_lib.lib().rv_stream_verify_begin(self.ctx.handle, C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])), buf,
@@ -220,8 +295,11 @@ def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = Tr
     """rv_verify_streaming: one pass over an op array in host memory -> (ok, stream info).  A torch GPU tensor of ops: the same through
     rv_stream_verify_begin / rv_stream_feed_device / rv_stream_verify_finish."""
     _check_device_z64(device_compile, device_z64, device_b2a)
+    on_device = _device_proof_bytes(proof, ctx, "verify_streaming") is not None
+    if on_device and ctx is None and isinstance(proof, DeviceProof):
+        ctx = proof.ctx
     ctx = _ops_ctx(ops, ctx)
-    if _is_device_ops(ops):
+    if _is_device_ops(ops) or on_device:
         sv = StreamingVerifier(wire_counts, proof, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
             sv.feed(ops)
@@ -289,6 +367,11 @@ class StreamingBatchProver:
         _set_device_compile(self.handle, device_compile, device_z64, device_b2a)
 
     def feed(self, ops, wits_gf2=(), wits_z64=()):
+        dw = _wdev(wits_gf2, wits_z64, getattr(self, "ctx", None), "StreamingBatchProver.feed", batched=_rows_batched(wits_gf2, wits_z64, self.batch))
+        if dw is not None:
+            if dw[1] != self.batch:
+                raise ValueError(f"witnesses must be [batch={self.batch}][n]")
+            return _feed_wdev(self.handle, self.ctx, ops, dw)
         g = _eval_wits(wits_gf2, self.batch, np.uint8)
         z = _eval_wits(wits_z64, self.batch, np.uint64)
         _feed(self.handle, self.ctx, ops, g, g.shape[1], z, z.shape[1])
@@ -300,7 +383,25 @@ class StreamingBatchProver:
         _lib.check(_lib.lib().rv_stream_commit_batch(self.handle, _ptr(comms)))
         return [comms[b].tobytes() for b in range(self.batch)]
 
-    def finish(self) -> "list[Proof]":
+    def finish(self, device: bool = False) -> "list[Proof] | list[DeviceProof]":
+        """the proofs; device=True: DeviceProof views of ONE torch uint8 GPU tensor (rv_stream_finish_batch_device; proof b at
+        b * stride, stride = the proof length rounded up to 256), the same bytes"""
+        if device:
+            import torch
+
+            want = self.info["proof_bytes"] // self.batch
+            stride = (want + 255) & ~255
+            out = torch.empty(self.batch * stride, dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
+            n = C.c_size_t()
+            _lib.check(_lib.lib().rv_stream_finish_batch_device(self.handle, C.c_void_p(out.data_ptr()), C.c_size_t(stride), C.byref(n)))
+            proofs = []
+            for b in range(self.batch):  # (the call has waited for its stream)
+                dp = DeviceProof.__new__(DeviceProof)
+                dp.lens, dp._comm, dp.ctx = None, None, self.ctx
+                dp.tensor = out[b * stride:b * stride + n.value]
+                dp._ptr, dp._len = out.data_ptr() + b * stride, n.value
+                proofs.append(dp)
+            return proofs
         outs = (C.c_void_p * self.batch)()
         lens = (C.c_size_t * self.batch)()
         _lib.check(_lib.lib().rv_stream_finish_batch(self.handle, outs, lens))
@@ -317,27 +418,33 @@ class StreamingBatchProver:
 
 
 def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
-                          ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False) -> "list[Proof]":
+                          ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
+                          device_proof: bool = False) -> "list[Proof]":
     """rv_prove_streaming_batch: both passes over an op array in host memory for the witnesses wits_gf2 [B][n] / wits_z64
-    [B][m] (B from whichever of the two is 2-D; the other may be []); seeds [B][256][16] or None.  `info` (a dict, optional) receives the stream's figures."""
+    [B][m] (B from whichever of the two is 2-D; the other may be []); seeds [B][256][16] or None.  `info` (a dict, optional) receives the stream's figures.
+    Witnesses that are torch GPU tensors are read where they lie; device_proof=True returns DeviceProof views of one GPU tensor."""
     _check_device_z64(device_compile, device_z64, device_b2a)
+    dw = _wdev(wits_gf2, wits_z64, ctx, "prove_streaming_batch", batched=True)  # (refuses before a context is made)
     ctx = _ops_ctx(ops, ctx)
-    g0 = np.asarray(wits_gf2, dtype=np.uint8)
-    z0 = np.asarray(wits_z64, dtype=np.uint64)
-    if g0.ndim == 2:  # (the batch is the first dimension of whichever witness array is 2-D: [] for the other domain)
-        batch = g0.shape[0]
-    elif z0.ndim == 2:
-        batch = z0.shape[0]
+    if dw is not None:  # (GPU tensors: [B][n] both, the batch from the descriptor)
+        g0, z0, batch = wits_gf2, wits_z64, dw[1]
     else:
-        raise ValueError("wits_gf2 or wits_z64 must be [batch][n]")
-    if _is_device_ops(ops):  # (a torch GPU tensor: begin / rv_stream_feed_device twice / finish)
+        g0 = np.asarray(wits_gf2, dtype=np.uint8)
+        z0 = np.asarray(wits_z64, dtype=np.uint64)
+        if g0.ndim == 2:  # (the batch is the first dimension of whichever witness array is 2-D: [] for the other domain)
+            batch = g0.shape[0]
+        elif z0.ndim == 2:
+            batch = z0.shape[0]
+        else:
+            raise ValueError("wits_gf2 or wits_z64 must be [batch][n]")
+    if _is_device_ops(ops) or dw is not None or device_proof:  # (begin / the feeds twice / finish)
         sp = StreamingBatchProver(wire_counts, batch, seeds, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
             sp.same_cuts()
             sp.feed(ops, g0, z0)
             sp.commit()
             sp.feed(ops, g0, z0)
-            proofs = sp.finish()
+            proofs = sp.finish(device=device_proof)
             if info is not None:
                 info.update(sp.info)
             return proofs
@@ -374,6 +481,17 @@ class StreamingBatchVerifier:
         self.batch = len(proofs)
         if self.batch < 1:
             raise ValueError("no proofs")
+        dev = [_device_proof_bytes(p, ctx, "StreamingBatchVerifier") for p in proofs]
+        if any(d is not None for d in dev):  # proofs in GPU memory, read in place: kept alive for the stream's life
+            if any(d is None for d in dev):
+                raise TypeError("StreamingBatchVerifier takes proofs that are all in GPU memory or all on the host")
+            self._keep = [d[2] for d in dev]
+            ptrs = (C.c_void_p * self.batch)(*[d[0] for d in dev])
+            lens = (C.c_size_t * self.batch)(*[d[1] for d in dev])
+            _lib.check(_lib.lib().rv_stream_verify_begin_batch_device(self.ctx.handle, int(wire_counts[0]), int(wire_counts[1]), self.batch, ptrs, lens,
+                                                                      int(max_chunk_ops), C.byref(self.handle)))
+            _set_device_compile(self.handle, device_compile, device_z64, device_b2a)
+            return
         self._keep, ptrs, lens = _proof_array(proofs)  # (kept alive: the stream reads them until finish)
         _lib.check(_lib.lib().rv_stream_verify_begin_batch(self.ctx.handle, int(wire_counts[0]), int(wire_counts[1]), self.batch, ptrs, lens,
                                                            int(max_chunk_ops), C.byref(self.handle)))
@@ -404,7 +522,8 @@ def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bo
     n = len(proofs)
     if n == 0:
         return []
-    if _is_device_ops(ops):  # (a torch GPU tensor: begin / rv_stream_feed_device / finish)
+    on_device = any(_device_proof_bytes(p, ctx, "verify_streaming_batch") is not None for p in proofs)
+    if _is_device_ops(ops) or on_device:  # (begin / one feed / finish)
         sv = StreamingBatchVerifier(wire_counts, proofs, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
             sv.feed(ops)
@@ -465,6 +584,11 @@ class StreamingEvaluator:
         _set_device_compile(self.handle, device_compile, device_z64, device_b2a, "rv_eval_stream_set_compile_flags")
 
     def feed(self, ops, wits_gf2=(), wits_z64=()):
+        dw = _wdev(wits_gf2, wits_z64, getattr(self, "ctx", None), "StreamingEvaluator.feed", batched=_rows_batched(wits_gf2, wits_z64, self.batch))
+        if dw is not None:
+            if dw[1] != self.batch:
+                raise ValueError(f"witnesses must be [batch={self.batch}][n] (1-D for batch 1)")
+            return _feed_wdev(self.handle, self.ctx, ops, dw, "rv_eval_stream_feed")
         g = _eval_wits(wits_gf2, self.batch, np.uint8)
         z = _eval_wits(wits_z64, self.batch, np.uint64)
         _feed(self.handle, self.ctx, ops, g, g.shape[1], z, z.shape[1], "rv_eval_stream_feed")
@@ -501,10 +625,15 @@ def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], ma
     wits_z64: [B][n] (1-D for one witness; the batch is len(wits_gf2)).  Returns the array-shaped Evaluation of
     Circuit.evaluate_batch; `info` (a dict, optional) receives the stream's figures."""
     _check_device_z64(device_compile, device_z64, device_b2a)
+    dims = [t.dim() for t in (wits_gf2, wits_z64) if hasattr(t, "data_ptr")]
+    dw = _wdev(wits_gf2, wits_z64, ctx, "evaluate_streaming", batched=bool(dims) and max(dims) == 2)  # (refuses before a context is made)
     ctx = _ops_ctx(ops, ctx)
-    g0 = np.asarray(wits_gf2, dtype=np.uint8)
-    batch = g0.shape[0] if g0.ndim == 2 else 1
-    if _is_device_ops(ops):  # (a torch GPU tensor: begin / rv_eval_stream_feed_device / finish)
+    if dw is not None:
+        g0, batch = wits_gf2, dw[1]
+    else:
+        g0 = np.asarray(wits_gf2, dtype=np.uint8)
+        batch = g0.shape[0] if g0.ndim == 2 else 1
+    if _is_device_ops(ops) or dw is not None:  # (begin / one feed / finish)
         se = StreamingEvaluator(wire_counts, batch, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
             se.feed(ops, g0, wits_z64)

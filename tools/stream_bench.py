@@ -6,6 +6,10 @@
     python tools/stream_bench.py --compare [--runs 5]         # config 4, host and device compiler side by side, one JSON line per row
     python tools/stream_bench.py --compiler device --ops device [--runs 5]   # config 4 fed from a GPU tensor (rv_stream_feed_device) beside
                                                               # the same calls fed from host memory, one JSON line per entry point
+    python tools/stream_bench.py --witness device --proof device [--ops device --compiler device] [--runs 5]   # config 4 with the witness
+                                                              # in a GPU tensor and / or the proof left in one (rv_stream_feed_wdev,
+                                                              # rv_stream_finish_device, rv_stream_verify_begin_device) beside the default
+                                                              # host cell, one JSON line per entry point
 bench.py imports streaming_record() for its `streaming` record.  RV_STREAM_STATS=1 prints the feeds' laps; with the device compiler they
 name the op upload, the device compile and the host copy of the pieces."""
 import os
@@ -175,6 +179,58 @@ def device_ops_rows(ctx, seeds, want: bytes, runs: int = 5, chunk_ops: int = 1 <
         yield rec
 
 
+def device_memory_rows(ctx, seeds, want: bytes, ops="host", witness="host", proof="host", runs: int = 5, chunk_ops: int = 1 << 18, layers: int = 153):
+    """config 4 (recycled wire indices) through prove_streaming with the ops, the witness and the proof each in host memory or in GPU
+    memory (tensors uploaded once, outside the timed region), beside the all-host cell, at the context's compile flags; then
+    verify_streaming on host proof bytes and -- proof == "device" -- on a DeviceProof.  One record per entry point, with the witness
+    and proof bytes each call moved (rv_hook_stream_traffic)."""
+    import ctypes as C
+
+    import torch
+
+    import circuits
+    from reverie_amd import _lib
+    from reverie_amd.stream import prove_streaming, verify_streaming
+
+    prog, wit, wc, st = circuits.layered_gf2(layers=layers, recycle=True)
+    wit = np.asarray(wit, np.uint8)
+    dev = f"cuda:{ctx.device}"
+    d_prog = torch.from_numpy(prog.view(np.uint8).reshape(-1, prog.dtype.itemsize)).to(dev) if ops == "device" else None
+    d_wit, d_w64 = torch.from_numpy(wit).to(dev), torch.zeros(0, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+
+    def traffic():
+        out = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().rv_hook_stream_traffic(out))
+        return np.array([int(x) for x in out])
+
+    def host_bytes(p):
+        return bytes(p) if proof == "host" else p.tensor.cpu().numpy().tobytes()
+
+    cell = {"ops": ops, "witness": witness, "proof": proof}
+    rec = {"row": "prove_streaming", "n_ops": int(len(prog)), "chunk_ops": chunk_ops, "compile_flags": int(getattr(ctx, "compile_flags", 0)), "cell": cell}
+    before = traffic()
+    t, out = _timed(lambda: prove_streaming(prog, wit, [], wc, seeds=seeds, max_chunk_ops=chunk_ops, ctx=ctx), runs)
+    rec["host_cell"] = dict(t, ok=bytes(out[0]) == want, witness_h2d_dev_proof_d2h_h2d_per_call=[int(x) for x in (traffic() - before) // (runs + 1)])
+    before = traffic()
+    t, out = _timed(lambda: prove_streaming(d_prog if ops == "device" else prog, d_wit if witness == "device" else wit, d_w64 if witness == "device" else [],
+                                            wc, seeds=seeds, max_chunk_ops=chunk_ops, ctx=ctx, device_proof=proof == "device"), runs)
+    rec["this_cell"] = dict(t, ok=host_bytes(out[0]) == want, witness_h2d_dev_proof_d2h_h2d_per_call=[int(x) for x in (traffic() - before) // (runs + 1)])
+    rec["this_over_host"] = rec["this_cell"]["ms"] / rec["host_cell"]["ms"]
+    yield rec
+    made = out[0]
+    rec = {"row": "verify_streaming", "n_ops": int(len(prog)), "chunk_ops": chunk_ops, "cell": cell}
+    before = traffic()
+    t, vout = _timed(lambda: verify_streaming(prog, wc, want, max_chunk_ops=chunk_ops, ctx=ctx), runs)
+    rec["host_cell"] = dict(t, ok=bool(vout[0]), witness_h2d_dev_proof_d2h_h2d_per_call=[int(x) for x in (traffic() - before) // (runs + 1)])
+    if proof == "device":
+        before = traffic()
+        t, vout = _timed(lambda: verify_streaming(d_prog if ops == "device" else prog, wc, made, max_chunk_ops=chunk_ops, ctx=ctx), runs)
+        rec["this_cell"] = dict(t, ok=bool(vout[0]), witness_h2d_dev_proof_d2h_h2d_per_call=[int(x) for x in (traffic() - before) // (runs + 1)])
+        rec["this_over_host"] = rec["this_cell"]["ms"] / rec["host_cell"]["ms"]
+    yield rec
+
+
 def z64_compiler_rows(ctx, seeds, runs=5, n_mul=1_000_000, chunk_ops=1 << 16):
     """config 5 through prove_streaming at the context's compile flags, with the default worker threads and with RV_STREAM_THREADS=1:
     medians of `runs` calls after a warm-up, the pieces the device compiler took per call, the proof against rv_prove's"""
@@ -271,6 +327,11 @@ if __name__ == "__main__":
     ap.add_argument("--compare", action="store_true", help="config 4 with both compilers, every streaming entry point")
     ap.add_argument("--ops", default="host", choices=["host", "device"],
                     help="device: config 4 fed from a GPU tensor beside the host-fed calls (prover, verifier, evaluator), one JSON line each")
+    ap.add_argument("--witness", default="host", choices=["host", "device"],
+                    help="device: config 4 with the witness read from a GPU tensor (rv_stream_feed_wdev) beside the all-host cell")
+    ap.add_argument("--proof", default="host", choices=["host", "device"],
+                    help="device: config 4 with the proof left in a GPU tensor (rv_stream_finish_device) and verified there "
+                         "(rv_stream_verify_begin_device) beside the all-host cell; combines with --witness and --ops")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--bench-record", action="store_true")
     args = ap.parse_args()
@@ -294,6 +355,10 @@ if __name__ == "__main__":
     circ = reverie_amd.Circuit(prog, wc, ctx)
     want = bytes(reverie_amd.Proof.new(circ, wit, [], seeds=seeds))
     circ.close()
+    if args.witness == "device" or args.proof == "device":
+        for rec in device_memory_rows(ctx, seeds, want, ops=args.ops, witness=args.witness, proof=args.proof, runs=args.runs, layers=layers):
+            print(json.dumps(rec), flush=True)
+        sys.exit(0)
     if args.ops == "device":
         for rec in device_ops_rows(ctx, seeds, want, runs=args.runs, layers=layers):
             print(json.dumps(rec), flush=True)
