@@ -901,6 +901,23 @@ int rv_hook_unpack64(rv_ctx *ctx, const uint8_t *blob, uint64_t blob_bytes, cons
  * on its own with the ShareGen phases predicted from the ops before it adds up to the whole (RV_E_DEVICE if not). */
 int rv_hook_compile_info(const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, size_t chunk_ops,
                          rv_circuit_info *info);
+/* The level table of the gate stream and the plan that assigns its levels to executors (host only, no device; the compile of
+ * rv_hook_compile_info).  out: ten int32 per level, the first `cap` levels -- the class bounds lo, mul11, mul, xor2, xork, hi of the
+ * level's gates (csrc/internal.h: LevelRange; one-base Mul, other Mul, two-base XorK, other XorK, everything else), 1 when the level
+ * holds Z64 gates, the index of the narrow run the level belongs to and that run's kind (1 per-gate, 0 class-loop, 2 lean; -1 and -1
+ * when the level is launched on its own), -1.  *n_levels: the levels there are.  The plan is computed by the function the upload
+ * path calls. */
+int rv_hook_compile_levels(const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, int32_t *out, size_t cap,
+                           size_t *n_levels);
+/* The same table of a compiled circuit; its tenth column is the index of the LDS run that holds the level (-1: none), planned for the
+ * LDS size of the circuit's context.  *vclr_ok (nullable): the circuit qualifies for MODE_PROVE_V; *general_levels (nullable): some
+ * level takes the kernel variant with the multi-base loops, which rules MODE_VERIFY_C out. */
+int rv_hook_circuit_levels(const rv_circuit *c, int32_t *out, size_t cap, size_t *n_levels, int *vclr_ok, int *general_levels);
+/* Launches of the GF(2) level executors this process has issued so far (relaxed atomic counters, bumped by the host launchers), eleven
+ * rows of four: rows = own launch fast, own launch general, generic k_interp, narrow per-gate, narrow class-loop, narrow lean, LDS run,
+ * batched full, batched narrow per-gate, batched narrow class-loop, batched LDS; columns = the kernel's mode PROVE, PROVE_V, VERIFY,
+ * VERIFY_C.  reset != 0: the counters return to zero as they are read. */
+int rv_hook_interp_launches(uint64_t counts[][4], int reset);
 /* The two gate-stream compilers against each other (host only): the program is compiled by the sequential compiler and by the
  * parallel one with `threads` host threads (>= 2), whatever its size, and the results are compared field by field.
  * *diff = 0: identical; > 0: a number naming the first differing table (csrc/compile_par.cpp, compiled_diff); -1: the parallel

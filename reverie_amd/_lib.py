@@ -106,6 +106,7 @@ SYMBOLS = [
     "rv_stream_verify_begin_device", "rv_stream_verify_begin_batch_device",
     "rv_hook_stream_traffic", "rv_hook_stream_verify_device_paths", "rv_hook_stream_wit_sums",
     "rv_hook_extract_bits", "rv_hook_extract_from_bits", "rv_hook_pack_corr_all", "rv_hook_unpack_bits", "rv_hook_extract64", "rv_hook_unpack64",
+    "rv_hook_compile_levels", "rv_hook_circuit_levels", "rv_hook_interp_launches",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -177,6 +178,10 @@ ARGTYPES = {
     "rv_hook_unpack_bits": [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint64, _P],
     "rv_hook_extract64": [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_int, C.c_uint32, _P, _P, C.c_int, C.c_uint32, _P, C.c_uint64],
     "rv_hook_unpack64": [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P],
+    # which executor runs which level (level table + run plan, launch counters)
+    "rv_hook_compile_levels": [_P, _Z, _Z, _Z, C.c_uint32, _P, _Z, C.POINTER(C.c_size_t)],
+    "rv_hook_circuit_levels": [_P, _P, _Z, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "rv_hook_interp_launches": [_P, C.c_int],
 }
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1

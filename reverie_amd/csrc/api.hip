@@ -1007,6 +1007,62 @@ static int rv_circuit_compile_impl(rv_ctx* ctx, const rv_op* ops, size_t n_ops, 
     return RV_OK;
 }
 
+// The narrow-run plan of a compiled gate stream, a function of the stream alone (circuit_upload keeps it in the circuit, rv_hook_compile_levels
+// reports it): maximal stretches of at least 3 consecutive GF(2)-only levels of at most NARROW gates, cut into pieces by level width
+static uint32_t narrow_level_limit() {
+    // gates; one 1024-thread workgroup covers 64 full-width gates per (4-way unrolled) step
+    static const uint32_t NARROW = std::min<uint32_t>(getenv("RV_NARROW") ? (uint32_t)atoi(getenv("RV_NARROW")) : 256, 512);  // <= NARROW_WIN / 2
+    return NARROW;
+}
+static void plan_narrow_runs(const Compiled& cc, std::vector<rv_circuit::NarrowRun>& narrow_runs, std::vector<int32_t>& run_of_level) {
+    const size_t n_levels = cc.level_start.empty() ? 0 : cc.level_start.size() - 1;
+    narrow_runs.clear();
+    run_of_level.assign(n_levels, -1);
+    const uint32_t NARROW = narrow_level_limit();
+    size_t l = 0;
+    while (l < n_levels) {
+        auto narrow = [&](size_t i) {
+            const bool no64 = cc.level_start64.empty() || cc.level_start64[i + 1] == cc.level_start64[i];
+            return no64 && cc.level_start[i + 1] - cc.level_start[i] <= NARROW;
+        };
+        if (!narrow(l)) {
+            l++;
+            continue;
+        }
+        size_t e = l;
+        while (e < n_levels && narrow(e)) e++;
+        if (e - l >= 3) {
+            // split the run: stretches of >= 8 levels that are all wider than 32 gates go to the class-loop kernel
+            // (4 gates per wavefront step, ~2 us per 64 gates), everything else to the per-gate kernel (one gate
+            // per wavefront, 1.2 us per 16 gates; measured on SHA-256 / AES-128)
+            auto wide = [&](size_t i) { return cc.level_start[i + 1] - cc.level_start[i] > 32; };
+            size_t a = l;
+            while (a < e) {
+                size_t b = a;
+                const bool w = wide(a);
+                while (b < e && wide(b) == w) b++;
+                int tiny = (w && b - a >= 8) ? 0 : 1;
+                if (!tiny) {  // a class-loop stretch without multi-base gates takes the lean variant (8-gate Xor steps)
+                    bool lean = true;
+                    for (size_t i = a; i < b; i++) {
+                        const LevelRange& lr = cc.level_range[i];
+                        lean = lean && lr.mul == lr.mul11 && lr.xork == lr.xor2;
+                    }
+                    if (lean) tiny = 2;
+                }
+                if (tiny == 1 && a > l && !narrow_runs.empty() && narrow_runs.back().second == a && narrow_runs.back().tiny == 1) {
+                    narrow_runs.back().second = (uint32_t)b;  // merge with the preceding per-gate piece
+                } else {
+                    narrow_runs.push_back(rv_circuit::NarrowRun{(uint32_t)a, (uint32_t)b, tiny});
+                }
+                for (size_t i = a; i < b; i++) run_of_level[i] = (int32_t)narrow_runs.size() - 1;
+                a = b;
+            }
+        }
+        l = e;
+    }
+}
+
 // The arrays circuit_upload sends first, in its order, each rounded up to 256 bytes: their size, and a copy of them into `dst`
 // (page-locked; any thread, no HIP call) that circuit_upload then sends from instead of going through the context's staging buffer
 template <class F>
@@ -1118,61 +1174,14 @@ static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged) {
     c->staged = nullptr;  // (the slot belongs to the next piece from here on)
     c->staged_bytes = 0;
     c->cc.info.upload_us = (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_compiled).count();
-    {
-        const size_t n_levels = cc.level_start.empty() ? 0 : cc.level_start.size() - 1;
-        c->run_of_level.assign(n_levels, -1);
-        // gates; one 1024-thread workgroup covers 64 full-width gates per (4-way unrolled) step
-        static const uint32_t NARROW = std::min<uint32_t>(getenv("RV_NARROW") ? (uint32_t)atoi(getenv("RV_NARROW")) : 256, 512);  // <= NARROW_WIN / 2
-        size_t l = 0;
-        while (l < n_levels) {
-            auto narrow = [&](size_t i) {
-                const bool no64 = cc.level_start64.empty() || cc.level_start64[i + 1] == cc.level_start64[i];
-                return no64 && cc.level_start[i + 1] - cc.level_start[i] <= NARROW;
-            };
-            if (!narrow(l)) {
-                l++;
-                continue;
-            }
-            size_t e = l;
-            while (e < n_levels && narrow(e)) e++;
-            if (e - l >= 3) {
-                // split the run: stretches of >= 8 levels that are all wider than 32 gates go to the class-loop kernel
-                // (4 gates per wavefront step, ~2 us per 64 gates), everything else to the per-gate kernel (one gate
-                // per wavefront, 1.2 us per 16 gates; measured on SHA-256 / AES-128)
-                auto wide = [&](size_t i) { return cc.level_start[i + 1] - cc.level_start[i] > 32; };
-                size_t a = l;
-                while (a < e) {
-                    size_t b = a;
-                    const bool w = wide(a);
-                    while (b < e && wide(b) == w) b++;
-                    int tiny = (w && b - a >= 8) ? 0 : 1;
-                    if (!tiny) {  // a class-loop stretch without multi-base gates takes the lean variant (8-gate Xor steps)
-                        bool lean = true;
-                        for (size_t i = a; i < b; i++) {
-                            const LevelRange& lr = cc.level_range[i];
-                            lean = lean && lr.mul == lr.mul11 && lr.xork == lr.xor2;
-                        }
-                        if (lean) tiny = 2;
-                    }
-                    if (tiny == 1 && a > l && !c->narrow_runs.empty() && c->narrow_runs.back().second == a && c->narrow_runs.back().tiny == 1) {
-                        c->narrow_runs.back().second = (uint32_t)b;  // merge with the preceding per-gate piece
-                    } else {
-                        c->narrow_runs.push_back(rv_circuit::NarrowRun{(uint32_t)a, (uint32_t)b, tiny});
-                    }
-                    for (size_t i = a; i < b; i++) c->run_of_level[i] = (int32_t)c->narrow_runs.size() - 1;
-                    a = b;
-                }
-            }
-            l = e;
-        }
-    }
+    plan_narrow_runs(cc, c->narrow_runs, c->run_of_level);
     {
         // LDS runs over the maximal narrow stretches (RV_LDS_RUN=0 switches them off; RV_LDS_QS=2/4 fixes the slice width)
         const size_t n_levels = cc.level_start.empty() ? 0 : cc.level_start.size() - 1;
         c->lds_run_of_level.assign(n_levels, -1);
         const int lds_on = getenv("RV_LDS_RUN") ? atoi(getenv("RV_LDS_RUN")) : 1;  // (read per circuit: the tests switch them)
         const uint32_t qs_env = getenv("RV_LDS_QS") ? (uint32_t)atoi(getenv("RV_LDS_QS")) : 0;
-        static const uint32_t NARROW = std::min<uint32_t>(getenv("RV_NARROW") ? (uint32_t)atoi(getenv("RV_NARROW")) : 256, 512);
+        const uint32_t NARROW = narrow_level_limit();
         bool any = false;
         for (size_t l = 0; l < n_levels && !any; l++) any = c->run_of_level[l] >= 0;
         if (lds_on && any && !cc.row_prg_base) {

@@ -453,3 +453,55 @@ extern "C" int rv_hook_unpack64(rv_ctx* ctx, const uint8_t* blob, uint64_t blob_
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return RV_OK;
 }
+
+// ------------------------------------------------------------------------------------
+// Which executor runs which level (interp.hip, ldsrun.hip): the compiled level table with the narrow-run plan, and the counters of the
+// launches issued.  Ten int32 per level: lo, mul11, mul, xor2, xork, hi (LevelRange), 1 when the level holds Z64 gates, the index of
+// its narrow run and that run's `tiny` (-1, -1: none), the index of its LDS run (-1: none; always -1 without a circuit).
+// ------------------------------------------------------------------------------------
+static void hook_write_levels(const Compiled& cc, const std::vector<rv_circuit::NarrowRun>& runs, const std::vector<int32_t>& run_of_level,
+                              const std::vector<int32_t>* lds_run_of_level, int32_t* out, size_t cap, size_t* n_levels) {
+    const size_t n = cc.level_start.empty() ? 0 : cc.level_start.size() - 1;
+    *n_levels = n;
+    for (size_t l = 0; l < n && l < cap; l++) {
+        const LevelRange& r = cc.level_range[l];
+        int32_t* o = out + 10 * l;
+        o[0] = (int32_t)r.lo, o[1] = (int32_t)r.mul11, o[2] = (int32_t)r.mul, o[3] = (int32_t)r.xor2, o[4] = (int32_t)r.xork, o[5] = (int32_t)r.hi;
+        o[6] = !cc.level_start64.empty() && cc.level_start64[l + 1] > cc.level_start64[l];
+        o[7] = run_of_level[l];
+        o[8] = run_of_level[l] >= 0 ? runs[(size_t)run_of_level[l]].tiny : -1;
+        o[9] = lds_run_of_level ? (*lds_run_of_level)[l] : -1;
+    }
+}
+
+extern "C" int rv_hook_compile_levels(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, int32_t* out, size_t cap,
+                                      size_t* n_levels) {
+    if (!n_levels || (cap && !out) || (n_ops && !ops) || (flags & ~RV_COMPILE_WHOLE_PROVER)) return RV_E_ARG;
+    try {
+        Compiled cc;
+        const int rc = compile_ops(ops, n_ops, z64_wires, gf2_wires, cc, nullptr, ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0);
+        if (rc) return rc;
+        std::vector<rv_circuit::NarrowRun> runs;
+        std::vector<int32_t> run_of_level;
+        plan_narrow_runs(cc, runs, run_of_level);
+        hook_write_levels(cc, runs, run_of_level, nullptr, out, cap, n_levels);
+        return RV_OK;
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}
+
+extern "C" int rv_hook_circuit_levels(const rv_circuit* c, int32_t* out, size_t cap, size_t* n_levels, int* vclr_ok, int* general_levels) {
+    if (!c || !n_levels || (cap && !out)) return RV_E_ARG;
+    hook_write_levels(c->cc, c->narrow_runs, c->run_of_level, &c->lds_run_of_level, out, cap, n_levels);
+    if (vclr_ok) *vclr_ok = c->vclr_ok;
+    if (general_levels) *general_levels = c->general_levels;
+    return RV_OK;
+}
+
+extern "C" int rv_hook_interp_launches(uint64_t counts[][4], int reset) {
+    if (!counts) return RV_E_ARG;
+    interp_launch_counts(counts, reset != 0);
+    return RV_OK;
+}

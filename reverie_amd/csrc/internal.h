@@ -226,6 +226,25 @@ struct LevelRange {
 // some level has enough multi-base Mul / Xor gates for the kernel variant with their loops (interp.hip: level_is_general);
 // launch_interp chooses per level, the verifier asks for the whole stream before it takes MODE_VERIFY_C
 bool any_level_general(const LevelRange* lr, size_t n_levels);
+// rv_hook_interp_launches: the launches of the GF(2) level executors this process has issued, counted on the host by the launchers
+// themselves -- one row per executor (the kernel that was launched, not the one the plan asked for: a class-loop piece on a row
+// width without a class-loop instantiation counts as per-gate), one column per Mode in the order PROVE, PROVE_V, VERIFY, VERIFY_C
+enum InterpExec : int {
+    IX_FULL_FAST = 0,   // k_interp_full<.., GENERAL = false>
+    IX_FULL_GENERAL,    // k_interp_full<.., GENERAL = true>
+    IX_GENERIC,         // k_interp (row widths other than 64 / 32 / 16 / 8 quad words)
+    IX_NARROW_GATE,     // k_interp_narrow<.., 0>
+    IX_NARROW_CLASS,    // k_interp_narrow<.., NQ>
+    IX_NARROW_LEAN,     // k_interp_narrow<.., 64, LEAN>
+    IX_LDS,             // k_interp_lds
+    IX_B_FULL,          // k_interp_full_b
+    IX_B_NARROW_GATE,   // k_interp_narrow_b<.., 0>
+    IX_B_NARROW_CLASS,  // k_interp_narrow_b<.., 64>
+    IX_B_LDS,           // k_interp_lds over a batch
+    IX_COUNT
+};
+void count_interp_launch(int exec, int mode);
+void interp_launch_counts(uint64_t out[][4], bool reset);
 // next: the level launched after this one by launch_interp too (nullable) -- the tail of this launch prefetches
 // its first gate records
 void launch_interp(hipStream_t st, int mode, const Gate* d_gates, const LevelRange& r, const InterpParams& p,

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 
 #include "gf2dev.h"
 #include "internal.h"
@@ -24,6 +25,17 @@ namespace rv {
 static size_t g_device_lds_limit = 160 * 1024;
 void set_device_lds_limit(size_t bytes) { g_device_lds_limit = bytes; }
 size_t device_lds_limit() { return g_device_lds_limit; }
+
+static std::atomic<uint64_t> g_interp_launches[IX_COUNT][4];
+void count_interp_launch(int exec, int mode) {
+    const int col = mode == MODE_PROVE ? 0 : mode == MODE_PROVE_V ? 1 : mode == MODE_VERIFY ? 2 : 3;
+    g_interp_launches[exec][col].fetch_add(1, std::memory_order_relaxed);
+}
+void interp_launch_counts(uint64_t out[][4], bool reset) {
+    for (int e = 0; e < IX_COUNT; e++)
+        for (int m = 0; m < 4; m++)
+            out[e][m] = reset ? g_interp_launches[e][m].exchange(0, std::memory_order_relaxed) : g_interp_launches[e][m].load(std::memory_order_relaxed);
+}
 
 
 // XOR of the n listed base rows / their corr bits.  Unused slots hold the zero row, so all
@@ -591,6 +603,7 @@ static PfPlan make_pf_plan(const LevelRange& r, const LevelRange* next) {
 template <int MODE, int NQ>
 static void launch_interp_full_mode(hipStream_t st, dim3 grid, bool general, const Gate* d_gates, const LevelRange& r, const InterpParams& p,
                                     const PfPlan& pf) {
+    count_interp_launch(general ? IX_FULL_GENERAL : IX_FULL_FAST, MODE);
     if (general)
         hipLaunchKernelGGL((k_interp_full<MODE, NQ, true>), grid, dim3(256), 0, st, d_gates, r, p, pf);
     else
@@ -699,6 +712,7 @@ __global__ __launch_bounds__(1024) void k_interp_narrow_b(const Gate* __restrict
 template <int NQT, bool LEAN = false>
 static void launch_narrow_nq(hipStream_t st, int mode, const Gate* d_gates, const LevelRange* d_lr, uint32_t a, uint32_t b,
                              const InterpParams& p) {
+    count_interp_launch(NQT == 0 ? IX_NARROW_GATE : LEAN ? IX_NARROW_LEAN : IX_NARROW_CLASS, mode == MODE_PROVE ? MODE_PROVE : MODE_VERIFY);
     if (mode == MODE_PROVE)
         hipLaunchKernelGGL((k_interp_narrow<MODE_PROVE, NQT, LEAN>), dim3(1), dim3(1024), 0, st, d_gates, d_lr, a, b, p);
     else
@@ -737,6 +751,7 @@ void launch_interp(hipStream_t st, int mode, const Gate* d_gates, const LevelRan
     const uint64_t want = (uint64_t)(r.hi - r.lo) * p.NQ;
     uint64_t blocks = (want + 255) / 256;
     if (blocks > 8192) blocks = 8192;
+    count_interp_launch(IX_GENERIC, mode == MODE_PROVE ? MODE_PROVE : MODE_VERIFY);
     if (mode == MODE_PROVE)
         hipLaunchKernelGGL(k_interp<MODE_PROVE>, dim3((unsigned)blocks), dim3(256), 0, st, d_gates, r.lo, r.hi, p);
     else
@@ -750,6 +765,7 @@ void launch_interp_batched(hipStream_t st, const Gate* d_gates, const LevelRange
     uint64_t blocks = (waves + 3) / 4;
     const uint64_t cap = std::max<uint64_t>(4096 / batch, 1);
     if (blocks > cap) blocks = cap;
+    count_interp_launch(IX_B_FULL, mode == MODE_PROVE ? MODE_PROVE : MODE_VERIFY);
     if (mode == MODE_PROVE)
         hipLaunchKernelGGL((k_interp_full_b<MODE_PROVE, 64>), dim3((unsigned)blocks, batch), dim3(256), 0, st, d_gates, r, d_pp);
     else
@@ -760,6 +776,7 @@ void launch_interp_narrow_batched(hipStream_t st, const Gate* d_gates, const Lev
                                   int tiny, const InterpParams* d_pp, uint32_t batch, int mode) {
     for (uint32_t a = l0; a < l1 && batch; a += NARROW_MAX_LEVELS) {
         const uint32_t b = (a + NARROW_MAX_LEVELS < l1) ? a + NARROW_MAX_LEVELS : l1;
+        count_interp_launch(tiny == 1 ? IX_B_NARROW_GATE : IX_B_NARROW_CLASS, mode == MODE_PROVE ? MODE_PROVE : MODE_VERIFY);
         if (mode == MODE_PROVE) {
             if (tiny == 1)
                 hipLaunchKernelGGL((k_interp_narrow_b<MODE_PROVE, 0>), dim3(batch), dim3(1024), 0, st, d_gates, d_level_range, a, b, d_pp);

@@ -328,6 +328,7 @@ void launch_interp_lds(hipStream_t st, int mode, uint32_t QS, uint32_t NQ, const
                        uint32_t eo0, uint32_t ep0, const InterpParams& p, const InterpParams* d_pp, uint32_t batch) {
     LdsRunParams rp{d_recs, n_steps, n_slots, eo0, ep0};
     const size_t lds = lds_run_bytes(QS, n_slots);
+    count_interp_launch(d_pp ? IX_B_LDS : IX_LDS, mode == MODE_VERIFY ? MODE_VERIFY : MODE_PROVE);
     if (QS == 4) {
         if (mode == MODE_VERIFY)
             launch_lds_mq<MODE_VERIFY, 4>(st, rp, lds, NQ, p, d_pp, batch);
