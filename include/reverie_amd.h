@@ -819,6 +819,45 @@ typedef struct rv_bristol_info {
 int rv_bristol_parse(const char *text, size_t len, int format, const uint8_t *expected_outputs, size_t n_expected, rv_op **ops,
                      size_t *n_ops, rv_bristol_info *info);
 
+/* ---- wire indices compacted by liveness -----------------------------------------
+ * A stream's wire store is sized by the wire counts it begins with: one row per wire index.  An op list in SSA form (a Bristol file,
+ * a list a parallel generator wrote) names one index per gate.  These two calls renumber the wires of a whole op list so that an
+ * index is reused once the value on it has had its last reader.  The proof does not depend on wire numbering (masks and transcript
+ * events follow op order), so the proof of the renumbered list under its new counts is byte for byte the proof of the original.
+ *
+ * The rule: every op with a destination defines a value; a read refers to the last value defined on its index.  The GF(2) indices
+ * inside any B2A range [a, a + 63] are pinned: they map to their rank among the pinned indices (new indices 0 .. P - 1, consecutive
+ * ranges stay consecutive) and are never reused.  A read of a non-pinned index that no earlier op wrote maps to one reserved,
+ * never-written wire of its domain (new GF(2) index P, new Z64 index 0; reserved only if there is such a read).  Every other value
+ * takes a slot from its domain's FIFO pool behind these, per op in this order: the destination takes the head of the queue (a fresh
+ * slot when it is empty); then each operand value whose last reader is this op is released to the tail (a before b; once when both
+ * name it); then the op's own value, if nothing reads it.  SizeHint ops stay in place with the new counts as their fields, so op
+ * indices keep their meaning and no count grows.  Input ops keep their places: witness order is unchanged.  RV_COMPILE_KEEP_WIRES and
+ * rv_evaluate* wire values refer to the new indices: the renumbered dst of an op is where its value lives.
+ *
+ * The slot count is the largest number of values alive across one op; for a list that is already tight the new count can exceed the
+ * old by one (the destination is allocated before the operands are released) plus the zero wire.  info reports the counts; whether to
+ * use the new list is the caller's choice.  info may be NULL.
+ *
+ * Errors: the list is validated as rv_circuit_compile validates it (domain, opcode, reserved, every wire index against the count in
+ * force at its op) and the code is the one rv_circuit_compile returns for the list -- that of the first bad op in op order.  Nothing
+ * is written then.  out may equal ops (in place); any other overlap is RV_E_ARG. */
+typedef struct rv_compact_info {
+    uint64_t z64_wires, gf2_wires;         /* new counts */
+    uint64_t gf2_pinned;                   /* P */
+    uint32_t gf2_zero_wire, z64_zero_wire; /* 1 if reserved */
+    uint64_t gf2_values, z64_values;       /* values defined */
+} rv_compact_info;
+/* host only, no GPU (like rv_bristol_parse): the sequential sweep */
+int rv_ops_compact_wires(const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, rv_op *out, rv_compact_info *info);
+/* The same result from kernels on the context's GPU, for a list that lies in device memory: d_ops and d_out are n_ops packed records
+ * in the memory of the context's device (rv_circuit_compile_device's conventions: the caller keeps ownership and must have finished
+ * writing d_ops; 8-byte aligned and inside an allocation of that device, RV_E_ARG otherwise, before anything is launched); d_out may
+ * equal d_ops.  Work memory (about 70 bytes per op, 8 per GF(2) wire index when the list has B2A ops) comes from the context arena
+ * and goes back before the call returns.  RV_E_UNSUPPORTED: 2^31 ops or more, or a wire count in force of 2^31 or more. */
+int rv_ops_compact_wires_device(rv_ctx *ctx, const rv_op *d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, rv_op *d_out,
+                                rv_compact_info *info);
+
 /* ---- program files (host only, no GPU) ---------------------------------------------------
  * The reference CLI reads its gate stream as bincode 1.3 of Vec<mcircuit::CombineOperation>
  * (src/main.rs:66,98,122).  rv_program_from_bincode turns such a file into rv_op records, rv_program_to_bincode

@@ -7,4 +7,5 @@ from .ops import B2A, GF2, Z64, SizeHint, largest_wires, program  # noqa: F401
 from .proof import Circuit, Context, DeviceEvaluation, DeviceProof, Evaluation, Proof, challenge, combine_digests, evaluate_composite_program, prove_batch_device, verify_batch, verify_batch_device  # noqa: F401
 from .stream import (StreamingBatchProver, StreamingBatchVerifier, StreamingEvaluator, StreamingProver, StreamingVerifier,  # noqa: F401
                      evaluate_streaming, prove_streaming, prove_streaming_batch, verify_streaming, verify_streaming_batch)
+from .compact import compact_wires  # noqa: F401
 from ._lib import ReverieError  # noqa: F401

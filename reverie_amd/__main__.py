@@ -47,6 +47,16 @@ def load_program(path: str, fmt: str, expected_path=None):
     return prog, info["wire_counts"]
 
 
+def compact_program(prog, wc):
+    """--compact-wires: the program renumbered by liveness (rv_ops_compact_wires, on the host) and its new wire counts; the counts
+    before and after go to stderr"""
+    from .compact import compact_wires
+
+    out, new_wc, _ = compact_wires(prog, wc)
+    print("compact-wires: wire counts (z64, gf2) %s -> %s" % (tuple(int(x) for x in wc), new_wc), file=sys.stderr)
+    return out, new_wc
+
+
 def evaluate_clear(prog, witness):
     """`oneshot`: cleartext evaluation (mcircuit::evaluate_composite_program, main.rs:115-132);
     GF(2) gates only, like the CLI's witness type.  Raises on a failing AssertZero."""
@@ -95,10 +105,12 @@ def evaluate_gpu(prog, wc, witness, compiler="host"):
         raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (r.first_failed_op, r.n_failed))
 
 
-def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, device_compile=False, device_z64=False, device_b2a=False):
+def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, device_compile=False, device_z64=False, device_b2a=False,
+                    compact=False):
     """`oneshot --evaluator stream`: the program evaluated in pieces with bounded device memory (rv_eval_stream_*), on the GPU like
     --evaluator gpu and with the same outcome.  An rvops file is read through a memory map, piece by piece; its wire counts come from
-    one pass over the mapping."""
+    one pass over the mapping.  compact (--compact-wires): the whole list is renumbered by liveness first (in host memory: 24 bytes
+    per op, against a wire-store row per gate of an SSA list) and the stream begins with the new counts."""
     from .stream import StreamingEvaluator
 
     if fmt == "auto":
@@ -121,7 +133,11 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
             z, g = largest_wires(np.asarray(prog[at:at + step]))
             z64, gf2 = max(z64, z), max(gf2, g)
         wc = (z64, gf2)
-        pieces = (np.asarray(prog[at:at + step]) for at in range(0, n, step))
+        if not compact:
+            pieces = (np.asarray(prog[at:at + step]) for at in range(0, n, step))
+    if compact:
+        prog, wc = compact_program(np.asarray(prog), wc)
+        pieces = (prog[at:at + STREAM_FEED_OPS] for at in range(0, max(n, 1), STREAM_FEED_OPS))
     se = StreamingEvaluator(wc, 1, max_chunk_ops, device_compile=device_compile, **({"device_z64": True} if device_z64 else {}),
                             **({"device_b2a": True} if device_b2a else {}))
     try:
@@ -171,6 +187,10 @@ def build_parser():
                          "always a SizeHint that grows a wire count, op-list errors, chains deeper than 2^16 rounds and "
                          "the deep, narrow circuits the host compiler recompiles with lazy sums still compile on the host); the proof bytes "
                          "and the outcome are the same")
+    ap.add_argument("--compact-wires", action="store_true",
+                    help="prove / verify / oneshot-zk and oneshot --evaluator stream: renumber the program's wires by liveness first "
+                         "(rv_ops_compact_wires), so that an SSA-numbered program needs a wire per live value instead of one per gate; "
+                         "the proof bytes and the outcome are the same, the wire counts before and after are printed on stderr")
     ap.add_argument("--reference-compat", action="store_true",
                     help="verify / oneshot-zk: RV_VERIFY_REFERENCE_COMPAT -- answer exactly like the reference's verifier, which "
                          "accepts proofs whose opened repetitions fail an AssertZero or name another omitted player than the "
@@ -191,14 +211,18 @@ def main(argv=None) -> int:
 
         print("reverie_version: speed-reverie (reverie_amd, C-ABI v%d, drop-in for reverie-zk 0.3.2)" % _lib.lib().rv_abi_version())
         return 0
+    if a.compact_wires and a.operation == "oneshot" and a.evaluator != "stream":
+        ap.error("--compact-wires with --operation oneshot needs --evaluator stream (the other evaluators keep no wire store)")
     if a.operation == "oneshot" and a.evaluator == "stream":
         print("Evaluating program in cleartext")
         evaluate_stream(a.program_path, a.program_format, a.expected_outputs_path, parse_witness(open(a.witness_path, "rb").read()),
                         a.max_chunk_ops, device_compile=a.compiler != "host", **({"device_z64": True} if a.compiler in ("device-z64", "device-b2a") else {}),
-                        **({"device_b2a": True} if a.compiler == "device-b2a" else {}))
+                        **({"device_b2a": True} if a.compiler == "device-b2a" else {}), **({"compact": True} if a.compact_wires else {}))
         print("()")
         return 0
     prog, wc = load_program(a.program_path, a.program_format, a.expected_outputs_path)
+    if a.compact_wires:
+        prog, wc = compact_program(prog, wc)
     if a.operation == "oneshot":
         print("Evaluating program in cleartext")
         wit = parse_witness(open(a.witness_path, "rb").read())

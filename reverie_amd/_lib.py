@@ -65,6 +65,11 @@ class EvalStreamInfo(C.Structure):  # rv_eval_stream_info
     _fields_ = [(n, C.c_uint64) for n in ("n_ops", "chunks", "levels", "wire_store_bytes", "peak_chunk_bytes")]
 
 
+class CompactInfo(C.Structure):  # rv_compact_info
+    _fields_ = [("z64_wires", C.c_uint64), ("gf2_wires", C.c_uint64), ("gf2_pinned", C.c_uint64), ("gf2_zero_wire", C.c_uint32),
+                ("z64_zero_wire", C.c_uint32), ("gf2_values", C.c_uint64), ("z64_values", C.c_uint64)]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8), ("calls", C.c_uint64)]
 
@@ -107,6 +112,7 @@ SYMBOLS = [
     "rv_hook_stream_traffic", "rv_hook_stream_verify_device_paths", "rv_hook_stream_wit_sums",
     "rv_hook_extract_bits", "rv_hook_extract_from_bits", "rv_hook_pack_corr_all", "rv_hook_unpack_bits", "rv_hook_extract64", "rv_hook_unpack64",
     "rv_hook_compile_levels", "rv_hook_circuit_levels", "rv_hook_interp_launches",
+    "rv_ops_compact_wires", "rv_ops_compact_wires_device",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -182,6 +188,9 @@ ARGTYPES = {
     "rv_hook_compile_levels": [_P, _Z, _Z, _Z, C.c_uint32, _P, _Z, C.POINTER(C.c_size_t)],
     "rv_hook_circuit_levels": [_P, _P, _Z, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "rv_hook_interp_launches": [_P, C.c_int],
+    # wire indices compacted by liveness
+    "rv_ops_compact_wires": [_P, _Z, _Z, _Z, _P, C.POINTER(CompactInfo)],
+    "rv_ops_compact_wires_device": [_P, _P, _Z, _Z, _Z, _P, C.POINTER(CompactInfo)],
 }
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1

@@ -22,6 +22,7 @@
 
 #include "b3.h"
 #include "compile.h"
+#include "compact_dev.h"
 #include "compile_dev.h"
 #include "internal.h"
 #include "launch.h"
@@ -1587,3 +1588,4 @@ extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
 #include "eval_stream.inc"
 #include "stream_wdev.inc"
 #include "witness_dev.inc"
+#include "compact.inc"

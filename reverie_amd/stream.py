@@ -31,6 +31,12 @@ int64 / uint64 [m] or [B][m], rows may be strided): the stream reads them where 
 rv_eval_stream_feed_wdev), with host or device ops alike.  `finish(device=True)` (one-shot: `device_proof=True`) leaves the proof in a
 torch uint8 GPU tensor and returns a `DeviceProof`; the verifiers take a `DeviceProof` or a uint8 GPU tensor wherever they take proof
 bytes and read it in place (rv_stream_verify_begin_device).  Proofs, answers and values are the same bytes either way.
+
+The one-shot functions take `compact_wires` (default False): the whole op list is first renumbered by liveness (`compact.compact_wires`,
+DESIGN §17) -- on the host for host ops, by kernels for a GPU tensor -- and the stream begins with the new, smaller wire counts, so an
+SSA-numbered list no longer costs a wire-store row per gate.  Proofs and answers are the same bytes; the wire values
+`evaluate_streaming` returns are those of the new indices (an op's renumbered `dst` is where its value lives), and the stream info
+carries rv_compact_info under "compact".  The feeding classes are unchanged: a caller who feeds in pieces compacts the whole list first.
 """
 from __future__ import annotations
 
@@ -41,6 +47,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from . import compact as _compact
 from .ops import OP_DTYPE, TOTAL_REPS, program
 from .proof import Context, DeviceProof, Evaluation, Proof, _device_bytes, _device_ops, _device_witness, _is_device_ops, _ptr
 
@@ -48,6 +55,19 @@ from .proof import Context, DeviceProof, Evaluation, Proof, _device_bytes, _devi
 def _ops_ctx(ops, ctx: Optional[Context]) -> Context:
     """the context of a one-shot call; an op tensor that is not in GPU memory is refused before a context is made"""
     return _device_ops(ops, ctx, "a stream of device ops")[2] if _is_device_ops(ops) else ctx or Context.default()
+
+
+def _compacted(ops, wire_counts, ctx: Context, wanted: bool):
+    """the op list and wire counts a one-shot call streams, and rv_compact_info (None: compact_wires was not asked for)"""
+    if not wanted:
+        return ops, wire_counts, None
+    return _compact.compact_wires(ops, wire_counts, ctx)
+
+
+def _with_compact(info: dict, cinfo) -> dict:
+    if cinfo is not None:
+        info["compact"] = cinfo
+    return info
 
 
 def _feed(handle, ctx: Context, ops, g, n_g: int, z, n_z: int, entry: str = "rv_stream_feed"):
@@ -215,12 +235,14 @@ class StreamingProver:
 
 def prove_streaming(ops, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
                     ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                    device_proof: bool = False) -> Tuple[Proof, dict]:
+                    device_proof: bool = False, compact_wires: bool = False) -> Tuple[Proof, dict]:
     """rv_prove_streaming: both passes over an op array in host memory -> (Proof, stream info).  A torch GPU tensor of ops, witnesses
-    that are torch GPU tensors or device_proof=True (-> a DeviceProof): the same through rv_stream_begin / the feeds / the finish."""
+    that are torch GPU tensors or device_proof=True (-> a DeviceProof): the same through rv_stream_begin / the feeds / the finish.
+    compact_wires: the list is renumbered by liveness first and the stream begins with the new counts (the same proof)."""
     _check_device_z64(device_compile, device_z64, device_b2a)
     on_device = _wdev(wit_gf2, wit_z64, ctx, "prove_streaming", batched=False) is not None  # (refuses before a context is made)
     ctx = _ops_ctx(ops, ctx)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires)
     if _is_device_ops(ops) or on_device or device_proof:
         sp = StreamingProver(wire_counts, seeds, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
@@ -228,7 +250,7 @@ def prove_streaming(ops, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=N
             sp.feed(ops, wit_gf2, wit_z64)
             sp.commit()
             sp.feed(ops, wit_gf2, wit_z64)
-            return sp.finish(device=device_proof), sp.info
+            return sp.finish(device=device_proof), _with_compact(sp.info, cinfo)
         finally:
             sp.close()
     ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
@@ -243,7 +265,7 @@ def prove_streaming(ops, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=N
         _lib.check(_lib.lib().rv_prove_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(int(wire_counts[0])),
                                                  C.c_size_t(int(wire_counts[1])), _ptr(g), C.c_size_t(len(g)), _ptr(z), C.c_size_t(len(z)), _ptr(s),
                                                  C.c_size_t(max_chunk_ops), C.byref(out), C.byref(n), C.byref(si)))
-    return Proof(_owned=(C.c_void_p(out.value), n.value)), {k: int(getattr(si, k)) for k, _ in si._fields_}
+    return Proof(_owned=(C.c_void_p(out.value), n.value)), _with_compact({k: int(getattr(si, k)) for k, _ in si._fields_}, cinfo)
 
 
 class StreamingVerifier:
@@ -291,19 +313,21 @@ class StreamingVerifier:
 
 
 def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = True, max_chunk_ops: int = 0,
-                     ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False) -> Tuple[bool, dict]:
+                     ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
+                     compact_wires: bool = False) -> Tuple[bool, dict]:
     """rv_verify_streaming: one pass over an op array in host memory -> (ok, stream info).  A torch GPU tensor of ops: the same through
-    rv_stream_verify_begin / rv_stream_feed_device / rv_stream_verify_finish."""
+    rv_stream_verify_begin / rv_stream_feed_device / rv_stream_verify_finish.  compact_wires: as in prove_streaming (the same answer)."""
     _check_device_z64(device_compile, device_z64, device_b2a)
     on_device = _device_proof_bytes(proof, ctx, "verify_streaming") is not None
     if on_device and ctx is None and isinstance(proof, DeviceProof):
         ctx = proof.ctx
     ctx = _ops_ctx(ops, ctx)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires)
     if _is_device_ops(ops) or on_device:
         sv = StreamingVerifier(wire_counts, proof, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
             sv.feed(ops)
-            return sv.finish(strict), sv.info
+            return sv.finish(strict), _with_compact(sv.info, cinfo)
         finally:
             sv.close()
     ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
@@ -315,7 +339,7 @@ def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = Tr
         _lib.check(_lib.lib().rv_verify_streaming(ctx.handle, _ptr(ops), C.c_size_t(len(ops)), C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])),
                                                   buf, C.c_size_t(n), C.c_uint32(0 if strict else _lib.RV_VERIFY_REFERENCE_COMPAT), C.c_size_t(max_chunk_ops),
                                                   C.byref(ok), C.byref(si)))
-    return bool(ok.value), {k: int(getattr(si, k)) for k, _ in si._fields_}
+    return bool(ok.value), _with_compact({k: int(getattr(si, k)) for k, _ in si._fields_}, cinfo)
 
 
 def _batch_seeds(seeds, batch: int):
@@ -419,13 +443,17 @@ class StreamingBatchProver:
 
 def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
                           ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                          device_proof: bool = False) -> "list[Proof]":
+                          device_proof: bool = False, compact_wires: bool = False) -> "list[Proof]":
     """rv_prove_streaming_batch: both passes over an op array in host memory for the witnesses wits_gf2 [B][n] / wits_z64
     [B][m] (B from whichever of the two is 2-D; the other may be []); seeds [B][256][16] or None.  `info` (a dict, optional) receives the stream's figures.
-    Witnesses that are torch GPU tensors are read where they lie; device_proof=True returns DeviceProof views of one GPU tensor."""
+    Witnesses that are torch GPU tensors are read where they lie; device_proof=True returns DeviceProof views of one GPU tensor.
+    compact_wires: as in prove_streaming (the same proofs; `info` also receives "compact")."""
     _check_device_z64(device_compile, device_z64, device_b2a)
     dw = _wdev(wits_gf2, wits_z64, ctx, "prove_streaming_batch", batched=True)  # (refuses before a context is made)
     ctx = _ops_ctx(ops, ctx)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires)
+    if info is not None:
+        _with_compact(info, cinfo)
     if dw is not None:  # (GPU tensors: [B][n] both, the batch from the descriptor)
         g0, z0, batch = wits_gf2, wits_z64, dw[1]
     else:
@@ -515,13 +543,18 @@ class StreamingBatchVerifier:
 
 
 def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bool = True, max_chunk_ops: int = 0,
-                           ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False) -> "list[bool]":
-    """rv_verify_streaming_batch: one pass over an op array in host memory for every proof -> one bool per proof"""
+                           ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
+                           compact_wires: bool = False) -> "list[bool]":
+    """rv_verify_streaming_batch: one pass over an op array in host memory for every proof -> one bool per proof.
+    compact_wires: as in prove_streaming (the same answers; `info` also receives "compact")."""
     _check_device_z64(device_compile, device_z64, device_b2a)
     ctx = _ops_ctx(ops, ctx)
     n = len(proofs)
     if n == 0:
         return []
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires)
+    if info is not None:
+        _with_compact(info, cinfo)
     on_device = any(_device_proof_bytes(p, ctx, "verify_streaming_batch") is not None for p in proofs)
     if _is_device_ops(ops) or on_device:  # (begin / one feed / finish)
         sv = StreamingBatchVerifier(wire_counts, proofs, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
@@ -620,14 +653,20 @@ class StreamingEvaluator:
 
 
 def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], max_chunk_ops: int = 0, values: bool = False,
-                       ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False) -> Evaluation:
+                       ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
+                       compact_wires: bool = False) -> Evaluation:
     """rv_evaluate_streaming: one op array in host memory, evaluated chunk by chunk with bounded device memory.  wits_gf2 /
     wits_z64: [B][n] (1-D for one witness; the batch is len(wits_gf2)).  Returns the array-shaped Evaluation of
-    Circuit.evaluate_batch; `info` (a dict, optional) receives the stream's figures."""
+    Circuit.evaluate_batch; `info` (a dict, optional) receives the stream's figures.  compact_wires: the list is renumbered by
+    liveness first; the statuses are the same, the wire values are those of the new indices under the new counts (an op's value
+    lives at its renumbered `dst`: compact.compact_wires gives the renumbered list), and `info` also receives "compact"."""
     _check_device_z64(device_compile, device_z64, device_b2a)
     dims = [t.dim() for t in (wits_gf2, wits_z64) if hasattr(t, "data_ptr")]
     dw = _wdev(wits_gf2, wits_z64, ctx, "evaluate_streaming", batched=bool(dims) and max(dims) == 2)  # (refuses before a context is made)
     ctx = _ops_ctx(ops, ctx)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires)
+    if info is not None:
+        _with_compact(info, cinfo)
     if dw is not None:
         g0, batch = wits_gf2, dw[1]
     else:
