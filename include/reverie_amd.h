@@ -1040,6 +1040,13 @@ uint64_t rv_hook_verify_proof_bytes(void);
 /* rv_verify_device / rv_verify_sections_device calls of this process that took out[0] = the device path, out[1] = the host fallback
  * (calls refused with RV_E_ARG count as neither). */
 int rv_hook_verify_device_paths(uint64_t out[2]);
+/* What the single-proof verifiers of this process (rv_verify*, rv_verify_shard*, rv_verify_device, rv_verify_sections_device on
+ * the device path) decided about their order of work, as running totals: out[0] = calls, out[1] = every host array and the proof
+ * in one copy through the staging buffer, out[2] = the proof's copy on the second stream, out[3] = the fused Z64 verifier's quad
+ * groups split around that copy, out[4] = the fused Z64 verifier, out[5] = the GF(2) mask generator beside the levels,
+ * out[6] = MODE_VERIFY_C (as rv_hook_verify_vc_count), out[7] = calls whose proof lay in device memory.  The answer is the same on
+ * every path; the tests use the counters to know which one a shape took. */
+int rv_hook_verify_schedule(uint64_t out[8]);
 /* Proofs rv_verify_batch_device verified in this process through out[0] = the one-pass device path, out[1] = the single-proof
  * device verifier, out[2] = a host copy (walks that stopped); calls refused with RV_E_ARG count nowhere. */
 int rv_hook_verify_batch_device_paths(uint64_t out[3]);

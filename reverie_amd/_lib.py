@@ -103,7 +103,7 @@ SYMBOLS = [
     "rv_hook_maskgen",
     "rv_stream_feed_device", "rv_eval_stream_feed_device", "rv_hook_stream_op_traffic", "rv_hook_stream_piece_sums",
     "rv_hook_compile_compare_device_chunk_ex", "rv_hook_compile_device_laps_z64",
-    "rv_verify_device", "rv_verify_sections_device", "rv_hook_verify_device_paths", "rv_hook_verify_walk",
+    "rv_verify_device", "rv_verify_sections_device", "rv_hook_verify_device_paths", "rv_hook_verify_walk", "rv_hook_verify_schedule",
     "rv_prove_batch_device", "rv_verify_batch_device", "rv_hook_verify_batch_device_paths",
     "rv_prove_wdev", "rv_prove_device_wdev", "rv_prove_batch_wdev", "rv_prove_batch_device_wdev", "rv_evaluate_batch_device",
     "rv_hook_witness_traffic",
@@ -153,6 +153,7 @@ ARGTYPES = {
     "rv_verify_device": [_P, _P, _P, _Z, C.c_uint32, C.POINTER(C.c_int)],
     "rv_verify_sections_device": [_P, _P, _P, _P, C.POINTER(C.c_size_t), C.c_uint32, C.POINTER(C.c_int)],
     "rv_hook_verify_device_paths": [C.POINTER(C.c_uint64)],
+    "rv_hook_verify_schedule": [C.POINTER(C.c_uint64)],
     "rv_hook_verify_walk": [_P, _Z, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)],
     # batches that stay in device memory
     "rv_prove_batch_device": [_P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _Z, C.POINTER(C.c_size_t)],

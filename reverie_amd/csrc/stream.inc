@@ -1790,6 +1790,60 @@ extern "C" int rv_stream_get_info(const rv_stream* S, rv_stream_info* info) {
 // verifier/online.rs:25-183; all 8 and recomputed corrections for the others, verifier/preprocess.rs:17-79), its
 // transcripts go into the same incremental BLAKE3 trees as the prover's first pass, and the end is rv_verify's end.
 // ------------------------------------------------------------------------------------
+// a verifier stream that runs nothing and answers `false`: rv_verify's answer for wrong repetition counts (proof/mod.rs:225-230),
+// and a batch member whose proof is refused
+static rv_stream* stream_dead_verifier(rv_ctx* ctx, const uint8_t* proof, size_t proof_len) {
+    rv_stream* S = new rv_stream();
+    S->ctx = ctx;
+    S->pass = 3;
+    S->format_bad = true;
+    S->h_proof = proof;
+    S->proof_len = proof_len;
+    return S;
+}
+
+// The verifier's slot arrays (slot order: the 40 opened repetitions first) and the Z64 keys' scratch, every block on `tmp` until
+// stream_verifier_arm hands it to a stream
+static int stream_verifier_alloc(rv_ctx* ctx, DevSlotArrays& a, uint8_t*& d_keys64, std::vector<void*>& tmp) {
+    constexpr uint32_t R = rv_stream::R, NQ = rv_stream::NQ;
+    auto get = [&](size_t count, auto*& ptr) {
+        const int rc = dalloc(ctx, count, &ptr);
+        if (!rc) tmp.push_back(ptr);
+        return rc;
+    };
+    int rc;
+    if ((rc = get((size_t)R * 16, a.seeds)) || (rc = get(R, a.omit)) || (rc = get((size_t)R * 128, a.hkeys)) || (rc = get((size_t)R * 32, a.hco)) ||
+        (rc = get((size_t)R * 32, a.hco64)) || (rc = get(NQ, a.keep)) || (rc = get(NQ, a.onm)) || (rc = get((size_t)6 * R, a.src)) ||
+        (rc = get((size_t)R * 16, a.seeds64)) || (rc = get(R, a.omit64)) || (rc = get((size_t)R * 128, a.hkeys64)) || (rc = get(NQ, a.keep64)) ||
+        (rc = get((size_t)6 * R, a.src64)) || (rc = get((size_t)R * 128, d_keys64)))
+        return rc;
+    return RV_OK;
+}
+// What both begins do once the arrays are filled in device memory: the eight arrays the chunks read now belong to the stream (and
+// leave `tmp`), then the two transcripts' round keys; waits for the stream
+static int stream_verifier_arm(rv_stream* S, const DevSlotArrays& a, uint8_t* d_keys64, std::vector<void*>& tmp) {
+    constexpr uint32_t R = rv_stream::R, NQ = rv_stream::NQ;
+    rv_ctx* ctx = S->ctx;
+    hipStream_t st = ctx->stream;
+    S->d_omit_v = a.omit, S->d_omit64_v = a.omit64, S->d_hco = a.hco, S->d_hco64 = a.hco64, S->d_keep = a.keep, S->d_keep64 = a.keep64, S->d_onm = a.onm,
+    S->d_src = a.src;
+    void* owned[] = {a.omit, a.omit64, a.hco, a.hco64, a.keep, a.keep64, a.onm, a.src};
+    for (void* p : owned) tmp.erase(std::find(tmp.begin(), tmp.end(), p));
+    if (int rc = dalloc(ctx, (size_t)RK_AREAS * 128 * NQ, &S->d_rk64)) return rc;
+    // GF(2) transcript: the opened slots' keys are the proof's (omitted one zeroed, online.rs:101-113); the others came with the
+    // prover's begin
+    launch_overlay_rows(st, (uint32_t*)S->d_keys, (const uint32_t*)a.hkeys, S->d_omit_v, R, 32, 1);
+    launch_key_schedule(st, S->d_keys, R * 8, S->d_rkbytes);
+    launch_bitslice_rk(st, S->d_rkbytes, NQ, S->d_rk);
+    // Z64 transcript: its own seeds / keys per repetition
+    launch_verifier_keys(st, R, a.seeds64, a.hkeys64, S->d_omit64_v, d_keys64);
+    launch_key_schedule(st, d_keys64, R * 8, S->d_rkbytes);
+    launch_bitslice_rk(st, S->d_rkbytes, NQ, S->d_rk64);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return hip_fail(hipGetLastError(), "streaming verifier setup", __FILE__, __LINE__);
+    return RV_OK;
+}
+
 static int stream_verify_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, const uint8_t* proof, size_t proof_len, size_t max_chunk_ops,
                                     rv_stream** out) {
     if (!ctx || !out || !proof) return RV_E_ARG;
@@ -1798,74 +1852,53 @@ static int stream_verify_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wi
     int rc = parse_proof(proof, proof_len, P);
     if (rc) return rc;
     constexpr uint32_t R = rv_stream::R, NQ = rv_stream::NQ;
-    if (!format_ok(P)) {  // the answer is `false`, as rv_verify's (proof/mod.rs:225-230): a stream that runs nothing
-        rv_stream* S = new rv_stream();
-        S->ctx = ctx;
-        S->pass = 3;
-        S->format_bad = true;
-        S->h_proof = proof;
-        S->proof_len = proof_len;
-        *out = S;
+    if (!format_ok(P)) {
+        *out = stream_dead_verifier(ctx, proof, proof_len);
         return RV_OK;
     }
-    // ---- the slots (verifier's order: the 40 opened repetitions first), as rv_verify_shard prepares them
+    // ---- the slots, as rv_verify_shard prepares them
     if ((rc = check_records_range(P, 0, R))) return rc;
     HostSlots H(R, true);
     fill_slots_range(P, proof, 0, R, 0, true, H.arrays());
-    // the prover's begin gives the stream its buffers and the GF(2) keys of the preprocessing slots (opened slots: overlaid below)
+    hipStream_t st = ctx->stream;
     rv_stream* S = nullptr;
-    if ((rc = stream_begin_impl(ctx, z64_wires, gf2_wires, H.seeds.data(), max_chunk_ops, &S))) return rc;
+    std::vector<void*> tmp;
+    auto fail = [&](int code) {
+        (void)hipStreamSynchronize(st);  // (the host vectors above leave scope)
+        for (void* p : tmp) ctx->release(p);
+        if (S) rv_stream_abort(S);
+        return code;
+    };
+    DevSlotArrays a{};
+    uint8_t* d_keys64 = nullptr;
+    if ((rc = stream_verifier_alloc(ctx, a, d_keys64, tmp))) return fail(rc);
+    // the prover's begin gives the stream its buffers and the GF(2) keys of the preprocessing slots (opened slots: overlaid below)
+    if ((rc = stream_begin_impl(ctx, z64_wires, gf2_wires, H.seeds.data(), max_chunk_ops, &S))) return fail(rc);
     S->pass = 3;
     S->h_proof = proof;
     S->proof_len = proof_len;
     S->src64 = H.src64;
-    hipStream_t st = ctx->stream;
-    auto fail = [&](int code) {
-        rv_stream_abort(S);
-        return code;
-    };
-    uint8_t *d_hkeys = nullptr, *d_seeds64 = nullptr, *d_keys64 = nullptr;
-    if ((rc = dalloc(ctx, std::max<size_t>(proof_len, 1), &S->d_vproof)) || (rc = dalloc(ctx, R, &S->d_omit_v)) || (rc = dalloc(ctx, R, &S->d_omit64_v)) ||
-        (rc = dalloc(ctx, (size_t)R * 32, &S->d_hco)) || (rc = dalloc(ctx, (size_t)R * 32, &S->d_hco64)) || (rc = dalloc(ctx, NQ, &S->d_keep)) ||
-        (rc = dalloc(ctx, NQ, &S->d_keep64)) || (rc = dalloc(ctx, NQ, &S->d_onm)) || (rc = dalloc(ctx, (size_t)RK_AREAS * 128 * NQ, &S->d_rk64)) ||
-        (rc = dalloc(ctx, (size_t)6 * R, &S->d_src)) || (rc = dalloc(ctx, (size_t)R * 128, &d_hkeys)) || (rc = dalloc(ctx, (size_t)R * 16, &d_seeds64)) ||
-        (rc = dalloc(ctx, (size_t)R * 128, &d_keys64))) {
-        ctx->release(d_hkeys);
-        ctx->release(d_seeds64);
-        ctx->release(d_keys64);
-        return fail(rc);
-    }
+    S->sup_nq = supplied_nq(H.onm.data(), NQ);
+    S->sup_r = supplied_r64(H.omit64.data(), R);
+    if ((rc = dalloc(ctx, std::max<size_t>(proof_len, 1), &S->d_vproof))) return fail(rc);
     bool ok = true;
     auto up = [&](void* dst, const void* from, size_t n) { ok = ok && hipMemcpyAsync(dst, from, n, hipMemcpyHostToDevice, st) == hipSuccess; };
     up(S->d_vproof, proof, proof_len);
     stream_traffic(3, proof_len);
-    up(S->d_omit_v, H.omit.data(), R);
-    up(S->d_omit64_v, H.omit64.data(), R);
-    up(S->d_hco, H.hco.data(), H.hco.size());
-    up(S->d_hco64, H.hco64.data(), H.hco64.size());
-    up(S->d_keep, H.keep.data(), (size_t)NQ * 4);
-    up(S->d_keep64, H.keep64.data(), (size_t)NQ * 4);
-    up(S->d_onm, H.onm.data(), (size_t)NQ * 4);
-    S->sup_nq = supplied_nq(H.onm.data(), NQ);
-    S->sup_r = supplied_r64(H.omit64.data(), R);
-    up(S->d_src, H.src.data(), H.src.size() * 8);
-    // GF(2) transcript: the opened slots' keys are the proof's (omitted one zeroed, online.rs:101-113)
-    up(d_hkeys, H.hkeys.data(), H.hkeys.size());
-    launch_overlay_rows(st, (uint32_t*)S->d_keys, (const uint32_t*)d_hkeys, S->d_omit_v, R, 32, 1);
-    launch_key_schedule(st, S->d_keys, R * 8, S->d_rkbytes);
-    launch_bitslice_rk(st, S->d_rkbytes, NQ, S->d_rk);
-    // Z64 transcript: its own seeds / keys per repetition
-    up(d_seeds64, H.seeds64.data(), H.seeds64.size());
-    launch_expand_seeds(st, d_seeds64, R, d_keys64);
-    up(d_hkeys, H.hkeys64.data(), H.hkeys64.size());  // (stream order: behind the overlay above that read the GF(2) keys)
-    launch_overlay_rows(st, (uint32_t*)d_keys64, (const uint32_t*)d_hkeys, S->d_omit64_v, R, 32, 1);
-    launch_key_schedule(st, d_keys64, R * 8, S->d_rkbytes);
-    launch_bitslice_rk(st, S->d_rkbytes, NQ, S->d_rk64);
-    ok = ok && hipStreamSynchronize(st) == hipSuccess;  // (the host vectors above leave scope)
-    ctx->release(d_hkeys);
-    ctx->release(d_seeds64);
-    ctx->release(d_keys64);
+    up(a.omit, H.omit.data(), R);
+    up(a.omit64, H.omit64.data(), R);
+    up(a.hco, H.hco.data(), H.hco.size());
+    up(a.hco64, H.hco64.data(), H.hco64.size());
+    up(a.keep, H.keep.data(), (size_t)NQ * 4);
+    up(a.keep64, H.keep64.data(), (size_t)NQ * 4);
+    up(a.onm, H.onm.data(), (size_t)NQ * 4);
+    up(a.src, H.src.data(), H.src.size() * 8);
+    up(a.hkeys, H.hkeys.data(), H.hkeys.size());
+    up(a.seeds64, H.seeds64.data(), H.seeds64.size());
+    up(a.hkeys64, H.hkeys64.data(), H.hkeys64.size());
     if (!ok) return fail(hip_fail(hipGetLastError(), "streaming verifier setup", __FILE__, __LINE__));
+    if ((rc = stream_verifier_arm(S, a, d_keys64, tmp))) return fail(rc);
+    for (void* p : tmp) ctx->release(p);
     *out = S;
     return RV_OK;
 }
@@ -1977,6 +2010,27 @@ static int stream_batch_fits(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, si
     return RV_OK;
 }
 
+// A handle over `batch` member streams, member b begun by begin(b, &member); the first member that cannot begin ends them all
+template <class Begin>
+static int stream_batch_handle(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch, int pass, Begin&& begin, rv_stream** out) {
+    if (int rc = stream_batch_fits(ctx, z64_wires, gf2_wires, batch)) return rc;
+    rv_stream* H = new rv_stream();
+    H->ctx = ctx;
+    H->z64_wires = z64_wires;
+    H->gf2_wires = gf2_wires;
+    H->pass = pass;
+    for (size_t b = 0; b < batch; b++) {
+        rv_stream* m = nullptr;
+        if (int rc = begin(b, &m)) {
+            rv_stream_abort(H);
+            return rc;
+        }
+        H->bat.push_back(m);
+    }
+    *out = H;
+    return RV_OK;
+}
+
 static int stream_begin_batch_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch, const uint8_t* seeds, size_t max_chunk_ops,
                                    rv_stream** out) {
     if (!ctx || !out) return RV_E_ARG;
@@ -1985,24 +2039,14 @@ static int stream_begin_batch_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wir
     if (gf2_wires > 0x3FFFFFFFull || z64_wires > 0x3FFFFFFFull) return RV_E_UNSUPPORTED;
     HIPCHK(hipSetDevice(ctx->device));
     if (batch == 1) return stream_begin_impl(ctx, z64_wires, gf2_wires, seeds, max_chunk_ops, out);  // (a single stream, as rv_stream_begin)
-    int rc;
-    if ((rc = stream_batch_fits(ctx, z64_wires, gf2_wires, batch))) return rc;
-    rv_stream* H = new rv_stream();
-    H->ctx = ctx;
-    H->z64_wires = z64_wires;
-    H->gf2_wires = gf2_wires;
-    for (size_t b = 0; b < batch; b++) {
-        rv_stream* m = nullptr;
-        if ((rc = stream_begin_impl(ctx, z64_wires, gf2_wires, seeds ? seeds + b * RV_TOTAL_REPS * RV_KEY_SIZE : nullptr, max_chunk_ops, &m))) {
-            rv_stream_abort(H);
-            return rc;
-        }
-        H->bat.push_back(m);
-    }
-    for (rv_stream* m : H->bat) m->keep_cap /= batch;  // (RV_STREAM_KEEP_MB is the budget of the whole batch)
-    *out = H;
+    auto begin = [&](size_t b, rv_stream** m) {
+        return stream_begin_impl(ctx, z64_wires, gf2_wires, seeds ? seeds + b * RV_TOTAL_REPS * RV_KEY_SIZE : nullptr, max_chunk_ops, m);
+    };
+    if (int rc = stream_batch_handle(ctx, z64_wires, gf2_wires, batch, 1, begin, out)) return rc;
+    for (rv_stream* m : (*out)->bat) m->keep_cap /= batch;  // (RV_STREAM_KEEP_MB is the budget of the whole batch)
     return RV_OK;
 }
+
 
 extern "C" int rv_stream_begin_batch(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch, const uint8_t* seeds, size_t max_chunk_ops,
                                      rv_stream** out) {
@@ -2056,13 +2100,7 @@ static int stream_verify_member(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires,
                                 rv_stream** out) {
     int rc = stream_verify_begin_impl(ctx, z64_wires, gf2_wires, proof, proof_len, max_chunk_ops, out);
     if (rc == RV_E_PROOF_MALFORMED) {
-        rv_stream* S = new rv_stream();
-        S->ctx = ctx;
-        S->pass = 3;
-        S->format_bad = true;
-        S->h_proof = proof;
-        S->proof_len = proof_len;
-        *out = S;
+        *out = stream_dead_verifier(ctx, proof, proof_len);
         rc = RV_OK;
     }
     return rc;
@@ -2077,25 +2115,11 @@ static int stream_verify_begin_batch_impl(rv_ctx* ctx, size_t z64_wires, size_t 
         if (!proofs[b]) return RV_E_ARG;
     if (gf2_wires > 0x3FFFFFFFull || z64_wires > 0x3FFFFFFFull) return RV_E_UNSUPPORTED;
     HIPCHK(hipSetDevice(ctx->device));
-    if (batch == 1) return stream_verify_member(ctx, z64_wires, gf2_wires, proofs[0], proof_lens[0], max_chunk_ops, out);
-    int rc;
-    if ((rc = stream_batch_fits(ctx, z64_wires, gf2_wires, batch))) return rc;
-    rv_stream* H = new rv_stream();
-    H->ctx = ctx;
-    H->z64_wires = z64_wires;
-    H->gf2_wires = gf2_wires;
-    H->pass = 3;
-    for (size_t b = 0; b < batch; b++) {
-        rv_stream* m = nullptr;
-        if ((rc = stream_verify_member(ctx, z64_wires, gf2_wires, proofs[b], proof_lens[b], max_chunk_ops, &m))) {
-            rv_stream_abort(H);
-            return rc;
-        }
-        H->bat.push_back(m);
-    }
-    *out = H;
-    return RV_OK;
+    auto begin = [&](size_t b, rv_stream** m) { return stream_verify_member(ctx, z64_wires, gf2_wires, proofs[b], proof_lens[b], max_chunk_ops, m); };
+    if (batch == 1) return begin(0, out);
+    return stream_batch_handle(ctx, z64_wires, gf2_wires, batch, 3, begin, out);
 }
+
 
 extern "C" int rv_stream_verify_begin_batch(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch, const uint8_t* const* proofs,
                                             const size_t* proof_lens, size_t max_chunk_ops, rv_stream** out) {

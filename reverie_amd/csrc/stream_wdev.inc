@@ -200,16 +200,12 @@ static int stream_verify_begin_device_impl(rv_ctx* ctx, size_t z64_wires, size_t
         rv_stream* S = nullptr;
         rc = stream_verify_begin_impl(ctx, z64_wires, gf2_wires, h.data(), proof_len, max_chunk_ops, &S);
         if (rc == RV_E_PROOF_MALFORMED && as_member) {
-            S = new rv_stream();
-            S->ctx = ctx;
-            S->pass = 3;
-            S->format_bad = true;
+            S = stream_dead_verifier(ctx, h.data(), proof_len);
             rc = RV_OK;
         }
         if (rc) return rc;
         S->own_proof = std::move(h);  // (the vector's buffer moves with it: h_proof, where the host form left it, stays valid)
         S->h_proof = S->own_proof.data();
-        S->proof_len = proof_len;
         *out = S;
         return RV_OK;
     }
@@ -217,40 +213,15 @@ static int stream_verify_begin_device_impl(rv_ctx* ctx, size_t z64_wires, size_t
     // the offsets and lengths of the records (the host keeps the Z64 vectors' places: ChunkRun shifts them chunk by chunk)
     if (hipMemcpy(table.data(), d_table, (size_t)VW_HEAD * 8, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(hip_fail(hipGetLastError(), "streaming verifier (table)", __FILE__, __LINE__));
-    // ---- the slot arrays on the device (slot order: the 40 online records first), as stream_verify_begin_impl uploads them
+    // ---- the slot arrays on the device, where stream_verify_begin_impl uploads them
     DevSlotArrays a{};
-    uint8_t *d_keys64 = nullptr;
-#define DA(count, ptr)                                       \
-    do {                                                     \
-        if ((rc = dalloc(ctx, (count), &(ptr)))) return fail(rc); \
-        tmp.push_back(ptr);                                  \
-    } while (0)
-    DA((size_t)R * 16, a.seeds);
-    DA(R, a.omit);
-    DA((size_t)R * 128, a.hkeys);
-    DA((size_t)R * 32, a.hco);
-    DA((size_t)R * 32, a.hco64);
-    DA(NQ, a.keep);
-    DA(NQ, a.onm);
-    DA((size_t)6 * R, a.src);
-    DA((size_t)R * 16, a.seeds64);
-    DA(R, a.omit64);
-    DA((size_t)R * 128, a.hkeys64);
-    DA(NQ, a.keep64);
-    DA((size_t)6 * R, a.src64);
-    DA((size_t)R * 128, d_keys64);
-#undef DA
+    uint8_t* d_keys64 = nullptr;
+    if ((rc = stream_verifier_alloc(ctx, a, d_keys64, tmp))) return fail(rc);
     launch_fill_slots_dev(st, d_proof, d_table, true, a);
     if (hipGetLastError() != hipSuccess) return fail(RV_E_DEVICE);
     // the prover's begin gives the stream its buffers and the GF(2) keys of the preprocessing slots, from the seeds the kernel wrote
     rv_stream* S = nullptr;
     if ((rc = stream_begin_impl(ctx, z64_wires, gf2_wires, a.seeds, max_chunk_ops, &S, /*seeds_on_device=*/true))) return fail(rc);
-    auto fail_stream = [&](int code) {
-        (void)hipStreamSynchronize(st);
-        release_tmp();  // (the arrays not yet handed to the stream)
-        rv_stream_abort(S);
-        return code;
-    };
     S->pass = 3;
     S->proof_len = proof_len;
     S->proof_in_place = true;
@@ -270,36 +241,22 @@ static int stream_verify_begin_device_impl(rv_ctx* ctx, size_t z64_wires, size_t
     // (the slot order puts the opened repetitions into the first ten quad words / forty repetitions: supplied_nq, supplied_r64)
     S->sup_nq = std::min(NQ, 16u);
     S->sup_r = std::min(R, 64u);
-    // the arrays the chunks read now belong to the stream
-    S->d_omit_v = a.omit, S->d_omit64_v = a.omit64, S->d_hco = a.hco, S->d_hco64 = a.hco64, S->d_keep = a.keep, S->d_keep64 = a.keep64, S->d_onm = a.onm,
-    S->d_src = a.src;
-    {
-        void* owned[] = {a.omit, a.omit64, a.hco, a.hco64, a.keep, a.keep64, a.onm, a.src};
-        for (void* p : owned) tmp.erase(std::find(tmp.begin(), tmp.end(), p));
+    if ((rc = stream_verifier_arm(S, a, d_keys64, tmp))) {
+        rc = fail(rc);  // (waits, and releases the arrays the stream has not taken)
+        rv_stream_abort(S);
+        return rc;
     }
-    if ((rc = dalloc(ctx, (size_t)RK_AREAS * 128 * NQ, &S->d_rk64))) return fail_stream(rc);
-    // GF(2) transcript: the opened slots' keys are the proof's (omitted one zeroed, online.rs:101-113)
-    launch_overlay_rows(st, (uint32_t*)S->d_keys, (const uint32_t*)a.hkeys, S->d_omit_v, R, 32, 1);
-    launch_key_schedule(st, S->d_keys, R * 8, S->d_rkbytes);
-    launch_bitslice_rk(st, S->d_rkbytes, NQ, S->d_rk);
-    // Z64 transcript: its own seeds / keys per repetition
-    launch_expand_seeds(st, a.seeds64, R, d_keys64);
-    launch_overlay_rows(st, (uint32_t*)d_keys64, (const uint32_t*)a.hkeys64, S->d_omit64_v, R, 32, 1);
-    launch_key_schedule(st, d_keys64, R * 8, S->d_rkbytes);
-    launch_bitslice_rk(st, S->d_rkbytes, NQ, S->d_rk64);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return fail_stream(hip_fail(hipGetLastError(), "streaming verifier setup (device proof)", __FILE__, __LINE__));
     release_tmp();
     *out = S;
     return RV_OK;
 }
+
 
 extern "C" int rv_stream_verify_begin_device(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, const uint8_t* d_proof, size_t proof_len, size_t max_chunk_ops,
                                              rv_stream** out) {
     return guarded([&] { return stream_verify_begin_device_impl(ctx, z64_wires, gf2_wires, d_proof, proof_len, max_chunk_ops, false, out); });
 }
 
-// a loop over the members, as stream_verify_begin_batch_impl
 extern "C" int rv_stream_verify_begin_batch_device(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, size_t batch, const uint8_t* const* d_proofs,
                                                    const size_t* proof_lens, size_t max_chunk_ops, rv_stream** out) {
     return guarded([&]() -> int {
@@ -310,22 +267,10 @@ extern "C" int rv_stream_verify_begin_batch_device(rv_ctx* ctx, size_t z64_wires
             if (!d_proofs[b]) return RV_E_ARG;
         if (gf2_wires > 0x3FFFFFFFull || z64_wires > 0x3FFFFFFFull) return RV_E_UNSUPPORTED;
         HIPCHK(hipSetDevice(ctx->device));
-        if (batch == 1) return stream_verify_begin_device_impl(ctx, z64_wires, gf2_wires, d_proofs[0], proof_lens[0], max_chunk_ops, true, out);
-        if (int rc = stream_batch_fits(ctx, z64_wires, gf2_wires, batch)) return rc;
-        rv_stream* H = new rv_stream();
-        H->ctx = ctx;
-        H->z64_wires = z64_wires;
-        H->gf2_wires = gf2_wires;
-        H->pass = 3;
-        for (size_t b = 0; b < batch; b++) {
-            rv_stream* m = nullptr;
-            if (int rc = stream_verify_begin_device_impl(ctx, z64_wires, gf2_wires, d_proofs[b], proof_lens[b], max_chunk_ops, true, &m)) {
-                rv_stream_abort(H);
-                return rc;
-            }
-            H->bat.push_back(m);
-        }
-        *out = H;
-        return RV_OK;
+        auto begin = [&](size_t b, rv_stream** m) {
+            return stream_verify_begin_device_impl(ctx, z64_wires, gf2_wires, d_proofs[b], proof_lens[b], max_chunk_ops, true, m);
+        };
+        if (batch == 1) return begin(0, out);
+        return stream_batch_handle(ctx, z64_wires, gf2_wires, batch, 3, begin, out);
     });
 }

@@ -242,12 +242,8 @@ static int verify_batch_pass(rv_ctx* ctx, const rv_circuit* c, const std::vector
             s->extra.push_back(d_sup_rec64);
         }
         g_recorder = &recs[k];
-        launch_expand_seeds(ctx->stream, s->d_seeds, R, s->d_keys);
-        launch_overlay_rows(ctx->stream, (uint32_t*)s->d_keys, (const uint32_t*)(d + L.hkeys), s->d_omit, R, 32, 1);
-        if (has64) {
-            launch_expand_seeds(ctx->stream, d + L.seeds64, R, s->d_keys64);
-            launch_overlay_rows(ctx->stream, (uint32_t*)s->d_keys64, (const uint32_t*)(d + L.hkeys64), s->d_omit64, R, 32, 1);
-        }
+        launch_verifier_keys(ctx->stream, R, s->d_seeds, d + L.hkeys, s->d_omit, s->d_keys);
+        if (has64) launch_verifier_keys(ctx->stream, R, d + L.seeds64, d + L.hkeys64, s->d_omit64, s->d_keys64);
         // (k_z64_fused and the single verifier's side-stream schedule for the Z64 records -- ev_sup64, mid64 -- stay out: a fresh
         // shard's z64f is false, and the records are unpacked here, from the slot, on the main stream)
         if (!(rc = shard_setup_prg(s, (const uint32_t*)(d + L.keep), has64 ? (const uint32_t*)(d + L.keep64) : nullptr))) {
@@ -291,11 +287,9 @@ static int verify_batch_pass(rv_ctx* ctx, const rv_circuit* c, const std::vector
     for (size_t k = 0; k < B && !rc; k++) {
         uint8_t* d = d_slab + HEAD + k * L.stride;
         rv_shard* s = sh[k];
-        const size_t DW = (size_t)R * 8;
         g_recorder = &recs[k];
         if (!(rc = shard_run_hash(s))) {
-            launch_overlay_rows(ctx->stream, s->d_dig + 1 * DW, (const uint32_t*)(d + L.hco), s->d_omit, R, 8, 0);
-            launch_overlay_rows(ctx->stream, s->d_dig + 3 * DW, (const uint32_t*)(d + L.hco64), s->d_omit, R, 8, 0);
+            launch_carried_commitments(ctx->stream, s, d + L.hco, d + L.hco64);
             rc = shard_join(s);
         }
         g_recorder = nullptr;

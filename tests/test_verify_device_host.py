@@ -98,7 +98,7 @@ def test_symbols_exported_and_bound(L):
     from reverie_amd import _lib
 
     hdr = open(os.path.join(ROOT, "include", "reverie_amd.h")).read()
-    for name in ("rv_verify_device", "rv_verify_sections_device", "rv_hook_verify_device_paths", "rv_hook_verify_walk"):
+    for name in ("rv_verify_device", "rv_verify_sections_device", "rv_hook_verify_device_paths", "rv_hook_verify_walk", "rv_hook_verify_schedule"):
         assert name in _lib.SYMBOLS and name in _lib.ARGTYPES
         assert getattr(L, name).argtypes is not None and getattr(L, name).restype is C.c_int
         assert re.search(r"\b" + name + r"\s*\(", hdr), name
@@ -106,6 +106,7 @@ def test_symbols_exported_and_bound(L):
     assert reverie_amd.DeviceProof is reverie_amd.proof.DeviceProof
     paths = (C.c_uint64 * 2)()
     assert L.rv_hook_verify_device_paths(paths) == 0 and L.rv_hook_verify_device_paths(None) == 9
+    assert L.rv_hook_verify_schedule((C.c_uint64 * 8)()) == 0 and L.rv_hook_verify_schedule(None) == 9
 
 
 def test_hook_arguments(L):
