@@ -818,6 +818,37 @@ typedef struct rv_bristol_info {
 } rv_bristol_info;
 int rv_bristol_parse(const char *text, size_t len, int format, const uint8_t *expected_outputs, size_t n_expected, rv_op **ops,
                      size_t *n_ops, rv_bristol_info *info);
+/* host only, no GPU: the header lines alone, by the code rv_bristol_parse runs on them -- line 1, the Fashion / old-Bristol decision
+ * (for the ambiguous "2 a b" second line a look at the first gate line), the input and output counts, and the checks that need no
+ * gate: n_inputs > n_wires and n_outputs > n_wires (RV_E_WIRE_OOB), n_gates > len / 8 + 1 (RV_E_BAD_OP).  info receives n_gates,
+ * n_wires, n_inputs and n_outputs, its other fields 0; *gates_offset the offset of the byte behind the last header line, where the gate
+ * lines begin.  The return code is rv_bristol_parse's for the same header defect; gate lines do not concern it.  text[0, len) must
+ * reach the end of the first non-blank gate line (the look-ahead reads it), and len enters the n_gates check: pass the whole text
+ * where it is at hand.  RV_E_ARG: a null argument. */
+int rv_bristol_header(const char *text, size_t len, int format, rv_bristol_info *info, size_t *gates_offset);
+/* rv_bristol_parse on the context's GPU: d_ops receives exactly the records rv_bristol_parse returns for the same bytes
+ * and arguments, byte for byte (the leading Input ops, one Mul per MAND lane, the assertion pairs, zeroed reserved and padding bytes),
+ * *n_ops and *info the same counts, and the return code is rv_bristol_parse's for every byte string: that of the first bad gate line
+ * in line order, decided inside the line in the host parser's order.  On an error *n_ops is 0 and d_ops holds anything.
+ * text: text_on_device == 0, host memory, copied by the library into context-arena memory; otherwise memory of the context's device
+ * (no alignment asked; inside one allocation where the runtime can tell, RV_E_ARG otherwise, before anything is launched) -- the
+ * library copies down only the first bytes that hold four non-blank lines, for the header code.  expected_outputs is host memory.
+ * d_ops / cap_ops: cap_ops records in the memory of the context's device, rv_circuit_compile_device's conventions (8-byte aligned,
+ * inside one allocation; the caller keeps it).  d_ops == NULL or cap_ops < the record count: RV_E_ARG with *n_ops = the count and info
+ * filled, nothing written (rv_stream_finish_device's rule) -- so a sizing call (NULL, 0) validates the whole text, and returns the
+ * text's own code when it has one.  No allocation follows the header's claims: a few bytes may name 2^32 - 1 inputs, and the count
+ * is merely reported.  Order of decisions: arguments (RV_E_ARG); len >= 2^32 (RV_E_UNSUPPORTED); the header's code (RV_E_ARG for
+ * n_expected != n_outputs among them); the gate lines' code; more than 2^32 - 1 wires with the assertion temporaries
+ * (RV_E_UNSUPPORTED); capacity; the records.
+ * Work memory comes from the context arena and goes back before the call returns: 8 bytes per gate line the header names (at most
+ * len / 8 + 1 lines: about one byte per byte of text at the very most, a third of that for ordinary lines), 8 bytes per 4096 bytes
+ * of text, and the text itself (and n_expected bytes) when it comes from host memory.  Runs on the context's stream and
+ * synchronises it once, at the end (a device text: once more for the header bytes). */
+int rv_bristol_parse_device(rv_ctx *ctx, const char *text, size_t len, int text_on_device, int format, const uint8_t *expected_outputs /* host */,
+                            size_t n_expected, rv_op *d_ops, size_t cap_ops, size_t *n_ops, rv_bristol_info *info);
+/* the device parser's two tile sizes: out[0] = bytes of text per workgroup of the tile kernels, out[1] = gate lines per workgroup of
+ * the line kernels (the lengths the tests go around) */
+int rv_hook_bristol_tiles(uint32_t out[2]);
 
 /* ---- wire indices compacted by liveness -----------------------------------------
  * A stream's wire store is sized by the wire counts it begins with: one row per wire index.  An op list in SSA form (a Bristol file,

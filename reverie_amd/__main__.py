@@ -9,7 +9,8 @@ same `Ok(())` / `Err("Unverifiable Proof")` result lines.  Differences, stated p
   mcircuit-bincode`, reverie_amd/csrc/program.cpp) but is never chosen automatically.  By
   default this front end reads Bristol / Bristol Fashion text (README.md:14-16), or a raw
   little-endian array of 24-byte `rv_op` records (`--program-format rvops`).  `--expected-outputs-path` (text of 0/1) appends the output
-  assertions to a Bristol circuit (see rv_bristol_parse).
+  assertions to a Bristol circuit (see rv_bristol_parse).  `--parser device` parses the Bristol text on the GPU instead
+  (rv_bristol_parse_device: the same records, made in device memory).
 * proofs are the same bincode bytes.
 * verification is strict by default (`--reference-compat` restores the reference verifier's two unchecked
   conditions), and a rejected proof exits with status 1 (the reference prints the same
@@ -47,9 +48,29 @@ def load_program(path: str, fmt: str, expected_path=None):
     return prog, info["wire_counts"]
 
 
+def load_program_device(path: str, expected_path=None):
+    """--parser device: a Bristol file memory-mapped and parsed on the GPU (rv_bristol_parse_device) -> (a torch uint8 tensor [n_ops, 24]
+    of rv_op records in GPU memory, wire counts); the records are those `load_program` returns"""
+    import mmap
+
+    from . import bristol
+
+    exp = parse_witness(open(expected_path, "rb").read()) if expected_path else None
+    with open(path, "rb") as f:
+        size = f.seek(0, 2)
+        text = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size else b""  # (an empty file cannot be mapped)
+        ops, info = bristol.parse_device(text, expected_outputs=exp)
+    return ops, info["wire_counts"]
+
+
+def host_program(ops):
+    """a device op tensor copied to host memory as an OP_DTYPE array"""
+    return ops.cpu().numpy().reshape(-1).view(OP_DTYPE)
+
+
 def compact_program(prog, wc):
-    """--compact-wires: the program renumbered by liveness (rv_ops_compact_wires, on the host) and its new wire counts; the counts
-    before and after go to stderr"""
+    """--compact-wires: the program renumbered by liveness (rv_ops_compact_wires, on the host; --parser device's op tensor by
+    rv_ops_compact_wires_device, where it lies) and its new wire counts; the counts before and after go to stderr"""
     from .compact import compact_wires
 
     out, new_wc, _ = compact_wires(prog, wc)
@@ -88,6 +109,16 @@ def evaluate_clear(prog, witness):
     return v
 
 
+def device_circuit(ops, wc, compiler, **kw):
+    """the circuit of a device op tensor (--parser device): compiled where it lies with the bits --compiler names; --compiler host =
+    the ops are copied down and compiled by the host compiler"""
+    from .proof import Circuit
+
+    if compiler == "host":
+        return Circuit(host_program(ops), wc, **{k: v for k, v in kw.items() if k != "device_keep_wires"})
+    return Circuit.from_device_ops(ops, wc, device_z64=compiler in ("device-z64", "device-b2a"), device_b2a=compiler == "device-b2a", **kw)
+
+
 def evaluate_gpu(prog, wc, witness, compiler="host"):
     """`oneshot` on the GPU (rv_evaluate): any program without Random ops, GF(2), Z64 and B2A alike (the CLI's witness is
     GF(2) bits only, as the reference's).  Raises SystemExit naming the op index of the first failing AssertZero.
@@ -95,7 +126,9 @@ def evaluate_gpu(prog, wc, witness, compiler="host"):
     RV_COMPILE_KEEP_WIRES | RV_COMPILE_DEVICE_KEEP_WIRES (the whole-circuit evaluator's compile); the outcome is the same."""
     from .proof import Circuit
 
-    if compiler == "host":
+    if not isinstance(prog, np.ndarray):  # (--parser device: the op tensor)
+        circuit = device_circuit(prog, wc, compiler, **({} if compiler == "host" else {"keep_wires": True, "device_keep_wires": True}))
+    elif compiler == "host":
         circuit = Circuit(prog, wc)
     else:
         circuit = Circuit(prog, wc, keep_wires=True, device_compile=True, device_z64=compiler in ("device-z64", "device-b2a"),
@@ -106,7 +139,7 @@ def evaluate_gpu(prog, wc, witness, compiler="host"):
 
 
 def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, device_compile=False, device_z64=False, device_b2a=False,
-                    compact=False):
+                    compact=False, parser="host"):
     """`oneshot --evaluator stream`: the program evaluated in pieces with bounded device memory (rv_eval_stream_*), on the GPU like
     --evaluator gpu and with the same outcome.  An rvops file is read through a memory map, piece by piece; its wire counts come from
     one pass over the mapping.  compact (--compact-wires): the whole list is renumbered by liveness first (in host memory: 24 bytes
@@ -116,7 +149,12 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
     if fmt == "auto":
         fmt = "rvops" if program_path.endswith(".rvops") else "bristol"
     wit = np.ascontiguousarray(np.asarray(witness, dtype=np.uint8))
-    if fmt != "rvops":
+    if parser == "device" and fmt == "bristol":  # the op tensor is the one piece (compacted where it lies)
+        prog, wc = load_program_device(program_path, expected_path)
+        if compact:
+            prog, wc = compact_program(prog, wc)
+        compact, pieces = False, [prog]
+    elif fmt != "rvops":
         prog, wc = load_program(program_path, fmt, expected_path)
         pieces, n = [prog], len(prog)
     else:
@@ -144,7 +182,8 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
         used = 0
         for piece in pieces:
             se.feed(piece, wit[used:])  # (the CLI's witness is GF(2) bits: a piece consumes one per GF(2) Input op)
-            used += int(np.count_nonzero((piece["domain"] == 0) & (piece["opcode"] == 0)))
+            if isinstance(piece, np.ndarray):
+                used += int(np.count_nonzero((piece["domain"] == 0) & (piece["opcode"] == 0)))
         r = se.finish()
     finally:
         se.close()
@@ -187,6 +226,11 @@ def build_parser():
                          "always a SizeHint that grows a wire count, op-list errors, chains deeper than 2^16 rounds and "
                          "the deep, narrow circuits the host compiler recompiles with lazy sums still compile on the host); the proof bytes "
                          "and the outcome are the same")
+    ap.add_argument("--parser", default="host", choices=["host", "device"],
+                    help="Bristol programs in prove / verify / oneshot-zk and oneshot --evaluator gpu / stream: parse the text on the host "
+                         "(default) or on the GPU (rv_bristol_parse_device: the file is memory-mapped, the op list is made in device memory "
+                         "and, with --compiler device*, compiled there; --compact-wires then renumbers it there too); the proof bytes and "
+                         "the outcome are the same")
     ap.add_argument("--compact-wires", action="store_true",
                     help="prove / verify / oneshot-zk and oneshot --evaluator stream: renumber the program's wires by liveness first "
                          "(rv_ops_compact_wires), so that an SSA-numbered program needs a wire per live value instead of one per gate; "
@@ -213,20 +257,33 @@ def main(argv=None) -> int:
         return 0
     if a.compact_wires and a.operation == "oneshot" and a.evaluator != "stream":
         ap.error("--compact-wires with --operation oneshot needs --evaluator stream (the other evaluators keep no wire store)")
+    fmt = a.program_format
+    if fmt == "auto":
+        fmt = "rvops" if a.program_path.endswith(".rvops") else "bristol"
+    device_parser = a.parser == "device" and fmt == "bristol"
+    if device_parser and a.operation == "oneshot":
+        if a.evaluator == "host":
+            ap.error("--parser device leaves the program in GPU memory: --evaluator host cannot read it (use gpu or stream)")
+        if a.evaluator == "auto":
+            a.evaluator = "gpu"
     if a.operation == "oneshot" and a.evaluator == "stream":
         print("Evaluating program in cleartext")
         evaluate_stream(a.program_path, a.program_format, a.expected_outputs_path, parse_witness(open(a.witness_path, "rb").read()),
                         a.max_chunk_ops, device_compile=a.compiler != "host", **({"device_z64": True} if a.compiler in ("device-z64", "device-b2a") else {}),
-                        **({"device_b2a": True} if a.compiler == "device-b2a" else {}), **({"compact": True} if a.compact_wires else {}))
+                        **({"device_b2a": True} if a.compiler == "device-b2a" else {}), **({"compact": True} if a.compact_wires else {}),
+                        **({"parser": "device"} if device_parser else {}))
         print("()")
         return 0
-    prog, wc = load_program(a.program_path, a.program_format, a.expected_outputs_path)
+    if device_parser:
+        prog, wc = load_program_device(a.program_path, a.expected_outputs_path)
+    else:
+        prog, wc = load_program(a.program_path, a.program_format, a.expected_outputs_path)
     if a.compact_wires:
         prog, wc = compact_program(prog, wc)
     if a.operation == "oneshot":
         print("Evaluating program in cleartext")
         wit = parse_witness(open(a.witness_path, "rb").read())
-        if use_gpu_evaluator(prog, a.evaluator):
+        if device_parser or use_gpu_evaluator(prog, a.evaluator):
             evaluate_gpu(prog, wc, wit, a.compiler)
         else:
             evaluate_clear(prog, wit)
@@ -234,7 +291,10 @@ def main(argv=None) -> int:
         return 0
     from .proof import Circuit, Proof
 
-    circuit = Circuit(prog, wc, device_compile=a.compiler != "host", device_z64=a.compiler in ("device-z64", "device-b2a"), device_b2a=a.compiler == "device-b2a")
+    if device_parser:
+        circuit = device_circuit(prog, wc, a.compiler)
+    else:
+        circuit = Circuit(prog, wc, device_compile=a.compiler != "host", device_z64=a.compiler in ("device-z64", "device-b2a"), device_b2a=a.compiler == "device-b2a")
     if a.operation in ("prove", "oneshot-zk"):
         wit = parse_witness(open(a.witness_path, "rb").read())
         print("Evaluating program in ~zero knowledge~")

@@ -113,6 +113,7 @@ SYMBOLS = [
     "rv_hook_extract_bits", "rv_hook_extract_from_bits", "rv_hook_pack_corr_all", "rv_hook_unpack_bits", "rv_hook_extract64", "rv_hook_unpack64",
     "rv_hook_compile_levels", "rv_hook_circuit_levels", "rv_hook_interp_launches",
     "rv_ops_compact_wires", "rv_ops_compact_wires_device",
+    "rv_bristol_header", "rv_bristol_parse_device", "rv_hook_bristol_tiles",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -192,6 +193,10 @@ ARGTYPES = {
     # wire indices compacted by liveness
     "rv_ops_compact_wires": [_P, _Z, _Z, _Z, _P, C.POINTER(CompactInfo)],
     "rv_ops_compact_wires_device": [_P, _P, _Z, _Z, _Z, _P, C.POINTER(CompactInfo)],
+    # the Bristol parser on the GPU
+    "rv_bristol_header": [_P, _Z, C.c_int, C.POINTER(BristolInfo), C.POINTER(C.c_size_t)],
+    "rv_bristol_parse_device": [_P, _P, _Z, C.c_int, C.c_int, _P, _Z, _P, _Z, C.POINTER(C.c_size_t), C.POINTER(BristolInfo)],
+    "rv_hook_bristol_tiles": [C.POINTER(C.c_uint32)],
 }
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "b3.h"
+#include "bristol_dev.h"
 #include "compile.h"
 #include "compact_dev.h"
 #include "compile_dev.h"
@@ -1589,3 +1590,4 @@ extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
 #include "stream_wdev.inc"
 #include "witness_dev.inc"
 #include "compact.inc"
+#include "bristol.inc"

@@ -77,11 +77,12 @@ extern "C" int rv_bristol_parse(const char* text, size_t len, int format, const 
     }
 }
 
-static int parse_impl(const char* text, size_t len, int format, const uint8_t* expected_outputs, size_t n_expected, rv_op** ops,
-                      size_t* n_ops, rv_bristol_info* info) {
-    if (!text || !ops || !n_ops) return RV_E_ARG;
-    *ops = nullptr;
-    *n_ops = 0;
+// The header lines (shared by rv_bristol_parse, rv_bristol_header and rv_bristol_parse_device): line 1, the Fashion / old-Bristol
+// decision with its look at the first gate line, the input / output counts and the checks that need no gate.  text[0, len) must reach
+// the end of the first non-blank gate line; full_len is the length of the whole text (the bound on n_gates).  On RV_OK bi holds the
+// four header counts (the rest 0) and *gates_offset the offset just behind the last header line.
+static int header_impl(const char* text, size_t len, size_t full_len, int format, bool has_expected, size_t n_expected, rv_bristol_info& bi,
+                       size_t& gates_offset) {
     Tok t{text, text + len};
     bool too_big = false;  // a number of 2^32 or more was read: RV_E_UNSUPPORTED rather than "malformed"
 #define BAD() return (too_big ? RV_E_UNSUPPORTED : RV_E_BAD_OP)
@@ -122,16 +123,44 @@ static int parse_impl(const char* text, size_t len, int format, const uint8_t* e
     }
     if (n_in > n_wires || n_out > n_wires) return RV_E_WIRE_OOB;
     // the assertions read expected_outputs[0 .. n_out): the caller states how many it passed, checked before any is read
-    if (expected_outputs && n_expected != n_out) return RV_E_ARG;
-
-    rv_bristol_info bi;
+    if (has_expected && n_expected != n_out) return RV_E_ARG;
+    if (n_gates > full_len / 8 + 1) BAD();  // every gate line needs at least 8 characters
     memset(&bi, 0, sizeof bi);
     bi.n_gates = n_gates;
     bi.n_wires = n_wires;
     bi.n_inputs = n_in;
     bi.n_outputs = n_out;
+    gates_offset = (size_t)(t.p - text);
+    return RV_OK;
+}
+
+// (bristol.inc: the device parser's header step; not part of the public header)
+extern "C" int rv_internal_bristol_header(const char* text, size_t len, size_t full_len, int format, int has_expected, size_t n_expected,
+                                          rv_bristol_info* info, size_t* gates_offset) {
+    try {
+        return header_impl(text, len, full_len, format, has_expected != 0, n_expected, *info, *gates_offset);
+    } catch (...) {
+        return RV_E_NOMEM;
+    }
+}
+
+extern "C" int rv_bristol_header(const char* text, size_t len, int format, rv_bristol_info* info, size_t* gates_offset) {
+    if (!text || !info || !gates_offset) return RV_E_ARG;
+    return rv_internal_bristol_header(text, len, len, format, 0, 0, info, gates_offset);
+}
+
+static int parse_impl(const char* text, size_t len, int format, const uint8_t* expected_outputs, size_t n_expected, rv_op** ops,
+                      size_t* n_ops, rv_bristol_info* info) {
+    if (!text || !ops || !n_ops) return RV_E_ARG;
+    *ops = nullptr;
+    *n_ops = 0;
+    rv_bristol_info bi;
+    size_t gates_offset = 0;
+    if (const int rc = header_impl(text, len, len, format, expected_outputs != nullptr, n_expected, bi, gates_offset)) return rc;
+    const uint64_t n_gates = bi.n_gates, n_wires = bi.n_wires, n_in = bi.n_inputs, n_out = bi.n_outputs;
+    Tok t{text + gates_offset, text + len};
+    bool too_big = false;
     std::vector<rv_op> out;
-    if (n_gates > len / 8 + 1) BAD();  // every gate line needs at least 8 characters
     // (a header may claim billions of input wires in a few bytes of text: reserve what the TEXT can justify, let the
     // vector grow for the rest -- a failed allocation is caught by the caller and reported as RV_E_NOMEM)
     out.reserve((size_t)std::min<uint64_t>(n_in + n_gates + 2 * n_out, (uint64_t)len + 4096));
