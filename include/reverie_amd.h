@@ -988,6 +988,22 @@ int rv_hook_circuit_levels(const rv_circuit *c, int32_t *out, size_t cap, size_t
  * batched full, batched narrow per-gate, batched narrow class-loop, batched LDS; columns = the kernel's mode PROVE, PROVE_V, VERIFY,
  * VERIFY_C.  reset != 0: the counters return to zero as they are read. */
 int rv_hook_interp_launches(uint64_t counts[][4], int reset);
+/* Launches of the Z64 level executors this process has issued so far, counted by the host launchers (one that returns early -- an
+ * empty level, no quad group -- counts nothing), four rows of two: rows = k_z64_fused in blocks of 16 quad words, k_z64_fused in
+ * blocks of 8, k_interp64, k_interp64_b (batches); columns = prover, verifier.  reset != 0: the counters return to zero as they are
+ * read. */
+int rv_hook_interp64_launches(uint64_t counts[][2], int reset);
+/* The grid of one k_z64_fused launch (host only; the function the launcher calls): for a level of n_mul Mul, n_lin linear and
+ * n_oth other gates over n_qg quad groups of qw (16 or 8) quad words on `cus` compute units (0: what the launcher uses on this
+ * machine, 256 where no device answers) -- out = chunks (workgroups per quad group; 0: nothing is launched), mul_per, lin_per,
+ * oth_per (a workgroup's share of each class), lin_bias. */
+int rv_hook_z64_fused_grid(uint32_t qw, uint32_t n_qg, uint32_t cus, uint32_t n_mul, uint32_t n_lin, uint32_t n_oth, uint32_t out[5]);
+/* The fused Z64 level table of a program (host only; the compile of rv_hook_compile_levels, then the function the upload path
+ * calls).  out: four uint32 per level, the first `cap` levels -- mul0, mul1, lin1, oth1: Mul gates [mul0, mul1), Add .. MulConst
+ * [mul1, lin1), Input / AssertZero / Const [lin1, oth1).  *eligible: 0 the circuit takes the fused path; 1 it holds a Random or
+ * B2A gate (no table: *n_levels = 0); 2 a Mul's mask pair straddles cipher blocks; 3 more than 64 Input block runs; 4 no Z64 gate. */
+int rv_hook_z64_fused_levels(const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, uint32_t *out, size_t cap,
+                             size_t *n_levels, int *eligible);
 /* The two gate-stream compilers against each other (host only): the program is compiled by the sequential compiler and by the
  * parallel one with `threads` host threads (>= 2), whatever its size, and the results are compared field by field.
  * *diff = 0: identical; > 0: a number naming the first differing table (csrc/compile_par.cpp, compiled_diff); -1: the parallel

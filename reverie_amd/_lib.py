@@ -112,6 +112,7 @@ SYMBOLS = [
     "rv_hook_stream_traffic", "rv_hook_stream_verify_device_paths", "rv_hook_stream_wit_sums",
     "rv_hook_extract_bits", "rv_hook_extract_from_bits", "rv_hook_pack_corr_all", "rv_hook_unpack_bits", "rv_hook_extract64", "rv_hook_unpack64",
     "rv_hook_compile_levels", "rv_hook_circuit_levels", "rv_hook_interp_launches",
+    "rv_hook_interp64_launches", "rv_hook_z64_fused_grid", "rv_hook_z64_fused_levels",
     "rv_ops_compact_wires", "rv_ops_compact_wires_device",
     "rv_bristol_header", "rv_bristol_parse_device", "rv_hook_bristol_tiles",
 ]
@@ -190,6 +191,9 @@ ARGTYPES = {
     "rv_hook_compile_levels": [_P, _Z, _Z, _Z, C.c_uint32, _P, _Z, C.POINTER(C.c_size_t)],
     "rv_hook_circuit_levels": [_P, _P, _Z, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "rv_hook_interp_launches": [_P, C.c_int],
+    "rv_hook_interp64_launches": [_P, C.c_int],
+    "rv_hook_z64_fused_grid": [C.c_uint32] * 6 + [C.POINTER(C.c_uint32)],
+    "rv_hook_z64_fused_levels": [_P, _Z, _Z, _Z, C.c_uint32, _P, _Z, C.POINTER(C.c_size_t), C.POINTER(C.c_int)],
     # wire indices compacted by liveness
     "rv_ops_compact_wires": [_P, _Z, _Z, _Z, _P, C.POINTER(CompactInfo)],
     "rv_ops_compact_wires_device": [_P, _P, _Z, _Z, _Z, _P, C.POINTER(CompactInfo)],

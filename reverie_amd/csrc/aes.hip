@@ -972,19 +972,23 @@ __global__ __launch_bounds__(512, 2) void k_z64_fused(const Gate64* __restrict__
 uint32_t z64_fused_qw(uint32_t NQ) { return NQ >= 16 && NQ % 16 == 0 ? 16u : (NQ >= 8 && NQ % 8 == 0 ? 8u : 0u); }
 bool z64_fused_supports(uint32_t NQ) { return z64_fused_qw(NQ) != 0; }
 
-template <int QW>
-static void launch_z64_fused_qw(hipStream_t st, const Gate64* d_gates, const Z64FLevel& lv, const Z64FParams& p) {
-    constexpr uint32_t JW = 64 / QW, STEP = 8 * JW;
+// The compute units the fused launches are planned for: the current device's, 256 where no device answers.
+uint32_t z64_fused_cus() {
     static const uint32_t cus = [] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
         return (uint32_t)n;
     }();
+    return cus;
+}
+
+// The grid of one fused level launch, a pure function of the level's class counts, the launch's quad groups and the compute units
+// (rv_hook_z64_fused_grid shows it to the tests); chunks == 0: nothing to launch.
+Z64FGrid z64_fused_grid(uint32_t qw, uint32_t n_qg, uint32_t cus, uint32_t n_mul, uint32_t n_lin, uint32_t n_oth) {
+    const uint32_t JW = 64 / qw, STEP = 8 * JW;
     // a Mul step (cipher batch + rows) in linear steps (rows only): what the wavefronts with one Mul step more get fewer of
     constexpr uint32_t lin_bias = 3;  // (measured 0 / 3 / 5 / 8: 38.6 / 38.3 / 38.9 / 38.8 ms)
-    const uint32_t n_qg = p.qgn;  // (quad groups of this launch)
-    const uint32_t n_mul = lv.mul1 - lv.mul0, n_lin = lv.lin1 - lv.mul1, n_oth = lv.oth1 - lv.lin1;
-    if (!(n_mul + n_lin + n_oth) || !n_qg) return;
+    if (!((uint64_t)n_mul + n_lin + n_oth) || !n_qg) return Z64FGrid{0, 0, 0, 0, lin_bias};
     auto up = [](uint64_t x, uint64_t m) { return (x + m - 1) / m * m; };
     // one generation of workgroups, one per compute unit (a workgroup owns it: 88 KiB of round keys, all registers), each with
     // an equal share of the level in whole wavefront steps; a level with little cipher work still gets enough workgroups for its
@@ -993,12 +997,20 @@ static void launch_z64_fused_qw(hipStream_t st, const Gate64* d_gates, const Z64
     uint64_t chunks = n_mul ? std::min<uint64_t>(per_qg, ((uint64_t)n_mul + STEP - 1) / STEP) : 1;
     const uint64_t mem_chunks = std::min<uint64_t>(((uint64_t)n_lin + n_oth + 2 * STEP - 1) / (2 * STEP), per_qg * (n_mul ? 1u : 4u));
     chunks = std::max<uint64_t>(std::max(chunks, mem_chunks), 1);
-    const uint32_t mul_per = (uint32_t)up((n_mul + chunks - 1) / chunks, JW), lin_per = (uint32_t)up((n_lin + chunks - 1) / chunks, JW),
-                   oth_per = (uint32_t)up((n_oth + chunks - 1) / chunks, STEP);
+    return Z64FGrid{(uint32_t)chunks, (uint32_t)up((n_mul + chunks - 1) / chunks, JW), (uint32_t)up((n_lin + chunks - 1) / chunks, JW),
+                    (uint32_t)up((n_oth + chunks - 1) / chunks, STEP), lin_bias};
+}
+
+template <int QW>
+static void launch_z64_fused_qw(hipStream_t st, const Gate64* d_gates, const Z64FLevel& lv, const Z64FParams& p) {
+    const uint32_t n_qg = p.qgn;  // (quad groups of this launch)
+    const Z64FGrid g = z64_fused_grid(QW, n_qg, z64_fused_cus(), lv.mul1 - lv.mul0, lv.lin1 - lv.mul1, lv.oth1 - lv.lin1);
+    if (!g.chunks) return;
+    count_interp64_launch(QW == 16 ? IX64_FUSED16 : IX64_FUSED8, p.omit != nullptr);
     if (p.omit)
-        hipLaunchKernelGGL((k_z64_fused<QW, true>), dim3((unsigned)(chunks * n_qg)), dim3(512), 0, st, d_gates, lv, mul_per, lin_per, oth_per, lin_bias, p);
+        hipLaunchKernelGGL((k_z64_fused<QW, true>), dim3((unsigned)((uint64_t)g.chunks * n_qg)), dim3(512), 0, st, d_gates, lv, g.mul_per, g.lin_per, g.oth_per, g.lin_bias, p);
     else
-        hipLaunchKernelGGL((k_z64_fused<QW, false>), dim3((unsigned)(chunks * n_qg)), dim3(512), 0, st, d_gates, lv, mul_per, lin_per, oth_per, lin_bias, p);
+        hipLaunchKernelGGL((k_z64_fused<QW, false>), dim3((unsigned)((uint64_t)g.chunks * n_qg)), dim3(512), 0, st, d_gates, lv, g.mul_per, g.lin_per, g.oth_per, g.lin_bias, p);
 }
 void launch_z64_fused(hipStream_t st, const Gate64* d_gates, const Z64FLevel& lv, const Z64FParams& p) {
     if (z64_fused_qw(p.NQ) == 16)

@@ -713,10 +713,19 @@ static bool z64_fused_on() {
     return !e || atoi(e) != 0;
 }
 // the circuit's Z64 gates grouped Mul | linear | other inside every level, the level table, and the cipher block runs whose rows
-// are Input masks.  false: not eligible (a Random or B2A gate, a Mul whose two masks straddle cipher blocks, too many runs)
-static bool build_z64_fused(const Compiled& cc, std::vector<Gate64>& sorted, std::vector<Z64FLevel>& levels, std::vector<std::pair<uint64_t, uint64_t>>& runs) {
+// are Input masks.  false: not eligible -- *why (nullable) names the rule: Z64F_GATE a Random or B2A gate, Z64F_ODD_M a Mul whose two
+// masks straddle cipher blocks, Z64F_RUNS more than 64 Input block runs (the first that applies, in this order; Z64F_NONE: no Z64
+// level at all).  With levels_anyway the level table is built for a circuit that is not eligible too, unless a gate has no class
+// (rv_hook_z64_fused_levels).
+enum Z64FWhy : int { Z64F_OK = 0, Z64F_GATE = 1, Z64F_ODD_M = 2, Z64F_RUNS = 3, Z64F_NONE = 4 };
+static bool build_z64_fused(const Compiled& cc, std::vector<Gate64>& sorted, std::vector<Z64FLevel>& levels, std::vector<std::pair<uint64_t, uint64_t>>& runs,
+                            int* why = nullptr, bool levels_anyway = false) {
+    int why_{};
+    if (!why) why = &why_;
+    *why = Z64F_NONE;
     const size_t n_levels = cc.level_start64.empty() ? 0 : cc.level_start64.size() - 1;
     if (!n_levels || cc.gates64.size() >= (1ull << 32)) return false;
+    *why = Z64F_OK;
     auto cls = [](uint32_t op) -> int {
         switch (op) {
         case G64_MUL: return 0;
@@ -728,8 +737,14 @@ static bool build_z64_fused(const Compiled& cc, std::vector<Gate64>& sorted, std
     std::vector<uint64_t> in_blocks;
     for (const Gate64& g : cc.gates64) {
         const int k = cls(g.op);
-        if (k < 0) return false;
-        if (g.op == G64_MUL && (g.m & 1)) return false;
+        if (k < 0) {
+            *why = Z64F_GATE;
+            return false;
+        }
+        if (g.op == G64_MUL && (g.m & 1) && *why == Z64F_OK) {
+            *why = Z64F_ODD_M;
+            if (!levels_anyway) return false;
+        }
         if (g.op == G64_INPUT) in_blocks.push_back(g.m >> 1);
     }
     std::sort(in_blocks.begin(), in_blocks.end());
@@ -741,7 +756,8 @@ static bool build_z64_fused(const Compiled& cc, std::vector<Gate64>& sorted, std
         else
             runs.emplace_back(b, 1);
     }
-    if (runs.size() > 64) return false;
+    if (runs.size() > 64 && *why == Z64F_OK) *why = Z64F_RUNS;
+    if (*why != Z64F_OK && !levels_anyway) return false;
     sorted.resize(cc.gates64.size());
     levels.assign(n_levels, Z64FLevel{});
     for (size_t l = 0; l < n_levels; l++) {
@@ -752,7 +768,7 @@ static bool build_z64_fused(const Compiled& cc, std::vector<Gate64>& sorted, std
         levels[l] = Z64FLevel{(uint32_t)lo, (uint32_t)at[1], (uint32_t)at[2], (uint32_t)hi};
         for (uint64_t i = lo; i < hi; i++) sorted[at[cls(cc.gates64[i].op)]++] = cc.gates64[i];
     }
-    return true;
+    return *why == Z64F_OK;
 }
 
 static size_t scratch_bytes_for(const Compiled& cc, uint32_t R) {

@@ -505,3 +505,45 @@ extern "C" int rv_hook_interp_launches(uint64_t counts[][4], int reset) {
     interp_launch_counts(counts, reset != 0);
     return RV_OK;
 }
+
+// ------------------------------------------------------------------------------------
+// Which executor runs a Z64 level (aes.hip: k_z64_fused, z64.hip: k_interp64 / k_interp64_b): the launch counters, the fused
+// launcher's grid arithmetic and the fused level table of a program with the reason a circuit is not eligible.
+// ------------------------------------------------------------------------------------
+extern "C" int rv_hook_interp64_launches(uint64_t counts[][2], int reset) {
+    if (!counts) return RV_E_ARG;
+    interp64_launch_counts(counts, reset != 0);
+    return RV_OK;
+}
+
+extern "C" int rv_hook_z64_fused_grid(uint32_t qw, uint32_t n_qg, uint32_t cus, uint32_t n_mul, uint32_t n_lin, uint32_t n_oth, uint32_t out[5]) {
+    if (!out || (qw != 16 && qw != 8)) return RV_E_ARG;
+    const Z64FGrid g = z64_fused_grid(qw, n_qg, cus ? cus : z64_fused_cus(), n_mul, n_lin, n_oth);
+    out[0] = g.chunks, out[1] = g.mul_per, out[2] = g.lin_per, out[3] = g.oth_per, out[4] = g.lin_bias;
+    return RV_OK;
+}
+
+extern "C" int rv_hook_z64_fused_levels(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, uint32_t* out, size_t cap,
+                                        size_t* n_levels, int* eligible) {
+    if (!n_levels || !eligible || (cap && !out) || (n_ops && !ops) || (flags & ~RV_COMPILE_WHOLE_PROVER)) return RV_E_ARG;
+    try {
+        Compiled cc;
+        const int rc = compile_ops(ops, n_ops, z64_wires, gf2_wires, cc, nullptr, ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0);
+        if (rc) return rc;
+        std::vector<Gate64> sorted;
+        std::vector<Z64FLevel> levels;
+        std::vector<std::pair<uint64_t, uint64_t>> runs;
+        int why = Z64F_NONE;
+        build_z64_fused(cc, sorted, levels, runs, &why, true);
+        *eligible = why;
+        *n_levels = levels.size();
+        for (size_t l = 0; l < levels.size() && l < cap; l++) {
+            uint32_t* o = out + 4 * l;
+            o[0] = levels[l].mul0, o[1] = levels[l].mul1, o[2] = levels[l].lin1, o[3] = levels[l].oth1;
+        }
+        return RV_OK;
+    } catch (...) {
+        g_last_error = "out of host memory";
+        return RV_E_NOMEM;
+    }
+}

@@ -333,6 +333,25 @@ struct Z64FParams {
     const uint64_t* sup_rec;
     uint32_t sup_r;
 };
+// The grid of one fused level launch (aes.hip: z64_fused_grid): `chunks` workgroups per quad group, each with mul_per Mul, lin_per
+// linear and oth_per other gates of the level (whole wavefront steps of JW = 64 / qw gates; oth_per whole workgroup steps of 8 JW);
+// lin_bias: the linear steps a wavefront with one Mul step more takes fewer of.  chunks == 0: an empty level or no quad group.
+struct Z64FGrid {
+    uint32_t chunks, mul_per, lin_per, oth_per, lin_bias;
+};
+Z64FGrid z64_fused_grid(uint32_t qw, uint32_t n_qg, uint32_t cus, uint32_t n_mul, uint32_t n_lin, uint32_t n_oth);
+uint32_t z64_fused_cus();  // the compute units the launcher plans for (256 where no device answers)
+// rv_hook_interp64_launches: the launches of the Z64 level executors, counted on the host by the launchers themselves (a launcher
+// that returns early counts nothing); one column for the prover, one for the verifier
+enum Interp64Exec : int {
+    IX64_FUSED16 = 0,  // k_z64_fused<16, ..>
+    IX64_FUSED8,       // k_z64_fused<8, ..>
+    IX64_INTERP,       // k_interp64
+    IX64_INTERP_B,     // k_interp64_b
+    IX64_COUNT
+};
+void count_interp64_launch(int exec, bool verify);
+void interp64_launch_counts(uint64_t out[][2], bool reset);
 bool z64_fused_supports(uint32_t NQ);
 uint32_t z64_fused_qw(uint32_t NQ);  // quad words per workgroup block of that path for rows of NQ quad words (16 or 8; 0: not taken)
 void launch_z64_fused(hipStream_t st, const Gate64* d_gates, const Z64FLevel& lv, const Z64FParams& p);

@@ -10,6 +10,7 @@
 // repetition; reconstruct = a local add + 2-step shuffle-add inside the 4-lane group.  A gate occupies
 // R*4 lanes (16 wavefronts at R = 256).
 #include <algorithm>
+#include <atomic>
 
 #include "b3.h"
 #include "internal.h"
@@ -81,8 +82,17 @@ __global__ __launch_bounds__(256) void k_interp64_b(const Gate64* __restrict__ g
 #include "z64_interp.inc"
 }
 
+static std::atomic<uint64_t> g_interp64_launches[IX64_COUNT][2];
+void count_interp64_launch(int exec, bool verify) { g_interp64_launches[exec][verify ? 1 : 0].fetch_add(1, std::memory_order_relaxed); }
+void interp64_launch_counts(uint64_t out[][2], bool reset) {
+    for (int e = 0; e < IX64_COUNT; e++)
+        for (int m = 0; m < 2; m++)
+            out[e][m] = reset ? g_interp64_launches[e][m].exchange(0, std::memory_order_relaxed) : g_interp64_launches[e][m].load(std::memory_order_relaxed);
+}
+
 void launch_interp64(hipStream_t st, int mode, const Gate64* d_gates, uint32_t lo, uint32_t hi, const Interp64Params& p) {
     if (hi <= lo) return;
+    count_interp64_launch(IX64_INTERP, mode != MODE_PROVE);
     const uint64_t S2 = (uint64_t)p.R * 4;  // lanes per gate
     const uint64_t want = (uint64_t)(hi - lo) * S2;
     uint64_t blocks = (want + 255) / 256;
@@ -98,6 +108,7 @@ void launch_interp64(hipStream_t st, int mode, const Gate64* d_gates, uint32_t l
 // whole launch keeps to the single launch's 8 192 workgroups: a level of a few gates fills the chip only through the batch.
 void launch_interp64_batched(hipStream_t st, int mode, const Gate64* d_gates, uint32_t lo, uint32_t hi, const Interp64Params* d_pp, uint32_t batch) {
     if (hi <= lo || !batch) return;
+    count_interp64_launch(IX64_INTERP_B, mode != MODE_PROVE);
     const uint64_t S2 = (uint64_t)RV_TOTAL_REPS * 4;  // lanes per gate
     const uint64_t bpw = S2 / 256;                     // workgroups per worker
     uint64_t workers = hi - lo;

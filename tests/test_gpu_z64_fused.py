@@ -11,7 +11,12 @@ others at 12 031, 9 000, 3 511, 2 531, 1 531, 731, 531 and below; the random pro
 the carry of counter byte 15 into byte 14 (block 255 -> 256) is crossed by most of them, but counter byte 13 stays 0 everywhere in
 this file: blocks from 65 536 up (32 768 Muls) are reached through this kernel only by the 10^5-Mul proof of
 tests/test_gpu_parity.py::test_z64_mid_size_vs_oracle_and_full_size_round_trip (against the oracle) and its 10^6-Mul round trip
-(prover against verifier only), and the last legal counter by nothing."""
+(prover against verifier only), and the last legal counter by nothing.  (Counter bytes 13 and up are out of reach of small
+circuits: they need 65 536 Mul gates or more.)
+
+Level shapes.  The circuits here come from generators that do not control what a level holds (circuits.layered_z64: about half Mul,
+half Add per layer; random_z64).  tests/test_gpu_level_classes64.py builds levels class by class and value by value instead -- every
+split of the launch grid and of the wavefront deal, step remainders, operand forms, edge values -- and asserts which executor ran."""
 import numpy as np
 import pytest
 
