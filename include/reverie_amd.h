@@ -899,6 +899,44 @@ int rv_ops_compact_wires_device(rv_ctx *ctx, const rv_op *d_ops, size_t n_ops, s
  * library-allocated (rv_free). */
 int rv_program_from_bincode(const uint8_t *data, size_t len, rv_op **ops, size_t *n_ops);
 int rv_program_to_bincode(const rv_op *ops, size_t n_ops, uint8_t **data, size_t *len);
+/* The same two on the context's GPU: a program file read into, and written from, op records in device memory.  The
+ * host pair above stays the definition and needs no GPU; the record layout both device calls read is one table
+ * (csrc/bincode_dev.h), with the variant order recalled above -- so nothing selects this format automatically here either. */
+typedef struct rv_program_info {
+    uint64_t n_ops;                /* the vector's length */
+    uint64_t bytes;                /* offset behind the last record read: bytes after it were not looked at */
+    uint64_t z64_wires, gf2_wires; /* mcircuit::largest_wires: what reverie_amd.ops.largest_wires returns for the records */
+    uint64_t n_gf2, n_z64, n_b2a, n_sizehint;
+} rv_program_info;
+/* rv_program_from_bincode for bytes the GPU parses: d_ops receives exactly the records rv_program_from_bincode returns for the same
+ * bytes, byte for byte (reserved and unused fields zero), *n_ops the same count, and the return code is rv_program_from_bincode's
+ * for every byte string: len < 8 or a count above (len - 8) / 16 is RV_E_BAD_OP (nothing is allocated or launched by what the count
+ * claims); then the code of the first of the `count` records that has one, decided inside the record in the host's order (an unknown
+ * domain or opcode, a bool above 1, a record that does not end inside len: RV_E_BAD_OP; else a wire field above 2^32 - 1:
+ * RV_E_UNSUPPORTED); fewer than `count` records before len: RV_E_BAD_OP.  Bytes behind record count - 1 are never judged.  A count of 0
+ * is RV_OK, nothing is written and no capacity is asked for.  On an error *n_ops is 0 and d_ops holds anything.
+ * data: data_on_device == 0, host memory, copied by the library into context-arena memory; otherwise memory of the context's device
+ * (no alignment asked; inside one allocation where the runtime can tell, RV_E_ARG otherwise, before anything is launched).  No byte
+ * outside data[0, len) is read.  d_ops / cap_ops: rv_circuit_compile_device's conventions (8-byte aligned, inside one allocation of
+ * the context's device; the caller keeps it).  d_ops == NULL or cap_ops < count: RV_E_ARG with *n_ops = the count and info filled,
+ * nothing written -- after the whole input has been validated: a sizing call (NULL, 0) on bad bytes returns the bytes' own code.
+ * Order of decisions: arguments (RV_E_ARG); len >= 2^32 (RV_E_UNSUPPORTED); the header; the records; capacity; writing.  info may
+ * be NULL.
+ * Work memory comes from the context arena and goes back before the call returns: 72 bytes per 4096 bytes of data (the tiles' entry
+ * maps: 1.8 % of len), 264 bytes per 2^20 bytes, some 3 KiB of counters, and the data itself when it comes from host memory.  Runs on
+ * the context's stream and synchronises it once, at the end (device data: once more for the 8 header bytes). */
+int rv_program_from_bincode_device(rv_ctx *ctx, const uint8_t *data, size_t len, int data_on_device, rv_op *d_ops, size_t cap_ops,
+                                   size_t *n_ops, rv_program_info *info /* may be NULL */);
+/* rv_program_to_bincode for records in device memory: d_out receives the bytes rv_program_to_bincode writes for the same records
+ * (GF(2) immediates as imm & 1), and the return code is its code: reserved != 0, an unknown domain or opcode -> RV_E_BAD_OP.
+ * d_ops as above (n_ops records); d_out / cap: memory of the context's device, no alignment asked.  d_out == NULL or cap < the
+ * file's length: RV_E_ARG with *len = the length, nothing written.  A file of 2^32 bytes or more: RV_E_UNSUPPORTED.  Work memory
+ * (4 bytes per record) comes from the context arena and goes back before the call returns; one synchronisation of the context's
+ * stream, at the end. */
+int rv_program_to_bincode_device(rv_ctx *ctx, const rv_op *d_ops, size_t n_ops, uint8_t *d_out, size_t cap, size_t *len);
+/* out[0] = bytes of the file per tile of the walk and decode kernels, tiles counted from data[0] whatever its address; out[1] =
+ * tiles per workgroup of the composing scan (the lengths the tests go around) */
+int rv_hook_bincode_tiles(uint32_t out[2]);
 
 /* ---- parity-test hooks: each mirrors one reference function so tests can compare the
  * HIP path with the oracle piecewise ---- */

@@ -10,7 +10,8 @@ same `Ok(())` / `Err("Unverifiable Proof")` result lines.  Differences, stated p
   default this front end reads Bristol / Bristol Fashion text (README.md:14-16), or a raw
   little-endian array of 24-byte `rv_op` records (`--program-format rvops`).  `--expected-outputs-path` (text of 0/1) appends the output
   assertions to a Bristol circuit (see rv_bristol_parse).  `--parser device` parses the Bristol text on the GPU instead
-  (rv_bristol_parse_device: the same records, made in device memory).
+  (rv_bristol_parse_device: the same records, made in device memory), and reads an mcircuit-bincode file there too
+  (rv_program_from_bincode_device).
 * proofs are the same bincode bytes.
 * verification is strict by default (`--reference-compat` restores the reference verifier's two unchecked
   conditions), and a rejected proof exits with status 1 (the reference prints the same
@@ -48,18 +49,23 @@ def load_program(path: str, fmt: str, expected_path=None):
     return prog, info["wire_counts"]
 
 
-def load_program_device(path: str, expected_path=None):
-    """--parser device: a Bristol file memory-mapped and parsed on the GPU (rv_bristol_parse_device) -> (a torch uint8 tensor [n_ops, 24]
-    of rv_op records in GPU memory, wire counts); the records are those `load_program` returns"""
+def load_program_device(path: str, expected_path=None, fmt: str = "bristol"):
+    """--parser device: a Bristol file (rv_bristol_parse_device) or an mcircuit-bincode file (rv_program_from_bincode_device)
+    memory-mapped and parsed on the GPU -> (a torch uint8 tensor [n_ops, 24] of rv_op records in GPU memory, wire counts); the records
+    are those `load_program` returns, and the bincode reader's wire counts come from its own pass (rv_program_info), not from
+    `largest_wires` on the host"""
     import mmap
 
-    from . import bristol
+    from . import bristol, program_file
 
     exp = parse_witness(open(expected_path, "rb").read()) if expected_path else None
     with open(path, "rb") as f:
         size = f.seek(0, 2)
         text = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size else b""  # (an empty file cannot be mapped)
-        ops, info = bristol.parse_device(text, expected_outputs=exp)
+        if fmt == "mcircuit-bincode":
+            ops, info = program_file.loads_device(text)
+        else:
+            ops, info = bristol.parse_device(text, expected_outputs=exp)
     return ops, info["wire_counts"]
 
 
@@ -149,8 +155,8 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
     if fmt == "auto":
         fmt = "rvops" if program_path.endswith(".rvops") else "bristol"
     wit = np.ascontiguousarray(np.asarray(witness, dtype=np.uint8))
-    if parser == "device" and fmt == "bristol":  # the op tensor is the one piece (compacted where it lies)
-        prog, wc = load_program_device(program_path, expected_path)
+    if parser == "device" and fmt in ("bristol", "mcircuit-bincode"):  # the op tensor is the one piece (compacted where it lies)
+        prog, wc = load_program_device(program_path, expected_path, fmt)
         if compact:
             prog, wc = compact_program(prog, wc)
         compact, pieces = False, [prog]
@@ -227,8 +233,8 @@ def build_parser():
                          "the deep, narrow circuits the host compiler recompiles with lazy sums still compile on the host); the proof bytes "
                          "and the outcome are the same")
     ap.add_argument("--parser", default="host", choices=["host", "device"],
-                    help="Bristol programs in prove / verify / oneshot-zk and oneshot --evaluator gpu / stream: parse the text on the host "
-                         "(default) or on the GPU (rv_bristol_parse_device: the file is memory-mapped, the op list is made in device memory "
+                    help="Bristol and mcircuit-bincode programs in prove / verify / oneshot-zk and oneshot --evaluator gpu / stream: parse the file "
+                         "on the host (default) or on the GPU (rv_bristol_parse_device / rv_program_from_bincode_device: the file is memory-mapped, the op list is made in device memory "
                          "and, with --compiler device*, compiled there; --compact-wires then renumbers it there too); the proof bytes and "
                          "the outcome are the same")
     ap.add_argument("--compact-wires", action="store_true",
@@ -260,7 +266,7 @@ def main(argv=None) -> int:
     fmt = a.program_format
     if fmt == "auto":
         fmt = "rvops" if a.program_path.endswith(".rvops") else "bristol"
-    device_parser = a.parser == "device" and fmt == "bristol"
+    device_parser = a.parser == "device" and fmt in ("bristol", "mcircuit-bincode")
     if device_parser and a.operation == "oneshot":
         if a.evaluator == "host":
             ap.error("--parser device leaves the program in GPU memory: --evaluator host cannot read it (use gpu or stream)")
@@ -275,7 +281,7 @@ def main(argv=None) -> int:
         print("()")
         return 0
     if device_parser:
-        prog, wc = load_program_device(a.program_path, a.expected_outputs_path)
+        prog, wc = load_program_device(a.program_path, a.expected_outputs_path, fmt)
     else:
         prog, wc = load_program(a.program_path, a.program_format, a.expected_outputs_path)
     if a.compact_wires:

@@ -70,6 +70,10 @@ class CompactInfo(C.Structure):  # rv_compact_info
                 ("z64_zero_wire", C.c_uint32), ("gf2_values", C.c_uint64), ("z64_values", C.c_uint64)]
 
 
+class ProgramInfo(C.Structure):  # rv_program_info
+    _fields_ = [(n, C.c_uint64) for n in ("n_ops", "bytes", "z64_wires", "gf2_wires", "n_gf2", "n_z64", "n_b2a", "n_sizehint")]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8), ("calls", C.c_uint64)]
 
@@ -115,6 +119,7 @@ SYMBOLS = [
     "rv_hook_interp64_launches", "rv_hook_z64_fused_grid", "rv_hook_z64_fused_levels",
     "rv_ops_compact_wires", "rv_ops_compact_wires_device",
     "rv_bristol_header", "rv_bristol_parse_device", "rv_hook_bristol_tiles",
+    "rv_program_from_bincode_device", "rv_program_to_bincode_device", "rv_hook_bincode_tiles",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -201,6 +206,10 @@ ARGTYPES = {
     "rv_bristol_header": [_P, _Z, C.c_int, C.POINTER(BristolInfo), C.POINTER(C.c_size_t)],
     "rv_bristol_parse_device": [_P, _P, _Z, C.c_int, C.c_int, _P, _Z, _P, _Z, C.POINTER(C.c_size_t), C.POINTER(BristolInfo)],
     "rv_hook_bristol_tiles": [C.POINTER(C.c_uint32)],
+    # program files on the GPU
+    "rv_program_from_bincode_device": [_P, _P, _Z, C.c_int, _P, _Z, C.POINTER(C.c_size_t), C.POINTER(ProgramInfo)],
+    "rv_program_to_bincode_device": [_P, _P, _Z, _P, _Z, C.POINTER(C.c_size_t)],
+    "rv_hook_bincode_tiles": [C.POINTER(C.c_uint32)],
 }
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1

@@ -22,6 +22,7 @@
 
 #include "b3.h"
 #include "bristol_dev.h"
+#include "bincode_dev.h"
 #include "compile.h"
 #include "compact_dev.h"
 #include "compile_dev.h"
@@ -1607,3 +1608,4 @@ extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
 #include "witness_dev.inc"
 #include "compact.inc"
 #include "bristol.inc"
+#include "bincode.inc"
