@@ -1132,6 +1132,15 @@ int rv_hook_verify_device_paths(uint64_t out[2]);
  * out[6] = MODE_VERIFY_C (as rv_hook_verify_vc_count), out[7] = calls whose proof lay in device memory.  The answer is the same on
  * every path; the tests use the counters to know which one a shape took. */
 int rv_hook_verify_schedule(uint64_t out[8]);
+/* What the provers of this process that commit and open one proof at a time (rv_prove*, rv_prove_device*, rv_prove_ops, a batch
+ * proved proof after proof, rv_shard_commit and rv_prove_sharded for their shard) decided, as running totals: out[0] = commitments
+ * queued, out[1] = early corrections, out[2] = ... in their Z64 form, out[3] = broadcast vectors written straight into the proof
+ * buffer, out[4] = the proof through the mapped staging buffer, out[5] = seeds and GF(2) witness in one page-locked copy,
+ * out[6] = MODE_PROVE_V, out[7] = the fused Z64 prover, out[8] = the GF(2) mask generator beside the levels, out[9] = the
+ * lane-distributed mask generator; then the form of every openings call (rv_shard_open* included): out[10] = one launch,
+ * out[11] = heads and inputs in one launch, out[12] = separate launches, out[13] = the error word sent by that one launch.
+ * out[14], out[15] = 0.  The proof is the same on every path; the tests use the counters to know which one a shape took. */
+int rv_hook_prove_schedule(uint64_t out[16]);
 /* Proofs rv_verify_batch_device verified in this process through out[0] = the one-pass device path, out[1] = the single-proof
  * device verifier, out[2] = a host copy (walks that stopped); calls refused with RV_E_ARG count nowhere. */
 int rv_hook_verify_batch_device_paths(uint64_t out[3]);

@@ -120,6 +120,7 @@ SYMBOLS = [
     "rv_ops_compact_wires", "rv_ops_compact_wires_device",
     "rv_bristol_header", "rv_bristol_parse_device", "rv_hook_bristol_tiles",
     "rv_program_from_bincode_device", "rv_program_to_bincode_device", "rv_hook_bincode_tiles",
+    "rv_hook_prove_schedule",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -161,6 +162,7 @@ ARGTYPES = {
     "rv_verify_sections_device": [_P, _P, _P, _P, C.POINTER(C.c_size_t), C.c_uint32, C.POINTER(C.c_int)],
     "rv_hook_verify_device_paths": [C.POINTER(C.c_uint64)],
     "rv_hook_verify_schedule": [C.POINTER(C.c_uint64)],
+    "rv_hook_prove_schedule": [C.POINTER(C.c_uint64)],
     "rv_hook_verify_walk": [_P, _Z, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)],
     # batches that stay in device memory
     "rv_prove_batch_device": [_P, _P, _Z, _P, _Z, _P, _Z, _P, _P, _Z, C.POINTER(C.c_size_t)],

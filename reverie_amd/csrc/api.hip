@@ -177,6 +177,12 @@ struct rv_ctx {
     // and a one-lane kernel adds the error word, instead of two copy-engine operations of ~25 us each behind them
     static constexpr size_t STAGE_BYTES = (size_t)1 << 20;
     uint8_t* h_stage = nullptr;
+    uint8_t* stage_mapped() {  // its device address (made on first use); NULL: not to be had, the caller copies instead
+        uint8_t* dev = nullptr;
+        if (!h_stage && hipHostMalloc((void**)&h_stage, STAGE_BYTES, hipHostMallocMapped) != hipSuccess) h_stage = nullptr;
+        if (!h_stage || hipHostGetDevicePointer((void**)&dev, h_stage, 0) != hipSuccess) (void)hipGetLastError(), dev = nullptr;
+        return dev;
+    }
     // ... and the seeds and the GF(2) witness of a whole proof enter through this one (one copy instead of two pageable ones)
     static constexpr size_t IN_STAGE_BYTES = (size_t)1 << 20;
     uint8_t* h_in = nullptr;
@@ -249,6 +255,38 @@ struct rv_ctx {
     uint32_t fs_seq = 0;
     HelperPool* ec_pool = nullptr;
     double ec_wait_us[17] = {0};  // running averages of the early-corrections waits (per chunk stamp, [16] the challenge): mailbox_wait
+    // the staging blocks grown to `bytes` (the device side only where the vectors are packed: GF(2)) and the mailbox, with its
+    // device address; false: the proof takes the plain path
+    bool early_blocks(size_t bytes, bool device_side, uint32_t** fs_dev) {
+        bool ok = true;
+        if (h_ec_cap < bytes) {
+            if (h_ec) (void)hipHostFree(h_ec);
+            h_ec = nullptr;
+            h_ec_cap = 0;
+            if (hipHostMalloc((void**)&h_ec, bytes, hipHostMallocDefault) == hipSuccess)
+                h_ec_cap = bytes;
+            else
+                ok = false;
+        }
+        if (ok && device_side && d_ec_cap < bytes) {
+            if (d_ec) (void)hipFree(d_ec);
+            d_ec = nullptr;
+            d_ec_cap = 0;
+            if (hipMalloc((void**)&d_ec, bytes) == hipSuccess)
+                d_ec_cap = bytes;
+            else
+                ok = false;
+        }
+        if (ok && !h_fs) {
+            if (hipHostMalloc((void**)&h_fs, 4096, hipHostMallocMapped) == hipSuccess)
+                memset(h_fs, 0, 4096);
+            else
+                ok = false;
+        }
+        if (ok && hipHostGetDevicePointer((void**)fs_dev, h_fs, 0) != hipSuccess) ok = false;
+        if (!ok) (void)hipGetLastError();
+        return ok;
+    }
     // rv_prove_ops / rv_verify_ops: the circuits compiled from raw op lists, kept by content (ops_cache_get): the reference's
     // Proof::new takes the op list at every call (proof/mod.rs:119-124), and a caller that proves one circuit again and again through
     // that signature should pay the 70 - 90 ms host compile once, not per proof
@@ -1138,8 +1176,7 @@ static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged) {
     for (size_t b : {dev_sent * cc.gates.size() * sizeof(Gate), dev_sent * cc.rec_rows.size() * 4, dev_sent * cc.in_rows.size() * 4, z_sent * cc.gates64.size() * sizeof(Gate64),
                      z_sent * cc.rec_offs64.size() * 8, z_sent * cc.in_offs64.size() * 8, cc.level_start.size() * 4, cc.level_range.size() * sizeof(LevelRange)})
         stage_need += (b + 255) & ~(size_t)255;
-    constexpr bool stage_on = true;
-    if (stage_on && stage_need <= rv_ctx::UP_STAGE_MAX && stage_need > ctx->h_up_cap) {
+    if (stage_need <= rv_ctx::UP_STAGE_MAX && stage_need > ctx->h_up_cap) {
         if (ctx->h_up) {
             (void)hipStreamSynchronize(ctx->stream);  // (no copy out of the old buffer may still be pending)
             (void)hipHostFree(ctx->h_up);
@@ -1163,7 +1200,7 @@ static int circuit_upload(rv_ctx* ctx, rv_circuit* c, bool async_staged) {
         if (from_slot) {  // (a streaming piece: copied here by a worker thread)
             src = c->staged + stage_off;
             stage_off += (bytes + 255) & ~(size_t)255;
-        } else if (stage_on && ctx->h_up && stage_off + bytes <= ctx->h_up_cap && stage_need <= rv_ctx::UP_STAGE_MAX) {
+        } else if (ctx->h_up &&stage_off + bytes <= ctx->h_up_cap && stage_need <= rv_ctx::UP_STAGE_MAX) {
             memcpy(ctx->h_up + stage_off, src, bytes);
             src = ctx->h_up + stage_off;
             stage_off += (bytes + 255) & ~(size_t)255;

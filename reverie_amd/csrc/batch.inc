@@ -114,32 +114,10 @@ struct BatchDst {
     size_t stride;
 };
 
-// One proof, framed, straight into device memory at d_dst (rv_prove_batch_device's proof-after-proof branch): rv_prove_device_impl
-// with the framing of a whole Proof around the sections and the repetition counts from k_frame_counts; the error word is all
-// the host waits for.
+// One proof, framed, straight into device memory at d_dst (rv_prove_batch_device's proof-after-proof branch): the error word is
+// all the host waits for.
 static int prove_framed_device(rv_ctx* ctx, const rv_circuit* c, const WitSrc& w, const uint8_t* seeds, uint8_t* d_dst) {
-    rv_shard* s = nullptr;
-    int rc = rv_shard_commit_impl(ctx, c, w, seeds, 0, RV_TOTAL_REPS, &s, /*defer_sync=*/true);
-    if (rc) return rc;
-    do {
-        void* d = nullptr;
-        size_t lens[4];
-        if ((rc = shard_open_impl(s, nullptr, d_dst, &d, lens, true, nullptr, nullptr, /*no_sync=*/true))) break;
-        int err = 0;
-        if (!launch_frame_counts(ctx->stream, d_dst, 0, 1, lens) || hipGetLastError() != hipSuccess) {
-            rc = RV_E_DEVICE;
-            break;
-        }
-        if (hipMemcpyAsync(&err, s->d_err, sizeof err, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            rc = hip_fail(hipGetLastError(), "rv_prove_batch_device", __FILE__, __LINE__);
-            break;
-        }
-        ctx->collect();
-        if (err) rc = RV_E_WITNESS_INVALID;
-    } while (0);
-    rv_shard_destroy(s);
-    return rc;
+    return prove_whole_to_device(ctx, c, w, seeds, d_dst, /*framed=*/true, nullptr, nullptr, nullptr, "rv_prove_batch_device");
 }
 
 static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, const WitSrc& w, const uint8_t* seeds, const BatchDst& out) {
@@ -155,16 +133,11 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
     for (size_t b = 0; b < batch && !dev; b++) proofs[b] = nullptr, proof_lens[b] = 0;
     if (n_gf2 < cc.n_in || n_z64 < cc.n_in64) return RV_E_WITNESS_SHORT;
     if ((cc.n_in && !wit_gf2) || (cc.n_in64 && !wit_z64)) return RV_E_ARG;
-    std::vector<uint8_t> os_seeds;
-    if (!seeds) {  // OsRng (proof/mod.rs:131-134)
-        os_seeds.resize(batch * RV_TOTAL_REPS * 16);
-        size_t got = 0;
-        while (got < os_seeds.size()) {
-            ssize_t n = getrandom(os_seeds.data() + got, os_seeds.size() - got, 0);
-            if (n <= 0) return RV_E_DEVICE;
-            got += (size_t)n;
-        }
-        seeds = os_seeds.data();
+    std::vector<uint8_t> drawn;
+    if (!seeds) {
+        drawn.resize(batch * RV_TOTAL_REPS * 16);
+        if (int rs = os_seeds(drawn.data(), drawn.size())) return rs;
+        seeds = drawn.data();
     }
     auto one_by_one = [&]() {  // Z64 / mixed circuits and batches of one: the plain entry point, proof after proof
         for (size_t b = 0; b < batch && dev; b++) {
@@ -193,9 +166,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
         // consecutive chunks of what fits in half of the free device memory (RV_BATCH_MAX caps a chunk), each with its own slab
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return RV_E_DEVICE;
-        uint8_t om[RV_TOTAL_REPS];
-        for (uint32_t r = 0; r < RV_TOTAL_REPS; r++) om[r] = r < RV_ONLINE_REPS ? 0 : RV_PLAYERS;
-        const size_t per_proof = cc.info.scratch_bytes + open_layout(cc, om, RV_TOTAL_REPS, true).total + cc.n_in + 8 * cc.n_in64 + 4096;
+        const size_t per_proof = cc.info.scratch_bytes + whole_proof_layout(cc).total + cc.n_in + 8 * cc.n_in64 + 4096;
         size_t chunk = std::min<size_t>(std::max<size_t>((free_b + ctx->cached_bytes) / 2 / per_proof, 2), 4096);
         if (const char* e = getenv("RV_BATCH_MAX")) chunk = std::min<size_t>(chunk, (size_t)std::max(atoi(e), 1));
         if (batch > chunk) {
@@ -261,9 +232,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
         // every proof of the batch lands in a slice of ONE page-locked buffer (released when the last proof has been
         // rv_free'd): a buffer per proof meant a hipHostMalloc of tens of MB per proof as soon as the caller held more
         // proofs than the pool keeps idle -- 7.7 ms per proof at 16 proofs per call instead of 6.2 at 2
-        uint8_t canon[RV_TOTAL_REPS];
-        for (uint32_t r = 0; r < RV_TOTAL_REPS; r++) canon[r] = r < RV_ONLINE_REPS ? 0 : RV_PLAYERS;
-        const size_t stride = (open_layout(cc, canon, RV_TOTAL_REPS, true).total + 4095) & ~(size_t)4095;
+        const size_t stride = (whole_proof_layout(cc).total + 4095) & ~(size_t)4095;
         uint8_t* slab = (uint8_t*)g_pinned.get(std::max<size_t>(stride * batch, PinnedPool::MIN_BYTES));
         if (!slab) return RV_E_NOMEM;
         int rcs[T_MAX] = {};
@@ -364,9 +333,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
     // 256 bytes into their slab: no proof's pointer equals an arena block, the slabs are released exactly once below.
     constexpr size_t SLAB_HEAD = 256;
     const size_t wit_stride = (std::max<size_t>(cc.n_in, 1) + 15) & ~(size_t)15;
-    uint8_t canon[RV_TOTAL_REPS];
-    for (uint32_t r = 0; r < RV_TOTAL_REPS; r++) canon[r] = r < RV_ONLINE_REPS ? 0 : RV_PLAYERS;
-    const size_t out_stride = (open_layout(cc, canon, R, true).total + 4 + 255) & ~(size_t)255;
+    const size_t out_stride = (whole_proof_layout(cc).total + 4 + 255) & ~(size_t)255;
     uint8_t *d_seeds_all = nullptr, *d_wit_all = nullptr, *d_out_all = nullptr;
     int* d_err_all = nullptr;
     if ((rc = dalloc(ctx, SLAB_HEAD + batch * (size_t)R * 16, &d_seeds_all))) return cleanup(rc);
@@ -443,11 +410,15 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
     size_t lens[4] = {0, 0, 0, 0};  // the same for every proof of the circuit (40 / 216 split)
     for (size_t b = 0; b < batch && !rc; b++) {
         rv_shard* s = sh[b];
-        void* d = nullptr;
+        OpenArgs a;
+        a.dst = dev ? out.d_dst + b * out.stride : d_out_all + SLAB_HEAD + b * out_stride;
+        a.framed = true;
+        a.no_sync = true;
+        OpenResult res;
         g_recorder = &recs[b];
-        if (!(rc = shard_run_hash(s)) && !(rc = shard_join(s)))
-            rc = shard_open_impl(s, nullptr, dev ? out.d_dst + b * out.stride : d_out_all + SLAB_HEAD + b * out_stride, &d, lens, true, nullptr, nullptr, /*no_sync=*/true);
+        if (!(rc = shard_run_hash(s)) && !(rc = shard_join(s))) rc = shard_open_impl(s, a, &res);
         g_recorder = nullptr;
+        for (int k = 0; k < 4; k++) lens[k] = res.lens[k];
     }
     if (rc) return cleanup(rc);
     mark("record digests/openings");
@@ -493,7 +464,6 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
         // munmaps in the caller: together they cost more than the GPU work of an AES-128 batch).  RV_BATCH_COPY_OUT=1
         // gives every proof its own malloc'ed buffer instead (callers that keep single proofs of many batches alive).
         static const bool copy_out = getenv("RV_BATCH_COPY_OUT") != nullptr;
-        const uint64_t counts[4] = {RV_ONLINE_REPS, RV_PREPROCESSING_REPS, RV_ONLINE_REPS, RV_PREPROCESSING_REPS};
         if (copy_out) {
             for (size_t b = 0; b < batch; b++) {
                 proofs[b] = (uint8_t*)malloc(proof_lens[b]);
@@ -505,13 +475,7 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
             for (size_t b = 0; b < batch; b++) proofs[b] = staging + b * slot;
             staging = nullptr;  // owned by the proofs now
         }
-        for (size_t b = 0; b < batch; b++) {
-            size_t off = 32;
-            for (int k = 0; k < 4; k++) {
-                put_le64(proofs[b] + off, counts[k]);
-                off += 8 + lens[k];
-            }
-        }
+        for (size_t b = 0; b < batch; b++) frame_counts_host(proofs[b], lens);
     }
     ctx->prof.calls += batch;
     mark("copy proofs out");
@@ -522,10 +486,5 @@ static int rv_prove_batch_impl(rv_ctx* ctx, const rv_circuit* c, size_t batch, c
 
 extern "C" int rv_prove_batch(rv_ctx* ctx, const rv_circuit* c, size_t batch, const uint8_t* wit_gf2, size_t n_gf2,
                               const uint64_t* wit_z64, size_t n_z64, const uint8_t* seeds, uint8_t** proofs, size_t* proof_lens) {
-    try {  // no C++ exception may cross the C boundary
-        return rv_prove_batch_impl(ctx, c, batch, wit_host(wit_gf2, n_gf2, wit_z64, n_z64), seeds, BatchDst{proofs, proof_lens, nullptr, 0});
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return rv_prove_batch_impl(ctx, c, batch, wit_host(wit_gf2, n_gf2, wit_z64, n_z64), seeds, BatchDst{proofs, proof_lens, nullptr, 0}); });
 }

@@ -23,9 +23,7 @@ extern "C" int rv_prove_batch_device(rv_ctx* ctx, const rv_circuit* c, size_t ba
                                      size_t n_z64, const uint8_t* seeds, void* dst_device, size_t stride, size_t* proof_len) {
     if (!ctx || !c || !batch || !seeds || !dst_device || !proof_len) return RV_E_ARG;
     return guarded([&]() -> int {
-        uint8_t canon[RV_TOTAL_REPS];
-        for (uint32_t r = 0; r < RV_TOTAL_REPS; r++) canon[r] = r < RV_ONLINE_REPS ? 0 : RV_PLAYERS;
-        const size_t total = open_layout(c->cc, canon, RV_TOTAL_REPS, true).total;
+        const size_t total = whole_proof_layout(c->cc).total;
         *proof_len = total;
         if (((uintptr_t)dst_device & 255) || (stride & 255) || stride < total || batch > SIZE_MAX / stride) return RV_E_ARG;
         HIPCHK(hipSetDevice(ctx->device));
@@ -77,17 +75,7 @@ static int rv_verify_batch_device_impl(rv_ctx* ctx, const rv_circuit* c, size_t 
     for (size_t b = 0; b < batch; b++) h_refs[b] = BatchProofRef{d_proofs[b], (uint64_t)proof_lens[b], d_tables + b * (size_t)VW_WORDS};
     const size_t head_bytes = batch * (size_t)VW_HEAD_WORDS * 8;
     std::vector<uint64_t> heads(batch * (size_t)VW_HEAD_WORDS);
-    uint8_t* stage_dev = nullptr;
-    if (head_bytes <= rv_ctx::STAGE_BYTES) {
-        if (!ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, rv_ctx::STAGE_BYTES, hipHostMallocMapped) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->h_stage = nullptr;
-        }
-        if (ctx->h_stage && hipHostGetDevicePointer((void**)&stage_dev, ctx->h_stage, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            stage_dev = nullptr;
-        }
-    }
+    uint8_t* const stage_dev = head_bytes <= rv_ctx::STAGE_BYTES ? ctx->stage_mapped() : nullptr;
     uint64_t* h_heads = nullptr;  // (without the mapped buffer: a page-locked one, one copy)
     if (!stage_dev) {
         if ((rc = dalloc(ctx, batch * (size_t)VW_HEAD_WORDS, &d_heads))) return cleanup(rc);

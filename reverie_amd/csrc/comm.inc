@@ -226,9 +226,14 @@ static int prove_sharded_impl(rv_comm* m, const rv_circuit* c, const uint8_t* wi
         if ((rc = dalloc(ctx, std::max<size_t>(cap, 1), &d_mine))) break;
         // ---- challenge + this shard's openings on the device (one host synchronisation: comm, the map, the sizes)
         uint8_t comm_bytes[32], omit[RV_TOTAL_REPS];
-        size_t lens[4];
-        void* d = nullptr;
-        if ((rc = shard_open_impl(s, nullptr, d_mine, &d, lens, false, comm_bytes, omit, false, m->d_allh))) break;
+        OpenArgs a;
+        a.dst = d_mine;
+        a.comm_out = comm_bytes;
+        a.omit_out = omit;
+        a.d_all_h = m->d_allh;
+        OpenResult res;
+        if ((rc = shard_open_impl(s, a, &res))) break;
+        const size_t* const lens = res.lens;
         int err = 0;
         if (hipMemcpyAsync(&err, s->d_err, sizeof err, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
             rc = RV_E_DEVICE;
@@ -274,8 +279,7 @@ static int prove_sharded_impl(rv_comm* m, const rv_circuit* c, const uint8_t* wi
             if (rc) break;
             if (m->rank == 0) {
                 memcpy(shared_out, comm_bytes, 32);
-                const uint64_t counts[4] = {RV_ONLINE_REPS, RV_PREPROCESSING_REPS, RV_ONLINE_REPS, RV_PREPROCESSING_REPS};
-                for (int k = 0; k < 4; k++) put_le64(shared_out + base[k] - 8, counts[k]);
+                frame_counts_at(shared_out, base);
                 *proof = shared_out;
                 *proof_len = total;
             }
@@ -339,8 +343,7 @@ static int prove_sharded_impl(rv_comm* m, const rv_circuit* c, const uint8_t* wi
             break;
         }
         memcpy(out, comm_bytes, 32);
-        const uint64_t counts[4] = {RV_ONLINE_REPS, RV_PREPROCESSING_REPS, RV_ONLINE_REPS, RV_PREPROCESSING_REPS};
-        for (int k = 0; k < 4; k++) put_le64(out + base[k] - 8, counts[k]);
+        frame_counts_at(out, base);
         *proof = out;
         *proof_len = total;
         out = nullptr;
@@ -355,33 +358,21 @@ static int prove_sharded_impl(rv_comm* m, const rv_circuit* c, const uint8_t* wi
 
 extern "C" int rv_prove_sharded(rv_comm* m, const rv_circuit* c, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64, size_t n_z64,
                                 const uint8_t* seeds, uint8_t** proof, size_t* proof_len) {
-    try {
-        return prove_sharded_impl(m, c, wit_gf2, n_gf2, wit_z64, n_z64, seeds, proof, proof_len);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return prove_sharded_impl(m, c, wit_gf2, n_gf2, wit_z64, n_z64, seeds, proof, proof_len); });
 }
 
 // one process, n GPUs: a host thread per rank runs rv_prove_sharded; the proof is rank 0's
 extern "C" int rv_prove_multi(rv_comm* const* comms, const rv_circuit* const* circuits, int n, const uint8_t* wit_gf2, size_t n_gf2,
                               const uint64_t* wit_z64, size_t n_z64, const uint8_t* seeds, uint8_t** proof, size_t* proof_len) {
     if (!comms || !circuits || n < 1 || !proof || !proof_len) return RV_E_ARG;
-    uint8_t os_seeds[RV_TOTAL_REPS * RV_KEY_SIZE];
+    uint8_t drawn[RV_TOTAL_REPS * RV_KEY_SIZE];
     if (!seeds) {  // every rank must use the same seeds: drawn once, here
-        size_t got = 0;
-        while (got < sizeof os_seeds) {
-            ssize_t k = getrandom(os_seeds + got, sizeof os_seeds - got, 0);
-            if (k <= 0) return RV_E_DEVICE;
-            got += (size_t)k;
-        }
-        seeds = os_seeds;
+        if (int rs = os_seeds(drawn, sizeof drawn)) return rs;
+        seeds = drawn;
     }
     // the framed proof's size does not depend on the challenge (40 / 216): one page-locked buffer that every rank fills its part of
-    uint8_t canon[RV_TOTAL_REPS];
-    for (uint32_t r = 0; r < RV_TOTAL_REPS; r++) canon[r] = r < RV_ONLINE_REPS ? 0 : RV_PLAYERS;
     if (!circuits[0]) return RV_E_ARG;
-    const size_t total = open_layout(circuits[0]->cc, canon, RV_TOTAL_REPS, true).total;
+    const size_t total = whole_proof_layout(circuits[0]->cc).total;
     // RV_MULTI_SENDRECV=1: rv_prove_sharded's own gather instead (sections to rank 0 by ncclSend / ncclRecv, one copy out) -- what several
     // PROCESSES run; the multi-rank tests drive both forms through this call (read at every call)
     const bool sendrecv = getenv("RV_MULTI_SENDRECV") && atoi(getenv("RV_MULTI_SENDRECV")) != 0;
@@ -392,12 +383,9 @@ extern "C" int rv_prove_multi(rv_comm* const* comms, const rv_circuit* const* ci
     std::vector<size_t> lens((size_t)n, 0);
     std::vector<std::string> errs((size_t)n);
     auto run = [&](int i) {
-        try {
-            rcs[(size_t)i] = prove_sharded_impl(comms[i], circuits[i], wit_gf2, n_gf2, wit_z64, n_z64, seeds, &outs[(size_t)i], &lens[(size_t)i], shared, total);
-        } catch (...) {
-            g_last_error = "out of host memory";
-            rcs[(size_t)i] = RV_E_NOMEM;
-        }
+        rcs[(size_t)i] = guarded([&] {
+            return prove_sharded_impl(comms[i], circuits[i], wit_gf2, n_gf2, wit_z64, n_z64, seeds, &outs[(size_t)i], &lens[(size_t)i], shared, total);
+        });
         if (rcs[(size_t)i]) errs[(size_t)i] = g_last_error;
     };
     std::vector<std::thread> th;
@@ -487,12 +475,7 @@ static int verify_sharded_impl(rv_comm* m, const rv_circuit* c, const uint8_t* p
 }
 
 extern "C" int rv_verify_sharded(rv_comm* m, const rv_circuit* c, const uint8_t* proof, size_t proof_len, uint32_t flags, int* ok) {
-    try {
-        return verify_sharded_impl(m, c, proof, proof_len, flags, ok);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return verify_sharded_impl(m, c, proof, proof_len, flags, ok); });
 }
 
 // one process, n GPUs: a host thread per rank runs rv_verify_sharded; every rank must come to the same (rc, ok)

@@ -136,24 +136,14 @@ extern "C" int rv_prove_ops(rv_ctx* ctx, const rv_op* ops, size_t n_ops, const u
     if (!proof || !proof_len) return RV_E_ARG;
     rv_circuit* c = nullptr;
     bool hit = false, owned = true;
-    int rc;
-    try {
-        // (under RV_COMPILE_DEVICE the prover's circuit is the device compiler's K = 1 form instead of the RV_COMPILE_WHOLE_PROVER
-        // one: the proof bytes are the same, header.  The device compiler builds the lazy-sum form too; asking it for that here made
-        // the cold call faster but not, measurably, the calls after it -- DESIGN.md 14.2)
-        const uint32_t fl = (ctx && (ctx->compile_flags & RV_COMPILE_DEVICE)) ? (ctx->compile_flags & RV_COMPILE_DEVICE_BITS) : RV_COMPILE_WHOLE_PROVER;
-        rc = ops_cache_get(ctx, ops, n_ops, z64_wires, gf2_wires, fl, &c, &hit, &owned);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    // (under RV_COMPILE_DEVICE the prover's circuit is the device compiler's K = 1 form instead of the RV_COMPILE_WHOLE_PROVER
+    // one: the proof bytes are the same, header.  The device compiler builds the lazy-sum form too; asking it for that here made
+    // the cold call faster but not, measurably, the calls after it -- DESIGN.md 14.2)
+    const uint32_t fl = (ctx && (ctx->compile_flags & RV_COMPILE_DEVICE)) ? (ctx->compile_flags & RV_COMPILE_DEVICE_BITS) : RV_COMPILE_WHOLE_PROVER;
+    int rc = guarded([&] { return ops_cache_get(ctx, ops, n_ops, z64_wires, gf2_wires, fl, &c, &hit, &owned); });
     if (rc) return rc;
-    try {  // (the first proof of a circuit, or of one nobody keeps: without the early-corrections staging; a circuit seen before takes it)
-        rc = rv_prove_impl(ctx, c, wit_host(wit_gf2, n_gf2, wit_z64, n_z64), seeds, proof, proof_len, nullptr, 0, /*allow_early=*/hit);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        rc = RV_E_NOMEM;
-    }
+    // (the first proof of a circuit, or of one nobody keeps: without the early-corrections staging; a circuit seen before takes it)
+    rc = guarded([&] { return rv_prove_impl(ctx, c, wit_host(wit_gf2, n_gf2, wit_z64, n_z64), seeds, proof, proof_len, nullptr, 0, /*allow_early=*/hit); });
     if (owned) rv_circuit_destroy(c);
     return rc;
 }

@@ -14,6 +14,16 @@ struct HostTrace {
     }
 };
 static thread_local HostTrace g_ht;
+
+// n bytes of seed material from the OS, where the reference uses OsRng (proof/mod.rs:131-134)
+static int os_seeds(uint8_t* buf, size_t n) {
+    for (size_t got = 0; got < n;) {
+        const ssize_t k = getrandom(buf + got, n - got, 0);
+        if (k <= 0) return RV_E_DEVICE;
+        got += (size_t)k;
+    }
+    return RV_OK;
+}
 // Part of api.hip (#included there, one translation unit): the shard: per-proof device state, the early-corrections plan, the mask generator beside the levels, the level loop, digests, commitment.
 
 // ------------------------------------------------------------------------------------
@@ -27,7 +37,6 @@ struct EarlyRun {
     uint8_t* h_ec = nullptr;
     size_t next = 0;                 // chunks whose "ready" stamp is in the interpreter's stream
     size_t pumped = 0;               // chunks whose copy has been handed to the second stream
-    std::vector<uint8_t> packed;     // per chunk: already packed when its stamp appears
     // progress stamps in the context's host-mapped mailbox (no HIP events: their status reached the host late, and the
     // host must see a chunk the moment it is ready): word 1 = (seq << 8 | chunks ready)
     uint32_t* box_dev = nullptr;
@@ -151,6 +160,18 @@ static void overlap_trace_dump() {
     delete g_ov_trace;
     g_ov_trace = nullptr;
 }
+// Which GF(2) generator: the lane-distributed one (aes_col4.hip) whenever it is to share the chip with the level launches
+// (RV_OVERLAP), for SMALL proofs (up to 4 096 cipher blocks per slot: the 128-plane kernel's wavefront runs 32 blocks per lane one
+// round after the other, ~45 us however few there are; a quad of lanes per state is through in ~19 -- tools/gen_sweep.py: AES-128
+// 0.27 -> 0.245 ms, even at 1 000 - 4 000 blocks, behind from 8 000), or on request (RV_AES_COL4=1 / 0, read once); recorded batches
+// keep the 128-plane kernel (its launch is replayable)
+static bool gf2_masks_col4(uint32_t NQ, uint64_t n_blocks, bool overlap) {
+    static const int col4_mode = [] {
+        const char* e = getenv("RV_AES_COL4");
+        return e ? atoi(e) : -1;
+    }();
+    return n_blocks && !g_recorder && aes_col4_supports(NQ) && (col4_mode > 0 || (col4_mode < 0 && (overlap || n_blocks <= 4096)));
+}
 // key material -> bitsliced round keys, masks
 static int shard_setup_prg(rv_shard* s, const uint32_t* d_keep, const uint32_t* d_keep64 = nullptr) {
     rv_ctx* ctx = s->ctx;
@@ -172,16 +193,7 @@ static int shard_setup_prg(rv_shard* s, const uint32_t* d_keep, const uint32_t* 
         launch_bitslice_rk(ctx->stream, s->d_rkbytes, s->NQ, s->d_rk);
         ctx->count(2);
     }
-    // which GF(2) generator: the lane-distributed one (aes_col4.hip) whenever it is to share the chip with the level launches
-    // (RV_OVERLAP), for SMALL proofs (up to 4 096 cipher blocks per slot: the 128-plane kernel's wavefront runs 32 blocks per lane one
-    // round after the other, ~45 us however few there are; a quad of lanes per state is through in ~19 -- tools/gen_sweep.py: AES-128
-    // 0.27 -> 0.245 ms, even at 1 000 - 4 000 blocks, behind from 8 000), or on request (RV_AES_COL4=1 / 0); recorded batches keep the
-    // 128-plane kernel (its launch is replayable)
-    static const int col4_mode = [] {
-        const char* e = getenv("RV_AES_COL4");
-        return e ? atoi(e) : -1;
-    }();
-    const bool col4 = n_blocks && !g_recorder && aes_col4_supports(s->NQ) && (col4_mode > 0 || (col4_mode < 0 && (s->overlap || n_blocks <= 4096)));
+    const bool col4 = gf2_masks_col4(s->NQ, n_blocks, s->overlap);
     if (s->overlap && !col4) s->overlap = false;
     if (col4) {
         if ((rc = dalloc(ctx, aes_col4_image_bytes(s->NQ) / 4, &s->d_rk_c4))) return rc;
@@ -270,8 +282,7 @@ static int overlap_need(rv_shard* s, uint64_t need, hipStream_t sb) {
         if (g_ov_trace) g_ov_trace->mark("main: levels queued so far end; wait for chunk ending at block", s->ov_next, sb);
         if (g_ov_trace) g_ov_trace->mark("  masks: chunk start at block", s->ov_next, ctx->stream_m);
         // (the first chunk is what the proof waits for with nothing beside it: half size)
-        constexpr uint64_t first = 0;
-        const uint64_t nb = std::min(s->ov_next == 0 ? (first ? first : std::max<uint64_t>(s->ov_chunk / 2, 512)) : s->ov_chunk, s->ov_blocks - s->ov_next);
+        const uint64_t nb = std::min(s->ov_next == 0 ? std::max<uint64_t>(s->ov_chunk / 2, 512) : s->ov_chunk, s->ov_blocks - s->ov_next);
         const auto ht0 = std::chrono::steady_clock::now();
         launch_aes_gf2_masks_col4(ctx->stream_m, s->d_rk_c4, s->ov_keep, s->NQ, s->ov_next, nb, s->d_masks + (size_t)s->ov_next * 128 * s->NQ);
         const auto ht1 = std::chrono::steady_clock::now();
@@ -395,6 +406,13 @@ static std::atomic<uint64_t> g_early_proofs{0};
 extern "C" uint64_t rv_hook_early_proofs(void) { return g_early_proofs.load(std::memory_order_relaxed); }
 static std::atomic<uint64_t> g_open_direct_proofs{0};
 extern "C" uint64_t rv_hook_open_direct_proofs(void) { return g_open_direct_proofs.load(std::memory_order_relaxed); }
+// rv_hook_prove_schedule (prove.inc): what the single-proof prover's calls decided, cumulative, in the hook's order
+enum { PS_CALLS, PS_EARLY, PS_EARLY_Z64, PS_OPEN_DIRECT, PS_STAGE_OUT, PS_STAGE_IN, PS_VCLR, PS_Z64F, PS_OVERLAP, PS_COL4,
+       PS_OPEN_ONE, PS_OPEN_HEADS_INPUTS, PS_OPEN_SEPARATE, PS_OPEN_ERR_WORD, PS_N };
+static std::atomic<uint64_t> g_prove_schedule[16];
+static void prove_counted(int what, bool on = true) {
+    if (on) g_prove_schedule[what].fetch_add(1, std::memory_order_relaxed);
+}
 static std::atomic<uint64_t> g_verify_vc{0};
 extern "C" uint64_t rv_hook_verify_vc_count(void) { return g_verify_vc.load(std::memory_order_relaxed); }
 
@@ -563,7 +581,7 @@ static uint64_t early_staging_bytes_of(const rv_circuit* c) {
 // ready_level (k < 16).
 extern "C" int rv_hook_early_plan(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, uint64_t out[22]) {
     if (!out || (n_ops && !ops) || (flags & ~RV_COMPILE_WHOLE_PROVER)) return RV_E_ARG;
-    try {
+    return guarded([&]() -> int {
         rv_circuit tmp;
         int rc = compile_ops(ops, n_ops, z64_wires, gf2_wires, tmp.cc, nullptr, ((flags & RV_COMPILE_WHOLE_PROVER) && !getenv("RV_LAZY_K")) ? RV_LIN_K : 0);
         if (rc) return rc;
@@ -603,10 +621,7 @@ extern "C" int rv_hook_early_plan(const rv_op* ops, size_t n_ops, size_t z64_wir
         }
         out[5] = good;
         return RV_OK;
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    });
 }
 
 // Early corrections, device side.  early_flush (called by the level loop) puts, behind the level that completes a chunk, the
@@ -615,7 +630,7 @@ extern "C" int rv_hook_early_plan(const rv_op* ops, size_t n_ops, size_t z64_wir
 // holds copy-engine work and the "arrived" stamps.  Measured on the 10^7-gate circuit (tools/early_ab.py, gpurun_out/e*.log):
 //  * packing kernels on the second stream are not dispatched while the first stream issues its short level launches back
 //    to back (kernel trace: the first one starts when the hash kernels do), so the copies piled up behind the challenge;
-//    in the interpreter's stream they cost 6 x 26 us (RV_EARLY_PACK_STREAM=0 / 2: the old placements);
+//    in the interpreter's stream they cost 6 x 26 us;
 //  * HIP events instead of stamps (hipEventRecord + hipStreamWaitEvent, or hipEventQuery from the host) were no cheaper, and
 //    neither was a second stream of the highest priority;
 //  * the packing kernel takes ~27 us per 27 MB chunk whatever its instruction count (a lane per repetition with multiplications,
@@ -632,21 +647,12 @@ static int early_flush_chunks(rv_shard* s, size_t last) {
     rv_ctx* ctx = s->ctx;
     const auto& chunks = e->plan->chunks;
     if (e->next >= chunks.size() || last <= e->next) return RV_OK;
-    constexpr int pack_stream = 1;  // 1: every chunk in-stream, 0: the last one, 2: none
-    const size_t first = e->next;
-    for (size_t k = first; k < last; k++) {
-        const bool in_stream = pack_stream == 1 || (pack_stream != 2 && k + 1 == chunks.size());
+    // every chunk is packed in the interpreter's own stream (Z64: nothing to pack, the rows are the vectors)
+    // (these launches sit inside the interpreter's phase but are not level launches: rv_profile counts them in slot 6)
+    for (size_t k = e->next; k < last && !e->plan->z64; k++) {
         const auto& ch = chunks[k];
-        // (these launches sit inside the interpreter's phase but are not level launches: rv_profile counts them in slot 6)
-        if (e->plan->z64) {
-            e->packed.push_back(1);  // nothing to pack: the rows are the vectors
-            continue;
-        }
-        if (in_stream) {
-            launch_pack_corr_all(ctx->stream, s->d_pre, s->c->cc.n_pre, ch.byte0, ch.nbytes, ch.pitch, e->d_ec + ch.off);
-            if (ctx->profiling) ctx->prof.launches[RV_PH_EARLY]++;
-        }
-        e->packed.push_back(in_stream ? 1 : 0);
+        launch_pack_corr_all(ctx->stream, s->d_pre, s->c->cc.n_pre, ch.byte0, ch.nbytes, ch.pitch, e->d_ec + ch.off);
+        if (ctx->profiling) ctx->prof.launches[RV_PH_EARLY]++;
     }
     launch_publish(ctx->stream, nullptr, 0, nullptr, e->box_dev + 1, (e->seq << 8) | (uint32_t)last);
     if (ctx->profiling) ctx->prof.launches[RV_PH_EARLY]++;
@@ -666,16 +672,14 @@ static int early_flush(rv_shard* s, size_t levels_queued) {
 // The host's waits of the early-corrections path (a chunk's stamp, the challenge): the mailbox is written by the GPU, so there is
 // nothing to block on -- but the caller need not burn a core for the milliseconds a proof takes either.  The wait SLEEPS through
 // most of what the same wait took last time on this context (`ema_us`, a running average per kind of wait: proofs of one circuit
-// repeat their timing to a few percent), then spins for the rest, so the word is seen as promptly as before; RV_EARLY_SPIN=1 spins
-// all the way.  Bounded: a stream that has ENDED (or failed) without the awaited word is RV_E_DEVICE at once; one still running is given
+// repeat their timing to a few percent), then spins for the rest, so the word is seen as promptly as before.  Bounded: a stream that has ENDED (or failed) without the awaited word is RV_E_DEVICE at once; one still running is given
 // ten times RV_EARLY_TIMEOUT_MS (default 20 000) -- a slow proof on a shared GPU is not a lost one -- then RV_E_DEVICE with a message, not a hang.
 template <class Pred>
 static int mailbox_wait(rv_ctx* ctx, Pred arrived, double* ema_us, const char* what) {
-    constexpr bool spin_only = false;
     static const long timeout_ms = getenv("RV_EARLY_TIMEOUT_MS") ? std::max(atol(getenv("RV_EARLY_TIMEOUT_MS")), 1l) : 20000;
     const auto t0 = std::chrono::steady_clock::now();
     auto elapsed_us = [&] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
-    if (!spin_only && ema_us && *ema_us > 200.0) {
+    if (ema_us && *ema_us > 200.0) {
         // sleep until ~80 % of the expected wait (minus the scheduler's slack) is over, in naps short enough to notice an early word
         const double until = 0.8 * *ema_us - 80.0;
         while (!arrived()) {
@@ -706,15 +710,14 @@ static int mailbox_wait(rv_ctx* ctx, Pred arrived, double* ema_us, const char* w
     return rc;
 }
 
-// host side: waits for every chunk's stamp in turn and queues its packing kernel (unless done), its copy to the host and the
-// stamp that says it has arrived
+// host side: waits for every chunk's stamp in turn and queues its copy to the host
 static int early_pump(rv_shard* s) {
     EarlyRun* e = s->ec;
     rv_ctx* ctx = s->ctx;
     const auto& chunks = e->plan->chunks;
     for (; e->pumped < chunks.size(); e->pumped++) {
         const size_t k = e->pumped;
-        if (k >= e->packed.size()) return RV_E_DEVICE;
+        if (k >= e->next) return RV_E_DEVICE;
         if (int rcw = mailbox_wait(ctx, [&] { return e->ready(k); }, k < 16 ? &ctx->ec_wait_us[k] : nullptr, "early corrections (pump)")) return rcw;
         const auto& ch = chunks[k];
         if (e->plan->z64) {
@@ -723,7 +726,6 @@ static int early_pump(rv_shard* s) {
             HIPCHK(hipMemcpy2DAsync(e->h_ec + ch.byte0, ch.pitch, (const uint8_t*)s->d_pre64 + ch.byte0, (size_t)s->c->cc.pre_words64 * 8, ch.nbytes,
                                     e->plan->r_spec, hipMemcpyDeviceToHost, ctx->stream2));
         } else {
-            if (!e->packed[k]) launch_pack_corr_all(ctx->stream2, s->d_pre, s->c->cc.n_pre, ch.byte0, ch.nbytes, ch.pitch, e->d_ec + ch.off);
             HIPCHK(hipMemcpyAsync(e->h_ec + ch.off, e->d_ec + ch.off, (size_t)e->plan->r_spec * ch.pitch, hipMemcpyDeviceToHost, ctx->stream2));
         }
         // (NO kernel or event behind the copy: a packet that waits for the copy engine's signal at the head of the second queue is
@@ -873,9 +875,8 @@ static int shard_run_hash(rv_shard* s) {
     uint32_t* dig = s->d_dig;
     const size_t DW = (size_t)s->R * 8;
     uint32_t n_launch;
-    constexpr bool pair_on = true;
-    if (pair_on && launch_b3_pair_small(ctx->stream, s->d_pre, cc.n_pre, s->d_on, cc.n_on, s->NQ, s->d_cv[0], s->d_cv[1], dig + 0 * DW, dig + 1 * DW,
-                                        s->d_on_quads, s->n_on_quads)) {
+    if (launch_b3_pair_small(ctx->stream, s->d_pre, cc.n_pre, s->d_on, cc.n_on, s->NQ, s->d_cv[0], s->d_cv[1], dig + 0 * DW, dig + 1 * DW,
+                             s->d_on_quads, s->n_on_quads)) {
         n_launch = 2;  // short transcripts (small circuits): both streams in the same two launches
     } else if (s->d_cv2[0]) {
         n_launch = launch_b3_pair_big(ctx->stream, s->d_pre, cc.n_pre, s->d_on, cc.n_on, s->NQ, s->d_cv[0], s->d_cv[1], s->d_cv2[0], s->d_cv2[1], dig + 0 * DW, dig + 1 * DW,
@@ -920,132 +921,6 @@ static int shard_join(rv_shard* s) {
     return RV_OK;
 }
 
-
-// defer_sync: do not wait for the device (nor look at the invalid-witness flag): the caller queues more work behind
-// the commitment and checks s->d_err itself after its own synchronisation
-static int rv_shard_commit_impl(rv_ctx* ctx, const rv_circuit* c, const WitSrc& w, const uint8_t* seeds, uint32_t rep_begin, uint32_t rep_count,
-                               rv_shard** out, bool defer_sync = false, EarlyRun* ec = nullptr);
-
-extern "C" int rv_shard_commit(rv_ctx* ctx, const rv_circuit* c, const uint8_t* wit_gf2, size_t n_gf2, const uint64_t* wit_z64,
-                               size_t n_z64, const uint8_t* seeds, uint32_t rep_begin, uint32_t rep_count, rv_shard** out) {
-    try {  // no C++ exception may cross the C boundary
-        return rv_shard_commit_impl(ctx, c, wit_host(wit_gf2, n_gf2, wit_z64, n_z64), seeds, rep_begin, rep_count, out);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
-}
-
-static int rv_shard_commit_impl(rv_ctx* ctx, const rv_circuit* c, const WitSrc& w, const uint8_t* seeds, uint32_t rep_begin, uint32_t rep_count,
-                               rv_shard** out, bool defer_sync, EarlyRun* ec) {
-    LibBusy busy_guard;  // (compile.h: the background unmapper keeps still while the GPU is driven)
-    if (!ctx || !c || !out || !seeds) return RV_E_ARG;
-    const uint8_t* const wit_gf2 = w.gf2;
-    const uint64_t* const wit_z64 = w.z64;
-    const size_t n_gf2 = w.n_gf2, n_z64 = w.n_z64;
-    if (rep_count == 0 || rep_count % 8 || rep_begin % 8 || rep_begin + rep_count > RV_TOTAL_REPS) return RV_E_ARG;
-    *out = nullptr;
-    const Compiled& cc = c->cc;
-    if (n_gf2 < cc.n_in || n_z64 < cc.n_in64) return RV_E_WITNESS_SHORT;
-    if ((cc.n_in && !wit_gf2) || (cc.n_in64 && !wit_z64)) return RV_E_ARG;
-    HIPCHK(hipSetDevice(ctx->device));
-    rv_shard* s = new rv_shard();
-    s->ctx = ctx;
-    s->c = c;
-    s->rep_begin = rep_begin;
-    s->R = rep_count;
-    s->NQ = rep_count / 4;
-    int rc = RV_OK;
-    auto fail = [&](int code) {
-        rv_shard_destroy(s);
-        return code;
-    };
-    // defer_sync callers (rv_prove and its relatives) wait for the stream before they return, so the page-locked input
-    // staging buffer is free again by the next call: seeds and witness go over in ONE asynchronous copy
-    const size_t seed_bytes = (size_t)s->R * 16;
-    const bool stage_in = defer_sync && seed_bytes + cc.n_in <= rv_ctx::IN_STAGE_BYTES &&
-                          (ctx->h_in || hipHostMalloc((void**)&ctx->h_in, rv_ctx::IN_STAGE_BYTES, hipHostMallocDefault) == hipSuccess);
-    if (!stage_in) (void)hipGetLastError();
-    if (stage_in) {
-        if ((rc = dalloc(ctx, seed_bytes + std::max<size_t>(cc.n_in, 1), &s->d_seeds)) || (rc = dalloc(ctx, (size_t)s->R * 128, &s->d_keys))) return fail(rc);
-        s->d_wit = s->d_seeds + seed_bytes;  // (inside d_seeds' block: the arena ignores it on release)
-        memcpy(ctx->h_in, seeds, seed_bytes);
-        // (a witness in device memory: only the seeds are staged, the witness is copied behind them from where it lies)
-        const size_t staged_wit = w.dev ? 0 : cc.n_in;
-        if (staged_wit) memcpy(ctx->h_in + seed_bytes, wit_gf2, staged_wit);
-        if (hipMemcpyAsync(s->d_seeds, ctx->h_in, seed_bytes + staged_wit, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
-        if (w.dev && cc.n_in && hipMemcpyAsync(s->d_wit, wit_gf2, cc.n_in, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
-    } else {
-        if ((rc = dalloc(ctx, seed_bytes, &s->d_seeds)) || (rc = dalloc(ctx, (size_t)s->R * 128, &s->d_keys)) ||
-            (rc = dalloc(ctx, std::max<size_t>(cc.n_in, 1), &s->d_wit)))
-            return fail(rc);
-        if (hipMemcpyAsync(s->d_seeds, seeds, seed_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
-        if (cc.n_in && hipMemcpyAsync(s->d_wit, wit_gf2, cc.n_in, w.kind(), ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
-    }
-    if (cc.n_in64) {
-        if ((rc = dalloc(ctx, cc.n_in64, &s->d_wit64))) return fail(rc);
-        if (hipMemcpyAsync(s->d_wit64, wit_z64, cc.n_in64 * 8, w.kind(), ctx->stream) != hipSuccess)
-            return fail(RV_E_DEVICE);
-    }
-    wit_count(w, cc.n_in + cc.n_in64 * 8);
-    static const bool vclr_on = [] {
-        const char* e = getenv("RV_VCLR");
-        return !e || atoi(e) != 0;
-    }();
-    const bool use_vclr = vclr_on && c->vclr_ok && (s->NQ == 64 || s->NQ == 32 || s->NQ == 16 || s->NQ == 8);
-    s->z64f = c->z64f_ok && z64_fused_on() && z64_fused_supports(s->NQ) && !g_recorder;
-    {
-        // the mask generator beside the level launches (RV_OVERLAP=0 turns it off; RV_OVERLAP_MIN = fewest CTR blocks): wide circuits
-        // only -- a level must be long enough to hide a share of the cipher behind
-        const int ov_mode = getenv("RV_OVERLAP") ? atoi(getenv("RV_OVERLAP")) : 1;  // (read at every call: bench.py and the tools switch it)
-        const uint64_t ov_min = getenv("RV_OVERLAP_MIN") ? strtoull(getenv("RV_OVERLAP_MIN"), nullptr, 0) : 8192;  // (per call: the tests lower it)
-        s->overlap = ov_mode != 0 && !g_recorder && aes_col4_supports(s->NQ) &&
-                     cc.n_masks_pad / 128 >= ov_min;
-    }
-    ctx->phase(RV_PH_SETUP);
-    ctx->count();
-    // (unrecorded proofs: the player keys come out of the one key-setup launch of shard_setup_prg)
-    s->keys_deferred = !g_recorder && s->R == 4 * s->NQ;
-    if (!s->keys_deferred) launch_expand_seeds(ctx->stream, s->d_seeds, s->R, s->d_keys);
-    {
-        g_ht.mark("inputs");
-        if ((rc = shard_setup_prg(s, nullptr))) return fail(rc);
-        g_ht.mark("prg");
-        if (ec) s->ec = ec;  // (the caller made sure this path is taken)
-        InterpParams p{};
-        p.wit = s->d_wit;
-        Interp64Params p64{};
-        p64.wit = s->d_wit64;
-        int mode = MODE_PROVE;
-        if (use_vclr) {
-            // eligible circuits (whole proofs and the repetition shards with a specialised interpreter): cleartext values
-            // instead of corr rows (internal.h: MODE_PROVE_V)
-            if ((rc = dalloc(ctx, (size_t)cc.n_rows, &s->d_vclr))) return fail(rc);
-            // (the zero row's value is cleared by k_shard_init: shard_run_alloc)
-            p.vclr = s->d_vclr;
-            mode = MODE_PROVE_V;
-        }
-        if ((rc = shard_run(s, mode, p, p64))) return fail(rc);
-    }
-    if ((rc = shard_join(s))) return fail(rc);
-    if (defer_sync) {
-        ctx->prof.calls++;
-        *out = s;
-        return RV_OK;
-    }
-    int err = 0;
-    if (hipMemcpyAsync(&err, s->d_err, sizeof err, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail(RV_E_DEVICE);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
-        return fail(RV_E_DEVICE);
-    }
-    ctx->collect();
-    ctx->prof.calls++;
-    if (err) return fail(RV_E_WITNESS_INVALID);
-    *out = s;
-    return RV_OK;
-}
 
 extern "C" int rv_shard_digests_device(rv_shard* s, void** dptr) {
     if (!s || !dptr) return RV_E_ARG;

@@ -424,18 +424,13 @@ static int stream_begin_impl(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, co
         // context's arena holds idle and would hand back)
         S->keep_cap = std::min<uint64_t>({(uint64_t)total_b / 8, ((uint64_t)free_b + (uint64_t)ctx->cached_bytes) / 2, (uint64_t)32 << 30});
     }
-    uint8_t os_seeds[RV_TOTAL_REPS * RV_KEY_SIZE];
-    if (!seeds) {  // proof/mod.rs:131-134 uses OsRng
-        size_t got = 0;
-        while (got < sizeof os_seeds) {
-            ssize_t n = getrandom(os_seeds + got, sizeof os_seeds - got, 0);
-            if (n <= 0) {
-                delete S;
-                return RV_E_DEVICE;
-            }
-            got += (size_t)n;
+    uint8_t drawn[RV_TOTAL_REPS * RV_KEY_SIZE];
+    if (!seeds) {
+        if (int rs = os_seeds(drawn, sizeof drawn)) {
+            delete S;
+            return rs;
         }
-        seeds = os_seeds;
+        seeds = drawn;
     }
     constexpr uint32_t R = rv_stream::R, NQ = rv_stream::NQ;
     int rc;
@@ -1590,27 +1585,14 @@ static int stream_commit_impl(rv_stream* S, uint8_t comm_out[RV_HASH_SIZE]) {
     ctx->phase(-1);
     // ---- layout of the proof from the totals, then Fiat-Shamir on the device
     S->tot = S->run;
-    Compiled fake;
-    fake.n_rec = S->tot.n_rec;
-    fake.n_pre = S->tot.n_pre;
-    fake.n_in = S->tot.n_in;
-    fake.n_rec64 = S->tot.n_rec64;
-    fake.n_corr64 = S->tot.n_corr64;
-    fake.n_in64 = S->tot.n_in64;
-    uint8_t canon[RV_TOTAL_REPS];
-    for (uint32_t r = 0; r < R; r++) canon[r] = r < RV_ONLINE_REPS ? 0 : RV_PLAYERS;
-    S->L = open_layout(fake, canon, R, /*framed=*/true);
-    constexpr size_t OL_WORDS = (sizeof(OnlineList) + 7) / 8;
-    constexpr size_t FS_TAIL = 32 + RV_TOTAL_REPS + 8;
+    S->L = open_layout_of(S->tot.n_rec, S->tot.n_pre, S->tot.n_in, S->tot.n_rec64, S->tot.n_corr64, S->tot.n_in64, RV_ONLINE_REPS, RV_PREPROCESSING_REPS,
+                          /*framed=*/true);
+    constexpr size_t OL_WORDS = OPEN_OL_WORDS, FS_TAIL = OPEN_FS_TAIL;
     if ((rc = dalloc(ctx, R + FS_TAIL, &S->d_omit)) || (rc = dalloc(ctx, (size_t)8 * R + OL_WORDS, &S->d_offs)) ||
         (rc = dalloc(ctx, std::max<size_t>(S->L.total, 1), &S->d_proof)))
         return S->sticky = rc;
     HIPCHK(hipMemsetAsync(S->d_proof, 0, std::max<size_t>(S->L.total, 1), st));
-    FsLayout F{};
-    for (int k = 0; k < 4; k++) F.base[k] = S->L.base[k];
-    F.sz2 = S->L.sz2, F.sz64 = S->L.sz64, F.l2r = S->L.l2r, F.l2c = S->L.l2c, F.l64r = S->L.l64r, F.l64c = S->L.l64c;
-    F.framed = 1;
-    F.comm2 = S->d_proof;  // a framed proof starts with comm
+    const FsLayout F = fs_layout_of(S->L, /*exact=*/true, S->d_proof);  // (a framed proof starts with comm)
     OnlineList* d_ol = (OnlineList*)(S->d_offs + (size_t)8 * R);
     ctx->phase(RV_PH_OPEN);
     launch_fs_challenge(st, S->d_h, F, 0, R, S->d_omit + R, S->d_omit, S->d_omit + R + 32, S->d_offs, d_ol, (uint32_t*)(S->d_omit + R + 32 + RV_TOTAL_REPS));
@@ -1728,12 +1710,7 @@ static int stream_finish_impl(rv_stream* S, uint8_t** proof, size_t* proof_len, 
     ctx->collect();
     ctx->release(d_dst_rows);
     ctx->release(d_ol);
-    size_t off = 32;
-    const uint64_t counts[4] = {RV_ONLINE_REPS, RV_PREPROCESSING_REPS, RV_ONLINE_REPS, RV_PREPROCESSING_REPS};
-    for (int k = 0; k < 4; k++) {
-        put_le64(out + off, counts[k]);
-        off += 8 + S->L.len[k];
-    }
+    frame_counts_at(out, S->L.base);
     *proof = out;
     *proof_len = S->L.total;
     S->sticky = RV_E_ARG;  // a finished stream takes no further calls (rv_stream_abort releases it)

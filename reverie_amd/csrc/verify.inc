@@ -357,24 +357,16 @@ static int groups_ok(const uint8_t* groups, uint32_t n_groups) {
 
 extern "C" int rv_verify_shard_groups(rv_ctx* ctx, const rv_circuit* c, const uint8_t* proof, size_t proof_len, const uint8_t* groups,
                                       uint32_t n_groups, uint8_t* digests, int* zero_checks_ok) {
-    try {  // no C++ exception may cross the C boundary
-        return verify_groups_impl(ctx, c, proof, proof_len, groups, n_groups, digests, zero_checks_ok);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return verify_groups_impl(ctx, c, proof, proof_len, groups, n_groups, digests, zero_checks_ok); });
 }
 
 extern "C" int rv_verify_shard_ex(rv_ctx* ctx, const rv_circuit* c, const uint8_t* proof, size_t proof_len, uint32_t slot_begin,
                                   uint32_t slot_count, uint8_t* digests, int* zero_checks_ok) {
     if (slot_count == 0 || slot_count % 8 || slot_begin % 8 || slot_begin + slot_count > RV_TOTAL_REPS) return RV_E_ARG;
-    try {
+    return guarded([&] {
         const std::vector<uint8_t> g = range_groups(slot_begin, slot_count);
         return verify_groups_impl(ctx, c, proof, proof_len, g.data(), (uint32_t)g.size(), digests, zero_checks_ok);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    });
 }
 
 extern "C" int rv_verify_shard(rv_ctx* ctx, const rv_circuit* c, const uint8_t* proof, size_t proof_len, uint32_t slot_begin,
@@ -749,17 +741,7 @@ struct VerifyRun {
     // operations of ~25 us each; see rv_prove_impl), unless it could not be had.  zero_checks_ok may be null.
     int digests_out(uint8_t* digests, int* zero_checks_ok) {
         int dev_flags = 0;  // RV_DEV_ZERO_CHECK: an AssertZero of an opened repetition did not reconstruct to zero
-        uint8_t* stage_dev = nullptr;
-        if (!g_recorder) {
-            if (!ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, rv_ctx::STAGE_BYTES, hipHostMallocMapped) != hipSuccess) {
-                (void)hipGetLastError();
-                ctx->h_stage = nullptr;
-            }
-            if (ctx->h_stage && hipHostGetDevicePointer((void**)&stage_dev, ctx->h_stage, 0) != hipSuccess) {
-                (void)hipGetLastError();
-                stage_dev = nullptr;
-            }
-        }
+        uint8_t* const stage_dev = g_recorder ? nullptr : ctx->stage_mapped();
         if (stage_dev) {
             launch_store_words(ctx->stream, (const uint32_t*)s->d_h, R * 8, (uint32_t*)stage_dev, zero_checks_ok ? s->d_err : nullptr, (int*)(stage_dev + (size_t)R * 32));
             HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -850,12 +832,7 @@ static int rv_verify_finish_impl(const uint8_t* proof, size_t proof_len, const u
 
 extern "C" int rv_verify_finish_ex(const uint8_t* proof, size_t proof_len, const uint8_t* slot_digests, uint32_t flags,
                                    int zero_checks_ok, int* ok) {
-    try {
-        return rv_verify_finish_impl(proof, proof_len, slot_digests, flags, zero_checks_ok, ok);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return rv_verify_finish_impl(proof, proof_len, slot_digests, flags, zero_checks_ok, ok); });
 }
 
 extern "C" int rv_verify_finish(const uint8_t* proof, size_t proof_len, const uint8_t* slot_digests, int* ok) {
@@ -866,12 +843,7 @@ extern "C" int rv_verify_finish(const uint8_t* proof, size_t proof_len, const ui
 static int rv_verify_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* proof, size_t proof_len, uint32_t flags, int* ok);
 
 extern "C" int rv_verify_ex(rv_ctx* ctx, const rv_circuit* c, const uint8_t* proof, size_t proof_len, uint32_t flags, int* ok) {
-    try {  // no C++ exception may cross the C boundary
-        return rv_verify_impl(ctx, c, proof, proof_len, flags, ok);
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+    return guarded([&] { return rv_verify_impl(ctx, c, proof, proof_len, flags, ok); });
 }
 
 extern "C" int rv_verify(rv_ctx* ctx, const rv_circuit* c, const uint8_t* proof, size_t proof_len, int* ok) {

@@ -66,15 +66,7 @@ static int verify_device_impl(rv_ctx* ctx, const rv_circuit* c, const uint8_t* c
         HIPCHK(hipMemcpyAsync(d_lens, lens64, sizeof lens64, hipMemcpyHostToDevice, ctx->stream));
     }
     uint64_t head[VW_HEAD_WORDS];
-    uint8_t* stage_dev = nullptr;
-    if (!ctx->h_stage && hipHostMalloc((void**)&ctx->h_stage, rv_ctx::STAGE_BYTES, hipHostMallocMapped) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->h_stage = nullptr;
-    }
-    if (ctx->h_stage && hipHostGetDevicePointer((void**)&stage_dev, ctx->h_stage, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        stage_dev = nullptr;
-    }
+    uint8_t* const stage_dev = ctx->stage_mapped();
     launch_parse_proof(ctx->stream, d_bytes, len, framing, d_lens, d_table, (uint64_t*)stage_dev);
     HIPCHK(hipGetLastError());
     if (!stage_dev) HIPCHK(hipMemcpyAsync(head, d_table + VW_HEAD, sizeof head, hipMemcpyDeviceToHost, ctx->stream));

@@ -37,11 +37,7 @@ static bool wit_overlaps(const WitSrc& w, size_t batch, const void* p, size_t le
 }
 
 // bincode(Proof) bytes of one proof of the circuit (the same for every witness: 40 / 216 split)
-static size_t proof_total_bytes(const rv_circuit* c) {
-    uint8_t canon[RV_TOTAL_REPS];
-    for (uint32_t r = 0; r < RV_TOTAL_REPS; r++) canon[r] = r < RV_ONLINE_REPS ? 0 : RV_PLAYERS;
-    return open_layout(c->cc, canon, RV_TOTAL_REPS, true).total;
-}
+static size_t proof_total_bytes(const rv_circuit* c) { return whole_proof_layout(c->cc).total; }
 
 extern "C" int rv_prove_wdev(rv_ctx* ctx, const rv_circuit* c, const rv_dev_witness* dw, const uint8_t* seeds, uint8_t** proof, size_t* proof_len) {
     if (!ctx || !c || !dw || !proof || !proof_len) return RV_E_ARG;

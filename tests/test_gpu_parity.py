@@ -1213,7 +1213,7 @@ def test_compile_hint_whole_prover(rv, oracle, rule_seeds):
 
 def test_early_corrections_path(rv, oracle, rule_seeds, monkeypatch):
     """rv_prove's early-corrections path (the corrections vectors of ALL repetitions cross PCIe before the challenge
-    exists, the host copies the 40 opened ones into the proof, a kernel writes the rest around them: csrc/api.hip) on
+    exists, the host copies the 40 opened ones into the proof, a kernel writes the rest around them: csrc/prove.inc, csrc/shard.inc) on
     circuits small enough for the oracle, with the size threshold lowered: the oracle's bytes for every chunk count,
     Mul counts that are and are not multiples of 8 (the always-present last byte), the plain path's bytes with
     RV_EARLY=0, an invalid witness reported, and the path really taken (rv_hook_early_proofs)."""
