@@ -1042,6 +1042,43 @@ int rv_hook_z64_fused_grid(uint32_t qw, uint32_t n_qg, uint32_t cus, uint32_t n_
  * B2A gate (no table: *n_levels = 0); 2 a Mul's mask pair straddles cipher blocks; 3 more than 64 Input block runs; 4 no Z64 gate. */
 int rv_hook_z64_fused_levels(const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, uint32_t *out, size_t cap,
                              size_t *n_levels, int *eligible);
+/* The transcript-hash kernels (BLAKE3 chunk kernels, trees, the incremental tree, the digest join), one production launch at a time
+ * on caller-supplied data (tests/test_gpu_b3_kernels.py, reference tests/b3_ref.py).  Kernel numbers -- chunk kernels: 1 a repetition
+ * per lane, 2 a quad word per lane, 3 a chunk per wavefront (rows of 64 quad words, no quad list); tree tops: 1 a lane per repetition,
+ * 2 the 64-node workgroup top, 3 the 512-node one; small pair: 1 a quad of lanes per compression, 2 a lane per repetition.
+ * `choice` = 0: production's own pick; else that kernel through the launch code production runs after picking -- RV_E_ARG, before
+ * anything is launched, when the kernel does not take the shape.  `batch` = 0: launched directly; 2..64: recorded that many times on
+ * as many inputs laid end to end, then replayed as one batch (the launchers see the batch).  Every output buffer is filled with 0xA5
+ * before the launch and returned whole, its size per input given by the caller (at least what the launch writes).
+ * rv_hook_b3_plan (host only): what production picks for a preprocessing stream of n_pre and an online stream of n_on events in rows
+ * of NQ quad words (`listed`: the online stream with a quad list of n_quads words), with a recorder of that batch (0: none) --
+ * out = online chunk kernel (0: nothing launched), preprocessing chunk kernel, {reduction launches, nodes at the top, top kernel} of
+ * the online and of the preprocessing tree, small pair (0: not taken), big pair taken, its launches, its two streams' nodes at the
+ * shared top (preprocessing, online). */
+int rv_hook_b3_plan(uint64_t n_pre, uint64_t n_on, uint32_t NQ, int listed, uint32_t n_quads, uint32_t batch, uint32_t out[13]);
+/* kind 0: byte rows [n][width] u32; 1: bit rows [n][width / 2] u8 (width = NQ); 2: contiguous streams [width][stride_words] u64 of which
+ * n words are hashed (width = R; choice must be 0) -> cvs [n_chunks][R][8] in front of cv_words words; *chosen: the kernel launched. */
+int rv_hook_b3_chunks(rv_ctx *ctx, int kind, const void *stream, uint64_t n, uint32_t width, uint64_t stride_words, const uint32_t *quads,
+                      uint32_t n_quads, uint64_t chunk_base, uint32_t root_ok, uint32_t choice, uint32_t batch, uint32_t *cvs, uint64_t cv_words,
+                      uint32_t *chosen);
+/* Both transcripts of a small proof in two shared launches: chaining values and digests of both; *taken = 0: the launcher declined. */
+int rv_hook_b3_pair_small(rv_ctx *ctx, const uint8_t *pre, uint64_t n_pre, const uint32_t *on, uint64_t n_on, uint32_t NQ, const uint32_t *quads,
+                          uint32_t n_quads, uint32_t choice, uint32_t batch, uint32_t *cv_pre, uint64_t cv_pre_words, uint32_t *cv_on,
+                          uint64_t cv_on_words, uint32_t *dig_pre, uint32_t *dig_on, uint64_t dig_words, uint32_t *taken);
+/* The shared chunk launch of a large proof's two transcripts (rows of 64 quad words). */
+int rv_hook_b3_pair_big_chunks(rv_ctx *ctx, const uint8_t *pre, uint64_t n_pre, const uint32_t *on, uint64_t n_on, const uint32_t *quads, uint32_t n_quads,
+                               uint32_t *cv_pre, uint64_t cv_pre_words, uint32_t *cv_on, uint64_t cv_on_words);
+/* The tree over cvs [n][R][8]; plan[3] = reduction launches, nodes at the top, top kernel. */
+int rv_hook_b3_tree(rv_ctx *ctx, const uint32_t *cvs, uint64_t n, uint32_t R, uint32_t choice, uint32_t batch, uint32_t *digest, uint64_t dig_words,
+                    uint32_t plan[3]);
+/* The two trees of a large proof in shared launches. */
+int rv_hook_b3_pair_big_tree(rv_ctx *ctx, const uint32_t *cvs_a, uint64_t n_a, const uint32_t *cvs_b, uint64_t n_b, uint32_t R, uint32_t *dig_a,
+                             uint32_t *dig_b, uint64_t dig_words, uint32_t *launches);
+/* The streaming prover's incremental tree over B streams (cvs [B][n][R][8]): n - 1 values absorbed in pieces, the last one closes. */
+int rv_hook_b3_incremental(rv_ctx *ctx, const uint32_t *cvs, uint64_t n, uint32_t R, uint32_t B, const uint64_t *pieces, uint32_t n_pieces,
+                           uint32_t *digest, uint64_t dig_words);
+/* The digest join: digs [4][R][8] (pre2, on2, pre64, on64) -> h [R][32] in front of h_bytes bytes. */
+int rv_hook_b3_join(rv_ctx *ctx, const uint32_t *digs, uint32_t R, uint32_t batch, uint8_t *h, uint64_t h_bytes);
 /* The two gate-stream compilers against each other (host only): the program is compiled by the sequential compiler and by the
  * parallel one with `threads` host threads (>= 2), whatever its size, and the results are compared field by field.
  * *diff = 0: identical; > 0: a number naming the first differing table (csrc/compile_par.cpp, compiled_diff); -1: the parallel

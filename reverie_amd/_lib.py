@@ -121,6 +121,8 @@ SYMBOLS = [
     "rv_bristol_header", "rv_bristol_parse_device", "rv_hook_bristol_tiles",
     "rv_program_from_bincode_device", "rv_program_to_bincode_device", "rv_hook_bincode_tiles",
     "rv_hook_prove_schedule",
+    "rv_hook_b3_plan", "rv_hook_b3_chunks", "rv_hook_b3_pair_small", "rv_hook_b3_pair_big_chunks", "rv_hook_b3_tree", "rv_hook_b3_pair_big_tree",
+    "rv_hook_b3_incremental", "rv_hook_b3_join",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -212,6 +214,17 @@ ARGTYPES = {
     "rv_program_from_bincode_device": [_P, _P, _Z, C.c_int, _P, _Z, C.POINTER(C.c_size_t), C.POINTER(ProgramInfo)],
     "rv_program_to_bincode_device": [_P, _P, _Z, _P, _Z, C.POINTER(C.c_size_t)],
     "rv_hook_bincode_tiles": [C.POINTER(C.c_uint32)],
+    # the transcript-hash kernels (parity hooks)
+    "rv_hook_b3_plan": [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)],
+    "rv_hook_b3_chunks": [_P, C.c_int, _P, C.c_uint64, C.c_uint32, C.c_uint64, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64,
+                          C.POINTER(C.c_uint32)],
+    "rv_hook_b3_pair_small": [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, _P, _P,
+                              C.c_uint64, C.POINTER(C.c_uint32)],
+    "rv_hook_b3_pair_big_chunks": [_P, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64],
+    "rv_hook_b3_tree": [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint32)],
+    "rv_hook_b3_pair_big_tree": [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, _P, _P, C.c_uint64, C.POINTER(C.c_uint32)],
+    "rv_hook_b3_incremental": [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint64],
+    "rv_hook_b3_join": [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64],
 }
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1

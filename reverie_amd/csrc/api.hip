@@ -1638,6 +1638,7 @@ extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
 #include "hooks.inc"
 #include "feed_ops.inc"
 #include "stream.inc"
+#include "hooks_b3.inc"
 #include "comm.inc"
 #include "eval.inc"
 #include "eval_stream.inc"

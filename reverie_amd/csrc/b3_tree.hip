@@ -469,19 +469,28 @@ __global__ __launch_bounds__(64) void k_b3_tree_tail_pair(const uint32_t* __rest
                                                           uint32_t n_b, uint32_t* __restrict__ dig_b, uint32_t R) {
     B_k_b3_tree_tail_pair{}(in_a, n_a, dig_a, in_b, n_b, dig_b, R);
 }
-// true (and two launches issued) when both streams are short enough for the paired kernels; d_cv_a / d_cv_b each hold one
-// stream's chunk chaining values (the tree tops need no second buffer at this size).  d_quads / n_quads as in
-// launch_b3_stream (the verifier hashes the online stream of the opened quads only; n_quads = 0 with a list: not paired)
-bool launch_b3_pair_small(hipStream_t st, const uint8_t* d_pre, uint64_t n_pre, const uint32_t* d_on, uint64_t n_on, uint32_t NQ, uint32_t* d_cv_a,
-                          uint32_t* d_cv_b, uint32_t* d_dig_pre, uint32_t* d_dig_on, const uint32_t* d_quads, uint32_t n_quads) {
-    if (d_quads && !n_quads) return false;
-    const uint64_t c_pre = n_pre == 0 ? 1 : (n_pre + 1023) / 1024, c_on = n_on == 0 ? 1 : (n_on + 1023) / 1024;
-    const uint32_t batch = g_recorder ? g_recorder->batch : 1u;
+// The launchers below decide and launch in two steps: a b3_choose_* / b3_plan_* function says which kernel takes a shape (pure: the
+// batch of the calling thread's recorder is an argument -- 0: no recorder), a launch_*_as / *_run function issues it.  Production calls
+// the first and hands its answer to the second; the kernel tests (hooks_b3.inc: rv_hook_b3_*) call the second with any choice that takes the
+// shape, so every kernel is reachable at small shapes, and tests/test_b3_plan_host.py pins the choices (rv_hook_b3_plan).
+static inline uint32_t b3_batch_now() { return g_recorder ? std::max(g_recorder->batch, 1u) : 0u; }
+static inline uint64_t b3_chunks_of(uint64_t n_events) { return n_events == 0 ? 1 : (n_events + 1023) / 1024; }
+
+// are both streams short enough for the paired kernels, and in which form?  d_quads / n_quads as in launch_b3_stream (the verifier
+// hashes the online stream of the opened quads only; n_quads = 0 with a list: not paired)
+B3PairSmall b3_choose_pair_small(uint64_t n_pre, uint64_t n_on, uint32_t NQ, bool listed, uint32_t n_quads, uint32_t batch) {
+    if (listed && !n_quads) return B3P_NONE;
+    const uint64_t c_pre = b3_chunks_of(n_pre), c_on = b3_chunks_of(n_on);
     // (the same "few chunks" rule as the separate launchers' one-repetition-per-lane choice, and trees the small tail kernel takes)
-    if (c_pre > 64 || c_on > 64 || std::max(c_pre, c_on) * NQ * batch >= 64 * 1024) return false;
+    if (c_pre > 64 || c_on > 64 || std::max(c_pre, c_on) * NQ * (batch ? batch : 1u) >= 64 * 1024) return B3P_NONE;
+    return batch ? B3P_LANE : B3P_QUAD;  // (one proof: a quad of lanes per repetition's chain)
+}
+// two launches; d_cv_a / d_cv_b each hold one stream's chunk chaining values (the tree tops need no second buffer at this size)
+void launch_b3_pair_small_as(hipStream_t st, B3PairSmall form, const uint8_t* d_pre, uint64_t n_pre, const uint32_t* d_on, uint64_t n_on, uint32_t NQ,
+                             uint32_t* d_cv_a, uint32_t* d_cv_b, uint32_t* d_dig_pre, uint32_t* d_dig_on, const uint32_t* d_quads, uint32_t n_quads) {
+    const uint64_t c_pre = b3_chunks_of(n_pre), c_on = b3_chunks_of(n_on);
     const uint32_t R = NQ * 4;
-    if (!g_recorder) {
-        // (one proof: a quad of lanes per repetition's chain)
+    if (form == B3P_QUAD) {
         const uint32_t b_pre = (uint32_t)((c_pre * NQ * 16 + 255) / 256), b_on = (uint32_t)((c_on * (d_quads ? n_quads : NQ) * 16 + 255) / 256);
         hipLaunchKernelGGL(k_b3_chunks_pair_q, dim3(b_pre + b_on), dim3(256), 0, st, d_pre, n_pre, d_cv_a, d_on, n_on, d_cv_b, NQ, b_pre, d_quads, n_quads);
     } else {
@@ -490,6 +499,13 @@ bool launch_b3_pair_small(hipStream_t st, const uint8_t* d_pre, uint64_t n_pre, 
     }
     launch<B_k_b3_tree_tail_pair, 64>(k_b3_tree_tail_pair, st, dim3(2 * R), dim3(64), (const uint32_t*)d_cv_a, (uint32_t)c_pre, d_dig_pre,
                                       (const uint32_t*)d_cv_b, (uint32_t)c_on, d_dig_on, R);
+}
+// true (and two launches issued) when both streams are short enough for the paired kernels
+bool launch_b3_pair_small(hipStream_t st, const uint8_t* d_pre, uint64_t n_pre, const uint32_t* d_on, uint64_t n_on, uint32_t NQ, uint32_t* d_cv_a,
+                          uint32_t* d_cv_b, uint32_t* d_dig_pre, uint32_t* d_dig_on, const uint32_t* d_quads, uint32_t n_quads) {
+    const B3PairSmall form = b3_choose_pair_small(n_pre, n_on, NQ, d_quads != nullptr, n_quads, b3_batch_now());
+    if (form == B3P_NONE) return false;
+    launch_b3_pair_small_as(st, form, d_pre, n_pre, d_on, n_on, NQ, d_cv_a, d_cv_b, d_dig_pre, d_dig_on, d_quads, n_quads);
     return true;
 }
 
@@ -555,13 +571,14 @@ __global__ __launch_bounds__(512) void k_b3_tree_tail_pair_big(const uint32_t* _
 }
 static uint64_t b3_rpl1_lanes();
 // does launch_b3_pair_big take these two transcripts?  (both trees must end in the 256-thread tree top: more than 64 nodes left)
-bool b3_pair_big_ok(uint64_t n_pre, uint64_t n_on, uint32_t NQ, const uint32_t* d_quads, uint32_t n_quads) {
-    if (NQ != 64 || g_recorder || RV_B3_RPL != 4) return false;
-    if (d_quads && !n_quads) return false;
+// recording: a recorder is present (a batch of proofs: never)
+bool b3_pair_big_takes(uint64_t n_pre, uint64_t n_on, uint32_t NQ, bool listed_on, uint32_t n_quads, bool recording) {
+    if (NQ != 64 || recording || RV_B3_RPL != 4) return false;
+    if (listed_on && !n_quads) return false;
     for (int i = 0; i < 2; i++) {
         const uint64_t n_ev = i == 0 ? n_pre : n_on;
-        const bool listed = i == 1 && d_quads;  // (the online stream of the listed quad words only)
-        uint64_t n = n_ev == 0 ? 1 : (n_ev + 1023) / 1024;
+        const bool listed = i == 1 && listed_on;  // (the online stream of the listed quad words only)
+        uint64_t n = b3_chunks_of(n_ev);
         // (short transcripts: the separate launchers pick other chunk kernels; few listed quad words are hashed a repetition per lane anyway)
         if (!(listed && n_quads * 4 <= NQ) && n * (listed ? std::min(n_quads, NQ) : NQ) < b3_rpl1_lanes()) return false;
         while (n > B3_TAIL_PAIR) n = (n + 7) / 8;
@@ -569,14 +586,25 @@ bool b3_pair_big_ok(uint64_t n_pre, uint64_t n_on, uint32_t NQ, const uint32_t* 
     }
     return true;
 }
-// cv_a0 / cv_a1 and cv_b0 / cv_b1: ping-pong buffers of the preprocessing and the online stream (b3_stream_scratch_words each);
-// -> launches
-uint32_t launch_b3_pair_big(hipStream_t st, const uint8_t* d_pre, uint64_t n_pre, const uint32_t* d_on, uint64_t n_on, uint32_t NQ, uint32_t* cv_a0,
-                            uint32_t* cv_a1, uint32_t* cv_b0, uint32_t* cv_b1, uint32_t* d_dig_pre, uint32_t* d_dig_on, const uint32_t* d_quads,
-                            uint32_t n_quads) {
-    const uint32_t R = NQ * 4;
-    uint64_t n_a = n_pre == 0 ? 1 : (n_pre + 1023) / 1024, n_b = n_on == 0 ? 1 : (n_on + 1023) / 1024;
-    uint32_t launches = 1;
+bool b3_pair_big_ok(uint64_t n_pre, uint64_t n_on, uint32_t NQ, const uint32_t* d_quads, uint32_t n_quads) {
+    return b3_pair_big_takes(n_pre, n_on, NQ, d_quads != nullptr, n_quads, g_recorder != nullptr);
+}
+// the shared reduction launches of two trees of n_a and n_b chaining values, and the nodes each has left for the shared tree top
+B3PairBigPlan b3_plan_pair_big_tree(uint64_t n_a, uint64_t n_b) {
+    B3PairBigPlan p{0, 0, 0};
+    while (n_a > B3_TAIL_PAIR || n_b > B3_TAIL_PAIR) {
+        if (n_a > B3_TAIL_PAIR) n_a = (n_a + 7) / 8;
+        if (n_b > B3_TAIL_PAIR) n_b = (n_b + 7) / 8;
+        p.reduces++;
+    }
+    p.top_a = (uint32_t)n_a, p.top_b = (uint32_t)n_b;
+    return p;
+}
+// the chunk chaining values of both transcripts in one launch (NQ = 64): cv_a the preprocessing stream's, cv_b the online stream's
+void launch_b3_pair_big_chunks(hipStream_t st, const uint8_t* d_pre, uint64_t n_pre, const uint32_t* d_on, uint64_t n_on, uint32_t* cv_a0, uint32_t* cv_b0,
+                               const uint32_t* d_quads, uint32_t n_quads) {
+    const uint32_t NQ = 64;
+    const uint64_t n_a = b3_chunks_of(n_pre), n_b = b3_chunks_of(n_on);
     const uint32_t b_pre = (uint32_t)((n_a * 64 + 255) / 256);  // (a chunk per wavefront)
     if (d_quads && n_quads * 4 <= NQ) {
         // (the chaining values of skipped quad words stay whatever the buffer held: the tree above them runs on garbage and the caller
@@ -593,6 +621,11 @@ uint32_t launch_b3_pair_big(hipStream_t st, const uint8_t* d_pre, uint64_t n_pre
         launch<B_k_b3_chunks_pair_uni<0>, 256>(k_b3_chunks_pair_uni<0>, st, dim3(b_pre + b_on), dim3(256), d_pre, n_pre, cv_a0, d_on, n_on, cv_b0, b_pre,
                                               (const uint32_t*)nullptr, 0u);
     }
+}
+// both trees over n_a / n_b chaining values in cv_a0 / cv_b0 (cv_a1 / cv_b1: the other halves of the ping-pong pairs) -> launches
+uint32_t launch_b3_pair_big_tree(hipStream_t st, uint32_t* cv_a0, uint32_t* cv_a1, uint64_t n_a, uint32_t* cv_b0, uint32_t* cv_b1, uint64_t n_b, uint32_t R,
+                                 uint32_t* d_dig_pre, uint32_t* d_dig_on) {
+    uint32_t launches = 0;
     while (n_a > B3_TAIL_PAIR || n_b > B3_TAIL_PAIR) {
         const uint64_t out_a = (n_a + 7) / 8, out_b = (n_b + 7) / 8;
         const uint64_t threads = std::max(n_a > B3_TAIL_PAIR ? out_a : 0, n_b > B3_TAIL_PAIR ? out_b : 0) * R;
@@ -606,11 +639,34 @@ uint32_t launch_b3_pair_big(hipStream_t st, const uint8_t* d_pre, uint64_t n_pre
                                            (const uint32_t*)cv_b0, (uint32_t)n_b, d_dig_on, R);
     return launches + 1;
 }
+// cv_a0 / cv_a1 and cv_b0 / cv_b1: ping-pong buffers of the preprocessing and the online stream (b3_stream_scratch_words each);
+// -> launches
+uint32_t launch_b3_pair_big(hipStream_t st, const uint8_t* d_pre, uint64_t n_pre, const uint32_t* d_on, uint64_t n_on, uint32_t NQ, uint32_t* cv_a0,
+                            uint32_t* cv_a1, uint32_t* cv_b0, uint32_t* cv_b1, uint32_t* d_dig_pre, uint32_t* d_dig_on, const uint32_t* d_quads,
+                            uint32_t n_quads) {
+    launch_b3_pair_big_chunks(st, d_pre, n_pre, d_on, n_on, cv_a0, cv_b0, d_quads, n_quads);
+    return 1 + launch_b3_pair_big_tree(st, cv_a0, cv_a1, b3_chunks_of(n_pre), cv_b0, cv_b1, b3_chunks_of(n_on), NQ * 4, d_dig_pre, d_dig_on);
+}
 
-// tree reduction of n chunk chaining values per repetition; the roots land in d_digest ([R][8] words)
-uint32_t b3_reduce_tree(hipStream_t st, uint32_t* cur, uint32_t* nxt, uint64_t n, uint32_t R, uint32_t* d_digest) {
-    uint32_t launches = 1;
-    while (n > B3_TAIL) {  // two levels per launch while the level is wide
+// the launches of a tree over n chunk chaining values: k_b3_reduce<2> while the level is wider than the tree top takes, then the top.
+// A single chunk is already its own root (the chunk kernels applied the ROOT flag): every top just copies it.
+// Lane per repetition: always for a batch of proofs (gridDim.y supplies the parallelism), for a single proof only while
+// its n - 1 dependent compressions (~1.2 us each) beat the workgroup version's log2(n) levels with their barriers
+B3TreePlan b3_plan_tree(uint64_t n, uint32_t batch) {
+    B3TreePlan p{0, 0, B3T_TAIL512};
+    while (n > B3_TAIL) n = (n + 3) / 4, p.reduces++;  // two levels per launch while the level is wide
+    p.n_top = (uint32_t)n;
+    if (n <= 64 && (batch >= 8 || n <= 4))
+        p.top = B3T_LANE;
+    else if (n <= 64)
+        p.top = B3T_TAIL64;
+    return p;
+}
+// does this tree top take n nodes?  (k_b3_tree_lane: six slots; the workgroup tops: their LDS)
+bool b3_top_takes(B3TopKernel top, uint64_t n) { return n >= 1 && n <= (top == B3T_TAIL512 ? B3_TAIL : 64u); }
+// tree reduction of n chunk chaining values per repetition as planned; the roots land in d_digest ([R][8] words)
+uint32_t b3_reduce_tree_run(hipStream_t st, const B3TreePlan& plan, uint32_t* cur, uint32_t* nxt, uint64_t n, uint32_t R, uint32_t* d_digest) {
+    for (uint32_t i = 0; i < plan.reduces; i++) {
         const uint64_t n_out = (n + 3) / 4;
         const uint64_t threads = n_out * R;
         launch<B_k_b3_reduce<2>, 256>(k_b3_reduce<2>, st, dim3((unsigned)((threads + 255) / 256)), dim3(256), cur, n, R, nxt);
@@ -618,18 +674,17 @@ uint32_t b3_reduce_tree(hipStream_t st, uint32_t* cur, uint32_t* nxt, uint64_t n
         cur = nxt;
         nxt = t;
         n = n_out;
-        launches++;
     }
-    // a single chunk is already its own root (the chunk kernels applied the ROOT flag): cnt == 1 just copies
-    // lane per repetition: always for a batch of proofs (gridDim.y supplies the parallelism), for a single proof only while
-    // its n - 1 dependent compressions (~1.2 us each) beat the workgroup version's log2(n) levels with their barriers
-    if (n <= 64 && ((g_recorder && g_recorder->batch >= 8) || n <= 4))
+    if (plan.top == B3T_LANE)
         launch<B_k_b3_tree_lane, 64>(k_b3_tree_lane, st, dim3((R + 63) / 64), dim3(64), cur, (uint32_t)n, R, d_digest);
-    else if (n <= 64)
+    else if (plan.top == B3T_TAIL64)
         launch<B_k_b3_tree_tail<64>, 64>(k_b3_tree_tail_small, st, dim3(R), dim3(64), cur, (uint32_t)n, R, d_digest);
     else
         launch<B_k_b3_tree_tail<(int)B3_TAIL>, 256>(k_b3_tree_tail, st, dim3(R), dim3(256), cur, (uint32_t)n, R, d_digest);
-    return launches;
+    return plan.reduces + 1;
+}
+uint32_t b3_reduce_tree(hipStream_t st, uint32_t* cur, uint32_t* nxt, uint64_t n, uint32_t R, uint32_t* d_digest) {
+    return b3_reduce_tree_run(st, b3_plan_tree(n, b3_batch_now()), cur, nxt, n, R, d_digest);
 }
 
 size_t b3_stream_scratch_words(uint64_t n_events, uint32_t R) {
@@ -641,21 +696,40 @@ size_t b3_stream_scratch_words(uint64_t n_events, uint32_t R) {
 // long -- for transcripts that would not fill the chip's wavefront slots otherwise
 static uint64_t b3_rpl1_lanes() { return (uint64_t)128 * 1024; }  // (64-repetition shards of the 10^7-gate circuit: digests 0.47 -> 0.38 ms)
 
+// which kernel hashes a byte-row transcript of n chunks (listed: with a quad list of n_quads words; none listed: nothing to launch)
+// few lanes (a quarter of the row or less in the verifier; a transcript of a few chunks, i.e. a small circuit):
+// one repetition per lane gives four times the wavefronts, each a quarter as long
+B3ChunkKernel b3_choose_stream_chunks(uint64_t n, uint32_t NQ, bool listed, uint32_t n_quads, uint32_t batch) {
+    if (listed && !n_quads) return B3C_NONE;
+    const uint64_t threads = n * (listed ? n_quads : NQ);
+    if ((listed && n_quads * 4 <= NQ) || threads * (batch ? batch : 1u) < b3_rpl1_lanes()) return B3C_RPL1;
+    if (RV_B3_RPL == 4 && NQ == 64 && !listed) return B3C_UNI;
+    return RV_B3_RPL == 4 ? B3C_RPL4 : B3C_RPL1;
+}
+// does the kernel take rows of NQ quad words?  (a chunk per wavefront: full-width rows and no quad list; bit rows: two quad words a byte)
+bool b3_chunk_kernel_takes(B3ChunkKernel k, uint32_t NQ, bool listed, bool bits) {
+    if (!NQ || (bits && (NQ & 1 || listed))) return false;
+    return k == B3C_RPL1 || k == B3C_RPL4 || (k == B3C_UNI && NQ == 64 && !listed);
+}
 // chunk chaining values only ([n_chunks][R][8] into d_cv); chunk_base / root_ok: see B_k_b3_chunks
-void launch_b3_stream_chunks(hipStream_t st, const uint32_t* d_stream, uint64_t n_events, uint32_t NQ, uint32_t* d_cv, const uint32_t* d_quads,
-                             uint32_t n_quads, uint64_t chunk_base, uint32_t root_ok) {
-    const uint64_t n = n_events == 0 ? 1 : (n_events + 1023) / 1024;
+void launch_b3_stream_chunks_as(hipStream_t st, B3ChunkKernel k, const uint32_t* d_stream, uint64_t n_events, uint32_t NQ, uint32_t* d_cv, const uint32_t* d_quads,
+                                uint32_t n_quads, uint64_t chunk_base, uint32_t root_ok) {
+    const uint64_t n = b3_chunks_of(n_events);
     // (the chaining values of skipped quads stay whatever the scratch buffer held: the tree above them runs on
     // garbage and the caller replaces those digests)
     const uint64_t threads = n * (d_quads ? n_quads : NQ);
-    // few lanes (a quarter of the row or less in the verifier; a transcript of a few chunks, i.e. a small circuit):
-    // one repetition per lane gives four times the wavefronts, each a quarter as long
-    if ((d_quads && n_quads * 4 <= NQ) || threads * (g_recorder ? g_recorder->batch : 1u) < b3_rpl1_lanes())
+    if (k == B3C_NONE) return;
+    if (k == B3C_RPL1)
         launch<B_k_b3_chunks<1>, 256>(k_b3_chunks<1>, st, dim3((unsigned)((threads * 4 + 255) / 256)), dim3(256), d_stream, n_events, NQ, n, d_cv, d_quads, n_quads, chunk_base, root_ok);
-    else if (RV_B3_RPL == 4 && NQ == 64 && !d_quads)
+    else if (k == B3C_UNI)
         launch<B_k_b3_chunks<4, true>, 256>(k_b3_chunks_uni, st, dim3((unsigned)((threads + 255) / 256)), dim3(256), d_stream, n_events, NQ, n, d_cv, d_quads, n_quads, chunk_base, root_ok);
     else
-        launch<B_k_b3_chunks<RV_B3_RPL>, 256>(k_b3_chunks<RV_B3_RPL>, st, dim3((unsigned)((threads * (4 / RV_B3_RPL) + 255) / 256)), dim3(256), d_stream, n_events, NQ, n, d_cv, d_quads, n_quads, chunk_base, root_ok);
+        launch<B_k_b3_chunks<4>, 256>(k_b3_chunks<4>, st, dim3((unsigned)((threads + 255) / 256)), dim3(256), d_stream, n_events, NQ, n, d_cv, d_quads, n_quads, chunk_base, root_ok);
+}
+void launch_b3_stream_chunks(hipStream_t st, const uint32_t* d_stream, uint64_t n_events, uint32_t NQ, uint32_t* d_cv, const uint32_t* d_quads,
+                             uint32_t n_quads, uint64_t chunk_base, uint32_t root_ok) {
+    const B3ChunkKernel k = b3_choose_stream_chunks(b3_chunks_of(n_events), NQ, d_quads != nullptr, n_quads, b3_batch_now());
+    launch_b3_stream_chunks_as(st, k, d_stream, n_events, NQ, d_cv, d_quads, n_quads, chunk_base, root_ok);
 }
 
 uint32_t launch_b3_stream(hipStream_t st, const uint32_t* d_stream, uint64_t n_events, uint32_t NQ, uint32_t* d_cv_a,
@@ -667,20 +741,29 @@ uint32_t launch_b3_stream(hipStream_t st, const uint32_t* d_stream, uint64_t n_e
     return 1 + b3_reduce_tree(st, d_cv_a, d_cv_b, n, R, d_digest);  // launches
 }
 
-void launch_b3_stream_bits_chunks(hipStream_t st, const uint8_t* d_stream, uint64_t n_events, uint32_t NQ, uint32_t* d_cv, uint64_t chunk_base,
-                                  uint32_t root_ok) {
-    const uint64_t n = n_events == 0 ? 1 : (n_events + 1023) / 1024;
+// ... and a bit-row transcript (k_b3_chunks_bits1 / k_b3_chunks_bits / k_b3_chunks_bits_uni)
+// a transcript of a few chunks (small circuit, and no batch to supply the wavefronts): one repetition per lane
+B3ChunkKernel b3_choose_bits_chunks(uint64_t n, uint32_t NQ, uint32_t batch) {
+    if (n * NQ * (batch ? batch : 1u) < b3_rpl1_lanes()) return B3C_RPL1;
+    return NQ == 64 ? B3C_UNI : B3C_RPL4;
+}
+void launch_b3_stream_bits_chunks_as(hipStream_t st, B3ChunkKernel k, const uint8_t* d_stream, uint64_t n_events, uint32_t NQ, uint32_t* d_cv, uint64_t chunk_base,
+                                     uint32_t root_ok) {
+    const uint64_t n = b3_chunks_of(n_events);
     const uint64_t threads = n * NQ;
-    // a transcript of a few chunks (small circuit, and no batch to supply the wavefronts): one repetition per lane
-    if (threads * (g_recorder ? g_recorder->batch : 1u) < b3_rpl1_lanes())
+    if (k == B3C_RPL1)
         launch<B_k_b3_chunks_bits<1>, 256>(k_b3_chunks_bits1, st, dim3((unsigned)((threads * 4 + 255) / 256)), dim3(256), d_stream, n_events, NQ, n,
                                            d_cv, chunk_base, root_ok);
-    else if (NQ == 64)
+    else if (k == B3C_UNI)
         launch<B_k_b3_chunks_bits<4, true>, 256>(k_b3_chunks_bits_uni, st, dim3((unsigned)((threads + 255) / 256)), dim3(256), d_stream, n_events, NQ, n,
                                                  d_cv, chunk_base, root_ok);
     else
         launch<B_k_b3_chunks_bits<4>, 256>(k_b3_chunks_bits, st, dim3((unsigned)((threads + 255) / 256)), dim3(256), d_stream, n_events, NQ, n,
                                            d_cv, chunk_base, root_ok);
+}
+void launch_b3_stream_bits_chunks(hipStream_t st, const uint8_t* d_stream, uint64_t n_events, uint32_t NQ, uint32_t* d_cv, uint64_t chunk_base,
+                                  uint32_t root_ok) {
+    launch_b3_stream_bits_chunks_as(st, b3_choose_bits_chunks(b3_chunks_of(n_events), NQ, b3_batch_now()), d_stream, n_events, NQ, d_cv, chunk_base, root_ok);
 }
 
 uint32_t launch_b3_stream_bits(hipStream_t st, const uint8_t* d_stream, uint64_t n_events, uint32_t NQ, uint32_t* d_cv_a,

@@ -245,6 +245,14 @@ struct HookBufs {
         return RV_OK;
     }
     template <class T>
+    int filled(int byte, size_t count, T** d) {  // count elements of `byte` bytes
+        int rc = dalloc(ctx, std::max<size_t>(count, 1), d);
+        if (rc) return rc;
+        owned.push_back(*d);
+        HIPCHK(hipMemsetAsync(*d, byte, std::max<size_t>(count, 1) * sizeof(T), ctx->stream));
+        return RV_OK;
+    }
+    template <class T>
     int down(T* dst, const T* d, size_t count) {
         if (count) HIPCHK(hipMemcpyAsync(dst, d, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
         return RV_OK;

@@ -260,6 +260,38 @@ void launch_interp_batched(hipStream_t st, const Gate* d_gates, const LevelRange
 // large proofs: the two transcripts' trees in shared launches (b3_tree.hip); four ping-pong buffers of b3_stream_scratch_words each
 // (d_quads / n_quads as in launch_b3_stream: the verifier's online stream of the quad words with an opened repetition)
 bool b3_pair_big_ok(uint64_t n_pre, uint64_t n_on, uint32_t NQ, const uint32_t* d_quads = nullptr, uint32_t n_quads = 0);
+// Which transcript-hash kernel takes which shape (b3_tree.hip): every launcher is a pure choice -- `batch`: the batch of the calling
+// thread's recorder, 0 without one -- and a launch that takes the choice (launch_*_as, *_run).  rv_hook_b3_plan returns the choices.
+enum B3ChunkKernel : uint32_t { B3C_NONE = 0, B3C_RPL1 = 1, B3C_RPL4 = 2, B3C_UNI = 3 };  // a repetition per lane, a quad word per lane, a chunk per wavefront
+enum B3TopKernel : uint32_t { B3T_LANE = 1, B3T_TAIL64 = 2, B3T_TAIL512 = 3 };           // k_b3_tree_lane, k_b3_tree_tail_small, k_b3_tree_tail
+enum B3PairSmall : uint32_t { B3P_NONE = 0, B3P_QUAD = 1, B3P_LANE = 2 };                // not taken, k_b3_chunks_pair_q, k_b3_chunks_pair
+struct B3TreePlan {
+    uint32_t reduces, n_top;  // k_b3_reduce<2> launches, nodes left for the top
+    B3TopKernel top;
+};
+struct B3PairBigPlan {
+    uint32_t reduces, top_a, top_b;  // k_b3_reduce_pair launches, nodes of either stream left for k_b3_tree_tail_pair_big
+};
+B3ChunkKernel b3_choose_stream_chunks(uint64_t n_chunks, uint32_t NQ, bool listed, uint32_t n_quads, uint32_t batch);
+B3ChunkKernel b3_choose_bits_chunks(uint64_t n_chunks, uint32_t NQ, uint32_t batch);
+bool b3_chunk_kernel_takes(B3ChunkKernel k, uint32_t NQ, bool listed, bool bits);
+B3TreePlan b3_plan_tree(uint64_t n, uint32_t batch);
+bool b3_top_takes(B3TopKernel top, uint64_t n);
+B3PairSmall b3_choose_pair_small(uint64_t n_pre, uint64_t n_on, uint32_t NQ, bool listed, uint32_t n_quads, uint32_t batch);
+bool b3_pair_big_takes(uint64_t n_pre, uint64_t n_on, uint32_t NQ, bool listed_on, uint32_t n_quads, bool recording);
+B3PairBigPlan b3_plan_pair_big_tree(uint64_t n_a, uint64_t n_b);
+void launch_b3_stream_chunks_as(hipStream_t st, B3ChunkKernel k, const uint32_t* d_stream, uint64_t n_events, uint32_t NQ, uint32_t* d_cv, const uint32_t* d_quads,
+                                uint32_t n_quads, uint64_t chunk_base, uint32_t root_ok);
+void launch_b3_stream_bits_chunks_as(hipStream_t st, B3ChunkKernel k, const uint8_t* d_stream, uint64_t n_events, uint32_t NQ, uint32_t* d_cv, uint64_t chunk_base,
+                                     uint32_t root_ok);
+uint32_t b3_reduce_tree_run(hipStream_t st, const B3TreePlan& plan, uint32_t* cur, uint32_t* nxt, uint64_t n, uint32_t R, uint32_t* d_digest);
+void launch_b3_pair_small_as(hipStream_t st, B3PairSmall form, const uint8_t* d_pre, uint64_t n_pre, const uint32_t* d_on, uint64_t n_on, uint32_t NQ,
+                             uint32_t* d_cv_a, uint32_t* d_cv_b, uint32_t* d_dig_pre, uint32_t* d_dig_on, const uint32_t* d_quads, uint32_t n_quads);
+// launch_b3_pair_big's two parts: the chunk chaining values of both streams (NQ = 64) and the two trees over them
+void launch_b3_pair_big_chunks(hipStream_t st, const uint8_t* d_pre, uint64_t n_pre, const uint32_t* d_on, uint64_t n_on, uint32_t* cv_a0, uint32_t* cv_b0,
+                               const uint32_t* d_quads, uint32_t n_quads);
+uint32_t launch_b3_pair_big_tree(hipStream_t st, uint32_t* cv_a0, uint32_t* cv_a1, uint64_t n_a, uint32_t* cv_b0, uint32_t* cv_b1, uint64_t n_b, uint32_t R,
+                                 uint32_t* d_dig_pre, uint32_t* d_dig_on);
 uint32_t launch_b3_pair_big(hipStream_t st, const uint8_t* d_pre, uint64_t n_pre, const uint32_t* d_on, uint64_t n_on, uint32_t NQ, uint32_t* cv_a0,
                             uint32_t* cv_a1, uint32_t* cv_b0, uint32_t* cv_b1, uint32_t* d_dig_pre, uint32_t* d_dig_on, const uint32_t* d_quads = nullptr,
                             uint32_t n_quads = 0);
