@@ -938,6 +938,46 @@ int rv_program_to_bincode_device(rv_ctx *ctx, const rv_op *d_ops, size_t n_ops, 
  * tiles per workgroup of the composing scan (the lengths the tests go around) */
 int rv_hook_bincode_tiles(uint32_t out[2]);
 
+/* A program file read in windows: rv_program_from_bincode_device for a file that is handed over in consecutive byte
+ * ranges of any length (0 and 1 included; one range below 2^32 bytes), so that neither the file nor its records are ever whole in
+ * memory.  file_len may be 2^32 and more.
+ *     rv_program_reader_begin(ctx, file_len, &r)
+ *     rv_program_reader_feed(r, data, len, on_device, d_ops, cap_ops, &piece)      the next len bytes of the file, again and again
+ *     rv_program_reader_finish(r, &info)
+ *     rv_program_reader_destroy(r)
+ * DEFINITION, for every byte string and every way of cutting it: the records delivered over all feeds, in order, are the records
+ * rv_program_from_bincode returns for the whole file, byte for byte, and the first nonzero code a feed (or finish) returns is its
+ * code.  A feed delivers to d_ops[0, piece->n_ops) the records not yet delivered whose last byte lies in the bytes fed so far and
+ * whose ordinal is below the header's count; no byte outside data[0, len) is read.  file_len < 8 (at the first feed) or a count above
+ * (file_len - 8) / 16 (as soon as the 8 header bytes are in; nothing is sized by the count) is RV_E_BAD_OP; a record's own code is
+ * bc_decode's (RV_E_BAD_OP before RV_E_UNSUPPORTED); a position no record can be read at is RV_E_BAD_OP once 32 bytes lie behind it
+ * or the file ends; so is the end of the file below the count.  After such a code the reader accepts only destroy (RV_E_ARG), and
+ * what earlier feeds delivered is "anything".  Bytes behind record count - 1 are never judged and need not be fed: finish is RV_OK
+ * with the whole file's info (bytes: the 64-bit file offset behind record count - 1) once `count` records are out (a count of 0:
+ * once the header is in), RV_E_ARG before.
+ * Arguments (RV_E_ARG, the reader's state unchanged): r, piece or (with len) data NULL; len >= 2^32 (before data is looked at);
+ * feeding past file_len; a non-NULL d_ops with cap_ops < len / 16 + 1 (the records inside the feed plus one that straddles in:
+ * always enough), before anything is launched.  d_ops == NULL is a scan feed: nothing is written, the piece and the info are
+ * complete; scan feeds and writing feeds mix.  data / d_ops: rv_program_from_bincode_device's conventions (host data is uploaded by
+ * the library; device data needs no alignment).
+ * Work memory comes from the context arena by len, never by file_len or the count, and goes back before the feed returns.  A feed
+ * runs on the context's stream and ends with one synchronisation (device data: once more for the feeds that bring the 8 header
+ * bytes). */
+typedef struct rv_program_reader rv_program_reader;
+typedef struct rv_program_piece {
+    uint64_t first_op, n_ops;          /* the records this feed delivered: ordinals first_op .. first_op + n_ops - 1 */
+    uint64_t n_input_gf2, n_input_z64; /* Input ops among them = what a stream feed of these records takes from the witness */
+} rv_program_piece;
+int rv_program_reader_begin(rv_ctx *ctx, uint64_t file_len, rv_program_reader **out);
+int rv_program_reader_feed(rv_program_reader *r, const uint8_t *data, size_t len, int data_on_device, rv_op *d_ops, size_t cap_ops,
+                           rv_program_piece *piece);
+int rv_program_reader_finish(rv_program_reader *r, rv_program_info *info /* may be NULL */);
+void rv_program_reader_destroy(rv_program_reader *r);
+/* Tests only: places a fresh reader as if file_off bytes holding next_op whole records had been read, with an empty carry (offsets
+ * and ordinals above 2^32 without 4 GB of input).  The count stays open: every whole record is delivered, and finish closes it at
+ * the records delivered, where the bytes fed end with a record. */
+int rv_hook_program_reader_resume(rv_program_reader *r, uint64_t file_off, uint64_t next_op);
+
 /* ---- parity-test hooks: each mirrors one reference function so tests can compare the
  * HIP path with the oracle piecewise ---- */
 /* PRG::new + gen (crypto/prg.rs:16-37) on the GPU: n_keys keys, blocks [first, first+n_blocks) each */

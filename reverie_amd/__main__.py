@@ -11,7 +11,9 @@ same `Ok(())` / `Err("Unverifiable Proof")` result lines.  Differences, stated p
   little-endian array of 24-byte `rv_op` records (`--program-format rvops`).  `--expected-outputs-path` (text of 0/1) appends the output
   assertions to a Bristol circuit (see rv_bristol_parse).  `--parser device` parses the Bristol text on the GPU instead
   (rv_bristol_parse_device: the same records, made in device memory), and reads an mcircuit-bincode file there too
-  (rv_program_from_bincode_device).
+  (rv_program_from_bincode_device).  `--stream` proves and verifies without compiling the program whole (StreamingProver /
+  StreamingVerifier), and with `--parser device` reads an mcircuit-bincode file in windows of `--window-mb` on the GPU
+  (rv_program_reader_*), so that the file's length is bounded by neither host nor device memory.
 * proofs are the same bincode bytes.
 * verification is strict by default (`--reference-compat` restores the reference verifier's two unchecked
   conditions), and a rejected proof exits with status 1 (the reference prints the same
@@ -144,25 +146,33 @@ def evaluate_gpu(prog, wc, witness, compiler="host"):
         raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (r.first_failed_op, r.n_failed))
 
 
-def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, device_compile=False, device_z64=False, device_b2a=False,
-                    compact=False, parser="host"):
-    """`oneshot --evaluator stream`: the program evaluated in pieces with bounded device memory (rv_eval_stream_*), on the GPU like
-    --evaluator gpu and with the same outcome.  An rvops file is read through a memory map, piece by piece; its wire counts come from
-    one pass over the mapping.  compact (--compact-wires): the whole list is renumbered by liveness first (in host memory: 24 bytes
-    per op, against a wire-store row per gate of an SSA list) and the stream begins with the new counts."""
-    from .stream import StreamingEvaluator
-
+def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_path=None, compact=False, windowed=True):
+    """What a stream needs of a program file: (wire counts, pieces) -- pieces() returns a fresh iterator of (ops, Input counts or
+    None) for every pass (`reverie_amd.stream.*_streaming_pieces`).
+      rvops                              read through a memory map, STREAM_FEED_OPS records per piece; the wire counts come from one
+                                         pass over the mapping
+      mcircuit-bincode, parser "device"  (windowed) read in windows of window_mb MiB on the GPU (program_file.iter_device); the wire
+                                         counts come from a scan pass (program_file.scan_device).  Device memory: one window
+      mcircuit-bincode with the host parser, Bristol, and windowed=False: parsed whole, one piece
+    compact (--compact-wires): the whole list is renumbered by liveness first, then fed, under the new counts."""
     if fmt == "auto":
         fmt = "rvops" if program_path.endswith(".rvops") else "bristol"
-    wit = np.ascontiguousarray(np.asarray(witness, dtype=np.uint8))
+    if fmt == "mcircuit-bincode" and parser == "device" and windowed and not compact:
+        from . import program_file
+
+        window = (DEFAULT_WINDOW_MB if window_mb is None else int(window_mb)) << 20
+        wc = program_file.scan_device(program_path, window)["wire_counts"]
+        return wc, lambda: program_file.iter_device(program_path, window)
     if parser == "device" and fmt in ("bristol", "mcircuit-bincode"):  # the op tensor is the one piece (compacted where it lies)
         prog, wc = load_program_device(program_path, expected_path, fmt)
         if compact:
             prog, wc = compact_program(prog, wc)
-        compact, pieces = False, [prog]
-    elif fmt != "rvops":
+        return wc, lambda: iter([(prog, None)])
+    if fmt != "rvops":
         prog, wc = load_program(program_path, fmt, expected_path)
-        pieces, n = [prog], len(prog)
+        n = len(prog)
+        if not compact:
+            return wc, lambda: iter([(prog, None)])
     else:
         import os
 
@@ -171,25 +181,36 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
             raise SystemExit("program file is not a whole number of 24-byte rv_op records")
         n = size // OP_DTYPE.itemsize
         prog = np.memmap(program_path, dtype=OP_DTYPE, mode="r", shape=(n,)) if n else np.zeros(0, OP_DTYPE)
-        step = STREAM_FEED_OPS
         z64 = gf2 = 0
-        for at in range(0, n, step):
-            z, g = largest_wires(np.asarray(prog[at:at + step]))
+        for at in range(0, n, STREAM_FEED_OPS):
+            z, g = largest_wires(np.asarray(prog[at:at + STREAM_FEED_OPS]))
             z64, gf2 = max(z64, z), max(gf2, g)
         wc = (z64, gf2)
-        if not compact:
-            pieces = (np.asarray(prog[at:at + step]) for at in range(0, n, step))
     if compact:
         prog, wc = compact_program(np.asarray(prog), wc)
-        pieces = (prog[at:at + STREAM_FEED_OPS] for at in range(0, max(n, 1), STREAM_FEED_OPS))
+    return wc, lambda: ((np.asarray(prog[at:at + STREAM_FEED_OPS]), None) for at in range(0, max(n, 1), STREAM_FEED_OPS))
+
+
+def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, device_compile=False, device_z64=False, device_b2a=False,
+                    compact=False, parser="host", window_mb=None):
+    """`oneshot --evaluator stream`: the program evaluated in pieces with bounded device memory (rv_eval_stream_*), on the GPU like
+    --evaluator gpu and with the same outcome.  An rvops file is read through a memory map, piece by piece; its wire counts come from
+    one pass over the mapping.  window_mb (--window-mb, with --parser device): an mcircuit-bincode file is read in windows of that
+    many MiB on the GPU; without it, it is parsed whole.  compact (--compact-wires): the whole list is renumbered by liveness first
+    (in host memory: 24 bytes per op, against a wire-store row per gate of an SSA list) and the stream begins with the new counts."""
+    from .stream import StreamingEvaluator, _piece_inputs
+
+    wit = np.ascontiguousarray(np.asarray(witness, dtype=np.uint8))
+    wc, pieces = stream_pieces(program_path, fmt, parser, window_mb, expected_path, compact, windowed=window_mb is not None)
     se = StreamingEvaluator(wc, 1, max_chunk_ops, device_compile=device_compile, **({"device_z64": True} if device_z64 else {}),
                             **({"device_b2a": True} if device_b2a else {}))
     try:
         used = 0
-        for piece in pieces:
+        for piece, counts in pieces():
+            if counts is not None and not len(piece):  # (a window that completed no record)
+                continue
             se.feed(piece, wit[used:])  # (the CLI's witness is GF(2) bits: a piece consumes one per GF(2) Input op)
-            if isinstance(piece, np.ndarray):
-                used += int(np.count_nonzero((piece["domain"] == 0) & (piece["opcode"] == 0)))
+            used += _piece_inputs(piece, counts)[0]
         r = se.finish()
     finally:
         se.close()
@@ -197,8 +218,42 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
         raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (r.first_failed_op[0], r.n_failed[0]))
 
 
+def run_streamed(a, ap, device_parser: bool) -> int:
+    """--stream: prove / verify / oneshot-zk through StreamingProver / StreamingVerifier, the program fed in `stream_pieces`' pieces
+    and never compiled whole.  The banners, the result lines and the exit status are the resident path's."""
+    from .stream import prove_streaming_pieces, verify_streaming_pieces
+
+    if a.strict and a.reference_compat:
+        ap.error("--strict and --reference-compat exclude each other")
+    wc, pieces = stream_pieces(a.program_path, a.program_format, "device" if device_parser else "host", a.window_mb, a.expected_outputs_path,
+                               a.compact_wires)
+    kw = dict(max_chunk_ops=a.max_chunk_ops, device_compile=a.compiler != "host", device_z64=a.compiler in ("device-z64", "device-b2a"),
+              device_b2a=a.compiler == "device-b2a")
+    if a.operation in ("prove", "oneshot-zk"):
+        wit = parse_witness(open(a.witness_path, "rb").read())
+        print("Evaluating program in ~zero knowledge~")
+        proof, _ = prove_streaming_pieces(pieces, wit, (), wc, **kw)
+        if a.operation == "prove":
+            with open(a.proof_path, "wb") as f:
+                f.write(bytes(proof))
+            print("Ok(())")
+            return 0
+    else:
+        proof = open(a.proof_path, "rb").read()
+        print("Verifying Proof")
+    ok, _ = verify_streaming_pieces(pieces, wc, proof, strict=not a.reference_compat, **kw)
+    if ok:
+        print("Ok(())")
+        return 0
+    print('Err("Unverifiable Proof")')  # (and status 1: see main)
+    return 1
+
+
 # --evaluator stream: an rvops file is fed in pieces of this many ops (the evaluator cuts them into chunks of --max-chunk-ops)
 STREAM_FEED_OPS = 1 << 22
+
+# --window-mb: the file window of --program-format mcircuit-bincode --parser device
+DEFAULT_WINDOW_MB = 64
 
 # --evaluator auto: programs from this many ops on (and every program with Z64 or B2A ops) are evaluated on the GPU
 GPU_EVAL_MIN_OPS = 100_000
@@ -224,7 +279,17 @@ def build_parser():
                          "B2A ops or at least %d ops; stream = on the GPU in pieces, with device memory bounded by the wire counts "
                          "and one chunk (an rvops file is read piece by piece)" % GPU_EVAL_MIN_OPS)
     ap.add_argument("--max-chunk-ops", type=int, default=0,
-                    help="oneshot --evaluator stream: ops per device chunk (0 = the library's default, 2^18)")
+                    help="oneshot --evaluator stream and --stream: ops per device chunk (0 = the library's default, 2^18)")
+    ap.add_argument("--stream", action="store_true",
+                    help="prove / verify / oneshot-zk: run the program through the streaming prover / verifier in pieces instead of compiling it "
+                         "whole -- device memory is the wire store plus one chunk.  An rvops file is read piece by piece through a memory map; "
+                         "an mcircuit-bincode file with --parser device is read in windows of --window-mb on the GPU (a scan pass for the wire "
+                         "counts, then one pass per proof pass), so neither the file nor its records are ever whole in memory; an "
+                         "mcircuit-bincode file with --parser host and a Bristol file are parsed whole and fed as one piece.  The proof "
+                         "verifies with and without --stream alike (oneshot streams with --evaluator stream)")
+    ap.add_argument("--window-mb", type=int, default=None,
+                    help="--program-format mcircuit-bincode --parser device with --stream, or with oneshot --evaluator stream (which reads the "
+                         "file in windows only when this is given): MiB of the file per window (default %d)" % DEFAULT_WINDOW_MB)
     ap.add_argument("--compiler", default="host", choices=["host", "device", "device-z64", "device-b2a"],
                     help="prove / verify / oneshot-zk and oneshot --evaluator gpu / stream: compile the program (the stream's pieces) on the host "
                          "(default) or on the GPU (device = RV_COMPILE_DEVICE: GF(2) programs; device-z64 = with RV_COMPILE_DEVICE_Z64: Z64 and "
@@ -261,6 +326,10 @@ def main(argv=None) -> int:
 
         print("reverie_version: speed-reverie (reverie_amd, C-ABI v%d, drop-in for reverie-zk 0.3.2)" % _lib.lib().rv_abi_version())
         return 0
+    if a.window_mb is not None and not 1 <= a.window_mb < 4096:
+        ap.error("--window-mb must be at least 1 (and below 4096: a window stays below 2^32 bytes)")
+    if a.stream and a.operation == "oneshot":
+        ap.error("--stream is for prove / verify / oneshot-zk; oneshot streams with --evaluator stream")
     if a.compact_wires and a.operation == "oneshot" and a.evaluator != "stream":
         ap.error("--compact-wires with --operation oneshot needs --evaluator stream (the other evaluators keep no wire store)")
     fmt = a.program_format
@@ -277,9 +346,11 @@ def main(argv=None) -> int:
         evaluate_stream(a.program_path, a.program_format, a.expected_outputs_path, parse_witness(open(a.witness_path, "rb").read()),
                         a.max_chunk_ops, device_compile=a.compiler != "host", **({"device_z64": True} if a.compiler in ("device-z64", "device-b2a") else {}),
                         **({"device_b2a": True} if a.compiler == "device-b2a" else {}), **({"compact": True} if a.compact_wires else {}),
-                        **({"parser": "device"} if device_parser else {}))
+                        **({"parser": "device"} if device_parser else {}), **({"window_mb": a.window_mb} if a.window_mb is not None else {}))
         print("()")
         return 0
+    if a.stream:
+        return run_streamed(a, ap, device_parser)
     if device_parser:
         prog, wc = load_program_device(a.program_path, a.expected_outputs_path, fmt)
     else:

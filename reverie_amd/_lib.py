@@ -74,6 +74,10 @@ class ProgramInfo(C.Structure):  # rv_program_info
     _fields_ = [(n, C.c_uint64) for n in ("n_ops", "bytes", "z64_wires", "gf2_wires", "n_gf2", "n_z64", "n_b2a", "n_sizehint")]
 
 
+class ProgramPiece(C.Structure):  # rv_program_piece
+    _fields_ = [(n, C.c_uint64) for n in ("first_op", "n_ops", "n_input_gf2", "n_input_z64")]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8), ("calls", C.c_uint64)]
 
@@ -120,6 +124,7 @@ SYMBOLS = [
     "rv_ops_compact_wires", "rv_ops_compact_wires_device",
     "rv_bristol_header", "rv_bristol_parse_device", "rv_hook_bristol_tiles",
     "rv_program_from_bincode_device", "rv_program_to_bincode_device", "rv_hook_bincode_tiles",
+    "rv_program_reader_begin", "rv_program_reader_feed", "rv_program_reader_finish", "rv_program_reader_destroy", "rv_hook_program_reader_resume",
     "rv_hook_prove_schedule",
     "rv_hook_b3_plan", "rv_hook_b3_chunks", "rv_hook_b3_pair_small", "rv_hook_b3_pair_big_chunks", "rv_hook_b3_tree", "rv_hook_b3_pair_big_tree",
     "rv_hook_b3_incremental", "rv_hook_b3_join",
@@ -214,6 +219,11 @@ ARGTYPES = {
     "rv_program_from_bincode_device": [_P, _P, _Z, C.c_int, _P, _Z, C.POINTER(C.c_size_t), C.POINTER(ProgramInfo)],
     "rv_program_to_bincode_device": [_P, _P, _Z, _P, _Z, C.POINTER(C.c_size_t)],
     "rv_hook_bincode_tiles": [C.POINTER(C.c_uint32)],
+    "rv_program_reader_begin": [_P, C.c_uint64, C.POINTER(_P)],
+    "rv_program_reader_feed": [_P, _P, _Z, C.c_int, _P, _Z, C.POINTER(ProgramPiece)],
+    "rv_program_reader_finish": [_P, C.POINTER(ProgramInfo)],
+    "rv_program_reader_destroy": [_P],
+    "rv_hook_program_reader_resume": [_P, C.c_uint64, C.c_uint64],
     # the transcript-hash kernels (parity hooks)
     "rv_hook_b3_plan": [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)],
     "rv_hook_b3_chunks": [_P, C.c_int, _P, C.c_uint64, C.c_uint32, C.c_uint64, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64,
@@ -277,7 +287,7 @@ def lib():
         for name in SYMBOLS:
             fn = getattr(L, name)
             if name in ("rv_ctx_destroy", "rv_circuit_destroy", "rv_shard_destroy", "rv_free", "rv_stream_abort", "rv_comm_destroy",
-                        "rv_eval_stream_abort"):
+                        "rv_eval_stream_abort", "rv_program_reader_destroy"):
                 fn.restype = None
             elif name in ("rv_hook_early_proofs", "rv_hook_open_direct_proofs", "rv_hook_verify_vc_count", "rv_hook_ops_cache_hits", "rv_hook_overlap_commits",
                           "rv_hook_verify_proof_bytes", "rv_hook_stream_device_chunks"):

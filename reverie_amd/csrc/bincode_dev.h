@@ -118,15 +118,20 @@ BC_HD inline uint32_t bc_peek(const R& r, uint32_t p, uint32_t avail, uint32_t& 
 constexpr uint32_t BC_STOP = 63;
 static_assert(BC_TILE_RECORDS < (1u << 9), "a tile's record count takes nine bits of a map entry");
 // starts: null, or room for BC_TILE_RECORDS offsets -- where the records begin
+// end: null, or where the walk stood when it returned -- the offset it stopped at, or (>= the tile's bytes) the one it left at
 template <class R>
-BC_HD inline uint32_t bc_walk_tile(const R& r, uint32_t avail, uint32_t entry, uint16_t* starts) {
+BC_HD inline uint32_t bc_walk_tile(const R& r, uint32_t avail, uint32_t entry, uint16_t* starts, uint32_t* end = nullptr) {
     uint32_t p = entry, n = 0, dom, opc;
     while (p < BINCODE_TILE_BYTES) {
         const uint32_t len = bc_peek(r, p, avail, dom, opc);
-        if (!len) return BC_STOP | n << 6;
+        if (!len) {
+            if (end) *end = p;
+            return BC_STOP | n << 6;
+        }
         if (starts) starts[n] = (uint16_t)p;
         n++, p += len;
     }
+    if (end) *end = p;
     return (p - BINCODE_TILE_BYTES) | n << 6;
 }
 
@@ -219,6 +224,156 @@ BC_HD inline void bc_encode(const uint64_t w[3], Put put) {
     if (f & BC_IMM8) field(w[2], 8);
 }
 
+// ---- windows ----
+// One file of file_len bytes handed over in consecutive windows of any length (rv_program_reader_*: the rule is in
+// include/reverie_amd.h, the stages in DESIGN §19.7).  Every record takes 16 .. 32 bytes, so what one window leaves the next is a
+// file offset, the next ordinal and a carry of fewer than 32 bytes: the bytes behind the last whole record of the bytes fed so far.
+// The 8 header bytes go through the same carry.  A window's kernels answer with a BcWindowResult; everything that decides -- what is
+// carried, which stop is final, the offsets and the counts -- is the plain C++ below, which the CPU model of
+// tests/bincode_window_model.cpp compiles as it stands.
+constexpr uint64_t BC_NO_ERR = ~0ull;
+enum { BC_I_GF2 = 0, BC_I_Z64, BC_I_B2A, BC_I_SIZEHINT, BC_I_Z64_WIRES, BC_I_GF2_WIRES, BC_I_IN_GF2, BC_I_IN_Z64, BC_I_WORDS };
+
+// bytes in plain memory (the carry and the head of a window, put together)
+struct BcBytes {
+    const uint8_t* p;
+    BC_HD uint32_t u8(uint32_t o) const { return p[o]; }
+    BC_HD uint32_t u32(uint32_t o) const { return (uint32_t)p[o] | (uint32_t)p[o + 1] << 8 | (uint32_t)p[o + 2] << 16 | (uint32_t)p[o + 3] << 24; }
+    BC_HD uint64_t u64(uint32_t o) const { return (uint64_t)u32(o) | (uint64_t)u32(o + 4) << 32; }
+};
+
+// The record that straddles into a window: r reads the carry's c bytes (1 .. 31) followed by the window's first avail - c bytes
+// (up to 31 of them).  straddle = 1: the record is whole in those bytes; the window's walk enters at `entry` (< 32), w and code are
+// bc_decode's.  straddle = 2: no record can be read there (bc_peek's 0) -- final when avail >= 32 or the file ends with the window.
+struct BcEnter {
+    uint32_t straddle, entry, dom;
+    int code;
+    uint64_t w[3];
+};
+template <class R>
+BC_HD inline BcEnter bc_enter(const R& r, uint32_t c, uint32_t avail) {
+    BcEnter e = {};
+    uint32_t opc = 0;
+    const uint32_t len = bc_peek(r, 0, avail, e.dom, opc);
+    if (len <= c) {  // (0; a whole record is never left in the carry)
+        e.straddle = 2;
+        return e;
+    }
+    e.straddle = 1, e.entry = len - c;
+    e.code = bc_decode(r, 0, e.dom, opc, e.w);
+    return e;
+}
+// what a record adds to a window's info words
+BC_HD inline bool bc_is_input(const uint64_t w[3], uint32_t dom) { return ((uint32_t)w[0] & 0xFFFFu) == dom; }  // (opcode RV_OP_INPUT = 0)
+
+struct BcWindowState {
+    uint64_t file_len, file_off;  // file_off: bytes fed so far
+    uint64_t next_op, count;      // count: the header's, once have_count
+    uint32_t have_count, open_count, carry_len, done;
+    int code;                     // the first nonzero code: the reader is over
+    uint8_t carry[BC_MAX_RECORD];
+    rv_program_info info;
+};
+struct BcWindowLaunch {
+    uint32_t carry_len, entry;  // carry_len != 0: the straddling record first; else the walk enters the window at `entry`
+    uint64_t remaining;         // records the header still owes
+};
+struct BcWindowResult {
+    uint32_t straddle;  // BcEnter's (0: there was no carry)
+    uint64_t found;     // whole records in the carry and the window, the straddling one included
+    uint64_t stop;      // the window offset the walk stopped at; BC_NO_ERR: it left the window at its last byte
+    uint64_t err;       // the smallest ordinal (counted from the feed's first) << 8 | code among the records' own codes
+    uint64_t bytes_end; // the window offset behind the record that is the header's last, where it is among them
+    uint8_t tail[BC_MAX_RECORD];  // the window's bytes from `stop` on, where fewer than 32 (straddle == 2: the whole window)
+    uint64_t info[BC_I_WORDS];
+};
+
+inline void bc_window_begin(BcWindowState& s, uint64_t file_len) {
+    s = BcWindowState{};
+    s.file_len = file_len;
+}
+// as if file_off bytes holding next_op whole records had been read; the count stays open: every whole record is delivered, and
+// bc_window_finish closes it at the records delivered, where the bytes fed end with a record
+inline void bc_window_resume(BcWindowState& s, uint64_t file_off, uint64_t next_op) {
+    const uint64_t file_len = s.file_len;
+    bc_window_begin(s, file_len);
+    s.file_off = file_off, s.next_op = next_op, s.have_count = s.open_count = 1, s.count = ~0ull;
+}
+// bytes of the window's start the header still needs (0: the header is in)
+inline uint32_t bc_window_head_need(const BcWindowState& s, uint64_t len) {
+    if (s.have_count) return 0;
+    const uint64_t need = BC_HEADER_BYTES - s.carry_len;
+    return (uint32_t)(len < need ? len : need);
+}
+// those bytes.  -> 0, or the file's code (then the reader is over).  Without a count afterwards the feed is over (the whole window
+// is in the carry); with one, the window is walked from offset n.
+inline int bc_window_head(BcWindowState& s, const uint8_t* b, uint32_t n, uint64_t len) {
+    if (s.file_len < BC_HEADER_BYTES) return s.code = RV_E_BAD_OP;
+    for (uint32_t k = 0; k < n; k++) s.carry[s.carry_len++] = b[k];
+    if (s.carry_len < BC_HEADER_BYTES) {
+        s.file_off += len;  // (len == n)
+        if (s.file_off == s.file_len) return s.code = RV_E_BAD_OP;
+        return 0;
+    }
+    s.count = 0;
+    for (uint32_t k = 0; k < BC_HEADER_BYTES; k++) s.count |= (uint64_t)s.carry[k] << (8 * k);
+    if (s.count > (s.file_len - BC_HEADER_BYTES) / BC_MIN_RECORD) return s.code = RV_E_BAD_OP;
+    s.have_count = 1, s.carry_len = 0;
+    s.info.bytes = BC_HEADER_BYTES;
+    if (!s.count) s.done = 1;
+    return 0;
+}
+inline BcWindowLaunch bc_window_launch(const BcWindowState& s, uint32_t head_taken) {
+    return BcWindowLaunch{s.carry_len, s.carry_len ? 0u : head_taken, s.count - s.next_op};
+}
+// a window of len bytes (none launched for: the records are all out, or len == 0)
+inline void bc_window_skip(BcWindowState& s, uint64_t len, rv_program_piece* piece) {
+    *piece = rv_program_piece{s.next_op, 0, 0, 0};
+    s.file_off += len;
+}
+// what the window's kernels found -> the feed's code, the piece, the state behind the window
+inline int bc_window_done(BcWindowState& s, uint64_t len, const BcWindowResult& res, rv_program_piece* piece) {
+    const uint64_t remaining = s.count - s.next_op;
+    const uint64_t deliver = res.found < remaining ? res.found : remaining;
+    uint64_t err = res.err;
+    uint32_t carry_len = 0;
+    if (res.found < remaining) {
+        // the walk stopped below the count: with 32 or more bytes before it, or at the file's end, no record can be read there
+        const uint64_t stop = res.straddle == 2 ? 0 : res.stop == BC_NO_ERR ? len : res.stop;
+        const uint64_t left = len - stop + (res.straddle == 2 ? s.carry_len : 0);
+        // (an open count owes nothing: the file may end with a record)
+        if (left >= BC_MAX_RECORD || (s.file_off + len == s.file_len && !(s.open_count && !left))) {
+            const uint64_t e = res.found << 8 | (uint64_t)RV_E_BAD_OP;
+            if (e < err) err = e;
+        } else {
+            carry_len = (uint32_t)left;
+        }
+    }
+    if (err != BC_NO_ERR) return s.code = (int)(err & 0xFFu);
+    const uint32_t keep = res.straddle == 2 ? s.carry_len : 0;  // (the carry grows by a window that completes no record)
+    for (uint32_t k = keep; k < carry_len; k++) s.carry[k] = res.tail[k - keep];
+    s.carry_len = carry_len;
+    *piece = rv_program_piece{s.next_op, deliver, res.info[BC_I_IN_GF2], res.info[BC_I_IN_Z64]};
+    rv_program_info& in = s.info;
+    in.n_gf2 += res.info[BC_I_GF2], in.n_z64 += res.info[BC_I_Z64], in.n_b2a += res.info[BC_I_B2A], in.n_sizehint += res.info[BC_I_SIZEHINT];
+    if (res.info[BC_I_Z64_WIRES] > in.z64_wires) in.z64_wires = res.info[BC_I_Z64_WIRES];
+    if (res.info[BC_I_GF2_WIRES] > in.gf2_wires) in.gf2_wires = res.info[BC_I_GF2_WIRES];
+    s.next_op += deliver;
+    if (deliver && deliver == remaining) s.done = 1, in.bytes = s.file_off + res.bytes_end;
+    else if (deliver) in.bytes = s.file_off + (res.straddle == 2 ? 0 : res.stop == BC_NO_ERR ? len : res.stop);
+    s.file_off += len;
+    return 0;
+}
+// RV_OK with the whole file's info once `count` records are out, RV_E_ARG before
+inline int bc_window_finish(BcWindowState& s, rv_program_info* info) {
+    if (s.code || !s.have_count) return RV_E_ARG;
+    if (s.open_count && !s.carry_len) s.count = s.next_op, s.open_count = 0, s.done = 1;
+    if (!s.done) return RV_E_ARG;
+    s.info.n_ops = s.count;
+    if (info) *info = s.info;
+    return RV_OK;
+}
+
 }  // namespace rv
 
 #if defined(__HIPCC__)
@@ -235,6 +390,10 @@ struct BincodeRead {
 // records go, room for `count` of them (null: nowhere).  Work memory from A, given back before the call returns; the stream is
 // synchronised once, at the end.  RV_OK (res filled), RV_E_NOMEM or RV_E_DEVICE.
 int bincode_read_device(hipStream_t st, const DevAlloc& A, const uint8_t* d_data, size_t len, uint64_t count, rv_op* d_ops, BincodeRead* res);
+// One window of a file read in windows: d_data[0, len) (1 <= len < 2^32), the carry (launch.carry_len bytes) before it.  d_ops: room
+// for len / 16 + 1 records (null: nowhere).  Work memory as above, by len; one synchronisation, at the end.
+int bincode_window_device(hipStream_t st, const DevAlloc& A, const uint8_t* d_data, size_t len, const BcWindowLaunch& launch, const uint8_t* carry,
+                          rv_op* d_ops, BcWindowResult* res);
 
 struct BincodeWrite {
     int code = 0;        // RV_OK or RV_E_BAD_OP

@@ -25,10 +25,17 @@
 // anything (the header allows it); whether they fit is known to the host before anything is launched (the count is the header's).
 // Work memory: 64 bytes per tile for the maps and 8 for the entries (1.8 % of len), 256 bytes per block, the state words.
 //
+// A file read in windows (bincode_window_device) runs the same steps on one window, behind a step 0 (k_bc_enter) that
+// decodes the record straddling in from the carry of the window before and hands the walk its entry; the whole file is the case "no
+// carry, enter at offset 8".  The tile in which the chain stops leaves the stop's offset and the bytes behind it (the next carry);
+// what is carried and which stop is final is decided on the host (bincode_dev.h: bc_window_*).
+//
 // A file written by kernels: 1. every record's length (0: a bad record) and their sum; 2. the exclusive scan of the lengths;
 // 3. a workgroup lays its 256 records out in LDS, at the position modulo 16 their bytes have in d_out, and stores the image: 16-byte
 // stores for the aligned chunks that are its own, bytes at the two ends (neighbours share those chunks).  Work memory: 4 bytes per record.
 #include "bincode_dev.h"
+
+#include <string.h>
 
 #include <algorithm>
 #include <vector>
@@ -43,8 +50,13 @@ constexpr int WAVE = 64;              // threads of the walk and decode workgrou
 constexpr uint32_t RAW = T + 64;      // a tile's LDS image: up to 15 bytes of alignment, the tile, 31 bytes behind it, the readers' slack
 constexpr uint32_t CHASE_BLOCKS = 64;  // block maps in LDS at a time
 constexpr uint32_t SLOTS = 64;        // copies of the info words the decode workgroups spread their atomics over
-enum { S_ERR, S_FOUND, S_BYTES, S_INFO, I_GF2 = 0, I_Z64, I_B2A, I_SIZEHINT, I_Z64_WIRES, I_GF2_WIRES, I_WORDS, S_WORDS = S_INFO + SLOTS * I_WORDS };
-constexpr uint64_t NO_ERR = ~0ull;
+// the state words: S_STOP, S_CHAIN0 (the chain the walk begins with: bc_block_entry), S_STRADDLE and S_TAIL are BcWindowResult's
+enum {
+    S_ERR, S_FOUND, S_BYTES, S_STOP, S_CHAIN0, S_STRADDLE, S_TAIL, S_INFO = S_TAIL + BC_MAX_RECORD / 8,
+    I_GF2 = BC_I_GF2, I_Z64 = BC_I_Z64, I_B2A = BC_I_B2A, I_SIZEHINT = BC_I_SIZEHINT, I_Z64_WIRES = BC_I_Z64_WIRES, I_GF2_WIRES = BC_I_GF2_WIRES,
+    I_IN_GF2 = BC_I_IN_GF2, I_IN_Z64 = BC_I_IN_Z64, I_WORDS = BC_I_WORDS, S_WORDS = S_INFO + SLOTS * I_WORDS
+};
+constexpr uint64_t NO_ERR = BC_NO_ERR;
 
 // a tile's image in LDS: byte o of the tile is raw[sh + o]
 struct LdsReader {
@@ -85,6 +97,50 @@ __device__ inline uint32_t stage_tile(const uint8_t* data, uint64_t len, uint64_
 }
 
 // ---- the read ----
+// The state words' first values and the chain the walk begins with.  c == 0: the walk enters the data at entry0.  c != 0 (a window
+// behind a carry of c bytes): the record that straddles in is put together from the carry and the data's first bytes (tile 0,
+// staged like any tile), decoded as ordinal 0 and written to out[0]; the walk enters behind it (bc_enter).
+struct BcCarry {
+    uint8_t b[BC_MAX_RECORD];
+};
+__global__ __launch_bounds__(TB) void k_bc_enter(const uint8_t* data, uint64_t len, BcCarry carry, uint32_t c, uint32_t entry0, uint64_t remaining,
+                                                 uint64_t* out, uint64_t* state) {
+    __shared__ __attribute__((aligned(16))) uint8_t raw[RAW];
+    __shared__ uint8_t buf[2 * BC_MAX_RECORD];
+    for (uint32_t k = threadIdx.x; k < S_WORDS; k += TB) state[k] = k == S_ERR || k == S_STOP ? NO_ERR : 0;
+    __syncthreads();
+    if (!c) {
+        if (threadIdx.x == 0) state[S_CHAIN0] = bc_block_entry(BcChain{entry0, 0, 0});
+        return;
+    }
+    uint32_t sh;
+    const uint32_t avail = stage_tile<TB>(data, len, 0, raw, sh), m = std::min(avail, BC_MAX_RECORD - 1);
+    if (threadIdx.x < c) buf[threadIdx.x] = carry.b[threadIdx.x];
+    else if (threadIdx.x < c + m) buf[threadIdx.x] = raw[sh + threadIdx.x - c];
+    __syncthreads();
+    if (threadIdx.x) return;
+    const BcEnter e = bc_enter(BcBytes{buf}, c, c + m);
+    state[S_STRADDLE] = e.straddle;
+    if (e.straddle == 2) {
+        state[S_CHAIN0] = bc_block_entry(BcChain{0, 1, 0});
+        state[S_STOP] = 0;
+        uint8_t* tail = reinterpret_cast<uint8_t*>(&state[S_TAIL]);
+        for (uint32_t k = 0; k < m; k++) tail[k] = buf[c + k];
+        return;
+    }
+    state[S_CHAIN0] = bc_block_entry(BcChain{e.entry, 0, 1});
+    if (e.code) state[S_ERR] = (uint64_t)e.code;
+    else {
+        uint64_t z, g;
+        bc_wire_needs(e.w, z, g);
+        uint64_t* w = &state[S_INFO];
+        w[I_GF2 + e.dom] = 1, w[I_Z64_WIRES] = z, w[I_GF2_WIRES] = g;
+        if (bc_is_input(e.w, RV_DOM_GF2)) w[I_IN_GF2] = 1;
+        if (bc_is_input(e.w, RV_DOM_Z64)) w[I_IN_Z64] = 1;
+    }
+    if (remaining == 1) state[S_BYTES] = e.entry;
+    if (out) out[0] = e.w[0], out[1] = e.w[1], out[2] = e.w[2];
+}
 __global__ __launch_bounds__(WAVE) void k_bc_walk(const uint8_t* data, uint64_t len, uint16_t* maps) {
     __shared__ __attribute__((aligned(16))) uint8_t raw[RAW];
     uint32_t sh;
@@ -109,10 +165,12 @@ __global__ __launch_bounds__(TB) void k_bc_blocks(const uint16_t* maps, uint32_t
     for (uint32_t t = 0; t < n && !c.stopped; t++) bc_chain_step(c, sm[t * E + c.entry]);
     bmaps[(size_t)blockIdx.x * E + threadIdx.x] = bc_block_entry(c);
 }
-// block_in[b] = the chain before block b (bc_block_entry); the state words of the chain's end
-__global__ __launch_bounds__(TB) void k_bc_chase(const uint64_t* bmaps, uint32_t n_blocks, uint64_t count, uint64_t* block_in, uint64_t* state) {
+// block_in[b] = the chain before block b (bc_block_entry); the state words of the chain's end.  final: the data is a whole file --
+// a chain that ends below the count is an error (of a window, the host decides: bc_window_done)
+__global__ __launch_bounds__(TB) void k_bc_chase(const uint64_t* bmaps, uint32_t n_blocks, uint64_t count, int final, uint64_t* block_in, uint64_t* state) {
     __shared__ uint64_t sm[CHASE_BLOCKS * E];
-    BcChain c{BC_HEADER_BYTES, 0, 0};
+    BcChain c{0, 0, 0};
+    bc_chain_block(c, state[S_CHAIN0]);
     for (uint32_t b0 = 0; b0 < n_blocks; b0 += CHASE_BLOCKS) {
         const uint32_t n = std::min(CHASE_BLOCKS, n_blocks - b0);
         for (uint32_t k = threadIdx.x; k < n * E; k += TB) sm[k] = bmaps[(size_t)b0 * E + k];
@@ -128,7 +186,7 @@ __global__ __launch_bounds__(TB) void k_bc_chase(const uint64_t* bmaps, uint32_t
         // stopped: record c.records cannot be read.  Not stopped: the chain left the last tile, which it can only do at the file's
         // last byte (a record that passes len stops it), and record c.records would begin at len.  RV_E_BAD_OP either way.
         state[S_FOUND] = c.records;
-        if (c.records < count) state[S_ERR] = c.records << 8 | (uint64_t)RV_E_BAD_OP;
+        if (final && c.records < count) state[S_ERR] = c.records << 8 | (uint64_t)RV_E_BAD_OP;
     }
 }
 __global__ __launch_bounds__(TB) void k_bc_resolve(const uint16_t* maps, uint32_t n_tiles, const uint64_t* block_in, uint64_t* tile_in) {
@@ -157,10 +215,21 @@ __global__ __launch_bounds__(WAVE) void k_bc_decode(const uint8_t* data, uint64_
     const uint32_t avail = stage_tile<WAVE>(data, len, blockIdx.x, raw, sh);
     const LdsReader r{raw, sh};
     if (threadIdx.x < I_WORDS) acc[threadIdx.x] = 0;
-    if (threadIdx.x == 0) n_found = bc_walk_tile(r, avail, (uint32_t)(in >> 32), starts) >> 6;
+    if (threadIdx.x == 0) {
+        uint32_t end;
+        const uint32_t m = bc_walk_tile(r, avail, (uint32_t)(in >> 32), starts, &end);
+        n_found = m >> 6;
+        if ((m & 63u) == BC_STOP) {  // the one tile the chain stops in: where, and the bytes from there on where they end the data
+            state[S_STOP] = (uint64_t)blockIdx.x * T + end;
+            if ((uint64_t)blockIdx.x * T + avail == len && avail - end < BC_MAX_RECORD) {
+                uint8_t* tail = reinterpret_cast<uint8_t*>(&state[S_TAIL]);
+                for (uint32_t k = end; k < avail; k++) tail[k - end] = (uint8_t)r.u8(k);
+            }
+        }
+    }
     __syncthreads();
     const uint32_t n = (uint32_t)std::min<uint64_t>(n_found, count - first);
-    uint32_t cnt[4] = {0, 0, 0, 0};
+    uint32_t cnt[4] = {0, 0, 0, 0}, inputs[2] = {0, 0};
     uint64_t z64 = 0, gf2 = 0;
     for (uint32_t r0 = 0; r0 < n; r0 += WAVE) {
         const uint32_t i = r0 + threadIdx.x;
@@ -174,6 +243,7 @@ __global__ __launch_bounds__(WAVE) void k_bc_decode(const uint8_t* data, uint64_
                 uint64_t z, g;
                 bc_wire_needs(w, z, g);
                 cnt[dom]++, z64 = std::max(z64, z), gf2 = std::max(gf2, g);
+                if (dom < 2 && opc == RV_OP_INPUT) inputs[dom]++;
             }
             if (first + i == count - 1) state[S_BYTES] = (uint64_t)blockIdx.x * T + p + rec_len;
             words[threadIdx.x * 3] = w[0], words[threadIdx.x * 3 + 1] = w[1], words[threadIdx.x * 3 + 2] = w[2];
@@ -188,13 +258,15 @@ __global__ __launch_bounds__(WAVE) void k_bc_decode(const uint8_t* data, uint64_
     }
     for (int d = 0; d < 4; d++)
         if (cnt[d]) atomicAdd(&acc[I_GF2 + d], (unsigned long long)cnt[d]);
+    for (int d = 0; d < 2; d++)
+        if (inputs[d]) atomicAdd(&acc[I_IN_GF2 + d], (unsigned long long)inputs[d]);
     if (z64) atomicMax(&acc[I_Z64_WIRES], (unsigned long long)z64);
     if (gf2) atomicMax(&acc[I_GF2_WIRES], (unsigned long long)gf2);
     __syncthreads();
     if (threadIdx.x < I_WORDS && acc[threadIdx.x]) {
         unsigned long long* slot = (unsigned long long*)&state[S_INFO + (blockIdx.x % SLOTS) * I_WORDS + threadIdx.x];
-        if (threadIdx.x < I_Z64_WIRES) atomicAdd(slot, acc[threadIdx.x]);
-        else atomicMax(slot, acc[threadIdx.x]);
+        if (threadIdx.x == I_Z64_WIRES || threadIdx.x == I_GF2_WIRES) atomicMax(slot, acc[threadIdx.x]);
+        else atomicAdd(slot, acc[threadIdx.x]);
     }
 }
 
@@ -252,7 +324,9 @@ __global__ __launch_bounds__(TB) void k_bw_emit(const uint64_t* ops, uint64_t n,
 
 }  // namespace
 
-int bincode_read_device(hipStream_t st, const DevAlloc& A, const uint8_t* d_data, size_t len, uint64_t count, rv_op* d_ops, BincodeRead* res) {
+// the five steps over d_data[0, len), entered as k_bc_enter says; `count` records at the most are judged and written; h: the state words
+static int read_steps(hipStream_t st, const DevAlloc& A, const uint8_t* d_data, size_t len, const BcCarry& carry, uint32_t c, uint32_t entry0,
+                      uint64_t count, int final, rv_op* d_ops, std::vector<uint64_t>& h) {
     Scratch S(A, st);
     const uint32_t n_tiles = blocks(len, T), n_blocks = blocks(n_tiles, B);
     uint64_t* state = S.get<uint64_t>(S_WORDS);
@@ -260,17 +334,23 @@ int bincode_read_device(hipStream_t st, const DevAlloc& A, const uint8_t* d_data
     uint64_t *bmaps = S.get<uint64_t>((size_t)n_blocks * E), *block_in = S.get<uint64_t>(n_blocks), *tile_in = S.get<uint64_t>((size_t)n_blocks * B);
     CDNEED(state && maps && bmaps && block_in && tile_in);
 
-    CDCHK(hipMemsetAsync(state, 0, S_WORDS * 8, st));
-    CDCHK(hipMemsetAsync(state, 0xFF, 8, st));
+    uint64_t* out = reinterpret_cast<uint64_t*>(d_ops);
+    k_bc_enter<<<1, TB, 0, st>>>(d_data, len, carry, c, entry0, count, out, state);
     k_bc_walk<<<n_tiles, WAVE, 0, st>>>(d_data, len, maps);
     k_bc_blocks<<<n_blocks, TB, 0, st>>>(maps, n_tiles, bmaps);
-    k_bc_chase<<<1, TB, 0, st>>>(bmaps, n_blocks, count, block_in, state);
+    k_bc_chase<<<1, TB, 0, st>>>(bmaps, n_blocks, count, final, block_in, state);
     k_bc_resolve<<<n_blocks, TB, 0, st>>>(maps, n_tiles, block_in, tile_in);
-    k_bc_decode<<<n_tiles, WAVE, 0, st>>>(d_data, len, tile_in, count, reinterpret_cast<uint64_t*>(d_ops), state);
+    k_bc_decode<<<n_tiles, WAVE, 0, st>>>(d_data, len, tile_in, count, out, state);
     CDCHK(hipGetLastError());
-    std::vector<uint64_t> h(S_WORDS);
+    h.resize(S_WORDS);
     CDCHK(fetch(st, h, state));
     CDCHK(hipStreamSynchronize(st));
+    return RV_OK;
+}
+
+int bincode_read_device(hipStream_t st, const DevAlloc& A, const uint8_t* d_data, size_t len, uint64_t count, rv_op* d_ops, BincodeRead* res) {
+    std::vector<uint64_t> h;
+    if (int rc = read_steps(st, A, d_data, len, BcCarry{}, 0, BC_HEADER_BYTES, count, 1, d_ops, h)) return rc;
     *res = BincodeRead{};
     if (h[S_ERR] != NO_ERR) {
         res->code = (int)(h[S_ERR] & 0xFFu);
@@ -284,6 +364,24 @@ int bincode_read_device(hipStream_t st, const DevAlloc& A, const uint8_t* d_data
         in.z64_wires = std::max(in.z64_wires, w[I_Z64_WIRES]), in.gf2_wires = std::max(in.gf2_wires, w[I_GF2_WIRES]);
     }
     res->written = d_ops != nullptr;
+    return RV_OK;
+}
+
+int bincode_window_device(hipStream_t st, const DevAlloc& A, const uint8_t* d_data, size_t len, const BcWindowLaunch& launch, const uint8_t* carry,
+                          rv_op* d_ops, BcWindowResult* res) {
+    BcCarry cb = {};
+    memcpy(cb.b, carry, launch.carry_len);
+    std::vector<uint64_t> h;
+    if (int rc = read_steps(st, A, d_data, len, cb, launch.carry_len, launch.entry, launch.remaining, 0, d_ops, h)) return rc;
+    *res = BcWindowResult{};
+    res->straddle = (uint32_t)h[S_STRADDLE], res->found = h[S_FOUND], res->stop = h[S_STOP], res->err = h[S_ERR], res->bytes_end = h[S_BYTES];
+    memcpy(res->tail, &h[S_TAIL], BC_MAX_RECORD);
+    for (uint32_t s = 0; s < SLOTS; s++) {
+        const uint64_t* w = &h[S_INFO + s * I_WORDS];
+        for (uint32_t k = 0; k < I_WORDS; k++)
+            if (k == I_Z64_WIRES || k == I_GF2_WIRES) res->info[k] = std::max(res->info[k], w[k]);
+            else res->info[k] += w[k];
+    }
     return RV_OK;
 }
 

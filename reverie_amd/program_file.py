@@ -3,7 +3,8 @@
 (`rv_program_from_bincode` / `rv_program_to_bincode`, reverie_amd/csrc/program.cpp); this is the ctypes
 wrapper.  The enum's variant order is recalled, not verifiable here — see the header.
 `loads_device` / `dumps_device` are the same two on the GPU (`rv_program_from_bincode_device` / `rv_program_to_bincode_device`,
-reverie_amd/csrc/bincode_dev.hip: DESIGN §19): the op list is made in, and written from, device memory."""
+reverie_amd/csrc/bincode_dev.hip: DESIGN §19): the op list is made in, and written from, device memory.  `DeviceReader` / `iter_device` /
+`scan_device` read a file in windows (`rv_program_reader_*`): for files no memory holds whole."""
 from __future__ import annotations
 
 import ctypes as C
@@ -114,3 +115,130 @@ def dumps_device(ops, device=None):
     out = torch.empty(int(n.value), dtype=torch.uint8, device=torch.device("cuda", ctx.device))
     _lib.check(L.rv_program_to_bincode_device(ctx.handle, p_ops, C.c_size_t(n_ops), C.c_void_p(out.data_ptr()), C.c_size_t(out.numel()), C.byref(n)))
     return out[:int(n.value)]
+
+
+# ---- a file read in windows (rv_program_reader_*) ----
+def _info_dict(info) -> dict:
+    d = {k: int(getattr(info, k)) for k, _ in info._fields_}
+    d["wire_counts"] = (d["z64_wires"], d["gf2_wires"])
+    return d
+
+
+class DeviceReader:
+    """`loads_device` for a file that is handed over in windows: consecutive byte ranges of any length (rv_program_reader_*).  Neither
+    the file nor its records are ever whole in memory, and file_len may be 2^32 and more (one window stays below 2^32 bytes).
+
+        with DeviceReader(file_len) as r:
+            for window in windows: ops, piece = r.feed(window)    # the records whose last byte has now been fed
+            info = r.finish()                                     # loads_device's info, for the whole file
+
+    The records of all feeds, in order, are exactly `loads`' records for the whole file, and the first error raised is `loads`'
+    error, for every byte string and every way of cutting it; afterwards the reader takes nothing more.  Bytes behind the last
+    record the header counts are never judged and need not be fed."""
+
+    def __init__(self, file_len: int, device=None):
+        self.ctx = _context(device)
+        self.handle = C.c_void_p()
+        _lib.check(_lib.lib().rv_program_reader_begin(self.ctx.handle, C.c_uint64(int(file_len)), C.byref(self.handle)))
+
+    def feed(self, data, scan: bool = False, out=None):
+        """-> (ops, piece).  data: bytes, any buffer (an mmap or a slice of one, a uint8 numpy array) or a uint8 torch tensor in GPU
+        memory (a slice of a larger one is fine; no alignment is asked).  ops: a torch uint8 tensor [n, 24] in GPU memory; scan=True:
+        None -- nothing is written, the piece and the info are complete all the same.  piece: first_op, n_ops, n_input_gf2,
+        n_input_z64 (what a stream feed of these records takes from the witness).  out: a uint8 GPU tensor with room for
+        len(data) // 16 + 1 records to write into instead of a new one."""
+        import torch
+
+        from .bristol import _host_buffer
+        from .proof import _is_device_ops
+
+        on_device = _is_device_ops(data)
+        if on_device:
+            if data.device.type != "cuda" or data.dtype != torch.uint8 or not data.is_contiguous():
+                raise ValueError("a tensor of file bytes must be a contiguous uint8 tensor in GPU memory")
+            if data.device.index is not None and data.device.index != self.ctx.device:
+                raise ValueError(f"the data is on {data.device}, the context on device {self.ctx.device}")
+            torch.cuda.synchronize(data.device)
+            n_data, p_data = data.numel(), data.data_ptr() if data.numel() else _EMPTY.ctypes.data
+            on_device = bool(data.numel())
+        else:
+            buf = _host_buffer(data)
+            n_data, p_data = buf.size, buf.ctypes.data if buf.size else _EMPTY.ctypes.data
+        ops, cap = None, n_data // 16 + 1
+        if not scan:
+            if out is None:
+                out = torch.empty((cap, OP_DTYPE.itemsize), dtype=torch.uint8, device=torch.device("cuda", self.ctx.device))
+            elif not _is_device_ops(out) or out.device.type != "cuda" or out.dtype != torch.uint8 or not out.is_contiguous():
+                raise ValueError("out must be a contiguous uint8 tensor in GPU memory")
+            ops, cap = out.reshape(-1, OP_DTYPE.itemsize), out.numel() // OP_DTYPE.itemsize
+        piece = _lib.ProgramPiece()
+        _lib.check(_lib.lib().rv_program_reader_feed(self.handle, C.c_void_p(p_data), C.c_size_t(n_data), C.c_int(1 if on_device else 0),
+                                                     C.c_void_p(ops.data_ptr()) if ops is not None else None, C.c_size_t(cap if ops is not None else 0),
+                                                     C.byref(piece)))
+        d = {k: int(getattr(piece, k)) for k, _ in piece._fields_}
+        return (ops[:d["n_ops"]] if ops is not None else None), d
+
+    def finish(self) -> dict:
+        """`loads_device`'s info for the whole file, once the records the header counts are out (an error before that)"""
+        info = _lib.ProgramInfo()
+        _lib.check(_lib.lib().rv_program_reader_finish(self.handle, C.byref(info)))
+        return _info_dict(info)
+
+    def close(self):
+        if self.handle:
+            if self.ctx.handle:
+                _lib.lib().rv_program_reader_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _window_source(source):
+    """(something to slice by bytes, its length) of a path (memory-mapped), a buffer or a uint8 GPU tensor"""
+    import os
+
+    from .bristol import _host_buffer
+    from .proof import _is_device_ops
+
+    if _is_device_ops(source):
+        return source.reshape(-1), source.numel()
+    if isinstance(source, (str, os.PathLike)):
+        size = os.path.getsize(source)
+        return (np.memmap(source, dtype=np.uint8, mode="r") if size else _EMPTY[:0]), size  # (an empty file cannot be mapped)
+    buf = _host_buffer(source)
+    return buf, buf.size
+
+
+def iter_device(source, window_bytes: int = 64 << 20, device=None, scan: bool = False, info=None):
+    """The program file `source` -- a path (memory-mapped), a buffer or a uint8 torch tensor in GPU memory -- read in windows of
+    window_bytes: yields `DeviceReader.feed`'s (ops, piece) per window, windows that complete no record included.  Device memory
+    is one window, its work memory and its records, whatever the file's length.  info: a dict that receives `finish`'s info at the
+    end."""
+    window_bytes = int(window_bytes)
+    if not 0 < window_bytes < 1 << 32:
+        raise ValueError("window_bytes must be in [1, 2^32)")
+    data, n = _window_source(source)
+    with DeviceReader(n, device) as r:
+        for at in range(0, max(n, 1), window_bytes):
+            yield r.feed(data[at:at + window_bytes], scan=scan)
+        done = r.finish()
+        if info is not None:
+            info.update(done)
+
+
+def scan_device(source, window_bytes: int = 64 << 20, device=None) -> dict:
+    """`loads_device`'s info of a file read in windows, nothing written: the pre-pass that gives a stream its wire counts"""
+    info = {}
+    for _ in iter_device(source, window_bytes, device, scan=True, info=info):
+        pass
+    return info

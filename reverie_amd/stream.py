@@ -697,3 +697,91 @@ def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], ma
     if info is not None:
         info.update({k: int(getattr(si, k)) for k, _ in si._fields_})
     return _eval_status(st, gv, zv)
+
+
+# ---- streams fed piece by piece from a source that is read again for every pass (a program file read in windows) ----
+def _piece_inputs(ops, counts) -> Tuple[int, int]:
+    """the Input ops of a piece per domain: what the piece's source counted -- (n_input_gf2, n_input_z64), or a piece dict of
+    `program_file.DeviceReader.feed` -- or, where a piece comes with None, counted here"""
+    if counts is not None:
+        if isinstance(counts, dict):
+            return int(counts["n_input_gf2"]), int(counts["n_input_z64"])
+        return int(counts[0]), int(counts[1])
+    if _is_device_ops(ops):  # (domain and opcode are a record's first two bytes)
+        recs = ops.reshape(-1, OP_DTYPE.itemsize)
+        inputs = recs[:, 1] == 0
+        return int((inputs & (recs[:, 0] == 0)).sum()), int((inputs & (recs[:, 0] == 1)).sum())
+    a = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+    inputs = a["opcode"] == 0
+    return int(np.count_nonzero(inputs & (a["domain"] == 0))), int(np.count_nonzero(inputs & (a["domain"] == 1)))
+
+
+def _host_or_device_wit(w, dtype):
+    return w if hasattr(w, "data_ptr") else np.ascontiguousarray(np.asarray(w, dtype=dtype))
+
+
+def _feed_pieces(feed, pieces, wit_gf2, wit_z64):
+    """every piece of one pass to feed(ops, gf2 elements, z64 elements); the witnesses (the last axis) advance by the pieces' Input
+    counts"""
+    used_g = used_z = 0
+    for ops, counts in (pieces() if callable(pieces) else pieces):
+        if ops is None or len(ops) == 0:
+            continue
+        n_g, n_z = _piece_inputs(ops, counts)
+        feed(ops, wit_gf2[..., used_g:used_g + n_g], wit_z64[..., used_z:used_z + n_z])
+        used_g, used_z = used_g + n_g, used_z + n_z
+
+
+def prove_streaming_pieces(pieces, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
+                           ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
+                           device_proof: bool = False) -> "Tuple[Proof | DeviceProof, dict]":
+    """`prove_streaming` for an op list that is never whole in memory: `pieces()` returns a fresh iterator of (ops, (n_input_gf2,
+    n_input_z64)) for each of the two passes -- `program_file.iter_device` on a program file, say (its piece dicts serve as the
+    counts).  ops: a host array or a torch GPU tensor of rv_op records; a host array may come with None, its Inputs are then counted
+    here.  Both passes must yield the same pieces (rv_stream_same_cuts is set).  The proof is `prove_streaming`'s for the
+    concatenated list; wire_counts are the whole list's (`program_file.scan_device`).  -> (Proof or DeviceProof, stream info)"""
+    if not callable(pieces):
+        raise TypeError("prove_streaming_pieces reads the pieces twice: pass a callable that returns a fresh iterator")
+    g, z = _host_or_device_wit(wit_gf2, np.uint8), _host_or_device_wit(wit_z64, np.uint64)
+    sp = StreamingProver(wire_counts, seeds, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
+    try:
+        sp.same_cuts()
+        _feed_pieces(sp.feed, pieces, g, z)
+        sp.commit()
+        _feed_pieces(sp.feed, pieces, g, z)
+        return sp.finish(device=device_proof), sp.info
+    finally:
+        sp.close()
+
+
+def verify_streaming_pieces(pieces, wire_counts: Tuple[int, int], proof, strict: bool = True, max_chunk_ops: int = 0,
+                            ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False,
+                            device_b2a: bool = False) -> Tuple[bool, dict]:
+    """`verify_streaming` for pieces as `prove_streaming_pieces` takes them (a callable or, the pass being one, an iterable; the
+    counts are not looked at).  proof: bytes, a Proof, a bincode-form DeviceProof or a uint8 GPU tensor.  -> (ok, stream info)"""
+    sv = StreamingVerifier(wire_counts, proof, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
+    try:
+        for ops, _ in (pieces() if callable(pieces) else pieces):
+            if ops is not None and len(ops):
+                sv.feed(ops)
+        return sv.finish(strict), sv.info
+    finally:
+        sv.close()
+
+
+def evaluate_streaming_pieces(pieces, wits_gf2, wits_z64, wire_counts: Tuple[int, int], max_chunk_ops: int = 0, values: bool = False,
+                              ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False,
+                              device_b2a: bool = False) -> Evaluation:
+    """`evaluate_streaming` for pieces as `prove_streaming_pieces` takes them, in one pass.  wits_gf2 / wits_z64: [B][n] (1-D for one
+    witness), host arrays or torch GPU tensors.  -> the array-shaped Evaluation; `info` receives the stream's figures."""
+    g, z = _host_or_device_wit(wits_gf2, np.uint8), _host_or_device_wit(wits_z64, np.uint64)
+    batch = g.shape[0] if g.ndim == 2 else 1
+    se = StreamingEvaluator(wire_counts, batch, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
+    try:
+        _feed_pieces(se.feed, pieces, g, z)
+        r = se.finish(values)
+        if info is not None:
+            info.update(se.info)
+        return r
+    finally:
+        se.close()
