@@ -849,6 +849,63 @@ int rv_bristol_parse_device(rv_ctx *ctx, const char *text, size_t len, int text_
 /* the device parser's two tile sizes: out[0] = bytes of text per workgroup of the tile kernels, out[1] = gate lines per workgroup of
  * the line kernels (the lengths the tests go around) */
 int rv_hook_bristol_tiles(uint32_t out[2]);
+/* host only, no GPU: rv_bristol_header for the HEAD of a text -- text[0, len) is a prefix (it must reach the end of the first non-blank
+ * gate line, or be the whole text) of a text of full_len bytes, and full_len, not len, enters the n_gates > full_len / 8 + 1 check.
+ * With len == full_len this is rv_bristol_header.  RV_E_ARG: a null argument, or len > full_len. */
+int rv_bristol_header_prefix(const char *text, size_t len, uint64_t full_len, int format, rv_bristol_info *info, size_t *gates_offset);
+
+/* ---- a Bristol text read in windows ---------------------------------------------
+ * rv_bristol_parse_device for a text that is handed over in consecutive byte ranges ("feeds") of any length, 0 and 1 included:
+ *     rv_bristol_reader_begin(ctx, file_len, format, expected, n_expected, &r)
+ *     rv_bristol_reader_feed(r, text, len, on_device, d_ops, cap_ops, &piece)      the next len bytes of the text, again and again
+ *     rv_bristol_reader_finish(r, &info)
+ *     rv_bristol_reader_destroy(r)
+ * Over all feeds the records delivered, in order, are rv_bristol_parse's records for the whole text and the same arguments, byte for
+ * byte; the first nonzero code a feed returns is its code; finish fills info as it does -- for every byte string the host parser
+ * answers and every way of cutting it.  file_len may be 2^32 and more; one feed stays below 2^32 bytes.
+ *   The header: the reader keeps the first bytes on the host until they hold four whole non-blank lines or the file ends (of a device
+ * text it copies down only those: 4096 bytes, then as many again as it holds), and runs rv_bristol_parse's header code on them with
+ * the file's length.  That feed returns the header's code (RV_E_ARG for n_expected != n_outputs among them) and its piece begins with
+ * the n_inputs Input records.
+ *   The lines: a gate line is final when its LF has been fed or the bytes fed reach file_len.  A feed judges and delivers exactly the
+ * final lines not yet delivered whose index is below n_gates; an unfinished line is never judged, so a bad line's code is returned by
+ * the feed that makes it final (among several the first in line order counts).  The feed that makes line n_gates - 1 final ends its
+ * piece with the assertion pairs (n_gates == 0: the header feed) and returns RV_E_UNSUPPORTED, after its lines' own codes, for more
+ * than 2^32 - 1 wires with the assertion temporaries.  Bytes behind that line are never judged and need not be fed.  A file that ends
+ * with fewer lines: RV_E_BAD_OP from the feed that reaches file_len.
+ *   After a code of the text the reader accepts only destroy (RV_E_ARG otherwise); what earlier feeds delivered is then anything.
+ * finish: RV_OK once the header is in and n_gates lines and the pairs are out, RV_E_ARG before.
+ *   d_ops / cap_ops: rv_bristol_parse_device's conventions.  cap_ops below what the feed delivers: RV_E_ARG with piece->n_ops = the
+ * count needed, nothing written and the reader unchanged -- the same bytes are fed again with a larger buffer.  This many always
+ * suffice: the Input records still due + (held + len) / 6 + 1 + 2 * n_expected, where `held` is what was fed before and no feed
+ * has made final -- the bytes behind the last LF fed, and every byte fed while the header is not complete.  (A MAND lane, three
+ * numbers and their blanks, takes six bytes of a line; any other record a line of eleven at least.)  d_ops == NULL is a scan feed:
+ * nothing is written, the piece and the info are complete; scan feeds and writing feeds mix.
+ *   RV_E_ARG with the reader unchanged, before any launch: a NULL r or piece, NULL text with len != 0, len >= 2^32, a feed past
+ * file_len, d_ops misaligned or outside an allocation, a device text outside an allocation.  held + len >= 2^32: RV_E_UNSUPPORTED,
+ * the reader unchanged.  No byte outside text[0, len) is read.
+ *   Memory: the unfinished last line (the carry) lives in context-arena memory between feeds; a line may span any number of feeds.
+ * A feed's work memory -- the carry and the window in one buffer, 8 bytes per 8 bytes of it for the line table at the most, 8 bytes
+ * per 4096 for the tiles -- is sized by carry + len, never by file_len, n_gates or n_inputs, and goes back before the feed returns.
+ * A feed runs on the context's stream and synchronises it twice (the header feed of a device text once more per copy of header
+ * bytes), whatever len is. */
+typedef struct rv_bristol_reader rv_bristol_reader;
+typedef struct rv_bristol_piece {
+    uint64_t first_op, n_ops;     /* records this feed delivered: ordinals in rv_bristol_parse's list */
+    uint64_t n_input_gf2;         /* Input ops among them */
+    uint64_t first_line, n_lines; /* gate lines this feed made final */
+} rv_bristol_piece;               /* 40 bytes */
+int rv_bristol_reader_begin(rv_ctx *ctx, uint64_t file_len, int format, const uint8_t *expected_outputs /* host, copied; may be NULL */,
+                            size_t n_expected, rv_bristol_reader **out);
+int rv_bristol_reader_feed(rv_bristol_reader *r, const char *text, size_t len, int text_on_device, rv_op *d_ops, size_t cap_ops,
+                           rv_bristol_piece *piece);
+/* RV_E_ARG until the header is in; then n_gates, n_wires, n_inputs, n_outputs and gf2_wires (the class counts: of the lines so far) */
+int rv_bristol_reader_header(rv_bristol_reader *r, rv_bristol_info *info);
+int rv_bristol_reader_finish(rv_bristol_reader *r, rv_bristol_info *info /* may be NULL */);
+void rv_bristol_reader_destroy(rv_bristol_reader *r);
+/* tests only, as rv_hook_program_reader_resume: the reader continues at byte file_off of the file, with gate line next_line and
+ * record next_op, nothing carried and the Input records out.  The header: that of a first feed of the header lines alone. */
+int rv_hook_bristol_reader_resume(rv_bristol_reader *r, uint64_t file_off, uint64_t next_line, uint64_t next_op);
 
 /* ---- wire indices compacted by liveness -----------------------------------------
  * A stream's wire store is sized by the wire counts it begins with: one row per wire index.  An op list in SSA form (a Bristol file,

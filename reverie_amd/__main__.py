@@ -153,7 +153,9 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
                                          pass over the mapping
       mcircuit-bincode, parser "device"  (windowed) read in windows of window_mb MiB on the GPU (program_file.iter_device); the wire
                                          counts come from a scan pass (program_file.scan_device).  Device memory: one window
-      mcircuit-bincode with the host parser, Bristol, and windowed=False: parsed whole, one piece
+      bristol, parser "device", window_mb given  read in windows of window_mb MiB on the GPU (bristol.iter_device); the wire counts
+                                         come from the header (bristol.wire_counts): no scan pass.  Device memory: one window
+      mcircuit-bincode with the host parser, Bristol otherwise, and windowed=False: parsed whole, one piece
     compact (--compact-wires): the whole list is renumbered by liveness first, then fed, under the new counts."""
     if fmt == "auto":
         fmt = "rvops" if program_path.endswith(".rvops") else "bristol"
@@ -163,6 +165,12 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
         window = (DEFAULT_WINDOW_MB if window_mb is None else int(window_mb)) << 20
         wc = program_file.scan_device(program_path, window)["wire_counts"]
         return wc, lambda: program_file.iter_device(program_path, window)
+    if fmt == "bristol" and parser == "device" and windowed and window_mb is not None and not compact:
+        from . import bristol
+
+        exp = parse_witness(open(expected_path, "rb").read()) if expected_path else None
+        wc = bristol.wire_counts(program_path, exp)
+        return wc, lambda: bristol.iter_device(program_path, int(window_mb) << 20, exp)
     if parser == "device" and fmt in ("bristol", "mcircuit-bincode"):  # the op tensor is the one piece (compacted where it lies)
         prog, wc = load_program_device(program_path, expected_path, fmt)
         if compact:
@@ -196,7 +204,7 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
     """`oneshot --evaluator stream`: the program evaluated in pieces with bounded device memory (rv_eval_stream_*), on the GPU like
     --evaluator gpu and with the same outcome.  An rvops file is read through a memory map, piece by piece; its wire counts come from
     one pass over the mapping.  window_mb (--window-mb, with --parser device): an mcircuit-bincode file is read in windows of that
-    many MiB on the GPU; without it, it is parsed whole.  compact (--compact-wires): the whole list is renumbered by liveness first
+    many MiB on the GPU, and so is a Bristol file; without it, either is parsed whole.  compact (--compact-wires): the whole list is renumbered by liveness first
     (in host memory: 24 bytes per op, against a wire-store row per gate of an SSA list) and the stream begins with the new counts."""
     from .stream import StreamingEvaluator, _piece_inputs
 
@@ -284,12 +292,16 @@ def build_parser():
                     help="prove / verify / oneshot-zk: run the program through the streaming prover / verifier in pieces instead of compiling it "
                          "whole -- device memory is the wire store plus one chunk.  An rvops file is read piece by piece through a memory map; "
                          "an mcircuit-bincode file with --parser device is read in windows of --window-mb on the GPU (a scan pass for the wire "
-                         "counts, then one pass per proof pass), so neither the file nor its records are ever whole in memory; an "
-                         "mcircuit-bincode file with --parser host and a Bristol file are parsed whole and fed as one piece.  The proof "
+                         "counts, then one pass per proof pass), so neither the file nor its records are ever whole in memory; a Bristol "
+                         "file with --parser device and --window-mb given is read in windows too (its header names the wire counts: no scan "
+                         "pass); an mcircuit-bincode file with --parser host and a Bristol file otherwise are parsed whole and fed as one "
+                         "piece.  The proof "
                          "verifies with and without --stream alike (oneshot streams with --evaluator stream)")
     ap.add_argument("--window-mb", type=int, default=None,
                     help="--program-format mcircuit-bincode --parser device with --stream, or with oneshot --evaluator stream (which reads the "
-                         "file in windows only when this is given): MiB of the file per window (default %d)" % DEFAULT_WINDOW_MB)
+                         "file in windows only when this is given): MiB of the file per window (default %d).  A Bristol file with --parser "
+                         "device is read in windows only when this is given (and --compact-wires is not); without it, it is parsed whole"
+                         % DEFAULT_WINDOW_MB)
     ap.add_argument("--compiler", default="host", choices=["host", "device", "device-z64", "device-b2a"],
                     help="prove / verify / oneshot-zk and oneshot --evaluator gpu / stream: compile the program (the stream's pieces) on the host "
                          "(default) or on the GPU (device = RV_COMPILE_DEVICE: GF(2) programs; device-z64 = with RV_COMPILE_DEVICE_Z64: Z64 and "

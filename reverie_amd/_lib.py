@@ -78,6 +78,10 @@ class ProgramPiece(C.Structure):  # rv_program_piece
     _fields_ = [(n, C.c_uint64) for n in ("first_op", "n_ops", "n_input_gf2", "n_input_z64")]
 
 
+class BristolPiece(C.Structure):  # rv_bristol_piece
+    _fields_ = [(n, C.c_uint64) for n in ("first_op", "n_ops", "n_input_gf2", "first_line", "n_lines")]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8), ("calls", C.c_uint64)]
 
@@ -125,6 +129,8 @@ SYMBOLS = [
     "rv_bristol_header", "rv_bristol_parse_device", "rv_hook_bristol_tiles",
     "rv_program_from_bincode_device", "rv_program_to_bincode_device", "rv_hook_bincode_tiles",
     "rv_program_reader_begin", "rv_program_reader_feed", "rv_program_reader_finish", "rv_program_reader_destroy", "rv_hook_program_reader_resume",
+    "rv_bristol_header_prefix", "rv_bristol_reader_begin", "rv_bristol_reader_feed", "rv_bristol_reader_header", "rv_bristol_reader_finish",
+    "rv_bristol_reader_destroy", "rv_hook_bristol_reader_resume",
     "rv_hook_prove_schedule",
     "rv_hook_b3_plan", "rv_hook_b3_chunks", "rv_hook_b3_pair_small", "rv_hook_b3_pair_big_chunks", "rv_hook_b3_tree", "rv_hook_b3_pair_big_tree",
     "rv_hook_b3_incremental", "rv_hook_b3_join",
@@ -224,6 +230,14 @@ ARGTYPES = {
     "rv_program_reader_finish": [_P, C.POINTER(ProgramInfo)],
     "rv_program_reader_destroy": [_P],
     "rv_hook_program_reader_resume": [_P, C.c_uint64, C.c_uint64],
+    # a Bristol text in windows
+    "rv_bristol_header_prefix": [_P, _Z, C.c_uint64, C.c_int, C.POINTER(BristolInfo), C.POINTER(C.c_size_t)],
+    "rv_bristol_reader_begin": [_P, C.c_uint64, C.c_int, _P, _Z, C.POINTER(_P)],
+    "rv_bristol_reader_feed": [_P, _P, _Z, C.c_int, _P, _Z, C.POINTER(BristolPiece)],
+    "rv_bristol_reader_header": [_P, C.POINTER(BristolInfo)],
+    "rv_bristol_reader_finish": [_P, C.POINTER(BristolInfo)],
+    "rv_bristol_reader_destroy": [_P],
+    "rv_hook_bristol_reader_resume": [_P, C.c_uint64, C.c_uint64, C.c_uint64],
     # the transcript-hash kernels (parity hooks)
     "rv_hook_b3_plan": [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)],
     "rv_hook_b3_chunks": [_P, C.c_int, _P, C.c_uint64, C.c_uint32, C.c_uint64, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64,
@@ -287,7 +301,7 @@ def lib():
         for name in SYMBOLS:
             fn = getattr(L, name)
             if name in ("rv_ctx_destroy", "rv_circuit_destroy", "rv_shard_destroy", "rv_free", "rv_stream_abort", "rv_comm_destroy",
-                        "rv_eval_stream_abort", "rv_program_reader_destroy"):
+                        "rv_eval_stream_abort", "rv_program_reader_destroy", "rv_bristol_reader_destroy"):
                 fn.restype = None
             elif name in ("rv_hook_early_proofs", "rv_hook_open_direct_proofs", "rv_hook_verify_vc_count", "rv_hook_ops_cache_hits", "rv_hook_overlap_commits",
                           "rv_hook_verify_proof_bytes", "rv_hook_stream_device_chunks"):

@@ -205,3 +205,166 @@ def dumps(prog, n_outputs: int = 0) -> bytes:
     for k in range(3):
         buf[pk + k] = kinds[:, k]
     return head + buf.tobytes()
+
+
+# ---- a text read in windows (rv_bristol_reader_*) ----
+def _expected(expected_outputs):
+    """(array or None, address or None, count) of the expected outputs, as the C calls take them"""
+    if expected_outputs is None:
+        return None, None, 0
+    exp = np.ascontiguousarray(np.asarray(expected_outputs, dtype=np.uint8))
+    return exp, (exp.ctypes.data if exp.size else _EMPTY.ctypes.data), int(exp.size)
+
+
+class DeviceReader:
+    """`parse_device` for a text that is handed over in windows: consecutive byte ranges of any length (rv_bristol_reader_*).  Neither
+    the text nor its records are ever whole in memory, and file_len may be 2^32 and more (one window stays below 2^32 bytes).
+
+        with DeviceReader(file_len, expected_outputs) as r:
+            for window in windows: ops, piece = r.feed(window)    # the records of the gate lines that are now complete
+            info = r.finish()                                     # parse_device's info, for the whole text
+
+    The records of all feeds, in order, are exactly `parse`'s records for the whole text, and the first error raised is `parse`'s
+    error, for every byte string and every way of cutting it; afterwards the reader takes nothing more.  The Input ops come with the
+    feed that completes the header, the assertion pairs with the feed that completes the last gate line; bytes behind that line are
+    never judged and need not be fed."""
+
+    def __init__(self, file_len: int, expected_outputs: Optional[Sequence[int]] = None, fmt: int = 0, device=None):
+        from .proof import Context
+
+        self.ctx = device if isinstance(device, Context) else Context.default() if device is None else Context(int(device))
+        self.handle = C.c_void_p()
+        exp, p_exp, self.n_expected = _expected(expected_outputs)
+        _lib.check(_lib.lib().rv_bristol_reader_begin(self.ctx.handle, C.c_uint64(int(file_len)), C.c_int(fmt),
+                                                      C.c_void_p(p_exp) if p_exp is not None else None, C.c_size_t(self.n_expected), C.byref(self.handle)))
+
+    def feed(self, data, scan: bool = False, out=None):
+        """-> (ops, piece).  data: bytes, any buffer (an mmap or a slice of one, a uint8 numpy array) or a uint8 torch tensor in GPU
+        memory (a slice of a larger one is fine; no alignment is asked).  ops: a torch uint8 tensor [n, 24] in GPU memory; scan=True:
+        None -- nothing is written, the piece and the info are complete all the same.  piece: first_op, n_ops, n_input_gf2 (what a
+        stream feed of these records takes from the witness; n_input_z64 is 0), first_line, n_lines.  out: a uint8 GPU tensor to
+        write into instead of a new one.  Where the buffer is too small for the feed -- len(data) // 6 + 1 records are tried first, a
+        header's inputs and pairs and a line carried over can ask for more -- the same bytes are fed again with the count the
+        library names (rv_stream_finish_device's rule)."""
+        import torch
+
+        from .proof import _is_device_ops
+
+        on_device = _is_device_ops(data)
+        if on_device:
+            if data.device.type != "cuda" or data.dtype != torch.uint8 or not data.is_contiguous():
+                raise ValueError("a tensor of text bytes must be a contiguous uint8 tensor in GPU memory")
+            if data.device.index is not None and data.device.index != self.ctx.device:
+                raise ValueError(f"the data is on {data.device}, the context on device {self.ctx.device}")
+            torch.cuda.synchronize(data.device)
+            n_data, p_data = data.numel(), data.data_ptr() if data.numel() else _EMPTY.ctypes.data
+            on_device = bool(data.numel())
+        else:
+            buf = _host_buffer(data)
+            n_data, p_data = buf.size, buf.ctypes.data if buf.size else _EMPTY.ctypes.data
+        piece = _lib.BristolPiece()
+
+        def call(ops, cap):
+            return _lib.lib().rv_bristol_reader_feed(self.handle, C.c_void_p(p_data), C.c_size_t(n_data), C.c_int(1 if on_device else 0),
+                                                     C.c_void_p(ops.data_ptr()) if ops is not None else None, C.c_size_t(cap), C.byref(piece))
+
+        ops = None
+        if scan:
+            _lib.check(call(None, 0))
+        else:
+            dev = torch.device("cuda", self.ctx.device)
+            if out is None:
+                out = torch.empty((n_data // 6 + 1, OP_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            elif not _is_device_ops(out) or out.device.type != "cuda" or out.dtype != torch.uint8 or not out.is_contiguous():
+                raise ValueError("out must be a contiguous uint8 tensor in GPU memory")
+            ops, cap = out.reshape(-1, OP_DTYPE.itemsize), out.numel() // OP_DTYPE.itemsize
+            rc = call(ops, cap)
+            if rc == _RV_E_ARG and int(piece.n_ops) > cap:  # the capacity answer: the reader has not moved
+                cap = int(piece.n_ops)
+                ops = torch.empty((cap, OP_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+                rc = call(ops, cap)
+            _lib.check(rc)
+        d = {k: int(getattr(piece, k)) for k, _ in piece._fields_}
+        d["n_input_z64"] = 0
+        return (ops[:d["n_ops"]] if ops is not None else None), d
+
+    def header(self) -> dict:
+        """the header's counts (n_gates, n_wires, n_inputs, n_outputs, gf2_wires, wire_counts) once the header is in (an error before)"""
+        info = _lib.BristolInfo()
+        _lib.check(_lib.lib().rv_bristol_reader_header(self.handle, C.byref(info)))
+        return _info_dict(info)
+
+    def finish(self) -> dict:
+        """`parse_device`'s info for the whole text, once the gate lines the header counts and the pairs are out (an error before)"""
+        info = _lib.BristolInfo()
+        _lib.check(_lib.lib().rv_bristol_reader_finish(self.handle, C.byref(info)))
+        return _info_dict(info)
+
+    def close(self):
+        if self.handle:
+            if self.ctx.handle:
+                _lib.lib().rv_bristol_reader_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def iter_device(source, window_bytes: int = 64 << 20, expected_outputs: Optional[Sequence[int]] = None, fmt: int = 0, device=None, scan: bool = False,
+                info=None):
+    """The Bristol text `source` -- a path (memory-mapped), a buffer or a uint8 torch tensor in GPU memory -- read in windows of
+    window_bytes: yields `DeviceReader.feed`'s (ops, piece) per window, windows that complete no line included.  Device memory is
+    one window, its work memory and its records, whatever the text's length.  info: a dict that receives `finish`'s info at the
+    end."""
+    from .program_file import _window_source
+
+    window_bytes = int(window_bytes)
+    if not 0 < window_bytes < 1 << 32:
+        raise ValueError("window_bytes must be in [1, 2^32)")
+    data, n = _window_source(source)
+    with DeviceReader(n, expected_outputs, fmt, device) as r:
+        for at in range(0, max(n, 1), window_bytes):
+            yield r.feed(data[at:at + window_bytes], scan=scan)
+        done = r.finish()
+        if info is not None:
+            info.update(done)
+
+
+def wire_counts(source, expected_outputs: Optional[Sequence[int]] = None, fmt: int = 0) -> Tuple[int, int]:
+    """(0, gf2_wires) of a Bristol text -- what a stream over `iter_device` begins with -- from the head of `source` (a path, a buffer
+    or a uint8 GPU tensor) alone: rv_bristol_header_prefix on the first bytes that hold four non-blank lines.  No pass over the text:
+    the header names the wires, and the assertion temporaries are one per expected output.  Errors are the header's."""
+    from .program_file import _window_source
+
+    data, n = _window_source(source)
+    exp, _, n_exp = _expected(expected_outputs)
+    take = min(n, 4096)
+    while True:
+        head = data[:take]
+        head = _host_buffer(head.cpu().numpy() if hasattr(head, "cpu") else head)
+        lines, token = 0, False
+        for c in head.tobytes():
+            if c == 10:
+                lines, token = lines + token, False
+            elif c not in (32, 9, 13):
+                token = True
+            if lines >= 4:
+                break
+        if lines >= 4 or take == n:
+            break
+        take = min(n, take * 2)
+    bi, off = _lib.BristolInfo(), C.c_size_t()
+    _lib.check(_lib.lib().rv_bristol_header_prefix(C.c_void_p(head.ctypes.data if head.size else _EMPTY.ctypes.data), C.c_size_t(head.size), C.c_uint64(n),
+                                                   C.c_int(fmt), C.byref(bi), C.byref(off)))
+    if exp is not None and n_exp != int(bi.n_outputs):
+        _lib.check(_RV_E_ARG)
+    return 0, int(bi.n_wires) + (n_exp if exp is not None else 0)

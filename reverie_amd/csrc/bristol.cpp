@@ -149,6 +149,11 @@ extern "C" int rv_bristol_header(const char* text, size_t len, int format, rv_br
     return rv_internal_bristol_header(text, len, len, format, 0, 0, info, gates_offset);
 }
 
+extern "C" int rv_bristol_header_prefix(const char* text, size_t len, uint64_t full_len, int format, rv_bristol_info* info, size_t* gates_offset) {
+    if (!text || !info || !gates_offset || len > full_len) return RV_E_ARG;
+    return rv_internal_bristol_header(text, len, (size_t)full_len, format, 0, 0, info, gates_offset);
+}
+
 static int parse_impl(const char* text, size_t len, int format, const uint8_t* expected_outputs, size_t n_expected, rv_op** ops,
                       size_t* n_ops, rv_bristol_info* info) {
     if (!text || !ops || !n_ops) return RV_E_ARG;
