@@ -946,6 +946,53 @@ int rv_ops_compact_wires(const rv_op *ops, size_t n_ops, size_t z64_wires, size_
 int rv_ops_compact_wires_device(rv_ctx *ctx, const rv_op *d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, rv_op *d_out,
                                 rv_compact_info *info);
 
+/* The same result for a list that is read in windows: the list passes through in feeds, twice -- a scan pass, then a
+ * rewrite pass -- and the records of all rewrite feeds together are rv_ops_compact_wires' records byte for byte, `info` its info,
+ * however the two passes are cut (the cuts are independent; feeds of 0 and 1 ops are allowed).
+ *
+ *   begin -> scan* -> scan_end [-> scan* -> scan_end] -> feed* [-> rewind -> feed*]... -> destroy
+ *
+ * scan       validates the ops (against the counts in force, carried from feed to feed) and records liveness.  A list
+ *            rv_ops_compact_wires refuses is refused with the same code by the scan feed that holds the first bad op in op order;
+ *            after that only destroy is accepted.
+ * scan_end   *again = 1: the list holds a B2A op.  Which GF(2) indices are pinned is known only now, and pinning changes which ops
+ *            take slots, so the whole list must be scanned once more (nothing is validated a second time), and scan_end called
+ *            again; it then gives *again = 0.  *again = 0: info is filled (when not NULL) and the rewrite pass may begin.
+ * feed       writes the feed's n_ops renumbered records to d_out (device memory; may equal a device `ops`, no other overlap).
+ * rewind     after a complete rewrite pass: the next feed is op 0 again (a prover reads its source twice).
+ *
+ * ops: host memory (ops_on_device == 0; the library uploads the feed) or memory of the context's device, by
+ * rv_circuit_compile_device's conventions, checked before anything is launched.  A rescan and every rewrite pass must be the list of
+ * the first scan: each pass carries the position-keyed digest of its ops and their count; a feed beyond the first scan's count, a
+ * scan_end or rewind of a shorter pass, and a digest that differs at the end of a pass (reported by the last feed of a rewrite pass,
+ * by scan_end of a rescan) are RV_E_ARG.  Calling out of order is RV_E_ARG and leaves the object as it was.  RV_E_UNSUPPORTED: 2^31
+ * ops or more in all (from the feed that crosses it) or in one feed, a wire count in force of 2^31 or more.
+ * RV_E_NOMEM or RV_E_DEVICE from any call: the carried state may be half moved; only destroy is accepted afterwards.
+ *
+ * Memory, all from the context arena.  Held between calls (rv_compactor_info.state_bytes, at most
+ *   8 * (Wz + Wg) + 8 * Wg * [a B2A op was met] + total_ops + 4 * (new z64 count + new gf2 count) + 4096):
+ *   8 bytes per wire index in force per domain (the tables grow when a SizeHint raises a count), 8 more per GF(2) index once a B2A op
+ *   was met (pinned flags and ranks), one mark byte per op of the list, 4 bytes per new slot (the free-slot queues).  Nothing else
+ *   follows the list's length; the index tables follow the OLD wire counts, which is what liveness needs to know.
+ * Per feed, given back before the call returns (peak_feed_bytes: the largest so far): 20 bytes per op of the feed in a scan feed, 68 in
+ *   a rewrite feed, plus 24 per op for an uploaded host feed and the scans' block sums (below 1 %).  scan_end reads the marks once,
+ *   with 24 bytes per 256 ops. */
+typedef struct rv_compactor rv_compactor;
+typedef struct rv_compactor_info {
+    uint64_t total_ops;       /* ops of the first scan pass so far (the list's length once it ended) */
+    uint64_t state_bytes;     /* device memory held now */
+    uint64_t peak_feed_bytes; /* the most work memory one call took */
+    uint32_t scans;           /* scan passes ended */
+    uint32_t b2a;             /* 1: a B2A op was met */
+} rv_compactor_info;
+int rv_compactor_begin(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, rv_compactor **out);
+int rv_compactor_scan(rv_compactor *c, const rv_op *ops, size_t n_ops, int ops_on_device);
+int rv_compactor_scan_end(rv_compactor *c, int *again, rv_compact_info *info /* filled when *again == 0; may be NULL */);
+int rv_compactor_feed(rv_compactor *c, const rv_op *ops, size_t n_ops, int ops_on_device, rv_op *d_out);
+int rv_compactor_rewind(rv_compactor *c);
+int rv_compactor_get_info(const rv_compactor *c, rv_compactor_info *info);
+void rv_compactor_destroy(rv_compactor *c);
+
 /* ---- program files (host only, no GPU) ---------------------------------------------------
  * The reference CLI reads its gate stream as bincode 1.3 of Vec<mcircuit::CombineOperation>
  * (src/main.rs:66,98,122).  rv_program_from_bincode turns such a file into rv_op records, rv_program_to_bincode

@@ -86,6 +86,16 @@ def compact_program(prog, wc):
     return out, new_wc
 
 
+def compact_windows(wc, pieces):
+    """--compact-windows: the pieces of a source that is read in windows, renumbered by liveness in windows (compact.compact_pieces:
+    the scan pass runs here, every later pass reads the source again) and the new wire counts; --compact-wires' line goes to stderr"""
+    from .compact import compact_pieces
+
+    new_wc, pieces2, _ = compact_pieces(pieces, wc)
+    print("compact-wires: wire counts (z64, gf2) %s -> %s" % (tuple(int(x) for x in wc), new_wc), file=sys.stderr)
+    return new_wc, pieces2
+
+
 def evaluate_clear(prog, witness):
     """`oneshot`: cleartext evaluation (mcircuit::evaluate_composite_program, main.rs:115-132);
     GF(2) gates only, like the CLI's witness type.  Raises on a failing AssertZero."""
@@ -146,7 +156,7 @@ def evaluate_gpu(prog, wc, witness, compiler="host"):
         raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (r.first_failed_op, r.n_failed))
 
 
-def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_path=None, compact=False, windowed=True):
+def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_path=None, compact=False, windowed=True, in_windows=False):
     """What a stream needs of a program file: (wire counts, pieces) -- pieces() returns a fresh iterator of (ops, Input counts or
     None) for every pass (`reverie_amd.stream.*_streaming_pieces`).
       rvops                              read through a memory map, STREAM_FEED_OPS records per piece; the wire counts come from one
@@ -156,7 +166,10 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
       bristol, parser "device", window_mb given  read in windows of window_mb MiB on the GPU (bristol.iter_device); the wire counts
                                          come from the header (bristol.wire_counts): no scan pass.  Device memory: one window
       mcircuit-bincode with the host parser, Bristol otherwise, and windowed=False: parsed whole, one piece
-    compact (--compact-wires): the whole list is renumbered by liveness first, then fed, under the new counts."""
+    compact (--compact-wires): the whole list is renumbered by liveness first, then fed, under the new counts.
+    in_windows (--compact-windows; one of the three windowed sources above): the windows stay, and the pieces are renumbered by
+    liveness window by window (`compact_windows`)."""
+    finish = compact_windows if in_windows else (lambda wc, pieces: (wc, pieces))
     if fmt == "auto":
         fmt = "rvops" if program_path.endswith(".rvops") else "bristol"
     if fmt == "mcircuit-bincode" and parser == "device" and windowed and not compact:
@@ -164,13 +177,13 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
 
         window = (DEFAULT_WINDOW_MB if window_mb is None else int(window_mb)) << 20
         wc = program_file.scan_device(program_path, window)["wire_counts"]
-        return wc, lambda: program_file.iter_device(program_path, window)
+        return finish(wc, lambda: program_file.iter_device(program_path, window))
     if fmt == "bristol" and parser == "device" and windowed and window_mb is not None and not compact:
         from . import bristol
 
         exp = parse_witness(open(expected_path, "rb").read()) if expected_path else None
         wc = bristol.wire_counts(program_path, exp)
-        return wc, lambda: bristol.iter_device(program_path, int(window_mb) << 20, exp)
+        return finish(wc, lambda: bristol.iter_device(program_path, int(window_mb) << 20, exp))
     if parser == "device" and fmt in ("bristol", "mcircuit-bincode"):  # the op tensor is the one piece (compacted where it lies)
         prog, wc = load_program_device(program_path, expected_path, fmt)
         if compact:
@@ -196,20 +209,21 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
         wc = (z64, gf2)
     if compact:
         prog, wc = compact_program(np.asarray(prog), wc)
-    return wc, lambda: ((np.asarray(prog[at:at + STREAM_FEED_OPS]), None) for at in range(0, max(n, 1), STREAM_FEED_OPS))
+    return finish(wc, lambda: ((np.asarray(prog[at:at + STREAM_FEED_OPS]), None) for at in range(0, max(n, 1), STREAM_FEED_OPS)))
 
 
 def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, device_compile=False, device_z64=False, device_b2a=False,
-                    compact=False, parser="host", window_mb=None):
+                    compact=False, parser="host", window_mb=None, in_windows=False):
     """`oneshot --evaluator stream`: the program evaluated in pieces with bounded device memory (rv_eval_stream_*), on the GPU like
     --evaluator gpu and with the same outcome.  An rvops file is read through a memory map, piece by piece; its wire counts come from
     one pass over the mapping.  window_mb (--window-mb, with --parser device): an mcircuit-bincode file is read in windows of that
     many MiB on the GPU, and so is a Bristol file; without it, either is parsed whole.  compact (--compact-wires): the whole list is renumbered by liveness first
-    (in host memory: 24 bytes per op, against a wire-store row per gate of an SSA list) and the stream begins with the new counts."""
+    (in host memory: 24 bytes per op, against a wire-store row per gate of an SSA list) and the stream begins with the new counts;
+    in_windows (--compact-windows): the pieces are renumbered window by window instead, and nothing is whole in memory."""
     from .stream import StreamingEvaluator, _piece_inputs
 
     wit = np.ascontiguousarray(np.asarray(witness, dtype=np.uint8))
-    wc, pieces = stream_pieces(program_path, fmt, parser, window_mb, expected_path, compact, windowed=window_mb is not None)
+    wc, pieces = stream_pieces(program_path, fmt, parser, window_mb, expected_path, compact, windowed=window_mb is not None, in_windows=in_windows)
     se = StreamingEvaluator(wc, 1, max_chunk_ops, device_compile=device_compile, **({"device_z64": True} if device_z64 else {}),
                             **({"device_b2a": True} if device_b2a else {}))
     try:
@@ -234,7 +248,7 @@ def run_streamed(a, ap, device_parser: bool) -> int:
     if a.strict and a.reference_compat:
         ap.error("--strict and --reference-compat exclude each other")
     wc, pieces = stream_pieces(a.program_path, a.program_format, "device" if device_parser else "host", a.window_mb, a.expected_outputs_path,
-                               a.compact_wires)
+                               a.compact_wires, in_windows=a.compact_windows)
     kw = dict(max_chunk_ops=a.max_chunk_ops, device_compile=a.compiler != "host", device_z64=a.compiler in ("device-z64", "device-b2a"),
               device_b2a=a.compiler == "device-b2a")
     if a.operation in ("prove", "oneshot-zk"):
@@ -300,7 +314,8 @@ def build_parser():
     ap.add_argument("--window-mb", type=int, default=None,
                     help="--program-format mcircuit-bincode --parser device with --stream, or with oneshot --evaluator stream (which reads the "
                          "file in windows only when this is given): MiB of the file per window (default %d).  A Bristol file with --parser "
-                         "device is read in windows only when this is given (and --compact-wires is not); without it, it is parsed whole"
+                         "device is read in windows only when this is given (and --compact-wires is not: --compact-windows keeps the windows); "
+                         "without it, it is parsed whole"
                          % DEFAULT_WINDOW_MB)
     ap.add_argument("--compiler", default="host", choices=["host", "device", "device-z64", "device-b2a"],
                     help="prove / verify / oneshot-zk and oneshot --evaluator gpu / stream: compile the program (the stream's pieces) on the host "
@@ -318,6 +333,11 @@ def build_parser():
                     help="prove / verify / oneshot-zk and oneshot --evaluator stream: renumber the program's wires by liveness first "
                          "(rv_ops_compact_wires), so that an SSA-numbered program needs a wire per live value instead of one per gate; "
                          "the proof bytes and the outcome are the same, the wire counts before and after are printed on stderr")
+    ap.add_argument("--compact-windows", action="store_true",
+                    help="--stream, or oneshot --evaluator stream, on a source that is read in windows (an rvops file; with --parser device "
+                         "an mcircuit-bincode file, or a Bristol file with --window-mb): renumber the wires by liveness window by window "
+                         "(rv_compactor_*: the source is read once more for a scan pass, twice with B2A ops), so that neither the op list nor "
+                         "a wire per gate is ever in memory; the result, the proof bytes and the stderr line are --compact-wires'")
     ap.add_argument("--reference-compat", action="store_true",
                     help="verify / oneshot-zk: RV_VERIFY_REFERENCE_COMPAT -- answer exactly like the reference's verifier, which "
                          "accepts proofs whose opened repetitions fail an AssertZero or name another omitted player than the "
@@ -348,6 +368,14 @@ def main(argv=None) -> int:
     if fmt == "auto":
         fmt = "rvops" if a.program_path.endswith(".rvops") else "bristol"
     device_parser = a.parser == "device" and fmt in ("bristol", "mcircuit-bincode")
+    if a.compact_windows:
+        streamed = a.stream or (a.operation == "oneshot" and a.evaluator == "stream")
+        windows = fmt == "rvops" or (device_parser and (a.window_mb is not None or (fmt == "mcircuit-bincode" and a.stream)))
+        if a.compact_wires:
+            ap.error("--compact-windows and --compact-wires exclude each other")
+        if not (streamed and windows):
+            ap.error("--compact-windows needs a source that is read in windows: --stream or oneshot --evaluator stream, with an rvops file, "
+                     "or with --parser device and an mcircuit-bincode file or a Bristol file and --window-mb")
     if device_parser and a.operation == "oneshot":
         if a.evaluator == "host":
             ap.error("--parser device leaves the program in GPU memory: --evaluator host cannot read it (use gpu or stream)")
@@ -358,7 +386,8 @@ def main(argv=None) -> int:
         evaluate_stream(a.program_path, a.program_format, a.expected_outputs_path, parse_witness(open(a.witness_path, "rb").read()),
                         a.max_chunk_ops, device_compile=a.compiler != "host", **({"device_z64": True} if a.compiler in ("device-z64", "device-b2a") else {}),
                         **({"device_b2a": True} if a.compiler == "device-b2a" else {}), **({"compact": True} if a.compact_wires else {}),
-                        **({"parser": "device"} if device_parser else {}), **({"window_mb": a.window_mb} if a.window_mb is not None else {}))
+                        **({"parser": "device"} if device_parser else {}), **({"window_mb": a.window_mb} if a.window_mb is not None else {}),
+                        **({"in_windows": True} if a.compact_windows else {}))
         print("()")
         return 0
     if a.stream:

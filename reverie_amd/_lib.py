@@ -70,6 +70,10 @@ class CompactInfo(C.Structure):  # rv_compact_info
                 ("z64_zero_wire", C.c_uint32), ("gf2_values", C.c_uint64), ("z64_values", C.c_uint64)]
 
 
+class CompactorInfo(C.Structure):  # rv_compactor_info
+    _fields_ = [("total_ops", C.c_uint64), ("state_bytes", C.c_uint64), ("peak_feed_bytes", C.c_uint64), ("scans", C.c_uint32), ("b2a", C.c_uint32)]
+
+
 class ProgramInfo(C.Structure):  # rv_program_info
     _fields_ = [(n, C.c_uint64) for n in ("n_ops", "bytes", "z64_wires", "gf2_wires", "n_gf2", "n_z64", "n_b2a", "n_sizehint")]
 
@@ -126,6 +130,8 @@ SYMBOLS = [
     "rv_hook_compile_levels", "rv_hook_circuit_levels", "rv_hook_interp_launches",
     "rv_hook_interp64_launches", "rv_hook_z64_fused_grid", "rv_hook_z64_fused_levels",
     "rv_ops_compact_wires", "rv_ops_compact_wires_device",
+    "rv_compactor_begin", "rv_compactor_scan", "rv_compactor_scan_end", "rv_compactor_feed", "rv_compactor_rewind", "rv_compactor_get_info",
+    "rv_compactor_destroy",
     "rv_bristol_header", "rv_bristol_parse_device", "rv_hook_bristol_tiles",
     "rv_program_from_bincode_device", "rv_program_to_bincode_device", "rv_hook_bincode_tiles",
     "rv_program_reader_begin", "rv_program_reader_feed", "rv_program_reader_finish", "rv_program_reader_destroy", "rv_hook_program_reader_resume",
@@ -217,6 +223,13 @@ ARGTYPES = {
     # wire indices compacted by liveness
     "rv_ops_compact_wires": [_P, _Z, _Z, _Z, _P, C.POINTER(CompactInfo)],
     "rv_ops_compact_wires_device": [_P, _P, _Z, _Z, _Z, _P, C.POINTER(CompactInfo)],
+    "rv_compactor_begin": [_P, _Z, _Z, C.POINTER(C.c_void_p)],
+    "rv_compactor_scan": [_P, _P, _Z, C.c_int],
+    "rv_compactor_scan_end": [_P, C.POINTER(C.c_int), C.POINTER(CompactInfo)],
+    "rv_compactor_feed": [_P, _P, _Z, C.c_int, _P],
+    "rv_compactor_rewind": [_P],
+    "rv_compactor_get_info": [_P, C.POINTER(CompactorInfo)],
+    "rv_compactor_destroy": [_P],
     # the Bristol parser on the GPU
     "rv_bristol_header": [_P, _Z, C.c_int, C.POINTER(BristolInfo), C.POINTER(C.c_size_t)],
     "rv_bristol_parse_device": [_P, _P, _Z, C.c_int, C.c_int, _P, _Z, _P, _Z, C.POINTER(C.c_size_t), C.POINTER(BristolInfo)],
@@ -301,7 +314,7 @@ def lib():
         for name in SYMBOLS:
             fn = getattr(L, name)
             if name in ("rv_ctx_destroy", "rv_circuit_destroy", "rv_shard_destroy", "rv_free", "rv_stream_abort", "rv_comm_destroy",
-                        "rv_eval_stream_abort", "rv_program_reader_destroy", "rv_bristol_reader_destroy"):
+                        "rv_eval_stream_abort", "rv_program_reader_destroy", "rv_bristol_reader_destroy", "rv_compactor_destroy"):
                 fn.restype = None
             elif name in ("rv_hook_early_proofs", "rv_hook_open_direct_proofs", "rv_hook_verify_vc_count", "rv_hook_ops_cache_hits", "rv_hook_overlap_commits",
                           "rv_hook_verify_proof_bytes", "rv_hook_stream_device_chunks"):

@@ -25,6 +25,7 @@
 #include "bincode_dev.h"
 #include "compile.h"
 #include "compact_dev.h"
+#include "compact_win.h"
 #include "compile_dev.h"
 #include "internal.h"
 #include "launch.h"

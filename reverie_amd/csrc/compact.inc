@@ -1,5 +1,6 @@
 // Part of api.hip (#included there, one translation unit): rv_ops_compact_wires_device -- the wire compaction of compact_dev.hip on the
-// context's stream, its work memory from the context arena.  (rv_ops_compact_wires, the host sweep, is compact.cpp.)
+// context's stream, its work memory from the context arena -- and rv_compactor_*, the same for a list read in windows (compact_win.hip).
+// (rv_ops_compact_wires, the host sweep, is compact.cpp.)
 
 extern "C" int rv_ops_compact_wires_device(rv_ctx* ctx, const rv_op* d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, rv_op* d_out,
                                            rv_compact_info* info) {
@@ -22,4 +23,114 @@ extern "C" int rv_ops_compact_wires_device(rv_ctx* ctx, const rv_op* d_ops, size
         g_last_error = "out of host memory";
         return RV_E_NOMEM;
     }
+}
+
+// ---- rv_compactor_*: the same compaction for a list read in windows (compact_win.hip), on the context's stream and arena ----
+struct rv_compactor {
+    rv_ctx* ctx;
+    WinCompactor* w;
+};
+
+extern "C" int rv_compactor_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, rv_compactor** out) {
+    if (!ctx || !out) return RV_E_ARG;
+    *out = nullptr;
+    return guarded([&]() -> int {
+        LibBusy busy_guard;
+        HIPCHK(hipSetDevice(ctx->device));
+        std::unique_ptr<rv_compactor> c(new rv_compactor{ctx, nullptr});
+        const int rc = wincompact_begin(ctx->stream, ctx_dev_allocator(ctx), z64_wires, gf2_wires, &c->w);
+        if (rc == RV_E_NOMEM) g_last_error = "windowed wire compaction: out of device memory";
+        if (rc == RV_E_DEVICE) g_last_error = "windowed wire compaction: HIP error";
+        if (rc) return rc;
+        *out = c.release();
+        return RV_OK;
+    });
+}
+
+extern "C" void rv_compactor_destroy(rv_compactor* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->ctx->device);
+    wincompact_destroy(c->w);
+    delete c;
+}
+
+// a scan feed (d_out null) or a rewrite feed
+static int compactor_pass(rv_compactor* c, const rv_op* ops, size_t n_ops, int ops_on_device, rv_op* d_out, bool rewrite) {
+    if (!c || (n_ops && (!ops || (rewrite && !d_out)))) return RV_E_ARG;
+    if (n_ops > (size_t)-1 / sizeof(rv_op)) return RV_E_UNSUPPORTED;
+    rv_ctx* ctx = c->ctx;
+    return guarded([&]() -> int {
+        LibBusy busy_guard;
+        HIPCHK(hipSetDevice(ctx->device));
+        const size_t bytes = n_ops * sizeof(rv_op);
+        if (n_ops) {
+            if (ops_on_device)
+                if (int rb = device_bytes_ok(ctx, ops, bytes, 8)) return rb;
+            if (rewrite) {
+                if (int rb = device_bytes_ok(ctx, d_out, bytes, 8)) return rb;
+                const uint8_t *i0 = (const uint8_t*)ops, *o0 = (const uint8_t*)d_out;
+                if (ops_on_device && o0 != i0 && o0 < i0 + bytes && i0 < o0 + bytes) return RV_E_ARG;
+            }
+        }
+        // (asked before the upload: a call out of order moves nothing)
+        if (const int rc = rewrite ? wincompact_admit_feed(c->w, n_ops) : wincompact_admit_scan(c->w, n_ops)) return rc;
+        void* d_up = nullptr;
+        const rv_op* d_ops = ops;
+        if (n_ops && !ops_on_device) {
+            if (ctx->alloc(bytes, &d_up) != RV_OK) {
+                g_last_error = "windowed wire compaction: out of device memory";
+                return RV_E_NOMEM;
+            }
+            if (hipMemcpyAsync(d_up, ops, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+                (void)hipStreamSynchronize(ctx->stream);
+                ctx->release(d_up);
+                g_last_error = "windowed wire compaction: HIP error";
+                return RV_E_DEVICE;
+            }
+            d_ops = (const rv_op*)d_up;
+        }
+        const int rc = rewrite ? wincompact_feed(c->w, d_ops, n_ops, d_out, d_up ? bytes : 0) : wincompact_scan(c->w, d_ops, n_ops, d_up ? bytes : 0);
+        if (d_up) {
+            (void)hipStreamSynchronize(ctx->stream);
+            ctx->release(d_up);
+        }
+        if (rc == RV_E_DEVICE) g_last_error = "windowed wire compaction: HIP error";
+        if (rc == RV_E_NOMEM) g_last_error = "windowed wire compaction: out of device memory";
+        if (rc == RV_E_ARG) g_last_error = "windowed wire compaction: the pass is not the list that was scanned";
+        return rc;
+    });
+}
+
+extern "C" int rv_compactor_scan(rv_compactor* c, const rv_op* ops, size_t n_ops, int ops_on_device) {
+    return compactor_pass(c, ops, n_ops, ops_on_device, nullptr, false);
+}
+
+extern "C" int rv_compactor_feed(rv_compactor* c, const rv_op* ops, size_t n_ops, int ops_on_device, rv_op* d_out) {
+    return compactor_pass(c, ops, n_ops, ops_on_device, d_out, true);
+}
+
+extern "C" int rv_compactor_scan_end(rv_compactor* c, int* again, rv_compact_info* info) {
+    if (!c || !again) return RV_E_ARG;
+    return guarded([&]() -> int {
+        LibBusy busy_guard;
+        HIPCHK(hipSetDevice(c->ctx->device));
+        const int rc = wincompact_scan_end(c->w, again, info);
+        if (rc == RV_E_DEVICE) g_last_error = "windowed wire compaction: HIP error";
+        if (rc == RV_E_NOMEM) g_last_error = "windowed wire compaction: out of device memory";
+        return rc;
+    });
+}
+
+extern "C" int rv_compactor_rewind(rv_compactor* c) {
+    if (!c) return RV_E_ARG;
+    return guarded([&]() -> int {
+        LibBusy busy_guard;
+        HIPCHK(hipSetDevice(c->ctx->device));
+        return wincompact_rewind(c->w);
+    });
+}
+
+extern "C" int rv_compactor_get_info(const rv_compactor* c, rv_compactor_info* info) {
+    if (!c || !info) return RV_E_ARG;
+    return wincompact_info(c->w, info);
 }

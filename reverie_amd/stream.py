@@ -36,7 +36,10 @@ The one-shot functions take `compact_wires` (default False): the whole op list i
 DESIGN §17) -- on the host for host ops, by kernels for a GPU tensor -- and the stream begins with the new, smaller wire counts, so an
 SSA-numbered list no longer costs a wire-store row per gate.  Proofs and answers are the same bytes; the wire values
 `evaluate_streaming` returns are those of the new indices (an op's renumbered `dst` is where its value lives), and the stream info
-carries rv_compact_info under "compact".  The feeding classes are unchanged: a caller who feeds in pieces compacts the whole list first.
+carries rv_compact_info under "compact".  The feeding classes are unchanged: a caller who feeds in pieces compacts the whole list first
+-- or, with the `*_streaming_pieces` functions, passes `compact_wires=True`: the pieces are then compacted in windows
+(`compact.compact_pieces`, DESIGN §17.5: the source is read once or twice more), nothing is sized by the whole list, and the result is
+the same.
 """
 from __future__ import annotations
 
@@ -62,6 +65,17 @@ def _compacted(ops, wire_counts, ctx: Context, wanted: bool):
     if not wanted:
         return ops, wire_counts, None
     return _compact.compact_wires(ops, wire_counts, ctx)
+
+
+def _compacted_pieces(pieces, wire_counts, ctx: Optional[Context], wanted: bool):
+    """the pieces and wire counts a `*_streaming_pieces` call streams, rv_compact_info (None: compact_wires was not asked for) and
+    the compactor this call made and has to close (None: it made none -- pieces that a caller compacted are the caller's)"""
+    if not wanted:
+        return pieces, wire_counts, None, None
+    if not callable(pieces):
+        raise TypeError("compact_wires reads the pieces more than once: pass a callable that returns a fresh iterator")
+    new_counts, pieces2, cinfo = _compact.compact_pieces(pieces, wire_counts, ctx)
+    return pieces2, new_counts, cinfo, pieces2.compactor
 
 
 def _with_compact(info: dict, cinfo) -> dict:
@@ -734,54 +748,68 @@ def _feed_pieces(feed, pieces, wit_gf2, wit_z64):
 
 def prove_streaming_pieces(pieces, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
                            ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                           device_proof: bool = False) -> "Tuple[Proof | DeviceProof, dict]":
+                           device_proof: bool = False, compact_wires: bool = False) -> "Tuple[Proof | DeviceProof, dict]":
     """`prove_streaming` for an op list that is never whole in memory: `pieces()` returns a fresh iterator of (ops, (n_input_gf2,
     n_input_z64)) for each of the two passes -- `program_file.iter_device` on a program file, say (its piece dicts serve as the
     counts).  ops: a host array or a torch GPU tensor of rv_op records; a host array may come with None, its Inputs are then counted
     here.  Both passes must yield the same pieces (rv_stream_same_cuts is set).  The proof is `prove_streaming`'s for the
-    concatenated list; wire_counts are the whole list's (`program_file.scan_device`).  -> (Proof or DeviceProof, stream info)"""
+    concatenated list; wire_counts are the whole list's (`program_file.scan_device`).  compact_wires: the pieces are renumbered by
+    liveness in windows (`compact.compact_pieces`: the source is read for a scan pass first, twice with B2A ops), wire_counts are
+    the source's and the stream begins with the new ones; the same proof, and info carries "compact".
+    -> (Proof or DeviceProof, stream info)"""
     if not callable(pieces):
         raise TypeError("prove_streaming_pieces reads the pieces twice: pass a callable that returns a fresh iterator")
     g, z = _host_or_device_wit(wit_gf2, np.uint8), _host_or_device_wit(wit_z64, np.uint64)
+    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires)
     sp = StreamingProver(wire_counts, seeds, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
     try:
         sp.same_cuts()
         _feed_pieces(sp.feed, pieces, g, z)
         sp.commit()
         _feed_pieces(sp.feed, pieces, g, z)
-        return sp.finish(device=device_proof), sp.info
+        return sp.finish(device=device_proof), _with_compact(sp.info, cinfo)
     finally:
         sp.close()
+        if own is not None:
+            own.close()
 
 
 def verify_streaming_pieces(pieces, wire_counts: Tuple[int, int], proof, strict: bool = True, max_chunk_ops: int = 0,
                             ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False,
-                            device_b2a: bool = False) -> Tuple[bool, dict]:
+                            device_b2a: bool = False, compact_wires: bool = False) -> Tuple[bool, dict]:
     """`verify_streaming` for pieces as `prove_streaming_pieces` takes them (a callable or, the pass being one, an iterable; the
-    counts are not looked at).  proof: bytes, a Proof, a bincode-form DeviceProof or a uint8 GPU tensor.  -> (ok, stream info)"""
+    counts are not looked at).  proof: bytes, a Proof, a bincode-form DeviceProof or a uint8 GPU tensor.  compact_wires: as in
+    `prove_streaming_pieces` (a callable is needed then).  -> (ok, stream info)"""
+    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires)
     sv = StreamingVerifier(wire_counts, proof, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
     try:
         for ops, _ in (pieces() if callable(pieces) else pieces):
             if ops is not None and len(ops):
                 sv.feed(ops)
-        return sv.finish(strict), sv.info
+        return sv.finish(strict), _with_compact(sv.info, cinfo)
     finally:
         sv.close()
+        if own is not None:
+            own.close()
 
 
 def evaluate_streaming_pieces(pieces, wits_gf2, wits_z64, wire_counts: Tuple[int, int], max_chunk_ops: int = 0, values: bool = False,
                               ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False,
-                              device_b2a: bool = False) -> Evaluation:
+                              device_b2a: bool = False, compact_wires: bool = False) -> Evaluation:
     """`evaluate_streaming` for pieces as `prove_streaming_pieces` takes them, in one pass.  wits_gf2 / wits_z64: [B][n] (1-D for one
-    witness), host arrays or torch GPU tensors.  -> the array-shaped Evaluation; `info` receives the stream's figures."""
+    witness), host arrays or torch GPU tensors.  compact_wires: as in `prove_streaming_pieces` (wire values are those of the new
+    indices).  -> the array-shaped Evaluation; `info` receives the stream's figures (and "compact")."""
     g, z = _host_or_device_wit(wits_gf2, np.uint8), _host_or_device_wit(wits_z64, np.uint64)
+    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires)
     batch = g.shape[0] if g.ndim == 2 else 1
     se = StreamingEvaluator(wire_counts, batch, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
     try:
         _feed_pieces(se.feed, pieces, g, z)
         r = se.finish(values)
         if info is not None:
-            info.update(se.info)
+            info.update(_with_compact(se.info, cinfo))
         return r
     finally:
         se.close()
+        if own is not None:
+            own.close()
