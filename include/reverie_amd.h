@@ -1082,6 +1082,74 @@ void rv_program_reader_destroy(rv_program_reader *r);
  * the records delivered, where the bytes fed end with a record. */
 int rv_hook_program_reader_resume(rv_program_reader *r, uint64_t file_off, uint64_t next_op);
 
+/* ---- Bristol text and program files written on the GPU, whole and in windows --------------------
+ * rv_bristol_write (host only, no GPU) is the definition: the records as Bristol Fashion text, exactly what reverie_amd.bristol.dumps
+ * returns for them.  The header is "%d %d\n1 %d\n1 %d\n\n" of the gate count, n_wires, the input count and n_outputs; the input count
+ * is the length of the leading run of GF(2) Input records, the gate count the records behind it.  Each later record is one line:
+ * Add "2 1 a b dst XOR", Mul "2 1 a b dst AND", AddConst 1 "1 1 a dst INV", AddConst 0 "1 1 a dst EQW", Const "1 1 imm dst EQ";
+ * the fields a line does not name are ignored.  n_wires == 0: the count is the largest index named plus one, or the input count if
+ * that is larger.  text is library-allocated (rv_free).
+ *   RV_E_ARG, before anything else: NULL text or len, or NULL ops with n_ops != 0.  Then the code of the first record in list order
+ * that has one; inside a record: (1) reserved != 0, an unknown domain or opcode (rv_program_to_bincode's rule): RV_E_BAD_OP; (2) a
+ * valid record Bristol text cannot say -- a domain other than GF(2), an Input behind the leading run, an Input of the run whose dst is
+ * not its position, Random, Sub, SubConst, MulConst or AssertZero, AddConst or Const with imm > 1: RV_E_UNSUPPORTED; (3) with a stated
+ * n_wires, an index the line names that is >= n_wires: RV_E_WIRE_OOB (an Input record has no line: the input count is checked next).
+ * Behind the records: n_outputs > n_wires or the input count > n_wires: RV_E_WIRE_OOB (rv_bristol_parse's header checks). */
+int rv_bristol_write(const rv_op *ops, size_t n_ops, uint64_t n_wires /* 0: derive */, uint64_t n_outputs, char **text, size_t *len);
+/* rv_bristol_write for records in device memory: d_text receives the bytes rv_bristol_write produces and the return code is its code,
+ * for every record list.  d_ops: n_ops records, rv_circuit_compile_device's conventions (8-byte aligned, inside one allocation of the
+ * context's device); d_text / cap: memory of that device, no alignment asked.  d_text == NULL or cap < the text's length: RV_E_ARG
+ * with *len = the length, nothing written -- after the records have been judged, so a sizing call (NULL, 0) on bad records returns
+ * their code.  A text of 2^32 bytes or more, or 2^32 records or more: RV_E_UNSUPPORTED.  Nothing is written for a list with a code.
+ * Work memory (4 bytes per record plus the scan's sums, 8 bytes per 2048 records) comes from the context arena and goes back before
+ * the call returns; the call runs on the context's stream and synchronises it once, at the end. */
+int rv_bristol_write_device(rv_ctx *ctx, const rv_op *d_ops, size_t n_ops, uint64_t n_wires, uint64_t n_outputs, char *d_text, size_t cap,
+                            size_t *len);
+/* out[0] = records per workgroup of the emit kernel, out[1] = records per workgroup of the scan (the sizes the tests go around) */
+int rv_hook_bristol_write_tiles(uint32_t out[2]);
+
+/* The two writers fed in windows: consecutive pieces of a record list ("feeds") of any length, 0 and 1 included.
+ *     rv_bristol_writer_begin(ctx, n_ops, n_inputs, n_wires, n_outputs, &w)      rv_program_writer_begin(ctx, n_ops, &w)
+ *     rv_bristol_writer_feed(w, ops, n, ops_on_device, d_text, cap, &piece)      rv_program_writer_feed(w, ops, n, ops_on_device, d_out, cap, &piece)
+ *     rv_bristol_writer_finish(w)                                                rv_program_writer_finish(w)
+ *     rv_bristol_writer_destroy(w)                                               rv_program_writer_destroy(w)
+ * DEFINITION, for every record list and every way of cutting it: the bytes of all feeds, in order, are the bytes of
+ * rv_bristol_write(ops, n_ops, n_wires, n_outputs), respectively rv_program_to_bincode(ops, n_ops), on the whole list, and the first
+ * nonzero code a feed returns is that call's code.  The first feed's bytes begin with the header (the Bristol header lines, or the
+ * 8-byte count), whatever the feed's length; a record is written whole by the feed that brings it; nothing is carried between feeds
+ * but the next ordinal, the file offset and "the header is out", and memory follows the feed, never the list.  n_ops and file_off may
+ * be 2^32 and more; one feed's bytes stay below 2^32 (RV_E_UNSUPPORTED, the writer unchanged; so is a Bristol feed of 2^32 records
+ * and a program feed of 2^28 records or more).
+ *   The Bristol writer is told at begin what the whole-list call derives, because the header goes out first: record i < n_inputs must
+ * be GF(2) Input(i), a record at or behind n_inputs must not be an Input (RV_E_UNSUPPORTED at that record, in rv_bristol_write's order
+ * inside the record), and every index a line names is checked against n_wires (RV_E_WIRE_OOB).  begin: RV_E_ARG for n_inputs > n_ops
+ * or n_wires == 0 with n_ops != 0, then RV_E_WIRE_OOB for n_inputs or n_outputs above n_wires.  With the values rv_bristol_write
+ * would derive the bytes are its bytes.
+ *   cap below what the feed writes (or a NULL buffer: a sizing feed): RV_E_ARG with piece->bytes = the need, nothing written and the
+ * writer unchanged -- the same records are fed again with a larger buffer.  96 + 41 * n bytes always suffice for Bristol text,
+ * 8 + 32 * n for a program file.  Also RV_E_ARG with the writer unchanged, before any launch: a NULL writer or piece, NULL ops with
+ * n != 0, feeding past n_ops, device ops misaligned or outside an allocation, a buffer outside an allocation.
+ *   After a code of the records the writer accepts only destroy (RV_E_ARG otherwise), and what earlier feeds wrote is "anything".
+ * finish: RV_OK once the header and exactly n_ops records are out, RV_E_ARG before.  A list of 0 records is allowed: its header goes
+ * out with a feed of 0 records.
+ *   ops: host memory (ops_on_device == 0; the library uploads the feed into context-arena memory) or memory of the context's device;
+ * host feeds and device feeds mix.  A feed runs on the context's stream and waits for it once; its work memory (4 bytes per record of
+ * the feed, the scan's sums, 24 per record of an uploaded feed) goes back before it returns. */
+typedef struct rv_bristol_writer rv_bristol_writer;
+typedef struct rv_program_writer rv_program_writer;
+typedef struct rv_writer_piece {
+    uint64_t first_op, n_ops; /* the records of this feed: ordinals first_op .. first_op + n_ops - 1 */
+    uint64_t file_off, bytes; /* where the feed's bytes lie in the whole output, and how many they are (or, with RV_E_ARG, would be) */
+} rv_writer_piece;
+int rv_bristol_writer_begin(rv_ctx *ctx, uint64_t n_ops, uint64_t n_inputs, uint64_t n_wires, uint64_t n_outputs, rv_bristol_writer **out);
+int rv_bristol_writer_feed(rv_bristol_writer *w, const rv_op *ops, size_t n, int ops_on_device, char *d_text, size_t cap, rv_writer_piece *piece);
+int rv_bristol_writer_finish(rv_bristol_writer *w);
+void rv_bristol_writer_destroy(rv_bristol_writer *w);
+int rv_program_writer_begin(rv_ctx *ctx, uint64_t n_ops, rv_program_writer **out);
+int rv_program_writer_feed(rv_program_writer *w, const rv_op *ops, size_t n, int ops_on_device, uint8_t *d_out, size_t cap, rv_writer_piece *piece);
+int rv_program_writer_finish(rv_program_writer *w);
+void rv_program_writer_destroy(rv_program_writer *w);
+
 /* ---- parity-test hooks: each mirrors one reference function so tests can compare the
  * HIP path with the oracle piecewise ---- */
 /* PRG::new + gen (crypto/prg.rs:16-37) on the GPU: n_keys keys, blocks [first, first+n_blocks) each */

@@ -14,6 +14,20 @@ same `Ok(())` / `Err("Unverifiable Proof")` result lines.  Differences, stated p
   (rv_program_from_bincode_device).  `--stream` proves and verifies without compiling the program whole (StreamingProver /
   StreamingVerifier), and with `--parser device` reads an mcircuit-bincode file in windows of `--window-mb` on the GPU
   (rv_program_reader_*), so that the file's length is bounded by neither host nor device memory.
+* `--operation convert` reads a program as the other operations do and writes it to `--output-path` in `--output-format` (rvops,
+  mcircuit-bincode or bristol), once, so that later runs need neither the parse nor the compaction: `--compact-wires` renumbers the
+  whole list by liveness first, `--compact-windows` renumbers it window by window.  A source that is read in windows (an
+  mcircuit-bincode or Bristol file with `--parser device` and `--window-mb`; an rvops file with `--compact-windows`) is converted
+  window by window through the windowed writers (rv_program_writer_* / rv_bristol_writer_*: one feed, one copy to the host and one
+  write per window); a source parsed whole with `--parser device` goes through the whole-list device calls
+  (rv_program_to_bincode_device / rv_bristol_write_device), and a source under `--parser host` through the host writers, which need
+  no GPU.  The op count and, for Bristol output, the input count come from where the wire counts come from (the bincode reader's
+  scan pass, the Bristol header plus the assertion pairs, the rvops file's size and its one pass), without another pass over the
+  source; a Bristol text with MAND lines of several lanes holds more records than its header says and is converted without
+  `--window-mb`.  Bristol output takes GF(2) programs of Bristol shape only, so `--expected-outputs-path` is refused with it
+  (assertions are not Bristol); its header states the wire count in force (the compacted count after a compaction, with 0 outputs:
+  renumbered wires are no longer "the last wires").  One line goes to stderr:
+  `convert: N ops, wire counts (z64, gf2) A -> B, M bytes`.
 * proofs are the same bincode bytes.
 * verification is strict by default (`--reference-compat` restores the reference verifier's two unchecked
   conditions), and a rejected proof exits with status 1 (the reference prints the same
@@ -240,6 +254,123 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
         raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (r.first_failed_op[0], r.n_failed[0]))
 
 
+def _unwritable_op(prog):
+    """the first record of a host op list that Bristol text cannot say (rv_bristol_write's RV_E_UNSUPPORTED or RV_E_BAD_OP), or None"""
+    p = np.asarray(prog)
+    idx = np.arange(len(p))
+    is_in = (p["domain"] == 0) & (p["opcode"] == 0)
+    n_in = int(np.argmin(is_in)) if not is_in.all() else len(p)
+    bad = (p["domain"] != 0) | (p["reserved"] != 0) | (is_in & ((idx >= n_in) | (p["dst"] != idx))) | ~np.isin(p["opcode"], (0, 2, 3, 6, 9)) | \
+        (np.isin(p["opcode"], (3, 9)) & (p["imm"] > 1))
+    return int(np.argmax(bad)) if bad.any() else None
+
+
+def convert_source(a, fmt, device_parser: bool):
+    """`stream_pieces`' sibling for --operation convert: the source as --stream understands it, and what the writers are told at
+    begin.  -> dict(wc, wc_out, n_ops, n_inputs, n_outputs, and either prog -- the whole list, a host array or a GPU tensor -- or
+    pieces -- a callable that returns a fresh iterator of (ops, anything), for a source that is read in windows)."""
+    from . import bristol, program_file
+
+    path, exp_path = a.program_path, a.expected_outputs_path
+    exp = parse_witness(open(exp_path, "rb").read()) if exp_path else None
+    windowed = a.window_mb is not None and device_parser and not a.compact_wires
+    d = {"n_inputs": None, "n_outputs": 0, "prog": None, "pieces": None}
+    head = bristol.head_info(path) if fmt == "bristol" else None
+    if head is not None and exp is None:
+        d["n_outputs"] = head["n_outputs"]
+    if fmt == "mcircuit-bincode" and windowed:
+        window, info, n_in = int(a.window_mb) << 20, {}, 0
+        for _, piece in program_file.iter_device(path, window, scan=True, info=info):  # the scan pass the wire counts come from
+            n_in += piece["n_input_gf2"]
+        d.update(wc=info["wire_counts"], n_ops=info["n_ops"], n_inputs=n_in, pieces=lambda: program_file.iter_device(path, window))
+    elif fmt == "bristol" and windowed:
+        window = int(a.window_mb) << 20
+        d.update(wc=bristol.wire_counts(path, exp), n_ops=head["n_inputs"] + head["n_gates"] + 2 * len(exp if exp is not None else ()),
+                 n_inputs=head["n_inputs"], pieces=lambda: bristol.iter_device(path, window, exp))
+    elif device_parser:
+        prog, wc = load_program_device(path, exp_path, fmt)
+        d.update(wc=wc, n_ops=len(prog), prog=prog)
+    elif fmt != "rvops":
+        prog, wc = load_program(path, fmt, exp_path)
+        d.update(wc=wc, n_ops=len(prog), prog=prog)
+    else:
+        import os
+
+        size = os.path.getsize(path)
+        if size % OP_DTYPE.itemsize:
+            raise SystemExit("program file is not a whole number of 24-byte rv_op records")
+        n = size // OP_DTYPE.itemsize
+        prog = np.memmap(path, dtype=OP_DTYPE, mode="r", shape=(n,)) if n else np.zeros(0, OP_DTYPE)
+        z64 = gf2 = n_in = 0
+        for at in range(0, n, STREAM_FEED_OPS):  # the one pass the wire counts come from
+            piece = np.asarray(prog[at:at + STREAM_FEED_OPS])
+            z, g = largest_wires(piece)
+            z64, gf2, n_in = max(z64, z), max(gf2, g), n_in + int(np.count_nonzero((piece["domain"] == 0) & (piece["opcode"] == 0)))
+        d.update(wc=(z64, gf2), n_ops=n, n_inputs=n_in)
+        if a.compact_windows:
+            d["pieces"] = lambda: ((np.asarray(prog[at:at + STREAM_FEED_OPS]), None) for at in range(0, max(n, 1), STREAM_FEED_OPS))
+        else:
+            d["prog"] = np.asarray(prog)
+    d["wc_out"] = d["wc"]
+    if a.compact_wires:
+        d["prog"], d["wc_out"] = compact_program(d["prog"], d["wc"])
+    elif a.compact_windows:
+        d["wc_out"], d["pieces"] = compact_windows(d["wc"], d["pieces"])
+    if a.compact_wires or a.compact_windows:
+        d["n_outputs"] = 0  # (the outputs of a renumbered list are no longer its last wires)
+    return d
+
+
+def run_convert(a, ap, fmt, device_parser: bool) -> int:
+    """--operation convert (see the module docstring)"""
+    from . import _lib, bristol, program_file
+
+    out_fmt = a.output_format
+    if out_fmt == "bristol" and a.expected_outputs_path:
+        raise SystemExit("convert: --output-format bristol cannot hold the assertions of --expected-outputs-path (AssertZero is not Bristol)")
+    if a.compact_windows and not (fmt == "rvops" or (device_parser and a.window_mb is not None)):
+        ap.error("--compact-windows needs a source that is read in windows: an rvops file, or --parser device and --window-mb with an "
+                 "mcircuit-bincode or a Bristol file")
+    src = convert_source(a, fmt, device_parser)
+    wires = int(src["wc_out"][1]) or None
+    try:
+        with open(a.output_path, "wb") as f:
+            if src["pieces"] is not None:
+                if out_fmt == "rvops":
+                    n_bytes = 0
+                    for ops, _ in src["pieces"]():
+                        rec = ops if isinstance(ops, np.ndarray) else host_program(ops)
+                        f.write(np.ascontiguousarray(rec).view(np.uint8).data)
+                        n_bytes += rec.nbytes
+                elif out_fmt == "mcircuit-bincode":
+                    n_bytes = program_file.write_device(src["pieces"](), f, src["n_ops"])
+                else:
+                    n_bytes = bristol.write_device(src["pieces"](), f, src["n_ops"], src["n_inputs"], wires or 0, src["n_outputs"])
+            else:
+                prog = src["prog"]
+                on_host = isinstance(prog, np.ndarray)
+                if out_fmt == "rvops":
+                    data = np.ascontiguousarray(prog if on_host else host_program(prog)).view(np.uint8).data
+                elif out_fmt == "mcircuit-bincode":
+                    data = program_file.dumps(prog) if on_host else program_file.dumps_device(prog).cpu().numpy().data
+                elif on_host:
+                    data = bristol.dumps_host(prog, src["n_outputs"], wires)
+                else:
+                    data = bristol.dumps_device(prog, src["n_outputs"], wires).cpu().numpy().data
+                f.write(data)
+                n_bytes = len(data) if isinstance(data, bytes) else data.nbytes
+    except _lib.ReverieError as e:
+        if out_fmt != "bristol" or e.code not in (5, 8):
+            raise
+        where = _unwritable_op(src["prog"]) if isinstance(src["prog"], np.ndarray) else None
+        detail = "op %d" % where if where is not None else _lib.lib().rv_last_error().decode()
+        raise SystemExit("convert: the program cannot be written as Bristol text (%s): Bristol holds GF(2) programs whose Input ops lead, "
+                         "with Add, Mul, AddConst 0/1 and Const 0/1 only" % detail)
+    print("convert: %d ops, wire counts (z64, gf2) %s -> %s, %d bytes" % (src["n_ops"], tuple(int(x) for x in src["wc"]),
+                                                                        tuple(int(x) for x in src["wc_out"]), n_bytes), file=sys.stderr)
+    return 0
+
+
 def run_streamed(a, ap, device_parser: bool) -> int:
     """--stream: prove / verify / oneshot-zk through StreamingProver / StreamingVerifier, the program fed in `stream_pieces`' pieces
     and never compiled whole.  The banners, the result lines and the exit status are the resident path's."""
@@ -289,7 +420,7 @@ def use_gpu_evaluator(prog, evaluator: str) -> bool:
 
 def build_parser():
     ap = argparse.ArgumentParser(prog="speed-reverie", description="Gotta go fast (MI355X)")
-    ap.add_argument("--operation", required=True, choices=["prove", "verify", "oneshot", "oneshot-zk", "version_info"])
+    ap.add_argument("--operation", required=True, choices=["prove", "verify", "oneshot", "oneshot-zk", "version_info", "convert"])
     ap.add_argument("--witness-path")
     ap.add_argument("--program-path")
     ap.add_argument("--proof-path")
@@ -338,6 +469,11 @@ def build_parser():
                          "an mcircuit-bincode file, or a Bristol file with --window-mb): renumber the wires by liveness window by window "
                          "(rv_compactor_*: the source is read once more for a scan pass, twice with B2A ops), so that neither the op list nor "
                          "a wire per gate is ever in memory; the result, the proof bytes and the stderr line are --compact-wires'")
+    ap.add_argument("--output-path", help="convert: the file to write")
+    ap.add_argument("--output-format", choices=["rvops", "mcircuit-bincode", "bristol"],
+                    help="convert: the format of --output-path.  The source is read as --stream reads it (--program-format, --parser, "
+                         "--window-mb, --expected-outputs-path; --compact-wires renumbers the whole list first, --compact-windows window "
+                         "by window); bristol takes GF(2) programs of Bristol shape only, without --expected-outputs-path")
     ap.add_argument("--reference-compat", action="store_true",
                     help="verify / oneshot-zk: RV_VERIFY_REFERENCE_COMPAT -- answer exactly like the reference's verifier, which "
                          "accepts proofs whose opened repetitions fail an AssertZero or name another omitted player than the "
@@ -349,10 +485,13 @@ def main(argv=None) -> int:
     ap = build_parser()
     a = ap.parse_args(argv)
     need = {"prove": ("program_path", "witness_path", "proof_path"), "verify": ("program_path", "proof_path"),
-            "oneshot": ("program_path", "witness_path"), "oneshot-zk": ("program_path", "witness_path"), "version_info": ()}
+            "oneshot": ("program_path", "witness_path"), "oneshot-zk": ("program_path", "witness_path"), "version_info": (),
+            "convert": ("program_path", "output_path", "output_format")}
     for k in need[a.operation]:
         if getattr(a, k) is None:
             ap.error(f"--{k.replace('_', '-')} is required for --operation {a.operation}")
+    if a.operation != "convert" and (a.output_path is not None or a.output_format is not None):
+        ap.error("--output-path and --output-format belong to --operation convert")
     if a.operation == "version_info":
         from . import _lib
 
@@ -368,6 +507,10 @@ def main(argv=None) -> int:
     if fmt == "auto":
         fmt = "rvops" if a.program_path.endswith(".rvops") else "bristol"
     device_parser = a.parser == "device" and fmt in ("bristol", "mcircuit-bincode")
+    if a.operation == "convert":
+        if a.compact_windows and a.compact_wires:
+            ap.error("--compact-windows and --compact-wires exclude each other")
+        return run_convert(a, ap, fmt, device_parser)
     if a.compact_windows:
         streamed = a.stream or (a.operation == "oneshot" and a.evaluator == "stream")
         windows = fmt == "rvops" or (device_parser and (a.window_mb is not None or (fmt == "mcircuit-bincode" and a.stream)))

@@ -4,7 +4,9 @@ The reference README advertises Bristol-format circuits but leaves parsing to th
 un-vendored `mcircuit` crate (/root/reference/README.md:14-16, src/lib.rs:6-7).  The
 parser itself is C++ behind the C-ABI (`rv_bristol_parse`, reverie_amd/csrc/bristol.cpp) and, for a program that is to be made in
 GPU memory, kernels behind it (`rv_bristol_parse_device`, reverie_amd/csrc/bristol_dev.hip: DESIGN §18); this is the ctypes wrapper.
-`dumps` writes a GF(2) program of Bristol shape back as Fashion text.
+`dumps` writes a GF(2) program of Bristol shape back as Fashion text, in numpy; `dumps_host` (rv_bristol_write), `dumps_device`
+(rv_bristol_write_device) and `DeviceWriter` / `write_device` (rv_bristol_writer_*: the list handed over in pieces) write the same
+bytes through the library, on the host and on the GPU (reverie_amd/csrc/bristol_write.h, bristol_write.hip: DESIGN §20).
 """
 from __future__ import annotations
 
@@ -15,6 +17,7 @@ import numpy as np
 
 from . import _lib
 from .ops import OP_DTYPE
+from .program_file import _WindowWriter
 
 
 def parse(text: str | bytes, expected_outputs: Optional[Sequence[int]] = None, fmt: int = 0, compact: bool = False) -> Tuple[np.ndarray, dict]:
@@ -339,14 +342,13 @@ def iter_device(source, window_bytes: int = 64 << 20, expected_outputs: Optional
             info.update(done)
 
 
-def wire_counts(source, expected_outputs: Optional[Sequence[int]] = None, fmt: int = 0) -> Tuple[int, int]:
-    """(0, gf2_wires) of a Bristol text -- what a stream over `iter_device` begins with -- from the head of `source` (a path, a buffer
-    or a uint8 GPU tensor) alone: rv_bristol_header_prefix on the first bytes that hold four non-blank lines.  No pass over the text:
-    the header names the wires, and the assertion temporaries are one per expected output.  Errors are the header's."""
+def head_info(source, fmt: int = 0) -> dict:
+    """the header's counts (n_gates, n_wires, n_inputs, n_outputs; the rest 0) of a Bristol text, from the head of `source` (a path, a
+    buffer or a uint8 GPU tensor) alone: rv_bristol_header_prefix on the first bytes that hold four non-blank lines.  Errors are the
+    header's."""
     from .program_file import _window_source
 
     data, n = _window_source(source)
-    exp, _, n_exp = _expected(expected_outputs)
     take = min(n, 4096)
     while True:
         head = data[:take]
@@ -365,6 +367,81 @@ def wire_counts(source, expected_outputs: Optional[Sequence[int]] = None, fmt: i
     bi, off = _lib.BristolInfo(), C.c_size_t()
     _lib.check(_lib.lib().rv_bristol_header_prefix(C.c_void_p(head.ctypes.data if head.size else _EMPTY.ctypes.data), C.c_size_t(head.size), C.c_uint64(n),
                                                    C.c_int(fmt), C.byref(bi), C.byref(off)))
-    if exp is not None and n_exp != int(bi.n_outputs):
+    return {k: int(getattr(bi, k)) for k, _ in bi._fields_}
+
+
+def wire_counts(source, expected_outputs: Optional[Sequence[int]] = None, fmt: int = 0) -> Tuple[int, int]:
+    """(0, gf2_wires) of a Bristol text -- what a stream over `iter_device` begins with -- from the head of `source` (a path, a buffer
+    or a uint8 GPU tensor) alone: rv_bristol_header_prefix on the first bytes that hold four non-blank lines.  No pass over the text:
+    the header names the wires, and the assertion temporaries are one per expected output.  Errors are the header's."""
+    exp, _, n_exp = _expected(expected_outputs)
+    bi = head_info(source, fmt)
+    if exp is not None and n_exp != bi["n_outputs"]:
         _lib.check(_RV_E_ARG)
-    return 0, int(bi.n_wires) + (n_exp if exp is not None else 0)
+    return 0, bi["n_wires"] + (n_exp if exp is not None else 0)
+
+
+# ---- Bristol text written on the GPU, whole and in windows (rv_bristol_write*, DESIGN §20) ----
+def dumps_host(prog, n_outputs: int = 0, n_wires: Optional[int] = None) -> bytes:
+    """`dumps` by the library's host writer (rv_bristol_write, no GPU): the same bytes, and a ReverieError where `dumps` raises
+    ValueError.  n_wires: the header's wire count (None: derived, as `dumps` derives it)."""
+    from .ops import program
+
+    p = program(prog) if len(prog) else np.zeros(0, OP_DTYPE)
+    out, n = C.c_void_p(), C.c_size_t()
+    _lib.check(_lib.lib().rv_bristol_write(C.c_void_p(p.ctypes.data) if len(p) else None, C.c_size_t(len(p)), C.c_uint64(int(n_wires or 0)),
+                                           C.c_uint64(int(n_outputs)), C.byref(out), C.byref(n)))
+    data = C.string_at(out, n.value)
+    _lib.lib().rv_free(out)
+    return data
+
+
+def dumps_device(ops, n_outputs: int = 0, n_wires: Optional[int] = None, device=None):
+    """an op tensor in GPU memory (packed rv_op records) -> the bytes `dumps` writes for its records, as a torch uint8 tensor in GPU
+    memory (rv_bristol_write_device: a sizing call, then the write).  Errors are rv_bristol_write's."""
+    import torch
+
+    from .proof import Context, _device_ops
+
+    ctx = device if isinstance(device, Context) else Context.default() if device is None else Context(int(device))
+    d_ops, n_ops, _ = _device_ops(ops, ctx, "dumps_device")
+    L = _lib.lib()
+    p_ops = C.c_void_p(d_ops) if n_ops else None
+    args = (ctx.handle, p_ops, C.c_size_t(n_ops), C.c_uint64(int(n_wires or 0)), C.c_uint64(int(n_outputs)))
+    n = C.c_size_t()
+    rc = L.rv_bristol_write_device(*args, None, C.c_size_t(0), C.byref(n))
+    if rc != _RV_E_ARG or not n.value:  # (a sizing call answers RV_E_ARG with the size; anything else is the records' own code)
+        _lib.check(rc or _RV_E_ARG)
+    out = torch.empty(int(n.value), dtype=torch.uint8, device=torch.device("cuda", ctx.device))
+    _lib.check(L.rv_bristol_write_device(*args, C.c_void_p(out.data_ptr()), C.c_size_t(out.numel()), C.byref(n)))
+    return out[:int(n.value)]
+
+
+class DeviceWriter(_WindowWriter):
+    """`dumps_device` for an op list that is handed over in pieces (rv_bristol_writer_*): the bytes of all feeds, in order, are
+    `dumps`' bytes for the whole list, however it is cut; the first feed's begin with the header lines.  The header goes out
+    first, so the writer is told what `dumps` derives: n_inputs (the leading Input records) and n_wires.
+
+        with DeviceWriter(n_ops, n_inputs, n_wires, n_outputs) as w:
+            for ops in pieces: text, piece = w.feed(ops)
+            w.finish()"""
+
+    _FEED, _FINISH, _DESTROY = "rv_bristol_writer_feed", "rv_bristol_writer_finish", "rv_bristol_writer_destroy"
+    _HEAD, _PER_OP = 96, 41
+
+    def __init__(self, n_ops: int, n_inputs: int, n_wires: int, n_outputs: int = 0, device=None):
+        from .program_file import _context
+
+        self.ctx = _context(device)
+        self.handle = C.c_void_p()
+        _lib.check(_lib.lib().rv_bristol_writer_begin(self.ctx.handle, C.c_uint64(int(n_ops)), C.c_uint64(int(n_inputs)), C.c_uint64(int(n_wires)),
+                                                      C.c_uint64(int(n_outputs)), C.byref(self.handle)))
+
+
+def write_device(pieces, dst, n_ops: int, n_inputs: int, n_wires: int, n_outputs: int = 0, device=None) -> int:
+    """Writes the Bristol text of an op list that comes in pieces -- an iterator of op pieces; tuples of (ops, anything), as
+    `iter_device` and `compact.compact_pieces` yield them, are taken as they are -- to dst, a path or a binary file object: one feed,
+    one copy to the host and one write per piece.  -> the bytes written."""
+    from .program_file import _write_pieces
+
+    return _write_pieces(DeviceWriter(n_ops, n_inputs, n_wires, n_outputs, device), pieces, dst)

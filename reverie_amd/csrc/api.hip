@@ -23,6 +23,7 @@
 #include "b3.h"
 #include "bristol_dev.h"
 #include "bincode_dev.h"
+#include "bristol_write.h"
 #include "compile.h"
 #include "compact_dev.h"
 #include "compact_win.h"
@@ -1648,3 +1649,4 @@ extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
 #include "compact.inc"
 #include "bristol.inc"
 #include "bincode.inc"
+#include "bristol_write.inc"

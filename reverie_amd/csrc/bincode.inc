@@ -86,7 +86,8 @@ extern "C" int rv_program_to_bincode_device(rv_ctx* ctx, const rv_op* d_ops, siz
         // (the shortest record takes BC_MIN_RECORD bytes: such a list cannot make a file below 2^32 bytes, whatever it holds)
         if (n_ops > ((1ull << 32) - 1 - BC_HEADER_BYTES) / BC_MIN_RECORD) return RV_E_UNSUPPORTED;
         BincodeWrite w;
-        const int rc = bincode_write_device(ctx->stream, ctx_dev_allocator(ctx), d_ops, n_ops, d_out, d_out ? cap : 0, &w);
+        const uint64_t count = n_ops;
+        const int rc = bincode_write_device(ctx->stream, ctx_dev_allocator(ctx), d_ops, n_ops, d_out, d_out ? cap : 0, &count, &w);
         if (rc == RV_E_DEVICE) g_last_error = "device bincode writer: HIP error";
         if (rc == RV_E_NOMEM) g_last_error = "device bincode writer: out of device memory";
         if (rc) return rc;

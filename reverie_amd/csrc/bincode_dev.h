@@ -401,8 +401,10 @@ struct BincodeWrite {
     bool written = false;
 };
 // d_ops[0, n_ops) (n_ops < 2^28) as a file at d_out[0, cap) (null: nowhere); written only when there is no bad record and
-// bytes <= min(cap, 2^32 - 1) -- decided on the device, one synchronisation.
-int bincode_write_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, uint8_t* d_out, uint64_t cap, BincodeWrite* res);
+// bytes <= min(cap, 2^32 - 1) -- decided on the device, one synchronisation.  header_count: the count the 8 header bytes say, in
+// front of the records (a whole file: n_ops; the first feed of a file written in windows: the whole list's); null: the records alone.
+int bincode_write_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, uint8_t* d_out, uint64_t cap, const uint64_t* header_count,
+                         BincodeWrite* res);
 
 }  // namespace rv
 #endif

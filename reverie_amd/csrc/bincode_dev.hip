@@ -289,22 +289,27 @@ __global__ __launch_bounds__(TB) void k_bw_lens(const uint64_t* ops, uint64_t n,
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd((unsigned long long*)&state[W_TOTAL], (unsigned long long)sum);
 }
-__global__ __launch_bounds__(TB) void k_bw_emit(const uint64_t* ops, uint64_t n, const uint32_t* offs, const uint64_t* state, uint64_t cap, uint8_t* out) {
+// HEADER: the image of block 0 begins with `count` as the file's header (a whole file: n; the first feed of a file written in windows:
+// the whole list's count); else the records alone (a later feed)
+template <bool HEADER>
+__global__ __launch_bounds__(TB) void k_bw_emit(const uint64_t* ops, uint64_t n, const uint32_t* offs, const uint64_t* state, uint64_t cap, uint64_t count,
+                                                uint8_t* out) {
+    constexpr uint32_t head = HEADER ? BC_HEADER_BYTES : 0;
     __shared__ __attribute__((aligned(16))) uint8_t raw[16 + TB * BC_MAX_RECORD + 16];
     __shared__ uint64_t s_end;
-    if (state[W_BAD] || BC_HEADER_BYTES + state[W_TOTAL] > cap) return;
+    if (state[W_BAD] || head + state[W_TOTAL] > cap) return;
     const uint64_t first = (uint64_t)blockIdx.x * TB, i = first + threadIdx.x;
     const uint32_t mine = (uint32_t)std::min<uint64_t>(TB, n > first ? n - first : 0);
     // the block's bytes: d_out[g0, g1); block 0's begin with the header
-    const uint64_t g0 = blockIdx.x ? BC_HEADER_BYTES + (uint64_t)offs[first] : 0;
+    const uint64_t g0 = blockIdx.x ? head + (uint64_t)offs[first] : 0;
     const uint32_t sh = (uint32_t)((uintptr_t)(out + g0) & 15u);
-    if (threadIdx.x == 0 && mine == 0) s_end = BC_HEADER_BYTES;  // (an empty program: the header alone)
+    if (threadIdx.x == 0 && mine == 0) s_end = head;  // (no record: the header alone)
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (uint32_t k = 0; k < BC_HEADER_BYTES; k++) raw[sh + k] = (uint8_t)(n >> (8 * k));
+        for (uint32_t k = 0; k < head; k++) raw[sh + k] = (uint8_t)(count >> (8 * k));
     if (threadIdx.x < mine) {
         uint64_t w[3];
         load_op(ops, i, w);
-        const uint64_t at = BC_HEADER_BYTES + (uint64_t)offs[i];
+        const uint64_t at = head + (uint64_t)offs[i];
         uint8_t* dst = raw + sh + (uint32_t)(at - g0);
         bc_encode(w, [&](uint32_t k, uint8_t v) { dst[k] = v; });
         if (threadIdx.x == mine - 1) s_end = at + bc_op_len(w);
@@ -385,7 +390,8 @@ int bincode_window_device(hipStream_t st, const DevAlloc& A, const uint8_t* d_da
     return RV_OK;
 }
 
-int bincode_write_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, uint8_t* d_out, uint64_t cap, BincodeWrite* res) {
+int bincode_write_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, uint8_t* d_out, uint64_t cap, const uint64_t* header_count,
+                         BincodeWrite* res) {
     Scratch S(A, st);
     uint64_t* state = S.get<uint64_t>(W_WORDS);
     uint32_t* lens = S.get<uint32_t>(n_ops);
@@ -393,6 +399,7 @@ int bincode_write_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, 
     const uint64_t* ops = reinterpret_cast<const uint64_t*>(d_ops);
     const uint32_t grid = blocks(n_ops, TB);
     const uint64_t room = std::min<uint64_t>(cap, 0xFFFFFFFFull);
+    const uint32_t head = header_count ? BC_HEADER_BYTES : 0;
 
     CDCHK(hipMemsetAsync(state, 0, W_WORDS * 8, st));
     if (n_ops) {
@@ -400,7 +407,8 @@ int bincode_write_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, 
         CDCHK(hipGetLastError());
         CDCHK((scan_excl<uint32_t, SumU32>(S, st, lens, lens, n_ops, nullptr)));  // (wraps only where nothing is written)
     }
-    if (d_out) k_bw_emit<<<grid, TB, 0, st>>>(ops, n_ops, lens, state, room, d_out);
+    if (d_out && header_count) k_bw_emit<true><<<grid, TB, 0, st>>>(ops, n_ops, lens, state, room, *header_count, d_out);
+    else if (d_out) k_bw_emit<false><<<grid, TB, 0, st>>>(ops, n_ops, lens, state, room, 0, d_out);
     CDCHK(hipGetLastError());
     std::vector<uint64_t> h(W_WORDS);
     CDCHK(fetch(st, h, state));
@@ -410,7 +418,7 @@ int bincode_write_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, 
         res->code = RV_E_BAD_OP;
         return RV_OK;
     }
-    res->bytes = BC_HEADER_BYTES + h[W_TOTAL];
+    res->bytes = head + h[W_TOTAL];
     res->written = d_out && res->bytes <= room;
     return RV_OK;
 }

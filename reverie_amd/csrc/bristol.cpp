@@ -232,3 +232,46 @@ static int parse_impl(const char* text, size_t len, int format, const uint8_t* e
     if (info) *info = bi;
     return RV_OK;
 }
+
+// ---- rv_op records -> Bristol Fashion text (host only): the definition rv_bristol_write_device and rv_bristol_writer_* follow ----
+#include "bristol_write.h"
+
+extern "C" int rv_bristol_write(const rv_op* ops, size_t n_ops, uint64_t n_wires, uint64_t n_outputs, char** text, size_t* len) {
+    if (!text || !len || (!ops && n_ops)) return RV_E_ARG;
+    *text = nullptr;
+    *len = 0;
+    auto words = [&](size_t i, uint64_t w[3]) { memcpy(w, &ops[i], sizeof(rv_op)); };
+    uint64_t w[3];
+    size_t n_in = 0;  // the leading run of GF(2) Input records
+    for (; n_in < n_ops; n_in++) {
+        words(n_in, w);
+        if (w[0] & 0xFFFFu) break;
+    }
+    uint64_t total = 0, wires = n_in;
+    uint32_t l;
+    for (size_t i = 0; i < n_ops; i++) {
+        uint64_t need;
+        words(i, w);
+        if (const int code = rv::bw_judge(w, i, i < n_in, n_wires, l, need)) return code;
+        total += l, wires = std::max(wires, need);
+    }
+    if (n_wires) wires = n_wires;
+    if (const int code = rv::bw_header_code(wires, n_in, n_outputs)) return code;
+    const uint64_t gates = n_ops - n_in;
+    const uint32_t head = rv::bw_header_len(gates, wires, n_in, n_outputs);
+    if (total > (uint64_t)(size_t)-1 - head) return RV_E_NOMEM;
+    uint8_t* out = (uint8_t*)malloc((size_t)(head + total));
+    if (!out) return RV_E_NOMEM;
+    rv::bw_header(gates, wires, n_in, n_outputs, [&](uint32_t k, uint8_t v) { out[k] = v; });
+    uint8_t* p = out + head;
+    for (size_t i = n_in; i < n_ops; i++) {
+        uint64_t need;
+        words(i, w);
+        rv::bw_judge(w, i, false, n_wires, l, need);
+        rv::bw_emit(w, [&](uint32_t k, uint8_t v) { p[k] = v; });
+        p += l;
+    }
+    *text = (char*)out;
+    *len = (size_t)(head + total);
+    return RV_OK;
+}

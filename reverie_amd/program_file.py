@@ -4,7 +4,8 @@
 wrapper.  The enum's variant order is recalled, not verifiable here — see the header.
 `loads_device` / `dumps_device` are the same two on the GPU (`rv_program_from_bincode_device` / `rv_program_to_bincode_device`,
 reverie_amd/csrc/bincode_dev.hip: DESIGN §19): the op list is made in, and written from, device memory.  `DeviceReader` / `iter_device` /
-`scan_device` read a file in windows (`rv_program_reader_*`): for files no memory holds whole."""
+`scan_device` read a file in windows (`rv_program_reader_*`): for files no memory holds whole.  `DeviceWriter` /
+`write_device` write one from an op list that is handed over in pieces (`rv_program_writer_*`)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -242,3 +243,110 @@ def scan_device(source, window_bytes: int = 64 << 20, device=None) -> dict:
     for _ in iter_device(source, window_bytes, device, scan=True, info=info):
         pass
     return info
+
+
+# ---- a file written in windows (rv_program_writer_*) ----
+class _WindowWriter:
+    """what `program_file.DeviceWriter` and `bristol.DeviceWriter` share: feeds of op pieces, each answered with its bytes"""
+
+    _FEED, _FINISH, _DESTROY = "", "", ""
+    _HEAD, _PER_OP = 0, 0  # head + per_op * n bytes always hold a feed of n records
+
+    def feed(self, ops, out=None):
+        """-> (bytes, piece).  ops: an OP_DTYPE array (uploaded by the library) or a torch tensor of packed rv_op records in GPU memory,
+        as `DeviceCompactor.feed` takes them.  bytes: a torch uint8 tensor in GPU memory, the feed's part of the output (the first
+        feed's begins with the header); piece: first_op, n_ops, file_off, bytes.  out: a uint8 GPU tensor to write into instead of a
+        new one; where it is too small the same records are fed again into a new one of the size the library names."""
+        import torch
+
+        from .proof import _device_ops, _is_device_ops, _ptr
+
+        if _is_device_ops(ops):
+            d_ops, n, _ = _device_ops(ops, self.ctx, type(self).__name__)
+            p, dev = C.c_void_p(d_ops) if n else None, 1
+        else:
+            a = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+            p, n, dev = _ptr(a), len(a), 0
+        if out is None:
+            out = torch.empty(self._HEAD + self._PER_OP * n, dtype=torch.uint8, device=torch.device("cuda", self.ctx.device))
+        elif not _is_device_ops(out) or out.device.type != "cuda" or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous uint8 tensor in GPU memory")
+        piece = _lib.WriterPiece()
+        call = getattr(_lib.lib(), self._FEED)
+        rc = call(self.handle, p, C.c_size_t(n), C.c_int(dev), C.c_void_p(out.data_ptr()), C.c_size_t(out.numel()), C.byref(piece))
+        if rc == _RV_E_ARG and int(piece.bytes) > out.numel():  # the capacity answer: the writer has not moved
+            out = torch.empty(int(piece.bytes), dtype=torch.uint8, device=out.device)
+            rc = call(self.handle, p, C.c_size_t(n), C.c_int(dev), C.c_void_p(out.data_ptr()), C.c_size_t(out.numel()), C.byref(piece))
+        _lib.check(rc)
+        d = {k: int(getattr(piece, k)) for k, _ in piece._fields_}
+        return out.reshape(-1)[:d["bytes"]], d
+
+    def finish(self) -> None:
+        """an error unless the header and exactly n_ops records are out"""
+        _lib.check(getattr(_lib.lib(), self._FINISH)(self.handle))
+
+    def close(self):
+        if self.handle:
+            if self.ctx.handle:
+                getattr(_lib.lib(), self._DESTROY)(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceWriter(_WindowWriter):
+    """`dumps_device` for an op list that is handed over in pieces (rv_program_writer_*): the bytes of all feeds, in order, are `dumps`'
+    bytes for the whole list, however it is cut; the first feed's begin with the 8-byte count.  n_ops may be 2^32 and more.
+
+        with DeviceWriter(n_ops) as w:
+            for ops in pieces: data, piece = w.feed(ops)
+            w.finish()"""
+
+    _FEED, _FINISH, _DESTROY = "rv_program_writer_feed", "rv_program_writer_finish", "rv_program_writer_destroy"
+    _HEAD, _PER_OP = 8, 32
+
+    def __init__(self, n_ops: int, device=None):
+        self.ctx = _context(device)
+        self.handle = C.c_void_p()
+        _lib.check(_lib.lib().rv_program_writer_begin(self.ctx.handle, C.c_uint64(int(n_ops)), C.byref(self.handle)))
+
+
+def _write_pieces(writer, pieces, dst) -> int:
+    """every piece through writer.feed, its bytes copied to the host and written to dst (a path or a binary file object) -> the count"""
+    import os
+
+    own = isinstance(dst, (str, os.PathLike))
+    f = open(dst, "wb") if own else dst
+    total, fed = 0, False
+    try:
+        with writer as w:
+            for piece in pieces:
+                data, _ = w.feed(piece[0] if isinstance(piece, tuple) else piece)
+                f.write(data.cpu().numpy().data)
+                total, fed = total + data.numel(), True
+            if not fed:  # (no piece at all: the header of an empty list goes out with a feed of 0 records)
+                data, _ = w.feed(np.zeros(0, OP_DTYPE))
+                f.write(data.cpu().numpy().data)
+                total += data.numel()
+            w.finish()
+    finally:
+        if own:
+            f.close()
+    return total
+
+
+def write_device(pieces, dst, n_ops: int, device=None) -> int:
+    """Writes the program file of an op list that comes in pieces -- an iterator of op pieces; tuples of (ops, anything), as
+    `iter_device` and `compact.compact_pieces` yield them, are taken as they are -- to dst, a path or a binary file object: one feed,
+    one copy to the host and one write per piece.  n_ops: the whole list's count (the header says it first).  -> the bytes written."""
+    return _write_pieces(DeviceWriter(n_ops, device), pieces, dst)
