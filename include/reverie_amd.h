@@ -1150,6 +1150,50 @@ int rv_program_writer_feed(rv_program_writer *w, const rv_op *ops, size_t n, int
 int rv_program_writer_finish(rv_program_writer *w);
 void rv_program_writer_destroy(rv_program_writer *w);
 
+/* ---- witness text read and written on the GPU, whole, in windows and in batches ------------------
+ * The witness file of the command line is text that is scanned byte by byte: '0' and '1' are bits, every other byte is skipped.
+ * rv_witness_parse (host only, no GPU) is the definition: byte b is a bit iff (b ^ 0x30) <= 1, its value is b & 1, and every byte
+ * string is a witness -- the text never produces an error.  bits receives one byte per bit, *n_bits the count.  bits == NULL: the
+ * count alone.  cap < the count: RV_E_ARG with *n_bits = the count and nothing written.  RV_E_ARG also for a NULL n_bits, or a NULL
+ * text with len != 0. */
+int rv_witness_parse(const char *text, size_t len, uint8_t *bits, size_t cap, size_t *n_bits);
+/* The writer's definition (host only): bit i becomes '0' + bits[i]; a line feed follows bit i when (i + 1) % line_bits == 0 or
+ * i == n - 1 (line_bits == 0: one line).  *len = n + ceil(n / line_bits) (n + 1 with line_bits == 0; 0 for n == 0, the empty text).
+ * text == NULL: the length alone (the bits are not looked at).  cap < the length: RV_E_ARG with *len = the length and nothing
+ * written.  A byte of bits above 1: RV_E_ARG, the contents of text unspecified.  rv_witness_parse on the text gives the bits back. */
+int rv_witness_write(const uint8_t *bits, size_t n, uint64_t line_bits, char *text, size_t cap, size_t *len);
+/* rv_witness_parse on the GPU: d_bits[0, *n_bits), the count and the return code are its answers for every byte string and every
+ * argument -- count-only with d_bits == NULL, RV_E_ARG with *n_bits = the count when cap is short; then not one byte of d_bits is
+ * written (decided on the device: the call runs on the context's stream and synchronises it once, at the end).
+ *   text: host memory (text_on_device == 0; uploaded into context-arena memory, and counted as host-to-device witness bytes by
+ * rv_hook_witness_traffic) or memory of the context's device, read in place, no alignment asked.  len >= 2^32: RV_E_UNSUPPORTED.
+ * d_bits / cap: memory of that device, no alignment asked; it may overlap neither a device text (RV_E_ARG) nor itself.
+ *   marks (host, ascending, each <= len, else RV_E_ARG; may be NULL with n_marks == 0): bits_before[m] (host, n_marks) = the number
+ * of bits in text[0, marks[m]) -- where each file's bits end when several texts are parsed as one.
+ *   Work memory (4 bytes per 4096 bytes of text, the scan's sums, 8 bytes per mark, the text where it is uploaded) comes from the
+ * context arena and goes back before the call returns. */
+int rv_witness_parse_device(rv_ctx *ctx, const char *text, size_t len, int text_on_device, uint8_t *d_bits, size_t cap, size_t *n_bits,
+                            const uint64_t *marks, size_t n_marks, uint64_t *bits_before);
+/* out[0] = bytes of text per workgroup of the parse kernels, out[1] = output bytes per workgroup of the writer (the sizes the
+ * tests go around) */
+int rv_hook_witness_text_tiles(uint32_t out[2]);
+/* A text read in windows: consecutive byte ranges ("feeds") of any length, 0 and 1 included, from host memory or from ranges of
+ * device memory; host feeds and device feeds mix.  Each feed delivers exactly the bits of its own bytes, so over all feeds the bits
+ * are rv_witness_parse's for the whole text, for every way of cutting it.  A text has no records: nothing is carried between feeds,
+ * and the reader's state is the two totals finish reports (they may pass 2^32; one feed stays below 2^32 bytes).  A feed is
+ * rv_witness_parse_device on its bytes, with its arguments, answers and memory; any answer but RV_OK -- a short cap among them:
+ * RV_E_ARG with *n_bits = the count -- leaves the reader unchanged, and the same bytes are fed again.  finish may be called at any
+ * time; either pointer may be NULL. */
+typedef struct rv_witness_reader rv_witness_reader;
+int rv_witness_reader_begin(rv_ctx *ctx, rv_witness_reader **out);
+int rv_witness_reader_feed(rv_witness_reader *r, const char *text, size_t len, int text_on_device, uint8_t *d_bits, size_t cap, size_t *n_bits);
+int rv_witness_reader_finish(rv_witness_reader *r, uint64_t *bytes_fed, uint64_t *bits_total);
+void rv_witness_reader_destroy(rv_witness_reader *r);
+/* rv_witness_write on the GPU: d_text receives its bytes and the return code is its code, for every list in device memory (d_bits,
+ * d_text / cap: memory of the context's device, no alignment asked, not overlapping).  d_text == NULL: the length alone.  n or the
+ * length >= 2^32: RV_E_UNSUPPORTED.  Runs on the context's stream and synchronises it once. */
+int rv_witness_write_device(rv_ctx *ctx, const uint8_t *d_bits, size_t n, uint64_t line_bits, char *d_text, size_t cap, size_t *len);
+
 /* ---- parity-test hooks: each mirrors one reference function so tests can compare the
  * HIP path with the oracle piecewise ---- */
 /* PRG::new + gen (crypto/prg.rs:16-37) on the GPU: n_keys keys, blocks [first, first+n_blocks) each */

@@ -28,6 +28,11 @@ same `Ok(())` / `Err("Unverifiable Proof")` result lines.  Differences, stated p
   (assertions are not Bristol); its header states the wire count in force (the compacted count after a compaction, with 0 outputs:
   renumbered wires are no longer "the last wires").  One line goes to stderr:
   `convert: N ops, wire counts (z64, gf2) A -> B, M bytes`.
+* `--witness-parser device` reads the witness file on the GPU (rv_witness_parse_device on the file's memory map: the same bits, made
+  in device memory and handed to the prover or evaluator there); with `--witness-window-mb N` a streamed operation (`--stream`, or
+  oneshot `--evaluator stream`) reads it in windows of N MiB as the pieces ask for bits (rv_witness_reader_*), so that neither the
+  text nor the witness is ever whole in memory.  The default is `host`: for a witness of a few KiB the host parser is faster
+  (DESIGN §21).  `--expected-outputs-path` is always parsed on the host.
 * proofs are the same bincode bytes.
 * verification is strict by default (`--reference-compat` restores the reference verifier's two unchecked
   conditions), and a rejected proof exits with status 1 (the reference prints the same
@@ -83,6 +88,24 @@ def load_program_device(path: str, expected_path=None, fmt: str = "bristol"):
         else:
             ops, info = bristol.parse_device(text, expected_outputs=exp)
     return ops, info["wire_counts"]
+
+
+def load_witness(path: str, parser: str = "host", window_mb=None):
+    """the witness file as the prover and the evaluators take it: --witness-parser host = `parse_witness`' host array; device = the
+    file memory-mapped and parsed on the GPU (witness.parse_device: a uint8 GPU tensor of the same bits); device with
+    --witness-window-mb = a witness.DeviceWindows over the file, which a stream reads in windows as its pieces ask for bits"""
+    if parser != "device":
+        return parse_witness(open(path, "rb").read())
+    import mmap
+
+    from . import witness
+
+    if window_mb is not None:
+        return witness.DeviceWindows(path, int(window_mb) << 20)
+    with open(path, "rb") as f:
+        size = f.seek(0, 2)
+        text = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if size else b""  # (an empty file cannot be mapped)
+        return witness.parse_device(text)
 
 
 def host_program(ops):
@@ -165,6 +188,11 @@ def evaluate_gpu(prog, wc, witness, compiler="host"):
     else:
         circuit = Circuit(prog, wc, keep_wires=True, device_compile=True, device_z64=compiler in ("device-z64", "device-b2a"),
                           device_b2a=compiler == "device-b2a", device_keep_wires=True)
+    if hasattr(witness, "data_ptr"):  # (--witness-parser device: the witness is read where it lies, the status comes back)
+        st = circuit.evaluate_batch_device(witness.reshape(1, -1)).status[0].tolist()
+        if st[0]:
+            raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (st[1], st[0]))
+        return
     r = circuit.evaluate(witness, [])
     if not r.ok:
         raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (r.first_failed_op, r.n_failed))
@@ -234,9 +262,10 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
     many MiB on the GPU, and so is a Bristol file; without it, either is parsed whole.  compact (--compact-wires): the whole list is renumbered by liveness first
     (in host memory: 24 bytes per op, against a wire-store row per gate of an SSA list) and the stream begins with the new counts;
     in_windows (--compact-windows): the pieces are renumbered window by window instead, and nothing is whole in memory."""
-    from .stream import StreamingEvaluator, _piece_inputs
+    from .stream import StreamingEvaluator, _is_wit_source, _piece_inputs
 
-    wit = np.ascontiguousarray(np.asarray(witness, dtype=np.uint8))
+    source = _is_wit_source(witness)  # (--witness-window-mb: the bits are read as the pieces ask for them)
+    wit = witness if source or hasattr(witness, "data_ptr") else np.ascontiguousarray(np.asarray(witness, dtype=np.uint8))
     wc, pieces = stream_pieces(program_path, fmt, parser, window_mb, expected_path, compact, windowed=window_mb is not None, in_windows=in_windows)
     se = StreamingEvaluator(wc, 1, max_chunk_ops, device_compile=device_compile, **({"device_z64": True} if device_z64 else {}),
                             **({"device_b2a": True} if device_b2a else {}))
@@ -245,8 +274,10 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
         for piece, counts in pieces():
             if counts is not None and not len(piece):  # (a window that completed no record)
                 continue
-            se.feed(piece, wit[used:])  # (the CLI's witness is GF(2) bits: a piece consumes one per GF(2) Input op)
-            used += _piece_inputs(piece, counts)[0]
+            n_g = _piece_inputs(piece, counts)[0]
+            # (the CLI's witness is GF(2) bits: a piece consumes one per GF(2) Input op; a GPU tensor is handed over by the piece's share)
+            se.feed(piece, wit.take(n_g) if source else wit[used:used + n_g] if hasattr(wit, "data_ptr") else wit[used:])
+            used += n_g
         r = se.finish()
     finally:
         se.close()
@@ -383,7 +414,7 @@ def run_streamed(a, ap, device_parser: bool) -> int:
     kw = dict(max_chunk_ops=a.max_chunk_ops, device_compile=a.compiler != "host", device_z64=a.compiler in ("device-z64", "device-b2a"),
               device_b2a=a.compiler == "device-b2a")
     if a.operation in ("prove", "oneshot-zk"):
-        wit = parse_witness(open(a.witness_path, "rb").read())
+        wit = load_witness(a.witness_path, a.witness_parser, a.witness_window_mb)
         print("Evaluating program in ~zero knowledge~")
         proof, _ = prove_streaming_pieces(pieces, wit, (), wc, **kw)
         if a.operation == "prove":
@@ -469,6 +500,14 @@ def build_parser():
                          "an mcircuit-bincode file, or a Bristol file with --window-mb): renumber the wires by liveness window by window "
                          "(rv_compactor_*: the source is read once more for a scan pass, twice with B2A ops), so that neither the op list nor "
                          "a wire per gate is ever in memory; the result, the proof bytes and the stderr line are --compact-wires'")
+    ap.add_argument("--witness-parser", default="host", choices=["host", "device"],
+                    help="prove / oneshot / oneshot-zk: parse the witness file on the host (default; faster for a witness of a few KiB) or "
+                         "on the GPU (rv_witness_parse_device: the file is memory-mapped, the bits are made in device memory and the prover "
+                         "or the GPU evaluators take them there); the proof bytes and the outcome are the same.  --expected-outputs-path is "
+                         "parsed on the host either way")
+    ap.add_argument("--witness-window-mb", type=int, default=None,
+                    help="--witness-parser device with --stream or oneshot --evaluator stream: read the witness file in windows of this many "
+                         "MiB as the pieces ask for bits (rv_witness_reader_*), so that neither the text nor the witness is whole in memory")
     ap.add_argument("--output-path", help="convert: the file to write")
     ap.add_argument("--output-format", choices=["rvops", "mcircuit-bincode", "bristol"],
                     help="convert: the format of --output-path.  The source is read as --stream reads it (--program-format, --parser, "
@@ -499,6 +538,15 @@ def main(argv=None) -> int:
         return 0
     if a.window_mb is not None and not 1 <= a.window_mb < 4096:
         ap.error("--window-mb must be at least 1 (and below 4096: a window stays below 2^32 bytes)")
+    if a.witness_parser == "device" and a.operation not in ("prove", "oneshot", "oneshot-zk"):
+        ap.error("--witness-parser device belongs to the operations that read a witness: prove, oneshot, oneshot-zk")
+    if a.witness_window_mb is not None:
+        if a.witness_parser != "device":
+            ap.error("--witness-window-mb needs --witness-parser device")
+        if not 1 <= a.witness_window_mb < 4096:
+            ap.error("--witness-window-mb must be at least 1 (and below 4096: a window stays below 2^32 bytes)")
+        if not (a.stream or (a.operation == "oneshot" and a.evaluator == "stream")):
+            ap.error("--witness-window-mb needs a streamed operation: --stream, or oneshot --evaluator stream")
     if a.stream and a.operation == "oneshot":
         ap.error("--stream is for prove / verify / oneshot-zk; oneshot streams with --evaluator stream")
     if a.compact_wires and a.operation == "oneshot" and a.evaluator != "stream":
@@ -524,9 +572,14 @@ def main(argv=None) -> int:
             ap.error("--parser device leaves the program in GPU memory: --evaluator host cannot read it (use gpu or stream)")
         if a.evaluator == "auto":
             a.evaluator = "gpu"
+    if a.witness_parser == "device" and a.operation == "oneshot":
+        if a.evaluator == "host":
+            ap.error("--witness-parser device leaves the witness in GPU memory: --evaluator host cannot read it (use gpu or stream)")
+        if a.evaluator == "auto":
+            a.evaluator = "gpu"
     if a.operation == "oneshot" and a.evaluator == "stream":
         print("Evaluating program in cleartext")
-        evaluate_stream(a.program_path, a.program_format, a.expected_outputs_path, parse_witness(open(a.witness_path, "rb").read()),
+        evaluate_stream(a.program_path, a.program_format, a.expected_outputs_path, load_witness(a.witness_path, a.witness_parser, a.witness_window_mb),
                         a.max_chunk_ops, device_compile=a.compiler != "host", **({"device_z64": True} if a.compiler in ("device-z64", "device-b2a") else {}),
                         **({"device_b2a": True} if a.compiler == "device-b2a" else {}), **({"compact": True} if a.compact_wires else {}),
                         **({"parser": "device"} if device_parser else {}), **({"window_mb": a.window_mb} if a.window_mb is not None else {}),
@@ -543,8 +596,8 @@ def main(argv=None) -> int:
         prog, wc = compact_program(prog, wc)
     if a.operation == "oneshot":
         print("Evaluating program in cleartext")
-        wit = parse_witness(open(a.witness_path, "rb").read())
-        if device_parser or use_gpu_evaluator(prog, a.evaluator):
+        wit = load_witness(a.witness_path, a.witness_parser)
+        if device_parser or a.witness_parser == "device" or use_gpu_evaluator(prog, a.evaluator):
             evaluate_gpu(prog, wc, wit, a.compiler)
         else:
             evaluate_clear(prog, wit)
@@ -557,7 +610,7 @@ def main(argv=None) -> int:
     else:
         circuit = Circuit(prog, wc, device_compile=a.compiler != "host", device_z64=a.compiler in ("device-z64", "device-b2a"), device_b2a=a.compiler == "device-b2a")
     if a.operation in ("prove", "oneshot-zk"):
-        wit = parse_witness(open(a.witness_path, "rb").read())
+        wit = load_witness(a.witness_path, a.witness_parser)
         print("Evaluating program in ~zero knowledge~")
         proof = Proof.new(circuit, wit, [])
         if a.operation == "prove":

@@ -144,6 +144,8 @@ SYMBOLS = [
     "rv_bristol_write", "rv_bristol_write_device", "rv_hook_bristol_write_tiles",
     "rv_bristol_writer_begin", "rv_bristol_writer_feed", "rv_bristol_writer_finish", "rv_bristol_writer_destroy",
     "rv_program_writer_begin", "rv_program_writer_feed", "rv_program_writer_finish", "rv_program_writer_destroy",
+    "rv_witness_parse", "rv_witness_write", "rv_witness_parse_device", "rv_hook_witness_text_tiles", "rv_witness_write_device",
+    "rv_witness_reader_begin", "rv_witness_reader_feed", "rv_witness_reader_finish", "rv_witness_reader_destroy",
     "rv_hook_prove_schedule",
     "rv_hook_b3_plan", "rv_hook_b3_chunks", "rv_hook_b3_pair_small", "rv_hook_b3_pair_big_chunks", "rv_hook_b3_tree", "rv_hook_b3_pair_big_tree",
     "rv_hook_b3_incremental", "rv_hook_b3_join",
@@ -270,6 +272,16 @@ ARGTYPES = {
     "rv_program_writer_feed": [_P, _P, _Z, C.c_int, _P, _Z, C.POINTER(WriterPiece)],
     "rv_program_writer_finish": [_P],
     "rv_program_writer_destroy": [_P],
+    # witness text on the host and on the GPU, whole and in windows
+    "rv_witness_parse": [_P, _Z, _P, _Z, C.POINTER(C.c_size_t)],
+    "rv_witness_write": [_P, _Z, C.c_uint64, _P, _Z, C.POINTER(C.c_size_t)],
+    "rv_witness_parse_device": [_P, _P, _Z, C.c_int, _P, _Z, C.POINTER(C.c_size_t), _P, _Z, _P],
+    "rv_hook_witness_text_tiles": [C.POINTER(C.c_uint32)],
+    "rv_witness_write_device": [_P, _P, _Z, C.c_uint64, _P, _Z, C.POINTER(C.c_size_t)],
+    "rv_witness_reader_begin": [_P, C.POINTER(_P)],
+    "rv_witness_reader_feed": [_P, _P, _Z, C.c_int, _P, _Z, C.POINTER(C.c_size_t)],
+    "rv_witness_reader_finish": [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "rv_witness_reader_destroy": [_P],
     # the transcript-hash kernels (parity hooks)
     "rv_hook_b3_plan": [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)],
     "rv_hook_b3_chunks": [_P, C.c_int, _P, C.c_uint64, C.c_uint32, C.c_uint64, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64,
@@ -334,7 +346,7 @@ def lib():
             fn = getattr(L, name)
             if name in ("rv_ctx_destroy", "rv_circuit_destroy", "rv_shard_destroy", "rv_free", "rv_stream_abort", "rv_comm_destroy",
                         "rv_eval_stream_abort", "rv_program_reader_destroy", "rv_bristol_reader_destroy", "rv_compactor_destroy",
-                        "rv_bristol_writer_destroy", "rv_program_writer_destroy"):
+                        "rv_bristol_writer_destroy", "rv_program_writer_destroy", "rv_witness_reader_destroy"):
                 fn.restype = None
             elif name in ("rv_hook_early_proofs", "rv_hook_open_direct_proofs", "rv_hook_verify_vc_count", "rv_hook_ops_cache_hits", "rv_hook_overlap_commits",
                           "rv_hook_verify_proof_bytes", "rv_hook_stream_device_chunks"):

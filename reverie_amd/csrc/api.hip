@@ -34,6 +34,7 @@
 #include "piece_pipe.h"
 #include "piece_sums.h"
 #include "verify_dev.h"
+#include "witness_text.h"
 
 using namespace rv;
 
@@ -1650,3 +1651,4 @@ extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
 #include "bristol.inc"
 #include "bincode.inc"
 #include "bristol_write.inc"
+#include "witness_text.inc"

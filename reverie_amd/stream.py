@@ -730,19 +730,28 @@ def _piece_inputs(ops, counts) -> Tuple[int, int]:
     return int(np.count_nonzero(inputs & (a["domain"] == 0))), int(np.count_nonzero(inputs & (a["domain"] == 1)))
 
 
+def _is_wit_source(w) -> bool:
+    """a GF(2) witness that is read as the pieces ask for it (`witness.DeviceWindows`): take(n) gives the next n bits as a GPU
+    tensor, rewind() starts over"""
+    return hasattr(w, "take") and hasattr(w, "rewind")
+
+
 def _host_or_device_wit(w, dtype):
-    return w if hasattr(w, "data_ptr") else np.ascontiguousarray(np.asarray(w, dtype=dtype))
+    return w if hasattr(w, "data_ptr") or _is_wit_source(w) else np.ascontiguousarray(np.asarray(w, dtype=dtype))
 
 
 def _feed_pieces(feed, pieces, wit_gf2, wit_z64):
     """every piece of one pass to feed(ops, gf2 elements, z64 elements); the witnesses (the last axis) advance by the pieces' Input
-    counts"""
+    counts.  A GF(2) witness source is rewound first and gives each piece its bits with take."""
     used_g = used_z = 0
+    source = _is_wit_source(wit_gf2)
+    if source:
+        wit_gf2.rewind()
     for ops, counts in (pieces() if callable(pieces) else pieces):
         if ops is None or len(ops) == 0:
             continue
         n_g, n_z = _piece_inputs(ops, counts)
-        feed(ops, wit_gf2[..., used_g:used_g + n_g], wit_z64[..., used_z:used_z + n_z])
+        feed(ops, wit_gf2.take(n_g) if source else wit_gf2[..., used_g:used_g + n_g], wit_z64[..., used_z:used_z + n_z])
         used_g, used_z = used_g + n_g, used_z + n_z
 
 
@@ -753,7 +762,8 @@ def prove_streaming_pieces(pieces, wit_gf2, wit_z64, wire_counts: Tuple[int, int
     n_input_z64)) for each of the two passes -- `program_file.iter_device` on a program file, say (its piece dicts serve as the
     counts).  ops: a host array or a torch GPU tensor of rv_op records; a host array may come with None, its Inputs are then counted
     here.  Both passes must yield the same pieces (rv_stream_same_cuts is set).  The proof is `prove_streaming`'s for the
-    concatenated list; wire_counts are the whole list's (`program_file.scan_device`).  compact_wires: the pieces are renumbered by
+    concatenated list; wire_counts are the whole list's (`program_file.scan_device`).  wit_gf2 may be a witness source that is read
+    as the pieces ask for bits (`witness.DeviceWindows`: rewound at the start of each pass, take(n) per piece).  compact_wires: the pieces are renumbered by
     liveness in windows (`compact.compact_pieces`: the source is read for a scan pass first, twice with B2A ops), wire_counts are
     the source's and the stream begins with the new ones; the same proof, and info carries "compact".
     -> (Proof or DeviceProof, stream info)"""
@@ -797,11 +807,11 @@ def evaluate_streaming_pieces(pieces, wits_gf2, wits_z64, wire_counts: Tuple[int
                               ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False,
                               device_b2a: bool = False, compact_wires: bool = False) -> Evaluation:
     """`evaluate_streaming` for pieces as `prove_streaming_pieces` takes them, in one pass.  wits_gf2 / wits_z64: [B][n] (1-D for one
-    witness), host arrays or torch GPU tensors.  compact_wires: as in `prove_streaming_pieces` (wire values are those of the new
+    witness), host arrays, torch GPU tensors or, for one GF(2) witness, a `witness.DeviceWindows`.  compact_wires: as in `prove_streaming_pieces` (wire values are those of the new
     indices).  -> the array-shaped Evaluation; `info` receives the stream's figures (and "compact")."""
     g, z = _host_or_device_wit(wits_gf2, np.uint8), _host_or_device_wit(wits_z64, np.uint64)
     pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires)
-    batch = g.shape[0] if g.ndim == 2 else 1
+    batch = 1 if _is_wit_source(g) else g.shape[0] if g.ndim == 2 else 1
     se = StreamingEvaluator(wire_counts, batch, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
     try:
         _feed_pieces(se.feed, pieces, g, z)
