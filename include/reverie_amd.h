@@ -1335,6 +1335,47 @@ int rv_hook_b3_incremental(rv_ctx *ctx, const uint32_t *cvs, uint64_t n, uint32_
                            uint32_t *digest, uint64_t dig_words);
 /* The digest join: digs [4][R][8] (pre2, on2, pre64, on64) -> h [R][32] in front of h_bytes bytes. */
 int rv_hook_b3_join(rv_ctx *ctx, const uint32_t *digs, uint32_t R, uint32_t batch, uint8_t *h, uint64_t h_bytes);
+/* ---- Fiat-Shamir, the record heads, the framing and the set-up kernels (csrc/open.hip), one production launch each on caller-supplied
+ * data (csrc/hooks_open.inc; proof/mod.rs:41-108, crypto/ro.rs:8-20).  As above: every output buffer is read first and returned whole,
+ * and RV_E_ARG is returned before anything is launched for whatever a kernel relies on its callers for. ---- */
+/* launch_fs_challenge on digests [B][256][32] (B = batch, or 1 when batch is 0) for the shard (rep_begin, R): both multiples of 8 inside
+ * the 256 repetitions.  layout[10] = the section starts base[4], then sz2, sz64, l2r, l2c, l64r, l64c (record sizes and vector byte
+ * lengths); framed (0 / 1; 1 only for the whole shard): base[1..3] are taken as given instead of following from the device's counts.
+ * flags: bit 0 omit_all, bit 1 res, bit 2 comm2, bit 3 the mailbox are passed to the kernel (NULL otherwise; the mailbox not in a batch).
+ * Outputs, B of each: comm [32], omit [R], omit_all [256], offs [8][R], ol (the kernel's list of opened repetitions, 488 bytes: u32 n,
+ * u32 rep[40], four bytes of padding, u64 dst[40]), res [2], comm2 [32]; mbox [128] words of host-mapped memory: word 0 receives
+ * mbox_seq, words 16 .. 89 comm, the whole map and the two counts.  batch >= 2: recorded and replayed as a batch of proofs is. */
+int rv_hook_fs_challenge(rv_ctx *ctx, const uint8_t *digests, const uint64_t *layout, uint32_t framed, uint32_t rep_begin, uint32_t R, uint32_t flags,
+                         uint32_t mbox_seq, uint32_t batch, uint8_t *comm, uint8_t *omit, uint8_t *omit_all, uint64_t *offs, uint8_t *ol, uint32_t *res,
+                         uint8_t *comm2, uint32_t *mbox);
+/* launch_open_headers: the fixed-size parts of a shard's records into out -- seeds [R][16], keys [R][128], on2 / on64 [R][8] u32 (the
+ * online transcripts' digests), off2 / off64 [R] the records' offsets, lens[6] = l2r, l2c, l2i, l64r, l64c, l64i.  RV_E_ARG for a record
+ * that does not lie inside out. */
+int rv_hook_open_headers(rv_ctx *ctx, uint32_t R, const uint8_t *omit, const uint8_t *seeds, const uint8_t *keys, const uint32_t *on2, const uint32_t *on64,
+                         const uint64_t *off2, const uint64_t *off64, const uint64_t *lens, uint8_t *out, uint64_t out_bytes);
+/* launch_open_small: the heads as above from the table offs [8][R], and the three GF(2) vectors: rows rec_rows[0 .. n_rec) and
+ * in_rows[0 .. n_in) (NULL: 0, 1, ...) of stream [stream_rows][R/4] u32, n_pre rows of the bit stream pre [n_pre][R/8] through the list ol
+ * (488 bytes as rv_hook_fs_challenge returns them), without the repetitions below corr_rep_min.  flags: bit 0 heads_inputs_only, bit 1
+ * the host-mapped error word is passed and receives err_src.  *taken = 0: the launcher declined and nothing ran; tiles[3]: the tiles of
+ * the three extractions in bytes. */
+int rv_hook_open_small(rv_ctx *ctx, uint32_t R, const uint8_t *omit, const uint8_t *seeds, const uint8_t *keys, const uint32_t *on2, const uint32_t *on64,
+                       const uint64_t *offs, const uint64_t *lens, const uint32_t *stream, uint64_t stream_rows, const uint32_t *rec_rows, uint64_t n_rec,
+                       const uint8_t *pre, uint64_t n_pre, const uint32_t *in_rows, uint64_t n_in, const uint8_t *ol, uint32_t corr_rep_min, int err_src,
+                       uint32_t flags, uint8_t *out, uint64_t out_bytes, int *taken, uint32_t *tiles, int *err_word);
+/* launch_frame_counts: the four repetition counts of `batch` framed proofs `stride` bytes apart in out; lens[4] the section lengths.
+ * *taken = 0: the launcher declined (no proof, an offset or stride that is no multiple of 8) and nothing ran. */
+int rv_hook_frame_counts(rv_ctx *ctx, uint8_t *out, uint64_t out_bytes, uint64_t stride, uint32_t batch, const uint64_t *lens, int *taken);
+/* launch_overlay_rows: rows of src replace those of dst ([R][row_words] u32) where (omit[r] < 8) == want_online. */
+int rv_hook_overlay_rows(rv_ctx *ctx, uint32_t *dst, const uint32_t *src, const uint8_t *omit, uint32_t R, uint32_t row_words, int want_online);
+/* launch_fill_digests: n_rows copies of digest[8] at the start of dst (dst_words words). */
+int rv_hook_fill_digests(rv_ctx *ctx, uint32_t *dst, uint64_t dst_words, uint32_t n_rows, const uint32_t *digest);
+/* launch_shard_init: err[0] (of two ints) cleared, the first n_mask_words of mask and n_corr_bytes of corr cleared (RV_E_ARG above 64: the
+ * kernel has 64 threads and no loop), n_fill_rows copies of digest[8] into fill (NULL: none), zero_byte[0] (NULL or 8 bytes) cleared. */
+int rv_hook_shard_init(rv_ctx *ctx, int *err, uint32_t *mask, uint64_t mask_words, uint32_t n_mask_words, uint8_t *corr, uint64_t corr_bytes,
+                       uint32_t n_corr_bytes, uint32_t *fill, uint64_t fill_words, uint32_t n_fill_rows, const uint32_t *digest, uint8_t *zero_byte);
+/* launch_store_words: src [n_words] into dst (dst_words < 1023 words, host-mapped for the launch); with_err: a device word holding
+ * err_value into *dst_err. */
+int rv_hook_store_words(rv_ctx *ctx, const uint32_t *src, uint32_t n_words, uint32_t *dst, uint32_t dst_words, int err_value, int with_err, int *dst_err);
 /* The two gate-stream compilers against each other (host only): the program is compiled by the sequential compiler and by the
  * parallel one with `threads` host threads (>= 2), whatever its size, and the results are compared field by field.
  * *diff = 0: identical; > 0: a number naming the first differing table (csrc/compile_par.cpp, compiled_diff); -1: the parallel

@@ -149,6 +149,8 @@ SYMBOLS = [
     "rv_hook_prove_schedule",
     "rv_hook_b3_plan", "rv_hook_b3_chunks", "rv_hook_b3_pair_small", "rv_hook_b3_pair_big_chunks", "rv_hook_b3_tree", "rv_hook_b3_pair_big_tree",
     "rv_hook_b3_incremental", "rv_hook_b3_join",
+    "rv_hook_fs_challenge", "rv_hook_open_headers", "rv_hook_open_small", "rv_hook_frame_counts",
+    "rv_hook_overlay_rows", "rv_hook_fill_digests", "rv_hook_shard_init", "rv_hook_store_words",
 ]
 _P, _Z = C.c_void_p, C.c_size_t
 # argument types of the batched stream entry points (ctypes checks every call against them)
@@ -293,6 +295,16 @@ ARGTYPES = {
     "rv_hook_b3_pair_big_tree": [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, _P, _P, C.c_uint64, C.POINTER(C.c_uint32)],
     "rv_hook_b3_incremental": [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint64],
     "rv_hook_b3_join": [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64],
+    # the Fiat-Shamir, record-head, framing and set-up kernels (parity hooks)
+    "rv_hook_fs_challenge": [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P],
+    "rv_hook_open_headers": [_P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64],
+    "rv_hook_open_small": [_P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint32, C.c_int,
+                           C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_int), _P, C.POINTER(C.c_int)],
+    "rv_hook_frame_counts": [_P, _P, C.c_uint64, C.c_uint64, C.c_uint32, _P, C.POINTER(C.c_int)],
+    "rv_hook_overlay_rows": [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_int],
+    "rv_hook_fill_digests": [_P, _P, C.c_uint64, C.c_uint32, _P],
+    "rv_hook_shard_init": [_P, _P, _P, C.c_uint64, C.c_uint32, _P, C.c_uint64, C.c_uint32, _P, C.c_uint64, C.c_uint32, _P, _P],
+    "rv_hook_store_words": [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_int)],
 }
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1

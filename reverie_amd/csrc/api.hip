@@ -1642,6 +1642,7 @@ extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
 #include "feed_ops.inc"
 #include "stream.inc"
 #include "hooks_b3.inc"
+#include "hooks_open.inc"
 #include "comm.inc"
 #include "eval.inc"
 #include "eval_stream.inc"

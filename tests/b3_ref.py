@@ -31,9 +31,8 @@ def _g(v, a, b, c, d, mx, my):
     v[b] = _rotr(v[b] ^ v[c], 7)
 
 
-def compress(cv, m, t, blen, flags):
-    """cv [..., 8], m [..., 16] uint32 words; t (64-bit counter), blen, flags: scalars or arrays that broadcast against the
-    leading dimensions -> the new chaining value [..., 8] (the first half of the output block)"""
+def _state(cv, m, t, blen, flags):
+    """the sixteen state words after the seven rounds, before the feed-forward"""
     cv = np.asarray(cv, np.uint32)
     m = np.asarray(m, np.uint32)
     lead = np.broadcast_shapes(cv.shape[:-1], m.shape[:-1], np.shape(t), np.shape(blen), np.shape(flags))
@@ -54,7 +53,22 @@ def compress(cv, m, t, blen, flags):
             _g(v, 3, 4, 9, 14, w[14], w[15])
             if rnd < 6:
                 w = [w[p] for p in MSG_PERMUTATION]
+    return v
+
+
+def compress(cv, m, t, blen, flags):
+    """cv [..., 8], m [..., 16] uint32 words; t (64-bit counter), blen, flags: scalars or arrays that broadcast against the
+    leading dimensions -> the new chaining value [..., 8] (the first half of the output block)"""
+    v = _state(cv, m, t, blen, flags)
     return np.stack([v[i] ^ v[i + 8] for i in range(8)], axis=-1)
+
+
+def compress_xof(cv, m, t, blen, flags):
+    """the whole 64-byte output block [..., 16] (extended output: t is the output-block counter): the chaining value's half, then the
+    state's upper half with the input chaining value fed forward"""
+    v = _state(cv, m, t, blen, flags)
+    cv = np.asarray(cv, np.uint32)
+    return np.stack([v[i] ^ v[i + 8] for i in range(8)] + [v[i + 8] ^ cv[..., i] for i in range(8)], axis=-1)
 
 
 def n_chunks(n_bytes):

@@ -7,9 +7,9 @@ The rv_hook_* entry points call the production launch_* functions unchanged and 
 0xA5, and a byte outside the expected vectors must still be 0xA5 afterwards (records lie side by side in a proof: a one-byte overrun
 is a wrong proof).  tests/test_pack_ref_host.py ties the reference to the CPU oracle.
 
-Not tested: more than 40 opened repetitions (ex_slots clamps there, production never exceeds it and the hooks refuse it);
-k_open_headers and k_open_small (fixed-size / the same bodies as ranges of one grid: every proof test runs them); the second draw
-round of k_fs_challenge."""
+Not tested: more than 40 opened repetitions (ex_slots clamps there, production never exceeds it and the hooks refuse it).
+k_fs_challenge, k_open_headers, k_open_small and k_frame_counts have their own file, tests/test_gpu_open_heads.py (which leaves out the
+second draw round of k_fs_challenge: no input is known that needs one)."""
 import ctypes as C
 import functools
 
