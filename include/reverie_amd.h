@@ -1194,6 +1194,95 @@ void rv_witness_reader_destroy(rv_witness_reader *r);
  * length >= 2^32: RV_E_UNSUPPORTED.  Runs on the context's stream and synchronises it once. */
 int rv_witness_write_device(rv_ctx *ctx, const uint8_t *d_bits, size_t n, uint64_t line_bits, char *d_text, size_t cap, size_t *len);
 
+/* ---- programs linked from circuit blocks, on the host and on the GPU, whole and in windows --------
+ * A statement is many copies ("instances") of a few function blocks wired together.  rv_link (host only, no GPU) is the definition
+ * of the linked op list; the plan below gives its bytes, for any range of ordinals, into device memory.
+ *   INPUTS.  blocks[n_blocks]: op lists with their stated wire counts.  A block may hold GF(2), Z64 and B2A records, Random and
+ * AssertZero included, and need not be in SSA form.  Its PORTS are its Input records in list order, both domains counted together.
+ * block_of[n_instances]: instance i is a copy of blocks[block_of[i]].  bindings[n_bindings]: the bindings of instance i's ports are
+ * the entries B(i) .. B(i) + ports(block_of[i]) - 1, B the running sum of the port counts; RV_LINK_WITNESS leaves the port an Input,
+ * any other value is a global wire index of the port's domain.  z64_base / gf2_base: the first wire index of instance 0 per domain.
+ * head[n_head], tail[n_tail]: op lists in global numbering (constants, global inputs, the assertions on outputs), copied as they are.
+ *   OUTPUT: head, the records of instance 0, 1, ... n_instances - 1, tail.  With Z(i) = z64_base + the sum of the stated z64_wires of
+ * the blocks of the instances before i, and G(i) likewise, record r of instance i's block is emitted with its domain, opcode,
+ * reserved and imm, and Z(i) or G(i) added to every field that names a wire, by the domain of the wire it names: dst in all records
+ * but AssertZero; a in all but Input, Random and Const; b in Add, Sub and Mul; in B2A dst is a Z64 wire and a a GF(2) wire.  A field
+ * that names no wire is copied unchanged.  An Input whose binding is not RV_LINK_WITNESS becomes AddConst(dst + base, binding, 0) of
+ * its domain with b = 0, reserved = 0 and imm = 0: a copy, what the Bristol front end makes of EQW.  Every instance emits exactly its
+ * block's record count, so record j of the output is a function of j alone.
+ *   INFO, derived without the output: n_ops; n_instances; n_input_gf2 / n_input_z64, the Input records of the whole output;
+ * z64_wires / gf2_wires, each the larger of what the largest-index rule (reverie_amd.ops.largest_wires: one more than the largest
+ * index a record names, a + 64 for B2A, a SizeHint's own counts) gives for head and tail, and, when there are instances, the base
+ * plus the sum of all instances' stated counts.
+ *   CODES, the first in this order of decisions:
+ *   (1) arguments: a NULL desc or info, a NULL array with a nonzero count, a stated wire count above 2^32: RV_E_ARG; 2^31 instances
+ *       or more, or 2^32 block records or more in all: RV_E_UNSUPPORTED;
+ *   (2) blocks in order, each block's records in order: reserved != 0, an unknown domain or opcode (rv_program_to_bincode's rule; the
+ *       opcode byte of a B2A or SizeHint record is not looked at): RV_E_BAD_OP; a SizeHint: RV_E_UNSUPPORTED; a named index at or above
+ *       the stated count of its domain (B2A: dst, and a + 64 above the GF(2) count): RV_E_WIRE_OOB;
+ *   (3) head in order, then (4) tail in order: the malformed-record rule (RV_E_BAD_OP) alone; a SizeHint is allowed;
+ *   (5) instances in order: block_of[i] >= n_blocks: RV_E_ARG; then n_bindings other than the sum of the port counts: RV_E_ARG; then,
+ *       with instances, a base plus the sum of the stated counts that does not fit in 32 bits, and in any case a result wire count
+ *       above 2^32 (a B2A of head or tail): RV_E_UNSUPPORTED;
+ *   (6) bindings in order: a value other than RV_LINK_WITNESS at or above the result's wire count of its port's domain: RV_E_WIRE_OOB.
+ * With a code nothing is returned.  rv_link: *ops is library-allocated (rv_free); ops == NULL gives the info alone. */
+#define RV_LINK_WITNESS 0xFFFFFFFFu
+typedef struct rv_link_block {
+    const rv_op *ops;
+    uint64_t n_ops;
+    uint64_t z64_wires, gf2_wires; /* the stated counts: the instance's share of the global numbering */
+} rv_link_block;
+typedef struct rv_link_desc {
+    const rv_link_block *blocks;
+    uint64_t n_blocks;
+    const uint32_t *block_of;
+    uint64_t n_instances;
+    const uint32_t *bindings;
+    uint64_t n_bindings;
+    uint64_t z64_base, gf2_base;
+    const rv_op *head;
+    uint64_t n_head;
+    const rv_op *tail;
+    uint64_t n_tail;
+} rv_link_desc;
+typedef struct rv_link_info {
+    uint64_t n_ops, n_instances, n_input_gf2, n_input_z64, z64_wires, gf2_wires;
+} rv_link_info;
+int rv_link(const rv_link_desc *desc, rv_op **ops, rv_link_info *info);
+/* The same list from kernels.  A plan is made once per descriptor and then emits any range of ordinals, any number of times and
+ * in any order (the streams read a source once per pass):
+ *     rv_link_plan_create(ctx, desc, flags, &plan)
+ *     rv_link_plan_info(plan, &info)
+ *     rv_link_plan_emit(plan, first_op, n, d_ops, &piece)
+ *     rv_link_plan_destroy(plan)
+ * create: the return code and the info are what rv_link gives for the same descriptor, for every descriptor, and a plan is made
+ * only for RV_OK.  The blocks' op lists (RV_LINK_BLOCKS_ON_DEVICE) and block_of / bindings (RV_LINK_TABLES_ON_DEVICE) may lie in the
+ * memory of the context's device (rv_circuit_compile_device's conventions: ops 8-byte aligned, tables 4-byte aligned, each inside
+ * one allocation; RV_E_ARG otherwise, and for an unknown flag); the rv_link_block array itself, head and tail are host memory.  The
+ * plan keeps its own device copy of everything, so nothing of the caller's has to outlive the call.  It runs on the context's stream:
+ * every block record is judged (the first code by a 64-bit minimum of position << 8 | code), each block's Input flags are scanned into
+ * port ordinals, the instances are scanned into four exclusive 64-bit prefix arrays (op offset, Z, G, B) while block_of is checked,
+ * and every binding is checked and counted.  MEMORY held until destroy, from the context arena: the copies (24 bytes per block, head
+ * and tail record, 4 per instance and per binding), 4 bytes per block record (port ordinals), 32 bytes per block and 32 per
+ * instance (the four prefix arrays).
+ * emit: records first_op .. first_op + n - 1 of the output list into d_ops (memory of the context's device, 8-byte aligned, inside
+ * one allocation), n == 0 included; piece receives the range and its Input counts per domain, what a stream piece needs.  Ordinals are
+ * 64-bit; one call stays below 2^28 records (RV_E_UNSUPPORTED: the program writer's limit).  RV_E_ARG before any launch, with d_ops
+ * untouched: a NULL plan or piece, a range outside the list, a NULL (with n != 0), misaligned or foreign d_ops.  The call runs on
+ * the context's stream and waits for it once. */
+#define RV_LINK_BLOCKS_ON_DEVICE 1u
+#define RV_LINK_TABLES_ON_DEVICE 2u
+typedef struct rv_link_plan rv_link_plan;
+typedef struct rv_link_piece {
+    uint64_t first_op, n_ops, n_input_gf2, n_input_z64;
+} rv_link_piece;
+int rv_link_plan_create(rv_ctx *ctx, const rv_link_desc *desc, uint32_t flags, rv_link_plan **plan);
+int rv_link_plan_info(const rv_link_plan *plan, rv_link_info *info);
+int rv_link_plan_emit(rv_link_plan *plan, uint64_t first_op, uint64_t n, rv_op *d_ops, rv_link_piece *piece);
+void rv_link_plan_destroy(rv_link_plan *plan);
+/* out[0] = records per workgroup of the emit kernel, out[1] = items per workgroup of the scans (the sizes the tests go around) */
+int rv_hook_link_tiles(uint32_t out[2]);
+
 /* ---- parity-test hooks: each mirrors one reference function so tests can compare the
  * HIP path with the oracle piecewise ---- */
 /* PRG::new + gen (crypto/prg.rs:16-37) on the GPU: n_keys keys, blocks [first, first+n_blocks) each */

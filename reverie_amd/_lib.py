@@ -90,6 +90,24 @@ class WriterPiece(C.Structure):  # rv_writer_piece
     _fields_ = [(n, C.c_uint64) for n in ("first_op", "n_ops", "file_off", "bytes")]
 
 
+class LinkBlock(C.Structure):  # rv_link_block
+    _fields_ = [("ops", C.c_void_p), ("n_ops", C.c_uint64), ("z64_wires", C.c_uint64), ("gf2_wires", C.c_uint64)]
+
+
+class LinkDesc(C.Structure):  # rv_link_desc
+    _fields_ = [("blocks", C.POINTER(LinkBlock)), ("n_blocks", C.c_uint64), ("block_of", C.c_void_p), ("n_instances", C.c_uint64),
+                ("bindings", C.c_void_p), ("n_bindings", C.c_uint64), ("z64_base", C.c_uint64), ("gf2_base", C.c_uint64),
+                ("head", C.c_void_p), ("n_head", C.c_uint64), ("tail", C.c_void_p), ("n_tail", C.c_uint64)]
+
+
+class LinkInfo(C.Structure):  # rv_link_info
+    _fields_ = [(n, C.c_uint64) for n in ("n_ops", "n_instances", "n_input_gf2", "n_input_z64", "z64_wires", "gf2_wires")]
+
+
+class LinkPiece(C.Structure):  # rv_link_piece
+    _fields_ = [(n, C.c_uint64) for n in ("first_op", "n_ops", "n_input_gf2", "n_input_z64")]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8), ("calls", C.c_uint64)]
 
@@ -146,6 +164,7 @@ SYMBOLS = [
     "rv_program_writer_begin", "rv_program_writer_feed", "rv_program_writer_finish", "rv_program_writer_destroy",
     "rv_witness_parse", "rv_witness_write", "rv_witness_parse_device", "rv_hook_witness_text_tiles", "rv_witness_write_device",
     "rv_witness_reader_begin", "rv_witness_reader_feed", "rv_witness_reader_finish", "rv_witness_reader_destroy",
+    "rv_link", "rv_link_plan_create", "rv_link_plan_info", "rv_link_plan_emit", "rv_link_plan_destroy", "rv_hook_link_tiles",
     "rv_hook_prove_schedule",
     "rv_hook_b3_plan", "rv_hook_b3_chunks", "rv_hook_b3_pair_small", "rv_hook_b3_pair_big_chunks", "rv_hook_b3_tree", "rv_hook_b3_pair_big_tree",
     "rv_hook_b3_incremental", "rv_hook_b3_join",
@@ -284,6 +303,13 @@ ARGTYPES = {
     "rv_witness_reader_feed": [_P, _P, _Z, C.c_int, _P, _Z, C.POINTER(C.c_size_t)],
     "rv_witness_reader_finish": [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "rv_witness_reader_destroy": [_P],
+    # programs linked from circuit blocks, on the host and on the GPU
+    "rv_link": [C.POINTER(LinkDesc), C.POINTER(_P), C.POINTER(LinkInfo)],
+    "rv_link_plan_create": [_P, C.POINTER(LinkDesc), C.c_uint32, C.POINTER(_P)],
+    "rv_link_plan_info": [_P, C.POINTER(LinkInfo)],
+    "rv_link_plan_emit": [_P, C.c_uint64, C.c_uint64, _P, C.POINTER(LinkPiece)],
+    "rv_link_plan_destroy": [_P],
+    "rv_hook_link_tiles": [C.POINTER(C.c_uint32)],
     # the transcript-hash kernels (parity hooks)
     "rv_hook_b3_plan": [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)],
     "rv_hook_b3_chunks": [_P, C.c_int, _P, C.c_uint64, C.c_uint32, C.c_uint64, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64,
@@ -306,6 +332,9 @@ ARGTYPES = {
     "rv_hook_shard_init": [_P, _P, _P, C.c_uint64, C.c_uint32, _P, C.c_uint64, C.c_uint32, _P, C.c_uint64, C.c_uint32, _P, _P],
     "rv_hook_store_words": [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_int)],
 }
+RV_LINK_WITNESS = 0xFFFFFFFF  # a binding that leaves the port an Input
+RV_LINK_BLOCKS_ON_DEVICE = 1
+RV_LINK_TABLES_ON_DEVICE = 2
 RV_VERIFY_STRICT = 1
 RV_COMPILE_WHOLE_PROVER = 1
 RV_COMPILE_KEEP_WIRES = 2  # the circuit keeps every wire's final value form: rv_evaluate can return wire values
@@ -358,7 +387,7 @@ def lib():
             fn = getattr(L, name)
             if name in ("rv_ctx_destroy", "rv_circuit_destroy", "rv_shard_destroy", "rv_free", "rv_stream_abort", "rv_comm_destroy",
                         "rv_eval_stream_abort", "rv_program_reader_destroy", "rv_bristol_reader_destroy", "rv_compactor_destroy",
-                        "rv_bristol_writer_destroy", "rv_program_writer_destroy", "rv_witness_reader_destroy"):
+                        "rv_bristol_writer_destroy", "rv_program_writer_destroy", "rv_witness_reader_destroy", "rv_link_plan_destroy"):
                 fn.restype = None
             elif name in ("rv_hook_early_proofs", "rv_hook_open_direct_proofs", "rv_hook_verify_vc_count", "rv_hook_ops_cache_hits", "rv_hook_overlap_commits",
                           "rv_hook_verify_proof_bytes", "rv_hook_stream_device_chunks"):

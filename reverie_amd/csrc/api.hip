@@ -30,6 +30,7 @@
 #include "compile_dev.h"
 #include "internal.h"
 #include "launch.h"
+#include "link.h"
 #include "ldsrun.h"
 #include "piece_pipe.h"
 #include "piece_sums.h"
@@ -1653,3 +1654,4 @@ extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
 #include "bincode.inc"
 #include "bristol_write.inc"
 #include "witness_text.inc"
+#include "link.inc"
