@@ -1387,6 +1387,47 @@ int rv_hook_z64_fused_grid(uint32_t qw, uint32_t n_qg, uint32_t cus, uint32_t n_
  * B2A gate (no table: *n_levels = 0); 2 a Mul's mask pair straddles cipher blocks; 3 more than 64 Input block runs; 4 no Z64 gate. */
 int rv_hook_z64_fused_levels(const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, uint32_t *out, size_t cap,
                              size_t *n_levels, int *eligible);
+/* What the upload path makes of a program for the fused Z64 path (host only; the same compile, then the same function): the records
+ * grouped Mul | linear | other inside every level (64 bytes each, the layout of csrc/internal.h: Gate64), the level table as above, the
+ * cipher block runs whose rows are Input masks (two uint64 per run: first block, blocks) and the eligibility code as above.  Count,
+ * then fill: *n_gates, *n_levels and *n_runs are always the full counts, every array takes its first `cap` entries.  sizes (nullable):
+ * Z64 SSA ids, mask rows, online and preprocessing words per repetition, input, correction and reconstruction ordinals. */
+int rv_hook_z64_fused_gates(const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, uint32_t flags, void *gates, size_t gates_cap,
+                            size_t *n_gates, uint32_t *levels, size_t levels_cap, size_t *n_levels, uint64_t *runs, size_t runs_cap,
+                            size_t *n_runs, int *eligible, uint64_t sizes[7]);
+/* One fused Z64 level launch after the other on caller-supplied records and buffers (tests/test_gpu_z64_fused_level.py, reference
+ * tests/z64f_ref.py): the production launcher, once per level of `levels` in order, over quad groups [qg0, qg0 + qgn) of the rows'
+ * R / 4 quad words, the cipher counting from first_block.  omit = NULL: the prover (wit, v); else the verifier (omit[R] = 0..7 the
+ * hidden player of an opened repetition, 8 not opened; wcorr and the three supplied arrays [ordinal][sup_r]).  Keys come from
+ * seeds[R][16] by the three set-up launches (key_path 0) or the fused one (1); the rows of the block runs are generated from
+ * first_block + first with the verifier's keep words, as a shard does, before the first level.  wmask [n_ssa][8 R], masks
+ * [n_mask_rows][8 R], v [n_ssa], wcorr [n_ssa][R], on [R][on_words], pre [R][pre_words] and err [1] are read first and come back
+ * whole.  RV_E_ARG, with nothing written: R / 4 is no multiple of 8, the quad groups leave the row, a level leaves the records, a
+ * record of the wrong class or a Random / B2A record, a Mul with odd m, any index of a record that leaves its buffer, an opened
+ * repetition at or past sup_r.  RV_E_UNSUPPORTED, with nothing written: a counter first_block + m / 2 of 2^24 or more. */
+typedef struct rv_hook_z64f_run_args {
+    const uint8_t *seeds;
+    const uint8_t *omit;
+    uint32_t R, key_path;
+    uint64_t first_block;
+    uint32_t qg0, qgn;
+    const void *gates;
+    size_t n_gates;
+    const uint32_t *levels; /* [n_levels][4] */
+    size_t n_levels;
+    const uint64_t *runs; /* [n_runs][2] */
+    size_t n_runs;
+    uint64_t on_words, pre_words;
+    const uint64_t *wit;
+    size_t n_wit;
+    const uint64_t *sup_in, *sup_corr, *sup_rec;
+    size_t n_in, n_corr, n_rec;
+    uint32_t sup_r, reserved;
+    size_t n_ssa, n_mask_rows;
+    uint64_t *wmask, *masks, *v, *wcorr, *on, *pre;
+    int32_t *err;
+} rv_hook_z64f_run_args;
+int rv_hook_z64_fused_run(rv_ctx *ctx, const rv_hook_z64f_run_args *args);
 /* The transcript-hash kernels (BLAKE3 chunk kernels, trees, the incremental tree, the digest join), one production launch at a time
  * on caller-supplied data (tests/test_gpu_b3_kernels.py, reference tests/b3_ref.py).  Kernel numbers -- chunk kernels: 1 a repetition
  * per lane, 2 a quad word per lane, 3 a chunk per wavefront (rows of 64 quad words, no quad list); tree tops: 1 a lane per repetition,

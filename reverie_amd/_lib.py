@@ -108,6 +108,16 @@ class LinkPiece(C.Structure):  # rv_link_piece
     _fields_ = [(n, C.c_uint64) for n in ("first_op", "n_ops", "n_input_gf2", "n_input_z64")]
 
 
+class Z64FRunArgs(C.Structure):  # rv_hook_z64f_run_args
+    _fields_ = [("seeds", C.c_void_p), ("omit", C.c_void_p), ("R", C.c_uint32), ("key_path", C.c_uint32), ("first_block", C.c_uint64),
+                ("qg0", C.c_uint32), ("qgn", C.c_uint32), ("gates", C.c_void_p), ("n_gates", C.c_size_t), ("levels", C.c_void_p),
+                ("n_levels", C.c_size_t), ("runs", C.c_void_p), ("n_runs", C.c_size_t), ("on_words", C.c_uint64), ("pre_words", C.c_uint64),
+                ("wit", C.c_void_p), ("n_wit", C.c_size_t), ("sup_in", C.c_void_p), ("sup_corr", C.c_void_p), ("sup_rec", C.c_void_p),
+                ("n_in", C.c_size_t), ("n_corr", C.c_size_t), ("n_rec", C.c_size_t), ("sup_r", C.c_uint32), ("reserved", C.c_uint32),
+                ("n_ssa", C.c_size_t), ("n_mask_rows", C.c_size_t), ("wmask", C.c_void_p), ("masks", C.c_void_p), ("v", C.c_void_p),
+                ("wcorr", C.c_void_p), ("on", C.c_void_p), ("pre", C.c_void_p), ("err", C.c_void_p)]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8), ("calls", C.c_uint64)]
 
@@ -150,7 +160,7 @@ SYMBOLS = [
     "rv_hook_stream_traffic", "rv_hook_stream_verify_device_paths", "rv_hook_stream_wit_sums",
     "rv_hook_extract_bits", "rv_hook_extract_from_bits", "rv_hook_pack_corr_all", "rv_hook_unpack_bits", "rv_hook_extract64", "rv_hook_unpack64",
     "rv_hook_compile_levels", "rv_hook_circuit_levels", "rv_hook_interp_launches",
-    "rv_hook_interp64_launches", "rv_hook_z64_fused_grid", "rv_hook_z64_fused_levels",
+    "rv_hook_interp64_launches", "rv_hook_z64_fused_grid", "rv_hook_z64_fused_levels", "rv_hook_z64_fused_gates", "rv_hook_z64_fused_run",
     "rv_ops_compact_wires", "rv_ops_compact_wires_device",
     "rv_compactor_begin", "rv_compactor_scan", "rv_compactor_scan_end", "rv_compactor_feed", "rv_compactor_rewind", "rv_compactor_get_info",
     "rv_compactor_destroy",
@@ -250,6 +260,9 @@ ARGTYPES = {
     "rv_hook_interp64_launches": [_P, C.c_int],
     "rv_hook_z64_fused_grid": [C.c_uint32] * 6 + [C.POINTER(C.c_uint32)],
     "rv_hook_z64_fused_levels": [_P, _Z, _Z, _Z, C.c_uint32, _P, _Z, C.POINTER(C.c_size_t), C.POINTER(C.c_int)],
+    "rv_hook_z64_fused_gates": [_P, _Z, _Z, _Z, C.c_uint32, _P, _Z, C.POINTER(C.c_size_t), _P, _Z, C.POINTER(C.c_size_t), _P, _Z,
+                                C.POINTER(C.c_size_t), C.POINTER(C.c_int), _P],
+    "rv_hook_z64_fused_run": [_P, C.POINTER(Z64FRunArgs)],
     # wire indices compacted by liveness
     "rv_ops_compact_wires": [_P, _Z, _Z, _Z, _P, C.POINTER(CompactInfo)],
     "rv_ops_compact_wires_device": [_P, _P, _Z, _Z, _Z, _P, C.POINTER(CompactInfo)],

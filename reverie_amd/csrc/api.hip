@@ -1644,6 +1644,7 @@ extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
 #include "stream.inc"
 #include "hooks_b3.inc"
 #include "hooks_open.inc"
+#include "hooks_z64f.inc"
 #include "comm.inc"
 #include "eval.inc"
 #include "eval_stream.inc"

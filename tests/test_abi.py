@@ -29,7 +29,8 @@ def test_header_symbols_exported(L):
     hdr = open(os.path.join(ROOT, "include", "reverie_amd.h")).read()
     declared = set(re.findall(r"\b(rv_[a-z0-9_]+)\s*\(", hdr))
     assert declared == set(_lib.SYMBOLS)
-    assert {"rv_hook_interp64_launches", "rv_hook_z64_fused_grid", "rv_hook_z64_fused_levels"} <= declared  # (test hooks: no ABI bump)
+    assert {"rv_hook_interp64_launches", "rv_hook_z64_fused_grid", "rv_hook_z64_fused_levels", "rv_hook_z64_fused_gates",
+            "rv_hook_z64_fused_run"} <= declared  # (test hooks: no ABI bump)
     for name in declared:
         assert getattr(L, name) is not None
     assert L.rv_abi_version() == 8

@@ -4,7 +4,9 @@ legal counter 2^24 - 1, with and without keep words, and through both key setups
 
 rv_hook_maskgen returns the device rows untouched; the reference builds them from the oracle's keystream and the definition of the
 layout (tests/test_maskgen_ref_host.py ties it to the oracle's share generators and the golden shares).  Not reached from here:
-k_z64_fused, which runs the same first rounds but has no launch without a gate list (tests/test_gpu_z64_fused.py)."""
+k_z64_fused, which runs the same first rounds inside another kernel and has no launch without a gate list.  Its cipher is pinned at the
+same windows, and at every carry into counter bits 16..23, by tests/test_gpu_z64_fused_level.py (rv_hook_z64_fused_run: Mul and Input
+levels at any first_block, against tests/z64f_ref.py, which takes its fresh masks from this file's reference)."""
 import ctypes as C
 import functools
 

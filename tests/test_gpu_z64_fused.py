@@ -5,14 +5,17 @@ DomainZ64::batches_to_shares (src/algebra/z64/domain.rs:64-83), ProverTranscript
 
 Counter coverage.  k_z64_fused runs the cipher's first rounds (rounds_0_to_9) at CTR block first_block + (m >> 1) of a Mul's mask
 pair m, and it has no launch without a gate list, so tests/test_gpu_maskgen.py (which pins the stand-alone generators at every counter
-byte and at the last legal counter 2^24 - 1) does not reach it: these whole proofs are its only check.  A program's Z64 cipher
-blocks number (Inputs + 2 Muls + 1) // 2.  The largest circuit here (layered_z64, 64 Inputs, 20 000 Muls) ends at block 20 031, the
-others at 12 031, 9 000, 3 511, 2 531, 1 531, 731, 531 and below; the random programs have 19 to 469 Muls (29 to 479 blocks).  So
-the carry of counter byte 15 into byte 14 (block 255 -> 256) is crossed by most of them, but counter byte 13 stays 0 everywhere in
-this file: blocks from 65 536 up (32 768 Muls) are reached through this kernel only by the 10^5-Mul proof of
+byte and at the last legal counter 2^24 - 1) does not reach it.  A program's Z64 cipher blocks number (Inputs + 2 Muls + 1) // 2.
+The largest circuit here (layered_z64, 64 Inputs, 20 000 Muls) ends at block 20 031, the others at 12 031, 9 000, 3 511, 2 531,
+1 531, 731, 531 and below; the random programs have 19 to 469 Muls (29 to 479 blocks).  So the carry of counter byte 15 into byte 14
+(block 255 -> 256) is crossed by most of them, but counter byte 13 stays 0 everywhere in this file, and whole proofs always start at
+first_block = 0: through them, blocks from 65 536 up (32 768 Muls) are reached only by the 10^5-Mul proof of
 tests/test_gpu_parity.py::test_z64_mid_size_vs_oracle_and_full_size_round_trip (against the oracle) and its 10^6-Mul round trip
-(prover against verifier only), and the last legal counter by nothing.  (Counter bytes 13 and up are out of reach of small
-circuits: they need 65 536 Mul gates or more.)
+(prover against verifier only).  The counters beyond are covered launch by launch instead: tests/test_gpu_z64_fused_level.py runs the
+production launcher on hand-made Mul and Input levels at any first_block (rv_hook_z64_fused_run) against tests/z64f_ref.py --
+test_counter_windows at blocks 0, 250, 65 530 and across every step 2^k - 1 -> 2^k for k = 16..23, test_last_counter_and_one_past on
+the last legal counter 2^24 - 1 and its refusal one block further, test_chain_vs_oracle_and_proof_commitment a whole program from a
+window that crosses 2^17 -- prover and verifier, at every row width of the kernel.
 
 Level shapes.  The circuits here come from generators that do not control what a level holds (circuits.layered_z64: about half Mul,
 half Add per layer; random_z64).  tests/test_gpu_level_classes64.py builds levels class by class and value by value instead -- every
