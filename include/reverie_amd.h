@@ -1283,6 +1283,76 @@ void rv_link_plan_destroy(rv_link_plan *plan);
 /* out[0] = records per workgroup of the emit kernel, out[1] = items per workgroup of the scans (the sizes the tests go around) */
 int rv_hook_link_tiles(uint32_t out[2]);
 
+/* ---- ops no assertion or output depends on, dropped ------------------------------
+ * A statement uses part of what its function blocks compute: an AES block of which a few output bytes are asserted, an adder whose
+ * sum bits nobody reads, whatever a circuit compiler left behind.  A dead op is not free: a dead Mul is a correction and a broadcast
+ * per repetition in the proof, a dead B2A the 442 GF(2) steps it expands into, a dead Random a mask.  These calls drop them.
+ *
+ * VALUES AND READS are those of the wire compaction above: every op with a destination defines a value on (domain, dst); a read
+ * refers to the last value defined on its index before the reading op, and to no value (the zero wire) where no op wrote the index.
+ * B2A defines a Z64 value and reads the 64 GF(2) indices a .. a + 63.  Nothing is pinned here: every GF(2) write is a writer like any
+ * other, B2A ranges included.
+ * ROOTS: every AssertZero; every Input of both domains (witness order and witness length are unchanged); every SizeHint (it stays in
+ * place); and, for every index in the caller's two output lists (GF(2) and Z64; both may be empty, an index may repeat), the value
+ * that is on that index at the end of the list -- so a function block without assertions can be pruned against its outputs.  An
+ * output index no op writes names no value.
+ * KEPT: an op is kept if it is a root, or if it defines a value that a kept op reads or that an output names.  Every other op is
+ * dropped.  The output is the kept records in list order, byte for byte as they were: nothing is renumbered, the wire counts stay
+ * valid as they are.  The kept set is unique (the least set closed under the rule), so the order of work cannot change it; pruning a
+ * pruned list with the same outputs changes nothing.  Not done: constant folding, copy propagation, common subexpressions, dropping
+ * unread Inputs (that would change the witness format).
+ *
+ * THE PROOF OF A PRUNED LIST IS THE PROOF OF THAT LIST -- byte for byte the reference's proof of the pruned program for the same
+ * seeds -- and NOT the proof of the original: unlike the wire compaction this changes proof bytes; that is its purpose.  So prover
+ * and verifier both prune, with the same output lists, or the pruned program is the file that is shipped.  Final wire values change
+ * as well (RV_COMPILE_KEEP_WIRES, rv_evaluate*): a dropped op's destination keeps whatever was there before.
+ *
+ * ERRORS: the list is validated as rv_ops_compact_wires validates it and the code is that of the first bad op in op order; then an
+ * output index at or above the final wire count of its domain (the stated count, raised by every SizeHint) is RV_E_ARG.  Nothing is
+ * written then.
+ *
+ * THE CALLS: out has room for cap records; *n_out receives the number kept.  out == NULL only counts (*n_out and the info: "what
+ * would it save"); cap is not looked at then.  cap below the number kept is RV_E_ARG and nothing is written.  old_index (may be
+ * NULL; room for cap entries) receives, for every kept record, the op's index in the old list, so that results such as the first
+ * failing AssertZero can be mapped back.  rv_ops_prune may write in place (out == ops; any other overlap is RV_E_ARG).
+ * n_out and info may be NULL. */
+typedef struct rv_prune_info {
+    uint64_t n_kept, n_dropped;
+    /* the dropped ops by class */
+    uint64_t dropped_gf2_mul, dropped_z64_mul, dropped_b2a, dropped_gf2_random, dropped_z64_random;
+    uint64_t dropped_gf2_other, dropped_z64_other; /* Add, AddConst, Sub, SubConst, MulConst, Const */
+    /* Inputs that were kept although no kept op reads them and no output names them */
+    uint64_t unread_gf2_inputs, unread_z64_inputs;
+    uint32_t device_rounds; /* frontier layers the device call peeled (0 from the host call) */
+    uint32_t on_device;     /* 1: the device call finished on the GPU (0 from the host call, and from the fall-back) */
+} rv_prune_info;            /* 96 bytes */
+/* host only, no GPU: the backward sweep -- the definition */
+int rv_ops_prune(const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const uint32_t *outputs_gf2, size_t n_outputs_gf2,
+                 const uint32_t *outputs_z64, size_t n_outputs_z64, rv_op *out, size_t cap, size_t *n_out, uint32_t *old_index,
+                 rv_prune_info *info);
+/* The same records, old_index and info from kernels on the context's GPU, for a list in device memory.  d_ops, d_out (cap records)
+ * and d_old_index (cap entries; 4-byte aligned) lie in the memory of the context's device, with rv_ops_compact_wires_device's
+ * conventions (8-byte aligned records inside one allocation, RV_E_ARG otherwise and before any launch; 2^31 ops or more, or a wire
+ * count in force of 2^31 or more: RV_E_UNSUPPORTED); the two output lists are host memory (they are copied).  ANY overlap of d_out and
+ * d_ops is RV_E_ARG before a launch.  Instead of the sweep the kernels count the readers of every value and peel: the first frontier is
+ * every value that is no root and has no reader; a round drops each frontier op and takes one from the count of every value it read;
+ * values that reach 0 form the next frontier.  Rounds are bounded by the longest chain inside the dead cones, not by the depth of
+ * the circuit, and a list with nothing dead costs none.  info->device_rounds counts the frontier layers.  After RV_PRUNE_MAX_ROUNDS
+ * layers (environment, read at call time; default 65536) with the frontier not yet empty the call gives up on the device: it copies
+ * the list down, runs rv_ops_prune, uploads the result and reports on_device = 0 (device_rounds: the layers peeled until then).
+ * The bytes are the same.  Work memory (about 33 bytes per op for a list of one domain, 49 for a mixed one) comes from the context
+ * arena and goes back before the call returns.  The call runs on the context's stream and synchronises it. */
+int rv_ops_prune_device(rv_ctx *ctx, const rv_op *d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const uint32_t *outputs_gf2,
+                        size_t n_outputs_gf2, const uint32_t *outputs_z64, size_t n_outputs_z64, rv_op *d_out, size_t cap, size_t *n_out,
+                        uint32_t *d_old_index, rv_prune_info *info);
+/* out[0] = threads per workgroup of the peeling kernels, out[1] = the widest frontier one workgroup peels round after round inside
+ * one launch (the solo limit), out[2] = rounds between two looks of the host at the device words, out[3] = records per workgroup of
+ * the emit kernel, out[4] = RV_PRUNE_MAX_ROUNDS as the next call would read it */
+int rv_hook_prune_limits(uint32_t out[5]);
+/* launches of this process so far: out[0] = emit kernels that wrote records, out[1] = count-only passes, out[2] = peeling launches
+ * (solo and wide together), out[3] = fall-backs to the host sweep */
+int rv_hook_prune_launches(uint64_t out[4]);
+
 /* ---- parity-test hooks: each mirrors one reference function so tests can compare the
  * HIP path with the oracle piecewise ---- */
 /* PRG::new + gen (crypto/prg.rs:16-37) on the GPU: n_keys keys, blocks [first, first+n_blocks) each */

@@ -123,6 +123,19 @@ def compact_program(prog, wc):
     return out, new_wc
 
 
+def prune_program(prog, wc, outputs_gf2=()):
+    """--prune: the program without the ops no assertion (and none of outputs_gf2) depends on (rv_ops_prune, on the host; --parser
+    device's op tensor by rv_ops_prune_device, where it lies); the wire counts stay.  The op counts before and after go to stderr.
+    The proof of the pruned program is not the proof of the original: prover and verifier both pass --prune."""
+    from .prune import prune_ops
+
+    out, info, _ = prune_ops(prog, wc, outputs_gf2=outputs_gf2)
+    print("prune: %d ops -> %d (dropped: %d GF(2) Mul, %d Z64 Mul, %d B2A, %d Random, %d other)"
+          % (info["n_kept"] + info["n_dropped"], info["n_kept"], info["dropped_gf2_mul"], info["dropped_z64_mul"], info["dropped_b2a"],
+             info["dropped_gf2_random"] + info["dropped_z64_random"], info["dropped_gf2_other"] + info["dropped_z64_other"]), file=sys.stderr)
+    return out, wc
+
+
 def compact_windows(wc, pieces):
     """--compact-windows: the pieces of a source that is read in windows, renumbered by liveness in windows (compact.compact_pieces:
     the scan pass runs here, every later pass reads the source again) and the new wire counts; --compact-wires' line goes to stderr"""
@@ -198,7 +211,8 @@ def evaluate_gpu(prog, wc, witness, compiler="host"):
         raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (r.first_failed_op, r.n_failed))
 
 
-def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_path=None, compact=False, windowed=True, in_windows=False):
+def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_path=None, compact=False, windowed=True, in_windows=False,
+                  prune=False):
     """What a stream needs of a program file: (wire counts, pieces) -- pieces() returns a fresh iterator of (ops, Input counts or
     None) for every pass (`reverie_amd.stream.*_streaming_pieces`).
       rvops                              read through a memory map, STREAM_FEED_OPS records per piece; the wire counts come from one
@@ -209,18 +223,20 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
                                          come from the header (bristol.wire_counts): no scan pass.  Device memory: one window
       mcircuit-bincode with the host parser, Bristol otherwise, and windowed=False: parsed whole, one piece
     compact (--compact-wires): the whole list is renumbered by liveness first, then fed, under the new counts.
+    prune (--prune): the source is read whole too, and the ops no assertion depends on are dropped first (`prune_program`).
     in_windows (--compact-windows; one of the three windowed sources above): the windows stay, and the pieces are renumbered by
     liveness window by window (`compact_windows`)."""
     finish = compact_windows if in_windows else (lambda wc, pieces: (wc, pieces))
+    whole = compact or prune
     if fmt == "auto":
         fmt = "rvops" if program_path.endswith(".rvops") else "bristol"
-    if fmt == "mcircuit-bincode" and parser == "device" and windowed and not compact:
+    if fmt == "mcircuit-bincode" and parser == "device" and windowed and not whole:
         from . import program_file
 
         window = (DEFAULT_WINDOW_MB if window_mb is None else int(window_mb)) << 20
         wc = program_file.scan_device(program_path, window)["wire_counts"]
         return finish(wc, lambda: program_file.iter_device(program_path, window))
-    if fmt == "bristol" and parser == "device" and windowed and window_mb is not None and not compact:
+    if fmt == "bristol" and parser == "device" and windowed and window_mb is not None and not whole:
         from . import bristol
 
         exp = parse_witness(open(expected_path, "rb").read()) if expected_path else None
@@ -228,11 +244,15 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
         return finish(wc, lambda: bristol.iter_device(program_path, int(window_mb) << 20, exp))
     if parser == "device" and fmt in ("bristol", "mcircuit-bincode"):  # the op tensor is the one piece (compacted where it lies)
         prog, wc = load_program_device(program_path, expected_path, fmt)
+        if prune:
+            prog, wc = prune_program(prog, wc)
         if compact:
             prog, wc = compact_program(prog, wc)
         return wc, lambda: iter([(prog, None)])
     if fmt != "rvops":
         prog, wc = load_program(program_path, fmt, expected_path)
+        if prune:
+            prog, wc = prune_program(prog, wc)
         n = len(prog)
         if not compact:
             return wc, lambda: iter([(prog, None)])
@@ -249,13 +269,16 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
             z, g = largest_wires(np.asarray(prog[at:at + STREAM_FEED_OPS]))
             z64, gf2 = max(z64, z), max(gf2, g)
         wc = (z64, gf2)
+        if prune:
+            prog, wc = prune_program(np.asarray(prog), wc)
+            n = len(prog)
     if compact:
         prog, wc = compact_program(np.asarray(prog), wc)
     return finish(wc, lambda: ((np.asarray(prog[at:at + STREAM_FEED_OPS]), None) for at in range(0, max(n, 1), STREAM_FEED_OPS)))
 
 
 def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, device_compile=False, device_z64=False, device_b2a=False,
-                    compact=False, parser="host", window_mb=None, in_windows=False):
+                    compact=False, parser="host", window_mb=None, in_windows=False, prune=False):
     """`oneshot --evaluator stream`: the program evaluated in pieces with bounded device memory (rv_eval_stream_*), on the GPU like
     --evaluator gpu and with the same outcome.  An rvops file is read through a memory map, piece by piece; its wire counts come from
     one pass over the mapping.  window_mb (--window-mb, with --parser device): an mcircuit-bincode file is read in windows of that
@@ -266,7 +289,8 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
 
     source = _is_wit_source(witness)  # (--witness-window-mb: the bits are read as the pieces ask for them)
     wit = witness if source or hasattr(witness, "data_ptr") else np.ascontiguousarray(np.asarray(witness, dtype=np.uint8))
-    wc, pieces = stream_pieces(program_path, fmt, parser, window_mb, expected_path, compact, windowed=window_mb is not None, in_windows=in_windows)
+    wc, pieces = stream_pieces(program_path, fmt, parser, window_mb, expected_path, compact, windowed=window_mb is not None, in_windows=in_windows,
+                              prune=prune)
     se = StreamingEvaluator(wc, 1, max_chunk_ops, device_compile=device_compile, **({"device_z64": True} if device_z64 else {}),
                             **({"device_b2a": True} if device_b2a else {}))
     try:
@@ -304,7 +328,7 @@ def convert_source(a, fmt, device_parser: bool):
 
     path, exp_path = a.program_path, a.expected_outputs_path
     exp = parse_witness(open(exp_path, "rb").read()) if exp_path else None
-    windowed = a.window_mb is not None and device_parser and not a.compact_wires
+    windowed = a.window_mb is not None and device_parser and not a.compact_wires and not a.prune
     d = {"n_inputs": None, "n_outputs": 0, "prog": None, "pieces": None}
     head = bristol.head_info(path) if fmt == "bristol" else None
     if head is not None and exp is None:
@@ -343,6 +367,10 @@ def convert_source(a, fmt, device_parser: bool):
         else:
             d["prog"] = np.asarray(prog)
     d["wc_out"] = d["wc"]
+    if a.prune:  # (a Bristol program without assertions is pruned against its outputs: its last n_outputs wires)
+        outs = range(head["n_wires"] - d["n_outputs"], head["n_wires"]) if head is not None and d["n_outputs"] else ()
+        d["prog"], _ = prune_program(d["prog"], d["wc"], outs)
+        d["n_ops"] = len(d["prog"])
     if a.compact_wires:
         d["prog"], d["wc_out"] = compact_program(d["prog"], d["wc"])
     elif a.compact_windows:
@@ -410,7 +438,7 @@ def run_streamed(a, ap, device_parser: bool) -> int:
     if a.strict and a.reference_compat:
         ap.error("--strict and --reference-compat exclude each other")
     wc, pieces = stream_pieces(a.program_path, a.program_format, "device" if device_parser else "host", a.window_mb, a.expected_outputs_path,
-                               a.compact_wires, in_windows=a.compact_windows)
+                               a.compact_wires, in_windows=a.compact_windows, prune=a.prune)
     kw = dict(max_chunk_ops=a.max_chunk_ops, device_compile=a.compiler != "host", device_z64=a.compiler in ("device-z64", "device-b2a"),
               device_b2a=a.compiler == "device-b2a")
     if a.operation in ("prove", "oneshot-zk"):
@@ -495,6 +523,11 @@ def build_parser():
                     help="prove / verify / oneshot-zk and oneshot --evaluator stream: renumber the program's wires by liveness first "
                          "(rv_ops_compact_wires), so that an SSA-numbered program needs a wire per live value instead of one per gate; "
                          "the proof bytes and the outcome are the same, the wire counts before and after are printed on stderr")
+    ap.add_argument("--prune", action="store_true",
+                    help="prove / verify / oneshot-zk / oneshot / convert, for a source that is read whole: drop the ops no assertion depends "
+                         "on first (rv_ops_prune; with --parser device rv_ops_prune_device, where the list lies), before --compact-wires; the "
+                         "op counts before and after are printed on stderr.  The proof is the proof of the pruned program, NOT of the original: "
+                         "prove and verify must both be given --prune.  Refused with --window-mb and --compact-windows (a source read in windows)")
     ap.add_argument("--compact-windows", action="store_true",
                     help="--stream, or oneshot --evaluator stream, on a source that is read in windows (an rvops file; with --parser device "
                          "an mcircuit-bincode file, or a Bristol file with --window-mb): renumber the wires by liveness window by window "
@@ -551,6 +584,8 @@ def main(argv=None) -> int:
         ap.error("--stream is for prove / verify / oneshot-zk; oneshot streams with --evaluator stream")
     if a.compact_wires and a.operation == "oneshot" and a.evaluator != "stream":
         ap.error("--compact-wires with --operation oneshot needs --evaluator stream (the other evaluators keep no wire store)")
+    if a.prune and (a.window_mb is not None or a.compact_windows):
+        ap.error("--prune needs a source that is read whole: it cannot be combined with --window-mb or --compact-windows")
     fmt = a.program_format
     if fmt == "auto":
         fmt = "rvops" if a.program_path.endswith(".rvops") else "bristol"
@@ -583,7 +618,7 @@ def main(argv=None) -> int:
                         a.max_chunk_ops, device_compile=a.compiler != "host", **({"device_z64": True} if a.compiler in ("device-z64", "device-b2a") else {}),
                         **({"device_b2a": True} if a.compiler == "device-b2a" else {}), **({"compact": True} if a.compact_wires else {}),
                         **({"parser": "device"} if device_parser else {}), **({"window_mb": a.window_mb} if a.window_mb is not None else {}),
-                        **({"in_windows": True} if a.compact_windows else {}))
+                        **({"in_windows": True} if a.compact_windows else {}), **({"prune": True} if a.prune else {}))
         print("()")
         return 0
     if a.stream:
@@ -592,6 +627,8 @@ def main(argv=None) -> int:
         prog, wc = load_program_device(a.program_path, a.expected_outputs_path, fmt)
     else:
         prog, wc = load_program(a.program_path, a.program_format, a.expected_outputs_path)
+    if a.prune:
+        prog, wc = prune_program(prog, wc)
     if a.compact_wires:
         prog, wc = compact_program(prog, wc)
     if a.operation == "oneshot":

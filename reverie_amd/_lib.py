@@ -108,6 +108,12 @@ class LinkPiece(C.Structure):  # rv_link_piece
     _fields_ = [(n, C.c_uint64) for n in ("first_op", "n_ops", "n_input_gf2", "n_input_z64")]
 
 
+class PruneInfo(C.Structure):  # rv_prune_info
+    _fields_ = [(n, C.c_uint64) for n in ("n_kept", "n_dropped", "dropped_gf2_mul", "dropped_z64_mul", "dropped_b2a", "dropped_gf2_random",
+                                          "dropped_z64_random", "dropped_gf2_other", "dropped_z64_other", "unread_gf2_inputs",
+                                          "unread_z64_inputs")] + [("device_rounds", C.c_uint32), ("on_device", C.c_uint32)]
+
+
 class Z64FRunArgs(C.Structure):  # rv_hook_z64f_run_args
     _fields_ = [("seeds", C.c_void_p), ("omit", C.c_void_p), ("R", C.c_uint32), ("key_path", C.c_uint32), ("first_block", C.c_uint64),
                 ("qg0", C.c_uint32), ("qgn", C.c_uint32), ("gates", C.c_void_p), ("n_gates", C.c_size_t), ("levels", C.c_void_p),
@@ -175,6 +181,7 @@ SYMBOLS = [
     "rv_witness_parse", "rv_witness_write", "rv_witness_parse_device", "rv_hook_witness_text_tiles", "rv_witness_write_device",
     "rv_witness_reader_begin", "rv_witness_reader_feed", "rv_witness_reader_finish", "rv_witness_reader_destroy",
     "rv_link", "rv_link_plan_create", "rv_link_plan_info", "rv_link_plan_emit", "rv_link_plan_destroy", "rv_hook_link_tiles",
+    "rv_ops_prune", "rv_ops_prune_device", "rv_hook_prune_limits", "rv_hook_prune_launches",
     "rv_hook_prove_schedule",
     "rv_hook_b3_plan", "rv_hook_b3_chunks", "rv_hook_b3_pair_small", "rv_hook_b3_pair_big_chunks", "rv_hook_b3_tree", "rv_hook_b3_pair_big_tree",
     "rv_hook_b3_incremental", "rv_hook_b3_join",
@@ -323,6 +330,11 @@ ARGTYPES = {
     "rv_link_plan_emit": [_P, C.c_uint64, C.c_uint64, _P, C.POINTER(LinkPiece)],
     "rv_link_plan_destroy": [_P],
     "rv_hook_link_tiles": [C.POINTER(C.c_uint32)],
+    # dead ops dropped, on the host and on the GPU
+    "rv_ops_prune": [_P, _Z, _Z, _Z, _P, _Z, _P, _Z, _P, _Z, C.POINTER(C.c_size_t), _P, C.POINTER(PruneInfo)],
+    "rv_ops_prune_device": [_P, _P, _Z, _Z, _Z, _P, _Z, _P, _Z, _P, _Z, C.POINTER(C.c_size_t), _P, C.POINTER(PruneInfo)],
+    "rv_hook_prune_limits": [C.POINTER(C.c_uint32)],
+    "rv_hook_prune_launches": [C.POINTER(C.c_uint64)],
     # the transcript-hash kernels (parity hooks)
     "rv_hook_b3_plan": [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)],
     "rv_hook_b3_chunks": [_P, C.c_int, _P, C.c_uint64, C.c_uint32, C.c_uint64, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64,

@@ -34,6 +34,7 @@
 #include "ldsrun.h"
 #include "piece_pipe.h"
 #include "piece_sums.h"
+#include "prune_dev.h"
 #include "verify_dev.h"
 #include "witness_text.h"
 
@@ -1656,3 +1657,4 @@ extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
 #include "bristol_write.inc"
 #include "witness_text.inc"
 #include "link.inc"
+#include "prune.inc"

@@ -69,6 +69,18 @@ class Block:
     def __len__(self) -> int:
         return _device_ops(self.ops, None, "Block")[1] if self.on_device else len(self.ops)
 
+    def pruned(self, ctx: Optional[Context] = None) -> "Block":
+        """The block without the ops its `.outputs` (GF(2) indices) do not depend on (`prune.prune_ops`: assertions, Inputs and what
+        they need stay too): the same ports, wire counts and outputs, so it takes the original's place in a `Netlist`.  A device block
+        is pruned where it lies.  .prune_info: rv_prune_info as a dict.  The linked program is another program: its proof is not the
+        proof of the one linked from the unpruned block."""
+        from .prune import prune_ops
+
+        ops, info, _ = prune_ops(self.ops, self.wire_counts, outputs_gf2=self.outputs, ctx=ctx)
+        b = Block(ops, self.wire_counts, n_ports=self.n_ports, outputs=self.outputs)
+        b.prune_info = info
+        return b
+
 
 class Instance:
     """What `Netlist.add` returns: where instance `index` lies in the global numbering."""

@@ -32,6 +32,10 @@ rv_eval_stream_feed_wdev), with host or device ops alike.  `finish(device=True)`
 torch uint8 GPU tensor and returns a `DeviceProof`; the verifiers take a `DeviceProof` or a uint8 GPU tensor wherever they take proof
 bytes and read it in place (rv_stream_verify_begin_device).  Proofs, answers and values are the same bytes either way.
 
+The whole-list one-shot functions also take `prune` (default False): the ops no assertion depends on are dropped first
+(`prune.prune_ops`), then `compact_wires` runs if asked for, and the stream info (or `info`) receives "prune".  The proof is then the
+proof of the pruned list -- prover and verifier must both pass prune=True; the `*_pieces` functions do not prune.
+
 The one-shot functions take `compact_wires` (default False): the whole op list is first renumbered by liveness (`compact.compact_wires`,
 DESIGN §17) -- on the host for host ops, by kernels for a GPU tensor -- and the stream begins with the new, smaller wire counts, so an
 SSA-numbered list no longer costs a wire-store row per gate.  Proofs and answers are the same bytes; the wire values
@@ -60,11 +64,17 @@ def _ops_ctx(ops, ctx: Optional[Context]) -> Context:
     return _device_ops(ops, ctx, "a stream of device ops")[2] if _is_device_ops(ops) else ctx or Context.default()
 
 
-def _compacted(ops, wire_counts, ctx: Context, wanted: bool):
-    """the op list and wire counts a one-shot call streams, and rv_compact_info (None: compact_wires was not asked for)"""
-    if not wanted:
-        return ops, wire_counts, None
-    return _compact.compact_wires(ops, wire_counts, ctx)
+def _compacted(ops, wire_counts, ctx: Context, wanted: bool, prune: bool = False):
+    """the op list and wire counts a one-shot call streams, and (rv_compact_info, rv_prune_info) -- None where compact_wires / prune
+    was not asked for.  Pruning (against the assertions: a stream has no outputs) comes first, then compaction."""
+    pinfo = cinfo = None
+    if prune:
+        from .prune import prune_ops
+
+        ops, pinfo, _ = prune_ops(ops, wire_counts, ctx=ctx)
+    if wanted:
+        ops, wire_counts, cinfo = _compact.compact_wires(ops, wire_counts, ctx)
+    return ops, wire_counts, (cinfo, pinfo)
 
 
 def _compacted_pieces(pieces, wire_counts, ctx: Optional[Context], wanted: bool):
@@ -79,6 +89,10 @@ def _compacted_pieces(pieces, wire_counts, ctx: Optional[Context], wanted: bool)
 
 
 def _with_compact(info: dict, cinfo) -> dict:
+    """cinfo: rv_compact_info, or _compacted's pair"""
+    cinfo, pinfo = cinfo if isinstance(cinfo, tuple) else (cinfo, None)
+    if pinfo is not None:
+        info["prune"] = pinfo
     if cinfo is not None:
         info["compact"] = cinfo
     return info
@@ -249,14 +263,14 @@ class StreamingProver:
 
 def prove_streaming(ops, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
                     ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                    device_proof: bool = False, compact_wires: bool = False) -> Tuple[Proof, dict]:
+                    device_proof: bool = False, compact_wires: bool = False, prune: bool = False) -> Tuple[Proof, dict]:
     """rv_prove_streaming: both passes over an op array in host memory -> (Proof, stream info).  A torch GPU tensor of ops, witnesses
     that are torch GPU tensors or device_proof=True (-> a DeviceProof): the same through rv_stream_begin / the feeds / the finish.
     compact_wires: the list is renumbered by liveness first and the stream begins with the new counts (the same proof)."""
     _check_device_z64(device_compile, device_z64, device_b2a)
     on_device = _wdev(wit_gf2, wit_z64, ctx, "prove_streaming", batched=False) is not None  # (refuses before a context is made)
     ctx = _ops_ctx(ops, ctx)
-    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune)
     if _is_device_ops(ops) or on_device or device_proof:
         sp = StreamingProver(wire_counts, seeds, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
@@ -328,7 +342,7 @@ class StreamingVerifier:
 
 def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = True, max_chunk_ops: int = 0,
                      ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                     compact_wires: bool = False) -> Tuple[bool, dict]:
+                     compact_wires: bool = False, prune: bool = False) -> Tuple[bool, dict]:
     """rv_verify_streaming: one pass over an op array in host memory -> (ok, stream info).  A torch GPU tensor of ops: the same through
     rv_stream_verify_begin / rv_stream_feed_device / rv_stream_verify_finish.  compact_wires: as in prove_streaming (the same answer)."""
     _check_device_z64(device_compile, device_z64, device_b2a)
@@ -336,7 +350,7 @@ def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = Tr
     if on_device and ctx is None and isinstance(proof, DeviceProof):
         ctx = proof.ctx
     ctx = _ops_ctx(ops, ctx)
-    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune)
     if _is_device_ops(ops) or on_device:
         sv = StreamingVerifier(wire_counts, proof, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
@@ -457,7 +471,7 @@ class StreamingBatchProver:
 
 def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
                           ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                          device_proof: bool = False, compact_wires: bool = False) -> "list[Proof]":
+                          device_proof: bool = False, compact_wires: bool = False, prune: bool = False) -> "list[Proof]":
     """rv_prove_streaming_batch: both passes over an op array in host memory for the witnesses wits_gf2 [B][n] / wits_z64
     [B][m] (B from whichever of the two is 2-D; the other may be []); seeds [B][256][16] or None.  `info` (a dict, optional) receives the stream's figures.
     Witnesses that are torch GPU tensors are read where they lie; device_proof=True returns DeviceProof views of one GPU tensor.
@@ -465,7 +479,7 @@ def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int],
     _check_device_z64(device_compile, device_z64, device_b2a)
     dw = _wdev(wits_gf2, wits_z64, ctx, "prove_streaming_batch", batched=True)  # (refuses before a context is made)
     ctx = _ops_ctx(ops, ctx)
-    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune)
     if info is not None:
         _with_compact(info, cinfo)
     if dw is not None:  # (GPU tensors: [B][n] both, the batch from the descriptor)
@@ -558,7 +572,7 @@ class StreamingBatchVerifier:
 
 def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bool = True, max_chunk_ops: int = 0,
                            ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                           compact_wires: bool = False) -> "list[bool]":
+                           compact_wires: bool = False, prune: bool = False) -> "list[bool]":
     """rv_verify_streaming_batch: one pass over an op array in host memory for every proof -> one bool per proof.
     compact_wires: as in prove_streaming (the same answers; `info` also receives "compact")."""
     _check_device_z64(device_compile, device_z64, device_b2a)
@@ -566,7 +580,7 @@ def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bo
     n = len(proofs)
     if n == 0:
         return []
-    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune)
     if info is not None:
         _with_compact(info, cinfo)
     on_device = any(_device_proof_bytes(p, ctx, "verify_streaming_batch") is not None for p in proofs)
@@ -668,7 +682,7 @@ class StreamingEvaluator:
 
 def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], max_chunk_ops: int = 0, values: bool = False,
                        ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                       compact_wires: bool = False) -> Evaluation:
+                       compact_wires: bool = False, prune: bool = False) -> Evaluation:
     """rv_evaluate_streaming: one op array in host memory, evaluated chunk by chunk with bounded device memory.  wits_gf2 /
     wits_z64: [B][n] (1-D for one witness; the batch is len(wits_gf2)).  Returns the array-shaped Evaluation of
     Circuit.evaluate_batch; `info` (a dict, optional) receives the stream's figures.  compact_wires: the list is renumbered by
@@ -678,7 +692,7 @@ def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], ma
     dims = [t.dim() for t in (wits_gf2, wits_z64) if hasattr(t, "data_ptr")]
     dw = _wdev(wits_gf2, wits_z64, ctx, "evaluate_streaming", batched=bool(dims) and max(dims) == 2)  # (refuses before a context is made)
     ctx = _ops_ctx(ops, ctx)
-    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune)
     if info is not None:
         _with_compact(info, cinfo)
     if dw is not None:
