@@ -1353,6 +1353,79 @@ int rv_hook_prune_limits(uint32_t out[5]);
  * (solo and wide together), out[3] = fall-backs to the host sweep */
 int rv_hook_prune_launches(uint64_t out[4]);
 
+/* ---- the same pruning for a list that passes through in windows ------------------
+ * rv_pruner_* gives, for a list that arrives in feeds, exactly rv_ops_prune's kept set, records, old_index and class counts, for
+ * every list and every way of cutting every pass.  Values, reads, roots and the kept rule are the ones above.  Pruning is a backward
+ * data-flow problem, so the MARK pass takes the windows from the last to the first; what one window tells the one before it is one
+ * NEEDED byte per wire index and domain (sized by the final wire counts): "a kept op behind this point reads the value now on this
+ * index".  Before the first mark feed it is 1 exactly on the indices of the two output lists.
+ *
+ * THE WINDOW STEP, for a window [lo, hi) and the needed table N as it stands at hi:
+ *   1. every read of the window is resolved to the last writer of its index inside the window and before the reader; a read with no
+ *      such writer ESCAPES the window;
+ *   2. one count per resolved read on the value it names, and one more on the window's LAST writer of index w when N[w] is set;
+ *   3. the peeling of rv_ops_prune_device: the first frontier is every defining op that is no root and has count 0, and so on;
+ *   4. unread Inputs are the Input ops whose count stayed 0;
+ *   5. KILL, THEN GEN, in that order: N[w] = 0 for every index w that any op of the window writes, kept or dropped; then N[w] = 1
+ *      for every escaping read of every kept op (a kept B2A may gen up to 64 indices).  A window that holds "kept op reads w; later
+ *      op writes w" leaves N[w] = 1;
+ *   6. the window's keep flags go to one mark byte per op, at the ops' ordinals.
+ *
+ * THE CALLS:  begin -> scan* -> scan_end -> mark* (windows LAST to FIRST, each window's ops in list order) -> mark_end
+ *             -> feed* [-> rewind -> feed*]... -> destroy.   The three passes may be cut differently; feeds of 0 and 1 ops are allowed
+ * everywhere.  `ops` is host memory (uploaded for the call) or, with ops_on_device, memory of the context's device with
+ * rv_ops_prune_device's conventions.
+ *   begin     copies the two output lists.
+ *   scan      the forward pass: it validates as rv_ops_prune does, the counts in force carried from feed to feed (a backward pass
+ *             cannot know the count in force at an op), and refuses a bad list with the code of the first bad op in op order, at
+ *             the feed that holds it; it counts the ops and sums the position-keyed digest rv_compactor_* uses.  It writes nothing.
+ *   scan_end  fixes the list's length and the final counts; an output index at or above its domain's final count is RV_E_ARG; the
+ *             needed tables and the marks are allocated.
+ *   mark      a feed covers the ordinals [pos - n_ops, pos), pos starting at the list's length; more ops than are left is RV_E_ARG.
+ *             Every index is checked against the final counts before it is used as an address; a record that fails is RV_E_ARG
+ *             (not the scanned list) and nothing is addressed by it.  *n_kept_here (may be NULL) receives the feed's kept ops.
+ *   mark_end  RV_E_ARG if the pass stopped short of ordinal 0 or its digest is not the scan's.  The info's class counts are
+ *             rv_ops_prune's; device_rounds is the SUM of the layers peeled over all mark feeds -- for one feed that holds the whole
+ *             list rv_ops_prune_device's figure, otherwise it depends on the cuts; on_device is 0 if any feed fell back (a mark feed
+ *             whose peeling reaches RV_PRUNE_MAX_ROUNDS layers is copied down with the two tables, stepped on the host and its marks
+ *             and tables uploaded: the bytes are the same, the other feeds stay on the device).
+ *   feed      a forward pass: the feed's kept records go to d_out (cap records), their ordinals IN THE WHOLE OLD LIST to d_old_index
+ *             (cap entries; may be NULL), the number to *n_out.  cap >= n_ops always suffices; a cap below the kept count is RV_E_ARG
+ *             with nothing written.  Any overlap of d_out with a device `ops` is RV_E_ARG before a launch.  The last feed of a pass
+ *             answers RV_E_ARG when the pass's digest is not the scan's.
+ *   rewind    after a complete emit pass: the next feed is the list's first again.  RV_E_ARG after a short pass.
+ * A call out of order is RV_E_ARG and leaves the object as it was.  2^31 ops or more in all, or a final wire count of 2^31 or more:
+ * RV_E_UNSUPPORTED.  After a validation code, RV_E_UNSUPPORTED, RV_E_NOMEM or RV_E_DEVICE only destroy is accepted.
+ * MEMORY, from the context arena.  Held between calls (state_bytes): one byte per wire index of both domains (final counts), one mark
+ * byte per op, and the words.  Per feed, given back before the call returns (peak_feed_bytes: the largest so far): what
+ * rv_ops_prune_device takes for a list of the feed's length, plus 24 bytes per op of an uploaded host feed. */
+typedef struct rv_pruner rv_pruner;
+typedef struct rv_pruner_info {
+    uint64_t total_ops;       /* the list's length (before scan_end: the ops scanned so far) */
+    uint64_t n_kept;          /* kept ops marked so far (after mark_end: of the list) */
+    uint64_t state_bytes;     /* device memory held between calls */
+    uint64_t peak_feed_bytes; /* the largest work memory of one call so far, an uploaded feed included */
+    uint64_t mark_feeds;      /* mark feeds that held an op */
+    uint64_t host_feeds;      /* of these: stepped on the host (the fall-back) */
+} rv_pruner_info;             /* 48 bytes */
+int rv_pruner_begin(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, const uint32_t *outputs_gf2, size_t n_outputs_gf2,
+                    const uint32_t *outputs_z64, size_t n_outputs_z64, rv_pruner **out);
+int rv_pruner_scan(rv_pruner *p, const rv_op *ops, size_t n_ops, int ops_on_device);
+int rv_pruner_scan_end(rv_pruner *p);
+int rv_pruner_mark(rv_pruner *p, const rv_op *ops, size_t n_ops, int ops_on_device, size_t *n_kept_here);
+int rv_pruner_mark_end(rv_pruner *p, rv_prune_info *info /* may be NULL */);
+int rv_pruner_feed(rv_pruner *p, const rv_op *ops, size_t n_ops, int ops_on_device, rv_op *d_out, size_t cap, size_t *n_out,
+                   uint32_t *d_old_index);
+int rv_pruner_rewind(rv_pruner *p);
+int rv_pruner_get_info(const rv_pruner *p, rv_pruner_info *info);
+void rv_pruner_destroy(rv_pruner *p);
+/* host only, no GPU: the three passes over the windows [0, cuts[0]), [cuts[0], cuts[1]), .. [cuts[n_cuts - 1], n_ops) -- the window
+ * step's definition in C.  cuts: n_cuts non-decreasing positions, none above n_ops (RV_E_ARG otherwise).  Everything else, and every
+ * byte of the result, is rv_ops_prune's (which is this call without a cut). */
+int rv_ops_prune_windows_host(const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const uint32_t *outputs_gf2,
+                              size_t n_outputs_gf2, const uint32_t *outputs_z64, size_t n_outputs_z64, const size_t *cuts, size_t n_cuts,
+                              rv_op *out, size_t cap, size_t *n_out, uint32_t *old_index, rv_prune_info *info);
+
 /* ---- parity-test hooks: each mirrors one reference function so tests can compare the
  * HIP path with the oracle piecewise ---- */
 /* PRG::new + gen (crypto/prg.rs:16-37) on the GPU: n_keys keys, blocks [first, first+n_blocks) each */

@@ -136,6 +136,19 @@ def prune_program(prog, wc, outputs_gf2=()):
     return out, wc
 
 
+def prune_windows(wc, pieces):
+    """--prune-windows: the pieces of an rvops file (`prune.window_pieces` over its memory map: both directions), without the ops no
+    assertion depends on (prune.prune_pieces: the scan pass and the backward mark pass run here, every later pass reads the source
+    again); --prune's line goes to stderr.  The wire counts stay.  -> (pieces, the ops kept)"""
+    from .prune import prune_pieces
+
+    pieces2, info = prune_pieces(pieces, wc)
+    print("prune: %d ops -> %d (dropped: %d GF(2) Mul, %d Z64 Mul, %d B2A, %d Random, %d other)"
+          % (info["n_kept"] + info["n_dropped"], info["n_kept"], info["dropped_gf2_mul"], info["dropped_z64_mul"], info["dropped_b2a"],
+             info["dropped_gf2_random"] + info["dropped_z64_random"], info["dropped_gf2_other"] + info["dropped_z64_other"]), file=sys.stderr)
+    return pieces2, info["n_kept"]
+
+
 def compact_windows(wc, pieces):
     """--compact-windows: the pieces of a source that is read in windows, renumbered by liveness in windows (compact.compact_pieces:
     the scan pass runs here, every later pass reads the source again) and the new wire counts; --compact-wires' line goes to stderr"""
@@ -143,7 +156,16 @@ def compact_windows(wc, pieces):
 
     new_wc, pieces2, _ = compact_pieces(pieces, wc)
     print("compact-wires: wire counts (z64, gf2) %s -> %s" % (tuple(int(x) for x in wc), new_wc), file=sys.stderr)
+    if hasattr(pieces, "pruner"):  # (--prune-windows underneath: `close_pruner` finds it)
+        pieces2.pruner = pieces.pruner
     return new_wc, pieces2
+
+
+def close_pruner(pieces):
+    """after the last pass over `pieces`: --prune-windows' pruner gives its marks and needed tables back to the device"""
+    pruner = getattr(pieces, "pruner", None)
+    if pruner is not None:
+        pruner.close()
 
 
 def evaluate_clear(prog, witness):
@@ -212,7 +234,7 @@ def evaluate_gpu(prog, wc, witness, compiler="host"):
 
 
 def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_path=None, compact=False, windowed=True, in_windows=False,
-                  prune=False):
+                  prune=False, prune_in_windows=False):
     """What a stream needs of a program file: (wire counts, pieces) -- pieces() returns a fresh iterator of (ops, Input counts or
     None) for every pass (`reverie_amd.stream.*_streaming_pieces`).
       rvops                              read through a memory map, STREAM_FEED_OPS records per piece; the wire counts come from one
@@ -225,7 +247,9 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
     compact (--compact-wires): the whole list is renumbered by liveness first, then fed, under the new counts.
     prune (--prune): the source is read whole too, and the ops no assertion depends on are dropped first (`prune_program`).
     in_windows (--compact-windows; one of the three windowed sources above): the windows stay, and the pieces are renumbered by
-    liveness window by window (`compact_windows`)."""
+    liveness window by window (`compact_windows`).
+    prune_in_windows (--prune-windows; an rvops file): the windows stay, and the ops no assertion depends on are dropped window by
+    window first (`prune_windows`)."""
     finish = compact_windows if in_windows else (lambda wc, pieces: (wc, pieces))
     whole = compact or prune
     if fmt == "auto":
@@ -274,23 +298,28 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
             n = len(prog)
     if compact:
         prog, wc = compact_program(np.asarray(prog), wc)
+    if prune_in_windows:
+        from .prune import window_pieces
+
+        return finish(wc, prune_windows(wc, window_pieces(prog, STREAM_FEED_OPS))[0])
     return finish(wc, lambda: ((np.asarray(prog[at:at + STREAM_FEED_OPS]), None) for at in range(0, max(n, 1), STREAM_FEED_OPS)))
 
 
 def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, device_compile=False, device_z64=False, device_b2a=False,
-                    compact=False, parser="host", window_mb=None, in_windows=False, prune=False):
+                    compact=False, parser="host", window_mb=None, in_windows=False, prune=False, prune_in_windows=False):
     """`oneshot --evaluator stream`: the program evaluated in pieces with bounded device memory (rv_eval_stream_*), on the GPU like
     --evaluator gpu and with the same outcome.  An rvops file is read through a memory map, piece by piece; its wire counts come from
     one pass over the mapping.  window_mb (--window-mb, with --parser device): an mcircuit-bincode file is read in windows of that
     many MiB on the GPU, and so is a Bristol file; without it, either is parsed whole.  compact (--compact-wires): the whole list is renumbered by liveness first
     (in host memory: 24 bytes per op, against a wire-store row per gate of an SSA list) and the stream begins with the new counts;
-    in_windows (--compact-windows): the pieces are renumbered window by window instead, and nothing is whole in memory."""
+    in_windows (--compact-windows): the pieces are renumbered window by window instead, and nothing is whole in memory.
+    prune_in_windows (--prune-windows): the ops no assertion depends on are dropped window by window first."""
     from .stream import StreamingEvaluator, _is_wit_source, _piece_inputs
 
     source = _is_wit_source(witness)  # (--witness-window-mb: the bits are read as the pieces ask for them)
     wit = witness if source or hasattr(witness, "data_ptr") else np.ascontiguousarray(np.asarray(witness, dtype=np.uint8))
     wc, pieces = stream_pieces(program_path, fmt, parser, window_mb, expected_path, compact, windowed=window_mb is not None, in_windows=in_windows,
-                              prune=prune)
+                              prune=prune, prune_in_windows=prune_in_windows)
     se = StreamingEvaluator(wc, 1, max_chunk_ops, device_compile=device_compile, **({"device_z64": True} if device_z64 else {}),
                             **({"device_b2a": True} if device_b2a else {}))
     try:
@@ -305,6 +334,7 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
         r = se.finish()
     finally:
         se.close()
+        close_pruner(pieces)
     if not r.ok[0]:
         raise SystemExit("assertion failed: AssertZero at op %d does not hold (%d failing)" % (r.first_failed_op[0], r.n_failed[0]))
 
@@ -362,7 +392,11 @@ def convert_source(a, fmt, device_parser: bool):
             z, g = largest_wires(piece)
             z64, gf2, n_in = max(z64, z), max(gf2, g), n_in + int(np.count_nonzero((piece["domain"] == 0) & (piece["opcode"] == 0)))
         d.update(wc=(z64, gf2), n_ops=n, n_inputs=n_in)
-        if a.compact_windows:
+        if a.prune_windows:
+            from .prune import window_pieces
+
+            d["pieces"], d["n_ops"] = prune_windows(d["wc"], window_pieces(prog, STREAM_FEED_OPS))
+        elif a.compact_windows:
             d["pieces"] = lambda: ((np.asarray(prog[at:at + STREAM_FEED_OPS]), None) for at in range(0, max(n, 1), STREAM_FEED_OPS))
         else:
             d["prog"] = np.asarray(prog)
@@ -425,6 +459,8 @@ def run_convert(a, ap, fmt, device_parser: bool) -> int:
         detail = "op %d" % where if where is not None else _lib.lib().rv_last_error().decode()
         raise SystemExit("convert: the program cannot be written as Bristol text (%s): Bristol holds GF(2) programs whose Input ops lead, "
                          "with Add, Mul, AddConst 0/1 and Const 0/1 only" % detail)
+    finally:
+        close_pruner(src["pieces"])
     print("convert: %d ops, wire counts (z64, gf2) %s -> %s, %d bytes" % (src["n_ops"], tuple(int(x) for x in src["wc"]),
                                                                         tuple(int(x) for x in src["wc_out"]), n_bytes), file=sys.stderr)
     return 0
@@ -438,27 +474,30 @@ def run_streamed(a, ap, device_parser: bool) -> int:
     if a.strict and a.reference_compat:
         ap.error("--strict and --reference-compat exclude each other")
     wc, pieces = stream_pieces(a.program_path, a.program_format, "device" if device_parser else "host", a.window_mb, a.expected_outputs_path,
-                               a.compact_wires, in_windows=a.compact_windows, prune=a.prune)
-    kw = dict(max_chunk_ops=a.max_chunk_ops, device_compile=a.compiler != "host", device_z64=a.compiler in ("device-z64", "device-b2a"),
-              device_b2a=a.compiler == "device-b2a")
-    if a.operation in ("prove", "oneshot-zk"):
-        wit = load_witness(a.witness_path, a.witness_parser, a.witness_window_mb)
-        print("Evaluating program in ~zero knowledge~")
-        proof, _ = prove_streaming_pieces(pieces, wit, (), wc, **kw)
-        if a.operation == "prove":
-            with open(a.proof_path, "wb") as f:
-                f.write(bytes(proof))
+                               a.compact_wires, in_windows=a.compact_windows, prune=a.prune, prune_in_windows=a.prune_windows)
+    try:
+        kw = dict(max_chunk_ops=a.max_chunk_ops, device_compile=a.compiler != "host", device_z64=a.compiler in ("device-z64", "device-b2a"),
+                  device_b2a=a.compiler == "device-b2a")
+        if a.operation in ("prove", "oneshot-zk"):
+            wit = load_witness(a.witness_path, a.witness_parser, a.witness_window_mb)
+            print("Evaluating program in ~zero knowledge~")
+            proof, _ = prove_streaming_pieces(pieces, wit, (), wc, **kw)
+            if a.operation == "prove":
+                with open(a.proof_path, "wb") as f:
+                    f.write(bytes(proof))
+                print("Ok(())")
+                return 0
+        else:
+            proof = open(a.proof_path, "rb").read()
+            print("Verifying Proof")
+        ok, _ = verify_streaming_pieces(pieces, wc, proof, strict=not a.reference_compat, **kw)
+        if ok:
             print("Ok(())")
             return 0
-    else:
-        proof = open(a.proof_path, "rb").read()
-        print("Verifying Proof")
-    ok, _ = verify_streaming_pieces(pieces, wc, proof, strict=not a.reference_compat, **kw)
-    if ok:
-        print("Ok(())")
-        return 0
-    print('Err("Unverifiable Proof")')  # (and status 1: see main)
-    return 1
+        print('Err("Unverifiable Proof")')  # (and status 1: see main)
+        return 1
+    finally:
+        close_pruner(pieces)
 
 
 # --evaluator stream: an rvops file is fed in pieces of this many ops (the evaluator cuts them into chunks of --max-chunk-ops)
@@ -528,6 +567,12 @@ def build_parser():
                          "on first (rv_ops_prune; with --parser device rv_ops_prune_device, where the list lies), before --compact-wires; the "
                          "op counts before and after are printed on stderr.  The proof is the proof of the pruned program, NOT of the original: "
                          "prove and verify must both be given --prune.  Refused with --window-mb and --compact-windows (a source read in windows)")
+    ap.add_argument("--prune-windows", action="store_true",
+                    help="--stream, oneshot --evaluator stream, or convert, on an rvops file (its memory map is read in both directions): "
+                         "--prune window by window (rv_pruner_*: the source is read once more for a scan pass and once, from the last window "
+                         "to the first, for the marks), so that the op list is never whole in memory; the kept records, the proof bytes and "
+                         "the stderr line are --prune's.  Combines with --compact-windows (pruning comes first).  Any other source is "
+                         "refused: convert it to rvops first")
     ap.add_argument("--compact-windows", action="store_true",
                     help="--stream, or oneshot --evaluator stream, on a source that is read in windows (an rvops file; with --parser device "
                          "an mcircuit-bincode file, or a Bristol file with --window-mb): renumber the wires by liveness window by window "
@@ -590,6 +635,13 @@ def main(argv=None) -> int:
     if fmt == "auto":
         fmt = "rvops" if a.program_path.endswith(".rvops") else "bristol"
     device_parser = a.parser == "device" and fmt in ("bristol", "mcircuit-bincode")
+    if a.prune_windows:
+        if fmt != "rvops":
+            ap.error("--prune-windows needs a source that can be read backwards: an rvops file (convert the program to rvops first)")
+        if a.prune or a.compact_wires:
+            ap.error("--prune-windows keeps the windows: it cannot be combined with --prune or --compact-wires (--compact-windows is its partner)")
+        if not (a.operation == "convert" or a.stream or (a.operation == "oneshot" and a.evaluator == "stream")):
+            ap.error("--prune-windows needs a streamed operation: --stream, oneshot --evaluator stream, or convert")
     if a.operation == "convert":
         if a.compact_windows and a.compact_wires:
             ap.error("--compact-windows and --compact-wires exclude each other")
@@ -618,7 +670,8 @@ def main(argv=None) -> int:
                         a.max_chunk_ops, device_compile=a.compiler != "host", **({"device_z64": True} if a.compiler in ("device-z64", "device-b2a") else {}),
                         **({"device_b2a": True} if a.compiler == "device-b2a" else {}), **({"compact": True} if a.compact_wires else {}),
                         **({"parser": "device"} if device_parser else {}), **({"window_mb": a.window_mb} if a.window_mb is not None else {}),
-                        **({"in_windows": True} if a.compact_windows else {}), **({"prune": True} if a.prune else {}))
+                        **({"in_windows": True} if a.compact_windows else {}), **({"prune": True} if a.prune else {}),
+                        **({"prune_in_windows": True} if a.prune_windows else {}))
         print("()")
         return 0
     if a.stream:

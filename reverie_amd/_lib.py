@@ -108,6 +108,10 @@ class LinkPiece(C.Structure):  # rv_link_piece
     _fields_ = [(n, C.c_uint64) for n in ("first_op", "n_ops", "n_input_gf2", "n_input_z64")]
 
 
+class PrunerInfo(C.Structure):  # rv_pruner_info
+    _fields_ = [(n, C.c_uint64) for n in ("total_ops", "n_kept", "state_bytes", "peak_feed_bytes", "mark_feeds", "host_feeds")]
+
+
 class PruneInfo(C.Structure):  # rv_prune_info
     _fields_ = [(n, C.c_uint64) for n in ("n_kept", "n_dropped", "dropped_gf2_mul", "dropped_z64_mul", "dropped_b2a", "dropped_gf2_random",
                                           "dropped_z64_random", "dropped_gf2_other", "dropped_z64_other", "unread_gf2_inputs",
@@ -182,6 +186,8 @@ SYMBOLS = [
     "rv_witness_reader_begin", "rv_witness_reader_feed", "rv_witness_reader_finish", "rv_witness_reader_destroy",
     "rv_link", "rv_link_plan_create", "rv_link_plan_info", "rv_link_plan_emit", "rv_link_plan_destroy", "rv_hook_link_tiles",
     "rv_ops_prune", "rv_ops_prune_device", "rv_hook_prune_limits", "rv_hook_prune_launches",
+    "rv_ops_prune_windows_host", "rv_pruner_begin", "rv_pruner_scan", "rv_pruner_scan_end", "rv_pruner_mark", "rv_pruner_mark_end", "rv_pruner_feed",
+    "rv_pruner_rewind", "rv_pruner_get_info", "rv_pruner_destroy",
     "rv_hook_prove_schedule",
     "rv_hook_b3_plan", "rv_hook_b3_chunks", "rv_hook_b3_pair_small", "rv_hook_b3_pair_big_chunks", "rv_hook_b3_tree", "rv_hook_b3_pair_big_tree",
     "rv_hook_b3_incremental", "rv_hook_b3_join",
@@ -335,6 +341,17 @@ ARGTYPES = {
     "rv_ops_prune_device": [_P, _P, _Z, _Z, _Z, _P, _Z, _P, _Z, _P, _Z, C.POINTER(C.c_size_t), _P, C.POINTER(PruneInfo)],
     "rv_hook_prune_limits": [C.POINTER(C.c_uint32)],
     "rv_hook_prune_launches": [C.POINTER(C.c_uint64)],
+    # the same for a list read in windows
+    "rv_ops_prune_windows_host": [_P, _Z, _Z, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _Z, C.POINTER(C.c_size_t), _P, C.POINTER(PruneInfo)],
+    "rv_pruner_begin": [_P, _Z, _Z, _P, _Z, _P, _Z, C.POINTER(C.c_void_p)],
+    "rv_pruner_scan": [_P, _P, _Z, C.c_int],
+    "rv_pruner_scan_end": [_P],
+    "rv_pruner_mark": [_P, _P, _Z, C.c_int, C.POINTER(C.c_size_t)],
+    "rv_pruner_mark_end": [_P, C.POINTER(PruneInfo)],
+    "rv_pruner_feed": [_P, _P, _Z, C.c_int, _P, _Z, C.POINTER(C.c_size_t), _P],
+    "rv_pruner_rewind": [_P],
+    "rv_pruner_get_info": [_P, C.POINTER(PrunerInfo)],
+    "rv_pruner_destroy": [_P],
     # the transcript-hash kernels (parity hooks)
     "rv_hook_b3_plan": [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)],
     "rv_hook_b3_chunks": [_P, C.c_int, _P, C.c_uint64, C.c_uint32, C.c_uint64, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint64,
@@ -412,7 +429,8 @@ def lib():
             fn = getattr(L, name)
             if name in ("rv_ctx_destroy", "rv_circuit_destroy", "rv_shard_destroy", "rv_free", "rv_stream_abort", "rv_comm_destroy",
                         "rv_eval_stream_abort", "rv_program_reader_destroy", "rv_bristol_reader_destroy", "rv_compactor_destroy",
-                        "rv_bristol_writer_destroy", "rv_program_writer_destroy", "rv_witness_reader_destroy", "rv_link_plan_destroy"):
+                        "rv_bristol_writer_destroy", "rv_program_writer_destroy", "rv_witness_reader_destroy", "rv_link_plan_destroy",
+                        "rv_pruner_destroy"):
                 fn.restype = None
             elif name in ("rv_hook_early_proofs", "rv_hook_open_direct_proofs", "rv_hook_verify_vc_count", "rv_hook_ops_cache_hits", "rv_hook_overlap_commits",
                           "rv_hook_verify_proof_bytes", "rv_hook_stream_device_chunks"):

@@ -35,6 +35,7 @@
 #include "piece_pipe.h"
 #include "piece_sums.h"
 #include "prune_dev.h"
+#include "prune_win.h"
 #include "verify_dev.h"
 #include "witness_text.h"
 

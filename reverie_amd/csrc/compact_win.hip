@@ -25,9 +25,9 @@
 #include "compact_win.h"
 
 #include <algorithm>
-#include <unordered_map>
 #include <vector>
 
+#include "dev_counting.h"
 #include "piece_sums.h"
 
 namespace rv {
@@ -371,29 +371,6 @@ __global__ __launch_bounds__(TB) void k_w_rewrite(const rv_op* ops, size_t n, co
         if (op.opcode != RV_OP_ASSERTZERO) op.dst = (d == G && pinned(pins, op.dst, Wg)) ? rank_of(op.dst) : slot[i];
     }
     out[i] = op;
-}
-
-// the work memory of one call, counted
-struct Counting {
-    DevAlloc inner;
-    size_t cur = 0, peak = 0;
-    std::unordered_map<void*, size_t> sizes;
-};
-int counting_alloc(void* self, size_t bytes, void** out) {
-    Counting* c = (Counting*)self;
-    const int rc = c->inner.alloc(c->inner.self, bytes, out);
-    if (rc == RV_OK) {
-        c->sizes[*out] = bytes;
-        c->cur += bytes;
-        c->peak = std::max(c->peak, c->cur);
-    }
-    return rc;
-}
-void counting_release(void* self, void* p) {
-    Counting* c = (Counting*)self;
-    const auto it = c->sizes.find(p);
-    if (it != c->sizes.end()) c->cur -= it->second, c->sizes.erase(it);
-    c->inner.release(c->inner.self, p);
 }
 
 }  // namespace
@@ -750,12 +727,9 @@ int scan_end_impl(WinCompactor* c, const DevAlloc& CA, int* again, rv_compact_in
 // one call's work memory, counted into peak_feed
 template <class Fn>
 int counted(WinCompactor* c, size_t upload_bytes, Fn&& fn) {
-    Counting cnt;
-    cnt.inner = c->A;
-    DevAlloc CA;
-    CA.self = &cnt, CA.alloc = counting_alloc, CA.release = counting_release;
-    const int rc = fn(CA);
-    c->peak_feed = std::max(c->peak_feed, cnt.peak + upload_bytes);
+    size_t peak = 0;
+    const int rc = counted_call(c->A, &peak, fn);
+    c->peak_feed = std::max(c->peak_feed, peak + upload_bytes);
     return rc;
 }
 

@@ -39,9 +39,14 @@ struct Needed {
     }
 };
 
-int sweep(const rv_op* ops, size_t n, size_t z64_wires, size_t gf2_wires, const uint32_t* outs[2], const size_t n_outs[2], rv_op* out, size_t cap,
-          size_t* n_out, uint32_t* old_index, rv_prune_info* info) {
+// The three passes over the windows [0, cuts[0]), [cuts[0], cuts[1]), .. [cuts[n_cuts - 1], n): the validation forwards (the counts in
+// force run on from window to window), the window step (prune.h: pr_window_sweep) from the last window to the first with the needed
+// tables handed on, the kept records forwards.  rv_ops_prune is this with no cut.
+int sweep(const rv_op* ops, size_t n, size_t z64_wires, size_t gf2_wires, const uint32_t* outs[2], const size_t n_outs[2], const size_t* cuts,
+          size_t n_cuts, rv_op* out, size_t cap, size_t* n_out, uint32_t* old_index, rv_prune_info* info) {
     if (n >= PR_NONE - 1) return RV_E_UNSUPPORTED;
+    for (size_t c = 0; c < n_cuts; c++)
+        if (cuts[c] > n || (c && cuts[c] < cuts[c - 1])) return RV_E_ARG;
     uint64_t nw[2] = {gf2_wires, z64_wires};
     for (size_t i = 0; i < n; i++) {
         if (ops[i].domain == RV_DOM_SIZEHINT && ops[i].reserved == 0)
@@ -59,21 +64,10 @@ int sweep(const rv_op* ops, size_t n, size_t z64_wires, size_t gf2_wires, const 
     std::vector<uint8_t> keep(n);
     rv_prune_info pi = {};
     uint64_t* cls = &pi.dropped_gf2_mul;  // (the nine class counters lie in prune.h's order)
-    for (size_t i = n; i-- > 0;) {
-        const rv_op& op = ops[i];
-        const int d = pr_def(op);
-        const bool wanted = d >= 0 && need[d].take(op.dst);
-        const bool kept = wanted || pr_root(op);
-        keep[i] = kept;
-        if (!kept) {
-            cls[pr_class(op)]++;
-            continue;
-        }
-        pi.n_kept++;
-        if (pr_is_input(op) && !wanted) cls[PR_C_INPUT_G + d]++;
-        const uint32_t r = pr_n_reads(op);
-        const int rd = pr_read_dom(op);
-        for (uint32_t k = 0; k < r; k++) need[rd].set(pr_read(op, k));
+    // the windows from the last to the first (no cut: the whole list is the one window)
+    for (size_t c = n_cuts + 1; c-- > 0;) {
+        const size_t lo = c ? cuts[c - 1] : 0, hi = c < n_cuts ? cuts[c] : n;
+        pi.n_kept += pr_window_sweep(ops + lo, hi - lo, need, keep.data() + lo, cls);
     }
     pi.n_dropped = n - pi.n_kept;
 
@@ -95,18 +89,25 @@ int sweep(const rv_op* ops, size_t n, size_t z64_wires, size_t gf2_wires, const 
 
 }  // namespace
 
-extern "C" int rv_ops_prune(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const uint32_t* outputs_gf2, size_t n_outputs_gf2,
-                            const uint32_t* outputs_z64, size_t n_outputs_z64, rv_op* out, size_t cap, size_t* n_out, uint32_t* old_index,
-                            rv_prune_info* info) {
-    if ((n_ops && !ops) || (n_outputs_gf2 && !outputs_gf2) || (n_outputs_z64 && !outputs_z64)) return RV_E_ARG;
+extern "C" int rv_ops_prune_windows_host(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const uint32_t* outputs_gf2,
+                                         size_t n_outputs_gf2, const uint32_t* outputs_z64, size_t n_outputs_z64, const size_t* cuts, size_t n_cuts,
+                                         rv_op* out, size_t cap, size_t* n_out, uint32_t* old_index, rv_prune_info* info) {
+    if ((n_ops && !ops) || (n_outputs_gf2 && !outputs_gf2) || (n_outputs_z64 && !outputs_z64) || (n_cuts && !cuts)) return RV_E_ARG;
     // (out == ops is the in-place form; any other overlap would have the copy read what it wrote)
     if (n_ops && out && out != ops && (const uint8_t*)out < (const uint8_t*)(ops + n_ops) && (const uint8_t*)ops < (const uint8_t*)(out + cap))
         return RV_E_ARG;
     const uint32_t* outs[2] = {outputs_gf2, outputs_z64};
     const size_t n_outs[2] = {n_outputs_gf2, n_outputs_z64};
     try {  // no C++ exception may cross the C boundary
-        return sweep(ops, n_ops, z64_wires, gf2_wires, outs, n_outs, out, cap, n_out, old_index, info);
+        return sweep(ops, n_ops, z64_wires, gf2_wires, outs, n_outs, cuts, n_cuts, out, cap, n_out, old_index, info);
     } catch (...) {
         return RV_E_NOMEM;
     }
+}
+
+extern "C" int rv_ops_prune(const rv_op* ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const uint32_t* outputs_gf2, size_t n_outputs_gf2,
+                            const uint32_t* outputs_z64, size_t n_outputs_z64, rv_op* out, size_t cap, size_t* n_out, uint32_t* old_index,
+                            rv_prune_info* info) {
+    return rv_ops_prune_windows_host(ops, n_ops, z64_wires, gf2_wires, outputs_gf2, n_outputs_gf2, outputs_z64, n_outputs_z64, nullptr, 0, out, cap, n_out,
+                                     old_index, info);
 }

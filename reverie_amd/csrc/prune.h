@@ -83,6 +83,67 @@ PR_HD inline uint32_t pr_value_read(const uint32_t* sk, const uint32_t* sv, uint
     return (lo > 0 && sk[lo - 1] == w) ? sv[lo - 1] : PR_NONE;
 }
 
+// ---- the window step: the rule on ops [lo, hi) of a list that passes through in windows, from the last window to the
+// first.  What a window hears from the ones behind it is one needed byte per index and domain: a kept op behind `hi` reads the value
+// now on the index.  The host form is the backward sweep itself; the device form counts and peels as the whole-list call does, with
+// the three decisions below around it. ----
+
+// a needed table over memory the caller holds, one byte per index (the host sweep's other table, a hash set, is prune.cpp's)
+struct PrDense {
+    uint8_t* p;
+    void set(uint32_t w) { p[w] = 1; }
+    // the flag, cleared
+    bool take(uint32_t w) {
+        const bool was = p[w] != 0;
+        p[w] = 0;
+        return was;
+    }
+};
+// The backward sweep over one window: need[PR_G], need[PR_Z] come in as they stand at the window's end and go out as they stand at
+// its beginning; keep[i] for the window's n ops; the dropped ops and the Inputs kept unwanted are added to cls[PR_CLASSES].  A
+// defining op takes (clears) the flag of its index whether it is kept or not, a kept op then sets the flags of what it reads: every
+// index the window writes is killed, and what a kept op reads ahead of the window's writers of it is generated after that.
+// -> the ops kept
+template <class Need>
+inline uint64_t pr_window_sweep(const rv_op* ops, size_t n, Need need[2], uint8_t* keep, uint64_t* cls) {
+    uint64_t n_kept = 0;
+    for (size_t i = n; i-- > 0;) {
+        const rv_op& op = ops[i];
+        const int d = pr_def(op);
+        const bool wanted = d >= 0 && need[d].take(op.dst);
+        const bool kept = wanted || pr_root(op);
+        keep[i] = kept;
+        if (kept) {
+            n_kept++;
+            if (pr_is_input(op) && !wanted) cls[PR_C_INPUT_G + d]++;
+            const uint32_t r = pr_n_reads(op);
+            const int rd = pr_read_dom(op);
+            for (uint32_t k = 0; k < r; k++) need[rd].set(pr_read(op, k));
+        } else {
+            cls[pr_class(op)]++;
+        }
+    }
+    return n_kept;
+}
+
+// The device's three decisions, on one domain's sorted (index, op) pairs of the window (nd defining ops) and its needed bytes N
+// (W of them).  Pair j is the window's LAST writer of its index when the next pair has another key.
+PR_HD inline bool pr_run_last(const uint32_t* sk, uint32_t nd, uint32_t j) { return j + 1 >= nd || sk[j + 1] != sk[j]; }
+// live-out: the value pair j's op defines is read behind the window (one more on its count) -- the last writer of a needed index
+PR_HD inline bool pr_live_out(const uint32_t* sk, uint32_t nd, uint32_t j, const uint8_t* N, uint64_t W) {
+    return pr_run_last(sk, nd, j) && sk[j] < W && N[sk[j]] != 0;
+}
+// kill: every index the window writes, whoever wrote it, kept or dropped (once per index: by the run's last pair)
+PR_HD inline void pr_kill(const uint32_t* sk, uint32_t nd, uint32_t j, uint8_t* N, uint64_t W) {
+    if (pr_run_last(sk, nd, j) && sk[j] < W) N[sk[j]] = 0;
+}
+// gen, after every kill: read k of the kept op i escapes the window (no writer of the index inside it and before i) -> the index is
+// needed ahead of the window.  Threads that store to one byte store the same value.
+PR_HD inline void pr_gen(const rv_op& op, uint32_t i, uint32_t k, const uint32_t* sk, const uint32_t* sv, uint32_t nd, uint8_t* N, uint64_t W) {
+    const uint32_t w = pr_read(op, k);
+    if (w < W && pr_value_read(sk, sv, nd, w, i) == PR_NONE) N[w] = 1;
+}
+
 // ---- the emit: a tile of PRUNE_TILE input records gathers its kept ones into an image that lies in LDS at the position modulo 16
 // its bytes have in d_out (link.h's layout).  `first` kept records precede the tile's. ----
 PR_HD inline uint32_t pr_image_shift(uint64_t out_addr, uint64_t first) { return (uint32_t)((out_addr + first * 24) & 15u); }

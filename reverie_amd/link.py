@@ -257,16 +257,24 @@ class LinkPlan:
     def pieces(self, window_ops: int):
         """-> a callable that returns a fresh iterator of (tensor, (n_input_gf2, n_input_z64)) over the list in windows of window_ops
         records: the shape `stream.prove_streaming_pieces`, `verify_streaming_pieces`, `evaluate_streaming_pieces`,
-        `compact.compact_pieces`, `bristol.write_device` and `program_file.write_device` take"""
+        `compact.compact_pieces`, `bristol.write_device` and `program_file.write_device` take.  The callable's `.backwards` is such
+        a callable over the same windows from the last to the first (`prune.prune_pieces` marks from it)"""
         if window_ops <= 0 or window_ops >= 1 << 28:
             raise ValueError("window_ops must lie in [1, 2^28)")
 
-        def it():
+        def windows(firsts):
             n = self.info["n_ops"]
-            for first in range(0, n, window_ops):
+            for first in firsts:
                 t = self.emit(first, min(window_ops, n - first))
                 yield t, self.last_piece
 
+        def it():
+            return windows(range(0, self.info["n_ops"], window_ops))
+
+        def backwards():
+            return windows(reversed(range(0, self.info["n_ops"], window_ops)))
+
+        it.backwards = backwards
         return it
 
     def close(self) -> None:

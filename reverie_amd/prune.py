@@ -77,3 +77,186 @@ def prune_ops(ops, wire_counts: Optional[Tuple[int, int]] = None, outputs_gf2: S
     _lib.check(L.rv_ops_prune(*head, _ptr(out), C.c_size_t(len(out)), C.byref(n_out), _ptr(old), C.byref(pi)))
     kept = int(n_out.value)
     return out[:kept].copy(), _info(pi), old[:kept].copy()
+
+
+# ---- the same for a list that passes through in windows (rv_pruner_*) ----
+class DevicePruner:
+    """rv_pruner: `prune_ops` for an op list that arrives in feeds.  scan(ops)... scan_end(); mark(ops)... with the windows from the
+    LAST to the first (each window's ops in list order), mark_end() -> rv_prune_info; then feed(ops)... forwards -> the kept records,
+    feed by feed; rewind() starts the emit pass again.  The three passes may be cut differently.  ops: an OP_DTYPE array (uploaded)
+    or a torch GPU tensor of packed rv_op records.  wire_counts: (z64, gf2) as stated; the outputs as in `prune_ops`."""
+
+    def __init__(self, wire_counts: Tuple[int, int], outputs_gf2: Sequence[int] = (), outputs_z64: Sequence[int] = (), ctx: Optional[Context] = None):
+        self.ctx = ctx or Context.default()
+        self.handle = C.c_void_p()
+        self.info = None
+        og, oz = _outputs(outputs_gf2), _outputs(outputs_z64)
+        _lib.check(_lib.lib().rv_pruner_begin(self.ctx.handle, C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])), _ptr(og),
+                                              C.c_size_t(og.size), _ptr(oz), C.c_size_t(oz.size), C.byref(self.handle)))
+
+    def _ops(self, ops):
+        """-> (pointer, n_ops, on device, what keeps the memory alive)"""
+        if _is_device_ops(ops):
+            d_ops, n_ops, _ = _device_ops(ops, self.ctx, "DevicePruner")
+            return C.c_void_p(d_ops), n_ops, 1, ops
+        a = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+        return _ptr(a), len(a), 0, a
+
+    def scan(self, ops) -> None:
+        p, n, dev, _keep = self._ops(ops)
+        _lib.check(_lib.lib().rv_pruner_scan(self.handle, p, C.c_size_t(n), C.c_int(dev)))
+
+    def scan_end(self) -> None:
+        _lib.check(_lib.lib().rv_pruner_scan_end(self.handle))
+
+    def mark(self, ops) -> int:
+        """-> the ops of the feed that are kept"""
+        p, n, dev, _keep = self._ops(ops)
+        kept = C.c_size_t(0)
+        _lib.check(_lib.lib().rv_pruner_mark(self.handle, p, C.c_size_t(n), C.c_int(dev), C.byref(kept)))
+        return int(kept.value)
+
+    def mark_end(self) -> dict:
+        """-> rv_prune_info as a dict (also .info)"""
+        pi = _lib.PruneInfo()
+        _lib.check(_lib.lib().rv_pruner_mark_end(self.handle, C.byref(pi)))
+        self.info = _info(pi)
+        return self.info
+
+    def feed(self, ops):
+        """-> (the feed's kept records as a uint8 GPU tensor [n_out, 24], their indices in the whole old list as an int32 GPU tensor
+        [n_out]; the bits are uint32)"""
+        import torch
+
+        p, n, dev, _keep = self._ops(ops)
+        device = f"cuda:{self.ctx.device}"
+        out = torch.empty((n, OP_DTYPE.itemsize), dtype=torch.uint8, device=device)
+        old = torch.empty((n,), dtype=torch.int32, device=device)
+        n_out = C.c_size_t(0)
+        _lib.check(_lib.lib().rv_pruner_feed(self.handle, p, C.c_size_t(n), C.c_int(dev), C.c_void_p(out.data_ptr()) if n else None, C.c_size_t(n),
+                                             C.byref(n_out), C.c_void_p(old.data_ptr()) if n else None))
+        kept = int(n_out.value)
+        out, old = out[:kept], old[:kept]
+        if 2 * kept < n:
+            out, old = out.clone(), old.clone()
+        return out, old
+
+    def rewind(self) -> None:
+        _lib.check(_lib.lib().rv_pruner_rewind(self.handle))
+
+    def get_info(self) -> dict:
+        """rv_pruner_info: total_ops, n_kept, state_bytes, peak_feed_bytes, mark_feeds, host_feeds"""
+        pi = _lib.PrunerInfo()
+        _lib.check(_lib.lib().rv_pruner_get_info(self.handle, C.byref(pi)))
+        return _info(pi)
+
+    def close(self) -> None:
+        """gives the pruner's device memory back to its context (a context that was closed first took its memory with it: the handle
+        is dropped then, not destroyed)"""
+        if self.handle:
+            if self.ctx.handle:
+                _lib.lib().rv_pruner_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        import sys
+
+        if sys.is_finalizing():  # (finalisers run in no order then: the context and the runtime may be gone; the process ends anyway)
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def window_pieces(ops, window_ops: int):
+    """-> a callable that returns a fresh iterator of (window, None) over `ops` -- an OP_DTYPE array, an `np.memmap` of one (an rvops
+    file's records) or a torch GPU tensor of packed rv_op records -- in windows of window_ops records, with `.backwards`: the same
+    windows from the last to the first.  The windows are views; nothing is copied here."""
+    if window_ops <= 0:
+        raise ValueError("window_ops must be positive")
+    if _is_device_ops(ops):  # (any layout `Circuit.from_device_ops` takes: uint8 [n, 24] or [n * 24], int64 / uint64 [n, 3]; as bytes)
+        import torch
+
+        if not ops.is_contiguous():
+            raise ValueError("window_pieces needs a contiguous tensor of packed rv_op records")
+        recs = ops.view(torch.uint8).reshape(-1, OP_DTYPE.itemsize)
+    else:
+        recs = ops
+    n = len(recs)
+
+    def windows(firsts):
+        for first in firsts:
+            yield recs[first:first + window_ops], None
+
+    def it():
+        return windows(range(0, n, window_ops))
+
+    def backwards():
+        return windows(reversed(range(0, n, window_ops)))
+
+    it.backwards = backwards
+    return it
+
+
+def prune_pieces(pieces, wire_counts: Tuple[int, int], outputs_gf2: Sequence[int] = (), outputs_z64: Sequence[int] = (), backwards=None,
+                 ctx: Optional[Context] = None):
+    """-> (pieces2, info) for `pieces` as `stream.prove_streaming_pieces` takes them: a callable that returns a fresh iterator of
+    (ops, Input counts).  `backwards`: a callable that returns a fresh iterator over the SAME LIST in windows from the last to the
+    first (its cuts need not be `pieces`'); default `pieces.backwards`.  The scan pass and the mark pass run here.  `pieces2` is such
+    a callable too: every call reads the source again and yields (the piece's kept records as a GPU tensor, the source's Input
+    counts) -- Inputs are roots, so the counts pass through; pieces of which nothing is kept are skipped, and a pass has to be read
+    to its end before the next one begins.  The wire counts do not change.  info: rv_prune_info as a dict, with "pruner"
+    (rv_pruner_info) beside it; the pruner lives as long as `pieces2` (`pieces2.pruner`)."""
+    if not callable(pieces):
+        raise TypeError("prune_pieces reads the pieces several times: pass a callable that returns a fresh iterator")
+    if backwards is None:
+        backwards = getattr(pieces, "backwards", None)
+    if not callable(backwards):
+        raise TypeError("prune_pieces marks from the last window to the first and needs a source that can be read backwards: "
+                        "LinkPlan.pieces(window_ops), prune.window_pieces(ops, window_ops) on a host array, an rvops memory map or a GPU "
+                        "tensor, or backwards=<a callable>; a Bristol text or a bincode file is read forwards only: convert it to "
+                        "rvops first")
+    dp = DevicePruner(wire_counts, outputs_gf2, outputs_z64, ctx)
+    try:
+        for ops, _ in pieces():
+            if ops is not None and len(ops):
+                dp.scan(ops)
+        dp.scan_end()
+        for ops, _ in backwards():
+            if ops is not None and len(ops):
+                dp.mark(ops)
+        info = dict(dp.mark_end())
+    except BaseException:
+        dp.close()
+        raise
+    started = [False]
+
+    def pieces2():
+        if started[0]:
+            dp.rewind()
+        started[0] = True
+        for ops, counts in pieces():
+            if ops is None or len(ops) == 0:
+                continue
+            if counts is None and not _is_device_ops(ops):  # (counted where the records still are a host array)
+                a = program(ops)
+                inputs = a["opcode"] == 0
+                counts = (int(np.count_nonzero(inputs & (a["domain"] == 0))), int(np.count_nonzero(inputs & (a["domain"] == 1))))
+            elif counts is None:  # (domain and opcode are a record's first two bytes)
+                recs = ops.reshape(-1, OP_DTYPE.itemsize)
+                inputs = recs[:, 1] == 0
+                counts = (int((inputs & (recs[:, 0] == 0)).sum()), int((inputs & (recs[:, 0] == 1)).sum()))
+            kept, _old = dp.feed(ops)
+            if len(kept):
+                yield kept, counts
+
+    pieces2.pruner = dp
+    info["pruner"] = dp.get_info()
+    return pieces2, info

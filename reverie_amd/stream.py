@@ -34,7 +34,9 @@ bytes and read it in place (rv_stream_verify_begin_device).  Proofs, answers and
 
 The whole-list one-shot functions also take `prune` (default False): the ops no assertion depends on are dropped first
 (`prune.prune_ops`), then `compact_wires` runs if asked for, and the stream info (or `info`) receives "prune".  The proof is then the
-proof of the pruned list -- prover and verifier must both pass prune=True; the `*_pieces` functions do not prune.
+proof of the pruned list -- prover and verifier must both pass prune=True.  The `*_streaming_pieces` functions take `prune` too:
+the pieces are then pruned in windows (`prune.prune_pieces`, DESIGN §23.8: the source is read twice more, one of them backwards, so
+the pieces' callable needs `.backwards`), before `compact_wires`, and the result is the same.
 
 The one-shot functions take `compact_wires` (default False): the whole op list is first renumbered by liveness (`compact.compact_wires`,
 DESIGN §17) -- on the host for host ops, by kernels for a GPU tensor -- and the stream begins with the new, smaller wire counts, so an
@@ -77,15 +79,41 @@ def _compacted(ops, wire_counts, ctx: Context, wanted: bool, prune: bool = False
     return ops, wire_counts, (cinfo, pinfo)
 
 
-def _compacted_pieces(pieces, wire_counts, ctx: Optional[Context], wanted: bool):
-    """the pieces and wire counts a `*_streaming_pieces` call streams, rv_compact_info (None: compact_wires was not asked for) and
-    the compactor this call made and has to close (None: it made none -- pieces that a caller compacted are the caller's)"""
-    if not wanted:
+class _Owned:
+    """the pruner and the compactor a `*_streaming_pieces` call made and has to close"""
+
+    def __init__(self, *objs):
+        self.objs = [o for o in objs if o is not None]
+
+    def close(self) -> None:
+        for o in self.objs:
+            o.close()
+
+
+def _compacted_pieces(pieces, wire_counts, ctx: Optional[Context], wanted: bool, prune: bool = False):
+    """the pieces and wire counts a `*_streaming_pieces` call streams, (rv_compact_info, rv_prune_info) (None where compact_wires /
+    prune was not asked for) and what this call made and has to close (None: it made nothing -- pieces that a caller pruned or
+    compacted are the caller's).  Pruning (in windows, against the assertions: `prune.prune_pieces`) comes first, then compaction
+    over the pruned pieces."""
+    if not wanted and not prune:
         return pieces, wire_counts, None, None
     if not callable(pieces):
-        raise TypeError("compact_wires reads the pieces more than once: pass a callable that returns a fresh iterator")
-    new_counts, pieces2, cinfo = _compact.compact_pieces(pieces, wire_counts, ctx)
-    return pieces2, new_counts, cinfo, pieces2.compactor
+        raise TypeError("compact_wires and prune read the pieces more than once: pass a callable that returns a fresh iterator")
+    pinfo = cinfo = pruner = compactor = None
+    if prune:
+        from .prune import prune_pieces
+
+        pieces, pinfo = prune_pieces(pieces, wire_counts, ctx=ctx)
+        pruner = pieces.pruner
+    if wanted:
+        try:
+            wire_counts, pieces, cinfo = _compact.compact_pieces(pieces, wire_counts, ctx)
+        except BaseException:
+            if pruner is not None:
+                pruner.close()
+            raise
+        compactor = pieces.compactor
+    return pieces, wire_counts, (cinfo, pinfo), _Owned(pruner, compactor)
 
 
 def _with_compact(info: dict, cinfo) -> dict:
@@ -771,7 +799,7 @@ def _feed_pieces(feed, pieces, wit_gf2, wit_z64):
 
 def prove_streaming_pieces(pieces, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
                            ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                           device_proof: bool = False, compact_wires: bool = False) -> "Tuple[Proof | DeviceProof, dict]":
+                           device_proof: bool = False, compact_wires: bool = False, prune: bool = False) -> "Tuple[Proof | DeviceProof, dict]":
     """`prove_streaming` for an op list that is never whole in memory: `pieces()` returns a fresh iterator of (ops, (n_input_gf2,
     n_input_z64)) for each of the two passes -- `program_file.iter_device` on a program file, say (its piece dicts serve as the
     counts).  ops: a host array or a torch GPU tensor of rv_op records; a host array may come with None, its Inputs are then counted
@@ -779,12 +807,15 @@ def prove_streaming_pieces(pieces, wit_gf2, wit_z64, wire_counts: Tuple[int, int
     concatenated list; wire_counts are the whole list's (`program_file.scan_device`).  wit_gf2 may be a witness source that is read
     as the pieces ask for bits (`witness.DeviceWindows`: rewound at the start of each pass, take(n) per piece).  compact_wires: the pieces are renumbered by
     liveness in windows (`compact.compact_pieces`: the source is read for a scan pass first, twice with B2A ops), wire_counts are
-    the source's and the stream begins with the new ones; the same proof, and info carries "compact".
+    the source's and the stream begins with the new ones; the same proof, and info carries "compact".  prune: the ops no assertion
+    depends on are dropped first, in windows (`prune.prune_pieces`: the pieces need `.backwards`, as `LinkPlan.pieces` and
+    `prune.window_pieces` have it; the source is read for a scan pass and, backwards, for a mark pass), then compact_wires runs over
+    the pruned pieces if asked for; the proof is the pruned list's (prover and verifier both pass prune=True), info carries "prune".
     -> (Proof or DeviceProof, stream info)"""
     if not callable(pieces):
         raise TypeError("prove_streaming_pieces reads the pieces twice: pass a callable that returns a fresh iterator")
     g, z = _host_or_device_wit(wit_gf2, np.uint8), _host_or_device_wit(wit_z64, np.uint64)
-    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires)
+    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires, prune)
     sp = StreamingProver(wire_counts, seeds, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
     try:
         sp.same_cuts()
@@ -800,11 +831,11 @@ def prove_streaming_pieces(pieces, wit_gf2, wit_z64, wire_counts: Tuple[int, int
 
 def verify_streaming_pieces(pieces, wire_counts: Tuple[int, int], proof, strict: bool = True, max_chunk_ops: int = 0,
                             ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False,
-                            device_b2a: bool = False, compact_wires: bool = False) -> Tuple[bool, dict]:
+                            device_b2a: bool = False, compact_wires: bool = False, prune: bool = False) -> Tuple[bool, dict]:
     """`verify_streaming` for pieces as `prove_streaming_pieces` takes them (a callable or, the pass being one, an iterable; the
     counts are not looked at).  proof: bytes, a Proof, a bincode-form DeviceProof or a uint8 GPU tensor.  compact_wires: as in
-    `prove_streaming_pieces` (a callable is needed then).  -> (ok, stream info)"""
-    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires)
+    `prove_streaming_pieces` (a callable is needed then); prune: as there.  -> (ok, stream info)"""
+    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires, prune)
     sv = StreamingVerifier(wire_counts, proof, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
     try:
         for ops, _ in (pieces() if callable(pieces) else pieces):
@@ -819,12 +850,12 @@ def verify_streaming_pieces(pieces, wire_counts: Tuple[int, int], proof, strict:
 
 def evaluate_streaming_pieces(pieces, wits_gf2, wits_z64, wire_counts: Tuple[int, int], max_chunk_ops: int = 0, values: bool = False,
                               ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False,
-                              device_b2a: bool = False, compact_wires: bool = False) -> Evaluation:
+                              device_b2a: bool = False, compact_wires: bool = False, prune: bool = False) -> Evaluation:
     """`evaluate_streaming` for pieces as `prove_streaming_pieces` takes them, in one pass.  wits_gf2 / wits_z64: [B][n] (1-D for one
     witness), host arrays, torch GPU tensors or, for one GF(2) witness, a `witness.DeviceWindows`.  compact_wires: as in `prove_streaming_pieces` (wire values are those of the new
-    indices).  -> the array-shaped Evaluation; `info` receives the stream's figures (and "compact")."""
+    indices); prune: as there.  -> the array-shaped Evaluation; `info` receives the stream's figures (and "compact", "prune")."""
     g, z = _host_or_device_wit(wits_gf2, np.uint8), _host_or_device_wit(wits_z64, np.uint64)
-    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires)
+    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires, prune)
     batch = 1 if _is_wit_source(g) else g.shape[0] if g.ndim == 2 else 1
     se = StreamingEvaluator(wire_counts, batch, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
     try:

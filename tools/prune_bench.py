@@ -1,6 +1,6 @@
 """Pruning (rv_ops_prune / rv_ops_prune_device) where it costs and where it pays.
 
-    python tools/prune_bench.py [--runs 5] [--only as-is,sixteenth,aes,chain] [--small]
+    python tools/prune_bench.py [--runs 5] [--only as-is,sixteenth,aes,chain] [--small] [--window-ops N[,N]]
 
 One JSON line per case; every time is the median of --runs calls after one warm-up, with [min, max], in this one process:
   as-is      layered_gf2() (10^7 GF(2) gates in SSA form) as it is -- little is dead: the device call against the host sweep and
@@ -13,6 +13,10 @@ One JSON line per case; every time is the median of --runs calls after one warm-
              text -> Block.from_bristol(device=True) -> plan -> link_device -> prove_streaming with and without prune=True
   chain      one dead chain of 50 000 single ops behind a live list of 10^6: device against host (where the device path loses), and
              the device call under RV_PRUNE_MAX_ROUNDS=1024 (the fall-back)
+--window-ops N[,N]: on as-is and aes, the same tensor through rv_pruner_* in windows of N ops -- the scan pass, the
+mark pass (last window first) and one emit pass timed apart, against the whole-list device call of the same process; the cost per
+feed above the whole call, state_bytes and peak_feed_bytes; and on aes the chain the windows are for: plan.pieces(N) -> the streamed
+proof with compact_wires=True, with and without prune=True, the list never whole.
 --small: the shapes of a smoke run (a quick layered_gf2, 16 AES instances, a chain of 2 000 behind 10^4)."""
 import argparse
 import json
@@ -44,8 +48,10 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--only", default="as-is,sixteenth,aes,chain")
     ap.add_argument("--small", action="store_true")
+    ap.add_argument("--window-ops", default="", help="window sizes for the windowed pruner, comma separated")
     a = ap.parse_args()
     only = set(a.only.split(","))
+    window_ops = [int(x) for x in a.window_ops.split(",") if x]
     import torch
 
     import bristol_gen
@@ -79,6 +85,47 @@ def main():
         rec["info"] = d_info
         return d_prog, d_out, d_info
 
+    def windowed(d_prog, wc, rec, want):
+        """the three passes of rv_pruner_* over the tensor in windows of each --window-ops size, timed apart"""
+        from reverie_amd.prune import DevicePruner
+
+        n = len(d_prog)
+        for w in window_ops:
+            firsts = list(range(0, n, w))
+            passes = {"scan": [], "mark": [], "emit": []}
+            for run in range(a.runs + 1):  # (the first is the warm-up)
+                with DevicePruner(wc, ctx=ctx) as dp:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for f in firsts:
+                        dp.scan(d_prog[f:f + w])
+                    dp.scan_end()
+                    t1 = time.perf_counter()
+                    for f in reversed(firsts):
+                        dp.mark(d_prog[f:f + w])
+                    info = dp.mark_end()
+                    t2 = time.perf_counter()
+                    outs = [dp.feed(d_prog[f:f + w])[0] for f in firsts]
+                    torch.cuda.synchronize()
+                    t3 = time.perf_counter()
+                    pinfo = dp.get_info()
+                    if run == 0:
+                        same = bool(torch.cat(outs).cpu().numpy().tobytes() == want.cpu().numpy().tobytes())
+                    del outs
+                if run:
+                    for k, t in zip(("scan", "mark", "emit"), (t1 - t0, t2 - t1, t3 - t2)):
+                        passes[k].append(t * 1e3)
+            r = {"feeds": len(firsts), "equals_whole_call": same, "device_rounds": info["device_rounds"], "on_device": info["on_device"],
+                 "state_bytes": pinfo["state_bytes"], "peak_feed_bytes": pinfo["peak_feed_bytes"], "host_feeds": pinfo["host_feeds"]}
+            total = 0.0
+            for k, ts in passes.items():
+                ts.sort()
+                r[k] = {"ms": round(ts[len(ts) // 2], 3), "ms_min_max": [round(ts[0], 3), round(ts[-1], 3)]}
+                total += ts[len(ts) // 2]
+            r["three_passes_ms"] = round(total, 3)
+            r["per_feed_ms_above_whole_call"] = round((total - rec["device"]["ms"]) / (3 * len(firsts)), 4)
+            rec["windows_%d" % w] = r
+
     def proofs(prog, wit, wc, pruned, rec):
         for name, ops in (("proof_original", prog), ("proof_pruned", pruned)):
             c = rv.Circuit(ops, wc, whole_prover=True)
@@ -91,7 +138,8 @@ def main():
         prog, wit, wc, st = gen()
     if "as-is" in only:
         rec = {"case": "as-is", "n_ops": len(prog), "runs": a.runs}
-        d_prog, _, _ = prune_pair(prog, wc, rec)
+        d_prog, d_whole, _ = prune_pair(prog, wc, rec)
+        windowed(d_prog, wc, rec, d_whole)
 
         def compact():
             r = rv.compact_wires(d_prog, wc, ctx)
@@ -129,8 +177,26 @@ def main():
             prog, linfo = nl.link_host()
             wc = linfo["wire_counts"]
             rec = {"case": "aes", "instances": n_inst, "n_ops": len(prog), "runs": a.runs}
-            _, d_out, info = prune_pair(prog, wc, rec)
+            d_prog, d_out, info = prune_pair(prog, wc, rec)
+            windowed(d_prog, wc, rec, d_out)
             proofs(prog, wit, wc, d_out.cpu().numpy().reshape(-1).view(OP_DTYPE), rec)
+            del d_prog
+
+            def never_whole(w, prune):
+                b = rv.Block.from_bristol(text, device=True)
+                nl2 = rv.Netlist([b])
+                for _ in range(n_inst):
+                    nl2.add(0, [rv.link.WITNESS] * b.n_ports)
+                nl2.set_tail(tail)
+                with nl2.plan(ctx) as plan:
+                    p, sinfo = rv.stream.prove_streaming_pieces(plan.pieces(w), wit, [], wc, seeds=seeds, ctx=ctx, device_compile=True, prune=prune,
+                                                                compact_wires=True)
+                return len(bytes(p))
+
+            for w in window_ops:
+                for prune in (False, True):
+                    n_bytes, t = timed(lambda: never_whole(w, prune), a.runs)
+                    rec["pieces_%d_to_streamed_proof%s" % (w, "_pruned" if prune else "")] = dict(t, proof_bytes=n_bytes)
 
             def chain(prune):
                 b = rv.Block.from_bristol(text, device=True)
