@@ -1299,8 +1299,8 @@ int rv_hook_link_tiles(uint32_t out[2]);
  * KEPT: an op is kept if it is a root, or if it defines a value that a kept op reads or that an output names.  Every other op is
  * dropped.  The output is the kept records in list order, byte for byte as they were: nothing is renumbered, the wire counts stay
  * valid as they are.  The kept set is unique (the least set closed under the rule), so the order of work cannot change it; pruning a
- * pruned list with the same outputs changes nothing.  Not done: constant folding, copy propagation, common subexpressions, dropping
- * unread Inputs (that would change the witness format).
+ * pruned list with the same outputs changes nothing.  Not done: copy propagation, common subexpressions, dropping unread Inputs
+ * (that would change the witness format).  Constant folding is rv_ops_fold below: fold first, then prune.
  *
  * THE PROOF OF A PRUNED LIST IS THE PROOF OF THAT LIST -- byte for byte the reference's proof of the pruned program for the same
  * seeds -- and NOT the proof of the original: unlike the wire compaction this changes proof bytes; that is its purpose.  So prover
@@ -1352,6 +1352,80 @@ int rv_hook_prune_limits(uint32_t out[5]);
 /* launches of this process so far: out[0] = emit kernels that wrote records, out[1] = count-only passes, out[2] = peeling launches
  * (solo and wide together), out[3] = fall-backs to the host sweep */
 int rv_hook_prune_launches(uint64_t out[4]);
+
+/* ---- constants folded, record for record ------------------------------------------
+ * Real statements wire public values into blocks written for secret ones: the IV and the padding block of a SHA-256, the round keys
+ * of a cipher with a public key, a comparison against a public bound, a Z64 factor.  A Mul with a known operand is linear (MulConst)
+ * or a constant; a gate whose operands are all known is a Const.  These calls rewrite such records.  The rest of the gain comes from
+ * the pruning above, run afterwards: it drops the Consts nothing reads any more.  The order is fold, then prune, then compact.
+ *
+ * VALUES AND READS are those of rv_ops_prune: every op with a destination defines a value on (domain, dst); a read refers to the last
+ * value defined on its index before the reading op, and a read of an index no earlier op wrote reads the zero wire.
+ * KNOWN: a value is known, with a value v (GF(2): one bit; Z64: uint64_t with wrapping arithmetic, rv_evaluate's semantics), when
+ *   - it is a read of an index no earlier op wrote: known 0;
+ *   - Const: known imm (GF(2): bit 0 of imm);
+ *   - Add, Sub, Mul with both reads known, AddConst, SubConst, MulConst with their read known: the value the op computes;
+ *   - Mul with one read known 0: known 0, whatever the other read is;
+ *   - MulConst whose constant is 0 (GF(2): bit 0 of imm is 0): known 0;
+ *   - B2A with all 64 reads known: bit k of the value comes from index a + k.
+ * Input and Random are never known; AssertZero and SizeHint define nothing.  The known set is the least fixed point of this rule
+ * over a DAG in op order, so it is unique whatever the order of work.
+ * REWRITE, one to one: record j of the output replaces record j of the input.  Nothing is dropped, moved or renumbered; the op count,
+ * the wire counts and the witness order stay.
+ *   - a defining op whose value is known becomes Const(dst, v) in the domain of the value (a B2A: a Z64 Const);
+ *   - Add(a, b) with exactly one read known becomes AddConst(dst, other, v);
+ *   - Sub(a, b) with b known becomes SubConst(dst, a, v); GF(2) Sub(a, b) with a known becomes AddConst(dst, b, v); Z64 Sub(a, b)
+ *     with only a known is LEFT AS IT IS (no single op computes c - x);
+ *   - Mul(a, b) with exactly one read known, nonzero, becomes MulConst(dst, other, v);
+ *   - everything else stays byte for byte as it was: Input, Random, AssertZero, SizeHint, a B2A with an unknown bit, ops with no
+ *     known read, and a record that already was a Const (high bits of imm included).
+ * A rewritten record has reserved = 0, every field its new opcode does not use set to 0, and a GF(2) imm of 0 or 1.
+ * So every wire's final value and every AssertZero's result are the original's for every witness (the difference from pruning);
+ * folding a folded list changes nothing; and a list with no Const, no zero MulConst and no read of an unwritten index comes out byte
+ * for byte as it went in.
+ * NOT DONE: algebraic identities (x + x, x - x, MulConst 1, AddConst 0); copy propagation and common subexpressions; dropping an
+ * AssertZero of a known 0 (it is a root and costs nothing in a proof -- the info counts such assertions, and those of a known
+ * nonzero value: a statement that can never hold).
+ *
+ * THE PROOF OF A FOLDED LIST IS THE PROOF OF THAT LIST -- byte for byte the reference's proof of the folded program for the same
+ * seeds -- and NOT the proof of the original: a folded Mul or B2A no longer contributes to it.  As with rv_ops_prune, prover and
+ * verifier both fold, or the folded program is the file that is shipped.
+ *
+ * ERRORS: the list is validated as rv_ops_prune validates it; the code is that of the first bad op in op order, and nothing is
+ * written then. */
+typedef struct rv_fold_info {
+    uint64_t n_ops, n_rewritten;
+    uint64_t n_known; /* defining ops whose value is known, the Consts already there included */
+    /* the rewritten records by class */
+    uint64_t gf2_mul_to_const, z64_mul_to_const, gf2_mul_to_linear, z64_mul_to_linear, b2a_to_const;
+    uint64_t gf2_other_rewritten, z64_other_rewritten; /* Add / Sub to AddConst / SubConst, a linear op or a zero MulConst to Const */
+    /* AssertZeros of a known value (they stay) */
+    uint64_t asserts_known_zero, asserts_known_nonzero;
+    uint32_t device_rounds; /* layers of known values the device call propagated (0 from the host call) */
+    uint32_t on_device;     /* 1: the device call finished on the GPU (0 from the host call, and from the fall-back) */
+} rv_fold_info;             /* 104 bytes */
+/* host only, no GPU: one forward sweep with a known flag and a value per wire index and domain -- the definition.  out has room
+ * for n_ops records; out == NULL only fills the info; out == ops folds in place (any other overlap is RV_E_ARG).  info may be NULL. */
+int rv_ops_fold(const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, rv_op *out, rv_fold_info *info);
+/* The same records and the same info (but for its last two words) from kernels on the context's GPU, for a list in device memory,
+ * with rv_ops_prune_device's conventions (8-byte aligned records inside one allocation of the context's device, RV_E_ARG otherwise
+ * and before any launch; 2^31 ops or more, or a wire count in force of 2^31 or more: RV_E_UNSUPPORTED).  d_out == d_ops folds in
+ * place (record j is written from record j and the call's own arrays alone); any other overlap is RV_E_ARG.  d_out == NULL counts
+ * only.  Instead of the sweep the kernels start from the records that are known at once (Const, a zero MulConst, no written read,
+ * a Mul with a zero-wire read) and propagate layer by layer through the readers of every known value; a list with nothing known at
+ * once costs no propagation, and one with no unwritten read either is copied.  info->device_rounds counts the layers.  After
+ * RV_FOLD_MAX_ROUNDS layers (environment, read at call time; default 65536) with the frontier not yet empty the call gives up on the
+ * device: it copies the list down, runs rv_ops_fold, uploads the result and reports on_device = 0.  The bytes are the same.  Work
+ * memory comes from the context arena and goes back before the call returns.  The call runs on the context's stream
+ * and synchronises it. */
+int rv_ops_fold_device(rv_ctx *ctx, const rv_op *d_ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, rv_op *d_out, rv_fold_info *info);
+/* out[0] = threads per workgroup of the propagation kernels, out[1] = the widest frontier one workgroup steps layer after layer
+ * inside one launch (the solo limit), out[2] = rounds between two looks of the host at the device words, out[3] = records per
+ * workgroup of the rewrite kernel, out[4] = RV_FOLD_MAX_ROUNDS as the next call would read it */
+int rv_hook_fold_limits(uint32_t out[5]);
+/* launches of this process so far: out[0] = rewrite kernels that wrote records, out[1] = count-only passes, out[2] = propagation
+ * launches (solo and wide together), out[3] = fall-backs to the host sweep */
+int rv_hook_fold_launches(uint64_t out[4]);
 
 /* ---- the same pruning for a list that passes through in windows ------------------
  * rv_pruner_* gives, for a list that arrives in feeds, exactly rv_ops_prune's kept set, records, old_index and class counts, for

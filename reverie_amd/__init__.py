@@ -9,5 +9,6 @@ from .stream import (StreamingBatchProver, StreamingBatchVerifier, StreamingEval
                      evaluate_streaming, prove_streaming, prove_streaming_batch, verify_streaming, verify_streaming_batch)
 from .compact import compact_wires  # noqa: F401
 from .prune import prune_ops  # noqa: F401
+from .fold import fold_ops  # noqa: F401
 from .link import Block, LinkPlan, Netlist  # noqa: F401
 from ._lib import ReverieError  # noqa: F401

@@ -123,6 +123,20 @@ def compact_program(prog, wc):
     return out, new_wc
 
 
+def fold_program(prog, wc):
+    """--fold: the program with its constants folded, record for record (rv_ops_fold, on the host; --parser device's op tensor by
+    rv_ops_fold_device, where it lies); the op count and the wire counts stay.  The counts go to stderr.  The proof of the folded
+    program is not the proof of the original: prover and verifier both pass --fold."""
+    from .fold import fold_ops
+
+    out, info = fold_ops(prog, wc)
+    print("fold: %d ops, %d rewritten (Mul to Const: %d GF(2), %d Z64; Mul to MulConst: %d GF(2), %d Z64; %d B2A to Const; %d other), %d known"
+          % (info["n_ops"], info["n_rewritten"], info["gf2_mul_to_const"], info["z64_mul_to_const"], info["gf2_mul_to_linear"],
+             info["z64_mul_to_linear"], info["b2a_to_const"], info["gf2_other_rewritten"] + info["z64_other_rewritten"], info["n_known"]),
+          file=sys.stderr)
+    return out, wc
+
+
 def prune_program(prog, wc, outputs_gf2=()):
     """--prune: the program without the ops no assertion (and none of outputs_gf2) depends on (rv_ops_prune, on the host; --parser
     device's op tensor by rv_ops_prune_device, where it lies); the wire counts stay.  The op counts before and after go to stderr.
@@ -234,7 +248,7 @@ def evaluate_gpu(prog, wc, witness, compiler="host"):
 
 
 def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_path=None, compact=False, windowed=True, in_windows=False,
-                  prune=False, prune_in_windows=False):
+                  prune=False, prune_in_windows=False, fold=False):
     """What a stream needs of a program file: (wire counts, pieces) -- pieces() returns a fresh iterator of (ops, Input counts or
     None) for every pass (`reverie_amd.stream.*_streaming_pieces`).
       rvops                              read through a memory map, STREAM_FEED_OPS records per piece; the wire counts come from one
@@ -246,12 +260,13 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
       mcircuit-bincode with the host parser, Bristol otherwise, and windowed=False: parsed whole, one piece
     compact (--compact-wires): the whole list is renumbered by liveness first, then fed, under the new counts.
     prune (--prune): the source is read whole too, and the ops no assertion depends on are dropped first (`prune_program`).
+    fold (--fold): the source is read whole too, and its constants are folded before anything else (`fold_program`).
     in_windows (--compact-windows; one of the three windowed sources above): the windows stay, and the pieces are renumbered by
     liveness window by window (`compact_windows`).
     prune_in_windows (--prune-windows; an rvops file): the windows stay, and the ops no assertion depends on are dropped window by
     window first (`prune_windows`)."""
     finish = compact_windows if in_windows else (lambda wc, pieces: (wc, pieces))
-    whole = compact or prune
+    whole = compact or prune or fold
     if fmt == "auto":
         fmt = "rvops" if program_path.endswith(".rvops") else "bristol"
     if fmt == "mcircuit-bincode" and parser == "device" and windowed and not whole:
@@ -268,6 +283,8 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
         return finish(wc, lambda: bristol.iter_device(program_path, int(window_mb) << 20, exp))
     if parser == "device" and fmt in ("bristol", "mcircuit-bincode"):  # the op tensor is the one piece (compacted where it lies)
         prog, wc = load_program_device(program_path, expected_path, fmt)
+        if fold:
+            prog, wc = fold_program(prog, wc)
         if prune:
             prog, wc = prune_program(prog, wc)
         if compact:
@@ -275,6 +292,8 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
         return wc, lambda: iter([(prog, None)])
     if fmt != "rvops":
         prog, wc = load_program(program_path, fmt, expected_path)
+        if fold:
+            prog, wc = fold_program(prog, wc)
         if prune:
             prog, wc = prune_program(prog, wc)
         n = len(prog)
@@ -293,6 +312,8 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
             z, g = largest_wires(np.asarray(prog[at:at + STREAM_FEED_OPS]))
             z64, gf2 = max(z64, z), max(gf2, g)
         wc = (z64, gf2)
+        if fold:
+            prog, wc = fold_program(np.asarray(prog), wc)
         if prune:
             prog, wc = prune_program(np.asarray(prog), wc)
             n = len(prog)
@@ -306,7 +327,7 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
 
 
 def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, device_compile=False, device_z64=False, device_b2a=False,
-                    compact=False, parser="host", window_mb=None, in_windows=False, prune=False, prune_in_windows=False):
+                    compact=False, parser="host", window_mb=None, in_windows=False, prune=False, prune_in_windows=False, fold=False):
     """`oneshot --evaluator stream`: the program evaluated in pieces with bounded device memory (rv_eval_stream_*), on the GPU like
     --evaluator gpu and with the same outcome.  An rvops file is read through a memory map, piece by piece; its wire counts come from
     one pass over the mapping.  window_mb (--window-mb, with --parser device): an mcircuit-bincode file is read in windows of that
@@ -319,7 +340,7 @@ def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, de
     source = _is_wit_source(witness)  # (--witness-window-mb: the bits are read as the pieces ask for them)
     wit = witness if source or hasattr(witness, "data_ptr") else np.ascontiguousarray(np.asarray(witness, dtype=np.uint8))
     wc, pieces = stream_pieces(program_path, fmt, parser, window_mb, expected_path, compact, windowed=window_mb is not None, in_windows=in_windows,
-                              prune=prune, prune_in_windows=prune_in_windows)
+                              prune=prune, prune_in_windows=prune_in_windows, fold=fold)
     se = StreamingEvaluator(wc, 1, max_chunk_ops, device_compile=device_compile, **({"device_z64": True} if device_z64 else {}),
                             **({"device_b2a": True} if device_b2a else {}))
     try:
@@ -358,7 +379,7 @@ def convert_source(a, fmt, device_parser: bool):
 
     path, exp_path = a.program_path, a.expected_outputs_path
     exp = parse_witness(open(exp_path, "rb").read()) if exp_path else None
-    windowed = a.window_mb is not None and device_parser and not a.compact_wires and not a.prune
+    windowed = a.window_mb is not None and device_parser and not a.compact_wires and not a.prune and not a.fold
     d = {"n_inputs": None, "n_outputs": 0, "prog": None, "pieces": None}
     head = bristol.head_info(path) if fmt == "bristol" else None
     if head is not None and exp is None:
@@ -401,6 +422,8 @@ def convert_source(a, fmt, device_parser: bool):
         else:
             d["prog"] = np.asarray(prog)
     d["wc_out"] = d["wc"]
+    if a.fold:
+        d["prog"], _ = fold_program(d["prog"], d["wc"])
     if a.prune:  # (a Bristol program without assertions is pruned against its outputs: its last n_outputs wires)
         outs = range(head["n_wires"] - d["n_outputs"], head["n_wires"]) if head is not None and d["n_outputs"] else ()
         d["prog"], _ = prune_program(d["prog"], d["wc"], outs)
@@ -474,7 +497,7 @@ def run_streamed(a, ap, device_parser: bool) -> int:
     if a.strict and a.reference_compat:
         ap.error("--strict and --reference-compat exclude each other")
     wc, pieces = stream_pieces(a.program_path, a.program_format, "device" if device_parser else "host", a.window_mb, a.expected_outputs_path,
-                               a.compact_wires, in_windows=a.compact_windows, prune=a.prune, prune_in_windows=a.prune_windows)
+                               a.compact_wires, in_windows=a.compact_windows, prune=a.prune, prune_in_windows=a.prune_windows, fold=a.fold)
     try:
         kw = dict(max_chunk_ops=a.max_chunk_ops, device_compile=a.compiler != "host", device_z64=a.compiler in ("device-z64", "device-b2a"),
                   device_b2a=a.compiler == "device-b2a")
@@ -567,6 +590,12 @@ def build_parser():
                          "on first (rv_ops_prune; with --parser device rv_ops_prune_device, where the list lies), before --compact-wires; the "
                          "op counts before and after are printed on stderr.  The proof is the proof of the pruned program, NOT of the original: "
                          "prove and verify must both be given --prune.  Refused with --window-mb and --compact-windows (a source read in windows)")
+    ap.add_argument("--fold", action="store_true",
+                    help="prove / verify / oneshot-zk / oneshot / convert, for a source that is read whole: fold constants first, record for "
+                         "record (rv_ops_fold; with --parser device rv_ops_fold_device, where the list lies), before --prune and "
+                         "--compact-wires; the counts are printed on stderr.  The proof is the proof of the folded program, NOT of the "
+                         "original: prove and verify must both be given --fold.  Refused with --window-mb, --compact-windows and "
+                         "--prune-windows (a source read in windows)")
     ap.add_argument("--prune-windows", action="store_true",
                     help="--stream, oneshot --evaluator stream, or convert, on an rvops file (its memory map is read in both directions): "
                          "--prune window by window (rv_pruner_*: the source is read once more for a scan pass and once, from the last window "
@@ -631,6 +660,8 @@ def main(argv=None) -> int:
         ap.error("--compact-wires with --operation oneshot needs --evaluator stream (the other evaluators keep no wire store)")
     if a.prune and (a.window_mb is not None or a.compact_windows):
         ap.error("--prune needs a source that is read whole: it cannot be combined with --window-mb or --compact-windows")
+    if a.fold and (a.window_mb is not None or a.compact_windows or a.prune_windows):
+        ap.error("--fold needs a source that is read whole: it cannot be combined with --window-mb, --compact-windows or --prune-windows")
     fmt = a.program_format
     if fmt == "auto":
         fmt = "rvops" if a.program_path.endswith(".rvops") else "bristol"
@@ -670,7 +701,7 @@ def main(argv=None) -> int:
                         a.max_chunk_ops, device_compile=a.compiler != "host", **({"device_z64": True} if a.compiler in ("device-z64", "device-b2a") else {}),
                         **({"device_b2a": True} if a.compiler == "device-b2a" else {}), **({"compact": True} if a.compact_wires else {}),
                         **({"parser": "device"} if device_parser else {}), **({"window_mb": a.window_mb} if a.window_mb is not None else {}),
-                        **({"in_windows": True} if a.compact_windows else {}), **({"prune": True} if a.prune else {}),
+                        **({"in_windows": True} if a.compact_windows else {}), **({"prune": True} if a.prune else {}), **({"fold": True} if a.fold else {}),
                         **({"prune_in_windows": True} if a.prune_windows else {}))
         print("()")
         return 0
@@ -680,6 +711,8 @@ def main(argv=None) -> int:
         prog, wc = load_program_device(a.program_path, a.expected_outputs_path, fmt)
     else:
         prog, wc = load_program(a.program_path, a.program_format, a.expected_outputs_path)
+    if a.fold:
+        prog, wc = fold_program(prog, wc)
     if a.prune:
         prog, wc = prune_program(prog, wc)
     if a.compact_wires:

@@ -118,6 +118,12 @@ class PruneInfo(C.Structure):  # rv_prune_info
                                           "unread_z64_inputs")] + [("device_rounds", C.c_uint32), ("on_device", C.c_uint32)]
 
 
+class FoldInfo(C.Structure):  # rv_fold_info
+    _fields_ = [(n, C.c_uint64) for n in ("n_ops", "n_rewritten", "n_known", "gf2_mul_to_const", "z64_mul_to_const", "gf2_mul_to_linear",
+                                          "z64_mul_to_linear", "b2a_to_const", "gf2_other_rewritten", "z64_other_rewritten",
+                                          "asserts_known_zero", "asserts_known_nonzero")] + [("device_rounds", C.c_uint32), ("on_device", C.c_uint32)]
+
+
 class Z64FRunArgs(C.Structure):  # rv_hook_z64f_run_args
     _fields_ = [("seeds", C.c_void_p), ("omit", C.c_void_p), ("R", C.c_uint32), ("key_path", C.c_uint32), ("first_block", C.c_uint64),
                 ("qg0", C.c_uint32), ("qgn", C.c_uint32), ("gates", C.c_void_p), ("n_gates", C.c_size_t), ("levels", C.c_void_p),
@@ -188,6 +194,7 @@ SYMBOLS = [
     "rv_ops_prune", "rv_ops_prune_device", "rv_hook_prune_limits", "rv_hook_prune_launches",
     "rv_ops_prune_windows_host", "rv_pruner_begin", "rv_pruner_scan", "rv_pruner_scan_end", "rv_pruner_mark", "rv_pruner_mark_end", "rv_pruner_feed",
     "rv_pruner_rewind", "rv_pruner_get_info", "rv_pruner_destroy",
+    "rv_ops_fold", "rv_ops_fold_device", "rv_hook_fold_limits", "rv_hook_fold_launches",
     "rv_hook_prove_schedule",
     "rv_hook_b3_plan", "rv_hook_b3_chunks", "rv_hook_b3_pair_small", "rv_hook_b3_pair_big_chunks", "rv_hook_b3_tree", "rv_hook_b3_pair_big_tree",
     "rv_hook_b3_incremental", "rv_hook_b3_join",
@@ -341,6 +348,10 @@ ARGTYPES = {
     "rv_ops_prune_device": [_P, _P, _Z, _Z, _Z, _P, _Z, _P, _Z, _P, _Z, C.POINTER(C.c_size_t), _P, C.POINTER(PruneInfo)],
     "rv_hook_prune_limits": [C.POINTER(C.c_uint32)],
     "rv_hook_prune_launches": [C.POINTER(C.c_uint64)],
+    "rv_ops_fold": [_P, _Z, _Z, _Z, _P, C.POINTER(FoldInfo)],
+    "rv_ops_fold_device": [_P, _P, _Z, _Z, _Z, _P, C.POINTER(FoldInfo)],
+    "rv_hook_fold_limits": [C.POINTER(C.c_uint32)],
+    "rv_hook_fold_launches": [C.POINTER(C.c_uint64)],
     # the same for a list read in windows
     "rv_ops_prune_windows_host": [_P, _Z, _Z, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _Z, C.POINTER(C.c_size_t), _P, C.POINTER(PruneInfo)],
     "rv_pruner_begin": [_P, _Z, _Z, _P, _Z, _P, _Z, C.POINTER(C.c_void_p)],

@@ -36,6 +36,7 @@
 #include "piece_sums.h"
 #include "prune_dev.h"
 #include "prune_win.h"
+#include "fold_dev.h"
 #include "verify_dev.h"
 #include "witness_text.h"
 
@@ -1659,3 +1660,4 @@ extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
 #include "witness_text.inc"
 #include "link.inc"
 #include "prune.inc"
+#include "fold.inc"

@@ -81,6 +81,19 @@ class Block:
         b.prune_info = info
         return b
 
+    def folded(self, ctx: Optional[Context] = None) -> "Block":
+        """The block with the constants of its own records folded (`fold.fold_ops`: a Mul by a Const becomes a MulConst, a gate of
+        known operands a Const; a value bound through a port or put on a wire by a netlist's `head` is not known here): the same
+        ports, wire counts and outputs, record for record, so it takes the original's place in a `Netlist`.  A device block is folded
+        where it lies, into a new tensor.  .fold_info: rv_fold_info as a dict.  `.folded().pruned()` then drops the Consts nothing
+        reads any more.  The linked program is another program: its proof is not the proof of the one linked from the unfolded block."""
+        from .fold import fold_ops
+
+        ops, info = fold_ops(self.ops, self.wire_counts, ctx=ctx)
+        b = Block(ops, self.wire_counts, n_ports=self.n_ports, outputs=self.outputs)
+        b.fold_info = info
+        return b
+
 
 class Instance:
     """What `Netlist.add` returns: where instance `index` lies in the global numbering."""

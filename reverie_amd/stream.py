@@ -38,6 +38,11 @@ proof of the pruned list -- prover and verifier must both pass prune=True.  The 
 the pieces are then pruned in windows (`prune.prune_pieces`, DESIGN §23.8: the source is read twice more, one of them backwards, so
 the pieces' callable needs `.backwards`), before `compact_wires`, and the result is the same.
 
+The whole-list one-shot functions take `fold` (default False) as well: constants are folded first (`fold.fold_ops`), before
+`prune` and `compact_wires`, and the info receives "fold".  The proof is the proof of the folded list -- prover and verifier must both
+pass fold=True.  The `*_streaming_pieces` functions refuse it: a read of an index no earlier op wrote is known 0, and a window's
+unwritten index is not the list's.
+
 The one-shot functions take `compact_wires` (default False): the whole op list is first renumbered by liveness (`compact.compact_wires`,
 DESIGN §17) -- on the host for host ops, by kernels for a GPU tensor -- and the stream begins with the new, smaller wire counts, so an
 SSA-numbered list no longer costs a wire-store row per gate.  Proofs and answers are the same bytes; the wire values
@@ -66,17 +71,22 @@ def _ops_ctx(ops, ctx: Optional[Context]) -> Context:
     return _device_ops(ops, ctx, "a stream of device ops")[2] if _is_device_ops(ops) else ctx or Context.default()
 
 
-def _compacted(ops, wire_counts, ctx: Context, wanted: bool, prune: bool = False):
-    """the op list and wire counts a one-shot call streams, and (rv_compact_info, rv_prune_info) -- None where compact_wires / prune
-    was not asked for.  Pruning (against the assertions: a stream has no outputs) comes first, then compaction."""
-    pinfo = cinfo = None
+def _compacted(ops, wire_counts, ctx: Context, wanted: bool, prune: bool = False, fold: bool = False):
+    """the op list and wire counts a one-shot call streams, and (rv_compact_info, rv_prune_info, rv_fold_info) -- None where
+    compact_wires / prune / fold was not asked for.  Folding comes first, then pruning (against the assertions: a stream has no
+    outputs), then compaction."""
+    pinfo = cinfo = finfo = None
+    if fold:
+        from .fold import fold_ops
+
+        ops, finfo = fold_ops(ops, wire_counts, ctx=ctx)
     if prune:
         from .prune import prune_ops
 
         ops, pinfo, _ = prune_ops(ops, wire_counts, ctx=ctx)
     if wanted:
         ops, wire_counts, cinfo = _compact.compact_wires(ops, wire_counts, ctx)
-    return ops, wire_counts, (cinfo, pinfo)
+    return ops, wire_counts, (cinfo, pinfo, finfo)
 
 
 class _Owned:
@@ -90,11 +100,14 @@ class _Owned:
             o.close()
 
 
-def _compacted_pieces(pieces, wire_counts, ctx: Optional[Context], wanted: bool, prune: bool = False):
+def _compacted_pieces(pieces, wire_counts, ctx: Optional[Context], wanted: bool, prune: bool = False, fold: bool = False):
     """the pieces and wire counts a `*_streaming_pieces` call streams, (rv_compact_info, rv_prune_info) (None where compact_wires /
     prune was not asked for) and what this call made and has to close (None: it made nothing -- pieces that a caller pruned or
     compacted are the caller's).  Pruning (in windows, against the assertions: `prune.prune_pieces`) comes first, then compaction
-    over the pruned pieces."""
+    over the pruned pieces.  fold is refused: the whole-list functions fold."""
+    if fold:
+        raise ValueError("fold=True needs the whole list: a read of an index no earlier op wrote is known 0, and a window's unwritten index "
+                         "is not the list's -- fold the list first (fold.fold_ops), or use the whole-list function")
     if not wanted and not prune:
         return pieces, wire_counts, None, None
     if not callable(pieces):
@@ -117,8 +130,10 @@ def _compacted_pieces(pieces, wire_counts, ctx: Optional[Context], wanted: bool,
 
 
 def _with_compact(info: dict, cinfo) -> dict:
-    """cinfo: rv_compact_info, or _compacted's pair"""
-    cinfo, pinfo = cinfo if isinstance(cinfo, tuple) else (cinfo, None)
+    """cinfo: rv_compact_info, or _compacted's tuple"""
+    cinfo, pinfo, finfo = (tuple(cinfo) + (None,))[:3] if isinstance(cinfo, tuple) else (cinfo, None, None)
+    if finfo is not None:
+        info["fold"] = finfo
     if pinfo is not None:
         info["prune"] = pinfo
     if cinfo is not None:
@@ -291,14 +306,14 @@ class StreamingProver:
 
 def prove_streaming(ops, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
                     ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                    device_proof: bool = False, compact_wires: bool = False, prune: bool = False) -> Tuple[Proof, dict]:
+                    device_proof: bool = False, compact_wires: bool = False, prune: bool = False, fold: bool = False) -> Tuple[Proof, dict]:
     """rv_prove_streaming: both passes over an op array in host memory -> (Proof, stream info).  A torch GPU tensor of ops, witnesses
     that are torch GPU tensors or device_proof=True (-> a DeviceProof): the same through rv_stream_begin / the feeds / the finish.
     compact_wires: the list is renumbered by liveness first and the stream begins with the new counts (the same proof)."""
     _check_device_z64(device_compile, device_z64, device_b2a)
     on_device = _wdev(wit_gf2, wit_z64, ctx, "prove_streaming", batched=False) is not None  # (refuses before a context is made)
     ctx = _ops_ctx(ops, ctx)
-    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune, fold)
     if _is_device_ops(ops) or on_device or device_proof:
         sp = StreamingProver(wire_counts, seeds, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
@@ -370,7 +385,7 @@ class StreamingVerifier:
 
 def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = True, max_chunk_ops: int = 0,
                      ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                     compact_wires: bool = False, prune: bool = False) -> Tuple[bool, dict]:
+                     compact_wires: bool = False, prune: bool = False, fold: bool = False) -> Tuple[bool, dict]:
     """rv_verify_streaming: one pass over an op array in host memory -> (ok, stream info).  A torch GPU tensor of ops: the same through
     rv_stream_verify_begin / rv_stream_feed_device / rv_stream_verify_finish.  compact_wires: as in prove_streaming (the same answer)."""
     _check_device_z64(device_compile, device_z64, device_b2a)
@@ -378,7 +393,7 @@ def verify_streaming(ops, wire_counts: Tuple[int, int], proof, strict: bool = Tr
     if on_device and ctx is None and isinstance(proof, DeviceProof):
         ctx = proof.ctx
     ctx = _ops_ctx(ops, ctx)
-    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune, fold)
     if _is_device_ops(ops) or on_device:
         sv = StreamingVerifier(wire_counts, proof, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
         try:
@@ -499,7 +514,7 @@ class StreamingBatchProver:
 
 def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
                           ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                          device_proof: bool = False, compact_wires: bool = False, prune: bool = False) -> "list[Proof]":
+                          device_proof: bool = False, compact_wires: bool = False, prune: bool = False, fold: bool = False) -> "list[Proof]":
     """rv_prove_streaming_batch: both passes over an op array in host memory for the witnesses wits_gf2 [B][n] / wits_z64
     [B][m] (B from whichever of the two is 2-D; the other may be []); seeds [B][256][16] or None.  `info` (a dict, optional) receives the stream's figures.
     Witnesses that are torch GPU tensors are read where they lie; device_proof=True returns DeviceProof views of one GPU tensor.
@@ -507,7 +522,7 @@ def prove_streaming_batch(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int],
     _check_device_z64(device_compile, device_z64, device_b2a)
     dw = _wdev(wits_gf2, wits_z64, ctx, "prove_streaming_batch", batched=True)  # (refuses before a context is made)
     ctx = _ops_ctx(ops, ctx)
-    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune, fold)
     if info is not None:
         _with_compact(info, cinfo)
     if dw is not None:  # (GPU tensors: [B][n] both, the batch from the descriptor)
@@ -600,7 +615,7 @@ class StreamingBatchVerifier:
 
 def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bool = True, max_chunk_ops: int = 0,
                            ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                           compact_wires: bool = False, prune: bool = False) -> "list[bool]":
+                           compact_wires: bool = False, prune: bool = False, fold: bool = False) -> "list[bool]":
     """rv_verify_streaming_batch: one pass over an op array in host memory for every proof -> one bool per proof.
     compact_wires: as in prove_streaming (the same answers; `info` also receives "compact")."""
     _check_device_z64(device_compile, device_z64, device_b2a)
@@ -608,7 +623,7 @@ def verify_streaming_batch(ops, wire_counts: Tuple[int, int], proofs, strict: bo
     n = len(proofs)
     if n == 0:
         return []
-    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune, fold)
     if info is not None:
         _with_compact(info, cinfo)
     on_device = any(_device_proof_bytes(p, ctx, "verify_streaming_batch") is not None for p in proofs)
@@ -710,7 +725,7 @@ class StreamingEvaluator:
 
 def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], max_chunk_ops: int = 0, values: bool = False,
                        ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                       compact_wires: bool = False, prune: bool = False) -> Evaluation:
+                       compact_wires: bool = False, prune: bool = False, fold: bool = False) -> Evaluation:
     """rv_evaluate_streaming: one op array in host memory, evaluated chunk by chunk with bounded device memory.  wits_gf2 /
     wits_z64: [B][n] (1-D for one witness; the batch is len(wits_gf2)).  Returns the array-shaped Evaluation of
     Circuit.evaluate_batch; `info` (a dict, optional) receives the stream's figures.  compact_wires: the list is renumbered by
@@ -720,7 +735,7 @@ def evaluate_streaming(ops, wits_gf2, wits_z64, wire_counts: Tuple[int, int], ma
     dims = [t.dim() for t in (wits_gf2, wits_z64) if hasattr(t, "data_ptr")]
     dw = _wdev(wits_gf2, wits_z64, ctx, "evaluate_streaming", batched=bool(dims) and max(dims) == 2)  # (refuses before a context is made)
     ctx = _ops_ctx(ops, ctx)
-    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune)
+    ops, wire_counts, cinfo = _compacted(ops, wire_counts, ctx, compact_wires, prune, fold)
     if info is not None:
         _with_compact(info, cinfo)
     if dw is not None:
@@ -799,7 +814,7 @@ def _feed_pieces(feed, pieces, wit_gf2, wit_z64):
 
 def prove_streaming_pieces(pieces, wit_gf2, wit_z64, wire_counts: Tuple[int, int], seeds=None, max_chunk_ops: int = 0,
                            ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False, device_b2a: bool = False,
-                           device_proof: bool = False, compact_wires: bool = False, prune: bool = False) -> "Tuple[Proof | DeviceProof, dict]":
+                           device_proof: bool = False, compact_wires: bool = False, prune: bool = False, fold: bool = False) -> "Tuple[Proof | DeviceProof, dict]":
     """`prove_streaming` for an op list that is never whole in memory: `pieces()` returns a fresh iterator of (ops, (n_input_gf2,
     n_input_z64)) for each of the two passes -- `program_file.iter_device` on a program file, say (its piece dicts serve as the
     counts).  ops: a host array or a torch GPU tensor of rv_op records; a host array may come with None, its Inputs are then counted
@@ -811,11 +826,12 @@ def prove_streaming_pieces(pieces, wit_gf2, wit_z64, wire_counts: Tuple[int, int
     depends on are dropped first, in windows (`prune.prune_pieces`: the pieces need `.backwards`, as `LinkPlan.pieces` and
     `prune.window_pieces` have it; the source is read for a scan pass and, backwards, for a mark pass), then compact_wires runs over
     the pruned pieces if asked for; the proof is the pruned list's (prover and verifier both pass prune=True), info carries "prune".
+    fold=True is refused (ValueError): a window's unwritten index is not the list's; fold the whole list first (`fold.fold_ops`).
     -> (Proof or DeviceProof, stream info)"""
     if not callable(pieces):
         raise TypeError("prove_streaming_pieces reads the pieces twice: pass a callable that returns a fresh iterator")
     g, z = _host_or_device_wit(wit_gf2, np.uint8), _host_or_device_wit(wit_z64, np.uint64)
-    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires, prune)
+    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires, prune, fold)
     sp = StreamingProver(wire_counts, seeds, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
     try:
         sp.same_cuts()
@@ -831,11 +847,11 @@ def prove_streaming_pieces(pieces, wit_gf2, wit_z64, wire_counts: Tuple[int, int
 
 def verify_streaming_pieces(pieces, wire_counts: Tuple[int, int], proof, strict: bool = True, max_chunk_ops: int = 0,
                             ctx: Optional[Context] = None, device_compile: bool = False, device_z64: bool = False,
-                            device_b2a: bool = False, compact_wires: bool = False, prune: bool = False) -> Tuple[bool, dict]:
+                            device_b2a: bool = False, compact_wires: bool = False, prune: bool = False, fold: bool = False) -> Tuple[bool, dict]:
     """`verify_streaming` for pieces as `prove_streaming_pieces` takes them (a callable or, the pass being one, an iterable; the
     counts are not looked at).  proof: bytes, a Proof, a bincode-form DeviceProof or a uint8 GPU tensor.  compact_wires: as in
     `prove_streaming_pieces` (a callable is needed then); prune: as there.  -> (ok, stream info)"""
-    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires, prune)
+    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires, prune, fold)
     sv = StreamingVerifier(wire_counts, proof, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
     try:
         for ops, _ in (pieces() if callable(pieces) else pieces):
@@ -850,12 +866,12 @@ def verify_streaming_pieces(pieces, wire_counts: Tuple[int, int], proof, strict:
 
 def evaluate_streaming_pieces(pieces, wits_gf2, wits_z64, wire_counts: Tuple[int, int], max_chunk_ops: int = 0, values: bool = False,
                               ctx: Optional[Context] = None, info: Optional[dict] = None, device_compile: bool = False, device_z64: bool = False,
-                              device_b2a: bool = False, compact_wires: bool = False, prune: bool = False) -> Evaluation:
+                              device_b2a: bool = False, compact_wires: bool = False, prune: bool = False, fold: bool = False) -> Evaluation:
     """`evaluate_streaming` for pieces as `prove_streaming_pieces` takes them, in one pass.  wits_gf2 / wits_z64: [B][n] (1-D for one
     witness), host arrays, torch GPU tensors or, for one GF(2) witness, a `witness.DeviceWindows`.  compact_wires: as in `prove_streaming_pieces` (wire values are those of the new
     indices); prune: as there.  -> the array-shaped Evaluation; `info` receives the stream's figures (and "compact", "prune")."""
     g, z = _host_or_device_wit(wits_gf2, np.uint8), _host_or_device_wit(wits_z64, np.uint64)
-    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires, prune)
+    pieces, wire_counts, cinfo, own = _compacted_pieces(pieces, wire_counts, ctx, compact_wires, prune, fold)
     batch = 1 if _is_wit_source(g) else g.shape[0] if g.ndim == 2 else 1
     se = StreamingEvaluator(wire_counts, batch, max_chunk_ops, ctx, device_compile, device_z64, device_b2a)
     try:
