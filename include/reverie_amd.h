@@ -1500,6 +1500,83 @@ int rv_ops_prune_windows_host(const rv_op *ops, size_t n_ops, size_t z64_wires, 
                               size_t n_outputs_gf2, const uint32_t *outputs_z64, size_t n_outputs_z64, const size_t *cuts, size_t n_cuts,
                               rv_op *out, size_t cap, size_t *n_out, uint32_t *old_index, rv_prune_info *info);
 
+/* ---- the same folding for a list that passes through in windows -------------------
+ * rv_folder_* gives, for a list that arrives in feeds, exactly rv_ops_fold's records and counts, for every list and every way of
+ * cutting it.  Values, reads, the known rule and the rewrite are the ones above.  Folding is a forward data-flow problem, so one
+ * pass suffices; what one window tells the next is one KNOWN byte and one 64-bit VALUE per wire index and domain: the state of the
+ * last value defined on the index so far.  The tables follow the counts in force and grow when a SizeHint raises one; every entry
+ * starts known, value 0 -- the zero wire: a read of an index no earlier op of the LIST wrote is known 0, as in rv_ops_fold.
+ *
+ * THE WINDOW STEP, for a feed [lo, hi) and the tables K, V as they stand at lo:
+ *   1. the feed is validated as rv_ops_fold validates, the counts in force carried from feed to feed; the first bad op in op order
+ *      gives its code at the feed that holds it, nothing is written for that feed, and only destroy is accepted afterwards;
+ *   2. every read is resolved to the last writer of its index inside the window and before the reader; a read with no such writer
+ *      ESCAPES the window, and is known exactly if K[domain][index] is set, with the value V[domain][index];
+ *   3. seed, pairs, propagation and rewrite are rv_ops_fold_device's, escaping reads taken from the tables: an op with an unknown
+ *      escaping read is never known because its other reads are (a Mul with a known 0 read still is; a B2A needs all 64 either way);
+ *   4. AFTER the rewrite has read the tables: for every index any op of the window writes, the window's LAST writer's (known, value)
+ *      goes to the tables (value 0 where it is not known).  An index read as escaping and written later in the window ends on the
+ *      writer's state;
+ *   5. n_known and the nine class counts add up over the feeds.
+ * device_rounds is the SUM of the layers over the feeds -- for one feed that holds the whole list rv_ops_fold_device's figure,
+ * otherwise it depends on the cuts; on_device is 0 if any feed fell back (a feed whose propagation reaches RV_FOLD_MAX_ROUNDS layers
+ * is copied down with the tables, stepped on the host and its records, tables and log entries uploaded: the bytes are the same, the
+ * other feeds stay on the device).  The shortcut of a feed is "no op known at once and no escaping read that is known": the records
+ * are copied; the tables are updated all the same.
+ *
+ * THE LOG (RV_FOLDER_KEEP_LOG) answers passes that do not run forwards -- rv_pruner_mark reads its windows from the last to the
+ * first.  Every record the rewrite changed is appended to a log in device memory as (ordinal in the whole list, new record),
+ * ascending by ordinal.  A replay of ANY window [first, first + n) of the source finds its slice of the log by two lower bounds,
+ * copies the source records to d_out unless in place, and stores the slice's records over them.  It propagates nothing and reads
+ * no table.
+ *
+ * THE CALLS:  begin -> feed* -> end [-> rewind -> feed* -> end]... ; after an end, with the log: replay* -> replay_end, any number
+ *             of rounds -> destroy.   Feeds of 0 and 1 ops are allowed.  `ops` is host memory (uploaded for the call) or, with
+ * ops_on_device, memory of the context's device with rv_ops_fold_device's conventions, checked before any launch.
+ *   feed        d_out: device memory for n_ops records; NULL counts (and logs) only; d_out == a device `ops` folds in place; any other
+ *               overlap is RV_E_ARG.  In a pass after a rewind, more ops than the first pass had is RV_E_ARG, and the feed that
+ *               reaches the list's length answers RV_E_ARG when the pass's position-keyed digest (rv_compactor_*'s) is not the first
+ *               pass's.
+ *   end         fixes the length and the digest (first pass), fills the info (may be NULL) with this pass's counts.  After a rewind:
+ *               RV_E_ARG when the pass stopped short.
+ *   rewind      after end: the tables back to known 0, the counts in force back to the declared ones, the log emptied; the next
+ *               feed is op 0 again.
+ *   replay      needs the log; after end; windows in any order; d_out as for feed, but not NULL.  A window beyond the list is
+ *               RV_E_ARG.
+ *   replay_end  RV_E_ARG unless the replays since the last replay_end (or end) covered every ordinal exactly once and their digest
+ *               is the folded pass's.  The next round begins either way.
+ * A call out of order is RV_E_ARG and leaves the object as it was.  2^31 ops or more in all or in one feed, or a wire count in force
+ * of 2^31 or more: RV_E_UNSUPPORTED.  After a validation code, RV_E_UNSUPPORTED, RV_E_NOMEM or RV_E_DEVICE only destroy is accepted.
+ * MEMORY, from the context arena.  Held between calls (state_bytes): nine bytes per table entry of both domains, and the words; the
+ * tables begin at the declared counts, and one that a SizeHint outgrows at least doubles (at most twice nine bytes per wire index).  The
+ * log (log_bytes): 28 bytes per entry of its capacity, which doubles when it is full -- at most twice 28 bytes per rewritten op above
+ * the first 1024 entries, and nothing per op that is not rewritten.  Per call, given back before it returns (peak_feed_bytes: the
+ * largest so far): what rv_ops_fold_device takes for a list of the feed's length, plus 24 bytes per op of an uploaded host feed. */
+#define RV_FOLDER_KEEP_LOG 1u
+typedef struct rv_folder rv_folder;
+typedef struct rv_folder_info {
+    uint64_t total_ops;       /* the list's length (before the first end: the ops fed so far) */
+    uint64_t state_bytes;     /* device memory held between calls, the log apart */
+    uint64_t log_bytes;       /* device memory of the log */
+    uint64_t log_records;     /* records in the log: after end, rv_fold_info's n_rewritten */
+    uint64_t peak_feed_bytes; /* the largest work memory of one call so far, an uploaded feed included */
+    uint64_t feeds;           /* feeds that held an op, over all passes */
+    uint64_t host_feeds;      /* of these: stepped on the host (the fall-back) */
+} rv_folder_info;             /* 56 bytes */
+int rv_folder_begin(rv_ctx *ctx, size_t z64_wires, size_t gf2_wires, uint32_t flags, rv_folder **out);
+int rv_folder_feed(rv_folder *f, const rv_op *ops, size_t n_ops, int ops_on_device, rv_op *d_out);
+int rv_folder_end(rv_folder *f, rv_fold_info *info /* may be NULL */);
+int rv_folder_rewind(rv_folder *f);
+int rv_folder_replay(rv_folder *f, const rv_op *ops, size_t n_ops, int ops_on_device, uint64_t first_ordinal, rv_op *d_out);
+int rv_folder_replay_end(rv_folder *f);
+int rv_folder_get_info(const rv_folder *f, rv_folder_info *info);
+void rv_folder_destroy(rv_folder *f);
+/* host only, no GPU: the forward sweep over the windows [0, cuts[0]), [cuts[0], cuts[1]), .. [cuts[n_cuts - 1], n_ops) with one
+ * state -- the window step's definition in C.  cuts: n_cuts non-decreasing positions, none above n_ops (RV_E_ARG otherwise).
+ * Everything else, and every byte of the result, is rv_ops_fold's (which is this call without a cut). */
+int rv_ops_fold_windows_host(const rv_op *ops, size_t n_ops, size_t z64_wires, size_t gf2_wires, const size_t *cuts, size_t n_cuts,
+                             rv_op *out, rv_fold_info *info);
+
 /* ---- parity-test hooks: each mirrors one reference function so tests can compare the
  * HIP path with the oracle piecewise ---- */
 /* PRG::new + gen (crypto/prg.rs:16-37) on the GPU: n_keys keys, blocks [first, first+n_blocks) each */

@@ -150,6 +150,24 @@ def prune_program(prog, wc, outputs_gf2=()):
     return out, wc
 
 
+FOLD_LINE = ("fold: %d ops, %d rewritten (Mul to Const: %d GF(2), %d Z64; Mul to MulConst: %d GF(2), %d Z64; %d B2A to Const; %d other), "
+             "%d known")
+
+
+def fold_windows(wc, pieces):
+    """--fold-windows: the pieces of a source that is read in windows, with their constants folded window by window and the known
+    values carried from one window to the next (fold.fold_pieces: one counting pass runs here and keeps the rewritten records on
+    the device; every later pass reads the source again, backwards too where the source can); --fold's line goes to stderr.  The op
+    count and the wire counts stay."""
+    from .fold import fold_pieces
+
+    pieces2, info = fold_pieces(pieces, wc)
+    print(FOLD_LINE % (info["n_ops"], info["n_rewritten"], info["gf2_mul_to_const"], info["z64_mul_to_const"], info["gf2_mul_to_linear"],
+                       info["z64_mul_to_linear"], info["b2a_to_const"], info["gf2_other_rewritten"] + info["z64_other_rewritten"], info["n_known"]),
+          file=sys.stderr)
+    return pieces2
+
+
 def prune_windows(wc, pieces):
     """--prune-windows: the pieces of an rvops file (`prune.window_pieces` over its memory map: both directions), without the ops no
     assertion depends on (prune.prune_pieces: the scan pass and the backward mark pass run here, every later pass reads the source
@@ -157,6 +175,8 @@ def prune_windows(wc, pieces):
     from .prune import prune_pieces
 
     pieces2, info = prune_pieces(pieces, wc)
+    if hasattr(pieces, "folder"):  # (--fold-windows underneath: `close_pruner` finds it)
+        pieces2.folder = pieces.folder
     print("prune: %d ops -> %d (dropped: %d GF(2) Mul, %d Z64 Mul, %d B2A, %d Random, %d other)"
           % (info["n_kept"] + info["n_dropped"], info["n_kept"], info["dropped_gf2_mul"], info["dropped_z64_mul"], info["dropped_b2a"],
              info["dropped_gf2_random"] + info["dropped_z64_random"], info["dropped_gf2_other"] + info["dropped_z64_other"]), file=sys.stderr)
@@ -172,14 +192,18 @@ def compact_windows(wc, pieces):
     print("compact-wires: wire counts (z64, gf2) %s -> %s" % (tuple(int(x) for x in wc), new_wc), file=sys.stderr)
     if hasattr(pieces, "pruner"):  # (--prune-windows underneath: `close_pruner` finds it)
         pieces2.pruner = pieces.pruner
+    if hasattr(pieces, "folder"):  # (--fold-windows underneath)
+        pieces2.folder = pieces.folder
     return new_wc, pieces2
 
 
 def close_pruner(pieces):
-    """after the last pass over `pieces`: --prune-windows' pruner gives its marks and needed tables back to the device"""
-    pruner = getattr(pieces, "pruner", None)
-    if pruner is not None:
-        pruner.close()
+    """after the last pass over `pieces`: --prune-windows' pruner gives its marks and needed tables back to the device, and
+    --fold-windows' folder its tables and its log"""
+    for name in ("pruner", "folder"):
+        owner = getattr(pieces, name, None)
+        if owner is not None:
+            owner.close()
 
 
 def evaluate_clear(prog, witness):
@@ -248,7 +272,7 @@ def evaluate_gpu(prog, wc, witness, compiler="host"):
 
 
 def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_path=None, compact=False, windowed=True, in_windows=False,
-                  prune=False, prune_in_windows=False, fold=False):
+                  prune=False, prune_in_windows=False, fold=False, fold_in_windows=False):
     """What a stream needs of a program file: (wire counts, pieces) -- pieces() returns a fresh iterator of (ops, Input counts or
     None) for every pass (`reverie_amd.stream.*_streaming_pieces`).
       rvops                              read through a memory map, STREAM_FEED_OPS records per piece; the wire counts come from one
@@ -264,8 +288,11 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
     in_windows (--compact-windows; one of the three windowed sources above): the windows stay, and the pieces are renumbered by
     liveness window by window (`compact_windows`).
     prune_in_windows (--prune-windows; an rvops file): the windows stay, and the ops no assertion depends on are dropped window by
-    window first (`prune_windows`)."""
-    finish = compact_windows if in_windows else (lambda wc, pieces: (wc, pieces))
+    window first (`prune_windows`).
+    fold_in_windows (--fold-windows; one of the three windowed sources): the windows stay, and the constants are folded window by
+    window before anything else (`fold_windows`)."""
+    after_fold = compact_windows if in_windows else (lambda wc, pieces: (wc, pieces))
+    finish = (lambda wc, pieces: after_fold(wc, fold_windows(wc, pieces))) if fold_in_windows and not prune_in_windows else after_fold
     whole = compact or prune or fold
     if fmt == "auto":
         fmt = "rvops" if program_path.endswith(".rvops") else "bristol"
@@ -322,25 +349,32 @@ def stream_pieces(program_path, fmt, parser="host", window_mb=None, expected_pat
     if prune_in_windows:
         from .prune import window_pieces
 
-        return finish(wc, prune_windows(wc, window_pieces(prog, STREAM_FEED_OPS))[0])
+        source = window_pieces(prog, STREAM_FEED_OPS)
+        return finish(wc, prune_windows(wc, fold_windows(wc, source) if fold_in_windows else source)[0])
+    if fold_in_windows:
+        from .prune import window_pieces
+
+        return finish(wc, window_pieces(prog, STREAM_FEED_OPS))
     return finish(wc, lambda: ((np.asarray(prog[at:at + STREAM_FEED_OPS]), None) for at in range(0, max(n, 1), STREAM_FEED_OPS)))
 
 
 def evaluate_stream(program_path, fmt, expected_path, witness, max_chunk_ops, device_compile=False, device_z64=False, device_b2a=False,
-                    compact=False, parser="host", window_mb=None, in_windows=False, prune=False, prune_in_windows=False, fold=False):
+                    compact=False, parser="host", window_mb=None, in_windows=False, prune=False, prune_in_windows=False, fold=False,
+                    fold_in_windows=False):
     """`oneshot --evaluator stream`: the program evaluated in pieces with bounded device memory (rv_eval_stream_*), on the GPU like
     --evaluator gpu and with the same outcome.  An rvops file is read through a memory map, piece by piece; its wire counts come from
     one pass over the mapping.  window_mb (--window-mb, with --parser device): an mcircuit-bincode file is read in windows of that
     many MiB on the GPU, and so is a Bristol file; without it, either is parsed whole.  compact (--compact-wires): the whole list is renumbered by liveness first
     (in host memory: 24 bytes per op, against a wire-store row per gate of an SSA list) and the stream begins with the new counts;
     in_windows (--compact-windows): the pieces are renumbered window by window instead, and nothing is whole in memory.
-    prune_in_windows (--prune-windows): the ops no assertion depends on are dropped window by window first."""
+    prune_in_windows (--prune-windows): the ops no assertion depends on are dropped window by window first.
+    fold_in_windows (--fold-windows): the constants are folded window by window before that."""
     from .stream import StreamingEvaluator, _is_wit_source, _piece_inputs
 
     source = _is_wit_source(witness)  # (--witness-window-mb: the bits are read as the pieces ask for them)
     wit = witness if source or hasattr(witness, "data_ptr") else np.ascontiguousarray(np.asarray(witness, dtype=np.uint8))
     wc, pieces = stream_pieces(program_path, fmt, parser, window_mb, expected_path, compact, windowed=window_mb is not None, in_windows=in_windows,
-                              prune=prune, prune_in_windows=prune_in_windows, fold=fold)
+                              prune=prune, prune_in_windows=prune_in_windows, fold=fold, fold_in_windows=fold_in_windows)
     se = StreamingEvaluator(wc, 1, max_chunk_ops, device_compile=device_compile, **({"device_z64": True} if device_z64 else {}),
                             **({"device_b2a": True} if device_b2a else {}))
     try:
@@ -389,10 +423,14 @@ def convert_source(a, fmt, device_parser: bool):
         for _, piece in program_file.iter_device(path, window, scan=True, info=info):  # the scan pass the wire counts come from
             n_in += piece["n_input_gf2"]
         d.update(wc=info["wire_counts"], n_ops=info["n_ops"], n_inputs=n_in, pieces=lambda: program_file.iter_device(path, window))
+        if a.fold_windows:
+            d["pieces"] = fold_windows(d["wc"], d["pieces"])
     elif fmt == "bristol" and windowed:
         window = int(a.window_mb) << 20
         d.update(wc=bristol.wire_counts(path, exp), n_ops=head["n_inputs"] + head["n_gates"] + 2 * len(exp if exp is not None else ()),
                  n_inputs=head["n_inputs"], pieces=lambda: bristol.iter_device(path, window, exp))
+        if a.fold_windows:
+            d["pieces"] = fold_windows(d["wc"], d["pieces"])
     elif device_parser:
         prog, wc = load_program_device(path, exp_path, fmt)
         d.update(wc=wc, n_ops=len(prog), prog=prog)
@@ -413,10 +451,14 @@ def convert_source(a, fmt, device_parser: bool):
             z, g = largest_wires(piece)
             z64, gf2, n_in = max(z64, z), max(gf2, g), n_in + int(np.count_nonzero((piece["domain"] == 0) & (piece["opcode"] == 0)))
         d.update(wc=(z64, gf2), n_ops=n, n_inputs=n_in)
-        if a.prune_windows:
+        if a.prune_windows or a.fold_windows:
             from .prune import window_pieces
 
-            d["pieces"], d["n_ops"] = prune_windows(d["wc"], window_pieces(prog, STREAM_FEED_OPS))
+            d["pieces"] = window_pieces(prog, STREAM_FEED_OPS)
+            if a.fold_windows:
+                d["pieces"] = fold_windows(d["wc"], d["pieces"])
+            if a.prune_windows:
+                d["pieces"], d["n_ops"] = prune_windows(d["wc"], d["pieces"])
         elif a.compact_windows:
             d["pieces"] = lambda: ((np.asarray(prog[at:at + STREAM_FEED_OPS]), None) for at in range(0, max(n, 1), STREAM_FEED_OPS))
         else:
@@ -497,7 +539,8 @@ def run_streamed(a, ap, device_parser: bool) -> int:
     if a.strict and a.reference_compat:
         ap.error("--strict and --reference-compat exclude each other")
     wc, pieces = stream_pieces(a.program_path, a.program_format, "device" if device_parser else "host", a.window_mb, a.expected_outputs_path,
-                               a.compact_wires, in_windows=a.compact_windows, prune=a.prune, prune_in_windows=a.prune_windows, fold=a.fold)
+                               a.compact_wires, in_windows=a.compact_windows, prune=a.prune, prune_in_windows=a.prune_windows, fold=a.fold,
+                               fold_in_windows=a.fold_windows)
     try:
         kw = dict(max_chunk_ops=a.max_chunk_ops, device_compile=a.compiler != "host", device_z64=a.compiler in ("device-z64", "device-b2a"),
                   device_b2a=a.compiler == "device-b2a")
@@ -595,7 +638,15 @@ def build_parser():
                          "record (rv_ops_fold; with --parser device rv_ops_fold_device, where the list lies), before --prune and "
                          "--compact-wires; the counts are printed on stderr.  The proof is the proof of the folded program, NOT of the "
                          "original: prove and verify must both be given --fold.  Refused with --window-mb, --compact-windows and "
-                         "--prune-windows (a source read in windows)")
+                         "--prune-windows (a source read in windows: --fold-windows folds that)")
+    ap.add_argument("--fold-windows", action="store_true",
+                    help="--stream, oneshot --evaluator stream, or convert, on a source that is read in windows (an rvops file; with "
+                         "--parser device an mcircuit-bincode file, or a Bristol file with --window-mb): --fold window by window, the known "
+                         "values carried from one window to the next (rv_folder_*: the source is read once more for a counting pass that keeps "
+                         "the rewritten records on the device; every later pass replays them over the source's windows), so that the op list is "
+                         "never whole in memory; the records, the proof bytes and the stderr line are --fold's.  It runs first: combines with "
+                         "--prune-windows and --compact-windows.  prove and verify must both be given it.  A source that is read whole is "
+                         "refused: --fold folds it")
     ap.add_argument("--prune-windows", action="store_true",
                     help="--stream, oneshot --evaluator stream, or convert, on an rvops file (its memory map is read in both directions): "
                          "--prune window by window (rv_pruner_*: the source is read once more for a scan pass and once, from the last window "
@@ -666,6 +717,18 @@ def main(argv=None) -> int:
     if fmt == "auto":
         fmt = "rvops" if a.program_path.endswith(".rvops") else "bristol"
     device_parser = a.parser == "device" and fmt in ("bristol", "mcircuit-bincode")
+    if a.fold_windows:
+        if a.fold or a.prune or a.compact_wires:
+            ap.error("--fold-windows keeps the windows: it cannot be combined with --fold, --prune or --compact-wires (--prune-windows and "
+                     "--compact-windows are its partners)")
+        streamed = a.operation == "convert" or a.stream or (a.operation == "oneshot" and a.evaluator == "stream")
+        # (convert reads a program file in windows only with --window-mb, whatever --stream says: `convert_source`)
+        default_window = fmt == "mcircuit-bincode" and a.stream and a.operation != "convert"
+        windows = fmt == "rvops" or (device_parser and (a.window_mb is not None or default_window))
+        if not (streamed and windows):
+            ap.error("--fold-windows needs a source that is read in windows: --stream, oneshot --evaluator stream or convert, with an rvops "
+                     "file, or with --parser device and an mcircuit-bincode file or a Bristol file and --window-mb; a source that is read "
+                     "whole is folded by --fold")
     if a.prune_windows:
         if fmt != "rvops":
             ap.error("--prune-windows needs a source that can be read backwards: an rvops file (convert the program to rvops first)")
@@ -702,7 +765,7 @@ def main(argv=None) -> int:
                         **({"device_b2a": True} if a.compiler == "device-b2a" else {}), **({"compact": True} if a.compact_wires else {}),
                         **({"parser": "device"} if device_parser else {}), **({"window_mb": a.window_mb} if a.window_mb is not None else {}),
                         **({"in_windows": True} if a.compact_windows else {}), **({"prune": True} if a.prune else {}), **({"fold": True} if a.fold else {}),
-                        **({"prune_in_windows": True} if a.prune_windows else {}))
+                        **({"prune_in_windows": True} if a.prune_windows else {}), **({"fold_in_windows": True} if a.fold_windows else {}))
         print("()")
         return 0
     if a.stream:

@@ -124,6 +124,10 @@ class FoldInfo(C.Structure):  # rv_fold_info
                                           "asserts_known_zero", "asserts_known_nonzero")] + [("device_rounds", C.c_uint32), ("on_device", C.c_uint32)]
 
 
+class FolderInfo(C.Structure):  # rv_folder_info
+    _fields_ = [(n, C.c_uint64) for n in ("total_ops", "state_bytes", "log_bytes", "log_records", "peak_feed_bytes", "feeds", "host_feeds")]
+
+
 class Z64FRunArgs(C.Structure):  # rv_hook_z64f_run_args
     _fields_ = [("seeds", C.c_void_p), ("omit", C.c_void_p), ("R", C.c_uint32), ("key_path", C.c_uint32), ("first_block", C.c_uint64),
                 ("qg0", C.c_uint32), ("qgn", C.c_uint32), ("gates", C.c_void_p), ("n_gates", C.c_size_t), ("levels", C.c_void_p),
@@ -195,6 +199,8 @@ SYMBOLS = [
     "rv_ops_prune_windows_host", "rv_pruner_begin", "rv_pruner_scan", "rv_pruner_scan_end", "rv_pruner_mark", "rv_pruner_mark_end", "rv_pruner_feed",
     "rv_pruner_rewind", "rv_pruner_get_info", "rv_pruner_destroy",
     "rv_ops_fold", "rv_ops_fold_device", "rv_hook_fold_limits", "rv_hook_fold_launches",
+    "rv_ops_fold_windows_host", "rv_folder_begin", "rv_folder_feed", "rv_folder_end", "rv_folder_rewind", "rv_folder_replay", "rv_folder_replay_end",
+    "rv_folder_get_info", "rv_folder_destroy",
     "rv_hook_prove_schedule",
     "rv_hook_b3_plan", "rv_hook_b3_chunks", "rv_hook_b3_pair_small", "rv_hook_b3_pair_big_chunks", "rv_hook_b3_tree", "rv_hook_b3_pair_big_tree",
     "rv_hook_b3_incremental", "rv_hook_b3_join",
@@ -352,6 +358,15 @@ ARGTYPES = {
     "rv_ops_fold_device": [_P, _P, _Z, _Z, _Z, _P, C.POINTER(FoldInfo)],
     "rv_hook_fold_limits": [C.POINTER(C.c_uint32)],
     "rv_hook_fold_launches": [C.POINTER(C.c_uint64)],
+    "rv_ops_fold_windows_host": [_P, _Z, _Z, _Z, _P, _Z, _P, C.POINTER(FoldInfo)],
+    "rv_folder_begin": [_P, _Z, _Z, C.c_uint32, C.POINTER(C.c_void_p)],
+    "rv_folder_feed": [_P, _P, _Z, C.c_int, _P],
+    "rv_folder_end": [_P, C.POINTER(FoldInfo)],
+    "rv_folder_rewind": [_P],
+    "rv_folder_replay": [_P, _P, _Z, C.c_int, C.c_uint64, _P],
+    "rv_folder_replay_end": [_P],
+    "rv_folder_get_info": [_P, C.POINTER(FolderInfo)],
+    "rv_folder_destroy": [_P],
     # the same for a list read in windows
     "rv_ops_prune_windows_host": [_P, _Z, _Z, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _Z, C.POINTER(C.c_size_t), _P, C.POINTER(PruneInfo)],
     "rv_pruner_begin": [_P, _Z, _Z, _P, _Z, _P, _Z, C.POINTER(C.c_void_p)],
@@ -441,7 +456,7 @@ def lib():
             if name in ("rv_ctx_destroy", "rv_circuit_destroy", "rv_shard_destroy", "rv_free", "rv_stream_abort", "rv_comm_destroy",
                         "rv_eval_stream_abort", "rv_program_reader_destroy", "rv_bristol_reader_destroy", "rv_compactor_destroy",
                         "rv_bristol_writer_destroy", "rv_program_writer_destroy", "rv_witness_reader_destroy", "rv_link_plan_destroy",
-                        "rv_pruner_destroy"):
+                        "rv_pruner_destroy", "rv_folder_destroy"):
                 fn.restype = None
             elif name in ("rv_hook_early_proofs", "rv_hook_open_direct_proofs", "rv_hook_verify_vc_count", "rv_hook_ops_cache_hits", "rv_hook_overlap_commits",
                           "rv_hook_verify_proof_bytes", "rv_hook_stream_device_chunks"):

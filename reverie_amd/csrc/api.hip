@@ -37,6 +37,7 @@
 #include "prune_dev.h"
 #include "prune_win.h"
 #include "fold_dev.h"
+#include "fold_win.h"
 #include "verify_dev.h"
 #include "witness_text.h"
 

@@ -1,14 +1,15 @@
 // Constants folded in op lists: on the host (rv_ops_fold, fold.cpp) and on the GPU (fold_dev.hip).  The rule is in
 // include/reverie_amd.h, the steps in DESIGN §24 and at the head of fold_dev.hip.
 //
-// ONE RECORD'S PART IN THE RULE -- whether it is known before anything is propagated (fd_seed), whether it is known given what is
-// known of its reads (fd_known), the value of a known record (fd_eval, fd_b2a_bit), the record that replaces it (fd_rewrite) and the
+// ONE RECORD'S PART IN THE RULE -- whether it is known given what is known of its reads (fd_known; before anything is propagated:
+// given the reads that have no producer -- fd_seed is that for a list that stands alone), the value of a known record (fd_eval, fd_b2a_bit), the record that replaces it (fd_rewrite) and the
 // class it is counted in (fd_class) -- is decided here and nowhere else.  What a record defines and reads, compile_ops' check of it,
 // the search that resolves a read and the way a tile's image is cut into stores are prune.h's.  The host sweep, the kernels and the
 // CPU model of tests/fold_model.cpp all call these functions.
 //
 // Everything here is plain C++ (the CPU model compiles it with g++); fold_dev.h holds what needs HIP.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "prune.h"
@@ -48,7 +49,9 @@ PR_HD inline bool fd_known(const rv_op& op, const bool* kn, const uint64_t* v) {
         default: return false;  // Input, Random
     }
 }
-// Is it known before any propagation?  unwritten[k]: read k names an index no earlier op wrote (the zero wire, known 0)
+// Is it known before any propagation, in a list that stands alone?  unwritten[k]: read k names an index no earlier op wrote (the
+// zero wire, known 0).  This is fd_known with the values 0: the seed kernel calls fd_known itself, with the values a window's
+// tables hold for such reads (null tables: 0, this function), and the CPU model of the whole-list call keeps this form.
 PR_HD inline bool fd_seed(const rv_op& op, const bool* unwritten) {
     const uint64_t zero[2] = {0, 0};
     return fd_known(op, unwritten, zero);
@@ -111,6 +114,77 @@ PR_HD inline int fd_class(const rv_op& op, const rv_op& now, const bool* kn, con
     const int z = op.domain == RV_DOM_Z64 ? 1 : 0;
     if (op.opcode == RV_OP_MUL) return (now.opcode == RV_OP_CONST ? FD_C_MUL_CONST_G : FD_C_MUL_LIN_G) + z;
     return FD_C_OTHER_G + z;
+}
+
+// ---- the window step: the rule on ops [lo, hi) of a list that passes through in windows, from the first window to
+// the last.  What a window hears from the ones before it is one KNOWN byte and one VALUE word per index and domain: the state of the
+// last value defined on the index ahead of the window (nothing written yet: known 0, the zero wire).  The host form is the forward
+// sweep itself; the device form seeds and propagates as the whole-list call does, with an escaping read taken from the tables and
+// the decisions below around it. ----
+
+// a known table over memory the caller holds, one byte and one word per index (the host sweep's other table, a hash map, is fold.cpp's)
+struct FdDense {
+    uint8_t* k;
+    uint64_t* v;
+    bool get(uint32_t w, uint64_t* val) const {
+        *val = v[w];
+        return k[w] != 0;
+    }
+    void set(uint32_t w, bool known, uint64_t val) { k[w] = known ? 1 : 0, v[w] = known ? val : 0; }
+};
+// The forward sweep over n valid records with the state as it stands before them (st[PR_G], st[PR_Z]); the state goes out as it
+// stands behind them.  out (may be null, may be ops) receives record j's replacement at j; the counts are added to cls[FD_CLASSES]
+// and *n_known.
+template <class Known>
+inline void fd_window_sweep(const rv_op* ops, size_t n, Known st[2], rv_op* out, uint64_t* cls, uint64_t* n_known) {
+    for (size_t i = 0; i < n; i++) {
+        const rv_op op = ops[i];  // (a copy: out may be ops)
+        const uint32_t r = pr_n_reads(op);
+        const int rd = pr_read_dom(op), d = pr_def(op);
+        bool kn[64] = {};
+        uint64_t v[64] = {};
+        for (uint32_t k = 0; k < r; k++) {
+            kn[k] = st[rd].get(pr_read(op, k), &v[k]);
+            if (!kn[k]) v[k] = 0;
+        }
+        const bool known = fd_known(op, kn, v);
+        uint64_t val = 0;
+        if (known && op.domain == RV_DOM_B2A)
+            for (uint32_t k = 0; k < 64; k++) val |= fd_b2a_bit(k, v[k]);
+        else if (known)
+            val = fd_eval(op, v);
+        const rv_op now = fd_rewrite(op, known, val, kn, v);
+        const int c = fd_class(op, now, kn, v);
+        if (c >= 0) cls[c]++;
+        if (known) (*n_known)++;
+        if (d >= 0) st[d].set(op.dst, known, val);
+        if (out) out[i] = now;
+    }
+}
+// fd_window_sweep over tables the caller holds (fold.cpp; K, V: [PR_G], [PR_Z]) -- the fall-back of one windowed device feed
+void fold_window_dense(const rv_op* ops, size_t n, uint8_t* const K[2], uint64_t* const V[2], rv_op* out, uint64_t* cls, uint64_t* n_known);
+// was the record rewritten (it counts in one of the FD_REWRITTEN classes): fd_rewrite changes the opcode or the domain, or nothing
+PR_HD inline bool fd_changed(const rv_op& op, const rv_op& now) { return now.domain != op.domain || now.opcode != op.opcode; }
+
+// The device's decisions around the whole-list steps, on one domain's sorted (index, op) pairs of the window (prune.h's pr_run_last:
+// pair j is the window's LAST writer of its index when the next pair has another key).
+// table update, after the rewrite has read the tables: the last writer's (known, value) goes to its index -- one storing thread per
+// index, no atomics
+PR_HD inline void fd_table_update(const uint32_t* sk, const uint32_t* sv, uint32_t nd, uint32_t j, const uint32_t* known, const uint64_t* val, uint8_t* K,
+                                  uint64_t* V, uint64_t W) {
+    if (!pr_run_last(sk, nd, j) || sk[j] >= W) return;
+    const bool kn = known[sv[j]] != 0u;
+    K[sk[j]] = kn ? 1 : 0, V[sk[j]] = kn ? val[sv[j]] : 0ull;
+}
+// replay: the first log entry whose ordinal is not below `ordinal` (the log is ascending by ordinal)
+PR_HD inline uint32_t fd_log_lower_bound(const uint32_t* ord, uint32_t n, uint64_t ordinal) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (ord[mid] < ordinal) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
 }
 
 }  // namespace rv

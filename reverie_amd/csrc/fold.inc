@@ -1,5 +1,5 @@
-// Part of api.hip (#included there, one translation unit, behind prune.inc): rv_ops_fold_device -- the kernels of fold_dev.hip on the
-// context's stream, their work memory from the context arena.  (rv_ops_fold, the host sweep and the definition, is fold.cpp.)
+// Part of api.hip (#included there, one translation unit, behind prune.inc): rv_ops_fold_device and rv_folder_* -- the kernels of
+// fold_dev.hip and fold_win.hip on the context's stream, their work memory from the context arena.  (rv_ops_fold, the host sweep and the definition, is fold.cpp.)
 
 extern "C" int rv_hook_fold_limits(uint32_t out[5]) {
     if (!out) return RV_E_ARG;
@@ -38,4 +38,121 @@ extern "C" int rv_ops_fold_device(rv_ctx* ctx, const rv_op* d_ops, size_t n_ops,
         if (rc == RV_E_NOMEM) g_last_error = "device folding: out of device memory";
         return rc;
     });
+}
+
+// ---- rv_folder_*: the same folding for a list read in windows (fold_win.hip), on the context's stream and arena ----
+struct rv_folder {
+    rv_ctx* ctx;
+    WinFolder* w;
+};
+
+static int folder_code(int rc) {
+    if (rc == RV_E_DEVICE) g_last_error = "windowed folding: HIP error";
+    if (rc == RV_E_NOMEM) g_last_error = "windowed folding: out of device memory";
+    return rc;
+}
+
+extern "C" int rv_folder_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, uint32_t flags, rv_folder** out) {
+    if (!ctx || !out || (flags & ~(uint32_t)RV_FOLDER_KEEP_LOG)) return RV_E_ARG;
+    *out = nullptr;
+    return guarded([&]() -> int {
+        LibBusy busy_guard;
+        HIPCHK(hipSetDevice(ctx->device));
+        std::unique_ptr<rv_folder> f(new rv_folder{ctx, nullptr});
+        if (const int rc = folder_code(winfold_begin(ctx->stream, ctx_dev_allocator(ctx), z64_wires, gf2_wires, (flags & RV_FOLDER_KEEP_LOG) != 0, &f->w)))
+            return rc;
+        *out = f.release();
+        return RV_OK;
+    });
+}
+
+extern "C" void rv_folder_destroy(rv_folder* f) {
+    if (!f) return;
+    (void)hipSetDevice(f->ctx->device);
+    winfold_destroy(f->w);
+    delete f;
+}
+
+// a feed (pass 0) or a replay (pass 1): the checks of the pointers, the upload of a host feed, the call
+static int folder_pass(rv_folder* f, int pass, const rv_op* ops, size_t n_ops, int ops_on_device, uint64_t first, rv_op* d_out) {
+    if (!f || (n_ops && (!ops || (pass == 1 && !d_out)))) return RV_E_ARG;
+    if (n_ops > (size_t)-1 / sizeof(rv_op)) return RV_E_UNSUPPORTED;
+    rv_ctx* ctx = f->ctx;
+    return guarded([&]() -> int {
+        LibBusy busy_guard;
+        HIPCHK(hipSetDevice(ctx->device));
+        const size_t bytes = n_ops * sizeof(rv_op);
+        // (asked first, and before the upload: a call out of order is RV_E_ARG whatever its pointers are, and moves nothing)
+        if (const int rc = winfold_admit(f->w, pass, n_ops, first)) return rc;
+        if (n_ops) {
+            if (ops_on_device)
+                if (int rb = device_bytes_ok(ctx, ops, bytes, 8)) return rb;
+            if (d_out && !(ops_on_device && d_out == ops)) {
+                if (int rb = device_bytes_ok(ctx, d_out, bytes, 8)) return rb;
+                // (d_out == ops is the in-place form: a tile writes the records it read; any other overlap has a tile's stores land
+                // where another tile's records are still to be read)
+                const uint8_t *i0 = (const uint8_t*)ops, *o0 = (const uint8_t*)d_out;
+                if (ops_on_device && o0 < i0 + bytes && i0 < o0 + bytes) return RV_E_ARG;
+            }
+        }
+        // the uploaded copy of a host feed: given back on every way out, once the stream is idle
+        struct Upload {
+            rv_ctx* ctx;
+            void* d = nullptr;
+            ~Upload() {
+                if (d) {
+                    (void)hipStreamSynchronize(ctx->stream);
+                    ctx->release(d);
+                }
+            }
+        } up{ctx};
+        const rv_op* d_ops = ops;
+        if (n_ops && !ops_on_device) {
+            if (ctx->alloc(bytes, &up.d) != RV_OK) return folder_code(RV_E_NOMEM);
+            if (hipMemcpyAsync(up.d, ops, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return folder_code(RV_E_DEVICE);
+            d_ops = (const rv_op*)up.d;
+        }
+        const size_t up_bytes = up.d ? bytes : 0;
+        const int rc = pass == 0 ? winfold_feed(f->w, d_ops, n_ops, up_bytes, d_out) : winfold_replay(f->w, d_ops, n_ops, up_bytes, first, d_out);
+        if (rc == RV_E_ARG) g_last_error = "windowed folding: the pass is not the list that was folded first";
+        return folder_code(rc);
+    });
+}
+
+extern "C" int rv_folder_feed(rv_folder* f, const rv_op* ops, size_t n_ops, int ops_on_device, rv_op* d_out) {
+    return folder_pass(f, 0, ops, n_ops, ops_on_device, 0, d_out);
+}
+
+extern "C" int rv_folder_replay(rv_folder* f, const rv_op* ops, size_t n_ops, int ops_on_device, uint64_t first_ordinal, rv_op* d_out) {
+    return folder_pass(f, 1, ops, n_ops, ops_on_device, first_ordinal, d_out);
+}
+
+extern "C" int rv_folder_end(rv_folder* f, rv_fold_info* info) {
+    if (!f) return RV_E_ARG;
+    return guarded([&]() -> int {
+        LibBusy busy_guard;
+        return winfold_end(f->w, info);
+    });
+}
+
+extern "C" int rv_folder_rewind(rv_folder* f) {
+    if (!f) return RV_E_ARG;
+    return guarded([&]() -> int {
+        LibBusy busy_guard;
+        HIPCHK(hipSetDevice(f->ctx->device));
+        return folder_code(winfold_rewind(f->w));
+    });
+}
+
+extern "C" int rv_folder_replay_end(rv_folder* f) {
+    if (!f) return RV_E_ARG;
+    return guarded([&]() -> int {
+        LibBusy busy_guard;
+        return winfold_replay_end(f->w);
+    });
+}
+
+extern "C" int rv_folder_get_info(const rv_folder* f, rv_folder_info* info) {
+    if (!f || !info) return RV_E_ARG;
+    return winfold_info(f->w, info);
 }

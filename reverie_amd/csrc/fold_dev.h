@@ -24,6 +24,8 @@ constexpr uint32_t FOLD_MAX_ROUNDS_DEFAULT = 65536;
 uint32_t fold_max_rounds();
 // out[0..4): rewrite launches, count-only passes, propagation launches, fall-backs of this process
 void fold_launches(uint64_t out[4]);
+// the windowed call's launches count with them (which: the word of fold_launches)
+void fold_count_launches(int which, uint64_t count);
 
 // d_ops: n_ops records in device memory; d_out (n_ops records) may be null (count only) or d_ops (in place).  Memory from A, given
 // back before the call returns.  RV_OK (info filled when not null), the list's validation code (d_out untouched), RV_E_UNSUPPORTED,

@@ -9,7 +9,7 @@
 //   2. writers    prune_dev.hip's step 2: per domain with a defining op, the defining ops sorted by destination (stable).  A read is
 //                 resolved by pr_value_read's binary search of the sorted pairs.
 //   3. seed       one thread per op: its reads resolved, the producers of the first two stored (a B2A resolves its 64 again when
-//                 they are needed), pending = the reads that have a producer.  A defining op that is known at once (fd_seed: Const, a
+//                 they are needed), pending = the reads that have a producer.  A defining op that is known at once (fd_known of the reads without a producer: Const, a
 //                 zero MulConst, no read with a producer, a Mul with a zero-wire read) sets its state word, stores its value and
 //                 enters the queue; its pending is 0.  The kernel also sums pending (the reader pairs of step 4) and notes whether
 //                 any read found no producer.  The host looks at the words: no known op and no such read -- the list is copied to
@@ -32,6 +32,7 @@
 //                 out in 16-byte stores with 8-byte end pieces (pr_chunk).  A tile reads its own records before it writes them and
 //                 nothing of another tile's: d_out may be d_ops.  The classes by a ballot per wavefront, one LDS atomic per
 //                 wavefront, one global atomic per workgroup.  The count-only call runs the counts alone.
+// The kernels of steps 3 - 6 are fold_dev_kernels.inc's, shared with the windowed call (fold_win.hip); here they run without tables.
 // The host reads device words after step 1, after step 3, inside the propagation loop and at the end.
 #include "fold_dev.h"
 
@@ -50,236 +51,7 @@ static_assert(TB == (int)FOLD_WG && TB == (int)FOLD_TILE, "the sizes rv_hook_fol
 static_assert(FOLD_SOLO_LIMIT % FOLD_WG == 0, "the solo kernel walks its frontier in whole strides");
 #include "prune_dev_kernels.inc"
 
-// this call's words behind the pruning kernels' (S_ERR_LO .. S_WIDE_DONE are theirs; FS_PAIRS is a 64-bit word)
-enum { FS_PAIRS = (S_WORDS + 1) & ~1, FS_UNWRITTEN = FS_PAIRS + 2, FS_CLS, FS_WORDS = FS_CLS + FD_CLASSES };
-
-// the arrays of one call, one entry per op: the producers of reads a and b (PR_NONE: none), the reads whose producer is not known
-// yet, the state word (1: known), the value
-struct Fold {
-    uint32_t *pa, *pb, *pending, *known;
-    uint64_t* val;
-};
-// the reader pairs sorted by producer, and where each producer's begin
-struct Readers {
-    const uint32_t *rk, *rv, *off;
-    uint32_t n_pairs;
-};
-
-// a value another wavefront may have stored in this launch: read where the stores went
-__device__ inline uint64_t ld_val(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void st_val(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// ---- step 3 ----
-__global__ __launch_bounds__(TB) void k_fd_seed(const rv_op* ops, size_t n, Writers w, Fold f, uint32_t* queue, uint32_t* state) {
-    __shared__ unsigned long long s_pairs;
-    __shared__ uint32_t s_unwritten;
-    if (threadIdx.x == 0) s_pairs = 0, s_unwritten = 0;
-    __syncthreads();
-    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-    bool known = false, unwritten = false;
-    uint32_t pend = 0;
-    if (i < n) {
-        const rv_op op = ops[i];
-        const uint32_t r = pr_n_reads(op);
-        const int rd = pr_read_dom(op);
-        uint32_t p[2] = {PR_NONE, PR_NONE}, have = 0;
-        for (uint32_t k = 0; k < r; k++) {
-            const uint32_t v = pr_value_read(w.sk[rd], w.sv[rd], w.nd[rd], pr_read(op, k), (uint32_t)i);
-            if (v != PR_NONE) have++;
-            if (k < 2 && op.domain != RV_DOM_B2A) p[k] = v;
-        }
-        unwritten = have < r;
-        uint64_t value = 0;
-        if (pr_def(op) >= 0) {
-            if (op.domain == RV_DOM_B2A) {
-                known = have == 0;  // (64 zero wires: the value 0)
-            } else {
-                const bool uw[2] = {r > 0 && p[0] == PR_NONE, r > 1 && p[1] == PR_NONE};
-                const uint64_t zero[2] = {0, 0};
-                known = fd_seed(op, uw);
-                if (known) value = fd_eval(op, zero);
-            }
-            if (!known) pend = have;
-        }
-        f.pa[i] = p[0], f.pb[i] = p[1];
-        f.pending[i] = pend, f.known[i] = known ? 1u : 0u, f.val[i] = value;
-    }
-    q_append(known, (uint32_t)i, queue, (uint32_t)n, state);
-    unsigned long long sum = pend;
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
-    const unsigned long long m = __ballot(unwritten);
-    if ((threadIdx.x & 63u) == 0) {
-        if (sum) atomicAdd(&s_pairs, sum);
-        if (m) atomicOr(&s_unwritten, 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (s_pairs) atomicAdd(reinterpret_cast<unsigned long long*>(&state[FS_PAIRS]), s_pairs);
-        if (s_unwritten) atomicOr(&state[FS_UNWRITTEN], 1u);
-    }
-}
-
-// ---- step 4 ----
-__global__ __launch_bounds__(TB) void k_fd_pairs(const rv_op* ops, size_t n, Writers w, Fold f, const uint32_t* pos, uint32_t n_pairs, uint32_t* pk,
-                                                 uint32_t* pv) {
-    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-    if (i >= n || f.pending[i] == 0u) return;
-    uint32_t at = pos[i];
-    const rv_op op = ops[i];
-    if (op.domain == RV_DOM_B2A) {
-        for (uint32_t k = 0; k < 64; k++) {
-            const uint32_t v = pr_value_read(w.sk[PR_G], w.sv[PR_G], w.nd[PR_G], op.a + k, (uint32_t)i);
-            if (v != PR_NONE && at < n_pairs) pk[at] = v, pv[at] = (uint32_t)i, at++;
-        }
-    } else {
-        const uint32_t p[2] = {f.pa[i], f.pb[i]};
-        for (int k = 0; k < 2; k++)
-            if (p[k] != PR_NONE && at < n_pairs) pk[at] = p[k], pv[at] = (uint32_t)i, at++;
-    }
-}
-// (off is zero before: a producer nobody reads points at pair 0, whose key is another's)
-__global__ __launch_bounds__(TB) void k_fd_offsets(const uint32_t* rk, uint32_t n_pairs, uint32_t n, uint32_t* off) {
-    const size_t j = (size_t)blockIdx.x * TB + threadIdx.x;
-    if (j >= n_pairs) return;
-    const uint32_t p = rk[j];
-    if ((j == 0 || rk[j - 1] != p) && p < n) off[p] = (uint32_t)j;
-}
-
-// ---- step 5 ----
-// the value of the known record r, all of whose reads are known (their values were stored before this round)
-__device__ inline uint64_t value_of(const rv_op& op, uint32_t r, const Writers& w, const Fold& f) {
-    if (op.domain == RV_DOM_B2A) {
-        uint64_t acc = 0;
-        for (uint32_t k = 0; k < 64; k++) {
-            const uint32_t p = pr_value_read(w.sk[PR_G], w.sv[PR_G], w.nd[PR_G], op.a + k, r);
-            acc |= fd_b2a_bit(k, p == PR_NONE ? 0ull : ld_val(&f.val[p]));
-        }
-        return acc;
-    }
-    const uint32_t pa = f.pa[r], pb = f.pb[r];
-    const uint64_t v[2] = {pa == PR_NONE ? 0ull : ld_val(&f.val[pa]), pb == PR_NONE ? 0ull : ld_val(&f.val[pb])};
-    return fd_eval(op, v);
-}
-// One frontier op p (or none: !have) told to its readers.  Every lane of the wavefront calls it; the loop runs as long as any lane
-// has a reader left.
-__device__ inline void spread(bool have, uint32_t p, const rv_op* ops, uint32_t n, const Writers& w, const Fold& f, const Readers& rd, uint32_t* queue,
-                              uint32_t* state) {
-    uint32_t j = 0;
-    uint64_t pval = 0;
-    if (have) j = rd.off[p], pval = ld_val(&f.val[p]);
-    for (;; j++) {
-        const bool live = have && j < rd.n_pairs && rd.rk[j] == p;
-        if (__ballot(live) == 0ull) break;
-        bool claimed = false;
-        uint32_t r = 0;
-        if (live) {
-            r = rd.rv[j];
-            if (r < n) {
-                const rv_op op = ops[r];
-                uint64_t value = 0;
-                bool mine = false;
-                if (fd_zero_kills(op) && pval == 0) {
-                    mine = true;
-                } else if (atomicSub(&f.pending[r], 1u) == 1u) {
-                    mine = true;
-                    value = value_of(op, r, w, f);
-                }
-                if (mine && atomicCAS(&f.known[r], 0u, 1u) == 0u) {
-                    st_val(&f.val[r], value);
-                    claimed = true;
-                }
-            }
-        }
-        q_append(claimed, r, queue, n, state);
-    }
-}
-// One workgroup: frontiers of at most FOLD_SOLO_LIMIT ops, layer after layer, until one is empty or wider, or the bound is reached.
-// EVERY thread keeps the round's bounds and the layer count in registers, and every thread takes the same way through the loop: no
-// branch around a barrier depends on the thread.  The words go back to device memory at the end, every thread storing the same values.
-__global__ __launch_bounds__(TB) void k_fd_solo(const rv_op* ops, uint32_t n, Writers w, Fold f, Readers rd, uint32_t* queue, uint32_t* state,
-                                                uint32_t max_rounds) {
-    uint32_t lo = uniform(state[S_Q_LO]), hi = uniform(state[S_Q_HI]), rounds = uniform(state[S_ROUNDS]);
-    const uint32_t tail0 = uniform(state[S_Q_TAIL]);
-    if (uniform(state[S_WIDE_DONE])) rounds += 1u, lo = hi, hi = tail0;  // the layer a wide launch stepped
-    __syncthreads();  // every thread has read the words (the appends below move the tail, the stores at the end the rest)
-    while (hi != lo && hi - lo <= FOLD_SOLO_LIMIT && rounds < max_rounds) {
-        for (uint32_t base = lo; base < hi; base += TB) {  // (whole strides: every lane of a wavefront calls spread)
-            const uint32_t at = base + threadIdx.x;
-            const bool have = at < hi;
-            // (the entry may have been written by another wavefront of this launch: read where the stores went)
-            const uint32_t p = have ? __hip_atomic_load(&queue[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-            spread(have && p < n, p, ops, n, w, f, rd, queue, state);
-        }
-        __threadfence();
-        __syncthreads();  // the layer's appends and values are done ...
-        const uint32_t tail = uniform(__hip_atomic_load(&state[S_Q_TAIL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        __syncthreads();  // ... and every thread has read the tail before the next layer moves it
-        rounds += 1u, lo = hi, hi = tail < n ? tail : n;
-    }
-    state[S_Q_LO] = lo, state[S_Q_HI] = hi, state[S_ROUNDS] = rounds, state[S_WIDE_DONE] = 0u;
-}
-// a frontier wider than the solo limit, grid-stride; the next solo launch counts the layer and moves the words on
-__global__ __launch_bounds__(TB) void k_fd_wide(const rv_op* ops, uint32_t n, Writers w, Fold f, Readers rd, uint32_t* queue, uint32_t* state,
-                                                uint32_t max_rounds) {
-    const uint32_t lo = uniform(state[S_Q_LO]), hi = uniform(state[S_Q_HI]);
-    if (hi - lo <= FOLD_SOLO_LIMIT || uniform(state[S_ROUNDS]) >= max_rounds) return;  // (no launch of this kind changes these words)
-    state[S_WIDE_DONE] = 1u;                                                           // (every thread stores the same word)
-    const uint64_t stride = (uint64_t)gridDim.x * TB;
-    for (uint64_t base = (uint64_t)lo + (uint64_t)blockIdx.x * TB; base < hi; base += stride) {
-        const uint64_t at = base + threadIdx.x;
-        const bool have = at < hi;
-        const uint32_t p = have ? queue[at] : 0u;
-        spread(have && p < n, p, ops, n, w, f, rd, queue, state);
-    }
-}
-
-// ---- step 6 ----
-template <bool EMIT>
-__global__ __launch_bounds__(TB) void k_fd_rewrite(const rv_op* ops, size_t n, Fold f, uint32_t* state, uint8_t* out) {
-    __shared__ __attribute__((aligned(16))) uint8_t raw[EMIT ? PR_IMAGE : 16];
-    __shared__ uint32_t s_cls[FD_CLASSES];
-    if (threadIdx.x < FD_CLASSES) s_cls[threadIdx.x] = 0;
-    __syncthreads();
-    const size_t t0 = (size_t)blockIdx.x * TB;
-    const uint32_t mine = (uint32_t)std::min<size_t>(TB, n - t0);
-    const size_t i = t0 + threadIdx.x;
-    const uint32_t sh = EMIT ? pr_image_shift((uint64_t)(uintptr_t)out, t0) : 0u;
-    int cls = -1;
-    if (threadIdx.x < mine) {
-        const rv_op op = ops[i];
-        const uint32_t r = op.domain == RV_DOM_B2A ? 0u : pr_n_reads(op);
-        const uint32_t p[2] = {f.pa[i], f.pb[i]};
-        bool kn[2] = {false, false};
-        uint64_t v[2] = {0, 0};
-        for (uint32_t k = 0; k < r; k++) {
-            kn[k] = p[k] == PR_NONE || f.known[p[k]] != 0u;
-            v[k] = (kn[k] && p[k] != PR_NONE) ? f.val[p[k]] : 0ull;
-        }
-        const rv_op now = fd_rewrite(op, f.known[i] != 0u, f.val[i], kn, v);
-        cls = fd_class(op, now, kn, v);
-        if (EMIT) {
-            const uint64_t* src = reinterpret_cast<const uint64_t*>(&now);
-            uint64_t* img = reinterpret_cast<uint64_t*>(raw + sh + threadIdx.x * 24);
-            img[0] = src[0], img[1] = src[1], img[2] = src[2];
-        }
-    }
-    for (int c = 0; c < FD_CLASSES; c++) {
-        const unsigned long long m = __ballot(cls == c);
-        if ((threadIdx.x & 63u) == 0 && m) atomicAdd(&s_cls[c], (uint32_t)__popcll(m));
-    }
-    __syncthreads();  // the image is whole, and every record of the tile has been read
-    if (EMIT) {
-        const uint32_t span = sh + mine * 24;
-        uint8_t* base = out + (uint64_t)t0 * 24 - sh;  // 16-byte aligned; only [sh, span) of it is this tile's to write
-        for (uint32_t c = threadIdx.x * 16; c < span; c += TB * 16) {
-            const uint32_t kind = pr_chunk(c, sh, span);
-            if (kind == 3) *reinterpret_cast<uint4*>(base + c) = *reinterpret_cast<const uint4*>(raw + c);
-            else if (kind == 1) *reinterpret_cast<uint2*>(base + c) = *reinterpret_cast<const uint2*>(raw + c);
-            else if (kind == 2) *reinterpret_cast<uint2*>(base + c + 8) = *reinterpret_cast<const uint2*>(raw + c + 8);
-        }
-    }
-    if (threadIdx.x < FD_CLASSES && s_cls[threadIdx.x]) atomicAdd(&state[FS_CLS + threadIdx.x], s_cls[threadIdx.x]);
-}
+#include "fold_dev_kernels.inc"
 
 std::atomic<uint64_t> g_launches[4];  // rewrite, count-only, propagation, fall-backs
 
@@ -311,36 +83,6 @@ int fold_on_host(Scratch& S, hipStream_t st, const rv_op* d_ops, size_t n, uint6
         info->device_rounds = rounds, info->on_device = 0;
     }
     return RV_OK;
-}
-
-// step 5 on `st`, from the first frontier to an empty one (prune_dev_kernels.inc's peel_layers with this call's kernels; the first
-// look was the caller's)
-hipError_t propagate(hipStream_t st, const rv_op* ops, size_t n, const Writers& w, const Fold& f, const Readers& rd, uint32_t* queue, uint32_t* state,
-                     uint32_t max_rounds, std::vector<uint32_t>& h, bool* gave_up, uint64_t* launches) {
-    const uint32_t gb = blocks(n, TB);
-    *gave_up = false;
-    hipError_t e = hipSuccess;
-    for (bool first = true; e == hipSuccess; first = false) {
-        if (!first) {
-            e = fetch(st, h, state);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) break;
-        }
-        if (!h[S_WIDE_DONE]) {
-            if (h[S_Q_HI] == h[S_Q_LO]) break;
-            if (h[S_ROUNDS] >= max_rounds) {
-                *gave_up = true;
-                break;
-            }
-        }
-        for (uint32_t k = 0; k < FOLD_LOOK_INTERVAL; k++) {
-            k_fd_solo<<<1, TB, 0, st>>>(ops, (uint32_t)n, w, f, rd, queue, state, max_rounds);
-            k_fd_wide<<<std::min<uint32_t>(FOLD_WIDE_BLOCKS, gb), TB, 0, st>>>(ops, (uint32_t)n, w, f, rd, queue, state, max_rounds);
-            *launches += 2;
-        }
-        e = hipGetLastError();
-    }
-    return e;
 }
 
 int fold_impl(hipStream_t st, const DevAlloc& A, const rv_op* ops, size_t n, uint64_t z64_wires, uint64_t gf2_wires, rv_op* d_out, rv_fold_info* info) {
@@ -388,7 +130,8 @@ int fold_impl(hipStream_t st, const DevAlloc& A, const rv_op* ops, size_t n, uin
     Fold f = {S.get<uint32_t>(n), S.get<uint32_t>(n), S.get<uint32_t>(n), S.get<uint32_t>(n), S.get<uint64_t>(n)};
     uint32_t* queue = S.get<uint32_t>(n);
     CDNEED(f.pa && f.pb && f.pending && f.known && f.val && queue);
-    k_fd_seed<<<gb, TB, 0, st>>>(ops, n, w, f, queue, state);
+    const Carried none = {};  // (the whole list: a read without a producer is the zero wire)
+    k_fd_seed<<<gb, TB, 0, st>>>(ops, n, w, f, none, queue, state);
     k_pr_begin<<<1, 64, 0, st>>>(state);
     CDCHK(hipGetLastError());
     CDCHK(fetch(st, h, state));
@@ -422,7 +165,7 @@ int fold_impl(hipStream_t st, const DevAlloc& A, const rv_op* ops, size_t n, uin
         // step 5
         bool gave_up = false;
         uint64_t launches = 0;
-        const hipError_t pe = propagate(st, ops, n, w, f, rd, queue, state, max_rounds, h, &gave_up, &launches);
+        const hipError_t pe = propagate(st, ops, n, w, f, none, rd, queue, state, max_rounds, h, &gave_up, &launches);
         g_launches[2] += launches;
         CDCHK(pe);
         if (gave_up) return fold_on_host(S, st, ops, n, z64_wires, gf2_wires, d_out, info, h[S_ROUNDS]);
@@ -433,10 +176,10 @@ int fold_impl(hipStream_t st, const DevAlloc& A, const rv_op* ops, size_t n, uin
 
     // step 6
     if (d_out) {
-        k_fd_rewrite<true><<<gb, TB, 0, st>>>(ops, n, f, state, reinterpret_cast<uint8_t*>(d_out));
+        k_fd_rewrite<true><<<gb, TB, 0, st>>>(ops, n, f, none, state, reinterpret_cast<uint8_t*>(d_out));
         g_launches[0]++;
     } else {
-        k_fd_rewrite<false><<<gb, TB, 0, st>>>(ops, n, f, state, nullptr);
+        k_fd_rewrite<false><<<gb, TB, 0, st>>>(ops, n, f, none, state, nullptr);
         g_launches[1]++;
     }
     CDCHK(hipGetLastError());
@@ -460,6 +203,8 @@ uint32_t fold_max_rounds() {
 void fold_launches(uint64_t out[4]) {
     for (int k = 0; k < 4; k++) out[k] = g_launches[k].load();
 }
+
+void fold_count_launches(int which, uint64_t count) { g_launches[which] += count; }
 
 int fold_ops_device(hipStream_t st, const DevAlloc& A, const rv_op* d_ops, size_t n_ops, uint64_t z64_wires, uint64_t gf2_wires, rv_op* d_out,
                     rv_fold_info* info) {

@@ -7,7 +7,11 @@ or SubConst.  Nothing is dropped, moved or renumbered, and every wire's value st
 Consts nothing reads any more.  The order is fold, then prune, then `compact_wires`.
 
 THE PROOF OF A FOLDED LIST IS THE PROOF OF THAT LIST, not of the original: a folded Mul or B2A no longer contributes to it.  Prover
-and verifier both fold, or the folded program is the file that is shipped."""
+and verifier both fold, or the folded program is the file that is shipped.
+
+A list that passes through in windows is folded by `DeviceFolder` (rv_folder_*): one forward pass that carries a known
+byte and a value per wire index from feed to feed, with the same bytes as `fold_ops` of the whole list for every cutting;
+`fold_pieces` wraps a source of pieces, and `fold_windows_host` is the window step's definition on the host."""
 from __future__ import annotations
 
 import ctypes as C
@@ -61,3 +65,200 @@ def fold_ops(ops, wire_counts: Optional[Tuple[int, int]] = None, ctx: Optional[C
     out = ops if inplace else np.empty_like(ops)
     _lib.check(L.rv_ops_fold(*head, _ptr(out), C.byref(fi)))
     return out, _info(fi)
+
+
+def fold_windows_host(ops, wire_counts: Optional[Tuple[int, int]] = None, cuts=()):
+    """-> (ops, info): rv_ops_fold_windows_host -- the forward sweep over the windows [0, cuts[0]), [cuts[0], cuts[1]), ..
+    [cuts[-1], len(ops)) with one carried state; no GPU.  Every byte is `fold_ops`'s, whatever the cuts (that is the contract the
+    windowed device folder is held to).  cuts: non-decreasing positions, none above len(ops) (ReverieError ARG otherwise)."""
+    ops = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+    if wire_counts is None:
+        wire_counts = largest_wires(ops) if len(ops) else (0, 0)
+    c = np.ascontiguousarray(np.asarray(list(cuts), dtype=np.int64).reshape(-1))
+    if c.size and c.min() < 0:
+        raise ValueError("a cut is a position in the list: 0 .. len(ops)")
+    c = c.astype(np.uintp)
+    fi = _lib.FoldInfo()
+    out = np.empty_like(ops)
+    _lib.check(_lib.lib().rv_ops_fold_windows_host(_ptr(ops), C.c_size_t(len(ops)), C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])),
+                                                   _ptr(c) if c.size else None, C.c_size_t(c.size), _ptr(out), C.byref(fi)))
+    return out, _info(fi)
+
+
+# ---- the same for a list that passes through in windows (rv_folder_*; DESIGN §24.8) ----
+KEEP_LOG = 1  # RV_FOLDER_KEEP_LOG
+
+
+class DeviceFolder:
+    """rv_folder: `fold_ops` for an op list that arrives in feeds.  feed(ops)... forwards -> the folded records, feed by feed; end()
+    -> rv_fold_info; rewind() folds the list again from op 0.  keep_log: every rewritten record is kept in a log on the device, and
+    after end() replay(ops, first) turns ANY window of the source into the same window of the folded list, in any order;
+    replay_end() closes a round that covered the whole list.  ops: an OP_DTYPE array (uploaded) or a torch GPU tensor of packed
+    rv_op records.  wire_counts: (z64, gf2) as stated."""
+
+    def __init__(self, wire_counts: Tuple[int, int], ctx: Optional[Context] = None, keep_log: bool = False):
+        self.ctx = ctx or Context.default()
+        self.handle = C.c_void_p()
+        self.info = None
+        _lib.check(_lib.lib().rv_folder_begin(self.ctx.handle, C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])),
+                                              C.c_uint32(KEEP_LOG if keep_log else 0), C.byref(self.handle)))
+
+    def _ops(self, ops):
+        """-> (pointer, n_ops, on device, what keeps the memory alive)"""
+        if _is_device_ops(ops):
+            d_ops, n_ops, _ = _device_ops(ops, self.ctx, "DeviceFolder")
+            return C.c_void_p(d_ops), n_ops, 1, ops
+        a = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
+        return _ptr(a), len(a), 0, a
+
+    def _out(self, n, ops, dev, inplace):
+        import torch
+
+        if inplace:
+            if not dev:
+                raise ValueError("inplace needs a GPU tensor of packed rv_op records")
+            return ops
+        return torch.empty((n, OP_DTYPE.itemsize), dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
+
+    def feed(self, ops, inplace: bool = False, count_only: bool = False):
+        """-> the feed's folded records as a uint8 GPU tensor [n, 24] (inplace: the argument, a GPU tensor, written over; count_only:
+        None -- the feed is counted, and logged where the log is kept, and nothing is written)"""
+        p, n, dev, _keep = self._ops(ops)
+        if count_only:
+            _lib.check(_lib.lib().rv_folder_feed(self.handle, p, C.c_size_t(n), C.c_int(dev), None))
+            return None
+        out = self._out(n, ops, dev, inplace)
+        _lib.check(_lib.lib().rv_folder_feed(self.handle, p, C.c_size_t(n), C.c_int(dev), (p if inplace else C.c_void_p(out.data_ptr())) if n else None))
+        return out
+
+    def end(self) -> dict:
+        """-> rv_fold_info of the pass as a dict (also .info)"""
+        fi = _lib.FoldInfo()
+        _lib.check(_lib.lib().rv_folder_end(self.handle, C.byref(fi)))
+        self.info = _info(fi)
+        return self.info
+
+    def rewind(self) -> None:
+        _lib.check(_lib.lib().rv_folder_rewind(self.handle))
+
+    def replay(self, ops, first: int, inplace: bool = False):
+        """ops: the source's records [first, first + len(ops)) -> the folded list's, as a uint8 GPU tensor [n, 24]"""
+        p, n, dev, _keep = self._ops(ops)
+        out = self._out(n, ops, dev, inplace)
+        _lib.check(_lib.lib().rv_folder_replay(self.handle, p, C.c_size_t(n), C.c_int(dev), C.c_uint64(int(first)),
+                                               (p if inplace else C.c_void_p(out.data_ptr())) if n else None))
+        return out
+
+    def replay_end(self) -> None:
+        _lib.check(_lib.lib().rv_folder_replay_end(self.handle))
+
+    def get_info(self) -> dict:
+        """rv_folder_info: total_ops, state_bytes, log_bytes, log_records, peak_feed_bytes, feeds, host_feeds"""
+        fi = _lib.FolderInfo()
+        _lib.check(_lib.lib().rv_folder_get_info(self.handle, C.byref(fi)))
+        return _info(fi)
+
+    def close(self) -> None:
+        """gives the folder's device memory back to its context (a context that was closed first took its memory with it: the handle
+        is dropped then, not destroyed)"""
+        if self.handle:
+            if self.ctx.handle:
+                _lib.lib().rv_folder_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        import sys
+
+        if sys.is_finalizing():  # (finalisers run in no order then: the context and the runtime may be gone; the process ends anyway)
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _input_counts(ops):
+    """the (GF(2), Z64) Input ops of a piece, as `prune.prune_pieces` counts them"""
+    if not _is_device_ops(ops):  # (counted where the records still are a host array)
+        a = program(ops)
+        inputs = a["opcode"] == 0
+        return int(np.count_nonzero(inputs & (a["domain"] == 0))), int(np.count_nonzero(inputs & (a["domain"] == 1)))
+    recs = ops.reshape(-1, OP_DTYPE.itemsize)  # (domain and opcode are a record's first two bytes)
+    inputs = recs[:, 1] == 0
+    return int((inputs & (recs[:, 0] == 0)).sum()), int((inputs & (recs[:, 0] == 1)).sum())
+
+
+def fold_pieces(pieces, wire_counts: Tuple[int, int], ctx: Optional[Context] = None):
+    """-> (pieces2, info) for `pieces` as `stream.prove_streaming_pieces` takes them: a callable that returns a fresh iterator of
+    (ops, Input counts).  One counting pass with the log kept runs here.  `pieces2` is such a callable too: every call reads the
+    source again and yields (the piece's folded records as a GPU tensor, the source's Input counts -- folding rewrites no Input, so
+    they pass through, or are counted where the source gives None); where `pieces` has `.backwards`, `pieces2.backwards()` yields the
+    same windows from the last to the first, so the result goes straight into `prune.prune_pieces`.  A pass has to be read to its end
+    (it is checked against the folded list then) before the next one begins.  info: rv_fold_info as a dict, with "folder"
+    (rv_folder_info) beside it; the folder lives as long as `pieces2` (`pieces2.folder`)."""
+    if not callable(pieces):
+        raise TypeError("fold_pieces reads the pieces several times: pass a callable that returns a fresh iterator")
+    df = DeviceFolder(wire_counts, ctx, keep_log=True)
+    try:
+        for ops, _ in pieces():
+            if ops is not None and len(ops):
+                df.feed(ops, count_only=True)
+        info = dict(df.end())
+    except BaseException:
+        df.close()
+        raise
+
+    open_round = [False]
+
+    def begin_round():
+        if open_round[0]:  # (a pass that was not read to its end: its replays do not count in this one)
+            try:
+                df.replay_end()
+            except _lib.ReverieError:
+                pass
+        open_round[0] = True
+
+    def end_round():
+        open_round[0] = False
+        df.replay_end()
+
+    def pieces2():
+        begin_round()
+        first = 0
+        for ops, counts in pieces():
+            if ops is None or len(ops) == 0:
+                continue
+            if counts is None:
+                counts = _input_counts(ops)
+            out = df.replay(ops, first)
+            first += len(out)
+            yield out, counts
+        end_round()
+
+    pieces2.folder = df
+    backwards = getattr(pieces, "backwards", None)
+    if callable(backwards):
+        total = int(info["n_ops"])
+
+        def backwards2():
+            begin_round()
+            end = total
+            for ops, counts in backwards():
+                if ops is None or len(ops) == 0:
+                    continue
+                if counts is None:
+                    counts = _input_counts(ops)
+                n = len(ops) if not _is_device_ops(ops) else len(ops.reshape(-1, OP_DTYPE.itemsize))
+                end -= n
+                yield df.replay(ops, end), counts
+            end_round()
+
+        pieces2.backwards = backwards2
+    info["folder"] = df.get_info()
+    return pieces2, info

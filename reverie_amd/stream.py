@@ -41,7 +41,8 @@ the pieces' callable needs `.backwards`), before `compact_wires`, and the result
 The whole-list one-shot functions take `fold` (default False) as well: constants are folded first (`fold.fold_ops`), before
 `prune` and `compact_wires`, and the info receives "fold".  The proof is the proof of the folded list -- prover and verifier must both
 pass fold=True.  The `*_streaming_pieces` functions refuse it: a read of an index no earlier op wrote is known 0, and a window's
-unwritten index is not the list's.
+unwritten index is not the list's.  `fold.fold_pieces(pieces, wire_counts)` is the windowed form: it carries the known
+values from window to window and returns pieces these functions take, `prune=True` and `compact_wires=True` on top included.
 
 The one-shot functions take `compact_wires` (default False): the whole op list is first renumbered by liveness (`compact.compact_wires`,
 DESIGN §17) -- on the host for host ops, by kernels for a GPU tensor -- and the stream begins with the new, smaller wire counts, so an
@@ -107,7 +108,9 @@ def _compacted_pieces(pieces, wire_counts, ctx: Optional[Context], wanted: bool,
     over the pruned pieces.  fold is refused: the whole-list functions fold."""
     if fold:
         raise ValueError("fold=True needs the whole list: a read of an index no earlier op wrote is known 0, and a window's unwritten index "
-                         "is not the list's -- fold the list first (fold.fold_ops), or use the whole-list function")
+                         "is not the list's -- fold the list first (fold.fold_ops), use the whole-list function, or fold the pieces in "
+                         "windows with the state carried from one to the next: fold.fold_pieces(pieces, wire_counts)[0] is a source of "
+                         "pieces that these functions take as it is (prover and verifier both)")
     if not wanted and not prune:
         return pieces, wire_counts, None, None
     if not callable(pieces):
@@ -826,7 +829,8 @@ def prove_streaming_pieces(pieces, wit_gf2, wit_z64, wire_counts: Tuple[int, int
     depends on are dropped first, in windows (`prune.prune_pieces`: the pieces need `.backwards`, as `LinkPlan.pieces` and
     `prune.window_pieces` have it; the source is read for a scan pass and, backwards, for a mark pass), then compact_wires runs over
     the pruned pieces if asked for; the proof is the pruned list's (prover and verifier both pass prune=True), info carries "prune".
-    fold=True is refused (ValueError): a window's unwritten index is not the list's; fold the whole list first (`fold.fold_ops`).
+    fold=True is refused (ValueError): a window's unwritten index is not the list's; fold the whole list first (`fold.fold_ops`), or pass
+    `fold.fold_pieces(pieces, wire_counts)[0]` as the pieces.
     -> (Proof or DeviceProof, stream info)"""
     if not callable(pieces):
         raise TypeError("prove_streaming_pieces reads the pieces twice: pass a callable that returns a fresh iterator")
