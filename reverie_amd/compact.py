@@ -17,12 +17,9 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _lib
+from ._window import _DeviceStage, info_dict as _info, input_counts
 from .ops import OP_DTYPE, largest_wires, program
 from .proof import Context, _device_ops, _is_device_ops, _ptr
-
-
-def _info(ci) -> dict:
-    return {n: int(getattr(ci, n)) for n, _ in ci._fields_}
 
 
 def compact_wires(ops, wire_counts: Optional[Tuple[int, int]] = None, ctx: Optional[Context] = None):
@@ -53,26 +50,18 @@ def compact_wires(ops, wire_counts: Optional[Tuple[int, int]] = None, ctx: Optio
     return out, (info["z64_wires"], info["gf2_wires"]), info
 
 
-class DeviceCompactor:
+class DeviceCompactor(_DeviceStage):
     """rv_compactor: `compact_wires` for an op list that arrives in feeds.  scan(ops)... scan_end() (again, when it says so), then
     feed(ops)... -> the renumbered records, feed by feed; rewind() starts the rewrite pass again.  The two passes may be cut
     differently.  ops: an OP_DTYPE array (uploaded) or a torch GPU tensor of packed rv_op records."""
 
+    _what, _destroy, _info_of = "DeviceCompactor", "rv_compactor_destroy", (_lib.CompactorInfo, "rv_compactor_get_info")
+
     def __init__(self, wire_counts: Tuple[int, int], ctx: Optional[Context] = None):
-        self.ctx = ctx or Context.default()
-        self.handle = C.c_void_p()
-        self.info = None
+        super().__init__(ctx or Context.default())
         self.wire_counts = None
         _lib.check(_lib.lib().rv_compactor_begin(self.ctx.handle, C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])),
                                                  C.byref(self.handle)))
-
-    def _ops(self, ops):
-        """-> (pointer, n_ops, on device, what keeps the memory alive)"""
-        if _is_device_ops(ops):
-            d_ops, n_ops, _ = _device_ops(ops, self.ctx, "DeviceCompactor")
-            return C.c_void_p(d_ops), n_ops, 1, ops
-        a = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
-        return _ptr(a), len(a), 0, a
 
     def scan(self, ops) -> None:
         p, n, dev, _keep = self._ops(ops)
@@ -102,33 +91,7 @@ class DeviceCompactor:
 
     def get_info(self) -> dict:
         """rv_compactor_info: total_ops, state_bytes, peak_feed_bytes, scans, b2a"""
-        ci = _lib.CompactorInfo()
-        _lib.check(_lib.lib().rv_compactor_get_info(self.handle, C.byref(ci)))
-        return _info(ci)
-
-    def close(self) -> None:
-        """gives the compactor's device memory back to its context (a context that was closed first took its memory with it: the
-        handle is dropped then, not destroyed)"""
-        if self.handle:
-            if self.ctx.handle:
-                _lib.lib().rv_compactor_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        import sys
-
-        if sys.is_finalizing():  # (finalisers run in no order then: the context and the runtime may be gone; the process ends anyway)
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
+        return super().get_info()
 
 
 def compact_pieces(pieces, wire_counts: Tuple[int, int], ctx: Optional[Context] = None):
@@ -156,10 +119,8 @@ def compact_pieces(pieces, wire_counts: Tuple[int, int], ctx: Optional[Context] 
         for ops, counts in pieces():
             if ops is None or len(ops) == 0:
                 continue
-            if counts is None and not _is_device_ops(ops):  # (counted where the records still are a host array)
-                a = program(ops)
-                inputs = a["opcode"] == 0
-                counts = (int(np.count_nonzero(inputs & (a["domain"] == 0))), int(np.count_nonzero(inputs & (a["domain"] == 1))))
+            if counts is None and not _is_device_ops(ops):  # (a device piece's counts stay None: the stream counts them where it needs them)
+                counts = input_counts(ops)
             yield dc.feed(ops), counts
 
     pieces2.compactor = dc

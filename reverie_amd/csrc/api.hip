@@ -1654,6 +1654,7 @@ extern "C" int rv_hook_witness_traffic(uint64_t out[3]) {
 #include "eval_stream.inc"
 #include "stream_wdev.inc"
 #include "witness_dev.inc"
+#include "win_pass.inc"
 #include "compact.inc"
 #include "bristol.inc"
 #include "bincode.inc"

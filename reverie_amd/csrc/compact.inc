@@ -6,7 +6,7 @@ extern "C" int rv_ops_compact_wires_device(rv_ctx* ctx, const rv_op* d_ops, size
                                            rv_compact_info* info) {
     if (!ctx || (n_ops && (!d_ops || !d_out))) return RV_E_ARG;
     if (n_ops >= (1ull << 31)) return RV_E_UNSUPPORTED;
-    try {
+    return guarded([&]() -> int {
         if (n_ops) {
             HIPCHK(hipSetDevice(ctx->device));
             if (int rb = device_bytes_ok(ctx, d_ops, n_ops * sizeof(rv_op), 8)) return rb;
@@ -15,14 +15,9 @@ extern "C" int rv_ops_compact_wires_device(rv_ctx* ctx, const rv_op* d_ops, size
             const uint8_t *i0 = (const uint8_t*)d_ops, *o0 = (const uint8_t*)d_out;
             if (o0 != i0 && o0 < i0 + n_ops * sizeof(rv_op) && i0 < o0 + n_ops * sizeof(rv_op)) return RV_E_ARG;
         }
-        const int rc = compact_ops_device(ctx->stream, ctx_dev_allocator(ctx), d_ops, n_ops, z64_wires, gf2_wires, d_out, info);
-        if (rc == RV_E_DEVICE) g_last_error = "device wire compaction: HIP error";
-        if (rc == RV_E_NOMEM) g_last_error = "device wire compaction: out of device memory";
-        return rc;
-    } catch (...) {
-        g_last_error = "out of host memory";
-        return RV_E_NOMEM;
-    }
+        return stage_code(compact_ops_device(ctx->stream, ctx_dev_allocator(ctx), d_ops, n_ops, z64_wires, gf2_wires, d_out, info),
+                          "device wire compaction");
+    });
 }
 
 // ---- rv_compactor_*: the same compaction for a list read in windows (compact_win.hip), on the context's stream and arena ----
@@ -39,9 +34,7 @@ extern "C" int rv_compactor_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wire
         HIPCHK(hipSetDevice(ctx->device));
         std::unique_ptr<rv_compactor> c(new rv_compactor{ctx, nullptr});
         const int rc = wincompact_begin(ctx->stream, ctx_dev_allocator(ctx), z64_wires, gf2_wires, &c->w);
-        if (rc == RV_E_NOMEM) g_last_error = "windowed wire compaction: out of device memory";
-        if (rc == RV_E_DEVICE) g_last_error = "windowed wire compaction: HIP error";
-        if (rc) return rc;
+        if (rc) return stage_code(rc, "windowed wire compaction");
         *out = c.release();
         return RV_OK;
     });
@@ -54,51 +47,16 @@ extern "C" void rv_compactor_destroy(rv_compactor* c) {
     delete c;
 }
 
-// a scan feed (d_out null) or a rewrite feed
+// a scan feed (d_out null) or a rewrite feed (in place where d_out is a device `ops`)
 static int compactor_pass(rv_compactor* c, const rv_op* ops, size_t n_ops, int ops_on_device, rv_op* d_out, bool rewrite) {
-    if (!c || (n_ops && (!ops || (rewrite && !d_out)))) return RV_E_ARG;
-    if (n_ops > (size_t)-1 / sizeof(rv_op)) return RV_E_UNSUPPORTED;
-    rv_ctx* ctx = c->ctx;
-    return guarded([&]() -> int {
-        LibBusy busy_guard;
-        HIPCHK(hipSetDevice(ctx->device));
-        const size_t bytes = n_ops * sizeof(rv_op);
-        if (n_ops) {
-            if (ops_on_device)
-                if (int rb = device_bytes_ok(ctx, ops, bytes, 8)) return rb;
-            if (rewrite) {
-                if (int rb = device_bytes_ok(ctx, d_out, bytes, 8)) return rb;
-                const uint8_t *i0 = (const uint8_t*)ops, *o0 = (const uint8_t*)d_out;
-                if (ops_on_device && o0 != i0 && o0 < i0 + bytes && i0 < o0 + bytes) return RV_E_ARG;
-            }
-        }
-        // (asked before the upload: a call out of order moves nothing)
-        if (const int rc = rewrite ? wincompact_admit_feed(c->w, n_ops) : wincompact_admit_scan(c->w, n_ops)) return rc;
-        void* d_up = nullptr;
-        const rv_op* d_ops = ops;
-        if (n_ops && !ops_on_device) {
-            if (ctx->alloc(bytes, &d_up) != RV_OK) {
-                g_last_error = "windowed wire compaction: out of device memory";
-                return RV_E_NOMEM;
-            }
-            if (hipMemcpyAsync(d_up, ops, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-                (void)hipStreamSynchronize(ctx->stream);
-                ctx->release(d_up);
-                g_last_error = "windowed wire compaction: HIP error";
-                return RV_E_DEVICE;
-            }
-            d_ops = (const rv_op*)d_up;
-        }
-        const int rc = rewrite ? wincompact_feed(c->w, d_ops, n_ops, d_out, d_up ? bytes : 0) : wincompact_scan(c->w, d_ops, n_ops, d_up ? bytes : 0);
-        if (d_up) {
-            (void)hipStreamSynchronize(ctx->stream);
-            ctx->release(d_up);
-        }
-        if (rc == RV_E_DEVICE) g_last_error = "windowed wire compaction: HIP error";
-        if (rc == RV_E_NOMEM) g_last_error = "windowed wire compaction: out of device memory";
-        if (rc == RV_E_ARG) g_last_error = "windowed wire compaction: the pass is not the list that was scanned";
-        return rc;
-    });
+    const PassShape shape = {"windowed wire compaction", "windowed wire compaction: the pass is not the list that was scanned", rewrite, true, n_ops,
+                             nullptr};
+    return stage_pass(
+        c ? c->ctx : nullptr, shape, ops, n_ops, ops_on_device, d_out,
+        [&] { return rewrite ? wincompact_admit_feed(c->w, n_ops) : wincompact_admit_scan(c->w, n_ops); },
+        [&](const rv_op* d_ops, size_t up_bytes) {
+            return rewrite ? wincompact_feed(c->w, d_ops, n_ops, d_out, up_bytes) : wincompact_scan(c->w, d_ops, n_ops, up_bytes);
+        });
 }
 
 extern "C" int rv_compactor_scan(rv_compactor* c, const rv_op* ops, size_t n_ops, int ops_on_device) {
@@ -114,10 +72,7 @@ extern "C" int rv_compactor_scan_end(rv_compactor* c, int* again, rv_compact_inf
     return guarded([&]() -> int {
         LibBusy busy_guard;
         HIPCHK(hipSetDevice(c->ctx->device));
-        const int rc = wincompact_scan_end(c->w, again, info);
-        if (rc == RV_E_DEVICE) g_last_error = "windowed wire compaction: HIP error";
-        if (rc == RV_E_NOMEM) g_last_error = "windowed wire compaction: out of device memory";
-        return rc;
+        return stage_code(wincompact_scan_end(c->w, again, info), "windowed wire compaction");
     });
 }
 

@@ -52,14 +52,7 @@ __device__ inline bool takes_slot(const rv_op& op, int d, const uint32_t* pins) 
     return value_dom(op) == d && !(op.domain == RV_DOM_GF2 && pinned(pins, op.dst));
 }
 
-// ---- step 1 ----
-__global__ __launch_bounds__(TB) void k_cw_hints(const rv_op* ops, size_t n, uint32_t* hz, uint32_t* hg) {
-    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-    if (i >= n) return;
-    const bool h = ops[i].domain == RV_DOM_SIZEHINT;
-    hz[i] = h ? ops[i].a : 0u;
-    hg[i] = h ? ops[i].b : 0u;
-}
+// ---- step 1 (the hints: compile_dev_prims.inc's k_pr_hints) ----
 __global__ __launch_bounds__(TB) void k_cw_classify(const rv_op* ops, size_t n, uint64_t decl_z, uint64_t decl_g, const uint32_t* cz, const uint32_t* cg,
                                                     uint32_t* state) {
     __shared__ uint32_t cnt[5];  // values G, values Z, B2A, ops G, ops Z
@@ -304,7 +297,7 @@ int compact_impl(hipStream_t st, const DevAlloc& A, const rv_op* ops, size_t n, 
     // step 1 (the hints and their scans borrow the sort's buffers)
     CDCHK(hipMemsetAsync(w.state, 0, S_WORDS * 4, st));
     CDCHK(hipMemsetAsync(w.state, 0xFF, 8, st));
-    k_cw_hints<<<gb, TB, 0, st>>>(ops, n, w.kbuf[0], w.kbuf[1]);
+    k_pr_hints<<<gb, TB, 0, st>>>(ops, n, w.kbuf[0], w.kbuf[1]);
     CDCHK((scan_excl<uint32_t, MaxU32>(S, st, w.kbuf[0], w.vbuf[0], n, &w.state[S_HINT_Z])));
     CDCHK((scan_excl<uint32_t, MaxU32>(S, st, w.kbuf[1], w.vbuf[1], n, &w.state[S_HINT_G])));
     k_cw_classify<<<gb, TB, 0, st>>>(ops, n, z64_wires, gf2_wires, w.vbuf[0], w.vbuf[1], w.state);

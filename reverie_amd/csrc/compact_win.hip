@@ -27,8 +27,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "dev_counting.h"
-#include "piece_sums.h"
+#include "win_stage.h"
 
 namespace rv {
 namespace {
@@ -44,7 +43,7 @@ constexpr uint32_t M_REL_A = 1, M_REL_B = 2, M_DEAD = 4, M_TAKES = 8, M_DOMZ = 1
 enum { S_P, S_ZERO_G, S_ZERO_Z, S_BAD, S_FEED_FIRST, S_ERR_LO = S_FEED_FIRST, S_ERR_HI, S_HINT_Z, S_HINT_G, S_VALUES_G, S_VALUES_Z, S_B2A, S_OPS_G, S_OPS_Z,
        S_ATOT_G, S_ATOT_Z, S_FTOT_G, S_FTOT_Z, S_NLOC_G, S_NLOC_Z, S_WORDS };
 static_assert(S_ERR_LO % 2 == 0, "the error word is one aligned 64-bit word");
-constexpr size_t STATE_BYTES = 1024, CUT_AT = 256, SUMS_AT = 512;  // the block: state words, the digest's cut pair, its sums
+static_assert(S_WORDS * 4 <= WIN_CUT_AT, "the state words are the start of the stage's block");
 constexpr int MAX_ROUNDS = 36, ROUNDS_PER_LOOK = 4;
 constexpr int RB = 256;  // ops per block of the marks' reduction
 
@@ -73,14 +72,7 @@ __device__ inline void finalise(uint32_t* marks, uint64_t total, uint32_t dv, ui
     else mark_or(marks, total, (r - 1u) >> 1, ((r - 1u) & 1u) ? M_REL_A : M_REL_B);
 }
 
-// ---- validation (first scan pass): compact_dev.hip's step 1 with the counts in force carried in ----
-__global__ __launch_bounds__(TB) void k_w_hints(const rv_op* ops, size_t n, uint32_t* hz, uint32_t* hg) {
-    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-    if (i >= n) return;
-    const bool h = ops[i].domain == RV_DOM_SIZEHINT;
-    hz[i] = h ? ops[i].a : 0u;
-    hg[i] = h ? ops[i].b : 0u;
-}
+// ---- validation (first scan pass): compact_dev.hip's step 1 with the counts in force carried in (the hints: k_pr_hints) ----
 __global__ __launch_bounds__(TB) void k_w_classify(const rv_op* ops, size_t n, uint64_t in_z, uint64_t in_g, const uint32_t* cz, const uint32_t* cg,
                                                    uint32_t* state) {
     __shared__ uint32_t cnt[5];  // values G, values Z, B2A, ops G, ops Z
@@ -375,52 +367,33 @@ __global__ __launch_bounds__(TB) void k_w_rewrite(const rv_op* ops, size_t n, co
 
 }  // namespace
 
-enum class Phase { SCAN, FEED, FAILED };
+enum class Phase { SCAN, FEED };
 
-struct WinCompactor {
-    hipStream_t st;
-    DevAlloc A;
+struct WinCompactor : WinStage {
     Phase phase = Phase::SCAN;
     uint64_t W[2];                             // counts in force ([G], [Z]): the tables' lengths
     uint32_t* tab[2] = {nullptr, nullptr};     // W[d] words def (the rewrite pass: slotof), then W[d] words rd
     uint32_t *pins = nullptr, *rank = nullptr; // W[G] words each; pins from the first B2A op on, rank from the end of the first scan
     uint32_t* marks = nullptr;
     uint64_t marks_cap = 0;                    // bytes
-    uint8_t* block = nullptr;                  // STATE_BYTES
     uint32_t* fifo[2] = {nullptr, nullptr};
     uint32_t cap[2] = {0, 0}, head[2] = {0, 0}, len[2] = {0, 0}, fresh[2] = {0, 0};
-    uint64_t pos = 0, total = 0, digest = 0, digest0 = 0, cut_h[2] = {0, 0};
     uint64_t values[2] = {0, 0};
     uint32_t scans = 0;
     bool b2a = false, ops_of[2] = {false, false};
     rv_compact_info info{};
-    size_t peak_feed = 0;
 
-    uint32_t* state() const { return (uint32_t*)block; }
+    bool at(Phase ph) const { return !failed && phase == ph; }
+    uint32_t* state() const { return (uint32_t*)block; }  // (the block's start)
     uint32_t* def(int d) const { return tab[d]; }
     uint32_t* rd(int d) const { return tab[d] + W[d]; }
     size_t state_bytes() const {
-        return STATE_BYTES + 8 * (size_t)(tab[G] ? W[G] : 0) + 8 * (size_t)(tab[Z] ? W[Z] : 0) + (pins ? 4 * (size_t)W[G] : 0) + (rank ? 4 * (size_t)W[G] : 0) +
-               (size_t)marks_cap + 4 * (size_t)(fifo[G] ? cap[G] : 0) + 4 * (size_t)(fifo[Z] ? cap[Z] : 0);
-    }
-    void* take(size_t bytes) {
-        void* p = nullptr;
-        return A.alloc(A.self, std::max<size_t>(bytes, 4), &p) == RV_OK ? p : nullptr;
-    }
-    void give(void* p) {
-        if (p) A.release(A.self, p);
+        return WIN_BLOCK_BYTES + 8 * (size_t)(tab[G] ? W[G] : 0) + 8 * (size_t)(tab[Z] ? W[Z] : 0) + (pins ? 4 * (size_t)W[G] : 0) +
+               (rank ? 4 * (size_t)W[G] : 0) + (size_t)marks_cap + 4 * (size_t)(fifo[G] ? cap[G] : 0) + 4 * (size_t)(fifo[Z] ? cap[Z] : 0);
     }
 };
 
 namespace {
-
-#define WCHK(x)                           \
-    do {                                  \
-        if ((x) != hipSuccess) {          \
-            (void)hipGetLastError();      \
-            return RV_E_DEVICE;           \
-        }                                 \
-    } while (0)
 
 // the tables of domain d at length w (>= the present one), the old contents kept; on an error nothing is held that was not held before
 int grow_tables(WinCompactor* c, int d, uint64_t w) {
@@ -474,11 +447,7 @@ hipError_t begin_feed(WinCompactor* c, const rv_op* d_ops, size_t n) {
     uint32_t* state = c->state();
     hipError_t e = hipMemsetAsync(state + S_FEED_FIRST, 0, (S_WORDS - S_FEED_FIRST) * 4, c->st);
     if (e == hipSuccess) e = hipMemsetAsync(state + S_ERR_LO, 0xFF, 8, c->st);
-    c->cut_h[0] = 0, c->cut_h[1] = n;
-    if (e == hipSuccess) e = hipMemcpyAsync(c->block + CUT_AT, c->cut_h, 16, hipMemcpyHostToDevice, c->st);
-    if (e != hipSuccess) return e;
-    launch_piece_sums(c->st, d_ops, (const uint64_t*)(c->block + CUT_AT), 1, n, c->pos, (PieceSums*)(c->block + SUMS_AT));
-    return hipGetLastError();
+    return e == hipSuccess ? stage_digest(*c, d_ops, n, c->pos) : e;
 }
 struct FeedWords {
     std::vector<uint32_t> h = std::vector<uint32_t>(S_WORDS);
@@ -486,7 +455,7 @@ struct FeedWords {
 };
 hipError_t fetch_feed(WinCompactor* c, FeedWords& f) {
     hipError_t e = hipMemcpyAsync(f.h.data(), c->state(), S_WORDS * 4, hipMemcpyDeviceToHost, c->st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&f.digest, c->block + SUMS_AT, 8, hipMemcpyDeviceToHost, c->st);
+    if (e == hipSuccess) e = stage_fetch_digest(*c, &f.digest);
     if (e == hipSuccess) e = hipStreamSynchronize(c->st);
     return e;
 }
@@ -505,19 +474,19 @@ int scan_impl(WinCompactor* c, const DevAlloc& CA, const rv_op* ops, size_t n) {
     CDCHK(begin_feed(c, ops, n));
     bool dom[2] = {c->W[G] > 0, c->W[Z] > 0};
     if (first) {
-        k_w_hints<<<gb, TB, 0, st>>>(ops, n, kbuf[0], kbuf[1]);
+        k_pr_hints<<<gb, TB, 0, st>>>(ops, n, kbuf[0], kbuf[1]);
         CDCHK((scan_excl<uint32_t, MaxU32>(S, st, kbuf[0], vbuf[0], n, &state[S_HINT_Z])));
         CDCHK((scan_excl<uint32_t, MaxU32>(S, st, kbuf[1], vbuf[1], n, &state[S_HINT_G])));
         k_w_classify<<<gb, TB, 0, st>>>(ops, n, c->W[Z], c->W[G], vbuf[0], vbuf[1], state);
         CDCHK(hipGetLastError());
         CDCHK(fetch_feed(c, f));
         if (f.h[S_ERR_HI] != 0xFFFFFFFFu || f.h[S_ERR_LO] != 0xFFFFFFFFu) {
-            c->phase = Phase::FAILED;
+            c->failed = true;
             return (int)(f.h[S_ERR_LO] & 0xFFu);
         }
         const uint64_t wz = std::max<uint64_t>(c->W[Z], f.h[S_HINT_Z]), wg = std::max<uint64_t>(c->W[G], f.h[S_HINT_G]);
-        if (wz >= (1ull << 31) || wg >= (1ull << 31)) {
-            c->phase = Phase::FAILED;
+        if (!stage_wires_ok(wz, wg)) {
+            c->failed = true;
             return RV_E_UNSUPPORTED;
         }
         if (f.h[S_B2A] && !c->pins) {
@@ -623,7 +592,7 @@ int feed_impl(WinCompactor* c, const DevAlloc& CA, const rv_op* ops, size_t n, r
         if (!bad && ((uint64_t)consumed[d] > (uint64_t)c->len[d] + f.h[S_FTOT_G + d] || (uint64_t)c->fresh[d] + f.h[S_NLOC_G + d] > c->cap[d])) bad = true;
     }
     if (bad) {
-        c->phase = Phase::FAILED;
+        c->failed = true;
         return RV_E_ARG;
     }
     k_w_rewrite<<<gb, TB, 0, st>>>(ops, n, c->pins, c->rank, (uint32_t)c->W[G], va, vb, slot, (uint32_t)c->info.gf2_pinned, (uint32_t)c->info.z64_wires,
@@ -642,11 +611,15 @@ int feed_impl(WinCompactor* c, const DevAlloc& CA, const rv_op* ops, size_t n, r
 }
 
 int reset_rewrite(WinCompactor* c) {
+    hipError_t e = hipSuccess;
     for (int d = 0; d < 2; d++) {
-        if (c->tab[d] && c->W[d]) WCHK(hipMemsetAsync(c->def(d), 0xFF, 4 * (size_t)c->W[d], c->st));
+        if (e == hipSuccess && c->tab[d] && c->W[d]) e = hipMemsetAsync(c->def(d), 0xFF, 4 * (size_t)c->W[d], c->st);
         c->head[d] = c->len[d] = c->fresh[d] = 0;
     }
-    WCHK(hipStreamSynchronize(c->st));
+    if (e != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) {
+        (void)hipGetLastError();
+        return RV_E_DEVICE;
+    }
     c->pos = 0, c->digest = 0;
     return RV_OK;
 }
@@ -690,7 +663,7 @@ int scan_end_impl(WinCompactor* c, const DevAlloc& CA, int* again, rv_compact_in
     CDCHK(fetch(st, h, state));
     CDCHK(hipStreamSynchronize(st));
     if (h[S_BAD]) {
-        c->phase = Phase::FAILED;
+        c->failed = true;
         return RV_E_ARG;
     }
     int64_t A[2] = {0, 0}, F[2] = {0, 0}, N[2] = {0, 0};
@@ -705,7 +678,7 @@ int scan_end_impl(WinCompactor* c, const DevAlloc& CA, int* again, rv_compact_in
     ci.z64_wires = (uint64_t)h[S_ZERO_Z] + (uint64_t)N[Z], ci.gf2_wires = ci.gf2_pinned + h[S_ZERO_G] + (uint64_t)N[G];
     ci.gf2_values = c->values[G], ci.z64_values = c->values[Z];
     if (ci.z64_wires >= MAX_SLOTS || ci.gf2_wires >= MAX_SLOTS) {
-        c->phase = Phase::FAILED;
+        c->failed = true;
         return RV_E_UNSUPPORTED;
     }
     for (int d = 0; d < 2; d++) {
@@ -724,25 +697,20 @@ int scan_end_impl(WinCompactor* c, const DevAlloc& CA, int* again, rv_compact_in
 #undef CDCHK
 #undef CDNEED
 
-// one call's work memory, counted into peak_feed
-template <class Fn>
-int counted(WinCompactor* c, size_t upload_bytes, Fn&& fn) {
-    size_t peak = 0;
-    const int rc = counted_call(c->A, &peak, fn);
-    c->peak_feed = std::max(c->peak_feed, peak + upload_bytes);
-    return rc;
+// a compactor that closes drops its rings
+int settled(WinCompactor* c, int rc) {
+    return stage_settled(*c, rc, [c] {
+        for (int d = 0; d < 2; d++) c->give(c->fifo[d]), c->fifo[d] = nullptr;
+    });
 }
 
 }  // namespace
 
 int wincompact_begin(hipStream_t st, const DevAlloc& A, uint64_t z64_wires, uint64_t gf2_wires, WinCompactor** out) {
-    if (z64_wires >= (1ull << 31) || gf2_wires >= (1ull << 31)) return RV_E_UNSUPPORTED;
+    if (!stage_wires_ok(z64_wires, gf2_wires)) return RV_E_UNSUPPORTED;
     WinCompactor* c = new WinCompactor;
-    c->st = st, c->A = A;
     c->W[G] = 0, c->W[Z] = 0;
-    c->block = (uint8_t*)c->take(STATE_BYTES);
-    int rc = c->block ? RV_OK : RV_E_NOMEM;
-    if (rc == RV_OK && (hipMemsetAsync(c->block, 0, STATE_BYTES, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) rc = RV_E_DEVICE;
+    int rc = stage_open(*c, st, A);
     if (rc == RV_OK) rc = grow_tables(c, G, gf2_wires);
     if (rc == RV_OK) rc = grow_tables(c, Z, z64_wires);
     if (rc != RV_OK) {
@@ -753,58 +721,44 @@ int wincompact_begin(hipStream_t st, const DevAlloc& A, uint64_t z64_wires, uint
     return RV_OK;
 }
 
-// a device or memory error in the middle of a call leaves the carried state half moved: only destroy is accepted afterwards
-static int settled(WinCompactor* c, int rc) {
-    if (rc == RV_E_NOMEM || rc == RV_E_DEVICE) {
-        (void)hipStreamSynchronize(c->st);
-        for (int d = 0; d < 2; d++) c->give(c->fifo[d]), c->fifo[d] = nullptr;
-        c->phase = Phase::FAILED;
-    }
-    return rc;
-}
-
 int wincompact_admit_scan(WinCompactor* c, size_t n) {
-    if (c->phase != Phase::SCAN) return RV_E_ARG;
-    if (c->scans && n < (1ull << 31)) return c->pos + n > c->total ? RV_E_ARG : RV_OK;
-    if (n >= (1ull << 31) || c->pos + n >= (1ull << 31)) {
-        c->phase = Phase::FAILED;
-        return RV_E_UNSUPPORTED;
-    }
-    return RV_OK;
+    if (!c->at(Phase::SCAN)) return RV_E_ARG;
+    if (c->scans && n < WIN_INDEX_LIMIT) return c->pos + n > c->total ? RV_E_ARG : RV_OK;
+    return stage_admit_first(*c, n);
 }
 int wincompact_admit_feed(const WinCompactor* c, size_t n) {
-    if (c->phase != Phase::FEED) return RV_E_ARG;
-    if (n >= (1ull << 31)) return RV_E_UNSUPPORTED;
+    if (!c->at(Phase::FEED)) return RV_E_ARG;
+    if (n >= WIN_INDEX_LIMIT) return RV_E_UNSUPPORTED;
     return c->pos + n > c->total ? RV_E_ARG : RV_OK;
 }
 
 int wincompact_scan(WinCompactor* c, const rv_op* d_ops, size_t n, size_t upload_bytes) {
     if (int rc = wincompact_admit_scan(c, n)) return rc;
     if (!n) return RV_OK;
-    return settled(c, counted(c, upload_bytes, [&](const DevAlloc& CA) { return scan_impl(c, CA, d_ops, n); }));
+    return settled(c, stage_counted(*c, upload_bytes, [&](const DevAlloc& CA) { return scan_impl(c, CA, d_ops, n); }));
 }
 
 int wincompact_scan_end(WinCompactor* c, int* again, rv_compact_info* info) {
-    if (c->phase != Phase::SCAN || !again) return RV_E_ARG;
-    if (c->scans && (c->pos != c->total || c->digest != c->digest0)) return RV_E_ARG;
-    return settled(c, counted(c, 0, [&](const DevAlloc& CA) { return scan_end_impl(c, CA, again, info); }));
+    if (!c->at(Phase::SCAN) || !again) return RV_E_ARG;
+    if (c->scans && !stage_pass_done(*c)) return RV_E_ARG;
+    return settled(c, stage_counted(*c, 0, [&](const DevAlloc& CA) { return scan_end_impl(c, CA, again, info); }));
 }
 
 int wincompact_feed(WinCompactor* c, const rv_op* d_ops, size_t n, rv_op* d_out, size_t upload_bytes) {
     if (int rc = wincompact_admit_feed(c, n)) return rc;
     if (n)
-        if (int rc = settled(c, counted(c, upload_bytes, [&](const DevAlloc& CA) { return feed_impl(c, CA, d_ops, n, d_out); }))) return rc;
-    if (c->pos == c->total && c->digest != c->digest0) return RV_E_ARG;  // (the pass was not the scanned list)
+        if (int rc = settled(c, stage_counted(*c, upload_bytes, [&](const DevAlloc& CA) { return feed_impl(c, CA, d_ops, n, d_out); }))) return rc;
+    if (c->pos == c->total && !stage_pass_done(*c)) return RV_E_ARG;  // (the pass was not the scanned list)
     return RV_OK;
 }
 
 int wincompact_rewind(WinCompactor* c) {
-    if (c->phase != Phase::FEED || c->pos != c->total) return RV_E_ARG;
+    if (!c->at(Phase::FEED) || c->pos != c->total) return RV_E_ARG;
     return settled(c, reset_rewrite(c));
 }
 
 int wincompact_info(const WinCompactor* c, rv_compactor_info* info) {
-    if (c->phase == Phase::FAILED) return RV_E_ARG;
+    if (c->failed) return RV_E_ARG;
     *info = rv_compactor_info{};
     info->total_ops = c->scans ? c->total : c->pos;
     info->state_bytes = c->state_bytes();
@@ -816,9 +770,9 @@ int wincompact_info(const WinCompactor* c, rv_compactor_info* info) {
 
 void wincompact_destroy(WinCompactor* c) {
     if (!c) return;
-    (void)hipStreamSynchronize(c->st);
+    stage_close(*c);
     for (int d = 0; d < 2; d++) c->give(c->tab[d]), c->give(c->fifo[d]);
-    c->give(c->pins), c->give(c->rank), c->give(c->marks), c->give(c->block);
+    c->give(c->pins), c->give(c->rank), c->give(c->marks);
     delete c;
 }
 

@@ -130,6 +130,17 @@ __global__ __launch_bounds__(TB) void k_rs_scatter(const uint32_t* kin, const ui
     }
 }
 
+// step 1 of every pass over an op list that checks wire indices (compact_dev.hip, prune_dev_kernels.inc's pr_step1, compact_win.hip):
+// the two fields of a SizeHint per op, for the max-scans that give the counts in force at every op.  (Not every file that takes
+// the scans and the sort from here launches it.)
+[[maybe_unused]] __global__ __launch_bounds__(TB) void k_pr_hints(const rv_op* ops, size_t n, uint32_t* hz, uint32_t* hg) {
+    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const bool h = ops[i].domain == RV_DOM_SIZEHINT;
+    hz[i] = h ? ops[i].a : 0u;
+    hg[i] = h ? ops[i].b : 0u;
+}
+
 inline uint32_t blocks(size_t n, size_t per) { return (uint32_t)std::max<size_t>(1, (n + per - 1) / per); }
 inline int bit_len(uint64_t v) {
     int b = 0;

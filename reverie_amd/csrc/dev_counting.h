@@ -1,5 +1,6 @@
 // The work memory of one call, counted: a DevAlloc in front of another one that remembers how many bytes are out and the most that
-// ever were (the windowed stages report it as peak_feed_bytes: compact_win.hip, prune_win.hip).
+// ever were (the windowed stages report it as peak_feed_bytes: win_stage.h's stage_counted, for compact_win.hip, prune_win.hip
+// and fold_win.hip).
 #pragma once
 #include <stddef.h>
 

@@ -46,12 +46,6 @@ struct rv_folder {
     WinFolder* w;
 };
 
-static int folder_code(int rc) {
-    if (rc == RV_E_DEVICE) g_last_error = "windowed folding: HIP error";
-    if (rc == RV_E_NOMEM) g_last_error = "windowed folding: out of device memory";
-    return rc;
-}
-
 extern "C" int rv_folder_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, uint32_t flags, rv_folder** out) {
     if (!ctx || !out || (flags & ~(uint32_t)RV_FOLDER_KEEP_LOG)) return RV_E_ARG;
     *out = nullptr;
@@ -59,8 +53,8 @@ extern "C" int rv_folder_begin(rv_ctx* ctx, size_t z64_wires, size_t gf2_wires, 
         LibBusy busy_guard;
         HIPCHK(hipSetDevice(ctx->device));
         std::unique_ptr<rv_folder> f(new rv_folder{ctx, nullptr});
-        if (const int rc = folder_code(winfold_begin(ctx->stream, ctx_dev_allocator(ctx), z64_wires, gf2_wires, (flags & RV_FOLDER_KEEP_LOG) != 0, &f->w)))
-            return rc;
+        const int rc = winfold_begin(ctx->stream, ctx_dev_allocator(ctx), z64_wires, gf2_wires, (flags & RV_FOLDER_KEEP_LOG) != 0, &f->w);
+        if (rc) return stage_code(rc, "windowed folding");
         *out = f.release();
         return RV_OK;
     });
@@ -73,50 +67,14 @@ extern "C" void rv_folder_destroy(rv_folder* f) {
     delete f;
 }
 
-// a feed (pass 0) or a replay (pass 1): the checks of the pointers, the upload of a host feed, the call
+// a feed (pass 0; d_out null: counted only) or a replay (pass 1), in place where d_out is a device `ops`
 static int folder_pass(rv_folder* f, int pass, const rv_op* ops, size_t n_ops, int ops_on_device, uint64_t first, rv_op* d_out) {
-    if (!f || (n_ops && (!ops || (pass == 1 && !d_out)))) return RV_E_ARG;
-    if (n_ops > (size_t)-1 / sizeof(rv_op)) return RV_E_UNSUPPORTED;
-    rv_ctx* ctx = f->ctx;
-    return guarded([&]() -> int {
-        LibBusy busy_guard;
-        HIPCHK(hipSetDevice(ctx->device));
-        const size_t bytes = n_ops * sizeof(rv_op);
-        // (asked first, and before the upload: a call out of order is RV_E_ARG whatever its pointers are, and moves nothing)
-        if (const int rc = winfold_admit(f->w, pass, n_ops, first)) return rc;
-        if (n_ops) {
-            if (ops_on_device)
-                if (int rb = device_bytes_ok(ctx, ops, bytes, 8)) return rb;
-            if (d_out && !(ops_on_device && d_out == ops)) {
-                if (int rb = device_bytes_ok(ctx, d_out, bytes, 8)) return rb;
-                // (d_out == ops is the in-place form: a tile writes the records it read; any other overlap has a tile's stores land
-                // where another tile's records are still to be read)
-                const uint8_t *i0 = (const uint8_t*)ops, *o0 = (const uint8_t*)d_out;
-                if (ops_on_device && o0 < i0 + bytes && i0 < o0 + bytes) return RV_E_ARG;
-            }
-        }
-        // the uploaded copy of a host feed: given back on every way out, once the stream is idle
-        struct Upload {
-            rv_ctx* ctx;
-            void* d = nullptr;
-            ~Upload() {
-                if (d) {
-                    (void)hipStreamSynchronize(ctx->stream);
-                    ctx->release(d);
-                }
-            }
-        } up{ctx};
-        const rv_op* d_ops = ops;
-        if (n_ops && !ops_on_device) {
-            if (ctx->alloc(bytes, &up.d) != RV_OK) return folder_code(RV_E_NOMEM);
-            if (hipMemcpyAsync(up.d, ops, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return folder_code(RV_E_DEVICE);
-            d_ops = (const rv_op*)up.d;
-        }
-        const size_t up_bytes = up.d ? bytes : 0;
-        const int rc = pass == 0 ? winfold_feed(f->w, d_ops, n_ops, up_bytes, d_out) : winfold_replay(f->w, d_ops, n_ops, up_bytes, first, d_out);
-        if (rc == RV_E_ARG) g_last_error = "windowed folding: the pass is not the list that was folded first";
-        return folder_code(rc);
-    });
+    const PassShape shape = {"windowed folding", "windowed folding: the pass is not the list that was folded first", pass == 1, true, n_ops, nullptr};
+    return stage_pass(
+        f ? f->ctx : nullptr, shape, ops, n_ops, ops_on_device, d_out, [&] { return winfold_admit(f->w, pass, n_ops, first); },
+        [&](const rv_op* d_ops, size_t up_bytes) {
+            return pass == 0 ? winfold_feed(f->w, d_ops, n_ops, up_bytes, d_out) : winfold_replay(f->w, d_ops, n_ops, up_bytes, first, d_out);
+        });
 }
 
 extern "C" int rv_folder_feed(rv_folder* f, const rv_op* ops, size_t n_ops, int ops_on_device, rv_op* d_out) {
@@ -140,7 +98,7 @@ extern "C" int rv_folder_rewind(rv_folder* f) {
     return guarded([&]() -> int {
         LibBusy busy_guard;
         HIPCHK(hipSetDevice(f->ctx->device));
-        return folder_code(winfold_rewind(f->w));
+        return stage_code(winfold_rewind(f->w), "windowed folding");
     });
 }
 

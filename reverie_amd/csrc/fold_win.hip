@@ -25,10 +25,9 @@
 #include <utility>
 #include <vector>
 
-#include "dev_counting.h"
 #include "fold_dev.h"
-#include "piece_sums.h"
 #include "prune_dev.h"
+#include "win_stage.h"
 
 namespace rv {
 namespace {
@@ -39,9 +38,9 @@ static_assert(FOLD_SOLO_LIMIT % FOLD_WG == 0, "the solo kernel walks its frontie
 
 #include "fold_dev_kernels.inc"
 
-enum { FW_LOG = FS_WORDS, FW_WORDS };                                             // the feed's words: the kernels', the changed records
-constexpr size_t BLOCK_BYTES = 1024, CUT_AT = 256, SUMS_AT = 512, BOUNDS_AT = 768;  // the resident block: the digest's cut pair, its sums, a replay's slice
-constexpr size_t LOG_FIRST = 1024;                                                // the log's first capacity, in records
+enum { FW_LOG = FS_WORDS, FW_WORDS };      // the feed's words: the kernels', the changed records
+constexpr size_t BOUNDS_AT = WIN_OWN_AT;   // the block's own quarter: a replay's slice of the log
+constexpr size_t LOG_FIRST = 1024;         // the log's first capacity, in records
 
 // ---- the tables ----
 // entries [from, to) of one domain: nothing written yet, the zero wire
@@ -97,47 +96,28 @@ __global__ __launch_bounds__(TB) void k_fw_replay(const uint32_t* ord, const rv_
 
 }  // namespace
 
-enum class Phase { FEED, ENDED, FAILED };
+enum class Phase { FEED, ENDED };
 
-struct WinFolder {
-    hipStream_t st;
-    DevAlloc A;
+struct WinFolder : WinStage {
     Phase phase = Phase::FEED;
     bool keep_log = false, first_pass = true;
     uint64_t W0[2] = {0, 0}, W[2] = {0, 0}, cap[2] = {0, 0};  // counts as declared, in force, the tables' entries ([PR_G], [PR_Z])
     uint8_t* K[2] = {nullptr, nullptr};
     uint64_t* V[2] = {nullptr, nullptr};
-    uint8_t* block = nullptr;  // BLOCK_BYTES
     uint32_t* log_ord = nullptr;
     rv_op* log_rec = nullptr;
     uint64_t log_n = 0, log_cap = 0;
-    uint64_t pos = 0, total = 0, digest = 0, digest0 = 0, cut_h[2] = {0, 0};
     // this pass's sums
     uint64_t n_known = 0, cls[FD_CLASSES] = {}, rounds = 0, pass_host_feeds = 0;
     uint64_t feeds = 0, host_feeds = 0;
-    size_t peak_feed = 0;
     // the replays since the last replay_end
     std::vector<std::pair<uint64_t, uint64_t>> replayed;
     uint64_t replay_digest = 0;
 
-    void* take(size_t bytes) {
-        void* p = nullptr;
-        return A.alloc(A.self, std::max<size_t>(bytes, 8), &p) == RV_OK ? p : nullptr;
-    }
-    void give(void* p) {
-        if (p) A.release(A.self, p);
-    }
+    bool at(Phase ph) const { return !failed && phase == ph; }
 };
 
 namespace {
-
-hipError_t launch_digest(WinFolder* p, const rv_op* d_ops, size_t n, uint64_t first) {
-    p->cut_h[0] = 0, p->cut_h[1] = n;  // (the folder's own words: they outlive the copy)
-    hipError_t e = hipMemcpyAsync(p->block + CUT_AT, p->cut_h, 16, hipMemcpyHostToDevice, p->st);
-    if (e != hipSuccess) return e;
-    launch_piece_sums(p->st, d_ops, (const uint64_t*)(p->block + CUT_AT), 1, n, first, (PieceSums*)(p->block + SUMS_AT));
-    return hipGetLastError();
-}
 
 // the tables hold at least `need` entries per domain afterwards; what they held stays, the new entries are known 0.  A table that
 // has to grow at least doubles (up to the largest count a list may have in force), as the log does: a list whose SizeHints raise a
@@ -256,49 +236,21 @@ int feed_impl(WinFolder* p, const DevAlloc& CA, const rv_op* ops, size_t n, rv_o
     for (int k = 0; k < 2; k++) kbuf[0][k] = S.get<uint32_t>(n), vbuf[0][k] = S.get<uint32_t>(n);
     CDNEED(state && kbuf[0][0] && kbuf[0][1] && vbuf[0][0] && vbuf[0][1]);
     std::vector<uint32_t> h(FW_WORDS);
-    uint64_t digest = 0;
 
     // step 1, the counts in force carried in (the hints and their scans borrow the first sort's buffers)
-    CDCHK(hipMemsetAsync(state, 0, FW_WORDS * 4, st));
-    CDCHK(hipMemsetAsync(state, 0xFF, 8, st));
-    CDCHK(launch_digest(p, ops, n, first));
-    k_pr_hints<<<gb, TB, 0, st>>>(ops, n, kbuf[0][0], kbuf[0][1]);
-    CDCHK((scan_excl<uint32_t, MaxU32>(S, st, kbuf[0][0], vbuf[0][0], n, &state[S_HINT_Z])));
-    CDCHK((scan_excl<uint32_t, MaxU32>(S, st, kbuf[0][1], vbuf[0][1], n, &state[S_HINT_G])));
-    k_pr_classify<<<gb, TB, 0, st>>>(ops, n, p->W[PR_Z], p->W[PR_G], vbuf[0][0], vbuf[0][1], state);
-    CDCHK(hipGetLastError());
-    CDCHK(fetch(st, h, state));
-    CDCHK(hipMemcpyAsync(&digest, p->block + SUMS_AT, 8, hipMemcpyDeviceToHost, st));
-    CDCHK(hipStreamSynchronize(st));
-    if (h[S_ERR_HI] != 0xFFFFFFFFu || h[S_ERR_LO] != 0xFFFFFFFFu) {
-        p->phase = Phase::FAILED;
-        return (int)(h[S_ERR_LO] & 0xFFu);
-    }
-    const uint64_t W[2] = {std::max<uint64_t>(p->W[PR_G], h[S_HINT_G]), std::max<uint64_t>(p->W[PR_Z], h[S_HINT_Z])};
-    if (W[PR_G] >= (1ull << 31) || W[PR_Z] >= (1ull << 31)) {
-        p->phase = Phase::FAILED;
-        return RV_E_UNSUPPORTED;
+    uint64_t W[2];
+    WinFeed feed = {*p, first};
+    if (const int rc = pr_step1(S, st, ops, n, state, FW_WORDS, p->W, kbuf[0], vbuf[0], &feed, h, W)) {
+        p->failed = true;
+        return rc;
     }
     if (const int rc = grow_tables(p, W)) return rc;
     p->W[PR_G] = W[PR_G], p->W[PR_Z] = W[PR_Z];
     const Carried c = {{p->K[PR_G], p->K[PR_Z]}, {p->V[PR_G], p->V[PR_Z]}};
 
     // step 2
-    Writers w = {};
-    int set = 0;  // the buffers the next sort takes
-    for (int d = 0; d < 2; d++) {
-        w.nd[d] = h[S_DEF_G + d];
-        if (!w.nd[d]) continue;  // (every read of the domain finds no value: the search looks at no pair)
-        if (set == 1) {
-            for (int k = 0; k < 2; k++) kbuf[1][k] = S.get<uint32_t>(n), vbuf[1][k] = S.get<uint32_t>(n);
-            CDNEED(kbuf[1][0] && kbuf[1][1] && vbuf[1][0] && vbuf[1][1]);
-        }
-        k_pr_keys<<<gb, TB, 0, st>>>(ops, n, d, (uint32_t)W[d], kbuf[set][0], vbuf[set][0]);
-        int which = 0;
-        CDCHK(radix_sort(S, st, kbuf[set], vbuf[set], n, bit_len(W[d]), &which));
-        w.sk[d] = kbuf[set][which], w.sv[d] = vbuf[set][which];
-        set++;
-    }
+    Writers w;
+    if (const int rc = pr_step2(S, st, ops, n, W, h, kbuf, vbuf, &w)) return rc;
 
     // step 3
     Fold f = {S.get<uint32_t>(n), S.get<uint32_t>(n), S.get<uint32_t>(n), S.get<uint32_t>(n), S.get<uint64_t>(n)};
@@ -389,7 +341,7 @@ int feed_impl(WinFolder* p, const DevAlloc& CA, const rv_op* ops, size_t n, rv_o
     p->n_known += n_known;
     p->rounds += rounds;
     p->feeds++;
-    p->digest += digest;
+    p->digest += feed.sum;
     p->pos += n;
     return RV_OK;
 }
@@ -400,11 +352,11 @@ int replay_impl(WinFolder* p, const DevAlloc& CA, const rv_op* ops, size_t n, ui
     uint64_t digest = 0;
     uint32_t bounds[2] = {0, 0};
     uint32_t* d_bounds = (uint32_t*)(p->block + BOUNDS_AT);
-    CDCHK(launch_digest(p, ops, n, first));
+    CDCHK(stage_digest(*p, ops, n, first));
     k_fw_bounds<<<1, 64, 0, st>>>(p->log_ord, (uint32_t)p->log_n, first, n, d_bounds);
     CDCHK(hipGetLastError());
     if (d_out != ops) CDCHK(hipMemcpyAsync(d_out, ops, n * sizeof(rv_op), hipMemcpyDeviceToDevice, st));
-    CDCHK(hipMemcpyAsync(&digest, p->block + SUMS_AT, 8, hipMemcpyDeviceToHost, st));
+    CDCHK(stage_fetch_digest(*p, &digest));
     CDCHK(hipMemcpyAsync(bounds, d_bounds, 8, hipMemcpyDeviceToHost, st));
     CDCHK(hipStreamSynchronize(st));
     if (bounds[0] > bounds[1] || bounds[1] > p->log_n) return RV_E_DEVICE;
@@ -420,31 +372,6 @@ int replay_impl(WinFolder* p, const DevAlloc& CA, const rv_op* ops, size_t n, ui
 }
 #undef CDCHK
 #undef CDNEED
-
-// one call's work memory, counted into peak_feed.  (No exception leaves a call: host memory that cannot be had is RV_E_NOMEM, and
-// `settled` closes the object as after any other one.)
-template <class Fn>
-int counted(WinFolder* p, size_t upload_bytes, Fn&& fn) {
-    size_t peak = 0;
-    int rc;
-    try {
-        rc = counted_call(p->A, &peak, fn);
-    } catch (...) {
-        (void)hipStreamSynchronize(p->st);
-        rc = RV_E_NOMEM;
-    }
-    p->peak_feed = std::max(p->peak_feed, peak + upload_bytes);
-    return rc;
-}
-
-// a device or memory error in the middle of a call leaves the carried state half moved: only destroy is accepted afterwards
-int settled(WinFolder* p, int rc) {
-    if (rc == RV_E_NOMEM || rc == RV_E_DEVICE) {
-        (void)hipStreamSynchronize(p->st);
-        p->phase = Phase::FAILED;
-    }
-    return rc;
-}
 
 // every entry of both tables: nothing written yet
 int clear_tables(WinFolder* p) {
@@ -467,14 +394,12 @@ void begin_pass(WinFolder* p) {
 }  // namespace
 
 int winfold_begin(hipStream_t st, const DevAlloc& A, uint64_t z64_wires, uint64_t gf2_wires, bool keep_log, WinFolder** out) {
-    if (z64_wires >= (1ull << 31) || gf2_wires >= (1ull << 31)) return RV_E_UNSUPPORTED;
+    if (!stage_wires_ok(z64_wires, gf2_wires)) return RV_E_UNSUPPORTED;
     WinFolder* p = new WinFolder;
-    p->st = st, p->A = A, p->keep_log = keep_log;
+    p->keep_log = keep_log;
     p->W0[PR_G] = gf2_wires, p->W0[PR_Z] = z64_wires;
     begin_pass(p);
-    p->block = (uint8_t*)p->take(BLOCK_BYTES);
-    int rc = p->block ? RV_OK : RV_E_NOMEM;
-    if (rc == RV_OK && (hipMemsetAsync(p->block, 0, BLOCK_BYTES, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) rc = RV_E_DEVICE;
+    int rc = stage_open(*p, st, A);
     if (rc == RV_OK) rc = grow_tables(p, p->W0);
     if (rc != RV_OK) {
         (void)hipGetLastError();
@@ -487,29 +412,26 @@ int winfold_begin(hipStream_t st, const DevAlloc& A, uint64_t z64_wires, uint64_
 
 int winfold_admit(WinFolder* p, int pass, size_t n, uint64_t first) {
     if (pass == 0) {
-        if (p->phase != Phase::FEED) return RV_E_ARG;
+        if (!p->at(Phase::FEED)) return RV_E_ARG;
         if (!p->first_pass) return n > p->total - p->pos ? RV_E_ARG : RV_OK;
-        if (n >= (1ull << 31) || p->pos + n >= (1ull << 31)) {
-            p->phase = Phase::FAILED;
-            return RV_E_UNSUPPORTED;
-        }
-        return RV_OK;
+        return stage_admit_first(*p, n);
     }
-    if (p->phase != Phase::ENDED || !p->keep_log) return RV_E_ARG;
+    if (!p->at(Phase::ENDED) || !p->keep_log) return RV_E_ARG;
     return (first > p->total || n > p->total - first) ? RV_E_ARG : RV_OK;
 }
 
 int winfold_feed(WinFolder* p, const rv_op* d_ops, size_t n, size_t upload_bytes, rv_op* d_out) {
     if (int rc = winfold_admit(p, 0, n, 0)) return rc;
     if (n)
-        if (int rc = settled(p, counted(p, upload_bytes, [&](const DevAlloc& CA) { return feed_impl(p, CA, d_ops, n, d_out); }))) return rc;
-    if (!p->first_pass && p->pos == p->total && p->digest != p->digest0) return RV_E_ARG;  // (the pass was not the first pass's list)
+        if (int rc = stage_settled(*p, stage_counted(*p, upload_bytes, [&](const DevAlloc& CA) { return feed_impl(p, CA, d_ops, n, d_out); })))
+            return rc;
+    if (!p->first_pass && p->pos == p->total && !stage_pass_done(*p)) return RV_E_ARG;  // (the pass was not the first pass's list)
     return RV_OK;
 }
 
 int winfold_end(WinFolder* p, rv_fold_info* info) {
-    if (p->phase != Phase::FEED) return RV_E_ARG;
-    if (!p->first_pass && (p->pos != p->total || p->digest != p->digest0)) return RV_E_ARG;
+    if (!p->at(Phase::FEED)) return RV_E_ARG;
+    if (!p->first_pass && !stage_pass_done(*p)) return RV_E_ARG;
     if (p->first_pass) p->total = p->pos, p->digest0 = p->digest, p->first_pass = false;
     if (info) {
         *info = rv_fold_info{};
@@ -525,8 +447,8 @@ int winfold_end(WinFolder* p, rv_fold_info* info) {
 }
 
 int winfold_rewind(WinFolder* p) {
-    if (p->phase != Phase::ENDED) return RV_E_ARG;
-    if (const int rc = settled(p, clear_tables(p))) return rc;
+    if (!p->at(Phase::ENDED)) return RV_E_ARG;
+    if (const int rc = stage_settled(*p, clear_tables(p))) return rc;
     begin_pass(p);
     p->phase = Phase::FEED;
     return RV_OK;
@@ -535,11 +457,11 @@ int winfold_rewind(WinFolder* p) {
 int winfold_replay(WinFolder* p, const rv_op* d_ops, size_t n, size_t upload_bytes, uint64_t first, rv_op* d_out) {
     if (int rc = winfold_admit(p, 1, n, first)) return rc;
     if (!n) return RV_OK;
-    return settled(p, counted(p, upload_bytes, [&](const DevAlloc& CA) { return replay_impl(p, CA, d_ops, n, first, d_out); }));
+    return stage_settled(*p, stage_counted(*p, upload_bytes, [&](const DevAlloc& CA) { return replay_impl(p, CA, d_ops, n, first, d_out); }));
 }
 
 int winfold_replay_end(WinFolder* p) {
-    if (p->phase != Phase::ENDED || !p->keep_log) return RV_E_ARG;
+    if (!p->at(Phase::ENDED) || !p->keep_log) return RV_E_ARG;
     std::vector<std::pair<uint64_t, uint64_t>> r;
     r.swap(p->replayed);  // (the next round begins here, whatever this one was)
     const uint64_t digest = p->replay_digest;
@@ -554,10 +476,10 @@ int winfold_replay_end(WinFolder* p) {
 }
 
 int winfold_info(const WinFolder* p, rv_folder_info* info) {
-    if (p->phase == Phase::FAILED) return RV_E_ARG;
+    if (p->failed) return RV_E_ARG;
     *info = rv_folder_info{};
     info->total_ops = p->first_pass ? p->pos : p->total;
-    info->state_bytes = BLOCK_BYTES + 9 * (p->cap[PR_G] + p->cap[PR_Z]);
+    info->state_bytes = WIN_BLOCK_BYTES + 9 * (p->cap[PR_G] + p->cap[PR_Z]);
     info->log_bytes = p->log_cap * (4 + sizeof(rv_op));
     info->log_records = p->log_n;
     info->peak_feed_bytes = p->peak_feed;
@@ -568,9 +490,9 @@ int winfold_info(const WinFolder* p, rv_folder_info* info) {
 
 void winfold_destroy(WinFolder* p) {
     if (!p) return;
-    (void)hipStreamSynchronize(p->st);
+    stage_close(*p);
     for (int d = 0; d < 2; d++) p->give(p->K[d]), p->give(p->V[d]);
-    p->give(p->log_ord), p->give(p->log_rec), p->give(p->block);
+    p->give(p->log_ord), p->give(p->log_rec);
     delete p;
 }
 

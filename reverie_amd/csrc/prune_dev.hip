@@ -34,6 +34,8 @@
 #include <atomic>
 #include <vector>
 
+#include "win_stage.h"
+
 namespace rv {
 namespace {
 #include "compile_dev_prims.inc"
@@ -101,38 +103,16 @@ int prune_impl(hipStream_t st, const DevAlloc& A, const rv_op* ops, size_t n, ui
     std::vector<uint32_t> h(S_WORDS);
 
     // step 1 (the hints and their scans borrow the first sort's buffers)
-    CDCHK(hipMemsetAsync(state, 0, S_WORDS * 4, st));
-    CDCHK(hipMemsetAsync(state, 0xFF, 8, st));
-    k_pr_hints<<<gb, TB, 0, st>>>(ops, n, kbuf[0][0], kbuf[0][1]);
-    CDCHK((scan_excl<uint32_t, MaxU32>(S, st, kbuf[0][0], vbuf[0][0], n, &state[S_HINT_Z])));
-    CDCHK((scan_excl<uint32_t, MaxU32>(S, st, kbuf[0][1], vbuf[0][1], n, &state[S_HINT_G])));
-    k_pr_classify<<<gb, TB, 0, st>>>(ops, n, z64_wires, gf2_wires, vbuf[0][0], vbuf[0][1], state);
-    CDCHK(hipGetLastError());
-    CDCHK(fetch(st, h, state));
-    CDCHK(hipStreamSynchronize(st));
-    if (h[S_ERR_HI] != 0xFFFFFFFFu || h[S_ERR_LO] != 0xFFFFFFFFu) return (int)(h[S_ERR_LO] & 0xFFu);
-    const uint64_t W[2] = {std::max<uint64_t>(gf2_wires, h[S_HINT_G]), std::max<uint64_t>(z64_wires, h[S_HINT_Z])};
-    if (W[PR_G] >= (1ull << 31) || W[PR_Z] >= (1ull << 31)) return RV_E_UNSUPPORTED;
+    const uint64_t stated[2] = {gf2_wires, z64_wires};
+    uint64_t W[2];
+    if (const int rc = pr_step1(S, st, ops, n, state, S_WORDS, stated, kbuf[0], vbuf[0], nullptr, h, W)) return rc;
     for (int d = 0; d < 2; d++)
         for (size_t k = 0; k < n_outs[d]; k++)
             if (outs[d][k] >= W[d]) return RV_E_ARG;
 
     // step 2
-    Writers w = {};
-    int set = 0;  // the buffers the next sort takes
-    for (int d = 0; d < 2; d++) {
-        w.nd[d] = h[S_DEF_G + d];
-        if (!w.nd[d]) continue;  // (every read of the domain finds no value: the search looks at no pair)
-        if (set == 1) {
-            for (int k = 0; k < 2; k++) kbuf[1][k] = S.get<uint32_t>(n), vbuf[1][k] = S.get<uint32_t>(n);
-            CDNEED(kbuf[1][0] && kbuf[1][1] && vbuf[1][0] && vbuf[1][1]);
-        }
-        k_pr_keys<<<gb, TB, 0, st>>>(ops, n, d, (uint32_t)W[d], kbuf[set][0], vbuf[set][0]);
-        int which = 0;
-        CDCHK(radix_sort(S, st, kbuf[set], vbuf[set], n, bit_len(W[d]), &which));
-        w.sk[d] = kbuf[set][which], w.sv[d] = vbuf[set][which];
-        set++;
-    }
+    Writers w;
+    if (const int rc = pr_step2(S, st, ops, n, W, h, kbuf, vbuf, &w)) return rc;
 
     // step 3
     uint32_t *cnt = S.get<uint32_t>(n), *keep = S.get<uint32_t>(n), *queue = S.get<uint32_t>(n);

@@ -1,7 +1,9 @@
 // The pruning kernels that the whole-list call (prune_dev.hip) and the windowed one (prune_win.hip) both launch: steps 1 - 4 of
 // DESIGN §23.3 and the emit.  #included inside an anonymous namespace of namespace rv, behind compile_dev_prims.inc (TB, the scans,
-// the sort) and prune.h, as compile_dev_prims.inc itself is shared: one text, a copy of the code per translation unit.  Every
-// per-record decision is prune.h's.  One thread per op where the step allows it; plain vector atomics and stores only.
+// the sort), prune.h and win_stage.h (step 1 joins a windowed stage's digest), as compile_dev_prims.inc itself is shared: one text, a
+// copy of the code per translation unit.  Every per-record decision is prune.h's.  One thread per op where the step allows it; plain
+// vector atomics and stores only.  Steps 1 and 2 have their host halves here too (pr_step1, pr_step2): prune_dev.hip, fold_dev.hip,
+// prune_win.hip and fold_win.hip all begin with them.
 
 // the words of one call (the windowed form: of one feed) in device memory
 enum { S_ERR_LO, S_ERR_HI, S_HINT_Z, S_HINT_G, S_DEF_G, S_DEF_Z, S_Q_LO, S_Q_HI, S_Q_TAIL, S_ROUNDS, S_WIDE_DONE, S_CLS, S_WORDS = S_CLS + PR_CLASSES };
@@ -13,13 +15,7 @@ struct Writers {
 };
 
 // ---- step 1 ----
-__global__ __launch_bounds__(TB) void k_pr_hints(const rv_op* ops, size_t n, uint32_t* hz, uint32_t* hg) {
-    const size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
-    if (i >= n) return;
-    const bool h = ops[i].domain == RV_DOM_SIZEHINT;
-    hz[i] = h ? ops[i].a : 0u;
-    hg[i] = h ? ops[i].b : 0u;
-}
+// (k_pr_hints is compile_dev_prims.inc's: the compactors launch it too)
 __global__ __launch_bounds__(TB) void k_pr_classify(const rv_op* ops, size_t n, uint64_t decl_z, uint64_t decl_g, const uint32_t* cz, const uint32_t* cg,
                                                     uint32_t* state) {
     __shared__ uint32_t cnt[2];
@@ -49,6 +45,58 @@ __global__ __launch_bounds__(TB) void k_pr_keys(const rv_op* ops, size_t n, int 
     const rv_op op = ops[i];
     key[i] = pr_def(op) == d ? op.dst : W;
     idx[i] = (uint32_t)i;
+}
+
+// ---- steps 1 and 2 on the host (S: the call's Scratch; the caller took `state` and the buffers from it) ----
+// Step 1 of ops [0, n) on `st`, with `in` ([PR_G], [PR_Z]) the counts in force before ops[0]: the n_words words of `state` cleared,
+// the hints (hint[0], hint[1]: Z64, GF(2)), their exclusive max-scans (into scan[0], scan[1]), the classify kernel, the words fetched
+// into h.  hint == nullptr: the ops are judged against `in` alone -- no hint of theirs raises a count; scan[0] is zeroed and stands
+// for both scans.  win: the feed of a windowed stage, whose digest the ops join (win->sum: their sum); nullptr: a whole list.
+// -> RV_OK and W = the counts in force behind the last op; the lowest bad op's code; RV_E_UNSUPPORTED for a count of 2^31; or
+// RV_E_NOMEM / RV_E_DEVICE.  The stream is idle afterwards.
+int pr_step1(Scratch& S, hipStream_t st, const rv_op* ops, size_t n, uint32_t* state, size_t n_words, const uint64_t in[2], uint32_t* const* hint,
+             uint32_t* const scan[2], WinFeed* win, std::vector<uint32_t>& h, uint64_t W[2]) {
+    const uint32_t gb = blocks(n, TB);
+    CDCHK(hipMemsetAsync(state, 0, n_words * 4, st));
+    CDCHK(hipMemsetAsync(state, 0xFF, 8, st));
+    if (win) CDCHK(stage_digest(win->stage, ops, n, win->first));
+    if (hint) {
+        k_pr_hints<<<gb, TB, 0, st>>>(ops, n, hint[0], hint[1]);
+        CDCHK((scan_excl<uint32_t, MaxU32>(S, st, hint[0], scan[0], n, &state[S_HINT_Z])));
+        CDCHK((scan_excl<uint32_t, MaxU32>(S, st, hint[1], scan[1], n, &state[S_HINT_G])));
+    } else {
+        CDCHK(hipMemsetAsync(scan[0], 0, n * 4, st));
+    }
+    k_pr_classify<<<gb, TB, 0, st>>>(ops, n, in[PR_Z], in[PR_G], scan[0], scan[hint ? 1 : 0], state);
+    CDCHK(hipGetLastError());
+    CDCHK(fetch(st, h, state));
+    if (win) CDCHK(stage_fetch_digest(win->stage, &win->sum));
+    CDCHK(hipStreamSynchronize(st));
+    if (h[S_ERR_HI] != 0xFFFFFFFFu || h[S_ERR_LO] != 0xFFFFFFFFu) return (int)(h[S_ERR_LO] & 0xFFu);
+    W[PR_G] = std::max<uint64_t>(in[PR_G], h[S_HINT_G]), W[PR_Z] = std::max<uint64_t>(in[PR_Z], h[S_HINT_Z]);
+    return (W[PR_G] >= (1ull << 31) || W[PR_Z] >= (1ull << 31)) ? RV_E_UNSUPPORTED : RV_OK;
+}
+// Step 2: per domain with a defining op (h: step 1's words) the keys and the sort, into w.  kbuf[0], vbuf[0]: the caller's first
+// set of buffers (step 1 may have borrowed them); the second set is taken from S only when both domains define.
+int pr_step2(Scratch& S, hipStream_t st, const rv_op* ops, size_t n, const uint64_t W[2], const std::vector<uint32_t>& h, uint32_t* kbuf[2][2],
+             uint32_t* vbuf[2][2], Writers* w) {
+    const uint32_t gb = blocks(n, TB);
+    *w = Writers{};
+    int set = 0;  // the buffers the next sort takes
+    for (int d = 0; d < 2; d++) {
+        w->nd[d] = h[S_DEF_G + d];
+        if (!w->nd[d]) continue;  // (every read of the domain finds no value: the search looks at no pair)
+        if (set == 1) {
+            for (int k = 0; k < 2; k++) kbuf[1][k] = S.get<uint32_t>(n), vbuf[1][k] = S.get<uint32_t>(n);
+            CDNEED(kbuf[1][0] && kbuf[1][1] && vbuf[1][0] && vbuf[1][1]);
+        }
+        k_pr_keys<<<gb, TB, 0, st>>>(ops, n, d, (uint32_t)W[d], kbuf[set][0], vbuf[set][0]);
+        int which = 0;
+        CDCHK(radix_sort(S, st, kbuf[set], vbuf[set], n, bit_len(W[d]), &which));
+        w->sk[d] = kbuf[set][which], w->sv[d] = vbuf[set][which];
+        set++;
+    }
+    return RV_OK;
 }
 
 // ---- step 3 ----

@@ -32,17 +32,14 @@
 #include <algorithm>
 #include <vector>
 
-#include "dev_counting.h"
-#include "piece_sums.h"
 #include "prune_dev.h"
+#include "win_stage.h"
 
 namespace rv {
 namespace {
 #include "compile_dev_prims.inc"
 static_assert(TB == (int)PRUNE_WG && TB == (int)PRUNE_TILE, "the kernels of prune_dev_kernels.inc are launched with TB threads");
 #include "prune_dev_kernels.inc"
-
-constexpr size_t BLOCK_BYTES = 1024, CUT_AT = 256, SUMS_AT = 512;  // the resident block: the digest's cut pair, its sums
 
 // ---- scan_end: the needed bytes of the output indices ----
 __global__ __launch_bounds__(TB) void k_pw_outputs(const uint32_t* outs, size_t n_outs, uint8_t* N, uint64_t W) {
@@ -86,77 +83,39 @@ __global__ __launch_bounds__(TB) void k_pw_marks_in(const uint8_t* marks, size_t
 
 }  // namespace
 
-enum class Phase { SCAN, MARK, FEED, FAILED };
+enum class Phase { SCAN, MARK, FEED };
 
-struct WinPruner {
-    hipStream_t st;
-    DevAlloc A;
+struct WinPruner : WinStage {
     Phase phase = Phase::SCAN;
     uint64_t W[2] = {0, 0};  // counts in force ([PR_G], [PR_Z]); final from scan_end on
     std::vector<uint32_t> outs[2];
     uint8_t* need[2] = {nullptr, nullptr};  // W[d] bytes
     uint8_t* marks = nullptr;               // total bytes
-    uint8_t* block = nullptr;               // BLOCK_BYTES
-    uint64_t pos = 0, total = 0, digest = 0, digest0 = 0, cut_h[2] = {0, 0};
     uint64_t n_kept = 0, cls[PR_CLASSES] = {}, rounds = 0, mark_feeds = 0, host_feeds = 0;
-    size_t peak_feed = 0;
 
-    size_t state_bytes() const { return BLOCK_BYTES + (need[PR_G] ? (size_t)W[PR_G] : 0) + (need[PR_Z] ? (size_t)W[PR_Z] : 0) + (marks ? (size_t)total : 0); }
-    void* take(size_t bytes) {
-        void* p = nullptr;
-        return A.alloc(A.self, std::max<size_t>(bytes, 4), &p) == RV_OK ? p : nullptr;
-    }
-    void give(void* p) {
-        if (p) A.release(A.self, p);
+    bool at(Phase ph) const { return !failed && phase == ph; }
+    size_t state_bytes() const {
+        return WIN_BLOCK_BYTES + (need[PR_G] ? (size_t)W[PR_G] : 0) + (need[PR_Z] ? (size_t)W[PR_Z] : 0) + (marks ? (size_t)total : 0);
     }
 };
 
 namespace {
 
-// the feed's digest sum goes to the block (ops [0, n) of d_ops at the ordinals first ..)
-hipError_t launch_digest(WinPruner* p, const rv_op* d_ops, size_t n, uint64_t first) {
-    p->cut_h[0] = 0, p->cut_h[1] = n;  // (the pruner's own words: they outlive the copy)
-    hipError_t e = hipMemcpyAsync(p->block + CUT_AT, p->cut_h, 16, hipMemcpyHostToDevice, p->st);
-    if (e != hipSuccess) return e;
-    launch_piece_sums(p->st, d_ops, (const uint64_t*)(p->block + CUT_AT), 1, n, first, (PieceSums*)(p->block + SUMS_AT));
-    return hipGetLastError();
-}
-hipError_t begin_words(hipStream_t st, uint32_t* state) {
-    hipError_t e = hipMemsetAsync(state, 0, S_WORDS * 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(state, 0xFF, 8, st);
-    return e;
-}
-
 int scan_impl(WinPruner* p, const DevAlloc& CA, const rv_op* ops, size_t n) {
     hipStream_t st = p->st;
     Scratch S(CA, st);
-    const uint32_t gb = blocks(n, TB);
     uint32_t* state = S.get<uint32_t>(S_WORDS);
-    uint32_t *hz = S.get<uint32_t>(n), *hg = S.get<uint32_t>(n), *cz = S.get<uint32_t>(n), *cg = S.get<uint32_t>(n);
-    CDNEED(state && hz && hg && cz && cg);
+    uint32_t *hint[2] = {S.get<uint32_t>(n), S.get<uint32_t>(n)}, *scan[2] = {S.get<uint32_t>(n), S.get<uint32_t>(n)};
+    CDNEED(state && hint[0] && hint[1] && scan[0] && scan[1]);
     std::vector<uint32_t> h(S_WORDS);
-    uint64_t digest = 0;
-    CDCHK(begin_words(st, state));
-    CDCHK(launch_digest(p, ops, n, p->pos));
-    k_pr_hints<<<gb, TB, 0, st>>>(ops, n, hz, hg);
-    CDCHK((scan_excl<uint32_t, MaxU32>(S, st, hz, cz, n, &state[S_HINT_Z])));
-    CDCHK((scan_excl<uint32_t, MaxU32>(S, st, hg, cg, n, &state[S_HINT_G])));
-    k_pr_classify<<<gb, TB, 0, st>>>(ops, n, p->W[PR_Z], p->W[PR_G], cz, cg, state);
-    CDCHK(hipGetLastError());
-    CDCHK(fetch(st, h, state));
-    CDCHK(hipMemcpyAsync(&digest, p->block + SUMS_AT, 8, hipMemcpyDeviceToHost, st));
-    CDCHK(hipStreamSynchronize(st));
-    if (h[S_ERR_HI] != 0xFFFFFFFFu || h[S_ERR_LO] != 0xFFFFFFFFu) {
-        p->phase = Phase::FAILED;
-        return (int)(h[S_ERR_LO] & 0xFFu);
+    uint64_t W[2];
+    WinFeed feed = {*p, p->pos};
+    if (const int rc = pr_step1(S, st, ops, n, state, S_WORDS, p->W, hint, scan, &feed, h, W)) {
+        p->failed = true;
+        return rc;
     }
-    const uint64_t wg = std::max<uint64_t>(p->W[PR_G], h[S_HINT_G]), wz = std::max<uint64_t>(p->W[PR_Z], h[S_HINT_Z]);
-    if (wg >= (1ull << 31) || wz >= (1ull << 31)) {
-        p->phase = Phase::FAILED;
-        return RV_E_UNSUPPORTED;
-    }
-    p->W[PR_G] = wg, p->W[PR_Z] = wz;
-    p->digest += digest;
+    p->W[PR_G] = W[PR_G], p->W[PR_Z] = W[PR_Z];
+    p->digest += feed.sum;
     p->pos += n;
     return RV_OK;
 }
@@ -166,7 +125,7 @@ int scan_end_impl(WinPruner* p, const DevAlloc& CA) {
     for (int d = 0; d < 2; d++)
         for (uint32_t w : p->outs[d])
             if (w >= p->W[d]) {
-                p->phase = Phase::FAILED;
+                p->failed = true;
                 return RV_E_ARG;
             }
     Scratch S(CA, st);
@@ -229,35 +188,16 @@ int mark_impl(WinPruner* p, const DevAlloc& CA, const rv_op* ops, size_t n, size
     for (int k = 0; k < 2; k++) kbuf[0][k] = S.get<uint32_t>(n), vbuf[0][k] = S.get<uint32_t>(n);
     CDNEED(state && kbuf[0][0] && kbuf[0][1] && vbuf[0][0] && vbuf[0][1]);
     std::vector<uint32_t> h(S_WORDS);
-    uint64_t digest = 0;
+    uint64_t W[2];
+    WinFeed feed = {*p, first};
 
-    // every record against the final counts (no hint of the feed can raise them: the zeroed words stand for its hints)
-    CDCHK(begin_words(st, state));
-    CDCHK(launch_digest(p, ops, n, first));
-    CDCHK(hipMemsetAsync(kbuf[0][0], 0, n * 4, st));
-    k_pr_classify<<<gb, TB, 0, st>>>(ops, n, p->W[PR_Z], p->W[PR_G], kbuf[0][0], kbuf[0][0], state);
-    CDCHK(hipGetLastError());
-    CDCHK(fetch(st, h, state));
-    CDCHK(hipMemcpyAsync(&digest, p->block + SUMS_AT, 8, hipMemcpyDeviceToHost, st));
-    CDCHK(hipStreamSynchronize(st));
-    if (h[S_ERR_HI] != 0xFFFFFFFFu || h[S_ERR_LO] != 0xFFFFFFFFu) return RV_E_ARG;  // (not the scanned list; nothing was addressed)
+    // every record against the final counts (no hint of the feed can raise them)
+    if (const int rc = pr_step1(S, st, ops, n, state, S_WORDS, p->W, nullptr, kbuf[0], &feed, h, W))
+        return (rc == RV_E_NOMEM || rc == RV_E_DEVICE) ? rc : RV_E_ARG;  // (not the scanned list; nothing was addressed)
 
     // step 2
-    Writers w = {};
-    int set = 0;  // the buffers the next sort takes
-    for (int d = 0; d < 2; d++) {
-        w.nd[d] = h[S_DEF_G + d];
-        if (!w.nd[d]) continue;
-        if (set == 1) {
-            for (int k = 0; k < 2; k++) kbuf[1][k] = S.get<uint32_t>(n), vbuf[1][k] = S.get<uint32_t>(n);
-            CDNEED(kbuf[1][0] && kbuf[1][1] && vbuf[1][0] && vbuf[1][1]);
-        }
-        k_pr_keys<<<gb, TB, 0, st>>>(ops, n, d, (uint32_t)p->W[d], kbuf[set][0], vbuf[set][0]);
-        int which = 0;
-        CDCHK(radix_sort(S, st, kbuf[set], vbuf[set], n, bit_len(p->W[d]), &which));
-        w.sk[d] = kbuf[set][which], w.sv[d] = vbuf[set][which];
-        set++;
-    }
+    Writers w;
+    if (const int rc = pr_step2(S, st, ops, n, p->W, h, kbuf, vbuf, &w)) return rc;
 
     // step 3, and the live-out
     uint32_t *cnt = S.get<uint32_t>(n), *keep = S.get<uint32_t>(n), *queue = S.get<uint32_t>(n);
@@ -294,7 +234,7 @@ int mark_impl(WinPruner* p, const DevAlloc& CA, const rv_op* ops, size_t n, size
     p->rounds += h[S_ROUNDS];
     p->n_kept += kept;
     p->mark_feeds++;
-    p->digest += digest;
+    p->digest += feed.sum;
     p->pos = first;
     if (n_kept_here) *n_kept_here = (size_t)kept;
     return RV_OK;
@@ -309,12 +249,13 @@ int feed_impl(WinPruner* p, const DevAlloc& CA, const rv_op* ops, size_t n, rv_o
     CDNEED(state && keep && at);
     std::vector<uint32_t> h(S_WORDS);
     uint64_t digest = 0;
-    CDCHK(begin_words(st, state));
-    CDCHK(launch_digest(p, ops, n, p->pos));
+    CDCHK(hipMemsetAsync(state, 0, S_WORDS * 4, st));
+    CDCHK(hipMemsetAsync(state, 0xFF, 8, st));
+    CDCHK(stage_digest(*p, ops, n, p->pos));
     k_pw_marks_in<<<gb, TB, 0, st>>>(p->marks + p->pos, n, keep);
     CDCHK((scan_excl<uint32_t, SumU32>(S, st, keep, at, n, &state[S_Q_TAIL])));  // (the word the kept count comes back in)
     CDCHK(fetch(st, h, state));
-    CDCHK(hipMemcpyAsync(&digest, p->block + SUMS_AT, 8, hipMemcpyDeviceToHost, st));
+    CDCHK(stage_fetch_digest(*p, &digest));
     CDCHK(hipStreamSynchronize(st));
     const size_t kept = h[S_Q_TAIL];
     if (cap < kept) return RV_E_ARG;  // (nothing written, nothing moved)
@@ -330,44 +271,15 @@ int feed_impl(WinPruner* p, const DevAlloc& CA, const rv_op* ops, size_t n, rv_o
 #undef CDCHK
 #undef CDNEED
 
-// one call's work memory, counted into peak_feed.  (No exception leaves a call: host memory that cannot be had -- the fall-back's
-// copies, the counting table -- is RV_E_NOMEM, and `settled` closes the object as after any other one.)
-template <class Fn>
-int counted(WinPruner* p, size_t upload_bytes, Fn&& fn) {
-    size_t peak = 0;
-    int rc;
-    try {
-        rc = counted_call(p->A, &peak, fn);
-    } catch (...) {
-        (void)hipStreamSynchronize(p->st);
-        rc = RV_E_NOMEM;
-    }
-    p->peak_feed = std::max(p->peak_feed, peak + upload_bytes);
-    return rc;
-}
-
-// a device or memory error in the middle of a call leaves the carried state half moved: only destroy is accepted afterwards
-int settled(WinPruner* p, int rc) {
-    if (rc == RV_E_NOMEM || rc == RV_E_DEVICE) {
-        (void)hipStreamSynchronize(p->st);
-        p->phase = Phase::FAILED;
-    }
-    return rc;
-}
-
 }  // namespace
 
 int winprune_begin(hipStream_t st, const DevAlloc& A, uint64_t z64_wires, uint64_t gf2_wires, const uint32_t* const outs[2], const size_t n_outs[2],
                    WinPruner** out) {
-    if (z64_wires >= (1ull << 31) || gf2_wires >= (1ull << 31)) return RV_E_UNSUPPORTED;
+    if (!stage_wires_ok(z64_wires, gf2_wires)) return RV_E_UNSUPPORTED;
     WinPruner* p = new WinPruner;
-    p->st = st, p->A = A;
     p->W[PR_G] = gf2_wires, p->W[PR_Z] = z64_wires;
     for (int d = 0; d < 2; d++) p->outs[d].assign(outs[d], outs[d] + n_outs[d]);
-    p->block = (uint8_t*)p->take(BLOCK_BYTES);
-    int rc = p->block ? RV_OK : RV_E_NOMEM;
-    if (rc == RV_OK && (hipMemsetAsync(p->block, 0, BLOCK_BYTES, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) rc = RV_E_DEVICE;
-    if (rc != RV_OK) {
+    if (const int rc = stage_open(*p, st, A)) {
         winprune_destroy(p);
         return rc;
     }
@@ -376,14 +288,8 @@ int winprune_begin(hipStream_t st, const DevAlloc& A, uint64_t z64_wires, uint64
 }
 
 int winprune_admit(WinPruner* p, int pass, size_t n) {
-    if (p->phase != (pass == 0 ? Phase::SCAN : pass == 1 ? Phase::MARK : Phase::FEED)) return RV_E_ARG;
-    if (pass == 0) {
-        if (n >= (1ull << 31) || p->pos + n >= (1ull << 31)) {
-            p->phase = Phase::FAILED;
-            return RV_E_UNSUPPORTED;
-        }
-        return RV_OK;
-    }
+    if (!p->at(pass == 0 ? Phase::SCAN : pass == 1 ? Phase::MARK : Phase::FEED)) return RV_E_ARG;
+    if (pass == 0) return stage_admit_first(*p, n);
     if (pass == 1) return n > p->pos ? RV_E_ARG : RV_OK;
     return n > p->total - p->pos ? RV_E_ARG : RV_OK;
 }
@@ -391,23 +297,23 @@ int winprune_admit(WinPruner* p, int pass, size_t n) {
 int winprune_scan(WinPruner* p, const rv_op* d_ops, size_t n, size_t upload_bytes) {
     if (int rc = winprune_admit(p, 0, n)) return rc;
     if (!n) return RV_OK;
-    return settled(p, counted(p, upload_bytes, [&](const DevAlloc& CA) { return scan_impl(p, CA, d_ops, n); }));
+    return stage_settled(*p, stage_counted(*p, upload_bytes, [&](const DevAlloc& CA) { return scan_impl(p, CA, d_ops, n); }));
 }
 
 int winprune_scan_end(WinPruner* p) {
-    if (p->phase != Phase::SCAN) return RV_E_ARG;
-    return settled(p, counted(p, 0, [&](const DevAlloc& CA) { return scan_end_impl(p, CA); }));
+    if (!p->at(Phase::SCAN)) return RV_E_ARG;
+    return stage_settled(*p, stage_counted(*p, 0, [&](const DevAlloc& CA) { return scan_end_impl(p, CA); }));
 }
 
 int winprune_mark(WinPruner* p, const rv_op* d_ops, size_t n, size_t upload_bytes, size_t* n_kept_here) {
     if (int rc = winprune_admit(p, 1, n)) return rc;
     if (n_kept_here) *n_kept_here = 0;
     if (!n) return RV_OK;
-    return settled(p, counted(p, upload_bytes, [&](const DevAlloc& CA) { return mark_impl(p, CA, d_ops, n, n_kept_here); }));
+    return stage_settled(*p, stage_counted(*p, upload_bytes, [&](const DevAlloc& CA) { return mark_impl(p, CA, d_ops, n, n_kept_here); }));
 }
 
 int winprune_mark_end(WinPruner* p, rv_prune_info* info) {
-    if (p->phase != Phase::MARK || p->pos != 0 || p->digest != p->digest0) return RV_E_ARG;
+    if (!p->at(Phase::MARK) || p->pos != 0 || p->digest != p->digest0) return RV_E_ARG;
     if (info) {
         *info = rv_prune_info{};
         info->n_kept = p->n_kept, info->n_dropped = p->total - p->n_kept;
@@ -424,20 +330,22 @@ int winprune_feed(WinPruner* p, const rv_op* d_ops, size_t n, size_t upload_byte
     if (int rc = winprune_admit(p, 2, n)) return rc;
     if (n_out) *n_out = 0;
     if (n)
-        if (int rc = settled(p, counted(p, upload_bytes, [&](const DevAlloc& CA) { return feed_impl(p, CA, d_ops, n, d_out, cap, n_out, d_old_index); })))
+        if (int rc = stage_settled(*p, stage_counted(*p, upload_bytes, [&](const DevAlloc& CA) {
+                return feed_impl(p, CA, d_ops, n, d_out, cap, n_out, d_old_index);
+            })))
             return rc;
-    if (p->pos == p->total && p->digest != p->digest0) return RV_E_ARG;  // (the pass was not the scanned list)
+    if (p->pos == p->total && !stage_pass_done(*p)) return RV_E_ARG;  // (the pass was not the scanned list)
     return RV_OK;
 }
 
 int winprune_rewind(WinPruner* p) {
-    if (p->phase != Phase::FEED || p->pos != p->total) return RV_E_ARG;
+    if (!p->at(Phase::FEED) || p->pos != p->total) return RV_E_ARG;
     p->pos = 0, p->digest = 0;
     return RV_OK;
 }
 
 int winprune_info(const WinPruner* p, rv_pruner_info* info) {
-    if (p->phase == Phase::FAILED) return RV_E_ARG;
+    if (p->failed) return RV_E_ARG;
     *info = rv_pruner_info{};
     info->total_ops = p->phase == Phase::SCAN ? p->pos : p->total;
     info->n_kept = p->n_kept;
@@ -450,8 +358,8 @@ int winprune_info(const WinPruner* p, rv_pruner_info* info) {
 
 void winprune_destroy(WinPruner* p) {
     if (!p) return;
-    (void)hipStreamSynchronize(p->st);
-    p->give(p->need[PR_G]), p->give(p->need[PR_Z]), p->give(p->marks), p->give(p->block);
+    stage_close(*p);
+    p->give(p->need[PR_G]), p->give(p->need[PR_Z]), p->give(p->marks);
     delete p;
 }
 

@@ -20,12 +20,9 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _lib
+from ._window import _DeviceStage, info_dict as _info, input_counts
 from .ops import OP_DTYPE, largest_wires, program
 from .proof import Context, _device_ops, _is_device_ops, _ptr
-
-
-def _info(fi) -> dict:
-    return {n: int(getattr(fi, n)) for n, _ in fi._fields_}
 
 
 def fold_ops(ops, wire_counts: Optional[Tuple[int, int]] = None, ctx: Optional[Context] = None, inplace: bool = False, count_only: bool = False):
@@ -89,27 +86,19 @@ def fold_windows_host(ops, wire_counts: Optional[Tuple[int, int]] = None, cuts=(
 KEEP_LOG = 1  # RV_FOLDER_KEEP_LOG
 
 
-class DeviceFolder:
+class DeviceFolder(_DeviceStage):
     """rv_folder: `fold_ops` for an op list that arrives in feeds.  feed(ops)... forwards -> the folded records, feed by feed; end()
     -> rv_fold_info; rewind() folds the list again from op 0.  keep_log: every rewritten record is kept in a log on the device, and
     after end() replay(ops, first) turns ANY window of the source into the same window of the folded list, in any order;
     replay_end() closes a round that covered the whole list.  ops: an OP_DTYPE array (uploaded) or a torch GPU tensor of packed
     rv_op records.  wire_counts: (z64, gf2) as stated."""
 
+    _what, _destroy, _info_of = "DeviceFolder", "rv_folder_destroy", (_lib.FolderInfo, "rv_folder_get_info")
+
     def __init__(self, wire_counts: Tuple[int, int], ctx: Optional[Context] = None, keep_log: bool = False):
-        self.ctx = ctx or Context.default()
-        self.handle = C.c_void_p()
-        self.info = None
+        super().__init__(ctx or Context.default())
         _lib.check(_lib.lib().rv_folder_begin(self.ctx.handle, C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])),
                                               C.c_uint32(KEEP_LOG if keep_log else 0), C.byref(self.handle)))
-
-    def _ops(self, ops):
-        """-> (pointer, n_ops, on device, what keeps the memory alive)"""
-        if _is_device_ops(ops):
-            d_ops, n_ops, _ = _device_ops(ops, self.ctx, "DeviceFolder")
-            return C.c_void_p(d_ops), n_ops, 1, ops
-        a = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
-        return _ptr(a), len(a), 0, a
 
     def _out(self, n, ops, dev, inplace):
         import torch
@@ -154,44 +143,7 @@ class DeviceFolder:
 
     def get_info(self) -> dict:
         """rv_folder_info: total_ops, state_bytes, log_bytes, log_records, peak_feed_bytes, feeds, host_feeds"""
-        fi = _lib.FolderInfo()
-        _lib.check(_lib.lib().rv_folder_get_info(self.handle, C.byref(fi)))
-        return _info(fi)
-
-    def close(self) -> None:
-        """gives the folder's device memory back to its context (a context that was closed first took its memory with it: the handle
-        is dropped then, not destroyed)"""
-        if self.handle:
-            if self.ctx.handle:
-                _lib.lib().rv_folder_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        import sys
-
-        if sys.is_finalizing():  # (finalisers run in no order then: the context and the runtime may be gone; the process ends anyway)
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _input_counts(ops):
-    """the (GF(2), Z64) Input ops of a piece, as `prune.prune_pieces` counts them"""
-    if not _is_device_ops(ops):  # (counted where the records still are a host array)
-        a = program(ops)
-        inputs = a["opcode"] == 0
-        return int(np.count_nonzero(inputs & (a["domain"] == 0))), int(np.count_nonzero(inputs & (a["domain"] == 1)))
-    recs = ops.reshape(-1, OP_DTYPE.itemsize)  # (domain and opcode are a record's first two bytes)
-    inputs = recs[:, 1] == 0
-    return int((inputs & (recs[:, 0] == 0)).sum()), int((inputs & (recs[:, 0] == 1)).sum())
+        return super().get_info()
 
 
 def fold_pieces(pieces, wire_counts: Tuple[int, int], ctx: Optional[Context] = None):
@@ -235,7 +187,7 @@ def fold_pieces(pieces, wire_counts: Tuple[int, int], ctx: Optional[Context] = N
             if ops is None or len(ops) == 0:
                 continue
             if counts is None:
-                counts = _input_counts(ops)
+                counts = input_counts(ops)
             out = df.replay(ops, first)
             first += len(out)
             yield out, counts
@@ -253,7 +205,7 @@ def fold_pieces(pieces, wire_counts: Tuple[int, int], ctx: Optional[Context] = N
                 if ops is None or len(ops) == 0:
                     continue
                 if counts is None:
-                    counts = _input_counts(ops)
+                    counts = input_counts(ops)
                 n = len(ops) if not _is_device_ops(ops) else len(ops.reshape(-1, OP_DTYPE.itemsize))
                 end -= n
                 yield df.replay(ops, end), counts

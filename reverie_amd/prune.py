@@ -16,12 +16,9 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from ._window import _DeviceStage, info_dict as _info, input_counts
 from .ops import OP_DTYPE, largest_wires, program
 from .proof import Context, _device_ops, _is_device_ops, _ptr
-
-
-def _info(pi) -> dict:
-    return {n: int(getattr(pi, n)) for n, _ in pi._fields_}
 
 
 def _outputs(outputs) -> np.ndarray:
@@ -80,27 +77,19 @@ def prune_ops(ops, wire_counts: Optional[Tuple[int, int]] = None, outputs_gf2: S
 
 
 # ---- the same for a list that passes through in windows (rv_pruner_*) ----
-class DevicePruner:
+class DevicePruner(_DeviceStage):
     """rv_pruner: `prune_ops` for an op list that arrives in feeds.  scan(ops)... scan_end(); mark(ops)... with the windows from the
     LAST to the first (each window's ops in list order), mark_end() -> rv_prune_info; then feed(ops)... forwards -> the kept records,
     feed by feed; rewind() starts the emit pass again.  The three passes may be cut differently.  ops: an OP_DTYPE array (uploaded)
     or a torch GPU tensor of packed rv_op records.  wire_counts: (z64, gf2) as stated; the outputs as in `prune_ops`."""
 
+    _what, _destroy, _info_of = "DevicePruner", "rv_pruner_destroy", (_lib.PrunerInfo, "rv_pruner_get_info")
+
     def __init__(self, wire_counts: Tuple[int, int], outputs_gf2: Sequence[int] = (), outputs_z64: Sequence[int] = (), ctx: Optional[Context] = None):
-        self.ctx = ctx or Context.default()
-        self.handle = C.c_void_p()
-        self.info = None
+        super().__init__(ctx or Context.default())
         og, oz = _outputs(outputs_gf2), _outputs(outputs_z64)
         _lib.check(_lib.lib().rv_pruner_begin(self.ctx.handle, C.c_size_t(int(wire_counts[0])), C.c_size_t(int(wire_counts[1])), _ptr(og),
                                               C.c_size_t(og.size), _ptr(oz), C.c_size_t(oz.size), C.byref(self.handle)))
-
-    def _ops(self, ops):
-        """-> (pointer, n_ops, on device, what keeps the memory alive)"""
-        if _is_device_ops(ops):
-            d_ops, n_ops, _ = _device_ops(ops, self.ctx, "DevicePruner")
-            return C.c_void_p(d_ops), n_ops, 1, ops
-        a = program(ops) if len(ops) else np.zeros(0, OP_DTYPE)
-        return _ptr(a), len(a), 0, a
 
     def scan(self, ops) -> None:
         p, n, dev, _keep = self._ops(ops)
@@ -146,33 +135,7 @@ class DevicePruner:
 
     def get_info(self) -> dict:
         """rv_pruner_info: total_ops, n_kept, state_bytes, peak_feed_bytes, mark_feeds, host_feeds"""
-        pi = _lib.PrunerInfo()
-        _lib.check(_lib.lib().rv_pruner_get_info(self.handle, C.byref(pi)))
-        return _info(pi)
-
-    def close(self) -> None:
-        """gives the pruner's device memory back to its context (a context that was closed first took its memory with it: the handle
-        is dropped then, not destroyed)"""
-        if self.handle:
-            if self.ctx.handle:
-                _lib.lib().rv_pruner_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        import sys
-
-        if sys.is_finalizing():  # (finalisers run in no order then: the context and the runtime may be gone; the process ends anyway)
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
+        return super().get_info()
 
 
 def window_pieces(ops, window_ops: int):
@@ -245,14 +208,8 @@ def prune_pieces(pieces, wire_counts: Tuple[int, int], outputs_gf2: Sequence[int
         for ops, counts in pieces():
             if ops is None or len(ops) == 0:
                 continue
-            if counts is None and not _is_device_ops(ops):  # (counted where the records still are a host array)
-                a = program(ops)
-                inputs = a["opcode"] == 0
-                counts = (int(np.count_nonzero(inputs & (a["domain"] == 0))), int(np.count_nonzero(inputs & (a["domain"] == 1))))
-            elif counts is None:  # (domain and opcode are a record's first two bytes)
-                recs = ops.reshape(-1, OP_DTYPE.itemsize)
-                inputs = recs[:, 1] == 0
-                counts = (int((inputs & (recs[:, 0] == 0)).sum()), int((inputs & (recs[:, 0] == 1)).sum()))
+            if counts is None:
+                counts = input_counts(ops)
             kept, _old = dp.feed(ops)
             if len(kept):
                 yield kept, counts
